@@ -11,6 +11,7 @@ sequences: each rank owns its own sequences and KV slabs, no collective on the d
   python bench.py --gpus 1 --steps 3 --warmup 1
   python bench.py --gpus N ...            (starts its own N rank processes, one per GPU, before any GPU call)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (ranks given by the launcher)
+  python bench.py ... --dump-outputs DIR  (also writes what the last timed step returned, as DIR/<name>.npy)
 
 Inputs are resident in HBM before the timed region (weights uploaded, token ids are 4 bytes each).
 """
@@ -29,7 +30,7 @@ sys.path.insert(0, str(ROOT))
 
 import numpy as np  # noqa: E402
 
-MFMA_BF16_PEAK_TFLOPS = 2500.0   # /opt/skills/guides/MI355X_MICROARCH.md: ~2.5 PF dense bf16
+MFMA_BF16_PEAK_TFLOPS = 2500.0   # MI355X: ~2.5 PF dense bf16
 HBM_PEAK_GBS = 8000.0            # 8.0 TB/s spec (6.29 TB/s measured copy)
 
 
@@ -63,7 +64,34 @@ def parse():
     ap.add_argument("--launch-check", action="store_true",
                     help="no GPU work: every rank joins the rendezvous (gloo), passes the barrier / max-reduce and rank 0 "
                          "prints a line with n_gpus — the multi-rank control flow on a CPU-only machine")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write what the last timed step returned to its caller as DIR/<name>.npy "
+                         "(float64): prefill_next_token [B] (the argmax after each prompt) and decode_tokens [G, B] (the "
+                         "token of every decode step).  Same arguments -> same weights, prompts and uniforms, so two "
+                         "builds can be compared output for output")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be >= 1")
+    return args
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir: Path, arrays: dict, suffix: str = ""):
+    """Writes every array as float64 DIR/<name><suffix>.npy.  An array larger than its share of DUMP_LIMIT_BYTES is
+    replaced by a fixed seeded sample of its flattened elements (<name>_sample_index.npy holds the sampled indices)."""
+    out_dir.mkdir(parents=True, exist_ok=True)
+    # the directory keeps itself out of version control wherever it is created (as .pytest_cache does)
+    (out_dir / ".gitignore").write_text("*\n")
+    share = DUMP_LIMIT_BYTES // (2 * max(1, len(arrays)))      # room for the index array of a sampled one
+    for name, a in arrays.items():
+        a = np.asarray(a, np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(0).choice(a.size, share // 8, replace=False))
+            np.save(out_dir / f"{name}_sample_index{suffix}.npy", idx.astype(np.float64))
+            a = a.reshape(-1)[idx]
+        np.save(out_dir / f"{name}{suffix}.npy", a)
 
 
 def gen_weights_on_device(pkg, cfg, model, torch, device, keep_host: bool):
@@ -221,7 +249,7 @@ def main():
     sample_u = rng.random((G, B)).astype(np.float32)
 
     def one_step(profile_prefill: bool, profile_decode: bool = False):
-        """prefill all B prompts, then G decode steps; returns (prefill_s, decode_s)."""
+        """prefill all B prompts, then G decode steps; returns (prefill_s, decode_s, {name: what the caller received})."""
         for sid in seq_ids:
             model.seq_reset(sid)
         torch.cuda.synchronize()
@@ -232,20 +260,26 @@ def main():
             ids = seq_ids[b0:b0 + seqs_per_call]
             _, am = model.forward_batch(ids, [prompts[i] for i in ids], [0] * len(ids), want_logits=False)
             nxt[b0:b0 + len(ids)] = am
+        prefill_tok = nxt.copy()
         model.set_profile(profile_decode)
         t_b = time.perf_counter()
         if args.decode == "fused":
-            model.decode_greedy(seq_ids, nxt, G)
+            dec = model.decode_greedy(seq_ids, nxt, G)
         elif args.decode == "sampled":
             hist = [np.concatenate([prompts[i], nxt[i:i + 1]]) for i in range(B)]
-            model.decode_sampled(seq_ids, nxt, G, hist, sample_u)
+            dec = model.decode_sampled(seq_ids, nxt, G, hist, sample_u)
         else:
+            steps = []
             for g in range(G):
                 _, am = model.forward_batch(seq_ids, [[int(t)] for t in nxt], [S + g] * B, want_logits=False)
                 nxt = am
+                steps.append(am)
         t_c = time.perf_counter()
         model.set_profile(False)
-        return t_b - t_a, t_c - t_b
+        if args.decode == "stepwise":
+            dec = np.stack(steps) if steps else np.empty((0, B), np.int32)
+        outputs = {"prefill_next_token": prefill_tok, "decode_tokens": dec}
+        return t_b - t_a, t_c - t_b, outputs
 
     for _ in range(args.warmup):
         one_step(False)
@@ -261,7 +295,7 @@ def main():
     t_start = time.perf_counter()
     pre_s = dec_s = 0.0
     for _ in range(args.steps):
-        p, d = one_step(True)
+        p, d, last_outputs = one_step(True)
         pre_s += p
         dec_s += d
     sync_all()
@@ -269,6 +303,8 @@ def main():
     elapsed, pre_s, dec_s = pkg.dist.max_over_ranks([elapsed, pre_s, dec_s],
                                                     device="cpu" if args.rehearse_on_one_gpu else device)
     st = model.stats()
+    if args.dump_outputs and (rank == 0 or not tp):       # tensor parallel: every rank holds the same tokens
+        dump_outputs(Path(args.dump_outputs), last_outputs, "" if rank == 0 else f"_rank{rank}")
     # Per-kernel view: ONE more step of the same workload AFTER the timed region with HIP events around every launch of
     # both phases (events in the decode loop would cost the timed value a few percent).  nvl_get_kernel_stats: per
     # launch site, launches, device time and algorithmic work.
