@@ -89,8 +89,16 @@ typedef struct nvl_runtime_opts {
                                   0: one contiguous slab per sequence slot                              */
     int32_t kv_block_size;     /* tokens per block in paged mode: 0 = 256 (Sequence.BlockSize, sequence.go:51);
                                   a multiple of 64                                                     */
-    int32_t reserved;
+    int32_t kv_cache_dtype;    /* NVL_KV_*: element type of the KV cache (was `reserved`; 0 keeps today's behaviour)      */
 } nvl_runtime_opts;
+
+/* KV cache element type (nvl_runtime_opts.kv_cache_dtype).  Anything else is refused by nvl_create (NVL_ERR_INVALID). */
+enum {
+    NVL_KV_AUTO = 0,        /* the model's precision (bf16 / f32)                                                  */
+    NVL_KV_FP8_E4M3 = 1     /* OCP e4m3fn codes (1 byte per element: twice the tokens per byte of cache) + one fp32
+                               scale per layer for K and one for V.  bf16 precision only, no
+                               tensor parallelism.  nvl_get_kv / nvl_get_kv_paged return s * e4m3(code).            */
+};
 
 typedef struct nvl_model nvl_model;
 
@@ -136,6 +144,11 @@ enum {
     NVL_LAYOUT_IN_OUT = 0, /* [in, out]: what the reference holds after Transpose (generic_loader.go:398-403) */
     NVL_LAYOUT_OUT_IN = 1  /* [out, in]: the checkpoint's own PyTorch layout, uploaded without the host transpose */
 };
+
+/* Per-layer K / V scales of an 8-bit cache (arrays of num_layers; default 1.0; Mamba2 layers' entries ignored).
+ * NVL_ERR_STATE on a model without an 8-bit cache or after the first forward; NVL_ERR_INVALID for a non-finite or
+ * non-positive scale.  nvl_load_safetensors sets them from *.self_attn.k_scale / v_scale when the checkpoint has them. */
+int nvl_set_kv_scales(nvl_model* m, const float* k_scale, const float* v_scale);
 
 /* ---- lifecycle ---- */
 
@@ -389,6 +402,13 @@ int nvl_op_rope(int device, float* t, int heads, int seq, int hd, int start_pos,
  * q [nH,S,hd], k/v [nKV,T,hd] (keys 0..T-1, the last S are the new tokens) -> out [nH,S,hd] */
 int nvl_op_attention(int device, int precision, const float* q, const float* k, const float* v,
                      int nH, int nKV, int S, int T, int hd, float scale, float* out);
+/* 8-bit KV cache.  The device quantizer and read path on an array: codes[i] = e4m3fn(x[i] / scale)
+ * (round-to-nearest-even, saturating to +-448, NaN -> NaN code), back[i] = scale * bf16(codes[i]) in fp32. */
+int nvl_op_fp8_kv_roundtrip(int device, const float* x, int64_t n, float scale, uint8_t* codes, float* back);
+/* nvl_op_attention (bf16 only) over an 8-bit cache: k / v are quantized on the device with k_scale / v_scale by the
+ * same quantizer, then the 8-bit attention kernels run (S == 1: decode kernel, key split at long T; else prefill). */
+int nvl_op_attention_kv8(int device, const float* q, const float* k, const float* v, int nH, int nKV, int S, int T,
+                         int hd, float scale, float k_scale, float v_scale, float* out);
 /* FeedForward.Forward transformer.go:40-96 (w1 [H,2F] gate|up or [H,F]; w2 [F,H]) */
 int nvl_op_ffn(int device, int precision, const float* x, const float* w1, const float* b1,
                const float* w2, const float* b2, int rows, int hidden, int ffn, int swiglu,

@@ -32,6 +32,7 @@ POS = {"learned": 0, "rope": 1, "nope": 2}
 ACT = {"gelu": 0, "swiglu": 1}
 BLOCK = {"sequential": 0, "parallel": 1}
 PRECISION = {"bf16": 0, "f32": 1}
+KV_CACHE_DTYPE = {"auto": 0, "fp8_e4m3": 1}
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 LAYOUT_IN_OUT, LAYOUT_OUT_IN = 0, 1
 FWD_ALL_LOGITS = 1
@@ -68,7 +69,7 @@ class RuntimeOptsC(C.Structure):
     _fields_ = [("device", C.c_int32), ("precision", C.c_int32), ("max_seqs", C.c_int32),
                 ("max_batch_tokens", C.c_int32), ("tp_rank", C.c_int32), ("tp_size", C.c_int32),
                 ("tp_force_single", C.c_int32), ("kv_num_blocks", C.c_int32), ("kv_block_size", C.c_int32),
-                ("reserved", C.c_int32)]
+                ("kv_cache_dtype", C.c_int32)]
 
 
 class StatsC(C.Structure):
@@ -167,6 +168,9 @@ def lib():
     L.nvl_op_silu.argtypes = [C.c_int, vp, vp, i64]
     L.nvl_op_rope.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]
     L.nvl_op_attention.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]
+    L.nvl_set_kv_scales.argtypes = [vp, vp, vp]
+    L.nvl_op_fp8_kv_roundtrip.argtypes = [C.c_int, vp, i64, f32, vp, vp]
+    L.nvl_op_attention_kv8.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, f32, f32, vp]
     L.nvl_op_ffn.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.nvl_op_moe.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, vp]
     L.nvl_op_argmax.argtypes = [C.c_int, vp, C.c_int, C.c_int, vp]

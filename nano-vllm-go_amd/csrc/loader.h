@@ -283,6 +283,19 @@ std::vector<float> to_f32(const StTensor& t) {
 }
 }  // namespace
 
+// FP8-KV checkpoints: the per-layer scalar *.self_attn.k_scale / v_scale, taken when the model has an 8-bit cache
+inline void load_kv_scales(nvl_model* m, const StSet& st, const std::string& p, int l) {
+    if (!m->kv8) return;
+    const StTensor* k = st.find(p + ".self_attn.k_scale");
+    const StTensor* v = st.find(p + ".self_attn.v_scale");
+    for (const StTensor* t : {k, v})
+        if (t && (t->dtype < 0 || t->numel != 1)) throw std::runtime_error(p + ": k_scale / v_scale must be scalars");
+    const float ks = k ? f32_of(*k, 0) : m->k_scale[(size_t)l], vs = v ? f32_of(*v, 0) : m->v_scale[(size_t)l];
+    if (!(ks > 0.f) || !(vs > 0.f) || !std::isfinite(ks) || !std::isfinite(vs))
+        throw std::runtime_error(p + ": k_scale / v_scale must be finite and positive");
+    m->k_scale[(size_t)l] = ks; m->v_scale[(size_t)l] = vs;
+}
+
 extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
     if (!m || !path) return NVL_ERR_INVALID;
     if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_load_safetensors: model already finalized");
@@ -356,6 +369,7 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
                     up2d(m, NVL_T_WK, l, st.need(p + ".self_attn.k_proj.weight"), OI);
                     up2d(m, NVL_T_WV, l, st.need(p + ".self_attn.v_proj.weight"), OI);
                     up2d(m, NVL_T_WO, l, st.need(p + ".self_attn.o_proj.weight"), OI);
+                    load_kv_scales(m, st, p, l);
                 }
                 up2d(m, NVL_T_W1, l, st.need(p + ".shared_mlp.input_linear.weight"), OI);
                 up2d(m, NVL_T_W2, l, st.need(p + ".shared_mlp.output_linear.weight"), OI);
@@ -367,6 +381,7 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
             up2d(m, NVL_T_WK, l, st.need(p + ".self_attn.k_proj.weight"), OI);
             up2d(m, NVL_T_WV, l, st.need(p + ".self_attn.v_proj.weight"), OI);
             up2d(m, NVL_T_WO, l, st.need(p + ".self_attn.o_proj.weight"), OI);
+            load_kv_scales(m, st, p, l);
             if (c.use_moe) {                                                   // loadMoE (:566-592)
                 up2d(m, NVL_T_ROUTER, l, st.need(p + ".block_sparse_moe.router.layer.weight"), OI);   // [E, H]: "always transpose"
                 for (int which = 0; which < 2; which++) {

@@ -11,6 +11,7 @@
 
 #include "../../include/nvllm.h"
 #include "attn.h"
+#include "kv8.h"
 #include "common.h"
 #include "elem.h"
 #include "sample.h"
@@ -73,6 +74,11 @@ struct nvl_model {
     nvl_runtime_opts opts{};
     bool f32 = false;            // NVL_PRECISION_F32
     bool finalized = false;
+    // 8-bit KV cache (kv_cache_dtype = NVL_KV_FP8_E4M3, kv8.h): e4m3fn codes, 1 byte per element; per-layer fp32 scales
+    bool kv8 = false;
+    int kv_esize = 2;                      // bytes per cached K/V element (wsize, or 1 in 8-bit mode)
+    std::vector<float> k_scale, v_scale;   // [num_layers], default 1 (Mamba2 layers' entries unused)
+    bool kv_written = false;               // a forward has been enqueued: the scales are fixed from then on
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;

@@ -224,6 +224,12 @@ extern "C" int nvl_create(const nvl_model_config* cfg, const nvl_runtime_opts* o
         return fail(nullptr, NVL_ERR_INVALID, "nvl_create: max_seqs must be >= 1 (KV slots / sequences per call)");
     if (opts->max_batch_tokens < 0 || opts->kv_num_blocks < 0 || opts->kv_block_size < 0)
         return fail(nullptr, NVL_ERR_INVALID, "nvl_create: negative max_batch_tokens / kv_num_blocks / kv_block_size");
+    if (opts->kv_cache_dtype != NVL_KV_AUTO && opts->kv_cache_dtype != NVL_KV_FP8_E4M3)
+        return fail(nullptr, NVL_ERR_INVALID, "nvl_create: kv_cache_dtype must be NVL_KV_AUTO (0) or NVL_KV_FP8_E4M3 (1)");
+    if (opts->kv_cache_dtype == NVL_KV_FP8_E4M3 && opts->precision == NVL_PRECISION_F32)
+        return fail(nullptr, NVL_ERR_INVALID, "nvl_create: the fp8 KV cache needs NVL_PRECISION_BF16");
+    if (opts->kv_cache_dtype == NVL_KV_FP8_E4M3 && ((opts->tp_size > 1) || opts->tp_force_single == 1))
+        return fail(nullptr, NVL_ERR_INVALID, "nvl_create: the fp8 KV cache does not cover tensor parallelism");
     const int tp = opts->tp_size > 1 ? opts->tp_size : 1;
     if (tp > 1) {
         const int nkv_full = c.attention_type == NVL_ATTN_MHA ? c.num_heads : c.num_kv_heads;
@@ -260,6 +266,10 @@ extern "C" int nvl_create(const nvl_model_config* cfg, const nvl_runtime_opts* o
     m->cfg = c; m->opts = *opts;
     m->f32 = (opts->precision == NVL_PRECISION_F32);
     m->wsize = m->f32 ? 4 : 2;
+    m->kv8 = opts->kv_cache_dtype == NVL_KV_FP8_E4M3;
+    m->kv_esize = m->kv8 ? 1 : m->wsize;
+    m->k_scale.assign((size_t)std::max(c.num_layers, 1), 1.0f);
+    m->v_scale.assign((size_t)std::max(c.num_layers, 1), 1.0f);
     m->device = opts->device;
     NVL_HIP(hipSetDevice(m->device));
     NVL_HIP(hipStreamCreateWithFlags(&m->stream, hipStreamNonBlocking));
@@ -617,6 +627,24 @@ std::vector<int32_t> swiglu_interleave(int64_t F, int64_t src_base) {
 
 }  // namespace
 
+extern "C" int nvl_set_kv_scales(nvl_model* m, const float* k_scale, const float* v_scale) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_kv_scales: no model");
+    if (!m->kv8) return fail(m, NVL_ERR_STATE, "nvl_set_kv_scales: the model's KV cache is not 8-bit (kv_cache_dtype)");
+    if (m->kv_written) return fail(m, NVL_ERR_STATE, "nvl_set_kv_scales: the cache has been written (first forward done)");
+    if (!k_scale || !v_scale) return fail(m, NVL_ERR_INVALID, "nvl_set_kv_scales: NULL scales");
+    const bool any_mamba = (m->cfg.mamba_layer_mask[0] | m->cfg.mamba_layer_mask[1]) != 0;
+    for (int l = 0; l < m->L; l++) {
+        if (any_mamba && ((m->cfg.mamba_layer_mask[l >> 6] >> (l & 63)) & 1)) continue;     // Mamba2 layers: ignored
+        if (!(k_scale[l] > 0.f) || !(v_scale[l] > 0.f) || !std::isfinite(k_scale[l]) || !std::isfinite(v_scale[l]))
+            return fail(m, NVL_ERR_INVALID, "nvl_set_kv_scales: scales must be finite and positive");
+    }
+    for (int l = 0; l < m->L; l++) { m->k_scale[(size_t)l] = k_scale[l]; m->v_scale[(size_t)l] = v_scale[l]; }
+    for (int l = 0; l < m->L; l++)        // (Mamba2 entries are not used; keep them valid)
+        if (!(m->k_scale[(size_t)l] > 0.f) || !(m->v_scale[(size_t)l] > 0.f) || !std::isfinite(m->k_scale[(size_t)l]) || !std::isfinite(m->v_scale[(size_t)l]))
+            m->k_scale[(size_t)l] = m->v_scale[(size_t)l] = 1.0f;
+    return NVL_OK;
+}
+
 extern "C" int nvl_finalize(nvl_model* m) {
     if (!m) return NVL_ERR_INVALID;
     if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_finalize: already finalized");
@@ -753,10 +781,10 @@ extern "C" int nvl_finalize(nvl_model* m) {
     m->layer_stride = (int64_t)m->nKV * m->Tmax * hd;
     m->slot_stride = m->layer_stride * m->L;
     const int64_t kv_elems = m->slot_stride * m->num_blocks;
-    m->kcache = dmalloc_bytes(kv_elems * (int64_t)m->wsize);
-    m->vcache = dmalloc_bytes(kv_elems * (int64_t)m->wsize);
-    NVL_HIP(hipMemsetAsync(m->kcache, 0, (size_t)kv_elems * m->wsize, m->stream));
-    NVL_HIP(hipMemsetAsync(m->vcache, 0, (size_t)kv_elems * m->wsize, m->stream));
+    m->kcache = dmalloc_bytes(kv_elems * (int64_t)m->kv_esize);
+    m->vcache = dmalloc_bytes(kv_elems * (int64_t)m->kv_esize);
+    NVL_HIP(hipMemsetAsync(m->kcache, 0, (size_t)kv_elems * m->kv_esize, m->stream));
+    NVL_HIP(hipMemsetAsync(m->vcache, 0, (size_t)kv_elems * m->kv_esize, m->stream));
     m->slot_len.assign((size_t)m->opts.max_seqs, 0);
     m->slot_tick.assign((size_t)m->opts.max_seqs, 0);
     m->slot_pin.assign((size_t)m->opts.max_seqs, 0);
@@ -1182,13 +1210,63 @@ void attention(nvl_model* m, int li, const Meta& md, int n_seqs, int max_len, do
     NVL_HIP(hipGetLastError());
 }
 
+// attention over an 8-bit (e4m3fn) cache: kc / vc are the layer's code slabs (same element layout as the bf16 slabs, one
+// byte per element); k_scale / v_scale the layer's scales (kv8.h).  bf16 only; same grids and wave choices as attention().
+void attention_kv8(nvl_model* m, const Meta& md, int n_seqs, int max_len, const void* kc, const void* vc, float ksc, float vsc) {
+    if (m->f32) throw std::runtime_error("attention_kv8: the 8-bit KV cache is bf16-only");
+    AttnArgs a{};
+    a.q = m->q; a.q_stride = m->nH * m->hd;
+    a.out = m->attn_out; a.out_stride = m->nH * m->hd;
+    a.kcache = kc; a.vcache = vc;
+    a.slot_stride = m->slot_stride; a.Tmax = m->Tmax;
+    a.seq_tok_start = md.seq_tok_start; a.seq_len = md.seq_len; a.seq_pos = md.seq_pos; a.blk_table = md.blk_table; a.tbl_stride = m->blocks_per_seq;
+    a.bs_shift = (m->Tmax & (m->Tmax - 1)) == 0 ? __builtin_ctz((unsigned)m->Tmax) : -1;
+    a.nH = m->nH; a.nKV = m->nKV; a.group = m->group; a.scale = m->attn_scale;
+    const double abytes = m->kv_tok * 2.0 * m->nKV * m->hd;
+    KScope ks(m, KC_ATTN, 0.0, KS_ATTN, abytes);
+    if (max_len == 1) {
+        const int cfg = decode_attn_cfg(m, n_seqs), nsplit = cfg >> 8, nw = cfg & 255;
+        dim3 grid(m->nKV * cdiv(m->group, 16), n_seqs, nsplit);
+        a.part = m->attn_part; a.part_cnt = m->attn_part_cnt;
+        a.kv_nt = g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && cdiv(m->group, 16) == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
+#define NVL_DEC8_LEAD a.seq_pos, a.blk_table, a.tbl_stride, a.bs_shift, a.Tmax, a.group
+#define NVL_DEC8(HDv)                                                                                                  \
+        do {                                                                                                           \
+            constexpr int tile_bytes = 64 * HDv * 2;                                                                   \
+            if (nw == 2) hipLaunchKernelGGL((attn_decode_kv8_kernel<HDv, 2>), grid, dim3(128), 2 * tile_bytes, m->stream, NVL_DEC8_LEAD, a, ksc, vsc);      \
+            else if (nw == 4) hipLaunchKernelGGL((attn_decode_kv8_kernel<HDv, 4>), grid, dim3(256), 4 * tile_bytes, m->stream, NVL_DEC8_LEAD, a, ksc, vsc); \
+            else {                                                                                                     \
+                NVL_LDS_ATTR((attn_decode_kv8_kernel<HDv, 8>), 8 * tile_bytes);                                        \
+                hipLaunchKernelGGL((attn_decode_kv8_kernel<HDv, 8>), grid, dim3(512), 8 * tile_bytes, m->stream, NVL_DEC8_LEAD, a, ksc, vsc);               \
+            }                                                                                                          \
+        } while (0)
+        if (m->hd == 64) NVL_DEC8(64); else NVL_DEC8(128);
+#undef NVL_DEC8
+#undef NVL_DEC8_LEAD
+    } else {
+        const int64_t qrows = (int64_t)max_len * m->group;
+        dim3 grid(m->nKV, n_seqs, cdiv(qrows, 256));
+        if (m->hd == 64) {
+            hipLaunchKernelGGL((attn_prefill_kv8_kernel<64>), grid, dim3(512), attn_prefill_kv8_lds_bytes<64>(), m->stream, a, ksc, vsc);
+        } else {
+            NVL_LDS_ATTR(attn_prefill_kv8_kernel<128>, attn_prefill_kv8_lds_bytes<128>());
+            hipLaunchKernelGGL((attn_prefill_kv8_kernel<128>), grid, dim3(512), attn_prefill_kv8_lds_bytes<128>(), m->stream, a, ksc, vsc);
+        }
+    }
+    NVL_HIP(hipGetLastError());
+}
+
 void rope_kv(nvl_model* m, int li, const Meta& md, int M) {
     KScope ks(m, KC_OTHER, 0, KS_ROPE, (double)M * m->n_qkv * (4.0 + (double)m->wsize));
     dim3 grid(M, m->nH + 2 * m->nKV);
     const int thr = m->hd / 2;
-    void* kc = (char*)m->kcache + (size_t)li * m->layer_stride * m->wsize;
-    void* vc = (char*)m->vcache + (size_t)li * m->layer_stride * m->wsize;
-    if (m->f32)
+    void* kc = (char*)m->kcache + (size_t)li * m->layer_stride * m->kv_esize;
+    void* vc = (char*)m->vcache + (size_t)li * m->layer_stride * m->kv_esize;
+    if (m->kv8)
+        hipLaunchKernelGGL(rope_kv8_kernel, grid, dim3(thr), 0, m->stream, m->qkv, m->n_qkv,
+                           md.tok_pos, md.tok_tbl, md.blk_table, m->rope_cos, m->rope_sin, (bf16_t*)m->q, m->nH * m->hd,
+                           (uint8_t*)kc, (uint8_t*)vc, m->slot_stride, m->Tmax, m->nH, m->nKV, m->hd, m->k_scale[li], m->v_scale[li]);
+    else if (m->f32)
         hipLaunchKernelGGL((rope_kv_kernel<float, false>), grid, dim3(thr), 0, m->stream, m->qkv, m->n_qkv,
                            md.tok_pos, md.tok_tbl, md.blk_table, m->rope_cos, m->rope_sin, (float*)m->q, m->nH * m->hd,
                            (float*)kc, (float*)vc, m->slot_stride, m->Tmax, m->nH, m->nKV, m->hd);
@@ -1609,6 +1687,7 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
                     int seam = 0) {
     const nvl_model_config& c = m->cfg;
     const int H = m->H;
+    m->kv_written = true;                  // (nvl_set_kv_scales is refused from here on)
     m->pending_slices = 0;
     m->phase = max_len > 1 ? 0 : 1;         // per-site profile: prefill / decode
     if ((m->keep_hidden || m->tap) && m->hidden_tokens < M) {
@@ -1755,7 +1834,7 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
         // short prefill batches (65..g_qkv_store_max_m tokens): the fused-epilogue tile kernel would run on M/128 * 24
         // workgroups; the decode form + rope_kv_kernel is faster there
         const bool short_prefill = max_len > 1 && M <= g_qkv_store_max_m && M <= g_chunk_max_m && g_force_tile == 0;
-        if (!m->f32 && M > 64 && !big_decode && !short_prefill) {
+        if (!m->f32 && !m->kv8 && M > 64 && !big_decode && !short_prefill) {
             // prefill: RoPE + Q/K/V placement fused into the projection's epilogue (no fp32 qkv round trip)
             GemmArgs a = mk(m->xn, H, l.w_qkv, nullptr, 0, l.b_qkv, 1.f, M, m->n_qkv, H);
             a.qkv.tok_pos = md.tok_pos; a.qkv.tok_tbl = md.tok_tbl; a.qkv.blk_table = md.blk_table; a.qkv.cos_t = m->rope_cos; a.qkv.sin_t = m->rope_sin;
@@ -1770,10 +1849,14 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
             if (qkv_deferred) set_deferred_in(m, aq);
             m->site = KS_QKV;
             gemm(m, EPI_STORE, true, aq);
-            fused_dec = !m->f32 && max_len == 1;     // decode: RoPE + KV append live in the attention kernel
-            if (!fused_dec) rope_kv(m, li, md, M);
+            fused_dec = !m->f32 && !m->kv8 && max_len == 1;     // decode: RoPE + KV append live in the attention kernel
+            if (!fused_dec) rope_kv(m, li, md, M);     // (8-bit mode: always here — rope_kv8_kernel is its only K/V writer)
         }
-        attention(m, li, md, n_seqs, max_len, attn_flops, fused_dec);
+        if (m->kv8)
+            attention_kv8(m, md, n_seqs, max_len, (char*)m->kcache + (size_t)li * m->layer_stride,
+                          (char*)m->vcache + (size_t)li * m->layer_stride, m->k_scale[li], m->v_scale[li]);
+        else
+            attention(m, li, md, n_seqs, max_len, attn_flops, fused_dec);
         const float* bo = (const float*)l.t[NVL_T_BO].p;
         if (parallel) {
             // generic_model.go:395-418: r + [am*]attn + [rm*]ffn, both branches read the same normed x
@@ -2409,14 +2492,18 @@ namespace {
 void read_kv(nvl_model* m, const int32_t* blocks, int n_blocks, int T, int layer, float* k_out, float* v_out) {
     const int hd = m->hd, BS = m->Tmax;
     const int64_t n = m->layer_stride;
-    std::vector<char> kb((size_t)n * m->wsize), vb((size_t)n * m->wsize);
+    std::vector<char> kb((size_t)n * m->kv_esize), vb((size_t)n * m->kv_esize);
     auto rd = [&](const std::vector<char>& b, int64_t i) -> float {
+        if (m->kv8) {                   // s * e4m3fn(code), the value the attention kernels use
+            const float s = &b == &kb ? m->k_scale[layer] : m->v_scale[layer];
+            return e4m3fn_value(((const uint8_t*)b.data())[i]) * s;
+        }
         if (m->f32) return ((const float*)b.data())[i];
         uint32_t u = ((uint32_t)((const uint16_t*)b.data())[i]) << 16;
         float f; memcpy(&f, &u, 4); return f;
     };
     for (int bi = 0; bi < n_blocks && bi * BS < T; bi++) {
-        const size_t off = ((size_t)blocks[bi] * m->slot_stride + (size_t)layer * m->layer_stride) * m->wsize;
+        const size_t off = ((size_t)blocks[bi] * m->slot_stride + (size_t)layer * m->layer_stride) * m->kv_esize;
         NVL_HIP(hipMemcpy(kb.data(), (char*)m->kcache + off, kb.size(), hipMemcpyDeviceToHost));
         NVL_HIP(hipMemcpy(vb.data(), (char*)m->vcache + off, vb.size(), hipMemcpyDeviceToHost));
         const int t1 = std::min(T, (bi + 1) * BS);

@@ -224,6 +224,87 @@ extern "C" int nvl_op_attention(int device, int precision, const float* q, const
     OP_CATCH
 }
 
+extern "C" int nvl_op_fp8_kv_roundtrip(int device, const float* x, int64_t n, float scale, uint8_t* codes, float* back) {
+    if (!x || !codes || !back || n <= 0 || !(scale > 0.f) || !std::isfinite(scale)) return op_fail("nvl_op_fp8_kv_roundtrip: bad arguments");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_BF16);
+    float* dx = cx.up_f32(x, n);
+    uint8_t* dc = (uint8_t*)cx.alloc(round_up(n, 4));
+    float* db = (float*)cx.alloc(n * 4);
+    const unsigned blocks = (unsigned)cdiv(cdiv(n, 4), 256);
+    hipLaunchKernelGGL(kv8_quant_kernel, dim3(blocks), dim3(256), 0, cx.m.stream, dx, n, scale, dc);
+    hipLaunchKernelGGL(kv8_dequant_kernel, dim3(blocks), dim3(256), 0, cx.m.stream, (const uint8_t*)dc, n, scale, db);
+    NVL_HIP(hipGetLastError());
+    NVL_HIP(hipMemcpyAsync(codes, dc, (size_t)n, hipMemcpyDeviceToHost, cx.m.stream));
+    cx.down(back, db, n);
+    return NVL_OK;
+    OP_CATCH
+}
+
+extern "C" int nvl_op_attention_kv8(int device, const float* q, const float* k, const float* v, int nH, int nKV, int S, int T,
+                                    int hd, float scale, float k_scale, float v_scale, float* out) {
+    if (!q || !k || !v || !out || nH <= 0 || nKV <= 0 || nH % nKV || S <= 0 || T < S || (hd != 64 && hd != 128))
+        return op_fail("nvl_op_attention_kv8: bad arguments");
+    if (!(k_scale > 0.f) || !(v_scale > 0.f) || !std::isfinite(k_scale) || !std::isfinite(v_scale))
+        return op_fail("nvl_op_attention_kv8: k_scale / v_scale must be finite and positive");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_BF16);
+    nvl_model& m = cx.m;
+    const int Tmax = (int)round_up(T, 64);
+    std::vector<float> qt((size_t)S * nH * hd), kc((size_t)nKV * Tmax * hd, 0.f), vc((size_t)nKV * Tmax * hd, 0.f);
+    for (int h = 0; h < nH; h++)
+        for (int s = 0; s < S; s++)
+            memcpy(&qt[((size_t)s * nH + h) * hd], q + ((size_t)h * S + s) * hd, (size_t)hd * 4);
+    for (int h = 0; h < nKV; h++)
+        for (int t = 0; t < T; t++) {
+            memcpy(&kc[((size_t)h * Tmax + t) * hd], k + ((size_t)h * T + t) * hd, (size_t)hd * 4);
+            memcpy(&vc[((size_t)h * Tmax + t) * hd], v + ((size_t)h * T + t) * hd, (size_t)hd * 4);
+        }
+    m.q = cx.up_mat(qt.data(), S, (int64_t)nH * hd, false, 1, true);
+    // the 8-bit slabs, written by the shared quantizer from the fp32 values (padding rows: code 0)
+    const int64_t n_el = (int64_t)kc.size();
+    const float* dk = cx.up_f32(kc.data(), n_el);
+    const float* dv = cx.up_f32(vc.data(), n_el);
+    uint8_t* k8 = (uint8_t*)cx.alloc(n_el);
+    uint8_t* v8 = (uint8_t*)cx.alloc(n_el);
+    const unsigned qblocks = (unsigned)cdiv(cdiv(n_el, 4), 256);
+    hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dk, n_el, k_scale, k8);
+    hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dv, n_el, v_scale, v8);
+    NVL_HIP(hipGetLastError());
+    m.attn_out = cx.alloc(round_up(S, 64) * nH * hd * 2);
+    m.nH = nH; m.nKV = nKV; m.group = nH / nKV; m.hd = hd; m.Tmax = Tmax; m.L = 1;
+    m.layer_stride = (int64_t)nKV * Tmax * hd; m.slot_stride = m.layer_stride;
+    m.attn_scale = scale != 0.f ? scale : 1.0f / std::sqrt((float)hd);
+    // the key-split decode form needs its partial-result scratch and the context length (as the model path)
+    m.attn_part = (float*)cx.alloc((int64_t)ATTN_SPLIT_MAX_PAIRS * ATTN_SPLIT_MAX * (hd == 64 ? attn_part_floats<64>() : attn_part_floats<128>()) * 4);
+    m.attn_part_cnt = (int32_t*)cx.alloc(ATTN_SPLIT_MAX_PAIRS * 4);
+    NVL_HIP(hipMemsetAsync(m.attn_part_cnt, 0, ATTN_SPLIT_MAX_PAIRS * 4, m.stream));
+    m.ctx_hint = T;
+    const int32_t meta[5] = {0, S, T - S, 0, 0};
+    int32_t* dmeta = (int32_t*)cx.alloc(20);
+    NVL_HIP(hipMemcpyAsync(dmeta, meta, 20, hipMemcpyHostToDevice, m.stream));
+    Meta md{};
+    md.seq_tok_start = dmeta; md.seq_len = dmeta + 1; md.seq_pos = dmeta + 2; md.seq_tbl = dmeta + 3; md.blk_table = dmeta + 4;
+    m.blocks_per_seq = 1;
+    attention_kv8(&m, md, 1, S, k8, v8, k_scale, v_scale);
+    std::vector<float> ot((size_t)S * nH * hd);
+    std::vector<uint16_t> ob((size_t)(round_up(S, 64) * nH * hd));
+    NVL_HIP(hipMemcpyAsync(ob.data(), m.attn_out, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
+    NVL_HIP(hipStreamSynchronize(m.stream));
+    const int64_t W = (int64_t)nH * hd;
+    for (int64_t r = 0; r < S; r++)
+        for (int64_t c = 0; c < W; c++) {
+            uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, W)]) << 16;
+            memcpy(&ot[(size_t)(r * W + c)], &u, 4);
+        }
+    for (int h = 0; h < nH; h++)
+        for (int s = 0; s < S; s++)
+            memcpy(out + ((size_t)h * S + s) * hd, &ot[((size_t)s * nH + h) * hd], (size_t)hd * 4);
+    m.q = m.attn_out = nullptr; m.attn_part = nullptr; m.attn_part_cnt = nullptr;   // owned by cx.bufs
+    return NVL_OK;
+    OP_CATCH
+}
+
 extern "C" int nvl_op_ffn(int device, int precision, const float* x, const float* w1, const float* b1, const float* w2,
                           const float* b2, int rows, int hidden, int ffn, int swiglu, float* y) {
     if (!x || !w1 || !w2 || !y || rows <= 0 || hidden % 64 || ffn % 64) return op_fail("nvl_op_ffn: bad arguments");

@@ -45,10 +45,13 @@ class HipTransformerModel:
 
     def __init__(self, cfg: dict, tensors: dict | None, *, device: int = 0, precision: str = "bf16",
                  max_seqs: int = 8, max_batch_tokens: int | None = None, tp_rank: int = 0, tp_size: int = 1,
-                 tp_force_single: bool = False, kv_num_blocks: int = 0, kv_block_size: int = 0):
+                 tp_force_single: bool = False, kv_num_blocks: int = 0, kv_block_size: int = 0,
+                 kv_cache_dtype: str = "auto", kv_scales=None):
         """tensors=None defers finalize(): upload() each tensor, then call finalize().
         tp_size > 1 makes this the tp_rank-th tensor-parallel shard: pass the FULL tensors, the library keeps
-        its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests)."""
+        its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests).
+        kv_cache_dtype="fp8_e4m3": 8-bit K/V (bf16 precision); kv_scales=(k, v), each a scalar or one value per layer
+        (nvl_set_kv_scales; a checkpoint's own *.self_attn.k_scale / v_scale, read by from_pretrained, take precedence)."""
         self.cfg = dict(cfg)
         self.lib = L.lib()
         self.h = C.c_void_p()
@@ -59,14 +62,27 @@ class HipTransformerModel:
         # kv_num_blocks > 0: paged KV — the host's block manager (nanovllm/block_manager.go) owns the cache
         opts.kv_num_blocks, opts.kv_block_size = int(kv_num_blocks), int(kv_block_size)
         self.kv_block_size = (kv_block_size or 256) if kv_num_blocks else 0
+        if kv_cache_dtype not in L.KV_CACHE_DTYPE:
+            raise ValueError(f"kv_cache_dtype must be one of {sorted(L.KV_CACHE_DTYPE)}")
+        opts.kv_cache_dtype = L.KV_CACHE_DTYPE[kv_cache_dtype]
+        self.kv_cache_dtype = kv_cache_dtype
         self._c = _cfg_struct(cfg)
         L.check(self.lib.nvl_create(C.byref(self._c), C.byref(opts), C.byref(self.h)))
+        if kv_scales is not None:
+            self.set_kv_scales(*kv_scales)
         self.V = cfg["vocab_size"]
         self.H = cfg["hidden"]
         if tensors is not None:
             for (slot, layer), arr in tensors.items():
                 self.upload(slot, layer, arr)
             self.finalize()
+
+    def set_kv_scales(self, k_scale, v_scale):
+        """per-layer K / V scales of the 8-bit cache (scalars broadcast over the layers); before the first forward"""
+        n = self.cfg["num_layers"]
+        k = np.broadcast_to(np.asarray(k_scale, np.float32), (n,)).copy()
+        v = np.broadcast_to(np.asarray(v_scale, np.float32), (n,)).copy()
+        L.check(self.lib.nvl_set_kv_scales(self.h, k.ctypes.data_as(C.c_void_p), v.ctypes.data_as(C.c_void_p)), self.h)
 
     @classmethod
     def from_pretrained(cls, path: str, **kw):

@@ -73,6 +73,25 @@ def attention(q, k, v, scale=0.0, precision="bf16", device=0):  # attention.go:3
     return out
 
 
+def fp8_kv_roundtrip(x, scale=1.0, device=0):                  # the 8-bit KV cache's quantizer + read path (kv8.h)
+    """-> (codes uint8, back fp32): codes = e4m3fn(x / scale), back = scale * bf16(code), both computed on the device."""
+    x = _f(x)
+    codes = np.empty(x.shape, np.uint8)
+    back = np.empty_like(x)
+    L.check(L.lib().nvl_op_fp8_kv_roundtrip(device, _p(x), x.size, scale, _p(codes), _p(back)))
+    return codes, back
+
+
+def attention_kv8(q, k, v, scale=0.0, k_scale=1.0, v_scale=1.0, device=0):   # attention() over an 8-bit cache (bf16)
+    q, k, v = _f(q), _f(k), _f(v)
+    nH, S, hd = q.shape
+    nKV, T, _ = k.shape
+    out = np.empty_like(q)
+    L.check(L.lib().nvl_op_attention_kv8(device, _p(q), _p(k), _p(v), nH, nKV, S, T, hd, scale, k_scale, v_scale,
+                                         _p(out)))
+    return out
+
+
 def feed_forward(x, w1, b1, w2, b2, swiglu, precision="bf16", device=0):   # FeedForward.Forward transformer.go:40
     x, w1, w2 = _f(x), _f(w1), _f(w2)
     b1 = None if b1 is None else _f(b1)

@@ -39,6 +39,7 @@ type Options struct {
 	MaxBatchTokens int  // >= Config.MaxNumBatchedTokens; 0 = the model's MaxSeqLen
 	Greedy         bool // return the device argmax (cmd/ask/main.go:389-402) instead of sampling
 	DeviceSampling bool // run tensor.SampleWithHistory on the device (only token ids cross PCIe)
+	KVCacheDType   int  // C.NVL_KV_AUTO (0) or C.NVL_KV_FP8_E4M3 (1): 8-bit K/V, twice the tokens per byte of cache
 }
 
 // HipModelRunner implements nanovllm.ModelRunner on one MI355X.
@@ -318,6 +319,7 @@ func create(cfg *C.nvl_model_config, o Options) (*HipModelRunner, error) {
 	opts.max_batch_tokens = C.int32_t(o.MaxBatchTokens)
 	opts.tp_rank = 0
 	opts.tp_size = 1
+	opts.kv_cache_dtype = C.int32_t(o.KVCacheDType)
 	r := &HipModelRunner{sampling: tensor.DefaultSamplingParams(), greedy: o.Greedy, deviceSampling: o.DeviceSampling}
 	if rc := C.nvl_create(cfg, &opts, &r.h); rc != 0 {
 		return nil, createErr()
