@@ -150,6 +150,25 @@ enum {
  * non-positive scale.  nvl_load_safetensors sets them from *.self_attn.k_scale / v_scale when the checkpoint has them. */
 int nvl_set_kv_scales(nvl_model* m, const float* k_scale, const float* v_scale);
 
+/* Storage type of the projection weights.  The reference keeps every weight fp32
+ * (generic_loader.go:398-403, loadTensorFromData); this is the library's own opt-in, reached only through this call. */
+enum {
+    NVL_W_AUTO = 0,        /* the precision's own type (bf16 / f32): today's behaviour                                     */
+    NVL_W_FP8_E4M3 = 1     /* WQ/WK/WV/WKV/WO/W1/W2 and the LM head (the token embedding when tied) as OCP e4m3fn codes with
+                            * one fp32 scale per output row: s = amax/448 (1 for a zero row), q = e4m3fn_rne(w / s).  Every path
+                            * computes with W~ = bf16_rne(s * e4m3(q)); nvl_get_weight returns W~; nvl_stats.weight_bytes
+                            * counts codes + scales.  Position embedding, router, MoE experts, Mamba2 projections stay bf16. */
+};
+/* After nvl_create, before the first 2-D upload (else NVL_ERR_STATE).  NVL_ERR_INVALID for an unknown value, and for
+ * NVL_W_FP8_E4M3 with f32 precision or tensor parallelism.  In fp8 mode nvl_upload_tensor refuses a non-finite weight. */
+int nvl_set_weight_dtype(nvl_model* m, int dtype);
+/* Pre-quantized 8-bit weight, taken as it is (the dtype of nvl_load_safetensors' F8_E4M3 tensors): codes [rows][cols] OCP
+ * e4m3fn in the checkpoint's [out, in] order (layout must be NVL_LAYOUT_OUT_IN), scales [rows] fp32, W~ = bf16(s * e4m3(q)).
+ * Counterpart of nvl_upload_tensor (generic_loader.go:353-604) for a kind this model stores 8-bit; NVL_ERR_INVALID for any
+ * other kind, a shape mismatch, a NaN code (0x7f / 0xff) or a non-finite / non-positive scale. */
+int nvl_upload_tensor_fp8(nvl_model* m, int kind, int layer, const uint8_t* codes, const float* scales, int64_t rows,
+                          int64_t cols, int layout);
+
 /* ---- lifecycle ---- */
 
 /* Replaces tensor.NewTransformerModel (generic_model.go:41-61) + the runner's model ownership
@@ -409,6 +428,11 @@ int nvl_op_fp8_kv_roundtrip(int device, const float* x, int64_t n, float scale, 
  * same quantizer, then the 8-bit attention kernels run (S == 1: decode kernel, key split at long T; else prefill). */
 int nvl_op_attention_kv8(int device, const float* q, const float* k, const float* v, int nH, int nKV, int S, int T,
                          int hd, float scale, float k_scale, float v_scale, float* out);
+/* 8-bit weights: tensor.MatMul (tensor.go:62-88) with b = w [K][N] quantized by the model's upload quantizer
+ * (NVL_W_FP8_E4M3), c [M][N] = bf16(a) · W~ through the model's own GEMM dispatch (M selects the decode or the tile form).
+ * codes_out [N][K] / scales_out [N] (either may be NULL) receive the quantized weight.  K % 64 == 0. */
+int nvl_op_matmul_fp8w(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* codes_out,
+                       float* scales_out);
 /* FeedForward.Forward transformer.go:40-96 (w1 [H,2F] gate|up or [H,F]; w2 [F,H]) */
 int nvl_op_ffn(int device, int precision, const float* x, const float* w1, const float* b1,
                const float* w2, const float* b2, int rows, int hidden, int ffn, int swiglu,

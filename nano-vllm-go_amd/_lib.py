@@ -33,6 +33,7 @@ ACT = {"gelu": 0, "swiglu": 1}
 BLOCK = {"sequential": 0, "parallel": 1}
 PRECISION = {"bf16": 0, "f32": 1}
 KV_CACHE_DTYPE = {"auto": 0, "fp8_e4m3": 1}
+WEIGHT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                # NVL_W_* (nvl_set_weight_dtype)
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 LAYOUT_IN_OUT, LAYOUT_OUT_IN = 0, 1
 FWD_ALL_LOGITS = 1
@@ -169,6 +170,9 @@ def lib():
     L.nvl_op_rope.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_int]
     L.nvl_op_attention.argtypes = [C.c_int, C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]
     L.nvl_set_kv_scales.argtypes = [vp, vp, vp]
+    L.nvl_set_weight_dtype.argtypes = [vp, C.c_int]
+    L.nvl_upload_tensor_fp8.argtypes = [vp, C.c_int, C.c_int, vp, vp, i64, i64, C.c_int]
+    L.nvl_op_matmul_fp8w.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.nvl_op_fp8_kv_roundtrip.argtypes = [C.c_int, vp, i64, f32, vp, vp]
     L.nvl_op_attention_kv8.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, f32, f32, vp]
     L.nvl_op_ffn.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp]

@@ -27,6 +27,7 @@
 // the tight-tolerance parity mode, not a performance path.
 #pragma once
 #include <stdexcept>
+#include <type_traits>
 #include "common.h"
 
 namespace nvl {
@@ -611,6 +612,25 @@ __device__ __forceinline__ bf16x8 weight_load(const bf16x8* p) {
     else return __builtin_nontemporal_load(p);
 }
 
+typedef __attribute__((ext_vector_type(2))) uint32_t u32x2;
+template <bool KEEP>
+__device__ __forceinline__ u32x2 weight_load8(const u32x2* p) {
+    if constexpr (KEEP) return *p;
+    else return __builtin_nontemporal_load(p);
+}
+// eight e4m3fn codes of one weight row -> the bf16 MFMA fragment of W~ = bf16_rne(s * e4m3(q)): the exact conversion to
+// fp32 (v_cvt_pk_f32_fp8, OCP e4m3fn on gfx950), one fp32 multiply by the row scale, one RNE rounding to bf16
+__device__ __forceinline__ bf16x8 w8_frag(u32x2 c, float s) {
+    bf16x8 o;
+#pragma unroll
+    for (int h = 0; h < 2; h++) {
+        const f32x2 a = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[h], false), b = __builtin_amdgcn_cvt_pk_f32_fp8((int)c[h], true);
+        o[4 * h + 0] = (__bf16)(a[0] * s); o[4 * h + 1] = (__bf16)(a[1] * s);
+        o[4 * h + 2] = (__bf16)(b[0] * s); o[4 * h + 3] = (__bf16)(b[1] * s);
+    }
+    return o;
+}
+
 // m_passes > 1: block id -> (weight block, 64-row activation group).  Ids that differ by 8 share an XCD and are
 // dispatched back to back: the groups of one weight block stream the same weights at the same time.
 __device__ __forceinline__ void skinny_pass_remap(GemmArgs& p, int& bx) {
@@ -839,6 +859,241 @@ __global__ __launch_bounds__(1024) void gemm_skinny_bf16_kernel(GemmArgs p) {
                                  EPI != EPI_STORE ? 1.0f : (RSTD_PRE && i == i_pre ? rstd_pre : deferred_rstd(p, 16 * i + fr)));
         }
     }
+}
+
+// fp8-weight form of the narrow kernel: the weights are e4m3fn codes in the same fragment-major order,
+// one byte per element (a lane loads 8 bytes per k-step), and w_scale[row] is the row's fp32 scale; w8_frag turns them into
+// the bf16 fragment of W~ = bf16_rne(s * e4m3(q)) — exactly the values the bf16 kernel would read from a bf16 W~.  The
+// body is gemm_skinny_bf16_kernel's with the weight load replaced (W8 = false reproduces it); the bf16 kernel keeps its
+// own copy because instantiating it from this body changed its instruction schedule and register count, and the bf16
+// kernels are kept byte-identical in the device assembly.
+template <int MT, int NTW, int U, int EPI, typename OutT, bool PASSES, bool MOE, bool HALF, bool W8>
+__device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scale) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    f32x4* red = (f32x4*)smem;                       // [NTW][ksplit][MT][64]
+    const int swg = blockIdx.y * gridDim.x + blockIdx.x;
+    NvlStamps stamps(p.stamps, swg);                 // (diagnostic runs; slot 0: workgroup entered)
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int ksplit = (blockDim.x >> 6) / NTW;
+    const int tile = wave / ksplit, kw = wave - tile * ksplit;
+    const int fr = lane & 15, fg = lane >> 4;
+    int bx = blockIdx.x;
+    if constexpr (PASSES) skinny_pass_remap(p, bx);     // (its own instantiation: rewriting the arguments costs the
+                                                        // single-group kernels a few scratch dwords otherwise)
+    const int half = HALF ? (bx & 1) : 0;
+    if constexpr (HALF) bx >>= 1;
+    const bool w_live = !HALF || (fr >> 3) == half;  // HALF: this lane's weight row belongs to the workgroup
+    const int nt0 = bx * NTW;                        // first 16-row weight tile of this workgroup
+    // K/32 k-steps dealt over (gridDim.y slices) x (ksplit waves) as evenly as possible (K need not divide:
+    // Falcon's 4544 = 142 steps)
+    const int i_off = p.m_split ? blockIdx.y : 0;                  // first 16-row activation tile of this workgroup
+    // deferred RMSNorm (consumer side): the scale of the rows of this wave's first epilogue element, fetched under the weight
+    // stream instead of after it.  Issued HERE, ahead of the first weight block.  (Round 3 moved it behind the first block on
+    // the evidence of in-kernel time stamps — first weight data 0.5 us earlier — and lost 0.5 us per QKV launch and 0.25 us
+    // per FFN-up launch at B = 32 by the kernel trace of the unstamped build: the stamp sites themselves had changed the
+    // schedule they measured.  profiles/r03_ab_vs_r02.txt)
+    const int i_pre = wave % MT;
+    // (MT = 4 — batches above 32 and the 64-row groups of larger ones — has no registers to hold it across the stream:
+    // 34-54 spilled there, QKV at 128 rows 7.2 -> 10.8 us; those launches are long enough to fetch it in the epilogue)
+    constexpr bool RSTD_PRE = MT <= 2;
+    const float rstd_pre = (RSTD_PRE && (EPI == EPI_STORE || EPI == EPI_SWIGLU) && wave < NTW * MT) ? deferred_rstd(p, 16 * i_pre + fr) : 1.0f;   // (only the waves that run an epilogue element)
+    // (grid_y: gridDim.y as an explicit argument — the built-in lives in the hidden part of the kernarg block and costs a
+    // dependent scalar round trip of its own before the first weight load)
+    const int nslices = p.m_split ? 1 : p.grid_y, slice = p.m_split ? 0 : blockIdx.y;
+    const int nparts = ksplit * nslices, part = slice * ksplit + kw;
+    const int nks = p.K >> 5, q = nks / nparts, rr = nks - q * nparts;
+    int my_steps = q + (part < rr ? 1 : 0);
+    const int ks0 = part * q + (part < rr ? part : rr);   // first k-step of this wave
+    // MoE decode (its own instantiation): stream only the experts some token of the batch picked.  Up: a workgroup's rows
+    // belong to one expert.  Down: a wave's K range covers up to four experts (one with the K split over workgroups, two
+    // to four in the deferred-norm form, which keeps all of K in one workgroup); blk_live bit b = block b (U k-steps,
+    // inside one expert: the launcher checks the divisibility) of this wave's range is to be streamed.
+    uint32_t blk_live = 0xffffffffu;
+    bool tail_live = true;                 // the ragged tail (fewer than U k-steps; it lies inside the range's last expert)
+    if constexpr (MOE) {
+        if (EPI == EPI_SWIGLU) { if (!moe_expert_live(p, (nt0 * 16) / (2 * p.moe_I))) return; }          // (whole workgroup: uniform)
+        else {
+            const int spe = p.moe_I >> 5, e0 = ks0 / spe, e1 = (ks0 + my_steps - 1) / spe;      // k-steps per expert; this wave's experts
+            float g[4];
+#pragma unroll
+            for (int j = 0; j < 4; j++) g[j] = (e0 + j <= e1 && lane < p.M) ? p.moe_gate[lane * p.moe_E + e0 + j] : 0.f;   // (one round trip for all four)
+            blk_live = 0;
+            tail_live = false;
+#pragma unroll
+            for (int j = 0; j < 4; j++) {
+                if (!__any(g[j] != 0.f)) continue;
+                if (e0 + j == e1) tail_live = true;
+                const int b0 = max(((e0 + j) * spe - ks0) / U, 0), b1 = min(((e0 + j + 1) * spe - ks0) / U, 32);
+                if (b1 > b0) blk_live |= (b1 - b0 >= 32 ? 0xffffffffu : ((1u << (b1 - b0)) - 1u)) << b0;
+            }
+        }
+    }
+
+    const bf16_t* wp = (const bf16_t*)p.W + (((int64_t)(nt0 + tile) * (p.K >> 5) + ks0) * 64 + lane) * 8;
+    const uint8_t* wq = (const uint8_t*)p.W + (((int64_t)(nt0 + tile) * (p.K >> 5) + ks0) * 64 + lane) * 8;
+    const float wsc = W8 ? w_scale[(nt0 + tile) * 16 + fr] : 1.0f;     // (rows are padded: every tile's scales exist)
+    auto wload = [&](int64_t s) -> bf16x8 { return w8_frag(weight_load8<PASSES>((const u32x2*)(wq + s * 512)), wsc); };
+    // W8: a block's registers hold the raw codes; they are converted where the MFMAs consume them (comp_blk).  Converting
+    // at the load put the conversion inside the HALF form's predicated load, and the compiler then waited for every load
+    // (vmcnt(0)) before issuing the next one: O / FFN-down at B <= 16 ran at about half speed.  MT = 4 (64-row groups,
+    // never HALF) converts at the load: holding raw codes there spilled 14-26 registers against the 128-register budget.
+    constexpr bool RAW = W8 && MT <= 2;
+    typedef typename std::conditional<RAW, u32x2, bf16x8>::type WReg;
+    auto wfrag = [&](const WReg& w) -> bf16x8 {
+        if constexpr (RAW) return w8_frag(w, wsc);
+        else return w;
+    };
+    const bf16_t* xp[MT];
+#pragma unroll
+    for (int i = 0; i < MT; i++)   // rows >= M of the last 16-row tile exist (padded allocation) and are never stored
+        xp[i] = (const bf16_t*)p.A + (((int64_t)(i + i_off) * (p.K >> 5) + ks0) * 64 + lane) * 8;
+    f32x4 acc[MT];
+#pragma unroll
+    for (int i = 0; i < MT; i++) acc[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+    // Only the lanes of rows < M fetch their activation fragment (the rest feed zeros: their output columns are never
+    // stored).  The CU's ingest rate, not HBM, bounds these kernels, and at M = 1 a padded 16-row fragment would be as
+    // many bytes as the weight fragment beside it (M <= 4: a quarter of it with the mask, four 64-byte sectors).
+    bool x_live[MT];
+#pragma unroll
+    for (int i = 0; i < MT; i++) x_live[i] = !p.x_mask || 16 * (i + i_off) + fr < p.M;   // (x_mask: the host sets it when M % 16 != 0)
+    const bf16x8 x_zero = {};
+
+    // k loop: blocks of U k-steps (U*32 of K), two register sets -> the next block's loads are in
+    // flight while the current block's MFMAs issue (the compiler emits counted vmcnt for these).
+    const int nblk = my_steps / U;
+    WReg wA[U], wB[U];
+    bf16x8 xA[U][MT], xB[U][MT];
+    auto load_blk = [&](WReg (&w)[U], bf16x8 (&x)[U][MT], int b) {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+            if constexpr (RAW) w[u] = (!HALF || w_live) ? weight_load8<PASSES>((const u32x2*)(wq + (int64_t)(b * U + u) * 512)) : u32x2{0u, 0u};
+            else if constexpr (W8) w[u] = (!HALF || w_live) ? wload((int64_t)(b * U + u)) : x_zero;
+            else if constexpr (HALF) w[u] = w_live ? weight_load<PASSES>((const bf16x8*)(wp + (int64_t)(b * U + u) * 512)) : x_zero;
+            else w[u] = weight_load<PASSES>((const bf16x8*)(wp + (int64_t)(b * U + u) * 512));
+#pragma unroll
+            for (int i = 0; i < MT; i++) {
+                const bf16x8* src = (const bf16x8*)(xp[i] + (int64_t)(b * U + u) * 512);
+                if (p.x_mask) x[u][i] = x_live[i] ? *src : x_zero; else x[u][i] = *src;      // (uniform branch)
+            }
+        }
+    };
+    auto comp_blk = [&](WReg (&w)[U], bf16x8 (&x)[U][MT]) {
+#pragma unroll
+        for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int i = 0; i < MT; i++)
+                acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfrag(w[u]), x[u][i], acc[i], 0, 0, 0);
+    };
+    // MoE down: the live blocks of the wave's range, in order, through the same two register sets
+    uint32_t live = 0;
+    int bA = -1;
+    if constexpr (MOE && EPI == EPI_RESID) {
+        live = blk_live & (nblk >= 32 ? 0xffffffffu : ((1u << nblk) - 1u));
+        live = __builtin_amdgcn_readfirstlane(live);
+        if (live) { bA = __builtin_ctz(live); live &= live - 1; load_blk(wA, xA, bA); }
+    } else {
+        if (nblk > 0) load_blk(wA, xA, 0);
+    }
+    stamps.mark(1);                     // first block of loads issued
+    // the residual operand of this wave's first epilogue element (deferred-norm producer form): fetched under the weight
+    // stream, not as a dependent round trip after the K reduction (this launch is the only writer of these elements)
+    f32x4 x_pre = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (EPI == EPI_RESID && p.rs_out && wave < NTW * MT) {
+        const int t = wave / MT, i = wave - t * MT;
+        const int m = 16 * (i + i_off) + fr, n = (nt0 + t) * 16 + 4 * fg;
+        if (m < p.M && n < p.N && (!HALF || (fg >> 1) == half)) x_pre = *(const f32x4*)((const float*)p.C + (int64_t)m * p.ldc + n);
+    }
+    if constexpr (MOE && EPI == EPI_RESID) {
+        while (bA >= 0) {
+            int bB = -1;
+            if (live) { bB = __builtin_ctz(live); live &= live - 1; load_blk(wB, xB, bB); }
+            comp_blk(wA, xA);
+            if (bB < 0) break;
+            bA = -1;
+            if (live) { bA = __builtin_ctz(live); live &= live - 1; load_blk(wA, xA, bA); }
+            comp_blk(wB, xB);
+        }
+    } else {
+    int b = 0;
+    for (; b + 2 <= nblk; b += 2) {
+        load_blk(wB, xB, b + 1);
+        comp_blk(wA, xA);
+        if (b == 0) stamps.mark_used(2, acc[0]);       // first block's data arrived and was used
+        if (b + 2 < nblk) load_blk(wA, xA, b + 2);
+        comp_blk(wB, xB);
+    }
+    if (b < nblk) comp_blk(wA, xA);
+    }
+    for (int s = nblk * U; s < (tail_live ? my_steps : 0); s++) {      // ragged tail: fewer than U k-steps
+        const bf16x8 w = w_live ? (W8 ? wload((int64_t)s) : weight_load<PASSES>((const bf16x8*)(wp + (int64_t)s * 512))) : x_zero;
+#pragma unroll
+        for (int i = 0; i < MT; i++)
+            acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x_live[i] ? *(const bf16x8*)(xp[i] + (int64_t)s * 512) : x_zero, acc[i], 0, 0, 0);
+    }
+
+    // ---- reduce the K slices in wave order ----
+#pragma unroll
+    for (int i = 0; i < MT; i++) red[((tile * ksplit + kw) * MT + i) * 64 + lane] = acc[i];
+    stamps.mark(3);                     // wave 0's stream done
+    __syncthreads();
+    stamps.mark(4);                     // every wave's stream done
+    auto ksum = [&](int t, int i) {
+        f32x4 s = red[((t * ksplit) * MT + i) * 64 + lane];
+        for (int w = 1; w < ksplit; w++) s += red[((t * ksplit + w) * MT + i) * 64 + lane];
+        return s;
+    };
+    if (EPI == EPI_SWIGLU) {
+        for (int i = wave; i < MT; i += NTW * ksplit) {
+            const int f = (nt0 >> 1) * 16 + 4 * fg;    // NTW == 2: tiles [gate 16 | up 16] of features 8*nt0..
+            epilogue_swiglu4<OutT, MOE>(p, 16 * i + fr, f, ksum(0, i), ksum(NTW - 1, i),
+                                        RSTD_PRE && i == i_pre ? rstd_pre : deferred_rstd(p, 16 * i + fr));
+        }
+    } else if (EPI == EPI_RESID && nslices > 1) {
+        // split-K across workgroups: publish the partial tile (slice 0 carries the bias); the following norm
+        // kernel adds the slices into x in slice order
+        for (int e = wave; e < NTW * MT; e += NTW * ksplit) {
+            const int t = e / MT, i = e - t * MT;
+            const int m = 16 * i + fr, n = (nt0 + t) * 16 + 4 * fg;
+            if (m >= p.M || n >= p.N) continue;
+            f32x4 v = ksum(t, i);
+            if (p.bias && slice == 0) v += *(const f32x4*)(p.bias + n);    // N % 4 == 0 for residual widths
+            *(f32x4*)(p.sk_part + ((int64_t)slice * p.M + m) * p.N + n) = v;
+        }
+    } else if (EPI == EPI_RESID && p.rs_out) {
+        // x += alpha * (acc + bias) in place, and the deferred-RMSNorm operand + x^2 partials for the next projection
+        for (int e = wave; e < NTW * MT; e += NTW * ksplit) {
+            const int t = e / MT, i = e - t * MT;
+            const int m = 16 * (i + i_off) + fr, n = (nt0 + t) * 16 + 4 * fg;      // N % 16 == 0 (hidden width)
+            f32x4 v = ksum(t, i);
+            float ss = 0.f;
+            if (m < p.M && n < p.N && (!HALF || (fg >> 1) == half)) {
+                if (p.bias) v += *(const f32x4*)(p.bias + n);
+                float* x = (float*)p.C + (int64_t)m * p.ldc + n;
+                const f32x4 o = (e == wave ? x_pre : *(f32x4*)x) + p.alpha * v;
+                *(f32x4*)x = o;
+                act_store4<bf16_t>(p.nrm_xn, m, n, p.N, o * *(const f32x4*)(p.nrm_w + n));
+                ss = o[0] * o[0] + o[1] * o[1] + o[2] * o[2] + o[3] * o[3];
+            }
+            ss += __shfl_xor(ss, 16, 64);
+            if constexpr (HALF) {     // the two lane rows (fg = 2 half, 2 half + 1) of this workgroup's 8 columns
+                if (fg == 2 * half && (nt0 + t) * 16 < p.N) p.rs_out[(int64_t)m * (p.N >> 3) + 2 * (nt0 + t) + half] = ss;
+                continue;
+            }
+            ss += __shfl_xor(ss, 32, 64);
+            if (fg == 0 && (nt0 + t) * 16 < p.N) p.rs_out[(int64_t)m * (p.N >> 4) + (nt0 + t)] = ss;
+        }
+    } else {
+        for (int e = wave; e < NTW * MT; e += NTW * ksplit) {
+            const int t = e / MT, i = e - t * MT;
+            epilogue4<EPI, OutT>(p, 16 * i + fr, (nt0 + t) * 16 + 4 * fg, ksum(t, i),
+                                 EPI != EPI_STORE ? 1.0f : (RSTD_PRE && i == i_pre ? rstd_pre : deferred_rstd(p, 16 * i + fr)));
+        }
+    }
+}
+
+template <int MT, int NTW, int U, int EPI, typename OutT, bool PASSES = false, bool HALF = false>
+__global__ __launch_bounds__(1024) void gemm_skinny_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
+    gemm_skinny_body<MT, NTW, U, EPI, OutT, PASSES, false, HALF, true>(p, w_scale);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1109,6 +1364,129 @@ __global__ __launch_bounds__(512) void gemm_skinny_wide_bf16_kernel(GemmArgs p) 
     }
 }
 
+// fp8-weight form of the wide kernel (see gemm_skinny_body)
+template <int MT, int NTB, int U, int EPI, typename OutT, bool PASSES, bool MOE, bool W8>
+__device__ __forceinline__ void gemm_skinny_wide_body(GemmArgs p, const float* w_scale) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    f32x4* red = (f32x4*)smem;                       // [ksplit][NTB][MT][64]
+    const int swg = blockIdx.x;
+    NvlStamps stamps(p.stamps, swg);
+    const int tid = threadIdx.x, lane = tid & 63, kw = tid >> 6;
+    const int ksplit = blockDim.x >> 6;
+    const int fr = lane & 15, fg = lane >> 4;
+    int bx = blockIdx.x;
+    if constexpr (PASSES) skinny_pass_remap(p, bx);     // (its own instantiation: rewriting the arguments costs the
+                                                        // single-group kernels a few scratch dwords otherwise)
+    const int nt0 = bx * NTB;
+    if constexpr (MOE) { if (!moe_expert_live(p, (nt0 * 16) / (2 * p.moe_I))) return; }      // MoE decode: untouched expert (uniform)
+    const int nks = p.K >> 5, q = nks / ksplit, rr = nks - q * ksplit;
+    const int my_steps = q + (kw < rr ? 1 : 0);
+    const int ks0 = kw * q + (kw < rr ? kw : rr);
+    const int64_t tile_stride = (int64_t)nks * 512;  // elements between consecutive 16-row weight tiles
+    // deferred RMSNorm: the scale of the rows this wave's epilogue elements belong to, fetched under the weight stream
+    // (ahead of the first weight block: see the narrow kernel)
+    const int i_pre = kw % MT;
+    const float rstd_pre = (EPI == EPI_SWIGLU || EPI == EPI_STORE) ? deferred_rstd(p, 16 * i_pre + fr) : 1.0f;
+    const bf16_t* wp = (const bf16_t*)p.W + (((int64_t)nt0 * nks + ks0) * 64 + lane) * 8;
+    const uint8_t* wq = (const uint8_t*)p.W + (((int64_t)nt0 * nks + ks0) * 64 + lane) * 8;
+    float wsc[NTB];
+#pragma unroll
+    for (int t = 0; t < NTB; t++) wsc[t] = W8 ? w_scale[(nt0 + t) * 16 + fr] : 1.0f;
+    auto wload = [&](int t, int64_t s) -> bf16x8 { return w8_frag(weight_load8<PASSES>((const u32x2*)(wq + t * tile_stride + s * 512)), wsc[t]); };
+    typedef typename std::conditional<W8, u32x2, bf16x8>::type WReg;     // raw codes until the MFMAs (see gemm_skinny_body)
+    auto wfrag = [&](const WReg& w, int t) -> bf16x8 {
+        if constexpr (W8) return w8_frag(w, wsc[t]);
+        else return w;
+    };
+    const bf16_t* xp = (const bf16_t*)p.A + ((int64_t)ks0 * 64 + lane) * 8;
+    f32x4 acc[NTB][MT];
+#pragma unroll
+    for (int t = 0; t < NTB; t++)
+#pragma unroll
+        for (int i = 0; i < MT; i++) acc[t][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+    // (no row mask here, unlike the narrow kernel: this form runs at 17..64 rows, where at most one tile is ragged, and its
+    // 256-register budget is full — the predicated loads cost 6 more spilled registers and 2 us per FFN-up launch at B = 32)
+    const int nblk = my_steps / U;
+    WReg wA[U][NTB], wB[U][NTB];
+    bf16x8 xA[U][MT], xB[U][MT];
+    auto load_blk = [&](WReg (&w)[U][NTB], bf16x8 (&x)[U][MT], int b) {
+#pragma unroll
+        for (int u = 0; u < U; u++) {
+#pragma unroll
+            for (int t = 0; t < NTB; t++)
+                if constexpr (W8) w[u][t] = weight_load8<PASSES>((const u32x2*)(wq + t * tile_stride + (int64_t)(b * U + u) * 512));
+                else w[u][t] = weight_load<PASSES>((const bf16x8*)(wp + t * tile_stride + (int64_t)(b * U + u) * 512));
+#pragma unroll
+            for (int i = 0; i < MT; i++) x[u][i] = *(const bf16x8*)(xp + i * tile_stride + (int64_t)(b * U + u) * 512);
+        }
+    };
+    auto comp_blk = [&](WReg (&w)[U][NTB], bf16x8 (&x)[U][MT]) {
+#pragma unroll
+        for (int u = 0; u < U; u++)
+#pragma unroll
+            for (int t = 0; t < NTB; t++)
+#pragma unroll
+                for (int i = 0; i < MT; i++)
+                    acc[t][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wfrag(w[u][t], t), x[u][i], acc[t][i], 0, 0, 0);
+    };
+    if (nblk > 0) load_blk(wA, xA, 0);
+    stamps.mark(1);
+    int b = 0;
+    for (; b + 2 <= nblk; b += 2) {
+        load_blk(wB, xB, b + 1);
+        comp_blk(wA, xA);
+        if (b == 0) stamps.mark_used(2, acc[0][0]);
+        if (b + 2 < nblk) load_blk(wA, xA, b + 2);
+        comp_blk(wB, xB);
+    }
+    if (b < nblk) comp_blk(wA, xA);
+    for (int s = nblk * U; s < my_steps; s++) {      // ragged tail
+        bf16x8 xs[MT];
+#pragma unroll
+        for (int i = 0; i < MT; i++) xs[i] = *(const bf16x8*)(xp + i * tile_stride + (int64_t)s * 512);
+#pragma unroll
+        for (int t = 0; t < NTB; t++) {
+            const bf16x8 w = W8 ? wload(t, (int64_t)s) : weight_load<PASSES>((const bf16x8*)(wp + t * tile_stride + (int64_t)s * 512));
+#pragma unroll
+            for (int i = 0; i < MT; i++) acc[t][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, xs[i], acc[t][i], 0, 0, 0);
+        }
+    }
+
+#pragma unroll
+    for (int t = 0; t < NTB; t++)
+#pragma unroll
+        for (int i = 0; i < MT; i++) red[((kw * NTB + t) * MT + i) * 64 + lane] = acc[t][i];
+    stamps.mark(3);
+    __syncthreads();
+    stamps.mark(4);
+    auto ksum = [&](int t, int i) {
+        f32x4 s = red[(t * MT + i) * 64 + lane];
+        for (int w = 1; w < ksplit; w++) s += red[((w * NTB + t) * MT + i) * 64 + lane];
+        return s;
+    };
+    if (EPI == EPI_SWIGLU) {
+        // tiles come as [gate16 | up16] pairs of the same 16 features
+        for (int e = kw; e < (NTB / 2) * MT; e += ksplit) {
+            const int j = e / MT, i = e - j * MT;
+            const int f = ((nt0 >> 1) + j) * 16 + 4 * fg;
+            epilogue_swiglu4<OutT, MOE>(p, 16 * i + fr, f, ksum(2 * j, i), ksum(2 * j + 1, i),
+                                        i == i_pre ? rstd_pre : deferred_rstd(p, 16 * i + fr));
+        }
+    } else {
+        for (int e = kw; e < NTB * MT; e += ksplit) {
+            const int t = e / MT, i = e - t * MT;
+            epilogue4<EPI, OutT>(p, 16 * i + fr, (nt0 + t) * 16 + 4 * fg, ksum(t, i),
+                                 EPI != EPI_STORE ? 1.0f : (i == i_pre ? rstd_pre : deferred_rstd(p, 16 * i + fr)));
+        }
+    }
+}
+
+template <int MT, int NTB, int U, int EPI, typename OutT, bool PASSES = false>
+__global__ __launch_bounds__(512) void gemm_skinny_wide_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
+    gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, PASSES, false, true>(p, w_scale);
+}
+
 static int g_chunk_max_m = 512;    // largest M that uses 64-row passes of the decode form at all (nvl_set_tuning key 11; 64 = off)
 static int g_chunk_all_m = 64;     // up to here every projection does; above, only those whose 128x128 tile grid would
                                    // have fewer than g_chunk_min_tiles workgroups (keys 14, 12).  Measured: the mix wins
@@ -1124,15 +1502,15 @@ static int g_x_mask = 1;            // nvl_set_tuning key 24: decode kernels ski
 static int g_force_ntw = 0, g_force_ksplit = 0;   // tuning overrides (nvl_bench_gemm only)
 static int g_force_tile = 0;                      // 0 automatic, 1: 128x128x2st, 2: 256x128x3st, 3: 256x256x2st, 5: ping-pong 256x256
 
-template <int EPI, typename OutT>
-static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a);
+template <int EPI, typename OutT, bool W8 = false>
+static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a, const float* ws = nullptr);
 constexpr int DEFER_MAX_M = 128;    // deferred RMSNorm (decode): rows of the x^2 partial buffer.  Above 64 rows the producer
                                     // runs as 64-row groups like every narrow projection (one workgroup per 16-row tile
                                     // was measured at M = 128: -13 %); above 128 rows FFN-up belongs on the tile kernels
 static inline int skinny_rows(const GemmArgs& a) { return a.m_passes > 1 && a.M > 64 ? 64 : a.M; }   // rows a workgroup covers
 // the groups of 64 rows as separate launches (weight-block count not a multiple of 8, or key 13 = 0)
-template <int EPI, typename OutT>
-static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a) {
+template <int EPI, typename OutT, bool W8 = false>
+static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
     for (int r0 = 0; r0 < a.M; r0 += 64) {
         GemmArgs c = a;
         c.m_passes = 0;
@@ -1144,17 +1522,18 @@ static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a
             c.C = (float*)a.C + (int64_t)r0 * a.ldc; c.nrm_xn = a.nrm_xn + (int64_t)r0 * a.N;
             c.rs_out = a.rs_out + (int64_t)r0 * (a.N >> 4);
         }
-        if (!launch_gemm_skinny_bf16<EPI, OutT>(st, c)) return false;
+        if (!launch_gemm_skinny_bf16<EPI, OutT, W8>(st, c, ws)) return false;
     }
     return true;
 }
 
 // skinny dispatch: M <= 64, no gather/segments.  Returns false when the shape is not eligible.
-template <int NTW, int EPI, typename OutT>
-static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a) {
+// W8: the same decisions, the fp8-weight kernels (ws: the per-row weight scales).  MoE weights are never 8-bit.
+template <int NTW, int EPI, typename OutT, bool W8 = false>
+static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
     const int MT = skinny_rows(a) <= 16 ? 1 : (skinny_rows(a) <= 32 ? 2 : 4);
     if (EPI == EPI_RESID && a.m_split && a.rs_out && NTW == 1 && a.m_passes <= 1 && a.grid_y != 1) {   // (m_split: grid_y unused, keep it defined)
-        GemmArgs c = a; c.grid_y = 1; return launch_gemm_skinny_ntw<NTW, EPI, OutT>(st, c);
+        GemmArgs c = a; c.grid_y = 1; return launch_gemm_skinny_ntw<NTW, EPI, OutT, W8>(st, c, ws);
     }
     const int U = MT <= 2 ? 4 : 2;                       // register budget: (1+MT)*U*2 fragments
     const int nblocks = cdiv(cdiv(a.N, 16), NTW);        // weight rows are padded to 128: all tiles exist
@@ -1165,6 +1544,7 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a) {
         while (ks > 1 && (a.K >> 5) / ks < 4) ks >>= 1;
         if (a.K % 32 != 0) return false;
         if constexpr (EPI == EPI_RESID) {
+            if (a.moe_gate && W8) return false;     // (MoE weights are never 8-bit)
             if (a.moe_gate) {     // MoE down as the deferred-norm producer: all experts in one workgroup's K range, 16 waves
                 ks = 16;
                 const int nks = a.K >> 5, spe = a.moe_I >> 5;
@@ -1181,11 +1561,19 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a) {
             }
             if (a.rs_half) {      // <= 16 rows: 8 weight rows per workgroup, twice the workgroups (HALF above)
                 if (a.M > 16) return false;
+                if constexpr (W8)
+                    hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<1, NTW, 4, EPI, OutT, false, true>), dim3(2 * nblocks, 1), dim3(NTW * ks * 64),
+                                       (size_t)NTW * ks * 64 * 16, st, a, ws);
+                else
                 hipLaunchKernelGGL((gemm_skinny_bf16_kernel<1, NTW, 4, EPI, OutT, false, false, true>), dim3(2 * nblocks, 1), dim3(NTW * ks * 64),
                                    (size_t)NTW * ks * 64 * 16, st, a);
                 return true;
             }
         }
+        if constexpr (W8)
+            hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<1, NTW, 4, EPI, OutT>), dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64),
+                               (size_t)NTW * ks * 64 * 16, st, a, ws);
+        else
         hipLaunchKernelGGL((gemm_skinny_bf16_kernel<1, NTW, 4, EPI, OutT>), dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64),
                            (size_t)NTW * ks * 64 * 16, st, a);
         return true;
@@ -1207,9 +1595,17 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a) {
     }
     if (a.K % 32 != 0) return false;
     const size_t lds = (size_t)NTW * ksplit * MT * 64 * 16;
-    if (a.m_passes > 1 && (nblocks % 8 != 0 || KS != 1)) return launch_skinny_passes_serial<EPI, OutT>(st, a);
+    if (a.m_passes > 1 && (nblocks % 8 != 0 || KS != 1)) return launch_skinny_passes_serial<EPI, OutT, W8>(st, a, ws);
     dim3 grid(nblocks * (a.m_passes > 1 ? a.m_passes : 1), KS), block(NTW * ksplit * 64);
-    if (a.grid_y != KS) { GemmArgs c = a; c.grid_y = KS; return launch_gemm_skinny_ntw<NTW, EPI, OutT>(st, c); }
+    if (a.grid_y != KS) { GemmArgs c = a; c.grid_y = KS; return launch_gemm_skinny_ntw<NTW, EPI, OutT, W8>(st, c, ws); }
+    if constexpr (W8) {
+        if (a.moe_gate) return false;
+        if (a.m_passes > 1) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<4, NTW, 2, EPI, OutT, true>), grid, block, lds, st, a, ws);
+        else if (MT == 1) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<1, NTW, 4, EPI, OutT>), grid, block, lds, st, a, ws);
+        else if (MT == 2) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<2, NTW, 4, EPI, OutT>), grid, block, lds, st, a, ws);
+        else hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<4, NTW, 2, EPI, OutT>), grid, block, lds, st, a, ws);
+        return true;
+    } else {
 #define NVL_SK(MTv, Uv) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MTv, NTW, Uv, EPI, OutT>), grid, block, lds, st, a)
 #define NVL_SKM(MTv, Uv) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MTv, NTW, Uv, EPI, OutT, false, true>), grid, block, lds, st, a)
     if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
@@ -1224,6 +1620,7 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a) {
 #undef NVL_SK
 #undef NVL_SKM
     return true;
+    }
 }
 // Weight tiles per wave of the wide form (nvl_set_tuning key 36: 0 automatic, 2 / 4 forced).  Four tiles per wave quarter the
 // activation fetches per weight byte, but an FFN-up launch is then only 256 workgroups of 2 waves — 64 KiB of weights in
@@ -1231,10 +1628,10 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a) {
 // tok/s (+2.4 %), B=20 +3.1 %, Falcon-7B B=32 +4.7 %, Llama-3-8B / Granite B=32 +0.8 %; the LM head (thousands of groups
 // either way) is indifferent, and 64-row launches (MT = 4) lose 2 % (profiles/r03_wide_tiles_per_wave.txt).
 static int g_wide_ntb = 0;
-template <int EPI, typename OutT, int NTB = 4>
-static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a) {
+template <int EPI, typename OutT, int NTB = 4, bool W8 = false>
+static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
     if constexpr (NTB == 4) {
-        if (g_wide_ntb == 2 || (g_wide_ntb == 0 && skinny_rows(a) <= 32 && a.N < 65536)) return launch_gemm_skinny_wide<EPI, OutT, 2>(st, a);
+        if (g_wide_ntb == 2 || (g_wide_ntb == 0 && skinny_rows(a) <= 32 && a.N < 65536)) return launch_gemm_skinny_wide<EPI, OutT, 2, W8>(st, a, ws);
     }
     if (a.K % 32 != 0 || a.sk_part) return false;
     const int groups = cdiv(cdiv(a.N, 16), NTB);     // weight rows are padded to 256: every tile of a group exists
@@ -1248,8 +1645,20 @@ static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a) {
     else { while (ksplit > 2 && groups * ksplit > 512) ksplit >>= 1; if (groups >= 1024) ksplit = 1; }   // LM head: one wave per group (cold sweep: 96 vs 104 us)
     while (ksplit > 1 && (a.K >> 5) / ksplit < U) ksplit >>= 1;
     const size_t lds = (size_t)ksplit * NTB * MT * 64 * 16;
-    if (a.m_passes > 1 && groups % 8 != 0) return launch_skinny_passes_serial<EPI, OutT>(st, a);
+    if (a.m_passes > 1 && groups % 8 != 0) return launch_skinny_passes_serial<EPI, OutT, W8>(st, a, ws);
     const int wgs = groups * (a.m_passes > 1 ? a.m_passes : 1);
+    if constexpr (W8) {
+#define NVL_SKW8(MTv, Uv, Pv)                                                                                            \
+    do {                                                                                                               \
+        NVL_LDS_ATTR((gemm_skinny_wide_fp8w_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), 8 * NTB * MTv * 64 * 16);            \
+        hipLaunchKernelGGL((gemm_skinny_wide_fp8w_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), dim3(wgs), dim3(ksplit * 64),      \
+                           lds, st, a, ws);                                                                            \
+    } while (0)
+        if (a.moe_gate) return false;
+        if (a.m_passes > 1) NVL_SKW8(4, 2, true); else if (MT == 1) NVL_SKW8(1, 4, false); else if (MT == 2) NVL_SKW8(2, 4, false); else NVL_SKW8(4, 2, false);
+#undef NVL_SKW8
+        return true;
+    }
 #define NVL_SKW(MTv, Uv, Pv)                                                                                             \
     do {                                                                                                               \
         NVL_LDS_ATTR((gemm_skinny_wide_bf16_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), 8 * NTB * MTv * 64 * 16);            \
@@ -1274,8 +1683,8 @@ static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a) {
 #undef NVL_SKWM
     return true;
 }
-template <int EPI, typename OutT>
-static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a0) {
+template <int EPI, typename OutT, bool W8>
+static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a0, const float* ws) {
     if (EPI == EPI_QKV) return false;               // prefill-only epilogue (a decode workgroup owns 16 columns, not a head)
     if (skinny_rows(a0) > 64 || a0.a_rows || a0.seg || a0.tile_map) return false;
     GemmArgs a = a0;
@@ -1283,12 +1692,12 @@ static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a0) {
     if constexpr (EPI == EPI_SWIGLU || EPI == EPI_STORE || EPI == EPI_GELU) {
         // wide-N form once its 64-row groups fill the chip (g_force_ntw: 8 forces it, 1/2/4 force the narrow form)
         const bool wide_ok = skinny_rows(a) > 16 && cdiv(a.N, 64) >= 256 && !a.sk_part;   // M <= 16: the narrow form streams as fast
-        if (g_force_ntw == 8 || (g_force_ntw == 0 && wide_ok)) { if (launch_gemm_skinny_wide<EPI, OutT>(st, a)) return true; }
+        if (g_force_ntw == 8 || (g_force_ntw == 0 && wide_ok)) { if (launch_gemm_skinny_wide<EPI, OutT, 4, W8>(st, a, ws)) return true; }
     }
-    if (EPI == EPI_SWIGLU) return launch_gemm_skinny_ntw<2, EPI, OutT>(st, a);
-    if (g_force_ntw == 2) return launch_gemm_skinny_ntw<2, EPI, OutT>(st, a);
-    if (g_force_ntw == 4) return launch_gemm_skinny_ntw<4, EPI, OutT>(st, a);
-    return launch_gemm_skinny_ntw<1, EPI, OutT>(st, a);
+    if (EPI == EPI_SWIGLU) return launch_gemm_skinny_ntw<2, EPI, OutT, W8>(st, a, ws);
+    if (g_force_ntw == 2) return launch_gemm_skinny_ntw<2, EPI, OutT, W8>(st, a, ws);
+    if constexpr (!W8) { if (g_force_ntw == 4) return launch_gemm_skinny_ntw<4, EPI, OutT>(st, a); }   // (tuning only: no fp8 form)
+    return launch_gemm_skinny_ntw<1, EPI, OutT, W8>(st, a, ws);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int STAGES, int EPI, typename OutT>

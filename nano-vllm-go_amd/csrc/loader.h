@@ -144,7 +144,10 @@ inline bool exists(const std::string& path, bool* is_dir = nullptr) {
 // safetensors: 8-byte LE header length, JSON header {name: {dtype, shape, data_offsets}}, raw little-endian data
 // (generic_loader.go:184-199, loader.go:13-17)
 // ---------------------------------------------------------------------------------------------
-struct StTensor { const uint8_t* data = nullptr; int dtype = 0; std::vector<int64_t> shape; size_t bytes = 0; int64_t numel = 1; };
+constexpr int ST_F8_E4M3 = 100;     // loader-only dtype tag of an F8_E4M3 tensor (never passed to nvl_upload_tensor)
+// scale: an F8_E4M3 "<name>.weight"'s "<name>.weight_scale" (linked after every file is read), or NULL
+struct StTensor { const uint8_t* data = nullptr; int dtype = 0; std::vector<int64_t> shape; size_t bytes = 0; int64_t numel = 1;
+                  const StTensor* scale = nullptr; };
 
 struct StFile {
     int fd = -1; void* map = MAP_FAILED; size_t size = 0;
@@ -177,7 +180,8 @@ struct StSet {
             if (!dt || !sh || !off || off->arr.size() != 2) throw std::runtime_error(path + ": malformed entry " + kv.first);
             StTensor t;
             if (dt->str == "F32") t.dtype = NVL_DTYPE_F32; else if (dt->str == "BF16") t.dtype = NVL_DTYPE_BF16;
-            else if (dt->str == "F16") t.dtype = NVL_DTYPE_F16; else t.dtype = -1;      // refused only if the model needs it (:660-662)
+            else if (dt->str == "F16") t.dtype = NVL_DTYPE_F16; else if (dt->str == "F8_E4M3") t.dtype = ST_F8_E4M3;
+            else t.dtype = -1;      // refused only if the model needs it (:660-662)
             for (auto& d : sh->arr) {      // dimensions: non-negative integers whose product stays far inside int64
                 if (d.kind != JVal::NUM || !(d.num >= 0) || d.num > 4.0e12 || d.num != (double)(int64_t)d.num)
                     throw std::runtime_error(path + ": bad dimension in the shape of " + kv.first);
@@ -192,7 +196,7 @@ struct StSet {
             const size_t b = (size_t)off->arr[0].num, e = (size_t)off->arr[1].num;
             if (e < b || e > data_len) throw std::runtime_error(path + ": data_offsets of " + kv.first + " outside the file");
             t.data = data + b; t.bytes = e - b;
-            if (t.dtype >= 0 && t.bytes != (size_t)t.numel * (t.dtype == NVL_DTYPE_F32 ? 4 : 2))
+            if (t.dtype >= 0 && t.bytes != (size_t)t.numel * (t.dtype == NVL_DTYPE_F32 ? 4 : t.dtype == ST_F8_E4M3 ? 1 : 2))
                 throw std::runtime_error(path + ": byte size of " + kv.first + " does not match its shape");
             tensors[kv.first] = std::move(t);
         }
@@ -222,6 +226,18 @@ struct StSet {
         }
         add_file(path + "/model.safetensors");
     }
+    // FP8 checkpoints (compressed-tensors naming): "<name>.weight" F8_E4M3 + "<name>.weight_scale"; "input_scale" is ignored
+    // (activations stay bf16).  Run once after every file is added.
+    void link_scales() {
+        for (auto& kv : tensors) {
+            if (kv.second.dtype != ST_F8_E4M3) continue;
+            const std::string& n = kv.first;
+            if (n.size() > 7 && n.compare(n.size() - 7, 7, ".weight") == 0) {
+                auto it = tensors.find(n + "_scale");
+                if (it != tensors.end()) kv.second.scale = &it->second;
+            }
+        }
+    }
     const StTensor* find(const std::string& name) const {           // :619-632
         auto it = tensors.find(name);
         if (it == tensors.end()) it = tensors.find("transformer." + name);
@@ -235,7 +251,33 @@ struct StSet {
     }
 };
 
+inline float f32_of(const StTensor& t, int64_t i);
+// the per-row scales of an F8_E4M3 [N, K] weight: weight_scale F32 / BF16 of shape [N], [N, 1] or a scalar (broadcast);
+// anything else (block-wise [N/b, K/b], per-input-channel, ...) is refused
+inline std::vector<float> f8_row_scales(const StTensor& t, const std::string& what) {
+    if (t.shape.size() != 2) throw std::runtime_error("F8_E4M3 tensor " + what + ": a 2-D weight was expected");
+    if (!t.scale) throw std::runtime_error("F8_E4M3 tensor " + what + " has no weight_scale");
+    const StTensor& s = *t.scale;
+    if (s.dtype != NVL_DTYPE_F32 && s.dtype != NVL_DTYPE_BF16) throw std::runtime_error(what + "_scale: F32 or BF16 expected");
+    const int64_t N = t.shape[0];
+    const bool scalar = s.numel == 1 && s.shape.size() <= 2;
+    const bool per_row = (s.shape.size() == 1 && s.shape[0] == N) || (s.shape.size() == 2 && s.shape[0] == N && s.shape[1] == 1);
+    if (!scalar && !per_row)
+        throw std::runtime_error(what + "_scale: only per-output-channel ([N] or [N,1]) or scalar scales are supported (block-wise scales are not)");
+    std::vector<float> v((size_t)N);
+    for (int64_t r = 0; r < N; r++) {
+        v[(size_t)r] = f32_of(s, scalar ? 0 : r);
+        if (!(v[(size_t)r] > 0.f) || !std::isfinite(v[(size_t)r])) throw std::runtime_error(what + "_scale: scales must be finite and positive");
+    }
+    return v;
+}
 inline float f32_of(const StTensor& t, int64_t i) {                  // :769-805
+    if (t.dtype == ST_F8_E4M3) {         // W~ = bf16(s * e4m3(code)): what an 8-bit-weight model computes with
+        const int64_t K = t.shape.size() == 2 ? t.shape[1] : 1;
+        const float s = t.scale ? f32_of(*t.scale, t.scale->numel == 1 ? 0 : i / K) : 1.0f;
+        if ((t.data[i] & 0x7F) == 0x7F) throw std::runtime_error("F8_E4M3 tensor holds a NaN code");
+        return nvl::w8_value(t.data[i], s);
+    }
     if (t.dtype == NVL_DTYPE_F32) { float f; memcpy(&f, t.data + i * 4, 4); return f; }
     uint16_t h; memcpy(&h, t.data + i * 2, 2);
     uint32_t u;
@@ -259,12 +301,35 @@ inline float f32_of(const StTensor& t, int64_t i) {                  // :769-805
 namespace {
 using nvl_loader::StSet; using nvl_loader::StTensor; using nvl_loader::JVal;
 
+// an F8_E4M3 weight [N, K] with its row scales: as it is into a kind the model stores 8-bit (checkpoint order [out, in]),
+// else W~ = bf16(s * e4m3(q)) through nvl_upload_tensor (exact in bf16)
+void up2d_f8(nvl_model* m, int kind, int layer, const uint8_t* codes, const std::vector<float>& sc, int64_t N, int64_t K, int layout) {
+    for (int64_t i = 0; i < N * K; i++)
+        if ((codes[i] & 0x7F) == 0x7F) throw std::runtime_error("loader: F8_E4M3 weight holds a NaN code");
+    int rc;
+    if (w8_kind(m, kind) && (layout == NVL_LAYOUT_OUT_IN || kind == NVL_T_TOK_EMB)) {
+        rc = nvl_upload_tensor_fp8(m, kind, layer, codes, sc.data(), N, K, NVL_LAYOUT_OUT_IN);
+    } else {
+        std::vector<float> w((size_t)(N * K));
+        for (int64_t r = 0; r < N; r++)
+            for (int64_t k = 0; k < K; k++) w[(size_t)(r * K + k)] = nvl::w8_value(codes[r * K + k], sc[(size_t)r]);
+        rc = nvl_upload_tensor(m, kind, layer, w.data(), NVL_DTYPE_F32, N, K, layout);
+    }
+    if (rc) throw std::runtime_error(std::string("loader: ") + nvl_last_error(m));
+}
 void up2d(nvl_model* m, int kind, int layer, const StTensor& t, int layout) {
     if (t.shape.size() != 2) throw std::runtime_error("loader: a 2-D tensor was expected");
+    if (t.dtype == nvl_loader::ST_F8_E4M3) {
+        if (layout != NVL_LAYOUT_OUT_IN && kind != NVL_T_TOK_EMB)
+            throw std::runtime_error("loader: F8_E4M3 weights are supported in the [out, in] layout only");
+        up2d_f8(m, kind, layer, t.data, nvl_loader::f8_row_scales(t, "weight"), t.shape[0], t.shape[1], layout);
+        return;
+    }
     const int rc = nvl_upload_tensor(m, kind, layer, t.data, t.dtype, t.shape[0], t.shape[1], layout);
     if (rc) throw std::runtime_error(std::string("loader: ") + nvl_last_error(m));
 }
 void up1d(nvl_model* m, int kind, int layer, const StTensor& t) {
+    if (t.dtype == nvl_loader::ST_F8_E4M3) throw std::runtime_error("loader: an F8_E4M3 1-D tensor is not supported");
     const int rc = nvl_upload_tensor(m, kind, layer, t.data, t.dtype, t.numel, 1, NVL_LAYOUT_IN_OUT);
     if (rc) throw std::runtime_error(std::string("loader: ") + nvl_last_error(m));
 }
@@ -302,6 +367,7 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
     NVL_TRY(m)
     StSet st;
     st.open_path(path);
+    st.link_scales();
     const nvl_model_config& c = m->cfg;
     // which WeightMapping (:60-181) — told from the checkpoint's own names
     const bool gpt2 = st.find("wte.weight") != nullptr;
@@ -315,6 +381,8 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
         if (const StTensor* pe = st.find("wpe.weight")) up2d(m, NVL_T_POS_EMB, 0, *pe, IO);
         for (int l = 0; l < c.num_layers; l++) {
             const std::string p = "h." + std::to_string(l);
+            if (st.need(p + ".attn.c_attn.weight").dtype == nvl_loader::ST_F8_E4M3)
+                throw std::runtime_error("loader: F8_E4M3 weights are supported in the [out, in] layout only");
             const std::vector<float> w = to_f32(st.need(p + ".attn.c_attn.weight"));     // splitGPT2QKV (:674-702)
             std::vector<float> b;
             if (const StTensor* bt = st.find(p + ".attn.c_attn.bias")) b = to_f32(*bt);
@@ -394,7 +462,16 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
             } else {                                                           // loadFFN (:513-563): gate | up -> W1
                 const StTensor& g = st.need(p + ".mlp.gate_proj.weight");
                 const StTensor* u = st.find(p + ".mlp.up_proj.weight");
-                if (u) {
+                if (u && g.dtype == nvl_loader::ST_F8_E4M3) {                 // 8-bit pair: codes and row scales side by side
+                    if (u->dtype != g.dtype || u->shape != g.shape || g.shape.size() != 2) throw std::runtime_error("gate_proj / up_proj mismatch");
+                    std::vector<uint8_t> cat(g.bytes + u->bytes);
+                    memcpy(cat.data(), g.data, g.bytes);
+                    memcpy(cat.data() + g.bytes, u->data, u->bytes);
+                    std::vector<float> sc = nvl_loader::f8_row_scales(g, p + ".mlp.gate_proj.weight");
+                    const std::vector<float> su = nvl_loader::f8_row_scales(*u, p + ".mlp.up_proj.weight");
+                    sc.insert(sc.end(), su.begin(), su.end());
+                    up2d_f8(m, NVL_T_W1, l, cat.data(), sc, 2 * g.shape[0], g.shape[1], OI);
+                } else if (u) {
                     if (u->dtype != g.dtype || u->shape != g.shape || g.shape.size() != 2) throw std::runtime_error("gate_proj / up_proj mismatch");
                     std::vector<uint8_t> cat(g.bytes + u->bytes);              // [2F, H] in the checkpoint's dtype == ([H, F] | [H, F])^T
                     memcpy(cat.data(), g.data, g.bytes);

@@ -16,6 +16,7 @@
 #include "elem.h"
 #include "sample.h"
 #include "gemm.h"
+#include "w8.h"
 #include "mamba.h"
 #include "tp_p2p.h"
 
@@ -23,6 +24,7 @@ namespace nvl {
 
 struct DevTensor {
     void* p = nullptr;      // canonical device copy: 2-D [rows_pad][cols] in weight dtype, 1-D fp32
+    float* scale = nullptr; // 8-bit weights (w8.h): p holds e4m3fn codes, scale[rows_pad] the per-row fp32 scales
     int64_t rows = 0, cols = 0, rows_pad = 0;
     bool present() const { return p != nullptr; }
 };
@@ -32,6 +34,7 @@ struct LayerW {
     // frozen by finalize()
     void* w_qkv = nullptr; int n_qkv = 0; float* b_qkv = nullptr;
     void* w1 = nullptr; int n1 = 0;      // fused rows (2F for SwiGLU, F for GELU)
+    float* s_qkv = nullptr; float* s1 = nullptr;   // 8-bit weights: the row scales of w_qkv / w1 (they follow the fused rows)
     void* moe_in = nullptr;              // [E][2I (interleaved in bf16 mode)][H]
     void* moe_out_cat = nullptr;         // bf16: W_down of all experts along K, [H_pad][E*I] (decode "dense-masked" form)
     bool mamba = false;                  // a Mamba2 block (attention tensors absent); index among the Mamba2 layers
@@ -79,6 +82,13 @@ struct nvl_model {
     int kv_esize = 2;                      // bytes per cached K/V element (wsize, or 1 in 8-bit mode)
     std::vector<float> k_scale, v_scale;   // [num_layers], default 1 (Mamba2 layers' entries unused)
     bool kv_written = false;               // a forward has been enqueued: the scales are fixed from then on
+    // 8-bit projection weights (nvl_set_weight_dtype NVL_W_FP8_E4M3, w8.h): e4m3fn codes + per-row fp32 scales
+    bool w8 = false;
+    bool w2d_uploaded = false;             // a 2-D tensor has been uploaded: the weight dtype is fixed from then on
+    struct W8Ref { const float* scale; int64_t rows_pad; };
+    std::map<const void*, W8Ref> w8_map;   // finalized 8-bit weights by code pointer (gemm() dispatch)
+    nvl::bf16_t* w8_scratch = nullptr; int64_t w8_scratch_elems = 0;   // W~ of the tile path (largest non-LM-head projection)
+    float* lm_head_scale = nullptr;
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;

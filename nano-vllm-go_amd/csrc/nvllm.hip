@@ -153,10 +153,32 @@ unsigned long long* next_stamps(nvl_model* m, int site, int nwg) {
 void gemm(nvl_model* m, int epi, bool out_f32, GemmArgs a, double flops = -1.0) {
     a.stamps = (m->stamping && !m->f32 && a.M <= 64 && !a.tile_map) ? next_stamps(m, m->site, STAMP_MAX_WG) : nullptr;
     // algorithmic bytes of a projection: every weight byte once + the activation operand + the output rows
+    const bool w8 = m->w8 && m->w8_map.count(a.W);     // 8-bit weight: one byte per element + the row scales
     const double gbytes = m->site_bytes > 0 ? m->site_bytes
-        : ((double)a.N * a.K + (double)a.M * a.K) * (double)m->wsize + (double)a.M * a.N * (out_f32 || epi == EPI_RESID ? 4.0 : (double)m->wsize);
+        : (double)a.N * a.K * (w8 ? 1.0 : (double)m->wsize) + (w8 ? 4.0 * a.N : 0.0) + (double)a.M * a.K * (double)m->wsize
+          + (double)a.M * a.N * (out_f32 || epi == EPI_RESID ? 4.0 : (double)m->wsize);
     KScope ks(m, KC_GEMM, flops >= 0 ? flops : 2.0 * (double)a.M * (double)a.N * (double)a.K, -1, gbytes);
     hipStream_t st = m->stream;
+    if (m->w8) {
+        const auto it = m->w8_map.find(a.W);
+        if (it != m->w8_map.end()) {     // an 8-bit weight (w8.h): the same dispatch on the fp8-weight kernels / dequantize + tile
+            const float* ws = it->second.scale;
+            const int64_t rp = it->second.rows_pad;
+            switch (epi) {
+                case EPI_STORE:
+                    if (out_f32) launch_gemm_w8<EPI_STORE, float>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems);
+                    else launch_gemm_w8<EPI_STORE, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems);
+                    break;
+                case EPI_RESID:  launch_gemm_w8<EPI_RESID, float>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems); break;
+                case EPI_SWIGLU: launch_gemm_w8<EPI_SWIGLU, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems); break;
+                case EPI_GELU:   launch_gemm_w8<EPI_GELU, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems); break;
+                case EPI_QKV:    launch_gemm_w8<EPI_QKV, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems); break;
+                default: throw std::runtime_error("gemm: bad epilogue");
+            }
+            NVL_HIP(hipGetLastError());
+            return;
+        }
+    }
     if (m->f32) {
         switch (epi) {
             case EPI_STORE: launch_gemm_f32<EPI_STORE, float>(st, a); break;
@@ -329,11 +351,13 @@ extern "C" void nvl_destroy(nvl_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
-    for (int k = 0; k < NVL_T_COUNT; k++) dfree(m->g[k].p);
+    for (int k = 0; k < NVL_T_COUNT; k++) { dfree(m->g[k].p); dfree(m->g[k].scale); }
     for (auto& l : m->layers) {
-        for (int k = 0; k < NVL_T_COUNT; k++) dfree(l.t[k].p);
+        for (int k = 0; k < NVL_T_COUNT; k++) { dfree(l.t[k].p); dfree(l.t[k].scale); }
         dfree(l.w_qkv); dfree(l.b_qkv); dfree(l.w1); dfree(l.moe_in); dfree(l.moe_out_cat);
+        dfree(l.s_qkv); dfree(l.s1);
     }
+    dfree(m->w8_scratch);
     if (m->lm_head && m->lm_head != m->g[NVL_T_TOK_EMB].p && m->lm_head != m->g[NVL_T_LM_HEAD].p) dfree(m->lm_head);
     dfree(m->rope_cos); dfree(m->rope_sin); dfree(m->kcache); dfree(m->vcache);
     dfree(m->x); dfree(m->xn); dfree(m->qkv); dfree(m->q); dfree(m->attn_out); dfree(m->attn_part); dfree(m->attn_part_cnt); dfree(m->hbuf); dfree(m->h2);
@@ -372,6 +396,55 @@ namespace {
 // canonical device copy: 2-D -> [rows_pad(W_ROW_PAD)][K] in weight dtype; 1-D -> fp32.
 // `sl` selects the sub-block of the uploaded tensor that lands in rows [dn0, dn0+N) (the whole tensor for
 // replicated kinds, this rank's shard for tensor-parallel kinds); total_rows sizes the destination.
+// is this 2-D kind stored 8-bit in an fp8-weight model?  The projections and the LM head; the token embedding only when it
+// is the (tied) LM head too.  Position embedding, router, MoE experts and Mamba2 projections stay bf16.
+bool w8_kind(const nvl_model* m, int kind) {
+    if (!m->w8) return false;
+    switch (kind) {
+        case NVL_T_WQ: case NVL_T_WK: case NVL_T_WV: case NVL_T_WKV: case NVL_T_WO: case NVL_T_W1: case NVL_T_W2:
+        case NVL_T_LM_HEAD: return true;
+        case NVL_T_TOK_EMB: return m->cfg.tied_embedding != 0;
+        default: return false;
+    }
+}
+
+// codes [Npad][K] zeroed, scales [Npad] = 1 (pad rows)
+void w8_alloc(nvl_model* m, DevTensor* t, int64_t Npad, int64_t K) {
+    dfree(t->p); dfree(t->scale);
+    t->p = dmalloc_bytes(Npad * K);
+    t->scale = dmalloc<float>(Npad);
+    NVL_HIP(hipMemsetAsync(t->p, 0, (size_t)(Npad * K), m->stream));
+    const std::vector<float> ones((size_t)Npad, 1.0f);
+    NVL_HIP(hipMemcpy(t->scale, ones.data(), (size_t)Npad * 4, hipMemcpyHostToDevice));   // (synchronous: `ones` is pageable and local)
+}
+
+// 8-bit weight (tensor parallelism is refused in this mode: the tensor is always whole, one piece): fp32 [N][K] on the
+// device, then w8_quant_rows_kernel -> codes [Npad][K] (fragment-major bytes) + scales [Npad]
+void upload_2d_w8(nvl_model* m, DevTensor* t, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out) {
+    if (K % 32 != 0) throw std::runtime_error("8-bit weights: the input width must be a multiple of 32");
+    const size_t esz = dtype == NVL_DTYPE_F32 ? 4 : 2;
+    void* raw = dmalloc_bytes(N * K * (int64_t)esz);
+    NVL_HIP(hipMemcpyAsync(raw, data, (size_t)(N * K) * esz, hipMemcpyDefault, m->stream));
+    float* f = dmalloc<float>(N * K);
+    hipLaunchKernelGGL((convert_2d_kernel<float, false>), dim3((unsigned)cdiv(K, 32), (unsigned)cdiv(N, 32)), dim3(256), 0,
+                       m->stream, raw, dtype, src_is_in_out ? 1 : 0, f, N, K, Slice2D{N, K, 0, 0, 0});
+    NVL_HIP(hipGetLastError());
+    const int64_t Npad = round_up(N, W_ROW_PAD);
+    w8_alloc(m, t, Npad, K);
+    int* bad = dmalloc<int>(1);
+    NVL_HIP(hipMemsetAsync(bad, 0, 4, m->stream));
+    hipLaunchKernelGGL(w8_quant_rows_kernel, dim3((unsigned)N), dim3(256), 0, m->stream, (const float*)f, K, (uint8_t*)t->p, t->scale, bad);
+    NVL_HIP(hipGetLastError());
+    int h_bad = 0;
+    NVL_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, m->stream));
+    NVL_HIP(hipStreamSynchronize(m->stream));
+    dfree(bad); dfree(f); dfree(raw);
+    t->rows = N; t->cols = K; t->rows_pad = Npad;
+    if (h_bad) { dfree(t->p); dfree(t->scale); t->p = nullptr; t->scale = nullptr;
+                 throw std::runtime_error("nvl_upload_tensor: a weight is not finite (8-bit weights refuse NaN / Inf)"); }
+    m->stats.weight_bytes += (double)Npad * K + (double)Npad * 4;
+}
+
 void upload_2d(nvl_model* m, DevTensor* t, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out,
                Slice2D sl, int64_t total_rows, bool first_piece) {
     const size_t esz = dtype == NVL_DTYPE_F32 ? 4 : 2;
@@ -486,7 +559,9 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
                      (long long)cols, (long long)want_rows, m->H);
             return fail(m, NVL_ERR_INVALID, buf);
         }
-        upload_2d(m, t, data, dtype, rows, cols, false, Slice2D{rows, cols, 0, 0, 0}, rows, true);
+        m->w2d_uploaded = true;
+        if (w8_kind(m, kind)) upload_2d_w8(m, t, data, dtype, rows, cols, false);
+        else upload_2d(m, t, data, dtype, rows, cols, false, Slice2D{rows, cols, 0, 0, 0}, rows, true);
         return NVL_OK;
     }
     if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {
@@ -498,6 +573,7 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
                      (long long)cols, (long long)out, (long long)in);
             return fail(m, NVL_ERR_INVALID, buf);
         }
+        m->w2d_uploaded = true;
         upload_2d(m, t, data, dtype, rows, cols, false, Slice2D{rows, cols, 0, 0, 0}, rows, true);
         return NVL_OK;
     }
@@ -512,6 +588,11 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
         return fail(m, NVL_ERR_INVALID, buf);
     }
     const bool io = layout == NVL_LAYOUT_IN_OUT;
+    m->w2d_uploaded = true;
+    if (w8_kind(m, kind)) {     // (tp == 1: nvl_set_weight_dtype refuses tensor parallelism)
+        upload_2d_w8(m, t, data, dtype, SN, SK, io);
+        return NVL_OK;
+    }
     if (m->tp == 1) {
         upload_2d(m, t, data, dtype, SN, SK, io, Slice2D{SN, SK, 0, 0, 0}, SN, true);
         return NVL_OK;
@@ -538,6 +619,45 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
         default:                                            // LM head etc.: replicated
             upload_2d(m, t, data, dtype, SN, SK, io, Slice2D{SN, SK, 0, 0, 0}, SN, true);
     }
+    return NVL_OK;
+    NVL_CATCH(m)
+}
+
+// pre-quantized 8-bit weight: codes [rows][cols] (OUT_IN: the checkpoint's [out, in]) and scales [rows], taken as they are
+extern "C" int nvl_upload_tensor_fp8(nvl_model* m, int kind, int layer, const uint8_t* codes, const float* scales,
+                                     int64_t rows, int64_t cols, int layout) {
+    if (!m || !codes || !scales) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: null argument");
+    if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_upload_tensor_fp8: model already finalized");
+    if (!w8_kind(m, kind)) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: not an 8-bit weight kind of this model (nvl_set_weight_dtype)");
+    if (layout != NVL_LAYOUT_OUT_IN) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
+    DevTensor* t = tensor_slot(m, kind, layer);
+    if (!t) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: bad kind or layer");
+    const int64_t SN = kind == NVL_T_TOK_EMB ? m->V : full_out(m, kind), SK = kind == NVL_T_TOK_EMB ? m->H : full_in(m, kind);
+    if (rows != SN || cols != SK || SK % 32 != 0) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "nvl_upload_tensor_fp8: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld]", kind,
+                 (long long)rows, (long long)cols, (long long)SN, (long long)SK);
+        return fail(m, NVL_ERR_INVALID, buf);
+    }
+    for (int64_t i = 0; i < rows * cols; i++)
+        if ((codes[i] & 0x7F) == 0x7F) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: NaN code (0x7f / 0xff)");
+    for (int64_t r = 0; r < rows; r++)
+        if (!(scales[r] > 0.f) || !std::isfinite(scales[r])) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: scales must be finite and positive");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    m->w2d_uploaded = true;
+    const int64_t Npad = round_up(rows, W_ROW_PAD);
+    w8_alloc(m, t, Npad, cols);
+    uint8_t* raw = (uint8_t*)dmalloc_bytes(rows * cols);
+    NVL_HIP(hipMemcpy(raw, codes, (size_t)(rows * cols), hipMemcpyHostToDevice));
+    NVL_HIP(hipMemcpy(t->scale, scales, (size_t)rows * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(w8_place_kernel, dim3((unsigned)cdiv(rows * cols / 4, 256)), dim3(256), 0, m->stream, (const uint8_t*)raw, rows,
+                       cols, (uint8_t*)t->p);
+    NVL_HIP(hipGetLastError());
+    NVL_HIP(hipStreamSynchronize(m->stream));
+    dfree(raw);
+    t->rows = rows; t->cols = cols; t->rows_pad = Npad;
+    m->stats.weight_bytes += (double)Npad * cols + (double)Npad * 4;
     return NVL_OK;
     NVL_CATCH(m)
 }
@@ -625,6 +745,54 @@ std::vector<int32_t> swiglu_interleave(int64_t F, int64_t src_base) {
     return idx;
 }
 
+// gather_rows for an 8-bit weight: the codes move as 16-row tiles (16*K bytes) and the scales with them; pad rows
+// (idx < 0) get codes 0 and scale 1
+void gather_rows_w8(nvl_model* m, const DevTensor& src, const std::vector<int32_t>& idx, void* dst, float* dst_scale, int64_t K) {
+    if (idx.size() % 16) throw std::runtime_error("gather_rows: row count must be a multiple of 16");
+    std::vector<int32_t> use(idx.size() / 16);
+    for (size_t t = 0; t < use.size(); t++) {
+        const int32_t r0 = idx[t * 16];
+        for (int c = 1; c < 16; c++)
+            if ((r0 < 0) != (idx[t * 16 + c] < 0) || (r0 >= 0 && (idx[t * 16 + c] != r0 + c || (r0 & 15))))
+                throw std::runtime_error("gather_rows: permutation does not preserve 16-row tiles");
+        use[t] = r0 < 0 ? -1 : r0 / 16;
+    }
+    std::vector<float> sc(idx.size()), ssrc((size_t)src.rows_pad);
+    NVL_HIP(hipMemcpy(ssrc.data(), src.scale, ssrc.size() * 4, hipMemcpyDeviceToHost));
+    for (size_t r = 0; r < idx.size(); r++) sc[r] = idx[r] < 0 ? 1.0f : ssrc[(size_t)idx[r]];
+    int32_t* didx = dmalloc<int32_t>((int64_t)use.size());
+    NVL_HIP(hipMemcpyAsync(didx, use.data(), use.size() * 4, hipMemcpyHostToDevice, m->stream));
+    NVL_HIP(hipMemcpyAsync(dst_scale, sc.data(), sc.size() * 4, hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL((gather_rows_kernel<uint8_t>), dim3((unsigned)use.size()), dim3(256), 0, m->stream,
+                       (const uint8_t*)src.p, didx, (uint8_t*)dst, 16 * K);
+    NVL_HIP(hipGetLastError());
+    NVL_HIP(hipStreamSynchronize(m->stream));
+    dfree(didx);
+}
+// the fused FFN-up weight of a layer (SwiGLU: gate|up rows interleaved in blocks of 16)
+void fuse_w1(nvl_model* m, LayerW& l, bool swiglu) {
+    const int64_t H = m->H;
+    if (swiglu && !m->f32) {
+        auto idx = swiglu_interleave(m->F, 0);
+        const int64_t np = round_up(l.n1, W_ROW_PAD);
+        idx.resize((size_t)np, -1);
+        if (l.t[NVL_T_W1].scale) {
+            l.w1 = dmalloc_bytes(np * H);
+            l.s1 = dmalloc<float>(np);
+            gather_rows_w8(m, l.t[NVL_T_W1], idx, l.w1, l.s1, H);
+            dfree(l.t[NVL_T_W1].scale); l.t[NVL_T_W1].scale = nullptr;
+        } else {
+            l.w1 = dmalloc_bytes(np * H * (int64_t)m->wsize);
+            gather_rows(m, l.t[NVL_T_W1].p, idx, l.w1, H);
+        }
+        dfree(l.t[NVL_T_W1].p); l.t[NVL_T_W1].p = nullptr;
+    } else {
+        l.w1 = l.t[NVL_T_W1].p; l.t[NVL_T_W1].p = nullptr;
+        l.s1 = l.t[NVL_T_W1].scale; l.t[NVL_T_W1].scale = nullptr;
+    }
+}
+
+
 }  // namespace
 
 extern "C" int nvl_set_kv_scales(nvl_model* m, const float* k_scale, const float* v_scale) {
@@ -642,6 +810,18 @@ extern "C" int nvl_set_kv_scales(nvl_model* m, const float* k_scale, const float
     for (int l = 0; l < m->L; l++)        // (Mamba2 entries are not used; keep them valid)
         if (!(m->k_scale[(size_t)l] > 0.f) || !(m->v_scale[(size_t)l] > 0.f) || !std::isfinite(m->k_scale[(size_t)l]) || !std::isfinite(m->v_scale[(size_t)l]))
             m->k_scale[(size_t)l] = m->v_scale[(size_t)l] = 1.0f;
+    return NVL_OK;
+}
+
+extern "C" int nvl_set_weight_dtype(nvl_model* m, int dtype) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_weight_dtype: no model");
+    if (m->finalized || m->w2d_uploaded)
+        return fail(m, NVL_ERR_STATE, "nvl_set_weight_dtype: call it after nvl_create and before the first 2-D weight upload");
+    if (dtype != NVL_W_AUTO && dtype != NVL_W_FP8_E4M3) return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: unknown weight dtype");
+    if (dtype == NVL_W_FP8_E4M3 && m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights need bf16 precision");
+    if (dtype == NVL_W_FP8_E4M3 && (m->tp > 1 || m->tp_force))
+        return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights are not available with tensor parallelism");
+    m->w8 = dtype == NVL_W_FP8_E4M3;
     return NVL_OK;
 }
 
@@ -666,16 +846,7 @@ extern "C" int nvl_finalize(nvl_model* m) {
             need(l.t[NVL_T_FFN_NORM_W].present() && l.t[NVL_T_W1].present() && l.t[NVL_T_W2].present(), "Mamba2 block: FFN norm / shared MLP");
             const bool swiglu = c.activation_type == NVL_ACT_SWIGLU;
             l.n1 = swiglu ? 2 * m->F : m->F;
-            if (swiglu && !m->f32) {
-                auto idx = swiglu_interleave(m->F, 0);
-                const int64_t np = round_up(l.n1, W_ROW_PAD);
-                idx.resize((size_t)np, -1);
-                l.w1 = dmalloc_bytes(np * H * (int64_t)m->wsize);
-                gather_rows(m, l.t[NVL_T_W1].p, idx, l.w1, H);
-                dfree(l.t[NVL_T_W1].p); l.t[NVL_T_W1].p = nullptr;
-            } else {
-                l.w1 = l.t[NVL_T_W1].p; l.t[NVL_T_W1].p = nullptr;
-            }
+            fuse_w1(m, l, swiglu);
             continue;
         }
         need(l.t[NVL_T_WQ].present() && l.t[NVL_T_WO].present(), "attention Q/O projection");
@@ -686,10 +857,24 @@ extern "C" int nvl_finalize(nvl_model* m) {
         // ---- fused QKV [n_qkv_pad][H]: rows Q | K | V (canonical rows are contiguous: plain copies)
         const int64_t nq = (int64_t)m->nH * hd, nkv = (int64_t)m->nKV * hd;
         const int64_t npad = round_up(m->n_qkv, W_ROW_PAD);
-        l.w_qkv = dmalloc_bytes(npad * H * (int64_t)m->wsize);
-        NVL_HIP(hipMemsetAsync(l.w_qkv, 0, (size_t)(npad * H) * m->wsize, m->stream));
+        const bool q8 = l.t[NVL_T_WQ].scale != nullptr;    // 8-bit weights: codes move like bf16 rows, scales beside them
+        const size_t we = q8 ? 1 : m->wsize;
+        l.w_qkv = dmalloc_bytes(npad * H * (int64_t)we);
+        NVL_HIP(hipMemsetAsync(l.w_qkv, 0, (size_t)(npad * H) * we, m->stream));
         char* dst = (char*)l.w_qkv;
-        const size_t rowb = (size_t)H * m->wsize;
+        const size_t rowb = (size_t)H * we;
+        if (q8) {
+            l.s_qkv = dmalloc<float>(npad);
+            const std::vector<float> ones((size_t)npad, 1.0f);
+            NVL_HIP(hipMemcpy(l.s_qkv, ones.data(), (size_t)npad * 4, hipMemcpyHostToDevice));   // (synchronous: pageable, local)
+            NVL_HIP(hipMemcpyAsync(l.s_qkv, l.t[NVL_T_WQ].scale, nq * 4, hipMemcpyDeviceToDevice, m->stream));
+            if (mqa) {
+                NVL_HIP(hipMemcpyAsync(l.s_qkv + nq, l.t[NVL_T_WKV].scale, 2 * hd * 4, hipMemcpyDeviceToDevice, m->stream));
+            } else {
+                NVL_HIP(hipMemcpyAsync(l.s_qkv + nq, l.t[NVL_T_WK].scale, nkv * 4, hipMemcpyDeviceToDevice, m->stream));
+                NVL_HIP(hipMemcpyAsync(l.s_qkv + nq + nkv, l.t[NVL_T_WV].scale, nkv * 4, hipMemcpyDeviceToDevice, m->stream));
+            }
+        }
         NVL_HIP(hipMemcpyAsync(dst, l.t[NVL_T_WQ].p, nq * rowb, hipMemcpyDeviceToDevice, m->stream));
         if (mqa) {
             NVL_HIP(hipMemcpyAsync(dst + nq * rowb, l.t[NVL_T_WKV].p, 2 * hd * rowb, hipMemcpyDeviceToDevice, m->stream));
@@ -706,7 +891,7 @@ extern "C" int nvl_finalize(nvl_model* m) {
             if (l.t[NVL_T_BV].present()) NVL_HIP(hipMemcpyAsync(l.b_qkv + nq + nkv, l.t[NVL_T_BV].p, nkv * 4, hipMemcpyDeviceToDevice, m->stream));
         }
         NVL_HIP(hipStreamSynchronize(m->stream));
-        for (int k : {NVL_T_WQ, NVL_T_WK, NVL_T_WV, NVL_T_WKV}) { dfree(l.t[k].p); l.t[k].p = nullptr; }
+        for (int k : {NVL_T_WQ, NVL_T_WK, NVL_T_WV, NVL_T_WKV}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].scale); l.t[k].scale = nullptr; }
 
         // ---- FFN / MoE
         if (c.use_moe) {
@@ -740,21 +925,33 @@ extern "C" int nvl_finalize(nvl_model* m) {
             need(l.t[NVL_T_W1].present() && l.t[NVL_T_W2].present(), "FFN weights");
             const bool swiglu = c.activation_type == NVL_ACT_SWIGLU;
             l.n1 = swiglu ? 2 * m->F : m->F;
-            if (swiglu && !m->f32) {
-                auto idx = swiglu_interleave(m->F, 0);
-                const int64_t np = round_up(l.n1, W_ROW_PAD);
-                idx.resize((size_t)np, -1);
-                l.w1 = dmalloc_bytes(np * H * (int64_t)m->wsize);
-                gather_rows(m, l.t[NVL_T_W1].p, idx, l.w1, H);
-                dfree(l.t[NVL_T_W1].p); l.t[NVL_T_W1].p = nullptr;
-            } else {
-                l.w1 = l.t[NVL_T_W1].p; l.t[NVL_T_W1].p = nullptr;
-            }
+            fuse_w1(m, l, swiglu);
         }
     }
     // ---- LM head: tied (or absent) => the token embedding itself, already [Vpad][H] K-contiguous
-    if (!c.tied_embedding && m->g[NVL_T_LM_HEAD].present()) m->lm_head = m->g[NVL_T_LM_HEAD].p;
-    else m->lm_head = m->g[NVL_T_TOK_EMB].p;   // generic_loader.go:255-259
+    if (!c.tied_embedding && m->g[NVL_T_LM_HEAD].present()) { m->lm_head = m->g[NVL_T_LM_HEAD].p; m->lm_head_scale = m->g[NVL_T_LM_HEAD].scale; }
+    else { m->lm_head = m->g[NVL_T_TOK_EMB].p; m->lm_head_scale = m->g[NVL_T_TOK_EMB].scale; }   // generic_loader.go:255-259
+    if (m->w8) {   // the 8-bit weights by code pointer (gemm() dispatch) and the dequantize scratch of the tile path
+        int64_t big = 0;
+        auto reg = [&](const void* p, const float* s, int64_t rows) {
+            if (!p || !s) return;
+            m->w8_map[p] = nvl_model::W8Ref{s, round_up(rows, W_ROW_PAD)};
+        };
+        for (auto& l : m->layers) {
+            reg(l.w_qkv, l.s_qkv, l.n_qkv); reg(l.w1, l.s1, l.n1);
+            reg(l.t[NVL_T_WO].p, l.t[NVL_T_WO].scale, H); reg(l.t[NVL_T_W2].p, l.t[NVL_T_W2].scale, H);
+            if (l.s_qkv) big = std::max(big, round_up(l.n_qkv, W_ROW_PAD) * H);
+            if (l.s1) big = std::max(big, round_up(l.n1, W_ROW_PAD) * H);
+            if (l.t[NVL_T_WO].scale) big = std::max(big, l.t[NVL_T_WO].rows_pad * l.t[NVL_T_WO].cols);
+            if (l.t[NVL_T_W2].scale) big = std::max(big, l.t[NVL_T_W2].rows_pad * l.t[NVL_T_W2].cols);
+        }
+        if (m->lm_head_scale) {
+            reg(m->lm_head, m->lm_head_scale, m->V);
+            big = std::max(big, W_ROW_PAD * H);      // (at least one row tile of the LM head: it runs in chunks)
+        }
+        m->w8_scratch_elems = big;
+        if (big) m->w8_scratch = dmalloc<bf16_t>(big);
+    }
 
     // ---- RoPE tables in fp64 on the host, exactly as NewRoPECache (rope.go:18-50)
     bool rope = false; double base = c.rope_base;
@@ -1705,6 +1902,10 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
         if (m->f32)
             hipLaunchKernelGGL((embed_kernel<float, false>), dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
                                (const float*)m->g[NVL_T_TOK_EMB].p, (const float*)pe, pe_rows, c.embedding_multiplier, m->x, H);
+        else if (m->g[NVL_T_TOK_EMB].scale)     // 8-bit tied table (w8.h)
+            hipLaunchKernelGGL(embed_w8_kernel, dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
+                               (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const float*)m->g[NVL_T_TOK_EMB].scale, (const bf16_t*)pe, pe_rows,
+                               c.embedding_multiplier, m->x, H);
         else
             hipLaunchKernelGGL((embed_kernel<bf16_t, true>), dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
                                (const bf16_t*)m->g[NVL_T_TOK_EMB].p, (const bf16_t*)pe, pe_rows, c.embedding_multiplier, m->x, H);
@@ -2241,13 +2442,22 @@ void decode_loop(nvl_model* m, const Meta& hm, int n_seqs, int n_steps, int32_t*
             const void* pe = (m->cfg.position_type == NVL_POS_LEARNED) ? m->g[NVL_T_POS_EMB].p : nullptr;
             const int pe_rows = pe ? (int)std::min<int64_t>(m->g[NVL_T_POS_EMB].rows, m->cfg.max_seq_len) : 0;
             const LayerW& l0 = m->layers[0];
-            hipLaunchKernelGGL(decode_seam_kernel, dim3(n_seqs), dim3(256), 0, m->stream, m->argmax_pval, m->argmax_pidx,
-                               cdiv(m->V, ARGMAX_CHUNK), sp ? (const int32_t*)m->samp.out : (const int32_t*)nullptr, m->samp_hist,
-                               (int64_t)m->cfg.max_seq_len, m->samp_hist_len, m->argmax_dev, m->ring, (const int32_t*)m->ring_pos0, n_seqs,
-                               md.tokens, md.tok_pos,
-                               md.seq_pos, (const bf16_t*)m->g[NVL_T_TOK_EMB].p, (const bf16_t*)pe, pe_rows,
-                               m->cfg.embedding_multiplier, m->x, (const float*)l0.t[NVL_T_ATTN_NORM_W].p,
-                               (const float*)l0.t[NVL_T_ATTN_NORM_B].p, m->cfg.norm_eps, (bf16_t*)m->xn, m->H);
+            if (m->g[NVL_T_TOK_EMB].scale)     // 8-bit tied embedding table (w8.h)
+                hipLaunchKernelGGL(decode_seam_w8_kernel, dim3(n_seqs), dim3(256), 0, m->stream, m->argmax_pval, m->argmax_pidx,
+                                   cdiv(m->V, ARGMAX_CHUNK), sp ? (const int32_t*)m->samp.out : (const int32_t*)nullptr, m->samp_hist,
+                                   (int64_t)m->cfg.max_seq_len, m->samp_hist_len, m->argmax_dev, m->ring, (const int32_t*)m->ring_pos0, n_seqs,
+                                   md.tokens, md.tok_pos,
+                                   md.seq_pos, (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const float*)m->g[NVL_T_TOK_EMB].scale, (const bf16_t*)pe, pe_rows,
+                                   m->cfg.embedding_multiplier, m->x, (const float*)l0.t[NVL_T_ATTN_NORM_W].p,
+                                   (const float*)l0.t[NVL_T_ATTN_NORM_B].p, m->cfg.norm_eps, (bf16_t*)m->xn, m->H);
+            else
+                hipLaunchKernelGGL(decode_seam_kernel, dim3(n_seqs), dim3(256), 0, m->stream, m->argmax_pval, m->argmax_pidx,
+                                   cdiv(m->V, ARGMAX_CHUNK), sp ? (const int32_t*)m->samp.out : (const int32_t*)nullptr, m->samp_hist,
+                                   (int64_t)m->cfg.max_seq_len, m->samp_hist_len, m->argmax_dev, m->ring, (const int32_t*)m->ring_pos0, n_seqs,
+                                   md.tokens, md.tok_pos,
+                                   md.seq_pos, (const bf16_t*)m->g[NVL_T_TOK_EMB].p, (const bf16_t*)pe, pe_rows,
+                                   m->cfg.embedding_multiplier, m->x, (const float*)l0.t[NVL_T_ATTN_NORM_W].p,
+                                   (const float*)l0.t[NVL_T_ATTN_NORM_B].p, m->cfg.norm_eps, (bf16_t*)m->xn, m->H);
         } else {
             hipLaunchKernelGGL(advance_decode_kernel, dim3(cdiv(n_seqs, 256)), dim3(256), 0, m->stream, m->argmax_dev, md.tokens,
                                md.tok_pos, md.seq_pos, m->ring + (int64_t)s * n_seqs, n_seqs);
@@ -2557,6 +2767,15 @@ extern "C" int nvl_get_weight(nvl_model* m, int kind, int layer, float* out, int
     NVL_HIP(hipSetDevice(m->device));
     NVL_HIP(hipStreamSynchronize(m->stream));
     const int64_t N = t->rows, K = t->cols, n_el = t->rows_pad * K;
+    if (t->scale) {     // 8-bit weight: W~ = bf16_rne(s * e4m3(q)), the values every GEMM path computes with
+        std::vector<uint8_t> codes((size_t)n_el);
+        std::vector<float> sc((size_t)t->rows_pad);
+        NVL_HIP(hipMemcpy(codes.data(), t->p, codes.size(), hipMemcpyDeviceToHost));
+        NVL_HIP(hipMemcpy(sc.data(), t->scale, sc.size() * 4, hipMemcpyDeviceToHost));
+        for (int64_t n = 0; n < N; n++)
+            for (int64_t k = 0; k < K; k++) out[k * N + n] = w8_value(codes[(size_t)fm_index(n, k, K)], sc[(size_t)n]);
+        return NVL_OK;
+    }
     std::vector<char> raw((size_t)n_el * m->wsize);
     NVL_HIP(hipMemcpy(raw.data(), t->p, raw.size(), hipMemcpyDeviceToHost));
     for (int64_t n = 0; n < N; n++)

@@ -224,6 +224,43 @@ extern "C" int nvl_op_attention(int device, int precision, const float* q, const
     OP_CATCH
 }
 
+// 8-bit weights (w8.h): W [K][N] ([in, out], as nvl_op_matmul) quantized by the upload quantizer, then C = bf16(A) · W~^T
+// through the model's dispatch (gemm(): M <= 64 the fp8-weight decode kernels, larger M the 64-row groups or
+// dequantize + tile; the scratch holds at most 2048 weight rows, as an LM head's would, so wide N runs in chunks).
+extern "C" int nvl_op_matmul_fp8w(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* codes_out,
+                                  float* scales_out) {
+    if (!a || !w || !c || M <= 0 || K <= 0 || N <= 0) return op_fail("nvl_op_matmul_fp8w: bad arguments");
+    if (K % 64 != 0) return op_fail("nvl_op_matmul_fp8w: K must be a multiple of 64");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_BF16);
+    cx.m.w8 = true;
+    void* A = cx.up_mat(a, M, K, false);
+    DevTensor t;
+    upload_2d_w8(&cx.m, &t, w, NVL_DTYPE_F32, N, K, true);
+    cx.bufs.push_back(t.p); cx.bufs.push_back(t.scale);
+    cx.m.w8_map[t.p] = nvl_model::W8Ref{t.scale, t.rows_pad};
+    cx.m.w8_scratch_elems = std::min<int64_t>(t.rows_pad, 2048) * K;
+    cx.m.w8_scratch = (bf16_t*)cx.alloc(cx.m.w8_scratch_elems * 2);
+    const int ldc = (int)round_up(N, 4);
+    float* C = (float*)cx.alloc((int64_t)M * ldc * 4);
+    gemm(&cx.m, EPI_STORE, true, mk(A, K, t.p, C, ldc, nullptr, 1.f, M, N, K));
+    std::vector<float> tmp((size_t)M * ldc);
+    cx.down(tmp.data(), C, (int64_t)M * ldc);
+    for (int i = 0; i < M; i++) memcpy(c + (size_t)i * N, &tmp[(size_t)i * ldc], (size_t)N * 4);
+    if (codes_out || scales_out) {
+        std::vector<uint8_t> codes((size_t)(t.rows_pad * K));
+        std::vector<float> sc((size_t)t.rows_pad);
+        NVL_HIP(hipMemcpy(codes.data(), t.p, codes.size(), hipMemcpyDeviceToHost));
+        NVL_HIP(hipMemcpy(sc.data(), t.scale, sc.size() * 4, hipMemcpyDeviceToHost));
+        if (scales_out) memcpy(scales_out, sc.data(), (size_t)N * 4);
+        if (codes_out)
+            for (int64_t n = 0; n < N; n++)
+                for (int64_t k = 0; k < K; k++) codes_out[n * K + k] = codes[(size_t)fm_index(n, k, K)];
+    }
+    return NVL_OK;
+    OP_CATCH
+}
+
 extern "C" int nvl_op_fp8_kv_roundtrip(int device, const float* x, int64_t n, float scale, uint8_t* codes, float* back) {
     if (!x || !codes || !back || n <= 0 || !(scale > 0.f) || !std::isfinite(scale)) return op_fail("nvl_op_fp8_kv_roundtrip: bad arguments");
     OP_TRY

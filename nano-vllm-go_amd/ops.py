@@ -73,6 +73,19 @@ def attention(q, k, v, scale=0.0, precision="bf16", device=0):  # attention.go:3
     return out
 
 
+def matmul_fp8w(a, w, device=0):                              # MatMul tensor.go:62 with 8-bit weights (w8.h)
+    """a [M][K], w [K][N] ([in, out]) -> (c, codes, scales): w quantized by the model's upload quantizer (codes [N][K]
+    uint8, scales [N]), c = bf16(a) @ W~ through the model's GEMM dispatch, W~ = bf16(scales[:, None] * e4m3(codes))."""
+    a, w = _f(a), _f(w)
+    m, k = a.shape
+    _, n = w.shape
+    c = np.empty((m, n), np.float32)
+    codes = np.empty((n, k), np.uint8)
+    scales = np.empty(n, np.float32)
+    L.check(L.lib().nvl_op_matmul_fp8w(device, _p(a), _p(w), m, n, k, _p(c), _p(codes), _p(scales)))
+    return c, codes, scales
+
+
 def fp8_kv_roundtrip(x, scale=1.0, device=0):                  # the 8-bit KV cache's quantizer + read path (kv8.h)
     """-> (codes uint8, back fp32): codes = e4m3fn(x / scale), back = scale * bf16(code), both computed on the device."""
     x = _f(x)

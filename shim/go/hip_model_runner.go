@@ -40,6 +40,7 @@ type Options struct {
 	Greedy         bool // return the device argmax (cmd/ask/main.go:389-402) instead of sampling
 	DeviceSampling bool // run tensor.SampleWithHistory on the device (only token ids cross PCIe)
 	KVCacheDType   int  // C.NVL_KV_AUTO (0) or C.NVL_KV_FP8_E4M3 (1): 8-bit K/V, twice the tokens per byte of cache
+	WeightDType    int  // C.NVL_W_AUTO (0) or C.NVL_W_FP8_E4M3 (1): 8-bit projection weights with per-row scales
 }
 
 // HipModelRunner implements nanovllm.ModelRunner on one MI355X.
@@ -323,6 +324,13 @@ func create(cfg *C.nvl_model_config, o Options) (*HipModelRunner, error) {
 	r := &HipModelRunner{sampling: tensor.DefaultSamplingParams(), greedy: o.Greedy, deviceSampling: o.DeviceSampling}
 	if rc := C.nvl_create(cfg, &opts, &r.h); rc != 0 {
 		return nil, createErr()
+	}
+	if o.WeightDType != 0 { // before the weights are uploaded (nvl_set_weight_dtype)
+		if rc := C.nvl_set_weight_dtype(r.h, C.int(o.WeightDType)); rc != 0 {
+			err := fmt.Errorf("nvl_set_weight_dtype: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
+			C.nvl_destroy(r.h)
+			return nil, err
+		}
 	}
 	return r, nil
 }
