@@ -162,6 +162,17 @@ enum {
 /* After nvl_create, before the first 2-D upload (else NVL_ERR_STATE).  NVL_ERR_INVALID for an unknown value, and for
  * NVL_W_FP8_E4M3 with f32 precision or tensor parallelism.  In fp8 mode nvl_upload_tensor refuses a non-finite weight. */
 int nvl_set_weight_dtype(nvl_model* m, int dtype);
+/* Activation operand of the projections that run on the tile (prefill) GEMM path, with 8-bit weights. */
+enum {
+    NVL_ACT_AUTO = 0,      /* bf16 activations: the weights' own mode (W8A16 with NVL_W_FP8_E4M3): today's behaviour           */
+    NVL_ACT_FP8_E4M3 = 1   /* W8A8: each tile-path launch quantizes its activation rows to OCP e4m3fn with one fp32 scale per
+                            * row (s_a = amax/448, 1 for a zero row, q = e4m3fn_rne(a / s_a), NaN -> NaN) and multiplies codes
+                            * x codes on the scaled FP8 MFMA: y = (acc * s_a[m]) * s_w[n], then the usual epilogue.  Decode-form
+                            * launches (M <= 64, the 64-row groups, the short-prefill QKV groups) keep bf16 activations.        */
+};
+/* After nvl_set_weight_dtype(m, NVL_W_FP8_E4M3), before nvl_finalize (else NVL_ERR_STATE).  NVL_ERR_INVALID for an unknown
+ * value and for NVL_ACT_FP8_E4M3 without 8-bit weights (so also with f32 precision or tensor parallelism). */
+int nvl_set_act_dtype(nvl_model* m, int dtype);
 /* Pre-quantized 8-bit weight, taken as it is (the dtype of nvl_load_safetensors' F8_E4M3 tensors): codes [rows][cols] OCP
  * e4m3fn in the checkpoint's [out, in] order (layout must be NVL_LAYOUT_OUT_IN), scales [rows] fp32, W~ = bf16(s * e4m3(q)).
  * Counterpart of nvl_upload_tensor (generic_loader.go:353-604) for a kind this model stores 8-bit; NVL_ERR_INVALID for any
@@ -433,6 +444,16 @@ int nvl_op_attention_kv8(int device, const float* q, const float* k, const float
  * codes_out [N][K] / scales_out [N] (either may be NULL) receive the quantized weight.  K % 64 == 0. */
 int nvl_op_matmul_fp8w(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* codes_out,
                        float* scales_out);
+/* 8-bit weights and activations (NVL_ACT_FP8_E4M3): as nvl_op_matmul_fp8w, through the model's dispatch in W8A8 mode.  M
+ * selects the decode form (bf16(a) · W~, bit-identical to nvl_op_matmul_fp8w) or the tile form, where bf16(a) is quantized
+ * per row and c = (sum_k e4m3(q_a) e4m3(q_w)) * s_a[m] * s_w[n].  a_codes_out [M][K] / a_scales_out [M] (either may be NULL)
+ * receive the activation quantization of the tile form (zeros and ones when the decode form ran).  K % 64 == 0. */
+int nvl_op_matmul_w8a8(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* a_codes_out,
+                       float* a_scales_out);
+/* The activation quantizer of the W8A8 tile step alone: a [M][K] fp32 is rounded to bf16 and stored as the fragment-major
+ * operand of a K-wide row (lda >= K, lda % 64 == 0; the columns past K hold a % 7 junk), then quantized reading K columns
+ * with row-tile stride 16 * lda.  codes [M][K] / scales [M] as nvl_op_matmul_w8a8 returns them. */
+int nvl_op_act_quant_fp8(int device, const float* a, int M, int K, int lda, uint8_t* codes, float* scales);
 /* FeedForward.Forward transformer.go:40-96 (w1 [H,2F] gate|up or [H,F]; w2 [F,H]) */
 int nvl_op_ffn(int device, int precision, const float* x, const float* w1, const float* b1,
                const float* w2, const float* b2, int rows, int hidden, int ffn, int swiglu,

@@ -89,6 +89,9 @@ struct nvl_model {
     std::map<const void*, W8Ref> w8_map;   // finalized 8-bit weights by code pointer (gemm() dispatch)
     nvl::bf16_t* w8_scratch = nullptr; int64_t w8_scratch_elems = 0;   // W~ of the tile path (largest non-LM-head projection)
     float* lm_head_scale = nullptr;
+    // 8-bit activations of the tile step (nvl_set_act_dtype NVL_ACT_FP8_E4M3, a8.h): codes [a8_rows][a8_k] + scales [a8_rows]
+    bool a8 = false;
+    uint8_t* a8_codes = nullptr; float* a8_scale = nullptr; int64_t a8_rows = 0, a8_k = 0;
     int device = 0;
     hipStream_t stream = nullptr;
     std::string err;

@@ -164,15 +164,17 @@ void gemm(nvl_model* m, int epi, bool out_f32, GemmArgs a, double flops = -1.0) 
         if (it != m->w8_map.end()) {     // an 8-bit weight (w8.h): the same dispatch on the fp8-weight kernels / dequantize + tile
             const float* ws = it->second.scale;
             const int64_t rp = it->second.rows_pad;
+            const A8Buf a8buf{m->a8_codes, m->a8_scale, m->a8_rows, m->a8_k};
+            const A8Buf* a8 = m->a8 ? &a8buf : nullptr;     // 8-bit activations at the tile step (a8.h)
             switch (epi) {
                 case EPI_STORE:
-                    if (out_f32) launch_gemm_w8<EPI_STORE, float>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems);
-                    else launch_gemm_w8<EPI_STORE, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems);
+                    if (out_f32) launch_gemm_w8<EPI_STORE, float>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8);
+                    else launch_gemm_w8<EPI_STORE, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8);
                     break;
-                case EPI_RESID:  launch_gemm_w8<EPI_RESID, float>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems); break;
-                case EPI_SWIGLU: launch_gemm_w8<EPI_SWIGLU, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems); break;
-                case EPI_GELU:   launch_gemm_w8<EPI_GELU, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems); break;
-                case EPI_QKV:    launch_gemm_w8<EPI_QKV, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems); break;
+                case EPI_RESID:  launch_gemm_w8<EPI_RESID, float>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8); break;
+                case EPI_SWIGLU: launch_gemm_w8<EPI_SWIGLU, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8); break;
+                case EPI_GELU:   launch_gemm_w8<EPI_GELU, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8); break;
+                case EPI_QKV:    launch_gemm_w8<EPI_QKV, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8); break;
                 default: throw std::runtime_error("gemm: bad epilogue");
             }
             NVL_HIP(hipGetLastError());
@@ -357,7 +359,7 @@ extern "C" void nvl_destroy(nvl_model* m) {
         dfree(l.w_qkv); dfree(l.b_qkv); dfree(l.w1); dfree(l.moe_in); dfree(l.moe_out_cat);
         dfree(l.s_qkv); dfree(l.s1);
     }
-    dfree(m->w8_scratch);
+    dfree(m->w8_scratch); dfree(m->a8_codes); dfree(m->a8_scale);
     if (m->lm_head && m->lm_head != m->g[NVL_T_TOK_EMB].p && m->lm_head != m->g[NVL_T_LM_HEAD].p) dfree(m->lm_head);
     dfree(m->rope_cos); dfree(m->rope_sin); dfree(m->kcache); dfree(m->vcache);
     dfree(m->x); dfree(m->xn); dfree(m->qkv); dfree(m->q); dfree(m->attn_out); dfree(m->attn_part); dfree(m->attn_part_cnt); dfree(m->hbuf); dfree(m->h2);
@@ -822,6 +824,17 @@ extern "C" int nvl_set_weight_dtype(nvl_model* m, int dtype) {
     if (dtype == NVL_W_FP8_E4M3 && (m->tp > 1 || m->tp_force))
         return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights are not available with tensor parallelism");
     m->w8 = dtype == NVL_W_FP8_E4M3;
+    if (!m->w8) m->a8 = false;     // (8-bit activations need 8-bit weights)
+    return NVL_OK;
+}
+
+extern "C" int nvl_set_act_dtype(nvl_model* m, int dtype) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_act_dtype: no model");
+    if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_set_act_dtype: call it before nvl_finalize");
+    if (dtype != NVL_ACT_AUTO && dtype != NVL_ACT_FP8_E4M3) return fail(m, NVL_ERR_INVALID, "nvl_set_act_dtype: unknown activation dtype");
+    if (dtype == NVL_ACT_FP8_E4M3 && !m->w8)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_act_dtype: 8-bit activations need 8-bit weights (nvl_set_weight_dtype first)");
+    m->a8 = dtype == NVL_ACT_FP8_E4M3;
     return NVL_OK;
 }
 
@@ -951,6 +964,17 @@ extern "C" int nvl_finalize(nvl_model* m) {
         }
         m->w8_scratch_elems = big;
         if (big) m->w8_scratch = dmalloc<bf16_t>(big);
+        if (m->a8) {   // the activation codes + row scales of the W8A8 tile step: every row of a batch, the widest K
+            int64_t kmax = H;
+            for (auto& l : m->layers) {
+                if (l.t[NVL_T_WO].scale) kmax = std::max(kmax, l.t[NVL_T_WO].cols);
+                if (l.t[NVL_T_W2].scale) kmax = std::max(kmax, l.t[NVL_T_W2].cols);
+            }
+            m->a8_rows = round_up(m->opts.max_batch_tokens, 16);
+            m->a8_k = kmax;
+            m->a8_codes = (uint8_t*)dmalloc_bytes(m->a8_rows * kmax);
+            m->a8_scale = dmalloc<float>(m->a8_rows);
+        }
     }
 
     // ---- RoPE tables in fp64 on the host, exactly as NewRoPECache (rope.go:18-50)

@@ -261,6 +261,75 @@ extern "C" int nvl_op_matmul_fp8w(int device, const float* a, const float* w, in
     OP_CATCH
 }
 
+// codes [rows_pad16][K] (fragment-major bytes) + scales on the device -> [M][K] row-major / [M] on the host
+static void a8_read_back(OpCtx& cx, const uint8_t* dcodes, const float* dscale, int M, int K, uint8_t* codes_out, float* scales_out) {
+    const int64_t rows = round_up(M, 16);
+    std::vector<uint8_t> codes((size_t)(rows * K));
+    std::vector<float> sc((size_t)rows);
+    NVL_HIP(hipStreamSynchronize(cx.m.stream));
+    NVL_HIP(hipMemcpy(codes.data(), dcodes, codes.size(), hipMemcpyDeviceToHost));
+    NVL_HIP(hipMemcpy(sc.data(), dscale, sc.size() * 4, hipMemcpyDeviceToHost));
+    if (scales_out) memcpy(scales_out, sc.data(), (size_t)M * 4);
+    if (codes_out)
+        for (int64_t r = 0; r < M; r++)
+            for (int64_t k = 0; k < K; k++) codes_out[r * K + k] = codes[(size_t)fm_index(r, k, K)];
+}
+
+// 8-bit weights and activations (a8.h): nvl_op_matmul_fp8w with the model's dispatch in W8A8 mode
+extern "C" int nvl_op_matmul_w8a8(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* a_codes_out,
+                                  float* a_scales_out) {
+    if (!a || !w || !c || M <= 0 || K <= 0 || N <= 0) return op_fail("nvl_op_matmul_w8a8: bad arguments");
+    if (K % 64 != 0) return op_fail("nvl_op_matmul_w8a8: K must be a multiple of 64");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_BF16);
+    cx.m.w8 = true;
+    cx.m.a8 = true;
+    void* A = cx.up_mat(a, M, K, false);
+    DevTensor t;
+    upload_2d_w8(&cx.m, &t, w, NVL_DTYPE_F32, N, K, true);
+    cx.bufs.push_back(t.p); cx.bufs.push_back(t.scale);
+    cx.m.w8_map[t.p] = nvl_model::W8Ref{t.scale, t.rows_pad};
+    cx.m.w8_scratch_elems = std::min<int64_t>(t.rows_pad, 2048) * K;
+    cx.m.w8_scratch = (bf16_t*)cx.alloc(cx.m.w8_scratch_elems * 2);
+    cx.m.a8_rows = round_up(M, 16);
+    cx.m.a8_k = K;
+    cx.m.a8_codes = (uint8_t*)cx.alloc(cx.m.a8_rows * K);
+    cx.m.a8_scale = (float*)cx.alloc(cx.m.a8_rows * 4);
+    NVL_HIP(hipMemsetAsync(cx.m.a8_codes, 0, (size_t)(cx.m.a8_rows * K), cx.m.stream));
+    const std::vector<float> ones((size_t)cx.m.a8_rows, 1.0f);
+    NVL_HIP(hipMemcpyAsync(cx.m.a8_scale, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, cx.m.stream));
+    NVL_HIP(hipStreamSynchronize(cx.m.stream));     // (pageable source)
+    const int ldc = (int)round_up(N, 4);
+    float* C = (float*)cx.alloc((int64_t)M * ldc * 4);
+    gemm(&cx.m, EPI_STORE, true, mk(A, K, t.p, C, ldc, nullptr, 1.f, M, N, K));
+    std::vector<float> tmp((size_t)M * ldc);
+    cx.down(tmp.data(), C, (int64_t)M * ldc);
+    for (int i = 0; i < M; i++) memcpy(c + (size_t)i * N, &tmp[(size_t)i * ldc], (size_t)N * 4);
+    if (a_codes_out || a_scales_out) a8_read_back(cx, cx.m.a8_codes, cx.m.a8_scale, M, K, a_codes_out, a_scales_out);
+    cx.m.a8_codes = nullptr; cx.m.a8_scale = nullptr;       // owned by cx.bufs
+    return NVL_OK;
+    OP_CATCH
+}
+
+extern "C" int nvl_op_act_quant_fp8(int device, const float* a, int M, int K, int lda, uint8_t* codes, float* scales) {
+    if (!a || !codes || !scales || M <= 0 || K <= 0 || K % 64 != 0 || lda < K || lda % 64 != 0)
+        return op_fail("nvl_op_act_quant_fp8: bad arguments");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_BF16);
+    std::vector<float> ext((size_t)M * lda);
+    for (int64_t r = 0; r < M; r++)
+        for (int64_t k = 0; k < lda; k++) ext[(size_t)(r * lda + k)] = k < K ? a[r * K + k] : (float)((r + k) % 7);
+    void* A = cx.up_mat(ext.data(), M, lda, false, 16);
+    const int64_t rows = round_up(M, 16);
+    uint8_t* dc = (uint8_t*)cx.alloc(rows * K);
+    float* ds = (float*)cx.alloc(rows * 4);
+    a8_quant_rows(cx.m.stream, A, lda, M, K, dc, ds);
+    NVL_HIP(hipGetLastError());
+    a8_read_back(cx, dc, ds, M, K, codes, scales);
+    return NVL_OK;
+    OP_CATCH
+}
+
 extern "C" int nvl_op_fp8_kv_roundtrip(int device, const float* x, int64_t n, float scale, uint8_t* codes, float* back) {
     if (!x || !codes || !back || n <= 0 || !(scale > 0.f) || !std::isfinite(scale)) return op_fail("nvl_op_fp8_kv_roundtrip: bad arguments");
     OP_TRY

@@ -15,6 +15,7 @@
 #pragma once
 #include "kv8.h"
 #include "gemm.h"
+#include "a8.h"
 
 namespace nvl {
 
@@ -168,9 +169,10 @@ static inline void w8_dequant_rows(hipStream_t st, const void* codes, const floa
 // The GEMM of an 8-bit weight (a.W: codes, ws: scales, w_rows_pad: its allocated rows).  Decode-sized calls go where the bf16
 // dispatch (launch_gemm_bf16) sends them, on the fp8-weight kernels; the rest run the bf16 dispatch on W~ in `scratch`
 // (scratch_elems bf16 elements), in row chunks when W~ does not fit (EPI_STORE with fp32 output only: the LM head).
+// With a8 (8-bit activations, a8.h) the tile step is the W8A8 kernel on the codes instead.
 template <int EPI, typename OutT>
 static inline void launch_gemm_w8(hipStream_t st, const GemmArgs& a, const float* ws, int64_t w_rows_pad, bf16_t* scratch,
-                                  int64_t scratch_elems) {
+                                  int64_t scratch_elems, const A8Buf* a8 = nullptr) {
     if (a.tile_map || a.seg || a.a_rows) throw std::runtime_error("gemm: an 8-bit weight in a gathered / grouped launch");
     if (launch_gemm_skinny_bf16<EPI, OutT, true>(st, a, ws)) return;
     if constexpr (EPI != EPI_QKV) {     // (the 64-row-group condition of launch_gemm_bf16, unchanged)
@@ -185,6 +187,10 @@ static inline void launch_gemm_w8(hipStream_t st, const GemmArgs& a, const float
         }
     }
     if (a.rs_in || a.rs_out) throw std::runtime_error("gemm: a deferred-RMSNorm projection did not fit the decode kernels");
+    if (a8) {
+        launch_gemm_w8a8<EPI, OutT>(st, a, ws, *a8);
+        return;
+    }
     if (w_rows_pad * a.K <= scratch_elems) {
         w8_dequant_rows(st, a.W, ws, a.K, 0, w_rows_pad, scratch);
         GemmArgs c = a;

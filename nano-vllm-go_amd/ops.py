@@ -86,6 +86,30 @@ def matmul_fp8w(a, w, device=0):                              # MatMul tensor.go
     return c, codes, scales
 
 
+def matmul_w8a8(a, w, device=0):                              # MatMul tensor.go:62 with 8-bit weights and activations (a8.h)
+    """a [M][K], w [K][N] ([in, out]) -> (c, a_codes, a_scales): matmul_fp8w's dispatch in W8A8 mode.  The tile form
+    quantizes bf16(a) per row (a_codes [M][K] uint8, a_scales [M]) and returns c = (e4m3(a_codes) @ e4m3(w codes)^T) * a_scales
+    * w scales; the decode form (small M) is matmul_fp8w's bf16(a) @ W~ and leaves a_codes 0, a_scales 1."""
+    a, w = _f(a), _f(w)
+    m, k = a.shape
+    _, n = w.shape
+    c = np.empty((m, n), np.float32)
+    codes = np.empty((m, k), np.uint8)
+    scales = np.empty(m, np.float32)
+    L.check(L.lib().nvl_op_matmul_w8a8(device, _p(a), _p(w), m, n, k, _p(c), _p(codes), _p(scales)))
+    return c, codes, scales
+
+
+def act_quant_fp8(a, lda=None, device=0):                     # the W8A8 activation quantizer alone (a8.h)
+    """a [M][K] -> (codes [M][K] uint8, scales [M]) of bf16(a), read as a fragment-major operand of row width lda >= K"""
+    a = _f(a)
+    m, k = a.shape
+    codes = np.empty((m, k), np.uint8)
+    scales = np.empty(m, np.float32)
+    L.check(L.lib().nvl_op_act_quant_fp8(device, _p(a), m, k, int(lda or k), _p(codes), _p(scales)))
+    return codes, scales
+
+
 def fp8_kv_roundtrip(x, scale=1.0, device=0):                  # the 8-bit KV cache's quantizer + read path (kv8.h)
     """-> (codes uint8, back fp32): codes = e4m3fn(x / scale), back = scale * bf16(code), both computed on the device."""
     x = _f(x)
