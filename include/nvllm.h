@@ -157,11 +157,23 @@ enum {
     NVL_W_FP8_E4M3 = 1     /* WQ/WK/WV/WKV/WO/W1/W2 and the LM head (the token embedding when tied) as OCP e4m3fn codes with
                             * one fp32 scale per output row: s = amax/448 (1 for a zero row), q = e4m3fn_rne(w / s).  Every path
                             * computes with W~ = bf16_rne(s * e4m3(q)); nvl_get_weight returns W~; nvl_stats.weight_bytes
-                            * counts codes + scales.  Position embedding, router, MoE experts, Mamba2 projections stay bf16. */
+                            * counts codes + scales.  Position embedding, router, Mamba2 projections stay bf16; MoE experts too
+                            * unless nvl_set_expert_dtype(m, NVL_EXPERT_FP8_E4M3). */
 };
 /* After nvl_create, before the first 2-D upload (else NVL_ERR_STATE).  NVL_ERR_INVALID for an unknown value, and for
  * NVL_W_FP8_E4M3 with f32 precision or tensor parallelism.  In fp8 mode nvl_upload_tensor refuses a non-finite weight. */
 int nvl_set_weight_dtype(nvl_model* m, int dtype);
+/* MoE expert weights (MOE_IN / MOE_OUT) with 8-bit projection weights. */
+enum {
+    NVL_EXPERT_AUTO = 0,       /* the experts stay bf16 (also under NVL_W_FP8_E4M3): today's behaviour                       */
+    NVL_EXPERT_FP8_E4M3 = 1    /* MOE_IN / MOE_OUT as OCP e4m3fn codes with one fp32 scale per (expert, output row), under the
+                                * contract of NVL_W_FP8_E4M3: s = amax/448, q = e4m3fn_rne(w / s), W~ = bf16_rne(s * e4m3(q)) on
+                                * every path; nvl_get_weight returns W~; nvl_stats.weight_bytes counts codes + scales.  Decode
+                                * streams the codes; prefill dequantizes one layer's experts at a time into a scratch buffer. */
+};
+/* After nvl_set_weight_dtype(m, NVL_W_FP8_E4M3), before the first expert upload and nvl_finalize (else NVL_ERR_STATE).
+ * NVL_ERR_INVALID for an unknown value, a model without MoE, f32 precision, or no 8-bit projection weights. */
+int nvl_set_expert_dtype(nvl_model* m, int dtype);
 /* Activation operand of the projections that run on the tile (prefill) GEMM path, with 8-bit weights. */
 enum {
     NVL_ACT_AUTO = 0,      /* bf16 activations: the weights' own mode (W8A16 with NVL_W_FP8_E4M3): today's behaviour           */
@@ -176,7 +188,8 @@ int nvl_set_act_dtype(nvl_model* m, int dtype);
 /* Pre-quantized 8-bit weight, taken as it is (the dtype of nvl_load_safetensors' F8_E4M3 tensors): codes [rows][cols] OCP
  * e4m3fn in the checkpoint's [out, in] order (layout must be NVL_LAYOUT_OUT_IN), scales [rows] fp32, W~ = bf16(s * e4m3(q)).
  * Counterpart of nvl_upload_tensor (generic_loader.go:353-604) for a kind this model stores 8-bit; NVL_ERR_INVALID for any
- * other kind, a shape mismatch, a NaN code (0x7f / 0xff) or a non-finite / non-positive scale. */
+ * other kind, a shape mismatch, a NaN code (0x7f / 0xff) or a non-finite / non-positive scale.  With NVL_EXPERT_FP8_E4M3
+ * it takes MOE_IN / MOE_OUT too: rows = E * out, cols = in, scales [E * out] (expert e's rows e*out .. e*out + out - 1). */
 int nvl_upload_tensor_fp8(nvl_model* m, int kind, int layer, const uint8_t* codes, const float* scales, int64_t rows,
                           int64_t cols, int layout);
 

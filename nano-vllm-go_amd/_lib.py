@@ -35,6 +35,7 @@ PRECISION = {"bf16": 0, "f32": 1}
 KV_CACHE_DTYPE = {"auto": 0, "fp8_e4m3": 1}
 WEIGHT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                # NVL_W_* (nvl_set_weight_dtype)
 ACT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                   # NVL_ACT_AUTO / NVL_ACT_FP8_E4M3 (nvl_set_act_dtype)
+EXPERT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                # NVL_EXPERT_AUTO / NVL_EXPERT_FP8_E4M3 (nvl_set_expert_dtype)
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 LAYOUT_IN_OUT, LAYOUT_OUT_IN = 0, 1
 FWD_ALL_LOGITS = 1
@@ -175,6 +176,7 @@ def lib():
     L.nvl_upload_tensor_fp8.argtypes = [vp, C.c_int, C.c_int, vp, vp, i64, i64, C.c_int]
     L.nvl_op_matmul_fp8w.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.nvl_set_act_dtype.argtypes = [vp, C.c_int]
+    L.nvl_set_expert_dtype.argtypes = [vp, C.c_int]
     L.nvl_op_matmul_w8a8.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.nvl_op_act_quant_fp8.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]
     L.nvl_op_fp8_kv_roundtrip.argtypes = [C.c_int, vp, i64, f32, vp, vp]

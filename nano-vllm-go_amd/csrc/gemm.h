@@ -931,7 +931,11 @@ __device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scal
 
     const bf16_t* wp = (const bf16_t*)p.W + (((int64_t)(nt0 + tile) * (p.K >> 5) + ks0) * 64 + lane) * 8;
     const uint8_t* wq = (const uint8_t*)p.W + (((int64_t)(nt0 + tile) * (p.K >> 5) + ks0) * 64 + lane) * 8;
-    const float wsc = W8 ? w_scale[(nt0 + tile) * 16 + fr] : 1.0f;     // (rows are padded: every tile's scales exist)
+    // (rows are padded: every tile's scales exist.)  MoE down (8-bit experts, the K-split form): the scales are [E][H_pad] and
+    // this wave's K range is exactly one expert, ks0 / (I / 32)
+    int wsc_row = (nt0 + tile) * 16 + fr;
+    if constexpr (MOE && W8 && EPI == EPI_RESID) wsc_row += (ks0 / (p.moe_I >> 5)) * (int)((p.N + W_ROW_PAD - 1) / W_ROW_PAD * W_ROW_PAD);
+    const float wsc = W8 ? w_scale[wsc_row] : 1.0f;
     auto wload = [&](int64_t s) -> bf16x8 { return w8_frag(weight_load8<PASSES>((const u32x2*)(wq + s * 512)), wsc); };
     // W8: a block's registers hold the raw codes; they are converted where the MFMAs consume them (comp_blk).  Converting
     // at the load put the conversion inside the HALF form's predicated load, and the compiler then waited for every load
@@ -1094,6 +1098,13 @@ __device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scal
 template <int MT, int NTW, int U, int EPI, typename OutT, bool PASSES = false, bool HALF = false>
 __global__ __launch_bounds__(1024) void gemm_skinny_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
     gemm_skinny_body<MT, NTW, U, EPI, OutT, PASSES, false, HALF, true>(p, w_scale);
+}
+// 8-bit MoE experts (nvl_set_expert_dtype): the MoE decode instantiation of the same body — expert skip,
+// gate weight in the SwiGLU epilogue; the down projection's scales are [E][H_pad] (one per expert and output row), K-split
+// form only (each wave one expert).  The deferred-norm producer form, whose waves cross experts, has no 8-bit instance.
+template <int MT, int NTW, int U, int EPI, typename OutT>
+__global__ __launch_bounds__(1024) void gemm_skinny_moe_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
+    gemm_skinny_body<MT, NTW, U, EPI, OutT, false, true, false, true>(p, w_scale);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1486,6 +1497,11 @@ template <int MT, int NTB, int U, int EPI, typename OutT, bool PASSES = false>
 __global__ __launch_bounds__(512) void gemm_skinny_wide_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
     gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, PASSES, false, true>(p, w_scale);
 }
+// 8-bit MoE experts: the wide form of the expert up projection (SwiGLU, gate weight in the epilogue)
+template <int MT, int NTB, int U, int EPI, typename OutT>
+__global__ __launch_bounds__(512) void gemm_skinny_wide_moe_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
+    gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, false, true, true>(p, w_scale);
+}
 
 static int g_chunk_max_m = 512;    // largest M that uses 64-row passes of the decode form at all (nvl_set_tuning key 11; 64 = off)
 static int g_chunk_all_m = 64;     // up to here every projection does; above, only those whose 128x128 tile grid would
@@ -1528,7 +1544,8 @@ static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a
 }
 
 // skinny dispatch: M <= 64, no gather/segments.  Returns false when the shape is not eligible.
-// W8: the same decisions, the fp8-weight kernels (ws: the per-row weight scales).  MoE weights are never 8-bit.
+// W8: the same decisions, the fp8-weight kernels (ws: the per-row weight scales).  8-bit MoE experts (moe_gate) take the
+// K-split down form and the SwiGLU up form; the deferred-norm producer form of the down projection has no 8-bit instance.
 template <int NTW, int EPI, typename OutT, bool W8 = false>
 static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
     const int MT = skinny_rows(a) <= 16 ? 1 : (skinny_rows(a) <= 32 ? 2 : 4);
@@ -1544,7 +1561,7 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
         while (ks > 1 && (a.K >> 5) / ks < 4) ks >>= 1;
         if (a.K % 32 != 0) return false;
         if constexpr (EPI == EPI_RESID) {
-            if (a.moe_gate && W8) return false;     // (MoE weights are never 8-bit)
+            if (a.moe_gate && W8) return false;     // (no 8-bit instance: a wave's blocks cross experts, see moe())
             if (a.moe_gate) {     // MoE down as the deferred-norm producer: all experts in one workgroup's K range, 16 waves
                 ks = 16;
                 const int nks = a.K >> 5, spe = a.moe_I >> 5;
@@ -1599,7 +1616,16 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
     dim3 grid(nblocks * (a.m_passes > 1 ? a.m_passes : 1), KS), block(NTW * ksplit * 64);
     if (a.grid_y != KS) { GemmArgs c = a; c.grid_y = KS; return launch_gemm_skinny_ntw<NTW, EPI, OutT, W8>(st, c, ws); }
     if constexpr (W8) {
-        if (a.moe_gate) return false;
+        if (a.moe_gate) {                                 // 8-bit MoE experts
+            if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
+                if (a.m_passes > 1) return false;
+                if (MT == 1) hipLaunchKernelGGL((gemm_skinny_moe_fp8w_kernel<1, NTW, 4, EPI, OutT>), grid, block, lds, st, a, ws);
+                else if (MT == 2) hipLaunchKernelGGL((gemm_skinny_moe_fp8w_kernel<2, NTW, 4, EPI, OutT>), grid, block, lds, st, a, ws);
+                else hipLaunchKernelGGL((gemm_skinny_moe_fp8w_kernel<4, NTW, 2, EPI, OutT>), grid, block, lds, st, a, ws);
+                return true;
+            }
+            return false;
+        }
         if (a.m_passes > 1) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<4, NTW, 2, EPI, OutT, true>), grid, block, lds, st, a, ws);
         else if (MT == 1) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<1, NTW, 4, EPI, OutT>), grid, block, lds, st, a, ws);
         else if (MT == 2) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<2, NTW, 4, EPI, OutT>), grid, block, lds, st, a, ws);
@@ -1654,7 +1680,21 @@ static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, co
         hipLaunchKernelGGL((gemm_skinny_wide_fp8w_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), dim3(wgs), dim3(ksplit * 64),      \
                            lds, st, a, ws);                                                                            \
     } while (0)
-        if (a.moe_gate) return false;
+#define NVL_SKW8M(MTv, Uv)                                                                                               \
+    do {                                                                                                               \
+        NVL_LDS_ATTR((gemm_skinny_wide_moe_fp8w_kernel<MTv, NTB, Uv, EPI, OutT>), 8 * NTB * MTv * 64 * 16);           \
+        hipLaunchKernelGGL((gemm_skinny_wide_moe_fp8w_kernel<MTv, NTB, Uv, EPI, OutT>), dim3(wgs), dim3(ksplit * 64),     \
+                           lds, st, a, ws);                                                                            \
+    } while (0)
+        if (a.moe_gate) {                                 // 8-bit MoE experts: the expert up projection
+            if constexpr (EPI == EPI_SWIGLU) {
+                if (a.m_passes > 1) return false;
+                if (MT == 1) NVL_SKW8M(1, 4); else if (MT == 2) NVL_SKW8M(2, 4); else NVL_SKW8M(4, 2);
+                return true;
+            }
+            return false;
+        }
+#undef NVL_SKW8M
         if (a.m_passes > 1) NVL_SKW8(4, 2, true); else if (MT == 1) NVL_SKW8(1, 4, false); else if (MT == 2) NVL_SKW8(2, 4, false); else NVL_SKW8(4, 2, false);
 #undef NVL_SKW8
         return true;

@@ -271,6 +271,28 @@ inline std::vector<float> f8_row_scales(const StTensor& t, const std::string& wh
     }
     return v;
 }
+// the per-(expert, output row) scales of an F8_E4M3 MoE expert weight [E, out, in]: weight_scale F32 / BF16 of shape
+// [E, out] or [E, out, 1], per expert ([E] or [E, 1, 1], broadcast over the rows) or a scalar; block-wise scales are refused
+inline std::vector<float> f8_expert_scales(const StTensor& t, const std::string& what) {
+    if (t.shape.size() != 3) throw std::runtime_error("F8_E4M3 tensor " + what + ": a 3-D [E, out, in] expert weight was expected");
+    if (!t.scale) throw std::runtime_error("F8_E4M3 tensor " + what + " has no weight_scale");
+    const StTensor& s = *t.scale;
+    if (s.dtype != NVL_DTYPE_F32 && s.dtype != NVL_DTYPE_BF16) throw std::runtime_error(what + "_scale: F32 or BF16 expected");
+    const int64_t E = t.shape[0], N = t.shape[1];
+    const auto& d = s.shape;
+    const bool scalar = s.numel == 1 && d.size() <= 3;
+    const bool per_row = (d.size() == 2 && d[0] == E && d[1] == N) || (d.size() == 3 && d[0] == E && d[1] == N && d[2] == 1);
+    const bool per_expert = (d.size() == 1 && d[0] == E) || (d.size() == 3 && d[0] == E && d[1] == 1 && d[2] == 1);
+    if (!scalar && !per_row && !per_expert)
+        throw std::runtime_error(what + "_scale: only per-(expert, output channel) ([E,out] or [E,out,1]), per-expert ([E] or [E,1,1]) "
+                                 "or scalar scales are supported (block-wise scales are not)");
+    std::vector<float> v((size_t)(E * N));
+    for (int64_t r = 0; r < E * N; r++) {
+        v[(size_t)r] = f32_of(s, scalar ? 0 : (per_row ? r : r / N));
+        if (!(v[(size_t)r] > 0.f) || !std::isfinite(v[(size_t)r])) throw std::runtime_error(what + "_scale: scales must be finite and positive");
+    }
+    return v;
+}
 inline float f32_of(const StTensor& t, int64_t i) {                  // :769-805
     if (t.dtype == ST_F8_E4M3) {         // W~ = bf16(s * e4m3(code)): what an 8-bit-weight model computes with
         const int64_t K = t.shape.size() == 2 ? t.shape[1] : 1;
@@ -453,8 +475,14 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
             if (c.use_moe) {                                                   // loadMoE (:566-592)
                 up2d(m, NVL_T_ROUTER, l, st.need(p + ".block_sparse_moe.router.layer.weight"), OI);   // [E, H]: "always transpose"
                 for (int which = 0; which < 2; which++) {
-                    const StTensor& e = st.need(p + (which ? ".block_sparse_moe.output_linear.weight" : ".block_sparse_moe.input_linear.weight"));
+                    const std::string name = p + (which ? ".block_sparse_moe.output_linear.weight" : ".block_sparse_moe.input_linear.weight");
+                    const StTensor& e = st.need(name);
                     if (e.shape.size() != 3) throw std::runtime_error("expert weights: 3-D [E, out, in] expected");
+                    if (e.dtype == nvl_loader::ST_F8_E4M3) {     // codes as they are into 8-bit experts, else W~ (up2d_f8)
+                        up2d_f8(m, which ? NVL_T_MOE_OUT : NVL_T_MOE_IN, l, e.data, nvl_loader::f8_expert_scales(e, name),
+                                e.shape[0] * e.shape[1], e.shape[2], OI);
+                        continue;
+                    }
                     const int rc = nvl_upload_tensor(m, which ? NVL_T_MOE_OUT : NVL_T_MOE_IN, l, e.data, e.dtype,
                                                      e.shape[0] * e.shape[1], e.shape[2], IO);
                     if (rc) throw std::runtime_error(nvl_last_error(m));

@@ -37,6 +37,11 @@ struct LayerW {
     float* s_qkv = nullptr; float* s1 = nullptr;   // 8-bit weights: the row scales of w_qkv / w1 (they follow the fused rows)
     void* moe_in = nullptr;              // [E][2I (interleaved in bf16 mode)][H]
     void* moe_out_cat = nullptr;         // bf16: W_down of all experts along K, [H_pad][E*I] (decode "dense-masked" form)
+    // 8-bit experts (nvl_set_expert_dtype): moe_in holds codes in the same interleaved order, s_moe_in [rows_pad] its row
+    // scales; moe_out8 the down codes, [H_pad][E*I] (the layout of moe_out_cat: moe_out_cat = moe_out8 when the decode
+    // form applies), s_moe_out [E][H_pad] its scales
+    float* s_moe_in = nullptr;
+    void* moe_out8 = nullptr; float* s_moe_out = nullptr;
     bool mamba = false;                  // a Mamba2 block (attention tensors absent); index among the Mamba2 layers
     int mamba_idx = -1;
 };
@@ -89,6 +94,10 @@ struct nvl_model {
     std::map<const void*, W8Ref> w8_map;   // finalized 8-bit weights by code pointer (gemm() dispatch)
     nvl::bf16_t* w8_scratch = nullptr; int64_t w8_scratch_elems = 0;   // W~ of the tile path (largest non-LM-head projection)
     float* lm_head_scale = nullptr;
+    // 8-bit MoE experts (nvl_set_expert_dtype NVL_EXPERT_FP8_E4M3, w8.h): W~ of one layer's experts for the grouped GEMMs
+    bool e8 = false;
+    bool expert_uploaded = false;          // an expert tensor has been uploaded: the expert dtype is fixed from then on
+    nvl::bf16_t* e8_scratch = nullptr; int64_t e8_scratch_elems = 0;
     // 8-bit activations of the tile step (nvl_set_act_dtype NVL_ACT_FP8_E4M3, a8.h): codes [a8_rows][a8_k] + scales [a8_rows]
     bool a8 = false;
     uint8_t* a8_codes = nullptr; float* a8_scale = nullptr; int64_t a8_rows = 0, a8_k = 0;

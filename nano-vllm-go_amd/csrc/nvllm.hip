@@ -358,8 +358,10 @@ extern "C" void nvl_destroy(nvl_model* m) {
         for (int k = 0; k < NVL_T_COUNT; k++) { dfree(l.t[k].p); dfree(l.t[k].scale); }
         dfree(l.w_qkv); dfree(l.b_qkv); dfree(l.w1); dfree(l.moe_in); dfree(l.moe_out_cat);
         dfree(l.s_qkv); dfree(l.s1);
+        if (l.moe_out_cat != l.moe_out8) dfree(l.moe_out8);
+        dfree(l.s_moe_in); dfree(l.s_moe_out);
     }
-    dfree(m->w8_scratch); dfree(m->a8_codes); dfree(m->a8_scale);
+    dfree(m->w8_scratch); dfree(m->e8_scratch); dfree(m->a8_codes); dfree(m->a8_scale);
     if (m->lm_head && m->lm_head != m->g[NVL_T_TOK_EMB].p && m->lm_head != m->g[NVL_T_LM_HEAD].p) dfree(m->lm_head);
     dfree(m->rope_cos); dfree(m->rope_sin); dfree(m->kcache); dfree(m->vcache);
     dfree(m->x); dfree(m->xn); dfree(m->qkv); dfree(m->q); dfree(m->attn_out); dfree(m->attn_part); dfree(m->attn_part_cnt); dfree(m->hbuf); dfree(m->h2);
@@ -399,13 +401,15 @@ namespace {
 // `sl` selects the sub-block of the uploaded tensor that lands in rows [dn0, dn0+N) (the whole tensor for
 // replicated kinds, this rank's shard for tensor-parallel kinds); total_rows sizes the destination.
 // is this 2-D kind stored 8-bit in an fp8-weight model?  The projections and the LM head; the token embedding only when it
-// is the (tied) LM head too.  Position embedding, router, MoE experts and Mamba2 projections stay bf16.
+// is the (tied) LM head too; the MoE experts with nvl_set_expert_dtype.  Position embedding, router and Mamba2 projections
+// stay bf16.
 bool w8_kind(const nvl_model* m, int kind) {
     if (!m->w8) return false;
     switch (kind) {
         case NVL_T_WQ: case NVL_T_WK: case NVL_T_WV: case NVL_T_WKV: case NVL_T_WO: case NVL_T_W1: case NVL_T_W2:
         case NVL_T_LM_HEAD: return true;
         case NVL_T_TOK_EMB: return m->cfg.tied_embedding != 0;
+        case NVL_T_MOE_IN: case NVL_T_MOE_OUT: return m->e8;
         default: return false;
     }
 }
@@ -576,7 +580,9 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
             return fail(m, NVL_ERR_INVALID, buf);
         }
         m->w2d_uploaded = true;
-        upload_2d(m, t, data, dtype, rows, cols, false, Slice2D{rows, cols, 0, 0, 0}, rows, true);
+        m->expert_uploaded = true;
+        if (w8_kind(m, kind)) upload_2d_w8(m, t, data, dtype, rows, cols, false);     // one scale per (expert, output row)
+        else upload_2d(m, t, data, dtype, rows, cols, false, Slice2D{rows, cols, 0, 0, 0}, rows, true);
         return NVL_OK;
     }
     if (kind >= NVL_T_MAMBA_IN_PROJ && !m->n_mamba) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor: the model has no Mamba2 layers");
@@ -634,7 +640,11 @@ extern "C" int nvl_upload_tensor_fp8(nvl_model* m, int kind, int layer, const ui
     if (layout != NVL_LAYOUT_OUT_IN) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
     DevTensor* t = tensor_slot(m, kind, layer);
     if (!t) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: bad kind or layer");
-    const int64_t SN = kind == NVL_T_TOK_EMB ? m->V : full_out(m, kind), SK = kind == NVL_T_TOK_EMB ? m->H : full_in(m, kind);
+    int64_t SN = kind == NVL_T_TOK_EMB ? m->V : full_out(m, kind), SK = kind == NVL_T_TOK_EMB ? m->H : full_in(m, kind);
+    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {     // [E * out][in], scales [E * out]
+        SN = (int64_t)m->cfg.num_experts * (kind == NVL_T_MOE_IN ? 2 * (int64_t)m->F : m->H);
+        SK = kind == NVL_T_MOE_IN ? m->H : m->F;
+    }
     if (rows != SN || cols != SK || SK % 32 != 0) {
         char buf[160];
         snprintf(buf, sizeof buf, "nvl_upload_tensor_fp8: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld]", kind,
@@ -648,6 +658,7 @@ extern "C" int nvl_upload_tensor_fp8(nvl_model* m, int kind, int layer, const ui
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
     m->w2d_uploaded = true;
+    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) m->expert_uploaded = true;
     const int64_t Npad = round_up(rows, W_ROW_PAD);
     w8_alloc(m, t, Npad, cols);
     uint8_t* raw = (uint8_t*)dmalloc_bytes(rows * cols);
@@ -824,7 +835,21 @@ extern "C" int nvl_set_weight_dtype(nvl_model* m, int dtype) {
     if (dtype == NVL_W_FP8_E4M3 && (m->tp > 1 || m->tp_force))
         return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights are not available with tensor parallelism");
     m->w8 = dtype == NVL_W_FP8_E4M3;
-    if (!m->w8) m->a8 = false;     // (8-bit activations need 8-bit weights)
+    if (!m->w8) m->a8 = m->e8 = false;     // (8-bit activations and experts need 8-bit weights)
+    return NVL_OK;
+}
+
+extern "C" int nvl_set_expert_dtype(nvl_model* m, int dtype) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_expert_dtype: no model");
+    if (m->finalized || m->expert_uploaded)
+        return fail(m, NVL_ERR_STATE, "nvl_set_expert_dtype: call it after nvl_set_weight_dtype and before the first expert upload");
+    if (dtype != NVL_EXPERT_AUTO && dtype != NVL_EXPERT_FP8_E4M3) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: unknown expert dtype");
+    if (dtype == NVL_EXPERT_FP8_E4M3) {
+        if (!m->cfg.use_moe || m->cfg.num_experts <= 0) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: the model has no MoE layers");
+        if (m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: 8-bit experts need bf16 precision");
+        if (!m->w8) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: 8-bit experts need 8-bit projection weights (nvl_set_weight_dtype first)");
+    }
+    m->e8 = dtype == NVL_EXPERT_FP8_E4M3;
     return NVL_OK;
 }
 
@@ -917,11 +942,36 @@ extern "C" int nvl_finalize(nvl_model* m) {
                     auto one = swiglu_interleave(I, e * 2 * I);
                     idx.insert(idx.end(), one.begin(), one.end());
                 }
+                const bool dense_form = I % 32 == 0 && H % 16 == 0 && E <= 64 && E / moe_down_slices((int)E) <= 16;
+                if (l.t[NVL_T_MOE_IN].scale) {     // 8-bit experts (nvl_set_expert_dtype): codes + scales follow the interleave
+                    const int64_t np = round_up(E * 2 * I, W_ROW_PAD), hp = round_up(H, W_ROW_PAD);
+                    idx.resize((size_t)np, -1);
+                    l.moe_in = dmalloc_bytes(np * H);
+                    l.s_moe_in = dmalloc<float>(np);
+                    gather_rows_w8(m, l.t[NVL_T_MOE_IN], idx, l.moe_in, l.s_moe_in, H);
+                    // down: codes [H_pad][E*I] (the decode form's layout; the tile path dequantizes from it), scales [E][H_pad]
+                    const DevTensor& d = l.t[NVL_T_MOE_OUT];
+                    l.moe_out8 = dmalloc_bytes(hp * E * I);
+                    l.s_moe_out = dmalloc<float>(E * hp);
+                    NVL_HIP(hipMemsetAsync(l.moe_out8, 0, (size_t)(hp * E * I), m->stream));
+                    hipLaunchKernelGGL(moe_cat_down_w8_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream,
+                                       (const uint8_t*)d.p, (uint8_t*)l.moe_out8, (int)H, (int)I, (int)E);
+                    NVL_HIP(hipGetLastError());
+                    std::vector<float> sd((size_t)d.rows_pad), so((size_t)(E * hp), 1.0f);
+                    NVL_HIP(hipMemcpy(sd.data(), d.scale, sd.size() * 4, hipMemcpyDeviceToHost));
+                    for (int64_t e = 0; e < E; e++)
+                        for (int64_t r = 0; r < H; r++) so[(size_t)(e * hp + r)] = sd[(size_t)(e * H + r)];
+                    NVL_HIP(hipMemcpy(l.s_moe_out, so.data(), so.size() * 4, hipMemcpyHostToDevice));
+                    NVL_HIP(hipStreamSynchronize(m->stream));
+                    if (dense_form) l.moe_out_cat = l.moe_out8;
+                    for (int k : {NVL_T_MOE_IN, NVL_T_MOE_OUT}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].scale); l.t[k].scale = nullptr; }
+                    continue;
+                }
                 l.moe_in = dmalloc_bytes(round_up(E * 2 * I, W_ROW_PAD) * H * (int64_t)m->wsize);   // (+ zero pad rows: the decode kernels read whole tiles)
                 NVL_HIP(hipMemsetAsync(l.moe_in, 0, (size_t)(round_up(E * 2 * I, W_ROW_PAD) * H) * m->wsize, m->stream));
                 gather_rows(m, l.t[NVL_T_MOE_IN].p, idx, l.moe_in, H);
                 dfree(l.t[NVL_T_MOE_IN].p); l.t[NVL_T_MOE_IN].p = nullptr;
-                if (I % 32 == 0 && H % 16 == 0 && E <= 64 && E / moe_down_slices((int)E) <= 16) {
+                if (dense_form) {
                     // decode form: the experts' down matrices side by side along K
                     const int64_t hp = round_up(H, W_ROW_PAD);
                     l.moe_out_cat = dmalloc_bytes(hp * E * I * 2);
@@ -964,6 +1014,18 @@ extern "C" int nvl_finalize(nvl_model* m) {
         }
         m->w8_scratch_elems = big;
         if (big) m->w8_scratch = dmalloc<bf16_t>(big);
+        if (m->e8) {   // 8-bit experts: the codes by pointer (decode dispatch), and the scratch of one layer's W~ (up, then down)
+            const int64_t E = c.num_experts, I = m->F, hp = round_up(H, W_ROW_PAD);
+            for (auto& l : m->layers) {
+                if (!l.s_moe_in) continue;
+                m->w8_map[l.moe_in] = nvl_model::W8Ref{l.s_moe_in, round_up(E * 2 * I, W_ROW_PAD)};
+                if (l.moe_out_cat) m->w8_map[l.moe_out_cat] = nvl_model::W8Ref{l.s_moe_out, hp};
+            }
+            // (down: the grouped GEMMs read whole 256-row tiles of the last expert past its H rows)
+            m->e8_scratch_elems = std::max(round_up(E * 2 * I, W_ROW_PAD) * H, (E * H + 2 * W_ROW_PAD) * I);
+            m->e8_scratch = dmalloc<bf16_t>(m->e8_scratch_elems);
+            NVL_HIP(hipMemsetAsync(m->e8_scratch, 0, (size_t)m->e8_scratch_elems * 2, m->stream));
+        }
         if (m->a8) {   // the activation codes + row scales of the W8A8 tile step: every row of a batch, the widest K
             int64_t kmax = H;
             for (auto& l : m->layers) {
@@ -1704,9 +1766,11 @@ void ffn_up(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false) {
 // (m-tiles mapped to (expert, row segment) by a device table; token rows gathered by per-lane source address)
 // -> combine in rank order into x (with the residual multiplier).  The fp32 parity mode launches per expert.
 // can this call take the decode ("dense-masked") MoE form?  (also decides whether the O projection may carry the FFN norm)
+// (the down form's per-wave live-block mask is 32 bits wide: an expert of more than 32 blocks of U k-steps — U = 4 up to 32
+// rows, 2 above — would lose the blocks past 32, so such widths take the grouped form: I > 4096, or I > 2048 above 32 rows)
 bool moe_dense_ok(const nvl_model* m, const LayerW& l, int M) {
     return !m->f32 && M <= 64 && g_moe_dense && l.moe_out_cat && m->moe_part && !m->keep_hidden && m->H % 4 == 0 &&
-           m->H <= 1024 * NORM_ROW_MAXCH && g_force_tile == 0;
+           m->H <= 1024 * NORM_ROW_MAXCH && g_force_tile == 0 && (m->F >> 5) / (M <= 32 ? 4 : 2) <= 32;
 }
 // deferred_norm: m->xn holds xn_raw = bf16(x * w_norm) and m->rs_part the x^2 partials (the O projection carried the FFN
 // norm): the router and the expert-up projection scale their accumulators by rstd[m] instead of reading a normed operand
@@ -1719,6 +1783,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
     const int pairs = M * k;
     // algorithmic weight bytes of the expert GEMMs: the experts a batch of `pairs` (token, rank) pairs can touch, once
     const double e_touch = (double)std::min(E, pairs);
+    const double eb = m->e8 ? 1.0 : (double)m->wsize;     // bytes per expert weight (8-bit experts: codes; scales not counted)
     m->site = KS_MOE_ROUTER;
     const bool dense = moe_dense_ok(m, l, M) && m->pending_slices == 0;
     // decode: router logits, softmax, top-k and the dense gate matrix in one launch (gemm.h moe_router_gate_kernel)
@@ -1748,10 +1813,11 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
         GemmArgs a = mk(m->xn, H, l.moe_in, m->moe_hall, E * I, nullptr, 1.f, M, E * 2 * I, H);
         a.moe_gate = m->moe_gate; a.moe_E = E; a.moe_I = I;
         if (deferred_norm) set_deferred_in(m, a);
-        m->site = KS_MOE_UP; m->site_bytes = (e_touch * 2 * I * H + (double)M * H + e_touch * M * I) * (double)m->wsize;
+        m->site = KS_MOE_UP; m->site_bytes = e_touch * 2 * I * H * eb + ((double)M * H + e_touch * M * I) * (double)m->wsize;
         gemm(m, EPI_SWIGLU, false, a, 2.0 * pairs * 2 * I * H);
         const int nks = (E * I) >> 5, spe = I >> 5;
-        if (next_norm_w && g_moe_defer_down && nks % 64 == 0 && spe % 4 == 0 && nks / 16 <= 4 * spe && nks / 64 <= 32) {
+        // (8-bit experts: no producer form — a wave's live blocks cross experts, the scale would change with the block)
+        if (next_norm_w && g_moe_defer_down && !m->e8 && nks % 64 == 0 && spe % 4 == 0 && nks / 16 <= 4 * spe && nks / 64 <= 32) {
             // (the launcher's conditions: 16 waves, whole blocks of 4 k-steps inside one expert, <= 4 experts per wave)
             GemmArgs d = mk(m->moe_hall, E * I, l.moe_out_cat, m->x, H, nullptr, m->resid_alpha, M, H, E * I);
             d.moe_gate = m->moe_gate; d.moe_E = E; d.moe_I = I;
@@ -1764,7 +1830,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
         GemmArgs d = mk(m->moe_hall, E * I, l.moe_out_cat, m->x, H, nullptr, 1.f, M, H, E * I);
         const int nsl = moe_down_slices(E);
         d.moe_gate = m->moe_gate; d.moe_E = E; d.moe_I = I; d.sk_part = m->moe_part; d.sk_slices = nsl;
-        m->site = KS_MOE_DOWN; m->site_bytes = (e_touch * H * I + e_touch * M * I) * (double)m->wsize + (double)nsl * M * H * 4.0;
+        m->site = KS_MOE_DOWN; m->site_bytes = e_touch * H * I * eb + e_touch * M * I * (double)m->wsize + (double)nsl * M * H * 4.0;
         gemm(m, EPI_RESID, true, d, 2.0 * pairs * H * I);
         m->pending_part = m->moe_part; m->pending_slices = nsl; m->pending_rows = M; m->pending_alpha = m->resid_alpha;
         return false;
@@ -1828,9 +1894,26 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
             a.A = m->moe_xg; a.a_rows = nullptr;
         }
         a.w_expert_stride = (int64_t)2 * I * H; a.grp_bm = pp ? 512 : BM; a.grp_deep = small && g_moe_deep;
+        // 8-bit experts: the grouped GEMMs run on this layer's W~, dequantized into one scratch buffer — up first, then down
+        // over it, in stream order (the down dequantize starts after the up GEMM has read the scratch)
+        const void* w_down = l.t[NVL_T_MOE_OUT].p;
+        if (m->e8) {
+            KScope ks(m, KC_OTHER, 0, KS_MOE_UP, (double)round_up(E * 2 * I, W_ROW_PAD) * H * 3.0);
+            w8_dequant_rows(m->stream, l.moe_in, l.s_moe_in, H, 0, round_up(E * 2 * I, W_ROW_PAD), m->e8_scratch);
+            NVL_HIP(hipGetLastError());
+            a.W = m->e8_scratch;
+        }
         m->site = KS_MOE_UP; m->site_bytes = (e_touch * 2 * I * H + (double)pairs * H + (double)pairs * I) * (double)m->wsize;
         gemm(m, EPI_SWIGLU, false, a, 2.0 * pairs * 2 * I * H);
-        GemmArgs d = mk(m->hbuf, I, l.t[NVL_T_MOE_OUT].p, m->moe_eo, H, nullptr, 1.f, max_mtiles, H, I);
+        if (m->e8) {
+            KScope ks(m, KC_OTHER, 0, KS_MOE_DOWN, (double)E * H * I * 3.0);
+            const int64_t n8 = (int64_t)E * H * I / 8;
+            hipLaunchKernelGGL(e8_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out8,
+                               l.s_moe_out, H, I, E, round_up(H, W_ROW_PAD), n8, m->e8_scratch);
+            NVL_HIP(hipGetLastError());
+            w_down = m->e8_scratch;
+        }
+        GemmArgs d = mk(m->hbuf, I, w_down, m->moe_eo, H, nullptr, 1.f, max_mtiles, H, I);
         d.tile_map = m->moe_tile_map; d.n_mtiles = m->moe_n_mtiles; d.w_expert_stride = (int64_t)H * I; d.grp_bm = pp ? 512 : BM; d.grp_deep = small && g_moe_deep;
         m->site = KS_MOE_DOWN; m->site_bytes = (e_touch * H * I + (double)pairs * I) * (double)m->wsize + (double)pairs * H * 4.0;
         gemm(m, EPI_STORE, true, d, 2.0 * pairs * H * I);

@@ -12,6 +12,9 @@
 //       row chunks that fit.
 // Storage: the codes in the bf16 fragment-major order, one byte per element ([rows_pad][K] bytes), scales [rows_pad]
 // (pad rows: codes 0, scale 1).
+// MoE experts (nvl_set_expert_dtype, §9 f-8): the same contract with one scale per (expert, output row).  Decode streams the
+// codes through gemm_skinny_moe_fp8w_kernel / gemm_skinny_wide_moe_fp8w_kernel; every other MoE launch runs the unchanged
+// grouped GEMMs on one layer's W~, dequantized (up, then down) into a scratch buffer.
 #pragma once
 #include "kv8.h"
 #include "gemm.h"
@@ -158,6 +161,29 @@ __global__ __launch_bounds__(256) void decode_seam_w8_kernel(const float* __rest
     norm_row_finish<bf16_t>(v, ww, bb, b, eps, y, r, H, red);
 }
 
+// 8-bit MoE experts (nvl_set_expert_dtype).  The down codes are stored once, in the decode form's layout:
+// [H_pad][E*I] bytes, fragment-major with K = E*I (expert e's k-steps e*I/32 .. (e+1)*I/32 - 1 of every 16-row tile), scales
+// [E][H_pad].  moe_cat_down_w8_kernel builds it from the uploaded [E*H][I] codes (moe_cat_down_kernel's byte form).
+__global__ __launch_bounds__(256) void moe_cat_down_w8_kernel(const uint8_t* __restrict__ src, uint8_t* __restrict__ dst, int H, int I, int E) {
+    const int nt = blockIdx.x, e = blockIdx.y, kbs = I >> 5;
+    const u32x2* s8 = (const u32x2*)(src + ((int64_t)e * H * I + (int64_t)nt * kbs * 512));
+    u32x2* d8 = (u32x2*)(dst + ((int64_t)nt * E * kbs + (int64_t)e * kbs) * 512);
+    for (int i = threadIdx.x; i < kbs * 64; i += 256) d8[i] = s8[i];
+}
+
+// the tile path's per-expert W~ of the down projection from the stored [H_pad][E*I] codes: out [E][H][I] bf16, fragment-major
+// per expert (expert e at e*H*I: the grouped GEMMs' w_expert_stride), n8 = E*H*I/8 groups of 8 elements, H % 16 == 0
+__global__ __launch_bounds__(256) void e8_dequant_down_kernel(const uint8_t* __restrict__ codes, const float* __restrict__ scale,
+                                                              int H, int I, int E, int64_t hp, int64_t n8, bf16_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    const int64_t per_e = (int64_t)H * I / 8, kbs = I >> 5;
+    const int64_t e = i / per_e, j = i - e * per_e;            // j = (tile * kbs + ks) * 64 + lane
+    const int64_t lane = j & 63, blk = j >> 6, tile = blk / kbs, ks = blk - tile * kbs;
+    const int64_t src = ((tile * E * kbs + e * kbs + ks) * 64 + lane) * 8;
+    *(bf16x8*)(out + i * 8) = w8_frag(*(const u32x2*)(codes + src), scale[e * hp + tile * 16 + (lane & 15)]);
+}
+
 // W~ of rows [row0, row0 + rows) (row0 % 16 == 0) into dst, fragment-major
 static inline void w8_dequant_rows(hipStream_t st, const void* codes, const float* scale, int64_t K, int64_t row0, int64_t rows,
                                    bf16_t* dst) {
@@ -174,6 +200,10 @@ template <int EPI, typename OutT>
 static inline void launch_gemm_w8(hipStream_t st, const GemmArgs& a, const float* ws, int64_t w_rows_pad, bf16_t* scratch,
                                   int64_t scratch_elems, const A8Buf* a8 = nullptr) {
     if (a.tile_map || a.seg || a.a_rows) throw std::runtime_error("gemm: an 8-bit weight in a gathered / grouped launch");
+    if (a.moe_gate) {     // 8-bit MoE experts, the decode (dense-masked) form: the only launch that reads their codes
+        if (launch_gemm_skinny_bf16<EPI, OutT, true>(st, a, ws)) return;
+        throw std::runtime_error("gemm: an 8-bit MoE projection did not fit the decode kernels");
+    }
     if (launch_gemm_skinny_bf16<EPI, OutT, true>(st, a, ws)) return;
     if constexpr (EPI != EPI_QKV) {     // (the 64-row-group condition of launch_gemm_bf16, unchanged)
         const bool few_tiles = cdiv(a.M, 128) * cdiv(a.N, 128) < g_chunk_min_tiles;

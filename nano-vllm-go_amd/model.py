@@ -47,7 +47,7 @@ class HipTransformerModel:
                  max_seqs: int = 8, max_batch_tokens: int | None = None, tp_rank: int = 0, tp_size: int = 1,
                  tp_force_single: bool = False, kv_num_blocks: int = 0, kv_block_size: int = 0,
                  kv_cache_dtype: str = "auto", kv_scales=None, weight_dtype: str = "auto",
-                 act_dtype: str = "auto"):
+                 act_dtype: str = "auto", expert_dtype: str = "auto"):
         """tensors=None defers finalize(): upload() each tensor, then call finalize().
         tp_size > 1 makes this the tp_rank-th tensor-parallel shard: pass the FULL tensors, the library keeps
         its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests).
@@ -56,7 +56,9 @@ class HipTransformerModel:
         weight_dtype="fp8_e4m3": 8-bit projection weights with per-row scales (nvl_set_weight_dtype; bf16 precision, no TP);
         the model computes with W~ = bf16(s * e4m3(q)), which get_weight returns.
         act_dtype="fp8_e4m3" (needs weight_dtype="fp8_e4m3"): W8A8 — the projections on the tile (prefill) GEMM path quantize
-        their activation rows to e4m3 with one scale per row and multiply codes x codes (nvl_set_act_dtype)."""
+        their activation rows to e4m3 with one scale per row and multiply codes x codes (nvl_set_act_dtype).
+        expert_dtype="fp8_e4m3" (needs weight_dtype="fp8_e4m3", a MoE model): the experts' weights are 8-bit too, one scale per
+        (expert, output row) (nvl_set_expert_dtype); otherwise the experts stay bf16."""
         self.cfg = dict(cfg)
         self.lib = L.lib()
         self.h = C.c_void_p()
@@ -78,10 +80,16 @@ class HipTransformerModel:
             raise ValueError(f"act_dtype must be one of {sorted(L.ACT_DTYPE)}")
         if act_dtype != "auto" and weight_dtype != "fp8_e4m3":
             raise ValueError('act_dtype="fp8_e4m3" needs weight_dtype="fp8_e4m3"')
+        if expert_dtype not in L.EXPERT_DTYPE:
+            raise ValueError(f"expert_dtype must be one of {sorted(L.EXPERT_DTYPE)}")
+        if expert_dtype != "auto" and weight_dtype != "fp8_e4m3":
+            raise ValueError('expert_dtype="fp8_e4m3" needs weight_dtype="fp8_e4m3"')
         L.check(self.lib.nvl_create(C.byref(self._c), C.byref(opts), C.byref(self.h)))
         self.weight_dtype = weight_dtype
         self.act_dtype = act_dtype
+        self.expert_dtype = expert_dtype
         for setter, table, value in ((self.lib.nvl_set_weight_dtype, L.WEIGHT_DTYPE, weight_dtype),
+                                     (self.lib.nvl_set_expert_dtype, L.EXPERT_DTYPE, expert_dtype),
                                      (self.lib.nvl_set_act_dtype, L.ACT_DTYPE, act_dtype)):
             if value == "auto":
                 continue

@@ -42,6 +42,7 @@ type Options struct {
 	KVCacheDType   int  // C.NVL_KV_AUTO (0) or C.NVL_KV_FP8_E4M3 (1): 8-bit K/V, twice the tokens per byte of cache
 	WeightDType    int  // C.NVL_W_AUTO (0) or C.NVL_W_FP8_E4M3 (1): 8-bit projection weights with per-row scales
 	ActDType       int  // C.NVL_ACT_AUTO (0) or C.NVL_ACT_FP8_E4M3 (1): W8A8 prefill projections (needs WeightDType 1)
+	ExpertDType    int  // C.NVL_EXPERT_AUTO (0) or C.NVL_EXPERT_FP8_E4M3 (1): 8-bit MoE expert weights (needs WeightDType 1)
 }
 
 // HipModelRunner implements nanovllm.ModelRunner on one MI355X.
@@ -333,7 +334,14 @@ func create(cfg *C.nvl_model_config, o Options) (*HipModelRunner, error) {
 			return nil, err
 		}
 	}
-	if o.ActDType != 0 { // right after the weight dtype (nvl_set_act_dtype)
+	if o.ExpertDType != 0 { // right after the weight dtype, before the experts are uploaded (nvl_set_expert_dtype)
+		if rc := C.nvl_set_expert_dtype(r.h, C.int(o.ExpertDType)); rc != 0 {
+			err := fmt.Errorf("nvl_set_expert_dtype: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
+			C.nvl_destroy(r.h)
+			return nil, err
+		}
+	}
+	if o.ActDType != 0 { // after the weight dtype (nvl_set_act_dtype)
 		if rc := C.nvl_set_act_dtype(r.h, C.int(o.ActDType)); rc != 0 {
 			err := fmt.Errorf("nvl_set_act_dtype: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
 			C.nvl_destroy(r.h)
