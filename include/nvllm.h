@@ -192,6 +192,27 @@ int nvl_set_act_dtype(nvl_model* m, int dtype);
  * it takes MOE_IN / MOE_OUT too: rows = E * out, cols = in, scales [E * out] (expert e's rows e*out .. e*out + out - 1). */
 int nvl_upload_tensor_fp8(nvl_model* m, int kind, int layer, const uint8_t* codes, const float* scales, int64_t rows,
                           int64_t cols, int layout);
+/* MXFP4 storage of the projection weights: OCP e2m1 elements with one e8m0 scale per block of 32
+ * consecutive input features of one output row.  The reference keeps every weight fp32 (generic_loader.go:398-403,
+ * loadTensorFromData); this is the library's own opt-in, reached only through this call. */
+enum {
+    NVL_MX_NONE = 0,       /* no MX storage: today's behaviour                                                            */
+    NVL_MX_FP4_E2M1 = 1    /* WQ/WK/WV/WKV/WO/W1/W2 as e2m1 codes.  Per 32-block: e = clamp(floor(log2(amax)) - 2, -120, 125)
+                            * (0 for an all-zero block), stored as E = e + 127; q = e2m1_rne(|w| / 2^e) on {0, .5, 1, 1.5, 2, 3,
+                            * 4, 6}, ties to the even mantissa bit, saturating at 6; the sign is bit 3.  Every path computes with
+                            * W~ = +-grid[q] * 2^e (exact in bf16); nvl_get_weight returns W~; nvl_stats.weight_bytes counts
+                            * codes + scales.  LM head, embeddings, router, Mamba2 projections and MoE experts stay bf16. */
+};
+/* After nvl_create, before the first 2-D upload (else NVL_ERR_STATE).  NVL_ERR_INVALID for an unknown value, and for
+ * NVL_MX_FP4_E2M1 with f32 precision, tensor parallelism or NVL_W_FP8_E4M3 (which in turn is refused once MX is set, and
+ * with it nvl_set_act_dtype / nvl_set_expert_dtype).  In MX mode nvl_upload_tensor refuses a non-finite weight. */
+int nvl_set_mx_weight_dtype(nvl_model* m, int dtype);
+/* Pre-quantized MXFP4 weight, taken as it is: codes [rows][cols/2], two per byte with the even input feature in the low
+ * nibble (OCP MX order), scales [rows][cols/32] e8m0 bytes, both in the checkpoint's [out, in] order (layout must be
+ * NVL_LAYOUT_OUT_IN).  NVL_ERR_INVALID for a kind this model does not store as MXFP4, a shape mismatch, cols % 32 != 0,
+ * and a scale byte outside [7, 252] (0xff is the e8m0 NaN). */
+int nvl_upload_tensor_mxfp4(nvl_model* m, int kind, int layer, const uint8_t* codes, const uint8_t* scales, int64_t rows,
+                            int64_t cols, int layout);
 
 /* ---- lifecycle ---- */
 
@@ -457,6 +478,11 @@ int nvl_op_attention_kv8(int device, const float* q, const float* k, const float
  * codes_out [N][K] / scales_out [N] (either may be NULL) receive the quantized weight.  K % 64 == 0. */
 int nvl_op_matmul_fp8w(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* codes_out,
                        float* scales_out);
+/* MXFP4 weights (NVL_MX_FP4_E2M1): as nvl_op_matmul_fp8w — w [K][N] quantized by the upload quantizer, c = bf16(a) · W~
+ * through the model's dispatch (M selects the decode kernels, the 64-row groups or dequantize + tile).  K % 64 == 0.
+ * codes_out [N][K/2] and scales_out [N][K/32] (either may be NULL) return the codes in nvl_upload_tensor_mxfp4's packing. */
+int nvl_op_matmul_mxfp4w(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* codes_out,
+                         uint8_t* scales_out);
 /* 8-bit weights and activations (NVL_ACT_FP8_E4M3): as nvl_op_matmul_fp8w, through the model's dispatch in W8A8 mode.  M
  * selects the decode form (bf16(a) · W~, bit-identical to nvl_op_matmul_fp8w) or the tile form, where bf16(a) is quantized
  * per row and c = (sum_k e4m3(q_a) e4m3(q_w)) * s_a[m] * s_w[n].  a_codes_out [M][K] / a_scales_out [M] (either may be NULL)

@@ -618,6 +618,16 @@ __device__ __forceinline__ u32x2 weight_load8(const u32x2* p) {
     if constexpr (KEEP) return *p;
     else return __builtin_nontemporal_load(p);
 }
+template <bool KEEP>
+__device__ __forceinline__ uint32_t weight_load4(const uint32_t* p) {
+    if constexpr (KEEP) return *p;
+    else return __builtin_nontemporal_load(p);
+}
+template <bool KEEP>
+__device__ __forceinline__ uint8_t weight_load1(const uint8_t* p) {
+    if constexpr (KEEP) return *p;
+    else return __builtin_nontemporal_load(p);
+}
 // eight e4m3fn codes of one weight row -> the bf16 MFMA fragment of W~ = bf16_rne(s * e4m3(q)): the exact conversion to
 // fp32 (v_cvt_pk_f32_fp8, OCP e4m3fn on gfx950), one fp32 multiply by the row scale, one RNE rounding to bf16
 __device__ __forceinline__ bf16x8 w8_frag(u32x2 c, float s) {
@@ -629,6 +639,18 @@ __device__ __forceinline__ bf16x8 w8_frag(u32x2 c, float s) {
         o[4 * h + 2] = (__bf16)(b[0] * s); o[4 * h + 3] = (__bf16)(b[1] * s);
     }
     return o;
+}
+// weight formats of the decode bodies below (gemm_skinny_body / gemm_skinny_wide_body)
+enum { WF_BF16 = 0, WF_FP8 = 1, WF_MXFP4 = 2 };
+// MXFP4 (w4.h): eight e2m1 codes of one weight row (4 bytes, even k in the low nibble) and the e8m0 byte E of
+// their 32-k block -> the bf16 MFMA fragment of W~ = +-grid[q] * 2^(E - 127).  2^(E - 127) is the fp32 with exponent field E
+// (E in [7, 252]: a normal number), and the product is exact in bf16: v_cvt_scalef32_pk_bf16_fp4 rounds nothing.
+__device__ __forceinline__ bf16x8 w4_frag(uint32_t c, uint32_t E) {
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+    const float s = __builtin_bit_cast(float, E << 23);
+    const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, s, 1),
+                   d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, s, 2), e = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, s, 3);
+    return bf16x8{a[0], a[1], b[0], b[1], d[0], d[1], e[0], e[1]};
 }
 
 // m_passes > 1: block id -> (weight block, 64-row activation group).  Ids that differ by 8 share an XCD and are
@@ -867,8 +889,11 @@ __global__ __launch_bounds__(1024) void gemm_skinny_bf16_kernel(GemmArgs p) {
 // body is gemm_skinny_bf16_kernel's with the weight load replaced (W8 = false reproduces it); the bf16 kernel keeps its
 // own copy because instantiating it from this body changed its instruction schedule and register count, and the bf16
 // kernels are kept byte-identical in the device assembly.
-template <int MT, int NTW, int U, int EPI, typename OutT, bool PASSES, bool MOE, bool HALF, bool W8>
+// WF = WF_MXFP4 (w4.h): the codes are nibble-packed in the same fragment order (a lane loads 4 bytes per k-step, a 16-row x
+// 32-k block is 256 bytes) and w_scale points at the e8m0 bytes, [16-row tile][k-step][16 rows]: one byte per weight fragment.
+template <int MT, int NTW, int U, int EPI, typename OutT, bool PASSES, bool MOE, bool HALF, int WF>
 __device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scale) {
+    constexpr bool W8 = WF == WF_FP8, MX = WF == WF_MXFP4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* red = (f32x4*)smem;                       // [NTW][ksplit][MT][64]
     const int swg = blockIdx.y * gridDim.x + blockIdx.x;
@@ -936,15 +961,28 @@ __device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scal
     int wsc_row = (nt0 + tile) * 16 + fr;
     if constexpr (MOE && W8 && EPI == EPI_RESID) wsc_row += (ks0 / (p.moe_I >> 5)) * (int)((p.N + W_ROW_PAD - 1) / W_ROW_PAD * W_ROW_PAD);
     const float wsc = W8 ? w_scale[wsc_row] : 1.0f;
-    auto wload = [&](int64_t s) -> bf16x8 { return w8_frag(weight_load8<PASSES>((const u32x2*)(wq + s * 512)), wsc); };
+    // MXFP4: this lane's 4 code bytes and its row's scale byte of k-step ks0 (then +256 / +16 bytes per k-step)
+    // (computed in the MXFP4 instantiations only: the fp8 ones keep their device assembly)
+    const uint8_t* mq = MX ? (const uint8_t*)p.W + (((int64_t)(nt0 + tile) * (p.K >> 5) + ks0) * 64 + lane) * 4 : nullptr;
+    const uint8_t* me = MX ? (const uint8_t*)w_scale + ((int64_t)(nt0 + tile) * (p.K >> 5) + ks0) * 16 + fr : nullptr;
+    auto mxraw = [&](int64_t s) -> u32x2 {     // {codes, E}
+        return u32x2{weight_load4<PASSES>((const uint32_t*)(mq + s * 256)), (uint32_t)weight_load1<PASSES>(me + s * 16)};
+    };
+    auto wload = [&](int64_t s) -> bf16x8 {
+        if constexpr (MX) { const u32x2 r = mxraw(s); return w4_frag(r[0], r[1]); }
+        else return w8_frag(weight_load8<PASSES>((const u32x2*)(wq + s * 512)), wsc);
+    };
     // W8: a block's registers hold the raw codes; they are converted where the MFMAs consume them (comp_blk).  Converting
     // at the load put the conversion inside the HALF form's predicated load, and the compiler then waited for every load
     // (vmcnt(0)) before issuing the next one: O / FFN-down at B <= 16 ran at about half speed.  MT = 4 (64-row groups,
     // never HALF) converts at the load: holding raw codes there spilled 14-26 registers against the 128-register budget.
-    constexpr bool RAW = W8 && MT <= 2;
+    // MXFP4 holds raw codes at every MT: {codes, E} is two registers against the fragment's four, and converting at the load
+    // spilled 22-30 registers at MT = 4.
+    constexpr bool RAW = (W8 && MT <= 2) || MX;
     typedef typename std::conditional<RAW, u32x2, bf16x8>::type WReg;
     auto wfrag = [&](const WReg& w) -> bf16x8 {
-        if constexpr (RAW) return w8_frag(w, wsc);
+        if constexpr (RAW && MX) return w4_frag(w[0], w[1]);
+        else if constexpr (RAW) return w8_frag(w, wsc);
         else return w;
     };
     const bf16_t* xp[MT];
@@ -970,8 +1008,9 @@ __device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scal
     auto load_blk = [&](WReg (&w)[U], bf16x8 (&x)[U][MT], int b) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
-            if constexpr (RAW) w[u] = (!HALF || w_live) ? weight_load8<PASSES>((const u32x2*)(wq + (int64_t)(b * U + u) * 512)) : u32x2{0u, 0u};
-            else if constexpr (W8) w[u] = (!HALF || w_live) ? wload((int64_t)(b * U + u)) : x_zero;
+            if constexpr (RAW && MX) w[u] = (!HALF || w_live) ? mxraw((int64_t)(b * U + u)) : u32x2{0u, 127u};
+            else if constexpr (RAW) w[u] = (!HALF || w_live) ? weight_load8<PASSES>((const u32x2*)(wq + (int64_t)(b * U + u) * 512)) : u32x2{0u, 0u};
+            else if constexpr (W8 || MX) w[u] = (!HALF || w_live) ? wload((int64_t)(b * U + u)) : x_zero;
             else if constexpr (HALF) w[u] = w_live ? weight_load<PASSES>((const bf16x8*)(wp + (int64_t)(b * U + u) * 512)) : x_zero;
             else w[u] = weight_load<PASSES>((const bf16x8*)(wp + (int64_t)(b * U + u) * 512));
 #pragma unroll
@@ -1029,7 +1068,7 @@ __device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scal
     if (b < nblk) comp_blk(wA, xA);
     }
     for (int s = nblk * U; s < (tail_live ? my_steps : 0); s++) {      // ragged tail: fewer than U k-steps
-        const bf16x8 w = w_live ? (W8 ? wload((int64_t)s) : weight_load<PASSES>((const bf16x8*)(wp + (int64_t)s * 512))) : x_zero;
+        const bf16x8 w = w_live ? ((W8 || MX) ? wload((int64_t)s) : weight_load<PASSES>((const bf16x8*)(wp + (int64_t)s * 512))) : x_zero;
 #pragma unroll
         for (int i = 0; i < MT; i++)
             acc[i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, x_live[i] ? *(const bf16x8*)(xp[i] + (int64_t)s * 512) : x_zero, acc[i], 0, 0, 0);
@@ -1097,14 +1136,19 @@ __device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scal
 
 template <int MT, int NTW, int U, int EPI, typename OutT, bool PASSES = false, bool HALF = false>
 __global__ __launch_bounds__(1024) void gemm_skinny_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
-    gemm_skinny_body<MT, NTW, U, EPI, OutT, PASSES, false, HALF, true>(p, w_scale);
+    gemm_skinny_body<MT, NTW, U, EPI, OutT, PASSES, false, HALF, WF_FP8>(p, w_scale);
+}
+// MXFP4-weight form of the narrow kernel (w4.h): the same body, w_scales = the e8m0 block scales beside the code tiles
+template <int MT, int NTW, int U, int EPI, typename OutT, bool PASSES = false, bool HALF = false>
+__global__ __launch_bounds__(1024) void gemm_skinny_mxfp4w_kernel(GemmArgs p, const uint8_t* __restrict__ w_scales) {
+    gemm_skinny_body<MT, NTW, U, EPI, OutT, PASSES, false, HALF, WF_MXFP4>(p, (const float*)w_scales);
 }
 // 8-bit MoE experts (nvl_set_expert_dtype): the MoE decode instantiation of the same body — expert skip,
 // gate weight in the SwiGLU epilogue; the down projection's scales are [E][H_pad] (one per expert and output row), K-split
 // form only (each wave one expert).  The deferred-norm producer form, whose waves cross experts, has no 8-bit instance.
 template <int MT, int NTW, int U, int EPI, typename OutT>
 __global__ __launch_bounds__(1024) void gemm_skinny_moe_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
-    gemm_skinny_body<MT, NTW, U, EPI, OutT, false, true, false, true>(p, w_scale);
+    gemm_skinny_body<MT, NTW, U, EPI, OutT, false, true, false, WF_FP8>(p, w_scale);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1376,8 +1420,9 @@ __global__ __launch_bounds__(512) void gemm_skinny_wide_bf16_kernel(GemmArgs p) 
 }
 
 // fp8-weight form of the wide kernel (see gemm_skinny_body)
-template <int MT, int NTB, int U, int EPI, typename OutT, bool PASSES, bool MOE, bool W8>
+template <int MT, int NTB, int U, int EPI, typename OutT, bool PASSES, bool MOE, int WF>
 __device__ __forceinline__ void gemm_skinny_wide_body(GemmArgs p, const float* w_scale) {
+    constexpr bool W8 = WF == WF_FP8, MX = WF == WF_MXFP4;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* red = (f32x4*)smem;                       // [ksplit][NTB][MT][64]
     const int swg = blockIdx.x;
@@ -1403,10 +1448,20 @@ __device__ __forceinline__ void gemm_skinny_wide_body(GemmArgs p, const float* w
     float wsc[NTB];
 #pragma unroll
     for (int t = 0; t < NTB; t++) wsc[t] = W8 ? w_scale[(nt0 + t) * 16 + fr] : 1.0f;
-    auto wload = [&](int t, int64_t s) -> bf16x8 { return w8_frag(weight_load8<PASSES>((const u32x2*)(wq + t * tile_stride + s * 512)), wsc[t]); };
-    typedef typename std::conditional<W8, u32x2, bf16x8>::type WReg;     // raw codes until the MFMAs (see gemm_skinny_body)
+    // MXFP4 (see gemm_skinny_body): 256 code bytes and 16 scale bytes per (16-row tile, k-step)
+    const uint8_t* mq = MX ? (const uint8_t*)p.W + (((int64_t)nt0 * nks + ks0) * 64 + lane) * 4 : nullptr;
+    const uint8_t* me = MX ? (const uint8_t*)w_scale + ((int64_t)nt0 * nks + ks0) * 16 + fr : nullptr;
+    auto mxraw = [&](int t, int64_t s) -> u32x2 {     // {codes, E}
+        return u32x2{weight_load4<PASSES>((const uint32_t*)(mq + ((int64_t)t * nks + s) * 256)), (uint32_t)weight_load1<PASSES>(me + ((int64_t)t * nks + s) * 16)};
+    };
+    auto wload = [&](int t, int64_t s) -> bf16x8 {
+        if constexpr (MX) { const u32x2 r = mxraw(t, s); return w4_frag(r[0], r[1]); }
+        else return w8_frag(weight_load8<PASSES>((const u32x2*)(wq + t * tile_stride + s * 512)), wsc[t]);
+    };
+    typedef typename std::conditional<W8 || MX, u32x2, bf16x8>::type WReg;     // raw codes until the MFMAs (see gemm_skinny_body)
     auto wfrag = [&](const WReg& w, int t) -> bf16x8 {
-        if constexpr (W8) return w8_frag(w, wsc[t]);
+        if constexpr (MX) return w4_frag(w[0], w[1]);
+        else if constexpr (W8) return w8_frag(w, wsc[t]);
         else return w;
     };
     const bf16_t* xp = (const bf16_t*)p.A + ((int64_t)ks0 * 64 + lane) * 8;
@@ -1426,7 +1481,8 @@ __device__ __forceinline__ void gemm_skinny_wide_body(GemmArgs p, const float* w
         for (int u = 0; u < U; u++) {
 #pragma unroll
             for (int t = 0; t < NTB; t++)
-                if constexpr (W8) w[u][t] = weight_load8<PASSES>((const u32x2*)(wq + t * tile_stride + (int64_t)(b * U + u) * 512));
+                if constexpr (MX) w[u][t] = mxraw(t, (int64_t)(b * U + u));
+                else if constexpr (W8) w[u][t] = weight_load8<PASSES>((const u32x2*)(wq + t * tile_stride + (int64_t)(b * U + u) * 512));
                 else w[u][t] = weight_load<PASSES>((const bf16x8*)(wp + t * tile_stride + (int64_t)(b * U + u) * 512));
 #pragma unroll
             for (int i = 0; i < MT; i++) x[u][i] = *(const bf16x8*)(xp + i * tile_stride + (int64_t)(b * U + u) * 512);
@@ -1458,7 +1514,7 @@ __device__ __forceinline__ void gemm_skinny_wide_body(GemmArgs p, const float* w
         for (int i = 0; i < MT; i++) xs[i] = *(const bf16x8*)(xp + i * tile_stride + (int64_t)s * 512);
 #pragma unroll
         for (int t = 0; t < NTB; t++) {
-            const bf16x8 w = W8 ? wload(t, (int64_t)s) : weight_load<PASSES>((const bf16x8*)(wp + t * tile_stride + (int64_t)s * 512));
+            const bf16x8 w = (W8 || MX) ? wload(t, (int64_t)s) : weight_load<PASSES>((const bf16x8*)(wp + t * tile_stride + (int64_t)s * 512));
 #pragma unroll
             for (int i = 0; i < MT; i++) acc[t][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w, xs[i], acc[t][i], 0, 0, 0);
         }
@@ -1495,12 +1551,16 @@ __device__ __forceinline__ void gemm_skinny_wide_body(GemmArgs p, const float* w
 
 template <int MT, int NTB, int U, int EPI, typename OutT, bool PASSES = false>
 __global__ __launch_bounds__(512) void gemm_skinny_wide_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
-    gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, PASSES, false, true>(p, w_scale);
+    gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, PASSES, false, WF_FP8>(p, w_scale);
+}
+template <int MT, int NTB, int U, int EPI, typename OutT, bool PASSES = false>
+__global__ __launch_bounds__(512) void gemm_skinny_wide_mxfp4w_kernel(GemmArgs p, const uint8_t* __restrict__ w_scales) {
+    gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, PASSES, false, WF_MXFP4>(p, (const float*)w_scales);
 }
 // 8-bit MoE experts: the wide form of the expert up projection (SwiGLU, gate weight in the epilogue)
 template <int MT, int NTB, int U, int EPI, typename OutT>
 __global__ __launch_bounds__(512) void gemm_skinny_wide_moe_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
-    gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, false, true, true>(p, w_scale);
+    gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, false, true, WF_FP8>(p, w_scale);
 }
 
 static int g_chunk_max_m = 512;    // largest M that uses 64-row passes of the decode form at all (nvl_set_tuning key 11; 64 = off)
@@ -1518,14 +1578,14 @@ static int g_x_mask = 1;            // nvl_set_tuning key 24: decode kernels ski
 static int g_force_ntw = 0, g_force_ksplit = 0;   // tuning overrides (nvl_bench_gemm only)
 static int g_force_tile = 0;                      // 0 automatic, 1: 128x128x2st, 2: 256x128x3st, 3: 256x256x2st, 5: ping-pong 256x256
 
-template <int EPI, typename OutT, bool W8 = false>
+template <int EPI, typename OutT, int WF = 0>
 static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a, const float* ws = nullptr);
 constexpr int DEFER_MAX_M = 128;    // deferred RMSNorm (decode): rows of the x^2 partial buffer.  Above 64 rows the producer
                                     // runs as 64-row groups like every narrow projection (one workgroup per 16-row tile
                                     // was measured at M = 128: -13 %); above 128 rows FFN-up belongs on the tile kernels
 static inline int skinny_rows(const GemmArgs& a) { return a.m_passes > 1 && a.M > 64 ? 64 : a.M; }   // rows a workgroup covers
 // the groups of 64 rows as separate launches (weight-block count not a multiple of 8, or key 13 = 0)
-template <int EPI, typename OutT, bool W8 = false>
+template <int EPI, typename OutT, int WF = 0>
 static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
     for (int r0 = 0; r0 < a.M; r0 += 64) {
         GemmArgs c = a;
@@ -1538,7 +1598,7 @@ static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a
             c.C = (float*)a.C + (int64_t)r0 * a.ldc; c.nrm_xn = a.nrm_xn + (int64_t)r0 * a.N;
             c.rs_out = a.rs_out + (int64_t)r0 * (a.N >> 4);
         }
-        if (!launch_gemm_skinny_bf16<EPI, OutT, W8>(st, c, ws)) return false;
+        if (!launch_gemm_skinny_bf16<EPI, OutT, WF>(st, c, ws)) return false;
     }
     return true;
 }
@@ -1546,11 +1606,12 @@ static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a
 // skinny dispatch: M <= 64, no gather/segments.  Returns false when the shape is not eligible.
 // W8: the same decisions, the fp8-weight kernels (ws: the per-row weight scales).  8-bit MoE experts (moe_gate) take the
 // K-split down form and the SwiGLU up form; the deferred-norm producer form of the down projection has no 8-bit instance.
-template <int NTW, int EPI, typename OutT, bool W8 = false>
+template <int NTW, int EPI, typename OutT, int WF = 0>
 static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
+    constexpr bool W8 = WF == WF_FP8, MX = WF == WF_MXFP4;     // (MX: ws carries the e8m0 scale bytes, w4.h)
     const int MT = skinny_rows(a) <= 16 ? 1 : (skinny_rows(a) <= 32 ? 2 : 4);
     if (EPI == EPI_RESID && a.m_split && a.rs_out && NTW == 1 && a.m_passes <= 1 && a.grid_y != 1) {   // (m_split: grid_y unused, keep it defined)
-        GemmArgs c = a; c.grid_y = 1; return launch_gemm_skinny_ntw<NTW, EPI, OutT, W8>(st, c, ws);
+        GemmArgs c = a; c.grid_y = 1; return launch_gemm_skinny_ntw<NTW, EPI, OutT, WF>(st, c, ws);
     }
     const int U = MT <= 2 ? 4 : 2;                       // register budget: (1+MT)*U*2 fragments
     const int nblocks = cdiv(cdiv(a.N, 16), NTW);        // weight rows are padded to 128: all tiles exist
@@ -1561,7 +1622,7 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
         while (ks > 1 && (a.K >> 5) / ks < 4) ks >>= 1;
         if (a.K % 32 != 0) return false;
         if constexpr (EPI == EPI_RESID) {
-            if (a.moe_gate && W8) return false;     // (no 8-bit instance: a wave's blocks cross experts, see moe())
+            if (a.moe_gate && (W8 || MX)) return false;     // (no 8-bit instance: a wave's blocks cross experts, see moe())
             if (a.moe_gate) {     // MoE down as the deferred-norm producer: all experts in one workgroup's K range, 16 waves
                 ks = 16;
                 const int nks = a.K >> 5, spe = a.moe_I >> 5;
@@ -1578,7 +1639,10 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
             }
             if (a.rs_half) {      // <= 16 rows: 8 weight rows per workgroup, twice the workgroups (HALF above)
                 if (a.M > 16) return false;
-                if constexpr (W8)
+                if constexpr (MX)
+                    hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<1, NTW, 4, EPI, OutT, false, true>), dim3(2 * nblocks, 1), dim3(NTW * ks * 64),
+                                       (size_t)NTW * ks * 64 * 16, st, a, (const uint8_t*)ws);
+                else if constexpr (W8)
                     hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<1, NTW, 4, EPI, OutT, false, true>), dim3(2 * nblocks, 1), dim3(NTW * ks * 64),
                                        (size_t)NTW * ks * 64 * 16, st, a, ws);
                 else
@@ -1587,7 +1651,10 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
                 return true;
             }
         }
-        if constexpr (W8)
+        if constexpr (MX)
+            hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<1, NTW, 4, EPI, OutT>), dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64),
+                               (size_t)NTW * ks * 64 * 16, st, a, (const uint8_t*)ws);
+        else if constexpr (W8)
             hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<1, NTW, 4, EPI, OutT>), dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64),
                                (size_t)NTW * ks * 64 * 16, st, a, ws);
         else
@@ -1612,10 +1679,18 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
     }
     if (a.K % 32 != 0) return false;
     const size_t lds = (size_t)NTW * ksplit * MT * 64 * 16;
-    if (a.m_passes > 1 && (nblocks % 8 != 0 || KS != 1)) return launch_skinny_passes_serial<EPI, OutT, W8>(st, a, ws);
+    if (a.m_passes > 1 && (nblocks % 8 != 0 || KS != 1)) return launch_skinny_passes_serial<EPI, OutT, WF>(st, a, ws);
     dim3 grid(nblocks * (a.m_passes > 1 ? a.m_passes : 1), KS), block(NTW * ksplit * 64);
-    if (a.grid_y != KS) { GemmArgs c = a; c.grid_y = KS; return launch_gemm_skinny_ntw<NTW, EPI, OutT, W8>(st, c, ws); }
-    if constexpr (W8) {
+    if (a.grid_y != KS) { GemmArgs c = a; c.grid_y = KS; return launch_gemm_skinny_ntw<NTW, EPI, OutT, WF>(st, c, ws); }
+    if constexpr (MX) {
+        const uint8_t* es = (const uint8_t*)ws;
+        if (a.moe_gate) return false;                     // (the experts stay bf16 in an MXFP4 model)
+        if (a.m_passes > 1) hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<4, NTW, 2, EPI, OutT, true>), grid, block, lds, st, a, es);
+        else if (MT == 1) hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<1, NTW, 4, EPI, OutT>), grid, block, lds, st, a, es);
+        else if (MT == 2) hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<2, NTW, 4, EPI, OutT>), grid, block, lds, st, a, es);
+        else hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<4, NTW, 2, EPI, OutT>), grid, block, lds, st, a, es);
+        return true;
+    } else if constexpr (W8) {
         if (a.moe_gate) {                                 // 8-bit MoE experts
             if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
                 if (a.m_passes > 1) return false;
@@ -1654,10 +1729,10 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
 // tok/s (+2.4 %), B=20 +3.1 %, Falcon-7B B=32 +4.7 %, Llama-3-8B / Granite B=32 +0.8 %; the LM head (thousands of groups
 // either way) is indifferent, and 64-row launches (MT = 4) lose 2 % (profiles/r03_wide_tiles_per_wave.txt).
 static int g_wide_ntb = 0;
-template <int EPI, typename OutT, int NTB = 4, bool W8 = false>
+template <int EPI, typename OutT, int NTB = 4, int WF = 0>
 static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
     if constexpr (NTB == 4) {
-        if (g_wide_ntb == 2 || (g_wide_ntb == 0 && skinny_rows(a) <= 32 && a.N < 65536)) return launch_gemm_skinny_wide<EPI, OutT, 2, W8>(st, a, ws);
+        if (g_wide_ntb == 2 || (g_wide_ntb == 0 && skinny_rows(a) <= 32 && a.N < 65536)) return launch_gemm_skinny_wide<EPI, OutT, 2, WF>(st, a, ws);
     }
     if (a.K % 32 != 0 || a.sk_part) return false;
     const int groups = cdiv(cdiv(a.N, 16), NTB);     // weight rows are padded to 256: every tile of a group exists
@@ -1671,8 +1746,21 @@ static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, co
     else { while (ksplit > 2 && groups * ksplit > 512) ksplit >>= 1; if (groups >= 1024) ksplit = 1; }   // LM head: one wave per group (cold sweep: 96 vs 104 us)
     while (ksplit > 1 && (a.K >> 5) / ksplit < U) ksplit >>= 1;
     const size_t lds = (size_t)ksplit * NTB * MT * 64 * 16;
-    if (a.m_passes > 1 && groups % 8 != 0) return launch_skinny_passes_serial<EPI, OutT, W8>(st, a, ws);
+    if (a.m_passes > 1 && groups % 8 != 0) return launch_skinny_passes_serial<EPI, OutT, WF>(st, a, ws);
     const int wgs = groups * (a.m_passes > 1 ? a.m_passes : 1);
+    constexpr bool W8 = WF == WF_FP8, MX = WF == WF_MXFP4;
+    if constexpr (MX) {
+#define NVL_SKW4(MTv, Uv, Pv)                                                                                            \
+    do {                                                                                                               \
+        NVL_LDS_ATTR((gemm_skinny_wide_mxfp4w_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), 8 * NTB * MTv * 64 * 16);          \
+        hipLaunchKernelGGL((gemm_skinny_wide_mxfp4w_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), dim3(wgs), dim3(ksplit * 64),    \
+                           lds, st, a, (const uint8_t*)ws);                                                            \
+    } while (0)
+        if (a.moe_gate) return false;
+        if (a.m_passes > 1) NVL_SKW4(4, 2, true); else if (MT == 1) NVL_SKW4(1, 4, false); else if (MT == 2) NVL_SKW4(2, 4, false); else NVL_SKW4(4, 2, false);
+#undef NVL_SKW4
+        return true;
+    }
     if constexpr (W8) {
 #define NVL_SKW8(MTv, Uv, Pv)                                                                                            \
     do {                                                                                                               \
@@ -1723,7 +1811,7 @@ static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, co
 #undef NVL_SKWM
     return true;
 }
-template <int EPI, typename OutT, bool W8>
+template <int EPI, typename OutT, int WF>
 static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a0, const float* ws) {
     if (EPI == EPI_QKV) return false;               // prefill-only epilogue (a decode workgroup owns 16 columns, not a head)
     if (skinny_rows(a0) > 64 || a0.a_rows || a0.seg || a0.tile_map) return false;
@@ -1732,12 +1820,12 @@ static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a0, c
     if constexpr (EPI == EPI_SWIGLU || EPI == EPI_STORE || EPI == EPI_GELU) {
         // wide-N form once its 64-row groups fill the chip (g_force_ntw: 8 forces it, 1/2/4 force the narrow form)
         const bool wide_ok = skinny_rows(a) > 16 && cdiv(a.N, 64) >= 256 && !a.sk_part;   // M <= 16: the narrow form streams as fast
-        if (g_force_ntw == 8 || (g_force_ntw == 0 && wide_ok)) { if (launch_gemm_skinny_wide<EPI, OutT, 4, W8>(st, a, ws)) return true; }
+        if (g_force_ntw == 8 || (g_force_ntw == 0 && wide_ok)) { if (launch_gemm_skinny_wide<EPI, OutT, 4, WF>(st, a, ws)) return true; }
     }
-    if (EPI == EPI_SWIGLU) return launch_gemm_skinny_ntw<2, EPI, OutT, W8>(st, a, ws);
-    if (g_force_ntw == 2) return launch_gemm_skinny_ntw<2, EPI, OutT, W8>(st, a, ws);
-    if constexpr (!W8) { if (g_force_ntw == 4) return launch_gemm_skinny_ntw<4, EPI, OutT>(st, a); }   // (tuning only: no fp8 form)
-    return launch_gemm_skinny_ntw<1, EPI, OutT, W8>(st, a, ws);
+    if (EPI == EPI_SWIGLU) return launch_gemm_skinny_ntw<2, EPI, OutT, WF>(st, a, ws);
+    if (g_force_ntw == 2) return launch_gemm_skinny_ntw<2, EPI, OutT, WF>(st, a, ws);
+    if constexpr (WF == WF_BF16) { if (g_force_ntw == 4) return launch_gemm_skinny_ntw<4, EPI, OutT>(st, a); }   // (tuning only: no fp8 form)
+    return launch_gemm_skinny_ntw<1, EPI, OutT, WF>(st, a, ws);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int STAGES, int EPI, typename OutT>

@@ -17,6 +17,7 @@
 #include "sample.h"
 #include "gemm.h"
 #include "w8.h"
+#include "w4.h"
 #include "mamba.h"
 #include "tp_p2p.h"
 
@@ -25,6 +26,7 @@ namespace nvl {
 struct DevTensor {
     void* p = nullptr;      // canonical device copy: 2-D [rows_pad][cols] in weight dtype, 1-D fp32
     float* scale = nullptr; // 8-bit weights (w8.h): p holds e4m3fn codes, scale[rows_pad] the per-row fp32 scales
+    uint8_t* mxs = nullptr; // MXFP4 weights (w4.h): p holds the nibble-packed e2m1 codes, mxs the e8m0 block scales
     int64_t rows = 0, cols = 0, rows_pad = 0;
     bool present() const { return p != nullptr; }
 };
@@ -35,6 +37,7 @@ struct LayerW {
     void* w_qkv = nullptr; int n_qkv = 0; float* b_qkv = nullptr;
     void* w1 = nullptr; int n1 = 0;      // fused rows (2F for SwiGLU, F for GELU)
     float* s_qkv = nullptr; float* s1 = nullptr;   // 8-bit weights: the row scales of w_qkv / w1 (they follow the fused rows)
+    uint8_t* e_qkv = nullptr; uint8_t* e1 = nullptr;   // MXFP4 weights: the block scales of w_qkv / w1 (they follow the 16-row tiles)
     void* moe_in = nullptr;              // [E][2I (interleaved in bf16 mode)][H]
     void* moe_out_cat = nullptr;         // bf16: W_down of all experts along K, [H_pad][E*I] (decode "dense-masked" form)
     // 8-bit experts (nvl_set_expert_dtype): moe_in holds codes in the same interleaved order, s_moe_in [rows_pad] its row
@@ -94,6 +97,11 @@ struct nvl_model {
     std::map<const void*, W8Ref> w8_map;   // finalized 8-bit weights by code pointer (gemm() dispatch)
     nvl::bf16_t* w8_scratch = nullptr; int64_t w8_scratch_elems = 0;   // W~ of the tile path (largest non-LM-head projection)
     float* lm_head_scale = nullptr;
+    // MXFP4 projection weights (nvl_set_mx_weight_dtype NVL_MX_FP4_E2M1, w4.h): e2m1 codes + e8m0 block scales; the tile
+    // path's W~ goes through w8_scratch (the two modes exclude each other)
+    bool mx = false;
+    struct W4Ref { const uint8_t* scales; int64_t rows_pad; };
+    std::map<const void*, W4Ref> w4_map;   // finalized MXFP4 weights by code pointer (gemm() dispatch)
     // 8-bit MoE experts (nvl_set_expert_dtype NVL_EXPERT_FP8_E4M3, w8.h): W~ of one layer's experts for the grouped GEMMs
     bool e8 = false;
     bool expert_uploaded = false;          // an expert tensor has been uploaded: the expert dtype is fixed from then on

@@ -154,8 +154,9 @@ void gemm(nvl_model* m, int epi, bool out_f32, GemmArgs a, double flops = -1.0) 
     a.stamps = (m->stamping && !m->f32 && a.M <= 64 && !a.tile_map) ? next_stamps(m, m->site, STAMP_MAX_WG) : nullptr;
     // algorithmic bytes of a projection: every weight byte once + the activation operand + the output rows
     const bool w8 = m->w8 && m->w8_map.count(a.W);     // 8-bit weight: one byte per element + the row scales
+    const bool w4 = m->mx && m->w4_map.count(a.W);     // MXFP4 weight: half a byte per element + a scale byte per 32
     const double gbytes = m->site_bytes > 0 ? m->site_bytes
-        : (double)a.N * a.K * (w8 ? 1.0 : (double)m->wsize) + (w8 ? 4.0 * a.N : 0.0) + (double)a.M * a.K * (double)m->wsize
+        : (double)a.N * a.K * (w4 ? 0.5 + 1.0 / 32 : w8 ? 1.0 : (double)m->wsize) + (w8 ? 4.0 * a.N : 0.0) + (double)a.M * a.K * (double)m->wsize
           + (double)a.M * a.N * (out_f32 || epi == EPI_RESID ? 4.0 : (double)m->wsize);
     KScope ks(m, KC_GEMM, flops >= 0 ? flops : 2.0 * (double)a.M * (double)a.N * (double)a.K, -1, gbytes);
     hipStream_t st = m->stream;
@@ -180,6 +181,24 @@ void gemm(nvl_model* m, int epi, bool out_f32, GemmArgs a, double flops = -1.0) 
             NVL_HIP(hipGetLastError());
             return;
         }
+    }
+    if (w4) {     // an MXFP4 weight (w4.h): the same dispatch on the MXFP4-weight kernels / dequantize + tile
+        const auto& ref = m->w4_map.find(a.W)->second;
+        const uint8_t* es = ref.scales;
+        const int64_t rp = ref.rows_pad;
+        switch (epi) {
+            case EPI_STORE:
+                if (out_f32) launch_gemm_w4<EPI_STORE, float>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems);
+                else launch_gemm_w4<EPI_STORE, bf16_t>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems);
+                break;
+            case EPI_RESID:  launch_gemm_w4<EPI_RESID, float>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems); break;
+            case EPI_SWIGLU: launch_gemm_w4<EPI_SWIGLU, bf16_t>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems); break;
+            case EPI_GELU:   launch_gemm_w4<EPI_GELU, bf16_t>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems); break;
+            case EPI_QKV:    launch_gemm_w4<EPI_QKV, bf16_t>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems); break;
+            default: throw std::runtime_error("gemm: bad epilogue");
+        }
+        NVL_HIP(hipGetLastError());
+        return;
     }
     if (m->f32) {
         switch (epi) {
@@ -353,11 +372,11 @@ extern "C" void nvl_destroy(nvl_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
-    for (int k = 0; k < NVL_T_COUNT; k++) { dfree(m->g[k].p); dfree(m->g[k].scale); }
+    for (int k = 0; k < NVL_T_COUNT; k++) { dfree(m->g[k].p); dfree(m->g[k].scale); dfree(m->g[k].mxs); }
     for (auto& l : m->layers) {
-        for (int k = 0; k < NVL_T_COUNT; k++) { dfree(l.t[k].p); dfree(l.t[k].scale); }
+        for (int k = 0; k < NVL_T_COUNT; k++) { dfree(l.t[k].p); dfree(l.t[k].scale); dfree(l.t[k].mxs); }
         dfree(l.w_qkv); dfree(l.b_qkv); dfree(l.w1); dfree(l.moe_in); dfree(l.moe_out_cat);
-        dfree(l.s_qkv); dfree(l.s1);
+        dfree(l.s_qkv); dfree(l.s1); dfree(l.e_qkv); dfree(l.e1);
         if (l.moe_out_cat != l.moe_out8) dfree(l.moe_out8);
         dfree(l.s_moe_in); dfree(l.s_moe_out);
     }
@@ -449,6 +468,52 @@ void upload_2d_w8(nvl_model* m, DevTensor* t, const void* data, int dtype, int64
     if (h_bad) { dfree(t->p); dfree(t->scale); t->p = nullptr; t->scale = nullptr;
                  throw std::runtime_error("nvl_upload_tensor: a weight is not finite (8-bit weights refuse NaN / Inf)"); }
     m->stats.weight_bytes += (double)Npad * K + (double)Npad * 4;
+}
+
+// is this 2-D kind stored as MXFP4 in an MX model (nvl_set_mx_weight_dtype)?  The attention and FFN projections only: the LM
+// head, both embeddings, the router, the Mamba2 projections and the MoE experts stay bf16.
+bool w4_kind(const nvl_model* m, int kind) {
+    if (!m->mx) return false;
+    switch (kind) {
+        case NVL_T_WQ: case NVL_T_WK: case NVL_T_WV: case NVL_T_WKV: case NVL_T_WO: case NVL_T_W1: case NVL_T_W2: return true;
+        default: return false;
+    }
+}
+
+// codes [Npad][K/2] zeroed, block scales [Npad/16][K/32][16] = 127 (2^0)
+void w4_alloc(nvl_model* m, DevTensor* t, int64_t Npad, int64_t K) {
+    dfree(t->p); dfree(t->mxs);
+    t->p = dmalloc_bytes(Npad * K / 2);
+    t->mxs = (uint8_t*)dmalloc_bytes(Npad * K / 32);
+    NVL_HIP(hipMemsetAsync(t->p, 0, (size_t)(Npad * K / 2), m->stream));
+    NVL_HIP(hipMemsetAsync(t->mxs, 127, (size_t)(Npad * K / 32), m->stream));
+}
+
+// MXFP4 weight (tensor parallelism is refused in this mode: the tensor is always whole): fp32 [N][K] on the device, then
+// w4_quant_rows_kernel -> codes + block scales in the device layout (w4.h)
+void upload_2d_w4(nvl_model* m, DevTensor* t, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out) {
+    if (K % 32 != 0) throw std::runtime_error("MXFP4 weights: the input width must be a multiple of 32");
+    const size_t esz = dtype == NVL_DTYPE_F32 ? 4 : 2;
+    void* raw = dmalloc_bytes(N * K * (int64_t)esz);
+    NVL_HIP(hipMemcpyAsync(raw, data, (size_t)(N * K) * esz, hipMemcpyDefault, m->stream));
+    float* f = dmalloc<float>(N * K);
+    hipLaunchKernelGGL((convert_2d_kernel<float, false>), dim3((unsigned)cdiv(K, 32), (unsigned)cdiv(N, 32)), dim3(256), 0,
+                       m->stream, raw, dtype, src_is_in_out ? 1 : 0, f, N, K, Slice2D{N, K, 0, 0, 0});
+    NVL_HIP(hipGetLastError());
+    const int64_t Npad = round_up(N, W_ROW_PAD);
+    w4_alloc(m, t, Npad, K);
+    int* bad = dmalloc<int>(1);
+    NVL_HIP(hipMemsetAsync(bad, 0, 4, m->stream));
+    hipLaunchKernelGGL(w4_quant_rows_kernel, dim3((unsigned)N), dim3(64), 0, m->stream, (const float*)f, K, (uint8_t*)t->p, t->mxs, bad);
+    NVL_HIP(hipGetLastError());
+    int h_bad = 0;
+    NVL_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, m->stream));
+    NVL_HIP(hipStreamSynchronize(m->stream));
+    dfree(bad); dfree(f); dfree(raw);
+    t->rows = N; t->cols = K; t->rows_pad = Npad;
+    if (h_bad) { dfree(t->p); dfree(t->mxs); t->p = nullptr; t->mxs = nullptr;
+                 throw std::runtime_error("nvl_upload_tensor: a weight is not finite (MXFP4 weights refuse NaN / Inf)"); }
+    m->stats.weight_bytes += (double)Npad * K / 2 + (double)Npad * K / 32;
 }
 
 void upload_2d(nvl_model* m, DevTensor* t, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out,
@@ -601,6 +666,10 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
         upload_2d_w8(m, t, data, dtype, SN, SK, io);
         return NVL_OK;
     }
+    if (w4_kind(m, kind)) {     // (tp == 1: nvl_set_mx_weight_dtype refuses tensor parallelism)
+        upload_2d_w4(m, t, data, dtype, SN, SK, io);
+        return NVL_OK;
+    }
     if (m->tp == 1) {
         upload_2d(m, t, data, dtype, SN, SK, io, Slice2D{SN, SK, 0, 0, 0}, SN, true);
         return NVL_OK;
@@ -671,6 +740,45 @@ extern "C" int nvl_upload_tensor_fp8(nvl_model* m, int kind, int layer, const ui
     dfree(raw);
     t->rows = rows; t->cols = cols; t->rows_pad = Npad;
     m->stats.weight_bytes += (double)Npad * cols + (double)Npad * 4;
+    return NVL_OK;
+    NVL_CATCH(m)
+}
+
+// pre-quantized MXFP4 weight in the ABI packing: codes [rows][cols/2] (even k in the low nibble), e8m0 scales [rows][cols/32]
+extern "C" int nvl_upload_tensor_mxfp4(nvl_model* m, int kind, int layer, const uint8_t* codes, const uint8_t* scales,
+                                       int64_t rows, int64_t cols, int layout) {
+    if (!m || !codes || !scales) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: null argument");
+    if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_upload_tensor_mxfp4: model already finalized");
+    if (!w4_kind(m, kind)) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: not an MXFP4 weight kind of this model (nvl_set_mx_weight_dtype)");
+    if (layout != NVL_LAYOUT_OUT_IN) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
+    DevTensor* t = tensor_slot(m, kind, layer);
+    if (!t) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: bad kind or layer");
+    const int64_t SN = full_out(m, kind), SK = full_in(m, kind);
+    if (rows != SN || cols != SK || SK % 32 != 0) {
+        char buf[160];
+        snprintf(buf, sizeof buf, "nvl_upload_tensor_mxfp4: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld], in %% 32 == 0", kind,
+                 (long long)rows, (long long)cols, (long long)SN, (long long)SK);
+        return fail(m, NVL_ERR_INVALID, buf);
+    }
+    for (int64_t i = 0; i < rows * (cols / 32); i++)
+        if (scales[i] < W4_E_MIN + 127 || scales[i] > W4_E_MAX + 127)
+            return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: a scale byte is outside [7, 252] (0xff is the e8m0 NaN)");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    m->w2d_uploaded = true;
+    const int64_t Npad = round_up(rows, W_ROW_PAD);
+    w4_alloc(m, t, Npad, cols);
+    uint8_t* raw = (uint8_t*)dmalloc_bytes(rows * cols / 2);
+    uint8_t* raw_s = (uint8_t*)dmalloc_bytes(rows * cols / 32);
+    NVL_HIP(hipMemcpy(raw, codes, (size_t)(rows * cols / 2), hipMemcpyHostToDevice));
+    NVL_HIP(hipMemcpy(raw_s, scales, (size_t)(rows * cols / 32), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(w4_place_kernel, dim3((unsigned)cdiv(rows * cols / 8, 256)), dim3(256), 0, m->stream, (const uint8_t*)raw,
+                       (const uint8_t*)raw_s, rows, cols, (uint8_t*)t->p, t->mxs);
+    NVL_HIP(hipGetLastError());
+    NVL_HIP(hipStreamSynchronize(m->stream));
+    dfree(raw); dfree(raw_s);
+    t->rows = rows; t->cols = cols; t->rows_pad = Npad;
+    m->stats.weight_bytes += (double)Npad * cols / 2 + (double)Npad * cols / 32;
     return NVL_OK;
     NVL_CATCH(m)
 }
@@ -782,6 +890,28 @@ void gather_rows_w8(nvl_model* m, const DevTensor& src, const std::vector<int32_
     NVL_HIP(hipStreamSynchronize(m->stream));
     dfree(didx);
 }
+// gather_rows for an MXFP4 weight: a 16-row tile is 8*K code bytes and K/2 scale bytes, both contiguous; pad tiles
+// (idx < 0) get zero bytes in both (W~ = 0; their outputs are never stored)
+void gather_rows_w4(nvl_model* m, const DevTensor& src, const std::vector<int32_t>& idx, void* dst, uint8_t* dst_scales, int64_t K) {
+    if (idx.size() % 16) throw std::runtime_error("gather_rows: row count must be a multiple of 16");
+    std::vector<int32_t> use(idx.size() / 16);
+    for (size_t t = 0; t < use.size(); t++) {
+        const int32_t r0 = idx[t * 16];
+        for (int c = 1; c < 16; c++)
+            if ((r0 < 0) != (idx[t * 16 + c] < 0) || (r0 >= 0 && (idx[t * 16 + c] != r0 + c || (r0 & 15))))
+                throw std::runtime_error("gather_rows: permutation does not preserve 16-row tiles");
+        use[t] = r0 < 0 ? -1 : r0 / 16;
+    }
+    int32_t* didx = dmalloc<int32_t>((int64_t)use.size());
+    NVL_HIP(hipMemcpyAsync(didx, use.data(), use.size() * 4, hipMemcpyHostToDevice, m->stream));
+    hipLaunchKernelGGL((gather_rows_kernel<uint8_t>), dim3((unsigned)use.size()), dim3(256), 0, m->stream,
+                       (const uint8_t*)src.p, didx, (uint8_t*)dst, 8 * K);
+    hipLaunchKernelGGL((gather_rows_kernel<uint8_t>), dim3((unsigned)use.size()), dim3(256), 0, m->stream,
+                       (const uint8_t*)src.mxs, didx, dst_scales, K / 2);
+    NVL_HIP(hipGetLastError());
+    NVL_HIP(hipStreamSynchronize(m->stream));
+    dfree(didx);
+}
 // the fused FFN-up weight of a layer (SwiGLU: gate|up rows interleaved in blocks of 16)
 void fuse_w1(nvl_model* m, LayerW& l, bool swiglu) {
     const int64_t H = m->H;
@@ -789,7 +919,12 @@ void fuse_w1(nvl_model* m, LayerW& l, bool swiglu) {
         auto idx = swiglu_interleave(m->F, 0);
         const int64_t np = round_up(l.n1, W_ROW_PAD);
         idx.resize((size_t)np, -1);
-        if (l.t[NVL_T_W1].scale) {
+        if (l.t[NVL_T_W1].mxs) {
+            l.w1 = dmalloc_bytes(np * H / 2);
+            l.e1 = (uint8_t*)dmalloc_bytes(np * H / 32);
+            gather_rows_w4(m, l.t[NVL_T_W1], idx, l.w1, l.e1, H);
+            dfree(l.t[NVL_T_W1].mxs); l.t[NVL_T_W1].mxs = nullptr;
+        } else if (l.t[NVL_T_W1].scale) {
             l.w1 = dmalloc_bytes(np * H);
             l.s1 = dmalloc<float>(np);
             gather_rows_w8(m, l.t[NVL_T_W1], idx, l.w1, l.s1, H);
@@ -802,6 +937,7 @@ void fuse_w1(nvl_model* m, LayerW& l, bool swiglu) {
     } else {
         l.w1 = l.t[NVL_T_W1].p; l.t[NVL_T_W1].p = nullptr;
         l.s1 = l.t[NVL_T_W1].scale; l.t[NVL_T_W1].scale = nullptr;
+        l.e1 = l.t[NVL_T_W1].mxs; l.t[NVL_T_W1].mxs = nullptr;
     }
 }
 
@@ -834,8 +970,24 @@ extern "C" int nvl_set_weight_dtype(nvl_model* m, int dtype) {
     if (dtype == NVL_W_FP8_E4M3 && m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights need bf16 precision");
     if (dtype == NVL_W_FP8_E4M3 && (m->tp > 1 || m->tp_force))
         return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights are not available with tensor parallelism");
+    if (dtype == NVL_W_FP8_E4M3 && m->mx)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: the model stores MXFP4 weights (nvl_set_mx_weight_dtype)");
     m->w8 = dtype == NVL_W_FP8_E4M3;
     if (!m->w8) m->a8 = m->e8 = false;     // (8-bit activations and experts need 8-bit weights)
+    return NVL_OK;
+}
+
+extern "C" int nvl_set_mx_weight_dtype(nvl_model* m, int dtype) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: no model");
+    if (m->finalized || m->w2d_uploaded)
+        return fail(m, NVL_ERR_STATE, "nvl_set_mx_weight_dtype: call it after nvl_create and before the first 2-D weight upload");
+    if (dtype != NVL_MX_NONE && dtype != NVL_MX_FP4_E2M1) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: unknown MX weight dtype");
+    if (dtype == NVL_MX_FP4_E2M1 && m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: MXFP4 weights need bf16 precision");
+    if (dtype == NVL_MX_FP4_E2M1 && (m->tp > 1 || m->tp_force))
+        return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: MXFP4 weights are not available with tensor parallelism");
+    if (dtype == NVL_MX_FP4_E2M1 && m->w8)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores 8-bit weights (nvl_set_weight_dtype)");
+    m->mx = dtype == NVL_MX_FP4_E2M1;
     return NVL_OK;
 }
 
@@ -896,11 +1048,24 @@ extern "C" int nvl_finalize(nvl_model* m) {
         const int64_t nq = (int64_t)m->nH * hd, nkv = (int64_t)m->nKV * hd;
         const int64_t npad = round_up(m->n_qkv, W_ROW_PAD);
         const bool q8 = l.t[NVL_T_WQ].scale != nullptr;    // 8-bit weights: codes move like bf16 rows, scales beside them
+        const bool q4 = l.t[NVL_T_WQ].mxs != nullptr;      // MXFP4 weights: half a byte per element, H/32 scale bytes per row
         const size_t we = q8 ? 1 : m->wsize;
-        l.w_qkv = dmalloc_bytes(npad * H * (int64_t)we);
-        NVL_HIP(hipMemsetAsync(l.w_qkv, 0, (size_t)(npad * H) * we, m->stream));
+        const size_t rowb = q4 ? (size_t)H / 2 : (size_t)H * we;
+        l.w_qkv = dmalloc_bytes(npad * (int64_t)rowb);
+        NVL_HIP(hipMemsetAsync(l.w_qkv, 0, (size_t)npad * rowb, m->stream));
         char* dst = (char*)l.w_qkv;
-        const size_t rowb = (size_t)H * we;
+        if (q4) {     // (row counts are multiples of 16: whole tiles, as for the codes)
+            const size_t rs = (size_t)H / 32;
+            l.e_qkv = (uint8_t*)dmalloc_bytes(npad * (int64_t)rs);
+            NVL_HIP(hipMemsetAsync(l.e_qkv, 127, (size_t)npad * rs, m->stream));
+            NVL_HIP(hipMemcpyAsync(l.e_qkv, l.t[NVL_T_WQ].mxs, nq * rs, hipMemcpyDeviceToDevice, m->stream));
+            if (mqa) {
+                NVL_HIP(hipMemcpyAsync(l.e_qkv + nq * rs, l.t[NVL_T_WKV].mxs, 2 * hd * rs, hipMemcpyDeviceToDevice, m->stream));
+            } else {
+                NVL_HIP(hipMemcpyAsync(l.e_qkv + nq * rs, l.t[NVL_T_WK].mxs, nkv * rs, hipMemcpyDeviceToDevice, m->stream));
+                NVL_HIP(hipMemcpyAsync(l.e_qkv + (nq + nkv) * rs, l.t[NVL_T_WV].mxs, nkv * rs, hipMemcpyDeviceToDevice, m->stream));
+            }
+        }
         if (q8) {
             l.s_qkv = dmalloc<float>(npad);
             const std::vector<float> ones((size_t)npad, 1.0f);
@@ -929,7 +1094,8 @@ extern "C" int nvl_finalize(nvl_model* m) {
             if (l.t[NVL_T_BV].present()) NVL_HIP(hipMemcpyAsync(l.b_qkv + nq + nkv, l.t[NVL_T_BV].p, nkv * 4, hipMemcpyDeviceToDevice, m->stream));
         }
         NVL_HIP(hipStreamSynchronize(m->stream));
-        for (int k : {NVL_T_WQ, NVL_T_WK, NVL_T_WV, NVL_T_WKV}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].scale); l.t[k].scale = nullptr; }
+        for (int k : {NVL_T_WQ, NVL_T_WK, NVL_T_WV, NVL_T_WKV}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].scale); l.t[k].scale = nullptr;
+                                                                  dfree(l.t[k].mxs); l.t[k].mxs = nullptr; }
 
         // ---- FFN / MoE
         if (c.use_moe) {
@@ -994,6 +1160,20 @@ extern "C" int nvl_finalize(nvl_model* m) {
     // ---- LM head: tied (or absent) => the token embedding itself, already [Vpad][H] K-contiguous
     if (!c.tied_embedding && m->g[NVL_T_LM_HEAD].present()) { m->lm_head = m->g[NVL_T_LM_HEAD].p; m->lm_head_scale = m->g[NVL_T_LM_HEAD].scale; }
     else { m->lm_head = m->g[NVL_T_TOK_EMB].p; m->lm_head_scale = m->g[NVL_T_TOK_EMB].scale; }   // generic_loader.go:255-259
+    if (m->mx) {   // the MXFP4 weights by code pointer (gemm() dispatch) and the dequantize scratch of the tile path
+        int64_t big = 0;
+        auto reg = [&](const void* p, const uint8_t* s, int64_t rows, int64_t K) {
+            if (!p || !s) return;
+            m->w4_map[p] = nvl_model::W4Ref{s, round_up(rows, W_ROW_PAD)};
+            big = std::max(big, round_up(rows, W_ROW_PAD) * K);
+        };
+        for (auto& l : m->layers) {
+            reg(l.w_qkv, l.e_qkv, l.n_qkv, H); reg(l.w1, l.e1, l.n1, H);
+            reg(l.t[NVL_T_WO].p, l.t[NVL_T_WO].mxs, H, l.t[NVL_T_WO].cols); reg(l.t[NVL_T_W2].p, l.t[NVL_T_W2].mxs, H, l.t[NVL_T_W2].cols);
+        }
+        m->w8_scratch_elems = big;
+        if (big) m->w8_scratch = dmalloc<bf16_t>(big);
+    }
     if (m->w8) {   // the 8-bit weights by code pointer (gemm() dispatch) and the dequantize scratch of the tile path
         int64_t big = 0;
         auto reg = [&](const void* p, const float* s, int64_t rows) {
@@ -2874,6 +3054,15 @@ extern "C" int nvl_get_weight(nvl_model* m, int kind, int layer, float* out, int
     NVL_HIP(hipSetDevice(m->device));
     NVL_HIP(hipStreamSynchronize(m->stream));
     const int64_t N = t->rows, K = t->cols, n_el = t->rows_pad * K;
+    if (t->mxs) {       // MXFP4 weight: W~ = +-grid[q] * 2^e, the values every GEMM path computes with
+        std::vector<uint8_t> codes((size_t)(n_el / 2)), sc((size_t)(n_el / 32));
+        NVL_HIP(hipMemcpy(codes.data(), t->p, codes.size(), hipMemcpyDeviceToHost));
+        NVL_HIP(hipMemcpy(sc.data(), t->mxs, sc.size(), hipMemcpyDeviceToHost));
+        for (int64_t n = 0; n < N; n++)
+            for (int64_t k = 0; k < K; k++)
+                out[k * N + n] = w4_value(w4_code_at(codes.data(), n, k, K), sc[(size_t)w4_scale_index(n, k >> 5, K >> 5)]);
+        return NVL_OK;
+    }
     if (t->scale) {     // 8-bit weight: W~ = bf16_rne(s * e4m3(q)), the values every GEMM path computes with
         std::vector<uint8_t> codes((size_t)n_el);
         std::vector<float> sc((size_t)t->rows_pad);

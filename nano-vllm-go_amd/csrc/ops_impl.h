@@ -261,6 +261,41 @@ extern "C" int nvl_op_matmul_fp8w(int device, const float* a, const float* w, in
     OP_CATCH
 }
 
+// MXFP4 weights (w4.h): nvl_op_matmul_fp8w's shape — W [K][N] quantized by the upload quantizer, C = bf16(A) · W~^T through
+// the model's dispatch (the MXFP4-weight decode kernels, the 64-row groups, dequantize + tile)
+extern "C" int nvl_op_matmul_mxfp4w(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* codes_out,
+                                    uint8_t* scales_out) {
+    if (!a || !w || !c || M <= 0 || K <= 0 || N <= 0) return op_fail("nvl_op_matmul_mxfp4w: bad arguments");
+    if (K % 64 != 0) return op_fail("nvl_op_matmul_mxfp4w: K must be a multiple of 64");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_BF16);
+    cx.m.mx = true;
+    void* A = cx.up_mat(a, M, K, false);
+    DevTensor t;
+    upload_2d_w4(&cx.m, &t, w, NVL_DTYPE_F32, N, K, true);
+    cx.bufs.push_back(t.p); cx.bufs.push_back(t.mxs);
+    cx.m.w4_map[t.p] = nvl_model::W4Ref{t.mxs, t.rows_pad};
+    cx.m.w8_scratch_elems = t.rows_pad * K;
+    cx.m.w8_scratch = (bf16_t*)cx.alloc(cx.m.w8_scratch_elems * 2);
+    const int ldc = (int)round_up(N, 4);
+    float* C = (float*)cx.alloc((int64_t)M * ldc * 4);
+    gemm(&cx.m, EPI_STORE, true, mk(A, K, t.p, C, ldc, nullptr, 1.f, M, N, K));
+    std::vector<float> tmp((size_t)M * ldc);
+    cx.down(tmp.data(), C, (int64_t)M * ldc);
+    for (int i = 0; i < M; i++) memcpy(c + (size_t)i * N, &tmp[(size_t)i * ldc], (size_t)N * 4);
+    if (codes_out || scales_out) {
+        std::vector<uint8_t> codes((size_t)(t.rows_pad * K / 2)), sc((size_t)(t.rows_pad * K / 32));
+        NVL_HIP(hipMemcpy(codes.data(), t.p, codes.size(), hipMemcpyDeviceToHost));
+        NVL_HIP(hipMemcpy(sc.data(), t.mxs, sc.size(), hipMemcpyDeviceToHost));
+        std::vector<uint8_t> co((size_t)N * K / 2), so((size_t)N * K / 32);
+        w4_to_abi(codes.data(), sc.data(), N, K, co.data(), so.data());
+        if (codes_out) memcpy(codes_out, co.data(), co.size());
+        if (scales_out) memcpy(scales_out, so.data(), so.size());
+    }
+    return NVL_OK;
+    OP_CATCH
+}
+
 // codes [rows_pad16][K] (fragment-major bytes) + scales on the device -> [M][K] row-major / [M] on the host
 static void a8_read_back(OpCtx& cx, const uint8_t* dcodes, const float* dscale, int M, int K, uint8_t* codes_out, float* scales_out) {
     const int64_t rows = round_up(M, 16);

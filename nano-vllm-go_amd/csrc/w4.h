@@ -1,0 +1,132 @@
+// w4.h — MXFP4 projection weights (nvl_set_mx_weight_dtype): OCP e2m1 elements with one e8m0 scale
+// per block of 32 consecutive k of one output row.  The quantizer every upload uses, the placement of pre-quantized input,
+// the dequantize kernel of the tile path, and the GEMM dispatch of an MXFP4 weight.
+//
+// Numerics, per 32-block: e = clamp(floor(log2(amax)) - 2, -120, 125) (0 for an all-zero block), stored E = e + 127;
+// q = e2m1_rne(|w| / 2^e) on {0, .5, 1, 1.5, 2, 3, 4, 6}, ties to the even mantissa bit, saturating at 6; sign in bit 3.
+// The model computes with W~ = +-grid[q] * 2^e, exact in bf16 and never denormal, on every path:
+//   decode (every call the bf16 dispatch sends to the weight-streaming kernels): gemm_skinny_mxfp4w_kernel /
+//       gemm_skinny_wide_mxfp4w_kernel, the fp8-weight bodies with the fragment built from 4 code bytes + the block's E
+//       (gemm.h w4_frag: v_cvt_scalef32_pk_bf16_fp4) — the same launch decisions as in bf16 mode;
+//   everything else (prefill, the tile and ping-pong kernels): w4_dequant_kernel writes W~ in the bf16 fragment-major
+//       layout into the tile-path scratch and the unchanged bf16 GEMM runs on it.
+// Storage: codes in the bf16 fragment-major order, two per byte ([rows_pad][K/2] bytes: a 16-row x 32-k block is 256
+// bytes, a lane's fragment 4 of them, even k in the low nibble); scales [rows_pad/16][K/32][16] bytes, a block's 16 rows
+// side by side (pad rows: codes 0, E = 127).  A fm_index() element offset halved is the byte of its code pair.
+#pragma once
+#include "gemm.h"
+
+namespace nvl {
+
+constexpr int W4_E_MIN = -120, W4_E_MAX = 125;     // block exponents; E = e + 127 in [7, 252]
+
+// byte offset of row r's scale of k-step ks (K/32 k-steps per row)
+__host__ __device__ __forceinline__ int64_t w4_scale_index(int64_t r, int64_t ks, int64_t nks) {
+    return ((r >> 4) * nks + ks) * 16 + (r & 15);
+}
+
+// the e2m1 code of |w| * 2^-e (v >= 0, finite): round to nearest, ties to the even mantissa bit, saturate at 6
+__device__ __forceinline__ uint32_t w4_code(float v) {
+    return (uint32_t)(v > 0.25f) + (uint32_t)(v >= 0.75f) + (uint32_t)(v > 1.25f) + (uint32_t)(v >= 1.75f) + (uint32_t)(v > 2.5f) +
+           (uint32_t)(v >= 3.5f) + (uint32_t)(v > 5.0f);
+}
+
+// x fp32 row-major [rows][K] -> codes + scales in the device layout; one wave per row, a lane per 32-block.
+// Any non-finite element sets *bad (the upload is refused).  Plain arithmetic: the chip's fp4 quantizing instruction is
+// not used (its ties and saturation are not pinned against the contract; the upload is not a hot path).
+__global__ __launch_bounds__(64) void w4_quant_rows_kernel(const float* __restrict__ x, int64_t K, uint8_t* __restrict__ codes,
+                                                           uint8_t* __restrict__ scales, int* __restrict__ bad) {
+    const int64_t r = blockIdx.x, nks = K >> 5;
+    bool fin = true;
+    for (int64_t ks = threadIdx.x; ks < nks; ks += 64) {
+        const uint32_t* xb = (const uint32_t*)(x + r * K + ks * 32);
+        uint32_t amax = 0;                                   // |w| as bits: the order of non-negative floats, no denormal mode involved
+        for (int k = 0; k < 32; k++) amax = max(amax, xb[k] & 0x7fffffffu);
+        if (amax >= 0x7f800000u) { fin = false; amax = 0; }
+        const int e = amax == 0 ? 0 : min(max((int)(amax >> 23) - 127 - 2, W4_E_MIN), W4_E_MAX);     // (denormal amax: field 0, clamped)
+        const float inv = __builtin_bit_cast(float, (uint32_t)(127 - e) << 23);                      // 2^-e, a normal number
+        scales[w4_scale_index(r, ks, nks)] = (uint8_t)(e + 127);
+        for (int fg = 0; fg < 4; fg++) {
+            uint32_t c = 0;
+            for (int k = 0; k < 8; k++) {
+                const uint32_t u = xb[8 * fg + k];
+                const uint32_t q = fin ? w4_code(__builtin_bit_cast(float, u & 0x7fffffffu) * inv) : 0u;
+                c |= (q | ((u >> 28) & 8u)) << (4 * k);
+            }
+            *(uint32_t*)(codes + (fm_index(r, ks * 32 + 8 * fg, K) >> 1)) = c;
+        }
+    }
+    if (!fin) atomicOr(bad, 1);
+}
+
+// pre-quantized input in the ABI packing (codes [rows][K/2], scales [rows][K/32], nvl_upload_tensor_mxfp4) -> the device
+// layout; a thread per 4 code bytes (one fragment), the first thread of a 32-block also moves its scale
+__global__ __launch_bounds__(256) void w4_place_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ src_scales,
+                                                       int64_t rows, int64_t K, uint8_t* __restrict__ dst, uint8_t* __restrict__ dst_scales) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;     // fragment index, row-major: [rows][K/8]
+    if (i >= rows * (K >> 3)) return;
+    const int64_t r = i / (K >> 3), k = (i - r * (K >> 3)) * 8;
+    *(uint32_t*)(dst + (fm_index(r, k, K) >> 1)) = *(const uint32_t*)(src + i * 4);
+    if ((k & 31) == 0) dst_scales[w4_scale_index(r, k >> 5, K >> 5)] = src_scales[r * (K >> 5) + (k >> 5)];
+}
+
+// codes + scales -> W~ (bf16, the fragment-major layout): n8 fragments starting at a 16-row tile boundary
+__global__ __launch_bounds__(256) void w4_dequant_kernel(const uint8_t* __restrict__ codes, const uint8_t* __restrict__ scales,
+                                                         int64_t n8, bf16_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;     // fragment index: (block, lane)
+    if (i >= n8) return;
+    *(bf16x8*)(out + i * 8) = w4_frag(*(const uint32_t*)(codes + i * 4), (uint32_t)scales[(i >> 6) * 16 + (i & 15)]);
+}
+
+// W~ of rows [0, rows) (whole 16-row tiles) into dst, fragment-major
+static inline void w4_dequant_rows(hipStream_t st, const void* codes, const uint8_t* scales, int64_t K, int64_t rows, bf16_t* dst) {
+    const int64_t n8 = rows * K / 8;
+    hipLaunchKernelGGL(w4_dequant_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, st, (const uint8_t*)codes, scales, n8, dst);
+}
+
+// The GEMM of an MXFP4 weight (a.W: codes, es: block scales, w_rows_pad: its allocated rows).  Decode-sized calls go where
+// the bf16 dispatch (launch_gemm_bf16) sends them, on the MXFP4-weight kernels; the rest run the bf16 dispatch on W~ in
+// `scratch` (scratch_elems bf16 elements; nvl_finalize sizes it for the largest MXFP4 projection).
+template <int EPI, typename OutT>
+static inline void launch_gemm_w4(hipStream_t st, const GemmArgs& a, const uint8_t* es, int64_t w_rows_pad, bf16_t* scratch,
+                                  int64_t scratch_elems) {
+    if (a.tile_map || a.seg || a.a_rows || a.moe_gate) throw std::runtime_error("gemm: an MXFP4 weight in a gathered / grouped launch");
+    const float* ws = (const float*)es;     // (the launchers' scale argument; the MXFP4 kernels take it back as bytes)
+    if (launch_gemm_skinny_bf16<EPI, OutT, WF_MXFP4>(st, a, ws)) return;
+    if constexpr (EPI != EPI_QKV) {     // (the 64-row-group condition of launch_gemm_bf16, unchanged)
+        const bool few_tiles = cdiv(a.M, 128) * cdiv(a.N, 128) < g_chunk_min_tiles;
+        if (a.M > 64 && a.M <= g_chunk_max_m && (a.M <= g_chunk_all_m || few_tiles || a.rs_in || a.rs_out) && !a.sk_part && a.K % 32 == 0 &&
+            g_force_tile == 0) {
+            GemmArgs c = a;
+            c.m_passes = cdiv(a.M, 64);
+            const bool ok = g_pass_interleave ? launch_gemm_skinny_bf16<EPI, OutT, WF_MXFP4>(st, c, ws)
+                                              : launch_skinny_passes_serial<EPI, OutT, WF_MXFP4>(st, c, ws);
+            if (ok) return;
+        }
+    }
+    if (a.rs_in || a.rs_out) throw std::runtime_error("gemm: a deferred-RMSNorm projection did not fit the decode kernels");
+    if (w_rows_pad * a.K > scratch_elems) throw std::runtime_error("gemm: an MXFP4 weight larger than its dequantize scratch");
+    w4_dequant_rows(st, a.W, es, a.K, w_rows_pad, scratch);
+    GemmArgs c = a;
+    c.W = scratch;
+    launch_gemm_bf16<EPI, OutT>(st, c);
+}
+
+// ---- host ----
+inline float w4_grid(uint8_t q) {
+    static const float g[8] = {0.f, 0.5f, 1.f, 1.5f, 2.f, 3.f, 4.f, 6.f};
+    return (q & 8) ? -g[q & 7] : g[q & 7];
+}
+// W~ of one code under the block scale byte E (the read-back of nvl_get_weight)
+inline float w4_value(uint8_t q, uint8_t E) { return std::ldexp(w4_grid(q), (int)E - 127); }
+// device layout (host copies) -> the code of element (r, k) and its block's scale byte
+inline uint8_t w4_code_at(const uint8_t* codes, int64_t r, int64_t k, int64_t K) { return (codes[fm_index(r, k, K) >> 1] >> (4 * (k & 1))) & 15; }
+// device layout -> the ABI packing: codes [N][K/2] (even k in the low nibble), scales [N][K/32]
+inline void w4_to_abi(const uint8_t* codes, const uint8_t* scales, int64_t N, int64_t K, uint8_t* codes_out, uint8_t* scales_out) {
+    for (int64_t r = 0; r < N; r++) {
+        for (int64_t k = 0; k < K; k += 2) codes_out[r * (K / 2) + k / 2] = codes[fm_index(r, k, K) >> 1];
+        for (int64_t ks = 0; ks < K / 32; ks++) scales_out[r * (K / 32) + ks] = scales[w4_scale_index(r, ks, K / 32)];
+    }
+}
+
+}  // namespace nvl

@@ -47,7 +47,7 @@ class HipTransformerModel:
                  max_seqs: int = 8, max_batch_tokens: int | None = None, tp_rank: int = 0, tp_size: int = 1,
                  tp_force_single: bool = False, kv_num_blocks: int = 0, kv_block_size: int = 0,
                  kv_cache_dtype: str = "auto", kv_scales=None, weight_dtype: str = "auto",
-                 act_dtype: str = "auto", expert_dtype: str = "auto"):
+                 act_dtype: str = "auto", expert_dtype: str = "auto", mx_weight_dtype: str = "none"):
         """tensors=None defers finalize(): upload() each tensor, then call finalize().
         tp_size > 1 makes this the tp_rank-th tensor-parallel shard: pass the FULL tensors, the library keeps
         its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests).
@@ -58,7 +58,10 @@ class HipTransformerModel:
         act_dtype="fp8_e4m3" (needs weight_dtype="fp8_e4m3"): W8A8 — the projections on the tile (prefill) GEMM path quantize
         their activation rows to e4m3 with one scale per row and multiply codes x codes (nvl_set_act_dtype).
         expert_dtype="fp8_e4m3" (needs weight_dtype="fp8_e4m3", a MoE model): the experts' weights are 8-bit too, one scale per
-        (expert, output row) (nvl_set_expert_dtype); otherwise the experts stay bf16."""
+        (expert, output row) (nvl_set_expert_dtype); otherwise the experts stay bf16.
+        mx_weight_dtype="fp4_e2m1": MXFP4 projection weights, e2m1 codes with one e8m0 scale per 32 input features
+        (nvl_set_mx_weight_dtype; bf16 precision, no TP, not with weight_dtype="fp8_e4m3"); the LM head, the embeddings and
+        the MoE experts stay bf16.  The model computes with W~ = grid[q] * 2^e, which get_weight returns."""
         self.cfg = dict(cfg)
         self.lib = L.lib()
         self.h = C.c_void_p()
@@ -84,14 +87,20 @@ class HipTransformerModel:
             raise ValueError(f"expert_dtype must be one of {sorted(L.EXPERT_DTYPE)}")
         if expert_dtype != "auto" and weight_dtype != "fp8_e4m3":
             raise ValueError('expert_dtype="fp8_e4m3" needs weight_dtype="fp8_e4m3"')
+        if mx_weight_dtype not in L.MX_WEIGHT_DTYPE:
+            raise ValueError(f"mx_weight_dtype must be one of {sorted(L.MX_WEIGHT_DTYPE)}")
+        if mx_weight_dtype != "none" and weight_dtype != "auto":
+            raise ValueError('mx_weight_dtype="fp4_e2m1" cannot be combined with weight_dtype="fp8_e4m3"')
         L.check(self.lib.nvl_create(C.byref(self._c), C.byref(opts), C.byref(self.h)))
         self.weight_dtype = weight_dtype
+        self.mx_weight_dtype = mx_weight_dtype
         self.act_dtype = act_dtype
         self.expert_dtype = expert_dtype
-        for setter, table, value in ((self.lib.nvl_set_weight_dtype, L.WEIGHT_DTYPE, weight_dtype),
+        for setter, table, value in ((self.lib.nvl_set_mx_weight_dtype, L.MX_WEIGHT_DTYPE, mx_weight_dtype),
+                                     (self.lib.nvl_set_weight_dtype, L.WEIGHT_DTYPE, weight_dtype),
                                      (self.lib.nvl_set_expert_dtype, L.EXPERT_DTYPE, expert_dtype),
                                      (self.lib.nvl_set_act_dtype, L.ACT_DTYPE, act_dtype)):
-            if value == "auto":
+            if value in ("auto", "none"):
                 continue
             rc = setter(self.h, table[value])
             if rc < 0:
@@ -189,6 +198,14 @@ class HipTransformerModel:
             rows, cols = shape
         L.check(self.lib.nvl_upload_tensor(self.h, L.SLOT_ID[slot], int(layer), ptr, dtype, rows, cols, layout), self.h)
         del keep
+
+    def upload_mxfp4(self, slot: str, layer: int, codes, scales):
+        """nvl_upload_tensor_mxfp4: pre-quantized codes [out][in/2] (even k in the low nibble) and e8m0 scales [out][in/32]"""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        scales = np.ascontiguousarray(scales, np.uint8)
+        L.check(self.lib.nvl_upload_tensor_mxfp4(self.h, L.SLOT_ID[slot], int(layer), codes.ctypes.data_as(C.c_void_p),
+                                                 scales.ctypes.data_as(C.c_void_p), codes.shape[0], codes.shape[1] * 2,
+                                                 L.LAYOUT_OUT_IN), self.h)
 
     # -- sequences (replace kvCaches map[int64]*KVCache, tensor_model_runner.go:13) ----------------
     def seq_reset(self, seq_id: int):

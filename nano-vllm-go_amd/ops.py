@@ -86,6 +86,20 @@ def matmul_fp8w(a, w, device=0):                              # MatMul tensor.go
     return c, codes, scales
 
 
+def matmul_mxfp4w(a, w, device=0):                            # MatMul tensor.go:62 with MXFP4 weights (w4.h)
+    """a [M][K], w [K][N] ([in, out]) -> (c, codes, scales): w quantized by the model's upload quantizer (codes [N][K/2]
+    uint8, two e2m1 codes per byte with even k in the low nibble; scales [N][K/32] e8m0 bytes), c = bf16(a) @ W~ through
+    the model's GEMM dispatch, W~ = grid[codes] * 2^(scales - 127)."""
+    a, w = _f(a), _f(w)
+    m, k = a.shape
+    _, n = w.shape
+    c = np.empty((m, n), np.float32)
+    codes = np.empty((n, k // 2), np.uint8)
+    scales = np.empty((n, k // 32), np.uint8)
+    L.check(L.lib().nvl_op_matmul_mxfp4w(device, _p(a), _p(w), m, n, k, _p(c), _p(codes), _p(scales)))
+    return c, codes, scales
+
+
 def matmul_w8a8(a, w, device=0):                              # MatMul tensor.go:62 with 8-bit weights and activations (a8.h)
     """a [M][K], w [K][N] ([in, out]) -> (c, a_codes, a_scales): matmul_fp8w's dispatch in W8A8 mode.  The tile form
     quantizes bf16(a) per row (a_codes [M][K] uint8, a_scales [M]) and returns c = (e4m3(a_codes) @ e4m3(w codes)^T) * a_scales

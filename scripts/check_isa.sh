@@ -51,6 +51,9 @@ check(r"attn_decode_bf16_kernelILi128ELi8ELb[01]ELb0E", "decode attention hd 128
 check(r"gemm_skinny_bf16_kernelILi4ELi[124]ELi2ELi[0-4]E\w+Lb1ELb0ELb0E", "narrow projection, 64-row groups", lambda r: r["spill"] <= 12)
 check(r"gemm_skinny_bf16_kernelILi[12]ELi[124]ELi4ELi[0-4]E\w+Lb0ELb0ELb[01]E", "narrow projection, <= 32 rows", lambda r: r["spill"] <= 12)
 check(r"gemm_skinny_wide_bf16_kernelILi[12]ELi[24]ELi4E", "wide projection, <= 32 rows", lambda r: r["spill"] <= 12)
+# the MXFP4-weight forms of the decode projections (w4.h): the fp8 forms' numbers
+check(r"gemm_skinny_mxfp4w_kernelILi[124]E", "narrow projection, MXFP4 weights", lambda r: r["spill"] <= 12 and r["vgpr"] <= 512)
+check(r"gemm_skinny_wide_mxfp4w_kernelILi[124]E", "wide projection, MXFP4 weights", lambda r: r["spill"] <= 12 and r["vgpr"] <= 512)
 sys.exit(1 if bad else 0)
 PY
 exit $rc

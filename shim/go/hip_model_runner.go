@@ -42,6 +42,7 @@ type Options struct {
 	KVCacheDType   int  // C.NVL_KV_AUTO (0) or C.NVL_KV_FP8_E4M3 (1): 8-bit K/V, twice the tokens per byte of cache
 	WeightDType    int  // C.NVL_W_AUTO (0) or C.NVL_W_FP8_E4M3 (1): 8-bit projection weights with per-row scales
 	ActDType       int  // C.NVL_ACT_AUTO (0) or C.NVL_ACT_FP8_E4M3 (1): W8A8 prefill projections (needs WeightDType 1)
+	MXWeightDType  int  // C.NVL_MX_NONE (0) or C.NVL_MX_FP4_E2M1 (1): MXFP4 projection weights (not with WeightDType 1)
 	ExpertDType    int  // C.NVL_EXPERT_AUTO (0) or C.NVL_EXPERT_FP8_E4M3 (1): 8-bit MoE expert weights (needs WeightDType 1)
 }
 
@@ -330,6 +331,13 @@ func create(cfg *C.nvl_model_config, o Options) (*HipModelRunner, error) {
 	if o.WeightDType != 0 { // before the weights are uploaded (nvl_set_weight_dtype)
 		if rc := C.nvl_set_weight_dtype(r.h, C.int(o.WeightDType)); rc != 0 {
 			err := fmt.Errorf("nvl_set_weight_dtype: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
+			C.nvl_destroy(r.h)
+			return nil, err
+		}
+	}
+	if o.MXWeightDType != 0 { // before the weights are uploaded (nvl_set_mx_weight_dtype)
+		if rc := C.nvl_set_mx_weight_dtype(r.h, C.int(o.MXWeightDType)); rc != 0 {
+			err := fmt.Errorf("nvl_set_mx_weight_dtype: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
 			C.nvl_destroy(r.h)
 			return nil, err
 		}
