@@ -1150,6 +1150,13 @@ template <int MT, int NTW, int U, int EPI, typename OutT>
 __global__ __launch_bounds__(1024) void gemm_skinny_moe_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
     gemm_skinny_body<MT, NTW, U, EPI, OutT, false, true, false, WF_FP8>(p, w_scale);
 }
+// MXFP4 MoE experts (nvl_set_mx_expert_dtype): the MoE decode instantiation with the MXFP4 fragment.  The
+// block scales lie beside the code tiles over the whole K of the launch, so the concatenated down projection (K = E*I)
+// needs no per-expert scale row: the body is used as it is.  K-split down form and SwiGLU up form, as for fp8.
+template <int MT, int NTW, int U, int EPI, typename OutT>
+__global__ __launch_bounds__(1024) void gemm_skinny_moe_mxfp4w_kernel(GemmArgs p, const uint8_t* __restrict__ w_scales) {
+    gemm_skinny_body<MT, NTW, U, EPI, OutT, false, true, false, WF_MXFP4>(p, (const float*)w_scales);
+}
 
 // ------------------------------------------------------------------------------------------
 // MoE decode routing in ONE launch (moe.go:57-103): router logits of a 16-row activation tile (E <= 64 experts, all of K),
@@ -1562,6 +1569,11 @@ template <int MT, int NTB, int U, int EPI, typename OutT>
 __global__ __launch_bounds__(512) void gemm_skinny_wide_moe_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
     gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, false, true, WF_FP8>(p, w_scale);
 }
+// MXFP4 MoE experts: the wide form of the expert up projection
+template <int MT, int NTB, int U, int EPI, typename OutT>
+__global__ __launch_bounds__(512) void gemm_skinny_wide_moe_mxfp4w_kernel(GemmArgs p, const uint8_t* __restrict__ w_scales) {
+    gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, false, true, WF_MXFP4>(p, (const float*)w_scales);
+}
 
 static int g_chunk_max_m = 512;    // largest M that uses 64-row passes of the decode form at all (nvl_set_tuning key 11; 64 = off)
 static int g_chunk_all_m = 64;     // up to here every projection does; above, only those whose 128x128 tile grid would
@@ -1606,6 +1618,7 @@ static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a
 // skinny dispatch: M <= 64, no gather/segments.  Returns false when the shape is not eligible.
 // W8: the same decisions, the fp8-weight kernels (ws: the per-row weight scales).  8-bit MoE experts (moe_gate) take the
 // K-split down form and the SwiGLU up form; the deferred-norm producer form of the down projection has no 8-bit instance.
+// MXFP4 MoE experts (nvl_set_mx_expert_dtype) take the same two forms on gemm_skinny_moe_mxfp4w_kernel.
 template <int NTW, int EPI, typename OutT, int WF = 0>
 static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
     constexpr bool W8 = WF == WF_FP8, MX = WF == WF_MXFP4;     // (MX: ws carries the e8m0 scale bytes, w4.h)
@@ -1622,7 +1635,7 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
         while (ks > 1 && (a.K >> 5) / ks < 4) ks >>= 1;
         if (a.K % 32 != 0) return false;
         if constexpr (EPI == EPI_RESID) {
-            if (a.moe_gate && (W8 || MX)) return false;     // (no 8-bit instance: a wave's blocks cross experts, see moe())
+            if (a.moe_gate && (W8 || MX)) return false;     // (no quantized instance of the producer form, see moe())
             if (a.moe_gate) {     // MoE down as the deferred-norm producer: all experts in one workgroup's K range, 16 waves
                 ks = 16;
                 const int nks = a.K >> 5, spe = a.moe_I >> 5;
@@ -1684,7 +1697,16 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
     if (a.grid_y != KS) { GemmArgs c = a; c.grid_y = KS; return launch_gemm_skinny_ntw<NTW, EPI, OutT, WF>(st, c, ws); }
     if constexpr (MX) {
         const uint8_t* es = (const uint8_t*)ws;
-        if (a.moe_gate) return false;                     // (the experts stay bf16 in an MXFP4 model)
+        if (a.moe_gate) {                                 // MXFP4 MoE experts (nvl_set_mx_expert_dtype)
+            if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
+                if (a.m_passes > 1) return false;
+                if (MT == 1) hipLaunchKernelGGL((gemm_skinny_moe_mxfp4w_kernel<1, NTW, 4, EPI, OutT>), grid, block, lds, st, a, es);
+                else if (MT == 2) hipLaunchKernelGGL((gemm_skinny_moe_mxfp4w_kernel<2, NTW, 4, EPI, OutT>), grid, block, lds, st, a, es);
+                else hipLaunchKernelGGL((gemm_skinny_moe_mxfp4w_kernel<4, NTW, 2, EPI, OutT>), grid, block, lds, st, a, es);
+                return true;
+            }
+            return false;
+        }
         if (a.m_passes > 1) hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<4, NTW, 2, EPI, OutT, true>), grid, block, lds, st, a, es);
         else if (MT == 1) hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<1, NTW, 4, EPI, OutT>), grid, block, lds, st, a, es);
         else if (MT == 2) hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<2, NTW, 4, EPI, OutT>), grid, block, lds, st, a, es);
@@ -1756,7 +1778,21 @@ static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, co
         hipLaunchKernelGGL((gemm_skinny_wide_mxfp4w_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), dim3(wgs), dim3(ksplit * 64),    \
                            lds, st, a, (const uint8_t*)ws);                                                            \
     } while (0)
-        if (a.moe_gate) return false;
+#define NVL_SKW4M(MTv, Uv)                                                                                               \
+    do {                                                                                                               \
+        NVL_LDS_ATTR((gemm_skinny_wide_moe_mxfp4w_kernel<MTv, NTB, Uv, EPI, OutT>), 8 * NTB * MTv * 64 * 16);         \
+        hipLaunchKernelGGL((gemm_skinny_wide_moe_mxfp4w_kernel<MTv, NTB, Uv, EPI, OutT>), dim3(wgs), dim3(ksplit * 64),   \
+                           lds, st, a, (const uint8_t*)ws);                                                            \
+    } while (0)
+        if (a.moe_gate) {                                 // MXFP4 MoE experts: the expert up projection
+            if constexpr (EPI == EPI_SWIGLU) {
+                if (a.m_passes > 1) return false;
+                if (MT == 1) NVL_SKW4M(1, 4); else if (MT == 2) NVL_SKW4M(2, 4); else NVL_SKW4M(4, 2);
+                return true;
+            }
+            return false;
+        }
+#undef NVL_SKW4M
         if (a.m_passes > 1) NVL_SKW4(4, 2, true); else if (MT == 1) NVL_SKW4(1, 4, false); else if (MT == 2) NVL_SKW4(2, 4, false); else NVL_SKW4(4, 2, false);
 #undef NVL_SKW4
         return true;

@@ -45,6 +45,11 @@ struct LayerW {
     // form applies), s_moe_out [E][H_pad] its scales
     float* s_moe_in = nullptr;
     void* moe_out8 = nullptr; float* s_moe_out = nullptr;
+    // MXFP4 experts (nvl_set_mx_expert_dtype): moe_in holds nibble-packed codes in the same interleaved order, e_moe_in its
+    // block scales; moe_out4 the down codes over K = E*I, [H_pad][E*I/2] (moe_out_cat = moe_out4 when the decode form
+    // applies), e_moe_out their block scales [H_pad/16][E*I/32][16] — beside the code tiles, no per-expert scale row
+    uint8_t* e_moe_in = nullptr;
+    void* moe_out4 = nullptr; uint8_t* e_moe_out = nullptr;
     bool mamba = false;                  // a Mamba2 block (attention tensors absent); index among the Mamba2 layers
     int mamba_idx = -1;
 };
@@ -106,6 +111,9 @@ struct nvl_model {
     bool e8 = false;
     bool expert_uploaded = false;          // an expert tensor has been uploaded: the expert dtype is fixed from then on
     nvl::bf16_t* e8_scratch = nullptr; int64_t e8_scratch_elems = 0;
+    // MXFP4 MoE experts (nvl_set_mx_expert_dtype NVL_MXE_FP4_E2M1, w4.h): the grouped GEMMs' W~ goes through e8_scratch (the
+    // two expert modes exclude each other, as their projection modes do)
+    bool e4 = false;
     // 8-bit activations of the tile step (nvl_set_act_dtype NVL_ACT_FP8_E4M3, a8.h): codes [a8_rows][a8_k] + scales [a8_rows]
     bool a8 = false;
     uint8_t* a8_codes = nullptr; float* a8_scale = nullptr; int64_t a8_rows = 0, a8_k = 0;

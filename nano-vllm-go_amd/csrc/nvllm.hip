@@ -378,7 +378,8 @@ extern "C" void nvl_destroy(nvl_model* m) {
         dfree(l.w_qkv); dfree(l.b_qkv); dfree(l.w1); dfree(l.moe_in); dfree(l.moe_out_cat);
         dfree(l.s_qkv); dfree(l.s1); dfree(l.e_qkv); dfree(l.e1);
         if (l.moe_out_cat != l.moe_out8) dfree(l.moe_out8);
-        dfree(l.s_moe_in); dfree(l.s_moe_out);
+        if (l.moe_out_cat != l.moe_out4) dfree(l.moe_out4);
+        dfree(l.s_moe_in); dfree(l.s_moe_out); dfree(l.e_moe_in); dfree(l.e_moe_out);
     }
     dfree(m->w8_scratch); dfree(m->e8_scratch); dfree(m->a8_codes); dfree(m->a8_scale);
     if (m->lm_head && m->lm_head != m->g[NVL_T_TOK_EMB].p && m->lm_head != m->g[NVL_T_LM_HEAD].p) dfree(m->lm_head);
@@ -470,12 +471,13 @@ void upload_2d_w8(nvl_model* m, DevTensor* t, const void* data, int dtype, int64
     m->stats.weight_bytes += (double)Npad * K + (double)Npad * 4;
 }
 
-// is this 2-D kind stored as MXFP4 in an MX model (nvl_set_mx_weight_dtype)?  The attention and FFN projections only: the LM
-// head, both embeddings, the router, the Mamba2 projections and the MoE experts stay bf16.
+// is this 2-D kind stored as MXFP4 in an MX model (nvl_set_mx_weight_dtype)?  The attention and FFN projections, and the MoE
+// experts with nvl_set_mx_expert_dtype: the LM head, both embeddings, the router and the Mamba2 projections stay bf16.
 bool w4_kind(const nvl_model* m, int kind) {
     if (!m->mx) return false;
     switch (kind) {
         case NVL_T_WQ: case NVL_T_WK: case NVL_T_WV: case NVL_T_WKV: case NVL_T_WO: case NVL_T_W1: case NVL_T_W2: return true;
+        case NVL_T_MOE_IN: case NVL_T_MOE_OUT: return m->e4;
         default: return false;
     }
 }
@@ -647,6 +649,7 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
         m->w2d_uploaded = true;
         m->expert_uploaded = true;
         if (w8_kind(m, kind)) upload_2d_w8(m, t, data, dtype, rows, cols, false);     // one scale per (expert, output row)
+        else if (w4_kind(m, kind)) upload_2d_w4(m, t, data, dtype, rows, cols, false);     // ... per 32 inputs of it
         else upload_2d(m, t, data, dtype, rows, cols, false, Slice2D{rows, cols, 0, 0, 0}, rows, true);
         return NVL_OK;
     }
@@ -753,7 +756,11 @@ extern "C" int nvl_upload_tensor_mxfp4(nvl_model* m, int kind, int layer, const 
     if (layout != NVL_LAYOUT_OUT_IN) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
     DevTensor* t = tensor_slot(m, kind, layer);
     if (!t) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: bad kind or layer");
-    const int64_t SN = full_out(m, kind), SK = full_in(m, kind);
+    int64_t SN = full_out(m, kind), SK = full_in(m, kind);
+    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {     // [E * out][in]
+        SN = (int64_t)m->cfg.num_experts * (kind == NVL_T_MOE_IN ? 2 * (int64_t)m->F : m->H);
+        SK = kind == NVL_T_MOE_IN ? m->H : m->F;
+    }
     if (rows != SN || cols != SK || SK % 32 != 0) {
         char buf[160];
         snprintf(buf, sizeof buf, "nvl_upload_tensor_mxfp4: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld], in %% 32 == 0", kind,
@@ -766,6 +773,7 @@ extern "C" int nvl_upload_tensor_mxfp4(nvl_model* m, int kind, int layer, const 
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
     m->w2d_uploaded = true;
+    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) m->expert_uploaded = true;
     const int64_t Npad = round_up(rows, W_ROW_PAD);
     w4_alloc(m, t, Npad, cols);
     uint8_t* raw = (uint8_t*)dmalloc_bytes(rows * cols / 2);
@@ -987,7 +995,23 @@ extern "C" int nvl_set_mx_weight_dtype(nvl_model* m, int dtype) {
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: MXFP4 weights are not available with tensor parallelism");
     if (dtype == NVL_MX_FP4_E2M1 && m->w8)
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores 8-bit weights (nvl_set_weight_dtype)");
+    if (dtype == NVL_MX_NONE && m->e4)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores MXFP4 experts (nvl_set_mx_expert_dtype), which need MXFP4 weights");
     m->mx = dtype == NVL_MX_FP4_E2M1;
+    return NVL_OK;
+}
+
+extern "C" int nvl_set_mx_expert_dtype(nvl_model* m, int dtype) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: no model");
+    if (m->finalized || m->expert_uploaded)
+        return fail(m, NVL_ERR_STATE, "nvl_set_mx_expert_dtype: call it after nvl_set_mx_weight_dtype and before the first expert upload");
+    if (dtype != NVL_MXE_NONE && dtype != NVL_MXE_FP4_E2M1) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: unknown MX expert dtype");
+    if (dtype == NVL_MXE_FP4_E2M1) {
+        if (!m->cfg.use_moe || m->cfg.num_experts <= 0) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: the model has no MoE layers");
+        if (m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: MXFP4 experts need bf16 precision");
+        if (!m->mx) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: MXFP4 experts need MXFP4 projection weights (nvl_set_mx_weight_dtype first)");
+    }
+    m->e4 = dtype == NVL_MXE_FP4_E2M1;
     return NVL_OK;
 }
 
@@ -1133,6 +1157,27 @@ extern "C" int nvl_finalize(nvl_model* m) {
                     for (int k : {NVL_T_MOE_IN, NVL_T_MOE_OUT}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].scale); l.t[k].scale = nullptr; }
                     continue;
                 }
+                if (l.t[NVL_T_MOE_IN].mxs) {     // MXFP4 experts (nvl_set_mx_expert_dtype): codes + block scales follow the interleave
+                    need(l.t[NVL_T_MOE_OUT].mxs != nullptr, "MXFP4 expert tensors");
+                    const int64_t np = round_up(E * 2 * I, W_ROW_PAD), hp = round_up(H, W_ROW_PAD);
+                    idx.resize((size_t)np, -1);
+                    l.moe_in = dmalloc_bytes(np * H / 2);
+                    l.e_moe_in = (uint8_t*)dmalloc_bytes(np * H / 32);
+                    gather_rows_w4(m, l.t[NVL_T_MOE_IN], idx, l.moe_in, l.e_moe_in, H);
+                    // down: codes and block scales over K = E*I (the decode form's layout; the tile path dequantizes from it)
+                    const DevTensor& d = l.t[NVL_T_MOE_OUT];
+                    l.moe_out4 = dmalloc_bytes(hp * E * I / 2);
+                    l.e_moe_out = (uint8_t*)dmalloc_bytes(hp * E * I / 32);
+                    NVL_HIP(hipMemsetAsync(l.moe_out4, 0, (size_t)(hp * E * I / 2), m->stream));
+                    NVL_HIP(hipMemsetAsync(l.e_moe_out, 127, (size_t)(hp * E * I / 32), m->stream));
+                    hipLaunchKernelGGL(moe_cat_down_w4_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream,
+                                       (const uint8_t*)d.p, (const uint8_t*)d.mxs, (uint8_t*)l.moe_out4, l.e_moe_out, (int)H, (int)I, (int)E);
+                    NVL_HIP(hipGetLastError());
+                    NVL_HIP(hipStreamSynchronize(m->stream));
+                    if (dense_form) l.moe_out_cat = l.moe_out4;
+                    for (int k : {NVL_T_MOE_IN, NVL_T_MOE_OUT}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].mxs); l.t[k].mxs = nullptr; }
+                    continue;
+                }
                 l.moe_in = dmalloc_bytes(round_up(E * 2 * I, W_ROW_PAD) * H * (int64_t)m->wsize);   // (+ zero pad rows: the decode kernels read whole tiles)
                 NVL_HIP(hipMemsetAsync(l.moe_in, 0, (size_t)(round_up(E * 2 * I, W_ROW_PAD) * H) * m->wsize, m->stream));
                 gather_rows(m, l.t[NVL_T_MOE_IN].p, idx, l.moe_in, H);
@@ -1173,6 +1218,18 @@ extern "C" int nvl_finalize(nvl_model* m) {
         }
         m->w8_scratch_elems = big;
         if (big) m->w8_scratch = dmalloc<bf16_t>(big);
+        if (m->e4) {   // MXFP4 experts: the codes by pointer (decode dispatch), and the scratch of one layer's W~ (up, then down)
+            const int64_t E = c.num_experts, I = m->F, hp = round_up(H, W_ROW_PAD);
+            for (auto& l : m->layers) {
+                if (!l.e_moe_in) continue;
+                m->w4_map[l.moe_in] = nvl_model::W4Ref{l.e_moe_in, round_up(E * 2 * I, W_ROW_PAD)};
+                if (l.moe_out_cat) m->w4_map[l.moe_out_cat] = nvl_model::W4Ref{l.e_moe_out, hp};
+            }
+            // (down: the grouped GEMMs read whole 256-row tiles of the last expert past its H rows)
+            m->e8_scratch_elems = std::max(round_up(E * 2 * I, W_ROW_PAD) * H, (E * H + 2 * W_ROW_PAD) * I);
+            m->e8_scratch = dmalloc<bf16_t>(m->e8_scratch_elems);
+            NVL_HIP(hipMemsetAsync(m->e8_scratch, 0, (size_t)m->e8_scratch_elems * 2, m->stream));
+        }
     }
     if (m->w8) {   // the 8-bit weights by code pointer (gemm() dispatch) and the dequantize scratch of the tile path
         int64_t big = 0;
@@ -1963,7 +2020,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
     const int pairs = M * k;
     // algorithmic weight bytes of the expert GEMMs: the experts a batch of `pairs` (token, rank) pairs can touch, once
     const double e_touch = (double)std::min(E, pairs);
-    const double eb = m->e8 ? 1.0 : (double)m->wsize;     // bytes per expert weight (8-bit experts: codes; scales not counted)
+    const double eb = m->e4 ? 0.5 : m->e8 ? 1.0 : (double)m->wsize;     // bytes per expert weight (quantized experts: codes; scales not counted)
     m->site = KS_MOE_ROUTER;
     const bool dense = moe_dense_ok(m, l, M) && m->pending_slices == 0;
     // decode: router logits, softmax, top-k and the dense gate matrix in one launch (gemm.h moe_router_gate_kernel)
@@ -1996,8 +2053,9 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
         m->site = KS_MOE_UP; m->site_bytes = e_touch * 2 * I * H * eb + ((double)M * H + e_touch * M * I) * (double)m->wsize;
         gemm(m, EPI_SWIGLU, false, a, 2.0 * pairs * 2 * I * H);
         const int nks = (E * I) >> 5, spe = I >> 5;
-        // (8-bit experts: no producer form — a wave's live blocks cross experts, the scale would change with the block)
-        if (next_norm_w && g_moe_defer_down && !m->e8 && nks % 64 == 0 && spe % 4 == 0 && nks / 16 <= 4 * spe && nks / 64 <= 32) {
+        // (8-bit experts: no producer form — a wave's live blocks cross experts, the scale would change with the block;
+        //  MXFP4 experts: no instance of it either — key 33 is off by default and was measured slower)
+        if (next_norm_w && g_moe_defer_down && !m->e8 && !m->e4 && nks % 64 == 0 && spe % 4 == 0 && nks / 16 <= 4 * spe && nks / 64 <= 32) {
             // (the launcher's conditions: 16 waves, whole blocks of 4 k-steps inside one expert, <= 4 experts per wave)
             GemmArgs d = mk(m->moe_hall, E * I, l.moe_out_cat, m->x, H, nullptr, m->resid_alpha, M, H, E * I);
             d.moe_gate = m->moe_gate; d.moe_E = E; d.moe_I = I;
@@ -2082,6 +2140,11 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
             w8_dequant_rows(m->stream, l.moe_in, l.s_moe_in, H, 0, round_up(E * 2 * I, W_ROW_PAD), m->e8_scratch);
             NVL_HIP(hipGetLastError());
             a.W = m->e8_scratch;
+        } else if (m->e4) {     // MXFP4 experts: the same two steps with the MX dequantize kernels
+            KScope ks(m, KC_OTHER, 0, KS_MOE_UP, (double)round_up(E * 2 * I, W_ROW_PAD) * H * 2.53);
+            w4_dequant_rows(m->stream, l.moe_in, l.e_moe_in, H, round_up(E * 2 * I, W_ROW_PAD), m->e8_scratch);
+            NVL_HIP(hipGetLastError());
+            a.W = m->e8_scratch;
         }
         m->site = KS_MOE_UP; m->site_bytes = (e_touch * 2 * I * H + (double)pairs * H + (double)pairs * I) * (double)m->wsize;
         gemm(m, EPI_SWIGLU, false, a, 2.0 * pairs * 2 * I * H);
@@ -2090,6 +2153,13 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
             const int64_t n8 = (int64_t)E * H * I / 8;
             hipLaunchKernelGGL(e8_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out8,
                                l.s_moe_out, H, I, E, round_up(H, W_ROW_PAD), n8, m->e8_scratch);
+            NVL_HIP(hipGetLastError());
+            w_down = m->e8_scratch;
+        } else if (m->e4) {
+            KScope ks(m, KC_OTHER, 0, KS_MOE_DOWN, (double)E * H * I * 2.53);
+            const int64_t n8 = (int64_t)E * H * I / 8;
+            hipLaunchKernelGGL(e4_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out4,
+                               (const uint8_t*)l.e_moe_out, H, I, E, n8, m->e8_scratch);
             NVL_HIP(hipGetLastError());
             w_down = m->e8_scratch;
         }

@@ -13,6 +13,9 @@
 // Storage: codes in the bf16 fragment-major order, two per byte ([rows_pad][K/2] bytes: a 16-row x 32-k block is 256
 // bytes, a lane's fragment 4 of them, even k in the low nibble); scales [rows_pad/16][K/32][16] bytes, a block's 16 rows
 // side by side (pad rows: codes 0, E = 127).  A fm_index() element offset halved is the byte of its code pair.
+// MoE experts (nvl_set_mx_expert_dtype, §9 f-10): the same contract with one scale per 32 input features of one (expert,
+// output row).  Decode streams the codes through gemm_skinny_moe_mxfp4w_kernel / gemm_skinny_wide_moe_mxfp4w_kernel; every
+// other MoE launch runs the unchanged grouped GEMMs on one layer's W~, dequantized (up, then down) into a scratch buffer.
 #pragma once
 #include "gemm.h"
 
@@ -78,6 +81,35 @@ __global__ __launch_bounds__(256) void w4_dequant_kernel(const uint8_t* __restri
     *(bf16x8*)(out + i * 8) = w4_frag(*(const uint32_t*)(codes + i * 4), (uint32_t)scales[(i >> 6) * 16 + (i & 15)]);
 }
 
+// MXFP4 MoE experts (nvl_set_mx_expert_dtype).  The down codes are stored once, in the decode form's
+// layout: [H_pad][E*I/2] bytes, fragment-major with K = E*I (expert e's k-steps e*I/32 .. (e+1)*I/32 - 1 of every 16-row
+// tile), the block scales [H_pad/16][E*I/32][16] over the same K.  moe_cat_down_w4_kernel builds both from the uploaded
+// [E*H][I] codes and scales (moe_cat_down_w8_kernel's nibble form; H % 16 == 0: an expert starts on a tile boundary).
+__global__ __launch_bounds__(256) void moe_cat_down_w4_kernel(const uint8_t* __restrict__ src, const uint8_t* __restrict__ src_scales,
+                                                              uint8_t* __restrict__ dst, uint8_t* __restrict__ dst_scales, int H, int I, int E) {
+    const int nt = blockIdx.x, e = blockIdx.y, kbs = I >> 5;
+    const int64_t sblk = ((int64_t)e * (H >> 4) + nt) * kbs, dblk = ((int64_t)nt * E + e) * kbs;     // first (tile, k-step) block
+    const uint32_t* s4 = (const uint32_t*)(src + sblk * 256);
+    uint32_t* d4 = (uint32_t*)(dst + dblk * 256);
+    for (int i = threadIdx.x; i < kbs * 64; i += 256) d4[i] = s4[i];
+    const uint32_t* ss = (const uint32_t*)(src_scales + sblk * 16);
+    uint32_t* ds = (uint32_t*)(dst_scales + dblk * 16);
+    for (int i = threadIdx.x; i < kbs * 4; i += 256) ds[i] = ss[i];
+}
+
+// the tile path's per-expert W~ of the down projection from the stored concatenated codes: out [E][H][I] bf16, fragment-major
+// per expert (expert e at e*H*I: the grouped GEMMs' w_expert_stride), n8 = E*H*I/8 fragments, H % 16 == 0
+__global__ __launch_bounds__(256) void e4_dequant_down_kernel(const uint8_t* __restrict__ codes, const uint8_t* __restrict__ scales,
+                                                              int H, int I, int E, int64_t n8, bf16_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    const int64_t per_e = (int64_t)H * I / 8, kbs = I >> 5;
+    const int64_t e = i / per_e, j = i - e * per_e;            // j = (tile * kbs + ks) * 64 + lane
+    const int64_t lane = j & 63, blk = j >> 6, tile = blk / kbs, ks = blk - tile * kbs;
+    const int64_t sblk = (tile * E + e) * kbs + ks;
+    *(bf16x8*)(out + i * 8) = w4_frag(*(const uint32_t*)(codes + (sblk * 64 + lane) * 4), (uint32_t)scales[sblk * 16 + (lane & 15)]);
+}
+
 // W~ of rows [0, rows) (whole 16-row tiles) into dst, fragment-major
 static inline void w4_dequant_rows(hipStream_t st, const void* codes, const uint8_t* scales, int64_t K, int64_t rows, bf16_t* dst) {
     const int64_t n8 = rows * K / 8;
@@ -90,8 +122,12 @@ static inline void w4_dequant_rows(hipStream_t st, const void* codes, const uint
 template <int EPI, typename OutT>
 static inline void launch_gemm_w4(hipStream_t st, const GemmArgs& a, const uint8_t* es, int64_t w_rows_pad, bf16_t* scratch,
                                   int64_t scratch_elems) {
-    if (a.tile_map || a.seg || a.a_rows || a.moe_gate) throw std::runtime_error("gemm: an MXFP4 weight in a gathered / grouped launch");
+    if (a.tile_map || a.seg || a.a_rows) throw std::runtime_error("gemm: an MXFP4 weight in a gathered / grouped launch");
     const float* ws = (const float*)es;     // (the launchers' scale argument; the MXFP4 kernels take it back as bytes)
+    if (a.moe_gate) {     // MXFP4 MoE experts, the decode (dense-masked) form: the only launch that reads their codes
+        if (launch_gemm_skinny_bf16<EPI, OutT, WF_MXFP4>(st, a, ws)) return;
+        throw std::runtime_error("gemm: an MXFP4 MoE projection did not fit the decode kernels");
+    }
     if (launch_gemm_skinny_bf16<EPI, OutT, WF_MXFP4>(st, a, ws)) return;
     if constexpr (EPI != EPI_QKV) {     // (the 64-row-group condition of launch_gemm_bf16, unchanged)
         const bool few_tiles = cdiv(a.M, 128) * cdiv(a.N, 128) < g_chunk_min_tiles;

@@ -54,6 +54,9 @@ check(r"gemm_skinny_wide_bf16_kernelILi[12]ELi[24]ELi4E", "wide projection, <= 3
 # the MXFP4-weight forms of the decode projections (w4.h): the fp8 forms' numbers
 check(r"gemm_skinny_mxfp4w_kernelILi[124]E", "narrow projection, MXFP4 weights", lambda r: r["spill"] <= 12 and r["vgpr"] <= 512)
 check(r"gemm_skinny_wide_mxfp4w_kernelILi[124]E", "wide projection, MXFP4 weights", lambda r: r["spill"] <= 12 and r["vgpr"] <= 512)
+# ... and their MoE instantiations (nvl_set_mx_expert_dtype)
+check(r"gemm_skinny_moe_mxfp4w_kernelILi[124]E", "narrow MoE projection, MXFP4 experts", lambda r: r["spill"] <= 12 and r["vgpr"] <= 512)
+check(r"gemm_skinny_wide_moe_mxfp4w_kernelILi[124]E", "wide MoE projection, MXFP4 experts", lambda r: r["spill"] <= 12 and r["vgpr"] <= 512)
 sys.exit(1 if bad else 0)
 PY
 exit $rc
