@@ -1,7 +1,7 @@
 // a8.h — 8-bit (OCP e4m3fn) activations on top of 8-bit weights (nvl_set_act_dtype NVL_ACT_FP8_E4M3, DESIGN.md §3 and
 // §9 f-7): the W8A8 form of every projection that w8.h would run as dequantize + tile.
 //
-// Numerics, per launch that reaches the tile step of launch_gemm_w8:
+// Numerics, per launch that reaches the tile step of launch_gemm_q (wq.h):
 //   activation rows: s_a[m] = amax_m / 448 (fp32 division; 1 for an all-zero row), q_a = e4m3fn_rne(a / s_a) through kv8.h's
 //       quantizer (fp32 division, saturated to +-448, NaN -> a NaN code; NaN elements do not enter amax_m, an infinite one
 //       makes s_a[m] infinite and the row's outputs NaN).  a is the bf16 operand the bf16 GEMM would read, exact in fp32.

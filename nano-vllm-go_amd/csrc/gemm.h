@@ -886,7 +886,7 @@ __global__ __launch_bounds__(1024) void gemm_skinny_bf16_kernel(GemmArgs p) {
 // fp8-weight form of the narrow kernel: the weights are e4m3fn codes in the same fragment-major order,
 // one byte per element (a lane loads 8 bytes per k-step), and w_scale[row] is the row's fp32 scale; w8_frag turns them into
 // the bf16 fragment of W~ = bf16_rne(s * e4m3(q)) — exactly the values the bf16 kernel would read from a bf16 W~.  The
-// body is gemm_skinny_bf16_kernel's with the weight load replaced (W8 = false reproduces it); the bf16 kernel keeps its
+// body is gemm_skinny_bf16_kernel's with the weight load replaced (WF = WF_BF16 reproduces it); the bf16 kernel keeps its
 // own copy because instantiating it from this body changed its instruction schedule and register count, and the bf16
 // kernels are kept byte-identical in the device assembly.
 // WF = WF_MXFP4 (w4.h): the codes are nibble-packed in the same fragment order (a lane loads 4 bytes per k-step, a 16-row x
@@ -1615,13 +1615,46 @@ static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a
     return true;
 }
 
+// The narrow / wide decode kernel of weight format WF with these template arguments: the one place that names the three
+// __global__ wrappers of a form (bf16: the kernel itself; quantized: the plain and the MoE wrapper of the shared body).
+// ws: the weight scales of a quantized format (fp32 per row, or the e8m0 bytes of MXFP4), unused for bf16.
+template <int WF, int MT, int NTW, int U, int EPI, typename OutT, bool PASSES = false, bool MOE = false, bool HALF = false>
+static inline void launch_skinny_wf(dim3 grid, dim3 block, size_t lds, hipStream_t st, const GemmArgs& a, const float* ws) {
+    static_assert(WF == WF_BF16 || !MOE || (!PASSES && !HALF), "the quantized MoE wrappers have no PASSES / HALF instance");
+    if constexpr (WF == WF_BF16) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MT, NTW, U, EPI, OutT, PASSES, MOE, HALF>), grid, block, lds, st, a);
+    else if constexpr (WF == WF_FP8 && MOE) hipLaunchKernelGGL((gemm_skinny_moe_fp8w_kernel<MT, NTW, U, EPI, OutT>), grid, block, lds, st, a, ws);
+    else if constexpr (WF == WF_FP8) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<MT, NTW, U, EPI, OutT, PASSES, HALF>), grid, block, lds, st, a, ws);
+    else if constexpr (MOE) hipLaunchKernelGGL((gemm_skinny_moe_mxfp4w_kernel<MT, NTW, U, EPI, OutT>), grid, block, lds, st, a, (const uint8_t*)ws);
+    else hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<MT, NTW, U, EPI, OutT, PASSES, HALF>), grid, block, lds, st, a, (const uint8_t*)ws);
+}
+template <int WF, int MT, int NTB, int U, int EPI, typename OutT, bool PASSES = false, bool MOE = false>
+static inline void launch_skinny_wide_wf(dim3 grid, dim3 block, size_t lds, hipStream_t st, const GemmArgs& a, const float* ws) {
+    static_assert(WF == WF_BF16 || !MOE || !PASSES, "the quantized MoE wrappers have no PASSES instance");
+    constexpr int max_lds = 8 * NTB * MT * 64 * 16;
+    if constexpr (WF == WF_BF16) {
+        NVL_LDS_ATTR((gemm_skinny_wide_bf16_kernel<MT, NTB, U, EPI, OutT, PASSES, MOE>), max_lds);
+        hipLaunchKernelGGL((gemm_skinny_wide_bf16_kernel<MT, NTB, U, EPI, OutT, PASSES, MOE>), grid, block, lds, st, a);
+    } else if constexpr (WF == WF_FP8 && MOE) {
+        NVL_LDS_ATTR((gemm_skinny_wide_moe_fp8w_kernel<MT, NTB, U, EPI, OutT>), max_lds);
+        hipLaunchKernelGGL((gemm_skinny_wide_moe_fp8w_kernel<MT, NTB, U, EPI, OutT>), grid, block, lds, st, a, ws);
+    } else if constexpr (WF == WF_FP8) {
+        NVL_LDS_ATTR((gemm_skinny_wide_fp8w_kernel<MT, NTB, U, EPI, OutT, PASSES>), max_lds);
+        hipLaunchKernelGGL((gemm_skinny_wide_fp8w_kernel<MT, NTB, U, EPI, OutT, PASSES>), grid, block, lds, st, a, ws);
+    } else if constexpr (MOE) {
+        NVL_LDS_ATTR((gemm_skinny_wide_moe_mxfp4w_kernel<MT, NTB, U, EPI, OutT>), max_lds);
+        hipLaunchKernelGGL((gemm_skinny_wide_moe_mxfp4w_kernel<MT, NTB, U, EPI, OutT>), grid, block, lds, st, a, (const uint8_t*)ws);
+    } else {
+        NVL_LDS_ATTR((gemm_skinny_wide_mxfp4w_kernel<MT, NTB, U, EPI, OutT, PASSES>), max_lds);
+        hipLaunchKernelGGL((gemm_skinny_wide_mxfp4w_kernel<MT, NTB, U, EPI, OutT, PASSES>), grid, block, lds, st, a, (const uint8_t*)ws);
+    }
+}
+
 // skinny dispatch: M <= 64, no gather/segments.  Returns false when the shape is not eligible.
-// W8: the same decisions, the fp8-weight kernels (ws: the per-row weight scales).  8-bit MoE experts (moe_gate) take the
-// K-split down form and the SwiGLU up form; the deferred-norm producer form of the down projection has no 8-bit instance.
-// MXFP4 MoE experts (nvl_set_mx_expert_dtype) take the same two forms on gemm_skinny_moe_mxfp4w_kernel.
+// Every weight format takes the same decisions (ws: the scales of a quantized format, launch_skinny_wf).  MoE experts
+// (moe_gate) take the K-split down form and the SwiGLU up form; the deferred-norm producer form of the down projection,
+// whose waves cross experts, exists for bf16 experts only.
 template <int NTW, int EPI, typename OutT, int WF = 0>
 static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
-    constexpr bool W8 = WF == WF_FP8, MX = WF == WF_MXFP4;     // (MX: ws carries the e8m0 scale bytes, w4.h)
     const int MT = skinny_rows(a) <= 16 ? 1 : (skinny_rows(a) <= 32 ? 2 : 4);
     if (EPI == EPI_RESID && a.m_split && a.rs_out && NTW == 1 && a.m_passes <= 1 && a.grid_y != 1) {   // (m_split: grid_y unused, keep it defined)
         GemmArgs c = a; c.grid_y = 1; return launch_gemm_skinny_ntw<NTW, EPI, OutT, WF>(st, c, ws);
@@ -1635,7 +1668,7 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
         while (ks > 1 && (a.K >> 5) / ks < 4) ks >>= 1;
         if (a.K % 32 != 0) return false;
         if constexpr (EPI == EPI_RESID) {
-            if (a.moe_gate && (W8 || MX)) return false;     // (no quantized instance of the producer form, see moe())
+            if (a.moe_gate && WF != WF_BF16) return false;     // (no quantized instance of the producer form, see moe())
             if (a.moe_gate) {     // MoE down as the deferred-norm producer: all experts in one workgroup's K range, 16 waves
                 ks = 16;
                 const int nks = a.K >> 5, spe = a.moe_I >> 5;
@@ -1652,27 +1685,11 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
             }
             if (a.rs_half) {      // <= 16 rows: 8 weight rows per workgroup, twice the workgroups (HALF above)
                 if (a.M > 16) return false;
-                if constexpr (MX)
-                    hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<1, NTW, 4, EPI, OutT, false, true>), dim3(2 * nblocks, 1), dim3(NTW * ks * 64),
-                                       (size_t)NTW * ks * 64 * 16, st, a, (const uint8_t*)ws);
-                else if constexpr (W8)
-                    hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<1, NTW, 4, EPI, OutT, false, true>), dim3(2 * nblocks, 1), dim3(NTW * ks * 64),
-                                       (size_t)NTW * ks * 64 * 16, st, a, ws);
-                else
-                hipLaunchKernelGGL((gemm_skinny_bf16_kernel<1, NTW, 4, EPI, OutT, false, false, true>), dim3(2 * nblocks, 1), dim3(NTW * ks * 64),
-                                   (size_t)NTW * ks * 64 * 16, st, a);
+                launch_skinny_wf<WF, 1, NTW, 4, EPI, OutT, false, false, true>(dim3(2 * nblocks, 1), dim3(NTW * ks * 64), (size_t)NTW * ks * 64 * 16, st, a, ws);
                 return true;
             }
         }
-        if constexpr (MX)
-            hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<1, NTW, 4, EPI, OutT>), dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64),
-                               (size_t)NTW * ks * 64 * 16, st, a, (const uint8_t*)ws);
-        else if constexpr (W8)
-            hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<1, NTW, 4, EPI, OutT>), dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64),
-                               (size_t)NTW * ks * 64 * 16, st, a, ws);
-        else
-        hipLaunchKernelGGL((gemm_skinny_bf16_kernel<1, NTW, 4, EPI, OutT>), dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64),
-                           (size_t)NTW * ks * 64 * 16, st, a);
+        launch_skinny_wf<WF, 1, NTW, 4, EPI, OutT>(dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64), (size_t)NTW * ks * 64 * 16, st, a, ws);
         return true;
     }
     // waves per launch: enough to cover HBM latency on every CU (~2-4 thousand), not more — extra K slices only
@@ -1695,55 +1712,19 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
     if (a.m_passes > 1 && (nblocks % 8 != 0 || KS != 1)) return launch_skinny_passes_serial<EPI, OutT, WF>(st, a, ws);
     dim3 grid(nblocks * (a.m_passes > 1 ? a.m_passes : 1), KS), block(NTW * ksplit * 64);
     if (a.grid_y != KS) { GemmArgs c = a; c.grid_y = KS; return launch_gemm_skinny_ntw<NTW, EPI, OutT, WF>(st, c, ws); }
-    if constexpr (MX) {
-        const uint8_t* es = (const uint8_t*)ws;
-        if (a.moe_gate) {                                 // MXFP4 MoE experts (nvl_set_mx_expert_dtype)
-            if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
-                if (a.m_passes > 1) return false;
-                if (MT == 1) hipLaunchKernelGGL((gemm_skinny_moe_mxfp4w_kernel<1, NTW, 4, EPI, OutT>), grid, block, lds, st, a, es);
-                else if (MT == 2) hipLaunchKernelGGL((gemm_skinny_moe_mxfp4w_kernel<2, NTW, 4, EPI, OutT>), grid, block, lds, st, a, es);
-                else hipLaunchKernelGGL((gemm_skinny_moe_mxfp4w_kernel<4, NTW, 2, EPI, OutT>), grid, block, lds, st, a, es);
-                return true;
-            }
-            return false;
-        }
-        if (a.m_passes > 1) hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<4, NTW, 2, EPI, OutT, true>), grid, block, lds, st, a, es);
-        else if (MT == 1) hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<1, NTW, 4, EPI, OutT>), grid, block, lds, st, a, es);
-        else if (MT == 2) hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<2, NTW, 4, EPI, OutT>), grid, block, lds, st, a, es);
-        else hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<4, NTW, 2, EPI, OutT>), grid, block, lds, st, a, es);
-        return true;
-    } else if constexpr (W8) {
-        if (a.moe_gate) {                                 // 8-bit MoE experts
-            if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
-                if (a.m_passes > 1) return false;
-                if (MT == 1) hipLaunchKernelGGL((gemm_skinny_moe_fp8w_kernel<1, NTW, 4, EPI, OutT>), grid, block, lds, st, a, ws);
-                else if (MT == 2) hipLaunchKernelGGL((gemm_skinny_moe_fp8w_kernel<2, NTW, 4, EPI, OutT>), grid, block, lds, st, a, ws);
-                else hipLaunchKernelGGL((gemm_skinny_moe_fp8w_kernel<4, NTW, 2, EPI, OutT>), grid, block, lds, st, a, ws);
-                return true;
-            }
-            return false;
-        }
-        if (a.m_passes > 1) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<4, NTW, 2, EPI, OutT, true>), grid, block, lds, st, a, ws);
-        else if (MT == 1) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<1, NTW, 4, EPI, OutT>), grid, block, lds, st, a, ws);
-        else if (MT == 2) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<2, NTW, 4, EPI, OutT>), grid, block, lds, st, a, ws);
-        else hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<4, NTW, 2, EPI, OutT>), grid, block, lds, st, a, ws);
-        return true;
-    } else {
-#define NVL_SK(MTv, Uv) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MTv, NTW, Uv, EPI, OutT>), grid, block, lds, st, a)
-#define NVL_SKM(MTv, Uv) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MTv, NTW, Uv, EPI, OutT, false, true>), grid, block, lds, st, a)
-    if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
-        if (a.moe_gate) {                                 // MoE decode instantiation (expert skip + gate weight)
+#define NVL_SK(MTv, Uv, ...) launch_skinny_wf<WF, MTv, NTW, Uv, EPI, OutT, __VA_ARGS__>(grid, block, lds, st, a, ws)
+    if (a.moe_gate) {                                 // MoE decode instantiation (expert skip + gate weight)
+        if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
             if (a.m_passes > 1) return false;
-            if (MT == 1) NVL_SKM(1, 4); else if (MT == 2) NVL_SKM(2, 4); else NVL_SKM(4, 2);
+            if (MT == 1) NVL_SK(1, 4, false, true); else if (MT == 2) NVL_SK(2, 4, false, true); else NVL_SK(4, 2, false, true);
             return true;
+        } else if constexpr (WF != WF_BF16) {
+            return false;     // (quantized experts: no other epilogue; bf16 falls through to the plain kernel, as it always has)
         }
     }
-    if (a.m_passes > 1) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<4, NTW, 2, EPI, OutT, true>), grid, block, lds, st, a);
-    else if (MT == 1) NVL_SK(1, 4); else if (MT == 2) NVL_SK(2, 4); else NVL_SK(4, 2);
+    if (a.m_passes > 1) NVL_SK(4, 2, true); else if (MT == 1) NVL_SK(1, 4, false); else if (MT == 2) NVL_SK(2, 4, false); else NVL_SK(4, 2, false);
 #undef NVL_SK
-#undef NVL_SKM
     return true;
-    }
 }
 // Weight tiles per wave of the wide form (nvl_set_tuning key 36: 0 automatic, 2 / 4 forced).  Four tiles per wave quarter the
 // activation fetches per weight byte, but an FFN-up launch is then only 256 workgroups of 2 waves — 64 KiB of weights in
@@ -1770,81 +1751,18 @@ static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, co
     const size_t lds = (size_t)ksplit * NTB * MT * 64 * 16;
     if (a.m_passes > 1 && groups % 8 != 0) return launch_skinny_passes_serial<EPI, OutT, WF>(st, a, ws);
     const int wgs = groups * (a.m_passes > 1 ? a.m_passes : 1);
-    constexpr bool W8 = WF == WF_FP8, MX = WF == WF_MXFP4;
-    if constexpr (MX) {
-#define NVL_SKW4(MTv, Uv, Pv)                                                                                            \
-    do {                                                                                                               \
-        NVL_LDS_ATTR((gemm_skinny_wide_mxfp4w_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), 8 * NTB * MTv * 64 * 16);          \
-        hipLaunchKernelGGL((gemm_skinny_wide_mxfp4w_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), dim3(wgs), dim3(ksplit * 64),    \
-                           lds, st, a, (const uint8_t*)ws);                                                            \
-    } while (0)
-#define NVL_SKW4M(MTv, Uv)                                                                                               \
-    do {                                                                                                               \
-        NVL_LDS_ATTR((gemm_skinny_wide_moe_mxfp4w_kernel<MTv, NTB, Uv, EPI, OutT>), 8 * NTB * MTv * 64 * 16);         \
-        hipLaunchKernelGGL((gemm_skinny_wide_moe_mxfp4w_kernel<MTv, NTB, Uv, EPI, OutT>), dim3(wgs), dim3(ksplit * 64),   \
-                           lds, st, a, (const uint8_t*)ws);                                                            \
-    } while (0)
-        if (a.moe_gate) {                                 // MXFP4 MoE experts: the expert up projection
-            if constexpr (EPI == EPI_SWIGLU) {
-                if (a.m_passes > 1) return false;
-                if (MT == 1) NVL_SKW4M(1, 4); else if (MT == 2) NVL_SKW4M(2, 4); else NVL_SKW4M(4, 2);
-                return true;
-            }
-            return false;
-        }
-#undef NVL_SKW4M
-        if (a.m_passes > 1) NVL_SKW4(4, 2, true); else if (MT == 1) NVL_SKW4(1, 4, false); else if (MT == 2) NVL_SKW4(2, 4, false); else NVL_SKW4(4, 2, false);
-#undef NVL_SKW4
-        return true;
-    }
-    if constexpr (W8) {
-#define NVL_SKW8(MTv, Uv, Pv)                                                                                            \
-    do {                                                                                                               \
-        NVL_LDS_ATTR((gemm_skinny_wide_fp8w_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), 8 * NTB * MTv * 64 * 16);            \
-        hipLaunchKernelGGL((gemm_skinny_wide_fp8w_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), dim3(wgs), dim3(ksplit * 64),      \
-                           lds, st, a, ws);                                                                            \
-    } while (0)
-#define NVL_SKW8M(MTv, Uv)                                                                                               \
-    do {                                                                                                               \
-        NVL_LDS_ATTR((gemm_skinny_wide_moe_fp8w_kernel<MTv, NTB, Uv, EPI, OutT>), 8 * NTB * MTv * 64 * 16);           \
-        hipLaunchKernelGGL((gemm_skinny_wide_moe_fp8w_kernel<MTv, NTB, Uv, EPI, OutT>), dim3(wgs), dim3(ksplit * 64),     \
-                           lds, st, a, ws);                                                                            \
-    } while (0)
-        if (a.moe_gate) {                                 // 8-bit MoE experts: the expert up projection
-            if constexpr (EPI == EPI_SWIGLU) {
-                if (a.m_passes > 1) return false;
-                if (MT == 1) NVL_SKW8M(1, 4); else if (MT == 2) NVL_SKW8M(2, 4); else NVL_SKW8M(4, 2);
-                return true;
-            }
-            return false;
-        }
-#undef NVL_SKW8M
-        if (a.m_passes > 1) NVL_SKW8(4, 2, true); else if (MT == 1) NVL_SKW8(1, 4, false); else if (MT == 2) NVL_SKW8(2, 4, false); else NVL_SKW8(4, 2, false);
-#undef NVL_SKW8
-        return true;
-    }
-#define NVL_SKW(MTv, Uv, Pv)                                                                                             \
-    do {                                                                                                               \
-        NVL_LDS_ATTR((gemm_skinny_wide_bf16_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), 8 * NTB * MTv * 64 * 16);            \
-        hipLaunchKernelGGL((gemm_skinny_wide_bf16_kernel<MTv, NTB, Uv, EPI, OutT, Pv>), dim3(wgs), dim3(ksplit * 64),      \
-                           lds, st, a);                                                                                \
-    } while (0)
-#define NVL_SKWM(MTv, Uv)                                                                                                \
-    do {                                                                                                               \
-        NVL_LDS_ATTR((gemm_skinny_wide_bf16_kernel<MTv, NTB, Uv, EPI, OutT, false, true>), 8 * NTB * MTv * 64 * 16);         \
-        hipLaunchKernelGGL((gemm_skinny_wide_bf16_kernel<MTv, NTB, Uv, EPI, OutT, false, true>), dim3(wgs), dim3(ksplit * 64), \
-                           lds, st, a);                                                                                \
-    } while (0)
-    if constexpr (EPI == EPI_SWIGLU) {
-        if (a.moe_gate) {
+#define NVL_SKW(MTv, Uv, ...) launch_skinny_wide_wf<WF, MTv, NTB, Uv, EPI, OutT, __VA_ARGS__>(dim3(wgs), dim3(ksplit * 64), lds, st, a, ws)
+    if (a.moe_gate) {                                 // MoE experts: the expert up projection
+        if constexpr (EPI == EPI_SWIGLU) {
             if (a.m_passes > 1) return false;
-            if (MT == 1) NVL_SKWM(1, 4); else if (MT == 2) NVL_SKWM(2, 4); else NVL_SKWM(4, 2);
+            if (MT == 1) NVL_SKW(1, 4, false, true); else if (MT == 2) NVL_SKW(2, 4, false, true); else NVL_SKW(4, 2, false, true);
             return true;
+        } else if constexpr (WF != WF_BF16) {
+            return false;     // (as in the narrow form: bf16 falls through to the plain kernel)
         }
     }
     if (a.m_passes > 1) NVL_SKW(4, 2, true); else if (MT == 1) NVL_SKW(1, 4, false); else if (MT == 2) NVL_SKW(2, 4, false); else NVL_SKW(4, 2, false);
 #undef NVL_SKW
-#undef NVL_SKWM
     return true;
 }
 template <int EPI, typename OutT, int WF>
@@ -1906,6 +1824,13 @@ static inline void launch_gemm_grouped(hipStream_t st, const GemmArgs& a, int ma
                        lds, st, a);
 }
 
+// the 64-row-group condition of launch_gemm_bf16 (below), shared with the quantized dispatch (wq.h)
+static inline bool skinny_groups_ok(const GemmArgs& a) {
+    const bool few_tiles = cdiv(a.M, 128) * cdiv(a.N, 128) < g_chunk_min_tiles;
+    return a.M > 64 && a.M <= g_chunk_max_m && (a.M <= g_chunk_all_m || few_tiles || a.rs_in || a.rs_out) && !a.a_rows && !a.seg && !a.sk_part &&
+           a.K % 32 == 0 && g_force_tile == 0;
+}
+
 template <int EPI, typename OutT>
 static inline void launch_gemm_bf16(hipStream_t st, const GemmArgs& a) {
     if (a.tile_map) { launch_gemm_grouped<EPI, OutT>(st, a, a.M); return; }   // a.M carries the m-tile bound
@@ -1916,9 +1841,7 @@ static inline void launch_gemm_bf16(hipStream_t st, const GemmArgs& a) {
         // in one launch instead (GemmArgs::m_passes): the groups of a weight block run side by side on one XCD, so the
         // weights cross HBM once.  Only the narrow projections (QKV, O, FFN-down) do; FFN-up and the LM head have enough
         // tiles (g_chunk_all_m: below it every projection would).
-        const bool few_tiles = cdiv(a.M, 128) * cdiv(a.N, 128) < g_chunk_min_tiles;
-        if (a.M > 64 && a.M <= g_chunk_max_m && (a.M <= g_chunk_all_m || few_tiles || a.rs_in || a.rs_out) && !a.a_rows && !a.seg && !a.sk_part && a.K % 32 == 0 &&
-            g_force_tile == 0) {
+        if (skinny_groups_ok(a)) {
             GemmArgs c = a;
             c.m_passes = cdiv(a.M, 64);
             const bool ok = g_pass_interleave ? launch_gemm_skinny_bf16<EPI, OutT>(st, c)

@@ -329,7 +329,7 @@ void up2d_f8(nvl_model* m, int kind, int layer, const uint8_t* codes, const std:
     for (int64_t i = 0; i < N * K; i++)
         if ((codes[i] & 0x7F) == 0x7F) throw std::runtime_error("loader: F8_E4M3 weight holds a NaN code");
     int rc;
-    if (w8_kind(m, kind) && (layout == NVL_LAYOUT_OUT_IN || kind == NVL_T_TOK_EMB)) {
+    if (q_kind(m, kind) == WF_FP8 && (layout == NVL_LAYOUT_OUT_IN || kind == NVL_T_TOK_EMB)) {
         rc = nvl_upload_tensor_fp8(m, kind, layer, codes, sc.data(), N, K, NVL_LAYOUT_OUT_IN);
     } else {
         std::vector<float> w((size_t)(N * K));

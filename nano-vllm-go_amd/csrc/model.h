@@ -16,8 +16,7 @@
 #include "elem.h"
 #include "sample.h"
 #include "gemm.h"
-#include "w8.h"
-#include "w4.h"
+#include "wq.h"
 #include "mamba.h"
 #include "tp_p2p.h"
 
@@ -25,8 +24,8 @@ namespace nvl {
 
 struct DevTensor {
     void* p = nullptr;      // canonical device copy: 2-D [rows_pad][cols] in weight dtype, 1-D fp32
-    float* scale = nullptr; // 8-bit weights (w8.h): p holds e4m3fn codes, scale[rows_pad] the per-row fp32 scales
-    uint8_t* mxs = nullptr; // MXFP4 weights (w4.h): p holds the nibble-packed e2m1 codes, mxs the e8m0 block scales
+    void* qs = nullptr;     // quantized weights (wf != WF_BF16): p holds the codes, qs their scales in the format's layout (wq.h)
+    int wf = WF_BF16;       // stored format (gemm.h WF_*)
     int64_t rows = 0, cols = 0, rows_pad = 0;
     bool present() const { return p != nullptr; }
 };
@@ -36,20 +35,15 @@ struct LayerW {
     // frozen by finalize()
     void* w_qkv = nullptr; int n_qkv = 0; float* b_qkv = nullptr;
     void* w1 = nullptr; int n1 = 0;      // fused rows (2F for SwiGLU, F for GELU)
-    float* s_qkv = nullptr; float* s1 = nullptr;   // 8-bit weights: the row scales of w_qkv / w1 (they follow the fused rows)
-    uint8_t* e_qkv = nullptr; uint8_t* e1 = nullptr;   // MXFP4 weights: the block scales of w_qkv / w1 (they follow the 16-row tiles)
+    void* qs_qkv = nullptr; void* qs1 = nullptr;   // quantized weights: the scales of w_qkv / w1 (they follow the fused rows / 16-row tiles)
     void* moe_in = nullptr;              // [E][2I (interleaved in bf16 mode)][H]
     void* moe_out_cat = nullptr;         // bf16: W_down of all experts along K, [H_pad][E*I] (decode "dense-masked" form)
-    // 8-bit experts (nvl_set_expert_dtype): moe_in holds codes in the same interleaved order, s_moe_in [rows_pad] its row
-    // scales; moe_out8 the down codes, [H_pad][E*I] (the layout of moe_out_cat: moe_out_cat = moe_out8 when the decode
-    // form applies), s_moe_out [E][H_pad] its scales
-    float* s_moe_in = nullptr;
-    void* moe_out8 = nullptr; float* s_moe_out = nullptr;
-    // MXFP4 experts (nvl_set_mx_expert_dtype): moe_in holds nibble-packed codes in the same interleaved order, e_moe_in its
-    // block scales; moe_out4 the down codes over K = E*I, [H_pad][E*I/2] (moe_out_cat = moe_out4 when the decode form
-    // applies), e_moe_out their block scales [H_pad/16][E*I/32][16] — beside the code tiles, no per-expert scale row
-    uint8_t* e_moe_in = nullptr;
-    void* moe_out4 = nullptr; uint8_t* e_moe_out = nullptr;
+    // quantized experts (nvl_set_expert_dtype / nvl_set_mx_expert_dtype): moe_in holds codes in the same interleaved order,
+    // qs_moe_in its scales; moe_out_q the down codes over K = E*I, [H_pad][E*I] (the layout of moe_out_cat: moe_out_cat =
+    // moe_out_q when the decode form applies), qs_moe_out its scales — fp8: [E][H_pad], one row per expert; MXFP4:
+    // [H_pad/16][E*I/32][16], beside the code tiles
+    void* qs_moe_in = nullptr;
+    void* moe_out_q = nullptr; void* qs_moe_out = nullptr;
     bool mamba = false;                  // a Mamba2 block (attention tensors absent); index among the Mamba2 layers
     int mamba_idx = -1;
 };
@@ -95,25 +89,15 @@ struct nvl_model {
     int kv_esize = 2;                      // bytes per cached K/V element (wsize, or 1 in 8-bit mode)
     std::vector<float> k_scale, v_scale;   // [num_layers], default 1 (Mamba2 layers' entries unused)
     bool kv_written = false;               // a forward has been enqueued: the scales are fixed from then on
-    // 8-bit projection weights (nvl_set_weight_dtype NVL_W_FP8_E4M3, w8.h): e4m3fn codes + per-row fp32 scales
-    bool w8 = false;
+    // quantized weights (wq.h): the stored format of the projections (nvl_set_weight_dtype: WF_FP8, nvl_set_mx_weight_dtype:
+    // WF_MXFP4) and of the MoE experts (nvl_set_expert_dtype / nvl_set_mx_expert_dtype; WF_BF16 or the projections' format)
+    int wf = nvl::WF_BF16, ef = nvl::WF_BF16;
     bool w2d_uploaded = false;             // a 2-D tensor has been uploaded: the weight dtype is fixed from then on
-    struct W8Ref { const float* scale; int64_t rows_pad; };
-    std::map<const void*, W8Ref> w8_map;   // finalized 8-bit weights by code pointer (gemm() dispatch)
-    nvl::bf16_t* w8_scratch = nullptr; int64_t w8_scratch_elems = 0;   // W~ of the tile path (largest non-LM-head projection)
-    float* lm_head_scale = nullptr;
-    // MXFP4 projection weights (nvl_set_mx_weight_dtype NVL_MX_FP4_E2M1, w4.h): e2m1 codes + e8m0 block scales; the tile
-    // path's W~ goes through w8_scratch (the two modes exclude each other)
-    bool mx = false;
-    struct W4Ref { const uint8_t* scales; int64_t rows_pad; };
-    std::map<const void*, W4Ref> w4_map;   // finalized MXFP4 weights by code pointer (gemm() dispatch)
-    // 8-bit MoE experts (nvl_set_expert_dtype NVL_EXPERT_FP8_E4M3, w8.h): W~ of one layer's experts for the grouped GEMMs
-    bool e8 = false;
     bool expert_uploaded = false;          // an expert tensor has been uploaded: the expert dtype is fixed from then on
-    nvl::bf16_t* e8_scratch = nullptr; int64_t e8_scratch_elems = 0;
-    // MXFP4 MoE experts (nvl_set_mx_expert_dtype NVL_MXE_FP4_E2M1, w4.h): the grouped GEMMs' W~ goes through e8_scratch (the
-    // two expert modes exclude each other, as their projection modes do)
-    bool e4 = false;
+    struct QRef { int wf; const void* scales; int64_t rows_pad; };
+    std::map<const void*, QRef> qmap;      // finalized quantized weights by code pointer (gemm() dispatch)
+    nvl::bf16_t* wq_scratch = nullptr; int64_t wq_scratch_elems = 0;   // tile path: W~ of one projection (the largest but the LM head)
+    nvl::bf16_t* eq_scratch = nullptr; int64_t eq_scratch_elems = 0;   // grouped GEMMs: W~ of one layer's experts (up, then down)
     // 8-bit activations of the tile step (nvl_set_act_dtype NVL_ACT_FP8_E4M3, a8.h): codes [a8_rows][a8_k] + scales [a8_rows]
     bool a8 = false;
     uint8_t* a8_codes = nullptr; float* a8_scale = nullptr; int64_t a8_rows = 0, a8_k = 0;

@@ -150,53 +150,34 @@ unsigned long long* next_stamps(nvl_model* m, int site, int nwg) {
     m->stamp_recs.push_back({site, m->phase, nwg});
     return m->stamp_buf + (size_t)(m->stamp_launches++) * STAMP_MAX_WG * 8;
 }
+// the epilogue switch of a quantized weight of format WF
+template <int WF>
+void gemm_q(nvl_model* m, int epi, bool out_f32, const GemmArgs& a, const nvl_model::QRef& q) {
+    const A8Buf a8buf{m->a8_codes, m->a8_scale, m->a8_rows, m->a8_k};
+    const A8Buf* a8 = m->a8 ? &a8buf : nullptr;     // 8-bit activations at the tile step (a8.h; fp8 weights only)
+#define NVL_GQ(EPIv, OutTv) launch_gemm_q<EPIv, OutTv, WF>(m->stream, a, q.scales, q.rows_pad, m->wq_scratch, m->wq_scratch_elems, a8)
+    switch (epi) {
+        case EPI_STORE:  if (out_f32) NVL_GQ(EPI_STORE, float); else NVL_GQ(EPI_STORE, bf16_t); break;
+        case EPI_RESID:  NVL_GQ(EPI_RESID, float); break;
+        case EPI_SWIGLU: NVL_GQ(EPI_SWIGLU, bf16_t); break;
+        case EPI_GELU:   NVL_GQ(EPI_GELU, bf16_t); break;
+        case EPI_QKV:    NVL_GQ(EPI_QKV, bf16_t); break;
+        default: throw std::runtime_error("gemm: bad epilogue");
+    }
+#undef NVL_GQ
+}
 void gemm(nvl_model* m, int epi, bool out_f32, GemmArgs a, double flops = -1.0) {
     a.stamps = (m->stamping && !m->f32 && a.M <= 64 && !a.tile_map) ? next_stamps(m, m->site, STAMP_MAX_WG) : nullptr;
     // algorithmic bytes of a projection: every weight byte once + the activation operand + the output rows
-    const bool w8 = m->w8 && m->w8_map.count(a.W);     // 8-bit weight: one byte per element + the row scales
-    const bool w4 = m->mx && m->w4_map.count(a.W);     // MXFP4 weight: half a byte per element + a scale byte per 32
+    const auto qi = m->qmap.find(a.W);     // a quantized weight: its codes + scales (wq.h: 1 byte + 4 bytes per row, or 0.5 + 1/32 bytes)
+    const nvl_model::QRef* q = qi != m->qmap.end() ? &qi->second : nullptr;
+    const double wbytes = q ? (double)(wf_code_bytes(q->wf, (int64_t)a.N * a.K) + wf_scale_bytes(q->wf, a.N, a.K)) : (double)a.N * a.K * (double)m->wsize;
     const double gbytes = m->site_bytes > 0 ? m->site_bytes
-        : (double)a.N * a.K * (w4 ? 0.5 + 1.0 / 32 : w8 ? 1.0 : (double)m->wsize) + (w8 ? 4.0 * a.N : 0.0) + (double)a.M * a.K * (double)m->wsize
-          + (double)a.M * a.N * (out_f32 || epi == EPI_RESID ? 4.0 : (double)m->wsize);
+        : wbytes + (double)a.M * a.K * (double)m->wsize + (double)a.M * a.N * (out_f32 || epi == EPI_RESID ? 4.0 : (double)m->wsize);
     KScope ks(m, KC_GEMM, flops >= 0 ? flops : 2.0 * (double)a.M * (double)a.N * (double)a.K, -1, gbytes);
     hipStream_t st = m->stream;
-    if (m->w8) {
-        const auto it = m->w8_map.find(a.W);
-        if (it != m->w8_map.end()) {     // an 8-bit weight (w8.h): the same dispatch on the fp8-weight kernels / dequantize + tile
-            const float* ws = it->second.scale;
-            const int64_t rp = it->second.rows_pad;
-            const A8Buf a8buf{m->a8_codes, m->a8_scale, m->a8_rows, m->a8_k};
-            const A8Buf* a8 = m->a8 ? &a8buf : nullptr;     // 8-bit activations at the tile step (a8.h)
-            switch (epi) {
-                case EPI_STORE:
-                    if (out_f32) launch_gemm_w8<EPI_STORE, float>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8);
-                    else launch_gemm_w8<EPI_STORE, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8);
-                    break;
-                case EPI_RESID:  launch_gemm_w8<EPI_RESID, float>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8); break;
-                case EPI_SWIGLU: launch_gemm_w8<EPI_SWIGLU, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8); break;
-                case EPI_GELU:   launch_gemm_w8<EPI_GELU, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8); break;
-                case EPI_QKV:    launch_gemm_w8<EPI_QKV, bf16_t>(st, a, ws, rp, m->w8_scratch, m->w8_scratch_elems, a8); break;
-                default: throw std::runtime_error("gemm: bad epilogue");
-            }
-            NVL_HIP(hipGetLastError());
-            return;
-        }
-    }
-    if (w4) {     // an MXFP4 weight (w4.h): the same dispatch on the MXFP4-weight kernels / dequantize + tile
-        const auto& ref = m->w4_map.find(a.W)->second;
-        const uint8_t* es = ref.scales;
-        const int64_t rp = ref.rows_pad;
-        switch (epi) {
-            case EPI_STORE:
-                if (out_f32) launch_gemm_w4<EPI_STORE, float>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems);
-                else launch_gemm_w4<EPI_STORE, bf16_t>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems);
-                break;
-            case EPI_RESID:  launch_gemm_w4<EPI_RESID, float>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems); break;
-            case EPI_SWIGLU: launch_gemm_w4<EPI_SWIGLU, bf16_t>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems); break;
-            case EPI_GELU:   launch_gemm_w4<EPI_GELU, bf16_t>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems); break;
-            case EPI_QKV:    launch_gemm_w4<EPI_QKV, bf16_t>(st, a, es, rp, m->w8_scratch, m->w8_scratch_elems); break;
-            default: throw std::runtime_error("gemm: bad epilogue");
-        }
+    if (q) {     // the same dispatch on the kernels of the weight's format / dequantize + tile (wq.h)
+        if (q->wf == WF_FP8) gemm_q<WF_FP8>(m, epi, out_f32, a, *q); else gemm_q<WF_MXFP4>(m, epi, out_f32, a, *q);
         NVL_HIP(hipGetLastError());
         return;
     }
@@ -372,16 +353,15 @@ extern "C" void nvl_destroy(nvl_model* m) {
     if (!m) return;
     (void)hipSetDevice(m->device);
     if (m->stream) (void)hipStreamSynchronize(m->stream);
-    for (int k = 0; k < NVL_T_COUNT; k++) { dfree(m->g[k].p); dfree(m->g[k].scale); dfree(m->g[k].mxs); }
+    for (int k = 0; k < NVL_T_COUNT; k++) { dfree(m->g[k].p); dfree(m->g[k].qs); }
     for (auto& l : m->layers) {
-        for (int k = 0; k < NVL_T_COUNT; k++) { dfree(l.t[k].p); dfree(l.t[k].scale); dfree(l.t[k].mxs); }
+        for (int k = 0; k < NVL_T_COUNT; k++) { dfree(l.t[k].p); dfree(l.t[k].qs); }
         dfree(l.w_qkv); dfree(l.b_qkv); dfree(l.w1); dfree(l.moe_in); dfree(l.moe_out_cat);
-        dfree(l.s_qkv); dfree(l.s1); dfree(l.e_qkv); dfree(l.e1);
-        if (l.moe_out_cat != l.moe_out8) dfree(l.moe_out8);
-        if (l.moe_out_cat != l.moe_out4) dfree(l.moe_out4);
-        dfree(l.s_moe_in); dfree(l.s_moe_out); dfree(l.e_moe_in); dfree(l.e_moe_out);
+        dfree(l.qs_qkv); dfree(l.qs1);
+        if (l.moe_out_cat != l.moe_out_q) dfree(l.moe_out_q);
+        dfree(l.qs_moe_in); dfree(l.qs_moe_out);
     }
-    dfree(m->w8_scratch); dfree(m->e8_scratch); dfree(m->a8_codes); dfree(m->a8_scale);
+    dfree(m->wq_scratch); dfree(m->eq_scratch); dfree(m->a8_codes); dfree(m->a8_scale);
     if (m->lm_head && m->lm_head != m->g[NVL_T_TOK_EMB].p && m->lm_head != m->g[NVL_T_LM_HEAD].p) dfree(m->lm_head);
     dfree(m->rope_cos); dfree(m->rope_sin); dfree(m->kcache); dfree(m->vcache);
     dfree(m->x); dfree(m->xn); dfree(m->qkv); dfree(m->q); dfree(m->attn_out); dfree(m->attn_part); dfree(m->attn_part_cnt); dfree(m->hbuf); dfree(m->h2);
@@ -420,34 +400,36 @@ namespace {
 // canonical device copy: 2-D -> [rows_pad(W_ROW_PAD)][K] in weight dtype; 1-D -> fp32.
 // `sl` selects the sub-block of the uploaded tensor that lands in rows [dn0, dn0+N) (the whole tensor for
 // replicated kinds, this rank's shard for tensor-parallel kinds); total_rows sizes the destination.
-// is this 2-D kind stored 8-bit in an fp8-weight model?  The projections and the LM head; the token embedding only when it
-// is the (tied) LM head too; the MoE experts with nvl_set_expert_dtype.  Position embedding, router and Mamba2 projections
-// stay bf16.
-bool w8_kind(const nvl_model* m, int kind) {
-    if (!m->w8) return false;
-    switch (kind) {
-        case NVL_T_WQ: case NVL_T_WK: case NVL_T_WV: case NVL_T_WKV: case NVL_T_WO: case NVL_T_W1: case NVL_T_W2:
-        case NVL_T_LM_HEAD: return true;
-        case NVL_T_TOK_EMB: return m->cfg.tied_embedding != 0;
-        case NVL_T_MOE_IN: case NVL_T_MOE_OUT: return m->e8;
-        default: return false;
+// the quantized format this 2-D kind is stored in (wq.h wf_covers), or WF_BF16
+int q_kind(const nvl_model* m, int kind) { return wf_covers(m->wf, m->ef, kind, m->cfg.tied_embedding != 0) ? m->wf : WF_BF16; }
+
+// the scales of `rows` rows of K inputs, every one the pad value of the format: fp32 1.0, or the e8m0 byte 127 (2^0)
+void* q_alloc_scales(nvl_model* m, int wf, int64_t rows, int64_t K) {
+    void* qs = dmalloc_bytes(wf_scale_bytes(wf, rows, K));
+    if (wf == WF_MXFP4) {
+        NVL_HIP(hipMemsetAsync(qs, 127, (size_t)wf_scale_bytes(wf, rows, K), m->stream));
+    } else {
+        const std::vector<float> ones((size_t)rows, 1.0f);
+        NVL_HIP(hipMemcpy(qs, ones.data(), (size_t)rows * 4, hipMemcpyHostToDevice));   // (synchronous: `ones` is pageable and local)
     }
+    return qs;
 }
 
-// codes [Npad][K] zeroed, scales [Npad] = 1 (pad rows)
-void w8_alloc(nvl_model* m, DevTensor* t, int64_t Npad, int64_t K) {
-    dfree(t->p); dfree(t->scale);
-    t->p = dmalloc_bytes(Npad * K);
-    t->scale = dmalloc<float>(Npad);
-    NVL_HIP(hipMemsetAsync(t->p, 0, (size_t)(Npad * K), m->stream));
-    const std::vector<float> ones((size_t)Npad, 1.0f);
-    NVL_HIP(hipMemcpy(t->scale, ones.data(), (size_t)Npad * 4, hipMemcpyHostToDevice));   // (synchronous: `ones` is pageable and local)
+// codes of [Npad][K] zeroed, scales at their pad value, and the tensor's shape
+void q_alloc(nvl_model* m, DevTensor* t, int wf, int64_t N, int64_t K) {
+    const int64_t Npad = round_up(N, W_ROW_PAD);
+    dfree(t->p); dfree(t->qs);
+    t->p = dmalloc_bytes(wf_code_bytes(wf, Npad * K));
+    NVL_HIP(hipMemsetAsync(t->p, 0, (size_t)wf_code_bytes(wf, Npad * K), m->stream));
+    t->qs = q_alloc_scales(m, wf, Npad, K);
+    t->wf = wf; t->rows = N; t->cols = K; t->rows_pad = Npad;
 }
+double q_bytes(const DevTensor& t) { return (double)wf_code_bytes(t.wf, t.rows_pad * t.cols) + (double)wf_scale_bytes(t.wf, t.rows_pad, t.cols); }
 
-// 8-bit weight (tensor parallelism is refused in this mode: the tensor is always whole, one piece): fp32 [N][K] on the
-// device, then w8_quant_rows_kernel -> codes [Npad][K] (fragment-major bytes) + scales [Npad]
-void upload_2d_w8(nvl_model* m, DevTensor* t, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out) {
-    if (K % 32 != 0) throw std::runtime_error("8-bit weights: the input width must be a multiple of 32");
+// quantized weight (tensor parallelism is refused in these modes: the tensor is always whole, one piece): fp32 [N][K] on the
+// device, then the format's quantizer -> codes + scales in its device layout (w8.h / w4.h)
+void upload_2d_q(nvl_model* m, DevTensor* t, int wf, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out) {
+    if (K % 32 != 0) throw std::runtime_error(std::string(wf_name(wf)) + " weights: the input width must be a multiple of 32");
     const size_t esz = dtype == NVL_DTYPE_F32 ? 4 : 2;
     void* raw = dmalloc_bytes(N * K * (int64_t)esz);
     NVL_HIP(hipMemcpyAsync(raw, data, (size_t)(N * K) * esz, hipMemcpyDefault, m->stream));
@@ -455,67 +437,23 @@ void upload_2d_w8(nvl_model* m, DevTensor* t, const void* data, int dtype, int64
     hipLaunchKernelGGL((convert_2d_kernel<float, false>), dim3((unsigned)cdiv(K, 32), (unsigned)cdiv(N, 32)), dim3(256), 0,
                        m->stream, raw, dtype, src_is_in_out ? 1 : 0, f, N, K, Slice2D{N, K, 0, 0, 0});
     NVL_HIP(hipGetLastError());
-    const int64_t Npad = round_up(N, W_ROW_PAD);
-    w8_alloc(m, t, Npad, K);
+    q_alloc(m, t, wf, N, K);
     int* bad = dmalloc<int>(1);
     NVL_HIP(hipMemsetAsync(bad, 0, 4, m->stream));
-    hipLaunchKernelGGL(w8_quant_rows_kernel, dim3((unsigned)N), dim3(256), 0, m->stream, (const float*)f, K, (uint8_t*)t->p, t->scale, bad);
+    if (wf == WF_MXFP4)
+        hipLaunchKernelGGL(w4_quant_rows_kernel, dim3((unsigned)N), dim3(64), 0, m->stream, (const float*)f, K, (uint8_t*)t->p, (uint8_t*)t->qs, bad);
+    else
+        hipLaunchKernelGGL(w8_quant_rows_kernel, dim3((unsigned)N), dim3(256), 0, m->stream, (const float*)f, K, (uint8_t*)t->p, (float*)t->qs, bad);
     NVL_HIP(hipGetLastError());
     int h_bad = 0;
     NVL_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, m->stream));
     NVL_HIP(hipStreamSynchronize(m->stream));
     dfree(bad); dfree(f); dfree(raw);
-    t->rows = N; t->cols = K; t->rows_pad = Npad;
-    if (h_bad) { dfree(t->p); dfree(t->scale); t->p = nullptr; t->scale = nullptr;
-                 throw std::runtime_error("nvl_upload_tensor: a weight is not finite (8-bit weights refuse NaN / Inf)"); }
-    m->stats.weight_bytes += (double)Npad * K + (double)Npad * 4;
-}
-
-// is this 2-D kind stored as MXFP4 in an MX model (nvl_set_mx_weight_dtype)?  The attention and FFN projections, and the MoE
-// experts with nvl_set_mx_expert_dtype: the LM head, both embeddings, the router and the Mamba2 projections stay bf16.
-bool w4_kind(const nvl_model* m, int kind) {
-    if (!m->mx) return false;
-    switch (kind) {
-        case NVL_T_WQ: case NVL_T_WK: case NVL_T_WV: case NVL_T_WKV: case NVL_T_WO: case NVL_T_W1: case NVL_T_W2: return true;
-        case NVL_T_MOE_IN: case NVL_T_MOE_OUT: return m->e4;
-        default: return false;
+    if (h_bad) {
+        dfree(t->p); dfree(t->qs); t->p = t->qs = nullptr;
+        throw std::runtime_error(std::string("nvl_upload_tensor: a weight is not finite (") + wf_name(wf) + " weights refuse NaN / Inf)");
     }
-}
-
-// codes [Npad][K/2] zeroed, block scales [Npad/16][K/32][16] = 127 (2^0)
-void w4_alloc(nvl_model* m, DevTensor* t, int64_t Npad, int64_t K) {
-    dfree(t->p); dfree(t->mxs);
-    t->p = dmalloc_bytes(Npad * K / 2);
-    t->mxs = (uint8_t*)dmalloc_bytes(Npad * K / 32);
-    NVL_HIP(hipMemsetAsync(t->p, 0, (size_t)(Npad * K / 2), m->stream));
-    NVL_HIP(hipMemsetAsync(t->mxs, 127, (size_t)(Npad * K / 32), m->stream));
-}
-
-// MXFP4 weight (tensor parallelism is refused in this mode: the tensor is always whole): fp32 [N][K] on the device, then
-// w4_quant_rows_kernel -> codes + block scales in the device layout (w4.h)
-void upload_2d_w4(nvl_model* m, DevTensor* t, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out) {
-    if (K % 32 != 0) throw std::runtime_error("MXFP4 weights: the input width must be a multiple of 32");
-    const size_t esz = dtype == NVL_DTYPE_F32 ? 4 : 2;
-    void* raw = dmalloc_bytes(N * K * (int64_t)esz);
-    NVL_HIP(hipMemcpyAsync(raw, data, (size_t)(N * K) * esz, hipMemcpyDefault, m->stream));
-    float* f = dmalloc<float>(N * K);
-    hipLaunchKernelGGL((convert_2d_kernel<float, false>), dim3((unsigned)cdiv(K, 32), (unsigned)cdiv(N, 32)), dim3(256), 0,
-                       m->stream, raw, dtype, src_is_in_out ? 1 : 0, f, N, K, Slice2D{N, K, 0, 0, 0});
-    NVL_HIP(hipGetLastError());
-    const int64_t Npad = round_up(N, W_ROW_PAD);
-    w4_alloc(m, t, Npad, K);
-    int* bad = dmalloc<int>(1);
-    NVL_HIP(hipMemsetAsync(bad, 0, 4, m->stream));
-    hipLaunchKernelGGL(w4_quant_rows_kernel, dim3((unsigned)N), dim3(64), 0, m->stream, (const float*)f, K, (uint8_t*)t->p, t->mxs, bad);
-    NVL_HIP(hipGetLastError());
-    int h_bad = 0;
-    NVL_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, m->stream));
-    NVL_HIP(hipStreamSynchronize(m->stream));
-    dfree(bad); dfree(f); dfree(raw);
-    t->rows = N; t->cols = K; t->rows_pad = Npad;
-    if (h_bad) { dfree(t->p); dfree(t->mxs); t->p = nullptr; t->mxs = nullptr;
-                 throw std::runtime_error("nvl_upload_tensor: a weight is not finite (MXFP4 weights refuse NaN / Inf)"); }
-    m->stats.weight_bytes += (double)Npad * K / 2 + (double)Npad * K / 32;
+    m->stats.weight_bytes += q_bytes(*t);
 }
 
 void upload_2d(nvl_model* m, DevTensor* t, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out,
@@ -633,7 +571,7 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
             return fail(m, NVL_ERR_INVALID, buf);
         }
         m->w2d_uploaded = true;
-        if (w8_kind(m, kind)) upload_2d_w8(m, t, data, dtype, rows, cols, false);
+        if (q_kind(m, kind)) upload_2d_q(m, t, q_kind(m, kind), data, dtype, rows, cols, false);
         else upload_2d(m, t, data, dtype, rows, cols, false, Slice2D{rows, cols, 0, 0, 0}, rows, true);
         return NVL_OK;
     }
@@ -648,8 +586,7 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
         }
         m->w2d_uploaded = true;
         m->expert_uploaded = true;
-        if (w8_kind(m, kind)) upload_2d_w8(m, t, data, dtype, rows, cols, false);     // one scale per (expert, output row)
-        else if (w4_kind(m, kind)) upload_2d_w4(m, t, data, dtype, rows, cols, false);     // ... per 32 inputs of it
+        if (q_kind(m, kind)) upload_2d_q(m, t, q_kind(m, kind), data, dtype, rows, cols, false);     // scales per (expert, output row)
         else upload_2d(m, t, data, dtype, rows, cols, false, Slice2D{rows, cols, 0, 0, 0}, rows, true);
         return NVL_OK;
     }
@@ -665,12 +602,8 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
     }
     const bool io = layout == NVL_LAYOUT_IN_OUT;
     m->w2d_uploaded = true;
-    if (w8_kind(m, kind)) {     // (tp == 1: nvl_set_weight_dtype refuses tensor parallelism)
-        upload_2d_w8(m, t, data, dtype, SN, SK, io);
-        return NVL_OK;
-    }
-    if (w4_kind(m, kind)) {     // (tp == 1: nvl_set_mx_weight_dtype refuses tensor parallelism)
-        upload_2d_w4(m, t, data, dtype, SN, SK, io);
+    if (q_kind(m, kind)) {     // (tp == 1: the weight dtype setters refuse tensor parallelism)
+        upload_2d_q(m, t, q_kind(m, kind), data, dtype, SN, SK, io);
         return NVL_OK;
     }
     if (m->tp == 1) {
@@ -703,92 +636,71 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
     NVL_CATCH(m)
 }
 
-// pre-quantized 8-bit weight: codes [rows][cols] (OUT_IN: the checkpoint's [out, in]) and scales [rows], taken as they are
-extern "C" int nvl_upload_tensor_fp8(nvl_model* m, int kind, int layer, const uint8_t* codes, const float* scales,
-                                     int64_t rows, int64_t cols, int layout) {
-    if (!m || !codes || !scales) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: null argument");
-    if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_upload_tensor_fp8: model already finalized");
-    if (!w8_kind(m, kind)) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: not an 8-bit weight kind of this model (nvl_set_weight_dtype)");
-    if (layout != NVL_LAYOUT_OUT_IN) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
+// The pre-quantized uploads: codes [rows][cols] in the ABI packing of format wf ([out, in], as in the checkpoint) and their
+// scales, taken as they are.  fn / setter: the entry point's name and its mode's setter, for the messages.
+static int upload_prequant(nvl_model* m, int wf, const char* fn, const char* setter, int kind, int layer, const uint8_t* codes,
+                           const void* scales, int64_t rows, int64_t cols, int layout) {
+    char buf[200];
+    auto bad = [&](int code, const char* fmt, auto... args) { snprintf(buf, sizeof buf, fmt, fn, args...); return fail(m, code, buf); };
+    if (!m || !codes || !scales) return bad(NVL_ERR_INVALID, "%s: null argument");
+    if (m->finalized) return bad(NVL_ERR_STATE, "%s: model already finalized");
+    if (q_kind(m, kind) != wf) return bad(NVL_ERR_INVALID, "%s: not an %s weight kind of this model (%s)", wf_name(wf), setter);
+    if (layout != NVL_LAYOUT_OUT_IN) return bad(NVL_ERR_INVALID, "%s: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
     DevTensor* t = tensor_slot(m, kind, layer);
-    if (!t) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: bad kind or layer");
+    if (!t) return bad(NVL_ERR_INVALID, "%s: bad kind or layer");
     int64_t SN = kind == NVL_T_TOK_EMB ? m->V : full_out(m, kind), SK = kind == NVL_T_TOK_EMB ? m->H : full_in(m, kind);
-    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {     // [E * out][in], scales [E * out]
+    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {     // [E * out][in], scales per (expert, output row)
         SN = (int64_t)m->cfg.num_experts * (kind == NVL_T_MOE_IN ? 2 * (int64_t)m->F : m->H);
         SK = kind == NVL_T_MOE_IN ? m->H : m->F;
     }
-    if (rows != SN || cols != SK || SK % 32 != 0) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "nvl_upload_tensor_fp8: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld]", kind,
-                 (long long)rows, (long long)cols, (long long)SN, (long long)SK);
-        return fail(m, NVL_ERR_INVALID, buf);
+    if (rows != SN || cols != SK || SK % 32 != 0)
+        return bad(NVL_ERR_INVALID, "%s: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld]%s", kind, (long long)rows,
+                   (long long)cols, (long long)SN, (long long)SK, wf == WF_MXFP4 ? ", in % 32 == 0" : "");
+    if (wf == WF_MXFP4) {
+        for (int64_t i = 0; i < rows * (cols / 32); i++)
+            if (((const uint8_t*)scales)[i] < W4_E_MIN + 127 || ((const uint8_t*)scales)[i] > W4_E_MAX + 127)
+                return bad(NVL_ERR_INVALID, "%s: a scale byte is outside [7, 252] (0xff is the e8m0 NaN)");
+    } else {
+        for (int64_t i = 0; i < rows * cols; i++)
+            if ((codes[i] & 0x7F) == 0x7F) return bad(NVL_ERR_INVALID, "%s: NaN code (0x7f / 0xff)");
+        for (int64_t r = 0; r < rows; r++)
+            if (!(((const float*)scales)[r] > 0.f) || !std::isfinite(((const float*)scales)[r])) return bad(NVL_ERR_INVALID, "%s: scales must be finite and positive");
     }
-    for (int64_t i = 0; i < rows * cols; i++)
-        if ((codes[i] & 0x7F) == 0x7F) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: NaN code (0x7f / 0xff)");
-    for (int64_t r = 0; r < rows; r++)
-        if (!(scales[r] > 0.f) || !std::isfinite(scales[r])) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_fp8: scales must be finite and positive");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
     m->w2d_uploaded = true;
     if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) m->expert_uploaded = true;
-    const int64_t Npad = round_up(rows, W_ROW_PAD);
-    w8_alloc(m, t, Npad, cols);
-    uint8_t* raw = (uint8_t*)dmalloc_bytes(rows * cols);
-    NVL_HIP(hipMemcpy(raw, codes, (size_t)(rows * cols), hipMemcpyHostToDevice));
-    NVL_HIP(hipMemcpy(t->scale, scales, (size_t)rows * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(w8_place_kernel, dim3((unsigned)cdiv(rows * cols / 4, 256)), dim3(256), 0, m->stream, (const uint8_t*)raw, rows,
-                       cols, (uint8_t*)t->p);
+    q_alloc(m, t, wf, rows, cols);
+    const int64_t cb = wf_code_bytes(wf, rows * cols), sb = wf_scale_bytes(wf, rows, cols);
+    uint8_t* raw = (uint8_t*)dmalloc_bytes(cb);
+    NVL_HIP(hipMemcpy(raw, codes, (size_t)cb, hipMemcpyHostToDevice));
+    if (wf == WF_MXFP4) {     // the scales are placed with the codes (row-major -> beside the 16-row tiles)
+        uint8_t* raw_s = (uint8_t*)dmalloc_bytes(sb);
+        NVL_HIP(hipMemcpy(raw_s, scales, (size_t)sb, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(w4_place_kernel, dim3((unsigned)cdiv(rows * cols / 8, 256)), dim3(256), 0, m->stream, (const uint8_t*)raw,
+                           (const uint8_t*)raw_s, rows, cols, (uint8_t*)t->p, (uint8_t*)t->qs);
+        NVL_HIP(hipStreamSynchronize(m->stream));
+        dfree(raw_s);
+    } else {                  // one scale per row: the device layout is the caller's
+        NVL_HIP(hipMemcpy(t->qs, scales, (size_t)sb, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(w8_place_kernel, dim3((unsigned)cdiv(rows * cols / 4, 256)), dim3(256), 0, m->stream, (const uint8_t*)raw, rows,
+                           cols, (uint8_t*)t->p);
+    }
     NVL_HIP(hipGetLastError());
     NVL_HIP(hipStreamSynchronize(m->stream));
     dfree(raw);
-    t->rows = rows; t->cols = cols; t->rows_pad = Npad;
-    m->stats.weight_bytes += (double)Npad * cols + (double)Npad * 4;
+    m->stats.weight_bytes += q_bytes(*t);
     return NVL_OK;
     NVL_CATCH(m)
 }
-
-// pre-quantized MXFP4 weight in the ABI packing: codes [rows][cols/2] (even k in the low nibble), e8m0 scales [rows][cols/32]
+extern "C" int nvl_upload_tensor_fp8(nvl_model* m, int kind, int layer, const uint8_t* codes, const float* scales,
+                                     int64_t rows, int64_t cols, int layout) {
+    return upload_prequant(m, WF_FP8, "nvl_upload_tensor_fp8", "nvl_set_weight_dtype", kind, layer, codes, scales, rows, cols, layout);
+}
+// MXFP4: codes [rows][cols/2] (even k in the low nibble), e8m0 scales [rows][cols/32]
 extern "C" int nvl_upload_tensor_mxfp4(nvl_model* m, int kind, int layer, const uint8_t* codes, const uint8_t* scales,
                                        int64_t rows, int64_t cols, int layout) {
-    if (!m || !codes || !scales) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: null argument");
-    if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_upload_tensor_mxfp4: model already finalized");
-    if (!w4_kind(m, kind)) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: not an MXFP4 weight kind of this model (nvl_set_mx_weight_dtype)");
-    if (layout != NVL_LAYOUT_OUT_IN) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
-    DevTensor* t = tensor_slot(m, kind, layer);
-    if (!t) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: bad kind or layer");
-    int64_t SN = full_out(m, kind), SK = full_in(m, kind);
-    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {     // [E * out][in]
-        SN = (int64_t)m->cfg.num_experts * (kind == NVL_T_MOE_IN ? 2 * (int64_t)m->F : m->H);
-        SK = kind == NVL_T_MOE_IN ? m->H : m->F;
-    }
-    if (rows != SN || cols != SK || SK % 32 != 0) {
-        char buf[160];
-        snprintf(buf, sizeof buf, "nvl_upload_tensor_mxfp4: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld], in %% 32 == 0", kind,
-                 (long long)rows, (long long)cols, (long long)SN, (long long)SK);
-        return fail(m, NVL_ERR_INVALID, buf);
-    }
-    for (int64_t i = 0; i < rows * (cols / 32); i++)
-        if (scales[i] < W4_E_MIN + 127 || scales[i] > W4_E_MAX + 127)
-            return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor_mxfp4: a scale byte is outside [7, 252] (0xff is the e8m0 NaN)");
-    NVL_TRY(m)
-    NVL_HIP(hipSetDevice(m->device));
-    m->w2d_uploaded = true;
-    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) m->expert_uploaded = true;
-    const int64_t Npad = round_up(rows, W_ROW_PAD);
-    w4_alloc(m, t, Npad, cols);
-    uint8_t* raw = (uint8_t*)dmalloc_bytes(rows * cols / 2);
-    uint8_t* raw_s = (uint8_t*)dmalloc_bytes(rows * cols / 32);
-    NVL_HIP(hipMemcpy(raw, codes, (size_t)(rows * cols / 2), hipMemcpyHostToDevice));
-    NVL_HIP(hipMemcpy(raw_s, scales, (size_t)(rows * cols / 32), hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(w4_place_kernel, dim3((unsigned)cdiv(rows * cols / 8, 256)), dim3(256), 0, m->stream, (const uint8_t*)raw,
-                       (const uint8_t*)raw_s, rows, cols, (uint8_t*)t->p, t->mxs);
-    NVL_HIP(hipGetLastError());
-    NVL_HIP(hipStreamSynchronize(m->stream));
-    dfree(raw); dfree(raw_s);
-    t->rows = rows; t->cols = cols; t->rows_pad = Npad;
-    m->stats.weight_bytes += (double)Npad * cols / 2 + (double)Npad * cols / 32;
-    return NVL_OK;
-    NVL_CATCH(m)
+    return upload_prequant(m, WF_MXFP4, "nvl_upload_tensor_mxfp4", "nvl_set_mx_weight_dtype", kind, layer, codes, scales, rows, cols, layout);
 }
 
 // splitGPT2QKV (generic_loader.go:674-702): c_attn [H, 3H] is [in,out]; columns split Q|K|V.
@@ -832,6 +744,20 @@ extern "C" int nvl_upload_falcon_qkv(nvl_model* m, int layer, const float* qkv) 
 
 namespace {
 
+// a row permutation in 16-row tiles (the fragment-major layouts move whole tiles): the source tile of every destination
+// tile, -1 for a pad tile
+std::vector<int32_t> gather_tiles(const std::vector<int32_t>& idx) {
+    if (idx.size() % 16) throw std::runtime_error("gather_rows: row count must be a multiple of 16");
+    std::vector<int32_t> use(idx.size() / 16);
+    for (size_t t = 0; t < use.size(); t++) {
+        const int32_t r0 = idx[t * 16];
+        for (int c = 1; c < 16; c++)
+            if ((r0 < 0) != (idx[t * 16 + c] < 0) || (r0 >= 0 && (idx[t * 16 + c] != r0 + c || (r0 & 15))))
+                throw std::runtime_error("gather_rows: permutation does not preserve 16-row tiles");
+        use[t] = r0 < 0 ? -1 : r0 / 16;
+    }
+    return use;
+}
 // dst row r = src row idx[r] (or zeros).  idx must move whole 16-row groups together (it does: the
 // SwiGLU interleave works in blocks of 16), because in the fragment-major bf16 layout the unit that
 // can be relocated is a 16-row n-tile (16*K contiguous elements).
@@ -839,15 +765,7 @@ void gather_rows(nvl_model* m, const void* src, const std::vector<int32_t>& idx,
     std::vector<int32_t> use = idx;
     int64_t unit = K;
     if (!m->f32) {
-        if (idx.size() % 16) throw std::runtime_error("gather_rows: row count must be a multiple of 16");
-        use.resize(idx.size() / 16);
-        for (size_t t = 0; t < use.size(); t++) {
-            const int32_t r0 = idx[t * 16];
-            for (int c = 1; c < 16; c++)
-                if ((r0 < 0) != (idx[t * 16 + c] < 0) || (r0 >= 0 && (idx[t * 16 + c] != r0 + c || (r0 & 15))))
-                    throw std::runtime_error("gather_rows: permutation does not preserve 16-row tiles");
-            use[t] = r0 < 0 ? -1 : r0 / 16;
-        }
+        use = gather_tiles(idx);
         unit = 16 * K;
     }
     int32_t* didx = dmalloc<int32_t>((int64_t)use.size());
@@ -874,48 +792,25 @@ std::vector<int32_t> swiglu_interleave(int64_t F, int64_t src_base) {
     return idx;
 }
 
-// gather_rows for an 8-bit weight: the codes move as 16-row tiles (16*K bytes) and the scales with them; pad rows
-// (idx < 0) get codes 0 and scale 1
-void gather_rows_w8(nvl_model* m, const DevTensor& src, const std::vector<int32_t>& idx, void* dst, float* dst_scale, int64_t K) {
-    if (idx.size() % 16) throw std::runtime_error("gather_rows: row count must be a multiple of 16");
-    std::vector<int32_t> use(idx.size() / 16);
-    for (size_t t = 0; t < use.size(); t++) {
-        const int32_t r0 = idx[t * 16];
-        for (int c = 1; c < 16; c++)
-            if ((r0 < 0) != (idx[t * 16 + c] < 0) || (r0 >= 0 && (idx[t * 16 + c] != r0 + c || (r0 & 15))))
-                throw std::runtime_error("gather_rows: permutation does not preserve 16-row tiles");
-        use[t] = r0 < 0 ? -1 : r0 / 16;
-    }
-    std::vector<float> sc(idx.size()), ssrc((size_t)src.rows_pad);
-    NVL_HIP(hipMemcpy(ssrc.data(), src.scale, ssrc.size() * 4, hipMemcpyDeviceToHost));
-    for (size_t r = 0; r < idx.size(); r++) sc[r] = idx[r] < 0 ? 1.0f : ssrc[(size_t)idx[r]];
+// gather_rows for a quantized weight: the codes move as 16-row tiles and the scales with them.  Pad rows (idx < 0) get
+// codes 0 and, fp8: scale 1 (the per-row scales are permuted on the host); MXFP4: zero scale bytes, a tile's K/2 scale
+// bytes being contiguous like its codes (W~ = 0 either way; pad outputs are never stored)
+void gather_rows_q(nvl_model* m, const DevTensor& src, const std::vector<int32_t>& idx, void* dst, void* dst_qs, int64_t K) {
+    const std::vector<int32_t> use = gather_tiles(idx);
     int32_t* didx = dmalloc<int32_t>((int64_t)use.size());
     NVL_HIP(hipMemcpyAsync(didx, use.data(), use.size() * 4, hipMemcpyHostToDevice, m->stream));
-    NVL_HIP(hipMemcpyAsync(dst_scale, sc.data(), sc.size() * 4, hipMemcpyHostToDevice, m->stream));
-    hipLaunchKernelGGL((gather_rows_kernel<uint8_t>), dim3((unsigned)use.size()), dim3(256), 0, m->stream,
-                       (const uint8_t*)src.p, didx, (uint8_t*)dst, 16 * K);
-    NVL_HIP(hipGetLastError());
-    NVL_HIP(hipStreamSynchronize(m->stream));
-    dfree(didx);
-}
-// gather_rows for an MXFP4 weight: a 16-row tile is 8*K code bytes and K/2 scale bytes, both contiguous; pad tiles
-// (idx < 0) get zero bytes in both (W~ = 0; their outputs are never stored)
-void gather_rows_w4(nvl_model* m, const DevTensor& src, const std::vector<int32_t>& idx, void* dst, uint8_t* dst_scales, int64_t K) {
-    if (idx.size() % 16) throw std::runtime_error("gather_rows: row count must be a multiple of 16");
-    std::vector<int32_t> use(idx.size() / 16);
-    for (size_t t = 0; t < use.size(); t++) {
-        const int32_t r0 = idx[t * 16];
-        for (int c = 1; c < 16; c++)
-            if ((r0 < 0) != (idx[t * 16 + c] < 0) || (r0 >= 0 && (idx[t * 16 + c] != r0 + c || (r0 & 15))))
-                throw std::runtime_error("gather_rows: permutation does not preserve 16-row tiles");
-        use[t] = r0 < 0 ? -1 : r0 / 16;
+    std::vector<float> sc, ssrc;     // (fp8; alive until the synchronize below)
+    if (src.wf == WF_MXFP4) {
+        hipLaunchKernelGGL((gather_rows_kernel<uint8_t>), dim3((unsigned)use.size()), dim3(256), 0, m->stream,
+                           (const uint8_t*)src.qs, didx, (uint8_t*)dst_qs, wf_scale_bytes(src.wf, 16, K));
+    } else {
+        ssrc.resize((size_t)src.rows_pad);
+        NVL_HIP(hipMemcpy(ssrc.data(), src.qs, ssrc.size() * 4, hipMemcpyDeviceToHost));
+        for (int32_t i : idx) sc.push_back(i < 0 ? 1.0f : ssrc[(size_t)i]);
+        NVL_HIP(hipMemcpyAsync(dst_qs, sc.data(), sc.size() * 4, hipMemcpyHostToDevice, m->stream));
     }
-    int32_t* didx = dmalloc<int32_t>((int64_t)use.size());
-    NVL_HIP(hipMemcpyAsync(didx, use.data(), use.size() * 4, hipMemcpyHostToDevice, m->stream));
     hipLaunchKernelGGL((gather_rows_kernel<uint8_t>), dim3((unsigned)use.size()), dim3(256), 0, m->stream,
-                       (const uint8_t*)src.p, didx, (uint8_t*)dst, 8 * K);
-    hipLaunchKernelGGL((gather_rows_kernel<uint8_t>), dim3((unsigned)use.size()), dim3(256), 0, m->stream,
-                       (const uint8_t*)src.mxs, didx, dst_scales, K / 2);
+                       (const uint8_t*)src.p, didx, (uint8_t*)dst, wf_code_bytes(src.wf, 16 * K));
     NVL_HIP(hipGetLastError());
     NVL_HIP(hipStreamSynchronize(m->stream));
     dfree(didx);
@@ -927,28 +822,22 @@ void fuse_w1(nvl_model* m, LayerW& l, bool swiglu) {
         auto idx = swiglu_interleave(m->F, 0);
         const int64_t np = round_up(l.n1, W_ROW_PAD);
         idx.resize((size_t)np, -1);
-        if (l.t[NVL_T_W1].mxs) {
-            l.w1 = dmalloc_bytes(np * H / 2);
-            l.e1 = (uint8_t*)dmalloc_bytes(np * H / 32);
-            gather_rows_w4(m, l.t[NVL_T_W1], idx, l.w1, l.e1, H);
-            dfree(l.t[NVL_T_W1].mxs); l.t[NVL_T_W1].mxs = nullptr;
-        } else if (l.t[NVL_T_W1].scale) {
-            l.w1 = dmalloc_bytes(np * H);
-            l.s1 = dmalloc<float>(np);
-            gather_rows_w8(m, l.t[NVL_T_W1], idx, l.w1, l.s1, H);
-            dfree(l.t[NVL_T_W1].scale); l.t[NVL_T_W1].scale = nullptr;
+        DevTensor& t = l.t[NVL_T_W1];
+        if (t.qs) {
+            l.w1 = dmalloc_bytes(wf_code_bytes(t.wf, np * H));
+            l.qs1 = dmalloc_bytes(wf_scale_bytes(t.wf, np, H));
+            gather_rows_q(m, t, idx, l.w1, l.qs1, H);
+            dfree(t.qs); t.qs = nullptr;
         } else {
             l.w1 = dmalloc_bytes(np * H * (int64_t)m->wsize);
-            gather_rows(m, l.t[NVL_T_W1].p, idx, l.w1, H);
+            gather_rows(m, t.p, idx, l.w1, H);
         }
-        dfree(l.t[NVL_T_W1].p); l.t[NVL_T_W1].p = nullptr;
+        dfree(t.p); t.p = nullptr;
     } else {
         l.w1 = l.t[NVL_T_W1].p; l.t[NVL_T_W1].p = nullptr;
-        l.s1 = l.t[NVL_T_W1].scale; l.t[NVL_T_W1].scale = nullptr;
-        l.e1 = l.t[NVL_T_W1].mxs; l.t[NVL_T_W1].mxs = nullptr;
+        l.qs1 = l.t[NVL_T_W1].qs; l.t[NVL_T_W1].qs = nullptr;
     }
 }
-
 
 }  // namespace
 
@@ -978,10 +867,10 @@ extern "C" int nvl_set_weight_dtype(nvl_model* m, int dtype) {
     if (dtype == NVL_W_FP8_E4M3 && m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights need bf16 precision");
     if (dtype == NVL_W_FP8_E4M3 && (m->tp > 1 || m->tp_force))
         return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights are not available with tensor parallelism");
-    if (dtype == NVL_W_FP8_E4M3 && m->mx)
+    if (dtype == NVL_W_FP8_E4M3 && m->wf == WF_MXFP4)
         return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: the model stores MXFP4 weights (nvl_set_mx_weight_dtype)");
-    m->w8 = dtype == NVL_W_FP8_E4M3;
-    if (!m->w8) m->a8 = m->e8 = false;     // (8-bit activations and experts need 8-bit weights)
+    if (dtype == NVL_W_FP8_E4M3) m->wf = WF_FP8;
+    else if (m->wf == WF_FP8) { m->wf = m->ef = WF_BF16; m->a8 = false; }     // (8-bit activations and experts need 8-bit weights)
     return NVL_OK;
 }
 
@@ -993,11 +882,12 @@ extern "C" int nvl_set_mx_weight_dtype(nvl_model* m, int dtype) {
     if (dtype == NVL_MX_FP4_E2M1 && m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: MXFP4 weights need bf16 precision");
     if (dtype == NVL_MX_FP4_E2M1 && (m->tp > 1 || m->tp_force))
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: MXFP4 weights are not available with tensor parallelism");
-    if (dtype == NVL_MX_FP4_E2M1 && m->w8)
+    if (dtype == NVL_MX_FP4_E2M1 && m->wf == WF_FP8)
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores 8-bit weights (nvl_set_weight_dtype)");
-    if (dtype == NVL_MX_NONE && m->e4)
+    if (dtype == NVL_MX_NONE && m->ef == WF_MXFP4)
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores MXFP4 experts (nvl_set_mx_expert_dtype), which need MXFP4 weights");
-    m->mx = dtype == NVL_MX_FP4_E2M1;
+    if (dtype == NVL_MX_FP4_E2M1) m->wf = WF_MXFP4;
+    else if (m->wf == WF_MXFP4) m->wf = WF_BF16;
     return NVL_OK;
 }
 
@@ -1009,9 +899,10 @@ extern "C" int nvl_set_mx_expert_dtype(nvl_model* m, int dtype) {
     if (dtype == NVL_MXE_FP4_E2M1) {
         if (!m->cfg.use_moe || m->cfg.num_experts <= 0) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: the model has no MoE layers");
         if (m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: MXFP4 experts need bf16 precision");
-        if (!m->mx) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: MXFP4 experts need MXFP4 projection weights (nvl_set_mx_weight_dtype first)");
+        if (m->wf != WF_MXFP4) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: MXFP4 experts need MXFP4 projection weights (nvl_set_mx_weight_dtype first)");
     }
-    m->e4 = dtype == NVL_MXE_FP4_E2M1;
+    if (dtype == NVL_MXE_FP4_E2M1) m->ef = WF_MXFP4;
+    else if (m->ef == WF_MXFP4) m->ef = WF_BF16;
     return NVL_OK;
 }
 
@@ -1023,9 +914,10 @@ extern "C" int nvl_set_expert_dtype(nvl_model* m, int dtype) {
     if (dtype == NVL_EXPERT_FP8_E4M3) {
         if (!m->cfg.use_moe || m->cfg.num_experts <= 0) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: the model has no MoE layers");
         if (m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: 8-bit experts need bf16 precision");
-        if (!m->w8) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: 8-bit experts need 8-bit projection weights (nvl_set_weight_dtype first)");
+        if (m->wf != WF_FP8) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: 8-bit experts need 8-bit projection weights (nvl_set_weight_dtype first)");
     }
-    m->e8 = dtype == NVL_EXPERT_FP8_E4M3;
+    if (dtype == NVL_EXPERT_FP8_E4M3) m->ef = WF_FP8;
+    else if (m->ef == WF_FP8) m->ef = WF_BF16;
     return NVL_OK;
 }
 
@@ -1033,7 +925,7 @@ extern "C" int nvl_set_act_dtype(nvl_model* m, int dtype) {
     if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_act_dtype: no model");
     if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_set_act_dtype: call it before nvl_finalize");
     if (dtype != NVL_ACT_AUTO && dtype != NVL_ACT_FP8_E4M3) return fail(m, NVL_ERR_INVALID, "nvl_set_act_dtype: unknown activation dtype");
-    if (dtype == NVL_ACT_FP8_E4M3 && !m->w8)
+    if (dtype == NVL_ACT_FP8_E4M3 && m->wf != WF_FP8)
         return fail(m, NVL_ERR_INVALID, "nvl_set_act_dtype: 8-bit activations need 8-bit weights (nvl_set_weight_dtype first)");
     m->a8 = dtype == NVL_ACT_FP8_E4M3;
     return NVL_OK;
@@ -1071,43 +963,26 @@ extern "C" int nvl_finalize(nvl_model* m) {
         // ---- fused QKV [n_qkv_pad][H]: rows Q | K | V (canonical rows are contiguous: plain copies)
         const int64_t nq = (int64_t)m->nH * hd, nkv = (int64_t)m->nKV * hd;
         const int64_t npad = round_up(m->n_qkv, W_ROW_PAD);
-        const bool q8 = l.t[NVL_T_WQ].scale != nullptr;    // 8-bit weights: codes move like bf16 rows, scales beside them
-        const bool q4 = l.t[NVL_T_WQ].mxs != nullptr;      // MXFP4 weights: half a byte per element, H/32 scale bytes per row
-        const size_t we = q8 ? 1 : m->wsize;
-        const size_t rowb = q4 ? (size_t)H / 2 : (size_t)H * we;
+        // quantized weights: the codes move like bf16 rows and the scales beside them (row counts are multiples of 16: whole
+        // tiles of both); cat copies the parts Q | K | V (or Q | KV) of `bytes`-per-row data into dst
+        const int wf = l.t[NVL_T_WQ].wf;
+        const size_t rowb = wf != WF_BF16 ? (size_t)wf_code_bytes(wf, H) : (size_t)H * m->wsize;
+        auto cat = [&](void* dst, size_t bytes, void* DevTensor::*part) {
+            char* d = (char*)dst;
+            NVL_HIP(hipMemcpyAsync(d, l.t[NVL_T_WQ].*part, nq * bytes, hipMemcpyDeviceToDevice, m->stream));
+            if (mqa) {
+                NVL_HIP(hipMemcpyAsync(d + nq * bytes, l.t[NVL_T_WKV].*part, 2 * hd * bytes, hipMemcpyDeviceToDevice, m->stream));
+            } else {
+                NVL_HIP(hipMemcpyAsync(d + nq * bytes, l.t[NVL_T_WK].*part, nkv * bytes, hipMemcpyDeviceToDevice, m->stream));
+                NVL_HIP(hipMemcpyAsync(d + (nq + nkv) * bytes, l.t[NVL_T_WV].*part, nkv * bytes, hipMemcpyDeviceToDevice, m->stream));
+            }
+        };
         l.w_qkv = dmalloc_bytes(npad * (int64_t)rowb);
         NVL_HIP(hipMemsetAsync(l.w_qkv, 0, (size_t)npad * rowb, m->stream));
-        char* dst = (char*)l.w_qkv;
-        if (q4) {     // (row counts are multiples of 16: whole tiles, as for the codes)
-            const size_t rs = (size_t)H / 32;
-            l.e_qkv = (uint8_t*)dmalloc_bytes(npad * (int64_t)rs);
-            NVL_HIP(hipMemsetAsync(l.e_qkv, 127, (size_t)npad * rs, m->stream));
-            NVL_HIP(hipMemcpyAsync(l.e_qkv, l.t[NVL_T_WQ].mxs, nq * rs, hipMemcpyDeviceToDevice, m->stream));
-            if (mqa) {
-                NVL_HIP(hipMemcpyAsync(l.e_qkv + nq * rs, l.t[NVL_T_WKV].mxs, 2 * hd * rs, hipMemcpyDeviceToDevice, m->stream));
-            } else {
-                NVL_HIP(hipMemcpyAsync(l.e_qkv + nq * rs, l.t[NVL_T_WK].mxs, nkv * rs, hipMemcpyDeviceToDevice, m->stream));
-                NVL_HIP(hipMemcpyAsync(l.e_qkv + (nq + nkv) * rs, l.t[NVL_T_WV].mxs, nkv * rs, hipMemcpyDeviceToDevice, m->stream));
-            }
-        }
-        if (q8) {
-            l.s_qkv = dmalloc<float>(npad);
-            const std::vector<float> ones((size_t)npad, 1.0f);
-            NVL_HIP(hipMemcpy(l.s_qkv, ones.data(), (size_t)npad * 4, hipMemcpyHostToDevice));   // (synchronous: pageable, local)
-            NVL_HIP(hipMemcpyAsync(l.s_qkv, l.t[NVL_T_WQ].scale, nq * 4, hipMemcpyDeviceToDevice, m->stream));
-            if (mqa) {
-                NVL_HIP(hipMemcpyAsync(l.s_qkv + nq, l.t[NVL_T_WKV].scale, 2 * hd * 4, hipMemcpyDeviceToDevice, m->stream));
-            } else {
-                NVL_HIP(hipMemcpyAsync(l.s_qkv + nq, l.t[NVL_T_WK].scale, nkv * 4, hipMemcpyDeviceToDevice, m->stream));
-                NVL_HIP(hipMemcpyAsync(l.s_qkv + nq + nkv, l.t[NVL_T_WV].scale, nkv * 4, hipMemcpyDeviceToDevice, m->stream));
-            }
-        }
-        NVL_HIP(hipMemcpyAsync(dst, l.t[NVL_T_WQ].p, nq * rowb, hipMemcpyDeviceToDevice, m->stream));
-        if (mqa) {
-            NVL_HIP(hipMemcpyAsync(dst + nq * rowb, l.t[NVL_T_WKV].p, 2 * hd * rowb, hipMemcpyDeviceToDevice, m->stream));
-        } else {
-            NVL_HIP(hipMemcpyAsync(dst + nq * rowb, l.t[NVL_T_WK].p, nkv * rowb, hipMemcpyDeviceToDevice, m->stream));
-            NVL_HIP(hipMemcpyAsync(dst + (nq + nkv) * rowb, l.t[NVL_T_WV].p, nkv * rowb, hipMemcpyDeviceToDevice, m->stream));
+        cat(l.w_qkv, rowb, &DevTensor::p);
+        if (wf != WF_BF16) {
+            l.qs_qkv = q_alloc_scales(m, wf, npad, H);
+            cat(l.qs_qkv, (size_t)wf_scale_bytes(wf, 1, H), &DevTensor::qs);
         }
         l.n_qkv = m->n_qkv;
         if (l.t[NVL_T_BQ].present() || l.t[NVL_T_BK].present() || l.t[NVL_T_BV].present()) {
@@ -1118,8 +993,7 @@ extern "C" int nvl_finalize(nvl_model* m) {
             if (l.t[NVL_T_BV].present()) NVL_HIP(hipMemcpyAsync(l.b_qkv + nq + nkv, l.t[NVL_T_BV].p, nkv * 4, hipMemcpyDeviceToDevice, m->stream));
         }
         NVL_HIP(hipStreamSynchronize(m->stream));
-        for (int k : {NVL_T_WQ, NVL_T_WK, NVL_T_WV, NVL_T_WKV}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].scale); l.t[k].scale = nullptr;
-                                                                  dfree(l.t[k].mxs); l.t[k].mxs = nullptr; }
+        for (int k : {NVL_T_WQ, NVL_T_WK, NVL_T_WV, NVL_T_WKV}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].qs); l.t[k].qs = nullptr; }
 
         // ---- FFN / MoE
         if (c.use_moe) {
@@ -1133,49 +1007,34 @@ extern "C" int nvl_finalize(nvl_model* m) {
                     idx.insert(idx.end(), one.begin(), one.end());
                 }
                 const bool dense_form = I % 32 == 0 && H % 16 == 0 && E <= 64 && E / moe_down_slices((int)E) <= 16;
-                if (l.t[NVL_T_MOE_IN].scale) {     // 8-bit experts (nvl_set_expert_dtype): codes + scales follow the interleave
+                if (l.t[NVL_T_MOE_IN].qs) {     // quantized experts: codes + scales follow the interleave
+                    const int wf = l.t[NVL_T_MOE_IN].wf;
                     const int64_t np = round_up(E * 2 * I, W_ROW_PAD), hp = round_up(H, W_ROW_PAD);
                     idx.resize((size_t)np, -1);
-                    l.moe_in = dmalloc_bytes(np * H);
-                    l.s_moe_in = dmalloc<float>(np);
-                    gather_rows_w8(m, l.t[NVL_T_MOE_IN], idx, l.moe_in, l.s_moe_in, H);
-                    // down: codes [H_pad][E*I] (the decode form's layout; the tile path dequantizes from it), scales [E][H_pad]
+                    l.moe_in = dmalloc_bytes(wf_code_bytes(wf, np * H));
+                    l.qs_moe_in = dmalloc_bytes(wf_scale_bytes(wf, np, H));
+                    gather_rows_q(m, l.t[NVL_T_MOE_IN], idx, l.moe_in, l.qs_moe_in, H);
+                    // down: codes over K = E*I, [H_pad][E*I] (the decode form's layout; the tile path dequantizes from it)
                     const DevTensor& d = l.t[NVL_T_MOE_OUT];
-                    l.moe_out8 = dmalloc_bytes(hp * E * I);
-                    l.s_moe_out = dmalloc<float>(E * hp);
-                    NVL_HIP(hipMemsetAsync(l.moe_out8, 0, (size_t)(hp * E * I), m->stream));
-                    hipLaunchKernelGGL(moe_cat_down_w8_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream,
-                                       (const uint8_t*)d.p, (uint8_t*)l.moe_out8, (int)H, (int)I, (int)E);
-                    NVL_HIP(hipGetLastError());
-                    std::vector<float> sd((size_t)d.rows_pad), so((size_t)(E * hp), 1.0f);
-                    NVL_HIP(hipMemcpy(sd.data(), d.scale, sd.size() * 4, hipMemcpyDeviceToHost));
-                    for (int64_t e = 0; e < E; e++)
-                        for (int64_t r = 0; r < H; r++) so[(size_t)(e * hp + r)] = sd[(size_t)(e * H + r)];
-                    NVL_HIP(hipMemcpy(l.s_moe_out, so.data(), so.size() * 4, hipMemcpyHostToDevice));
-                    NVL_HIP(hipStreamSynchronize(m->stream));
-                    if (dense_form) l.moe_out_cat = l.moe_out8;
-                    for (int k : {NVL_T_MOE_IN, NVL_T_MOE_OUT}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].scale); l.t[k].scale = nullptr; }
-                    continue;
-                }
-                if (l.t[NVL_T_MOE_IN].mxs) {     // MXFP4 experts (nvl_set_mx_expert_dtype): codes + block scales follow the interleave
-                    need(l.t[NVL_T_MOE_OUT].mxs != nullptr, "MXFP4 expert tensors");
-                    const int64_t np = round_up(E * 2 * I, W_ROW_PAD), hp = round_up(H, W_ROW_PAD);
-                    idx.resize((size_t)np, -1);
-                    l.moe_in = dmalloc_bytes(np * H / 2);
-                    l.e_moe_in = (uint8_t*)dmalloc_bytes(np * H / 32);
-                    gather_rows_w4(m, l.t[NVL_T_MOE_IN], idx, l.moe_in, l.e_moe_in, H);
-                    // down: codes and block scales over K = E*I (the decode form's layout; the tile path dequantizes from it)
-                    const DevTensor& d = l.t[NVL_T_MOE_OUT];
-                    l.moe_out4 = dmalloc_bytes(hp * E * I / 2);
-                    l.e_moe_out = (uint8_t*)dmalloc_bytes(hp * E * I / 32);
-                    NVL_HIP(hipMemsetAsync(l.moe_out4, 0, (size_t)(hp * E * I / 2), m->stream));
-                    NVL_HIP(hipMemsetAsync(l.e_moe_out, 127, (size_t)(hp * E * I / 32), m->stream));
-                    hipLaunchKernelGGL(moe_cat_down_w4_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream,
-                                       (const uint8_t*)d.p, (const uint8_t*)d.mxs, (uint8_t*)l.moe_out4, l.e_moe_out, (int)H, (int)I, (int)E);
+                    l.moe_out_q = dmalloc_bytes(wf_code_bytes(wf, hp * E * I));
+                    NVL_HIP(hipMemsetAsync(l.moe_out_q, 0, (size_t)wf_code_bytes(wf, hp * E * I), m->stream));
+                    if (wf == WF_MXFP4) {     // block scales over the same K, moved with the code tiles
+                        l.qs_moe_out = q_alloc_scales(m, wf, hp, E * I);
+                        hipLaunchKernelGGL(moe_cat_down_w4_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream, (const uint8_t*)d.p,
+                                           (const uint8_t*)d.qs, (uint8_t*)l.moe_out_q, (uint8_t*)l.qs_moe_out, (int)H, (int)I, (int)E);
+                    } else {                  // row scales [E][H_pad]: one row per expert, through the host
+                        l.qs_moe_out = q_alloc_scales(m, wf, E * hp, I);
+                        hipLaunchKernelGGL(moe_cat_down_w8_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream,
+                                           (const uint8_t*)d.p, (uint8_t*)l.moe_out_q, (int)H, (int)I, (int)E);
+                        std::vector<float> sd((size_t)d.rows_pad);
+                        NVL_HIP(hipMemcpy(sd.data(), d.qs, sd.size() * 4, hipMemcpyDeviceToHost));
+                        for (int64_t e = 0; e < E; e++)
+                            NVL_HIP(hipMemcpy((float*)l.qs_moe_out + e * hp, &sd[(size_t)(e * H)], (size_t)H * 4, hipMemcpyHostToDevice));
+                    }
                     NVL_HIP(hipGetLastError());
                     NVL_HIP(hipStreamSynchronize(m->stream));
-                    if (dense_form) l.moe_out_cat = l.moe_out4;
-                    for (int k : {NVL_T_MOE_IN, NVL_T_MOE_OUT}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].mxs); l.t[k].mxs = nullptr; }
+                    if (dense_form) l.moe_out_cat = l.moe_out_q;
+                    for (int k : {NVL_T_MOE_IN, NVL_T_MOE_OUT}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].qs); l.t[k].qs = nullptr; }
                     continue;
                 }
                 l.moe_in = dmalloc_bytes(round_up(E * 2 * I, W_ROW_PAD) * H * (int64_t)m->wsize);   // (+ zero pad rows: the decode kernels read whole tiles)
@@ -1203,71 +1062,42 @@ extern "C" int nvl_finalize(nvl_model* m) {
         }
     }
     // ---- LM head: tied (or absent) => the token embedding itself, already [Vpad][H] K-contiguous
-    if (!c.tied_embedding && m->g[NVL_T_LM_HEAD].present()) { m->lm_head = m->g[NVL_T_LM_HEAD].p; m->lm_head_scale = m->g[NVL_T_LM_HEAD].scale; }
-    else { m->lm_head = m->g[NVL_T_TOK_EMB].p; m->lm_head_scale = m->g[NVL_T_TOK_EMB].scale; }   // generic_loader.go:255-259
-    if (m->mx) {   // the MXFP4 weights by code pointer (gemm() dispatch) and the dequantize scratch of the tile path
+    const DevTensor& head = (!c.tied_embedding && m->g[NVL_T_LM_HEAD].present()) ? m->g[NVL_T_LM_HEAD] : m->g[NVL_T_TOK_EMB];   // generic_loader.go:255-259
+    m->lm_head = head.p;
+    if (m->wf != WF_BF16) {   // the quantized weights by code pointer (gemm() dispatch) and the dequantize scratch of the tile path
         int64_t big = 0;
-        auto reg = [&](const void* p, const uint8_t* s, int64_t rows, int64_t K) {
-            if (!p || !s) return;
-            m->w4_map[p] = nvl_model::W4Ref{s, round_up(rows, W_ROW_PAD)};
+        auto reg = [&](const void* p, const void* qs, int64_t rows, int64_t K) {
+            if (!p || !qs) return;
+            m->qmap[p] = nvl_model::QRef{m->wf, qs, round_up(rows, W_ROW_PAD)};
             big = std::max(big, round_up(rows, W_ROW_PAD) * K);
         };
         for (auto& l : m->layers) {
-            reg(l.w_qkv, l.e_qkv, l.n_qkv, H); reg(l.w1, l.e1, l.n1, H);
-            reg(l.t[NVL_T_WO].p, l.t[NVL_T_WO].mxs, H, l.t[NVL_T_WO].cols); reg(l.t[NVL_T_W2].p, l.t[NVL_T_W2].mxs, H, l.t[NVL_T_W2].cols);
+            reg(l.w_qkv, l.qs_qkv, l.n_qkv, H); reg(l.w1, l.qs1, l.n1, H);
+            reg(l.t[NVL_T_WO].p, l.t[NVL_T_WO].qs, H, l.t[NVL_T_WO].cols); reg(l.t[NVL_T_W2].p, l.t[NVL_T_W2].qs, H, l.t[NVL_T_W2].cols);
         }
-        m->w8_scratch_elems = big;
-        if (big) m->w8_scratch = dmalloc<bf16_t>(big);
-        if (m->e4) {   // MXFP4 experts: the codes by pointer (decode dispatch), and the scratch of one layer's W~ (up, then down)
+        if (head.qs) {   // (fp8; at least one row tile of the LM head: it runs in chunks)
+            m->qmap[head.p] = nvl_model::QRef{m->wf, head.qs, round_up(m->V, W_ROW_PAD)};
+            big = std::max(big, W_ROW_PAD * H);
+        }
+        m->wq_scratch_elems = big;
+        if (big) m->wq_scratch = dmalloc<bf16_t>(big);
+        if (m->ef != WF_BF16) {   // quantized experts: the codes by pointer (decode dispatch), and the scratch of one layer's W~ (up, then down)
             const int64_t E = c.num_experts, I = m->F, hp = round_up(H, W_ROW_PAD);
             for (auto& l : m->layers) {
-                if (!l.e_moe_in) continue;
-                m->w4_map[l.moe_in] = nvl_model::W4Ref{l.e_moe_in, round_up(E * 2 * I, W_ROW_PAD)};
-                if (l.moe_out_cat) m->w4_map[l.moe_out_cat] = nvl_model::W4Ref{l.e_moe_out, hp};
+                if (!l.qs_moe_in) continue;
+                m->qmap[l.moe_in] = nvl_model::QRef{m->ef, l.qs_moe_in, round_up(E * 2 * I, W_ROW_PAD)};
+                if (l.moe_out_cat) m->qmap[l.moe_out_cat] = nvl_model::QRef{m->ef, l.qs_moe_out, hp};
             }
             // (down: the grouped GEMMs read whole 256-row tiles of the last expert past its H rows)
-            m->e8_scratch_elems = std::max(round_up(E * 2 * I, W_ROW_PAD) * H, (E * H + 2 * W_ROW_PAD) * I);
-            m->e8_scratch = dmalloc<bf16_t>(m->e8_scratch_elems);
-            NVL_HIP(hipMemsetAsync(m->e8_scratch, 0, (size_t)m->e8_scratch_elems * 2, m->stream));
-        }
-    }
-    if (m->w8) {   // the 8-bit weights by code pointer (gemm() dispatch) and the dequantize scratch of the tile path
-        int64_t big = 0;
-        auto reg = [&](const void* p, const float* s, int64_t rows) {
-            if (!p || !s) return;
-            m->w8_map[p] = nvl_model::W8Ref{s, round_up(rows, W_ROW_PAD)};
-        };
-        for (auto& l : m->layers) {
-            reg(l.w_qkv, l.s_qkv, l.n_qkv); reg(l.w1, l.s1, l.n1);
-            reg(l.t[NVL_T_WO].p, l.t[NVL_T_WO].scale, H); reg(l.t[NVL_T_W2].p, l.t[NVL_T_W2].scale, H);
-            if (l.s_qkv) big = std::max(big, round_up(l.n_qkv, W_ROW_PAD) * H);
-            if (l.s1) big = std::max(big, round_up(l.n1, W_ROW_PAD) * H);
-            if (l.t[NVL_T_WO].scale) big = std::max(big, l.t[NVL_T_WO].rows_pad * l.t[NVL_T_WO].cols);
-            if (l.t[NVL_T_W2].scale) big = std::max(big, l.t[NVL_T_W2].rows_pad * l.t[NVL_T_W2].cols);
-        }
-        if (m->lm_head_scale) {
-            reg(m->lm_head, m->lm_head_scale, m->V);
-            big = std::max(big, W_ROW_PAD * H);      // (at least one row tile of the LM head: it runs in chunks)
-        }
-        m->w8_scratch_elems = big;
-        if (big) m->w8_scratch = dmalloc<bf16_t>(big);
-        if (m->e8) {   // 8-bit experts: the codes by pointer (decode dispatch), and the scratch of one layer's W~ (up, then down)
-            const int64_t E = c.num_experts, I = m->F, hp = round_up(H, W_ROW_PAD);
-            for (auto& l : m->layers) {
-                if (!l.s_moe_in) continue;
-                m->w8_map[l.moe_in] = nvl_model::W8Ref{l.s_moe_in, round_up(E * 2 * I, W_ROW_PAD)};
-                if (l.moe_out_cat) m->w8_map[l.moe_out_cat] = nvl_model::W8Ref{l.s_moe_out, hp};
-            }
-            // (down: the grouped GEMMs read whole 256-row tiles of the last expert past its H rows)
-            m->e8_scratch_elems = std::max(round_up(E * 2 * I, W_ROW_PAD) * H, (E * H + 2 * W_ROW_PAD) * I);
-            m->e8_scratch = dmalloc<bf16_t>(m->e8_scratch_elems);
-            NVL_HIP(hipMemsetAsync(m->e8_scratch, 0, (size_t)m->e8_scratch_elems * 2, m->stream));
+            m->eq_scratch_elems = std::max(round_up(E * 2 * I, W_ROW_PAD) * H, (E * H + 2 * W_ROW_PAD) * I);
+            m->eq_scratch = dmalloc<bf16_t>(m->eq_scratch_elems);
+            NVL_HIP(hipMemsetAsync(m->eq_scratch, 0, (size_t)m->eq_scratch_elems * 2, m->stream));
         }
         if (m->a8) {   // the activation codes + row scales of the W8A8 tile step: every row of a batch, the widest K
             int64_t kmax = H;
             for (auto& l : m->layers) {
-                if (l.t[NVL_T_WO].scale) kmax = std::max(kmax, l.t[NVL_T_WO].cols);
-                if (l.t[NVL_T_W2].scale) kmax = std::max(kmax, l.t[NVL_T_W2].cols);
+                if (l.t[NVL_T_WO].qs) kmax = std::max(kmax, l.t[NVL_T_WO].cols);
+                if (l.t[NVL_T_W2].qs) kmax = std::max(kmax, l.t[NVL_T_W2].cols);
             }
             m->a8_rows = round_up(m->opts.max_batch_tokens, 16);
             m->a8_k = kmax;
@@ -2020,7 +1850,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
     const int pairs = M * k;
     // algorithmic weight bytes of the expert GEMMs: the experts a batch of `pairs` (token, rank) pairs can touch, once
     const double e_touch = (double)std::min(E, pairs);
-    const double eb = m->e4 ? 0.5 : m->e8 ? 1.0 : (double)m->wsize;     // bytes per expert weight (quantized experts: codes; scales not counted)
+    const double eb = m->ef != WF_BF16 ? wf_code_bytes(m->ef, 2) / 2.0 : (double)m->wsize;     // bytes per expert weight (quantized experts: codes; scales not counted)
     m->site = KS_MOE_ROUTER;
     const bool dense = moe_dense_ok(m, l, M) && m->pending_slices == 0;
     // decode: router logits, softmax, top-k and the dense gate matrix in one launch (gemm.h moe_router_gate_kernel)
@@ -2055,7 +1885,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
         const int nks = (E * I) >> 5, spe = I >> 5;
         // (8-bit experts: no producer form — a wave's live blocks cross experts, the scale would change with the block;
         //  MXFP4 experts: no instance of it either — key 33 is off by default and was measured slower)
-        if (next_norm_w && g_moe_defer_down && !m->e8 && !m->e4 && nks % 64 == 0 && spe % 4 == 0 && nks / 16 <= 4 * spe && nks / 64 <= 32) {
+        if (next_norm_w && g_moe_defer_down && m->ef == WF_BF16 && nks % 64 == 0 && spe % 4 == 0 && nks / 16 <= 4 * spe && nks / 64 <= 32) {
             // (the launcher's conditions: 16 waves, whole blocks of 4 k-steps inside one expert, <= 4 experts per wave)
             GemmArgs d = mk(m->moe_hall, E * I, l.moe_out_cat, m->x, H, nullptr, m->resid_alpha, M, H, E * I);
             d.moe_gate = m->moe_gate; d.moe_E = E; d.moe_I = I;
@@ -2132,36 +1962,30 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
             a.A = m->moe_xg; a.a_rows = nullptr;
         }
         a.w_expert_stride = (int64_t)2 * I * H; a.grp_bm = pp ? 512 : BM; a.grp_deep = small && g_moe_deep;
-        // 8-bit experts: the grouped GEMMs run on this layer's W~, dequantized into one scratch buffer — up first, then down
-        // over it, in stream order (the down dequantize starts after the up GEMM has read the scratch)
+        // quantized experts: the grouped GEMMs run on this layer's W~, dequantized into one scratch buffer — up first, then down
+        // over it, in stream order (the down dequantize starts after the up GEMM has read the scratch).  Algorithmic bytes
+        // of a dequantize, per element: the code + its share of the scales in, 2 bytes out (3.0 for fp8, 2.53 for MXFP4)
         const void* w_down = l.t[NVL_T_MOE_OUT].p;
-        if (m->e8) {
-            KScope ks(m, KC_OTHER, 0, KS_MOE_UP, (double)round_up(E * 2 * I, W_ROW_PAD) * H * 3.0);
-            w8_dequant_rows(m->stream, l.moe_in, l.s_moe_in, H, 0, round_up(E * 2 * I, W_ROW_PAD), m->e8_scratch);
+        const double dq_bytes = m->ef == WF_MXFP4 ? 2.53 : 3.0;
+        if (m->ef != WF_BF16) {
+            KScope ks(m, KC_OTHER, 0, KS_MOE_UP, (double)round_up(E * 2 * I, W_ROW_PAD) * H * dq_bytes);
+            wf_dequant_rows(m->stream, m->ef, l.moe_in, l.qs_moe_in, H, 0, round_up(E * 2 * I, W_ROW_PAD), m->eq_scratch);
             NVL_HIP(hipGetLastError());
-            a.W = m->e8_scratch;
-        } else if (m->e4) {     // MXFP4 experts: the same two steps with the MX dequantize kernels
-            KScope ks(m, KC_OTHER, 0, KS_MOE_UP, (double)round_up(E * 2 * I, W_ROW_PAD) * H * 2.53);
-            w4_dequant_rows(m->stream, l.moe_in, l.e_moe_in, H, round_up(E * 2 * I, W_ROW_PAD), m->e8_scratch);
-            NVL_HIP(hipGetLastError());
-            a.W = m->e8_scratch;
+            a.W = m->eq_scratch;
         }
         m->site = KS_MOE_UP; m->site_bytes = (e_touch * 2 * I * H + (double)pairs * H + (double)pairs * I) * (double)m->wsize;
         gemm(m, EPI_SWIGLU, false, a, 2.0 * pairs * 2 * I * H);
-        if (m->e8) {
-            KScope ks(m, KC_OTHER, 0, KS_MOE_DOWN, (double)E * H * I * 3.0);
+        if (m->ef != WF_BF16) {
+            KScope ks(m, KC_OTHER, 0, KS_MOE_DOWN, (double)E * H * I * dq_bytes);
             const int64_t n8 = (int64_t)E * H * I / 8;
-            hipLaunchKernelGGL(e8_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out8,
-                               l.s_moe_out, H, I, E, round_up(H, W_ROW_PAD), n8, m->e8_scratch);
+            if (m->ef == WF_MXFP4)
+                hipLaunchKernelGGL(e4_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
+                                   (const uint8_t*)l.qs_moe_out, H, I, E, n8, m->eq_scratch);
+            else
+                hipLaunchKernelGGL(e8_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
+                                   (const float*)l.qs_moe_out, H, I, E, round_up(H, W_ROW_PAD), n8, m->eq_scratch);
             NVL_HIP(hipGetLastError());
-            w_down = m->e8_scratch;
-        } else if (m->e4) {
-            KScope ks(m, KC_OTHER, 0, KS_MOE_DOWN, (double)E * H * I * 2.53);
-            const int64_t n8 = (int64_t)E * H * I / 8;
-            hipLaunchKernelGGL(e4_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out4,
-                               (const uint8_t*)l.e_moe_out, H, I, E, n8, m->e8_scratch);
-            NVL_HIP(hipGetLastError());
-            w_down = m->e8_scratch;
+            w_down = m->eq_scratch;
         }
         GemmArgs d = mk(m->hbuf, I, w_down, m->moe_eo, H, nullptr, 1.f, max_mtiles, H, I);
         d.tile_map = m->moe_tile_map; d.n_mtiles = m->moe_n_mtiles; d.w_expert_stride = (int64_t)H * I; d.grp_bm = pp ? 512 : BM; d.grp_deep = small && g_moe_deep;
@@ -2259,9 +2083,9 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
         if (m->f32)
             hipLaunchKernelGGL((embed_kernel<float, false>), dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
                                (const float*)m->g[NVL_T_TOK_EMB].p, (const float*)pe, pe_rows, c.embedding_multiplier, m->x, H);
-        else if (m->g[NVL_T_TOK_EMB].scale)     // 8-bit tied table (w8.h)
+        else if (m->g[NVL_T_TOK_EMB].qs)     // 8-bit tied table (w8.h)
             hipLaunchKernelGGL(embed_w8_kernel, dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
-                               (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const float*)m->g[NVL_T_TOK_EMB].scale, (const bf16_t*)pe, pe_rows,
+                               (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const float*)m->g[NVL_T_TOK_EMB].qs, (const bf16_t*)pe, pe_rows,
                                c.embedding_multiplier, m->x, H);
         else
             hipLaunchKernelGGL((embed_kernel<bf16_t, true>), dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
@@ -2799,12 +2623,12 @@ void decode_loop(nvl_model* m, const Meta& hm, int n_seqs, int n_steps, int32_t*
             const void* pe = (m->cfg.position_type == NVL_POS_LEARNED) ? m->g[NVL_T_POS_EMB].p : nullptr;
             const int pe_rows = pe ? (int)std::min<int64_t>(m->g[NVL_T_POS_EMB].rows, m->cfg.max_seq_len) : 0;
             const LayerW& l0 = m->layers[0];
-            if (m->g[NVL_T_TOK_EMB].scale)     // 8-bit tied embedding table (w8.h)
+            if (m->g[NVL_T_TOK_EMB].qs)     // 8-bit tied embedding table (w8.h)
                 hipLaunchKernelGGL(decode_seam_w8_kernel, dim3(n_seqs), dim3(256), 0, m->stream, m->argmax_pval, m->argmax_pidx,
                                    cdiv(m->V, ARGMAX_CHUNK), sp ? (const int32_t*)m->samp.out : (const int32_t*)nullptr, m->samp_hist,
                                    (int64_t)m->cfg.max_seq_len, m->samp_hist_len, m->argmax_dev, m->ring, (const int32_t*)m->ring_pos0, n_seqs,
                                    md.tokens, md.tok_pos,
-                                   md.seq_pos, (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const float*)m->g[NVL_T_TOK_EMB].scale, (const bf16_t*)pe, pe_rows,
+                                   md.seq_pos, (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const float*)m->g[NVL_T_TOK_EMB].qs, (const bf16_t*)pe, pe_rows,
                                    m->cfg.embedding_multiplier, m->x, (const float*)l0.t[NVL_T_ATTN_NORM_W].p,
                                    (const float*)l0.t[NVL_T_ATTN_NORM_B].p, m->cfg.norm_eps, (bf16_t*)m->xn, m->H);
             else
@@ -3124,22 +2948,14 @@ extern "C" int nvl_get_weight(nvl_model* m, int kind, int layer, float* out, int
     NVL_HIP(hipSetDevice(m->device));
     NVL_HIP(hipStreamSynchronize(m->stream));
     const int64_t N = t->rows, K = t->cols, n_el = t->rows_pad * K;
-    if (t->mxs) {       // MXFP4 weight: W~ = +-grid[q] * 2^e, the values every GEMM path computes with
-        std::vector<uint8_t> codes((size_t)(n_el / 2)), sc((size_t)(n_el / 32));
+    if (t->qs) {     // quantized weight: W~, the values every GEMM path computes with — fp8: bf16_rne(s * e4m3(q)); MXFP4: +-grid[q] * 2^e
+        std::vector<uint8_t> codes((size_t)wf_code_bytes(t->wf, n_el)), sc((size_t)wf_scale_bytes(t->wf, t->rows_pad, K));
         NVL_HIP(hipMemcpy(codes.data(), t->p, codes.size(), hipMemcpyDeviceToHost));
-        NVL_HIP(hipMemcpy(sc.data(), t->mxs, sc.size(), hipMemcpyDeviceToHost));
+        NVL_HIP(hipMemcpy(sc.data(), t->qs, sc.size(), hipMemcpyDeviceToHost));
         for (int64_t n = 0; n < N; n++)
             for (int64_t k = 0; k < K; k++)
-                out[k * N + n] = w4_value(w4_code_at(codes.data(), n, k, K), sc[(size_t)w4_scale_index(n, k >> 5, K >> 5)]);
-        return NVL_OK;
-    }
-    if (t->scale) {     // 8-bit weight: W~ = bf16_rne(s * e4m3(q)), the values every GEMM path computes with
-        std::vector<uint8_t> codes((size_t)n_el);
-        std::vector<float> sc((size_t)t->rows_pad);
-        NVL_HIP(hipMemcpy(codes.data(), t->p, codes.size(), hipMemcpyDeviceToHost));
-        NVL_HIP(hipMemcpy(sc.data(), t->scale, sc.size() * 4, hipMemcpyDeviceToHost));
-        for (int64_t n = 0; n < N; n++)
-            for (int64_t k = 0; k < K; k++) out[k * N + n] = w8_value(codes[(size_t)fm_index(n, k, K)], sc[(size_t)n]);
+                out[k * N + n] = t->wf == WF_MXFP4 ? w4_value(w4_code_at(codes.data(), n, k, K), sc[(size_t)w4_scale_index(n, k >> 5, K >> 5)])
+                                                   : w8_value(codes[(size_t)fm_index(n, k, K)], ((const float*)sc.data())[n]);
         return NVL_OK;
     }
     std::vector<char> raw((size_t)n_el * m->wsize);

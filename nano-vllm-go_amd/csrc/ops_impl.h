@@ -224,34 +224,40 @@ extern "C" int nvl_op_attention(int device, int precision, const float* q, const
     OP_CATCH
 }
 
-// 8-bit weights (w8.h): W [K][N] ([in, out], as nvl_op_matmul) quantized by the upload quantizer, then C = bf16(A) · W~^T
-// through the model's dispatch (gemm(): M <= 64 the fp8-weight decode kernels, larger M the 64-row groups or
-// dequantize + tile; the scratch holds at most 2048 weight rows, as an LM head's would, so wide N runs in chunks).
-extern "C" int nvl_op_matmul_fp8w(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* codes_out,
-                                  float* scales_out) {
-    if (!a || !w || !c || M <= 0 || K <= 0 || N <= 0) return op_fail("nvl_op_matmul_fp8w: bad arguments");
-    if (K % 64 != 0) return op_fail("nvl_op_matmul_fp8w: K must be a multiple of 64");
-    OP_TRY
-    OpCtx cx(device, NVL_PRECISION_BF16);
-    cx.m.w8 = true;
+// The one-weight model of the quantized matmul ops: W [K][N] ([in, out], as nvl_op_matmul) quantized by the upload quantizer
+// of format wf into t and registered for gemm(), a tile-path scratch of at most scratch_rows weight rows, then
+// C = bf16(A) · W~^T through the model's dispatch into c [M][N].
+static void op_matmul_q(OpCtx& cx, int wf, const float* a, const float* w, int M, int N, int K, float* c, DevTensor& t, int64_t scratch_rows) {
+    cx.m.wf = wf;
     void* A = cx.up_mat(a, M, K, false);
-    DevTensor t;
-    upload_2d_w8(&cx.m, &t, w, NVL_DTYPE_F32, N, K, true);
-    cx.bufs.push_back(t.p); cx.bufs.push_back(t.scale);
-    cx.m.w8_map[t.p] = nvl_model::W8Ref{t.scale, t.rows_pad};
-    cx.m.w8_scratch_elems = std::min<int64_t>(t.rows_pad, 2048) * K;
-    cx.m.w8_scratch = (bf16_t*)cx.alloc(cx.m.w8_scratch_elems * 2);
+    upload_2d_q(&cx.m, &t, wf, w, NVL_DTYPE_F32, N, K, true);
+    cx.bufs.push_back(t.p); cx.bufs.push_back(t.qs);
+    cx.m.qmap[t.p] = nvl_model::QRef{wf, t.qs, t.rows_pad};
+    cx.m.wq_scratch_elems = std::min<int64_t>(t.rows_pad, scratch_rows) * K;
+    cx.m.wq_scratch = (bf16_t*)cx.alloc(cx.m.wq_scratch_elems * 2);
     const int ldc = (int)round_up(N, 4);
     float* C = (float*)cx.alloc((int64_t)M * ldc * 4);
     gemm(&cx.m, EPI_STORE, true, mk(A, K, t.p, C, ldc, nullptr, 1.f, M, N, K));
     std::vector<float> tmp((size_t)M * ldc);
     cx.down(tmp.data(), C, (int64_t)M * ldc);
     for (int i = 0; i < M; i++) memcpy(c + (size_t)i * N, &tmp[(size_t)i * ldc], (size_t)N * 4);
+}
+
+// 8-bit weights (w8.h): M <= 64 the fp8-weight decode kernels, larger M the 64-row groups or dequantize + tile; the scratch
+// holds at most 2048 weight rows, as an LM head's would, so wide N runs in chunks.
+extern "C" int nvl_op_matmul_fp8w(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* codes_out,
+                                  float* scales_out) {
+    if (!a || !w || !c || M <= 0 || K <= 0 || N <= 0) return op_fail("nvl_op_matmul_fp8w: bad arguments");
+    if (K % 64 != 0) return op_fail("nvl_op_matmul_fp8w: K must be a multiple of 64");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_BF16);
+    DevTensor t;
+    op_matmul_q(cx, WF_FP8, a, w, M, N, K, c, t, 2048);
     if (codes_out || scales_out) {
         std::vector<uint8_t> codes((size_t)(t.rows_pad * K));
         std::vector<float> sc((size_t)t.rows_pad);
         NVL_HIP(hipMemcpy(codes.data(), t.p, codes.size(), hipMemcpyDeviceToHost));
-        NVL_HIP(hipMemcpy(sc.data(), t.scale, sc.size() * 4, hipMemcpyDeviceToHost));
+        NVL_HIP(hipMemcpy(sc.data(), t.qs, sc.size() * 4, hipMemcpyDeviceToHost));
         if (scales_out) memcpy(scales_out, sc.data(), (size_t)N * 4);
         if (codes_out)
             for (int64_t n = 0; n < N; n++)
@@ -261,32 +267,19 @@ extern "C" int nvl_op_matmul_fp8w(int device, const float* a, const float* w, in
     OP_CATCH
 }
 
-// MXFP4 weights (w4.h): nvl_op_matmul_fp8w's shape — W [K][N] quantized by the upload quantizer, C = bf16(A) · W~^T through
-// the model's dispatch (the MXFP4-weight decode kernels, the 64-row groups, dequantize + tile)
+// MXFP4 weights (w4.h): the MXFP4-weight decode kernels, the 64-row groups, dequantize + tile (the scratch holds all of W~)
 extern "C" int nvl_op_matmul_mxfp4w(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* codes_out,
                                     uint8_t* scales_out) {
     if (!a || !w || !c || M <= 0 || K <= 0 || N <= 0) return op_fail("nvl_op_matmul_mxfp4w: bad arguments");
     if (K % 64 != 0) return op_fail("nvl_op_matmul_mxfp4w: K must be a multiple of 64");
     OP_TRY
     OpCtx cx(device, NVL_PRECISION_BF16);
-    cx.m.mx = true;
-    void* A = cx.up_mat(a, M, K, false);
     DevTensor t;
-    upload_2d_w4(&cx.m, &t, w, NVL_DTYPE_F32, N, K, true);
-    cx.bufs.push_back(t.p); cx.bufs.push_back(t.mxs);
-    cx.m.w4_map[t.p] = nvl_model::W4Ref{t.mxs, t.rows_pad};
-    cx.m.w8_scratch_elems = t.rows_pad * K;
-    cx.m.w8_scratch = (bf16_t*)cx.alloc(cx.m.w8_scratch_elems * 2);
-    const int ldc = (int)round_up(N, 4);
-    float* C = (float*)cx.alloc((int64_t)M * ldc * 4);
-    gemm(&cx.m, EPI_STORE, true, mk(A, K, t.p, C, ldc, nullptr, 1.f, M, N, K));
-    std::vector<float> tmp((size_t)M * ldc);
-    cx.down(tmp.data(), C, (int64_t)M * ldc);
-    for (int i = 0; i < M; i++) memcpy(c + (size_t)i * N, &tmp[(size_t)i * ldc], (size_t)N * 4);
+    op_matmul_q(cx, WF_MXFP4, a, w, M, N, K, c, t, INT64_MAX);
     if (codes_out || scales_out) {
         std::vector<uint8_t> codes((size_t)(t.rows_pad * K / 2)), sc((size_t)(t.rows_pad * K / 32));
         NVL_HIP(hipMemcpy(codes.data(), t.p, codes.size(), hipMemcpyDeviceToHost));
-        NVL_HIP(hipMemcpy(sc.data(), t.mxs, sc.size(), hipMemcpyDeviceToHost));
+        NVL_HIP(hipMemcpy(sc.data(), t.qs, sc.size(), hipMemcpyDeviceToHost));
         std::vector<uint8_t> co((size_t)N * K / 2), so((size_t)N * K / 32);
         w4_to_abi(codes.data(), sc.data(), N, K, co.data(), so.data());
         if (codes_out) memcpy(codes_out, co.data(), co.size());
@@ -317,15 +310,7 @@ extern "C" int nvl_op_matmul_w8a8(int device, const float* a, const float* w, in
     if (K % 64 != 0) return op_fail("nvl_op_matmul_w8a8: K must be a multiple of 64");
     OP_TRY
     OpCtx cx(device, NVL_PRECISION_BF16);
-    cx.m.w8 = true;
     cx.m.a8 = true;
-    void* A = cx.up_mat(a, M, K, false);
-    DevTensor t;
-    upload_2d_w8(&cx.m, &t, w, NVL_DTYPE_F32, N, K, true);
-    cx.bufs.push_back(t.p); cx.bufs.push_back(t.scale);
-    cx.m.w8_map[t.p] = nvl_model::W8Ref{t.scale, t.rows_pad};
-    cx.m.w8_scratch_elems = std::min<int64_t>(t.rows_pad, 2048) * K;
-    cx.m.w8_scratch = (bf16_t*)cx.alloc(cx.m.w8_scratch_elems * 2);
     cx.m.a8_rows = round_up(M, 16);
     cx.m.a8_k = K;
     cx.m.a8_codes = (uint8_t*)cx.alloc(cx.m.a8_rows * K);
@@ -334,12 +319,8 @@ extern "C" int nvl_op_matmul_w8a8(int device, const float* a, const float* w, in
     const std::vector<float> ones((size_t)cx.m.a8_rows, 1.0f);
     NVL_HIP(hipMemcpyAsync(cx.m.a8_scale, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, cx.m.stream));
     NVL_HIP(hipStreamSynchronize(cx.m.stream));     // (pageable source)
-    const int ldc = (int)round_up(N, 4);
-    float* C = (float*)cx.alloc((int64_t)M * ldc * 4);
-    gemm(&cx.m, EPI_STORE, true, mk(A, K, t.p, C, ldc, nullptr, 1.f, M, N, K));
-    std::vector<float> tmp((size_t)M * ldc);
-    cx.down(tmp.data(), C, (int64_t)M * ldc);
-    for (int i = 0; i < M; i++) memcpy(c + (size_t)i * N, &tmp[(size_t)i * ldc], (size_t)N * 4);
+    DevTensor t;
+    op_matmul_q(cx, WF_FP8, a, w, M, N, K, c, t, 2048);
     if (a_codes_out || a_scales_out) a8_read_back(cx, cx.m.a8_codes, cx.m.a8_scale, M, K, a_codes_out, a_scales_out);
     cx.m.a8_codes = nullptr; cx.m.a8_scale = nullptr;       // owned by cx.bufs
     return NVL_OK;

@@ -1,6 +1,6 @@
 // w4.h — MXFP4 projection weights (nvl_set_mx_weight_dtype): OCP e2m1 elements with one e8m0 scale
 // per block of 32 consecutive k of one output row.  The quantizer every upload uses, the placement of pre-quantized input,
-// the dequantize kernel of the tile path, and the GEMM dispatch of an MXFP4 weight.
+// and the dequantize kernel of the tile path.  The host side shared with fp8 (format table, GEMM dispatch) is wq.h.
 //
 // Numerics, per 32-block: e = clamp(floor(log2(amax)) - 2, -120, 125) (0 for an all-zero block), stored E = e + 127;
 // q = e2m1_rne(|w| / 2^e) on {0, .5, 1, 1.5, 2, 3, 4, 6}, ties to the even mantissa bit, saturating at 6; sign in bit 3.
@@ -108,44 +108,6 @@ __global__ __launch_bounds__(256) void e4_dequant_down_kernel(const uint8_t* __r
     const int64_t lane = j & 63, blk = j >> 6, tile = blk / kbs, ks = blk - tile * kbs;
     const int64_t sblk = (tile * E + e) * kbs + ks;
     *(bf16x8*)(out + i * 8) = w4_frag(*(const uint32_t*)(codes + (sblk * 64 + lane) * 4), (uint32_t)scales[sblk * 16 + (lane & 15)]);
-}
-
-// W~ of rows [0, rows) (whole 16-row tiles) into dst, fragment-major
-static inline void w4_dequant_rows(hipStream_t st, const void* codes, const uint8_t* scales, int64_t K, int64_t rows, bf16_t* dst) {
-    const int64_t n8 = rows * K / 8;
-    hipLaunchKernelGGL(w4_dequant_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, st, (const uint8_t*)codes, scales, n8, dst);
-}
-
-// The GEMM of an MXFP4 weight (a.W: codes, es: block scales, w_rows_pad: its allocated rows).  Decode-sized calls go where
-// the bf16 dispatch (launch_gemm_bf16) sends them, on the MXFP4-weight kernels; the rest run the bf16 dispatch on W~ in
-// `scratch` (scratch_elems bf16 elements; nvl_finalize sizes it for the largest MXFP4 projection).
-template <int EPI, typename OutT>
-static inline void launch_gemm_w4(hipStream_t st, const GemmArgs& a, const uint8_t* es, int64_t w_rows_pad, bf16_t* scratch,
-                                  int64_t scratch_elems) {
-    if (a.tile_map || a.seg || a.a_rows) throw std::runtime_error("gemm: an MXFP4 weight in a gathered / grouped launch");
-    const float* ws = (const float*)es;     // (the launchers' scale argument; the MXFP4 kernels take it back as bytes)
-    if (a.moe_gate) {     // MXFP4 MoE experts, the decode (dense-masked) form: the only launch that reads their codes
-        if (launch_gemm_skinny_bf16<EPI, OutT, WF_MXFP4>(st, a, ws)) return;
-        throw std::runtime_error("gemm: an MXFP4 MoE projection did not fit the decode kernels");
-    }
-    if (launch_gemm_skinny_bf16<EPI, OutT, WF_MXFP4>(st, a, ws)) return;
-    if constexpr (EPI != EPI_QKV) {     // (the 64-row-group condition of launch_gemm_bf16, unchanged)
-        const bool few_tiles = cdiv(a.M, 128) * cdiv(a.N, 128) < g_chunk_min_tiles;
-        if (a.M > 64 && a.M <= g_chunk_max_m && (a.M <= g_chunk_all_m || few_tiles || a.rs_in || a.rs_out) && !a.sk_part && a.K % 32 == 0 &&
-            g_force_tile == 0) {
-            GemmArgs c = a;
-            c.m_passes = cdiv(a.M, 64);
-            const bool ok = g_pass_interleave ? launch_gemm_skinny_bf16<EPI, OutT, WF_MXFP4>(st, c, ws)
-                                              : launch_skinny_passes_serial<EPI, OutT, WF_MXFP4>(st, c, ws);
-            if (ok) return;
-        }
-    }
-    if (a.rs_in || a.rs_out) throw std::runtime_error("gemm: a deferred-RMSNorm projection did not fit the decode kernels");
-    if (w_rows_pad * a.K > scratch_elems) throw std::runtime_error("gemm: an MXFP4 weight larger than its dequantize scratch");
-    w4_dequant_rows(st, a.W, es, a.K, w_rows_pad, scratch);
-    GemmArgs c = a;
-    c.W = scratch;
-    launch_gemm_bf16<EPI, OutT>(st, c);
 }
 
 // ---- host ----

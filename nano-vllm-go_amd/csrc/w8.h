@@ -1,6 +1,6 @@
 // w8.h — 8-bit (OCP e4m3fn) projection weights with one fp32 scale per output row (nvl_set_weight_dtype, DESIGN.md §3 and
 // §9 f-6): the quantizer every upload uses, the dequantize kernel of the tile path, the embedding gather of a quantized
-// tied table, and the GEMM dispatch of an 8-bit weight.
+// tied table.  The host side shared with MXFP4 (format table, GEMM dispatch) is wq.h.
 //
 // Numerics: s_n = amax_n / 448 (1 when the row is all zeros), q = e4m3fn_rne(w / s_n) through kv8.h's quantizer; the model
 // computes with W~ = bf16_rne(s_n * e4m3(q)) (fp32 product, one rounding), on every path:
@@ -18,7 +18,6 @@
 #pragma once
 #include "kv8.h"
 #include "gemm.h"
-#include "a8.h"
 
 namespace nvl {
 
@@ -182,68 +181,6 @@ __global__ __launch_bounds__(256) void e8_dequant_down_kernel(const uint8_t* __r
     const int64_t lane = j & 63, blk = j >> 6, tile = blk / kbs, ks = blk - tile * kbs;
     const int64_t src = ((tile * E * kbs + e * kbs + ks) * 64 + lane) * 8;
     *(bf16x8*)(out + i * 8) = w8_frag(*(const u32x2*)(codes + src), scale[e * hp + tile * 16 + (lane & 15)]);
-}
-
-// W~ of rows [row0, row0 + rows) (row0 % 16 == 0) into dst, fragment-major
-static inline void w8_dequant_rows(hipStream_t st, const void* codes, const float* scale, int64_t K, int64_t row0, int64_t rows,
-                                   bf16_t* dst) {
-    const int64_t n8 = rows * K / 8;
-    hipLaunchKernelGGL(w8_dequant_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, st, (const uint8_t*)codes + row0 * K,
-                       scale + row0, K, n8, dst);
-}
-
-// The GEMM of an 8-bit weight (a.W: codes, ws: scales, w_rows_pad: its allocated rows).  Decode-sized calls go where the bf16
-// dispatch (launch_gemm_bf16) sends them, on the fp8-weight kernels; the rest run the bf16 dispatch on W~ in `scratch`
-// (scratch_elems bf16 elements), in row chunks when W~ does not fit (EPI_STORE with fp32 output only: the LM head).
-// With a8 (8-bit activations, a8.h) the tile step is the W8A8 kernel on the codes instead.
-template <int EPI, typename OutT>
-static inline void launch_gemm_w8(hipStream_t st, const GemmArgs& a, const float* ws, int64_t w_rows_pad, bf16_t* scratch,
-                                  int64_t scratch_elems, const A8Buf* a8 = nullptr) {
-    if (a.tile_map || a.seg || a.a_rows) throw std::runtime_error("gemm: an 8-bit weight in a gathered / grouped launch");
-    if (a.moe_gate) {     // 8-bit MoE experts, the decode (dense-masked) form: the only launch that reads their codes
-        if (launch_gemm_skinny_bf16<EPI, OutT, true>(st, a, ws)) return;
-        throw std::runtime_error("gemm: an 8-bit MoE projection did not fit the decode kernels");
-    }
-    if (launch_gemm_skinny_bf16<EPI, OutT, true>(st, a, ws)) return;
-    if constexpr (EPI != EPI_QKV) {     // (the 64-row-group condition of launch_gemm_bf16, unchanged)
-        const bool few_tiles = cdiv(a.M, 128) * cdiv(a.N, 128) < g_chunk_min_tiles;
-        if (a.M > 64 && a.M <= g_chunk_max_m && (a.M <= g_chunk_all_m || few_tiles || a.rs_in || a.rs_out) && !a.sk_part && a.K % 32 == 0 &&
-            g_force_tile == 0) {
-            GemmArgs c = a;
-            c.m_passes = cdiv(a.M, 64);
-            const bool ok = g_pass_interleave ? launch_gemm_skinny_bf16<EPI, OutT, true>(st, c, ws)
-                                              : launch_skinny_passes_serial<EPI, OutT, true>(st, c, ws);
-            if (ok) return;
-        }
-    }
-    if (a.rs_in || a.rs_out) throw std::runtime_error("gemm: a deferred-RMSNorm projection did not fit the decode kernels");
-    if (a8) {
-        launch_gemm_w8a8<EPI, OutT>(st, a, ws, *a8);
-        return;
-    }
-    if (w_rows_pad * a.K <= scratch_elems) {
-        w8_dequant_rows(st, a.W, ws, a.K, 0, w_rows_pad, scratch);
-        GemmArgs c = a;
-        c.W = scratch;
-        launch_gemm_bf16<EPI, OutT>(st, c);
-        return;
-    }
-    if constexpr (EPI == EPI_STORE && std::is_same<OutT, float>::value) {
-        const int64_t chunk = (scratch_elems / a.K) / W_ROW_PAD * W_ROW_PAD;     // whole padded tiles per chunk
-        if (chunk < W_ROW_PAD) throw std::runtime_error("gemm: the 8-bit weight scratch holds no whole row tile");
-        for (int64_t n0 = 0; n0 < a.N; n0 += chunk) {
-            const int64_t rows = std::min<int64_t>(chunk, w_rows_pad - n0);
-            w8_dequant_rows(st, a.W, ws, a.K, n0, rows, scratch);
-            GemmArgs c = a;
-            c.W = scratch;
-            c.N = (int)std::min<int64_t>(chunk, a.N - n0);
-            c.C = (float*)a.C + n0;
-            if (a.bias) c.bias = a.bias + n0;
-            launch_gemm_bf16<EPI, OutT>(st, c);
-        }
-        return;
-    }
-    throw std::runtime_error("gemm: an 8-bit weight larger than its dequantize scratch");
 }
 
 // host: W~ of one code (the read-back of nvl_get_weight)

@@ -9,6 +9,8 @@
 # And the register budgets of the decode kernels (from the code object metadata in the same assembly): round 3 lost 5-14 % of
 # decode throughput on three configs to changes that were only measured on the headline one — the MHA / small-batch
 # decode-attention instantiations went from two waves per SIMD to one, the 64-row-group projections spilled 34-54 registers.
+# Whether a change left the device code as it was is another question: build the assembly of both trees with the hipcc line
+# below and compare them with scripts/isa_diff.py OLD.s NEW.s (function bodies and kernel metadata by mangled name).
 set -e
 S=${TMPDIR:-/tmp}/nvllm_check.s
 cd "$(dirname "$0")/.."
