@@ -201,13 +201,15 @@ enum {
                             * (0 for an all-zero block), stored as E = e + 127; q = e2m1_rne(|w| / 2^e) on {0, .5, 1, 1.5, 2, 3,
                             * 4, 6}, ties to the even mantissa bit, saturating at 6; the sign is bit 3.  Every path computes with
                             * W~ = +-grid[q] * 2^e (exact in bf16); nvl_get_weight returns W~; nvl_stats.weight_bytes counts
-                            * codes + scales.  LM head, embeddings, router and Mamba2 projections stay bf16; MoE experts too
-                            * unless nvl_set_mx_expert_dtype(m, NVL_MXE_FP4_E2M1). */
+                            * codes + scales.  Embeddings, router and Mamba2 projections stay bf16; MoE experts too unless
+                            * nvl_set_mx_expert_dtype(m, NVL_MXE_FP4_E2M1); the LM head and the tied token embedding too
+                            * unless nvl_set_mx_head_dtype(m, NVL_MXH_FP4_E2M1). */
 };
 /* After nvl_create, before the first 2-D upload (else NVL_ERR_STATE).  NVL_ERR_INVALID for an unknown value, and for
  * NVL_MX_FP4_E2M1 with f32 precision, tensor parallelism or NVL_W_FP8_E4M3 (which in turn is refused once MX is set, and
  * with it nvl_set_act_dtype / nvl_set_expert_dtype).  In MX mode nvl_upload_tensor refuses a non-finite weight.
- * NVL_MX_NONE is refused (NVL_ERR_INVALID) while nvl_set_mx_expert_dtype holds NVL_MXE_FP4_E2M1. */
+ * NVL_MX_NONE is refused (NVL_ERR_INVALID) while nvl_set_mx_expert_dtype holds NVL_MXE_FP4_E2M1 or nvl_set_mx_head_dtype
+ * holds NVL_MXH_FP4_E2M1. */
 int nvl_set_mx_weight_dtype(nvl_model* m, int dtype);
 /* MoE expert weights (MOE_IN / MOE_OUT) of a model with MXFP4 projection weights. */
 enum {
@@ -222,6 +224,24 @@ enum {
 /* After nvl_set_mx_weight_dtype(m, NVL_MX_FP4_E2M1), before the first expert upload and nvl_finalize (else NVL_ERR_STATE).
  * NVL_ERR_INVALID for a NULL model, an unknown value, a model without MoE, f32 precision, or no MXFP4 projection weights. */
 int nvl_set_mx_expert_dtype(nvl_model* m, int dtype);
+/* LM head and tied token embedding of a model with MXFP4 projection weights. */
+enum {
+    NVL_MXH_NONE = 0,          /* the LM head and the token embedding stay bf16 (also under NVL_MX_FP4_E2M1): today's behaviour */
+    NVL_MXH_FP4_E2M1 = 1       /* LM_HEAD as e2m1 codes under the contract of NVL_MX_FP4_E2M1, byte for byte: one e8m0 scale per
+                                * 32 consecutive input features of one output (vocabulary) row, the same exponent rule, clamp,
+                                * ties and saturation; W~ = +-grid[q] * 2^e on every path.  TOK_EMB is stored the same way when
+                                * tied_embedding is set (the rule of NVL_W_FP8_E4M3): the gathered embedding row is W~, exact in
+                                * bf16, and the embedding multiplier and the learned position row (bf16) apply to it as always.
+                                * An untied model whose LM head is absent runs the bf16 head on its bf16 embedding.  Position
+                                * embedding, router and Mamba2 projections stay bf16.  nvl_get_weight returns W~ for both kinds;
+                                * nvl_stats.weight_bytes counts codes + scales; nvl_upload_tensor refuses a non-finite head or
+                                * embedding weight; nvl_upload_tensor_mxfp4 takes LM_HEAD, and TOK_EMB when tied (rows = vocab_size,
+                                * cols = hidden). */
+};
+/* After nvl_set_mx_weight_dtype(m, NVL_MX_FP4_E2M1) and before the first 2-D upload (else NVL_ERR_STATE).  NVL_ERR_INVALID
+ * for a NULL model, an unknown value, f32 precision, or no MXFP4 projection weights (which covers tensor parallelism and
+ * NVL_W_FP8_E4M3).  While it holds NVL_MXH_FP4_E2M1, nvl_set_mx_weight_dtype(m, NVL_MX_NONE) is refused (NVL_ERR_INVALID). */
+int nvl_set_mx_head_dtype(nvl_model* m, int dtype);
 /* Pre-quantized MXFP4 weight, taken as it is: codes [rows][cols/2], two per byte with the even input feature in the low
  * nibble (OCP MX order), scales [rows][cols/32] e8m0 bytes, both in the checkpoint's [out, in] order (layout must be
  * NVL_LAYOUT_OUT_IN).  NVL_ERR_INVALID for a kind this model does not store as MXFP4, a shape mismatch, cols % 32 != 0,

@@ -36,6 +36,7 @@ KV_CACHE_DTYPE = {"auto": 0, "fp8_e4m3": 1}
 WEIGHT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                # NVL_W_* (nvl_set_weight_dtype)
 MX_WEIGHT_DTYPE = {"none": 0, "fp4_e2m1": 1}             # NVL_MX_* (nvl_set_mx_weight_dtype)
 MX_EXPERT_DTYPE = {"none": 0, "fp4_e2m1": 1}             # NVL_MXE_* (nvl_set_mx_expert_dtype)
+MX_HEAD_DTYPE = {"none": 0, "fp4_e2m1": 1}               # NVL_MXH_* (nvl_set_mx_head_dtype)
 ACT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                   # NVL_ACT_AUTO / NVL_ACT_FP8_E4M3 (nvl_set_act_dtype)
 EXPERT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                # NVL_EXPERT_AUTO / NVL_EXPERT_FP8_E4M3 (nvl_set_expert_dtype)
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
@@ -180,6 +181,7 @@ def lib():
     L.nvl_set_act_dtype.argtypes = [vp, C.c_int]
     L.nvl_set_mx_weight_dtype.argtypes = [vp, C.c_int]
     L.nvl_set_mx_expert_dtype.argtypes = [vp, C.c_int]
+    L.nvl_set_mx_head_dtype.argtypes = [vp, C.c_int]
     L.nvl_upload_tensor_mxfp4.argtypes = [vp, C.c_int, C.c_int, vp, vp, i64, i64, C.c_int]
     L.nvl_op_matmul_mxfp4w.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.nvl_set_expert_dtype.argtypes = [vp, C.c_int]

@@ -401,7 +401,7 @@ namespace {
 // `sl` selects the sub-block of the uploaded tensor that lands in rows [dn0, dn0+N) (the whole tensor for
 // replicated kinds, this rank's shard for tensor-parallel kinds); total_rows sizes the destination.
 // the quantized format this 2-D kind is stored in (wq.h wf_covers), or WF_BF16
-int q_kind(const nvl_model* m, int kind) { return wf_covers(m->wf, m->ef, kind, m->cfg.tied_embedding != 0) ? m->wf : WF_BF16; }
+int q_kind(const nvl_model* m, int kind) { return wf_covers(m->wf, m->ef, m->hf, kind, m->cfg.tied_embedding != 0) ? m->wf : WF_BF16; }
 
 // the scales of `rows` rows of K inputs, every one the pad value of the format: fp32 1.0, or the e8m0 byte 127 (2^0)
 void* q_alloc_scales(nvl_model* m, int wf, int64_t rows, int64_t K) {
@@ -886,8 +886,23 @@ extern "C" int nvl_set_mx_weight_dtype(nvl_model* m, int dtype) {
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores 8-bit weights (nvl_set_weight_dtype)");
     if (dtype == NVL_MX_NONE && m->ef == WF_MXFP4)
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores MXFP4 experts (nvl_set_mx_expert_dtype), which need MXFP4 weights");
+    if (dtype == NVL_MX_NONE && m->hf == WF_MXFP4)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores an MXFP4 LM head (nvl_set_mx_head_dtype), which needs MXFP4 weights");
     if (dtype == NVL_MX_FP4_E2M1) m->wf = WF_MXFP4;
     else if (m->wf == WF_MXFP4) m->wf = WF_BF16;
+    return NVL_OK;
+}
+
+extern "C" int nvl_set_mx_head_dtype(nvl_model* m, int dtype) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mx_head_dtype: no model");
+    if (m->finalized || m->w2d_uploaded)
+        return fail(m, NVL_ERR_STATE, "nvl_set_mx_head_dtype: call it after nvl_set_mx_weight_dtype and before the first 2-D weight upload");
+    if (dtype != NVL_MXH_NONE && dtype != NVL_MXH_FP4_E2M1) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_head_dtype: unknown MX head dtype");
+    if (dtype == NVL_MXH_FP4_E2M1) {
+        if (m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_head_dtype: an MXFP4 LM head needs bf16 precision");
+        if (m->wf != WF_MXFP4) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_head_dtype: an MXFP4 LM head needs MXFP4 projection weights (nvl_set_mx_weight_dtype first)");
+    }
+    m->hf = dtype == NVL_MXH_FP4_E2M1 ? WF_MXFP4 : WF_BF16;
     return NVL_OK;
 }
 
@@ -1075,7 +1090,7 @@ extern "C" int nvl_finalize(nvl_model* m) {
             reg(l.w_qkv, l.qs_qkv, l.n_qkv, H); reg(l.w1, l.qs1, l.n1, H);
             reg(l.t[NVL_T_WO].p, l.t[NVL_T_WO].qs, H, l.t[NVL_T_WO].cols); reg(l.t[NVL_T_W2].p, l.t[NVL_T_W2].qs, H, l.t[NVL_T_W2].cols);
         }
-        if (head.qs) {   // (fp8; at least one row tile of the LM head: it runs in chunks)
+        if (head.qs) {   // (fp8, or MXFP4 with nvl_set_mx_head_dtype; at least one row tile of the LM head: it runs in chunks)
             m->qmap[head.p] = nvl_model::QRef{m->wf, head.qs, round_up(m->V, W_ROW_PAD)};
             big = std::max(big, W_ROW_PAD * H);
         }
@@ -2083,6 +2098,10 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
         if (m->f32)
             hipLaunchKernelGGL((embed_kernel<float, false>), dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
                                (const float*)m->g[NVL_T_TOK_EMB].p, (const float*)pe, pe_rows, c.embedding_multiplier, m->x, H);
+        else if (m->g[NVL_T_TOK_EMB].wf == WF_MXFP4)     // MXFP4 tied table (w4.h)
+            hipLaunchKernelGGL(embed_w4_kernel, dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
+                               (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const uint8_t*)m->g[NVL_T_TOK_EMB].qs, (const bf16_t*)pe, pe_rows,
+                               c.embedding_multiplier, m->x, H);
         else if (m->g[NVL_T_TOK_EMB].qs)     // 8-bit tied table (w8.h)
             hipLaunchKernelGGL(embed_w8_kernel, dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
                                (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const float*)m->g[NVL_T_TOK_EMB].qs, (const bf16_t*)pe, pe_rows,
@@ -2623,7 +2642,15 @@ void decode_loop(nvl_model* m, const Meta& hm, int n_seqs, int n_steps, int32_t*
             const void* pe = (m->cfg.position_type == NVL_POS_LEARNED) ? m->g[NVL_T_POS_EMB].p : nullptr;
             const int pe_rows = pe ? (int)std::min<int64_t>(m->g[NVL_T_POS_EMB].rows, m->cfg.max_seq_len) : 0;
             const LayerW& l0 = m->layers[0];
-            if (m->g[NVL_T_TOK_EMB].qs)     // 8-bit tied embedding table (w8.h)
+            if (m->g[NVL_T_TOK_EMB].wf == WF_MXFP4)     // MXFP4 tied embedding table (w4.h)
+                hipLaunchKernelGGL(decode_seam_w4_kernel, dim3(n_seqs), dim3(256), 0, m->stream, m->argmax_pval, m->argmax_pidx,
+                                   cdiv(m->V, ARGMAX_CHUNK), sp ? (const int32_t*)m->samp.out : (const int32_t*)nullptr, m->samp_hist,
+                                   (int64_t)m->cfg.max_seq_len, m->samp_hist_len, m->argmax_dev, m->ring, (const int32_t*)m->ring_pos0, n_seqs,
+                                   md.tokens, md.tok_pos,
+                                   md.seq_pos, (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const uint8_t*)m->g[NVL_T_TOK_EMB].qs, (const bf16_t*)pe, pe_rows,
+                                   m->cfg.embedding_multiplier, m->x, (const float*)l0.t[NVL_T_ATTN_NORM_W].p,
+                                   (const float*)l0.t[NVL_T_ATTN_NORM_B].p, m->cfg.norm_eps, (bf16_t*)m->xn, m->H);
+            else if (m->g[NVL_T_TOK_EMB].qs)     // 8-bit tied embedding table (w8.h)
                 hipLaunchKernelGGL(decode_seam_w8_kernel, dim3(n_seqs), dim3(256), 0, m->stream, m->argmax_pval, m->argmax_pidx,
                                    cdiv(m->V, ARGMAX_CHUNK), sp ? (const int32_t*)m->samp.out : (const int32_t*)nullptr, m->samp_hist,
                                    (int64_t)m->cfg.max_seq_len, m->samp_hist_len, m->argmax_dev, m->ring, (const int32_t*)m->ring_pos0, n_seqs,

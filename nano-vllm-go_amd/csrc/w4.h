@@ -81,6 +81,110 @@ __global__ __launch_bounds__(256) void w4_dequant_kernel(const uint8_t* __restri
     *(bf16x8*)(out + i * 8) = w4_frag(*(const uint32_t*)(codes + i * 4), (uint32_t)scales[(i >> 6) * 16 + (i & 15)]);
 }
 
+// MXFP4 LM head / tied embedding table (nvl_set_mx_head_dtype): the head is one more [Vpad][H] weight of
+// the layout above, streamed by the same decode kernels; the two kernels below gather rows of it.
+// embed_kernel<bf16_t, true> over the MXFP4 (tied) table: each gathered element is W~.  A thread takes the 8 codes of one
+// fragment (4 bytes, one load) and the byte of their block; H % 32 == 0.
+__global__ __launch_bounds__(256) void embed_w4_kernel(const int32_t* __restrict__ tokens, const int32_t* __restrict__ tok_pos,
+                                                       const uint8_t* __restrict__ emb, const uint8_t* __restrict__ escales,
+                                                       const bf16_t* __restrict__ pos_emb, int max_seq, float mult,
+                                                       float* __restrict__ x, int H) {
+    const int t = blockIdx.x;
+    const int tok = tokens[t];
+    const int pos = tok_pos[t];
+    const bool use_pos = pos_emb && pos < max_seq;
+    float* xr = x + (int64_t)t * H;
+    for (int j = threadIdx.x * 8; j < H; j += 256 * 8) {
+        const bf16x8 e = w4_frag(*(const uint32_t*)(emb + (fm_index(tok, j, H) >> 1)), (uint32_t)escales[w4_scale_index(tok, j >> 5, H >> 5)]);
+        bf16x8 pe = {};
+        if (use_pos) pe = *(const bf16x8*)(pos_emb + fm_index(pos, j, H));
+        f32x4 lo, hi;
+#pragma unroll
+        for (int k = 0; k < 8; k++) {
+            float f = (float)e[k];
+            if (use_pos) f += (float)pe[k];
+            if (mult != 0.f) f *= mult;
+            if (k < 4) lo[k] = f; else hi[k - 4] = f;
+        }
+        *(f32x4*)(xr + j) = lo;
+        *(f32x4*)(xr + j + 4) = hi;
+    }
+}
+
+// decode_seam_kernel (elem.h) over the MXFP4 (tied) embedding table: the same launch, the gathered row is W~.  A thread
+// keeps the 4 elements norm_row_finish expects of it: it loads its fragment's 4 code bytes and converts its half of them.
+__global__ __launch_bounds__(256) void decode_seam_w4_kernel(const float* __restrict__ pval, const int32_t* __restrict__ pidx,
+                                                          int chunks, const int32_t* __restrict__ sampled,
+                                                          int32_t* __restrict__ hist, int64_t hist_stride,
+                                                          int32_t* __restrict__ hist_len, int32_t* __restrict__ argmax_out,
+                                                          int32_t* __restrict__ ring_out, const int32_t* __restrict__ ring_pos0,
+                                                          int ring_rows, int32_t* __restrict__ tokens,
+                                                          int32_t* __restrict__ tok_pos, int32_t* __restrict__ seq_pos,
+                                                          const uint8_t* __restrict__ emb, const uint8_t* __restrict__ escales, const bf16_t* __restrict__ pos_emb,
+                                                          int max_seq, float mult, float* __restrict__ x,
+                                                          const float* __restrict__ w, const float* __restrict__ b,
+                                                          float eps, bf16_t* __restrict__ y, int H) {
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+    __shared__ float red[4];
+    __shared__ int tok_s, pos_s;
+    const int r = blockIdx.x;
+    if (threadIdx.x < 64) {
+        float best = -INFINITY;
+        int bi = 0x7fffffff;
+        if (!sampled) {
+            for (int c = threadIdx.x; c < chunks; c += 64) argmax_merge(best, bi, pval[r * chunks + c], pidx[r * chunks + c]);
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) argmax_merge(best, bi, __shfl_xor(best, o, 64), __shfl_xor(bi, o, 64));
+        }
+        if (threadIdx.x == 0) {
+            int t = (bi == 0x7fffffff) ? 0 : bi;
+            if (sampled) {                 // the token comes from sample_row_kernel; it joins the sequence's history
+                t = sampled[r];
+                const int n = hist_len[r];
+                hist[(int64_t)r * hist_stride + n] = t;
+                hist_len[r] = n + 1;
+            }
+            const int pos = tok_pos[r] + 1;
+            // ring row = steps since the loop started (from the positions, so every step's launch has the same arguments)
+            argmax_out[r] = t; ring_out[(int64_t)(pos - 1 - ring_pos0[r]) * ring_rows + r] = t; tokens[r] = t;
+            tok_pos[r] = pos; seq_pos[r] = pos;          // (one token per sequence: row r IS sequence r)
+            tok_s = t; pos_s = pos;
+        }
+    }
+    __syncthreads();
+    const int tok = tok_s, pos = pos_s;
+    const bool use_pos = pos_emb && pos < max_seq;
+    float* xr = x + (int64_t)r * H;
+    const int H4 = H >> 2;
+    f32x4 v[NORM_ROW_MAXCH], ww[NORM_ROW_MAXCH], bb[NORM_ROW_MAXCH];
+#pragma unroll
+    for (int c = 0; c < NORM_ROW_MAXCH; c++) {
+        const int j = threadIdx.x + c * 256;
+        v[c] = f32x4{0.f, 0.f, 0.f, 0.f};
+        if (j < H4) {
+            const int k8 = (j * 4) & ~7;                                                   // the fragment of this thread's 4 elements
+            const uint32_t code8 = *(const uint32_t*)(emb + (fm_index(tok, k8, H) >> 1));
+            const uint32_t code4 = code8 >> (16 * (j & 1));                                // its 4 codes in the low 2 bytes
+            const float es = __builtin_bit_cast(float, (uint32_t)escales[w4_scale_index(tok, j >> 3, H >> 5)] << 23);
+            const bf16x2_t lo = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(code4, es, 0), hi = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(code4, es, 1);
+            const bf16x4 e = {lo[0], lo[1], hi[0], hi[1]};                                 // W~ of the 4 gathered codes
+            bf16x4 pe = {};
+            if (use_pos) pe = *(const bf16x4*)(pos_emb + fm_index(pos, j * 4, H));
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                float f = (float)e[k];
+                if (use_pos) f += (float)pe[k];
+                if (mult != 0.f) f *= mult;
+                v[c][k] = f;
+            }
+            *(f32x4*)(xr + j * 4) = v[c];
+            ww[c] = *(const f32x4*)(w + j * 4);
+            if (b) bb[c] = *(const f32x4*)(b + j * 4);
+        }
+    }
+    norm_row_finish<bf16_t>(v, ww, bb, b, eps, y, r, H, red);
+}
+
 // MXFP4 MoE experts (nvl_set_mx_expert_dtype).  The down codes are stored once, in the decode form's
 // layout: [H_pad][E*I/2] bytes, fragment-major with K = E*I (expert e's k-steps e*I/32 .. (e+1)*I/32 - 1 of every 16-row
 // tile), the block scales [H_pad/16][E*I/32][16] over the same K.  moe_cat_down_w4_kernel builds both from the uploaded

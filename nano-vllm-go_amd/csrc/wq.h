@@ -16,14 +16,14 @@ inline int64_t wf_code_bytes(int wf, int64_t elems) { return wf == WF_MXFP4 ? el
 inline int64_t wf_scale_bytes(int wf, int64_t rows, int64_t K) { return wf == WF_MXFP4 ? rows * K / 32 : rows * 4; }
 // the name of the format in error messages
 inline const char* wf_name(int wf) { return wf == WF_MXFP4 ? "MXFP4" : "8-bit"; }
-// does the format cover this 2-D tensor kind (experts: when the expert format `ef` is set too)?  Attention and FFN
-// projections in both; fp8 also the LM head, and the token embedding when it is the (tied) LM head.  Position embedding,
-// router and Mamba2 projections stay bf16.
-inline bool wf_covers(int wf, int ef, int kind, bool tied_embedding) {
+// does the format cover this 2-D tensor kind (experts: when the expert format `ef` is set too; LM head: the head format
+// `hf`)?  Attention and FFN projections in both; the LM head, and the token embedding when it is the (tied) LM head, in
+// fp8 always and in MXFP4 when nvl_set_mx_head_dtype asked for it.  Position embedding, router and Mamba2 projections stay bf16.
+inline bool wf_covers(int wf, int ef, int hf, int kind, bool tied_embedding) {
     switch (kind) {
         case NVL_T_WQ: case NVL_T_WK: case NVL_T_WV: case NVL_T_WKV: case NVL_T_WO: case NVL_T_W1: case NVL_T_W2: return wf != WF_BF16;
-        case NVL_T_LM_HEAD: return wf == WF_FP8;
-        case NVL_T_TOK_EMB: return wf == WF_FP8 && tied_embedding;
+        case NVL_T_LM_HEAD: return wf == WF_FP8 || (wf != WF_BF16 && hf == wf);
+        case NVL_T_TOK_EMB: return (wf == WF_FP8 || (wf != WF_BF16 && hf == wf)) && tied_embedding;
         case NVL_T_MOE_IN: case NVL_T_MOE_OUT: return wf != WF_BF16 && ef == wf;
         default: return false;
     }
@@ -42,8 +42,8 @@ static inline void wf_dequant_rows(hipStream_t st, int wf, const void* codes, co
 
 // The GEMM of a quantized weight (a.W: codes, qs: its scales, w_rows_pad: its allocated rows).  Decode-sized calls go where
 // the bf16 dispatch (launch_gemm_bf16) sends them, on the kernels of format WF; the rest run the bf16 dispatch on W~ in
-// `scratch` (scratch_elems bf16 elements).  fp8 only: with a8 (8-bit activations, a8.h) the tile step is the W8A8 kernel on
-// the codes instead, and a W~ that does not fit runs in row chunks (EPI_STORE with fp32 output only: the LM head).
+// `scratch` (scratch_elems bf16 elements); a W~ that does not fit runs in row chunks (EPI_STORE with fp32 output only: the
+// LM head).  fp8 only: with a8 (8-bit activations, a8.h) the tile step is the W8A8 kernel on the codes instead.
 template <int EPI, typename OutT, int WF>
 static inline void launch_gemm_q(hipStream_t st, const GemmArgs& a, const void* qs, int64_t w_rows_pad, bf16_t* scratch,
                                  int64_t scratch_elems, const A8Buf* a8 = nullptr) {
@@ -79,9 +79,9 @@ static inline void launch_gemm_q(hipStream_t st, const GemmArgs& a, const void* 
         launch_gemm_bf16<EPI, OutT>(st, c);
         return;
     }
-    if constexpr (WF == WF_FP8 && EPI == EPI_STORE && std::is_same<OutT, float>::value) {
+    if constexpr (EPI == EPI_STORE && std::is_same<OutT, float>::value) {
         const int64_t chunk = (scratch_elems / a.K) / W_ROW_PAD * W_ROW_PAD;     // whole padded tiles per chunk
-        if (chunk < W_ROW_PAD) throw std::runtime_error("gemm: the 8-bit weight scratch holds no whole row tile");
+        if (chunk < W_ROW_PAD) throw err(" weight's scratch holds no whole row tile");
         for (int64_t n0 = 0; n0 < a.N; n0 += chunk) {
             const int64_t rows = std::min<int64_t>(chunk, w_rows_pad - n0);
             wf_dequant_rows(st, WF, a.W, qs, a.K, n0, rows, scratch);

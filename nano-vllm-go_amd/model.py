@@ -48,7 +48,7 @@ class HipTransformerModel:
                  tp_force_single: bool = False, kv_num_blocks: int = 0, kv_block_size: int = 0,
                  kv_cache_dtype: str = "auto", kv_scales=None, weight_dtype: str = "auto",
                  act_dtype: str = "auto", expert_dtype: str = "auto", mx_weight_dtype: str = "none",
-                 mx_expert_dtype: str = "none"):
+                 mx_expert_dtype: str = "none", mx_head_dtype: str = "none"):
         """tensors=None defers finalize(): upload() each tensor, then call finalize().
         tp_size > 1 makes this the tp_rank-th tensor-parallel shard: pass the FULL tensors, the library keeps
         its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests).
@@ -64,7 +64,9 @@ class HipTransformerModel:
         (nvl_set_mx_weight_dtype; bf16 precision, no TP, not with weight_dtype="fp8_e4m3"); the LM head, the embeddings and
         the MoE experts stay bf16.  The model computes with W~ = grid[q] * 2^e, which get_weight returns.
         mx_expert_dtype="fp4_e2m1" (needs mx_weight_dtype="fp4_e2m1", a MoE model): the experts' weights are MXFP4 too, one
-        e8m0 scale per 32 input features of an (expert, output row) (nvl_set_mx_expert_dtype)."""
+        e8m0 scale per 32 input features of an (expert, output row) (nvl_set_mx_expert_dtype).
+        mx_head_dtype="fp4_e2m1" (needs mx_weight_dtype="fp4_e2m1"): the LM head, and the token embedding of a tied model, are
+        MXFP4 too, one e8m0 scale per 32 input features of a vocabulary row (nvl_set_mx_head_dtype)."""
         self.cfg = dict(cfg)
         self.lib = L.lib()
         self.h = C.c_void_p()
@@ -98,14 +100,20 @@ class HipTransformerModel:
             raise ValueError(f"mx_expert_dtype must be one of {sorted(L.MX_EXPERT_DTYPE)}")
         if mx_expert_dtype != "none" and mx_weight_dtype != "fp4_e2m1":
             raise ValueError('mx_expert_dtype="fp4_e2m1" needs mx_weight_dtype="fp4_e2m1"')
+        if mx_head_dtype not in L.MX_HEAD_DTYPE:
+            raise ValueError(f"mx_head_dtype must be one of {sorted(L.MX_HEAD_DTYPE)}")
+        if mx_head_dtype != "none" and mx_weight_dtype != "fp4_e2m1":
+            raise ValueError('mx_head_dtype="fp4_e2m1" needs mx_weight_dtype="fp4_e2m1"')
         L.check(self.lib.nvl_create(C.byref(self._c), C.byref(opts), C.byref(self.h)))
         self.weight_dtype = weight_dtype
         self.mx_weight_dtype = mx_weight_dtype
         self.mx_expert_dtype = mx_expert_dtype
+        self.mx_head_dtype = mx_head_dtype
         self.act_dtype = act_dtype
         self.expert_dtype = expert_dtype
         for setter, table, value in ((self.lib.nvl_set_mx_weight_dtype, L.MX_WEIGHT_DTYPE, mx_weight_dtype),
                                      (self.lib.nvl_set_mx_expert_dtype, L.MX_EXPERT_DTYPE, mx_expert_dtype),
+                                     (self.lib.nvl_set_mx_head_dtype, L.MX_HEAD_DTYPE, mx_head_dtype),
                                      (self.lib.nvl_set_weight_dtype, L.WEIGHT_DTYPE, weight_dtype),
                                      (self.lib.nvl_set_expert_dtype, L.EXPERT_DTYPE, expert_dtype),
                                      (self.lib.nvl_set_act_dtype, L.ACT_DTYPE, act_dtype)):
@@ -210,7 +218,8 @@ class HipTransformerModel:
 
     def upload_mxfp4(self, slot: str, layer: int, codes, scales):
         """nvl_upload_tensor_mxfp4: pre-quantized codes [out][in/2] (even k in the low nibble) and e8m0 scales [out][in/32];
-        with mx_expert_dtype="fp4_e2m1" also moe_in / moe_out, as [E * out][in/2] and [E * out][in/32]"""
+        with mx_expert_dtype="fp4_e2m1" also moe_in / moe_out, as [E * out][in/2] and [E * out][in/32]; with
+        mx_head_dtype="fp4_e2m1" also lm_head, and tok_emb of a tied model, as [vocab][hidden/2] and [vocab][hidden/32]"""
         codes = np.ascontiguousarray(codes, np.uint8)
         scales = np.ascontiguousarray(scales, np.uint8)
         L.check(self.lib.nvl_upload_tensor_mxfp4(self.h, L.SLOT_ID[slot], int(layer), codes.ctypes.data_as(C.c_void_p),

@@ -44,6 +44,7 @@ type Options struct {
 	ActDType       int  // C.NVL_ACT_AUTO (0) or C.NVL_ACT_FP8_E4M3 (1): W8A8 prefill projections (needs WeightDType 1)
 	MXWeightDType  int  // C.NVL_MX_NONE (0) or C.NVL_MX_FP4_E2M1 (1): MXFP4 projection weights (not with WeightDType 1)
 	MXExpertDType  int  // C.NVL_MXE_NONE (0) or C.NVL_MXE_FP4_E2M1 (1): MXFP4 MoE expert weights (needs MXWeightDType 1)
+	MXHeadDType    int  // C.NVL_MXH_NONE (0) or C.NVL_MXH_FP4_E2M1 (1): MXFP4 LM head / tied embedding (needs MXWeightDType 1)
 	ExpertDType    int  // C.NVL_EXPERT_AUTO (0) or C.NVL_EXPERT_FP8_E4M3 (1): 8-bit MoE expert weights (needs WeightDType 1)
 }
 
@@ -339,6 +340,13 @@ func create(cfg *C.nvl_model_config, o Options) (*HipModelRunner, error) {
 	if o.MXWeightDType != 0 { // before the weights are uploaded (nvl_set_mx_weight_dtype)
 		if rc := C.nvl_set_mx_weight_dtype(r.h, C.int(o.MXWeightDType)); rc != 0 {
 			err := fmt.Errorf("nvl_set_mx_weight_dtype: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
+			C.nvl_destroy(r.h)
+			return nil, err
+		}
+	}
+	if o.MXHeadDType != 0 { // after the MX weight dtype, before the first 2-D upload (nvl_set_mx_head_dtype)
+		if rc := C.nvl_set_mx_head_dtype(r.h, C.int(o.MXHeadDType)); rc != 0 {
+			err := fmt.Errorf("nvl_set_mx_head_dtype: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
 			C.nvl_destroy(r.h)
 			return nil, err
 		}
