@@ -127,6 +127,178 @@ __device__ __forceinline__ float rows_max(float x) {
 }
 
 // ------------------------------------------------------------------------------------------
+// Tile arithmetic shared by the bf16 kernels below and the kernels over an 8-bit cache (kv8.h).  Those differ in how a
+// K / V tile reaches registers or its bf16 LDS image and in two scale factors (k_scale inside sl2, v_scale as `osc`);
+// everything from the images on is written once, here.  All pieces work on the calling kernel's own register arrays.
+// ------------------------------------------------------------------------------------------
+// fragment read offsets of lane (fq, fg), bytes inside a K / V image.  K: chunk 4 ks + fg of row fq (+ 16 t rows);
+// V: row 4 fg + fq / 4 (+ 32 u, + 16), 32-byte segment d, half fq & 1 (ds_read_b64_tr_b16: 4 rows x 16 columns per 16 lanes)
+template <int HD> __device__ __forceinline__ int attn_k_off(int fq, int fg, int ks) { return 16 * kv_img_chunk<HD>(fq, ks * 4 + fg); }
+template <int HD> __device__ __forceinline__ int attn_v_off(int fq, int fg, int d) {
+    const int q4 = fq >> 2, p4 = fq & 3;
+    return 16 * kv_img_chunk<HD>(4 * fg + q4, 2 * d + (p4 >> 1)) + 8 * (p4 & 1);
+}
+
+// O^T += V^T · P^T of one 64-key tile for TQ query sub-tiles (decode: 1, prefill: 2): the V^T operand comes out of the
+// row-major V image by transposed LDS reads; the k index (keys 32u + 4fg + r, then 32u + 16 + 4fg + r) is permuted
+// identically on both operands.  s[qi] holds P^T (fp32, lane = S^T[key = 16t + 4fg + r][q = fq]).
+// ROWSUM (prefill): the row sums of P (as rounded for the product) ride the MFMA pipe too, ones · P^T into lacc: 32 f32
+// adds less per tile on the vector ALU, which is the busier unit there.
+template <int HD, int TQ, bool ROWSUM>
+__device__ __forceinline__ void attn_pv_tile(const char* vimg, const int (&v_off)[HD / 16], const f32x4 (*s)[4], f32x4 (*o)[HD / 16], f32x4* lacc) {
+    constexpr int DT = HD / 16, CPR = HD / 8;
+#pragma unroll
+    for (int u = 0; u < 2; u++) {
+        bf16x8 pf[TQ];
+#pragma unroll
+        for (int qi = 0; qi < TQ; qi++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                pf[qi][r] = (bf16_t)s[qi][2 * u][r];          // keys 32u + 4fg + r
+                pf[qi][4 + r] = (bf16_t)s[qi][2 * u + 1][r];  // keys 32u + 16 + 4fg + r
+            }
+#pragma unroll
+        for (int d = 0; d < DT; d++) {
+            const bf16x4 lo = lds_read_tr4(vimg + v_off[d] + u * (32 * CPR * 16));
+            const bf16x4 hi = lds_read_tr4(vimg + v_off[d] + u * (32 * CPR * 16) + 16 * CPR * 16);
+            bf16x8 vf;
+#pragma unroll
+            for (int r = 0; r < 4; r++) { vf[r] = lo[r]; vf[4 + r] = hi[r]; }
+#pragma unroll
+            for (int qi = 0; qi < TQ; qi++)
+                o[qi][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qi], o[qi][d], 0, 0, 0);
+        }
+        if constexpr (ROWSUM) {
+            bf16x8 ones;
+#pragma unroll
+            for (int r = 0; r < 8; r++) ones[r] = (bf16_t)1.0f;
+#pragma unroll
+            for (int qi = 0; qi < TQ; qi++)
+                lacc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[qi], lacc[qi], 0, 0, 0);
+        }
+    }
+}
+
+// ---- prefill: one workgroup = 8 waves = PF_QROWS query rows of one (sequence, kv head), PF_TQ 16-row sub-tiles per wave ----
+constexpr int PF_TQ = 2, PF_QROWS = 256;
+// where a wave's rows are: filled once by the kernel, read by the pieces below
+struct AttnPrefillRows {
+    int qt, wave, fq, fg;       // query tile of the workgroup, wave, MFMA role of the lane
+    int R;                      // query rows of this (seq, kv head)
+    int tok0, pos0, kvh;
+    // this lane's query row of sub-tile qi (one per sub-tile); position and head are re-derived where needed (registers)
+    __device__ __forceinline__ int row_of(int qi, bool& ok) const {
+        int row = qt * PF_QROWS + (wave * PF_TQ + qi) * 16 + fq;
+        ok = row < R;
+        return ok ? row : qt * PF_QROWS;          // clamp to a valid row; result discarded
+    }
+};
+// the lane's Q fragments, and qpos: the position of each of its rows = the last key the row may see (kept for the tiles'
+// masks: re-deriving it there is an integer division per sub-tile and diagonal tile)
+template <int HD>
+__device__ __forceinline__ void attn_prefill_load_q(const AttnArgs& p, const AttnPrefillRows& w, bf16x8 (&qf)[PF_TQ][HD / 32], int (&qpos)[PF_TQ]) {
+#pragma unroll
+    for (int qi = 0; qi < PF_TQ; qi++) {
+        bool ok;
+        const int row = w.row_of(qi, ok), si = row / p.group, hd_ = w.kvh * p.group + (row - si * p.group);
+        qpos[qi] = w.pos0 + si;
+        const bf16_t* qp = (const bf16_t*)p.q + (int64_t)(w.tok0 + si) * p.q_stride + hd_ * HD;
+#pragma unroll
+        for (int ks = 0; ks < HD / 32; ks++) qf[qi][ks] = *(const bf16x8*)(qp + ks * 32 + w.fg * 8);
+    }
+}
+// key tiles of the workgroup, of this WAVE (up to its last valid row's causal limit; none when the wave has no valid row),
+// and the last key every row of the wave sees (tiles wholly below it need no masking)
+__device__ __forceinline__ void attn_prefill_setup(const AttnArgs& p, const AttnPrefillRows& w, int& n_kt, int& wave_n_kt, int& wave_first_limit) {
+    int last_row = w.qt * PF_QROWS + PF_QROWS - 1;
+    if (last_row > w.R - 1) last_row = w.R - 1;
+    n_kt = (w.pos0 + last_row / p.group) / 64 + 1;
+    const int w_row0 = w.qt * PF_QROWS + w.wave * 32;
+    int w_last = w_row0 + 31;
+    if (w_last > w.R - 1) w_last = w.R - 1;
+    wave_n_kt = w_row0 < w.R ? (w.pos0 + w_last / p.group) / 64 + 1 : 0;
+    wave_first_limit = w.pos0 + w_row0 / p.group;
+}
+// one 64-key tile from its LDS images: scores, causal mask (qpos: the last key each of the lane's rows may see), online
+// softmax, O^T += V^T · P^T
+template <int HD>
+__device__ __forceinline__ void attn_prefill_tile(int fg, const int (&qpos)[PF_TQ], int kt, int wave_first_limit, float sl2,
+                                                  const char* kimg, const char* vimg, const int (&k_off)[HD / 32], const int (&v_off)[HD / 16],
+                                                  const bf16x8 (&qf)[PF_TQ][HD / 32], f32x4 (&o)[PF_TQ][HD / 16], f32x4 (&lacc)[PF_TQ], float (&m_run)[PF_TQ]) {
+    constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, TQ = PF_TQ;
+    // ---- S^T = K · Q^T : 4 sub-tiles of 16 keys, each K fragment used for both query sub-tiles ----
+    f32x4 s[TQ][4];
+#pragma unroll
+    for (int qi = 0; qi < TQ; qi++)
+#pragma unroll
+        for (int t = 0; t < 4; t++) s[qi][t] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int t = 0; t < 4; t++)
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) {
+            const bf16x8 kf = *(const bf16x8*)(kimg + k_off[ks] + t * (16 * CPR * 16));
+#pragma unroll
+            for (int qi = 0; qi < TQ; qi++)
+                s[qi][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qi][ks], s[qi][t], 0, 0, 0);
+        }
+    // lane holds S^T[key = kt*64 + 16t + 4fg + r][q = fq] per sub-tile
+    const bool whole = kt * 64 + 63 <= wave_first_limit;      // every row of the wave sees the whole tile
+    if (!whole) {                                             // a tile on the causal diagonal
+#pragma unroll
+        for (int qi = 0; qi < TQ; qi++) {
+            const int lim = qpos[qi] - kt * 64 - fg * 4;      // last key (tile-relative) this row may see
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+#pragma unroll
+                for (int r = 0; r < 4; r++)
+                    s[qi][t][r] = (t * 16 + r <= lim) ? s[qi][t][r] : -INFINITY;  // reference: -1e10 then exp() == 0 exactly
+        }
+    }
+    // scores stay RAW; the softmax scale (sl2 > 0: checked by the host) is folded into the exponent's fma:
+    // p = exp2(s * sl2 - m), m = running max of s * sl2 (finite from the first tile on: key 0 <= limit)
+    float m_new[TQ];
+    bool moved = false;
+#pragma unroll
+    for (int qi = 0; qi < TQ; qi++) {
+        const float tmax = rows_max(vmax16(s[qi][0], s[qi][1], s[qi][2], s[qi][3]));
+        m_new[qi] = vmax2(m_run[qi], tmax * sl2);
+        moved |= m_new[qi] != m_run[qi];
+    }
+    if (__any(moved)) {                                       // the running maximum moved for some row: rescale
+#pragma unroll
+        for (int qi = 0; qi < TQ; qi++) {
+            const float alpha = __builtin_amdgcn_exp2f(m_run[qi] - m_new[qi]);
+            lacc[qi] *= alpha;
+#pragma unroll
+            for (int d = 0; d < DT; d++) o[qi][d] *= alpha;
+            m_run[qi] = m_new[qi];
+        }
+    }
+#pragma unroll
+    for (int qi = 0; qi < TQ; qi++)
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) s[qi][t][r] = __builtin_amdgcn_exp2f(fmaf(s[qi][t][r], sl2, -m_new[qi]));
+    attn_pv_tile<HD, TQ, true>(vimg, v_off, s, o, lacc);
+}
+// normalise (osc / l: osc = 1, or the v_scale of an 8-bit cache) and store
+template <int HD>
+__device__ __forceinline__ void attn_prefill_store(const AttnArgs& p, const AttnPrefillRows& w, const f32x4 (&o)[PF_TQ][HD / 16], const f32x4 (&lacc)[PF_TQ], float osc) {
+#pragma unroll
+    for (int qi = 0; qi < PF_TQ; qi++) {
+        const float l = lacc[qi][0];
+        bool ok;
+        const int row = w.row_of(qi, ok), si = row / p.group, hd_ = w.kvh * p.group + (row - si * p.group);
+        if (!ok) continue;
+        const float inv = osc / l;
+#pragma unroll
+        for (int d = 0; d < HD / 16; d++)    // O[q][d = 16d + 4fg + r], written in the next GEMM's operand layout
+            act_store4<bf16_t>((bf16_t*)p.out, w.tok0 + si, hd_ * HD + d * 16 + w.fg * 4, p.out_stride, o[qi][d] * inv);
+    }
+}
+
+// ------------------------------------------------------------------------------------------
 // bf16 prefill kernel.  One workgroup = 8 waves = 256 query rows of one (sequence, kv head); each wave owns 32 rows as
 // two 16-row sub-tiles, so every K / V fragment read from LDS feeds two MFMAs.  K and V tiles (64 keys) stream
 // HBM -> LDS by LDS-DMA through a 3-slot ring, two tiles ahead of the compute, with ONE barrier per tile:
@@ -137,9 +309,8 @@ __device__ __forceinline__ float rows_max(float x) {
 // ------------------------------------------------------------------------------------------
 template <int HD>
 __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_kernel(AttnArgs p) {
-    constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, TQ = 2;
+    constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, TQ = PF_TQ, QROWS = PF_QROWS;
     constexpr int TILE_BYTES = 64 * HD * 2, PIECES = TILE_BYTES / 1024, PW = 2 * PIECES / 8, NBUF = 3;
-    constexpr int QROWS = 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];     // NBUF x [K image | V image]
     __shared__ int32_t sblk[128];          // this sequence's block table (<= 128 blocks: host-checked)
 
@@ -163,21 +334,10 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_kerne
     // also waits for the DMA issued a moment ago and serialises the whole ring (measured: 4200 cycles per tile instead of ~1300)
     if (tid < p.tbl_stride && tid < 128) sblk[tid] = tbl[tid];
 
-    // ---- this lane's query rows (one per sub-tile); position and head are re-derived where needed (registers) ----
+    const AttnPrefillRows w{qt, wave, fq, fg, R, tok0, pos0, kvh};
     bf16x8 qf[TQ][KS];
-    auto row_of = [&](int qi, bool& ok) {
-        int row = qt * QROWS + (wave * TQ + qi) * 16 + fq;
-        ok = row < R;
-        return ok ? row : qt * QROWS;          // clamp to a valid row; result discarded
-    };
-#pragma unroll
-    for (int qi = 0; qi < TQ; qi++) {
-        bool ok;
-        const int row = row_of(qi, ok), si = row / p.group, hd_ = kvh * p.group + (row - si * p.group);
-        const bf16_t* qp = (const bf16_t*)p.q + (int64_t)(tok0 + si) * p.q_stride + hd_ * HD;
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) qf[qi][ks] = *(const bf16x8*)(qp + ks * 32 + fg * 8);
-    }
+    int qpos[TQ];
+    attn_prefill_load_q<HD>(p, w, qf, qpos);
     // the Q fragments are complete before the first DMA is issued (an empty asm that "rewrites" them: the compiler waits
     // here, once, and no register is pending on a vector load when the loop starts)
 #pragma unroll
@@ -185,15 +345,8 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_kerne
 #pragma unroll
         for (int ks = 0; ks < KS; ks++) asm volatile("" : "+v"(qf[qi][ks]));
     __syncthreads();                      // sblk is visible
-    int last_row = qt * QROWS + QROWS - 1;
-    if (last_row > R - 1) last_row = R - 1;
-    const int n_kt = (pos0 + last_row / p.group) / 64 + 1;
-    // key tiles this WAVE needs: up to its last valid row's causal limit (none when the wave has no valid row)
-    const int w_row0 = qt * QROWS + wave * 32;
-    int w_last = w_row0 + 31;
-    if (w_last > R - 1) w_last = R - 1;
-    const int wave_n_kt = w_row0 < R ? (pos0 + w_last / p.group) / 64 + 1 : 0;
-    const int wave_first_limit = pos0 + w_row0 / p.group;     // tiles wholly below it need no masking
+    int n_kt, wave_n_kt, wave_first_limit;
+    attn_prefill_setup(p, w, n_kt, wave_n_kt, wave_first_limit);
 
     // ---- LDS-DMA: wave w moves pieces w*PW .. w*PW+PW-1 of each tile's [K pieces | V pieces] list ----
     int src_off[PW];                 // element offset of this lane's 16 bytes inside the (K or V) tile
@@ -218,25 +371,14 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_kerne
         }
     };
 
-    // ---- fragment read offsets (bytes inside a K / V image) ----
-    int k_off[KS];                    // row 16t + fq: + t * 16 rows
+    int k_off[KS], v_off[DT];         // fragment read offsets (bytes inside a K / V image)
 #pragma unroll
-    for (int ks = 0; ks < KS; ks++) k_off[ks] = 16 * kv_img_chunk<HD>(fq, ks * 4 + fg);
-    const int q4 = fq >> 2, p4 = fq & 3;
-    int v_off[DT];                    // row 4 fg + q4 (+ 32 u, + 16): 32-byte segment d, half p4 & 1
+    for (int ks = 0; ks < KS; ks++) k_off[ks] = attn_k_off<HD>(fq, fg, ks);
 #pragma unroll
-    for (int d = 0; d < DT; d++) v_off[d] = 16 * kv_img_chunk<HD>(4 * fg + q4, 2 * d + (p4 >> 1)) + 8 * (p4 & 1);
-
-    f32x4 o[TQ][DT];
-    f32x4 lacc[TQ];                   // softmax denominators out of the MFMA pipe: ones · P^T, every row the complete sum
-    float m_run[TQ];
-#pragma unroll
-    for (int qi = 0; qi < TQ; qi++) {
-        m_run[qi] = -INFINITY;
-        lacc[qi] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int d = 0; d < DT; d++) o[qi][d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    }
+    for (int d = 0; d < DT; d++) v_off[d] = attn_v_off<HD>(fq, fg, d);
+    f32x4 o[TQ][DT] = {};
+    f32x4 lacc[TQ] = {};              // softmax denominators out of the MFMA pipe: ones · P^T, every row the complete sum
+    float m_run[TQ] = {-INFINITY, -INFINITY};
     const float sl2 = p.scale * 1.4426950408889634f;     // exp2 domain
 
     issue(0, 0);
@@ -257,107 +399,9 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_kerne
         buf = buf + 1 == NBUF ? 0 : buf + 1;
         if (kt >= wave_n_kt) continue;                   // (wave-uniform) every row of this wave is masked out here
 
-        // ---- S^T = K · Q^T : 4 sub-tiles of 16 keys, each K fragment used for both query sub-tiles ----
-        f32x4 s[TQ][4];
-#pragma unroll
-        for (int qi = 0; qi < TQ; qi++)
-#pragma unroll
-            for (int t = 0; t < 4; t++) s[qi][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-#pragma unroll
-            for (int ks = 0; ks < KS; ks++) {
-                const bf16x8 kf = *(const bf16x8*)(kimg + k_off[ks] + t * (16 * CPR * 16));
-#pragma unroll
-                for (int qi = 0; qi < TQ; qi++)
-                    s[qi][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qi][ks], s[qi][t], 0, 0, 0);
-            }
-        // lane holds S^T[key = kt*64 + 16t + 4fg + r][q = fq] per sub-tile
-        const bool whole = kt * 64 + 63 <= wave_first_limit;      // every row of the wave sees the whole tile
-        if (!whole) {                                             // a tile on the causal diagonal
-#pragma unroll
-            for (int qi = 0; qi < TQ; qi++) {
-                bool ok;
-                const int lim = pos0 + row_of(qi, ok) / p.group - kt * 64 - fg * 4;   // last key (tile-relative) this row may see
-#pragma unroll
-                for (int t = 0; t < 4; t++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++)
-                        s[qi][t][r] = (t * 16 + r <= lim) ? s[qi][t][r] : -INFINITY;  // reference: -1e10 then exp() == 0 exactly
-            }
-        }
-        // scores stay RAW; the softmax scale (sl2 > 0: checked by the host) is folded into the exponent's fma:
-        // p = exp2(s * sl2 - m), m = running max of s * sl2 (finite from the first tile on: key 0 <= limit)
-        float m_new[TQ];
-        bool moved = false;
-#pragma unroll
-        for (int qi = 0; qi < TQ; qi++) {
-            const float tmax = rows_max(vmax16(s[qi][0], s[qi][1], s[qi][2], s[qi][3]));
-            m_new[qi] = vmax2(m_run[qi], tmax * sl2);
-            moved |= m_new[qi] != m_run[qi];
-        }
-        if (__any(moved)) {                                       // the running maximum moved for some row: rescale
-#pragma unroll
-            for (int qi = 0; qi < TQ; qi++) {
-                const float alpha = __builtin_amdgcn_exp2f(m_run[qi] - m_new[qi]);
-                lacc[qi] *= alpha;
-#pragma unroll
-                for (int d = 0; d < DT; d++) o[qi][d] *= alpha;
-                m_run[qi] = m_new[qi];
-            }
-        }
-#pragma unroll
-        for (int qi = 0; qi < TQ; qi++)
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) s[qi][t][r] = __builtin_amdgcn_exp2f(fmaf(s[qi][t][r], sl2, -m_new[qi]));
-
-        // ---- O^T += V^T · P^T : the V^T operand comes out of the row-major V image by transposed LDS reads; the k index
-        // (keys 32u + 4fg + r, then 32u + 16 + 4fg + r) is permuted identically on both operands ----
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            bf16x8 pf[TQ];
-#pragma unroll
-            for (int qi = 0; qi < TQ; qi++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    pf[qi][r] = (bf16_t)s[qi][2 * u][r];          // keys 32u + 4fg + r
-                    pf[qi][4 + r] = (bf16_t)s[qi][2 * u + 1][r];  // keys 32u + 16 + 4fg + r
-                }
-#pragma unroll
-            for (int d = 0; d < DT; d++) {
-                const bf16x4 lo = lds_read_tr4(vimg + v_off[d] + u * (32 * CPR * 16));
-                const bf16x4 hi = lds_read_tr4(vimg + v_off[d] + u * (32 * CPR * 16) + 16 * CPR * 16);
-                bf16x8 vf;
-#pragma unroll
-                for (int r = 0; r < 4; r++) { vf[r] = lo[r]; vf[4 + r] = hi[r]; }
-#pragma unroll
-                for (int qi = 0; qi < TQ; qi++)
-                    o[qi][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qi], o[qi][d], 0, 0, 0);
-            }
-            // the row sums of P (as rounded for the product above) ride the MFMA pipe too: 32 f32 adds less per tile on
-            // the vector ALU, which is the busier unit here
-            bf16x8 ones;
-#pragma unroll
-            for (int r = 0; r < 8; r++) ones[r] = (bf16_t)1.0f;
-#pragma unroll
-            for (int qi = 0; qi < TQ; qi++)
-                lacc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[qi], lacc[qi], 0, 0, 0);
-        }
+        attn_prefill_tile<HD>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run);
     }
-
-#pragma unroll
-    for (int qi = 0; qi < TQ; qi++) {
-        const float l = lacc[qi][0];
-        bool ok;
-        const int row = row_of(qi, ok), si = row / p.group, hd_ = kvh * p.group + (row - si * p.group);
-        if (!ok) continue;
-        const float inv = 1.0f / l;
-#pragma unroll
-        for (int d = 0; d < DT; d++)    // O[q][d = 16d + 4fg + r], written in the next GEMM's operand layout
-            act_store4<bf16_t>((bf16_t*)p.out, tok0 + si, hd_ * HD + d * 16 + fg * 4, p.out_stride, o[qi][d] * inv);
-    }
+    attn_prefill_store<HD>(p, w, o, lacc, 1.0f);
 }
 template <int HD> constexpr int attn_prefill_lds_bytes() { return 3 * 2 * 64 * HD * 2; }
 
@@ -415,10 +459,37 @@ __device__ __forceinline__ void rope_math8(const RopeRaw& r, bool rot, bf16x8& l
     }
 }
 
+// The softmax step of a decode round, from the round's masked, scaled scores s (exp2 domain) and their lane maximum tmax:
+// the new running maximum and denominator, s -> P^T, and the rescale of O^T.
+template <int HD, int NT2>
+__device__ __forceinline__ void attn_decode_softmax(f32x4 (&s)[NT2][4], float tmax, float& m_run, float& l_run, f32x4 (&o)[HD / 16]) {
+    constexpr int DT = HD / 16;
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
+    tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
+    const float m_new = fmaxf(m_run, tmax);     // finite: the round's first tile kt0 < n_kt holds key kt0*64 <= pos0
+    const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
+    float psum = 0.f;
+#pragma unroll
+    for (int h = 0; h < NT2; h++)
+#pragma unroll
+        for (int t = 0; t < 4; t++)
+#pragma unroll
+            for (int r = 0; r < 4; r++) {
+                const float pv = __builtin_amdgcn_exp2f(s[h][t][r] - m_new);
+                s[h][t][r] = pv;
+                psum += pv;
+            }
+    l_run = l_run * alpha + psum;
+    m_run = m_new;
+#pragma unroll
+    for (int d = 0; d < DT; d++) o[d] *= alpha;
+}
+
 // combine of a split decode launch: the nsplit partial results of one (sequence, kv head, query tile), in workgroup order
 // whichever workgroup runs it.  One wave, the lanes of real heads; lane (fq, fg) as in the kernel's own combine.
+// osc: the output scale (1, or the v_scale of an 8-bit cache: kv8.h).
 template <int HD>
-__device__ __forceinline__ void attn_decode_merge(const AttnArgs& p, int pair, int tok, int head, int nsplit, int lane) {
+__device__ __forceinline__ void attn_decode_merge(const AttnArgs& p, int pair, int tok, int head, int nsplit, int lane, float osc) {
     constexpr int DT = HD / 16;
     const int fq = lane & 15, fg = lane >> 4;
     const float* rec0 = p.part + (int64_t)pair * nsplit * attn_part_floats<HD>();
@@ -437,7 +508,85 @@ __device__ __forceinline__ void attn_decode_merge(const AttnArgs& p, int pair, i
 #pragma unroll
         for (int d = 0; d < DT; d++) O[d] += ((const f32x4*)rec)[d * 64 + lane] * sc;
     }
-    const float inv = 1.0f / L;
+    const float inv = osc / L;
+#pragma unroll
+    for (int d = 0; d < DT; d++)
+        act_store4<bf16_t>((bf16_t*)p.out, tok, head * HD + d * 16 + fg * 4, p.out_stride, O[d] * inv);
+}
+
+// The end of a decode kernel: flash-decoding combine of the NW waves' partial results through LDS (the partial O^T
+// overwrites each wave's own V image), fixed wave order; with gridDim.z > 1 the workgroup's record, the ticket and the
+// last arriver's merge.  osc as in attn_decode_merge; stamps: the diagnostic instantiation's (NvlStampsT<false> is empty).
+template <int HD, int NW, typename Stamps>
+__device__ __forceinline__ void attn_decode_finish(const AttnArgs& p, char* smem, char* vimg, float (&red_m)[NW][16], float (&red_l)[NW][16],
+                                                   const f32x4 (&o)[HD / 16], float m_run, float l_run, int seq, int tok, int head, bool row_ok,
+                                                   int wave, int lane, int fq, int fg, float osc, Stamps& stamps) {
+    constexpr int DT = HD / 16, TILE_BYTES = 64 * HD * 2;
+    l_run += __shfl_xor(l_run, 16, 64);
+    l_run += __shfl_xor(l_run, 32, 64);
+    if (fg == 0) { red_m[wave][fq] = m_run; red_l[wave][fq] = l_run; }
+    f32x4* my_o = (f32x4*)vimg;                              // [DT][64 lanes]
+#pragma unroll
+    for (int d = 0; d < DT; d++) my_o[d * 64 + lane] = o[d];
+    __syncthreads();
+    stamps.mark(4);                     // every wave's tiles done
+    if (gridDim.z == 1 && NW >= DT) {
+        // whole (sequence, kv head) in this workgroup: wave d combines output block d (same sums, same order as below;
+        // one wave doing all DT blocks: B = 32 33.55 K -> 33.80 K decode tok/s, B = 8 +0.9 %, same-box A/B)
+        if (wave >= DT || !row_ok) return;
+        float ms = red_m[0][fq];
+#pragma unroll
+        for (int w = 1; w < NW; w++) ms = fmaxf(ms, red_m[w][fq]);
+        float Ls = 0.f;
+        f32x4 Od = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            const float sc = __builtin_amdgcn_exp2f(red_m[w][fq] - ms);
+            Ls += red_l[w][fq] * sc;
+            Od += ((const f32x4*)(smem + w * TILE_BYTES))[wave * 64 + lane] * sc;
+        }
+        act_store4<bf16_t>((bf16_t*)p.out, tok, head * HD + wave * 16 + fg * 4, p.out_stride, Od * (osc / Ls));
+        return;
+    }
+    if (wave != 0 || !row_ok) return;
+    float mstar = red_m[0][fq];
+#pragma unroll
+    for (int w = 1; w < NW; w++) mstar = fmaxf(mstar, red_m[w][fq]);
+    float L = 0.f;
+    f32x4 O[DT];
+#pragma unroll
+    for (int d = 0; d < DT; d++) O[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    if (mstar > -INFINITY) {       // (a workgroup of a split launch may have had no tile at all)
+#pragma unroll
+        for (int w = 0; w < NW; w++) {
+            const float sc = __builtin_amdgcn_exp2f(red_m[w][fq] - mstar);   // idle waves: exp2(-inf) = 0
+            L += red_l[w][fq] * sc;
+            const f32x4* wo = (const f32x4*)(smem + w * TILE_BYTES);
+#pragma unroll
+            for (int d = 0; d < DT; d++) O[d] += wo[d * 64 + lane] * sc;
+        }
+    }
+    if (gridDim.z > 1) {
+        const int pair = seq * gridDim.x + blockIdx.x;               // (sequence, kv head, query tile)
+        float* rec = p.part + ((int64_t)pair * gridDim.z + blockIdx.z) * attn_part_floats<HD>();
+#pragma unroll
+        for (int d = 0; d < DT; d++) ((f32x4*)rec)[d * 64 + lane] = O[d];
+        if (fg == 0) { rec[DT * 256 + fq] = mstar; rec[DT * 256 + 16 + fq] = L; }
+        // Last arriver combines (no second launch: a merge kernel cost 5-7 us of the 8-11 the split saves).  Release my
+        // record device-wide (the workgroups of a pair may sit on different XCDs, whose L2s are not coherent), draw a
+        // ticket, and if it is the last one acquire the others' records.  The order of the sum is z order regardless.
+        __threadfence();
+        int ticket = 0;
+        int32_t* cnt = p.part_cnt + pair;
+        if (lane == 0) ticket = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ticket = __builtin_amdgcn_readfirstlane(ticket);
+        if (ticket != (int)gridDim.z - 1) return;
+        __threadfence();
+        attn_decode_merge<HD>(p, pair, tok, head, gridDim.z, lane, osc);
+        if (lane == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // for the next launch
+        return;
+    }
+    const float inv = osc / L;
 #pragma unroll
     for (int d = 0; d < DT; d++)
         act_store4<bf16_t>((bf16_t*)p.out, tok, head * HD + d * 16 + fg * 4, p.out_stride, O[d] * inv);
@@ -502,10 +651,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t
     // LDS offsets: where this lane's V chunks go (row i*KPI + ksub, chunk dch) and where its transposed reads come from
     // (row i*KPI + ksub: the swizzle pattern only depends on i & 1, so two bases + compile-time row offsets)
     const int w_base[2] = {16 * kv_img_chunk<HD>(ksub, dch), 16 * kv_img_chunk<HD>(KPI + ksub, dch) - 16 * KPI * CPR};
-    const int q4 = fq >> 2, p4 = fq & 3;
     int v_off[DT];
 #pragma unroll
-    for (int d = 0; d < DT; d++) v_off[d] = 16 * kv_img_chunk<HD>(4 * fg + q4, 2 * d + (p4 >> 1)) + 8 * (p4 & 1);
+    for (int d = 0; d < DT; d++) v_off[d] = attn_v_off<HD>(fq, fg, d);
 
     bf16x8 kf[NT2][4][KS];
     bf16x8 vch[NT2][NVL];
@@ -646,25 +794,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t
                 s[h][t] = acc;
             }
         }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float m_new = fmaxf(m_run, tmax);     // finite: the round's first tile kt0 < n_kt holds key kt0*64 <= pos0
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int h = 0; h < NT2; h++)
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const float pv = __builtin_amdgcn_exp2f(s[h][t][r] - m_new);
-                    s[h][t][r] = pv;
-                    psum += pv;
-                }
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int d = 0; d < DT; d++) o[d] *= alpha;
+        attn_decode_softmax<HD, NT2>(s, tmax, m_run, l_run, o);
         // ---- O^T += V^T · P^T: the tile's V rows go through this wave's LDS image and come back as the transposed
         // MFMA operand (ds_read_b64_tr_b16); a wave's LDS accesses execute in order, so no barrier ----
 #pragma unroll
@@ -672,21 +802,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t
             if (kt0 + h * nvw >= n_kt) continue;
 #pragma unroll
             for (int i = 0; i < NVL; i++) *(bf16x8*)(vimg + w_base[i & 1] + i * (16 * KPI * CPR)) = vch[h][i];
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                bf16x8 pf;
-#pragma unroll
-                for (int r = 0; r < 4; r++) { pf[r] = (bf16_t)s[h][2 * u][r]; pf[4 + r] = (bf16_t)s[h][2 * u + 1][r]; }
-#pragma unroll
-                for (int d = 0; d < DT; d++) {
-                    const bf16x4 lo = lds_read_tr4(vimg + v_off[d] + u * (32 * CPR * 16));
-                    const bf16x4 hi = lds_read_tr4(vimg + v_off[d] + u * (32 * CPR * 16) + 16 * CPR * 16);
-                    bf16x8 vf;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) { vf[r] = lo[r]; vf[4 + r] = hi[r]; }
-                    o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[d], 0, 0, 0);
-                }
-            }
+            attn_pv_tile<HD, 1, false>(vimg, v_off, &s[h], &o, nullptr);
         }
     };
     if (vw < n_kt) do_round(vw);
@@ -709,74 +825,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t
     }
     // ---- flash-decoding combine through LDS (the partial O^T overwrites this wave's own V image), fixed wave order ----
     stamps.mark_used(3, o[0]);          // wave 0's tiles done
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
-    if (fg == 0) { red_m[wave][fq] = m_run; red_l[wave][fq] = l_run; }
-    f32x4* my_o = (f32x4*)vimg;                              // [DT][64 lanes]
-#pragma unroll
-    for (int d = 0; d < DT; d++) my_o[d * 64 + lane] = o[d];
-    __syncthreads();
-    stamps.mark(4);                     // every wave's tiles done
-    if (gridDim.z == 1 && NW >= DT) {
-        // whole (sequence, kv head) in this workgroup: wave d combines output block d (same sums, same order as below;
-        // one wave doing all DT blocks: B = 32 33.55 K -> 33.80 K decode tok/s, B = 8 +0.9 %, same-box A/B)
-        if (wave >= DT || !row_ok) return;
-        float ms = red_m[0][fq];
-#pragma unroll
-        for (int w = 1; w < NW; w++) ms = fmaxf(ms, red_m[w][fq]);
-        float Ls = 0.f;
-        f32x4 Od = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int w = 0; w < NW; w++) {
-            const float sc = __builtin_amdgcn_exp2f(red_m[w][fq] - ms);
-            Ls += red_l[w][fq] * sc;
-            Od += ((const f32x4*)(smem + w * TILE_BYTES))[wave * 64 + lane] * sc;
-        }
-        act_store4<bf16_t>((bf16_t*)p.out, tok, head * HD + wave * 16 + fg * 4, p.out_stride, Od * (1.0f / Ls));
-        return;
-    }
-    if (wave != 0 || !row_ok) return;
-    float mstar = red_m[0][fq];
-#pragma unroll
-    for (int w = 1; w < NW; w++) mstar = fmaxf(mstar, red_m[w][fq]);
-    float L = 0.f;
-    f32x4 O[DT];
-#pragma unroll
-    for (int d = 0; d < DT; d++) O[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (mstar > -INFINITY) {       // (a workgroup of a split launch may have had no tile at all)
-#pragma unroll
-        for (int w = 0; w < NW; w++) {
-            const float sc = __builtin_amdgcn_exp2f(red_m[w][fq] - mstar);   // idle waves: exp2(-inf) = 0
-            L += red_l[w][fq] * sc;
-            const f32x4* wo = (const f32x4*)(smem + w * TILE_BYTES);
-#pragma unroll
-            for (int d = 0; d < DT; d++) O[d] += wo[d * 64 + lane] * sc;
-        }
-    }
-    if (gridDim.z > 1) {
-        const int pair = seq * gridDim.x + blockIdx.x;               // (sequence, kv head, query tile)
-        float* rec = p.part + ((int64_t)pair * gridDim.z + blockIdx.z) * attn_part_floats<HD>();
-#pragma unroll
-        for (int d = 0; d < DT; d++) ((f32x4*)rec)[d * 64 + lane] = O[d];
-        if (fg == 0) { rec[DT * 256 + fq] = mstar; rec[DT * 256 + 16 + fq] = L; }
-        // Last arriver combines (no second launch: a merge kernel cost 5-7 us of the 8-11 the split saves).  Release my
-        // record device-wide (the workgroups of a pair may sit on different XCDs, whose L2s are not coherent), draw a
-        // ticket, and if it is the last one acquire the others' records.  The order of the sum is z order regardless.
-        __threadfence();
-        int ticket = 0;
-        int32_t* cnt = p.part_cnt + pair;
-        if (lane == 0) ticket = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ticket = __builtin_amdgcn_readfirstlane(ticket);
-        if (ticket != (int)gridDim.z - 1) return;
-        __threadfence();
-        attn_decode_merge<HD>(p, pair, tok, head, gridDim.z, lane);
-        if (lane == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);    // for the next launch
-        return;
-    }
-    const float inv = 1.0f / L;
-#pragma unroll
-    for (int d = 0; d < DT; d++)
-        act_store4<bf16_t>((bf16_t*)p.out, tok, head * HD + d * 16 + fg * 4, p.out_stride, O[d] * inv);
+    attn_decode_finish<HD, NW>(p, smem, vimg, red_m, red_l, o, m_run, l_run, seq, tok, head, row_ok, wave, lane, fq, fg, 1.0f, stamps);
 }
 
 // ------------------------------------------------------------------------------------------

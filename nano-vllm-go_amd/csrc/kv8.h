@@ -8,7 +8,8 @@
 //          fp32 scores (folded into the exp2 pre-scale sl2), v_scale the fp32 output at the final normalisation.
 // Attention over an 8-bit cache is therefore bf16 attention over the dequantized cache, up to fp32 summation order.
 //
-// The kernels keep the bf16 kernels' structure (attn.h) with their own names; the bf16 instantiations are not touched:
+// The kernels here hold only what an 8-bit cache changes — how a K / V tile reaches registers or its bf16 LDS image, and
+// the two scales; the tile arithmetic, the decode tail and the prefill tile / epilogue are attn.h's, shared with the bf16 kernels:
 //   decode: K fragments straight HBM -> VGPR, 16 bytes per lane = two bf16x8 MFMA fragments (the k index of K and Q is
 //           permuted identically: MFMA step ks = 2 ks2 + j covers columns ks2*64 + fg*16 + j*8 .. +8); V as whole rows,
 //           16 codes per lane, converted into the bf16 LDS image of attn.h and read back transposed (ds_read_b64_tr_b16).
@@ -117,37 +118,11 @@ __global__ void rope_kv8_kernel(const float* __restrict__ qkv, int qkv_stride, c
 // ------------------------------------------------------------------------------------------
 // 8-bit decode kernel: attn_decode_bf16_kernel's non-fused form over an 8-bit cache (see the header comment).
 // ------------------------------------------------------------------------------------------
-template <int HD>
-__device__ __forceinline__ void attn_decode_kv8_merge(const AttnArgs& p, int pair, int tok, int head, int nsplit, int lane, float vsc) {
-    constexpr int DT = HD / 16;
-    const int fq = lane & 15, fg = lane >> 4;
-    const float* rec0 = p.part + (int64_t)pair * nsplit * attn_part_floats<HD>();
-    float mstar = -INFINITY;
-    for (int z = 0; z < nsplit; z++) mstar = fmaxf(mstar, rec0[(int64_t)z * attn_part_floats<HD>() + DT * 256 + fq]);
-    float L = 0.f;
-    f32x4 O[DT];
-#pragma unroll
-    for (int d = 0; d < DT; d++) O[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    for (int z = 0; z < nsplit; z++) {
-        const float* rec = rec0 + (int64_t)z * attn_part_floats<HD>();
-        const float mz = rec[DT * 256 + fq];
-        if (mz == -INFINITY) continue;
-        const float sc = __builtin_amdgcn_exp2f(mz - mstar);
-        L += rec[DT * 256 + 16 + fq] * sc;
-#pragma unroll
-        for (int d = 0; d < DT; d++) O[d] += ((const f32x4*)rec)[d * 64 + lane] * sc;
-    }
-    const float inv = vsc / L;
-#pragma unroll
-    for (int d = 0; d < DT; d++)
-        act_store4<bf16_t>((bf16_t*)p.out, tok, head * HD + d * 16 + fg * 4, p.out_stride, O[d] * inv);
-}
-
 template <int HD, int NW>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                   int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p,
                                                                   float ksc, float vsc) {
-    constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8;
+    constexpr int KS = HD / 32, DT = HD / 16;
     constexpr int CPR8 = HD / 16, KPI8 = 64 / CPR8, NVL8 = 64 / KPI8;     // 16-code chunks per row, rows per load, loads per tile
     constexpr int NT2 = HD <= 64 ? 2 : 1;
     constexpr int TILE_BYTES = 64 * HD * 2;                               // the bf16 LDS image
@@ -172,10 +147,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
     for (int d = 0; d < DT; d++) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
     const float sl2 = p.scale * ksc * 1.4426950408889634f;
-    const int q4 = fq >> 2, p4 = fq & 3;
     int v_off[DT];
 #pragma unroll
-    for (int d = 0; d < DT; d++) v_off[d] = 16 * kv_img_chunk<HD>(4 * fg + q4, 2 * d + (p4 >> 1)) + 8 * (p4 & 1);
+    for (int d = 0; d < DT; d++) v_off[d] = attn_v_off<HD>(fq, fg, d);
     // Q in the permuted k order of the 16-byte K loads
     bf16x8 qf[KS];
     {
@@ -244,25 +218,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
                 s[h][t] = acc;
             }
         }
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
-        tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-        const float m_new = fmaxf(m_run, tmax);
-        const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
-        float psum = 0.f;
-#pragma unroll
-        for (int h = 0; h < NT2; h++)
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    const float pv = __builtin_amdgcn_exp2f(s[h][t][r] - m_new);
-                    s[h][t][r] = pv;
-                    psum += pv;
-                }
-        l_run = l_run * alpha + psum;
-        m_run = m_new;
-#pragma unroll
-        for (int d = 0; d < DT; d++) o[d] *= alpha;
+        attn_decode_softmax<HD, NT2>(s, tmax, m_run, l_run, o);
 #pragma unroll
         for (int h = 0; h < NT2; h++) {
             if (kt0 + h * nvw >= n_kt) continue;
@@ -273,90 +229,15 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
                 *(bf16x8*)(vimg + 16 * kv_img_chunk<HD>(row, 2 * dch8)) = kv8_to_bf16x8(w[0], w[1]);
                 *(bf16x8*)(vimg + 16 * kv_img_chunk<HD>(row, 2 * dch8 + 1)) = kv8_to_bf16x8(w[2], w[3]);
             }
-#pragma unroll
-            for (int u = 0; u < 2; u++) {
-                bf16x8 pf;
-#pragma unroll
-                for (int r = 0; r < 4; r++) { pf[r] = (bf16_t)s[h][2 * u][r]; pf[4 + r] = (bf16_t)s[h][2 * u + 1][r]; }
-#pragma unroll
-                for (int d = 0; d < DT; d++) {
-                    const bf16x4 lo = lds_read_tr4(vimg + v_off[d] + u * (32 * CPR * 16));
-                    const bf16x4 hi = lds_read_tr4(vimg + v_off[d] + u * (32 * CPR * 16) + 16 * CPR * 16);
-                    bf16x8 vf;
-#pragma unroll
-                    for (int r = 0; r < 4; r++) { vf[r] = lo[r]; vf[4 + r] = hi[r]; }
-                    o[d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf, o[d], 0, 0, 0);
-                }
-            }
+            attn_pv_tile<HD, 1, false>(vimg, v_off, &s[h], &o, nullptr);
         }
     };
     for (int kt0 = vw; kt0 < n_kt; kt0 += NT2 * nvw) {
         issue_round(kt0);
         do_round(kt0);
     }
-    // ---- flash-decoding combine through LDS, fixed wave order (as attn_decode_bf16_kernel) ----
-    l_run += __shfl_xor(l_run, 16, 64);
-    l_run += __shfl_xor(l_run, 32, 64);
-    if (fg == 0) { red_m[wave][fq] = m_run; red_l[wave][fq] = l_run; }
-    f32x4* my_o = (f32x4*)vimg;
-#pragma unroll
-    for (int d = 0; d < DT; d++) my_o[d * 64 + lane] = o[d];
-    __syncthreads();
-    if (gridDim.z == 1 && NW >= DT) {
-        if (wave >= DT || !row_ok) return;
-        float ms = red_m[0][fq];
-#pragma unroll
-        for (int w = 1; w < NW; w++) ms = fmaxf(ms, red_m[w][fq]);
-        float Ls = 0.f;
-        f32x4 Od = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int w = 0; w < NW; w++) {
-            const float sc = __builtin_amdgcn_exp2f(red_m[w][fq] - ms);
-            Ls += red_l[w][fq] * sc;
-            Od += ((const f32x4*)(smem + w * TILE_BYTES))[wave * 64 + lane] * sc;
-        }
-        act_store4<bf16_t>((bf16_t*)p.out, tok, head * HD + wave * 16 + fg * 4, p.out_stride, Od * (vsc / Ls));
-        return;
-    }
-    if (wave != 0 || !row_ok) return;
-    float mstar = red_m[0][fq];
-#pragma unroll
-    for (int w = 1; w < NW; w++) mstar = fmaxf(mstar, red_m[w][fq]);
-    float L = 0.f;
-    f32x4 O[DT];
-#pragma unroll
-    for (int d = 0; d < DT; d++) O[d] = f32x4{0.f, 0.f, 0.f, 0.f};
-    if (mstar > -INFINITY) {
-#pragma unroll
-        for (int w = 0; w < NW; w++) {
-            const float sc = __builtin_amdgcn_exp2f(red_m[w][fq] - mstar);
-            L += red_l[w][fq] * sc;
-            const f32x4* wo = (const f32x4*)(smem + w * TILE_BYTES);
-#pragma unroll
-            for (int d = 0; d < DT; d++) O[d] += wo[d * 64 + lane] * sc;
-        }
-    }
-    if (gridDim.z > 1) {
-        const int pair = seq * gridDim.x + blockIdx.x;
-        float* rec = p.part + ((int64_t)pair * gridDim.z + blockIdx.z) * attn_part_floats<HD>();
-#pragma unroll
-        for (int d = 0; d < DT; d++) ((f32x4*)rec)[d * 64 + lane] = O[d];
-        if (fg == 0) { rec[DT * 256 + fq] = mstar; rec[DT * 256 + 16 + fq] = L; }
-        __threadfence();
-        int ticket = 0;
-        int32_t* cnt = p.part_cnt + pair;
-        if (lane == 0) ticket = __hip_atomic_fetch_add(cnt, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ticket = __builtin_amdgcn_readfirstlane(ticket);
-        if (ticket != (int)gridDim.z - 1) return;
-        __threadfence();
-        attn_decode_kv8_merge<HD>(p, pair, tok, head, gridDim.z, lane, vsc);
-        if (lane == 0) __hip_atomic_store(cnt, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        return;
-    }
-    const float inv = vsc / L;
-#pragma unroll
-    for (int d = 0; d < DT; d++)
-        act_store4<bf16_t>((bf16_t*)p.out, tok, head * HD + d * 16 + fg * 4, p.out_stride, O[d] * inv);
+    NvlStampsT<false> stamps(nullptr, 0);
+    attn_decode_finish<HD, NW>(p, smem, vimg, red_m, red_l, o, m_run, l_run, seq, tok, head, row_ok, wave, lane, fq, fg, vsc, stamps);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -366,9 +247,8 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
 // ------------------------------------------------------------------------------------------
 template <int HD>
 __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_kv8_kernel(AttnArgs p, float ksc, float vsc) {
-    constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, CPR8 = HD / 16, TQ = 2;
+    constexpr int KS = HD / 32, DT = HD / 16, CPR8 = HD / 16, TQ = PF_TQ, QROWS = PF_QROWS;
     constexpr int TILE_BYTES = 64 * HD * 2, CH = 64 * CPR8, NCH = 2 * CH / 512;
-    constexpr int QROWS = 256;
     extern __shared__ __attribute__((aligned(16))) char smem[];     // [K image | V image] (bf16)
     const int seq = blockIdx.y, kvh = blockIdx.x, qt = gridDim.z - 1 - blockIdx.z;
     const int S = p.seq_len[seq];
@@ -380,28 +260,12 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_kv8_kernel
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int fq = lane & 15, fg = lane >> 4;
 
+    const AttnPrefillRows w{qt, wave, fq, fg, R, tok0, pos0, kvh};
     bf16x8 qf[TQ][KS];
-    auto row_of = [&](int qi, bool& ok) {
-        int row = qt * QROWS + (wave * TQ + qi) * 16 + fq;
-        ok = row < R;
-        return ok ? row : qt * QROWS;
-    };
-#pragma unroll
-    for (int qi = 0; qi < TQ; qi++) {
-        bool ok;
-        const int row = row_of(qi, ok), si = row / p.group, hd_ = kvh * p.group + (row - si * p.group);
-        const bf16_t* qp = (const bf16_t*)p.q + (int64_t)(tok0 + si) * p.q_stride + hd_ * HD;
-#pragma unroll
-        for (int ks = 0; ks < KS; ks++) qf[qi][ks] = *(const bf16x8*)(qp + ks * 32 + fg * 8);
-    }
-    int last_row = qt * QROWS + QROWS - 1;
-    if (last_row > R - 1) last_row = R - 1;
-    const int n_kt = (pos0 + last_row / p.group) / 64 + 1;
-    const int w_row0 = qt * QROWS + wave * 32;
-    int w_last = w_row0 + 31;
-    if (w_last > R - 1) w_last = R - 1;
-    const int wave_n_kt = w_row0 < R ? (pos0 + w_last / p.group) / 64 + 1 : 0;
-    const int wave_first_limit = pos0 + w_row0 / p.group;
+    int qpos[TQ];
+    attn_prefill_load_q<HD>(p, w, qf, qpos);
+    int n_kt, wave_n_kt, wave_first_limit;
+    attn_prefill_setup(p, w, n_kt, wave_n_kt, wave_first_limit);
 
     // this thread's pieces: piece g = tid + j * 512 of the [K pieces | V pieces] list; piece = 16 codes of one row
     int src_off[NCH], dst_off[NCH];
@@ -421,19 +285,16 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_kv8_kernel
             raw[j] = *(const u32x4*)(base + src_off[j]);
         }
     };
-    int k_off[KS];
+    int k_off[KS], v_off[DT];
 #pragma unroll
-    for (int ks = 0; ks < KS; ks++) k_off[ks] = 16 * kv_img_chunk<HD>(fq, ks * 4 + fg);
-    const int q4 = fq >> 2, p4 = fq & 3;
-    int v_off[DT];
+    for (int ks = 0; ks < KS; ks++) k_off[ks] = attn_k_off<HD>(fq, fg, ks);
 #pragma unroll
-    for (int d = 0; d < DT; d++) v_off[d] = 16 * kv_img_chunk<HD>(4 * fg + q4, 2 * d + (p4 >> 1)) + 8 * (p4 & 1);
-
+    for (int d = 0; d < DT; d++) v_off[d] = attn_v_off<HD>(fq, fg, d);
     f32x4 o[TQ][DT];
     f32x4 lacc[TQ];
     float m_run[TQ];
 #pragma unroll
-    for (int qi = 0; qi < TQ; qi++) {
+    for (int qi = 0; qi < TQ; qi++) {       // (as a loop, not "= {}": that form costs the hd-64 kernel 5 registers)
         m_run[qi] = -INFINITY;
         lacc[qi] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
@@ -455,99 +316,9 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_kv8_kernel
         if (kt + 1 < n_kt) load_tile(kt + 1);            // in flight during this tile's MFMAs
         __syncthreads();
         if (kt >= wave_n_kt) continue;
-
-        f32x4 s[TQ][4];
-#pragma unroll
-        for (int qi = 0; qi < TQ; qi++)
-#pragma unroll
-            for (int t = 0; t < 4; t++) s[qi][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int t = 0; t < 4; t++)
-#pragma unroll
-            for (int ks = 0; ks < KS; ks++) {
-                const bf16x8 kf = *(const bf16x8*)(kimg + k_off[ks] + t * (16 * CPR * 16));
-#pragma unroll
-                for (int qi = 0; qi < TQ; qi++)
-                    s[qi][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qi][ks], s[qi][t], 0, 0, 0);
-            }
-        const bool whole = kt * 64 + 63 <= wave_first_limit;
-        if (!whole) {
-#pragma unroll
-            for (int qi = 0; qi < TQ; qi++) {
-                bool ok;
-                const int lim = pos0 + row_of(qi, ok) / p.group - kt * 64 - fg * 4;
-#pragma unroll
-                for (int t = 0; t < 4; t++)
-#pragma unroll
-                    for (int r = 0; r < 4; r++)
-                        s[qi][t][r] = (t * 16 + r <= lim) ? s[qi][t][r] : -INFINITY;
-            }
-        }
-        float m_new[TQ];
-        bool moved = false;
-#pragma unroll
-        for (int qi = 0; qi < TQ; qi++) {
-            const float tmax = rows_max(vmax16(s[qi][0], s[qi][1], s[qi][2], s[qi][3]));
-            m_new[qi] = vmax2(m_run[qi], tmax * sl2);
-            moved |= m_new[qi] != m_run[qi];
-        }
-        if (__any(moved)) {
-#pragma unroll
-            for (int qi = 0; qi < TQ; qi++) {
-                const float alpha = __builtin_amdgcn_exp2f(m_run[qi] - m_new[qi]);
-                lacc[qi] *= alpha;
-#pragma unroll
-                for (int d = 0; d < DT; d++) o[qi][d] *= alpha;
-                m_run[qi] = m_new[qi];
-            }
-        }
-#pragma unroll
-        for (int qi = 0; qi < TQ; qi++)
-#pragma unroll
-            for (int t = 0; t < 4; t++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) s[qi][t][r] = __builtin_amdgcn_exp2f(fmaf(s[qi][t][r], sl2, -m_new[qi]));
-#pragma unroll
-        for (int u = 0; u < 2; u++) {
-            bf16x8 pf[TQ];
-#pragma unroll
-            for (int qi = 0; qi < TQ; qi++)
-#pragma unroll
-                for (int r = 0; r < 4; r++) {
-                    pf[qi][r] = (bf16_t)s[qi][2 * u][r];
-                    pf[qi][4 + r] = (bf16_t)s[qi][2 * u + 1][r];
-                }
-#pragma unroll
-            for (int d = 0; d < DT; d++) {
-                const bf16x4 lo = lds_read_tr4(vimg + v_off[d] + u * (32 * CPR * 16));
-                const bf16x4 hi = lds_read_tr4(vimg + v_off[d] + u * (32 * CPR * 16) + 16 * CPR * 16);
-                bf16x8 vf;
-#pragma unroll
-                for (int r = 0; r < 4; r++) { vf[r] = lo[r]; vf[4 + r] = hi[r]; }
-#pragma unroll
-                for (int qi = 0; qi < TQ; qi++)
-                    o[qi][d] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(vf, pf[qi], o[qi][d], 0, 0, 0);
-            }
-            bf16x8 ones;
-#pragma unroll
-            for (int r = 0; r < 8; r++) ones[r] = (bf16_t)1.0f;
-#pragma unroll
-            for (int qi = 0; qi < TQ; qi++)
-                lacc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones, pf[qi], lacc[qi], 0, 0, 0);
-        }
+        attn_prefill_tile<HD>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run);
     }
-
-#pragma unroll
-    for (int qi = 0; qi < TQ; qi++) {
-        const float l = lacc[qi][0];
-        bool ok;
-        const int row = row_of(qi, ok), si = row / p.group, hd_ = kvh * p.group + (row - si * p.group);
-        if (!ok) continue;
-        const float inv = vsc / l;
-#pragma unroll
-        for (int d = 0; d < DT; d++)
-            act_store4<bf16_t>((bf16_t*)p.out, tok0 + si, hd_ * HD + d * 16 + fg * 4, p.out_stride, o[qi][d] * inv);
-    }
+    attn_prefill_store<HD>(p, w, o, lacc, vsc);
 }
 template <int HD> constexpr int attn_prefill_kv8_lds_bytes() { return 2 * 64 * HD * 2; }
 

@@ -1504,18 +1504,33 @@ int decode_attn_cfg(const nvl_model* m, int n_seqs) {
     return (g_attn_nw ? g_attn_nw : std::min(nw, cap)) | (1 << 8);
 }
 int decode_attn_waves(const nvl_model* m, int n_seqs) { return decode_attn_cfg(m, n_seqs); }   // (graph keys: the whole shape)
-void attention(nvl_model* m, int li, const Meta& md, int n_seqs, int max_len, double flops, bool fused_qkv = false) {
+// The decode launch ladder: 2 / 4 / 8 waves per workgroup, K2 / K4 / K8 the kernel's instantiations for them; `rest` are
+// the kernel's arguments after the AttnArgs (the scales of an 8-bit cache).
+template <auto K2, auto K4, auto K8, typename... Rest>
+static void launch_decode_attn(nvl_model* m, dim3 grid, int nw, int tile_bytes, const AttnArgs& a, Rest... rest) {
+#define NVL_DEC_LEAD a.seq_pos, a.blk_table, a.tbl_stride, a.bs_shift, a.Tmax, a.group      /* the preloaded leading arguments (attn.h) */
+    if (nw == 2) hipLaunchKernelGGL(K2, grid, dim3(128), 2 * tile_bytes, m->stream, NVL_DEC_LEAD, a, rest...);
+    else if (nw == 4) hipLaunchKernelGGL(K4, grid, dim3(256), 4 * tile_bytes, m->stream, NVL_DEC_LEAD, a, rest...);
+    else {
+        NVL_LDS_ATTR(K8, 8 * tile_bytes);
+        hipLaunchKernelGGL(K8, grid, dim3(512), 8 * tile_bytes, m->stream, NVL_DEC_LEAD, a, rest...);
+    }
+#undef NVL_DEC_LEAD
+}
+// Every attention launch.  kc / vc: the layer's K / V slabs; kv8: {k_scale, v_scale} of an 8-bit (e4m3fn) cache — the slabs
+// are then the layer's code slabs (same element layout, one byte per element; kv8.h) — else NULL.  The 8-bit kernels have
+// no fused (RoPE + append) and no stamped form, and their prefill kernel reads the block table from global memory (no
+// 128-block limit); grids, wave choices and the K/V load policy are the same.
+static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_len, const void* kc, const void* vc,
+                             double flops, double abytes, bool fused_qkv, const float* kv8) {
     AttnArgs a{};
     a.q = m->q; a.q_stride = m->nH * m->hd;
     a.out = m->attn_out; a.out_stride = m->nH * m->hd;
-    a.kcache = (char*)m->kcache + (size_t)li * m->layer_stride * m->wsize;
-    a.vcache = (char*)m->vcache + (size_t)li * m->layer_stride * m->wsize;
+    a.kcache = kc; a.vcache = vc;
     a.slot_stride = m->slot_stride; a.Tmax = m->Tmax;
     a.seq_tok_start = md.seq_tok_start; a.seq_len = md.seq_len; a.seq_pos = md.seq_pos; a.blk_table = md.blk_table; a.tbl_stride = m->blocks_per_seq;
     a.bs_shift = (m->Tmax & (m->Tmax - 1)) == 0 ? __builtin_ctz((unsigned)m->Tmax) : -1;
     a.nH = m->nH; a.nKV = m->nKV; a.group = m->group; a.scale = m->attn_scale;
-    // algorithmic bytes: every cached key/value of the batch once + Q in + O out (+ the fp32 QKV row of a fused decode step)
-    const double abytes = m->kv_tok * 2.0 * m->nKV * m->hd * (double)m->wsize;
     KScope ks(m, KC_ATTN, flops, KS_ATTN, abytes);
     if (m->f32) {
         const size_t lds = (size_t)m->Tmax * 4;
@@ -1537,88 +1552,53 @@ void attention(nvl_model* m, int li, const Meta& md, int n_seqs, int max_len, do
         if (fused_qkv) {   // RoPE + KV append + attention in one launch, straight from the QKV projection's fp32 output
             a.qkv = m->qkv; a.qkv_stride = m->n_qkv; a.cos_t = m->rope_cos; a.sin_t = m->rope_sin;
         }
-#define NVL_DEC_LEAD a.seq_pos, a.blk_table, a.tbl_stride, a.bs_shift, a.Tmax, a.group      /* the preloaded leading arguments (attn.h) */
-#define NVL_DEC(HDv, FUSEDv)                                                                                           \
-        do {                                                                                                           \
-            constexpr int tile_bytes = 64 * HDv * 2;                                                                   \
-            if (nw == 2) hipLaunchKernelGGL((attn_decode_bf16_kernel<HDv, 2, FUSEDv>), grid, dim3(128), 2 * tile_bytes, m->stream, NVL_DEC_LEAD, a);      \
-            else if (nw == 4) hipLaunchKernelGGL((attn_decode_bf16_kernel<HDv, 4, FUSEDv>), grid, dim3(256), 4 * tile_bytes, m->stream, NVL_DEC_LEAD, a); \
-            else {                                                                                                     \
-                NVL_LDS_ATTR((attn_decode_bf16_kernel<HDv, 8, FUSEDv>), 8 * tile_bytes);                               \
-                hipLaunchKernelGGL((attn_decode_bf16_kernel<HDv, 8, FUSEDv>), grid, dim3(512), 8 * tile_bytes, m->stream, NVL_DEC_LEAD, a);               \
-            }                                                                                                          \
-        } while (0)
-        if (a.stamps && fused_qkv && m->hd == 64) {     // diagnostic instantiation with the in-kernel stamps compiled in
-            constexpr int tb = 64 * 64 * 2;
-            if (nw == 2) hipLaunchKernelGGL((attn_decode_bf16_kernel<64, 2, true, true>), grid, dim3(128), 2 * tb, m->stream, NVL_DEC_LEAD, a);
-            else if (nw == 4) hipLaunchKernelGGL((attn_decode_bf16_kernel<64, 4, true, true>), grid, dim3(256), 4 * tb, m->stream, NVL_DEC_LEAD, a);
-            else {
-                NVL_LDS_ATTR((attn_decode_bf16_kernel<64, 8, true, true>), 8 * tb);
-                hipLaunchKernelGGL((attn_decode_bf16_kernel<64, 8, true, true>), grid, dim3(512), 8 * tb, m->stream, NVL_DEC_LEAD, a);
-            }
-        } else if (fused_qkv) { if (m->hd == 64) NVL_DEC(64, true); else NVL_DEC(128, true); }
-        else { if (m->hd == 64) NVL_DEC(64, false); else NVL_DEC(128, false); }
+#define NVL_DEC(HDv, KERN, ...) launch_decode_attn<KERN(HDv, 2), KERN(HDv, 4), KERN(HDv, 8)>(m, grid, nw, 64 * HDv * 2, a, ##__VA_ARGS__)
+#define NVL_DEC_KV8(HDv, NWv) attn_decode_kv8_kernel<HDv, NWv>
+#define NVL_DEC_PLAIN(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, false>
+#define NVL_DEC_FUSED(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true>
+#define NVL_DEC_STAMP(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true, true>     /* diagnostic: the in-kernel stamps compiled in */
+        if (kv8) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_KV8, kv8[0], kv8[1]); else NVL_DEC(128, NVL_DEC_KV8, kv8[0], kv8[1]); }
+        else if (a.stamps) NVL_DEC(64, NVL_DEC_STAMP);
+        else if (fused_qkv) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_FUSED); else NVL_DEC(128, NVL_DEC_FUSED); }
+        else { if (m->hd == 64) NVL_DEC(64, NVL_DEC_PLAIN); else NVL_DEC(128, NVL_DEC_PLAIN); }
+#undef NVL_DEC_STAMP
+#undef NVL_DEC_FUSED
+#undef NVL_DEC_PLAIN
+#undef NVL_DEC_KV8
 #undef NVL_DEC
-#undef NVL_DEC_LEAD
     } else {
-        // 256 query rows (position x head-in-group, position-major) per workgroup of 8 waves; K/V tiles by LDS-DMA
+        // 256 query rows (position x head-in-group, position-major) per workgroup of 8 waves
         const int64_t qrows = (int64_t)max_len * m->group;
-        if (m->blocks_per_seq > 128) throw std::runtime_error("attention: more than 128 KV blocks per sequence");
         dim3 grid(m->nKV, n_seqs, cdiv(qrows, 256));      // (kv head fastest, query tile slowest: attn.h)
-        if (m->hd == 64) {
-            hipLaunchKernelGGL((attn_prefill_bf16_kernel<64>), grid, dim3(512), attn_prefill_lds_bytes<64>(), m->stream, a);
-        } else {
-            NVL_LDS_ATTR(attn_prefill_bf16_kernel<128>, attn_prefill_lds_bytes<128>());
-            hipLaunchKernelGGL((attn_prefill_bf16_kernel<128>), grid, dim3(512), attn_prefill_lds_bytes<128>(), m->stream, a);
+        if (kv8) {     // K/V tiles through registers into one bf16 image pair
+            if (m->hd == 64) {
+                hipLaunchKernelGGL((attn_prefill_kv8_kernel<64>), grid, dim3(512), attn_prefill_kv8_lds_bytes<64>(), m->stream, a, kv8[0], kv8[1]);
+            } else {
+                NVL_LDS_ATTR(attn_prefill_kv8_kernel<128>, attn_prefill_kv8_lds_bytes<128>());
+                hipLaunchKernelGGL((attn_prefill_kv8_kernel<128>), grid, dim3(512), attn_prefill_kv8_lds_bytes<128>(), m->stream, a, kv8[0], kv8[1]);
+            }
+        } else {       // K/V tiles by LDS-DMA; the kernel keeps the sequence's block table in LDS
+            if (m->blocks_per_seq > 128) throw std::runtime_error("attention: more than 128 KV blocks per sequence");
+            if (m->hd == 64) {
+                hipLaunchKernelGGL((attn_prefill_bf16_kernel<64>), grid, dim3(512), attn_prefill_lds_bytes<64>(), m->stream, a);
+            } else {
+                NVL_LDS_ATTR(attn_prefill_bf16_kernel<128>, attn_prefill_lds_bytes<128>());
+                hipLaunchKernelGGL((attn_prefill_bf16_kernel<128>), grid, dim3(512), attn_prefill_lds_bytes<128>(), m->stream, a);
+            }
         }
     }
     NVL_HIP(hipGetLastError());
 }
-
-// attention over an 8-bit (e4m3fn) cache: kc / vc are the layer's code slabs (same element layout as the bf16 slabs, one
-// byte per element); k_scale / v_scale the layer's scales (kv8.h).  bf16 only; same grids and wave choices as attention().
+// algorithmic bytes: every cached key/value of the batch once + Q in + O out (+ the fp32 QKV row of a fused decode step)
+void attention(nvl_model* m, int li, const Meta& md, int n_seqs, int max_len, double flops, bool fused_qkv = false) {
+    attention_launch(m, md, n_seqs, max_len, (char*)m->kcache + (size_t)li * m->layer_stride * m->wsize,
+                     (char*)m->vcache + (size_t)li * m->layer_stride * m->wsize, flops, m->kv_tok * 2.0 * m->nKV * m->hd * (double)m->wsize, fused_qkv, nullptr);
+}
+// attention over an 8-bit cache: kc / vc the layer's code slabs, k_scale / v_scale the layer's scales.  bf16 only.
 void attention_kv8(nvl_model* m, const Meta& md, int n_seqs, int max_len, const void* kc, const void* vc, float ksc, float vsc) {
     if (m->f32) throw std::runtime_error("attention_kv8: the 8-bit KV cache is bf16-only");
-    AttnArgs a{};
-    a.q = m->q; a.q_stride = m->nH * m->hd;
-    a.out = m->attn_out; a.out_stride = m->nH * m->hd;
-    a.kcache = kc; a.vcache = vc;
-    a.slot_stride = m->slot_stride; a.Tmax = m->Tmax;
-    a.seq_tok_start = md.seq_tok_start; a.seq_len = md.seq_len; a.seq_pos = md.seq_pos; a.blk_table = md.blk_table; a.tbl_stride = m->blocks_per_seq;
-    a.bs_shift = (m->Tmax & (m->Tmax - 1)) == 0 ? __builtin_ctz((unsigned)m->Tmax) : -1;
-    a.nH = m->nH; a.nKV = m->nKV; a.group = m->group; a.scale = m->attn_scale;
-    const double abytes = m->kv_tok * 2.0 * m->nKV * m->hd;
-    KScope ks(m, KC_ATTN, 0.0, KS_ATTN, abytes);
-    if (max_len == 1) {
-        const int cfg = decode_attn_cfg(m, n_seqs), nsplit = cfg >> 8, nw = cfg & 255;
-        dim3 grid(m->nKV * cdiv(m->group, 16), n_seqs, nsplit);
-        a.part = m->attn_part; a.part_cnt = m->attn_part_cnt;
-        a.kv_nt = g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && cdiv(m->group, 16) == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
-#define NVL_DEC8_LEAD a.seq_pos, a.blk_table, a.tbl_stride, a.bs_shift, a.Tmax, a.group
-#define NVL_DEC8(HDv)                                                                                                  \
-        do {                                                                                                           \
-            constexpr int tile_bytes = 64 * HDv * 2;                                                                   \
-            if (nw == 2) hipLaunchKernelGGL((attn_decode_kv8_kernel<HDv, 2>), grid, dim3(128), 2 * tile_bytes, m->stream, NVL_DEC8_LEAD, a, ksc, vsc);      \
-            else if (nw == 4) hipLaunchKernelGGL((attn_decode_kv8_kernel<HDv, 4>), grid, dim3(256), 4 * tile_bytes, m->stream, NVL_DEC8_LEAD, a, ksc, vsc); \
-            else {                                                                                                     \
-                NVL_LDS_ATTR((attn_decode_kv8_kernel<HDv, 8>), 8 * tile_bytes);                                        \
-                hipLaunchKernelGGL((attn_decode_kv8_kernel<HDv, 8>), grid, dim3(512), 8 * tile_bytes, m->stream, NVL_DEC8_LEAD, a, ksc, vsc);               \
-            }                                                                                                          \
-        } while (0)
-        if (m->hd == 64) NVL_DEC8(64); else NVL_DEC8(128);
-#undef NVL_DEC8
-#undef NVL_DEC8_LEAD
-    } else {
-        const int64_t qrows = (int64_t)max_len * m->group;
-        dim3 grid(m->nKV, n_seqs, cdiv(qrows, 256));
-        if (m->hd == 64) {
-            hipLaunchKernelGGL((attn_prefill_kv8_kernel<64>), grid, dim3(512), attn_prefill_kv8_lds_bytes<64>(), m->stream, a, ksc, vsc);
-        } else {
-            NVL_LDS_ATTR(attn_prefill_kv8_kernel<128>, attn_prefill_kv8_lds_bytes<128>());
-            hipLaunchKernelGGL((attn_prefill_kv8_kernel<128>), grid, dim3(512), attn_prefill_kv8_lds_bytes<128>(), m->stream, a, ksc, vsc);
-        }
-    }
-    NVL_HIP(hipGetLastError());
+    const float scales[2] = {ksc, vsc};
+    attention_launch(m, md, n_seqs, max_len, kc, vc, 0.0, m->kv_tok * 2.0 * m->nKV * m->hd, false, scales);
 }
 
 void rope_kv(nvl_model* m, int li, const Meta& md, int M) {
