@@ -443,6 +443,39 @@ int nvl_runner_run_sampled(nvl_model* m, int n_seqs, const int64_t* seq_ids, con
                            const int32_t* token_lens, int is_prefill, const nvl_sampling_params* params,
                            const float* uniforms, int32_t* next_tokens);
 
+/* ---- log-probabilities on the device (no reference counterpart: cmd/check-logits/main.go prints raw
+ * logits, generic_model.go:467-470 computes every row's and :595-604 keeps the last) ----
+ * Per logits row, with x' the final logits (LogitsScaling applied, generic_model.go:473-477):
+ *   logprob = x'_t - logsumexp(x') for the row's target id t (t = -1: no target, +0.0f is written),
+ *   argmax  = the greedy id (first strict maximum, cmd/ask/main.go:389-402; the id nvl_forward's argmax_out carries),
+ *   the top_k (0..8) most probable ids and their log-probabilities, value descending then id ascending ([rows][top_k];
+ *   entry 0 is the argmax; a row with fewer than top_k logits above -inf pads with id -1, -inf).
+ * The sums run in fp32 in a fixed tree order (reproducible bit for bit); |logprob error| <= 1e-5 + 2^-21 max|x'| against
+ * float64 on the same logits.  Any output pointer may be NULL; targets may be NULL (= all -1). */
+/* The rows of the LAST forward group — exactly the rows nvl_sample sees, in that order (generic_model.go:595-604: one per
+ * sequence, or every row after NVL_FWD_ALL_LOGITS, generic_model.go:467-470) — after nvl_forward (replayed decode passes
+ * included), nvl_forward_paged, nvl_runner_run*, nvl_decode_*; f32 and bf16; on a tensor-parallel rank too (the logits are
+ * replicated).  n_rows > the rows left, top_k outside [0, 8] or a target outside [-1, V): NVL_ERR_INVALID. */
+int nvl_logprobs(nvl_model* m, int n_rows, const int32_t* targets, int top_k, float* logprob_out, int32_t* argmax_out,
+                 int32_t* topk_ids_out, float* topk_logprob_out);
+/* nvl_forward (generic_model.go:276-480; the same validation, KV append and Mamba2 state update, so a long document can be
+ * scored over several calls and decoding can go on afterwards) returning, per NEW token row (generic_model.go:467-470: all
+ * sum(seq_lens) of them), the quantities above instead of logits: targets / logprob_out / argmax_out are [sum(seq_lens)],
+ * the top-k outputs [sum(seq_lens)][top_k].  Final norm + LM head + reduction run over chunks of at most R rows
+ * (nvl_set_tuning key 37, default 1024): the device never holds more than R x Vpad logits, and 4 x (2 + 2 top_k) bytes per
+ * row cross PCIe.  The pass takes the all-rows path (no deferred final norm, no graph replay) in every weight / KV /
+ * activation mode of the model.  Afterwards no logits rows are left: nvl_sample / nvl_logprobs answer NVL_ERR_INVALID
+ * until the next forward; the next token of a sequence is argmax_out of its last row.  Tensor-parallel models:
+ * NVL_ERR_STATE. */
+int nvl_score(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, const int32_t* seq_lens,
+              const int32_t* pos_offsets, const int32_t* targets, int top_k, float* logprob_out, int32_t* argmax_out,
+              int32_t* topk_ids_out, float* topk_logprob_out);
+/* nvl_score over block tables: nvl_forward_paged's arguments (generic_model.go:276-480 through Sequence.BlockTable,
+ * sequence.go:23), then nvl_score's. */
+int nvl_score_paged(nvl_model* m, int n_seqs, const int32_t* tokens, const int32_t* seq_lens, const int32_t* pos_offsets,
+                    const int32_t* block_tables, const int32_t* table_offsets, const int32_t* targets, int top_k,
+                    float* logprob_out, int32_t* argmax_out, int32_t* topk_ids_out, float* topk_logprob_out);
+
 /* ---- measurement (the reference only has wall-clock prints: cmd/ask/main.go:196-198) ---- */
 typedef struct nvl_stats {
     uint64_t forward_calls, prefill_tokens, decode_tokens;
@@ -544,6 +577,11 @@ int nvl_op_argmax(int device, const float* x, int rows, int cols, int32_t* out);
 int nvl_op_sample(int device, const float* logits, int rows, int V, const nvl_sampling_params* params,
                   const int32_t* const* history_ptrs, const int32_t* history_lens, const float* uniforms,
                   int32_t* out_tokens, float* probs_out);
+/* The log-probability kernels (nvl_logprobs; generic_model.go:467-470 rows, cmd/check-logits/main.go's view of them) on
+ * host logits [rows][ld], V valid columns (ld >= V: the pad columns travel too and are never used), divided by
+ * logits_scaling first when it is not 0 (generic_model.go:473-477). */
+int nvl_op_logprobs(int device, const float* logits, int rows, int V, int ld, float logits_scaling, const int32_t* targets,
+                    int top_k, float* logprob_out, int32_t* argmax_out, int32_t* topk_ids_out, float* topk_logprob_out);
 /* ---- tuning / measurement (no reference counterpart) ----
  * Times one projection GEMM shape (random bf16 operands resident in HBM) with HIP events on the
  * library's stream: avg_us per launch over `iters` back-to-back launches.  epi: 0 store-fp32,
@@ -588,6 +626,8 @@ int nvl_bench_gemm(int device, int M, int N, int K, int epi, int force_bnt, int 
  * 2 / 4 forced.
  * key 33: MoE decode: the experts' down projection carries the next RMSNorm (no K slices, no norm launch before the next QKV);
  * 0 (default): measured slower (rejected list (27)).
+ * key 37: rows per chunk of nvl_score's final norm + LM head + log-probability reduction (default 1024; rounded up to a
+ * multiple of 16, at least 16): the logits workspace of a scoring pass is that many rows.
  * The settings are PROCESS-GLOBAL and unsynchronised (every model in the process sees them): set them from one thread
  * while no forward call is running.  Every call starts a new tuning epoch: captured decode graphs bake the tuning in and are re-captured.
  * Returns the previous value. */

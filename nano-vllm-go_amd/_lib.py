@@ -159,6 +159,10 @@ def lib():
     L.nvl_sample.argtypes = [vp, C.c_int, C.POINTER(SamplingParamsC), vp, vp, vp, vp]
     L.nvl_runner_run_sampled.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, C.POINTER(SamplingParamsC), vp, vp]
     L.nvl_op_sample.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.POINTER(SamplingParamsC), vp, vp, vp, vp, vp]
+    L.nvl_logprobs.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp]
+    L.nvl_score.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.nvl_score_paged.argtypes = [vp, C.c_int, vp, vp, vp, vp, vp, vp, C.c_int, vp, vp, vp, vp]
+    L.nvl_op_logprobs.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, f32, vp, C.c_int, vp, vp, vp, vp]
     L.nvl_set_profile.argtypes = [vp, C.c_int]
     L.nvl_get_stats.argtypes = [vp, C.POINTER(StatsC)]
     L.nvl_reset_stats.argtypes = [vp]

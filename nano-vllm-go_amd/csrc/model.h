@@ -15,6 +15,7 @@
 #include "common.h"
 #include "elem.h"
 #include "sample.h"
+#include "logprob.h"
 #include "gemm.h"
 #include "wq.h"
 #include "mamba.h"
@@ -52,7 +53,7 @@ enum KClass { KC_GEMM = 0, KC_ATTN = 1, KC_OTHER = 2 };
 // where in the layer a launch sits (per-kernel roofline entries of nvl_get_kernel_stats; names in nvllm.hip)
 enum KSite { KS_OTHER = 0, KS_QKV, KS_ATTN, KS_OPROJ, KS_FFN_UP, KS_FFN_DOWN, KS_LM_HEAD, KS_NORM, KS_MOE_ROUTER, KS_MOE_PLAN,
              KS_MOE_UP, KS_MOE_DOWN, KS_MOE_COMBINE, KS_EMBED, KS_ARGMAX, KS_ROPE, KS_MAMBA_IN, KS_MAMBA_CONV, KS_MAMBA_SCAN,
-             KS_MAMBA_GATE, KS_MAMBA_OUT, KS_ALLREDUCE, KS_COUNT };
+             KS_MAMBA_GATE, KS_MAMBA_OUT, KS_ALLREDUCE, KS_LOGPROBS, KS_COUNT };
 
 struct ProfRec { hipEvent_t a, b; int cls; double flops; int site, phase; double bytes; };
 struct SiteStat { double ms = 0, flops = 0, bytes = 0; uint64_t launches = 0; };
@@ -66,6 +67,17 @@ struct SampleBufs {
     int32_t* hist = nullptr; int64_t hist_cap = 0;
     int32_t* off = nullptr; int32_t* out = nullptr; float* u = nullptr; int rows_cap = 0;
     float* probs = nullptr; int64_t probs_elems = 0;
+};
+
+// device scratch of the log-probability kernels (logprob.h); grows on demand
+struct LogprobBufs {
+    void* part = nullptr; int64_t part_words = 0;     // pass-1 partials of one launch
+    int32_t* io = nullptr; int64_t io_rows = 0;       // per row: target | logprob | argmax | top-k ids [8] | top-k logprobs [8]
+    int32_t* targets() const { return io; }
+    float* logprob() const { return (float*)(io + io_rows); }
+    int32_t* argmax() const { return io + 2 * io_rows; }
+    int32_t* topk_ids() const { return io + 3 * io_rows; }
+    float* topk_lp() const { return (float*)(io + (3 + nvl::LOGPROB_MAX_K) * io_rows); }
 };
 
 struct nvl_local_group {
@@ -176,6 +188,7 @@ struct nvl_model {
     int conv_chain = 0;          // set by runner_impl around the chunks of one long history
     float *ssd_z = nullptr, *ssd_decay = nullptr; int64_t ssd_z_floats = 0, ssd_decay_floats = 0;   // chunk-parallel SSD scan scratch (mamba.h)
     SampleBufs samp;             // nvl_sample scratch
+    LogprobBufs lpb;             // nvl_logprobs / nvl_score scratch
     int32_t* samp_hist = nullptr; int32_t* samp_hist_len = nullptr; int64_t samp_hist_cap = 0;   // nvl_decode_sampled: device-kept histories
     float* samp_u_steps = nullptr; int64_t samp_u_cap = 0;
     int last_rows = 0;           // logits rows the last forward left in `logits`

@@ -91,6 +91,21 @@ void free_sample_bufs(SampleBufs& b) {
     b = SampleBufs{};
 }
 
+void free_logprob_bufs(LogprobBufs& b) {
+    dfree(b.part); dfree(b.io);
+    b = LogprobBufs{};
+}
+// room for one launch over `launch_rows` rows and for the per-row inputs / outputs of `io_rows` rows
+void reserve_logprob_bufs(LogprobBufs& b, int64_t launch_rows, int64_t io_rows, int V) {
+    const int64_t words = logprob_part_words(launch_rows, V, LOGPROB_MAX_K);
+    if (words > b.part_words) { dfree(b.part); b.part = nullptr; b.part_words = 0; b.part = dmalloc<int32_t>(words); b.part_words = words; }
+    if (io_rows > b.io_rows) {
+        dfree(b.io); b.io = nullptr; b.io_rows = 0;
+        const int64_t cap = round_up(io_rows, 64);
+        b.io = dmalloc<int32_t>(cap * (3 + 2 * LOGPROB_MAX_K)); b.io_rows = cap;
+    }
+}
+
 bool is_1d(int kind) {
     switch (kind) {
         case NVL_T_FINAL_NORM_W: case NVL_T_FINAL_NORM_B: case NVL_T_ATTN_NORM_W: case NVL_T_ATTN_NORM_B:
@@ -377,6 +392,7 @@ extern "C" void nvl_destroy(nvl_model* m) {
     dfree(m->conv_tail); dfree(m->stamp_buf); dfree(m->ssd_z); dfree(m->ssd_decay);
     dfree(m->ssm_state); dfree(m->mproj); dfree(m->mxbc); dfree(m->mdelta); dfree(m->my); dfree(m->myn);
     free_sample_bufs(m->samp);
+    free_logprob_bufs(m->lpb);
     dfree(m->samp_hist); dfree(m->samp_hist_len); dfree(m->samp_u_steps);
     if (m->tp_comm) (void)ncclCommDestroy((ncclComm_t)m->tp_comm);
     if (m->tp_local) {
@@ -2056,8 +2072,14 @@ void tap_layer(nvl_model* m, int li, int M) {
 // seam: 0 = whole pass; bit 0 = x and layer 0's normed operand are already in place (skip embed + first norm);
 // bit 1 = stop after the argmax partials (the caller's decode_seam_kernel finishes the step); bit 2 = no argmax at
 // all (the caller samples from the logits)
+// Either tail leaves LogitsScaling APPLIED IN PLACE in m->logits (argmax_partial_kernel writes the divided value back,
+// scale_rows_kernel is the division itself): nvl_sample and nvl_logprobs read final logits and never divide again.
+// `sc` != NULL (nvl_score; flags carry NVL_FWD_ALL_LOGITS): the tail is final norm over every row, then LM head +
+// logprob kernels over chunks of at most g_score_rows rows; no logits rows are left (last_rows = 0).
+struct ScoreReq { int top_k; bool want_topk; };
+static int g_score_rows = 1024;   // nvl_set_tuning key 37: rows per LM-head + logprob chunk of nvl_score (a multiple of 16)
 int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len, double attn_flops, uint32_t flags,
-                    int seam = 0) {
+                    int seam = 0, const ScoreReq* sc = nullptr) {
     const nvl_model_config& c = m->cfg;
     const int H = m->H;
     m->kv_written = true;                  // (nvl_set_kv_scales is refused from here on)
@@ -2281,7 +2303,7 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
 
     // ---- final norm + LM head on the rows the caller keeps (generic_model.go:464-477, :595-604) ----
     const bool all = (flags & NVL_FWD_ALL_LOGITS) != 0;
-    const int rows = all ? M : n_seqs;
+    const int rows = sc ? std::min(M, g_score_rows) : (all ? M : n_seqs);      // rows of m->logits this pass needs
     if (rows > m->logit_rows) {
         clear_graphs(m);               // (captured passes hold the old addresses)
         dfree(m->logits); dfree(m->xn_last);
@@ -2289,6 +2311,33 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
         m->xn_last = dmalloc_bytes(round_up(rows, 64) * H * (int64_t)m->wsize);
         NVL_HIP(hipMemsetAsync(m->xn_last, 0, (size_t)(round_up(rows, 64) * H) * m->wsize, m->stream));
         m->logit_rows = rows;
+    }
+    if (sc) {
+        // ONE final norm over all M rows (the launch an all-logits pass makes: it also completes a pending split-K
+        // residual) into m->xn, free by now; then per chunk of `rows` rows: its normed rows -> xn_last (whole 16-row
+        // tiles of the fragment-major operand are contiguous: chunk starts are multiples of 16), LM head, logprob kernels.
+        if (xn_deferred) throw std::runtime_error("score: deferred final norm on the all-rows path");
+        norm(m, m->x, nullptr, m->g[NVL_T_FINAL_NORM_W], m->g[NVL_T_FINAL_NORM_B], m->xn, M);
+        if (m->pending_slices != 0) throw std::runtime_error("forward: a split-K residual was left unconsumed");
+        const LogprobBufs& b = m->lpb;
+        for (int r0 = 0; r0 < M; r0 += rows) {
+            const int n = std::min(rows, M - r0);
+            const size_t row_bytes = (size_t)H * m->wsize;
+            NVL_HIP(hipMemcpyAsync(m->xn_last, (const char*)m->xn + (size_t)r0 * row_bytes,
+                                   (size_t)(m->f32 ? n : round_up(n, 16)) * row_bytes, hipMemcpyDeviceToDevice, m->stream));
+            m->site = KS_LM_HEAD;
+            gemm(m, EPI_STORE, true, mk(m->xn_last, H, m->lm_head, m->logits, m->Vpad, nullptr, 1.f, n, m->V, H));
+            KScope ks(m, KC_OTHER, 0, KS_LOGPROBS, (double)n * m->V * 4.0);
+            LogprobArgs a{};
+            a.x = m->logits; a.ld = m->Vpad; a.V = m->V; a.top_k = sc->want_topk ? sc->top_k : 0; a.scaling = c.logits_scaling;
+            a.targets = b.targets() + r0; a.logprob = b.logprob() + r0; a.argmax = b.argmax() + r0;
+            a.topk_ids = b.topk_ids() + (int64_t)r0 * a.top_k; a.topk_lp = b.topk_lp() + (int64_t)r0 * a.top_k;
+            launch_logprobs(m->stream, a, n, b.part);
+            NVL_HIP(hipGetLastError());
+        }
+        m->last_rows = 0;
+        m->ctx_hint = 0;
+        return M;
     }
     if (xn_deferred) {       // the last FFN-down projection already produced the final norm's operand for every row
         GemmArgs al = mk(m->xn, H, m->lm_head, m->logits, m->Vpad, nullptr, 1.f, rows, m->V, H);
@@ -2334,9 +2383,34 @@ __global__ void advance_decode_kernel(const int32_t* __restrict__ argmax, int32_
 }
 }  // namespace
 
-extern "C" int nvl_forward(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* tokens,
-                           const int32_t* seq_lens, const int32_t* pos_offsets, uint32_t flags,
-                           float* logits_out, int32_t* argmax_out) {
+namespace {
+// what nvl_score / nvl_score_paged return instead of logits: host pointers, [sum(seq_lens)] rows (any may be NULL)
+struct ScoreOut { const int32_t* targets; int top_k; float* logprob; int32_t* argmax; int32_t* topk_ids; float* topk_lp; };
+// before the pass: refusals, device room, targets upload.  Returns NVL_OK or the refusal (m->err set).
+int score_prepare(nvl_model* m, const ScoreOut& so, int M, const char* who) {
+    if (m->tp > 1 || m->tp_force) return fail(m, NVL_ERR_STATE, std::string(who) + ": tensor-parallel models are not supported");
+    if (so.top_k < 0 || so.top_k > LOGPROB_MAX_K) return fail(m, NVL_ERR_INVALID, std::string(who) + ": top_k outside [0, 8]");
+    if (!so.targets) return fail(m, NVL_ERR_INVALID, std::string(who) + ": null targets");
+    for (int i = 0; i < M; i++)
+        if (so.targets[i] < -1 || so.targets[i] >= m->V) return fail(m, NVL_ERR_INVALID, std::string(who) + ": target id outside [-1, V)");
+    reserve_logprob_bufs(m->lpb, std::min(M, g_score_rows), M, m->V);
+    NVL_HIP(hipMemcpyAsync(m->lpb.targets(), so.targets, (size_t)M * 4, hipMemcpyHostToDevice, m->stream));
+    return NVL_OK;
+}
+// after the pass is enqueued: the per-row results to the host (the caller synchronises the stream)
+void score_download(nvl_model* m, const ScoreOut& so, int M) {
+    const LogprobBufs& b = m->lpb;
+    if (so.logprob) NVL_HIP(hipMemcpyAsync(so.logprob, b.logprob(), (size_t)M * 4, hipMemcpyDeviceToHost, m->stream));
+    if (so.argmax) NVL_HIP(hipMemcpyAsync(so.argmax, b.argmax(), (size_t)M * 4, hipMemcpyDeviceToHost, m->stream));
+    if (so.top_k > 0 && so.topk_ids) NVL_HIP(hipMemcpyAsync(so.topk_ids, b.topk_ids(), (size_t)M * so.top_k * 4, hipMemcpyDeviceToHost, m->stream));
+    if (so.top_k > 0 && so.topk_lp) NVL_HIP(hipMemcpyAsync(so.topk_lp, b.topk_lp(), (size_t)M * so.top_k * 4, hipMemcpyDeviceToHost, m->stream));
+}
+
+// nvl_forward, and nvl_score when `so` != NULL (the same validation, KV append and state update; flags then carry
+// NVL_FWD_ALL_LOGITS and logits_out / argmax_out are NULL)
+int forward_slab(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* tokens,
+                 const int32_t* seq_lens, const int32_t* pos_offsets, uint32_t flags,
+                 float* logits_out, int32_t* argmax_out, const ScoreOut* so) {
     if (!m) return NVL_ERR_INVALID;
     if (!m->finalized) return fail(m, NVL_ERR_STATE, "nvl_forward: model not finalized");
     if (n_seqs <= 0 || !seq_ids || !tokens || !seq_lens || !pos_offsets)
@@ -2378,6 +2452,8 @@ extern "C" int nvl_forward(nvl_model* m, int n_seqs, const int64_t* seq_ids, con
         }
         h_last[i] = t - 1;
     }
+    const ScoreReq sreq{so ? so->top_k : 0, so && so->top_k > 0 && (so->topk_ids || so->topk_lp)};
+    if (so) { const int rc = score_prepare(m, *so, M, "nvl_score"); if (rc) return rc; }
     const Meta md = bind_meta(m, m->meta_dev, M);
     NVL_HIP(hipEventRecord(m->ev0, m->stream));
 
@@ -2394,7 +2470,7 @@ extern "C" int nvl_forward(nvl_model* m, int n_seqs, const int64_t* seq_ids, con
     std::vector<int32_t> am;
     const int32_t* am_p = nullptr;
     bool replayed = false;
-    if (!prefill && rows <= m->logit_rows) {
+    if (!so && !prefill && rows <= m->logit_rows) {
         // a decode pass (what TensorModelRunner.Run issues every step): metadata upload + all launches + the argmax
         // download as ONE graph launch once this configuration has been seen
         const std::array<int, 5> key{0, n_seqs, decode_attn_waves(m, n_seqs), (int)flags, g_tune_epoch};
@@ -2407,19 +2483,20 @@ extern "C" int nvl_forward(nvl_model* m, int n_seqs, const int64_t* seq_ids, con
     }
     if (!replayed) {
         NVL_HIP(hipMemcpyAsync(m->meta_dev, m->meta_host, meta_bytes(m, M), hipMemcpyHostToDevice, m->stream));
-        rows = enqueue_forward(m, md, n_seqs, M, max_len, attn_flops, flags);
+        rows = enqueue_forward(m, md, n_seqs, M, max_len, attn_flops, flags, 0, so ? &sreq : nullptr);
         am.resize((size_t)rows);
-        NVL_HIP(hipMemcpyAsync(am.data(), m->argmax_dev, (size_t)rows * 4, hipMemcpyDeviceToHost, m->stream));
+        if (!so) NVL_HIP(hipMemcpyAsync(am.data(), m->argmax_dev, (size_t)rows * 4, hipMemcpyDeviceToHost, m->stream));
         am_p = am.data();
     }
     NVL_HIP(hipEventRecord(m->ev1, m->stream));
+    if (so) score_download(m, *so, M);
     if (logits_out)
         NVL_HIP(hipMemcpy2DAsync(logits_out, (size_t)m->V * 4, m->logits, (size_t)m->Vpad * 4, (size_t)m->V * 4,
                                  (size_t)rows, hipMemcpyDeviceToHost, m->stream));
     NVL_HIP(hipStreamSynchronize(m->stream));
     reap_graphs(m);
     p2p_check(m);
-    m->last_rows = rows;
+    m->last_rows = so ? 0 : rows;        // (a scoring pass leaves no logits rows: nvl_sample / nvl_logprobs are refused after it)
     if (argmax_out) {
         if (all) for (int i = 0; i < n_seqs; i++) argmax_out[i] = am_p[(size_t)h_last[i]];
         else for (int i = 0; i < n_seqs; i++) argmax_out[i] = am_p[(size_t)i];
@@ -2434,12 +2511,28 @@ extern "C" int nvl_forward(nvl_model* m, int n_seqs, const int64_t* seq_ids, con
     return NVL_OK;
     NVL_CATCH(m)
 }
+}  // namespace
+
+extern "C" int nvl_forward(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* tokens,
+                           const int32_t* seq_lens, const int32_t* pos_offsets, uint32_t flags,
+                           float* logits_out, int32_t* argmax_out) {
+    return forward_slab(m, n_seqs, seq_ids, tokens, seq_lens, pos_offsets, flags, logits_out, argmax_out, nullptr);
+}
+// nvl_forward returning per NEW token row its target's log-probability, the greedy id and the top-k instead of logits
+// (the checks and their messages are nvl_forward's own)
+extern "C" int nvl_score(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, const int32_t* seq_lens,
+                         const int32_t* pos_offsets, const int32_t* targets, int top_k, float* logprob_out,
+                         int32_t* argmax_out, int32_t* topk_ids_out, float* topk_logprob_out) {
+    const ScoreOut so{targets, top_k, logprob_out, argmax_out, topk_ids_out, topk_logprob_out};
+    return forward_slab(m, n_seqs, seq_ids, tokens, seq_lens, pos_offsets, NVL_FWD_ALL_LOGITS, nullptr, nullptr, &so);
+}
 
 // nvl_forward for a model whose KV cache is the host block manager's pool (block_manager.go:128-263,
 // sequence.go:22-23): no per-sequence state here, the block tables say where every position lives.
-extern "C" int nvl_forward_paged(nvl_model* m, int n_seqs, const int32_t* tokens, const int32_t* seq_lens,
-                                 const int32_t* pos_offsets, const int32_t* block_tables, const int32_t* table_offsets,
-                                 uint32_t flags, float* logits_out, int32_t* argmax_out) {
+namespace {
+int forward_paged_impl(nvl_model* m, int n_seqs, const int32_t* tokens, const int32_t* seq_lens,
+                       const int32_t* pos_offsets, const int32_t* block_tables, const int32_t* table_offsets,
+                       uint32_t flags, float* logits_out, int32_t* argmax_out, const ScoreOut* so) {
     if (!m) return NVL_ERR_INVALID;
     if (!m->finalized) return fail(m, NVL_ERR_STATE, "nvl_forward_paged: model not finalized");
     if (!m->paged) return fail(m, NVL_ERR_STATE, "nvl_forward_paged: the model was created without kv_num_blocks");
@@ -2484,6 +2577,8 @@ extern "C" int nvl_forward_paged(nvl_model* m, int n_seqs, const int32_t* tokens
         }
         hm.last_rows[i] = t - 1;
     }
+    const ScoreReq sreq{so ? so->top_k : 0, so && so->top_k > 0 && (so->topk_ids || so->topk_lp)};
+    if (so) { const int rc = score_prepare(m, *so, M, "nvl_score_paged"); if (rc) return rc; }
     const Meta md = bind_meta(m, m->meta_dev, M);
     NVL_HIP(hipEventRecord(m->ev0, m->stream));
     NVL_HIP(hipMemcpyAsync(m->meta_dev, m->meta_host, meta_bytes(m, M), hipMemcpyHostToDevice, m->stream));
@@ -2496,10 +2591,11 @@ extern "C" int nvl_forward_paged(nvl_model* m, int n_seqs, const int32_t* tokens
     }
     m->kv_tok = kv_tok;
     const bool all = (flags & NVL_FWD_ALL_LOGITS) != 0;
-    const int rows = enqueue_forward(m, md, n_seqs, M, max_len, attn_flops, flags);
+    const int rows = enqueue_forward(m, md, n_seqs, M, max_len, attn_flops, flags, 0, so ? &sreq : nullptr);
     NVL_HIP(hipEventRecord(m->ev1, m->stream));
     std::vector<int32_t> am((size_t)rows);
-    NVL_HIP(hipMemcpyAsync(am.data(), m->argmax_dev, (size_t)rows * 4, hipMemcpyDeviceToHost, m->stream));
+    if (so) score_download(m, *so, M);
+    else NVL_HIP(hipMemcpyAsync(am.data(), m->argmax_dev, (size_t)rows * 4, hipMemcpyDeviceToHost, m->stream));
     if (logits_out)
         NVL_HIP(hipMemcpy2DAsync(logits_out, (size_t)m->V * 4, m->logits, (size_t)m->Vpad * 4, (size_t)m->V * 4,
                                  (size_t)rows, hipMemcpyDeviceToHost, m->stream));
@@ -2516,6 +2612,20 @@ extern "C" int nvl_forward_paged(nvl_model* m, int n_seqs, const int32_t* tokens
     if (m->profile) drain_profile(m);
     return NVL_OK;
     NVL_CATCH(m)
+}
+}  // namespace
+
+extern "C" int nvl_forward_paged(nvl_model* m, int n_seqs, const int32_t* tokens, const int32_t* seq_lens,
+                                 const int32_t* pos_offsets, const int32_t* block_tables, const int32_t* table_offsets,
+                                 uint32_t flags, float* logits_out, int32_t* argmax_out) {
+    return forward_paged_impl(m, n_seqs, tokens, seq_lens, pos_offsets, block_tables, table_offsets, flags, logits_out, argmax_out, nullptr);
+}
+extern "C" int nvl_score_paged(nvl_model* m, int n_seqs, const int32_t* tokens, const int32_t* seq_lens,
+                               const int32_t* pos_offsets, const int32_t* block_tables, const int32_t* table_offsets,
+                               const int32_t* targets, int top_k, float* logprob_out, int32_t* argmax_out,
+                               int32_t* topk_ids_out, float* topk_logprob_out) {
+    const ScoreOut so{targets, top_k, logprob_out, argmax_out, topk_ids_out, topk_logprob_out};
+    return forward_paged_impl(m, n_seqs, tokens, seq_lens, pos_offsets, block_tables, table_offsets, NVL_FWD_ALL_LOGITS, nullptr, nullptr, &so);
 }
 
 // ModelRunner.Run over block tables: what a runner that honours Sequence.BlockTable / NumCachedTokens does
@@ -3014,7 +3124,7 @@ extern "C" int nvl_reset_stats(nvl_model* m) {
 static const char* const k_site_names[KS_COUNT] = {
     "other", "qkv_proj", "attention", "o_proj", "ffn_up", "ffn_down", "lm_head", "norm", "moe_router", "moe_plan", "moe_up",
     "moe_down", "moe_combine", "embed", "argmax", "rope_kv", "mamba_in_proj", "mamba_conv", "mamba_scan", "mamba_gate_norm",
-    "mamba_out_proj", "tp_allreduce"};
+    "mamba_out_proj", "tp_allreduce", "logprobs"};
 extern "C" const char* nvl_kernel_site_name(int site) { return site >= 0 && site < KS_COUNT ? k_site_names[site] : ""; }
 extern "C" int nvl_get_kernel_stats(nvl_model* m, nvl_kernel_stat* out, int cap) {
     if (!m || (cap > 0 && !out)) return NVL_ERR_INVALID;
@@ -3098,6 +3208,57 @@ extern "C" int nvl_sample(nvl_model* m, int n_rows, const nvl_sampling_params* p
     const int rc = sample_rows(m->stream, m->samp, m->logits, m->Vpad, n_rows, m->V, params, history_ptrs, history_lens,
                                uniforms, out_tokens, nullptr, err);
     return rc ? fail(m, rc, "nvl_sample: " + err) : NVL_OK;
+    NVL_CATCH(m)
+}
+
+// =================================================================================================
+// log-probabilities on the device (logprob.h): what generic_model.go:467-470 / :595-604 logits are turned into by a
+// perplexity tool or a server's `logprobs` (cmd/check-logits/main.go prints logits; nothing in the reference reduces them)
+// =================================================================================================
+namespace {
+// rows of device logits -> per-row results on the host.  `scaling`: the LogitsScaling divisor still to apply (0 = none).
+int logprob_rows(hipStream_t st, LogprobBufs& b, const float* logits_dev, int64_t ld, int rows, int V, float scaling,
+                 const int32_t* targets, int top_k, float* logprob_out, int32_t* argmax_out, int32_t* topk_ids_out,
+                 float* topk_lp_out, std::string& err) {
+    if (rows <= 0 || V <= 0 || ld < V) { err = "bad shape"; return NVL_ERR_INVALID; }
+    if (top_k < 0 || top_k > LOGPROB_MAX_K) { err = "top_k outside [0, 8]"; return NVL_ERR_INVALID; }
+    if (targets)
+        for (int i = 0; i < rows; i++)
+            if (targets[i] < -1 || targets[i] >= V) { err = "target id outside [-1, V)"; return NVL_ERR_INVALID; }
+    reserve_logprob_bufs(b, rows, rows, V);
+    if (targets) NVL_HIP(hipMemcpyAsync(b.targets(), targets, (size_t)rows * 4, hipMemcpyHostToDevice, st));
+    LogprobArgs a{};
+    a.x = logits_dev; a.ld = ld; a.V = V; a.scaling = scaling;
+    a.top_k = (topk_ids_out || topk_lp_out) ? top_k : 0;
+    a.targets = targets ? b.targets() : nullptr; a.logprob = b.logprob(); a.argmax = b.argmax();
+    a.topk_ids = b.topk_ids(); a.topk_lp = b.topk_lp();
+    launch_logprobs(st, a, rows, b.part);
+    NVL_HIP(hipGetLastError());
+    if (logprob_out) NVL_HIP(hipMemcpyAsync(logprob_out, b.logprob(), (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+    if (argmax_out) NVL_HIP(hipMemcpyAsync(argmax_out, b.argmax(), (size_t)rows * 4, hipMemcpyDeviceToHost, st));
+    if (a.top_k > 0 && topk_ids_out) NVL_HIP(hipMemcpyAsync(topk_ids_out, b.topk_ids(), (size_t)rows * top_k * 4, hipMemcpyDeviceToHost, st));
+    if (a.top_k > 0 && topk_lp_out) NVL_HIP(hipMemcpyAsync(topk_lp_out, b.topk_lp(), (size_t)rows * top_k * 4, hipMemcpyDeviceToHost, st));
+    NVL_HIP(hipStreamSynchronize(st));
+    return NVL_OK;
+}
+}  // namespace
+
+extern "C" int nvl_logprobs(nvl_model* m, int n_rows, const int32_t* targets, int top_k, float* logprob_out,
+                            int32_t* argmax_out, int32_t* topk_ids_out, float* topk_logprob_out) {
+    if (!m) return NVL_ERR_INVALID;
+    if (!m->finalized) return fail(m, NVL_ERR_STATE, "nvl_logprobs: model not finalized");
+    if (n_rows <= 0 || n_rows > m->last_rows) return fail(m, NVL_ERR_INVALID, "nvl_logprobs: n_rows exceeds the logits rows of the last forward");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    std::string err;
+    int rc;
+    {   // every forward tail has applied LogitsScaling in place (enqueue_forward): scaling 0 here, never twice
+        KScope ks(m, KC_OTHER, 0, KS_LOGPROBS, (double)n_rows * m->V * 4.0);
+        rc = logprob_rows(m->stream, m->lpb, m->logits, m->Vpad, n_rows, m->V, 0.f, targets, top_k, logprob_out, argmax_out,
+                          topk_ids_out, topk_logprob_out, err);
+    }
+    if (m->profile) { NVL_HIP(hipStreamSynchronize(m->stream)); drain_profile(m); }
+    return rc ? fail(m, rc, "nvl_logprobs: " + err) : NVL_OK;
     NVL_CATCH(m)
 }
 

@@ -548,6 +548,23 @@ extern "C" int nvl_op_sample(int device, const float* logits, int rows, int V, c
     OP_CATCH
 }
 
+extern "C" int nvl_op_logprobs(int device, const float* logits, int rows, int V, int ld, float logits_scaling,
+                               const int32_t* targets, int top_k, float* logprob_out, int32_t* argmax_out,
+                               int32_t* topk_ids_out, float* topk_logprob_out) {
+    if (!logits || rows <= 0 || V <= 0 || ld < V) return op_fail("nvl_op_logprobs: bad arguments");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_F32);
+    float* L = cx.up_f32(logits, (int64_t)rows * ld);
+    LogprobBufs b;
+    std::string err;
+    int rc;
+    try { rc = logprob_rows(cx.m.stream, b, L, ld, rows, V, logits_scaling, targets, top_k, logprob_out, argmax_out, topk_ids_out, topk_logprob_out, err); }
+    catch (...) { free_logprob_bufs(b); throw; }
+    free_logprob_bufs(b);
+    return rc ? op_fail("nvl_op_logprobs: " + err, rc) : NVL_OK;
+    OP_CATCH
+}
+
 extern "C" int nvl_bench_gemm(int device, int M, int N, int K, int epi, int force_bnt, int force_ksplit, int iters,
                               float* avg_us) {
     if (!avg_us || M <= 0 || N <= 0 || K % 64 || iters <= 0) return op_fail("nvl_bench_gemm: bad arguments");
@@ -630,5 +647,6 @@ extern "C" int nvl_set_tuning(int key, int value) {
     if (key == 33) { const int old = g_moe_defer_down; g_moe_defer_down = value; return old; }
     if (key == 35) { const int old = g_attn_kv_nt; g_attn_kv_nt = value; return old; }
     if (key == 36) { const int old = g_wide_ntb; g_wide_ntb = value; return old; }
+    if (key == 37) { const int old = g_score_rows; g_score_rows = value < 16 ? 16 : (value + 15) / 16 * 16; return old; }
     return -1;
 }

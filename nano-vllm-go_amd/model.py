@@ -363,6 +363,72 @@ class HipTransformerModel:
         L.check(self.lib.nvl_sample(self.h, n, C.byref(sp), ptrs, _ptr(lens), _ptr(u), _ptr(out)), self.h)
         return out
 
+    # -- log-probabilities (logprob.h) ------------------------------------------------------------------
+    def _score_args(self, token_lists, targets, top_k):
+        """-> (lens, tokens, targets, output arrays) of a scoring call; the default targets are each list's next token,
+        -1 for its last row.  Length mismatches raise ValueError before any library call."""
+        lens = np.asarray([len(t) for t in token_lists], np.int32)
+        if len(token_lists) == 0 or (lens <= 0).any():
+            raise ValueError("score: every sequence needs at least one token")
+        if targets is None:
+            targets = [list(t[1:]) + [-1] for t in token_lists]
+        if len(targets) != len(token_lists):
+            raise ValueError(f"score: {len(targets)} target lists for {len(token_lists)} sequences")
+        for i, (t, g) in enumerate(zip(token_lists, targets)):
+            if len(g) != len(t):
+                raise ValueError(f"score: sequence {i} has {len(t)} tokens but {len(g)} targets")
+        if not 0 <= int(top_k) <= 8:
+            raise ValueError("score: top_k must be in [0, 8]")
+        toks = np.concatenate([np.asarray(t, np.int32) for t in token_lists]).astype(np.int32)
+        tg = np.concatenate([np.asarray(g, np.int32) for g in targets]).astype(np.int32)
+        rows = int(lens.sum())
+        out = (np.empty(rows, np.float32), np.empty(rows, np.int32),
+               np.empty((rows, top_k), np.int32) if top_k else None, np.empty((rows, top_k), np.float32) if top_k else None)
+        return lens, toks, tg, out
+
+    @staticmethod
+    def _per_seq(lens, out):
+        cuts = np.cumsum(lens)[:-1]
+        return tuple(None if a is None else np.split(a, cuts) for a in out)
+
+    def score(self, seq_ids, token_lists, pos_offsets, targets=None, top_k=0):
+        """nvl_score: nvl_forward (KV append included) returning per new token row the log-probability of its target (default:
+        the next token of its list; -1 = none -> 0.0), the greedy id and the top_k ids / log-probabilities instead of logits.
+        -> (logprobs, argmax, topk_ids, topk_logprobs): per-sequence lists of arrays [len] / [len, top_k] (None when top_k == 0)."""
+        if not (len(seq_ids) == len(token_lists) == len(pos_offsets)):
+            raise ValueError("score: seq_ids, token_lists and pos_offsets differ in length")
+        lens, toks, tg, out = self._score_args(token_lists, targets, top_k)
+        ids = np.asarray(seq_ids, np.int64)
+        pos = np.asarray(pos_offsets, np.int32)
+        L.check(self.lib.nvl_score(self.h, len(lens), _ptr(ids), _ptr(toks), _ptr(lens), _ptr(pos), _ptr(tg), int(top_k),
+                                   _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3])), self.h)
+        return self._per_seq(lens, out)
+
+    def score_paged(self, token_lists, pos_offsets, block_tables, targets=None, top_k=0):
+        """nvl_score_paged: score() over the sequences' block tables (forward_paged's arguments)."""
+        if not (len(token_lists) == len(pos_offsets) == len(block_tables)):
+            raise ValueError("score_paged: token_lists, pos_offsets and block_tables differ in length")
+        lens, toks, tg, out = self._score_args(token_lists, targets, top_k)
+        pos = np.asarray(pos_offsets, np.int32)
+        tbl = np.concatenate([np.asarray(b, np.int32) for b in block_tables]).astype(np.int32)
+        off = np.concatenate([[0], np.cumsum([len(b) for b in block_tables])]).astype(np.int32)
+        L.check(self.lib.nvl_score_paged(self.h, len(lens), _ptr(toks), _ptr(lens), _ptr(pos), _ptr(tbl), _ptr(off), _ptr(tg),
+                                         int(top_k), _ptr(out[0]), _ptr(out[1]), _ptr(out[2]), _ptr(out[3])), self.h)
+        return self._per_seq(lens, out)
+
+    def logprobs(self, targets, top_k=0):
+        """nvl_logprobs on the logits rows the last forward left on the device (the rows sample() sees), one target per
+        row (-1 = none).  -> (logprobs [n], argmax [n], topk_ids [n, top_k] or None, topk_logprobs or None)."""
+        tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+        n = tg.size
+        if not 0 <= int(top_k) <= 8:
+            raise ValueError("logprobs: top_k must be in [0, 8]")
+        lp, am = np.empty(n, np.float32), np.empty(n, np.int32)
+        ti = np.empty((n, top_k), np.int32) if top_k else None
+        tl = np.empty((n, top_k), np.float32) if top_k else None
+        L.check(self.lib.nvl_logprobs(self.h, n, _ptr(tg), int(top_k), _ptr(lp), _ptr(am), _ptr(ti), _ptr(tl)), self.h)
+        return lp, am, ti, tl
+
     # -- debug / parity taps ------------------------------------------------------------------------
     def set_debug(self, keep_hidden: bool):
         L.check(self.lib.nvl_set_debug(self.h, int(keep_hidden)), self.h)

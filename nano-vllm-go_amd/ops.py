@@ -172,6 +172,37 @@ def argmax(x, device=0):                                       # argmax cmd/ask/
     return out
 
 
+def logprobs(logits, targets, top_k=0, logits_scaling=0.0, ld=None, device=0):   # logprob.h on host logits
+    """Per row of logits [rows, V]: the log-probability of targets[row] (-1 = none -> 0.0) under softmax(logits /
+    logits_scaling) (0 = no scaling), the greedy id, and the top_k ids / log-probabilities.
+    ld=None: the rows are passed densely.  ld=n: `logits` is the float32 view buf[:, :V] of a buffer buf [rows, n] and the
+    rows are passed as they lie in memory, pad columns included (what the model's [rows][Vpad] logits look like).
+    -> (logprobs [rows], argmax [rows], topk_ids [rows, top_k] or None, topk_logprobs or None)."""
+    if ld is None:
+        lg = _f(logits)
+        if lg.ndim == 1:
+            lg = lg[None]
+        rows, V = lg.shape
+        stride = V
+    else:
+        lg, stride = logits, int(ld)
+        if not isinstance(lg, np.ndarray) or lg.dtype != np.float32 or lg.ndim != 2:
+            raise ValueError("logprobs: with ld, logits must be a 2-D float32 numpy view")
+        rows, V = lg.shape
+        if V > stride or lg.strides != (stride * 4, 4) or lg.base is None or lg.base.size < rows * stride:
+            raise ValueError(f"logprobs: logits is not the [:, :{V}] view of a [rows, {stride}] buffer")
+    tg = np.ascontiguousarray(targets, dtype=np.int32).reshape(-1)
+    if tg.size != rows:
+        raise ValueError(f"logprobs: {tg.size} targets for {rows} rows")
+    top_k = int(top_k)
+    lp, am = np.empty(rows, np.float32), np.empty(rows, np.int32)
+    ti = np.empty((rows, top_k), np.int32) if top_k > 0 else None
+    tl = np.empty((rows, top_k), np.float32) if top_k > 0 else None
+    L.check(L.lib().nvl_op_logprobs(device, _p(lg), rows, V, stride, float(logits_scaling), _p(tg), top_k, _p(lp), _p(am),
+                                    _p(ti), _p(tl)))
+    return lp, am, ti, tl
+
+
 def _histories(histories, rows):
     """-> (pointer array, int32 lengths, keep-alive list) for `rows` token histories (None = no history)."""
     arrs = [np.ascontiguousarray([] if h is None else h, dtype=np.int32) for h in (histories or [None] * rows)]
