@@ -368,6 +368,49 @@ int nvl_get_kv_paged(nvl_model* m, const int32_t* block_table, int n_blocks, int
 int nvl_decode_greedy(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
                       int32_t* out_tokens);
 
+/* Greedy speculative decoding.  The reference generates one token per pass (cmd/ask/main.go:315-360: the
+ * loop; generic_model.go:276-480: the pass); these calls run the same pass over 1 + k rows per sequence and keep the longest
+ * draft prefix the model itself would have produced greedily.
+ *
+ * nvl_verify_greedy: tokens [n_seqs][1+k] — tokens[i][0] is sequence i's next input token (what first_tokens carries for
+ * nvl_decode_greedy), tokens[i][1..k] the draft.  One pass at positions P_i .. P_i + k (P_i = the cached length); the greedy
+ * id g[i][j] of every row is computed on the device, a_i = the length of the longest prefix with tokens[i][j+1] == g[i][j].
+ * n_accepted_out[i] = a_i; out_tokens [n_seqs][1+k]: out_tokens[i][0..a_i] = g[i][0..a_i], the rest -1.  Afterwards the
+ * cached length is P_i + a_i + 1 (rows behind it are dead and get overwritten).  Only n_seqs x (2 + k) int32 come back; the
+ * n_seqs x (1+k) logits rows stay as the last forward group, in token order, for nvl_logprobs / nvl_sample.
+ * In bf16 with a bf16 cache the pass runs the multi-position decode attention (nvl_set_tuning key 38); in f32 and over an
+ * 8-bit cache it runs the existing kernels.  A pass of at most 64 rows whose shape was seen before is replayed as a graph.
+ * k outside 1..7 or n_seqs x (1+k) > max_batch_tokens: NVL_ERR_INVALID; P_i + 1 + k > max_seq_len: NVL_ERR_POSITION; no
+ * slot: NVL_ERR_UNKNOWN_SEQ; a model with Mamba2 layers (its state cannot be rolled back), a tensor-parallel model or a
+ * paged model: NVL_ERR_STATE.  A refused call changes no length. */
+int nvl_verify_greedy(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, int k,
+                      int32_t* n_accepted_out, int32_t* out_tokens);
+/* nvl_verify_greedy for a paged-KV model: nvl_forward_paged's table arguments, pos_offsets[i] = P_i; the tables must cover
+ * P_i + 1 + k tokens.  The library keeps no lengths in this mode: the caller advances by a_i + 1. */
+int nvl_verify_greedy_paged(nvl_model* m, int n_seqs, const int32_t* tokens, int k, const int32_t* pos_offsets,
+                            const int32_t* block_tables, const int32_t* table_offsets, int32_t* n_accepted_out,
+                            int32_t* out_tokens);
+/* Roll a slab sequence back to new_len <= its cached length (longer or negative: NVL_ERR_INVALID; a Mamba2 model or a
+ * paged model: NVL_ERR_STATE). */
+int nvl_seq_truncate(nvl_model* m, int64_t seq_id, int new_len);
+/* Prompt-lookup drafting; pure host code, callable without a device.  For g = min(ngram, n-1) down to 1: the largest
+ * s < n - g with history[s..s+g) == history[n-g..n); the draft is the tokens after that match, up to k of them, missing
+ * entries repeating the last one taken.  No match at any g: every entry is history[n-1].  Returns the number of real
+ * (unpadded) draft tokens, or NVL_ERR_INVALID (NULL, n < 1, k < 1). */
+int nvl_lookup_draft(const int32_t* history, int n, int k, int ngram, int32_t* draft_out);
+/* nvl_decode_greedy's contract (out_tokens [n_steps][n_seqs], cached length P_i + n_steps afterwards) driven by
+ * nvl_lookup_draft + nvl_verify_greedy passes over the sequences that still need tokens; an overshoot of the last pass
+ * is truncated.  history_ptrs[i] / history_lens[i]: the sequence's tokens as the first step sees them, ending with
+ * first_tokens[i] (NULL: the history starts at first_tokens[i]).  passes_out (may be NULL): passes run, between
+ * ceil(n_steps / (k+1)) and n_steps.  Slab mode only; refusals as nvl_verify_greedy; an error in a later pass leaves the
+ * sequences where the passes before it put them.
+ * Equivalence to nvl_decode_greedy: the ids are the same wherever the model's top-2 logit margin exceeds the precision's
+ * stated logits tolerance (f32: always in practice).  1 + k rows take other projection forms than one row, so the
+ * logits are not bit-identical. */
+int nvl_decode_greedy_lookup(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
+                             int k, int ngram, const int32_t* const* history_ptrs, const int32_t* history_lens,
+                             int32_t* out_tokens, int32_t* passes_out);
+
 /* Debug/parity: copy the residual stream after layer `layer` of the LAST nvl_forward call,
  * [sum(seq_lens), H] fp32 (requires nvl_set_debug(m, 1 or 2) before the call).  Mode 1 completes every residual add in its
  * own launch (no split-K partials left to the next norm, no deferred RMSNorm, no graph replay): the layer outputs of a
@@ -535,6 +578,11 @@ int nvl_op_rope(int device, float* t, int heads, int seq, int hd, int start_pos,
  * q [nH,S,hd], k/v [nKV,T,hd] (keys 0..T-1, the last S are the new tokens) -> out [nH,S,hd] */
 int nvl_op_attention(int device, int precision, const float* q, const float* k, const float* v,
                      int nH, int nKV, int S, int T, int hd, float scale, float* out);
+/* The multi-position decode attention of a verify pass (generic_model.go:276-480 over S = 2..8 new positions of one
+ * sequence; attn.h attn_decode_mq_bf16_kernel) alone, bf16, whatever nvl_set_tuning key 38 says: nvl_op_attention's
+ * argument conventions. */
+int nvl_op_attention_mq(int device, const float* q, const float* k, const float* v, int nH, int nKV, int S, int T, int hd,
+                        float scale, float* out);
 /* 8-bit KV cache.  The device quantizer and read path on an array: codes[i] = e4m3fn(x[i] / scale)
  * (round-to-nearest-even, saturating to +-448, NaN -> NaN code), back[i] = scale * bf16(codes[i]) in fp32. */
 int nvl_op_fp8_kv_roundtrip(int device, const float* x, int64_t n, float scale, uint8_t* codes, float* back);
@@ -628,6 +676,8 @@ int nvl_bench_gemm(int device, int M, int N, int K, int epi, int force_bnt, int 
  * 0 (default): measured slower (rejected list (27)).
  * key 37: rows per chunk of nvl_score's final norm + LM head + log-probability reduction (default 1024; rounded up to a
  * multiple of 16, at least 16): the logits workspace of a scoring pass is that many rows.
+ * key 38: verify passes (nvl_verify_greedy*, nvl_decode_greedy_lookup) in bf16 over a bf16 cache run the multi-position
+ * decode attention (1, default); 0 = rope_kv + the prefill attention kernel, the route of an nvl_forward of 1 + k rows.
  * The settings are PROCESS-GLOBAL and unsynchronised (every model in the process sees them): set them from one thread
  * while no forward call is running.  Every call starts a new tuning epoch: captured decode graphs bake the tuning in and are re-captured.
  * Returns the previous value. */

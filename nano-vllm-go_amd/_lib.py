@@ -205,6 +205,12 @@ def lib():
     L.nvl_tp_p2p_attach.argtypes = [vp, vp, C.c_int]
     L.nvl_tp_p2p_rearm.argtypes = [vp]
     L.nvl_sizeof.argtypes = [C.c_int]
+    L.nvl_verify_greedy.argtypes = [vp, C.c_int, vp, vp, C.c_int, vp, vp]
+    L.nvl_verify_greedy_paged.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, vp, vp]
+    L.nvl_seq_truncate.argtypes = [vp, i64, C.c_int]
+    L.nvl_lookup_draft.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
+    L.nvl_decode_greedy_lookup.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
+    L.nvl_op_attention_mq.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]
     _lib = L
     return L
 

@@ -461,12 +461,17 @@ __device__ __forceinline__ void rope_math8(const RopeRaw& r, bool rot, bf16x8& l
 
 // The softmax step of a decode round, from the round's masked, scaled scores s (exp2 domain) and their lane maximum tmax:
 // the new running maximum and denominator, s -> P^T, and the rescale of O^T.
-template <int HD, int NT2>
+// GUARD (the multi-position kernel): a row may have seen no key at all so far — its mask limit lies below the tiles this
+// wave was dealt, or it is a padding row — so the maximum may still be -inf; the exponentials then take 0 as their
+// reference (exp2(-inf - 0) = 0: the row's state stays m = -inf, l = 0, O = 0, and no NaN is made).
+template <int HD, int NT2, bool GUARD = false>
 __device__ __forceinline__ void attn_decode_softmax(f32x4 (&s)[NT2][4], float tmax, float& m_run, float& l_run, f32x4 (&o)[HD / 16]) {
     constexpr int DT = HD / 16;
     tmax = fmaxf(tmax, __shfl_xor(tmax, 16, 64));
     tmax = fmaxf(tmax, __shfl_xor(tmax, 32, 64));
-    const float m_new = fmaxf(m_run, tmax);     // finite: the round's first tile kt0 < n_kt holds key kt0*64 <= pos0
+    float m_new = fmaxf(m_run, tmax);           // finite: the round's first tile kt0 < n_kt holds key kt0*64 <= pos0
+    const float m_keep = m_new;
+    if constexpr (GUARD) m_new = m_new == -INFINITY ? 0.f : m_new;
     const float alpha = __builtin_amdgcn_exp2f(m_run - m_new);
     float psum = 0.f;
 #pragma unroll
@@ -480,7 +485,7 @@ __device__ __forceinline__ void attn_decode_softmax(f32x4 (&s)[NT2][4], float tm
                 psum += pv;
             }
     l_run = l_run * alpha + psum;
-    m_run = m_new;
+    m_run = m_keep;
 #pragma unroll
     for (int d = 0; d < DT; d++) o[d] *= alpha;
 }
@@ -825,6 +830,139 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t
     }
     // ---- flash-decoding combine through LDS (the partial O^T overwrites this wave's own V image), fixed wave order ----
     stamps.mark_used(3, o[0]);          // wave 0's tiles done
+    attn_decode_finish<HD, NW>(p, smem, vimg, red_m, red_l, o, m_run, l_run, seq, tok, head, row_ok, wave, lane, fq, fg, 1.0f, stamps);
+}
+
+// ------------------------------------------------------------------------------------------
+// bf16 multi-position decode kernel (a verify pass of speculative decoding: S = 2..8 new positions per sequence, their
+// K/V already in the cache, Q pre-rotated: the FUSED = false form of the kernel above).  A query row is a (position j,
+// head-in-group g) pair, position-major as in the prefill kernel: r = j * group + g < S * group; a workgroup takes 16
+// consecutive rows of one (sequence, kv head), grid.x = nKV * cdiv(S * group, 16).  With group 4 and S = 4 the MFMA tile
+// the one-position kernel fills to a quarter is full, for the same K/V stream.  Row r sees keys 0 .. seq_pos + j: the
+// mask limit is per lane, and the workgroup walks the key tiles of its LAST real row, so a row may find every key of a
+// round masked (attn_decode_softmax<.., GUARD>).  Rows with j >= seq_len or r >= S * group are padding: masked
+// entirely (limit -1), never stored.  Stream, split-T over the waves, kv_nt policy and the combine are the one-position
+// kernel's; keys are never split over workgroups (gridDim.z == 1: the partial-result buffers hold one tile per pair).
+// ------------------------------------------------------------------------------------------
+template <int HD, int NW>
+__global__ __launch_bounds__(NW * 64) void attn_decode_mq_bf16_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
+                                                                      int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p, int S) {
+    constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, KPI = 64 / CPR, NVL = 64 / KPI;
+    constexpr int NT2 = HD <= 64 ? 2 : 1;                    // key tiles whose loads are in flight together, per wave
+    constexpr int TILE_BYTES = 64 * HD * 2;
+    extern __shared__ __attribute__((aligned(16))) char smem[];     // [NW] wave-private V images (later: the partial O^T)
+    __shared__ float red_m[NW][16];
+    __shared__ float red_l[NW][16];
+    NvlStampsT<false> stamps(nullptr, 0);
+    const int QT = (S * a_group + 15) >> 4;
+    const int seq = blockIdx.y, kvh = blockIdx.x / QT, qt = blockIdx.x - kvh * QT;
+    const int32_t* tbl = a_blk_table + (int64_t)seq * a_tbl_stride;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int pos0 = a_seq_pos[seq], tok0 = p.seq_tok_start[seq];
+    const int R = min(p.seq_len[seq], S) * a_group;          // real query rows of this (sequence, kv head)
+    if (qt * 16 >= R) return;                                // (the whole workgroup: a sequence shorter than the batch's longest)
+    const int fq = lane & 15, fg = lane >> 4;                // MFMA role: query row qt*16 + fq, k group fg
+    const int dch = lane % CPR, ksub = lane / CPR;           // row role: 16-byte chunk dch of key row ksub (+ i*KPI)
+    const int r = qt * 16 + fq;
+    const bool row_ok = r < R;
+    const int rc = row_ok ? r : qt * 16;                     // padding rows load a real row's Q; nothing of theirs is stored
+    const int j = rc / a_group;
+    const int tok = tok0 + j, head = kvh * a_group + (rc - j * a_group);
+    const int qlim = row_ok ? pos0 + j : -1;                 // last key this lane's row may see
+    const int n_kt = (pos0 + (min(qt * 16 + 15, R - 1)) / a_group) / 64 + 1;     // key tiles of the tile's last real row
+    char* vimg = smem + wave * TILE_BYTES;
+    const int vw = wave, nvw = NW;
+    bf16x8 qf[KS];
+    f32x4 o[DT];
+#pragma unroll
+    for (int d = 0; d < DT; d++) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    float m_run = -INFINITY, l_run = 0.f;     // exp2 domain
+    const float sl2 = p.scale * 1.4426950408889634f;
+    const int w_base[2] = {16 * kv_img_chunk<HD>(ksub, dch), 16 * kv_img_chunk<HD>(KPI + ksub, dch) - 16 * KPI * CPR};
+    int v_off[DT];
+#pragma unroll
+    for (int d = 0; d < DT; d++) v_off[d] = attn_v_off<HD>(fq, fg, d);
+
+    bf16x8 kf[NT2][4][KS];
+    bf16x8 vch[NT2][NVL];
+    auto issue_round_t = [&](int kt0, auto nt_tag) {
+        constexpr bool NT = decltype(nt_tag)::value;
+#pragma unroll
+        for (int h = 0; h < NT2; h++) {
+            const int kt = kt0 + h * nvw;
+            if (kt >= n_kt) continue;
+            const int bi = kv_block_index(p, kt * 64), krow0 = kt * 64 - bi * p.Tmax;     // the KV block holding this tile
+            const int blk = tbl[min(bi, a_tbl_stride - 1)];
+            const int64_t blk_off = (int64_t)blk * p.slot_stride + ((int64_t)kvh * p.Tmax + krow0) * HD;
+            const bf16_t* kbase = (const bf16_t*)p.kcache + blk_off;
+            const bf16_t* vbase = (const bf16_t*)p.vcache + blk_off;
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+#pragma unroll
+                for (int ks = 0; ks < KS; ks++) {
+                    const bf16x8* src = (const bf16x8*)(kbase + (int64_t)(t * 16 + fq) * HD + ks * 32 + fg * 8);
+                    if constexpr (NT) kf[h][t][ks] = __builtin_nontemporal_load(src); else kf[h][t][ks] = *src;
+                }
+#pragma unroll
+            for (int i = 0; i < NVL; i++) {                                                                 // 1 KiB, contiguous
+                const bf16x8* src = (const bf16x8*)(vbase + (int64_t)lane * 8 + i * 512);
+                if constexpr (NT) vch[h][i] = __builtin_nontemporal_load(src); else vch[h][i] = *src;
+            }
+        }
+    };
+    auto issue_round = [&](int kt0) {
+        if (p.kv_nt) issue_round_t(kt0, std::true_type{}); else issue_round_t(kt0, std::false_type{});
+    };
+    {
+        const bf16_t* qp = (const bf16_t*)p.q + (int64_t)tok * p.q_stride + head * HD;
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) qf[ks] = *(const bf16x8*)(qp + ks * 32 + fg * 8);
+    }
+    if (vw < n_kt) issue_round(vw);
+    auto do_round = [&](int kt0) __attribute__((always_inline)) {
+        f32x4 s[NT2][4];
+        float tmax = -INFINITY;
+#pragma unroll
+        for (int h = 0; h < NT2; h++) {
+            const int kt = kt0 + h * nvw;
+            if (kt >= n_kt) {
+#pragma unroll
+                for (int t = 0; t < 4; t++) s[h][t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                continue;
+            }
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int ks = 0; ks < KS; ks++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[h][t][ks], qf[ks], acc, 0, 0, 0);
+                const int lim = qlim - kt * 64 - fg * 4;      // this row's last visible key, relative to the lane's first
+#pragma unroll
+                for (int r4 = 0; r4 < 4; r4++) {
+                    float v = acc[r4] * sl2;
+                    v = (t * 16 + r4 <= lim) ? v : -INFINITY;
+                    acc[r4] = v;
+                    tmax = fmaxf(tmax, v);
+                }
+                s[h][t] = acc;
+            }
+        }
+        attn_decode_softmax<HD, NT2, true>(s, tmax, m_run, l_run, o);
+#pragma unroll
+        for (int h = 0; h < NT2; h++) {
+            if (kt0 + h * nvw >= n_kt) continue;
+#pragma unroll
+            for (int i = 0; i < NVL; i++) *(bf16x8*)(vimg + w_base[i & 1] + i * (16 * KPI * CPR)) = vch[h][i];
+            attn_pv_tile<HD, 1, false>(vimg, v_off, &s[h], &o, nullptr);
+        }
+    };
+    if (vw < n_kt) do_round(vw);
+    for (int kt0 = vw + NT2 * nvw; kt0 < n_kt; kt0 += NT2 * nvw) {
+        issue_round(kt0);
+        do_round(kt0);
+    }
+    // the one-position kernel's combine: tok / head are per lane there too (every real row saw key 0, so its maximum
+    // over the waves is finite; a wave that saw none of a row's keys enters with weight exp2(-inf) = 0)
     attn_decode_finish<HD, NW>(p, smem, vimg, red_m, red_l, o, m_run, l_run, seq, tok, head, row_ok, wave, lane, fq, fg, 1.0f, stamps);
 }
 

@@ -200,6 +200,7 @@ struct nvl_model {
     std::vector<hipGraphExec_t> graphs_retired;       // evicted execs, destroyed after the next stream sync (reap_graphs)
     bool graphs_ok = true;
     int32_t* am_host = nullptr;                       // pinned: argmax ids of a replayed decode pass
+    int32_t* verify_dev = nullptr; int32_t* verify_host = nullptr;    // a verify pass's accept counts + ids (device, pinned)
     // debug
     // nvl_set_debug mode 4: in-kernel time stamps of the decode kernels (common.h nvl_stamp), one record per launch
     bool stamping = false; unsigned long long* stamp_buf = nullptr; int stamp_launches = 0;

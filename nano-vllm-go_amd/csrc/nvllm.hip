@@ -388,6 +388,8 @@ extern "C" void nvl_destroy(nvl_model* m) {
     dfree(m->moe_gate); dfree(m->moe_hall); dfree(m->moe_part);
     clear_graphs(m);
     if (m->am_host) (void)hipHostFree(m->am_host);
+    if (m->verify_host) (void)hipHostFree(m->verify_host);
+    dfree(m->verify_dev);
     dfree(m->ring_pos0);
     dfree(m->conv_tail); dfree(m->stamp_buf); dfree(m->ssd_z); dfree(m->ssd_decay);
     dfree(m->ssm_state); dfree(m->mproj); dfree(m->mxbc); dfree(m->mdelta); dfree(m->my); dfree(m->myn);
@@ -1246,6 +1248,8 @@ extern "C" int nvl_finalize(nvl_model* m) {
     NVL_HIP(hipHostMalloc((void**)&m->meta_host, (size_t)m->meta_ints * 4, hipHostMallocDefault));
     m->meta_dev = dmalloc<int32_t>(m->meta_ints);
     NVL_HIP(hipHostMalloc((void**)&m->am_host, (size_t)std::max<int64_t>(S, Mmax) * 4, hipHostMallocDefault));
+    NVL_HIP(hipHostMalloc((void**)&m->verify_host, (size_t)(S + Mmax) * 4, hipHostMallocDefault));    // a verify pass: [accepted S | ids Mmax]
+    m->verify_dev = dmalloc<int32_t>(S + Mmax);
     m->ring_pos0 = dmalloc<int32_t>(S);
     NVL_HIP(hipStreamSynchronize(m->stream));   // every memset/copy above ran on the model's own (non-blocking) stream
     m->finalized = true;
@@ -1497,6 +1501,7 @@ static int g_attn_nw = 0;      // nvl_set_tuning key 15: waves per decode-attent
 static int g_attn_tq2 = 1;     // nvl_set_tuning key 10: unused since round 2 (the prefill kernel always keeps two sub-tiles per wave)
 static int g_attn_kv_nt = 1;   // nvl_set_tuning key 35: non-temporal K/V loads in the decode attention (0 never, 1 automatic, 2 always)
 static int g_attn_split = 1;   // nvl_set_tuning key 25: split a decode attention's keys over up to 8 workgroups per (sequence, kv head) (0 = never)
+static int g_verify_mq = 1;    // nvl_set_tuning key 38: verify passes (nvl_verify_greedy*) run the multi-position decode attention (0 = rope_kv + the prefill kernel)
 // Launch shape of the decode attention for the batch being enqueued (also part of a captured graph's key): waves per
 // workgroup | workgroups per (sequence, kv head) << 8.
 // Split: a workgroup pulls all K/V of its (sequence, kv head) through ONE CU; with a few sequences and a long context
@@ -1506,11 +1511,12 @@ static int g_attn_split = 1;   // nvl_set_tuning key 25: split a decode attentio
 // Llama-3.2-1B, 2048 / 1024 keys): B=1 0.891 -> 0.811 / 0.808 -> 0.780, B=2 0.893 -> 0.834 / 0.869 -> 0.792, B=4 (4
 // workgroups per pair) 0.924 -> 0.883 / 0.812 -> 0.817 (hence from 2048 keys on above 16 pairs); B=8 loses either way
 // (2 workgroups per pair 0.96 -> 0.99, 8 per pair -> 1.13).
-int decode_attn_cfg(const nvl_model* m, int n_seqs) {
+// mq_S > 0: the multi-position kernel with mq_S positions per sequence — its grid, and never a key split.
+int decode_attn_cfg(const nvl_model* m, int n_seqs, int mq_S = 0) {
     const int n_kt = m->ctx_hint > 0 ? (m->ctx_hint - 1) / 64 + 1 : 1 << 20;
     const int per_wave = m->hd == 64 ? 2 : 1;
-    const int wgs = m->nKV * cdiv(m->group, 16) * n_seqs;
-    if (g_attn_split && !g_attn_nw && m->attn_part && m->ctx_hint > 0 && wgs <= ATTN_SPLIT_MAX_PAIRS && n_kt >= 16) {
+    const int wgs = m->nKV * cdiv(m->group * std::max(mq_S, 1), 16) * n_seqs;
+    if (!mq_S && g_attn_split && !g_attn_nw && m->attn_part && m->ctx_hint > 0 && wgs <= ATTN_SPLIT_MAX_PAIRS && n_kt >= 16) {
         const int want = cdiv(n_kt, 2 * per_wave);                       // workgroups of 2 waves that get a full round each
         const int ns = (wgs > 16 && n_kt < 32) ? 1 : std::min(std::min(want, ATTN_SPLIT_MAX), 128 / wgs);
         if (ns >= 2) return 2 | (ns << 8);
@@ -1537,8 +1543,10 @@ static void launch_decode_attn(nvl_model* m, dim3 grid, int nw, int tile_bytes, 
 // are then the layer's code slabs (same element layout, one byte per element; kv8.h) — else NULL.  The 8-bit kernels have
 // no fused (RoPE + append) and no stamped form, and their prefill kernel reads the block table from global memory (no
 // 128-block limit); grids, wave choices and the K/V load policy are the same.
+// mq: the caller is a verify pass (or nvl_op_attention_mq): 2..8 positions per sequence on attn_decode_mq_bf16_kernel.
+static bool attention_mq_ok(const nvl_model* m, int max_len) { return !m->f32 && !m->kv8 && max_len >= 2 && max_len <= 8; }
 static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_len, const void* kc, const void* vc,
-                             double flops, double abytes, bool fused_qkv, const float* kv8) {
+                             double flops, double abytes, bool fused_qkv, const float* kv8, bool mq = false) {
     AttnArgs a{};
     a.q = m->q; a.q_stride = m->nH * m->hd;
     a.out = m->attn_out; a.out_stride = m->nH * m->hd;
@@ -1551,6 +1559,15 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
     if (m->f32) {
         const size_t lds = (size_t)m->Tmax * 4;
         hipLaunchKernelGGL(attn_f32_kernel, dim3(max_len, m->nH, n_seqs), dim3(256), lds, m->stream, a, m->hd);
+    } else if (mq && !kv8 && attention_mq_ok(m, max_len)) {
+        const int nw = decode_attn_cfg(m, n_seqs, max_len) & 255;
+        dim3 grid(m->nKV * cdiv(m->group * max_len, 16), n_seqs, 1);     // (kv head x 16-row query tile, sequence); no key split
+        // K/V read once per step by its only workgroup: the one-position launch's policy, with this grid
+        a.kv_nt = g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && cdiv(m->group * max_len, 16) == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
+#define NVL_DEC_MQ(HDv, NWv) attn_decode_mq_bf16_kernel<HDv, NWv>
+        if (m->hd == 64) launch_decode_attn<NVL_DEC_MQ(64, 2), NVL_DEC_MQ(64, 4), NVL_DEC_MQ(64, 8)>(m, grid, nw, 64 * 64 * 2, a, max_len);
+        else launch_decode_attn<NVL_DEC_MQ(128, 2), NVL_DEC_MQ(128, 4), NVL_DEC_MQ(128, 8)>(m, grid, nw, 64 * 128 * 2, a, max_len);
+#undef NVL_DEC_MQ
     } else if (max_len == 1) {
         const int cfg = decode_attn_cfg(m, n_seqs), nsplit = cfg >> 8;
         dim3 grid(m->nKV * cdiv(m->group, 16), n_seqs, nsplit);      // (kv head x 16-head query tile, sequence, key split)
@@ -1606,9 +1623,9 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
     NVL_HIP(hipGetLastError());
 }
 // algorithmic bytes: every cached key/value of the batch once + Q in + O out (+ the fp32 QKV row of a fused decode step)
-void attention(nvl_model* m, int li, const Meta& md, int n_seqs, int max_len, double flops, bool fused_qkv = false) {
+void attention(nvl_model* m, int li, const Meta& md, int n_seqs, int max_len, double flops, bool fused_qkv = false, bool mq = false) {
     attention_launch(m, md, n_seqs, max_len, (char*)m->kcache + (size_t)li * m->layer_stride * m->wsize,
-                     (char*)m->vcache + (size_t)li * m->layer_stride * m->wsize, flops, m->kv_tok * 2.0 * m->nKV * m->hd * (double)m->wsize, fused_qkv, nullptr);
+                     (char*)m->vcache + (size_t)li * m->layer_stride * m->wsize, flops, m->kv_tok * 2.0 * m->nKV * m->hd * (double)m->wsize, fused_qkv, nullptr, mq);
 }
 // attention over an 8-bit cache: kc / vc the layer's code slabs, k_scale / v_scale the layer's scales.  bf16 only.
 void attention_kv8(nvl_model* m, const Meta& md, int n_seqs, int max_len, const void* kc, const void* vc, float ksc, float vsc) {
@@ -2071,7 +2088,8 @@ void tap_layer(nvl_model* m, int li, int M) {
 // metadata `md` — no host synchronisation.  Returns the number of logits rows produced.
 // seam: 0 = whole pass; bit 0 = x and layer 0's normed operand are already in place (skip embed + first norm);
 // bit 1 = stop after the argmax partials (the caller's decode_seam_kernel finishes the step); bit 2 = no argmax at
-// all (the caller samples from the logits)
+// all (the caller samples from the logits); bit 3 = a verify pass (nvl_verify_greedy*): its 2..8 positions per sequence
+// take the multi-position decode attention instead of the prefill kernel (attention_mq_ok)
 // Either tail leaves LogitsScaling APPLIED IN PLACE in m->logits (argmax_partial_kernel writes the divided value back,
 // scale_rows_kernel is the division itself): nvl_sample and nvl_logprobs read final logits and never divide again.
 // `sc` != NULL (nvl_score; flags carry NVL_FWD_ALL_LOGITS): the tail is final norm over every row, then LM head +
@@ -2259,7 +2277,7 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
             attention_kv8(m, md, n_seqs, max_len, (char*)m->kcache + (size_t)li * m->layer_stride,
                           (char*)m->vcache + (size_t)li * m->layer_stride, m->k_scale[li], m->v_scale[li]);
         else
-            attention(m, li, md, n_seqs, max_len, attn_flops, fused_dec);
+            attention(m, li, md, n_seqs, max_len, attn_flops, fused_dec, (seam & 8) != 0);
         const float* bo = (const float*)l.t[NVL_T_BO].p;
         if (parallel) {
             // generic_model.go:395-418: r + [am*]attn + [rm*]ffn, both branches read the same normed x
@@ -2858,6 +2876,256 @@ extern "C" int nvl_decode_greedy_paged(nvl_model* m, int n_seqs, const int32_t* 
         hm.tokens[i] = first_tokens[i]; hm.tok_pos[i] = pos; hm.tok_tbl[i] = tb;
     }
     decode_loop(m, hm, n_seqs, n_steps, out_tokens);
+    return NVL_OK;
+    NVL_CATCH(m)
+}
+
+// =================================================================================================
+// greedy speculative decoding: verify 1 + k rows per sequence in one pass, accept on the device, roll the cache back
+// =================================================================================================
+namespace {
+// per sequence i: g = the pass's greedy ids of its 1 + k rows, t = its input rows (t[0] the next input token, t[1..k] the
+// draft).  a = the longest prefix with t[j+1] == g[j]; res = [a: n | out_tokens: n x (1+k)], out_tokens[i][0..a] = g, the rest -1.
+__global__ void verify_accept_kernel(const int32_t* __restrict__ argmax, const int32_t* __restrict__ tokens, int k, int n,
+                                     int32_t* __restrict__ res) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int S = 1 + k;
+    const int32_t* g = argmax + (int64_t)i * S;
+    const int32_t* t = tokens + (int64_t)i * S;
+    int a = 0;
+    while (a < k && t[a + 1] == g[a]) a++;
+    res[i] = a;
+    int32_t* o = res + n + (int64_t)i * S;
+    for (int j = 0; j < S; j++) o[j] = j <= a ? g[j] : -1;
+}
+
+// The pass itself, metadata already in meta_host (n_seqs sequences of 1 + k rows each, positions h_pos[i] ..): upload,
+// launches, accept kernel and result download — captured and replayed like a decode pass when every projection is in
+// decode form (<= 64 rows) — then the host copies.  Leaves the n_seqs x (1+k) logits rows as the last forward group.
+void verify_pass(nvl_model* m, int n_seqs, int k, const int32_t* h_pos, int32_t* n_acc_out, int32_t* out_tokens) {
+    const int S = 1 + k, M = n_seqs * S;
+    const Meta md = bind_meta(m, m->meta_dev, M);
+    NVL_HIP(hipEventRecord(m->ev0, m->stream));
+    double attn_flops = 0, kv_tok = 0;
+    for (int i = 0; i < n_seqs; i++) {
+        const double s = S, p0 = h_pos[i];
+        attn_flops += 4.0 * m->hd * m->nH * (s * p0 + s * (s + 1) / 2);
+        m->ctx_hint = std::max(m->ctx_hint, h_pos[i] + S);
+        kv_tok += p0 + s;
+    }
+    m->kv_tok = kv_tok;
+    const bool mq = g_verify_mq && attention_mq_ok(m, S);
+    const int nres = n_seqs * (1 + S);
+    auto pass = [&] {
+        NVL_HIP(hipMemcpyAsync(m->meta_dev, m->meta_host, meta_bytes(m, M), hipMemcpyHostToDevice, m->stream));
+        enqueue_forward(m, md, n_seqs, M, S, attn_flops, NVL_FWD_ALL_LOGITS, mq ? 8 : 0);
+        hipLaunchKernelGGL(verify_accept_kernel, dim3(cdiv(n_seqs, 64)), dim3(64), 0, m->stream, m->argmax_dev, md.tokens, k, n_seqs, m->verify_dev);
+        NVL_HIP(hipGetLastError());
+        NVL_HIP(hipMemcpyAsync(m->verify_host, m->verify_dev, (size_t)nres * 4, hipMemcpyDeviceToHost, m->stream));
+    };
+    bool replayed = false;
+    if (M <= 64 && M <= m->logit_rows) {
+        const int acfg = mq ? decode_attn_cfg(m, n_seqs, S) : (S == 1 ? decode_attn_waves(m, n_seqs) : 0);
+        const std::array<int, 5> key{3, n_seqs, acfg, k | (mq ? 256 : 0), g_tune_epoch};
+        replayed = replay_or_capture(m, key, pass);
+    }
+    if (!replayed) pass();
+    m->ctx_hint = 0;
+    NVL_HIP(hipEventRecord(m->ev1, m->stream));
+    NVL_HIP(hipStreamSynchronize(m->stream));
+    reap_graphs(m);
+    m->last_rows = M;
+    if (n_acc_out) memcpy(n_acc_out, m->verify_host, (size_t)n_seqs * 4);
+    if (out_tokens) memcpy(out_tokens, m->verify_host + n_seqs, (size_t)M * 4);
+    float ms = 0.f;
+    (void)hipEventElapsedTime(&ms, m->ev0, m->ev1);
+    m->stats.forward_calls++;
+    m->stats.decode_tokens += (uint64_t)M; m->stats.decode_ms += ms;
+    if (m->profile) drain_profile(m);
+}
+
+int verify_refusals(nvl_model* m, const char* who, int n_seqs, int k, int k_min) {
+    if (!m->finalized) return fail(m, NVL_ERR_STATE, std::string(who) + ": model not finalized");
+    if (k < k_min || k > 7) return fail(m, NVL_ERR_INVALID, std::string(who) + ": k outside 1..7");
+    if (n_seqs <= 0 || n_seqs > m->opts.max_seqs) return fail(m, NVL_ERR_INVALID, std::string(who) + ": n_seqs outside 1..max_seqs");
+    if ((int64_t)n_seqs * (1 + k) > m->opts.max_batch_tokens) return fail(m, NVL_ERR_INVALID, std::string(who) + ": n_seqs x (1 + k) exceeds max_batch_tokens");
+    if (m->n_mamba) return fail(m, NVL_ERR_STATE, std::string(who) + ": a Mamba2 state cannot be rolled back");
+    if (m->tp > 1 || m->tp_force) return fail(m, NVL_ERR_STATE, std::string(who) + ": tensor-parallel models are not supported");
+    return NVL_OK;
+}
+
+// nvl_verify_greedy (k_min = 1) and the passes of nvl_decode_greedy_lookup (k_min = 0: a last pass of one row per sequence).
+// keep[i] (or NULL): at most that many of sequence i's accepted tokens stay in the cache.
+int verify_slab(nvl_model* m, const char* who, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, int k, int k_min,
+                int32_t* n_acc_out, int32_t* out_tokens, const int* keep) {
+    const int rc = verify_refusals(m, who, n_seqs, k, k_min);
+    if (rc) return rc;
+    if (m->paged) return fail(m, NVL_ERR_STATE, std::string(who) + ": the model is in paged-KV mode (use nvl_verify_greedy_paged)");
+    const int S = 1 + k, M = n_seqs * S;
+    const Meta hm = bind_meta(m, m->meta_host, M);
+    std::vector<int> h_slot((size_t)n_seqs);
+    for (int i = 0; i < n_seqs; i++) {
+        auto it = m->seq_slot.find(seq_ids[i]);
+        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, std::string(who) + ": sequence has no KV slot (nvl_seq_open first)");
+        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, std::string(who) + ": duplicate sequence in batch");
+        const int slot = it->second, pos = m->slot_len[(size_t)slot];
+        if (pos > m->cfg.max_seq_len - S) return fail(m, NVL_ERR_POSITION, std::string(who) + ": position exceeds max_seq_len");
+        hm.seq_tok_start[i] = i * S; hm.seq_len[i] = S; hm.seq_pos[i] = pos; h_slot[(size_t)i] = slot; hm.seq_tbl[i] = i; hm.blk_table[i] = slot;
+        for (int j = 0; j < S; j++) {
+            const int tok = tokens[i * S + j];
+            if (tok < 0 || tok >= m->V) return fail(m, NVL_ERR_INVALID, std::string(who) + ": token id out of range");
+            hm.tokens[i * S + j] = tok; hm.tok_pos[i * S + j] = pos + j; hm.tok_tbl[i * S + j] = i;
+        }
+        hm.last_rows[i] = i * S + S - 1;
+    }
+    verify_pass(m, n_seqs, k, hm.seq_pos, n_acc_out, out_tokens);
+    // rollback: the accepted prefix and the row that produced the first unaccepted id stay; the rows behind are dead
+    for (int i = 0; i < n_seqs; i++) {
+        int adv = m->verify_host[i] + 1;
+        if (keep) adv = std::min(adv, keep[i]);
+        m->slot_len[(size_t)h_slot[(size_t)i]] += adv; m->slot_tick[(size_t)h_slot[(size_t)i]] = ++m->tick;
+    }
+    return NVL_OK;
+}
+}  // namespace
+
+extern "C" int nvl_verify_greedy(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, int k,
+                                 int32_t* n_accepted_out, int32_t* out_tokens) {
+    if (!m) return NVL_ERR_INVALID;
+    if (!seq_ids || !tokens || !n_accepted_out || !out_tokens) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy: null arguments");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    return verify_slab(m, "nvl_verify_greedy", n_seqs, seq_ids, tokens, k, 1, n_accepted_out, out_tokens, nullptr);
+    NVL_CATCH(m)
+}
+
+extern "C" int nvl_verify_greedy_paged(nvl_model* m, int n_seqs, const int32_t* tokens, int k, const int32_t* pos_offsets,
+                                       const int32_t* block_tables, const int32_t* table_offsets, int32_t* n_accepted_out,
+                                       int32_t* out_tokens) {
+    if (!m) return NVL_ERR_INVALID;
+    if (!tokens || !pos_offsets || !block_tables || !table_offsets || !n_accepted_out || !out_tokens)
+        return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: null arguments");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    const int rc = verify_refusals(m, "nvl_verify_greedy_paged", n_seqs, k, 1);
+    if (rc) return rc;
+    if (!m->paged) return fail(m, NVL_ERR_STATE, "nvl_verify_greedy_paged: the model was created without kv_num_blocks");
+    const int S = 1 + k, M = n_seqs * S, BS = m->Tmax;
+    const Meta hm = bind_meta(m, m->meta_host, M);
+    if (table_offsets[0] < 0) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: negative table offset");
+    for (int i = 0; i < n_seqs; i++) {
+        const int pos = pos_offsets[i];
+        if (pos < 0) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: negative pos_offset");
+        if (pos > m->cfg.max_seq_len - S) return fail(m, NVL_ERR_POSITION, "nvl_verify_greedy_paged: position exceeds max_seq_len");
+        if (table_offsets[i + 1] < table_offsets[i]) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: table_offsets must be non-decreasing");
+        const int nb = table_offsets[i + 1] - table_offsets[i];
+        if (nb < cdiv(pos + S, BS)) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: block table shorter than the sequence");
+        if (nb > m->blocks_per_seq) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: block table too long");
+        const int tb = i * m->blocks_per_seq;
+        for (int j = 0; j < nb; j++) {
+            const int b = block_tables[table_offsets[i] + j];
+            if (b < 0 || b >= m->num_blocks) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: block id out of range");
+            hm.blk_table[tb + j] = b;
+        }
+        hm.seq_tok_start[i] = i * S; hm.seq_len[i] = S; hm.seq_pos[i] = pos; hm.seq_tbl[i] = tb;
+        for (int j = 0; j < S; j++) {
+            const int tok = tokens[i * S + j];
+            if (tok < 0 || tok >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: token id out of range");
+            hm.tokens[i * S + j] = tok; hm.tok_pos[i * S + j] = pos + j; hm.tok_tbl[i * S + j] = tb;
+        }
+        hm.last_rows[i] = i * S + S - 1;
+    }
+    verify_pass(m, n_seqs, k, hm.seq_pos, n_accepted_out, out_tokens);
+    return NVL_OK;
+    NVL_CATCH(m)
+}
+
+extern "C" int nvl_seq_truncate(nvl_model* m, int64_t seq_id, int new_len) {
+    if (!m) return NVL_ERR_INVALID;
+    if (!m->finalized) return fail(m, NVL_ERR_STATE, "nvl_seq_truncate: model not finalized");
+    if (m->n_mamba) return fail(m, NVL_ERR_STATE, "nvl_seq_truncate: a Mamba2 state cannot be rolled back");
+    if (m->paged) return fail(m, NVL_ERR_STATE, "nvl_seq_truncate: paged-KV mode keeps no lengths (the caller owns them)");
+    auto it = m->seq_slot.find(seq_id);
+    if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_seq_truncate: sequence has no KV slot");
+    if (new_len < 0 || new_len > m->slot_len[(size_t)it->second]) return fail(m, NVL_ERR_INVALID, "nvl_seq_truncate: new_len outside [0, cached length]");
+    m->slot_len[(size_t)it->second] = new_len;
+    return NVL_OK;
+}
+
+// prompt-lookup drafting: pure host code, no device
+extern "C" int nvl_lookup_draft(const int32_t* history, int n, int k, int ngram, int32_t* draft_out) {
+    if (!history || !draft_out || n < 1 || k < 1) return NVL_ERR_INVALID;
+    for (int g = std::min(ngram, n - 1); g >= 1; g--)
+        for (int s = n - g - 1; s >= 0; s--) {
+            if (memcmp(history + s, history + n - g, (size_t)g * 4) != 0) continue;
+            const int take = std::min(k, n - (s + g));       // (s < n - g: at least one token follows the match)
+            for (int j = 0; j < k; j++) draft_out[j] = history[s + g + std::min(j, take - 1)];
+            return take;
+        }
+    for (int j = 0; j < k; j++) draft_out[j] = history[n - 1];
+    return 0;
+}
+
+extern "C" int nvl_decode_greedy_lookup(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
+                                        int k, int ngram, const int32_t* const* history_ptrs, const int32_t* history_lens,
+                                        int32_t* out_tokens, int32_t* passes_out) {
+    if (!m) return NVL_ERR_INVALID;
+    if (!seq_ids || !first_tokens || !out_tokens || n_steps <= 0 || ngram < 1 || (history_ptrs && !history_lens))
+        return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_lookup: null/empty arguments");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    int rc = verify_refusals(m, "nvl_decode_greedy_lookup", n_seqs, k, 1);
+    if (rc) return rc;
+    if (m->paged) return fail(m, NVL_ERR_STATE, "nvl_decode_greedy_lookup: not available in paged-KV mode");
+    std::vector<std::vector<int32_t>> hist((size_t)n_seqs);
+    std::vector<int> done((size_t)n_seqs, 0);
+    for (int i = 0; i < n_seqs; i++) {
+        auto it = m->seq_slot.find(seq_ids[i]);
+        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_decode_greedy_lookup: sequence has no KV slot");
+        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_lookup: duplicate sequence");
+        if (m->slot_len[(size_t)it->second] + n_steps > m->cfg.max_seq_len) return fail(m, NVL_ERR_POSITION, "nvl_decode_greedy_lookup: position exceeds max_seq_len");
+        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_lookup: token id out of range");
+        if (history_ptrs && history_ptrs[i] && history_lens[i] > 0) {
+            hist[(size_t)i].assign(history_ptrs[i], history_ptrs[i] + history_lens[i]);
+            if (hist[(size_t)i].back() != first_tokens[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_lookup: a history must end with its first token");
+        } else
+            hist[(size_t)i].push_back(first_tokens[i]);
+    }
+    int passes = 0;
+    std::vector<int64_t> ids; std::vector<int> who, keep; std::vector<int32_t> toks, acc, got;
+    for (;;) {
+        who.clear(); ids.clear(); keep.clear();
+        int k_pass = 0, room = k;
+        for (int i = 0; i < n_seqs; i++) {
+            if (done[(size_t)i] >= n_steps) continue;
+            who.push_back(i); ids.push_back(seq_ids[i]); keep.push_back(n_steps - done[(size_t)i]);
+            k_pass = std::max(k_pass, n_steps - done[(size_t)i] - 1);
+            room = std::min(room, m->cfg.max_seq_len - m->slot_len[(size_t)m->seq_slot[seq_ids[i]]] - 1);
+        }
+        if (who.empty()) break;
+        k_pass = std::min(k_pass, room);
+        const int na = (int)who.size(), S = 1 + k_pass;
+        toks.assign((size_t)na * S, 0); acc.assign((size_t)na, 0); got.assign((size_t)na * S, -1);
+        for (int a = 0; a < na; a++) {
+            const std::vector<int32_t>& h = hist[(size_t)who[(size_t)a]];
+            toks[(size_t)a * S] = h.back();
+            if (k_pass > 0) (void)nvl_lookup_draft(h.data(), (int)h.size(), k_pass, ngram, &toks[(size_t)a * S + 1]);
+        }
+        rc = verify_slab(m, "nvl_decode_greedy_lookup", na, ids.data(), toks.data(), k_pass, 0, acc.data(), got.data(), keep.data());
+        if (rc) return rc;
+        passes++;
+        for (int a = 0; a < na; a++) {
+            const int i = who[(size_t)a], take = std::min(acc[(size_t)a] + 1, keep[(size_t)a]);
+            for (int j = 0; j < take; j++) {
+                const int32_t t = got[(size_t)a * S + j];
+                out_tokens[(size_t)(done[(size_t)i] + j) * n_seqs + i] = t;
+                hist[(size_t)i].push_back(t);
+            }
+            done[(size_t)i] += take;
+        }
+    }
+    if (passes_out) *passes_out = passes;
     return NVL_OK;
     NVL_CATCH(m)
 }

@@ -224,6 +224,57 @@ extern "C" int nvl_op_attention(int device, int precision, const float* q, const
     OP_CATCH
 }
 
+// attn_decode_mq_bf16_kernel alone (whatever nvl_set_tuning key 38 says): nvl_op_attention's conventions, S = 2..8 new positions
+extern "C" int nvl_op_attention_mq(int device, const float* q, const float* k, const float* v, int nH, int nKV, int S, int T,
+                                   int hd, float scale, float* out) {
+    if (!q || !k || !v || !out || nH <= 0 || nKV <= 0 || nH % nKV || S < 2 || S > 8 || T < S || (hd != 64 && hd != 128))
+        return op_fail("nvl_op_attention_mq: bad arguments");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_BF16);
+    nvl_model& m = cx.m;
+    const int Tmax = (int)round_up(T, 64);
+    std::vector<float> qt((size_t)S * nH * hd), kc((size_t)nKV * Tmax * hd, 0.f), vc((size_t)nKV * Tmax * hd, 0.f);
+    for (int h = 0; h < nH; h++)
+        for (int s = 0; s < S; s++)
+            memcpy(&qt[((size_t)s * nH + h) * hd], q + ((size_t)h * S + s) * hd, (size_t)hd * 4);
+    for (int h = 0; h < nKV; h++)
+        for (int t = 0; t < T; t++) {
+            memcpy(&kc[((size_t)h * Tmax + t) * hd], k + ((size_t)h * T + t) * hd, (size_t)hd * 4);
+            memcpy(&vc[((size_t)h * Tmax + t) * hd], v + ((size_t)h * T + t) * hd, (size_t)hd * 4);
+        }
+    m.q = cx.up_mat(qt.data(), S, (int64_t)nH * hd, false, 1, true);
+    m.kcache = cx.up_mat(kc.data(), 1, (int64_t)kc.size(), false, 1, true);
+    m.vcache = cx.up_mat(vc.data(), 1, (int64_t)vc.size(), false, 1, true);
+    m.attn_out = cx.alloc(round_up(S, 64) * nH * hd * 2);
+    m.nH = nH; m.nKV = nKV; m.group = nH / nKV; m.hd = hd; m.Tmax = Tmax; m.L = 1;
+    m.layer_stride = (int64_t)nKV * Tmax * hd; m.slot_stride = m.layer_stride;
+    m.attn_scale = scale != 0.f ? scale : 1.0f / std::sqrt((float)hd);
+    m.ctx_hint = T;                                   // (the wave ladder follows the context, as in the model path)
+    const int32_t meta[5] = {0, S, T - S, 0, 0};      // one sequence whose block table is the single block 0
+    int32_t* dmeta = (int32_t*)cx.alloc(20);
+    NVL_HIP(hipMemcpyAsync(dmeta, meta, 20, hipMemcpyHostToDevice, m.stream));
+    Meta md{};
+    md.seq_tok_start = dmeta; md.seq_len = dmeta + 1; md.seq_pos = dmeta + 2; md.seq_tbl = dmeta + 3; md.blk_table = dmeta + 4;
+    m.blocks_per_seq = 1;
+    attention(&m, 0, md, 1, S, 0.0, false, true);
+    std::vector<float> ot((size_t)S * nH * hd);
+    std::vector<uint16_t> ob((size_t)(round_up(S, 64) * nH * hd));
+    NVL_HIP(hipMemcpyAsync(ob.data(), m.attn_out, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
+    NVL_HIP(hipStreamSynchronize(m.stream));
+    const int64_t W = (int64_t)nH * hd;     // the kernel wrote the next GEMM's fragment-major operand
+    for (int64_t r = 0; r < S; r++)
+        for (int64_t c = 0; c < W; c++) {
+            uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, W)]) << 16;
+            memcpy(&ot[(size_t)(r * W + c)], &u, 4);
+        }
+    for (int h = 0; h < nH; h++)
+        for (int s = 0; s < S; s++)
+            memcpy(out + ((size_t)h * S + s) * hd, &ot[((size_t)s * nH + h) * hd], (size_t)hd * 4);
+    m.q = m.kcache = m.vcache = m.attn_out = nullptr;   // owned by cx.bufs
+    return NVL_OK;
+    OP_CATCH
+}
+
 // The one-weight model of the quantized matmul ops: W [K][N] ([in, out], as nvl_op_matmul) quantized by the upload quantizer
 // of format wf into t and registered for gemm(), a tile-path scratch of at most scratch_rows weight rows, then
 // C = bf16(A) · W~^T through the model's dispatch into c [M][N].
@@ -647,6 +698,7 @@ extern "C" int nvl_set_tuning(int key, int value) {
     if (key == 33) { const int old = g_moe_defer_down; g_moe_defer_down = value; return old; }
     if (key == 35) { const int old = g_attn_kv_nt; g_attn_kv_nt = value; return old; }
     if (key == 36) { const int old = g_wide_ntb; g_wide_ntb = value; return old; }
+    if (key == 38) { const int old = g_verify_mq; g_verify_mq = value; return old; }
     if (key == 37) { const int old = g_score_rows; g_score_rows = value < 16 ? 16 : (value + 15) / 16 * 16; return old; }
     return -1;
 }

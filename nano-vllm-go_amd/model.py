@@ -327,6 +327,51 @@ class HipTransformerModel:
         L.check(self.lib.nvl_decode_greedy(self.h, n, _ptr(ids), _ptr(first), n_steps, _ptr(out)), self.h)
         return out
 
+    # -- greedy speculative decoding ----------------------------------------------------------------
+    def verify_greedy(self, seq_ids, token_rows, k: int):
+        """nvl_verify_greedy: token_rows [n_seqs, 1+k] (row i: the next input token, then k draft tokens) -> (n_accepted
+        [n_seqs], out_tokens [n_seqs, 1+k]: the greedy ids 0..a_i, the rest -1).  The cached length grows by a_i + 1; the
+        n_seqs x (1+k) logits rows stay for logprobs() / sample()."""
+        n = len(seq_ids)
+        ids = np.ascontiguousarray(seq_ids, dtype=np.int64)
+        toks = np.ascontiguousarray(token_rows, dtype=np.int32).reshape(n, 1 + k)
+        acc = np.empty(n, np.int32)
+        out = np.empty((n, 1 + k), np.int32)
+        L.check(self.lib.nvl_verify_greedy(self.h, n, _ptr(ids), _ptr(toks), int(k), _ptr(acc), _ptr(out)), self.h)
+        return acc, out
+
+    def verify_greedy_paged(self, token_rows, k: int, pos_offsets, block_tables):
+        """nvl_verify_greedy_paged: verify_greedy over the sequences' block tables; the caller advances by a_i + 1."""
+        n = len(pos_offsets)
+        toks = np.ascontiguousarray(token_rows, dtype=np.int32).reshape(n, 1 + k)
+        pos = np.ascontiguousarray(pos_offsets, dtype=np.int32)
+        tbl = np.concatenate([np.asarray(b, np.int32) for b in block_tables]).astype(np.int32)
+        off = np.concatenate([[0], np.cumsum([len(b) for b in block_tables])]).astype(np.int32)
+        acc = np.empty(n, np.int32)
+        out = np.empty((n, 1 + k), np.int32)
+        L.check(self.lib.nvl_verify_greedy_paged(self.h, n, _ptr(toks), int(k), _ptr(pos), _ptr(tbl), _ptr(off), _ptr(acc),
+                                                 _ptr(out)), self.h)
+        return acc, out
+
+    def seq_truncate(self, seq_id: int, new_len: int):
+        """nvl_seq_truncate: roll a slab sequence back to new_len <= its cached length."""
+        L.check(self.lib.nvl_seq_truncate(self.h, seq_id, int(new_len)), self.h)
+
+    def greedy_lookup(self, seq_ids, first_tokens, n_steps: int, k: int = 3, ngram: int = 3, histories=None):
+        """nvl_decode_greedy_lookup: decode_greedy's result [n_steps, n_seqs] from prompt-lookup drafts + verify passes.
+        histories[i] = the sequence's tokens so far, ending with first_tokens[i] (None: start at the first token).
+        -> (out_tokens, passes)."""
+        from .ops import _histories
+        n = len(seq_ids)
+        ids = np.ascontiguousarray(seq_ids, dtype=np.int64)
+        first = np.ascontiguousarray(first_tokens, dtype=np.int32)
+        ptrs, lens, keep = _histories(histories, n) if histories is not None else (None, None, None)
+        out = np.empty((n_steps, n), dtype=np.int32)
+        passes = np.zeros(1, np.int32)
+        L.check(self.lib.nvl_decode_greedy_lookup(self.h, n, _ptr(ids), _ptr(first), n_steps, int(k), int(ngram), ptrs,
+                                                  _ptr(lens), _ptr(out), _ptr(passes)), self.h)
+        return out, int(passes[0])
+
     def greedy_fused(self, prompt, max_tokens: int, seq_id: int = 0):
         """greedy() with the whole decode loop in one nvl_decode_greedy call."""
         self.seq_reset(seq_id)

@@ -73,6 +73,23 @@ def attention(q, k, v, scale=0.0, precision="bf16", device=0):  # attention.go:3
     return out
 
 
+def attention_mq(q, k, v, scale=0.0, device=0):   # the multi-position decode attention of a verify pass (bf16, S = 2..8)
+    q, k, v = _f(q), _f(k), _f(v)
+    nH, S, hd = q.shape
+    nKV, T, _ = k.shape
+    out = np.empty_like(q)
+    L.check(L.lib().nvl_op_attention_mq(device, _p(q), _p(k), _p(v), nH, nKV, S, T, hd, scale, _p(out)))
+    return out
+
+
+def lookup_draft(history, k, ngram=3):
+    """nvl_lookup_draft (host only): -> (draft [k], number of real draft tokens)."""
+    h = np.ascontiguousarray(history, dtype=np.int32)
+    draft = np.empty(k, np.int32)
+    n_real = L.check(L.lib().nvl_lookup_draft(_p(h), h.size, int(k), int(ngram), _p(draft)))
+    return draft, n_real
+
+
 def matmul_fp8w(a, w, device=0):                              # MatMul tensor.go:62 with 8-bit weights (w8.h)
     """a [M][K], w [K][N] ([in, out]) -> (c, codes, scales): w quantized by the model's upload quantizer (codes [N][K]
     uint8, scales [N]), c = bf16(a) @ W~ through the model's GEMM dispatch, W~ = bf16(scales[:, None] * e4m3(codes))."""

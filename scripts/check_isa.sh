@@ -49,6 +49,8 @@ def check(pattern, what, ok):
 # decode attention, hd 64 (fused and plain): two waves per SIMD (<= 256 unified registers), nothing spilled
 check(r"attn_decode_bf16_kernelILi64ELi[248]ELb[01]ELb0E", "decode attention hd 64, 2 waves/SIMD", lambda r: r["vgpr"] <= 256 and r["spill"] == 0)
 check(r"attn_decode_bf16_kernelILi128ELi8ELb[01]ELb0E", "decode attention hd 128, 8 waves", lambda r: r["vgpr"] <= 256 and r["spill"] <= 8)
+# the multi-position decode attention of a verify pass: the same budget at every wave count and both head sizes
+check(r"attn_decode_mq_bf16_kernelILi(64|128)ELi[248]E", "multi-position decode attention", lambda r: r["vgpr"] <= 256 and r["spill"] == 0)
 # decode projections: the 64-row-group instantiations (PASSES) and the wide form
 check(r"gemm_skinny_bf16_kernelILi4ELi[124]ELi2ELi[0-4]E\w+Lb1ELb0ELb0E", "narrow projection, 64-row groups", lambda r: r["spill"] <= 12)
 check(r"gemm_skinny_bf16_kernelILi[12]ELi[124]ELi4ELi[0-4]E\w+Lb0ELb0ELb[01]E", "narrow projection, <= 32 rows", lambda r: r["spill"] <= 12)

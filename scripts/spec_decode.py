@@ -1,0 +1,160 @@
+"""Greedy speculative decoding on Llama-3.2-1B shapes (random weights, bench.py's generator), context 512, B in {1, 8},
+k in {1, 3, 7}: milliseconds per verify pass of 1 + k rows per sequence for three routes, timed alternately in one process,
+next to milliseconds per plain step of nvl_decode_greedy:
+  (a) nvl_verify_greedy, nvl_set_tuning key 38 = 1 (the multi-position decode attention)
+  (b) nvl_verify_greedy, key 38 = 0 (rope_kv + the prefill attention kernel)
+  (c) nvl_forward with seq_lens = 1 + k and NVL_FWD_ALL_LOGITS, the accept rule on the host
+Every pass runs at the same context: the sequences are rolled back (nvl_seq_truncate) after each.
+Random weights have no real-text acceptance rate, so the generation rate is reported at its two bounds: drafts that are
+always right (the ids of a plain greedy run) and drafts that are always wrong.  Acceptance on real checkpoints: not measured.
+bench.py's seeded weights (gen_weights_on_device) are reused; bench.py itself is not changed or run.
+
+    python scripts/spec_decode.py [--batches 1,8] [--ks 1,3,7] [--ctx 512] [--gen 64] [--passes 32] [--reps 5]"""
+import argparse
+import importlib
+import importlib.util
+import statistics
+import sys
+import time
+from pathlib import Path
+
+import numpy as np
+
+ROOT = Path(__file__).resolve().parent.parent
+sys.path.insert(0, str(ROOT))
+
+
+def load_bench():
+    spec = importlib.util.spec_from_file_location("bench_weights", ROOT / "bench.py")
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)                   # (module level only defines; main() runs under __main__)
+    return mod
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--batches", default="1,8")
+    ap.add_argument("--ks", default="1,3,7")
+    ap.add_argument("--ctx", type=int, default=512)
+    ap.add_argument("--gen", type=int, default=64)
+    ap.add_argument("--passes", type=int, default=32)
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    import torch
+    pkg = importlib.import_module("nano-vllm-go_amd")
+    assert pkg.lib().nvl_device_count() >= 1, "no GPU: nothing here can be measured without one"
+    bench = load_bench()
+    cfg = dict(pkg.synth.FULL_CONFIGS["llama-3.2-1b"])
+    V, S, G = cfg["vocab_size"], args.ctx, args.gen
+    batches = [int(b) for b in args.batches.split(",")]
+    ks = [int(k) for k in args.ks.split(",")]
+    Bmax = max(batches)
+    model = pkg.HipTransformerModel(cfg, None, device=0, precision="bf16", max_seqs=Bmax, max_batch_tokens=Bmax * S)
+    bench.gen_weights_on_device(pkg, cfg, model, torch, torch.device("cuda", 0), keep_host=False)
+    model.finalize()
+    prompts = np.random.default_rng(0).integers(0, V, (Bmax, S)).astype(np.int32)
+    tune = pkg.lib().nvl_set_tuning
+
+    def clock(fn):
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        fn()
+        torch.cuda.synchronize()
+        return time.perf_counter() - t0
+
+    for B in batches:
+        ids = list(range(B))
+
+        def prefill():
+            for i in ids:
+                model.seq_reset(i)
+            _, am = model.forward_batch(ids, [prompts[i] for i in ids], [0] * B, want_logits=False)
+            return am.copy()
+
+        def rewind():
+            for i in ids:
+                model.seq_truncate(i, S)
+
+        first = prefill()
+        ref = model.decode_greedy(ids, first, G + max(ks))             # [steps, B]: the plain greedy ids (also the warm-up)
+        plain = []
+        for _ in range(args.reps):
+            rewind()
+            plain.append(clock(lambda: model.decode_greedy(ids, first, G)) / G * 1e3)
+        print(f"B={B} ctx={S}: plain nvl_decode_greedy {statistics.median(plain):.4f} ms/step "
+              f"(min {min(plain):.4f}, max {max(plain):.4f}; {args.reps} x {G} steps)", flush=True)
+
+        for k in ks:
+            rows = np.concatenate([first[:, None], ref[:k].T], axis=1).astype(np.int32)       # [B, 1+k], drafts all right
+
+            def verify():
+                acc, _ = model.verify_greedy(ids, rows, k)
+                return acc
+
+            def forward_host():
+                logits, _ = model.forward_batch(ids, list(rows), [S] * B, all_logits=True)
+                g = logits.reshape(B, 1 + k, V).argmax(axis=2)
+                acc = np.zeros(B, np.int32)
+                for i in range(B):
+                    while acc[i] < k and rows[i, acc[i] + 1] == g[i, acc[i]]:
+                        acc[i] += 1
+                return acc
+
+            routes = {"a verify key38=1": (1, verify), "b verify key38=0": (0, verify), "c forward+host": (1, forward_host)}
+            times = {name: [] for name in routes}
+            accs = {}
+            for rep in range(args.reps + 1):               # rep 0: warm-up of every route (first sight, graph capture)
+                for name, (mq, fn) in routes.items():
+                    old = tune(38, mq)
+
+                    def many():
+                        for _ in range(args.passes):
+                            accs[name] = fn()
+                            rewind()
+                    rewind()
+                    many() if rep == 0 else times[name].append(clock(many) / args.passes * 1e3)
+                    tune(38, old)
+            line = "  ".join(f"({name}) {statistics.median(t):.4f} [{min(t):.4f}..{max(t):.4f}]" for name, t in times.items())
+            agree = {name: int((a == k).sum()) for name, a in accs.items()}
+            ms_a = statistics.median(times["a verify key38=1"])
+            print(f"B={B} k={k}: rate at full acceptance from (a): {B * (k + 1) / ms_a * 1e3:9.1f} tok/s; at none: "
+                  f"{B / ms_a * 1e3:9.1f} tok/s", flush=True)
+            print(f"B={B} k={k}: ms per pass, median [min..max] of {args.reps} x {args.passes}: {line} | "
+                  f"sequences whose right drafts were all accepted: {agree}", flush=True)
+
+            # the two bounds of the generation rate, key 38 = 1 then 0
+            def generate(right):
+                done, cur, passes = 0, first.copy(), 0
+                while done < G:
+                    d = ref[done:done + k].T if right else (ref[done:done + k].T + 1) % V
+                    acc, toks = model.verify_greedy(ids, np.concatenate([cur[:, None], d], axis=1).astype(np.int32), k)
+                    a = int(acc.min())                      # (all right: k everywhere; all wrong: 0 everywhere)
+                    for i in ids:                           # keep the batch in step where bf16 margins made them differ
+                        if acc[i] > a:
+                            model.seq_truncate(i, model.seq_len(i) - int(acc[i] - a))
+                    cur = toks[:, a].copy()
+                    done += a + 1
+                    passes += 1
+                return passes
+
+            for mq in (1, 0):
+                old = tune(38, mq)
+                res = []
+                for right in (True, False):
+                    rewind(); generate(right)              # warm-up
+                    best, passes = 1e30, 0
+                    for _ in range(3):
+                        rewind()
+                        t0 = time.perf_counter()
+                        passes = generate(right)
+                        best = min(best, time.perf_counter() - t0)
+                    res.append((B * G / best, passes))
+                tune(38, old)
+                print(f"B={B} k={k} key38={mq}: >= {G} tokens per sequence: drafts always right {res[0][0]:9.1f} tok/s in "
+                      f"{res[0][1]} passes, always wrong {res[1][0]:9.1f} tok/s in {res[1][1]} passes "
+                      f"(plain greedy: {B / statistics.median(plain) * 1e3:9.1f} tok/s)", flush=True)
+    model.close()
+
+
+if __name__ == "__main__":
+    main()
