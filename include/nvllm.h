@@ -480,6 +480,47 @@ int nvl_sample(nvl_model* m, int n_rows, const nvl_sampling_params* params, cons
 int nvl_decode_sampled(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
                        const nvl_sampling_params* params, const int32_t* const* history_ptrs, const int32_t* history_lens,
                        const float* uniforms, int32_t* out_tokens);
+/* Sampled speculative decoding.  The reference runner never decodes greedily: every step ends in
+ * SampleWithHistory(logits, seq.TokenIDs, defaultSampling) (tensor_model_runner.go:89-93, sampling.go:33-102), so these are
+ * nvl_verify_greedy / nvl_decode_greedy_lookup under that sampler.  A prompt-lookup draft is a point mass, so exact
+ * speculative sampling needs no rejection step: row j is SAMPLED from the model's own filtered distribution with that decode
+ * step's draw, and the draft token is accepted iff it is the token drawn.  Given the same draws the emitted ids are the
+ * ones the sequential sampler (nvl_sample step by step, nvl_decode_sampled) produces, up to what 1 + k rows per pass do to
+ * the logits (nvl_decode_greedy_lookup's remark).
+ *
+ * nvl_verify_sampled (sampling.go:33-102 per row, tensor_model_runner.go:89-93): tokens [n_seqs][1+k] as nvl_verify_greedy.
+ * history_ptrs[i] / history_lens[i] = Sequence.TokenIDs as row 0 sees it: it ends with tokens[i][0] (nvl_decode_sampled's
+ * contract for first_tokens).  Row j of sequence i sees that history extended by tokens[i][1..j], read on the device from
+ * the pass's own token rows; the "last 10 tokens count 3" window (sampling.go:46-66) runs over the concatenation.
+ * uniforms [n_seqs][1+k]: uniforms[i][j] is the rand.Float32() draw of sequence i's decode step j counted from this pass.
+ * Only the draws of rows 0..a_i are consumed; a caller who wants the Go host's math/rand stream unchanged passes the draws
+ * of the rows behind the accepted prefix again, in order, as the first draws of that sequence's next pass.
+ * s[i][j] = the sampled id; a_i = the longest prefix with tokens[i][j+1] == s[i][j]; n_accepted_out / out_tokens / the cached
+ * length P_i + a_i + 1 / the logits rows left behind / graph replay (parameters, draws and histories are contents of device
+ * buffers, never baked in) as nvl_verify_greedy.  f32 and bf16, every weight and KV mode; key 38 as there.
+ * Refusals: nvl_verify_greedy's, and NVL_ERR_INVALID for a history that is missing or does not end with tokens[i][0],
+ * history_lens[i] + k > max_seq_len, a negative history id, a uniform outside [0, 1], NaN parameters or
+ * repetition_penalty == 0.  A refused call changes no length. */
+int nvl_verify_sampled(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, int k,
+                       const nvl_sampling_params* params, const int32_t* const* history_ptrs, const int32_t* history_lens,
+                       const float* uniforms, int32_t* n_accepted_out, int32_t* out_tokens);
+/* nvl_verify_sampled (sampling.go:33-102, tensor_model_runner.go:89-93) for a paged-KV model: nvl_verify_greedy_paged's
+ * table arguments.  No lengths are kept: the caller advances by a_i + 1. */
+int nvl_verify_sampled_paged(nvl_model* m, int n_seqs, const int32_t* tokens, int k, const int32_t* pos_offsets,
+                             const int32_t* block_tables, const int32_t* table_offsets, const nvl_sampling_params* params,
+                             const int32_t* const* history_ptrs, const int32_t* history_lens, const float* uniforms,
+                             int32_t* n_accepted_out, int32_t* out_tokens);
+/* nvl_decode_sampled's contract (sampling.go:33-102 per step, tensor_model_runner.go:89-93; out_tokens [n_steps][n_seqs],
+ * cached length P_i + n_steps afterwards) driven by nvl_lookup_draft + sampled verify passes over the sequences that still
+ * need tokens, as nvl_decode_greedy_lookup drives the greedy ones (overshoot truncated, a last pass of one row).  uniforms
+ * [n_steps][n_seqs]: decode step t of sequence i always uses uniforms[t][i], however the passes group the steps; draws of
+ * unaccepted rows are not consumed.  The histories (required, each ending with first_tokens[i], ids inside the vocabulary:
+ * drafts are taken from them) are uploaded once; the accept kernel appends what each pass emits, so a pass uploads only
+ * drafts and draws.  f32 and bf16, slab mode only; refusals as nvl_verify_sampled, with history_lens[i] + n_steps >
+ * max_seq_len refused too.  passes_out may be NULL. */
+int nvl_decode_sampled_lookup(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
+                              int k, int ngram, const nvl_sampling_params* params, const int32_t* const* history_ptrs,
+                              const int32_t* history_lens, const float* uniforms, int32_t* out_tokens, int32_t* passes_out);
 /* TensorModelRunner.Run including its sampling step (tensor_model_runner.go:55-97): nvl_runner_run, then
  * SampleWithHistory(lastTokenLogits, seq.TokenIDs, defaultSampling) per sequence on the device. */
 int nvl_runner_run_sampled(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* const* token_ptrs,
@@ -625,6 +666,14 @@ int nvl_op_argmax(int device, const float* x, int rows, int cols, int32_t* out);
 int nvl_op_sample(int device, const float* logits, int rows, int V, const nvl_sampling_params* params,
                   const int32_t* const* history_ptrs, const int32_t* history_lens, const float* uniforms,
                   int32_t* out_tokens, float* probs_out);
+/* The sampler of a sampled verify pass and its accept kernel on host logits [n_seqs * (1+k)][V] (sampling.go:33-102 per
+ * row with the history extension of nvl_verify_sampled; tensor_model_runner.go:89-93).  tokens / histories / uniforms as
+ * nvl_verify_sampled (k may be 0); sampled_out [n_seqs * (1+k)] returns EVERY row's id (the model-level calls return the
+ * accepted ones only); n_accepted_out, out_tokens and probs_out ([n_seqs * (1+k)][V], the final distributions) may be NULL. */
+int nvl_op_sample_drafts(int device, const float* logits, int n_seqs, int k, int V, const nvl_sampling_params* params,
+                         const int32_t* tokens, const int32_t* const* history_ptrs, const int32_t* history_lens,
+                         const float* uniforms, int32_t* sampled_out, int32_t* n_accepted_out, int32_t* out_tokens,
+                         float* probs_out);
 /* The log-probability kernels (nvl_logprobs; generic_model.go:467-470 rows, cmd/check-logits/main.go's view of them) on
  * host logits [rows][ld], V valid columns (ld >= V: the pad columns travel too and are never used), divided by
  * logits_scaling first when it is not 0 (generic_model.go:473-477). */
@@ -676,7 +725,7 @@ int nvl_bench_gemm(int device, int M, int N, int K, int epi, int force_bnt, int 
  * 0 (default): measured slower (rejected list (27)).
  * key 37: rows per chunk of nvl_score's final norm + LM head + log-probability reduction (default 1024; rounded up to a
  * multiple of 16, at least 16): the logits workspace of a scoring pass is that many rows.
- * key 38: verify passes (nvl_verify_greedy*, nvl_decode_greedy_lookup) in bf16 over a bf16 cache run the multi-position
+ * key 38: verify passes (nvl_verify_greedy*, nvl_decode_greedy_lookup, nvl_verify_sampled*, nvl_decode_sampled_lookup) in bf16 over a bf16 cache run the multi-position
  * decode attention (1, default); 0 = rope_kv + the prefill attention kernel, the route of an nvl_forward of 1 + k rows.
  * The settings are PROCESS-GLOBAL and unsynchronised (every model in the process sees them): set them from one thread
  * while no forward call is running.  Every call starts a new tuning epoch: captured decode graphs bake the tuning in and are re-captured.

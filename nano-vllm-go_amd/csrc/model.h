@@ -201,6 +201,7 @@ struct nvl_model {
     bool graphs_ok = true;
     int32_t* am_host = nullptr;                       // pinned: argmax ids of a replayed decode pass
     int32_t* verify_dev = nullptr; int32_t* verify_host = nullptr;    // a verify pass's accept counts + ids (device, pinned)
+    int32_t* vs_dev = nullptr; int32_t* vs_host = nullptr;            // a sampled verify pass's parameters, keeps, history rows, draws
     // debug
     // nvl_set_debug mode 4: in-kernel time stamps of the decode kernels (common.h nvl_stamp), one record per launch
     bool stamping = false; unsigned long long* stamp_buf = nullptr; int stamp_launches = 0;

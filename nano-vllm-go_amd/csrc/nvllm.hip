@@ -390,6 +390,8 @@ extern "C" void nvl_destroy(nvl_model* m) {
     if (m->am_host) (void)hipHostFree(m->am_host);
     if (m->verify_host) (void)hipHostFree(m->verify_host);
     dfree(m->verify_dev);
+    if (m->vs_host) (void)hipHostFree(m->vs_host);
+    dfree(m->vs_dev);
     dfree(m->ring_pos0);
     dfree(m->conv_tail); dfree(m->stamp_buf); dfree(m->ssd_z); dfree(m->ssd_decay);
     dfree(m->ssm_state); dfree(m->mproj); dfree(m->mxbc); dfree(m->mdelta); dfree(m->my); dfree(m->myn);
@@ -1250,6 +1252,8 @@ extern "C" int nvl_finalize(nvl_model* m) {
     NVL_HIP(hipHostMalloc((void**)&m->am_host, (size_t)std::max<int64_t>(S, Mmax) * 4, hipHostMallocDefault));
     NVL_HIP(hipHostMalloc((void**)&m->verify_host, (size_t)(S + Mmax) * 4, hipHostMallocDefault));    // a verify pass: [accepted S | ids Mmax]
     m->verify_dev = dmalloc<int32_t>(S + Mmax);
+    NVL_HIP(hipHostMalloc((void**)&m->vs_host, (size_t)(4 + 3 * S + Mmax) * 4, hipHostMallocDefault));   // a sampled verify pass (bind_vs) + S history lengths to upload
+    m->vs_dev = dmalloc<int32_t>(4 + 2 * S + Mmax);
     m->ring_pos0 = dmalloc<int32_t>(S);
     NVL_HIP(hipStreamSynchronize(m->stream));   // every memset/copy above ran on the model's own (non-blocking) stream
     m->finalized = true;
@@ -2743,7 +2747,7 @@ void decode_loop(nvl_model* m, const Meta& hm, int n_seqs, int n_steps, int32_t*
             a.hist_off = nullptr; a.hist_stride = m->cfg.max_seq_len; a.hist_len = m->samp_hist_len;
             a.uniforms = uniforms_dev + (int64_t)s * n_seqs; a.out = m->samp.out; a.probs_out = nullptr; a.ldp = m->V;
             a.V = m->V; a.top_k = sp->top_k; a.temperature = sp->temperature; a.top_p = sp->top_p; a.rep_penalty = sp->repetition_penalty;
-            hipLaunchKernelGGL(sample_row_kernel, dim3(n_seqs), dim3(SAMPLE_THREADS), 0, m->stream, a);
+            hipLaunchKernelGGL(sample_row_kernel<false>, dim3(n_seqs), dim3(SAMPLE_THREADS), 0, m->stream, a);
             NVL_HIP(hipGetLastError());
         }
         if (seam_ok) {
@@ -2900,10 +2904,75 @@ __global__ void verify_accept_kernel(const int32_t* __restrict__ argmax, const i
     for (int j = 0; j < S; j++) o[j] = j <= a ? g[j] : -1;
 }
 
+// The sampled twin: s = the ids sample_row_kernel<true> drew for the pass's rows; same rule, same result
+// layout.  hist != NULL (nvl_decode_sampled_lookup): sequence i's history is row hist_row[i] of the device history buffer;
+// the kernel appends s[0 .. min(a, keep[i] - 1)], the tokens the loop emits, and advances the length, so the next pass
+// finds the history current and uploads only drafts and draws.
+__global__ void verify_accept_sampled_kernel(const int32_t* __restrict__ s, const int32_t* __restrict__ tokens, int k, int n,
+                                             int32_t* __restrict__ res, int32_t* __restrict__ hist, int64_t hist_stride,
+                                             int32_t* __restrict__ hist_len, const int32_t* __restrict__ hist_row,
+                                             const int32_t* __restrict__ keep) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int S = 1 + k;
+    const int32_t* g = s + (int64_t)i * S;
+    const int32_t* t = tokens + (int64_t)i * S;
+    int a = 0;
+    while (a < k && t[a + 1] == g[a]) a++;
+    res[i] = a;
+    int32_t* o = res + n + (int64_t)i * S;
+    for (int j = 0; j < S; j++) o[j] = j <= a ? g[j] : -1;
+    if (hist) {
+        const int h = hist_row[i], len = hist_len[h];
+        const int take = min(min(a + 1, keep[i]), (int)hist_stride - len);
+        for (int j = 0; j < take; j++) hist[(int64_t)h * hist_stride + len + j] = g[j];
+        hist_len[h] = len + take;
+    }
+}
+
+// What a sampled verify pass reads besides the metadata, in ONE pinned block mirrored on the device (vs_host / vs_dev):
+//   [nvl_sampling_params | keep n_seqs | hist_row n_seqs | uniforms M]
+// A captured pass bakes in only addresses inside the block: parameters, draws and history rows are its CONTENTS.
+struct VsBlock { nvl_sampling_params* params; int32_t *keep, *hist_row; float* u; };
+VsBlock bind_vs(int32_t* base, int n_seqs) {
+    return VsBlock{(nvl_sampling_params*)base, base + 4, base + 4 + n_seqs, (float*)(base + 4 + 2 * n_seqs)};
+}
+static_assert(sizeof(nvl_sampling_params) == 16, "bind_vs layout");
+// `append`: the accept kernel also appends the emitted ids to the device histories (the loop); the histories themselves are
+// rows of m->samp_hist with lengths m->samp_hist_len in either case.
+struct SampledPass { bool append; };
+
+// the sampler's scratch for `rows` rows; a captured sampled pass holds these addresses
+void reserve_sample_rows(nvl_model* m, int rows) {
+    SampleBufs& b = m->samp;
+    const int64_t elems = (int64_t)rows * round_up(m->V, 4);
+    if (elems > b.elems || rows > b.rows_cap) clear_graphs(m);
+    if (elems > b.elems) {
+        dfree(b.work); dfree(b.cnt); b.work = nullptr; b.cnt = nullptr; b.elems = 0;
+        b.work = dmalloc<float>(elems); b.cnt = dmalloc<int32_t>(elems); b.elems = elems;
+        NVL_HIP(hipMemsetAsync(b.cnt, 0, (size_t)elems * 4, m->stream));
+    }
+    if (rows > b.rows_cap) {
+        dfree(b.off); dfree(b.out); dfree(b.u); b.off = nullptr; b.out = nullptr; b.u = nullptr; b.rows_cap = 0;
+        const int cap = (int)round_up(rows, 64);
+        b.off = dmalloc<int32_t>(cap + 1); b.out = dmalloc<int32_t>(cap); b.u = dmalloc<float>(cap);
+        b.rows_cap = cap;
+    }
+}
+// the device-kept histories: one row of max_seq_len ids per sequence, allocated once (the address never changes)
+void reserve_sample_hist(nvl_model* m) {
+    if (m->samp_hist) return;
+    m->samp_hist_cap = (int64_t)m->opts.max_seqs * m->cfg.max_seq_len;
+    m->samp_hist = dmalloc<int32_t>(m->samp_hist_cap); m->samp_hist_len = dmalloc<int32_t>(m->opts.max_seqs);
+}
+
 // The pass itself, metadata already in meta_host (n_seqs sequences of 1 + k rows each, positions h_pos[i] ..): upload,
 // launches, accept kernel and result download — captured and replayed like a decode pass when every projection is in
 // decode form (<= 64 rows) — then the host copies.  Leaves the n_seqs x (1+k) logits rows as the last forward group.
-void verify_pass(nvl_model* m, int n_seqs, int k, const int32_t* h_pos, int32_t* n_acc_out, int32_t* out_tokens) {
+// `sp` != NULL: a sampled pass (vs_host filled, histories on the device): the sampler and its accept kernel take the place of
+// the argmax and verify_accept_kernel.
+void verify_pass(nvl_model* m, int n_seqs, int k, const int32_t* h_pos, int32_t* n_acc_out, int32_t* out_tokens,
+                 const SampledPass* sp = nullptr) {
     const int S = 1 + k, M = n_seqs * S;
     const Meta md = bind_meta(m, m->meta_dev, M);
     NVL_HIP(hipEventRecord(m->ev0, m->stream));
@@ -2917,17 +2986,34 @@ void verify_pass(nvl_model* m, int n_seqs, int k, const int32_t* h_pos, int32_t*
     m->kv_tok = kv_tok;
     const bool mq = g_verify_mq && attention_mq_ok(m, S);
     const int nres = n_seqs * (1 + S);
+    if (sp) reserve_sample_rows(m, M);
     auto pass = [&] {
         NVL_HIP(hipMemcpyAsync(m->meta_dev, m->meta_host, meta_bytes(m, M), hipMemcpyHostToDevice, m->stream));
-        enqueue_forward(m, md, n_seqs, M, S, attn_flops, NVL_FWD_ALL_LOGITS, mq ? 8 : 0);
-        hipLaunchKernelGGL(verify_accept_kernel, dim3(cdiv(n_seqs, 64)), dim3(64), 0, m->stream, m->argmax_dev, md.tokens, k, n_seqs, m->verify_dev);
+        if (sp) {
+            NVL_HIP(hipMemcpyAsync(m->vs_dev, m->vs_host, (size_t)(4 + 2 * n_seqs + M) * 4, hipMemcpyHostToDevice, m->stream));
+            enqueue_forward(m, md, n_seqs, M, S, attn_flops, NVL_FWD_ALL_LOGITS, (mq ? 8 : 0) | 4);
+            const VsBlock vs = bind_vs(m->vs_dev, n_seqs);
+            SampleArgs a{};
+            a.logits = m->logits; a.ld = m->Vpad; a.work = m->samp.work; a.cnt = m->samp.cnt; a.hist = m->samp_hist;
+            a.hist_off = nullptr; a.hist_stride = m->cfg.max_seq_len; a.hist_len = m->samp_hist_len;
+            a.uniforms = vs.u; a.out = m->samp.out; a.probs_out = nullptr; a.ldp = m->V; a.V = m->V;
+            a.ext = md.tokens; a.ext_S = S; a.hist_row = vs.hist_row; a.params = vs.params;
+            hipLaunchKernelGGL(sample_row_kernel<true>, dim3(M), dim3(SAMPLE_THREADS), 0, m->stream, a);
+            NVL_HIP(hipGetLastError());
+            hipLaunchKernelGGL(verify_accept_sampled_kernel, dim3(cdiv(n_seqs, 64)), dim3(64), 0, m->stream, (const int32_t*)m->samp.out,
+                               (const int32_t*)md.tokens, k, n_seqs, m->verify_dev, sp->append ? m->samp_hist : (int32_t*)nullptr,
+                               (int64_t)m->cfg.max_seq_len, m->samp_hist_len, (const int32_t*)vs.hist_row, (const int32_t*)vs.keep);
+        } else {
+            enqueue_forward(m, md, n_seqs, M, S, attn_flops, NVL_FWD_ALL_LOGITS, mq ? 8 : 0);
+            hipLaunchKernelGGL(verify_accept_kernel, dim3(cdiv(n_seqs, 64)), dim3(64), 0, m->stream, m->argmax_dev, md.tokens, k, n_seqs, m->verify_dev);
+        }
         NVL_HIP(hipGetLastError());
         NVL_HIP(hipMemcpyAsync(m->verify_host, m->verify_dev, (size_t)nres * 4, hipMemcpyDeviceToHost, m->stream));
     };
     bool replayed = false;
     if (M <= 64 && M <= m->logit_rows) {
         const int acfg = mq ? decode_attn_cfg(m, n_seqs, S) : (S == 1 ? decode_attn_waves(m, n_seqs) : 0);
-        const std::array<int, 5> key{3, n_seqs, acfg, k | (mq ? 256 : 0), g_tune_epoch};
+        const std::array<int, 5> key{sp ? 4 : 3, n_seqs, acfg, k | (mq ? 256 : 0) | (sp && sp->append ? 512 : 0), g_tune_epoch};
         replayed = replay_or_capture(m, key, pass);
     }
     if (!replayed) pass();
@@ -2955,10 +3041,55 @@ int verify_refusals(nvl_model* m, const char* who, int n_seqs, int k, int k_min)
     return NVL_OK;
 }
 
+// ---- the sampled calls' arguments (SampleWithHistory per row, sampling.go:33-102) ----
+struct SampledReq { const nvl_sampling_params* params; const int32_t* const* hist_ptrs; const int32_t* hist_lens; const float* uniforms; };
+
+bool sampling_params_ok(const nvl_sampling_params* sp) {     // the rules of nvl_sample / nvl_decode_sampled
+    return sp->repetition_penalty != 0.f && sp->repetition_penalty == sp->repetition_penalty &&
+           sp->temperature == sp->temperature && sp->top_p == sp->top_p;
+}
+// every history present, ending with its sequence's first token of the pass, free of negative ids, and short enough that
+// history + `grow` more ids fit `max_len`; `n_u` draws inside [0, 1].  Pure validation.
+const char* sampled_check(const SampledReq& rq, int n_seqs, const int32_t* first, int first_stride, int grow, int64_t max_len, int64_t n_u) {
+    if (!sampling_params_ok(rq.params)) return "bad sampling parameters (NaN, or repetition_penalty 0)";
+    for (int i = 0; i < n_seqs; i++) {
+        const int hn = rq.hist_lens[i];
+        if (!rq.hist_ptrs[i] || hn <= 0) return "a sequence has no history (it must end with the sequence's first token)";
+        if ((int64_t)hn + grow > max_len) return "history longer than max_seq_len";
+        if (rq.hist_ptrs[i][hn - 1] != first[(int64_t)i * first_stride]) return "a history must end with its first token";
+        for (int j = 0; j < hn; j++) if (rq.hist_ptrs[i][j] < 0) return "negative token id in the history";
+    }
+    for (int64_t i = 0; i < n_u; i++) if (!(rq.uniforms[i] >= 0.f && rq.uniforms[i] <= 1.f)) return "uniform draw outside [0, 1]";
+    return nullptr;
+}
+// histories -> rows 0 .. n_seqs-1 of the device history buffer (the lengths go through the pinned tail of vs_host).  The
+// caller's arrays must stay alive until the stream is synchronised.
+void sampled_stage_histories(nvl_model* m, int n_seqs, const SampledReq& rq) {
+    reserve_sample_hist(m);
+    const int64_t T = m->cfg.max_seq_len;
+    int32_t* hlen = m->vs_host + 4 + 2 * (int64_t)m->opts.max_seqs + m->opts.max_batch_tokens;
+    for (int i = 0; i < n_seqs; i++) {
+        hlen[i] = rq.hist_lens[i];
+        NVL_HIP(hipMemcpyAsync(m->samp_hist + i * T, rq.hist_ptrs[i], (size_t)rq.hist_lens[i] * 4, hipMemcpyHostToDevice, m->stream));
+    }
+    NVL_HIP(hipMemcpyAsync(m->samp_hist_len, hlen, (size_t)n_seqs * 4, hipMemcpyHostToDevice, m->stream));
+}
+// a single sampled pass (nvl_verify_sampled[_paged]): stage the histories and fill the pass's block
+void sampled_stage_pass(nvl_model* m, int n_seqs, int k, const SampledReq& rq) {
+    sampled_stage_histories(m, n_seqs, rq);
+    const int S = 1 + k;
+    const VsBlock vs = bind_vs(m->vs_host, n_seqs);
+    *vs.params = *rq.params;
+    for (int i = 0; i < n_seqs; i++) { vs.keep[i] = S; vs.hist_row[i] = i; }
+    memcpy(vs.u, rq.uniforms, (size_t)n_seqs * S * 4);
+}
+
 // nvl_verify_greedy (k_min = 1) and the passes of nvl_decode_greedy_lookup (k_min = 0: a last pass of one row per sequence).
 // keep[i] (or NULL): at most that many of sequence i's accepted tokens stay in the cache.
+// rq != NULL: nvl_verify_sampled — checked here, after everything else, and staged; sp != NULL alone: a pass of
+// nvl_decode_sampled_lookup, which has staged its histories and filled the block itself.
 int verify_slab(nvl_model* m, const char* who, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, int k, int k_min,
-                int32_t* n_acc_out, int32_t* out_tokens, const int* keep) {
+                int32_t* n_acc_out, int32_t* out_tokens, const int* keep, const SampledReq* rq = nullptr, const SampledPass* sp = nullptr) {
     const int rc = verify_refusals(m, who, n_seqs, k, k_min);
     if (rc) return rc;
     if (m->paged) return fail(m, NVL_ERR_STATE, std::string(who) + ": the model is in paged-KV mode (use nvl_verify_greedy_paged)");
@@ -2979,7 +3110,13 @@ int verify_slab(nvl_model* m, const char* who, int n_seqs, const int64_t* seq_id
         }
         hm.last_rows[i] = i * S + S - 1;
     }
-    verify_pass(m, n_seqs, k, hm.seq_pos, n_acc_out, out_tokens);
+    const SampledPass single{false};
+    if (rq) {
+        if (const char* why = sampled_check(*rq, n_seqs, tokens, S, k, m->cfg.max_seq_len, (int64_t)M)) return fail(m, NVL_ERR_INVALID, std::string(who) + ": " + why);
+        sampled_stage_pass(m, n_seqs, k, *rq);
+        sp = &single;
+    }
+    verify_pass(m, n_seqs, k, hm.seq_pos, n_acc_out, out_tokens, sp);
     // rollback: the accepted prefix and the row that produced the first unaccepted id stay; the rows behind are dead
     for (int i = 0; i < n_seqs; i++) {
         int adv = m->verify_host[i] + 1;
@@ -3000,6 +3137,48 @@ extern "C" int nvl_verify_greedy(nvl_model* m, int n_seqs, const int64_t* seq_id
     NVL_CATCH(m)
 }
 
+namespace {
+int verify_paged(nvl_model* m, const std::string& who, int n_seqs, const int32_t* tokens, int k, const int32_t* pos_offsets,
+                 const int32_t* block_tables, const int32_t* table_offsets, int32_t* n_accepted_out, int32_t* out_tokens,
+                 const SampledReq* rq) {
+    const int rc = verify_refusals(m, who.c_str(), n_seqs, k, 1);
+    if (rc) return rc;
+    if (!m->paged) return fail(m, NVL_ERR_STATE, who + ": the model was created without kv_num_blocks");
+    const int S = 1 + k, M = n_seqs * S, BS = m->Tmax;
+    const Meta hm = bind_meta(m, m->meta_host, M);
+    if (table_offsets[0] < 0) return fail(m, NVL_ERR_INVALID, who + ": negative table offset");
+    for (int i = 0; i < n_seqs; i++) {
+        const int pos = pos_offsets[i];
+        if (pos < 0) return fail(m, NVL_ERR_INVALID, who + ": negative pos_offset");
+        if (pos > m->cfg.max_seq_len - S) return fail(m, NVL_ERR_POSITION, who + ": position exceeds max_seq_len");
+        if (table_offsets[i + 1] < table_offsets[i]) return fail(m, NVL_ERR_INVALID, who + ": table_offsets must be non-decreasing");
+        const int nb = table_offsets[i + 1] - table_offsets[i];
+        if (nb < cdiv(pos + S, BS)) return fail(m, NVL_ERR_INVALID, who + ": block table shorter than the sequence");
+        if (nb > m->blocks_per_seq) return fail(m, NVL_ERR_INVALID, who + ": block table too long");
+        const int tb = i * m->blocks_per_seq;
+        for (int j = 0; j < nb; j++) {
+            const int b = block_tables[table_offsets[i] + j];
+            if (b < 0 || b >= m->num_blocks) return fail(m, NVL_ERR_INVALID, who + ": block id out of range");
+            hm.blk_table[tb + j] = b;
+        }
+        hm.seq_tok_start[i] = i * S; hm.seq_len[i] = S; hm.seq_pos[i] = pos; hm.seq_tbl[i] = tb;
+        for (int j = 0; j < S; j++) {
+            const int tok = tokens[i * S + j];
+            if (tok < 0 || tok >= m->V) return fail(m, NVL_ERR_INVALID, who + ": token id out of range");
+            hm.tokens[i * S + j] = tok; hm.tok_pos[i * S + j] = pos + j; hm.tok_tbl[i * S + j] = tb;
+        }
+        hm.last_rows[i] = i * S + S - 1;
+    }
+    const SampledPass single{false};
+    if (rq) {
+        if (const char* why = sampled_check(*rq, n_seqs, tokens, S, k, m->cfg.max_seq_len, (int64_t)M)) return fail(m, NVL_ERR_INVALID, who + ": " + why);
+        sampled_stage_pass(m, n_seqs, k, *rq);
+    }
+    verify_pass(m, n_seqs, k, hm.seq_pos, n_accepted_out, out_tokens, rq ? &single : nullptr);
+    return NVL_OK;
+}
+}  // namespace
+
 extern "C" int nvl_verify_greedy_paged(nvl_model* m, int n_seqs, const int32_t* tokens, int k, const int32_t* pos_offsets,
                                        const int32_t* block_tables, const int32_t* table_offsets, int32_t* n_accepted_out,
                                        int32_t* out_tokens) {
@@ -3008,36 +3187,40 @@ extern "C" int nvl_verify_greedy_paged(nvl_model* m, int n_seqs, const int32_t* 
         return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: null arguments");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
-    const int rc = verify_refusals(m, "nvl_verify_greedy_paged", n_seqs, k, 1);
-    if (rc) return rc;
-    if (!m->paged) return fail(m, NVL_ERR_STATE, "nvl_verify_greedy_paged: the model was created without kv_num_blocks");
-    const int S = 1 + k, M = n_seqs * S, BS = m->Tmax;
-    const Meta hm = bind_meta(m, m->meta_host, M);
-    if (table_offsets[0] < 0) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: negative table offset");
-    for (int i = 0; i < n_seqs; i++) {
-        const int pos = pos_offsets[i];
-        if (pos < 0) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: negative pos_offset");
-        if (pos > m->cfg.max_seq_len - S) return fail(m, NVL_ERR_POSITION, "nvl_verify_greedy_paged: position exceeds max_seq_len");
-        if (table_offsets[i + 1] < table_offsets[i]) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: table_offsets must be non-decreasing");
-        const int nb = table_offsets[i + 1] - table_offsets[i];
-        if (nb < cdiv(pos + S, BS)) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: block table shorter than the sequence");
-        if (nb > m->blocks_per_seq) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: block table too long");
-        const int tb = i * m->blocks_per_seq;
-        for (int j = 0; j < nb; j++) {
-            const int b = block_tables[table_offsets[i] + j];
-            if (b < 0 || b >= m->num_blocks) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: block id out of range");
-            hm.blk_table[tb + j] = b;
-        }
-        hm.seq_tok_start[i] = i * S; hm.seq_len[i] = S; hm.seq_pos[i] = pos; hm.seq_tbl[i] = tb;
-        for (int j = 0; j < S; j++) {
-            const int tok = tokens[i * S + j];
-            if (tok < 0 || tok >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: token id out of range");
-            hm.tokens[i * S + j] = tok; hm.tok_pos[i * S + j] = pos + j; hm.tok_tbl[i * S + j] = tb;
-        }
-        hm.last_rows[i] = i * S + S - 1;
-    }
-    verify_pass(m, n_seqs, k, hm.seq_pos, n_accepted_out, out_tokens);
-    return NVL_OK;
+    return verify_paged(m, "nvl_verify_greedy_paged", n_seqs, tokens, k, pos_offsets, block_tables, table_offsets, n_accepted_out,
+                        out_tokens, nullptr);
+    NVL_CATCH(m)
+}
+
+// ---- sampled speculative decoding: the verify pass under tensor.SampleWithHistory (sampling.go:33-102),
+// the step every TensorModelRunner.Run ends in (tensor_model_runner.go:89-93) ----
+extern "C" int nvl_verify_sampled(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, int k,
+                                  const nvl_sampling_params* params, const int32_t* const* history_ptrs, const int32_t* history_lens,
+                                  const float* uniforms, int32_t* n_accepted_out, int32_t* out_tokens) {
+    if (!m) return NVL_ERR_INVALID;
+    if (!seq_ids || !tokens || !params || !history_ptrs || !history_lens || !uniforms || !n_accepted_out || !out_tokens)
+        return fail(m, NVL_ERR_INVALID, "nvl_verify_sampled: null arguments");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    const SampledReq rq{params, history_ptrs, history_lens, uniforms};
+    return verify_slab(m, "nvl_verify_sampled", n_seqs, seq_ids, tokens, k, 1, n_accepted_out, out_tokens, nullptr, &rq);
+    NVL_CATCH(m)
+}
+
+extern "C" int nvl_verify_sampled_paged(nvl_model* m, int n_seqs, const int32_t* tokens, int k, const int32_t* pos_offsets,
+                                        const int32_t* block_tables, const int32_t* table_offsets,
+                                        const nvl_sampling_params* params, const int32_t* const* history_ptrs,
+                                        const int32_t* history_lens, const float* uniforms, int32_t* n_accepted_out,
+                                        int32_t* out_tokens) {
+    if (!m) return NVL_ERR_INVALID;
+    if (!tokens || !pos_offsets || !block_tables || !table_offsets || !params || !history_ptrs || !history_lens || !uniforms ||
+        !n_accepted_out || !out_tokens)
+        return fail(m, NVL_ERR_INVALID, "nvl_verify_sampled_paged: null arguments");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    const SampledReq rq{params, history_ptrs, history_lens, uniforms};
+    return verify_paged(m, "nvl_verify_sampled_paged", n_seqs, tokens, k, pos_offsets, block_tables, table_offsets, n_accepted_out,
+                        out_tokens, &rq);
     NVL_CATCH(m)
 }
 
@@ -3130,6 +3313,84 @@ extern "C" int nvl_decode_greedy_lookup(nvl_model* m, int n_seqs, const int64_t*
     NVL_CATCH(m)
 }
 
+// nvl_decode_sampled's contract from prompt-lookup drafts + sampled verify passes: nvl_decode_greedy_lookup's loop with
+// the histories kept on the device (uploaded once; verify_accept_sampled_kernel appends what each pass emits) and the draw
+// of decode step t of sequence i fixed to uniforms[t][i] however the passes group the steps.
+extern "C" int nvl_decode_sampled_lookup(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
+                                         int k, int ngram, const nvl_sampling_params* params, const int32_t* const* history_ptrs,
+                                         const int32_t* history_lens, const float* uniforms, int32_t* out_tokens, int32_t* passes_out) {
+    if (!m) return NVL_ERR_INVALID;
+    if (!seq_ids || !first_tokens || !params || !history_ptrs || !history_lens || !uniforms || !out_tokens || n_steps <= 0 || ngram < 1)
+        return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled_lookup: null/empty arguments");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    int rc = verify_refusals(m, "nvl_decode_sampled_lookup", n_seqs, k, 1);
+    if (rc) return rc;
+    if (m->paged) return fail(m, NVL_ERR_STATE, "nvl_decode_sampled_lookup: not available in paged-KV mode");
+    for (int i = 0; i < n_seqs; i++) {
+        auto it = m->seq_slot.find(seq_ids[i]);
+        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_decode_sampled_lookup: sequence has no KV slot");
+        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled_lookup: duplicate sequence");
+        if (m->slot_len[(size_t)it->second] + n_steps > m->cfg.max_seq_len) return fail(m, NVL_ERR_POSITION, "nvl_decode_sampled_lookup: position exceeds max_seq_len");
+        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled_lookup: token id out of range");
+        if (history_ptrs[i])       // (drafts are taken from the history and fed to the model)
+            for (int j = 0; j < history_lens[i]; j++)
+                if (history_ptrs[i][j] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled_lookup: history id outside the vocabulary");
+    }
+    const SampledReq rq{params, history_ptrs, history_lens, uniforms};
+    if (const char* why = sampled_check(rq, n_seqs, first_tokens, 1, n_steps, m->cfg.max_seq_len, (int64_t)n_steps * n_seqs))
+        return fail(m, NVL_ERR_INVALID, std::string("nvl_decode_sampled_lookup: ") + why);
+    std::vector<std::vector<int32_t>> hist((size_t)n_seqs);       // the host's copy, for drafting only
+    for (int i = 0; i < n_seqs; i++) hist[(size_t)i].assign(history_ptrs[i], history_ptrs[i] + history_lens[i]);
+    std::vector<int> done((size_t)n_seqs, 0);
+    sampled_stage_histories(m, n_seqs, rq);
+    const SampledPass sp{true};
+    int passes = 0;
+    std::vector<int64_t> ids; std::vector<int> who, keep; std::vector<int32_t> toks, acc, got;
+    for (;;) {
+        who.clear(); ids.clear(); keep.clear();
+        int k_pass = 0, room = k;
+        for (int i = 0; i < n_seqs; i++) {
+            if (done[(size_t)i] >= n_steps) continue;
+            who.push_back(i); ids.push_back(seq_ids[i]); keep.push_back(n_steps - done[(size_t)i]);
+            k_pass = std::max(k_pass, n_steps - done[(size_t)i] - 1);
+            room = std::min(room, m->cfg.max_seq_len - m->slot_len[(size_t)m->seq_slot[seq_ids[i]]] - 1);
+        }
+        if (who.empty()) break;
+        k_pass = std::min(k_pass, room);
+        const int na = (int)who.size(), S = 1 + k_pass;
+        toks.assign((size_t)na * S, 0); acc.assign((size_t)na, 0); got.assign((size_t)na * S, -1);
+        const VsBlock vs = bind_vs(m->vs_host, na);
+        *vs.params = *params;
+        for (int a = 0; a < na; a++) {
+            const int i = who[(size_t)a];
+            const std::vector<int32_t>& h = hist[(size_t)i];
+            toks[(size_t)a * S] = h.back();
+            if (k_pass > 0) (void)nvl_lookup_draft(h.data(), (int)h.size(), k_pass, ngram, &toks[(size_t)a * S + 1]);
+            vs.keep[a] = keep[(size_t)a]; vs.hist_row[a] = i;
+            for (int j = 0; j < S; j++) {       // row j is decode step done + j of the sequence; rows past the last step are never emitted
+                const int t = done[(size_t)i] + j;
+                vs.u[a * S + j] = t < n_steps ? uniforms[(size_t)t * n_seqs + i] : 0.f;
+            }
+        }
+        rc = verify_slab(m, "nvl_decode_sampled_lookup", na, ids.data(), toks.data(), k_pass, 0, acc.data(), got.data(), keep.data(), nullptr, &sp);
+        if (rc) { (void)hipStreamSynchronize(m->stream); return rc; }      // (the staged histories read the caller's arrays)
+        passes++;
+        for (int a = 0; a < na; a++) {
+            const int i = who[(size_t)a], take = std::min(acc[(size_t)a] + 1, keep[(size_t)a]);
+            for (int j = 0; j < take; j++) {
+                const int32_t t = got[(size_t)a * S + j];
+                out_tokens[(size_t)(done[(size_t)i] + j) * n_seqs + i] = t;
+                hist[(size_t)i].push_back(t);
+            }
+            done[(size_t)i] += take;
+        }
+    }
+    if (passes_out) *passes_out = passes;
+    return NVL_OK;
+    NVL_CATCH(m)
+}
+
 // nvl_decode_greedy with the reference runner's sampling step instead of the argmax (tensor_model_runner.go:89-93):
 // every step draws SampleWithHistory(logits, seq.TokenIDs, params) on the device and feeds the token back.
 // history_ptrs[i]/history_lens[i] = Sequence.TokenIDs as the first decode step sees it (prompt + the token sampled from
@@ -3178,6 +3439,7 @@ extern "C" int nvl_decode_sampled(nvl_model* m, int n_seqs, const int64_t* seq_i
     // device state of the sampler
     SampleBufs& b = m->samp;
     const int64_t elems = (int64_t)n_seqs * round_up(m->V, 4);
+    if (elems > b.elems || n_seqs > b.rows_cap) clear_graphs(m);      // (captured sampled verify passes hold the old addresses)
     if (elems > b.elems) {
         dfree(b.work); dfree(b.cnt);
         b.work = dmalloc<float>(elems); b.cnt = dmalloc<int32_t>(elems); b.elems = elems;
@@ -3456,7 +3718,7 @@ int sample_rows(hipStream_t st, SampleBufs& b, const float* logits_dev, int64_t 
     a.logits = logits_dev; a.ld = ld; a.work = b.work; a.cnt = b.cnt; a.hist = b.hist; a.hist_off = b.off;
     a.uniforms = b.u; a.out = b.out; a.probs_out = probs_host ? b.probs : nullptr; a.ldp = V;
     a.V = V; a.top_k = sp->top_k; a.temperature = sp->temperature; a.top_p = sp->top_p; a.rep_penalty = sp->repetition_penalty;
-    hipLaunchKernelGGL(sample_row_kernel, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
+    hipLaunchKernelGGL(sample_row_kernel<false>, dim3(rows), dim3(SAMPLE_THREADS), 0, st, a);
     NVL_HIP(hipGetLastError());
     NVL_HIP(hipMemcpyAsync(out_host, b.out, (size_t)rows * 4, hipMemcpyDeviceToHost, st));
     if (probs_host) NVL_HIP(hipMemcpyAsync(probs_host, b.probs, (size_t)rows * V * 4, hipMemcpyDeviceToHost, st));
@@ -3473,6 +3735,8 @@ extern "C" int nvl_sample(nvl_model* m, int n_rows, const nvl_sampling_params* p
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
     std::string err;
+    // (captured sampled verify passes hold the scratch addresses sample_rows is about to replace)
+    if ((int64_t)n_rows * round_up(m->V, 4) > m->samp.elems || n_rows > m->samp.rows_cap) clear_graphs(m);
     const int rc = sample_rows(m->stream, m->samp, m->logits, m->Vpad, n_rows, m->V, params, history_ptrs, history_lens,
                                uniforms, out_tokens, nullptr, err);
     return rc ? fail(m, rc, "nvl_sample: " + err) : NVL_OK;

@@ -599,6 +599,57 @@ extern "C" int nvl_op_sample(int device, const float* logits, int rows, int V, c
     OP_CATCH
 }
 
+// The sampler of a sampled verify pass (sample_row_kernel<true>, histories in the offset form) and its accept kernel on
+// host logits [n_seqs * (1+k)][V].
+extern "C" int nvl_op_sample_drafts(int device, const float* logits, int n_seqs, int k, int V, const nvl_sampling_params* params,
+                                    const int32_t* tokens, const int32_t* const* history_ptrs, const int32_t* history_lens,
+                                    const float* uniforms, int32_t* sampled_out, int32_t* n_accepted_out, int32_t* out_tokens,
+                                    float* probs_out) {
+    if (!logits || n_seqs <= 0 || k < 0 || k > 7 || V <= 0 || !params || !tokens || !history_ptrs || !history_lens || !uniforms || !sampled_out)
+        return op_fail("nvl_op_sample_drafts: bad arguments");
+    const int S = 1 + k, M = n_seqs * S;
+    const SampledReq rq{params, history_ptrs, history_lens, uniforms};
+    if (const char* why = sampled_check(rq, n_seqs, tokens, S, 0, INT64_MAX, (int64_t)M)) return op_fail(std::string("nvl_op_sample_drafts: ") + why);
+    for (int r = 0; r < M; r++) if (tokens[r] < 0) return op_fail("nvl_op_sample_drafts: negative token id");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_F32);
+    std::vector<int32_t> off((size_t)n_seqs + 1, 0), hist;
+    for (int i = 0; i < n_seqs; i++) {
+        hist.insert(hist.end(), history_ptrs[i], history_ptrs[i] + history_lens[i]);
+        off[(size_t)i + 1] = (int32_t)hist.size();
+    }
+    const int64_t Vp = round_up(V, 4);
+    auto up_i32 = [&](const void* h, int64_t n) {
+        void* d = cx.alloc(n * 4);
+        NVL_HIP(hipMemcpyAsync(d, h, (size_t)n * 4, hipMemcpyHostToDevice, cx.m.stream));
+        return d;
+    };
+    SampleArgs a{};
+    a.logits = cx.up_f32(logits, (int64_t)M * V); a.ld = V;
+    a.work = (float*)cx.alloc((int64_t)M * Vp * 4);
+    a.cnt = (int32_t*)cx.alloc((int64_t)M * V * 4);
+    NVL_HIP(hipMemsetAsync(a.cnt, 0, (size_t)M * V * 4, cx.m.stream));
+    a.hist = (const int32_t*)up_i32(hist.data(), (int64_t)hist.size()); a.hist_off = (const int32_t*)up_i32(off.data(), (int64_t)off.size());
+    a.uniforms = (const float*)up_i32(uniforms, M);
+    a.out = (int32_t*)cx.alloc((int64_t)M * 4);
+    a.probs_out = probs_out ? (float*)cx.alloc((int64_t)M * V * 4) : nullptr; a.ldp = V;
+    a.V = V; a.top_k = params->top_k; a.temperature = params->temperature; a.top_p = params->top_p; a.rep_penalty = params->repetition_penalty;
+    a.ext = (const int32_t*)up_i32(tokens, M); a.ext_S = S; a.hist_row = nullptr; a.params = nullptr;
+    int32_t* res = (int32_t*)cx.alloc((int64_t)(n_seqs + M) * 4);
+    hipLaunchKernelGGL(sample_row_kernel<true>, dim3(M), dim3(SAMPLE_THREADS), 0, cx.m.stream, a);
+    NVL_HIP(hipGetLastError());
+    hipLaunchKernelGGL(verify_accept_sampled_kernel, dim3(cdiv(n_seqs, 64)), dim3(64), 0, cx.m.stream, (const int32_t*)a.out, a.ext, k, n_seqs,
+                       res, (int32_t*)nullptr, (int64_t)0, (int32_t*)nullptr, (const int32_t*)nullptr, (const int32_t*)nullptr);
+    NVL_HIP(hipGetLastError());
+    NVL_HIP(hipMemcpyAsync(sampled_out, a.out, (size_t)M * 4, hipMemcpyDeviceToHost, cx.m.stream));
+    if (n_accepted_out) NVL_HIP(hipMemcpyAsync(n_accepted_out, res, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, cx.m.stream));
+    if (out_tokens) NVL_HIP(hipMemcpyAsync(out_tokens, res + n_seqs, (size_t)M * 4, hipMemcpyDeviceToHost, cx.m.stream));
+    if (probs_out) NVL_HIP(hipMemcpyAsync(probs_out, a.probs_out, (size_t)M * V * 4, hipMemcpyDeviceToHost, cx.m.stream));
+    NVL_HIP(hipStreamSynchronize(cx.m.stream));   // (also keeps the host vectors alive until the copies are done)
+    return NVL_OK;
+    OP_CATCH
+}
+
 extern "C" int nvl_op_logprobs(int device, const float* logits, int rows, int V, int ld, float logits_scaling,
                                const int32_t* targets, int top_k, float* logprob_out, int32_t* argmax_out,
                                int32_t* topk_ids_out, float* topk_logprob_out) {

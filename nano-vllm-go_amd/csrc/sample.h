@@ -27,6 +27,12 @@ struct SampleArgs {
     float* probs_out; int64_t ldp;        // optional [rows][ldp]: the final distribution (parity tap)
     int V, top_k;
     float temperature, top_p, rep_penalty;
+    // sampled verify pass only (sample_row_kernel<true>): row r = i * ext_S + j is position j of sequence i and sees the
+    // history  base_i ++ ext[i * ext_S + 1 .. + j]  (the pass's own token rows: tokens[i][0] already ends base_i)
+    const int32_t* ext; int ext_S;        // [rows] token rows of the pass, 1 + k per sequence
+    const int32_t* hist_row;              // optional [rows / ext_S]: sequence i's base history is history hist_row[i], not i
+    const nvl_sampling_params* params;    // optional device copy of the four parameters, read instead of the fields above
+                                          // (a captured pass must not bake them in)
 };
 
 constexpr int SAMPLE_THREADS = 1024, SAMPLE_WAVES = SAMPLE_THREADS / 64;
@@ -137,8 +143,17 @@ __device__ __forceinline__ void sample_for_each(float* w, int V, F4 f4, F1 f1) {
     for (int j = (V4 << 2) + threadIdx.x; j < V; j += SAMPLE_THREADS) w[j] = f1(w[j]);
 }
 
+// EXT: the history extension of a sampled verify pass (SampleArgs::ext).  The counts are taken over the concatenation, so
+// everything after them sees what nvl_sample sees when it is given the concatenated history explicitly.
+template <bool EXT>
 __global__ __launch_bounds__(SAMPLE_THREADS) void sample_row_kernel(SampleArgs a) {
     __shared__ SampleShared sh;
+    if constexpr (EXT) {
+        if (a.params) {
+            const nvl_sampling_params sp = *a.params;
+            a.top_k = sp.top_k; a.temperature = sp.temperature; a.top_p = sp.top_p; a.rep_penalty = sp.repetition_penalty;
+        }
+    }
     const int row = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int V = a.V;
     const float* lg = a.logits + (int64_t)row * a.ld;
@@ -156,16 +171,22 @@ __global__ __launch_bounds__(SAMPLE_THREADS) void sample_row_kernel(SampleArgs a
 #pragma unroll 8
         for (int j = tid; j < V; j += SAMPLE_THREADS) w[j] = lg[j];
     }
-    const int64_t h0 = a.hist_off ? (int64_t)a.hist_off[row] : (int64_t)row * a.hist_stride;
-    const int hn = a.hist_off ? a.hist_off[row + 1] - a.hist_off[row] : a.hist_len[row];
+    // history `hi` is the row's base (hb tokens); hn tokens in all, the last `nx` of them from the pass's token rows
+    const int hi = EXT ? (a.hist_row ? a.hist_row[row / a.ext_S] : row / a.ext_S) : row;
+    const int nx = EXT ? row % a.ext_S : 0;
+    const int32_t* ext = EXT ? a.ext + (int64_t)(row / a.ext_S) * a.ext_S + 1 : nullptr;
+    const int64_t h0 = a.hist_off ? (int64_t)a.hist_off[hi] : (int64_t)hi * a.hist_stride;
+    const int hb = a.hist_off ? a.hist_off[hi + 1] - a.hist_off[hi] : a.hist_len[hi];
+    const int hn = hb + nx;
+    auto token = [&](int i) { return (!EXT || i < hb) ? a.hist[h0 + i] : ext[i - hb]; };
     if (a.rep_penalty != 1.0f && hn > 0) {
         for (int i = tid; i < hn; i += SAMPLE_THREADS) {
-            const int t = a.hist[h0 + i];
+            const int t = token(i);
             if (t >= 0 && t < V) atomicAdd(&cnt[t], i >= hn - 10 ? 3 : 1);
         }
         __syncthreads();
         for (int i = tid; i < hn; i += SAMPLE_THREADS) {
-            const int t = a.hist[h0 + i];
+            const int t = token(i);
             if (t < 0 || t >= V) continue;
             const int c = atomicExch(&cnt[t], 0);          // exactly one thread per distinct token sees the count
             if (c > 0) {

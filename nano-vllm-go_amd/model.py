@@ -372,6 +372,82 @@ class HipTransformerModel:
                                                   _ptr(lens), _ptr(out), _ptr(passes)), self.h)
         return out, int(passes[0])
 
+    # -- sampled speculative decoding -----------------------------------------------------------------
+    @staticmethod
+    def _sampled_args(who, n, rows, k, histories, uniforms, u_shape):
+        """token rows [n, 1+k] (or first tokens [n]), histories and draws of a sampled call; mismatches raise ValueError
+        before any library call"""
+        from .ops import _histories
+        if not 0 <= int(k) <= 7:
+            raise ValueError(f"{who}: k must be in [0, 7]")
+        if n <= 0:
+            raise ValueError(f"{who}: no sequences")
+        toks = np.ascontiguousarray(rows, dtype=np.int32)
+        if histories is None or len(histories) != n:
+            raise ValueError(f"{who}: {0 if histories is None else len(histories)} histories for {n} sequences")
+        if any(h is None or len(h) == 0 for h in histories):
+            raise ValueError(f"{who}: every sequence needs its history (ending with its first token)")
+        u = np.ascontiguousarray(uniforms, dtype=np.float32)
+        want = (n, 1 + k) if u_shape is None else u_shape
+        if u.size != want[0] * want[1]:
+            raise ValueError(f"{who}: {u.size} uniforms, expected {want[0]} x {want[1]}")
+        ptrs, lens, keep = _histories(histories, n)
+        return toks, u.reshape(want), ptrs, lens, keep
+
+    def verify_sampled(self, seq_ids, token_rows, k: int, histories, uniforms, *, temperature=1.0, top_p=1.0, top_k=0,
+                       repetition_penalty=1.2):
+        """nvl_verify_sampled: verify_greedy under SampleWithHistory.  histories[i] = the sequence's ids as row 0 sees them
+        (ending with token_rows[i][0]); uniforms [n_seqs, 1+k], row j being the draw of the sequence's decode step j.
+        -> (n_accepted [n_seqs], out_tokens [n_seqs, 1+k]: the sampled ids 0..a_i, the rest -1)."""
+        n = len(seq_ids)
+        toks, u, ptrs, lens, keep = self._sampled_args("verify_sampled", n, token_rows, k, histories, uniforms, None)
+        if toks.size != n * (1 + k):
+            raise ValueError(f"verify_sampled: {toks.size} tokens for {n} x {1 + k} rows")
+        ids = np.ascontiguousarray(seq_ids, dtype=np.int64)
+        acc = np.empty(n, np.int32)
+        out = np.empty((n, 1 + k), np.int32)
+        sp = L.sampling_params(temperature, top_p, top_k, repetition_penalty)
+        L.check(self.lib.nvl_verify_sampled(self.h, n, _ptr(ids), _ptr(toks), int(k), C.byref(sp), ptrs, _ptr(lens), _ptr(u),
+                                            _ptr(acc), _ptr(out)), self.h)
+        return acc, out
+
+    def verify_sampled_paged(self, token_rows, k: int, pos_offsets, block_tables, histories, uniforms, *, temperature=1.0,
+                             top_p=1.0, top_k=0, repetition_penalty=1.2):
+        """nvl_verify_sampled_paged: verify_sampled over the sequences' block tables; the caller advances by a_i + 1."""
+        n = len(pos_offsets)
+        if len(block_tables) != n:
+            raise ValueError("verify_sampled_paged: pos_offsets and block_tables differ in length")
+        toks, u, ptrs, lens, keep = self._sampled_args("verify_sampled_paged", n, token_rows, k, histories, uniforms, None)
+        if toks.size != n * (1 + k):
+            raise ValueError(f"verify_sampled_paged: {toks.size} tokens for {n} x {1 + k} rows")
+        pos = np.ascontiguousarray(pos_offsets, dtype=np.int32)
+        tbl = np.concatenate([np.asarray(b, np.int32) for b in block_tables]).astype(np.int32)
+        off = np.concatenate([[0], np.cumsum([len(b) for b in block_tables])]).astype(np.int32)
+        acc = np.empty(n, np.int32)
+        out = np.empty((n, 1 + k), np.int32)
+        sp = L.sampling_params(temperature, top_p, top_k, repetition_penalty)
+        L.check(self.lib.nvl_verify_sampled_paged(self.h, n, _ptr(toks), int(k), _ptr(pos), _ptr(tbl), _ptr(off), C.byref(sp),
+                                                  ptrs, _ptr(lens), _ptr(u), _ptr(acc), _ptr(out)), self.h)
+        return acc, out
+
+    def sampled_lookup(self, seq_ids, first_tokens, n_steps: int, histories, uniforms, k: int = 3, ngram: int = 3, *,
+                       temperature=1.0, top_p=1.0, top_k=0, repetition_penalty=1.2):
+        """nvl_decode_sampled_lookup: decode_sampled's result [n_steps, n_seqs] from prompt-lookup drafts + sampled verify
+        passes; uniforms [n_steps, n_seqs], step t of sequence i always using uniforms[t][i].  -> (out_tokens, passes)."""
+        n = len(seq_ids)
+        if int(n_steps) <= 0:
+            raise ValueError("sampled_lookup: n_steps must be positive")
+        first, u, ptrs, lens, keep = self._sampled_args("sampled_lookup", n, first_tokens, k, histories, uniforms, (int(n_steps), n))
+        if first.size != n:
+            raise ValueError(f"sampled_lookup: {first.size} first tokens for {n} sequences")
+        ids = np.ascontiguousarray(seq_ids, dtype=np.int64)
+        out = np.empty((n_steps, n), dtype=np.int32)
+        passes = np.zeros(1, np.int32)
+        sp = L.sampling_params(temperature, top_p, top_k, repetition_penalty)
+        L.check(self.lib.nvl_decode_sampled_lookup(self.h, n, _ptr(ids), _ptr(first), int(n_steps), int(k), int(ngram), C.byref(sp),
+                                                   ptrs, _ptr(lens), _ptr(u), _ptr(out), _ptr(passes)), self.h)
+        return out, int(passes[0])
+
     def greedy_fused(self, prompt, max_tokens: int, seq_id: int = 0):
         """greedy() with the whole decode loop in one nvl_decode_greedy call."""
         self.seq_reset(seq_id)

@@ -241,3 +241,31 @@ def sample_with_history(logits, histories, uniforms, *, temperature=1.0, top_p=1
     sp = L.sampling_params(temperature, top_p, top_k, repetition_penalty)
     L.check(L.lib().nvl_op_sample(device, _p(lg), rows, V, C.byref(sp), ptrs, _p(lens), _p(u), _p(out), _p(probs)))
     return (out, probs) if return_probs else out
+
+
+def sample_drafts(logits, token_rows, k, histories, uniforms, *, temperature=1.0, top_p=1.0, top_k=0, repetition_penalty=1.2,
+                  return_probs=False, device=0):
+    """nvl_op_sample_drafts: the sampler of a sampled verify pass + its accept kernel on host logits [n_seqs * (1+k), V].
+    token_rows [n_seqs, 1+k]; histories[i] ends with token_rows[i][0]; uniforms [n_seqs, 1+k].
+    -> (sampled [n_seqs, 1+k], n_accepted [n_seqs], out_tokens [n_seqs, 1+k][, probs [n_seqs * (1+k), V]])."""
+    lg = _f(logits)
+    k = int(k)
+    if lg.ndim != 2 or not 0 <= k <= 7 or lg.shape[0] % (1 + k):
+        raise ValueError("sample_drafts: logits must be [n_seqs * (1+k), V] with k in [0, 7]")
+    M, V = lg.shape
+    n = M // (1 + k)
+    toks = np.ascontiguousarray(token_rows, dtype=np.int32)
+    if toks.size != M:
+        raise ValueError(f"sample_drafts: {toks.size} tokens for {M} rows")
+    if histories is None or len(histories) != n or any(h is None or len(h) == 0 for h in histories):
+        raise ValueError(f"sample_drafts: {n} sequences need {n} non-empty histories")
+    u = _f(uniforms)
+    if u.size != M:
+        raise ValueError(f"sample_drafts: {u.size} uniforms for {M} rows")
+    ptrs, lens, keep = _histories(histories, n)
+    sampled, acc, out = np.empty((n, 1 + k), np.int32), np.empty(n, np.int32), np.empty((n, 1 + k), np.int32)
+    probs = np.empty((M, V), np.float32) if return_probs else None
+    sp = L.sampling_params(temperature, top_p, top_k, repetition_penalty)
+    L.check(L.lib().nvl_op_sample_drafts(device, _p(lg), n, k, V, C.byref(sp), _p(toks), ptrs, _p(lens), _p(u), _p(sampled),
+                                         _p(acc), _p(out), _p(probs)))
+    return (sampled, acc, out, probs) if return_probs else (sampled, acc, out)

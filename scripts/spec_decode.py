@@ -9,7 +9,18 @@ Random weights have no real-text acceptance rate, so the generation rate is repo
 always right (the ids of a plain greedy run) and drafts that are always wrong.  Acceptance on real checkpoints: not measured.
 bench.py's seeded weights (gen_weights_on_device) are reused; bench.py itself is not changed or run.
 
-    python scripts/spec_decode.py [--batches 1,8] [--ks 1,3,7] [--ctx 512] [--gen 64] [--passes 32] [--reps 5]"""
+    python scripts/spec_decode.py [--batches 1,8] [--ks 1,3,7] [--ctx 512] [--gen 64] [--passes 32] [--reps 5]
+
+--sampled: the same shapes under tensor.SampleWithHistory, for the default sampling parameters and for
+temperature 0.8 / top_k 40 / top_p 0.95, timed alternately in one process:
+  (a) one nvl_verify_sampled pass (forward of 1 + k rows, sampler with the history extension, accept kernel; replayed graph)
+  (c) the host route it replaces: nvl_forward of 1 + k rows, nvl_sample with the 1 + k hand-extended histories of every
+      sequence, the compare on the host, nvl_seq_truncate
+next to one step of nvl_decode_sampled.  Two figures per route: wall clock per pass with the device idle before and after
+(what a host loop pays, synchronisations included), and the library's own HIP-event time of the forward passes
+(nvl_stats; it covers (a) whole — its sampler and accept kernel lie inside the events — and of (c) only the nvl_forward).
+
+    python scripts/spec_decode.py --sampled --ks 3"""
 import argparse
 import importlib
 import importlib.util
@@ -39,6 +50,7 @@ def main():
     ap.add_argument("--gen", type=int, default=64)
     ap.add_argument("--passes", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
+    ap.add_argument("--sampled", action="store_true")
     args = ap.parse_args()
     import torch
     pkg = importlib.import_module("nano-vllm-go_amd")
@@ -61,6 +73,11 @@ def main():
         fn()
         torch.cuda.synchronize()
         return time.perf_counter() - t0
+
+    if args.sampled:
+        sampled_mode(args, pkg, model, prompts, batches, ks, clock)
+        model.close()
+        return
 
     for B in batches:
         ids = list(range(B))
@@ -154,6 +171,78 @@ def main():
                       f"{res[0][1]} passes, always wrong {res[1][0]:9.1f} tok/s in {res[1][1]} passes "
                       f"(plain greedy: {B / statistics.median(plain) * 1e3:9.1f} tok/s)", flush=True)
     model.close()
+
+
+def sampled_mode(args, pkg, model, prompts, batches, ks, clock):
+    V, S, G = model.cfg["vocab_size"], args.ctx, args.gen
+    r = np.random.default_rng(1)
+
+    def device_ms():
+        st = model.stats()
+        return st["decode_ms"] + st["prefill_ms"]
+
+    for B in batches:
+        ids = list(range(B))
+        for i in ids:
+            model.seq_reset(i)
+        _, first = model.forward_batch(ids, [prompts[i] for i in ids], [0] * B, want_logits=False)
+        first = first.copy()
+        hists = [prompts[i].tolist() + [int(first[i])] for i in ids]
+
+        def rewind():
+            for i in ids:
+                model.seq_truncate(i, S)
+
+        for name, kw in (("default", {}), ("T0.8 k40 p0.95", dict(temperature=0.8, top_k=40, top_p=0.95))):
+            U = r.random((G, B)).astype(np.float32)
+            model.decode_sampled(ids, first, G, hists, U, **kw)          # warm-up
+            plain, plain_dev = [], []
+            for _ in range(args.reps):
+                rewind()
+                d0 = device_ms()
+                plain.append(clock(lambda: model.decode_sampled(ids, first, G, hists, U, **kw)) / G * 1e3)
+                plain_dev.append((device_ms() - d0) / G)
+            print(f"B={B} ctx={S} [{name}]: plain nvl_decode_sampled {statistics.median(plain):.4f} ms/step wall "
+                  f"[{min(plain):.4f}..{max(plain):.4f}], {statistics.median(plain_dev):.4f} ms/step device "
+                  f"({args.reps} x {G} steps)", flush=True)
+            for k in ks:
+                rows = np.concatenate([first[:, None], r.integers(0, V, (B, k))], axis=1).astype(np.int32)
+                u = r.random((B, 1 + k)).astype(np.float32)
+                ext = [h + rows[i, 1:j + 1].tolist() for i, h in enumerate(hists) for j in range(1 + k)]
+                got = {}
+
+                def fused():
+                    got["a"] = model.verify_sampled(ids, rows, k, hists, u, **kw)[0]
+
+                def host():
+                    model.forward_batch(ids, list(rows), [S] * B, all_logits=True, want_logits=False)
+                    s = model.sample(ext, u.reshape(-1), **kw).reshape(B, 1 + k)
+                    acc = np.zeros(B, np.int32)
+                    for i in range(B):
+                        while acc[i] < k and rows[i, acc[i] + 1] == s[i, acc[i]]:
+                            acc[i] += 1
+                        model.seq_truncate(i, S + int(acc[i]) + 1)
+                    got["c"] = acc
+
+                routes = {"a nvl_verify_sampled": fused, "c forward+sample+host": host}
+                wall = {n: [] for n in routes}
+                dev = {n: [] for n in routes}
+                for rep_i in range(args.reps + 1):            # rep 0: warm-up of every route (first sight, graph capture)
+                    for n, fn in routes.items():
+                        def many():
+                            for _ in range(args.passes):
+                                fn()
+                                rewind()
+                        rewind()
+                        d0 = device_ms()
+                        t = clock(many) / args.passes * 1e3
+                        if rep_i:
+                            wall[n].append(t)
+                            dev[n].append((device_ms() - d0) / args.passes)
+                line = "  ".join(f"({n}) wall {statistics.median(wall[n]):.4f} [{min(wall[n]):.4f}..{max(wall[n]):.4f}] "
+                                 f"device {statistics.median(dev[n]):.4f}" for n in routes)
+                print(f"B={B} k={k} [{name}]: ms per pass, median [min..max] of {args.reps} x {args.passes}: {line} | "
+                      f"accepted (random drafts): a {got['a'].tolist()} c {got['c'].tolist()}", flush=True)
 
 
 if __name__ == "__main__":
