@@ -521,6 +521,65 @@ int nvl_verify_sampled_paged(nvl_model* m, int n_seqs, const int32_t* tokens, in
 int nvl_decode_sampled_lookup(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
                               int k, int ngram, const nvl_sampling_params* params, const int32_t* const* history_ptrs,
                               const int32_t* history_lens, const float* uniforms, int32_t* out_tokens, int32_t* passes_out);
+/* ---- speculative decoding with a draft MODEL ----
+ * The reference draws one token per step from SampleWithHistory (sampling.go:33-102, tensor_model_runner.go:89-93).  With
+ * proposals x ~ q from a second, smaller model the law of every emitted token stays the target's filtered distribution p
+ * under the rejection rule: accept x with probability min(1, p(x) / q(x)), otherwise draw from norm(max(0, p - q)).  Both
+ * steps run on the device over V-wide rows (csrc/spec.h): no distribution crosses PCIe.  The draws differ in meaning from the
+ * sequential sampler's (an accept test is no multinomial draw), so the Go host's math/rand stream cannot be preserved here:
+ * the emitted ids are a sample of the same law, not the ids rand.Float32() would have produced.
+ *
+ * nvl_draft_sampled: nvl_decode_sampled on the draft model with n_steps = k (1..7) - the same validation, the same ids bit
+ * for bit, out_tokens [k][n_seqs], uniforms [k][n_seqs] - which also keeps every step's final distribution q_j (after
+ * penalty, temperature, top-k, top-p and the renormalisation, sampling.go:33-102) on the device: k x n_seqs x
+ * round_up(V, 4) floats, allocated on first use, freed by nvl_destroy.  The model records n_seqs, k, the sequence ids in
+ * order and the sampled ids; any later forward-type call on it (nvl_forward*, nvl_decode_*, nvl_verify_*, nvl_score*,
+ * nvl_runner_run*) invalidates them.  bf16 slab models only (nvl_decode_sampled's rule); a Mamba2 model is refused with
+ * NVL_ERR_STATE (its state cannot be rolled back).  Synchronises before returning. */
+int nvl_draft_sampled(nvl_model* draft, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int k,
+                      const nvl_sampling_params* params, const int32_t* const* history_ptrs, const int32_t* history_lens,
+                      const float* uniforms, int32_t* out_tokens);
+/* The verify pass of that scheme (sampling.go:33-102 per row, tensor_model_runner.go:89-93).  tokens [n_seqs][1+k]:
+ * tokens[i][0] the next input token, tokens[i][j+1] = d_j the id the draft sampled at step j (checked against the kept
+ * proposals).  The target runs nvl_verify_sampled's pass: 1 + k rows, the sampler with the history extension, so p_j, row
+ * j's final distribution, sees history ++ tokens[i][1..j]; histories as nvl_verify_sampled.  accept_uniforms [n_seqs][k],
+ * final_uniforms [n_seqs], all in [0, 1].  Row j is accepted iff  accept_uniforms[i][j] * q_j(d_j) < p_j(d_j), product and
+ * compare in fp32 as written (q_j(d_j) == 0 accepts iff p_j(d_j) > 0); a_i = the number of leading accepted rows.
+ * a_i < k: the emitted id e is the first index whose running sum of r = max(p_a - q_a, 0) reaches final_uniforms[i] * sum(r)
+ * (the sampler's multinomial scan, fallback V - 1; p_a itself should rounding leave sum(r) == 0).  a_i == k: e is that scan
+ * of p_k - bit for bit what the sampler draws for row k with that uniform.  n_accepted_out [n_seqs] = a_i; out_tokens
+ * [n_seqs][1+k] = d_0 .. d_{a_i - 1}, e, then -1 (nvl_verify_greedy's layout); accept_prob_out (may be NULL) [n_seqs][k][2] =
+ * {p_j(d_j), q_j(d_j)} of every row, so a host can replay each decision.  Afterwards the target's cached length is
+ * P_i + a_i + 1 and its n_seqs x (1+k) logits rows are the last forward group; the draft's cache is not touched (the
+ * caller truncates it: nvl_seq_truncate).  f32 and bf16 targets, every weight and KV mode nvl_verify_sampled serves, key 38
+ * as there; the pass is launched eagerly (no graph replay).
+ * Refusals: nvl_verify_sampled's on the target; NVL_ERR_INVALID for draft == target (or a NULL model: no message is kept),
+ * different devices, different vocab_size, a tokens[i][j+1] that is not the draft's id of step j, n_seqs / k / sequence
+ * ids other than those of the kept proposals; NVL_ERR_STATE when the draft holds no valid proposals.  The message is kept
+ * on the target.  A refused call changes no length on either model. */
+int nvl_verify_speculative(nvl_model* target, nvl_model* draft, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, int k,
+                           const nvl_sampling_params* params, const int32_t* const* history_ptrs, const int32_t* history_lens,
+                           const float* accept_uniforms, const float* final_uniforms, int32_t* n_accepted_out,
+                           int32_t* out_tokens, float* accept_prob_out);
+/* nvl_decode_sampled's contract (sampling.go:33-102 per step, tensor_model_runner.go:89-93; out_tokens [n_steps][n_seqs])
+ * from draft phases + speculative verify passes; both models end at the cached length P_i + n_steps and must hold every
+ * sequence at the same cached length on entry (NVL_ERR_INVALID otherwise).  Pass scheduling as nvl_decode_sampled_lookup: the
+ * sequences that still need tokens, k shrunk to the shortest remainder and to max_seq_len (of either model, the draft's
+ * extra step and its history counted), overshoot cut,
+ * a last pass of one row = a plain sampled step of the target.  uniforms [n_steps][n_seqs][2k+1]: pass t (there are at most
+ * n_steps) gives sequence i its draft draws [0..k), its accept draws [k..2k) and its final draw [2k]; a pass of k' < k
+ * drafts uses the first k' of each group.  Every pass the draft samples one step more than it proposes (that id is
+ * discarded, its draw is 0): the step caches the row of the last proposal, so after any outcome the draft is rolled back
+ * by truncation to the target's new length alone.  Histories (required, as nvl_decode_sampled_lookup) are restaged from
+ * the host every pass.  passes_out and accepted_out [n_seqs] (the accepted drafts per sequence in total) may be NULL.  The
+ * draft must be a bf16 slab model without Mamba2 layers (NVL_ERR_STATE); other refusals as nvl_verify_speculative.  Everything
+ * that depends on the arguments is checked before the first pass; should a pass fail later (a HIP error), that pass is
+ * undone on the draft (truncated to the target's length) while earlier passes stay: both models then hold the same lengths,
+ * seq_len(target) - P_i ids of out_tokens' column i are valid. */
+int nvl_decode_speculative(nvl_model* target, nvl_model* draft, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens,
+                           int n_steps, int k, const nvl_sampling_params* params, const int32_t* const* history_ptrs,
+                           const int32_t* history_lens, const float* uniforms, int32_t* out_tokens, int32_t* passes_out,
+                           int32_t* accepted_out);
 /* TensorModelRunner.Run including its sampling step (tensor_model_runner.go:55-97): nvl_runner_run, then
  * SampleWithHistory(lastTokenLogits, seq.TokenIDs, defaultSampling) per sequence on the device. */
 int nvl_runner_run_sampled(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* const* token_ptrs,
@@ -674,6 +733,12 @@ int nvl_op_sample_drafts(int device, const float* logits, int n_seqs, int k, int
                          const int32_t* tokens, const int32_t* const* history_ptrs, const int32_t* history_lens,
                          const float* uniforms, int32_t* sampled_out, int32_t* n_accepted_out, int32_t* out_tokens,
                          float* probs_out);
+/* The rejection kernel of nvl_verify_speculative (the rule stated there; sampling.go:33-102 gives p and q their meaning,
+ * tensor_model_runner.go:89-93 the step it replaces) on host distributions: p [n_seqs][1+k][V], q [n_seqs][k][V], rows
+ * padded to round_up(V, 4) on upload; tokens [n_seqs][1+k] (column 0 unused), k in 1..7.  accept_prob_out may be NULL. */
+int nvl_op_spec_reject(int device, const float* p, const float* q, const int32_t* tokens, int n_seqs, int k, int V,
+                       const float* accept_uniforms, const float* final_uniforms, int32_t* n_accepted_out,
+                       int32_t* out_tokens, float* accept_prob_out);
 /* The log-probability kernels (nvl_logprobs; generic_model.go:467-470 rows, cmd/check-logits/main.go's view of them) on
  * host logits [rows][ld], V valid columns (ld >= V: the pad columns travel too and are never used), divided by
  * logits_scaling first when it is not 0 (generic_model.go:473-477). */

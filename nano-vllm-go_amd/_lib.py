@@ -216,6 +216,10 @@ def lib():
     L.nvl_verify_sampled_paged.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, sp, vp, vp, vp, vp, vp]
     L.nvl_decode_sampled_lookup.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, sp, vp, vp, vp, vp, vp]
     L.nvl_op_sample_drafts.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, sp, vp, vp, vp, vp, vp, vp, vp, vp]
+    L.nvl_draft_sampled.argtypes = [vp, C.c_int, vp, vp, C.c_int, sp, vp, vp, vp, vp]
+    L.nvl_verify_speculative.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, sp, vp, vp, vp, vp, vp, vp, vp]
+    L.nvl_decode_speculative.argtypes = [vp, vp, C.c_int, vp, vp, C.c_int, C.c_int, sp, vp, vp, vp, vp, vp, vp]
+    L.nvl_op_spec_reject.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp, vp]
     _lib = L
     return L
 

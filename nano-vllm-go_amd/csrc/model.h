@@ -15,6 +15,7 @@
 #include "common.h"
 #include "elem.h"
 #include "sample.h"
+#include "spec.h"
 #include "logprob.h"
 #include "gemm.h"
 #include "wq.h"
@@ -53,7 +54,7 @@ enum KClass { KC_GEMM = 0, KC_ATTN = 1, KC_OTHER = 2 };
 // where in the layer a launch sits (per-kernel roofline entries of nvl_get_kernel_stats; names in nvllm.hip)
 enum KSite { KS_OTHER = 0, KS_QKV, KS_ATTN, KS_OPROJ, KS_FFN_UP, KS_FFN_DOWN, KS_LM_HEAD, KS_NORM, KS_MOE_ROUTER, KS_MOE_PLAN,
              KS_MOE_UP, KS_MOE_DOWN, KS_MOE_COMBINE, KS_EMBED, KS_ARGMAX, KS_ROPE, KS_MAMBA_IN, KS_MAMBA_CONV, KS_MAMBA_SCAN,
-             KS_MAMBA_GATE, KS_MAMBA_OUT, KS_ALLREDUCE, KS_LOGPROBS, KS_COUNT };
+             KS_MAMBA_GATE, KS_MAMBA_OUT, KS_ALLREDUCE, KS_LOGPROBS, KS_SPEC_REJECT, KS_COUNT };
 
 struct ProfRec { hipEvent_t a, b; int cls; double flops; int site, phase; double bytes; };
 struct SiteStat { double ms = 0, flops = 0, bytes = 0; uint64_t launches = 0; };
@@ -191,6 +192,12 @@ struct nvl_model {
     LogprobBufs lpb;             // nvl_logprobs / nvl_score scratch
     int32_t* samp_hist = nullptr; int32_t* samp_hist_len = nullptr; int64_t samp_hist_cap = 0;   // nvl_decode_sampled: device-kept histories
     float* samp_u_steps = nullptr; int64_t samp_u_cap = 0;
+    // nvl_draft_sampled: the final distribution of every draft step, [steps][n_seqs][round_up(V, 4)] on the
+    // device, and what it holds; any later forward pass of this model invalidates it (enqueue_forward)
+    float* draft_q = nullptr; int64_t draft_q_elems = 0;
+    bool draft_valid = false; int draft_n = 0, draft_k = 0;
+    std::vector<int64_t> draft_ids; std::vector<int32_t> draft_tok;      // sequence ids in order; sampled ids [k][n_seqs]
+    float* spec_ap = nullptr;    // a speculative verify pass's {p(d), q(d)} pairs [max_seqs][7][2] (allocated on first use)
     int last_rows = 0;           // logits rows the last forward left in `logits`
     int32_t* ring = nullptr; int64_t ring_ints = 0;   // nvl_decode_greedy: [steps][seqs] tokens on the device
     int32_t* ring_pos0 = nullptr;                     // position of every sequence when the fused loop started (ring row index)

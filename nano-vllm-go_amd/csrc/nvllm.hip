@@ -398,6 +398,7 @@ extern "C" void nvl_destroy(nvl_model* m) {
     free_sample_bufs(m->samp);
     free_logprob_bufs(m->lpb);
     dfree(m->samp_hist); dfree(m->samp_hist_len); dfree(m->samp_u_steps);
+    dfree(m->draft_q); dfree(m->spec_ap);
     if (m->tp_comm) (void)ncclCommDestroy((ncclComm_t)m->tp_comm);
     if (m->tp_local) {
         bool last;
@@ -2047,6 +2048,7 @@ namespace {
 // of a key runs eagerly (it also sets the per-function attributes, which must not happen during capture).
 template <typename F>
 bool replay_or_capture(nvl_model* m, const std::array<int, 5>& key, F&& enqueue) {
+    m->draft_valid = false;      // a replayed pass never reaches enqueue_forward: the kept proposals of nvl_draft_sampled end here too
     // (tensor parallel: only with the P2P all-reduce, whose call state lives on the device; RCCL / the in-process emulation
     //  are host-driven)
     if (!g_use_graphs || !m->graphs_ok || m->profile || m->keep_hidden || m->tap || m->stamping || ((m->tp > 1 || m->tp_force) && !m->p2p_ready)) return false;
@@ -2105,6 +2107,7 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
     const nvl_model_config& c = m->cfg;
     const int H = m->H;
     m->kv_written = true;                  // (nvl_set_kv_scales is refused from here on)
+    m->draft_valid = false;                // (the kept proposals of nvl_draft_sampled describe the pass before this one)
     m->pending_slices = 0;
     m->phase = max_len > 1 ? 0 : 1;         // per-site profile: prefill / decode
     if ((m->keep_hidden || m->tap) && m->hidden_tokens < M) {
@@ -2710,9 +2713,10 @@ namespace {
 // every later step's tokens / positions are produced on the device
 // `sp` != NULL: every step samples (tensor.SampleWithHistory, sample.h) instead of taking the argmax; the histories live
 // on the device (m->samp_hist, one row of max_seq_len ids per sequence) and grow by the sampled token each step;
-// `uniforms_dev` is [n_steps][n_seqs]
+// `uniforms_dev` is [n_steps][n_seqs]; `keep` (nvl_draft_sampled, or NULL) receives every step's final distribution,
+// [n_steps][n_seqs][round_up(V, 4)]
 void decode_loop(nvl_model* m, const Meta& hm, int n_seqs, int n_steps, int32_t* out_tokens,
-                 const nvl_sampling_params* sp = nullptr, const float* uniforms_dev = nullptr) {
+                 const nvl_sampling_params* sp = nullptr, const float* uniforms_dev = nullptr, float* keep = nullptr) {
     const int M = n_seqs;
     const int32_t* h_pos = hm.seq_pos;
     const Meta md = bind_meta(m, m->meta_dev, M);
@@ -2746,6 +2750,7 @@ void decode_loop(nvl_model* m, const Meta& hm, int n_seqs, int n_steps, int32_t*
             a.logits = m->logits; a.ld = m->Vpad; a.work = m->samp.work; a.cnt = m->samp.cnt; a.hist = m->samp_hist;
             a.hist_off = nullptr; a.hist_stride = m->cfg.max_seq_len; a.hist_len = m->samp_hist_len;
             a.uniforms = uniforms_dev + (int64_t)s * n_seqs; a.out = m->samp.out; a.probs_out = nullptr; a.ldp = m->V;
+            if (keep) { a.ldp = round_up(m->V, 4); a.probs_out = keep + (int64_t)s * n_seqs * a.ldp; }
             a.V = m->V; a.top_k = sp->top_k; a.temperature = sp->temperature; a.top_p = sp->top_p; a.rep_penalty = sp->repetition_penalty;
             hipLaunchKernelGGL(sample_row_kernel<false>, dim3(n_seqs), dim3(SAMPLE_THREADS), 0, m->stream, a);
             NVL_HIP(hipGetLastError());
@@ -2940,7 +2945,9 @@ VsBlock bind_vs(int32_t* base, int n_seqs) {
 static_assert(sizeof(nvl_sampling_params) == 16, "bind_vs layout");
 // `append`: the accept kernel also appends the emitted ids to the device histories (the loop); the histories themselves are
 // rows of m->samp_hist with lengths m->samp_hist_len in either case.
-struct SampledPass { bool append; };
+// `spec` (nvl_verify_speculative): the draft's kept distributions; spec_reject_kernel (spec.h) takes the accept kernel's place.
+struct SpecReq { const float* q; int64_t ldq, q_seq, q_step; float* accept_prob_out; };
+struct SampledPass { bool append; const SpecReq* spec = nullptr; };
 
 // the sampler's scratch for `rows` rows; a captured sampled pass holds these addresses
 void reserve_sample_rows(nvl_model* m, int rows) {
@@ -3000,6 +3007,14 @@ void verify_pass(nvl_model* m, int n_seqs, int k, const int32_t* h_pos, int32_t*
             a.ext = md.tokens; a.ext_S = S; a.hist_row = vs.hist_row; a.params = vs.params;
             hipLaunchKernelGGL(sample_row_kernel<true>, dim3(M), dim3(SAMPLE_THREADS), 0, m->stream, a);
             NVL_HIP(hipGetLastError());
+            if (sp->spec) {     // the sampler left row r's final distribution in work row r; its ids of the pass are not used
+                SpecArgs r{};
+                r.p = m->samp.work; r.ldp = round_up(m->V, 4); r.q = sp->spec->q; r.ldq = sp->spec->ldq; r.q_seq = sp->spec->q_seq;
+                r.q_step = sp->spec->q_step; r.tokens = md.tokens; r.u = vs.u; r.res = m->verify_dev; r.accept_prob = m->spec_ap;
+                r.k = k; r.V = m->V;
+                KScope ks(m, KC_OTHER, 0, KS_SPEC_REJECT, (double)n_seqs * m->V * 8.0);
+                hipLaunchKernelGGL(spec_reject_kernel, dim3(n_seqs), dim3(SAMPLE_THREADS), 0, m->stream, r);
+            } else
             hipLaunchKernelGGL(verify_accept_sampled_kernel, dim3(cdiv(n_seqs, 64)), dim3(64), 0, m->stream, (const int32_t*)m->samp.out,
                                (const int32_t*)md.tokens, k, n_seqs, m->verify_dev, sp->append ? m->samp_hist : (int32_t*)nullptr,
                                (int64_t)m->cfg.max_seq_len, m->samp_hist_len, (const int32_t*)vs.hist_row, (const int32_t*)vs.keep);
@@ -3009,9 +3024,11 @@ void verify_pass(nvl_model* m, int n_seqs, int k, const int32_t* h_pos, int32_t*
         }
         NVL_HIP(hipGetLastError());
         NVL_HIP(hipMemcpyAsync(m->verify_host, m->verify_dev, (size_t)nres * 4, hipMemcpyDeviceToHost, m->stream));
+        if (sp && sp->spec && sp->spec->accept_prob_out)      // (a speculative pass is never captured: the host address is not baked in)
+            NVL_HIP(hipMemcpyAsync(sp->spec->accept_prob_out, m->spec_ap, (size_t)n_seqs * k * 2 * 4, hipMemcpyDeviceToHost, m->stream));
     };
     bool replayed = false;
-    if (M <= 64 && M <= m->logit_rows) {
+    if (M <= 64 && M <= m->logit_rows && !(sp && sp->spec)) {      // (a speculative pass runs eagerly: it reads another model's buffer)
         const int acfg = mq ? decode_attn_cfg(m, n_seqs, S) : (S == 1 ? decode_attn_waves(m, n_seqs) : 0);
         const std::array<int, 5> key{sp ? 4 : 3, n_seqs, acfg, k | (mq ? 256 : 0) | (sp && sp->append ? 512 : 0), g_tune_epoch};
         replayed = replay_or_capture(m, key, pass);
@@ -3089,7 +3106,8 @@ void sampled_stage_pass(nvl_model* m, int n_seqs, int k, const SampledReq& rq) {
 // rq != NULL: nvl_verify_sampled — checked here, after everything else, and staged; sp != NULL alone: a pass of
 // nvl_decode_sampled_lookup, which has staged its histories and filled the block itself.
 int verify_slab(nvl_model* m, const char* who, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, int k, int k_min,
-                int32_t* n_acc_out, int32_t* out_tokens, const int* keep, const SampledReq* rq = nullptr, const SampledPass* sp = nullptr) {
+                int32_t* n_acc_out, int32_t* out_tokens, const int* keep, const SampledReq* rq = nullptr, const SampledPass* sp = nullptr,
+                const SpecReq* spec = nullptr) {
     const int rc = verify_refusals(m, who, n_seqs, k, k_min);
     if (rc) return rc;
     if (m->paged) return fail(m, NVL_ERR_STATE, std::string(who) + ": the model is in paged-KV mode (use nvl_verify_greedy_paged)");
@@ -3110,9 +3128,10 @@ int verify_slab(nvl_model* m, const char* who, int n_seqs, const int64_t* seq_id
         }
         hm.last_rows[i] = i * S + S - 1;
     }
-    const SampledPass single{false};
+    const SampledPass single{false, spec};
     if (rq) {
         if (const char* why = sampled_check(*rq, n_seqs, tokens, S, k, m->cfg.max_seq_len, (int64_t)M)) return fail(m, NVL_ERR_INVALID, std::string(who) + ": " + why);
+        if (spec && !m->spec_ap) m->spec_ap = dmalloc<float>((int64_t)m->opts.max_seqs * 7 * 2);
         sampled_stage_pass(m, n_seqs, k, *rq);
         sp = &single;
     }
@@ -3396,20 +3415,22 @@ extern "C" int nvl_decode_sampled_lookup(nvl_model* m, int n_seqs, const int64_t
 // history_ptrs[i]/history_lens[i] = Sequence.TokenIDs as the first decode step sees it (prompt + the token sampled from
 // the prefill = first_tokens[i]); uniforms is [n_steps][n_seqs] (one rand.Float32() per sequence per step, in the
 // order the host's serial loop would draw them).
-extern "C" int nvl_decode_sampled(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
-                                  const nvl_sampling_params* params, const int32_t* const* history_ptrs,
-                                  const int32_t* history_lens, const float* uniforms, int32_t* out_tokens) {
+namespace {
+// `keep`: nvl_draft_sampled — every step's final distribution stays in m->draft_q and the model records what it holds
+int decode_sampled_impl(nvl_model* m, const std::string& who, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
+                        const nvl_sampling_params* params, const int32_t* const* history_ptrs,
+                        const int32_t* history_lens, const float* uniforms, int32_t* out_tokens, bool keep) {
     if (!m) return NVL_ERR_INVALID;
-    if (!m->finalized) return fail(m, NVL_ERR_STATE, "nvl_decode_sampled: model not finalized");
-    if (m->paged) return fail(m, NVL_ERR_STATE, "nvl_decode_sampled: not available in paged-KV mode");
-    if (m->f32) return fail(m, NVL_ERR_STATE, "nvl_decode_sampled: bf16 models only");
+    if (!m->finalized) return fail(m, NVL_ERR_STATE, who + ": model not finalized");
+    if (m->paged) return fail(m, NVL_ERR_STATE, who + ": not available in paged-KV mode");
+    if (m->f32) return fail(m, NVL_ERR_STATE, who + ": bf16 models only");
     if (n_seqs <= 0 || n_steps <= 0 || !seq_ids || !first_tokens || !params || !history_ptrs || !history_lens || !uniforms || !out_tokens)
-        return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled: null/empty arguments");
+        return fail(m, NVL_ERR_INVALID, who + ": null/empty arguments");
     if (n_seqs > m->opts.max_seqs || n_seqs > m->opts.max_batch_tokens)
-        return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled: n_seqs exceeds max_seqs / max_batch_tokens");
+        return fail(m, NVL_ERR_INVALID, who + ": n_seqs exceeds max_seqs / max_batch_tokens");
     if (params->repetition_penalty == 0.f || !(params->repetition_penalty == params->repetition_penalty) ||
         !(params->temperature == params->temperature) || !(params->top_p == params->top_p))
-        return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled: bad sampling parameters");
+        return fail(m, NVL_ERR_INVALID, who + ": bad sampling parameters");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
     const int M = n_seqs, T = m->cfg.max_seq_len;
@@ -3418,15 +3439,15 @@ extern "C" int nvl_decode_sampled(nvl_model* m, int n_seqs, const int64_t* seq_i
     std::vector<int32_t> hist((size_t)n_seqs * T, 0), hlen((size_t)n_seqs);
     for (int i = 0; i < n_seqs; i++) {
         auto it = m->seq_slot.find(seq_ids[i]);
-        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_decode_sampled: sequence has no KV slot");
-        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled: duplicate sequence");
+        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, who + ": sequence has no KV slot");
+        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, who + ": duplicate sequence");
         const int slot = it->second, pos = m->slot_len[(size_t)slot];
-        if (pos + n_steps > T) return fail(m, NVL_ERR_POSITION, "nvl_decode_sampled: position exceeds max_seq_len");
-        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled: token id out of range");
+        if (pos + n_steps > T) return fail(m, NVL_ERR_POSITION, who + ": position exceeds max_seq_len");
+        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, who + ": token id out of range");
         const int hn = history_lens[i];
-        if (hn < 0 || hn + n_steps > T || (hn > 0 && !history_ptrs[i])) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled: history longer than max_seq_len");
+        if (hn < 0 || hn + n_steps > T || (hn > 0 && !history_ptrs[i])) return fail(m, NVL_ERR_INVALID, who + ": history longer than max_seq_len");
         for (int j = 0; j < hn; j++) {
-            if (history_ptrs[i][j] < 0) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled: negative token id in the history");
+            if (history_ptrs[i][j] < 0) return fail(m, NVL_ERR_INVALID, who + ": negative token id in the history");
             hist[(size_t)i * T + j] = history_ptrs[i][j];
         }
         hlen[(size_t)i] = hn;
@@ -3435,7 +3456,7 @@ extern "C" int nvl_decode_sampled(nvl_model* m, int n_seqs, const int64_t* seq_i
         hm.tokens[i] = first_tokens[i]; hm.tok_pos[i] = pos; hm.tok_tbl[i] = i;
     }
     for (int64_t i = 0; i < (int64_t)n_steps * n_seqs; i++)
-        if (!(uniforms[i] >= 0.f && uniforms[i] <= 1.f)) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled: uniform draw outside [0, 1]");
+        if (!(uniforms[i] >= 0.f && uniforms[i] <= 1.f)) return fail(m, NVL_ERR_INVALID, who + ": uniform draw outside [0, 1]");
     // device state of the sampler
     SampleBufs& b = m->samp;
     const int64_t elems = (int64_t)n_seqs * round_up(m->V, 4);
@@ -3463,8 +3484,208 @@ extern "C" int nvl_decode_sampled(nvl_model* m, int n_seqs, const int64_t* seq_i
     NVL_HIP(hipMemcpyAsync(m->samp_hist, hist.data(), hist.size() * 4, hipMemcpyHostToDevice, m->stream));
     NVL_HIP(hipMemcpyAsync(m->samp_hist_len, hlen.data(), hlen.size() * 4, hipMemcpyHostToDevice, m->stream));
     NVL_HIP(hipMemcpyAsync(m->samp_u_steps, uniforms, (size_t)n_steps * n_seqs * 4, hipMemcpyHostToDevice, m->stream));
-    decode_loop(m, hm, n_seqs, n_steps, out_tokens, params, m->samp_u_steps);   // (synchronises: the host vectors stay alive)
+    if (keep) {
+        const int64_t need = (int64_t)n_steps * n_seqs * round_up(m->V, 4);
+        if (need > m->draft_q_elems) {
+            NVL_HIP(hipStreamSynchronize(m->stream));
+            dfree(m->draft_q); m->draft_q = nullptr; m->draft_q_elems = 0;
+            m->draft_q = dmalloc<float>(need); m->draft_q_elems = need;
+        }
+    }
+    decode_loop(m, hm, n_seqs, n_steps, out_tokens, params, m->samp_u_steps, keep ? m->draft_q : nullptr);   // (synchronises: the host vectors stay alive)
     for (int i = 0; i < n_seqs; i++) { m->slot_len[(size_t)h_slot[(size_t)i]] += n_steps; m->slot_tick[(size_t)h_slot[(size_t)i]] = ++m->tick; }
+    if (keep) {
+        m->draft_n = n_seqs; m->draft_k = n_steps;
+        m->draft_ids.assign(seq_ids, seq_ids + n_seqs); m->draft_tok.assign(out_tokens, out_tokens + (size_t)n_steps * n_seqs);
+        m->draft_valid = true;
+    }
+    return NVL_OK;
+    NVL_CATCH(m)
+}
+}  // namespace
+
+extern "C" int nvl_decode_sampled(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
+                                  const nvl_sampling_params* params, const int32_t* const* history_ptrs,
+                                  const int32_t* history_lens, const float* uniforms, int32_t* out_tokens) {
+    return decode_sampled_impl(m, "nvl_decode_sampled", n_seqs, seq_ids, first_tokens, n_steps, params, history_ptrs, history_lens,
+                               uniforms, out_tokens, false);
+}
+
+// ---- speculative decoding with a draft MODEL ----
+// The draft phase: nvl_decode_sampled with n_steps = k whose per-step final distributions q_0 .. q_{k-1} stay on the device.
+extern "C" int nvl_draft_sampled(nvl_model* draft, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int k,
+                                 const nvl_sampling_params* params, const int32_t* const* history_ptrs,
+                                 const int32_t* history_lens, const float* uniforms, int32_t* out_tokens) {
+    if (!draft) return NVL_ERR_INVALID;
+    if (k < 1 || k > 7) return fail(draft, NVL_ERR_INVALID, "nvl_draft_sampled: k outside 1..7");
+    if (draft->n_mamba) return fail(draft, NVL_ERR_STATE, "nvl_draft_sampled: a Mamba2 state cannot be rolled back");
+    return decode_sampled_impl(draft, "nvl_draft_sampled", n_seqs, seq_ids, first_tokens, k, params, history_ptrs, history_lens,
+                               uniforms, out_tokens, true);
+}
+
+namespace {
+// the draws of a speculative pass in the pass's uniform block: accept draw j in row j's slot, the final draw in row k's
+std::vector<float> spec_merge_draws(int n_seqs, int k, const float* ua, const float* uf) {
+    std::vector<float> u((size_t)n_seqs * (1 + k));
+    for (int i = 0; i < n_seqs; i++) {
+        for (int j = 0; j < k; j++) u[(size_t)i * (1 + k) + j] = ua[(size_t)i * k + j];
+        u[(size_t)i * (1 + k) + k] = uf[i];
+    }
+    return u;
+}
+// what must hold between the two models, and between the call and the proposals the draft keeps
+int spec_pair_refusals(nvl_model* t, nvl_model* d, const char* who) {
+    if (!d->finalized) return fail(t, NVL_ERR_STATE, std::string(who) + ": draft model not finalized");
+    if (t->device != d->device) return fail(t, NVL_ERR_INVALID, std::string(who) + ": target and draft live on different devices");
+    if (t->V != d->V) return fail(t, NVL_ERR_INVALID, std::string(who) + ": target and draft differ in vocab_size");
+    return NVL_OK;
+}
+int spec_proposals_check(nvl_model* t, nvl_model* d, const char* who, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, int k,
+                         int k_kept) {
+    if (!d->draft_valid || !d->draft_q) return fail(t, NVL_ERR_STATE, std::string(who) + ": the draft holds no valid proposals (nvl_draft_sampled first)");
+    if (d->draft_n != n_seqs || d->draft_k != k_kept) return fail(t, NVL_ERR_INVALID, std::string(who) + ": n_seqs / k are not those of the kept proposals");
+    for (int i = 0; i < n_seqs; i++) {
+        if (d->draft_ids[(size_t)i] != seq_ids[i]) return fail(t, NVL_ERR_INVALID, std::string(who) + ": sequence ids are not those of the kept proposals");
+        for (int j = 0; j < k; j++)
+            if (tokens[(size_t)i * (1 + k) + j + 1] != d->draft_tok[(size_t)j * n_seqs + i])
+                return fail(t, NVL_ERR_INVALID, std::string(who) + ": a draft token is not the id the draft sampled at that step");
+    }
+    return NVL_OK;
+}
+}  // namespace
+
+extern "C" int nvl_verify_speculative(nvl_model* target, nvl_model* draft, int n_seqs, const int64_t* seq_ids, const int32_t* tokens,
+                                      int k, const nvl_sampling_params* params, const int32_t* const* history_ptrs,
+                                      const int32_t* history_lens, const float* accept_uniforms, const float* final_uniforms,
+                                      int32_t* n_accepted_out, int32_t* out_tokens, float* accept_prob_out) {
+    if (!target || !draft || target == draft) return NVL_ERR_INVALID;
+    nvl_model* m = target;
+    if (!seq_ids || !tokens || !params || !history_ptrs || !history_lens || !accept_uniforms || !final_uniforms || !n_accepted_out || !out_tokens)
+        return fail(m, NVL_ERR_INVALID, "nvl_verify_speculative: null arguments");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    int rc = verify_refusals(m, "nvl_verify_speculative", n_seqs, k, 1);
+    if (rc) return rc;
+    if ((rc = spec_pair_refusals(m, draft, "nvl_verify_speculative"))) return rc;
+    if ((rc = spec_proposals_check(m, draft, "nvl_verify_speculative", n_seqs, seq_ids, tokens, k, k))) return rc;
+    const std::vector<float> u = spec_merge_draws(n_seqs, k, accept_uniforms, final_uniforms);
+    const SampledReq rq{params, history_ptrs, history_lens, u.data()};
+    const SpecReq spec{draft->draft_q, round_up(m->V, 4), 1, n_seqs, accept_prob_out};
+    return verify_slab(m, "nvl_verify_speculative", n_seqs, seq_ids, tokens, k, 1, n_accepted_out, out_tokens, nullptr, &rq, nullptr, &spec);
+    NVL_CATCH(m)
+}
+
+// nvl_decode_sampled's contract from a draft model's proposals + speculative verify passes.  Per pass over the active
+// sequences: the draft samples k_pass + 1 steps (the last one only to cache the row of d_k, its id is discarded: then the
+// draft's cache holds every row the target may keep, and truncating it to the target's new length is all the rollback there
+// is), the target verifies 1 + k_pass rows under the rejection rule, the draft is truncated.  Histories are restaged from the
+// host on every pass.  A pass of one row (k_pass = 0) is a plain sampled step of the target.
+extern "C" int nvl_decode_speculative(nvl_model* target, nvl_model* draft, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens,
+                                      int n_steps, int k, const nvl_sampling_params* params, const int32_t* const* history_ptrs,
+                                      const int32_t* history_lens, const float* uniforms, int32_t* out_tokens, int32_t* passes_out,
+                                      int32_t* accepted_out) {
+    if (!target || !draft || target == draft) return NVL_ERR_INVALID;
+    nvl_model* m = target;
+    if (!seq_ids || !first_tokens || !params || !history_ptrs || !history_lens || !uniforms || !out_tokens || n_steps <= 0)
+        return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: null/empty arguments");
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    int rc = verify_refusals(m, "nvl_decode_speculative", n_seqs, k, 1);
+    if (rc) return rc;
+    if (m->paged) return fail(m, NVL_ERR_STATE, "nvl_decode_speculative: not available in paged-KV mode");
+    if ((rc = spec_pair_refusals(m, draft, "nvl_decode_speculative"))) return rc;
+    if (draft->paged || draft->f32) return fail(m, NVL_ERR_STATE, "nvl_decode_speculative: the draft must be a bf16 slab model");
+    if (draft->n_mamba) return fail(m, NVL_ERR_STATE, "nvl_decode_speculative: a Mamba2 draft cannot be rolled back");
+    if (n_seqs > draft->opts.max_seqs || n_seqs > draft->opts.max_batch_tokens)
+        return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: n_seqs exceeds the draft's max_seqs / max_batch_tokens");
+    const int U = 2 * k + 1;
+    std::vector<int> dslot((size_t)n_seqs), tslot((size_t)n_seqs);
+    for (int i = 0; i < n_seqs; i++) {
+        auto it = m->seq_slot.find(seq_ids[i]);
+        auto id = draft->seq_slot.find(seq_ids[i]);
+        if (it == m->seq_slot.end() || id == draft->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_decode_speculative: sequence has no KV slot on the target or the draft");
+        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: duplicate sequence");
+        tslot[(size_t)i] = it->second; dslot[(size_t)i] = id->second;
+        if (m->slot_len[(size_t)it->second] != draft->slot_len[(size_t)id->second])
+            return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: target and draft hold a sequence at different cached lengths");
+        if (m->slot_len[(size_t)it->second] + n_steps > std::min(m->cfg.max_seq_len, draft->cfg.max_seq_len))
+            return fail(m, NVL_ERR_POSITION, "nvl_decode_speculative: position exceeds max_seq_len");
+        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: token id out of range");
+        if (history_ptrs[i])       // (the ids are fed to both models)
+            for (int j = 0; j < history_lens[i]; j++)
+                if (history_ptrs[i][j] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: history id outside the vocabulary");
+    }
+    const SampledReq rq0{params, history_ptrs, history_lens, uniforms};
+    if (const char* why = sampled_check(rq0, n_seqs, first_tokens, 1, n_steps, std::min(m->cfg.max_seq_len, draft->cfg.max_seq_len),
+                                        (int64_t)n_steps * n_seqs * U))
+        return fail(m, NVL_ERR_INVALID, std::string("nvl_decode_speculative: ") + why);
+    std::vector<std::vector<int32_t>> hist((size_t)n_seqs);
+    for (int i = 0; i < n_seqs; i++) hist[(size_t)i].assign(history_ptrs[i], history_ptrs[i] + history_lens[i]);
+    std::vector<int> done((size_t)n_seqs, 0);
+    if (accepted_out) for (int i = 0; i < n_seqs; i++) accepted_out[i] = 0;
+    int passes = 0;
+    std::vector<int64_t> ids; std::vector<int> who, keep; std::vector<int32_t> toks, acc, got, first, dtok, hl; std::vector<float> du, ua, uf;
+    std::vector<const int32_t*> hp;
+    for (;;) {
+        who.clear(); ids.clear(); keep.clear();
+        int k_pass = 0, room = k;
+        for (int i = 0; i < n_seqs; i++) {
+            if (done[(size_t)i] >= n_steps) continue;
+            who.push_back(i); ids.push_back(seq_ids[i]); keep.push_back(n_steps - done[(size_t)i]);
+            k_pass = std::max(k_pass, n_steps - done[(size_t)i] - 1);
+            // the draft runs k_pass + 1 steps: k_pass + 1 more positions and k_pass + 1 more history ids must fit (the history
+            // usually holds one id more than the cache; both are >= 0 here: P + n_steps and history + n_steps fit, checked above)
+            const int T = std::min(m->cfg.max_seq_len, draft->cfg.max_seq_len);
+            room = std::min(room, T - std::max(m->slot_len[(size_t)tslot[(size_t)i]], (int)hist[(size_t)i].size()) - 1);
+        }
+        if (who.empty()) break;
+        k_pass = std::min(k_pass, room);
+        const int na = (int)who.size(), S = 1 + k_pass;
+        toks.assign((size_t)na * S, 0); acc.assign((size_t)na, 0); got.assign((size_t)na * S, -1);
+        first.resize((size_t)na); hp.resize((size_t)na); hl.resize((size_t)na);
+        dtok.assign((size_t)S * na, 0); du.assign((size_t)S * na, 0.f); ua.assign((size_t)na * std::max(k_pass, 1), 0.f); uf.resize((size_t)na);
+        for (int a = 0; a < na; a++) {
+            const int i = who[(size_t)a];
+            const float* u = uniforms + ((size_t)passes * n_seqs + i) * U;      // pass t's block of sequence i
+            first[(size_t)a] = hist[(size_t)i].back(); hp[(size_t)a] = hist[(size_t)i].data(); hl[(size_t)a] = (int32_t)hist[(size_t)i].size();
+            for (int j = 0; j < k_pass; j++) { du[(size_t)j * na + a] = u[j]; ua[(size_t)a * k_pass + j] = u[k + j]; }
+            uf[(size_t)a] = u[2 * k];
+        }
+        // the draft phase: k_pass proposals and the cached row of the last one
+        rc = decode_sampled_impl(draft, "nvl_decode_speculative (draft)", na, ids.data(), first.data(), S, params, hp.data(), hl.data(),
+                                 du.data(), dtok.data(), true);
+        if (rc) return fail(m, rc, std::string("nvl_decode_speculative: the draft refused: ") + draft->err);      // (it changed nothing)
+        // a refusal from here on leaves the draft where the target is: this pass is undone, earlier passes stay
+        auto undo_draft = [&] { for (int a = 0; a < na; a++) draft->slot_len[(size_t)dslot[(size_t)who[(size_t)a]]] = m->slot_len[(size_t)tslot[(size_t)who[(size_t)a]]]; };
+        for (int a = 0; a < na; a++) {
+            toks[(size_t)a * S] = first[(size_t)a];
+            for (int j = 0; j < k_pass; j++) toks[(size_t)a * S + 1 + j] = dtok[(size_t)j * na + a];
+        }
+        if (k_pass > 0) {
+            if ((rc = spec_proposals_check(m, draft, "nvl_decode_speculative", na, ids.data(), toks.data(), k_pass, S))) { undo_draft(); return rc; }
+            const std::vector<float> u = spec_merge_draws(na, k_pass, ua.data(), uf.data());
+            const SampledReq rq{params, hp.data(), hl.data(), u.data()};
+            const SpecReq spec{draft->draft_q, round_up(m->V, 4), 1, na, nullptr};
+            rc = verify_slab(m, "nvl_decode_speculative", na, ids.data(), toks.data(), k_pass, 1, acc.data(), got.data(), keep.data(), &rq, nullptr, &spec);
+        } else {
+            const SampledReq rq{params, hp.data(), hl.data(), uf.data()};
+            rc = verify_slab(m, "nvl_decode_speculative", na, ids.data(), toks.data(), 0, 0, acc.data(), got.data(), keep.data(), &rq);
+        }
+        if (rc) { undo_draft(); return rc; }
+        passes++;
+        for (int a = 0; a < na; a++) {
+            const int i = who[(size_t)a], take = std::min(acc[(size_t)a] + 1, keep[(size_t)a]);
+            for (int j = 0; j < take; j++) {
+                const int32_t t = got[(size_t)a * S + j];
+                out_tokens[(size_t)(done[(size_t)i] + j) * n_seqs + i] = t;
+                hist[(size_t)i].push_back(t);
+            }
+            done[(size_t)i] += take;
+            if (accepted_out) accepted_out[i] += std::min(acc[(size_t)a], take);
+            draft->slot_len[(size_t)dslot[(size_t)i]] = m->slot_len[(size_t)tslot[(size_t)i]];      // the draft's rollback
+        }
+    }
+    if (passes_out) *passes_out = passes;
     return NVL_OK;
     NVL_CATCH(m)
 }
@@ -3654,7 +3875,7 @@ extern "C" int nvl_reset_stats(nvl_model* m) {
 static const char* const k_site_names[KS_COUNT] = {
     "other", "qkv_proj", "attention", "o_proj", "ffn_up", "ffn_down", "lm_head", "norm", "moe_router", "moe_plan", "moe_up",
     "moe_down", "moe_combine", "embed", "argmax", "rope_kv", "mamba_in_proj", "mamba_conv", "mamba_scan", "mamba_gate_norm",
-    "mamba_out_proj", "tp_allreduce", "logprobs"};
+    "mamba_out_proj", "tp_allreduce", "logprobs", "spec_reject"};
 extern "C" const char* nvl_kernel_site_name(int site) { return site >= 0 && site < KS_COUNT ? k_site_names[site] : ""; }
 extern "C" int nvl_get_kernel_stats(nvl_model* m, nvl_kernel_stat* out, int cap) {
     if (!m || (cap > 0 && !out)) return NVL_ERR_INVALID;

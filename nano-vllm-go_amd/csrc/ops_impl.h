@@ -650,6 +650,56 @@ extern "C" int nvl_op_sample_drafts(int device, const float* logits, int n_seqs,
     OP_CATCH
 }
 
+// spec_reject_kernel (spec.h) on host distributions: p [n_seqs][1+k][V] (the target's rows), q [n_seqs][k][V]
+// (the draft's steps), rows padded to round_up(V, 4) floats on upload as the model path keeps them.
+extern "C" int nvl_op_spec_reject(int device, const float* p, const float* q, const int32_t* tokens, int n_seqs, int k, int V,
+                                  const float* accept_uniforms, const float* final_uniforms, int32_t* n_accepted_out,
+                                  int32_t* out_tokens, float* accept_prob_out) {
+    if (!p || !q || !tokens || n_seqs <= 0 || k < 1 || k > 7 || V <= 0 || !accept_uniforms || !final_uniforms || !n_accepted_out || !out_tokens)
+        return op_fail("nvl_op_spec_reject: bad arguments");
+    const int S = 1 + k, M = n_seqs * S;
+    for (int i = 0; i < n_seqs; i++)
+        for (int j = 1; j < S; j++)
+            if (tokens[i * S + j] < 0 || tokens[i * S + j] >= V) return op_fail("nvl_op_spec_reject: draft id outside the vocabulary");
+    for (int i = 0; i < n_seqs * k; i++) if (!(accept_uniforms[i] >= 0.f && accept_uniforms[i] <= 1.f)) return op_fail("nvl_op_spec_reject: uniform draw outside [0, 1]");
+    for (int i = 0; i < n_seqs; i++) if (!(final_uniforms[i] >= 0.f && final_uniforms[i] <= 1.f)) return op_fail("nvl_op_spec_reject: uniform draw outside [0, 1]");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_F32);
+    const int64_t Vp = round_up(V, 4);
+    auto up_rows = [&](const float* h, int64_t rows) {
+        float* d = (float*)cx.alloc(rows * Vp * 4);
+        NVL_HIP(hipMemsetAsync(d, 0, (size_t)(rows * Vp) * 4, cx.m.stream));
+        NVL_HIP(hipMemcpy2DAsync(d, (size_t)Vp * 4, h, (size_t)V * 4, (size_t)V * 4, (size_t)rows, hipMemcpyHostToDevice, cx.m.stream));
+        return d;
+    };
+    auto up_words = [&](const void* h, int64_t n) {
+        void* d = cx.alloc(n * 4);
+        NVL_HIP(hipMemcpyAsync(d, h, (size_t)n * 4, hipMemcpyHostToDevice, cx.m.stream));
+        return d;
+    };
+    std::vector<float> u((size_t)M);
+    for (int i = 0; i < n_seqs; i++) {
+        for (int j = 0; j < k; j++) u[(size_t)i * S + j] = accept_uniforms[(size_t)i * k + j];
+        u[(size_t)i * S + k] = final_uniforms[i];
+    }
+    SpecArgs a{};
+    a.p = up_rows(p, M); a.ldp = Vp;
+    a.q = up_rows(q, (int64_t)n_seqs * k); a.ldq = Vp; a.q_seq = k; a.q_step = 1;
+    a.tokens = (const int32_t*)up_words(tokens, M);
+    a.u = (const float*)up_words(u.data(), M);
+    a.res = (int32_t*)cx.alloc((int64_t)(n_seqs + M) * 4);
+    a.accept_prob = (float*)cx.alloc((int64_t)n_seqs * k * 2 * 4);
+    a.k = k; a.V = V;
+    hipLaunchKernelGGL(spec_reject_kernel, dim3(n_seqs), dim3(SAMPLE_THREADS), 0, cx.m.stream, a);
+    NVL_HIP(hipGetLastError());
+    NVL_HIP(hipMemcpyAsync(n_accepted_out, a.res, (size_t)n_seqs * 4, hipMemcpyDeviceToHost, cx.m.stream));
+    NVL_HIP(hipMemcpyAsync(out_tokens, a.res + n_seqs, (size_t)M * 4, hipMemcpyDeviceToHost, cx.m.stream));
+    if (accept_prob_out) NVL_HIP(hipMemcpyAsync(accept_prob_out, a.accept_prob, (size_t)n_seqs * k * 2 * 4, hipMemcpyDeviceToHost, cx.m.stream));
+    NVL_HIP(hipStreamSynchronize(cx.m.stream));   // (also keeps the host vector alive until the copies are done)
+    return NVL_OK;
+    OP_CATCH
+}
+
 extern "C" int nvl_op_logprobs(int device, const float* logits, int rows, int V, int ld, float logits_scaling,
                                const int32_t* targets, int top_k, float* logprob_out, int32_t* argmax_out,
                                int32_t* topk_ids_out, float* topk_logprob_out) {

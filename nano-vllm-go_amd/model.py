@@ -448,6 +448,68 @@ class HipTransformerModel:
                                                    ptrs, _ptr(lens), _ptr(u), _ptr(out), _ptr(passes)), self.h)
         return out, int(passes[0])
 
+    # -- speculative decoding with a draft model ---------------------------------------
+    def draft_sampled(self, seq_ids, first_tokens, k: int, histories, uniforms, *, temperature=1.0, top_p=1.0, top_k=0,
+                      repetition_penalty=1.2):
+        """nvl_draft_sampled on THIS (draft) model: decode_sampled with n_steps = k -> ids [k, n_seqs]; every step's final
+        distribution stays on the device for the target's verify_speculative."""
+        n = len(seq_ids)
+        if not 1 <= int(k) <= 7:
+            raise ValueError("draft_sampled: k must be in [1, 7]")
+        first, u, ptrs, lens, keep = self._sampled_args("draft_sampled", n, first_tokens, k, histories, uniforms, (int(k), n))
+        if first.size != n:
+            raise ValueError(f"draft_sampled: {first.size} first tokens for {n} sequences")
+        ids = np.ascontiguousarray(seq_ids, dtype=np.int64)
+        out = np.empty((int(k), n), dtype=np.int32)
+        sp = L.sampling_params(temperature, top_p, top_k, repetition_penalty)
+        L.check(self.lib.nvl_draft_sampled(self.h, n, _ptr(ids), _ptr(first), int(k), C.byref(sp), ptrs, _ptr(lens), _ptr(u),
+                                           _ptr(out)), self.h)
+        return out
+
+    def verify_speculative(self, draft, seq_ids, token_rows, k: int, histories, accept_uniforms, final_uniforms, *,
+                           temperature=1.0, top_p=1.0, top_k=0, repetition_penalty=1.2, return_probs=False):
+        """nvl_verify_speculative on THIS (target) model against the proposals `draft` keeps.  token_rows [n_seqs, 1+k]: the
+        next input token, then the draft's ids; accept_uniforms [n_seqs, k], final_uniforms [n_seqs].
+        -> (n_accepted [n_seqs], out_tokens [n_seqs, 1+k][, accept_prob [n_seqs, k, 2] = {p_j(d_j), q_j(d_j)}])."""
+        n = len(seq_ids)
+        toks, ua, ptrs, lens, keep = self._sampled_args("verify_speculative", n, token_rows, k, histories, accept_uniforms, (n, int(k)))
+        if toks.size != n * (1 + k):
+            raise ValueError(f"verify_speculative: {toks.size} tokens for {n} x {1 + k} rows")
+        uf = np.ascontiguousarray(final_uniforms, dtype=np.float32)
+        if uf.size != n:
+            raise ValueError(f"verify_speculative: {uf.size} final uniforms for {n} sequences")
+        ids = np.ascontiguousarray(seq_ids, dtype=np.int64)
+        acc = np.empty(n, np.int32)
+        out = np.empty((n, 1 + k), np.int32)
+        ap = np.empty((n, int(k), 2), np.float32) if return_probs else None
+        sp = L.sampling_params(temperature, top_p, top_k, repetition_penalty)
+        L.check(self.lib.nvl_verify_speculative(self.h, draft.h, n, _ptr(ids), _ptr(toks), int(k), C.byref(sp), ptrs, _ptr(lens),
+                                                _ptr(ua), _ptr(uf), _ptr(acc), _ptr(out), _ptr(ap)), self.h)
+        return (acc, out, ap) if return_probs else (acc, out)
+
+    def decode_speculative(self, draft, seq_ids, first_tokens, n_steps: int, histories, uniforms, k: int = 3, *,
+                           temperature=1.0, top_p=1.0, top_k=0, repetition_penalty=1.2):
+        """nvl_decode_speculative: decode_sampled's result shape [n_steps, n_seqs] from `draft`'s proposals + speculative
+        verify passes on THIS (target) model; uniforms [n_steps, n_seqs, 2k+1] (per pass: k draft draws, k accept draws, the
+        final draw).  -> (out_tokens, passes, accepted [n_seqs])."""
+        n = len(seq_ids)
+        if int(n_steps) <= 0:
+            raise ValueError("decode_speculative: n_steps must be positive")
+        if not 1 <= int(k) <= 7:
+            raise ValueError("decode_speculative: k must be in [1, 7]")
+        first, u, ptrs, lens, keep = self._sampled_args("decode_speculative", n, first_tokens, k, histories, uniforms,
+                                                        (int(n_steps) * n, 2 * int(k) + 1))
+        if first.size != n:
+            raise ValueError(f"decode_speculative: {first.size} first tokens for {n} sequences")
+        ids = np.ascontiguousarray(seq_ids, dtype=np.int64)
+        out = np.empty((n_steps, n), dtype=np.int32)
+        passes = np.zeros(1, np.int32)
+        accepted = np.zeros(n, np.int32)
+        sp = L.sampling_params(temperature, top_p, top_k, repetition_penalty)
+        L.check(self.lib.nvl_decode_speculative(self.h, draft.h, n, _ptr(ids), _ptr(first), int(n_steps), int(k), C.byref(sp), ptrs,
+                                                _ptr(lens), _ptr(u), _ptr(out), _ptr(passes), _ptr(accepted)), self.h)
+        return out, int(passes[0]), accepted
+
     def greedy_fused(self, prompt, max_tokens: int, seq_id: int = 0):
         """greedy() with the whole decode loop in one nvl_decode_greedy call."""
         self.seq_reset(seq_id)

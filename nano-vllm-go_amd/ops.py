@@ -269,3 +269,23 @@ def sample_drafts(logits, token_rows, k, histories, uniforms, *, temperature=1.0
     L.check(L.lib().nvl_op_sample_drafts(device, _p(lg), n, k, V, C.byref(sp), _p(toks), ptrs, _p(lens), _p(u), _p(sampled),
                                          _p(acc), _p(out), _p(probs)))
     return (sampled, acc, out, probs) if return_probs else (sampled, acc, out)
+
+
+def spec_reject(p, q, token_rows, accept_uniforms, final_uniforms, device=0):
+    """nvl_op_spec_reject: the rejection kernel of speculative sampling with a draft model on host distributions.
+    p [n_seqs, 1+k, V] (the target's rows), q [n_seqs, k, V] (the draft's steps), token_rows [n_seqs, 1+k] (column 0 unused,
+    column j+1 the draft's id of step j), accept_uniforms [n_seqs, k], final_uniforms [n_seqs].
+    -> (n_accepted [n_seqs], out_tokens [n_seqs, 1+k], accept_prob [n_seqs, k, 2] = {p_j(d_j), q_j(d_j)})."""
+    p, q = _f(p), _f(q)
+    if p.ndim != 3 or q.ndim != 3 or p.shape[0] != q.shape[0] or p.shape[1] != q.shape[1] + 1 or p.shape[2] != q.shape[2]:
+        raise ValueError("spec_reject: p must be [n_seqs, 1+k, V] and q [n_seqs, k, V]")
+    n, k, V = q.shape
+    if not 1 <= k <= 7:
+        raise ValueError("spec_reject: k must be in [1, 7]")
+    toks = np.ascontiguousarray(token_rows, dtype=np.int32)
+    ua, uf = _f(accept_uniforms), _f(final_uniforms)
+    if toks.size != n * (1 + k) or ua.size != n * k or uf.size != n:
+        raise ValueError(f"spec_reject: {toks.size} tokens / {ua.size} accept draws / {uf.size} final draws for {n} x (1 + {k}) rows")
+    acc, out, ap = np.empty(n, np.int32), np.empty((n, 1 + k), np.int32), np.empty((n, k, 2), np.float32)
+    L.check(L.lib().nvl_op_spec_reject(device, _p(p), _p(q), _p(toks), n, k, V, _p(ua), _p(uf), _p(acc), _p(out), _p(ap)))
+    return acc, out, ap

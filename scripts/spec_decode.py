@@ -20,7 +20,16 @@ next to one step of nvl_decode_sampled.  Two figures per route: wall clock per p
 (what a host loop pays, synchronisations included), and the library's own HIP-event time of the forward passes
 (nvl_stats; it covers (a) whole — its sampler and accept kernel lie inside the events — and of (c) only the nvl_forward).
 
-    python scripts/spec_decode.py --sampled --ks 3"""
+    python scripts/spec_decode.py --sampled --ks 3
+
+--draft: speculative decoding with a draft MODEL.  Target: the Llama-3.2-1B shapes; draft: the same width
+with 4 layers; both random, so nothing is accepted beyond chance and only times are reported: per draft phase
+(nvl_draft_sampled, k steps), per verify pass (nvl_verify_speculative: forward of 1 + k rows, sampler, rejection kernel;
+launched eagerly), the rejection kernel's own time from the library's per-kernel events (nvl_set_profile, site
+"spec_reject"; taken in a separate run of the same passes), one step of nvl_decode_sampled on the target, and the
+accepted drafts per pass from which a pass pair pays:  (draft + verify) / plain step - 1.
+
+    python scripts/spec_decode.py --draft --ks 3"""
 import argparse
 import importlib
 import importlib.util
@@ -51,6 +60,8 @@ def main():
     ap.add_argument("--passes", type=int, default=32)
     ap.add_argument("--reps", type=int, default=5)
     ap.add_argument("--sampled", action="store_true")
+    ap.add_argument("--draft", action="store_true")
+    ap.add_argument("--draft-layers", type=int, default=4)
     args = ap.parse_args()
     import torch
     pkg = importlib.import_module("nano-vllm-go_amd")
@@ -74,6 +85,15 @@ def main():
         torch.cuda.synchronize()
         return time.perf_counter() - t0
 
+    if args.draft:
+        dcfg = dict(cfg, num_layers=args.draft_layers)
+        draft = pkg.HipTransformerModel(dcfg, None, device=0, precision="bf16", max_seqs=Bmax, max_batch_tokens=Bmax * S)
+        bench.gen_weights_on_device(pkg, dcfg, draft, torch, torch.device("cuda", 0), keep_host=False)
+        draft.finalize()
+        draft_mode(args, model, draft, prompts, batches, ks, clock)
+        draft.close()
+        model.close()
+        return
     if args.sampled:
         sampled_mode(args, pkg, model, prompts, batches, ks, clock)
         model.close()
@@ -243,6 +263,82 @@ def sampled_mode(args, pkg, model, prompts, batches, ks, clock):
                                  f"device {statistics.median(dev[n]):.4f}" for n in routes)
                 print(f"B={B} k={k} [{name}]: ms per pass, median [min..max] of {args.reps} x {args.passes}: {line} | "
                       f"accepted (random drafts): a {got['a'].tolist()} c {got['c'].tolist()}", flush=True)
+
+
+def draft_mode(args, model, draft, prompts, batches, ks, clock):
+    V, S, G = model.cfg["vocab_size"], args.ctx, args.gen
+    r = np.random.default_rng(2)
+
+    def device_ms(m):
+        st = m.stats()
+        return st["decode_ms"] + st["prefill_ms"]
+
+    for B in batches:
+        ids = list(range(B))
+        for m in (model, draft):
+            for i in ids:
+                m.seq_reset(i)
+        _, first = model.forward_batch(ids, [prompts[i] for i in ids], [0] * B, want_logits=False)
+        draft.forward_batch(ids, [prompts[i] for i in ids], [0] * B, want_logits=False)
+        first = first.copy()
+        hists = [prompts[i].tolist() + [int(first[i])] for i in ids]
+
+        def rewind():
+            for i in ids:
+                model.seq_truncate(i, S)
+                draft.seq_truncate(i, S)
+
+        for name, kw in (("default", {}), ("T0.8 k40 p0.95", dict(temperature=0.8, top_k=40, top_p=0.95))):
+            U = r.random((G, B)).astype(np.float32)
+            model.decode_sampled(ids, first, G, hists, U, **kw)          # warm-up
+            plain = []
+            for _ in range(args.reps):
+                rewind()
+                plain.append(clock(lambda: model.decode_sampled(ids, first, G, hists, U, **kw)) / G * 1e3)
+            rewind()
+            ms_plain = statistics.median(plain)
+            print(f"B={B} ctx={S} [{name}]: plain nvl_decode_sampled (target) {ms_plain:.4f} ms/step wall "
+                  f"[{min(plain):.4f}..{max(plain):.4f}] ({args.reps} x {G} steps)", flush=True)
+            for k in ks:
+                ud, ua, uf = r.random((k, B)).astype(np.float32), r.random((B, k)).astype(np.float32), r.random(B).astype(np.float32)
+                got = {}
+
+                def one_pass():
+                    d = draft.draft_sampled(ids, first, k, hists, ud, **kw)
+                    rows = np.concatenate([first[:, None], d.T], axis=1).astype(np.int32)
+                    got["acc"] = model.verify_speculative(draft, ids, rows, k, hists, ua, uf, **kw)[0]
+
+                t_draft, t_verify, d_draft, d_verify = [], [], [], []
+                for rep_i in range(args.reps + 1):            # rep 0: warm-up (first sight of every launch configuration)
+                    td = tv = 0.0
+                    dd0, dv0 = device_ms(draft), device_ms(model)
+                    for _ in range(args.passes):
+                        rewind()
+                        d = [None]
+                        td += clock(lambda: d.__setitem__(0, draft.draft_sampled(ids, first, k, hists, ud, **kw)))
+                        rows = np.concatenate([first[:, None], d[0].T], axis=1).astype(np.int32)
+                        tv += clock(lambda: got.__setitem__("acc", model.verify_speculative(draft, ids, rows, k, hists, ua, uf, **kw)[0]))
+                    if rep_i:
+                        t_draft.append(td / args.passes * 1e3); t_verify.append(tv / args.passes * 1e3)
+                        d_draft.append((device_ms(draft) - dd0) / args.passes); d_verify.append((device_ms(model) - dv0) / args.passes)
+                # the rejection kernel alone: the library's per-kernel events, in a run of their own
+                model.set_profile(True)
+                model.reset_stats()
+                for _ in range(args.passes):
+                    rewind()
+                    one_pass()
+                rej = [s for s in model.kernel_stats() if s["site"] == "spec_reject"]
+                model.set_profile(False)
+                model.reset_stats()
+                rewind()
+                ms_rej = sum(s["ms"] for s in rej) / max(1, sum(s["launches"] for s in rej))
+                md, mv = statistics.median(t_draft), statistics.median(t_verify)
+                dv = statistics.median(d_verify)
+                print(f"B={B} k={k} [{name}]: ms, median [min..max] of {args.reps} x {args.passes}: draft phase wall {md:.4f} "
+                      f"[{min(t_draft):.4f}..{max(t_draft):.4f}] device {statistics.median(d_draft):.4f} | verify pass wall {mv:.4f} "
+                      f"[{min(t_verify):.4f}..{max(t_verify):.4f}] device {dv:.4f} | spec_reject kernel {ms_rej:.4f} "
+                      f"({100 * ms_rej / dv:.1f} % of the pass's device time) | break-even accepted drafts per pass "
+                      f"{(md + mv) / ms_plain - 1:.2f} | accepted (random models): {got['acc'].tolist()}", flush=True)
 
 
 if __name__ == "__main__":
