@@ -13,6 +13,7 @@
 #include <rccl/rccl.h>
 
 #include "model.h"
+#include "spec_loop.h"
 
 using namespace nvl;
 
@@ -2431,6 +2432,112 @@ void score_download(nvl_model* m, const ScoreOut& so, int M) {
     if (so.top_k > 0 && so.topk_lp) NVL_HIP(hipMemcpyAsync(so.topk_lp, b.topk_lp(), (size_t)M * so.top_k * 4, hipMemcpyDeviceToHost, m->stream));
 }
 
+// ---- the batch planner: every entry point validates its batch and fills meta_host here ----------------------------------
+// A batch is n_seqs sequences whose token rows lie back to back in `tokens` (M rows in all): lens[i] rows each, or S rows
+// each when lens == NULL.  `need` more positions must fit every sequence (lens[i] when lens != NULL).
+// ORDER OF THE CHECKS (the one place that states it).  Paged mode first refuses table_offsets[0] < 0.  Then sequence by
+// sequence, i ascending, the first defect of the first defective sequence is reported:
+//   slab:   unknown sequence -> duplicate of an earlier sequence -> pos_offset != cached length (nvl_forward only)
+//   paged:  negative position
+//   both:   position + need beyond max_seq_len
+//   paged:  table_offsets decreasing -> block table too short -> block table too long -> block id out of range
+//   both:   token id outside [0, V), row by row
+// Nothing but meta_host (scratch of the call) is written: a refused call leaves every length, tick and draft record alone.
+struct Batch {
+    const char* who; int n_seqs, M; const int32_t* tokens; const int32_t* lens; int S, need;
+    static Batch uniform(const char* who, int n_seqs, const int32_t* tokens, int S, int need) { return {who, n_seqs, n_seqs * S, tokens, nullptr, S, need}; }
+    static Batch ragged(const char* who, int n_seqs, int M, const int32_t* tokens, const int32_t* lens) { return {who, n_seqs, M, tokens, lens, 0, 0}; }
+    int rows(int i) const { return lens ? lens[i] : S; }
+    int fit(int i) const { return lens ? lens[i] : need; }
+};
+int refuse(nvl_model* m, const Batch& b, int code, const char* what) { return fail(m, code, std::string(b.who) + ": " + what); }
+// what both front ends end in: sequence i's rows, starting at row t, positions pos .., block-table row at blk_table + tbl
+int plan_rows(nvl_model* m, const Batch& b, const Meta& hm, int i, int& t, int pos, int tbl) {
+    const int n = b.rows(i);
+    hm.seq_tok_start[i] = t; hm.seq_len[i] = n; hm.seq_pos[i] = pos; hm.seq_tbl[i] = tbl;
+    for (int j = 0; j < n; j++, t++) {
+        const int tok = b.tokens[t];
+        if (tok < 0 || tok >= m->V) return refuse(m, b, NVL_ERR_INVALID, "token id out of range");
+        hm.tokens[t] = tok; hm.tok_pos[t] = pos + j; hm.tok_tbl[t] = tbl;
+    }
+    hm.last_rows[i] = t - 1;
+    return NVL_OK;
+}
+// slab front end: seq_ids -> h_slot; positions are the cached lengths, which pos_offsets (nvl_forward, else NULL) must equal.
+// `limit`: max_seq_len, or the smaller one of a target / draft pair.  The sequence's block table is the one entry
+// blk_table[i] = its slot (blocks_per_seq == 1 here).
+int plan_slab(nvl_model* m, const Batch& b, const int64_t* seq_ids, const int32_t* pos_offsets, std::vector<int>& h_slot, int limit) {
+    const Meta hm = bind_meta(m, m->meta_host, b.M);
+    h_slot.resize((size_t)b.n_seqs);
+    for (int i = 0, t = 0; i < b.n_seqs; i++) {
+        auto it = m->seq_slot.find(seq_ids[i]);
+        if (it == m->seq_slot.end()) return refuse(m, b, NVL_ERR_UNKNOWN_SEQ, "sequence has no KV slot (nvl_seq_open first)");
+        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return refuse(m, b, NVL_ERR_INVALID, "duplicate sequence in batch");
+        const int slot = it->second, pos = m->slot_len[(size_t)slot];
+        if (pos_offsets && pos_offsets[i] != pos) return refuse(m, b, NVL_ERR_INVALID, "pos_offset does not equal the cached length");
+        if (pos > limit - b.fit(i))   // rope.go:84-86 / :176-178 panic
+            return refuse(m, b, NVL_ERR_POSITION, "position exceeds max_seq_len");
+        h_slot[(size_t)i] = slot; hm.blk_table[i] = slot;
+        if (const int rc = plan_rows(m, b, hm, i, t, pos, i)) return rc;
+    }
+    return NVL_OK;
+}
+// paged front end: the caller's positions and block tables (table i = block_tables[table_offsets[i] .. table_offsets[i+1])),
+// which must cover position + need
+int plan_paged(nvl_model* m, const Batch& b, const int32_t* pos_offsets, const int32_t* block_tables, const int32_t* table_offsets) {
+    const Meta hm = bind_meta(m, m->meta_host, b.M);
+    if (table_offsets[0] < 0) return refuse(m, b, NVL_ERR_INVALID, "negative table offset");
+    for (int i = 0, t = 0; i < b.n_seqs; i++) {
+        const int pos = pos_offsets[i];
+        if (pos < 0) return refuse(m, b, NVL_ERR_INVALID, "negative position");
+        if (pos > m->cfg.max_seq_len - b.fit(i))      // (written so that the sum cannot overflow)
+            return refuse(m, b, NVL_ERR_POSITION, "position exceeds max_seq_len");
+        if (table_offsets[i + 1] < table_offsets[i]) return refuse(m, b, NVL_ERR_INVALID, "table_offsets must be non-decreasing");
+        const int nb = table_offsets[i + 1] - table_offsets[i];
+        if (nb < cdiv(pos + b.fit(i), m->Tmax)) return refuse(m, b, NVL_ERR_INVALID, "block table shorter than the positions it must cover");
+        if (nb > m->blocks_per_seq) return refuse(m, b, NVL_ERR_INVALID, "block table too long");
+        const int tb = i * m->blocks_per_seq;                      // fixed stride: the kernels index blk_table[seq][block]
+        for (int j = 0; j < nb; j++) {
+            const int blk = block_tables[table_offsets[i] + j];
+            if (blk < 0 || blk >= m->num_blocks) return refuse(m, b, NVL_ERR_INVALID, "block id out of range");
+            hm.blk_table[tb + j] = blk;
+        }
+        if (const int rc = plan_rows(m, b, hm, i, t, pos, tb)) return rc;
+    }
+    return NVL_OK;
+}
+// A planned pass's attention cost, `step` positions on (decode_loop: step s of one row per sequence): 4*hd FLOPs per (query,
+// visible key) pair per head -> returned; cached + new keys of the batch -> kv_tok; the longest context -> ctx_hint.
+double attn_cost(nvl_model* m, const Meta& hm, int n_seqs, int step = 0) {
+    double attn_flops = 0, kv_tok = 0;
+    for (int i = 0; i < n_seqs; i++) {
+        const double s = hm.seq_len[i], p0 = hm.seq_pos[i] + step;
+        attn_flops += 4.0 * m->hd * m->nH * (s * p0 + s * (s + 1) / 2);
+        m->ctx_hint = std::max(m->ctx_hint, hm.seq_pos[i] + step + hm.seq_len[i]);
+        kv_tok += p0 + s;
+    }
+    m->kv_tok = kv_tok;
+    return attn_flops;
+}
+// after a slab pass: sequence i's cache grew by rows(i)
+template <typename F>
+void advance_slots(nvl_model* m, const std::vector<int>& h_slot, F rows) {
+    for (size_t i = 0; i < h_slot.size(); i++) { m->slot_len[(size_t)h_slot[i]] += rows((int)i); m->slot_tick[(size_t)h_slot[i]] = ++m->tick; }
+}
+// the rows of a ragged batch: NVL_OK and M / the longest sequence / whether any has more than one row, or the refusal
+int count_rows(nvl_model* m, const char* who, int n_seqs, const int32_t* seq_lens, int& M, int& max_len, bool& prefill) {
+    int64_t M64 = 0;
+    max_len = 0; prefill = false;
+    for (int i = 0; i < n_seqs; i++) {
+        if (seq_lens[i] <= 0) return fail(m, NVL_ERR_INVALID, std::string(who) + ": empty sequence");
+        M64 += seq_lens[i]; max_len = std::max(max_len, seq_lens[i]);
+        if (seq_lens[i] > 1) prefill = true;
+    }
+    if (M64 > m->opts.max_batch_tokens) return fail(m, NVL_ERR_INVALID, std::string(who) + ": batch exceeds max_batch_tokens");
+    M = (int)M64;
+    return NVL_OK;
+}
+
 // nvl_forward, and nvl_score when `so` != NULL (the same validation, KV append and state update; flags then carry
 // NVL_FWD_ALL_LOGITS and logits_out / argmax_out are NULL)
 int forward_slab(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* tokens,
@@ -2443,53 +2550,18 @@ int forward_slab(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t
     if (n_seqs > m->opts.max_seqs) return fail(m, NVL_ERR_INVALID, "nvl_forward: n_seqs exceeds max_seqs");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
-    const nvl_model_config& c = m->cfg;
-    const int H = m->H;
     // ---- validate + build metadata -------------------------------------------------------
-    int64_t M64 = 0; int max_len = 0; bool prefill = false;
-    for (int i = 0; i < n_seqs; i++) {
-        if (seq_lens[i] <= 0) return fail(m, NVL_ERR_INVALID, "nvl_forward: empty sequence");
-        M64 += seq_lens[i]; max_len = std::max(max_len, seq_lens[i]);
-        if (seq_lens[i] > 1) prefill = true;
-    }
-    if (M64 > m->opts.max_batch_tokens) return fail(m, NVL_ERR_INVALID, "nvl_forward: batch exceeds max_batch_tokens");
-    const int M = (int)M64;
+    int M = 0, max_len = 0; bool prefill = false;
+    if (const int rc = count_rows(m, "nvl_forward", n_seqs, seq_lens, M, max_len, prefill)) return rc;
     if (m->paged) return fail(m, NVL_ERR_STATE, "nvl_forward: the model is in paged-KV mode (use nvl_forward_paged)");
+    std::vector<int> h_slot;
+    if (const int rc = plan_slab(m, Batch::ragged("nvl_forward", n_seqs, M, tokens, seq_lens), seq_ids, pos_offsets, h_slot, m->cfg.max_seq_len)) return rc;
     const Meta hm = bind_meta(m, m->meta_host, M);
-    int32_t *h_sts = hm.seq_tok_start, *h_len = hm.seq_len, *h_pos = hm.seq_pos, *h_tbl = hm.seq_tbl, *h_last = hm.last_rows,
-            *h_tokens = hm.tokens, *h_tok_pos = hm.tok_pos, *h_tok_tbl = hm.tok_tbl;
-    std::vector<int> h_slot((size_t)n_seqs);
-    int t = 0;
-    for (int i = 0; i < n_seqs; i++) {
-        auto it = m->seq_slot.find(seq_ids[i]);
-        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_forward: sequence has no KV slot (nvl_seq_open first)");
-        const int slot = it->second;
-        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, "nvl_forward: duplicate sequence in batch");
-        if (pos_offsets[i] != m->slot_len[(size_t)slot]) return fail(m, NVL_ERR_INVALID, "nvl_forward: pos_offset does not equal the cached length");
-        if (pos_offsets[i] > c.max_seq_len - seq_lens[i])   // rope.go:84-86 / :176-178 panic
-            return fail(m, NVL_ERR_POSITION, "nvl_forward: position exceeds max_seq_len");
-        // slab mode: the sequence's block table is the one entry blk_table[i] = its slot
-        h_sts[i] = t; h_len[i] = seq_lens[i]; h_pos[i] = pos_offsets[i]; h_slot[(size_t)i] = slot; h_tbl[i] = i; hm.blk_table[i] = slot;     // (blocks_per_seq == 1 here)
-        for (int j = 0; j < seq_lens[i]; j++, t++) {
-            const int tok = tokens[t];
-            if (tok < 0 || tok >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_forward: token id out of range");
-            h_tokens[t] = tok; h_tok_pos[t] = pos_offsets[i] + j; h_tok_tbl[t] = i;
-        }
-        h_last[i] = t - 1;
-    }
     const ScoreReq sreq{so ? so->top_k : 0, so && so->top_k > 0 && (so->topk_ids || so->topk_lp)};
     if (so) { const int rc = score_prepare(m, *so, M, "nvl_score"); if (rc) return rc; }
     const Meta md = bind_meta(m, m->meta_dev, M);
     NVL_HIP(hipEventRecord(m->ev0, m->stream));
-
-    double attn_flops = 0, kv_tok = 0;   // 4*hd per (query, visible key) pair per head; cached + new keys of the batch
-    for (int i = 0; i < n_seqs; i++) {
-        const double s = seq_lens[i], p0 = pos_offsets[i];
-        attn_flops += 4.0 * m->hd * m->nH * (s * p0 + s * (s + 1) / 2);
-        m->ctx_hint = std::max(m->ctx_hint, (int)(pos_offsets[i] + seq_lens[i]));
-        kv_tok += p0 + s;
-    }
-    m->kv_tok = kv_tok;
+    const double attn_flops = attn_cost(m, hm, n_seqs);
     const bool all = (flags & NVL_FWD_ALL_LOGITS) != 0;
     int rows = all ? M : n_seqs;
     std::vector<int32_t> am;
@@ -2523,10 +2595,10 @@ int forward_slab(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t
     p2p_check(m);
     m->last_rows = so ? 0 : rows;        // (a scoring pass leaves no logits rows: nvl_sample / nvl_logprobs are refused after it)
     if (argmax_out) {
-        if (all) for (int i = 0; i < n_seqs; i++) argmax_out[i] = am_p[(size_t)h_last[i]];
+        if (all) for (int i = 0; i < n_seqs; i++) argmax_out[i] = am_p[(size_t)hm.last_rows[i]];
         else for (int i = 0; i < n_seqs; i++) argmax_out[i] = am_p[(size_t)i];
     }
-    for (int i = 0; i < n_seqs; i++) { m->slot_len[(size_t)h_slot[(size_t)i]] += seq_lens[i]; m->slot_tick[(size_t)h_slot[(size_t)i]] = ++m->tick; }
+    advance_slots(m, h_slot, [&](int i) { return seq_lens[i]; });
     float ms = 0.f;
     (void)hipEventElapsedTime(&ms, m->ev0, m->ev1);
     m->stats.forward_calls++;
@@ -2566,55 +2638,16 @@ int forward_paged_impl(nvl_model* m, int n_seqs, const int32_t* tokens, const in
     if (n_seqs > m->opts.max_seqs) return fail(m, NVL_ERR_INVALID, "nvl_forward_paged: n_seqs exceeds max_seqs");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
-    const nvl_model_config& c = m->cfg;
-    const int BS = m->Tmax;
-    int64_t M64 = 0; int max_len = 0; bool prefill = false;
-    for (int i = 0; i < n_seqs; i++) {
-        if (seq_lens[i] <= 0) return fail(m, NVL_ERR_INVALID, "nvl_forward_paged: empty sequence");
-        if (pos_offsets[i] < 0) return fail(m, NVL_ERR_INVALID, "nvl_forward_paged: negative pos_offset");
-        M64 += seq_lens[i]; max_len = std::max(max_len, seq_lens[i]);
-        if (seq_lens[i] > 1) prefill = true;
-    }
-    if (M64 > m->opts.max_batch_tokens) return fail(m, NVL_ERR_INVALID, "nvl_forward_paged: batch exceeds max_batch_tokens");
-    const int M = (int)M64;
+    int M = 0, max_len = 0; bool prefill = false;
+    if (const int rc = count_rows(m, "nvl_forward_paged", n_seqs, seq_lens, M, max_len, prefill)) return rc;
+    if (const int rc = plan_paged(m, Batch::ragged("nvl_forward_paged", n_seqs, M, tokens, seq_lens), pos_offsets, block_tables, table_offsets)) return rc;
     const Meta hm = bind_meta(m, m->meta_host, M);
-    int t = 0, tb = 0;
-    if (table_offsets[0] < 0) return fail(m, NVL_ERR_INVALID, "nvl_forward_paged: negative table offset");
-    for (int i = 0; i < n_seqs; i++) {
-        if (pos_offsets[i] > c.max_seq_len - seq_lens[i])      // (written so that the sum cannot overflow)
-            return fail(m, NVL_ERR_POSITION, "nvl_forward_paged: position exceeds max_seq_len");
-        const int end = pos_offsets[i] + seq_lens[i];
-        if (table_offsets[i + 1] < table_offsets[i]) return fail(m, NVL_ERR_INVALID, "nvl_forward_paged: table_offsets must be non-decreasing");
-        const int nb = table_offsets[i + 1] - table_offsets[i];
-        if (nb < cdiv(end, BS)) return fail(m, NVL_ERR_INVALID, "nvl_forward_paged: block table shorter than the sequence");
-        if (nb > m->blocks_per_seq) return fail(m, NVL_ERR_INVALID, "nvl_forward_paged: block table too long");
-        tb = i * m->blocks_per_seq;                      // fixed stride: the kernels index blk_table[seq][block]
-        hm.seq_tok_start[i] = t; hm.seq_len[i] = seq_lens[i]; hm.seq_pos[i] = pos_offsets[i]; hm.seq_tbl[i] = tb;
-        for (int j = 0; j < nb; j++) {
-            const int b = block_tables[table_offsets[i] + j];
-            if (b < 0 || b >= m->num_blocks) return fail(m, NVL_ERR_INVALID, "nvl_forward_paged: block id out of range");
-            hm.blk_table[tb + j] = b;
-        }
-        for (int j = 0; j < seq_lens[i]; j++, t++) {
-            const int tok = tokens[t];
-            if (tok < 0 || tok >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_forward_paged: token id out of range");
-            hm.tokens[t] = tok; hm.tok_pos[t] = pos_offsets[i] + j; hm.tok_tbl[t] = tb;
-        }
-        hm.last_rows[i] = t - 1;
-    }
     const ScoreReq sreq{so ? so->top_k : 0, so && so->top_k > 0 && (so->topk_ids || so->topk_lp)};
     if (so) { const int rc = score_prepare(m, *so, M, "nvl_score_paged"); if (rc) return rc; }
     const Meta md = bind_meta(m, m->meta_dev, M);
     NVL_HIP(hipEventRecord(m->ev0, m->stream));
     NVL_HIP(hipMemcpyAsync(m->meta_dev, m->meta_host, meta_bytes(m, M), hipMemcpyHostToDevice, m->stream));
-    double attn_flops = 0, kv_tok = 0;
-    for (int i = 0; i < n_seqs; i++) {
-        const double s = seq_lens[i], p0 = pos_offsets[i];
-        attn_flops += 4.0 * m->hd * m->nH * (s * p0 + s * (s + 1) / 2);
-        m->ctx_hint = std::max(m->ctx_hint, (int)(pos_offsets[i] + seq_lens[i]));
-        kv_tok += p0 + s;
-    }
-    m->kv_tok = kv_tok;
+    const double attn_flops = attn_cost(m, hm, n_seqs);
     const bool all = (flags & NVL_FWD_ALL_LOGITS) != 0;
     const int rows = enqueue_forward(m, md, n_seqs, M, max_len, attn_flops, flags, 0, so ? &sreq : nullptr);
     NVL_HIP(hipEventRecord(m->ev1, m->stream));
@@ -2709,6 +2742,15 @@ extern "C" int nvl_runner_run_paged(nvl_model* m, int n_seqs, const int32_t* con
 }
 
 namespace {
+// the sampler's arguments over the device-kept histories (rows of m->samp_hist, max_seq_len ids each), drawing from `uniforms`;
+// the caller adds what only its form of sample_row_kernel reads
+SampleArgs sample_args(const nvl_model* m, const float* uniforms) {
+    SampleArgs a{};
+    a.logits = m->logits; a.ld = m->Vpad; a.work = m->samp.work; a.cnt = m->samp.cnt; a.hist = m->samp_hist;
+    a.hist_off = nullptr; a.hist_stride = m->cfg.max_seq_len; a.hist_len = m->samp_hist_len;
+    a.uniforms = uniforms; a.out = m->samp.out; a.probs_out = nullptr; a.ldp = m->V; a.V = m->V;
+    return a;
+}
 // the n_steps decode passes of nvl_decode_greedy[_paged]: metadata for step 0 is in meta_host (one token per sequence),
 // every later step's tokens / positions are produced on the device
 // `sp` != NULL: every step samples (tensor.SampleWithHistory, sample.h) instead of taking the argmax; the histories live
@@ -2732,13 +2774,7 @@ void decode_loop(nvl_model* m, const Meta& hm, int n_seqs, int n_steps, int32_t*
     const bool dbg = m->keep_hidden, dbg_tap = m->tap;
     m->keep_hidden = false; m->tap = false;      // the per-layer taps belong to single nvl_forward calls
     for (int s = 0; s < n_steps; s++) {
-        double attn_flops = 0, kv_tok = 0;
-        for (int i = 0; i < n_seqs; i++) {
-            attn_flops += 4.0 * m->hd * m->nH * (double)(h_pos[i] + s + 1);
-            m->ctx_hint = std::max(m->ctx_hint, h_pos[i] + s + 1);
-            kv_tok += h_pos[i] + s + 1;
-        }
-        m->kv_tok = kv_tok;
+        const double attn_flops = attn_cost(m, hm, n_seqs, s);
         // bf16 path: the step's tail (argmax, token feedback) and the next step's head (embedding gather + layer 0's
         // norm) are one launch (decode_seam_kernel); fp32 parity mode keeps the separate kernels
         const bool seam_ok = (g_decode_seam || sp) && !m->f32 && m->H <= 1024 * NORM_ROW_MAXCH && m->H % 4 == 0;
@@ -2746,12 +2782,9 @@ void decode_loop(nvl_model* m, const Meta& hm, int n_seqs, int n_steps, int32_t*
         auto one_step = [&] {
         enqueue_forward(m, md, n_seqs, M, 1, attn_flops, 0, seam_ok ? ((s > 0 ? 1 : 0) | (sp ? 4 : 2)) : 0);
         if (sp) {
-            SampleArgs a{};
-            a.logits = m->logits; a.ld = m->Vpad; a.work = m->samp.work; a.cnt = m->samp.cnt; a.hist = m->samp_hist;
-            a.hist_off = nullptr; a.hist_stride = m->cfg.max_seq_len; a.hist_len = m->samp_hist_len;
-            a.uniforms = uniforms_dev + (int64_t)s * n_seqs; a.out = m->samp.out; a.probs_out = nullptr; a.ldp = m->V;
+            SampleArgs a = sample_args(m, uniforms_dev + (int64_t)s * n_seqs);
             if (keep) { a.ldp = round_up(m->V, 4); a.probs_out = keep + (int64_t)s * n_seqs * a.ldp; }
-            a.V = m->V; a.top_k = sp->top_k; a.temperature = sp->temperature; a.top_p = sp->top_p; a.rep_penalty = sp->repetition_penalty;
+            a.top_k = sp->top_k; a.temperature = sp->temperature; a.top_p = sp->top_p; a.rep_penalty = sp->repetition_penalty;
             hipLaunchKernelGGL(sample_row_kernel<false>, dim3(n_seqs), dim3(SAMPLE_THREADS), 0, m->stream, a);
             NVL_HIP(hipGetLastError());
         }
@@ -2827,23 +2860,11 @@ extern "C" int nvl_decode_greedy(nvl_model* m, int n_seqs, const int64_t* seq_id
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
     if (m->paged) return fail(m, NVL_ERR_STATE, "nvl_decode_greedy: not available in paged-KV mode");
-    const int M = n_seqs;
-    const Meta hm = bind_meta(m, m->meta_host, M);
-    int32_t *h_sts = hm.seq_tok_start, *h_len = hm.seq_len, *h_pos = hm.seq_pos, *h_tbl = hm.seq_tbl, *h_last = hm.last_rows,
-            *h_tokens = hm.tokens, *h_tok_pos = hm.tok_pos, *h_tok_tbl = hm.tok_tbl;
-    std::vector<int> h_slot((size_t)n_seqs);
-    for (int i = 0; i < n_seqs; i++) {
-        auto it = m->seq_slot.find(seq_ids[i]);
-        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_decode_greedy: sequence has no KV slot");
-        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy: duplicate sequence");
-        const int slot = it->second, pos = m->slot_len[(size_t)slot];
-        if (pos + n_steps > m->cfg.max_seq_len) return fail(m, NVL_ERR_POSITION, "nvl_decode_greedy: position exceeds max_seq_len");
-        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy: token id out of range");
-        h_sts[i] = i; h_len[i] = 1; h_pos[i] = pos; h_slot[(size_t)i] = slot; h_last[i] = i; h_tbl[i] = i; hm.blk_table[i] = slot;
-        h_tokens[i] = first_tokens[i]; h_tok_pos[i] = pos; h_tok_tbl[i] = i;
-    }
+    std::vector<int> h_slot;
+    if (const int rc = plan_slab(m, Batch::uniform("nvl_decode_greedy", n_seqs, first_tokens, 1, n_steps), seq_ids, nullptr, h_slot, m->cfg.max_seq_len)) return rc;
+    const Meta hm = bind_meta(m, m->meta_host, n_seqs);
     decode_loop(m, hm, n_seqs, n_steps, out_tokens);
-    for (int i = 0; i < n_seqs; i++) { m->slot_len[(size_t)h_slot[(size_t)i]] += n_steps; m->slot_tick[(size_t)h_slot[(size_t)i]] = ++m->tick; }
+    advance_slots(m, h_slot, [&](int) { return n_steps; });
     return NVL_OK;
     NVL_CATCH(m)
 }
@@ -2863,27 +2884,8 @@ extern "C" int nvl_decode_greedy_paged(nvl_model* m, int n_seqs, const int32_t* 
         return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_paged: n_seqs exceeds max_seqs / max_batch_tokens");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
-    const int M = n_seqs, BS = m->Tmax;
-    const Meta hm = bind_meta(m, m->meta_host, M);
-    for (int i = 0; i < n_seqs; i++) {
-        const int pos = positions[i];
-        if (pos < 0) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_paged: negative position");
-        if (pos > m->cfg.max_seq_len - n_steps) return fail(m, NVL_ERR_POSITION, "nvl_decode_greedy_paged: position exceeds max_seq_len");
-        const int end = pos + n_steps;
-        if ((i == 0 && table_offsets[0] < 0) || table_offsets[i + 1] < table_offsets[i])
-            return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_paged: table_offsets must be non-negative and non-decreasing");
-        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_paged: token id out of range");
-        const int nb = table_offsets[i + 1] - table_offsets[i];
-        if (nb < cdiv(end, BS) || nb > m->blocks_per_seq) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_paged: block table does not cover the generated positions");
-        const int tb = i * m->blocks_per_seq;
-        for (int j = 0; j < nb; j++) {
-            const int b = block_tables[table_offsets[i] + j];
-            if (b < 0 || b >= m->num_blocks) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_paged: block id out of range");
-            hm.blk_table[tb + j] = b;
-        }
-        hm.seq_tok_start[i] = i; hm.seq_len[i] = 1; hm.seq_pos[i] = pos; hm.seq_tbl[i] = tb; hm.last_rows[i] = i;
-        hm.tokens[i] = first_tokens[i]; hm.tok_pos[i] = pos; hm.tok_tbl[i] = tb;
-    }
+    if (const int rc = plan_paged(m, Batch::uniform("nvl_decode_greedy_paged", n_seqs, first_tokens, 1, n_steps), positions, block_tables, table_offsets)) return rc;
+    const Meta hm = bind_meta(m, m->meta_host, n_seqs);
     decode_loop(m, hm, n_seqs, n_steps, out_tokens);
     return NVL_OK;
     NVL_CATCH(m)
@@ -2943,11 +2945,31 @@ VsBlock bind_vs(int32_t* base, int n_seqs) {
     return VsBlock{(nvl_sampling_params*)base, base + 4, base + 4 + n_seqs, (float*)(base + 4 + 2 * n_seqs)};
 }
 static_assert(sizeof(nvl_sampling_params) == 16, "bind_vs layout");
-// `append`: the accept kernel also appends the emitted ids to the device histories (the loop); the histories themselves are
-// rows of m->samp_hist with lengths m->samp_hist_len in either case.
-// `spec` (nvl_verify_speculative): the draft's kept distributions; spec_reject_kernel (spec.h) takes the accept kernel's place.
+// the sampled calls' arguments (SampleWithHistory per row, sampling.go:33-102)
+struct SampledReq { const nvl_sampling_params* params; const int32_t* const* hist_ptrs; const int32_t* hist_lens; const float* uniforms; };
+// the draft's kept distributions of a speculative pass (nvl_verify_speculative)
 struct SpecReq { const float* q; int64_t ldq, q_seq, q_step; float* accept_prob_out; };
-struct SampledPass { bool append; const SpecReq* spec = nullptr; };
+// What a verify pass is, as one value.  The factories are the only way to make one, so every value is a legal pass:
+//   greedy       the argmax and verify_accept_kernel
+//   sampled      ONE sampled pass (nvl_verify_sampled[_paged]): the caller's histories and draws are checked and staged, then
+//                the sampler and verify_accept_sampled_kernel
+//   in_loop      a pass of nvl_decode_sampled_lookup: the loop has staged the histories and filled vs_host itself, and the
+//                accept kernel also appends the emitted ids to the device histories
+//   speculative  `sampled` with the draft's distributions: spec_reject_kernel (spec.h) takes the accept kernel's place
+// The histories are rows of m->samp_hist with lengths m->samp_hist_len in every sampled kind.
+class VerifyKind {
+public:
+    enum Tag { GREEDY, SAMPLED, IN_LOOP, SPECULATIVE };
+    static VerifyKind greedy() { return VerifyKind(GREEDY, SampledReq{}, SpecReq{}); }
+    static VerifyKind sampled(const SampledReq& rq) { return VerifyKind(SAMPLED, rq, SpecReq{}); }
+    static VerifyKind in_loop() { return VerifyKind(IN_LOOP, SampledReq{}, SpecReq{}); }
+    static VerifyKind speculative(const SampledReq& rq, const SpecReq& spec) { return VerifyKind(SPECULATIVE, rq, spec); }
+    const Tag tag; const SampledReq rq; const SpecReq spec;
+    bool samples() const { return tag != GREEDY; }
+    bool stages() const { return tag == SAMPLED || tag == SPECULATIVE; }      // rq is the caller's, to be checked and staged
+private:
+    VerifyKind(Tag t, const SampledReq& r, const SpecReq& s) : tag(t), rq(r), spec(s) {}
+};
 
 // the sampler's scratch for `rows` rows; a captured sampled pass holds these addresses
 void reserve_sample_rows(nvl_model* m, int rows) {
@@ -2973,50 +2995,39 @@ void reserve_sample_hist(nvl_model* m) {
     m->samp_hist = dmalloc<int32_t>(m->samp_hist_cap); m->samp_hist_len = dmalloc<int32_t>(m->opts.max_seqs);
 }
 
-// The pass itself, metadata already in meta_host (n_seqs sequences of 1 + k rows each, positions h_pos[i] ..): upload,
+// The pass itself, metadata already in meta_host (n_seqs sequences of 1 + k rows each, positions seq_pos[i] ..): upload,
 // launches, accept kernel and result download — captured and replayed like a decode pass when every projection is in
 // decode form (<= 64 rows) — then the host copies.  Leaves the n_seqs x (1+k) logits rows as the last forward group.
-// `sp` != NULL: a sampled pass (vs_host filled, histories on the device): the sampler and its accept kernel take the place of
-// the argmax and verify_accept_kernel.
-void verify_pass(nvl_model* m, int n_seqs, int k, const int32_t* h_pos, int32_t* n_acc_out, int32_t* out_tokens,
-                 const SampledPass* sp = nullptr) {
+// A sampled kind finds vs_host filled and the histories on the device.
+void verify_pass(nvl_model* m, int n_seqs, int k, int32_t* n_acc_out, int32_t* out_tokens, const VerifyKind& vk) {
     const int S = 1 + k, M = n_seqs * S;
     const Meta md = bind_meta(m, m->meta_dev, M);
     NVL_HIP(hipEventRecord(m->ev0, m->stream));
-    double attn_flops = 0, kv_tok = 0;
-    for (int i = 0; i < n_seqs; i++) {
-        const double s = S, p0 = h_pos[i];
-        attn_flops += 4.0 * m->hd * m->nH * (s * p0 + s * (s + 1) / 2);
-        m->ctx_hint = std::max(m->ctx_hint, h_pos[i] + S);
-        kv_tok += p0 + s;
-    }
-    m->kv_tok = kv_tok;
+    const double attn_flops = attn_cost(m, bind_meta(m, m->meta_host, M), n_seqs);
+    const bool spec = vk.tag == VerifyKind::SPECULATIVE;
     const bool mq = g_verify_mq && attention_mq_ok(m, S);
     const int nres = n_seqs * (1 + S);
-    if (sp) reserve_sample_rows(m, M);
+    if (vk.samples()) reserve_sample_rows(m, M);
     auto pass = [&] {
         NVL_HIP(hipMemcpyAsync(m->meta_dev, m->meta_host, meta_bytes(m, M), hipMemcpyHostToDevice, m->stream));
-        if (sp) {
+        if (vk.samples()) {
             NVL_HIP(hipMemcpyAsync(m->vs_dev, m->vs_host, (size_t)(4 + 2 * n_seqs + M) * 4, hipMemcpyHostToDevice, m->stream));
             enqueue_forward(m, md, n_seqs, M, S, attn_flops, NVL_FWD_ALL_LOGITS, (mq ? 8 : 0) | 4);
             const VsBlock vs = bind_vs(m->vs_dev, n_seqs);
-            SampleArgs a{};
-            a.logits = m->logits; a.ld = m->Vpad; a.work = m->samp.work; a.cnt = m->samp.cnt; a.hist = m->samp_hist;
-            a.hist_off = nullptr; a.hist_stride = m->cfg.max_seq_len; a.hist_len = m->samp_hist_len;
-            a.uniforms = vs.u; a.out = m->samp.out; a.probs_out = nullptr; a.ldp = m->V; a.V = m->V;
+            SampleArgs a = sample_args(m, vs.u);
             a.ext = md.tokens; a.ext_S = S; a.hist_row = vs.hist_row; a.params = vs.params;
             hipLaunchKernelGGL(sample_row_kernel<true>, dim3(M), dim3(SAMPLE_THREADS), 0, m->stream, a);
             NVL_HIP(hipGetLastError());
-            if (sp->spec) {     // the sampler left row r's final distribution in work row r; its ids of the pass are not used
+            if (spec) {     // the sampler left row r's final distribution in work row r; its ids of the pass are not used
                 SpecArgs r{};
-                r.p = m->samp.work; r.ldp = round_up(m->V, 4); r.q = sp->spec->q; r.ldq = sp->spec->ldq; r.q_seq = sp->spec->q_seq;
-                r.q_step = sp->spec->q_step; r.tokens = md.tokens; r.u = vs.u; r.res = m->verify_dev; r.accept_prob = m->spec_ap;
+                r.p = m->samp.work; r.ldp = round_up(m->V, 4); r.q = vk.spec.q; r.ldq = vk.spec.ldq; r.q_seq = vk.spec.q_seq;
+                r.q_step = vk.spec.q_step; r.tokens = md.tokens; r.u = vs.u; r.res = m->verify_dev; r.accept_prob = m->spec_ap;
                 r.k = k; r.V = m->V;
                 KScope ks(m, KC_OTHER, 0, KS_SPEC_REJECT, (double)n_seqs * m->V * 8.0);
                 hipLaunchKernelGGL(spec_reject_kernel, dim3(n_seqs), dim3(SAMPLE_THREADS), 0, m->stream, r);
             } else
             hipLaunchKernelGGL(verify_accept_sampled_kernel, dim3(cdiv(n_seqs, 64)), dim3(64), 0, m->stream, (const int32_t*)m->samp.out,
-                               (const int32_t*)md.tokens, k, n_seqs, m->verify_dev, sp->append ? m->samp_hist : (int32_t*)nullptr,
+                               (const int32_t*)md.tokens, k, n_seqs, m->verify_dev, vk.tag == VerifyKind::IN_LOOP ? m->samp_hist : (int32_t*)nullptr,
                                (int64_t)m->cfg.max_seq_len, m->samp_hist_len, (const int32_t*)vs.hist_row, (const int32_t*)vs.keep);
         } else {
             enqueue_forward(m, md, n_seqs, M, S, attn_flops, NVL_FWD_ALL_LOGITS, mq ? 8 : 0);
@@ -3024,13 +3035,13 @@ void verify_pass(nvl_model* m, int n_seqs, int k, const int32_t* h_pos, int32_t*
         }
         NVL_HIP(hipGetLastError());
         NVL_HIP(hipMemcpyAsync(m->verify_host, m->verify_dev, (size_t)nres * 4, hipMemcpyDeviceToHost, m->stream));
-        if (sp && sp->spec && sp->spec->accept_prob_out)      // (a speculative pass is never captured: the host address is not baked in)
-            NVL_HIP(hipMemcpyAsync(sp->spec->accept_prob_out, m->spec_ap, (size_t)n_seqs * k * 2 * 4, hipMemcpyDeviceToHost, m->stream));
+        if (spec && vk.spec.accept_prob_out)      // (a speculative pass is never captured: the host address is not baked in)
+            NVL_HIP(hipMemcpyAsync(vk.spec.accept_prob_out, m->spec_ap, (size_t)n_seqs * k * 2 * 4, hipMemcpyDeviceToHost, m->stream));
     };
     bool replayed = false;
-    if (M <= 64 && M <= m->logit_rows && !(sp && sp->spec)) {      // (a speculative pass runs eagerly: it reads another model's buffer)
+    if (M <= 64 && M <= m->logit_rows && !spec) {      // (a speculative pass runs eagerly: it reads another model's buffer)
         const int acfg = mq ? decode_attn_cfg(m, n_seqs, S) : (S == 1 ? decode_attn_waves(m, n_seqs) : 0);
-        const std::array<int, 5> key{sp ? 4 : 3, n_seqs, acfg, k | (mq ? 256 : 0) | (sp && sp->append ? 512 : 0), g_tune_epoch};
+        const std::array<int, 5> key{vk.samples() ? 4 : 3, n_seqs, acfg, k | (mq ? 256 : 0) | (vk.tag == VerifyKind::IN_LOOP ? 512 : 0), g_tune_epoch};
         replayed = replay_or_capture(m, key, pass);
     }
     if (!replayed) pass();
@@ -3058,22 +3069,21 @@ int verify_refusals(nvl_model* m, const char* who, int n_seqs, int k, int k_min)
     return NVL_OK;
 }
 
-// ---- the sampled calls' arguments (SampleWithHistory per row, sampling.go:33-102) ----
-struct SampledReq { const nvl_sampling_params* params; const int32_t* const* hist_ptrs; const int32_t* hist_lens; const float* uniforms; };
-
 bool sampling_params_ok(const nvl_sampling_params* sp) {     // the rules of nvl_sample / nvl_decode_sampled
     return sp->repetition_penalty != 0.f && sp->repetition_penalty == sp->repetition_penalty &&
            sp->temperature == sp->temperature && sp->top_p == sp->top_p;
 }
 // every history present, ending with its sequence's first token of the pass, free of negative ids, and short enough that
-// history + `grow` more ids fit `max_len`; `n_u` draws inside [0, 1].  Pure validation.
-const char* sampled_check(const SampledReq& rq, int n_seqs, const int32_t* first, int first_stride, int grow, int64_t max_len, int64_t n_u) {
+// history + `grow` more ids fit `max_len`; `n_u` draws inside [0, 1].  `strict` = false (nvl_decode_sampled, nvl_draft_sampled):
+// a history may be empty and need not end with the first token.  Pure validation.
+const char* sampled_check(const SampledReq& rq, int n_seqs, const int32_t* first, int first_stride, int grow, int64_t max_len, int64_t n_u,
+                          bool strict = true) {
     if (!sampling_params_ok(rq.params)) return "bad sampling parameters (NaN, or repetition_penalty 0)";
     for (int i = 0; i < n_seqs; i++) {
         const int hn = rq.hist_lens[i];
-        if (!rq.hist_ptrs[i] || hn <= 0) return "a sequence has no history (it must end with the sequence's first token)";
+        if (hn < 0 || (hn > 0 && !rq.hist_ptrs[i]) || (strict && hn == 0)) return "a sequence has no history (it must end with the sequence's first token)";
         if ((int64_t)hn + grow > max_len) return "history longer than max_seq_len";
-        if (rq.hist_ptrs[i][hn - 1] != first[(int64_t)i * first_stride]) return "a history must end with its first token";
+        if (strict && rq.hist_ptrs[i][hn - 1] != first[(int64_t)i * first_stride]) return "a history must end with its first token";
         for (int j = 0; j < hn; j++) if (rq.hist_ptrs[i][j] < 0) return "negative token id in the history";
     }
     for (int64_t i = 0; i < n_u; i++) if (!(rq.uniforms[i] >= 0.f && rq.uniforms[i] <= 1.f)) return "uniform draw outside [0, 1]";
@@ -3101,47 +3111,34 @@ void sampled_stage_pass(nvl_model* m, int n_seqs, int k, const SampledReq& rq) {
     memcpy(vs.u, rq.uniforms, (size_t)n_seqs * S * 4);
 }
 
-// nvl_verify_greedy (k_min = 1) and the passes of nvl_decode_greedy_lookup (k_min = 0: a last pass of one row per sequence).
-// keep[i] (or NULL): at most that many of sequence i's accepted tokens stay in the cache.
-// rq != NULL: nvl_verify_sampled — checked here, after everything else, and staged; sp != NULL alone: a pass of
-// nvl_decode_sampled_lookup, which has staged its histories and filled the block itself.
-int verify_slab(nvl_model* m, const char* who, int n_seqs, const int64_t* seq_ids, const int32_t* tokens, int k, int k_min,
-                int32_t* n_acc_out, int32_t* out_tokens, const int* keep, const SampledReq* rq = nullptr, const SampledPass* sp = nullptr,
-                const SpecReq* spec = nullptr) {
-    const int rc = verify_refusals(m, who, n_seqs, k, k_min);
-    if (rc) return rc;
-    if (m->paged) return fail(m, NVL_ERR_STATE, std::string(who) + ": the model is in paged-KV mode (use nvl_verify_greedy_paged)");
+// where a verify pass's sequences live: KV slots of the slab (seq_ids), or the caller's block tables
+struct KvRef {
+    const int64_t* seq_ids; const int32_t *pos_offsets, *block_tables, *table_offsets;
+    static KvRef slab(const int64_t* seq_ids) { return {seq_ids, nullptr, nullptr, nullptr}; }
+    static KvRef paged(const int32_t* pos_offsets, const int32_t* block_tables, const int32_t* table_offsets) { return {nullptr, pos_offsets, block_tables, table_offsets}; }
+};
+// Every verify call and every pass of the three loops: k_min = 1, or 0 for a loop's last pass of one row per sequence.
+// keep[i] (or NULL): at most that many of sequence i's accepted tokens stay in the cache.  A caller's histories and draws
+// (vk.stages()) are checked here, after everything else, and staged.
+int verify_batch(nvl_model* m, const char* who, int n_seqs, const KvRef& kv, const int32_t* tokens, int k, int k_min,
+                 int32_t* n_acc_out, int32_t* out_tokens, const int* keep, const VerifyKind& vk) {
+    if (const int rc = verify_refusals(m, who, n_seqs, k, k_min)) return rc;
+    const bool slab = kv.seq_ids != nullptr;
+    if (slab && m->paged) return fail(m, NVL_ERR_STATE, std::string(who) + ": the model is in paged-KV mode (use the _paged call)");
+    if (!slab && !m->paged) return fail(m, NVL_ERR_STATE, std::string(who) + ": the model was created without kv_num_blocks");
     const int S = 1 + k, M = n_seqs * S;
-    const Meta hm = bind_meta(m, m->meta_host, M);
-    std::vector<int> h_slot((size_t)n_seqs);
-    for (int i = 0; i < n_seqs; i++) {
-        auto it = m->seq_slot.find(seq_ids[i]);
-        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, std::string(who) + ": sequence has no KV slot (nvl_seq_open first)");
-        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, std::string(who) + ": duplicate sequence in batch");
-        const int slot = it->second, pos = m->slot_len[(size_t)slot];
-        if (pos > m->cfg.max_seq_len - S) return fail(m, NVL_ERR_POSITION, std::string(who) + ": position exceeds max_seq_len");
-        hm.seq_tok_start[i] = i * S; hm.seq_len[i] = S; hm.seq_pos[i] = pos; h_slot[(size_t)i] = slot; hm.seq_tbl[i] = i; hm.blk_table[i] = slot;
-        for (int j = 0; j < S; j++) {
-            const int tok = tokens[i * S + j];
-            if (tok < 0 || tok >= m->V) return fail(m, NVL_ERR_INVALID, std::string(who) + ": token id out of range");
-            hm.tokens[i * S + j] = tok; hm.tok_pos[i * S + j] = pos + j; hm.tok_tbl[i * S + j] = i;
-        }
-        hm.last_rows[i] = i * S + S - 1;
+    const Batch b = Batch::uniform(who, n_seqs, tokens, S, S);
+    std::vector<int> h_slot;      // (stays empty in paged mode: the caller owns the lengths)
+    if (const int rc = slab ? plan_slab(m, b, kv.seq_ids, nullptr, h_slot, m->cfg.max_seq_len)
+                            : plan_paged(m, b, kv.pos_offsets, kv.block_tables, kv.table_offsets)) return rc;
+    if (vk.stages()) {
+        if (const char* why = sampled_check(vk.rq, n_seqs, tokens, S, k, m->cfg.max_seq_len, (int64_t)M)) return fail(m, NVL_ERR_INVALID, std::string(who) + ": " + why);
+        if (vk.tag == VerifyKind::SPECULATIVE && !m->spec_ap) m->spec_ap = dmalloc<float>((int64_t)m->opts.max_seqs * 7 * 2);
+        sampled_stage_pass(m, n_seqs, k, vk.rq);
     }
-    const SampledPass single{false, spec};
-    if (rq) {
-        if (const char* why = sampled_check(*rq, n_seqs, tokens, S, k, m->cfg.max_seq_len, (int64_t)M)) return fail(m, NVL_ERR_INVALID, std::string(who) + ": " + why);
-        if (spec && !m->spec_ap) m->spec_ap = dmalloc<float>((int64_t)m->opts.max_seqs * 7 * 2);
-        sampled_stage_pass(m, n_seqs, k, *rq);
-        sp = &single;
-    }
-    verify_pass(m, n_seqs, k, hm.seq_pos, n_acc_out, out_tokens, sp);
-    // rollback: the accepted prefix and the row that produced the first unaccepted id stay; the rows behind are dead
-    for (int i = 0; i < n_seqs; i++) {
-        int adv = m->verify_host[i] + 1;
-        if (keep) adv = std::min(adv, keep[i]);
-        m->slot_len[(size_t)h_slot[(size_t)i]] += adv; m->slot_tick[(size_t)h_slot[(size_t)i]] = ++m->tick;
-    }
+    verify_pass(m, n_seqs, k, n_acc_out, out_tokens, vk);
+    // slab rollback: the accepted prefix and the row that produced the first unaccepted id stay; the rows behind are dead
+    advance_slots(m, h_slot, [&](int i) { const int adv = m->verify_host[i] + 1; return keep ? std::min(adv, keep[i]) : adv; });
     return NVL_OK;
 }
 }  // namespace
@@ -3152,51 +3149,9 @@ extern "C" int nvl_verify_greedy(nvl_model* m, int n_seqs, const int64_t* seq_id
     if (!seq_ids || !tokens || !n_accepted_out || !out_tokens) return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy: null arguments");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
-    return verify_slab(m, "nvl_verify_greedy", n_seqs, seq_ids, tokens, k, 1, n_accepted_out, out_tokens, nullptr);
+    return verify_batch(m, "nvl_verify_greedy", n_seqs, KvRef::slab(seq_ids), tokens, k, 1, n_accepted_out, out_tokens, nullptr, VerifyKind::greedy());
     NVL_CATCH(m)
 }
-
-namespace {
-int verify_paged(nvl_model* m, const std::string& who, int n_seqs, const int32_t* tokens, int k, const int32_t* pos_offsets,
-                 const int32_t* block_tables, const int32_t* table_offsets, int32_t* n_accepted_out, int32_t* out_tokens,
-                 const SampledReq* rq) {
-    const int rc = verify_refusals(m, who.c_str(), n_seqs, k, 1);
-    if (rc) return rc;
-    if (!m->paged) return fail(m, NVL_ERR_STATE, who + ": the model was created without kv_num_blocks");
-    const int S = 1 + k, M = n_seqs * S, BS = m->Tmax;
-    const Meta hm = bind_meta(m, m->meta_host, M);
-    if (table_offsets[0] < 0) return fail(m, NVL_ERR_INVALID, who + ": negative table offset");
-    for (int i = 0; i < n_seqs; i++) {
-        const int pos = pos_offsets[i];
-        if (pos < 0) return fail(m, NVL_ERR_INVALID, who + ": negative pos_offset");
-        if (pos > m->cfg.max_seq_len - S) return fail(m, NVL_ERR_POSITION, who + ": position exceeds max_seq_len");
-        if (table_offsets[i + 1] < table_offsets[i]) return fail(m, NVL_ERR_INVALID, who + ": table_offsets must be non-decreasing");
-        const int nb = table_offsets[i + 1] - table_offsets[i];
-        if (nb < cdiv(pos + S, BS)) return fail(m, NVL_ERR_INVALID, who + ": block table shorter than the sequence");
-        if (nb > m->blocks_per_seq) return fail(m, NVL_ERR_INVALID, who + ": block table too long");
-        const int tb = i * m->blocks_per_seq;
-        for (int j = 0; j < nb; j++) {
-            const int b = block_tables[table_offsets[i] + j];
-            if (b < 0 || b >= m->num_blocks) return fail(m, NVL_ERR_INVALID, who + ": block id out of range");
-            hm.blk_table[tb + j] = b;
-        }
-        hm.seq_tok_start[i] = i * S; hm.seq_len[i] = S; hm.seq_pos[i] = pos; hm.seq_tbl[i] = tb;
-        for (int j = 0; j < S; j++) {
-            const int tok = tokens[i * S + j];
-            if (tok < 0 || tok >= m->V) return fail(m, NVL_ERR_INVALID, who + ": token id out of range");
-            hm.tokens[i * S + j] = tok; hm.tok_pos[i * S + j] = pos + j; hm.tok_tbl[i * S + j] = tb;
-        }
-        hm.last_rows[i] = i * S + S - 1;
-    }
-    const SampledPass single{false};
-    if (rq) {
-        if (const char* why = sampled_check(*rq, n_seqs, tokens, S, k, m->cfg.max_seq_len, (int64_t)M)) return fail(m, NVL_ERR_INVALID, who + ": " + why);
-        sampled_stage_pass(m, n_seqs, k, *rq);
-    }
-    verify_pass(m, n_seqs, k, hm.seq_pos, n_accepted_out, out_tokens, rq ? &single : nullptr);
-    return NVL_OK;
-}
-}  // namespace
 
 extern "C" int nvl_verify_greedy_paged(nvl_model* m, int n_seqs, const int32_t* tokens, int k, const int32_t* pos_offsets,
                                        const int32_t* block_tables, const int32_t* table_offsets, int32_t* n_accepted_out,
@@ -3206,8 +3161,8 @@ extern "C" int nvl_verify_greedy_paged(nvl_model* m, int n_seqs, const int32_t* 
         return fail(m, NVL_ERR_INVALID, "nvl_verify_greedy_paged: null arguments");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
-    return verify_paged(m, "nvl_verify_greedy_paged", n_seqs, tokens, k, pos_offsets, block_tables, table_offsets, n_accepted_out,
-                        out_tokens, nullptr);
+    return verify_batch(m, "nvl_verify_greedy_paged", n_seqs, KvRef::paged(pos_offsets, block_tables, table_offsets), tokens, k, 1,
+                        n_accepted_out, out_tokens, nullptr, VerifyKind::greedy());
     NVL_CATCH(m)
 }
 
@@ -3221,8 +3176,8 @@ extern "C" int nvl_verify_sampled(nvl_model* m, int n_seqs, const int64_t* seq_i
         return fail(m, NVL_ERR_INVALID, "nvl_verify_sampled: null arguments");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
-    const SampledReq rq{params, history_ptrs, history_lens, uniforms};
-    return verify_slab(m, "nvl_verify_sampled", n_seqs, seq_ids, tokens, k, 1, n_accepted_out, out_tokens, nullptr, &rq);
+    return verify_batch(m, "nvl_verify_sampled", n_seqs, KvRef::slab(seq_ids), tokens, k, 1, n_accepted_out, out_tokens, nullptr,
+                        VerifyKind::sampled({params, history_ptrs, history_lens, uniforms}));
     NVL_CATCH(m)
 }
 
@@ -3237,9 +3192,8 @@ extern "C" int nvl_verify_sampled_paged(nvl_model* m, int n_seqs, const int32_t*
         return fail(m, NVL_ERR_INVALID, "nvl_verify_sampled_paged: null arguments");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
-    const SampledReq rq{params, history_ptrs, history_lens, uniforms};
-    return verify_paged(m, "nvl_verify_sampled_paged", n_seqs, tokens, k, pos_offsets, block_tables, table_offsets, n_accepted_out,
-                        out_tokens, &rq);
+    return verify_batch(m, "nvl_verify_sampled_paged", n_seqs, KvRef::paged(pos_offsets, block_tables, table_offsets), tokens, k, 1,
+                        n_accepted_out, out_tokens, nullptr, VerifyKind::sampled({params, history_ptrs, history_lens, uniforms}));
     NVL_CATCH(m)
 }
 
@@ -3257,17 +3211,20 @@ extern "C" int nvl_seq_truncate(nvl_model* m, int64_t seq_id, int new_len) {
 
 // prompt-lookup drafting: pure host code, no device
 extern "C" int nvl_lookup_draft(const int32_t* history, int n, int k, int ngram, int32_t* draft_out) {
-    if (!history || !draft_out || n < 1 || k < 1) return NVL_ERR_INVALID;
-    for (int g = std::min(ngram, n - 1); g >= 1; g--)
-        for (int s = n - g - 1; s >= 0; s--) {
-            if (memcmp(history + s, history + n - g, (size_t)g * 4) != 0) continue;
-            const int take = std::min(k, n - (s + g));       // (s < n - g: at least one token follows the match)
-            for (int j = 0; j < k; j++) draft_out[j] = history[s + g + std::min(j, take - 1)];
-            return take;
-        }
-    for (int j = 0; j < k; j++) draft_out[j] = history[n - 1];
-    return 0;
+    return (!history || !draft_out || n < 1 || k < 1) ? NVL_ERR_INVALID : lookup_draft(history, n, k, ngram, draft_out);
 }
+
+namespace {
+// how many rows beyond the first a pass may still append to the sequence in `slot` (the lookup loops' room rule)
+int cache_room(const nvl_model* m, int slot) { return m->cfg.max_seq_len - m->slot_len[(size_t)slot] - 1; }
+// drafts are taken from the history and fed to the model(s): every id must be inside the vocabulary
+bool history_in_vocab(const nvl_model* m, int n_seqs, const int32_t* const* history_ptrs, const int32_t* history_lens) {
+    for (int i = 0; i < n_seqs; i++)
+        if (history_ptrs[i])
+            for (int j = 0; j < history_lens[i]; j++) if (history_ptrs[i][j] >= m->V) return false;
+    return true;
+}
+}  // namespace
 
 extern "C" int nvl_decode_greedy_lookup(nvl_model* m, int n_seqs, const int64_t* seq_ids, const int32_t* first_tokens, int n_steps,
                                         int k, int ngram, const int32_t* const* history_ptrs, const int32_t* history_lens,
@@ -3280,54 +3237,25 @@ extern "C" int nvl_decode_greedy_lookup(nvl_model* m, int n_seqs, const int64_t*
     int rc = verify_refusals(m, "nvl_decode_greedy_lookup", n_seqs, k, 1);
     if (rc) return rc;
     if (m->paged) return fail(m, NVL_ERR_STATE, "nvl_decode_greedy_lookup: not available in paged-KV mode");
-    std::vector<std::vector<int32_t>> hist((size_t)n_seqs);
-    std::vector<int> done((size_t)n_seqs, 0);
+    std::vector<int> h_slot;
+    if ((rc = plan_slab(m, Batch::uniform("nvl_decode_greedy_lookup", n_seqs, first_tokens, 1, n_steps), seq_ids, nullptr, h_slot, m->cfg.max_seq_len))) return rc;
+    SpecLoop loop(n_seqs, n_steps);
     for (int i = 0; i < n_seqs; i++) {
-        auto it = m->seq_slot.find(seq_ids[i]);
-        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_decode_greedy_lookup: sequence has no KV slot");
-        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_lookup: duplicate sequence");
-        if (m->slot_len[(size_t)it->second] + n_steps > m->cfg.max_seq_len) return fail(m, NVL_ERR_POSITION, "nvl_decode_greedy_lookup: position exceeds max_seq_len");
-        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_lookup: token id out of range");
+        std::vector<int32_t>& h = loop.hist[(size_t)i];
         if (history_ptrs && history_ptrs[i] && history_lens[i] > 0) {
-            hist[(size_t)i].assign(history_ptrs[i], history_ptrs[i] + history_lens[i]);
-            if (hist[(size_t)i].back() != first_tokens[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_lookup: a history must end with its first token");
+            h.assign(history_ptrs[i], history_ptrs[i] + history_lens[i]);
+            if (h.back() != first_tokens[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_greedy_lookup: a history must end with its first token");
         } else
-            hist[(size_t)i].push_back(first_tokens[i]);
+            h.push_back(first_tokens[i]);
     }
-    int passes = 0;
-    std::vector<int64_t> ids; std::vector<int> who, keep; std::vector<int32_t> toks, acc, got;
-    for (;;) {
-        who.clear(); ids.clear(); keep.clear();
-        int k_pass = 0, room = k;
-        for (int i = 0; i < n_seqs; i++) {
-            if (done[(size_t)i] >= n_steps) continue;
-            who.push_back(i); ids.push_back(seq_ids[i]); keep.push_back(n_steps - done[(size_t)i]);
-            k_pass = std::max(k_pass, n_steps - done[(size_t)i] - 1);
-            room = std::min(room, m->cfg.max_seq_len - m->slot_len[(size_t)m->seq_slot[seq_ids[i]]] - 1);
-        }
-        if (who.empty()) break;
-        k_pass = std::min(k_pass, room);
-        const int na = (int)who.size(), S = 1 + k_pass;
-        toks.assign((size_t)na * S, 0); acc.assign((size_t)na, 0); got.assign((size_t)na * S, -1);
-        for (int a = 0; a < na; a++) {
-            const std::vector<int32_t>& h = hist[(size_t)who[(size_t)a]];
-            toks[(size_t)a * S] = h.back();
-            if (k_pass > 0) (void)nvl_lookup_draft(h.data(), (int)h.size(), k_pass, ngram, &toks[(size_t)a * S + 1]);
-        }
-        rc = verify_slab(m, "nvl_decode_greedy_lookup", na, ids.data(), toks.data(), k_pass, 0, acc.data(), got.data(), keep.data());
+    while (loop.plan(k, seq_ids, [&](int i) { return cache_room(m, h_slot[(size_t)i]); })) {
+        loop.draft_by_lookup(ngram);
+        rc = verify_batch(m, "nvl_decode_greedy_lookup", loop.na, KvRef::slab(loop.ids.data()), loop.toks.data(), loop.k_pass, 0, loop.acc.data(),
+                          loop.got.data(), loop.keep.data(), VerifyKind::greedy());
         if (rc) return rc;
-        passes++;
-        for (int a = 0; a < na; a++) {
-            const int i = who[(size_t)a], take = std::min(acc[(size_t)a] + 1, keep[(size_t)a]);
-            for (int j = 0; j < take; j++) {
-                const int32_t t = got[(size_t)a * S + j];
-                out_tokens[(size_t)(done[(size_t)i] + j) * n_seqs + i] = t;
-                hist[(size_t)i].push_back(t);
-            }
-            done[(size_t)i] += take;
-        }
+        loop.emit(out_tokens);
     }
-    if (passes_out) *passes_out = passes;
+    if (passes_out) *passes_out = loop.passes;
     return NVL_OK;
     NVL_CATCH(m)
 }
@@ -3346,66 +3274,34 @@ extern "C" int nvl_decode_sampled_lookup(nvl_model* m, int n_seqs, const int64_t
     int rc = verify_refusals(m, "nvl_decode_sampled_lookup", n_seqs, k, 1);
     if (rc) return rc;
     if (m->paged) return fail(m, NVL_ERR_STATE, "nvl_decode_sampled_lookup: not available in paged-KV mode");
-    for (int i = 0; i < n_seqs; i++) {
-        auto it = m->seq_slot.find(seq_ids[i]);
-        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_decode_sampled_lookup: sequence has no KV slot");
-        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled_lookup: duplicate sequence");
-        if (m->slot_len[(size_t)it->second] + n_steps > m->cfg.max_seq_len) return fail(m, NVL_ERR_POSITION, "nvl_decode_sampled_lookup: position exceeds max_seq_len");
-        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled_lookup: token id out of range");
-        if (history_ptrs[i])       // (drafts are taken from the history and fed to the model)
-            for (int j = 0; j < history_lens[i]; j++)
-                if (history_ptrs[i][j] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled_lookup: history id outside the vocabulary");
-    }
+    std::vector<int> h_slot;
+    if ((rc = plan_slab(m, Batch::uniform("nvl_decode_sampled_lookup", n_seqs, first_tokens, 1, n_steps), seq_ids, nullptr, h_slot, m->cfg.max_seq_len))) return rc;
+    if (!history_in_vocab(m, n_seqs, history_ptrs, history_lens)) return fail(m, NVL_ERR_INVALID, "nvl_decode_sampled_lookup: history id outside the vocabulary");
     const SampledReq rq{params, history_ptrs, history_lens, uniforms};
     if (const char* why = sampled_check(rq, n_seqs, first_tokens, 1, n_steps, m->cfg.max_seq_len, (int64_t)n_steps * n_seqs))
         return fail(m, NVL_ERR_INVALID, std::string("nvl_decode_sampled_lookup: ") + why);
-    std::vector<std::vector<int32_t>> hist((size_t)n_seqs);       // the host's copy, for drafting only
-    for (int i = 0; i < n_seqs; i++) hist[(size_t)i].assign(history_ptrs[i], history_ptrs[i] + history_lens[i]);
-    std::vector<int> done((size_t)n_seqs, 0);
+    SpecLoop loop(n_seqs, n_steps);       // (the host's copy of the histories is for drafting only)
+    for (int i = 0; i < n_seqs; i++) loop.hist[(size_t)i].assign(history_ptrs[i], history_ptrs[i] + history_lens[i]);
     sampled_stage_histories(m, n_seqs, rq);
-    const SampledPass sp{true};
-    int passes = 0;
-    std::vector<int64_t> ids; std::vector<int> who, keep; std::vector<int32_t> toks, acc, got;
-    for (;;) {
-        who.clear(); ids.clear(); keep.clear();
-        int k_pass = 0, room = k;
-        for (int i = 0; i < n_seqs; i++) {
-            if (done[(size_t)i] >= n_steps) continue;
-            who.push_back(i); ids.push_back(seq_ids[i]); keep.push_back(n_steps - done[(size_t)i]);
-            k_pass = std::max(k_pass, n_steps - done[(size_t)i] - 1);
-            room = std::min(room, m->cfg.max_seq_len - m->slot_len[(size_t)m->seq_slot[seq_ids[i]]] - 1);
-        }
-        if (who.empty()) break;
-        k_pass = std::min(k_pass, room);
-        const int na = (int)who.size(), S = 1 + k_pass;
-        toks.assign((size_t)na * S, 0); acc.assign((size_t)na, 0); got.assign((size_t)na * S, -1);
+    while (loop.plan(k, seq_ids, [&](int i) { return cache_room(m, h_slot[(size_t)i]); })) {
+        loop.draft_by_lookup(ngram);
+        const int na = loop.na, S = loop.S;
         const VsBlock vs = bind_vs(m->vs_host, na);
         *vs.params = *params;
         for (int a = 0; a < na; a++) {
-            const int i = who[(size_t)a];
-            const std::vector<int32_t>& h = hist[(size_t)i];
-            toks[(size_t)a * S] = h.back();
-            if (k_pass > 0) (void)nvl_lookup_draft(h.data(), (int)h.size(), k_pass, ngram, &toks[(size_t)a * S + 1]);
-            vs.keep[a] = keep[(size_t)a]; vs.hist_row[a] = i;
+            const int i = loop.who[(size_t)a];
+            vs.keep[a] = loop.keep[(size_t)a]; vs.hist_row[a] = i;
             for (int j = 0; j < S; j++) {       // row j is decode step done + j of the sequence; rows past the last step are never emitted
-                const int t = done[(size_t)i] + j;
+                const int t = loop.done[(size_t)i] + j;
                 vs.u[a * S + j] = t < n_steps ? uniforms[(size_t)t * n_seqs + i] : 0.f;
             }
         }
-        rc = verify_slab(m, "nvl_decode_sampled_lookup", na, ids.data(), toks.data(), k_pass, 0, acc.data(), got.data(), keep.data(), nullptr, &sp);
+        rc = verify_batch(m, "nvl_decode_sampled_lookup", na, KvRef::slab(loop.ids.data()), loop.toks.data(), loop.k_pass, 0, loop.acc.data(),
+                          loop.got.data(), loop.keep.data(), VerifyKind::in_loop());
         if (rc) { (void)hipStreamSynchronize(m->stream); return rc; }      // (the staged histories read the caller's arrays)
-        passes++;
-        for (int a = 0; a < na; a++) {
-            const int i = who[(size_t)a], take = std::min(acc[(size_t)a] + 1, keep[(size_t)a]);
-            for (int j = 0; j < take; j++) {
-                const int32_t t = got[(size_t)a * S + j];
-                out_tokens[(size_t)(done[(size_t)i] + j) * n_seqs + i] = t;
-                hist[(size_t)i].push_back(t);
-            }
-            done[(size_t)i] += take;
-        }
+        loop.emit(out_tokens);
     }
-    if (passes_out) *passes_out = passes;
+    if (passes_out) *passes_out = loop.passes;
     return NVL_OK;
     NVL_CATCH(m)
 }
@@ -3428,54 +3324,20 @@ int decode_sampled_impl(nvl_model* m, const std::string& who, int n_seqs, const 
         return fail(m, NVL_ERR_INVALID, who + ": null/empty arguments");
     if (n_seqs > m->opts.max_seqs || n_seqs > m->opts.max_batch_tokens)
         return fail(m, NVL_ERR_INVALID, who + ": n_seqs exceeds max_seqs / max_batch_tokens");
-    if (params->repetition_penalty == 0.f || !(params->repetition_penalty == params->repetition_penalty) ||
-        !(params->temperature == params->temperature) || !(params->top_p == params->top_p))
-        return fail(m, NVL_ERR_INVALID, who + ": bad sampling parameters");
+    if (!sampling_params_ok(params)) return fail(m, NVL_ERR_INVALID, who + ": bad sampling parameters");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
-    const int M = n_seqs, T = m->cfg.max_seq_len;
-    const Meta hm = bind_meta(m, m->meta_host, M);
-    std::vector<int> h_slot((size_t)n_seqs);
-    std::vector<int32_t> hist((size_t)n_seqs * T, 0), hlen((size_t)n_seqs);
-    for (int i = 0; i < n_seqs; i++) {
-        auto it = m->seq_slot.find(seq_ids[i]);
-        if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, who + ": sequence has no KV slot");
-        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, who + ": duplicate sequence");
-        const int slot = it->second, pos = m->slot_len[(size_t)slot];
-        if (pos + n_steps > T) return fail(m, NVL_ERR_POSITION, who + ": position exceeds max_seq_len");
-        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, who + ": token id out of range");
-        const int hn = history_lens[i];
-        if (hn < 0 || hn + n_steps > T || (hn > 0 && !history_ptrs[i])) return fail(m, NVL_ERR_INVALID, who + ": history longer than max_seq_len");
-        for (int j = 0; j < hn; j++) {
-            if (history_ptrs[i][j] < 0) return fail(m, NVL_ERR_INVALID, who + ": negative token id in the history");
-            hist[(size_t)i * T + j] = history_ptrs[i][j];
-        }
-        hlen[(size_t)i] = hn;
-        hm.seq_tok_start[i] = i; hm.seq_len[i] = 1; hm.seq_pos[i] = pos; h_slot[(size_t)i] = slot; hm.last_rows[i] = i;
-        hm.seq_tbl[i] = i; hm.blk_table[i] = slot;
-        hm.tokens[i] = first_tokens[i]; hm.tok_pos[i] = pos; hm.tok_tbl[i] = i;
-    }
-    for (int64_t i = 0; i < (int64_t)n_steps * n_seqs; i++)
-        if (!(uniforms[i] >= 0.f && uniforms[i] <= 1.f)) return fail(m, NVL_ERR_INVALID, who + ": uniform draw outside [0, 1]");
+    const int T = m->cfg.max_seq_len;
+    std::vector<int> h_slot;
+    if (const int rc = plan_slab(m, Batch::uniform(who.c_str(), n_seqs, first_tokens, 1, n_steps), seq_ids, nullptr, h_slot, T)) return rc;
+    const Meta hm = bind_meta(m, m->meta_host, n_seqs);
+    const SampledReq rq{params, history_ptrs, history_lens, uniforms};
+    if (const char* why = sampled_check(rq, n_seqs, first_tokens, 1, n_steps, T, (int64_t)n_steps * n_seqs, false)) return fail(m, NVL_ERR_INVALID, who + ": " + why);
+    std::vector<int32_t> hist((size_t)n_seqs * T, 0), hlen(history_lens, history_lens + n_seqs);
+    for (int i = 0; i < n_seqs; i++) std::copy(history_ptrs[i], history_ptrs[i] + hlen[(size_t)i], hist.begin() + (size_t)i * T);
     // device state of the sampler
-    SampleBufs& b = m->samp;
-    const int64_t elems = (int64_t)n_seqs * round_up(m->V, 4);
-    if (elems > b.elems || n_seqs > b.rows_cap) clear_graphs(m);      // (captured sampled verify passes hold the old addresses)
-    if (elems > b.elems) {
-        dfree(b.work); dfree(b.cnt);
-        b.work = dmalloc<float>(elems); b.cnt = dmalloc<int32_t>(elems); b.elems = elems;
-        NVL_HIP(hipMemsetAsync(b.cnt, 0, (size_t)elems * 4, m->stream));
-    }
-    if (n_seqs > b.rows_cap) {
-        dfree(b.off); dfree(b.out); dfree(b.u);
-        b.rows_cap = (int)round_up(n_seqs, 64);
-        b.off = dmalloc<int32_t>(b.rows_cap + 1); b.out = dmalloc<int32_t>(b.rows_cap); b.u = dmalloc<float>(b.rows_cap);
-    }
-    if ((int64_t)n_seqs * T > m->samp_hist_cap) {
-        dfree(m->samp_hist); dfree(m->samp_hist_len);
-        m->samp_hist_cap = (int64_t)m->opts.max_seqs * T;
-        m->samp_hist = dmalloc<int32_t>(m->samp_hist_cap); m->samp_hist_len = dmalloc<int32_t>(m->opts.max_seqs);
-    }
+    reserve_sample_rows(m, n_seqs);
+    reserve_sample_hist(m);
     if ((int64_t)n_steps * n_seqs > m->samp_u_cap) {
         dfree(m->samp_u_steps);
         m->samp_u_cap = (int64_t)n_steps * n_seqs;
@@ -3493,7 +3355,7 @@ int decode_sampled_impl(nvl_model* m, const std::string& who, int n_seqs, const 
         }
     }
     decode_loop(m, hm, n_seqs, n_steps, out_tokens, params, m->samp_u_steps, keep ? m->draft_q : nullptr);   // (synchronises: the host vectors stay alive)
-    for (int i = 0; i < n_seqs; i++) { m->slot_len[(size_t)h_slot[(size_t)i]] += n_steps; m->slot_tick[(size_t)h_slot[(size_t)i]] = ++m->tick; }
+    advance_slots(m, h_slot, [&](int) { return n_steps; });
     if (keep) {
         m->draft_n = n_seqs; m->draft_k = n_steps;
         m->draft_ids.assign(seq_ids, seq_ids + n_seqs); m->draft_tok.assign(out_tokens, out_tokens + (size_t)n_steps * n_seqs);
@@ -3571,7 +3433,8 @@ extern "C" int nvl_verify_speculative(nvl_model* target, nvl_model* draft, int n
     const std::vector<float> u = spec_merge_draws(n_seqs, k, accept_uniforms, final_uniforms);
     const SampledReq rq{params, history_ptrs, history_lens, u.data()};
     const SpecReq spec{draft->draft_q, round_up(m->V, 4), 1, n_seqs, accept_prob_out};
-    return verify_slab(m, "nvl_verify_speculative", n_seqs, seq_ids, tokens, k, 1, n_accepted_out, out_tokens, nullptr, &rq, nullptr, &spec);
+    return verify_batch(m, "nvl_verify_speculative", n_seqs, KvRef::slab(seq_ids), tokens, k, 1, n_accepted_out, out_tokens, nullptr,
+                        VerifyKind::speculative(rq, spec));
     NVL_CATCH(m)
 }
 
@@ -3598,94 +3461,63 @@ extern "C" int nvl_decode_speculative(nvl_model* target, nvl_model* draft, int n
     if (draft->n_mamba) return fail(m, NVL_ERR_STATE, "nvl_decode_speculative: a Mamba2 draft cannot be rolled back");
     if (n_seqs > draft->opts.max_seqs || n_seqs > draft->opts.max_batch_tokens)
         return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: n_seqs exceeds the draft's max_seqs / max_batch_tokens");
-    const int U = 2 * k + 1;
-    std::vector<int> dslot((size_t)n_seqs), tslot((size_t)n_seqs);
+    const int U = 2 * k + 1, T = std::min(m->cfg.max_seq_len, draft->cfg.max_seq_len);
+    std::vector<int> dslot((size_t)n_seqs), tslot;
+    if ((rc = plan_slab(m, Batch::uniform("nvl_decode_speculative", n_seqs, first_tokens, 1, n_steps), seq_ids, nullptr, tslot, T))) return rc;
     for (int i = 0; i < n_seqs; i++) {
-        auto it = m->seq_slot.find(seq_ids[i]);
         auto id = draft->seq_slot.find(seq_ids[i]);
-        if (it == m->seq_slot.end() || id == draft->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_decode_speculative: sequence has no KV slot on the target or the draft");
-        for (int j = 0; j < i; j++) if (seq_ids[j] == seq_ids[i]) return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: duplicate sequence");
-        tslot[(size_t)i] = it->second; dslot[(size_t)i] = id->second;
-        if (m->slot_len[(size_t)it->second] != draft->slot_len[(size_t)id->second])
+        if (id == draft->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_decode_speculative: sequence has no KV slot on the draft");
+        dslot[(size_t)i] = id->second;
+        if (m->slot_len[(size_t)tslot[(size_t)i]] != draft->slot_len[(size_t)id->second])
             return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: target and draft hold a sequence at different cached lengths");
-        if (m->slot_len[(size_t)it->second] + n_steps > std::min(m->cfg.max_seq_len, draft->cfg.max_seq_len))
-            return fail(m, NVL_ERR_POSITION, "nvl_decode_speculative: position exceeds max_seq_len");
-        if (first_tokens[i] < 0 || first_tokens[i] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: token id out of range");
-        if (history_ptrs[i])       // (the ids are fed to both models)
-            for (int j = 0; j < history_lens[i]; j++)
-                if (history_ptrs[i][j] >= m->V) return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: history id outside the vocabulary");
     }
+    if (!history_in_vocab(m, n_seqs, history_ptrs, history_lens)) return fail(m, NVL_ERR_INVALID, "nvl_decode_speculative: history id outside the vocabulary");
     const SampledReq rq0{params, history_ptrs, history_lens, uniforms};
-    if (const char* why = sampled_check(rq0, n_seqs, first_tokens, 1, n_steps, std::min(m->cfg.max_seq_len, draft->cfg.max_seq_len),
-                                        (int64_t)n_steps * n_seqs * U))
+    if (const char* why = sampled_check(rq0, n_seqs, first_tokens, 1, n_steps, T, (int64_t)n_steps * n_seqs * U))
         return fail(m, NVL_ERR_INVALID, std::string("nvl_decode_speculative: ") + why);
-    std::vector<std::vector<int32_t>> hist((size_t)n_seqs);
-    for (int i = 0; i < n_seqs; i++) hist[(size_t)i].assign(history_ptrs[i], history_ptrs[i] + history_lens[i]);
-    std::vector<int> done((size_t)n_seqs, 0);
+    SpecLoop loop(n_seqs, n_steps);
+    for (int i = 0; i < n_seqs; i++) loop.hist[(size_t)i].assign(history_ptrs[i], history_ptrs[i] + history_lens[i]);
     if (accepted_out) for (int i = 0; i < n_seqs; i++) accepted_out[i] = 0;
-    int passes = 0;
-    std::vector<int64_t> ids; std::vector<int> who, keep; std::vector<int32_t> toks, acc, got, first, dtok, hl; std::vector<float> du, ua, uf;
+    std::vector<int32_t> first, dtok, hl; std::vector<float> du, ua, uf;
     std::vector<const int32_t*> hp;
-    for (;;) {
-        who.clear(); ids.clear(); keep.clear();
-        int k_pass = 0, room = k;
-        for (int i = 0; i < n_seqs; i++) {
-            if (done[(size_t)i] >= n_steps) continue;
-            who.push_back(i); ids.push_back(seq_ids[i]); keep.push_back(n_steps - done[(size_t)i]);
-            k_pass = std::max(k_pass, n_steps - done[(size_t)i] - 1);
-            // the draft runs k_pass + 1 steps: k_pass + 1 more positions and k_pass + 1 more history ids must fit (the history
-            // usually holds one id more than the cache; both are >= 0 here: P + n_steps and history + n_steps fit, checked above)
-            const int T = std::min(m->cfg.max_seq_len, draft->cfg.max_seq_len);
-            room = std::min(room, T - std::max(m->slot_len[(size_t)tslot[(size_t)i]], (int)hist[(size_t)i].size()) - 1);
-        }
-        if (who.empty()) break;
-        k_pass = std::min(k_pass, room);
-        const int na = (int)who.size(), S = 1 + k_pass;
-        toks.assign((size_t)na * S, 0); acc.assign((size_t)na, 0); got.assign((size_t)na * S, -1);
+    // the draft runs k_pass + 1 steps: k_pass + 1 more positions and k_pass + 1 more history ids must fit (the history usually
+    // holds one id more than the cache; both are >= 0 here: P + n_steps and history + n_steps fit, checked above)
+    const auto room = [&](int i) { return T - std::max(m->slot_len[(size_t)tslot[(size_t)i]], (int)loop.hist[(size_t)i].size()) - 1; };
+    while (loop.plan(k, seq_ids, room)) {
+        const int na = loop.na, S = loop.S, k_pass = loop.k_pass;
+        const std::vector<int>& who = loop.who;
         first.resize((size_t)na); hp.resize((size_t)na); hl.resize((size_t)na);
         dtok.assign((size_t)S * na, 0); du.assign((size_t)S * na, 0.f); ua.assign((size_t)na * std::max(k_pass, 1), 0.f); uf.resize((size_t)na);
         for (int a = 0; a < na; a++) {
-            const int i = who[(size_t)a];
-            const float* u = uniforms + ((size_t)passes * n_seqs + i) * U;      // pass t's block of sequence i
-            first[(size_t)a] = hist[(size_t)i].back(); hp[(size_t)a] = hist[(size_t)i].data(); hl[(size_t)a] = (int32_t)hist[(size_t)i].size();
+            const std::vector<int32_t>& h = loop.hist[(size_t)who[(size_t)a]];
+            const float* u = uniforms + ((size_t)loop.passes * n_seqs + who[(size_t)a]) * U;      // pass t's block of sequence i
+            first[(size_t)a] = h.back(); hp[(size_t)a] = h.data(); hl[(size_t)a] = (int32_t)h.size();
             for (int j = 0; j < k_pass; j++) { du[(size_t)j * na + a] = u[j]; ua[(size_t)a * k_pass + j] = u[k + j]; }
             uf[(size_t)a] = u[2 * k];
         }
         // the draft phase: k_pass proposals and the cached row of the last one
-        rc = decode_sampled_impl(draft, "nvl_decode_speculative (draft)", na, ids.data(), first.data(), S, params, hp.data(), hl.data(),
+        rc = decode_sampled_impl(draft, "nvl_decode_speculative (draft)", na, loop.ids.data(), first.data(), S, params, hp.data(), hl.data(),
                                  du.data(), dtok.data(), true);
         if (rc) return fail(m, rc, std::string("nvl_decode_speculative: the draft refused: ") + draft->err);      // (it changed nothing)
-        // a refusal from here on leaves the draft where the target is: this pass is undone, earlier passes stay
-        auto undo_draft = [&] { for (int a = 0; a < na; a++) draft->slot_len[(size_t)dslot[(size_t)who[(size_t)a]]] = m->slot_len[(size_t)tslot[(size_t)who[(size_t)a]]]; };
-        for (int a = 0; a < na; a++) {
-            toks[(size_t)a * S] = first[(size_t)a];
-            for (int j = 0; j < k_pass; j++) toks[(size_t)a * S + 1 + j] = dtok[(size_t)j * na + a];
-        }
+        // the draft's rollback, and what undoes this pass after a refusal (earlier passes stay): the draft goes where the target is
+        auto draft_to_target = [&] { for (int a = 0; a < na; a++) draft->slot_len[(size_t)dslot[(size_t)who[(size_t)a]]] = m->slot_len[(size_t)tslot[(size_t)who[(size_t)a]]]; };
+        for (int a = 0; a < na; a++)
+            for (int j = 0; j < k_pass; j++) loop.toks[(size_t)a * S + 1 + j] = dtok[(size_t)j * na + a];
+        const KvRef kv = KvRef::slab(loop.ids.data());
         if (k_pass > 0) {
-            if ((rc = spec_proposals_check(m, draft, "nvl_decode_speculative", na, ids.data(), toks.data(), k_pass, S))) { undo_draft(); return rc; }
+            if ((rc = spec_proposals_check(m, draft, "nvl_decode_speculative", na, loop.ids.data(), loop.toks.data(), k_pass, S))) { draft_to_target(); return rc; }
             const std::vector<float> u = spec_merge_draws(na, k_pass, ua.data(), uf.data());
-            const SampledReq rq{params, hp.data(), hl.data(), u.data()};
             const SpecReq spec{draft->draft_q, round_up(m->V, 4), 1, na, nullptr};
-            rc = verify_slab(m, "nvl_decode_speculative", na, ids.data(), toks.data(), k_pass, 1, acc.data(), got.data(), keep.data(), &rq, nullptr, &spec);
-        } else {
-            const SampledReq rq{params, hp.data(), hl.data(), uf.data()};
-            rc = verify_slab(m, "nvl_decode_speculative", na, ids.data(), toks.data(), 0, 0, acc.data(), got.data(), keep.data(), &rq);
-        }
-        if (rc) { undo_draft(); return rc; }
-        passes++;
-        for (int a = 0; a < na; a++) {
-            const int i = who[(size_t)a], take = std::min(acc[(size_t)a] + 1, keep[(size_t)a]);
-            for (int j = 0; j < take; j++) {
-                const int32_t t = got[(size_t)a * S + j];
-                out_tokens[(size_t)(done[(size_t)i] + j) * n_seqs + i] = t;
-                hist[(size_t)i].push_back(t);
-            }
-            done[(size_t)i] += take;
-            if (accepted_out) accepted_out[i] += std::min(acc[(size_t)a], take);
-            draft->slot_len[(size_t)dslot[(size_t)i]] = m->slot_len[(size_t)tslot[(size_t)i]];      // the draft's rollback
-        }
+            rc = verify_batch(m, "nvl_decode_speculative", na, kv, loop.toks.data(), k_pass, 1, loop.acc.data(), loop.got.data(), loop.keep.data(),
+                              VerifyKind::speculative({params, hp.data(), hl.data(), u.data()}, spec));
+        } else
+            rc = verify_batch(m, "nvl_decode_speculative", na, kv, loop.toks.data(), 0, 0, loop.acc.data(), loop.got.data(), loop.keep.data(),
+                              VerifyKind::sampled({params, hp.data(), hl.data(), uf.data()}));
+        draft_to_target();
+        if (rc) return rc;
+        loop.emit(out_tokens, accepted_out);
     }
-    if (passes_out) *passes_out = passes;
+    if (passes_out) *passes_out = loop.passes;
     return NVL_OK;
     NVL_CATCH(m)
 }
