@@ -683,6 +683,20 @@ int nvl_op_attention(int device, int precision, const float* q, const float* k, 
  * argument conventions. */
 int nvl_op_attention_mq(int device, const float* q, const float* k, const float* v, int nH, int nKV, int S, int T, int hd,
                         float scale, float* out);
+/* Mamba2Layer.Forward between its two projections (mamba2.go:107-170; mamba.h) through the model's own dispatch: causal
+ * conv + SiLU and softplus(dt), the scan (sequential, or in bf16 the chunked SSD forms that nvl_set_tuning key 30 selects),
+ * gate + RMS norm.  proj [M][EH + conv_dim + nh] (EH = nh x hd, conv_dim = EH + 2 x ng x ss) holds the token rows of
+ * n_seqs sequences back to back, sequence i with seq_len[i] tokens from position seq_pos[i] in state slot seq_slot[i]
+ * (distinct, < n_slots).  conv_w [conv_dim][K]; conv_b, a_log, D, dt_bias, norm_w may be NULL.  state
+ * [n_slots][nh][hd][ss] and tail [n_slots][K-1][conv_dim] (may be NULL) are read and written in place; chain 0 / 1 / 2 is
+ * the conv tail of a chained prefill (mamba.h MambaArgs::chain), non-zero only with n_seqs == 1.  Out: xbc [M][conv_dim],
+ * delta [M][nh], y [M][EH] before gating, normed [M][EH] (bf16: the rounded out_proj operand).  A geometry the kernels do
+ * not cover is NVL_ERR_INVALID, before anything is launched. */
+int nvl_op_mamba_mixer(int device, int precision, const float* proj, int n_seqs, const int32_t* seq_len,
+                       const int32_t* seq_pos, const int32_t* seq_slot, int n_slots, int nh, int hd, int ss, int ng, int K,
+                       const float* conv_w, const float* conv_b, const float* a_log, const float* D, const float* dt_bias,
+                       const float* norm_w, float* state, float* tail, int chain, float* xbc, float* delta, float* y,
+                       float* normed);
 /* 8-bit KV cache.  The device quantizer and read path on an array: codes[i] = e4m3fn(x[i] / scale)
  * (round-to-nearest-even, saturating to +-448, NaN -> NaN code), back[i] = scale * bf16(codes[i]) in fp32. */
 int nvl_op_fp8_kv_roundtrip(int device, const float* x, int64_t n, float scale, uint8_t* codes, float* back);

@@ -51,6 +51,17 @@ struct MambaArgs {
     float* ssd_decay;              // [sequences][max_chunks][nh]
 };
 
+// What the kernels below need of a Mamba2 geometry (nvl_create and nvl_op_mamba_mixer refuse anything else): the
+// sequential scan runs 256 threads = head_dim x SG lane groups with PER = state / SG states per thread, PER one of its
+// four instantiations (a PER between two of them would run the next larger one and walk past the state row); the
+// gate-norm and the SSD staging read four floats at a time; the conv tail keeps at most 7 rows in registers.
+inline bool mamba_geometry_ok(int nh, int hd, int ss, int ng, int K) {
+    if (nh <= 0 || hd <= 0 || ss <= 0 || ng <= 0 || K <= 0 || K > 8) return false;
+    if (256 % hd != 0 || 256 / hd > 64 || ss % (256 / hd) != 0) return false;
+    const int per = ss / (256 / hd);
+    return (per == 4 || per == 8 || per == 16 || per == 32) && ((int64_t)nh * hd) % 64 == 0 && nh % ng == 0;
+}
+
 __device__ __forceinline__ float silu_ref(float x) { return x / (1.0f + __expf(-x)); }
 __device__ __forceinline__ float softplus_ref(float x) { return x > 20.f ? x : log1pf(__expf(x)); }    // mamba2.go:370-376
 
@@ -145,20 +156,23 @@ __global__ __launch_bounds__(256) void mamba_scan_kernel(MambaArgs p) {
 // steps (mamba2.go:256-351 is the sequential statement; this is its algebra).  With a_j = A dt_j, s_t = sum_{j<=t} a_j
 // (inclusive, inside the chunk) and S_in the state entering the chunk:
 //     state_t = exp(s_t) S_in + sum_{j<=t} exp(s_t - s_j) dt_j  u_j (x) B_j
-//     y_t     = exp(s_t) (C_t . S_in) + sum_{j<=t} [exp(s_t - s_j) dt_j (C_t . B_j)] u_j + D u_t
+//     y_t     = exp(s_t) (C_t . S_in) + sum_{j<t} [exp(s_t - s_j) dt_j (C_t . B_j)] u_j + (D + dt_t (C_t . B_t)) u_t
 //     S_out   = exp(s_Q) S_in + sum_j [exp(s_Q - s_j) dt_j u_j] (x) B_j
 // i.e. four products per chunk, all v_mfma_f32_16x16x32_bf16 with fp32 accumulation:
 //     G = C B^T (Q x Q, k = state);  Y_intra = (G o L) U (k = token);  Y_inter = C S_in^T (k = state);  S += (U o w)^T B (k = token)
 // Every decay factor is exp of a NON-POSITIVE fp32 number (s decreases), the state lives in fp32 accumulators across the
-// chunks and is rounded to bf16 only as the Y_inter operand; u, B, C and the masked decay matrix G o L are rounded to bf16 as
-// MFMA operands — the same kind of rounding point the projections around this kernel already have; the
+// chunks and is rounded to bf16 only as the Y_inter operand; u, B, C and the masked decay matrix G o L below its diagonal
+// (j < t) are rounded to bf16 as MFMA operands — the same kind of rounding point the projections around this kernel already
+// have.  A token's own term (j = t) stays in fp32 beside the D skip, from the fp32 rows: D and dt_t (C_t . B_t)
+// can cancel, and a token with little else in y (the first of a short call on a decayed state) would then show their bf16
+// error undiluted (12 % of its largest output in the one-token sequence of tests/test_mamba_ops_gpu.py).  The
 // fp32 parity mode keeps mamba_scan_kernel.  Operands sit in LDS K-contiguous ([row][k], rows padded by 16 bytes: the
 // fragment reads are conflict-free), B and U additionally transposed.  A ragged last chunk runs with dt = 0 for the missing
 // tokens: they neither decay nor feed the state, and their rows are not stored.
 // ------------------------------------------------------------------------------------------
 template <int HD, int SS>
 constexpr int mamba_ssd_lds_bytes() {
-    return 2 * ((64 * (SS + 8)) * 2 + SS * (64 + 8) + 2 * HD * (64 + 8) + 64 * (64 + 8) + HD * (SS + 8)) + 64 * 4 * 3;
+    return 2 * ((64 * (SS + 8)) * 2 + SS * (64 + 8) + 2 * HD * (64 + 8) + 64 * (64 + 8) + HD * (SS + 8)) + 64 * 4 * 4;
 }
 // MODE 0: one workgroup per (sequence, head) walks the chunks in order (the state stays in its accumulators).
 // With few (sequence, head) pairs and long prompts that leaves most of the chip idle, so the chunks can run in parallel:
@@ -184,6 +198,7 @@ __global__ __launch_bounds__(256) void mamba_ssd_kernel(MambaArgs p) {
     float* s_cum = (float*)(Sb + HD * LC);        // [Q] inclusive prefix sums of a_j
     float* s_dt = s_cum + Q;                      // [Q] dt_j
     float* s_w = s_dt + Q;                        // [Q] exp(s_Q - s_j) dt_j
+    float* s_diag = s_w + Q;                      // [Q] C_t . B_t in fp32 (the diagonal of G)
     const int h = blockIdx.x, seq = blockIdx.y;
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int fr = lane & 15, fg = lane >> 4;
@@ -230,7 +245,11 @@ __global__ __launch_bounds__(256) void mamba_ssd_kernel(MambaArgs p) {
         }
         __syncthreads();
         // ---- stage u, B, C of the chunk (fp32 rows of xbc -> bf16, K-contiguous; B and u also transposed) ----
-        for (int i = tid; i < Q * (SS / 4); i += 256) {
+        constexpr int BC_IT = Q * (SS / 4) / 256;
+        float dg[BC_IT];        // this lane's four products of C_t . B_t per pass, reduced after the loads (below)
+#pragma unroll
+        for (int it = 0; it < BC_IT; it++) {
+            const int i = tid + it * 256;
             const int t = i / (SS / 4), q4 = (i - t * (SS / 4)) * 4;
             f32x4 b = f32x4{0.f, 0.f, 0.f, 0.f}, c = b;
             if (t < nv) {
@@ -241,7 +260,23 @@ __global__ __launch_bounds__(256) void mamba_ssd_kernel(MambaArgs p) {
             bf16x4 bb, cc;
 #pragma unroll
             for (int r = 0; r < 4; r++) { bb[r] = (bf16_t)b[r]; cc[r] = (bf16_t)c[r]; if (MODE != 2) Bt[(q4 + r) * LQ + t] = (bf16_t)b[r]; }
-            if (MODE != 1) { *(bf16x4*)(Bs + t * LC + q4) = bb; *(bf16x4*)(Cs + t * LC + q4) = cc; }
+            if (MODE != 1) {
+                *(bf16x4*)(Bs + t * LC + q4) = bb; *(bf16x4*)(Cs + t * LC + q4) = cc;
+                dg[it] = fmaf(b[3], c[3], fmaf(b[2], c[2], fmaf(b[1], c[1], b[0] * c[0])));
+            }
+        }
+        if (MODE != 1) {
+            // the diagonal of G from the fp32 rows (a token's SS / 4 quads sit in neighbouring lanes): a token's own term
+            // dt_t (C_t . B_t) u_t joins D u_t in fp32 — the two can cancel, and a token with little else in y would carry
+            // their bf16 error whole
+#pragma unroll
+            for (int it = 0; it < BC_IT; it++) {
+                float v = dg[it];
+#pragma unroll
+                for (int o = 1; o < SS / 4; o <<= 1) v += __shfl_xor(v, o, 64);
+                const int i = tid + it * 256;
+                if (i % (SS / 4) == 0) s_diag[i / (SS / 4)] = v;
+            }
         }
         for (int i = tid; i < Q * (HD / 4); i += 256) {
             const int t = i / (HD / 4), d4 = (i - t * (HD / 4)) * 4;
@@ -277,7 +312,7 @@ __global__ __launch_bounds__(256) void mamba_ssd_kernel(MambaArgs p) {
 #pragma unroll
                     for (int r = 0; r < 4; r++) {
                         const int t = 16 * tt + 4 * fg + r;
-                        const float v = (j <= t) ? gacc[r] * (__expf(srow[r] - sj) * dj) : 0.f;
+                        const float v = (j < t) ? gacc[r] * (__expf(srow[r] - sj) * dj) : 0.f;      // (the diagonal: fp32, below)
                         Ms[t * LQ + j] = (bf16_t)v;
                     }
                 }
@@ -313,10 +348,11 @@ __global__ __launch_bounds__(256) void mamba_ssd_kernel(MambaArgs p) {
                     const int t = 16 * tt + 4 * fg + r;
                     if (t >= nv) continue;
                     const float es = __expf(s_cum[t]);
+                    const float own = fmaf(s_dt[t], s_diag[t], Dh);      // D + dt_t (C_t . B_t)
                     const float* ur = p.xbc + (int64_t)(t0 + c0 + t) * p.conv_dim + h * HD;
                     float* yr = p.y + (int64_t)(t0 + c0 + t) * p.EH + h * HD;
 #pragma unroll
-                    for (int d = 0; d < DT; d++) yr[16 * d + fr] = yi[d][r] + es * ye[d][r] + Dh * ur[16 * d + fr];
+                    for (int d = 0; d < DT; d++) yr[16 * d + fr] = yi[d][r] + es * ye[d][r] + own * ur[16 * d + fr];
                 }
             }
         }

@@ -291,8 +291,7 @@ extern "C" int nvl_create(const nvl_model_config* cfg, const nvl_runtime_opts* o
             c.mamba_conv_kernel <= 0 || c.mamba_conv_kernel > 8 || mhd <= 0 || mhd * c.mamba_num_heads != eh)
             return fail(nullptr, NVL_ERR_INVALID, "nvl_create: bad Mamba2 dimensions (heads x head_dim must equal expand x hidden)");
         // the scan kernel keeps state_size / (256 / head_dim) states per thread: head_dim | 256, at most 32 states per thread
-        if (256 % mhd != 0 || 256 / mhd > 64 || c.mamba_state_size % (256 / mhd) != 0 || c.mamba_state_size / (256 / mhd) > 32 ||
-            (c.mamba_state_size / (256 / mhd)) % 4 != 0 || eh % 64 != 0 || c.mamba_num_heads % c.mamba_n_groups != 0)
+        if (!mamba_geometry_ok(c.mamba_num_heads, mhd, c.mamba_state_size, c.mamba_n_groups, c.mamba_conv_kernel))
             return fail(nullptr, NVL_ERR_INVALID, "nvl_create: Mamba2 head_dim / state_size not supported by the scan kernel");
         if (tp > 1) return fail(nullptr, NVL_ERR_INVALID, "nvl_create: tensor parallelism does not cover Mamba2 layers");
         if (opts->kv_num_blocks > 0)
@@ -2091,6 +2090,81 @@ void tap_layer(nvl_model* m, int li, int M) {
     NVL_HIP(hipGetLastError());
 }
 
+// Mamba2Layer.Forward between its two projections (mamba2.go:107-170) for the batch `a` describes: conv + softplus (and
+// the tail of a chained prefill), the scan in the form the batch calls for, gate + RMS norm into `out` (the out_proj
+// operand, ActT).  `a` arrives without the chunk-parallel scratch, which is the model's and grows here.  y_pre != NULL
+// (nvl_op_mamba_mixer) receives the scan's y before the gate kernel overwrites it in place.
+void mamba_mixer(nvl_model* m, MambaArgs a, int M, int n_seqs, int max_len, void* out, float* y_pre = nullptr) {
+    const int64_t state_floats = (int64_t)a.nh * a.hd * a.ss;
+    {
+        KScope ks(m, KC_OTHER, 0, KS_MAMBA_CONV, (double)M * (a.P + a.conv_dim + a.nh) * 4.0);
+        hipLaunchKernelGGL(mamba_conv_kernel, dim3(M), dim3(256), 0, m->stream, a);
+        if (a.chain) hipLaunchKernelGGL(mamba_tail_kernel, dim3(n_seqs), dim3(256), 0, m->stream, a);
+        NVL_HIP(hipGetLastError());
+    }
+    {
+        KScope ks(m, KC_OTHER, 2.0 * 3.0 * (double)M * a.EH * a.ss, KS_MAMBA_SCAN,
+                  (double)M * (a.conv_dim + a.nh + a.EH) * 4.0 + 2.0 * n_seqs * (double)state_floats * 4.0);
+        const int per = a.ss / (256 / a.hd);
+        dim3 grid(a.nh, n_seqs);
+        // prefill-sized calls, bf16 mode: the chunked (SSD) form on MFMA — 64 tokens per step instead of one
+        const bool ssd = g_mamba_ssd && !m->f32 && max_len >= 16 && (a.hd == 32 || a.hd == 64) &&
+                         (a.ss == 32 || a.ss == 64 || a.ss == 128) && a.conv_dim % 4 == 0 && a.EH % 4 == 0;
+        // (sequence, head) pairs for fewer than half the CUs and several chunks: the chunks of a sequence in parallel (state
+        // contributions, a short recurrence over the chunks, outputs: three launches; 1 x 2048: 318 -> 90 us per layer) —
+        // with a workgroup per CU already (8 x 512) the extra state traffic loses (86 -> 174 us); scratch capped at 256 MB
+        const int max_chunks = cdiv(max_len, 64);
+        const int64_t z_floats = (int64_t)n_seqs * max_chunks * state_floats;
+        const bool par = ssd && g_mamba_ssd >= 1 && g_mamba_ssd != 2 && max_chunks >= 4 && a.nh * n_seqs < 128 && z_floats * 4 <= (256ll << 20);
+        if (par && z_floats > m->ssd_z_floats) {
+            NVL_HIP(hipStreamSynchronize(m->stream));
+            dfree(m->ssd_z); dfree(m->ssd_decay);
+            m->ssd_z = dmalloc<float>(z_floats); m->ssd_z_floats = z_floats;
+            m->ssd_decay = dmalloc<float>((int64_t)n_seqs * max_chunks * a.nh + 1024);
+            m->ssd_decay_floats = (int64_t)n_seqs * max_chunks * a.nh + 1024;
+        }
+        if (par && (int64_t)n_seqs * max_chunks * a.nh > m->ssd_decay_floats) {
+            NVL_HIP(hipStreamSynchronize(m->stream));
+            dfree(m->ssd_decay);
+            m->ssd_decay_floats = (int64_t)n_seqs * max_chunks * a.nh + 1024;
+            m->ssd_decay = dmalloc<float>(m->ssd_decay_floats);
+        }
+        a.ssd_z = m->ssd_z; a.ssd_decay = m->ssd_decay;
+#define NVL_SSD(HDv, SSv)                                                                                              \
+        do {                                                                                                   \
+            constexpr int lds_ = mamba_ssd_lds_bytes<HDv, SSv>();                                              \
+            if (par) {                                                                                         \
+                dim3 g3(a.nh, n_seqs, max_chunks);                                                             \
+                NVL_LDS_ATTR((mamba_ssd_kernel<HDv, SSv, 1>), lds_);                                           \
+                NVL_LDS_ATTR((mamba_ssd_kernel<HDv, SSv, 2>), lds_);                                           \
+                hipLaunchKernelGGL((mamba_ssd_kernel<HDv, SSv, 1>), g3, dim3(256), lds_, m->stream, a);        \
+                hipLaunchKernelGGL(mamba_ssd_prefix_kernel, dim3(a.nh, n_seqs, cdiv(HDv * SSv, 1024)), dim3(256), 0, m->stream, a, max_chunks, HDv * SSv); \
+                hipLaunchKernelGGL((mamba_ssd_kernel<HDv, SSv, 2>), g3, dim3(256), lds_, m->stream, a);        \
+            } else {                                                                                           \
+                NVL_LDS_ATTR((mamba_ssd_kernel<HDv, SSv, 0>), lds_);                                           \
+                hipLaunchKernelGGL((mamba_ssd_kernel<HDv, SSv, 0>), grid, dim3(256), lds_, m->stream, a);      \
+            }                                                                                                  \
+        } while (0)
+        if (ssd) {
+            if (a.hd == 64) { if (a.ss == 128) NVL_SSD(64, 128); else if (a.ss == 64) NVL_SSD(64, 64); else NVL_SSD(64, 32); }
+            else { if (a.ss == 128) NVL_SSD(32, 128); else if (a.ss == 64) NVL_SSD(32, 64); else NVL_SSD(32, 32); }
+        } else
+#undef NVL_SSD
+        if (per <= 4) hipLaunchKernelGGL(mamba_scan_kernel<4>, grid, dim3(256), 0, m->stream, a);
+        else if (per <= 8) hipLaunchKernelGGL(mamba_scan_kernel<8>, grid, dim3(256), 0, m->stream, a);
+        else if (per <= 16) hipLaunchKernelGGL(mamba_scan_kernel<16>, grid, dim3(256), 0, m->stream, a);
+        else hipLaunchKernelGGL(mamba_scan_kernel<32>, grid, dim3(256), 0, m->stream, a);
+        NVL_HIP(hipGetLastError());
+    }
+    if (y_pre) NVL_HIP(hipMemcpyAsync(y_pre, a.y, (size_t)M * a.EH * 4, hipMemcpyDeviceToDevice, m->stream));
+    {
+        KScope ks(m, KC_OTHER, 0, KS_MAMBA_GATE, (double)M * a.EH * (8.0 + (double)m->wsize));
+        if (m->f32) hipLaunchKernelGGL((mamba_gate_norm_kernel<float>), dim3(M), dim3(256), 0, m->stream, a, (float*)out);
+        else hipLaunchKernelGGL((mamba_gate_norm_kernel<bf16_t>), dim3(M), dim3(256), 0, m->stream, a, (bf16_t*)out);
+        NVL_HIP(hipGetLastError());
+    }
+}
+
 // Enqueue ONE forward pass (embedding ... argmax) on the model's stream for the batch described by the device
 // metadata `md` — no host synchronisation.  Returns the number of logits rows produced.
 // seam: 0 = whole pass; bit 0 = x and layer 0's normed operand are already in place (skip embed + first norm);
@@ -2178,72 +2252,7 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
             a.chain = m->conv_tail ? m->conv_chain : 0;
             a.tail = m->conv_tail ? m->conv_tail + (int64_t)l.mamba_idx * m->conv_tail_layer_stride : nullptr;
             a.tail_slot_stride = m->conv_tail_slot_stride;
-            {
-                KScope ks(m, KC_OTHER, 0, KS_MAMBA_CONV, (double)M * (m->mP + m->mConv + m->m_nh) * 4.0);
-                hipLaunchKernelGGL(mamba_conv_kernel, dim3(M), dim3(256), 0, m->stream, a);
-                if (a.chain) hipLaunchKernelGGL(mamba_tail_kernel, dim3(n_seqs), dim3(256), 0, m->stream, a);
-                NVL_HIP(hipGetLastError());
-            }
-            {
-                KScope ks(m, KC_OTHER, 2.0 * 3.0 * (double)M * m->mEH * m->m_ss, KS_MAMBA_SCAN,
-                          (double)M * (m->mConv + m->m_nh + m->mEH) * 4.0 + 2.0 * n_seqs * (double)m->ssm_layer_stride * 4.0);
-                const int per = m->m_ss / (256 / m->m_hd);
-                dim3 grid(m->m_nh, n_seqs);
-                // prefill-sized calls, bf16 mode: the chunked (SSD) form on MFMA — 64 tokens per step instead of one
-                const bool ssd = g_mamba_ssd && !m->f32 && max_len >= 16 && (m->m_hd == 32 || m->m_hd == 64) &&
-                                 (m->m_ss == 32 || m->m_ss == 64 || m->m_ss == 128) && m->mConv % 4 == 0 && m->mEH % 4 == 0;
-                // (sequence, head) pairs for fewer than half the CUs and several chunks: the chunks of a sequence in parallel (state
-                // contributions, a short recurrence over the chunks, outputs: three launches; 1 x 2048: 318 -> 90 us per layer) —
-                // with a workgroup per CU already (8 x 512) the extra state traffic loses (86 -> 174 us); scratch capped at 256 MB
-                const int max_chunks = cdiv(max_len, 64);
-                const int64_t z_floats = (int64_t)n_seqs * max_chunks * m->m_nh * m->m_hd * m->m_ss;
-                const bool par = ssd && g_mamba_ssd >= 1 && g_mamba_ssd != 2 && max_chunks >= 4 && m->m_nh * n_seqs < 128 && z_floats * 4 <= (256ll << 20);
-                if (par && z_floats > m->ssd_z_floats) {
-                    NVL_HIP(hipStreamSynchronize(m->stream));
-                    dfree(m->ssd_z); dfree(m->ssd_decay);
-                    m->ssd_z = dmalloc<float>(z_floats); m->ssd_z_floats = z_floats;
-                    m->ssd_decay = dmalloc<float>((int64_t)n_seqs * max_chunks * m->m_nh + 1024);
-                    m->ssd_decay_floats = (int64_t)n_seqs * max_chunks * m->m_nh + 1024;
-                }
-                if (par && (int64_t)n_seqs * max_chunks * m->m_nh > m->ssd_decay_floats) {
-                    NVL_HIP(hipStreamSynchronize(m->stream));
-                    dfree(m->ssd_decay);
-                    m->ssd_decay_floats = (int64_t)n_seqs * max_chunks * m->m_nh + 1024;
-                    m->ssd_decay = dmalloc<float>(m->ssd_decay_floats);
-                }
-                a.ssd_z = m->ssd_z; a.ssd_decay = m->ssd_decay;
-#define NVL_SSD(HDv, SSv)                                                                                              \
-                do {                                                                                                   \
-                    constexpr int lds_ = mamba_ssd_lds_bytes<HDv, SSv>();                                              \
-                    if (par) {                                                                                         \
-                        dim3 g3(m->m_nh, n_seqs, max_chunks);                                                          \
-                        NVL_LDS_ATTR((mamba_ssd_kernel<HDv, SSv, 1>), lds_);                                           \
-                        NVL_LDS_ATTR((mamba_ssd_kernel<HDv, SSv, 2>), lds_);                                           \
-                        hipLaunchKernelGGL((mamba_ssd_kernel<HDv, SSv, 1>), g3, dim3(256), lds_, m->stream, a);        \
-                        hipLaunchKernelGGL(mamba_ssd_prefix_kernel, dim3(m->m_nh, n_seqs, cdiv(HDv * SSv, 1024)), dim3(256), 0, m->stream, a, max_chunks, HDv * SSv); \
-                        hipLaunchKernelGGL((mamba_ssd_kernel<HDv, SSv, 2>), g3, dim3(256), lds_, m->stream, a);        \
-                    } else {                                                                                           \
-                        NVL_LDS_ATTR((mamba_ssd_kernel<HDv, SSv, 0>), lds_);                                           \
-                        hipLaunchKernelGGL((mamba_ssd_kernel<HDv, SSv, 0>), grid, dim3(256), lds_, m->stream, a);      \
-                    }                                                                                                  \
-                } while (0)
-                if (ssd) {
-                    if (m->m_hd == 64) { if (m->m_ss == 128) NVL_SSD(64, 128); else if (m->m_ss == 64) NVL_SSD(64, 64); else NVL_SSD(64, 32); }
-                    else { if (m->m_ss == 128) NVL_SSD(32, 128); else if (m->m_ss == 64) NVL_SSD(32, 64); else NVL_SSD(32, 32); }
-                } else
-#undef NVL_SSD
-                if (per <= 4) hipLaunchKernelGGL(mamba_scan_kernel<4>, grid, dim3(256), 0, m->stream, a);
-                else if (per <= 8) hipLaunchKernelGGL(mamba_scan_kernel<8>, grid, dim3(256), 0, m->stream, a);
-                else if (per <= 16) hipLaunchKernelGGL(mamba_scan_kernel<16>, grid, dim3(256), 0, m->stream, a);
-                else hipLaunchKernelGGL(mamba_scan_kernel<32>, grid, dim3(256), 0, m->stream, a);
-                NVL_HIP(hipGetLastError());
-            }
-            {
-                KScope ks(m, KC_OTHER, 0, KS_MAMBA_GATE, (double)M * m->mEH * (8.0 + (double)m->wsize));
-                if (m->f32) hipLaunchKernelGGL((mamba_gate_norm_kernel<float>), dim3(M), dim3(256), 0, m->stream, a, (float*)m->myn);
-                else hipLaunchKernelGGL((mamba_gate_norm_kernel<bf16_t>), dim3(M), dim3(256), 0, m->stream, a, (bf16_t*)m->myn);
-                NVL_HIP(hipGetLastError());
-            }
+            mamba_mixer(m, a, M, n_seqs, max_len, m->myn);
             m->site = KS_MAMBA_OUT;
             resid_gemm(m, m->myn, m->mEH, l.t[NVL_T_MAMBA_OUT_PROJ].p, nullptr, m->resid_alpha, M, H, m->mEH);
             norm(m, m->x, nullptr, l.t[NVL_T_FFN_NORM_W], l.t[NVL_T_FFN_NORM_B], m->xn, M);

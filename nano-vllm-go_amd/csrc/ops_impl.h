@@ -275,6 +275,89 @@ extern "C" int nvl_op_attention_mq(int device, const float* q, const float* k, c
     OP_CATCH
 }
 
+// Mamba2Layer.Forward between its two projections (mamba2.go:107-170) through the model's own dispatch (mamba_mixer):
+// a ragged batch of n_seqs sequences, token rows back to back in proj, sequence i at position seq_pos[i] in state slot
+// seq_slot[i].  Every stage's output comes back: xbc, delta, y before gating, and the gated + normed rows (bf16 mode:
+// un-permuted from the fragment-major out_proj operand).  state / tail are read and written in place.
+extern "C" int nvl_op_mamba_mixer(int device, int precision, const float* proj, int n_seqs, const int32_t* seq_len,
+                                  const int32_t* seq_pos, const int32_t* seq_slot, int n_slots, int nh, int hd, int ss, int ng, int K,
+                                  const float* conv_w, const float* conv_b, const float* a_log, const float* D, const float* dt_bias,
+                                  const float* norm_w, float* state, float* tail, int chain, float* xbc, float* delta, float* y,
+                                  float* normed) {
+    if (!proj || !seq_len || !seq_pos || !seq_slot || !conv_w || !state || !xbc || !delta || !y || !normed || n_seqs <= 0 || n_slots <= 0)
+        return op_fail("nvl_op_mamba_mixer: bad arguments");
+    if (!mamba_geometry_ok(nh, hd, ss, ng, K)) return op_fail("nvl_op_mamba_mixer: head_dim / state_size / groups / conv kernel not supported by the kernels");
+    if (chain < 0 || chain > 2 || (chain && (n_seqs != 1 || (K > 1 && !tail))))
+        return op_fail("nvl_op_mamba_mixer: a chained prefill is one sequence with a tail");
+    int64_t M64 = 0;
+    int max_len = 0;
+    std::vector<char> used((size_t)n_slots, 0);
+    for (int i = 0; i < n_seqs; i++) {
+        if (seq_len[i] <= 0 || seq_pos[i] < 0 || seq_slot[i] < 0 || seq_slot[i] >= n_slots || used[(size_t)seq_slot[i]])
+            return op_fail("nvl_op_mamba_mixer: bad sequence length / position / slot");
+        used[(size_t)seq_slot[i]] = 1;
+        M64 += seq_len[i]; max_len = std::max(max_len, (int)seq_len[i]);
+    }
+    if (M64 > (1 << 20)) return op_fail("nvl_op_mamba_mixer: too many tokens");
+    OP_TRY
+    OpCtx cx(device, precision);
+    nvl_model& m = cx.m;
+    struct Scratch {      // the chunk-parallel scratch mamba_mixer grows on the model
+        nvl_model& m;
+        ~Scratch() { (void)hipStreamSynchronize(m.stream); dfree(m.ssd_z); dfree(m.ssd_decay); m.ssd_z = m.ssd_decay = nullptr; }
+    } scratch{m};
+    const int M = (int)M64, EH = nh * hd, conv_dim = EH + 2 * ng * ss, P = EH + conv_dim + nh;
+    std::vector<int32_t> meta((size_t)(4 * n_seqs + 2 * M));
+    int32_t *h_start = meta.data(), *h_len = h_start + n_seqs, *h_pos = h_len + n_seqs, *h_slot = h_pos + n_seqs,
+            *h_tpos = h_slot + n_seqs, *h_tseq = h_tpos + M;
+    for (int i = 0, t = 0; i < n_seqs; i++) {
+        h_start[i] = t; h_len[i] = seq_len[i]; h_pos[i] = seq_pos[i]; h_slot[i] = seq_slot[i];
+        for (int j = 0; j < seq_len[i]; j++, t++) { h_tpos[t] = seq_pos[i] + j; h_tseq[t] = i; }
+    }
+    int32_t* dmeta = (int32_t*)cx.alloc((int64_t)meta.size() * 4);
+    NVL_HIP(hipMemcpyAsync(dmeta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, m.stream));
+    MambaArgs a{};
+    a.proj = cx.up_f32(proj, (int64_t)M * P); a.P = P; a.EH = EH; a.conv_dim = conv_dim; a.nh = nh; a.hd = hd; a.ss = ss; a.ng = ng; a.K = K;
+    a.conv_w = cx.up_f32(conv_w, (int64_t)conv_dim * K);
+    a.conv_b = conv_b ? cx.up_f32(conv_b, conv_dim) : nullptr;
+    a.a_log = a_log ? cx.up_f32(a_log, nh) : nullptr;
+    a.Dskip = D ? cx.up_f32(D, nh) : nullptr;
+    a.dt_bias = dt_bias ? cx.up_f32(dt_bias, nh) : nullptr;
+    a.norm_w = norm_w ? cx.up_f32(norm_w, EH) : nullptr;
+    a.xbc = (float*)cx.alloc((int64_t)M * conv_dim * 4); a.delta = (float*)cx.alloc((int64_t)M * nh * 4); a.y = (float*)cx.alloc((int64_t)M * EH * 4);
+    const int64_t state_floats = (int64_t)nh * hd * ss, tail_floats = (int64_t)(K - 1) * conv_dim;
+    a.state = cx.up_f32(state, state_floats * n_slots); a.state_slot_stride = state_floats;
+    a.seq_tok_start = dmeta; a.seq_len = dmeta + n_seqs; a.seq_pos = dmeta + 2 * n_seqs; a.seq_slot = dmeta + 3 * n_seqs;
+    a.tok_pos = dmeta + 4 * n_seqs; a.tok_seq = a.tok_pos + M;
+    const bool have_tail = tail && K > 1;      // (as the model: no tail buffer, no chain)
+    a.tail = have_tail ? cx.up_f32(tail, tail_floats * n_slots) : nullptr; a.tail_slot_stride = tail_floats;
+    a.chain = have_tail ? chain : 0;
+    float* y_pre = (float*)cx.alloc((int64_t)M * EH * 4);
+    const int64_t Mp = round_up(M, 64);
+    void* out = cx.alloc(Mp * EH * (int64_t)m.wsize);
+    NVL_HIP(hipMemsetAsync(out, 0, (size_t)(Mp * EH) * m.wsize, m.stream));
+    mamba_mixer(&m, a, M, n_seqs, max_len, out, y_pre);
+    cx.down(xbc, a.xbc, (int64_t)M * conv_dim);
+    cx.down(delta, a.delta, (int64_t)M * nh);
+    cx.down(y, y_pre, (int64_t)M * EH);
+    cx.down(state, a.state, state_floats * n_slots);
+    if (have_tail) cx.down(tail, a.tail, tail_floats * n_slots);
+    if (m.f32) {
+        cx.down(normed, out, (int64_t)M * EH);
+    } else {
+        std::vector<uint16_t> ob((size_t)(Mp * EH));
+        NVL_HIP(hipMemcpyAsync(ob.data(), out, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
+        NVL_HIP(hipStreamSynchronize(m.stream));
+        for (int64_t r = 0; r < M; r++)       // the kernel wrote the out_proj GEMM's fragment-major operand
+            for (int64_t c = 0; c < EH; c++) {
+                uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, EH)]) << 16;
+                memcpy(&normed[(size_t)(r * EH + c)], &u, 4);
+            }
+    }
+    return NVL_OK;
+    OP_CATCH
+}
+
 // The one-weight model of the quantized matmul ops: W [K][N] ([in, out], as nvl_op_matmul) quantized by the upload quantizer
 // of format wf into t and registered for gemm(), a tile-path scratch of at most scratch_rows weight rows, then
 // C = bf16(A) · W~^T through the model's dispatch into c [M][N].

@@ -82,6 +82,30 @@ def attention_mq(q, k, v, scale=0.0, device=0):   # the multi-position decode at
     return out
 
 
+def mamba_mixer(proj, seq_len, seq_pos, seq_slot, state, nh, hd, ss, ng, K, conv_w, conv_b=None, a_log=None, D=None,
+                dt_bias=None, norm_w=None, tail=None, chain=0, precision="bf16", device=0):   # mamba2.go:107-170
+    """The Mamba2 mixer between its projections through the model's dispatch (csrc/mamba.h): proj [M][EH + conv_dim + nh],
+    sequence i = seq_len[i] rows from position seq_pos[i] in slot seq_slot[i] of state [n_slots][nh][hd][ss] (and of tail
+    [n_slots][K-1][conv_dim]).  -> dict(xbc, delta, y (before gating), normed, state, tail); state / tail are new arrays."""
+    proj, conv_w = _f(proj), _f(conv_w)
+    opt = [None if v is None else _f(v) for v in (conv_b, a_log, D, dt_bias, norm_w)]
+    sl, sp, so = (np.ascontiguousarray(v, dtype=np.int32) for v in (seq_len, seq_pos, seq_slot))
+    state = _f(state).copy()
+    tail = None if tail is None else _f(tail).copy()
+    M, EH, conv_dim = proj.shape[0], nh * hd, nh * hd + 2 * ng * ss
+    if proj.shape != (M, EH + conv_dim + nh) or conv_w.shape != (conv_dim, K) or M != int(sl.sum()) or not sl.size == sp.size == so.size:
+        raise ValueError("mamba_mixer: shapes do not match the geometry")
+    if state.ndim != 4 or state.shape[1:] != (nh, hd, ss) or (tail is not None and tail.shape != (state.shape[0], K - 1, conv_dim)):
+        raise ValueError("mamba_mixer: state / tail shape")
+    out = dict(xbc=np.empty((M, conv_dim), np.float32), delta=np.empty((M, nh), np.float32), y=np.empty((M, EH), np.float32),
+               normed=np.empty((M, EH), np.float32))
+    L.check(L.lib().nvl_op_mamba_mixer(device, L.PRECISION[precision], _p(proj), sl.size, _p(sl), _p(sp), _p(so), state.shape[0],
+                                       nh, hd, ss, ng, K, _p(conv_w), *[_p(v) for v in opt], _p(state), _p(tail), chain,
+                                       _p(out["xbc"]), _p(out["delta"]), _p(out["y"]), _p(out["normed"])))
+    out["state"], out["tail"] = state, tail
+    return out
+
+
 def lookup_draft(history, k, ngram=3):
     """nvl_lookup_draft (host only): -> (draft [k], number of real draft tokens)."""
     h = np.ascontiguousarray(history, dtype=np.int32)

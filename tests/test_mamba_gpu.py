@@ -210,6 +210,34 @@ def test_chunked_ssd_scan_matches_oracle_and_the_sequential_scan(gpu, oracle, va
         assert rel_err(got[ssd][0], got[0][0]) <= 6e-3 and rel_err(got[ssd][1], got[0][1]) <= 6e-3
 
 
+def test_chunk_parallel_ssd_scan_continues_a_carried_state(gpu, oracle):
+    """Two prefill-sized calls on ONE sequence, 300 tokens and then 260 more, with key 30 = 1: both are five chunks on
+    8 heads, so both take the chunk-parallel three-launch form, the second entering it on the state the first left
+    (seq_pos > 0) — through nvl_forward, against the oracle's two Forward calls."""
+    cfg = gpu.synth.tiny_config("granite_hybrid", **dict(VARIANTS[0], max_seq_len=640))
+    w = gpu.synth.make_weights(cfg, seed=17, scale=0.05)
+    r = np.random.default_rng(61)
+    first, second = (r.integers(0, cfg["vocab_size"], n).tolist() for n in (300, 260))
+    om = oracle.OracleModel(cfg, w)
+    kv = om.new_cache()
+    want1 = om.forward_with_cache(first, kv, 0)[-1]
+    want2 = om.forward_with_cache(second, kv, 300)[-1]
+    states = [om.mamba_state(li) for li, k in enumerate(cfg["hybrid_layers"]) if k == "mamba"]
+    old = gpu.lib().nvl_set_tuning(30, 1)
+    try:
+        hm = gpu.HipTransformerModel(cfg, w, precision="bf16", max_seqs=2, max_batch_tokens=512)
+        hm.seq_reset(1)
+        got1, _ = hm.forward_batch([1], [first], [0])
+        got2, _ = hm.forward_batch([1], [second], [300])
+        st = [hm.get_mamba_state(1, li) for li, k in enumerate(cfg["hybrid_layers"]) if k == "mamba"]
+        hm.close()
+    finally:
+        gpu.lib().nvl_set_tuning(30, old)
+    assert rel_err(got1[0], want1) <= TOL["bf16"] and rel_err(got2[0], want2) <= TOL["bf16"]
+    for x, y in zip(st, states):
+        assert rel_err(x, y) <= TOL["bf16"]
+
+
 def test_hybrid_is_refused_where_it_cannot_work(gpu):
     cfg = gpu.synth.tiny_config("granite_hybrid")
     with pytest.raises(gpu.NvlError):                       # per-sequence state lives in KV slots: no paged mode
@@ -219,3 +247,6 @@ def test_hybrid_is_refused_where_it_cannot_work(gpu):
     bad = dict(cfg, mamba_num_heads=3)                      # heads x head_dim != expand x hidden
     with pytest.raises(gpu.NvlError):
         gpu.HipTransformerModel(bad, None)
+    odd = dict(cfg, mamba_state_size=96)                    # 96 states over 8 lane groups = 12 per thread: no such scan instantiation
+    with pytest.raises(gpu.NvlError):
+        gpu.HipTransformerModel(odd, None)
