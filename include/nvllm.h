@@ -249,6 +249,35 @@ int nvl_set_mx_head_dtype(nvl_model* m, int dtype);
  * E * out, cols = in, codes [E * out][in / 2], scales [E * out][in / 32] (expert e's rows e*out .. e*out + out - 1). */
 int nvl_upload_tensor_mxfp4(nvl_model* m, int kind, int layer, const uint8_t* codes, const uint8_t* scales, int64_t rows,
                             int64_t cols, int layout);
+/* INT4 group-quantized storage of the projection weights: the W4A16 format of AWQ / GPTQ checkpoints.
+ * The reference keeps every weight fp32 (generic_loader.go:398-403, loadTensorFromData); this is the library's own opt-in,
+ * reached only through this call. */
+enum {
+    NVL_GQ_NONE = 0,       /* no group-quantized storage: today's behaviour                                                */
+    NVL_GQ_UINT4 = 1       /* WQ/WK/WV/WKV/WO/W1/W2 as unsigned 4-bit codes with one fp16 scale s and one 4-bit zero point z per
+                            * group of group_size (32, 64 or 128) consecutive input features of one output row; the input width
+                            * must be a multiple of it.  Quantizer, per group, in fp32 with correctly rounded division and
+                            * round-half-even: lo = min(0, min w), hi = max(0, max w), r = hi - lo; r == 0: s = 1, z = 0, q = 0;
+                            * else s = fp16_rne(r / 15) (2^-24 if that rounds to 0), z = clamp(rint(-lo / s), 0, 15),
+                            * q = clamp(rint(w / s) + z, 0, 15).  Every path computes with W~ = bf16_rne(fp32(s) * (q - z))
+                            * (the product is exact in fp32: one rounding); nvl_get_weight returns W~.  nvl_stats.weight_bytes
+                            * counts, per stored row (rows are padded to the weight row tile), in / 2 bytes of codes and
+                            * 4 bytes per group: one 32-bit word {fp16 s, z}.  The LM head, both embeddings, the router, the
+                            * MoE experts and the Mamba2 projections stay bf16, as AWQ / GPTQ checkpoints keep them fp16. */
+};
+/* After nvl_create, before the first 2-D upload (else NVL_ERR_STATE).  NVL_ERR_INVALID for a NULL model, an unknown dtype, a
+ * group_size outside {32, 64, 128}, and for NVL_GQ_UINT4 with f32 precision, tensor parallelism, NVL_W_FP8_E4M3 or
+ * NVL_MX_FP4_E2M1 already set (each of those two setters in turn refuses once NVL_GQ_UINT4 is set).  In this mode
+ * nvl_upload_tensor quantizes the covered kinds from F32 / BF16 / F16 in either layout (tensor.go:62-88 keeps them fp32) and
+ * refuses a non-finite weight and a group with r / 15 > 65504. */
+int nvl_set_gq_weight_dtype(nvl_model* m, int dtype, int group_size);
+/* Pre-quantized INT4 weight, taken as it is (the loader's path for .qweight / .qzeros / .scales; generic_loader.go:398-403
+ * reads fp32 only): codes [rows][cols/2], two per byte with the even input feature in the low nibble; scales
+ * [rows][cols/group_size] as fp16 bit patterns; zeros [rows][cols/group_size] with values 0..15; all in [out, in] order
+ * (layout must be NVL_LAYOUT_OUT_IN).  NVL_ERR_INVALID for a kind this model does not store this way, a shape mismatch,
+ * cols % group_size != 0, a zero above 15, or a scale that is NaN, infinite or <= 0. */
+int nvl_upload_tensor_int4(nvl_model* m, int kind, int layer, const uint8_t* codes, const uint16_t* scales, const uint8_t* zeros,
+                           int64_t rows, int64_t cols, int layout);
 
 /* ---- lifecycle ---- */
 
@@ -714,6 +743,12 @@ int nvl_op_matmul_fp8w(int device, const float* a, const float* w, int M, int N,
  * codes_out [N][K/2] and scales_out [N][K/32] (either may be NULL) return the codes in nvl_upload_tensor_mxfp4's packing. */
 int nvl_op_matmul_mxfp4w(int device, const float* a, const float* w, int M, int N, int K, float* c, uint8_t* codes_out,
                          uint8_t* scales_out);
+/* INT4 group-quantized weights (NVL_GQ_UINT4; the reference multiplies fp32 weights, tensor.go:62-88): as nvl_op_matmul_mxfp4w —
+ * w [K][N] quantized by the upload quantizer with this group_size, c = bf16(a) · W~ through the model's own dispatch.
+ * K % 64 == 0 and K % group_size == 0.  codes_out [N][K/2], scales_out [N][K/group_size] (fp16 bits) and zeros_out
+ * [N][K/group_size] (any may be NULL) return the quantizer's result in nvl_upload_tensor_int4's packing. */
+int nvl_op_matmul_int4w(int device, const float* a, const float* w, int M, int N, int K, int group_size, float* c,
+                        uint8_t* codes_out, uint16_t* scales_out, uint8_t* zeros_out);
 /* 8-bit weights and activations (NVL_ACT_FP8_E4M3): as nvl_op_matmul_fp8w, through the model's dispatch in W8A8 mode.  M
  * selects the decode form (bf16(a) · W~, bit-identical to nvl_op_matmul_fp8w) or the tile form, where bf16(a) is quantized
  * per row and c = (sum_k e4m3(q_a) e4m3(q_w)) * s_a[m] * s_w[n].  a_codes_out [M][K] / a_scales_out [M] (either may be NULL)

@@ -37,6 +37,8 @@ WEIGHT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                # NVL_W_* (nvl_set_weig
 MX_WEIGHT_DTYPE = {"none": 0, "fp4_e2m1": 1}             # NVL_MX_* (nvl_set_mx_weight_dtype)
 MX_EXPERT_DTYPE = {"none": 0, "fp4_e2m1": 1}             # NVL_MXE_* (nvl_set_mx_expert_dtype)
 MX_HEAD_DTYPE = {"none": 0, "fp4_e2m1": 1}               # NVL_MXH_* (nvl_set_mx_head_dtype)
+GQ_WEIGHT_DTYPE = {"none": 0, "uint4": 1}                # NVL_GQ_* (nvl_set_gq_weight_dtype)
+GQ_GROUP_SIZES = (32, 64, 128)
 ACT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                   # NVL_ACT_AUTO / NVL_ACT_FP8_E4M3 (nvl_set_act_dtype)
 EXPERT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                # NVL_EXPERT_AUTO / NVL_EXPERT_FP8_E4M3 (nvl_set_expert_dtype)
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
@@ -188,6 +190,9 @@ def lib():
     L.nvl_set_mx_head_dtype.argtypes = [vp, C.c_int]
     L.nvl_upload_tensor_mxfp4.argtypes = [vp, C.c_int, C.c_int, vp, vp, i64, i64, C.c_int]
     L.nvl_op_matmul_mxfp4w.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
+    L.nvl_set_gq_weight_dtype.argtypes = [vp, C.c_int, C.c_int]
+    L.nvl_upload_tensor_int4.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, i64, i64, C.c_int]
+    L.nvl_op_matmul_int4w.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.nvl_set_expert_dtype.argtypes = [vp, C.c_int]
     L.nvl_op_matmul_w8a8.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.nvl_op_act_quant_fp8.argtypes = [C.c_int, vp, C.c_int, C.c_int, C.c_int, vp, vp]

@@ -641,7 +641,7 @@ __device__ __forceinline__ bf16x8 w8_frag(u32x2 c, float s) {
     return o;
 }
 // weight formats of the decode bodies below (gemm_skinny_body / gemm_skinny_wide_body)
-enum { WF_BF16 = 0, WF_FP8 = 1, WF_MXFP4 = 2 };
+enum { WF_BF16 = 0, WF_FP8 = 1, WF_MXFP4 = 2, WF_INT4 = 3 };
 // MXFP4 (w4.h): eight e2m1 codes of one weight row (4 bytes, even k in the low nibble) and the e8m0 byte E of
 // their 32-k block -> the bf16 MFMA fragment of W~ = +-grid[q] * 2^(E - 127).  2^(E - 127) is the fp32 with exponent field E
 // (E in [7, 252]: a normal number), and the product is exact in bf16: v_cvt_scalef32_pk_bf16_fp4 rounds nothing.
@@ -651,6 +651,33 @@ __device__ __forceinline__ bf16x8 w4_frag(uint32_t c, uint32_t E) {
     const bf16x2_t a = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, s, 0), b = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, s, 1),
                    d = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, s, 2), e = __builtin_amdgcn_cvt_scalef32_pk_bf16_fp4(c, s, 3);
     return bf16x8{a[0], a[1], b[0], b[1], d[0], d[1], e[0], e[1]};
+}
+
+// INT4 group-quantized (w4g.h): eight unsigned 4-bit codes of one weight row (4 bytes, even k in the low nibble)
+// and the word of their group, {fp16 scale s in bits 0-15, zero point z in bits 16-19} -> the bf16 MFMA fragment of
+// W~ = bf16_rne(fp32(s) * (q - z)).  The even and the odd codes are masked into the bytes of two registers, a byte converts
+// to fp32 in one instruction (v_cvt_f32_ubyteN), and fma(q, s, -(z * s)) is s * (q - z) exactly: q * s and z * s are exact
+// in fp32 (4 x 11 bits) and so is their difference (5 x 11 bits), so the fma's single rounding rounds nothing;
+// v_cvt_pk_bf16_f32 then rounds once, to nearest even.  2.5 VALU instructions per weight.
+__device__ __forceinline__ bf16x8 w4g_frag(uint32_t c, uint32_t gw) {
+    typedef __attribute__((ext_vector_type(2))) __bf16 bf16x2_t;
+    typedef __attribute__((ext_vector_type(4))) uint32_t u32x4_t;
+    const float s = (float)__builtin_bit_cast(_Float16, (uint16_t)gw);
+    const float nzs = -((float)((gw >> 16) & 15u) * s);
+    const uint32_t ev = c & 0x0f0f0f0fu, od = (c >> 4) & 0x0f0f0f0fu;     // codes 0, 2, 4, 6 / 1, 3, 5, 7, one per byte
+    u32x4_t o;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const bf16x2_t pr = {(__bf16)__builtin_fmaf((float)((ev >> (8 * j)) & 0xffu), s, nzs),
+                             (__bf16)__builtin_fmaf((float)((od >> (8 * j)) & 0xffu), s, nzs)};
+        o[j] = __builtin_bit_cast(uint32_t, pr);
+    }
+    return __builtin_bit_cast(bf16x8, o);
+}
+// the fragment of a 4-bit format from its two raw registers {codes, e8m0 byte | group word}
+template <int WF>
+__device__ __forceinline__ bf16x8 q4_frag(uint32_t c, uint32_t e) {
+    if constexpr (WF == WF_INT4) return w4g_frag(c, e); else return w4_frag(c, e);
 }
 
 // m_passes > 1: block id -> (weight block, 64-row activation group).  Ids that differ by 8 share an XCD and are
@@ -891,9 +918,11 @@ __global__ __launch_bounds__(1024) void gemm_skinny_bf16_kernel(GemmArgs p) {
 // kernels are kept byte-identical in the device assembly.
 // WF = WF_MXFP4 (w4.h): the codes are nibble-packed in the same fragment order (a lane loads 4 bytes per k-step, a 16-row x
 // 32-k block is 256 bytes) and w_scale points at the e8m0 bytes, [16-row tile][k-step][16 rows]: one byte per weight fragment.
+// WF = WF_INT4 (w4g.h): the codes as MXFP4 stores them; w_scale points at the group words, [16-row tile][K/g][16 rows], and
+// gshift = log2(g / 32): the word of k-step s is that of group s >> gshift.
 template <int MT, int NTW, int U, int EPI, typename OutT, bool PASSES, bool MOE, bool HALF, int WF>
-__device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scale) {
-    constexpr bool W8 = WF == WF_FP8, MX = WF == WF_MXFP4;
+__device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scale, int gshift = 0) {
+    constexpr bool W8 = WF == WF_FP8, GQ = WF == WF_INT4, MX = WF == WF_MXFP4 || GQ;     // (MX: the two-register 4-bit forms)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* red = (f32x4*)smem;                       // [NTW][ksplit][MT][64]
     const int swg = blockIdx.y * gridDim.x + blockIdx.x;
@@ -964,12 +993,18 @@ __device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scal
     // MXFP4: this lane's 4 code bytes and its row's scale byte of k-step ks0 (then +256 / +16 bytes per k-step)
     // (computed in the MXFP4 instantiations only: the fp8 ones keep their device assembly)
     const uint8_t* mq = MX ? (const uint8_t*)p.W + (((int64_t)(nt0 + tile) * (p.K >> 5) + ks0) * 64 + lane) * 4 : nullptr;
-    const uint8_t* me = MX ? (const uint8_t*)w_scale + ((int64_t)(nt0 + tile) * (p.K >> 5) + ks0) * 16 + fr : nullptr;
-    auto mxraw = [&](int64_t s) -> u32x2 {     // {codes, E}
-        return u32x2{weight_load4<PASSES>((const uint32_t*)(mq + s * 256)), (uint32_t)weight_load1<PASSES>(me + s * 16)};
+    const uint8_t* me = (MX && !GQ) ? (const uint8_t*)w_scale + ((int64_t)(nt0 + tile) * (p.K >> 5) + ks0) * 16 + fr : nullptr;
+    // INT4: the group words of this wave's tile ([K/g][16] words).  Tile and first k-step are wave-uniform: said so, the tile's
+    // base stays in scalar registers and a load's address is that base + one 32-bit lane offset (a 64-bit lane address per
+    // load in flight spilled 38 registers in the 64-row-group instantiations)
+    const uint32_t* gw = GQ ? (const uint32_t*)w_scale + (int64_t)__builtin_amdgcn_readfirstlane(nt0 + tile) * ((p.K >> 5) >> gshift) * 16 : nullptr;
+    const int gks0 = GQ ? __builtin_amdgcn_readfirstlane(ks0) : 0;
+    auto mxraw = [&](int64_t s) -> u32x2 {     // {codes, E} / {codes, group word}
+        if constexpr (GQ) return u32x2{weight_load4<PASSES>((const uint32_t*)(mq + s * 256)), weight_load4<PASSES>(gw + (uint32_t)((((gks0 + (int)s) >> gshift) << 4) + fr))};
+        else return u32x2{weight_load4<PASSES>((const uint32_t*)(mq + s * 256)), (uint32_t)weight_load1<PASSES>(me + s * 16)};
     };
     auto wload = [&](int64_t s) -> bf16x8 {
-        if constexpr (MX) { const u32x2 r = mxraw(s); return w4_frag(r[0], r[1]); }
+        if constexpr (MX) { const u32x2 r = mxraw(s); return q4_frag<WF>(r[0], r[1]); }
         else return w8_frag(weight_load8<PASSES>((const u32x2*)(wq + s * 512)), wsc);
     };
     // W8: a block's registers hold the raw codes; they are converted where the MFMAs consume them (comp_blk).  Converting
@@ -981,7 +1016,7 @@ __device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scal
     constexpr bool RAW = (W8 && MT <= 2) || MX;
     typedef typename std::conditional<RAW, u32x2, bf16x8>::type WReg;
     auto wfrag = [&](const WReg& w) -> bf16x8 {
-        if constexpr (RAW && MX) return w4_frag(w[0], w[1]);
+        if constexpr (RAW && MX) return q4_frag<WF>(w[0], w[1]);
         else if constexpr (RAW) return w8_frag(w, wsc);
         else return w;
     };
@@ -1008,7 +1043,7 @@ __device__ __forceinline__ void gemm_skinny_body(GemmArgs p, const float* w_scal
     auto load_blk = [&](WReg (&w)[U], bf16x8 (&x)[U][MT], int b) {
 #pragma unroll
         for (int u = 0; u < U; u++) {
-            if constexpr (RAW && MX) w[u] = (!HALF || w_live) ? mxraw((int64_t)(b * U + u)) : u32x2{0u, 127u};
+            if constexpr (RAW && MX) w[u] = (!HALF || w_live) ? mxraw((int64_t)(b * U + u)) : u32x2{0u, GQ ? 0x3c00u : 127u};
             else if constexpr (RAW) w[u] = (!HALF || w_live) ? weight_load8<PASSES>((const u32x2*)(wq + (int64_t)(b * U + u) * 512)) : u32x2{0u, 0u};
             else if constexpr (W8 || MX) w[u] = (!HALF || w_live) ? wload((int64_t)(b * U + u)) : x_zero;
             else if constexpr (HALF) w[u] = w_live ? weight_load<PASSES>((const bf16x8*)(wp + (int64_t)(b * U + u) * 512)) : x_zero;
@@ -1142,6 +1177,12 @@ __global__ __launch_bounds__(1024) void gemm_skinny_fp8w_kernel(GemmArgs p, cons
 template <int MT, int NTW, int U, int EPI, typename OutT, bool PASSES = false, bool HALF = false>
 __global__ __launch_bounds__(1024) void gemm_skinny_mxfp4w_kernel(GemmArgs p, const uint8_t* __restrict__ w_scales) {
     gemm_skinny_body<MT, NTW, U, EPI, OutT, PASSES, false, HALF, WF_MXFP4>(p, (const float*)w_scales);
+}
+// INT4 group-quantized form of the narrow kernel (w4g.h): the same body, w_words = the group words beside the code tiles,
+// gshift = log2(group size / 32)
+template <int MT, int NTW, int U, int EPI, typename OutT, bool PASSES = false, bool HALF = false>
+__global__ __launch_bounds__(1024) void gemm_skinny_int4w_kernel(GemmArgs p, const uint32_t* __restrict__ w_words, int gshift) {
+    gemm_skinny_body<MT, NTW, U, EPI, OutT, PASSES, false, HALF, WF_INT4>(p, (const float*)w_words, gshift);
 }
 // 8-bit MoE experts (nvl_set_expert_dtype): the MoE decode instantiation of the same body — expert skip,
 // gate weight in the SwiGLU epilogue; the down projection's scales are [E][H_pad] (one per expert and output row), K-split
@@ -1428,8 +1469,8 @@ __global__ __launch_bounds__(512) void gemm_skinny_wide_bf16_kernel(GemmArgs p) 
 
 // fp8-weight form of the wide kernel (see gemm_skinny_body)
 template <int MT, int NTB, int U, int EPI, typename OutT, bool PASSES, bool MOE, int WF>
-__device__ __forceinline__ void gemm_skinny_wide_body(GemmArgs p, const float* w_scale) {
-    constexpr bool W8 = WF == WF_FP8, MX = WF == WF_MXFP4;
+__device__ __forceinline__ void gemm_skinny_wide_body(GemmArgs p, const float* w_scale, int gshift = 0) {
+    constexpr bool W8 = WF == WF_FP8, GQ = WF == WF_INT4, MX = WF == WF_MXFP4 || GQ;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     f32x4* red = (f32x4*)smem;                       // [ksplit][NTB][MT][64]
     const int swg = blockIdx.x;
@@ -1457,17 +1498,21 @@ __device__ __forceinline__ void gemm_skinny_wide_body(GemmArgs p, const float* w
     for (int t = 0; t < NTB; t++) wsc[t] = W8 ? w_scale[(nt0 + t) * 16 + fr] : 1.0f;
     // MXFP4 (see gemm_skinny_body): 256 code bytes and 16 scale bytes per (16-row tile, k-step)
     const uint8_t* mq = MX ? (const uint8_t*)p.W + (((int64_t)nt0 * nks + ks0) * 64 + lane) * 4 : nullptr;
-    const uint8_t* me = MX ? (const uint8_t*)w_scale + ((int64_t)nt0 * nks + ks0) * 16 + fr : nullptr;
-    auto mxraw = [&](int t, int64_t s) -> u32x2 {     // {codes, E}
-        return u32x2{weight_load4<PASSES>((const uint32_t*)(mq + ((int64_t)t * nks + s) * 256)), (uint32_t)weight_load1<PASSES>(me + ((int64_t)t * nks + s) * 16)};
+    const uint8_t* me = (MX && !GQ) ? (const uint8_t*)w_scale + ((int64_t)nt0 * nks + ks0) * 16 + fr : nullptr;
+    const uint32_t* gw = GQ ? (const uint32_t*)w_scale + (int64_t)nt0 * (nks >> gshift) * 16 : nullptr;     // INT4 group words (uniform base, see gemm_skinny_body)
+    const int gks0 = GQ ? __builtin_amdgcn_readfirstlane(ks0) : 0;
+    auto mxraw = [&](int t, int64_t s) -> u32x2 {     // {codes, E} / {codes, group word}
+        if constexpr (GQ) return u32x2{weight_load4<PASSES>((const uint32_t*)(mq + ((int64_t)t * nks + s) * 256)),
+                                       weight_load4<PASSES>(gw + (uint32_t)(((t * (nks >> gshift) + ((gks0 + (int)s) >> gshift)) << 4) + fr))};
+        else return u32x2{weight_load4<PASSES>((const uint32_t*)(mq + ((int64_t)t * nks + s) * 256)), (uint32_t)weight_load1<PASSES>(me + ((int64_t)t * nks + s) * 16)};
     };
     auto wload = [&](int t, int64_t s) -> bf16x8 {
-        if constexpr (MX) { const u32x2 r = mxraw(t, s); return w4_frag(r[0], r[1]); }
+        if constexpr (MX) { const u32x2 r = mxraw(t, s); return q4_frag<WF>(r[0], r[1]); }
         else return w8_frag(weight_load8<PASSES>((const u32x2*)(wq + t * tile_stride + s * 512)), wsc[t]);
     };
     typedef typename std::conditional<W8 || MX, u32x2, bf16x8>::type WReg;     // raw codes until the MFMAs (see gemm_skinny_body)
     auto wfrag = [&](const WReg& w, int t) -> bf16x8 {
-        if constexpr (MX) return w4_frag(w[0], w[1]);
+        if constexpr (MX) return q4_frag<WF>(w[0], w[1]);
         else if constexpr (W8) return w8_frag(w, wsc[t]);
         else return w;
     };
@@ -1564,6 +1609,10 @@ template <int MT, int NTB, int U, int EPI, typename OutT, bool PASSES = false>
 __global__ __launch_bounds__(512) void gemm_skinny_wide_mxfp4w_kernel(GemmArgs p, const uint8_t* __restrict__ w_scales) {
     gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, PASSES, false, WF_MXFP4>(p, (const float*)w_scales);
 }
+template <int MT, int NTB, int U, int EPI, typename OutT, bool PASSES = false>
+__global__ __launch_bounds__(512) void gemm_skinny_wide_int4w_kernel(GemmArgs p, const uint32_t* __restrict__ w_words, int gshift) {
+    gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, PASSES, false, WF_INT4>(p, (const float*)w_words, gshift);
+}
 // 8-bit MoE experts: the wide form of the expert up projection (SwiGLU, gate weight in the epilogue)
 template <int MT, int NTB, int U, int EPI, typename OutT>
 __global__ __launch_bounds__(512) void gemm_skinny_wide_moe_fp8w_kernel(GemmArgs p, const float* __restrict__ w_scale) {
@@ -1591,14 +1640,14 @@ static int g_force_ntw = 0, g_force_ksplit = 0;   // tuning overrides (nvl_bench
 static int g_force_tile = 0;                      // 0 automatic, 1: 128x128x2st, 2: 256x128x3st, 3: 256x256x2st, 5: ping-pong 256x256
 
 template <int EPI, typename OutT, int WF = 0>
-static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a, const float* ws = nullptr);
+static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a, const float* ws = nullptr, int gsh = 0);
 constexpr int DEFER_MAX_M = 128;    // deferred RMSNorm (decode): rows of the x^2 partial buffer.  Above 64 rows the producer
                                     // runs as 64-row groups like every narrow projection (one workgroup per 16-row tile
                                     // was measured at M = 128: -13 %); above 128 rows FFN-up belongs on the tile kernels
 static inline int skinny_rows(const GemmArgs& a) { return a.m_passes > 1 && a.M > 64 ? 64 : a.M; }   // rows a workgroup covers
 // the groups of 64 rows as separate launches (weight-block count not a multiple of 8, or key 13 = 0)
 template <int EPI, typename OutT, int WF = 0>
-static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
+static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a, const float* ws = nullptr, int gsh = 0) {
     for (int r0 = 0; r0 < a.M; r0 += 64) {
         GemmArgs c = a;
         c.m_passes = 0;
@@ -1610,25 +1659,34 @@ static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a
             c.C = (float*)a.C + (int64_t)r0 * a.ldc; c.nrm_xn = a.nrm_xn + (int64_t)r0 * a.N;
             c.rs_out = a.rs_out + (int64_t)r0 * (a.N >> 4);
         }
-        if (!launch_gemm_skinny_bf16<EPI, OutT, WF>(st, c, ws)) return false;
+        if (!launch_gemm_skinny_bf16<EPI, OutT, WF>(st, c, ws, gsh)) return false;
     }
     return true;
 }
 
 // The narrow / wide decode kernel of weight format WF with these template arguments: the one place that names the three
 // __global__ wrappers of a form (bf16: the kernel itself; quantized: the plain and the MoE wrapper of the shared body).
-// ws: the weight scales of a quantized format (fp32 per row, or the e8m0 bytes of MXFP4), unused for bf16.
+// ws: the weight scales of a quantized format (fp32 per row, the e8m0 bytes of MXFP4, or the group words of INT4 with
+// gsh = log2(group size / 32)), unused for bf16.  INT4 covers no MoE experts: its MoE branches are never taken.
 template <int WF, int MT, int NTW, int U, int EPI, typename OutT, bool PASSES = false, bool MOE = false, bool HALF = false>
-static inline void launch_skinny_wf(dim3 grid, dim3 block, size_t lds, hipStream_t st, const GemmArgs& a, const float* ws) {
+static inline void launch_skinny_wf(dim3 grid, dim3 block, size_t lds, hipStream_t st, const GemmArgs& a, const float* ws, int gsh = 0) {
     static_assert(WF == WF_BF16 || !MOE || (!PASSES && !HALF), "the quantized MoE wrappers have no PASSES / HALF instance");
     if constexpr (WF == WF_BF16) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MT, NTW, U, EPI, OutT, PASSES, MOE, HALF>), grid, block, lds, st, a);
     else if constexpr (WF == WF_FP8 && MOE) hipLaunchKernelGGL((gemm_skinny_moe_fp8w_kernel<MT, NTW, U, EPI, OutT>), grid, block, lds, st, a, ws);
     else if constexpr (WF == WF_FP8) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<MT, NTW, U, EPI, OutT, PASSES, HALF>), grid, block, lds, st, a, ws);
+    else if constexpr (WF == WF_INT4 && MOE) throw std::runtime_error("gemm: INT4 weights have no MoE decode kernel");
+    else if constexpr (WF == WF_INT4) {
+        // MT = 4 (64-row groups): one k-step per register set, not two.  With U = 2 the fragment conversion's temporaries on top of
+        // the 64 activation registers spilled 24-38 registers inside the k loop of the PASSES instantiations (the launcher's
+        // K split, sized for U = 2, leaves every wave at least two k-steps either way)
+        constexpr int UG = MT == 4 ? 1 : U;
+        hipLaunchKernelGGL((gemm_skinny_int4w_kernel<MT, NTW, UG, EPI, OutT, PASSES, HALF>), grid, block, lds, st, a, (const uint32_t*)ws, gsh);
+    }
     else if constexpr (MOE) hipLaunchKernelGGL((gemm_skinny_moe_mxfp4w_kernel<MT, NTW, U, EPI, OutT>), grid, block, lds, st, a, (const uint8_t*)ws);
     else hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<MT, NTW, U, EPI, OutT, PASSES, HALF>), grid, block, lds, st, a, (const uint8_t*)ws);
 }
 template <int WF, int MT, int NTB, int U, int EPI, typename OutT, bool PASSES = false, bool MOE = false>
-static inline void launch_skinny_wide_wf(dim3 grid, dim3 block, size_t lds, hipStream_t st, const GemmArgs& a, const float* ws) {
+static inline void launch_skinny_wide_wf(dim3 grid, dim3 block, size_t lds, hipStream_t st, const GemmArgs& a, const float* ws, int gsh = 0) {
     static_assert(WF == WF_BF16 || !MOE || !PASSES, "the quantized MoE wrappers have no PASSES instance");
     constexpr int max_lds = 8 * NTB * MT * 64 * 16;
     if constexpr (WF == WF_BF16) {
@@ -1640,6 +1698,11 @@ static inline void launch_skinny_wide_wf(dim3 grid, dim3 block, size_t lds, hipS
     } else if constexpr (WF == WF_FP8) {
         NVL_LDS_ATTR((gemm_skinny_wide_fp8w_kernel<MT, NTB, U, EPI, OutT, PASSES>), max_lds);
         hipLaunchKernelGGL((gemm_skinny_wide_fp8w_kernel<MT, NTB, U, EPI, OutT, PASSES>), grid, block, lds, st, a, ws);
+    } else if constexpr (WF == WF_INT4 && MOE) {
+        throw std::runtime_error("gemm: INT4 weights have no MoE decode kernel");
+    } else if constexpr (WF == WF_INT4) {
+        NVL_LDS_ATTR((gemm_skinny_wide_int4w_kernel<MT, NTB, U, EPI, OutT, PASSES>), max_lds);
+        hipLaunchKernelGGL((gemm_skinny_wide_int4w_kernel<MT, NTB, U, EPI, OutT, PASSES>), grid, block, lds, st, a, (const uint32_t*)ws, gsh);
     } else if constexpr (MOE) {
         NVL_LDS_ATTR((gemm_skinny_wide_moe_mxfp4w_kernel<MT, NTB, U, EPI, OutT>), max_lds);
         hipLaunchKernelGGL((gemm_skinny_wide_moe_mxfp4w_kernel<MT, NTB, U, EPI, OutT>), grid, block, lds, st, a, (const uint8_t*)ws);
@@ -1654,10 +1717,10 @@ static inline void launch_skinny_wide_wf(dim3 grid, dim3 block, size_t lds, hipS
 // (moe_gate) take the K-split down form and the SwiGLU up form; the deferred-norm producer form of the down projection,
 // whose waves cross experts, exists for bf16 experts only.
 template <int NTW, int EPI, typename OutT, int WF = 0>
-static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
+static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, const float* ws = nullptr, int gsh = 0) {
     const int MT = skinny_rows(a) <= 16 ? 1 : (skinny_rows(a) <= 32 ? 2 : 4);
     if (EPI == EPI_RESID && a.m_split && a.rs_out && NTW == 1 && a.m_passes <= 1 && a.grid_y != 1) {   // (m_split: grid_y unused, keep it defined)
-        GemmArgs c = a; c.grid_y = 1; return launch_gemm_skinny_ntw<NTW, EPI, OutT, WF>(st, c, ws);
+        GemmArgs c = a; c.grid_y = 1; return launch_gemm_skinny_ntw<NTW, EPI, OutT, WF>(st, c, ws, gsh);
     }
     const int U = MT <= 2 ? 4 : 2;                       // register budget: (1+MT)*U*2 fragments
     const int nblocks = cdiv(cdiv(a.N, 16), NTW);        // weight rows are padded to 128: all tiles exist
@@ -1685,11 +1748,11 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
             }
             if (a.rs_half) {      // <= 16 rows: 8 weight rows per workgroup, twice the workgroups (HALF above)
                 if (a.M > 16) return false;
-                launch_skinny_wf<WF, 1, NTW, 4, EPI, OutT, false, false, true>(dim3(2 * nblocks, 1), dim3(NTW * ks * 64), (size_t)NTW * ks * 64 * 16, st, a, ws);
+                launch_skinny_wf<WF, 1, NTW, 4, EPI, OutT, false, false, true>(dim3(2 * nblocks, 1), dim3(NTW * ks * 64), (size_t)NTW * ks * 64 * 16, st, a, ws, gsh);
                 return true;
             }
         }
-        launch_skinny_wf<WF, 1, NTW, 4, EPI, OutT>(dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64), (size_t)NTW * ks * 64 * 16, st, a, ws);
+        launch_skinny_wf<WF, 1, NTW, 4, EPI, OutT>(dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64), (size_t)NTW * ks * 64 * 16, st, a, ws, gsh);
         return true;
     }
     // waves per launch: enough to cover HBM latency on every CU (~2-4 thousand), not more — extra K slices only
@@ -1709,10 +1772,10 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
     }
     if (a.K % 32 != 0) return false;
     const size_t lds = (size_t)NTW * ksplit * MT * 64 * 16;
-    if (a.m_passes > 1 && (nblocks % 8 != 0 || KS != 1)) return launch_skinny_passes_serial<EPI, OutT, WF>(st, a, ws);
+    if (a.m_passes > 1 && (nblocks % 8 != 0 || KS != 1)) return launch_skinny_passes_serial<EPI, OutT, WF>(st, a, ws, gsh);
     dim3 grid(nblocks * (a.m_passes > 1 ? a.m_passes : 1), KS), block(NTW * ksplit * 64);
-    if (a.grid_y != KS) { GemmArgs c = a; c.grid_y = KS; return launch_gemm_skinny_ntw<NTW, EPI, OutT, WF>(st, c, ws); }
-#define NVL_SK(MTv, Uv, ...) launch_skinny_wf<WF, MTv, NTW, Uv, EPI, OutT, __VA_ARGS__>(grid, block, lds, st, a, ws)
+    if (a.grid_y != KS) { GemmArgs c = a; c.grid_y = KS; return launch_gemm_skinny_ntw<NTW, EPI, OutT, WF>(st, c, ws, gsh); }
+#define NVL_SK(MTv, Uv, ...) launch_skinny_wf<WF, MTv, NTW, Uv, EPI, OutT, __VA_ARGS__>(grid, block, lds, st, a, ws, gsh)
     if (a.moe_gate) {                                 // MoE decode instantiation (expert skip + gate weight)
         if constexpr (EPI == EPI_SWIGLU || EPI == EPI_RESID) {
             if (a.m_passes > 1) return false;
@@ -1733,9 +1796,9 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
 // either way) is indifferent, and 64-row launches (MT = 4) lose 2 % (profiles/r03_wide_tiles_per_wave.txt).
 static int g_wide_ntb = 0;
 template <int EPI, typename OutT, int NTB = 4, int WF = 0>
-static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, const float* ws = nullptr) {
+static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, const float* ws = nullptr, int gsh = 0) {
     if constexpr (NTB == 4) {
-        if (g_wide_ntb == 2 || (g_wide_ntb == 0 && skinny_rows(a) <= 32 && a.N < 65536)) return launch_gemm_skinny_wide<EPI, OutT, 2, WF>(st, a, ws);
+        if (g_wide_ntb == 2 || (g_wide_ntb == 0 && skinny_rows(a) <= 32 && a.N < 65536)) return launch_gemm_skinny_wide<EPI, OutT, 2, WF>(st, a, ws, gsh);
     }
     if (a.K % 32 != 0 || a.sk_part) return false;
     const int groups = cdiv(cdiv(a.N, 16), NTB);     // weight rows are padded to 256: every tile of a group exists
@@ -1749,9 +1812,9 @@ static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, co
     else { while (ksplit > 2 && groups * ksplit > 512) ksplit >>= 1; if (groups >= 1024) ksplit = 1; }   // LM head: one wave per group (cold sweep: 96 vs 104 us)
     while (ksplit > 1 && (a.K >> 5) / ksplit < U) ksplit >>= 1;
     const size_t lds = (size_t)ksplit * NTB * MT * 64 * 16;
-    if (a.m_passes > 1 && groups % 8 != 0) return launch_skinny_passes_serial<EPI, OutT, WF>(st, a, ws);
+    if (a.m_passes > 1 && groups % 8 != 0) return launch_skinny_passes_serial<EPI, OutT, WF>(st, a, ws, gsh);
     const int wgs = groups * (a.m_passes > 1 ? a.m_passes : 1);
-#define NVL_SKW(MTv, Uv, ...) launch_skinny_wide_wf<WF, MTv, NTB, Uv, EPI, OutT, __VA_ARGS__>(dim3(wgs), dim3(ksplit * 64), lds, st, a, ws)
+#define NVL_SKW(MTv, Uv, ...) launch_skinny_wide_wf<WF, MTv, NTB, Uv, EPI, OutT, __VA_ARGS__>(dim3(wgs), dim3(ksplit * 64), lds, st, a, ws, gsh)
     if (a.moe_gate) {                                 // MoE experts: the expert up projection
         if constexpr (EPI == EPI_SWIGLU) {
             if (a.m_passes > 1) return false;
@@ -1766,7 +1829,7 @@ static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, co
     return true;
 }
 template <int EPI, typename OutT, int WF>
-static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a0, const float* ws) {
+static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a0, const float* ws, int gsh) {
     if (EPI == EPI_QKV) return false;               // prefill-only epilogue (a decode workgroup owns 16 columns, not a head)
     if (skinny_rows(a0) > 64 || a0.a_rows || a0.seg || a0.tile_map) return false;
     GemmArgs a = a0;
@@ -1774,12 +1837,12 @@ static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a0, c
     if constexpr (EPI == EPI_SWIGLU || EPI == EPI_STORE || EPI == EPI_GELU) {
         // wide-N form once its 64-row groups fill the chip (g_force_ntw: 8 forces it, 1/2/4 force the narrow form)
         const bool wide_ok = skinny_rows(a) > 16 && cdiv(a.N, 64) >= 256 && !a.sk_part;   // M <= 16: the narrow form streams as fast
-        if (g_force_ntw == 8 || (g_force_ntw == 0 && wide_ok)) { if (launch_gemm_skinny_wide<EPI, OutT, 4, WF>(st, a, ws)) return true; }
+        if (g_force_ntw == 8 || (g_force_ntw == 0 && wide_ok)) { if (launch_gemm_skinny_wide<EPI, OutT, 4, WF>(st, a, ws, gsh)) return true; }
     }
-    if (EPI == EPI_SWIGLU) return launch_gemm_skinny_ntw<2, EPI, OutT, WF>(st, a, ws);
-    if (g_force_ntw == 2) return launch_gemm_skinny_ntw<2, EPI, OutT, WF>(st, a, ws);
+    if (EPI == EPI_SWIGLU) return launch_gemm_skinny_ntw<2, EPI, OutT, WF>(st, a, ws, gsh);
+    if (g_force_ntw == 2) return launch_gemm_skinny_ntw<2, EPI, OutT, WF>(st, a, ws, gsh);
     if constexpr (WF == WF_BF16) { if (g_force_ntw == 4) return launch_gemm_skinny_ntw<4, EPI, OutT>(st, a); }   // (tuning only: no fp8 form)
-    return launch_gemm_skinny_ntw<1, EPI, OutT, WF>(st, a, ws);
+    return launch_gemm_skinny_ntw<1, EPI, OutT, WF>(st, a, ws, gsh);
 }
 
 template <int BM, int BN, int WAVES_M, int WAVES_N, int STAGES, int EPI, typename OutT>

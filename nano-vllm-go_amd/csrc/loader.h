@@ -10,6 +10,7 @@
 // Differences from the reference, on purpose: sharded checkpoints may hold MoE layers (the reference's shard path has
 // none, :1270-1273); a tensor is looked up under its name and under "transformer." + name in every file (:622-629).
 #pragma once
+#include "int4_unpack.h"
 
 #include <fcntl.h>
 #include <sys/mman.h>
@@ -145,6 +146,7 @@ inline bool exists(const std::string& path, bool* is_dir = nullptr) {
 // (generic_loader.go:184-199, loader.go:13-17)
 // ---------------------------------------------------------------------------------------------
 constexpr int ST_F8_E4M3 = 100;     // loader-only dtype tag of an F8_E4M3 tensor (never passed to nvl_upload_tensor)
+constexpr int ST_I32 = 101;         // ... of an I32 tensor: the packed .qweight / .qzeros / .g_idx of AWQ / GPTQ checkpoints
 // scale: an F8_E4M3 "<name>.weight"'s "<name>.weight_scale" (linked after every file is read), or NULL
 struct StTensor { const uint8_t* data = nullptr; int dtype = 0; std::vector<int64_t> shape; size_t bytes = 0; int64_t numel = 1;
                   const StTensor* scale = nullptr; };
@@ -181,6 +183,7 @@ struct StSet {
             StTensor t;
             if (dt->str == "F32") t.dtype = NVL_DTYPE_F32; else if (dt->str == "BF16") t.dtype = NVL_DTYPE_BF16;
             else if (dt->str == "F16") t.dtype = NVL_DTYPE_F16; else if (dt->str == "F8_E4M3") t.dtype = ST_F8_E4M3;
+            else if (dt->str == "I32") t.dtype = ST_I32;
             else t.dtype = -1;      // refused only if the model needs it (:660-662)
             for (auto& d : sh->arr) {      // dimensions: non-negative integers whose product stays far inside int64
                 if (d.kind != JVal::NUM || !(d.num >= 0) || d.num > 4.0e12 || d.num != (double)(int64_t)d.num)
@@ -196,7 +199,7 @@ struct StSet {
             const size_t b = (size_t)off->arr[0].num, e = (size_t)off->arr[1].num;
             if (e < b || e > data_len) throw std::runtime_error(path + ": data_offsets of " + kv.first + " outside the file");
             t.data = data + b; t.bytes = e - b;
-            if (t.dtype >= 0 && t.bytes != (size_t)t.numel * (t.dtype == NVL_DTYPE_F32 ? 4 : t.dtype == ST_F8_E4M3 ? 1 : 2))
+            if (t.dtype >= 0 && t.bytes != (size_t)t.numel * (t.dtype == NVL_DTYPE_F32 || t.dtype == ST_I32 ? 4 : t.dtype == ST_F8_E4M3 ? 1 : 2))
                 throw std::runtime_error(path + ": byte size of " + kv.first + " does not match its shape");
             tensors[kv.first] = std::move(t);
         }
@@ -350,6 +353,46 @@ void up2d(nvl_model* m, int kind, int layer, const StTensor& t, int layout) {
     const int rc = nvl_upload_tensor(m, kind, layer, t.data, t.dtype, t.shape[0], t.shape[1], layout);
     if (rc) throw std::runtime_error(std::string("loader: ") + nvl_last_error(m));
 }
+// INT4 group-quantized checkpoints (AWQ / GPTQ, int4_unpack.h): "<base>.qweight" + ".qzeros" + ".scales" (I32 / I32 / F16,
+// GPTQ also ".g_idx") where a covered projection's "<base>.weight" would be.  true: unpacked into `out` (rows appended: the
+// Q|K|V-free pairs gate | up are concatenated by calling it twice); false: the checkpoint has no such tensor.
+bool gq_unpack(nvl_model* m, const StSet& st, const std::string& base, nvl_int4::Canon* out) {
+    const StTensor* qw = st.find(base + ".qweight");
+    if (!qw) return false;
+    if (nvl::wf_base(m->wf) != nvl::WF_INT4)
+        throw std::runtime_error("loader: " + base + " is INT4 group-quantized (.qweight); call nvl_set_gq_weight_dtype with the checkpoint's group_size first");
+    const StTensor *qz = st.find(base + ".qzeros"), *sc = st.find(base + ".scales"), *gi = st.find(base + ".g_idx");
+    if (!qz || !sc) throw std::runtime_error("loader: " + base + ".qweight without .qzeros / .scales");
+    if (qw->dtype != nvl_loader::ST_I32 || qz->dtype != nvl_loader::ST_I32 || sc->dtype != NVL_DTYPE_F16)
+        throw std::runtime_error("loader: " + base + ": qweight / qzeros / scales must be I32 / I32 / F16");
+    int layout = 0, g = 0;
+    int64_t K = 0, N = 0;
+    std::string e = nvl_int4::detect(qw->shape, qz->shape, sc->shape, &layout, &K, &N, &g);
+    if (!e.empty()) throw std::runtime_error("loader: " + base + ": " + e);
+    if (g != nvl::wf_group(m->wf))
+        throw std::runtime_error("loader: " + base + ": group size " + std::to_string(g) + " differs from the model's " + std::to_string(nvl::wf_group(m->wf)));
+    if (gi && (gi->dtype != nvl_loader::ST_I32 || gi->numel != K)) throw std::runtime_error("loader: " + base + ".g_idx must be I32 [K]");
+    nvl_int4::Canon c;
+    if (layout == nvl_int4::LAYOUT_AWQ) e = nvl_int4::unpack_awq((const int32_t*)qw->data, (const int32_t*)qz->data, (const uint16_t*)sc->data, K, N, g, &c);
+    else e = nvl_int4::unpack_gptq((const int32_t*)qw->data, (const int32_t*)qz->data, (const uint16_t*)sc->data, gi ? (const int32_t*)gi->data : nullptr, K, N, g, &c);
+    if (!e.empty()) throw std::runtime_error("loader: " + base + ": " + e);
+    if (out->N && out->K != c.K) throw std::runtime_error("loader: " + base + ": input width differs from its pair's");
+    out->K = c.K; out->g = c.g; out->N += c.N;
+    out->codes.insert(out->codes.end(), c.codes.begin(), c.codes.end());
+    out->scales.insert(out->scales.end(), c.scales.begin(), c.scales.end());
+    out->zeros.insert(out->zeros.end(), c.zeros.begin(), c.zeros.end());
+    return true;
+}
+void gq_upload(nvl_model* m, int kind, int layer, const nvl_int4::Canon& c) {
+    if (nvl_upload_tensor_int4(m, kind, layer, c.codes.data(), c.scales.data(), c.zeros.data(), c.N, c.K, NVL_LAYOUT_OUT_IN))
+        throw std::runtime_error(std::string("loader: ") + nvl_last_error(m));
+}
+// a projection "<base>.weight" [out, in], or its INT4 group-quantized form
+void up2d_proj(nvl_model* m, int kind, int layer, const StSet& st, const std::string& base) {
+    nvl_int4::Canon c;
+    if (gq_unpack(m, st, base, &c)) gq_upload(m, kind, layer, c);
+    else up2d(m, kind, layer, st.need(base + ".weight"), NVL_LAYOUT_OUT_IN);
+}
 void up1d(nvl_model* m, int kind, int layer, const StTensor& t) {
     if (t.dtype == nvl_loader::ST_F8_E4M3) throw std::runtime_error("loader: an F8_E4M3 1-D tensor is not supported");
     const int rc = nvl_upload_tensor(m, kind, layer, t.data, t.dtype, t.numel, 1, NVL_LAYOUT_IN_OUT);
@@ -467,10 +510,10 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
                 load_norm(m, st, p + ".post_attention_layernorm.weight", NVL_T_FFN_NORM_W, NVL_T_FFN_NORM_B, l);
                 continue;
             }
-            up2d(m, NVL_T_WQ, l, st.need(p + ".self_attn.q_proj.weight"), OI);
-            up2d(m, NVL_T_WK, l, st.need(p + ".self_attn.k_proj.weight"), OI);
-            up2d(m, NVL_T_WV, l, st.need(p + ".self_attn.v_proj.weight"), OI);
-            up2d(m, NVL_T_WO, l, st.need(p + ".self_attn.o_proj.weight"), OI);
+            up2d_proj(m, NVL_T_WQ, l, st, p + ".self_attn.q_proj");        // (or the projection's .qweight / .qzeros / .scales)
+            up2d_proj(m, NVL_T_WK, l, st, p + ".self_attn.k_proj");
+            up2d_proj(m, NVL_T_WV, l, st, p + ".self_attn.v_proj");
+            up2d_proj(m, NVL_T_WO, l, st, p + ".self_attn.o_proj");
             load_kv_scales(m, st, p, l);
             if (c.use_moe) {                                                   // loadMoE (:566-592)
                 up2d(m, NVL_T_ROUTER, l, st.need(p + ".block_sparse_moe.router.layer.weight"), OI);   // [E, H]: "always transpose"
@@ -487,6 +530,12 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
                                                      e.shape[0] * e.shape[1], e.shape[2], IO);
                     if (rc) throw std::runtime_error(nvl_last_error(m));
                 }
+            } else if (st.find(p + ".mlp.gate_proj.qweight")) {                 // INT4 pair: gate rows, then up rows (groups lie along k)
+                nvl_int4::Canon w1;
+                if (!gq_unpack(m, st, p + ".mlp.gate_proj", &w1) || !gq_unpack(m, st, p + ".mlp.up_proj", &w1))
+                    throw std::runtime_error("loader: " + p + ".mlp: gate_proj / up_proj must both be INT4 group-quantized");
+                gq_upload(m, NVL_T_W1, l, w1);
+                up2d_proj(m, NVL_T_W2, l, st, p + ".mlp.down_proj");
             } else {                                                           // loadFFN (:513-563): gate | up -> W1
                 const StTensor& g = st.need(p + ".mlp.gate_proj.weight");
                 const StTensor* u = st.find(p + ".mlp.up_proj.weight");

@@ -171,7 +171,7 @@ template <int WF>
 void gemm_q(nvl_model* m, int epi, bool out_f32, const GemmArgs& a, const nvl_model::QRef& q) {
     const A8Buf a8buf{m->a8_codes, m->a8_scale, m->a8_rows, m->a8_k};
     const A8Buf* a8 = m->a8 ? &a8buf : nullptr;     // 8-bit activations at the tile step (a8.h; fp8 weights only)
-#define NVL_GQ(EPIv, OutTv) launch_gemm_q<EPIv, OutTv, WF>(m->stream, a, q.scales, q.rows_pad, m->wq_scratch, m->wq_scratch_elems, a8)
+#define NVL_GQ(EPIv, OutTv) launch_gemm_q<EPIv, OutTv, WF>(m->stream, a, q.scales, q.rows_pad, m->wq_scratch, m->wq_scratch_elems, a8, wf_group(q.wf))
     switch (epi) {
         case EPI_STORE:  if (out_f32) NVL_GQ(EPI_STORE, float); else NVL_GQ(EPI_STORE, bf16_t); break;
         case EPI_RESID:  NVL_GQ(EPI_RESID, float); break;
@@ -193,7 +193,9 @@ void gemm(nvl_model* m, int epi, bool out_f32, GemmArgs a, double flops = -1.0) 
     KScope ks(m, KC_GEMM, flops >= 0 ? flops : 2.0 * (double)a.M * (double)a.N * (double)a.K, -1, gbytes);
     hipStream_t st = m->stream;
     if (q) {     // the same dispatch on the kernels of the weight's format / dequantize + tile (wq.h)
-        if (q->wf == WF_FP8) gemm_q<WF_FP8>(m, epi, out_f32, a, *q); else gemm_q<WF_MXFP4>(m, epi, out_f32, a, *q);
+        if (q->wf == WF_FP8) gemm_q<WF_FP8>(m, epi, out_f32, a, *q);
+        else if (wf_base(q->wf) == WF_INT4) gemm_q<WF_INT4>(m, epi, out_f32, a, *q);
+        else gemm_q<WF_MXFP4>(m, epi, out_f32, a, *q);
         NVL_HIP(hipGetLastError());
         return;
     }
@@ -424,11 +426,15 @@ namespace {
 // the quantized format this 2-D kind is stored in (wq.h wf_covers), or WF_BF16
 int q_kind(const nvl_model* m, int kind) { return wf_covers(m->wf, m->ef, m->hf, kind, m->cfg.tied_embedding != 0) ? m->wf : WF_BF16; }
 
-// the scales of `rows` rows of K inputs, every one the pad value of the format: fp32 1.0, or the e8m0 byte 127 (2^0)
+// the scales of `rows` rows of K inputs, every one the pad value of the format: fp32 1.0, the e8m0 byte 127 (2^0), or the
+// INT4 group word {s = 1, z = 0}
 void* q_alloc_scales(nvl_model* m, int wf, int64_t rows, int64_t K) {
     void* qs = dmalloc_bytes(wf_scale_bytes(wf, rows, K));
     if (wf == WF_MXFP4) {
         NVL_HIP(hipMemsetAsync(qs, 127, (size_t)wf_scale_bytes(wf, rows, K), m->stream));
+    } else if (wf_base(wf) == WF_INT4) {
+        const std::vector<uint32_t> pad((size_t)(wf_scale_bytes(wf, rows, K) / 4), W4G_PAD_WORD);
+        NVL_HIP(hipMemcpy(qs, pad.data(), pad.size() * 4, hipMemcpyHostToDevice));
     } else {
         const std::vector<float> ones((size_t)rows, 1.0f);
         NVL_HIP(hipMemcpy(qs, ones.data(), (size_t)rows * 4, hipMemcpyHostToDevice));   // (synchronous: `ones` is pageable and local)
@@ -451,6 +457,7 @@ double q_bytes(const DevTensor& t) { return (double)wf_code_bytes(t.wf, t.rows_p
 // device, then the format's quantizer -> codes + scales in its device layout (w8.h / w4.h)
 void upload_2d_q(nvl_model* m, DevTensor* t, int wf, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out) {
     if (K % 32 != 0) throw std::runtime_error(std::string(wf_name(wf)) + " weights: the input width must be a multiple of 32");
+    if (wf_base(wf) == WF_INT4 && K % wf_group(wf) != 0) throw std::runtime_error("INT4 weights: the input width must be a multiple of the group size");
     const size_t esz = dtype == NVL_DTYPE_F32 ? 4 : 2;
     void* raw = dmalloc_bytes(N * K * (int64_t)esz);
     NVL_HIP(hipMemcpyAsync(raw, data, (size_t)(N * K) * esz, hipMemcpyDefault, m->stream));
@@ -461,7 +468,9 @@ void upload_2d_q(nvl_model* m, DevTensor* t, int wf, const void* data, int dtype
     q_alloc(m, t, wf, N, K);
     int* bad = dmalloc<int>(1);
     NVL_HIP(hipMemsetAsync(bad, 0, 4, m->stream));
-    if (wf == WF_MXFP4)
+    if (wf_base(wf) == WF_INT4)
+        hipLaunchKernelGGL(w4g_quant_rows_kernel, dim3((unsigned)N), dim3(64), 0, m->stream, (const float*)f, K, wf_gshift(wf), (uint8_t*)t->p, (uint32_t*)t->qs, bad);
+    else if (wf == WF_MXFP4)
         hipLaunchKernelGGL(w4_quant_rows_kernel, dim3((unsigned)N), dim3(64), 0, m->stream, (const float*)f, K, (uint8_t*)t->p, (uint8_t*)t->qs, bad);
     else
         hipLaunchKernelGGL(w8_quant_rows_kernel, dim3((unsigned)N), dim3(256), 0, m->stream, (const float*)f, K, (uint8_t*)t->p, (float*)t->qs, bad);
@@ -472,7 +481,8 @@ void upload_2d_q(nvl_model* m, DevTensor* t, int wf, const void* data, int dtype
     dfree(bad); dfree(f); dfree(raw);
     if (h_bad) {
         dfree(t->p); dfree(t->qs); t->p = t->qs = nullptr;
-        throw std::runtime_error(std::string("nvl_upload_tensor: a weight is not finite (") + wf_name(wf) + " weights refuse NaN / Inf)");
+        throw std::runtime_error(std::string("nvl_upload_tensor: a weight is not finite (") + wf_name(wf) + " weights refuse NaN / Inf" +
+                                 (wf_base(wf) == WF_INT4 ? ", and a group whose scale exceeds the fp16 range)" : ")"));
     }
     m->stats.weight_bytes += q_bytes(*t);
 }
@@ -724,6 +734,49 @@ extern "C" int nvl_upload_tensor_mxfp4(nvl_model* m, int kind, int layer, const 
     return upload_prequant(m, WF_MXFP4, "nvl_upload_tensor_mxfp4", "nvl_set_mx_weight_dtype", kind, layer, codes, scales, rows, cols, layout);
 }
 
+// INT4 (w4g.h): codes [rows][cols/2] (even k in the low nibble), fp16 scales and zero points [rows][cols/g]; taken as they are
+extern "C" int nvl_upload_tensor_int4(nvl_model* m, int kind, int layer, const uint8_t* codes, const uint16_t* scales, const uint8_t* zeros,
+                                      int64_t rows, int64_t cols, int layout) {
+    const char* fn = "nvl_upload_tensor_int4";
+    char buf[200];
+    auto bad = [&](int code, const char* fmt, auto... args) { snprintf(buf, sizeof buf, fmt, fn, args...); return fail(m, code, buf); };
+    if (!m || !codes || !scales || !zeros) return bad(NVL_ERR_INVALID, "%s: null argument");
+    if (m->finalized) return bad(NVL_ERR_STATE, "%s: model already finalized");
+    const int wf = m->wf;
+    if (wf_base(wf) != WF_INT4 || q_kind(m, kind) != wf) return bad(NVL_ERR_INVALID, "%s: not an INT4 weight kind of this model (nvl_set_gq_weight_dtype)");
+    if (layout != NVL_LAYOUT_OUT_IN) return bad(NVL_ERR_INVALID, "%s: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
+    DevTensor* t = tensor_slot(m, kind, layer);
+    if (!t) return bad(NVL_ERR_INVALID, "%s: bad kind or layer");
+    const int64_t SN = full_out(m, kind), SK = full_in(m, kind), g = wf_group(wf);
+    if (rows != SN || cols != SK || SK % g != 0 || SK % 32 != 0)
+        return bad(NVL_ERR_INVALID, "%s: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld], in %% group size == 0", kind,
+                   (long long)rows, (long long)cols, (long long)SN, (long long)SK);
+    const int64_t ng = rows * (cols / g);
+    for (int64_t i = 0; i < ng; i++) {
+        if (zeros[i] > 15) return bad(NVL_ERR_INVALID, "%s: a zero point is above 15");
+        const uint16_t h = scales[i];     // fp16 bits: positive (sign 0, not zero) and finite (exponent field below 31)
+        if ((h & 0x8000) || h == 0 || (h & 0x7c00) == 0x7c00) return bad(NVL_ERR_INVALID, "%s: scales must be finite and positive");
+    }
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    m->w2d_uploaded = true;
+    q_alloc(m, t, wf, rows, cols);
+    uint8_t* raw = (uint8_t*)dmalloc_bytes(rows * cols / 2);
+    uint16_t* raw_s = (uint16_t*)dmalloc_bytes(ng * 2);
+    uint8_t* raw_z = (uint8_t*)dmalloc_bytes(ng);
+    NVL_HIP(hipMemcpy(raw, codes, (size_t)(rows * cols / 2), hipMemcpyHostToDevice));
+    NVL_HIP(hipMemcpy(raw_s, scales, (size_t)ng * 2, hipMemcpyHostToDevice));
+    NVL_HIP(hipMemcpy(raw_z, zeros, (size_t)ng, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(w4g_place_kernel, dim3((unsigned)cdiv(rows * cols / 8, 256)), dim3(256), 0, m->stream, (const uint8_t*)raw,
+                       (const uint16_t*)raw_s, (const uint8_t*)raw_z, rows, cols, wf_gshift(wf), (uint8_t*)t->p, (uint32_t*)t->qs);
+    NVL_HIP(hipGetLastError());
+    NVL_HIP(hipStreamSynchronize(m->stream));
+    dfree(raw); dfree(raw_s); dfree(raw_z);
+    m->stats.weight_bytes += q_bytes(*t);
+    return NVL_OK;
+    NVL_CATCH(m)
+}
+
 // splitGPT2QKV (generic_loader.go:674-702): c_attn [H, 3H] is [in,out]; columns split Q|K|V.
 extern "C" int nvl_upload_gpt2_qkv(nvl_model* m, int layer, const float* w, const float* b) {
     if (!m || !w) return fail(m, NVL_ERR_INVALID, "nvl_upload_gpt2_qkv: null argument");
@@ -815,13 +868,13 @@ std::vector<int32_t> swiglu_interleave(int64_t F, int64_t src_base) {
 
 // gather_rows for a quantized weight: the codes move as 16-row tiles and the scales with them.  Pad rows (idx < 0) get
 // codes 0 and, fp8: scale 1 (the per-row scales are permuted on the host); MXFP4: zero scale bytes, a tile's K/2 scale
-// bytes being contiguous like its codes (W~ = 0 either way; pad outputs are never stored)
+// bytes being contiguous like its codes; INT4: zero group words, moved the same way (W~ = 0 every way; pad outputs are never stored)
 void gather_rows_q(nvl_model* m, const DevTensor& src, const std::vector<int32_t>& idx, void* dst, void* dst_qs, int64_t K) {
     const std::vector<int32_t> use = gather_tiles(idx);
     int32_t* didx = dmalloc<int32_t>((int64_t)use.size());
     NVL_HIP(hipMemcpyAsync(didx, use.data(), use.size() * 4, hipMemcpyHostToDevice, m->stream));
     std::vector<float> sc, ssrc;     // (fp8; alive until the synchronize below)
-    if (src.wf == WF_MXFP4) {
+    if (src.wf == WF_MXFP4 || wf_base(src.wf) == WF_INT4) {
         hipLaunchKernelGGL((gather_rows_kernel<uint8_t>), dim3((unsigned)use.size()), dim3(256), 0, m->stream,
                            (const uint8_t*)src.qs, didx, (uint8_t*)dst_qs, wf_scale_bytes(src.wf, 16, K));
     } else {
@@ -890,6 +943,8 @@ extern "C" int nvl_set_weight_dtype(nvl_model* m, int dtype) {
         return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights are not available with tensor parallelism");
     if (dtype == NVL_W_FP8_E4M3 && m->wf == WF_MXFP4)
         return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: the model stores MXFP4 weights (nvl_set_mx_weight_dtype)");
+    if (dtype == NVL_W_FP8_E4M3 && wf_base(m->wf) == WF_INT4)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: the model stores INT4 weights (nvl_set_gq_weight_dtype)");
     if (dtype == NVL_W_FP8_E4M3) m->wf = WF_FP8;
     else if (m->wf == WF_FP8) { m->wf = m->ef = WF_BF16; m->a8 = false; }     // (8-bit activations and experts need 8-bit weights)
     return NVL_OK;
@@ -905,12 +960,33 @@ extern "C" int nvl_set_mx_weight_dtype(nvl_model* m, int dtype) {
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: MXFP4 weights are not available with tensor parallelism");
     if (dtype == NVL_MX_FP4_E2M1 && m->wf == WF_FP8)
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores 8-bit weights (nvl_set_weight_dtype)");
+    if (dtype == NVL_MX_FP4_E2M1 && wf_base(m->wf) == WF_INT4)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores INT4 weights (nvl_set_gq_weight_dtype)");
     if (dtype == NVL_MX_NONE && m->ef == WF_MXFP4)
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores MXFP4 experts (nvl_set_mx_expert_dtype), which need MXFP4 weights");
     if (dtype == NVL_MX_NONE && m->hf == WF_MXFP4)
         return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores an MXFP4 LM head (nvl_set_mx_head_dtype), which needs MXFP4 weights");
     if (dtype == NVL_MX_FP4_E2M1) m->wf = WF_MXFP4;
     else if (m->wf == WF_MXFP4) m->wf = WF_BF16;
+    return NVL_OK;
+}
+
+extern "C" int nvl_set_gq_weight_dtype(nvl_model* m, int dtype, int group_size) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: no model");
+    if (m->finalized || m->w2d_uploaded)
+        return fail(m, NVL_ERR_STATE, "nvl_set_gq_weight_dtype: call it after nvl_create and before the first 2-D weight upload");
+    if (dtype != NVL_GQ_NONE && dtype != NVL_GQ_UINT4) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: unknown group-quantized weight dtype");
+    if (group_size != 32 && group_size != 64 && group_size != 128)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: the group size must be 32, 64 or 128");
+    if (dtype == NVL_GQ_UINT4 && m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: INT4 weights need bf16 precision");
+    if (dtype == NVL_GQ_UINT4 && (m->tp > 1 || m->tp_force))
+        return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: INT4 weights are not available with tensor parallelism");
+    if (dtype == NVL_GQ_UINT4 && m->wf == WF_FP8)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: the model stores 8-bit weights (nvl_set_weight_dtype)");
+    if (dtype == NVL_GQ_UINT4 && m->wf == WF_MXFP4)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: the model stores MXFP4 weights (nvl_set_mx_weight_dtype)");
+    if (dtype == NVL_GQ_UINT4) m->wf = wf_int4(group_size);
+    else if (wf_base(m->wf) == WF_INT4) m->wf = WF_BF16;
     return NVL_OK;
 }
 
@@ -3657,6 +3733,17 @@ extern "C" int nvl_get_weight(nvl_model* m, int kind, int layer, float* out, int
     NVL_HIP(hipSetDevice(m->device));
     NVL_HIP(hipStreamSynchronize(m->stream));
     const int64_t N = t->rows, K = t->cols, n_el = t->rows_pad * K;
+    if (t->qs && wf_base(t->wf) == WF_INT4) {     // INT4: W~ = bf16_rne(s * (q - z)) (w4g.h)
+        std::vector<uint8_t> codes((size_t)wf_code_bytes(t->wf, n_el));
+        std::vector<uint32_t> words((size_t)wf_scale_bytes(t->wf, t->rows_pad, K) / 4);
+        NVL_HIP(hipMemcpy(codes.data(), t->p, codes.size(), hipMemcpyDeviceToHost));
+        NVL_HIP(hipMemcpy(words.data(), t->qs, words.size() * 4, hipMemcpyDeviceToHost));
+        const int64_t g = wf_group(t->wf);
+        for (int64_t n = 0; n < N; n++)
+            for (int64_t k = 0; k < K; k++)
+                out[k * N + n] = w4g_value(w4_code_at(codes.data(), n, k, K), words[(size_t)w4g_word_index(n, k / g, K / g)]);
+        return NVL_OK;
+    }
     if (t->qs) {     // quantized weight: W~, the values every GEMM path computes with — fp8: bf16_rne(s * e4m3(q)); MXFP4: +-grid[q] * 2^e
         std::vector<uint8_t> codes((size_t)wf_code_bytes(t->wf, n_el)), sc((size_t)wf_scale_bytes(t->wf, t->rows_pad, K));
         NVL_HIP(hipMemcpy(codes.data(), t->p, codes.size(), hipMemcpyDeviceToHost));

@@ -423,6 +423,27 @@ extern "C" int nvl_op_matmul_mxfp4w(int device, const float* a, const float* w, 
     OP_CATCH
 }
 
+// INT4 group-quantized weights (w4g.h): the INT4-weight decode kernels, the 64-row groups, dequantize + tile
+extern "C" int nvl_op_matmul_int4w(int device, const float* a, const float* w, int M, int N, int K, int group_size, float* c,
+                                   uint8_t* codes_out, uint16_t* scales_out, uint8_t* zeros_out) {
+    if (!a || !w || !c || M <= 0 || K <= 0 || N <= 0) return op_fail("nvl_op_matmul_int4w: bad arguments");
+    if (group_size != 32 && group_size != 64 && group_size != 128) return op_fail("nvl_op_matmul_int4w: the group size must be 32, 64 or 128");
+    if (K % 64 != 0 || K % group_size != 0) return op_fail("nvl_op_matmul_int4w: K must be a multiple of 64 and of the group size");
+    OP_TRY
+    OpCtx cx(device, NVL_PRECISION_BF16);
+    DevTensor t;
+    op_matmul_q(cx, wf_int4(group_size), a, w, M, N, K, c, t, INT64_MAX);
+    if (codes_out || scales_out || zeros_out) {
+        std::vector<uint8_t> codes((size_t)(t.rows_pad * K / 2));
+        std::vector<uint32_t> words((size_t)(t.rows_pad * (K / group_size)));
+        NVL_HIP(hipMemcpy(codes.data(), t.p, codes.size(), hipMemcpyDeviceToHost));
+        NVL_HIP(hipMemcpy(words.data(), t.qs, words.size() * 4, hipMemcpyDeviceToHost));
+        w4g_to_abi(codes.data(), words.data(), N, K, group_size, codes_out, scales_out, zeros_out);
+    }
+    return NVL_OK;
+    OP_CATCH
+}
+
 // codes [rows_pad16][K] (fragment-major bytes) + scales on the device -> [M][K] row-major / [M] on the host
 static void a8_read_back(OpCtx& cx, const uint8_t* dcodes, const float* dscale, int M, int K, uint8_t* codes_out, float* scales_out) {
     const int64_t rows = round_up(M, 16);

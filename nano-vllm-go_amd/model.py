@@ -48,7 +48,8 @@ class HipTransformerModel:
                  tp_force_single: bool = False, kv_num_blocks: int = 0, kv_block_size: int = 0,
                  kv_cache_dtype: str = "auto", kv_scales=None, weight_dtype: str = "auto",
                  act_dtype: str = "auto", expert_dtype: str = "auto", mx_weight_dtype: str = "none",
-                 mx_expert_dtype: str = "none", mx_head_dtype: str = "none"):
+                 mx_expert_dtype: str = "none", mx_head_dtype: str = "none", gq_weight_dtype: str = "none",
+                 gq_group_size: int = 128):
         """tensors=None defers finalize(): upload() each tensor, then call finalize().
         tp_size > 1 makes this the tp_rank-th tensor-parallel shard: pass the FULL tensors, the library keeps
         its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests).
@@ -66,7 +67,11 @@ class HipTransformerModel:
         mx_expert_dtype="fp4_e2m1" (needs mx_weight_dtype="fp4_e2m1", a MoE model): the experts' weights are MXFP4 too, one
         e8m0 scale per 32 input features of an (expert, output row) (nvl_set_mx_expert_dtype).
         mx_head_dtype="fp4_e2m1" (needs mx_weight_dtype="fp4_e2m1"): the LM head, and the token embedding of a tied model, are
-        MXFP4 too, one e8m0 scale per 32 input features of a vocabulary row (nvl_set_mx_head_dtype)."""
+        MXFP4 too, one e8m0 scale per 32 input features of a vocabulary row (nvl_set_mx_head_dtype).
+        gq_weight_dtype="uint4": INT4 group-quantized projection weights, the W4A16 format of AWQ / GPTQ checkpoints — unsigned
+        4-bit codes with one fp16 scale and one zero point per gq_group_size (32 / 64 / 128) input features
+        (nvl_set_gq_weight_dtype; bf16 precision, no TP, not with weight_dtype / mx_weight_dtype); the LM head, the embeddings
+        and the MoE experts stay bf16.  The model computes with W~ = bf16(s * (q - z)), which get_weight returns."""
         self.cfg = dict(cfg)
         self.lib = L.lib()
         self.h = C.c_void_p()
@@ -104,8 +109,22 @@ class HipTransformerModel:
             raise ValueError(f"mx_head_dtype must be one of {sorted(L.MX_HEAD_DTYPE)}")
         if mx_head_dtype != "none" and mx_weight_dtype != "fp4_e2m1":
             raise ValueError('mx_head_dtype="fp4_e2m1" needs mx_weight_dtype="fp4_e2m1"')
+        if gq_weight_dtype not in L.GQ_WEIGHT_DTYPE:
+            raise ValueError(f"gq_weight_dtype must be one of {sorted(L.GQ_WEIGHT_DTYPE)}")
+        if gq_group_size not in L.GQ_GROUP_SIZES:
+            raise ValueError(f"gq_group_size must be one of {L.GQ_GROUP_SIZES}")
+        if gq_weight_dtype != "none" and (weight_dtype != "auto" or mx_weight_dtype != "none"):
+            raise ValueError('gq_weight_dtype="uint4" cannot be combined with weight_dtype="fp8_e4m3" or mx_weight_dtype="fp4_e2m1"')
         L.check(self.lib.nvl_create(C.byref(self._c), C.byref(opts), C.byref(self.h)))
         self.weight_dtype = weight_dtype
+        self.gq_weight_dtype = gq_weight_dtype
+        self.gq_group_size = gq_group_size
+        if gq_weight_dtype != "none":
+            rc = self.lib.nvl_set_gq_weight_dtype(self.h, L.GQ_WEIGHT_DTYPE[gq_weight_dtype], int(gq_group_size))
+            if rc < 0:
+                msg = self.lib.nvl_last_error(self.h)
+                self.close()
+                raise L.NvlError(rc, msg.decode() if msg else "")
         self.mx_weight_dtype = mx_weight_dtype
         self.mx_expert_dtype = mx_expert_dtype
         self.mx_head_dtype = mx_head_dtype
@@ -225,6 +244,17 @@ class HipTransformerModel:
         L.check(self.lib.nvl_upload_tensor_mxfp4(self.h, L.SLOT_ID[slot], int(layer), codes.ctypes.data_as(C.c_void_p),
                                                  scales.ctypes.data_as(C.c_void_p), codes.shape[0], codes.shape[1] * 2,
                                                  L.LAYOUT_OUT_IN), self.h)
+
+    def upload_int4(self, slot: str, layer: int, codes, scales, zeros):
+        """nvl_upload_tensor_int4: pre-quantized codes [out][in/2] (even k in the low nibble), fp16 scales [out][in/g] (float16
+        values or their uint16 bit patterns) and zero points [out][in/g] (0..15)"""
+        codes = np.ascontiguousarray(codes, np.uint8)
+        scales = np.ascontiguousarray(scales)
+        scales = scales.view(np.uint16) if scales.dtype == np.float16 else np.ascontiguousarray(scales, np.uint16)
+        zeros = np.ascontiguousarray(zeros, np.uint8)
+        L.check(self.lib.nvl_upload_tensor_int4(self.h, L.SLOT_ID[slot], int(layer), codes.ctypes.data_as(C.c_void_p),
+                                                scales.ctypes.data_as(C.c_void_p), zeros.ctypes.data_as(C.c_void_p),
+                                                codes.shape[0], codes.shape[1] * 2, L.LAYOUT_OUT_IN), self.h)
 
     # -- sequences (replace kvCaches map[int64]*KVCache, tensor_model_runner.go:13) ----------------
     def seq_reset(self, seq_id: int):

@@ -141,6 +141,21 @@ def matmul_mxfp4w(a, w, device=0):                            # MatMul tensor.go
     return c, codes, scales
 
 
+def matmul_int4w(a, w, group, device=0):                      # MatMul tensor.go:62 with INT4 group-quantized weights (w4g.h)
+    """a [M][K], w [K][N] ([in, out]) -> (c, codes, scales, zeros): w quantized by the model's upload quantizer with groups
+    of `group` input features (codes [N][K/2] uint8, even k in the low nibble; scales [N][K/group] float16; zeros
+    [N][K/group] uint8), c = bf16(a) @ W~ through the model's GEMM dispatch, W~ = bf16(scales * (codes - zeros))."""
+    a, w = _f(a), _f(w)
+    m, k = a.shape
+    _, n = w.shape
+    c = np.empty((m, n), np.float32)
+    codes = np.empty((n, k // 2), np.uint8)
+    scales = np.empty((n, k // group), np.float16)
+    zeros = np.empty((n, k // group), np.uint8)
+    L.check(L.lib().nvl_op_matmul_int4w(device, _p(a), _p(w), m, n, k, int(group), _p(c), _p(codes), _p(scales), _p(zeros)))
+    return c, codes, scales, zeros
+
+
 def matmul_w8a8(a, w, device=0):                              # MatMul tensor.go:62 with 8-bit weights and activations (a8.h)
     """a [M][K], w [K][N] ([in, out]) -> (c, a_codes, a_scales): matmul_fp8w's dispatch in W8A8 mode.  The tile form
     quantizes bf16(a) per row (a_codes [M][K] uint8, a_scales [M]) and returns c = (e4m3(a_codes) @ e4m3(w codes)^T) * a_scales
