@@ -767,6 +767,26 @@ int nvl_op_ffn(int device, int precision, const float* x, const float* w1, const
 int nvl_op_moe(int device, int precision, const float* x, const float* router, const float* w_in,
                const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter,
                float* y);
+/* MoELayer.Forward moe.go:43-128 as a layer of the MODEL runs it (bf16 only; NVL_PRECISION_F32 is NVL_ERR_INVALID), with
+ * its stages: the op sets up what finalize and the workspace allocation set up (the experts' down matrices side by side
+ * along K where finalize would build them, the decode scratch, no debug taps), calls the model's MoE dispatch on a zeroed
+ * residual stream with multiplier 1, and completes what that leaves pending for the next norm the way debug mode 2 reads
+ * it.  So rows <= 64 take the decode ("dense-masked") form wherever a model would, and nvl_set_tuning keys 31 / 22 / 8 /
+ * 2 / 16 / 17 select the other forms.  Every scratch buffer the forms own is filled with 0xFF bytes (NaN as bf16 and as
+ * fp32) before the call: a read of something no launch wrote shows in y.  hidden % 64 == 0, inter % 32 == 0, n_experts <=
+ * 64.  (A sorted form on inter % 64 == 32 — a width nvl_create refuses — runs on experts zero-padded to inter + 32.)
+ * Out: y [rows][hidden]; router_logits [rows][n_experts], the fp32 logits the routing consumed; gate [rows][n_experts],
+ * the renormalised routing weight of (token, expert), 0 where the token did not pick the expert (moe.go:63-103; the
+ * sorted forms' expert ids / weights scattered on the host); *form, what ran. */
+enum {
+    NVL_MOE_FORM_DENSE_FUSED = 1,   /* dense-masked, router + routing in one launch */
+    NVL_MOE_FORM_DENSE = 2,         /* dense-masked, router GEMM then the gate-matrix launch */
+    NVL_MOE_FORM_PLAN = 3,          /* sort-based: one planning launch, grouped GEMMs */
+    NVL_MOE_FORM_GROUPED = 4        /* sort-based: route / histogram / scan / scatter launches, grouped GEMMs */
+};
+int nvl_op_moe_stages(int device, int precision, const float* x, const float* router, const float* w_in,
+                      const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter,
+                      float* y, float* router_logits, float* gate, int32_t* form);
 /* argmax cmd/ask/main.go:389-402 (first strict maximum) */
 int nvl_op_argmax(int device, const float* x, int rows, int cols, int32_t* out);
 

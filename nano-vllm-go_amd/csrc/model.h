@@ -173,6 +173,7 @@ struct nvl_model {
     float* moe_part = nullptr;        // decode: [MOE_DOWN_SLICES][64][H] K-slice partials of the down projection
     void* moe_xg = nullptr;           // bf16: the normed rows in expert order, fragment-major [round_up(Mmax*k, 64)][H] (prefill)
     int32_t *moe_counts = nullptr, *moe_cursor = nullptr, *moe_tile_map = nullptr, *moe_n_mtiles = nullptr;
+    int moe_form = 0;                 // the form the last moe() call took (NVL_MOE_FORM_*; nvl_op_moe_stages reports it)
     // decode split-K: partial slices of the last residual GEMM, consumed by the next norm launch
     float* rs_part = nullptr;    // deferred RMSNorm: [H/16][64] partial sums of x^2 (gemm.h)
     int ctx_hint = 0;    // longest context (keys) of the batch being enqueued; 0 = unknown (decode attention sizing)

@@ -1964,6 +1964,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
     const bool dense = moe_dense_ok(m, l, M) && m->pending_slices == 0;
     // decode: router logits, softmax, top-k and the dense gate matrix in one launch (gemm.h moe_router_gate_kernel)
     const bool fused_route = dense && g_moe_fused_route && E <= 64 && H % 32 == 0;
+    m->moe_form = dense ? (fused_route ? NVL_MOE_FORM_DENSE_FUSED : NVL_MOE_FORM_DENSE) : 0;      // (the sorted forms: below)
     {
         GemmArgs ar = mk(m->xn, H, l.t[NVL_T_ROUTER].p, m->router_logits, 128, nullptr, 1.f, M, E, H);
         if (deferred_norm) set_deferred_in(m, ar);
@@ -2004,12 +2005,16 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
             gemm(m, EPI_RESID, true, d, 2.0 * pairs * H * I);
             return true;
         }
-        GemmArgs d = mk(m->moe_hall, E * I, l.moe_out_cat, m->x, H, nullptr, 1.f, M, H, E * I);
+        // One slice (a prime E above MOE_DOWN_SLICES: 5, 7, 11, 13) is no K split: the kernel's single workgroup per column
+        // tile adds alpha x its sum into x itself and writes no partial, so nothing is left pending.  (This branch used to
+        // announce one pending slice all the same: the next norm then added the unwritten moe_part rows on top.)
         const int nsl = moe_down_slices(E);
-        d.moe_gate = m->moe_gate; d.moe_E = E; d.moe_I = I; d.sk_part = m->moe_part; d.sk_slices = nsl;
+        GemmArgs d = mk(m->moe_hall, E * I, l.moe_out_cat, m->x, H, nullptr, nsl > 1 ? 1.f : m->resid_alpha, M, H, E * I);
+        d.moe_gate = m->moe_gate; d.moe_E = E; d.moe_I = I;
+        if (nsl > 1) { d.sk_part = m->moe_part; d.sk_slices = nsl; }
         m->site = KS_MOE_DOWN; m->site_bytes = e_touch * H * I * eb + e_touch * M * I * (double)m->wsize + (double)nsl * M * H * 4.0;
         gemm(m, EPI_RESID, true, d, 2.0 * pairs * H * I);
-        m->pending_part = m->moe_part; m->pending_slices = nsl; m->pending_rows = M; m->pending_alpha = m->resid_alpha;
+        if (nsl > 1) { m->pending_part = m->moe_part; m->pending_slices = nsl; m->pending_rows = M; m->pending_alpha = m->resid_alpha; }
         return false;
     }
     // decode-sized batches: one planning launch, and the weighted combine rides on the norm that follows
@@ -2019,6 +2024,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
     // prefill default: 256-row m-tiles on the ping-pong kernel (needs the rows copied into expert order and K >= 160)
     const bool pp = !m->f32 && !small && g_moe_bm == 0 && m->moe_xg && g_moe_gather && H >= 160 && I >= 160 && (2 * I) % 256 == 0 && H % 256 == 0;
     const int BM = pp ? 256 : ((!m->f32 && !small && g_moe_bm == 256) ? 256 : 128);
+    m->moe_form = small ? NVL_MOE_FORM_PLAN : NVL_MOE_FORM_GROUPED;
     if (small) {
         KScope ks(m, KC_OTHER, 0, KS_MOE_PLAN);
         hipLaunchKernelGGL(moe_plan_kernel, dim3(1), dim3(M <= 4 ? 256 : (M <= 8 ? 512 : 1024)), 0, m->stream, m->router_logits, 128, M, E, k, 128, m->expert_ids,

@@ -666,6 +666,119 @@ extern "C" int nvl_op_moe(int device, int precision, const float* x, const float
     OP_CATCH
 }
 
+// moe() as a layer of the model runs it, stage by stage: finalize's weight forms (the interleaved gate|up rows with their
+// zero pad rows, the down matrices side by side along K under finalize's own predicate), the decode scratch of the
+// workspace allocation, keep_hidden off — so moe_dense_ok() answers as it does in a model —, then whatever moe() left for
+// the next norm completed by tap_hidden_kernel, as tap_layer does.  Every scratch buffer a form owns starts as 0xFF bytes
+// (NaN in bf16 and in fp32): the columns of an expert nobody picked, an unwritten K slice or a stale row show in y.
+extern "C" int nvl_op_moe_stages(int device, int precision, const float* x, const float* router, const float* w_in,
+                                 const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter, float* y,
+                                 float* router_logits, float* gate, int32_t* form) {
+    if (!x || !router || !w_in || !w_out || !y || !router_logits || !gate || !form || precision != NVL_PRECISION_BF16 || rows <= 0 ||
+        rows > (1 << 16) || hidden <= 0 || hidden % 64 || inter <= 0 || inter % 32 || n_experts < 1 || n_experts > 64 || top_k < 1 ||
+        top_k > n_experts)
+        return op_fail("nvl_op_moe_stages: bad arguments (bf16 only; hidden % 64, inter % 32, top_k <= n_experts <= 64)");
+    OP_TRY
+    OpCtx cx(device, precision);
+    nvl_model& m = cx.m;
+    const int E = n_experts, H = hidden, k = top_k;
+    const int64_t pairs = (int64_t)rows * k, hp = round_up(H, W_ROW_PAD);
+    auto nan_fill = [&](int64_t bytes) { void* p = cx.alloc(bytes); NVL_HIP(hipMemsetAsync(p, 0xFF, (size_t)bytes, m.stream)); return p; };
+    m.H = H; m.F = inter;
+    m.cfg.num_experts = E; m.cfg.num_experts_per_tok = k; m.cfg.use_moe = 1;
+    m.cfg.residual_multiplier = 0.f; m.resid_alpha = 1.f;      // multiplier 1 both ways (nvl_create's reading of 0)
+    m.keep_hidden = false;
+    LayerW l;
+    // the decode form's scratch (nvl_create) and weight (finalize, under its dense_form predicate)
+    m.moe_gate = (float*)nan_fill(64 * (int64_t)E * 4);
+    m.moe_hall = nan_fill(64 * (int64_t)E * inter * 2);
+    m.moe_part = (float*)nan_fill((int64_t)MOE_DOWN_SLICES * 64 * H * 4);
+    const bool dense_form = inter % 32 == 0 && H % 16 == 0 && E <= 64 && E / moe_down_slices(E) <= 16;
+    if (dense_form) l.moe_out_cat = cx.alloc(hp * E * inter * 2);
+    // The grouped GEMMs of the sorted forms stream K in 64-wide tiles (nvl_create refuses ffn_dim % 64 != 0), the decode
+    // kernels in 32-wide k-steps: a call that will not take the dense form on inter % 64 == 32 runs on experts padded
+    // with 32 zero columns — h = silu(0) * 0 = 0 there, times a zero weight: every sum gains exact zeros.
+    const int I = (!moe_dense_ok(&m, l, rows) && inter % 64) ? inter + 32 : inter;
+    if (I != inter) { l.moe_out_cat = nullptr; m.F = I; }
+    std::vector<float> pin, pout;
+    {   // host copies: [E][2I][H] (gate rows, then up rows) and [E][H][I], + 128 zero rows after the last expert's down
+        // matrix (the grouped down GEMM stages 128 weight rows of an expert whatever H is)
+        pout.assign((size_t)(((int64_t)E * H + 128) * I), 0.f);
+        for (int64_t r = 0; r < (int64_t)E * H; r++) memcpy(&pout[(size_t)(r * I)], w_out + r * inter, (size_t)inter * 4);
+        if (I != inter) {
+            pin.assign((size_t)((int64_t)E * 2 * I * H), 0.f);
+            for (int64_t e = 0; e < E; e++)
+                for (int half = 0; half < 2; half++)
+                    memcpy(&pin[(size_t)((e * 2 * I + (int64_t)half * I) * H)], w_in + (e * 2 * inter + (int64_t)half * inter) * H, (size_t)inter * H * 4);
+        }
+    }
+    m.xn = cx.up_mat(x, rows, H, false);
+    l.t[NVL_T_ROUTER].p = cx.up_mat(router, E, H, true, W_ROW_PAD);
+    void* inc = cx.up_mat(I != inter ? pin.data() : w_in, (int64_t)E * 2 * I, H, false, W_ROW_PAD);
+    std::vector<int32_t> idx;
+    for (int e = 0; e < E; e++) {
+        auto one = swiglu_interleave(I, (int64_t)e * 2 * I);
+        idx.insert(idx.end(), one.begin(), one.end());
+    }
+    idx.resize((size_t)round_up((int64_t)E * 2 * I, W_ROW_PAD), -1);      // (+ zero pad rows: the decode kernels read whole tiles)
+    l.moe_in = cx.alloc((int64_t)idx.size() * H * 2);
+    gather_rows(&m, inc, idx, l.moe_in, H);
+    l.t[NVL_T_MOE_OUT].p = cx.up_mat(pout.data(), (int64_t)E * H + 128, I, false, W_ROW_PAD);
+    if (l.moe_out_cat) {
+        NVL_HIP(hipMemsetAsync(l.moe_out_cat, 0, (size_t)(hp * E * I) * 2, m.stream));
+        hipLaunchKernelGGL(moe_cat_down_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m.stream,
+                           (const bf16_t*)l.t[NVL_T_MOE_OUT].p, (bf16_t*)l.moe_out_cat, H, I, E);
+        NVL_HIP(hipGetLastError());
+    }
+    // the sorted forms' workspaces (nvl_create)
+    m.router_logits = (float*)nan_fill((int64_t)rows * 128 * 4);
+    m.expert_ids = (int32_t*)cx.alloc(pairs * 4); m.expert_w = (float*)cx.alloc(pairs * 4);
+    m.seg_start = (int32_t*)cx.alloc((E + 1) * 4);
+    m.moe_counts = (int32_t*)cx.alloc(E * 4); m.moe_cursor = (int32_t*)cx.alloc(E * 4);
+    m.moe_tile_map = (int32_t*)cx.alloc(16 * (cdiv(pairs, 128) + E)); m.moe_n_mtiles = (int32_t*)cx.alloc(16);
+    m.perm_token = (int32_t*)cx.alloc(pairs * 4); m.slot_of = (int32_t*)cx.alloc(pairs * 4);
+    m.moe_eo = (float*)nan_fill(pairs * H * 4);
+    m.moe_xg = cx.alloc(round_up(pairs, 64) * H * 2);
+    m.hbuf = nan_fill(round_up(pairs, 64) * I * 2);
+    m.x = (float*)cx.alloc((int64_t)rows * H * 4);
+    NVL_HIP(hipMemsetAsync(m.x, 0, (size_t)rows * H * 4, m.stream));
+    moe(&m, l, rows);
+    *form = m.moe_form;
+    float* yd = (float*)cx.alloc((int64_t)rows * H * 4);
+    if (m.pending_slices == 0) {
+        NVL_HIP(hipMemcpyAsync(yd, m.x, (size_t)rows * H * 4, hipMemcpyDeviceToDevice, m.stream));
+    } else {       // what the next norm would add on its read of x
+        PendingResid pr{m.pending_part, m.pending_slices, m.pending_rows, m.pending_alpha, m.pending_slot_of, m.pending_gate_w};
+        hipLaunchKernelGGL(tap_hidden_kernel, dim3(rows), dim3(256), 0, m.stream, m.x, yd, H, pr);
+        NVL_HIP(hipGetLastError());
+    }
+    cx.down(y, yd, (int64_t)rows * H);
+    std::vector<float> lg((size_t)rows * 128);
+    cx.down(lg.data(), m.router_logits, (int64_t)rows * 128);
+    for (int r = 0; r < rows; r++) memcpy(router_logits + (size_t)r * E, &lg[(size_t)r * 128], (size_t)E * 4);
+    if (m.moe_form == NVL_MOE_FORM_DENSE_FUSED || m.moe_form == NVL_MOE_FORM_DENSE) {
+        cx.down(gate, m.moe_gate, (int64_t)rows * E);
+    } else {       // (token, rank) -> dense
+        std::vector<int32_t> ids((size_t)pairs);
+        std::vector<float> gw((size_t)pairs);
+        NVL_HIP(hipMemcpyAsync(ids.data(), m.expert_ids, (size_t)pairs * 4, hipMemcpyDeviceToHost, m.stream));
+        cx.down(gw.data(), m.expert_w, pairs);
+        std::fill(gate, gate + (size_t)rows * E, 0.f);
+        for (int64_t i = 0; i < pairs; i++) {
+            if (ids[(size_t)i] < 0 || ids[(size_t)i] >= E) return op_fail("nvl_op_moe_stages: the routing chose an expert out of range", NVL_ERR_STATE);
+            gate[(size_t)((i / k) * E + ids[(size_t)i])] = gw[(size_t)i];
+        }
+    }
+    l.moe_in = nullptr; l.moe_out_cat = nullptr; l.t[NVL_T_ROUTER].p = nullptr; l.t[NVL_T_MOE_OUT].p = nullptr;
+    m.xn = m.hbuf = nullptr; m.x = nullptr; m.router_logits = nullptr; m.expert_ids = nullptr;
+    m.expert_w = nullptr; m.seg_start = m.perm_token = m.slot_of = nullptr; m.moe_eo = nullptr; m.moe_xg = nullptr;
+    m.moe_counts = m.moe_cursor = m.moe_tile_map = m.moe_n_mtiles = nullptr;
+    m.moe_gate = nullptr; m.moe_hall = nullptr; m.moe_part = nullptr;
+    m.pending_part = nullptr; m.pending_slices = 0; m.pending_slot_of = nullptr; m.pending_gate_w = nullptr;
+    return NVL_OK;
+    OP_CATCH
+}
+
 extern "C" int nvl_op_argmax(int device, const float* x, int rows, int cols, int32_t* out) {
     if (!x || !out || rows <= 0 || cols <= 0) return op_fail("nvl_op_argmax: bad arguments");
     OP_TRY

@@ -219,6 +219,28 @@ def moe_forward(x, router, w_in, w_out, top_k, precision="bf16", device=0):   # 
     return y
 
 
+MOE_FORMS = {1: "dense_fused", 2: "dense", 3: "plan", 4: "grouped"}      # NVL_MOE_FORM_*
+
+
+def moe_stages(x, router, w_in, w_out, top_k, precision="bf16", device=0):   # MoELayer.Forward moe.go:43
+    """The MoE block as a layer of the model runs it (nvl_op_moe_stages: the decode form wherever a model would take it,
+    every scratch buffer pre-filled with NaN).  x [rows][H], router [H][E], w_in [E][2I][H], w_out [E][H][I] ->
+    dict(y [rows][H], router_logits [rows][E], gate [rows][E] (0 = not picked), form (a MOE_FORMS name))."""
+    x, router, w_in, w_out = _f(x), _f(router), _f(w_in), _f(w_out)
+    rows, hidden = x.shape
+    E, I = router.shape[1], w_out.shape[2]
+    if router.shape != (hidden, E) or w_in.shape != (E, 2 * I, hidden) or w_out.shape != (E, hidden, I):
+        raise ValueError("moe_stages: shapes do not match")
+    out = dict(y=np.empty((rows, hidden), np.float32), router_logits=np.empty((rows, E), np.float32),
+               gate=np.empty((rows, E), np.float32))
+    form = C.c_int32(0)
+    L.check(L.lib().nvl_op_moe_stages(device, L.PRECISION[precision], _p(x), _p(router), _p(w_in), _p(w_out), rows, hidden, E,
+                                      int(top_k), I, _p(out["y"]), _p(out["router_logits"]), _p(out["gate"]),
+                                      C.cast(C.byref(form), C.c_void_p)))
+    out["form"] = MOE_FORMS[form.value]
+    return out
+
+
 def argmax(x, device=0):                                       # argmax cmd/ask/main.go:389
     x = _f(x)
     if x.ndim == 1:

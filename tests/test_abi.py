@@ -9,10 +9,10 @@ import pytest
 def test_library_exports_every_declared_symbol(pkg):
     L = pkg.lib()
     names = pkg.declared_symbols()
-    assert len(names) >= 30 and "nvl_forward" in names and "nvl_runner_run" in names
+    assert len(names) >= 30 and "nvl_forward" in names and "nvl_runner_run" in names and "nvl_op_moe_stages" in names
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing
-    assert L.nvl_abi_version() == 3
+    assert L.nvl_abi_version() == 3                                 # (nvl_op_moe_stages is an addition: the version stays)
 
 
 def test_header_cites_the_reference_for_every_entry_point(pkg):
@@ -46,6 +46,24 @@ def test_no_cpu_fallback(pkg):
     with pytest.raises(pkg.NvlError) as e:
         pkg.ops.mat_mul(np.zeros((1, 64), np.float32), np.zeros((64, 16), np.float32))
     assert e.value.code == -8
+
+
+def test_moe_stages_refuses_bad_arguments_before_touching_a_device(pkg):
+    """nvl_op_moe_stages is bf16 only, and its shape rules are checked before the device probe (NVL_ERR_INVALID, not
+    NVL_ERR_NO_DEVICE, on a machine without a GPU)."""
+    import numpy as np
+    z = np.zeros
+    for kw, shape in ((dict(precision="f32"), (2, 64, 4, 64)), (dict(), (2, 64, 4, 48)), (dict(top_k=5), (2, 64, 4, 64)),
+                      (dict(), (2, 64, 65, 64))):
+        M, H, E, I = shape
+        with pytest.raises(pkg.NvlError) as e:
+            pkg.ops.moe_stages(z((M, H), np.float32), z((H, E), np.float32), z((E, 2 * I, H), np.float32), z((E, H, I), np.float32),
+                               kw.get("top_k", 2), precision=kw.get("precision", "bf16"))
+        assert e.value.code == -1, (kw, shape)                      # NVL_ERR_INVALID
+    assert pkg.ops.MOE_FORMS == {1: "dense_fused", 2: "dense", 3: "plan", 4: "grouped"}
+    text = pkg._lib.HEADER.read_text()
+    for code, name in enumerate(("DENSE_FUSED", "DENSE", "PLAN", "GROUPED"), 1):
+        assert re.search(rf"NVL_MOE_FORM_{name} = {code}\b", text), name
 
 
 def test_product_package_never_imports_the_oracle(pkg):
