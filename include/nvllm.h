@@ -733,6 +733,41 @@ int nvl_op_fp8_kv_roundtrip(int device, const float* x, int64_t n, float scale, 
  * same quantizer, then the 8-bit attention kernels run (S == 1: decode kernel, key split at long T; else prefill). */
 int nvl_op_attention_kv8(int device, const float* q, const float* k, const float* v, int nH, int nKV, int S, int T,
                          int hd, float scale, float k_scale, float v_scale, float* out);
+/* The attention of one layer on a BATCH laid out as the paged front end lays it out (generic_model.go:276-480 over
+ * block_manager.go's block tables), through the model's own attention dispatch: n_seqs sequences, sequence i with
+ * seq_len[i] new rows (token rows back to back in sequence order) behind seq_pos[i] cached keys; row j sees keys
+ * 0 .. seq_pos[i] + j.  k_pool / v_pool [n_blocks][nKV][block_size][hd] (block_size % 64 == 0) are the layer's K / V
+ * blocks, block_table [n_seqs][tbl_stride] names each sequence's blocks and reaches the kernels verbatim, unused
+ * entries included.  Set up as a model has it: the longest context as the decode-attention hint, the split-K scratch and
+ * its zeroed tickets; the output rows and that scratch start as 0xFF bytes (NaN), so `out` is finite only if nothing
+ * unwritten was read.  Every seq_len == 1 takes the decode kernels, otherwise the prefill kernels; nvl_set_tuning keys 15 /
+ * 25 / 35 act as in a model.  `form`:
+ *   NVL_ATTN_OP_PLAIN  q [tokens][nH][hd], K / V of the new rows already in the pools (bf16 or f32)
+ *   NVL_ATTN_OP_FUSED  bf16, every seq_len == 1: q holds the fp32 QKV rows [n_seqs][(nH + 2 nKV) hd]; the decode kernel
+ *                      applies RoPE (tables [max_seq][hd] for rope_base; rope_base == 0: none), patches the new key into
+ *                      its tile and appends K / V to the pools, which are written back to k_pool / v_pool as fp32
+ *   NVL_ATTN_OP_MQ     bf16: PLAIN with the verify pass's flag (2..8 rows per sequence run the multi-position kernel)
+ *   NVL_ATTN_OP_KV8    bf16: the pools are quantized with k_scale / v_scale by the cache's own quantizer first
+ * Out: out [tokens][nH][hd]; ran[3] = {NVL_ATTN_RAN_* of the kernel that ran, waves per workgroup, workgroups per
+ * (sequence, kv head) of a key split}; part_cnt [32], the split's tickets after the launch (all zero again).
+ * Refused before anything is launched: what the paged front end refuses — a negative position (NVL_ERR_INVALID),
+ * seq_pos + seq_len > max_seq (NVL_ERR_POSITION), a table too short for seq_pos + seq_len — and ANY table entry outside
+ * [0, n_blocks).  More than 128 table entries per sequence are refused by the bf16 prefill kernel's launch. */
+enum { NVL_ATTN_OP_PLAIN = 0, NVL_ATTN_OP_FUSED = 1, NVL_ATTN_OP_MQ = 2, NVL_ATTN_OP_KV8 = 3 };
+enum {
+    NVL_ATTN_RAN_F32 = 1,             /* attn_f32_kernel */
+    NVL_ATTN_RAN_PREFILL = 2,         /* attn_prefill_bf16_kernel */
+    NVL_ATTN_RAN_PREFILL_KV8 = 3,     /* attn_prefill_kv8_kernel */
+    NVL_ATTN_RAN_DECODE = 4,          /* attn_decode_bf16_kernel, Q / K / V prepared by earlier launches */
+    NVL_ATTN_RAN_DECODE_FUSED = 5,    /* attn_decode_bf16_kernel with RoPE + append */
+    NVL_ATTN_RAN_DECODE_KV8 = 6,      /* attn_decode_kv8_kernel */
+    NVL_ATTN_RAN_DECODE_MQ = 7,       /* attn_decode_mq_bf16_kernel */
+    NVL_ATTN_RAN_DECODE_STAMPED = 8   /* the diagnostic instantiation of the fused form (nvl_set_debug mode 4) */
+};
+int nvl_op_attention_batch(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                           const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                           int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                           int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt);
 /* 8-bit weights: tensor.MatMul (tensor.go:62-88) with b = w [K][N] quantized by the model's upload quantizer
  * (NVL_W_FP8_E4M3), c [M][N] = bf16(a) · W~ through the model's own GEMM dispatch (M selects the decode or the tile form).
  * codes_out [N][K] / scales_out [N] (either may be NULL) receive the quantized weight.  K % 64 == 0. */

@@ -217,6 +217,8 @@ def lib():
     L.nvl_decode_greedy_lookup.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.nvl_op_attention_mq.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]
     L.nvl_op_moe_stages.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp] + [C.c_int] * 5 + [vp] * 4
+    L.nvl_op_attention_batch.argtypes = ([C.c_int] * 6 + [f32, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_double,
+                                          C.c_int, f32, f32, vp, vp, vp])
     L.nvl_op_mamba_mixer.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp] + [C.c_int] * 6 + [vp] * 8 + [C.c_int] + [vp] * 4
     sp = C.POINTER(SamplingParamsC)
     L.nvl_verify_sampled.argtypes = [vp, C.c_int, vp, vp, C.c_int, sp, vp, vp, vp, vp, vp]

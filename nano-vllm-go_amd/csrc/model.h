@@ -176,6 +176,7 @@ struct nvl_model {
     int moe_form = 0;                 // the form the last moe() call took (NVL_MOE_FORM_*; nvl_op_moe_stages reports it)
     // decode split-K: partial slices of the last residual GEMM, consumed by the next norm launch
     float* rs_part = nullptr;    // deferred RMSNorm: [H/16][64] partial sums of x^2 (gemm.h)
+    int attn_ran[3] = {0, 0, 0};      // the last attention launch: kernel form (NVL_ATTN_RAN_*), waves per workgroup, key split (nvl_op_attention_batch reports them)
     int ctx_hint = 0;    // longest context (keys) of the batch being enqueued; 0 = unknown (decode attention sizing)
     float* sk_part = nullptr; int sk_max_slices = 4; int pending_slices = 0, pending_rows = 0; float pending_alpha = 1.f; const float* pending_part = nullptr;
     int sk_rows = 64;             // rows the sk_part slices are allocated for

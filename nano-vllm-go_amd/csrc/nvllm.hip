@@ -247,6 +247,21 @@ extern "C" int nvl_device_count(void) {
 
 extern "C" const char* nvl_last_error(const nvl_model* m) { return m ? m->err.c_str() : g_create_err.c_str(); }
 
+// The RoPE tables [max_seq][hd] in fp64 on the host, exactly as NewRoPECache (rope.go:18-50): both halves of a row hold
+// the same hd/2 values (nvl_create's tables; nvl_op_attention_batch builds its own with the same function)
+static void rope_tables(double base, int max_seq, int hd, std::vector<float>& ct, std::vector<float>& st) {
+    const int half = hd / 2;
+    ct.resize((size_t)max_seq * hd); st.resize((size_t)max_seq * hd);
+    for (int pos = 0; pos < max_seq; pos++)
+        for (int i = 0; i < half; i++) {
+            const double freq = 1.0 / std::pow(base, (double)(2 * i) / (double)hd);
+            const double ang = (double)pos * freq;
+            const float cv = (float)std::cos(ang), sv = (float)std::sin(ang);
+            ct[(size_t)pos * hd + i] = cv; ct[(size_t)pos * hd + half + i] = cv;
+            st[(size_t)pos * hd + i] = sv; st[(size_t)pos * hd + half + i] = sv;
+        }
+}
+
 extern "C" int nvl_create(const nvl_model_config* cfg, const nvl_runtime_opts* opts, nvl_model** out) {
     if (!cfg || !opts || !out) return fail(nullptr, NVL_ERR_INVALID, "nvl_create: null argument");
     *out = nullptr;
@@ -1223,16 +1238,8 @@ extern "C" int nvl_finalize(nvl_model* m) {
     if (c.attention_type == NVL_ATTN_MQA) { rope = true; base = 10000.0; }           // mqa.go:35
     else if (c.attention_type == NVL_ATTN_GQA && c.position_type == NVL_POS_ROPE) rope = true;
     if (rope) {
-        const int half = (int)hd / 2;
-        std::vector<float> ct((size_t)c.max_seq_len * hd), stt((size_t)c.max_seq_len * hd);
-        for (int pos = 0; pos < c.max_seq_len; pos++)
-            for (int i = 0; i < half; i++) {
-                const double freq = 1.0 / std::pow(base, (double)(2 * i) / (double)hd);
-                const double ang = (double)pos * freq;
-                const float cv = (float)std::cos(ang), sv = (float)std::sin(ang);
-                ct[(size_t)pos * hd + i] = cv; ct[(size_t)pos * hd + half + i] = cv;
-                stt[(size_t)pos * hd + i] = sv; stt[(size_t)pos * hd + half + i] = sv;
-            }
+        std::vector<float> ct, stt;
+        rope_tables(base, c.max_seq_len, (int)hd, ct, stt);
         m->rope_cos = dmalloc<float>((int64_t)ct.size());
         m->rope_sin = dmalloc<float>((int64_t)stt.size());
         NVL_HIP(hipMemcpy(m->rope_cos, ct.data(), ct.size() * 4, hipMemcpyHostToDevice));
@@ -1638,8 +1645,11 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
     a.nH = m->nH; a.nKV = m->nKV; a.group = m->group; a.scale = m->attn_scale;
     KScope ks(m, KC_ATTN, flops, KS_ATTN, abytes);
     if (m->f32) {
-        const size_t lds = (size_t)m->Tmax * 4;
+        // one score per key a row can see: up to blocks_per_seq blocks of Tmax keys (slab mode: the one block)
+        const size_t lds = (size_t)m->Tmax * m->blocks_per_seq * 4;
+        if (lds > 64 * 1024) NVL_LDS_ATTR(attn_f32_kernel, 160 * 1024 - 64);
         hipLaunchKernelGGL(attn_f32_kernel, dim3(max_len, m->nH, n_seqs), dim3(256), lds, m->stream, a, m->hd);
+        m->attn_ran[0] = NVL_ATTN_RAN_F32; m->attn_ran[1] = 4; m->attn_ran[2] = 1;
     } else if (mq && !kv8 && attention_mq_ok(m, max_len)) {
         const int nw = decode_attn_cfg(m, n_seqs, max_len) & 255;
         dim3 grid(m->nKV * cdiv(m->group * max_len, 16), n_seqs, 1);     // (kv head x 16-row query tile, sequence); no key split
@@ -1649,6 +1659,7 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         if (m->hd == 64) launch_decode_attn<NVL_DEC_MQ(64, 2), NVL_DEC_MQ(64, 4), NVL_DEC_MQ(64, 8)>(m, grid, nw, 64 * 64 * 2, a, max_len);
         else launch_decode_attn<NVL_DEC_MQ(128, 2), NVL_DEC_MQ(128, 4), NVL_DEC_MQ(128, 8)>(m, grid, nw, 64 * 128 * 2, a, max_len);
 #undef NVL_DEC_MQ
+        m->attn_ran[0] = NVL_ATTN_RAN_DECODE_MQ; m->attn_ran[1] = nw; m->attn_ran[2] = 1;
     } else if (max_len == 1) {
         const int cfg = decode_attn_cfg(m, n_seqs), nsplit = cfg >> 8;
         dim3 grid(m->nKV * cdiv(m->group, 16), n_seqs, nsplit);      // (kv head x 16-head query tile, sequence, key split)
@@ -1675,6 +1686,8 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         else if (a.stamps) NVL_DEC(64, NVL_DEC_STAMP);
         else if (fused_qkv) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_FUSED); else NVL_DEC(128, NVL_DEC_FUSED); }
         else { if (m->hd == 64) NVL_DEC(64, NVL_DEC_PLAIN); else NVL_DEC(128, NVL_DEC_PLAIN); }
+        m->attn_ran[0] = kv8 ? NVL_ATTN_RAN_DECODE_KV8 : (a.stamps ? NVL_ATTN_RAN_DECODE_STAMPED : (fused_qkv ? NVL_ATTN_RAN_DECODE_FUSED : NVL_ATTN_RAN_DECODE));
+        m->attn_ran[1] = nw; m->attn_ran[2] = nsplit;
 #undef NVL_DEC_STAMP
 #undef NVL_DEC_FUSED
 #undef NVL_DEC_PLAIN
@@ -1684,6 +1697,7 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         // 256 query rows (position x head-in-group, position-major) per workgroup of 8 waves
         const int64_t qrows = (int64_t)max_len * m->group;
         dim3 grid(m->nKV, n_seqs, cdiv(qrows, 256));      // (kv head fastest, query tile slowest: attn.h)
+        m->attn_ran[0] = kv8 ? NVL_ATTN_RAN_PREFILL_KV8 : NVL_ATTN_RAN_PREFILL; m->attn_ran[1] = 8; m->attn_ran[2] = 1;
         if (kv8) {     // K/V tiles through registers into one bf16 image pair
             if (m->hd == 64) {
                 hipLaunchKernelGGL((attn_prefill_kv8_kernel<64>), grid, dim3(512), attn_prefill_kv8_lds_bytes<64>(), m->stream, a, kv8[0], kv8[1]);

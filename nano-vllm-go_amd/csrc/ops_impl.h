@@ -582,6 +582,143 @@ extern "C" int nvl_op_attention_kv8(int device, const float* q, const float* k, 
     OP_CATCH
 }
 
+// attention() / attention_kv8() on a batch as plan_paged lays it out, set up as nvl_create sets a model up: Tmax = the block
+// size, slot_stride = one block of one layer, blocks_per_seq = the table's stride, ctx_hint as attn_cost computes it, the
+// split scratch and its zeroed tickets.  attn_out and attn_part start as 0xFF bytes (NaN in bf16 and fp32): a row nobody
+// wrote, or a partial record read before its workgroup wrote it, shows in `out`.  Nothing that could index outside the
+// pools reaches a kernel: every table entry is checked, used or not.
+extern "C" int nvl_op_attention_batch(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                                      const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                                      int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                                      int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt) {
+    const char* who = "nvl_op_attention_batch: ";
+    if (!seq_len || !seq_pos || !k_pool || !v_pool || !block_table || !q || !out || !ran || !part_cnt || nH <= 0 || nKV <= 0 ||
+        nH % nKV || (hd != 64 && hd != 128) || n_seqs <= 0 || n_seqs > 4096 || n_blocks <= 0 || block_size <= 0 || block_size % 64 ||
+        tbl_stride <= 0 || max_seq <= 0 || form < NVL_ATTN_OP_PLAIN || form > NVL_ATTN_OP_KV8 ||
+        (precision != NVL_PRECISION_BF16 && precision != NVL_PRECISION_F32) || !(scale >= 0.f) || !std::isfinite(scale))
+        return op_fail(std::string(who) + "bad arguments");
+    const bool fused = form == NVL_ATTN_OP_FUSED, kv8 = form == NVL_ATTN_OP_KV8, mq = form == NVL_ATTN_OP_MQ;
+    if (form != NVL_ATTN_OP_PLAIN && precision != NVL_PRECISION_BF16) return op_fail(std::string(who) + "the fused, mq and kv8 forms are bf16 only");
+    if (kv8 && (!(k_scale > 0.f) || !(v_scale > 0.f) || !std::isfinite(k_scale) || !std::isfinite(v_scale)))
+        return op_fail(std::string(who) + "k_scale / v_scale must be finite and positive");
+    if (fused && (!(rope_base >= 0.0) || !std::isfinite(rope_base))) return op_fail(std::string(who) + "rope_base must be finite and >= 0");
+    // plan_paged's refusals, in its order, then the rest of the table
+    int64_t tokens = 0;
+    int max_len = 0, ctx = 0;
+    for (int i = 0; i < n_seqs; i++) {
+        if (seq_len[i] <= 0 || seq_len[i] > (1 << 16)) return op_fail(std::string(who) + "sequence without rows (or more than 65536)");
+        if (fused && seq_len[i] != 1) return op_fail(std::string(who) + "the fused form is a decode step: one row per sequence");
+        if (seq_pos[i] < 0) return op_fail(std::string(who) + "negative position");
+        if (seq_pos[i] > max_seq - seq_len[i]) return op_fail(std::string(who) + "position exceeds max_seq", NVL_ERR_POSITION);
+        if (tbl_stride < cdiv((int64_t)seq_pos[i] + seq_len[i], block_size))
+            return op_fail(std::string(who) + "block table shorter than the positions it must cover");
+        tokens += seq_len[i];
+        max_len = std::max(max_len, seq_len[i]);
+        ctx = std::max(ctx, seq_pos[i] + seq_len[i]);
+    }
+    if (tokens > (1 << 16)) return op_fail(std::string(who) + "more than 65536 rows");
+    for (int64_t i = 0; i < (int64_t)n_seqs * tbl_stride; i++)
+        if (block_table[i] < 0 || block_table[i] >= n_blocks) return op_fail(std::string(who) + "block id out of range");
+    if (precision == NVL_PRECISION_F32 && (int64_t)tbl_stride * block_size > 12000)
+        return op_fail(std::string(who) + "block table too long for the f32 kernel");
+    OP_TRY
+    OpCtx cx(device, precision);
+    nvl_model& m = cx.m;
+    auto nan_fill = [&](int64_t bytes) { void* p = cx.alloc(bytes); NVL_HIP(hipMemsetAsync(p, 0xFF, (size_t)bytes, m.stream)); return p; };
+    const int64_t W = (int64_t)nH * hd, n_el = (int64_t)n_blocks * nKV * block_size * hd;
+    m.nH = nH; m.nKV = nKV; m.group = nH / nKV; m.hd = hd; m.L = 1;
+    m.paged = 1; m.Tmax = block_size; m.num_blocks = n_blocks; m.blocks_per_seq = tbl_stride;
+    m.layer_stride = (int64_t)nKV * block_size * hd; m.slot_stride = m.layer_stride;
+    m.n_qkv = (nH + 2 * nKV) * hd;
+    m.attn_scale = scale != 0.f ? scale : 1.0f / std::sqrt((float)hd);
+    m.kv8 = kv8; m.kv_esize = kv8 ? 1 : (int)m.wsize;
+    uint8_t *k8 = nullptr, *v8 = nullptr;
+    if (kv8) {      // the 8-bit blocks, written by the shared quantizer from the fp32 values
+        const float* dk = cx.up_f32(k_pool, n_el);
+        const float* dv = cx.up_f32(v_pool, n_el);
+        k8 = (uint8_t*)cx.alloc(n_el); v8 = (uint8_t*)cx.alloc(n_el);
+        const unsigned qblocks = (unsigned)cdiv(cdiv(n_el, 4), 256);
+        hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dk, n_el, k_scale, k8);
+        hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dv, n_el, v_scale, v8);
+        NVL_HIP(hipGetLastError());
+    } else {
+        m.kcache = cx.up_mat(k_pool, 1, n_el, false, 1, true);
+        m.vcache = cx.up_mat(v_pool, 1, n_el, false, 1, true);
+    }
+    if (fused) {
+        m.qkv = cx.up_f32(q, (int64_t)n_seqs * m.n_qkv);
+        if (rope_base > 0.0) {
+            std::vector<float> ct, st;
+            rope_tables(rope_base, max_seq, hd, ct, st);
+            m.rope_cos = cx.up_f32(ct.data(), (int64_t)ct.size());
+            m.rope_sin = cx.up_f32(st.data(), (int64_t)st.size());
+        }
+    } else {
+        m.q = cx.up_mat(q, tokens, W, false, 1, true);
+    }
+    m.attn_out = nan_fill(round_up(tokens, 64) * W * (int64_t)m.wsize);
+    if (!m.f32) {       // (nvl_create: the split scratch of every bf16 model with a head size the kernels have)
+        m.attn_part = (float*)nan_fill((int64_t)ATTN_SPLIT_MAX_PAIRS * ATTN_SPLIT_MAX * (hd == 64 ? attn_part_floats<64>() : attn_part_floats<128>()) * 4);
+        m.attn_part_cnt = (int32_t*)cx.alloc(ATTN_SPLIT_MAX_PAIRS * 4);
+        NVL_HIP(hipMemsetAsync(m.attn_part_cnt, 0, ATTN_SPLIT_MAX_PAIRS * 4, m.stream));
+    }
+    // the pass's metadata as plan_paged / plan_rows leave it: [tok_start | len | pos | tbl | the table, verbatim]
+    std::vector<int32_t> meta((size_t)4 * n_seqs + (size_t)n_seqs * tbl_stride);
+    for (int i = 0, t = 0; i < n_seqs; t += seq_len[i], i++) {
+        meta[(size_t)i] = t; meta[(size_t)n_seqs + i] = seq_len[i]; meta[(size_t)2 * n_seqs + i] = seq_pos[i];
+        meta[(size_t)3 * n_seqs + i] = i * tbl_stride;
+    }
+    memcpy(&meta[(size_t)4 * n_seqs], block_table, (size_t)n_seqs * tbl_stride * 4);
+    int32_t* dmeta = (int32_t*)cx.alloc((int64_t)meta.size() * 4);
+    NVL_HIP(hipMemcpyAsync(dmeta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, m.stream));
+    Meta md{};
+    md.seq_tok_start = dmeta; md.seq_len = dmeta + n_seqs; md.seq_pos = dmeta + 2 * n_seqs; md.seq_tbl = dmeta + 3 * n_seqs;
+    md.blk_table = dmeta + 4 * n_seqs;
+    m.ctx_hint = ctx;                                  // attn_cost: the longest context of the batch
+    auto release = [&]() {                             // everything is owned by cx.bufs
+        m.q = m.kcache = m.vcache = m.attn_out = nullptr; m.qkv = nullptr; m.rope_cos = m.rope_sin = nullptr;
+        m.attn_part = nullptr; m.attn_part_cnt = nullptr;
+    };
+    try {
+        if (kv8) attention_kv8(&m, md, n_seqs, max_len, k8, v8, k_scale, v_scale);
+        else attention(&m, 0, md, n_seqs, max_len, 0.0, fused, mq);
+    } catch (...) { release(); throw; }
+    for (int i = 0; i < 3; i++) ran[i] = m.attn_ran[i];
+    // out: token-major [tokens][nH][hd]
+    if (m.f32) {
+        cx.down(out, m.attn_out, tokens * W);
+    } else {
+        std::vector<uint16_t> ob((size_t)(round_up(tokens, 64) * W));
+        NVL_HIP(hipMemcpyAsync(ob.data(), m.attn_out, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
+        NVL_HIP(hipStreamSynchronize(m.stream));
+        for (int64_t r = 0; r < tokens; r++)        // the kernel wrote the next GEMM's fragment-major operand
+            for (int64_t c = 0; c < W; c++) {
+                const uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, W)]) << 16;
+                memcpy(&out[(size_t)(r * W + c)], &u, 4);
+            }
+    }
+    std::fill(part_cnt, part_cnt + ATTN_SPLIT_MAX_PAIRS, 0);
+    if (m.attn_part_cnt) {
+        NVL_HIP(hipMemcpyAsync(part_cnt, m.attn_part_cnt, ATTN_SPLIT_MAX_PAIRS * 4, hipMemcpyDeviceToHost, m.stream));
+        NVL_HIP(hipStreamSynchronize(m.stream));
+    }
+    if (fused) {       // the pools after the append
+        std::vector<uint16_t> pb((size_t)n_el);
+        for (int which = 0; which < 2; which++) {
+            NVL_HIP(hipMemcpyAsync(pb.data(), which ? m.vcache : m.kcache, (size_t)n_el * 2, hipMemcpyDeviceToHost, m.stream));
+            NVL_HIP(hipStreamSynchronize(m.stream));
+            float* dst = which ? v_pool : k_pool;
+            for (int64_t i = 0; i < n_el; i++) {
+                const uint32_t u = ((uint32_t)pb[(size_t)i]) << 16;
+                memcpy(&dst[i], &u, 4);
+            }
+        }
+    }
+    release();
+    return NVL_OK;
+    OP_CATCH
+}
+
 extern "C" int nvl_op_ffn(int device, int precision, const float* x, const float* w1, const float* b1, const float* w2,
                           const float* b2, int rows, int hidden, int ffn, int swiglu, float* y) {
     if (!x || !w1 || !w2 || !y || rows <= 0 || hidden % 64 || ffn % 64) return op_fail("nvl_op_ffn: bad arguments");

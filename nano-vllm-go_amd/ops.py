@@ -241,6 +241,40 @@ def moe_stages(x, router, w_in, w_out, top_k, precision="bf16", device=0):   # M
     return out
 
 
+ATTN_OP_FORMS = {"plain": 0, "fused": 1, "mq": 2, "kv8": 3}                                  # NVL_ATTN_OP_*
+ATTN_RAN = {1: "f32", 2: "prefill", 3: "prefill_kv8", 4: "decode", 5: "decode_fused", 6: "decode_kv8", 7: "decode_mq",
+            8: "decode_stamped"}                                                                 # NVL_ATTN_RAN_*
+
+
+def attention_batch(q, k_pool, v_pool, block_table, seq_len, seq_pos, nH, form="plain", scale=0.0, rope_base=0.0, max_seq=0,
+                    k_scale=1.0, v_scale=1.0, precision="bf16", device=0):   # generic_model.go:276 over block tables
+    """One layer's attention on a batch laid out as the paged front end lays it out, through the model's own dispatch
+    (nvl_op_attention_batch): k_pool / v_pool [n_blocks][nKV][block_size][hd], block_table [n_seqs][tbl_stride] (passed
+    verbatim), sequence i = seq_len[i] new rows behind seq_pos[i] cached keys.  q [tokens][nH][hd]; form "fused": the fp32
+    QKV rows [n_seqs][(nH + 2 nKV) hd] of a decode step (RoPE with rope_base, 0 = none; K / V appended by the kernel).
+    max_seq 0 = what the table covers.  -> dict(out [tokens][nH][hd], ran (an ATTN_RAN name), nw, nsplit, part_cnt [32],
+    and for "fused" k_pool / v_pool after the launch)."""
+    k_pool, v_pool = _f(k_pool).copy(), _f(v_pool).copy()
+    q = _f(q)
+    tbl = np.ascontiguousarray(block_table, dtype=np.int32)
+    sl, sp = np.ascontiguousarray(seq_len, dtype=np.int32), np.ascontiguousarray(seq_pos, dtype=np.int32)
+    n_blocks, nKV, bs, hd = k_pool.shape
+    n_seqs, stride = tbl.shape
+    tokens = int(sl.sum())
+    if v_pool.shape != k_pool.shape or sl.shape != (n_seqs,) or sp.shape != (n_seqs,) or \
+            q.shape != ((n_seqs, (nH + 2 * nKV) * hd) if form == "fused" else (tokens, nH, hd)):
+        raise ValueError("attention_batch: shapes do not match")
+    out = np.empty((tokens, nH, hd), np.float32)
+    ran, cnt = np.zeros(3, np.int32), np.zeros(32, np.int32)
+    L.check(L.lib().nvl_op_attention_batch(device, L.PRECISION[precision], ATTN_OP_FORMS[form], nH, nKV, hd, scale, n_seqs, _p(sl),
+                                           _p(sp), _p(k_pool), _p(v_pool), n_blocks, bs, _p(tbl), stride, _p(q), float(rope_base),
+                                           int(max_seq) if max_seq else stride * bs, k_scale, v_scale, _p(out), _p(ran), _p(cnt)))
+    res = dict(out=out, ran=ATTN_RAN[int(ran[0])], nw=int(ran[1]), nsplit=int(ran[2]), part_cnt=cnt)
+    if form == "fused":
+        res.update(k_pool=k_pool, v_pool=v_pool)
+    return res
+
+
 def argmax(x, device=0):                                       # argmax cmd/ask/main.go:389
     x = _f(x)
     if x.ndim == 1:

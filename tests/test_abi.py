@@ -10,9 +10,10 @@ def test_library_exports_every_declared_symbol(pkg):
     L = pkg.lib()
     names = pkg.declared_symbols()
     assert len(names) >= 30 and "nvl_forward" in names and "nvl_runner_run" in names and "nvl_op_moe_stages" in names
+    assert "nvl_op_attention_batch" in names
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing
-    assert L.nvl_abi_version() == 3                                 # (nvl_op_moe_stages is an addition: the version stays)
+    assert L.nvl_abi_version() == 3                                 # (nvl_op_moe_stages / nvl_op_attention_batch are additions: the version stays)
 
 
 def test_header_cites_the_reference_for_every_entry_point(pkg):
@@ -64,6 +65,29 @@ def test_moe_stages_refuses_bad_arguments_before_touching_a_device(pkg):
     text = pkg._lib.HEADER.read_text()
     for code, name in enumerate(("DENSE_FUSED", "DENSE", "PLAN", "GROUPED"), 1):
         assert re.search(rf"NVL_MOE_FORM_{name} = {code}\b", text), name
+
+
+def test_attention_batch_refuses_bad_arguments_before_touching_a_device(pkg):
+    """nvl_op_attention_batch checks what the paged front end checks, and every table entry, before the device probe
+    (NVL_ERR_INVALID / NVL_ERR_POSITION, not NVL_ERR_NO_DEVICE, on a machine without a GPU)."""
+    import numpy as np
+    nH, nKV, hd, bs = 8, 2, 64, 64
+    pool = np.zeros((3, nKV, bs, hd), np.float32)
+    ok = dict(q=np.zeros((2, nH, hd), np.float32), k_pool=pool, v_pool=pool, block_table=[[0, 1], [2, 2]], seq_len=[1, 1],
+              seq_pos=[70, 3], nH=nH)
+    for over, code in ((dict(block_table=[[0, 1], [2, 3]]), -1), (dict(block_table=[[0, 1], [-1, 2]]), -1), (dict(seq_pos=[70, -1]), -1),
+                       (dict(seq_pos=[128, 3], max_seq=256), -1), (dict(max_seq=70), -2), (dict(seq_len=[1, 0], q=np.zeros((1, nH, hd), np.float32)), -1),
+                       (dict(form="kv8", v_scale=float("inf")), -1), (dict(form="mq", precision="f32"), -1),
+                       (dict(form="fused", q=np.zeros((2, (nH + 2 * nKV) * hd), np.float32), seq_len=[1, 2], seq_pos=[70, 3]), -1)):
+        with pytest.raises(pkg.NvlError) as e:
+            pkg.ops.attention_batch(**{**ok, **over})
+        assert e.value.code == code, (over, e.value)
+    assert pkg.ops.ATTN_OP_FORMS == {"plain": 0, "fused": 1, "mq": 2, "kv8": 3}
+    text = pkg._lib.HEADER.read_text()
+    for code, name in pkg.ops.ATTN_RAN.items():
+        assert re.search(rf"NVL_ATTN_RAN_{name.upper()} = {code}\b", text), name
+    for name, code in pkg.ops.ATTN_OP_FORMS.items():
+        assert re.search(rf"NVL_ATTN_OP_{name.upper()} = {code}\b", text), name
 
 
 def test_product_package_never_imports_the_oracle(pkg):
