@@ -262,8 +262,9 @@ enum {
                             * q = clamp(rint(w / s) + z, 0, 15).  Every path computes with W~ = bf16_rne(fp32(s) * (q - z))
                             * (the product is exact in fp32: one rounding); nvl_get_weight returns W~.  nvl_stats.weight_bytes
                             * counts, per stored row (rows are padded to the weight row tile), in / 2 bytes of codes and
-                            * 4 bytes per group: one 32-bit word {fp16 s, z}.  The LM head, both embeddings, the router, the
-                            * MoE experts and the Mamba2 projections stay bf16, as AWQ / GPTQ checkpoints keep them fp16. */
+                            * 4 bytes per group: one 32-bit word {fp16 s, z}.  The LM head, both embeddings, the router and
+                            * the Mamba2 projections stay bf16, as AWQ / GPTQ checkpoints keep them fp16; the MoE experts too
+                            * unless nvl_set_gq_expert_dtype(m, NVL_GQE_UINT4). */
 };
 /* After nvl_create, before the first 2-D upload (else NVL_ERR_STATE).  NVL_ERR_INVALID for a NULL model, an unknown dtype, a
  * group_size outside {32, 64, 128}, and for NVL_GQ_UINT4 with f32 precision, tensor parallelism, NVL_W_FP8_E4M3 or
@@ -278,6 +279,27 @@ int nvl_set_gq_weight_dtype(nvl_model* m, int dtype, int group_size);
  * cols % group_size != 0, a zero above 15, or a scale that is NaN, infinite or <= 0. */
 int nvl_upload_tensor_int4(nvl_model* m, int kind, int layer, const uint8_t* codes, const uint16_t* scales, const uint8_t* zeros,
                            int64_t rows, int64_t cols, int layout);
+/* MoE expert weights (MOE_IN / MOE_OUT) of a model with INT4 projection weights.  No checkpoint
+ * reading comes with it: nvl_load_safetensors maps no AWQ / GPTQ MoE layout (the Granite mapping keeps its fused expert
+ * tensors, which such checkpoints do not carry); the experts arrive through nvl_upload_tensor / nvl_upload_tensor_int4. */
+enum {
+    NVL_GQE_NONE = 0,          /* the experts stay bf16 (also under NVL_GQ_UINT4): today's behaviour                          */
+    NVL_GQE_UINT4 = 1          /* MOE_IN / MOE_OUT under the contract of NVL_GQ_UINT4, byte for byte, with the model's own
+                                * group size g: one {fp16 s, 4-bit z} word per g consecutive input features of one (expert,
+                                * output row), the same quantizer (lo / hi include 0, r == 0 gives s = 1 and z = q = 0, the
+                                * 2^-24 floor, rint, the clamps); W~ = bf16_rne(fp32(s) * (q - z)) on every path;
+                                * nvl_get_weight returns W~; nvl_stats.weight_bytes counts codes + 4 bytes per group.  Decode
+                                * streams the codes; prefill dequantizes one layer's experts at a time into a scratch buffer.
+                                * nvl_upload_tensor quantizes the experts from F32 / BF16 / F16 and refuses a non-finite
+                                * expert weight and a group with r / 15 > 65504.  nvl_upload_tensor_int4 takes MOE_IN / MOE_OUT
+                                * too: rows = E * out, cols = in, codes [E * out][in / 2], scales and zeros [E * out][in / g]
+                                * (expert e's rows e*out .. e*out + out - 1), under its usual validation. */
+};
+/* After nvl_set_gq_weight_dtype(m, NVL_GQ_UINT4, g), before the first expert upload and nvl_finalize (else NVL_ERR_STATE).
+ * NVL_ERR_INVALID for a NULL model, an unknown value, a model without MoE, f32 precision, no INT4 projection weights, and
+ * hidden % g != 0 or expert width % g != 0 (a group must not straddle two experts of the concatenated down matrix).  While
+ * it holds NVL_GQE_UINT4, nvl_set_gq_weight_dtype refuses NVL_GQ_NONE and another group size (NVL_ERR_INVALID). */
+int nvl_set_gq_expert_dtype(nvl_model* m, int dtype);
 
 /* ---- lifecycle ---- */
 

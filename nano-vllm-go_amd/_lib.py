@@ -39,6 +39,7 @@ MX_EXPERT_DTYPE = {"none": 0, "fp4_e2m1": 1}             # NVL_MXE_* (nvl_set_mx
 MX_HEAD_DTYPE = {"none": 0, "fp4_e2m1": 1}               # NVL_MXH_* (nvl_set_mx_head_dtype)
 GQ_WEIGHT_DTYPE = {"none": 0, "uint4": 1}                # NVL_GQ_* (nvl_set_gq_weight_dtype)
 GQ_GROUP_SIZES = (32, 64, 128)
+GQ_EXPERT_DTYPE = {"none": 0, "uint4": 1}                # NVL_GQE_* (nvl_set_gq_expert_dtype)
 ACT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                   # NVL_ACT_AUTO / NVL_ACT_FP8_E4M3 (nvl_set_act_dtype)
 EXPERT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                # NVL_EXPERT_AUTO / NVL_EXPERT_FP8_E4M3 (nvl_set_expert_dtype)
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
@@ -191,6 +192,7 @@ def lib():
     L.nvl_upload_tensor_mxfp4.argtypes = [vp, C.c_int, C.c_int, vp, vp, i64, i64, C.c_int]
     L.nvl_op_matmul_mxfp4w.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp]
     L.nvl_set_gq_weight_dtype.argtypes = [vp, C.c_int, C.c_int]
+    L.nvl_set_gq_expert_dtype.argtypes = [vp, C.c_int]
     L.nvl_upload_tensor_int4.argtypes = [vp, C.c_int, C.c_int, vp, vp, vp, i64, i64, C.c_int]
     L.nvl_op_matmul_int4w.argtypes = [C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.nvl_set_expert_dtype.argtypes = [vp, C.c_int]

@@ -1198,6 +1198,15 @@ template <int MT, int NTW, int U, int EPI, typename OutT>
 __global__ __launch_bounds__(1024) void gemm_skinny_moe_mxfp4w_kernel(GemmArgs p, const uint8_t* __restrict__ w_scales) {
     gemm_skinny_body<MT, NTW, U, EPI, OutT, false, true, false, WF_MXFP4>(p, (const float*)w_scales);
 }
+// INT4 MoE experts (nvl_set_gq_expert_dtype): the MoE decode instantiation with the INT4 fragment.  The
+// group words lie beside the code tiles over the whole K of the launch ([tile][p.K / g][16], the body's index is
+// (ks0 + s) >> gshift over p.K), so the concatenated down projection (K = E*I, I % g == 0: no group straddles two experts)
+// addresses expert e's groups at e*I/g .. and needs no per-expert base: the body is used as it is.  K-split down form and
+// SwiGLU up form, as for fp8 and MXFP4.
+template <int MT, int NTW, int U, int EPI, typename OutT>
+__global__ __launch_bounds__(1024) void gemm_skinny_moe_int4w_kernel(GemmArgs p, const uint32_t* __restrict__ w_words, int gshift) {
+    gemm_skinny_body<MT, NTW, U, EPI, OutT, false, true, false, WF_INT4>(p, (const float*)w_words, gshift);
+}
 
 // ------------------------------------------------------------------------------------------
 // MoE decode routing in ONE launch (moe.go:57-103): router logits of a 16-row activation tile (E <= 64 experts, all of K),
@@ -1623,6 +1632,11 @@ template <int MT, int NTB, int U, int EPI, typename OutT>
 __global__ __launch_bounds__(512) void gemm_skinny_wide_moe_mxfp4w_kernel(GemmArgs p, const uint8_t* __restrict__ w_scales) {
     gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, false, true, WF_MXFP4>(p, (const float*)w_scales);
 }
+// INT4 MoE experts: the wide form of the expert up projection
+template <int MT, int NTB, int U, int EPI, typename OutT>
+__global__ __launch_bounds__(512) void gemm_skinny_wide_moe_int4w_kernel(GemmArgs p, const uint32_t* __restrict__ w_words, int gshift) {
+    gemm_skinny_wide_body<MT, NTB, U, EPI, OutT, false, true, WF_INT4>(p, (const float*)w_words, gshift);
+}
 
 static int g_chunk_max_m = 512;    // largest M that uses 64-row passes of the decode form at all (nvl_set_tuning key 11; 64 = off)
 static int g_chunk_all_m = 64;     // up to here every projection does; above, only those whose 128x128 tile grid would
@@ -1667,20 +1681,21 @@ static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a
 // The narrow / wide decode kernel of weight format WF with these template arguments: the one place that names the three
 // __global__ wrappers of a form (bf16: the kernel itself; quantized: the plain and the MoE wrapper of the shared body).
 // ws: the weight scales of a quantized format (fp32 per row, the e8m0 bytes of MXFP4, or the group words of INT4 with
-// gsh = log2(group size / 32)), unused for bf16.  INT4 covers no MoE experts: its MoE branches are never taken.
+// gsh = log2(group size / 32)), unused for bf16.
 template <int WF, int MT, int NTW, int U, int EPI, typename OutT, bool PASSES = false, bool MOE = false, bool HALF = false>
 static inline void launch_skinny_wf(dim3 grid, dim3 block, size_t lds, hipStream_t st, const GemmArgs& a, const float* ws, int gsh = 0) {
     static_assert(WF == WF_BF16 || !MOE || (!PASSES && !HALF), "the quantized MoE wrappers have no PASSES / HALF instance");
     if constexpr (WF == WF_BF16) hipLaunchKernelGGL((gemm_skinny_bf16_kernel<MT, NTW, U, EPI, OutT, PASSES, MOE, HALF>), grid, block, lds, st, a);
     else if constexpr (WF == WF_FP8 && MOE) hipLaunchKernelGGL((gemm_skinny_moe_fp8w_kernel<MT, NTW, U, EPI, OutT>), grid, block, lds, st, a, ws);
     else if constexpr (WF == WF_FP8) hipLaunchKernelGGL((gemm_skinny_fp8w_kernel<MT, NTW, U, EPI, OutT, PASSES, HALF>), grid, block, lds, st, a, ws);
-    else if constexpr (WF == WF_INT4 && MOE) throw std::runtime_error("gemm: INT4 weights have no MoE decode kernel");
     else if constexpr (WF == WF_INT4) {
         // MT = 4 (64-row groups): one k-step per register set, not two.  With U = 2 the fragment conversion's temporaries on top of
         // the 64 activation registers spilled 24-38 registers inside the k loop of the PASSES instantiations (the launcher's
-        // K split, sized for U = 2, leaves every wave at least two k-steps either way)
+        // K split, sized for U = 2, leaves every wave at least two k-steps either way).  The MoE instantiations take the same
+        // U: a down block of one k-step lies inside one expert whenever a block of two does.
         constexpr int UG = MT == 4 ? 1 : U;
-        hipLaunchKernelGGL((gemm_skinny_int4w_kernel<MT, NTW, UG, EPI, OutT, PASSES, HALF>), grid, block, lds, st, a, (const uint32_t*)ws, gsh);
+        if constexpr (MOE) hipLaunchKernelGGL((gemm_skinny_moe_int4w_kernel<MT, NTW, UG, EPI, OutT>), grid, block, lds, st, a, (const uint32_t*)ws, gsh);
+        else hipLaunchKernelGGL((gemm_skinny_int4w_kernel<MT, NTW, UG, EPI, OutT, PASSES, HALF>), grid, block, lds, st, a, (const uint32_t*)ws, gsh);
     }
     else if constexpr (MOE) hipLaunchKernelGGL((gemm_skinny_moe_mxfp4w_kernel<MT, NTW, U, EPI, OutT>), grid, block, lds, st, a, (const uint8_t*)ws);
     else hipLaunchKernelGGL((gemm_skinny_mxfp4w_kernel<MT, NTW, U, EPI, OutT, PASSES, HALF>), grid, block, lds, st, a, (const uint8_t*)ws);
@@ -1699,7 +1714,8 @@ static inline void launch_skinny_wide_wf(dim3 grid, dim3 block, size_t lds, hipS
         NVL_LDS_ATTR((gemm_skinny_wide_fp8w_kernel<MT, NTB, U, EPI, OutT, PASSES>), max_lds);
         hipLaunchKernelGGL((gemm_skinny_wide_fp8w_kernel<MT, NTB, U, EPI, OutT, PASSES>), grid, block, lds, st, a, ws);
     } else if constexpr (WF == WF_INT4 && MOE) {
-        throw std::runtime_error("gemm: INT4 weights have no MoE decode kernel");
+        NVL_LDS_ATTR((gemm_skinny_wide_moe_int4w_kernel<MT, NTB, U, EPI, OutT>), max_lds);
+        hipLaunchKernelGGL((gemm_skinny_wide_moe_int4w_kernel<MT, NTB, U, EPI, OutT>), grid, block, lds, st, a, (const uint32_t*)ws, gsh);
     } else if constexpr (WF == WF_INT4) {
         NVL_LDS_ATTR((gemm_skinny_wide_int4w_kernel<MT, NTB, U, EPI, OutT, PASSES>), max_lds);
         hipLaunchKernelGGL((gemm_skinny_wide_int4w_kernel<MT, NTB, U, EPI, OutT, PASSES>), grid, block, lds, st, a, (const uint32_t*)ws, gsh);
@@ -1769,6 +1785,7 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
     if (a.moe_gate && EPI == EPI_RESID) {      // MoE down: every wave's K range is exactly one expert (the skip test needs it)
         ksplit = a.moe_E / KS;
         if (ksplit < 1 || ksplit * KS != a.moe_E || ksplit > 16 || (a.moe_I >> 5) < 1) return false;
+        if (WF == WF_INT4 && MT == 4 && (a.moe_I >> 5) > 32) return false;     // (blocks of one k-step there, launch_skinny_wf: the live-block mask holds 32)
     }
     if (a.K % 32 != 0) return false;
     const size_t lds = (size_t)NTW * ksplit * MT * 64 * 16;

@@ -103,7 +103,7 @@ struct nvl_model {
     std::vector<float> k_scale, v_scale;   // [num_layers], default 1 (Mamba2 layers' entries unused)
     bool kv_written = false;               // a forward has been enqueued: the scales are fixed from then on
     // quantized weights (wq.h): the stored format of the projections (nvl_set_weight_dtype: WF_FP8, nvl_set_mx_weight_dtype:
-    // WF_MXFP4, nvl_set_gq_weight_dtype: wq.h wf_int4(g), WF_INT4 with its group size), of the MoE experts (nvl_set_expert_dtype / nvl_set_mx_expert_dtype; WF_BF16 or the projections' format) and
+    // WF_MXFP4, nvl_set_gq_weight_dtype: wq.h wf_int4(g), WF_INT4 with its group size), of the MoE experts (nvl_set_expert_dtype / nvl_set_mx_expert_dtype / nvl_set_gq_expert_dtype; WF_BF16 or the projections' format, INT4 with the same group size) and
     // of the MXFP4 LM head / tied embedding (nvl_set_mx_head_dtype; WF_BF16 or WF_MXFP4 — the fp8 head follows wf itself)
     int wf = nvl::WF_BF16, ef = nvl::WF_BF16, hf = nvl::WF_BF16;
     bool w2d_uploaded = false;             // a 2-D tensor has been uploaded: the weight dtype is fixed from then on

@@ -749,7 +749,8 @@ extern "C" int nvl_upload_tensor_mxfp4(nvl_model* m, int kind, int layer, const 
     return upload_prequant(m, WF_MXFP4, "nvl_upload_tensor_mxfp4", "nvl_set_mx_weight_dtype", kind, layer, codes, scales, rows, cols, layout);
 }
 
-// INT4 (w4g.h): codes [rows][cols/2] (even k in the low nibble), fp16 scales and zero points [rows][cols/g]; taken as they are
+// INT4 (w4g.h): codes [rows][cols/2] (even k in the low nibble), fp16 scales and zero points [rows][cols/g]; taken as they are.
+// With nvl_set_gq_expert_dtype also MOE_IN / MOE_OUT, as [E * out][in] (q_kind covers them only then)
 extern "C" int nvl_upload_tensor_int4(nvl_model* m, int kind, int layer, const uint8_t* codes, const uint16_t* scales, const uint8_t* zeros,
                                       int64_t rows, int64_t cols, int layout) {
     const char* fn = "nvl_upload_tensor_int4";
@@ -762,7 +763,12 @@ extern "C" int nvl_upload_tensor_int4(nvl_model* m, int kind, int layer, const u
     if (layout != NVL_LAYOUT_OUT_IN) return bad(NVL_ERR_INVALID, "%s: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
     DevTensor* t = tensor_slot(m, kind, layer);
     if (!t) return bad(NVL_ERR_INVALID, "%s: bad kind or layer");
-    const int64_t SN = full_out(m, kind), SK = full_in(m, kind), g = wf_group(wf);
+    int64_t SN = full_out(m, kind), SK = full_in(m, kind);
+    const int64_t g = wf_group(wf);
+    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {     // INT4 experts: [E * out][in], words per (expert, output row)
+        SN = (int64_t)m->cfg.num_experts * (kind == NVL_T_MOE_IN ? 2 * (int64_t)m->F : m->H);
+        SK = kind == NVL_T_MOE_IN ? m->H : m->F;
+    }
     if (rows != SN || cols != SK || SK % g != 0 || SK % 32 != 0)
         return bad(NVL_ERR_INVALID, "%s: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld], in %% group size == 0", kind,
                    (long long)rows, (long long)cols, (long long)SN, (long long)SK);
@@ -775,6 +781,7 @@ extern "C" int nvl_upload_tensor_int4(nvl_model* m, int kind, int layer, const u
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
     m->w2d_uploaded = true;
+    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) m->expert_uploaded = true;
     q_alloc(m, t, wf, rows, cols);
     uint8_t* raw = (uint8_t*)dmalloc_bytes(rows * cols / 2);
     uint16_t* raw_s = (uint16_t*)dmalloc_bytes(ng * 2);
@@ -1000,8 +1007,28 @@ extern "C" int nvl_set_gq_weight_dtype(nvl_model* m, int dtype, int group_size) 
         return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: the model stores 8-bit weights (nvl_set_weight_dtype)");
     if (dtype == NVL_GQ_UINT4 && m->wf == WF_MXFP4)
         return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: the model stores MXFP4 weights (nvl_set_mx_weight_dtype)");
+    if (wf_base(m->ef) == WF_INT4 && (dtype == NVL_GQ_NONE || wf_int4(group_size) != m->ef))
+        return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: the model stores INT4 experts (nvl_set_gq_expert_dtype), which need INT4 weights of their group size");
     if (dtype == NVL_GQ_UINT4) m->wf = wf_int4(group_size);
     else if (wf_base(m->wf) == WF_INT4) m->wf = WF_BF16;
+    return NVL_OK;
+}
+
+extern "C" int nvl_set_gq_expert_dtype(nvl_model* m, int dtype) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: no model");
+    if (m->finalized || m->expert_uploaded)
+        return fail(m, NVL_ERR_STATE, "nvl_set_gq_expert_dtype: call it after nvl_set_gq_weight_dtype and before the first expert upload");
+    if (dtype != NVL_GQE_NONE && dtype != NVL_GQE_UINT4) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: unknown group-quantized expert dtype");
+    if (dtype == NVL_GQE_UINT4) {
+        if (!m->cfg.use_moe || m->cfg.num_experts <= 0) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: the model has no MoE layers");
+        if (m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: INT4 experts need bf16 precision");
+        if (wf_base(m->wf) != WF_INT4) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: INT4 experts need INT4 projection weights (nvl_set_gq_weight_dtype first)");
+        // (a group of the concatenated down matrix, K = E*I, must lie inside one expert)
+        if (m->H % wf_group(m->wf) != 0 || m->F % wf_group(m->wf) != 0)
+            return fail(m, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: the hidden width and the expert width must be multiples of the group size");
+    }
+    if (dtype == NVL_GQE_UINT4) m->ef = m->wf;
+    else if (wf_base(m->ef) == WF_INT4) m->ef = WF_BF16;
     return NVL_OK;
 }
 
@@ -1149,7 +1176,11 @@ extern "C" int nvl_finalize(nvl_model* m) {
                         l.qs_moe_out = q_alloc_scales(m, wf, hp, E * I);
                         hipLaunchKernelGGL(moe_cat_down_w4_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream, (const uint8_t*)d.p,
                                            (const uint8_t*)d.qs, (uint8_t*)l.moe_out_q, (uint8_t*)l.qs_moe_out, (int)H, (int)I, (int)E);
-                    } else {                  // row scales [E][H_pad]: one row per expert, through the host
+                    } else if (wf_base(wf) == WF_INT4) {     // group words over the same K (pad rows: {s = 1, z = 0}), moved with the code tiles
+                        l.qs_moe_out = q_alloc_scales(m, wf, hp, E * I);
+                        hipLaunchKernelGGL(moe_cat_down_w4g_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream, (const uint8_t*)d.p,
+                                           (const uint32_t*)d.qs, (uint8_t*)l.moe_out_q, (uint32_t*)l.qs_moe_out, (int)H, (int)I, (int)E, wf_gshift(wf));
+                    } else {                // row scales [E][H_pad]: one row per expert, through the host
                         l.qs_moe_out = q_alloc_scales(m, wf, E * hp, I);
                         hipLaunchKernelGGL(moe_cat_down_w8_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream,
                                            (const uint8_t*)d.p, (uint8_t*)l.moe_out_q, (int)H, (int)I, (int)E);
@@ -1959,8 +1990,11 @@ void ffn_up(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false) {
 // (the down form's per-wave live-block mask is 32 bits wide: an expert of more than 32 blocks of U k-steps — U = 4 up to 32
 // rows, 2 above — would lose the blocks past 32, so such widths take the grouped form: I > 4096, or I > 2048 above 32 rows)
 bool moe_dense_ok(const nvl_model* m, const LayerW& l, int M) {
+    // (the last condition: an expert's k-steps in blocks of U fit the down form's 32-bit live-block mask; U = 4 up to 32 rows,
+    //  then 2, and 1 for INT4 experts, whose 64-row kernels run one k-step per register set: gemm.h launch_skinny_wf)
+    const int u_down = M <= 32 ? 4 : (wf_base(m->ef) == WF_INT4 ? 1 : 2);
     return !m->f32 && M <= 64 && g_moe_dense && l.moe_out_cat && m->moe_part && !m->keep_hidden && m->H % 4 == 0 &&
-           m->H <= 1024 * NORM_ROW_MAXCH && g_force_tile == 0 && (m->F >> 5) / (M <= 32 ? 4 : 2) <= 32;
+           m->H <= 1024 * NORM_ROW_MAXCH && g_force_tile == 0 && (m->F >> 5) / u_down <= 32;
 }
 // deferred_norm: m->xn holds xn_raw = bf16(x * w_norm) and m->rs_part the x^2 partials (the O projection carried the FFN
 // norm): the router and the expert-up projection scale their accumulators by rstd[m] instead of reading a normed operand
@@ -1973,7 +2007,9 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
     const int pairs = M * k;
     // algorithmic weight bytes of the expert GEMMs: the experts a batch of `pairs` (token, rank) pairs can touch, once
     const double e_touch = (double)std::min(E, pairs);
-    const double eb = m->ef != WF_BF16 ? wf_code_bytes(m->ef, 2) / 2.0 : (double)m->wsize;     // bytes per expert weight (quantized experts: codes; scales not counted)
+    // bytes per expert weight (quantized experts: codes; the row and block scales are not counted, INT4's group words — 4 / g
+    // bytes per weight, a quarter of the codes at g = 32 — are)
+    const double eb = m->ef != WF_BF16 ? wf_code_bytes(m->ef, 2) / 2.0 + (wf_base(m->ef) == WF_INT4 ? 4.0 / wf_group(m->ef) : 0.0) : (double)m->wsize;
     m->site = KS_MOE_ROUTER;
     const bool dense = moe_dense_ok(m, l, M) && m->pending_slices == 0;
     // decode: router logits, softmax, top-k and the dense gate matrix in one launch (gemm.h moe_router_gate_kernel)
@@ -2008,7 +2044,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
         gemm(m, EPI_SWIGLU, false, a, 2.0 * pairs * 2 * I * H);
         const int nks = (E * I) >> 5, spe = I >> 5;
         // (8-bit experts: no producer form — a wave's live blocks cross experts, the scale would change with the block;
-        //  MXFP4 experts: no instance of it either — key 33 is off by default and was measured slower)
+        //  MXFP4 and INT4 experts: no instance of it either — key 33 is off by default and was measured slower)
         if (next_norm_w && g_moe_defer_down && m->ef == WF_BF16 && nks % 64 == 0 && spe % 4 == 0 && nks / 16 <= 4 * spe && nks / 64 <= 32) {
             // (the launcher's conditions: 16 waves, whole blocks of 4 k-steps inside one expert, <= 4 experts per wave)
             GemmArgs d = mk(m->moe_hall, E * I, l.moe_out_cat, m->x, H, nullptr, m->resid_alpha, M, H, E * I);
@@ -2093,9 +2129,10 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
         a.w_expert_stride = (int64_t)2 * I * H; a.grp_bm = pp ? 512 : BM; a.grp_deep = small && g_moe_deep;
         // quantized experts: the grouped GEMMs run on this layer's W~, dequantized into one scratch buffer — up first, then down
         // over it, in stream order (the down dequantize starts after the up GEMM has read the scratch).  Algorithmic bytes
-        // of a dequantize, per element: the code + its share of the scales in, 2 bytes out (3.0 for fp8, 2.53 for MXFP4)
+        // of a dequantize, per element: the code + its share of the scales in, 2 bytes out (3.0 for fp8, 2.53 for MXFP4,
+        // 2.5 + 4 / g for INT4)
         const void* w_down = l.t[NVL_T_MOE_OUT].p;
-        const double dq_bytes = m->ef == WF_MXFP4 ? 2.53 : 3.0;
+        const double dq_bytes = m->ef == WF_MXFP4 ? 2.53 : (wf_base(m->ef) == WF_INT4 ? 2.5 + 4.0 / wf_group(m->ef) : 3.0);
         if (m->ef != WF_BF16) {
             KScope ks(m, KC_OTHER, 0, KS_MOE_UP, (double)round_up(E * 2 * I, W_ROW_PAD) * H * dq_bytes);
             wf_dequant_rows(m->stream, m->ef, l.moe_in, l.qs_moe_in, H, 0, round_up(E * 2 * I, W_ROW_PAD), m->eq_scratch);
@@ -2110,6 +2147,9 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
             if (m->ef == WF_MXFP4)
                 hipLaunchKernelGGL(e4_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
                                    (const uint8_t*)l.qs_moe_out, H, I, E, n8, m->eq_scratch);
+            else if (wf_base(m->ef) == WF_INT4)
+                hipLaunchKernelGGL(e4g_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
+                                   (const uint32_t*)l.qs_moe_out, H, I, E, wf_gshift(m->ef), n8, m->eq_scratch);
             else
                 hipLaunchKernelGGL(e8_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
                                    (const float*)l.qs_moe_out, H, I, E, round_up(H, W_ROW_PAD), n8, m->eq_scratch);

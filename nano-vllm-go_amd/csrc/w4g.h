@@ -13,6 +13,10 @@
 // Storage: codes exactly as MXFP4's (w4.h: nibble-packed fragment-major, 256 bytes per 16-row x 32-k block, even k in the low
 // nibble); one 32-bit word per (row, group), {fp16 s in bits 0-15, z in bits 16-19}, [rows_pad/16][K/g][16]: the 16 rows of
 // a tile side by side, one 4-byte load beside the codes (pad rows: codes 0, s = 1, z = 0).
+// MoE experts (nvl_set_gq_expert_dtype, §9 f-19): the same contract with one word per g input features of one (expert, output
+// row).  Decode streams the codes through gemm_skinny_moe_int4w_kernel / gemm_skinny_wide_moe_int4w_kernel; every other MoE
+// launch runs the unchanged grouped GEMMs on one layer's W~, dequantized (up, then down) into a scratch buffer.  No checkpoint
+// reading: no AWQ / GPTQ MoE layout is mapped by the loader, the experts arrive through the upload calls.
 #pragma once
 #include "gemm.h"
 
@@ -85,6 +89,37 @@ __global__ __launch_bounds__(256) void w4g_dequant_kernel(const uint8_t* __restr
     if (i >= n8) return;
     const int64_t blk = i >> 6, tile = blk / nks, ks = blk - tile * nks;
     *(bf16x8*)(out + i * 8) = w4g_frag(*(const uint32_t*)(codes + i * 4), words[(tile * (nks >> gshift) + (ks >> gshift)) * 16 + (i & 15)]);
+}
+
+// INT4 MoE experts (nvl_set_gq_expert_dtype).  As for MXFP4 experts (w4.h) the down codes are stored once, in
+// the decode form's layout: [H_pad][E*I/2] bytes, fragment-major with K = E*I (expert e's k-steps e*I/32 .. (e+1)*I/32 - 1 of
+// every 16-row tile), the group words [H_pad/16][E*I/g][16] over the same K (expert e's groups e*I/g .. (e+1)*I/g - 1: I % g
+// == 0, no group straddles two experts).  moe_cat_down_w4g_kernel builds both from the uploaded [E*H][I] codes and words
+// (moe_cat_down_w4_kernel with words for scale bytes; H % 16 == 0: an expert starts on a tile boundary).
+__global__ __launch_bounds__(256) void moe_cat_down_w4g_kernel(const uint8_t* __restrict__ src, const uint32_t* __restrict__ src_words,
+                                                               uint8_t* __restrict__ dst, uint32_t* __restrict__ dst_words, int H, int I, int E,
+                                                               int gshift) {
+    const int nt = blockIdx.x, e = blockIdx.y, kbs = I >> 5, ngs = kbs >> gshift;     // k-steps and groups per expert row
+    const int64_t stile = (int64_t)e * (H >> 4) + nt, dtile = nt;
+    const uint32_t* s4 = (const uint32_t*)(src + stile * kbs * 256);
+    uint32_t* d4 = (uint32_t*)(dst + (dtile * E + e) * kbs * 256);
+    for (int i = threadIdx.x; i < kbs * 64; i += 256) d4[i] = s4[i];
+    const uint32_t* sw = src_words + stile * ngs * 16;
+    uint32_t* dw = dst_words + (dtile * E + e) * ngs * 16;
+    for (int i = threadIdx.x; i < ngs * 16; i += 256) dw[i] = sw[i];
+}
+
+// the tile path's per-expert W~ of the down projection from the stored concatenated codes: out [E][H][I] bf16, fragment-major
+// per expert (expert e at e*H*I: the grouped GEMMs' w_expert_stride), n8 = E*H*I/8 fragments, H % 16 == 0
+__global__ __launch_bounds__(256) void e4g_dequant_down_kernel(const uint8_t* __restrict__ codes, const uint32_t* __restrict__ words,
+                                                               int H, int I, int E, int gshift, int64_t n8, bf16_t* __restrict__ out) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n8) return;
+    const int64_t per_e = (int64_t)H * I / 8, kbs = I >> 5;
+    const int64_t e = i / per_e, j = i - e * per_e;            // j = (tile * kbs + ks) * 64 + lane
+    const int64_t lane = j & 63, blk = j >> 6, tile = blk / kbs, ks = blk - tile * kbs;
+    const int64_t sblk = (tile * E + e) * kbs + ks;            // the (tile, k-step) block over K = E*I; its group: sblk >> gshift
+    *(bf16x8*)(out + i * 8) = w4g_frag(*(const uint32_t*)(codes + (sblk * 64 + lane) * 4), words[(sblk >> gshift) * 16 + (lane & 15)]);
 }
 
 // ---- host ----

@@ -29,7 +29,8 @@ inline const char* wf_name(int wf) { return wf == WF_MXFP4 ? "MXFP4" : (wf_base(
 // does the format cover this 2-D tensor kind (experts: when the expert format `ef` is set too; LM head: the head format
 // `hf`)?  Attention and FFN projections in both; the LM head, and the token embedding when it is the (tied) LM head, in
 // fp8 always and in MXFP4 when nvl_set_mx_head_dtype asked for it.  Position embedding, router and Mamba2 projections stay bf16.
-// INT4 (ef = hf = WF_BF16 always) covers the attention and FFN projections only, as AWQ / GPTQ checkpoints do.
+// INT4 (hf = WF_BF16 always) covers the attention and FFN projections, as AWQ / GPTQ checkpoints do, and the MoE experts when
+// nvl_set_gq_expert_dtype asked for them (ef = wf then, the group size included).
 inline bool wf_covers(int wf, int ef, int hf, int kind, bool tied_embedding) {
     switch (kind) {
         case NVL_T_WQ: case NVL_T_WK: case NVL_T_WV: case NVL_T_WKV: case NVL_T_WO: case NVL_T_W1: case NVL_T_W2: return wf != WF_BF16;

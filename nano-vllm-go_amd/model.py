@@ -49,7 +49,7 @@ class HipTransformerModel:
                  kv_cache_dtype: str = "auto", kv_scales=None, weight_dtype: str = "auto",
                  act_dtype: str = "auto", expert_dtype: str = "auto", mx_weight_dtype: str = "none",
                  mx_expert_dtype: str = "none", mx_head_dtype: str = "none", gq_weight_dtype: str = "none",
-                 gq_group_size: int = 128):
+                 gq_group_size: int = 128, gq_expert_dtype: str = "none"):
         """tensors=None defers finalize(): upload() each tensor, then call finalize().
         tp_size > 1 makes this the tp_rank-th tensor-parallel shard: pass the FULL tensors, the library keeps
         its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests).
@@ -71,7 +71,10 @@ class HipTransformerModel:
         gq_weight_dtype="uint4": INT4 group-quantized projection weights, the W4A16 format of AWQ / GPTQ checkpoints — unsigned
         4-bit codes with one fp16 scale and one zero point per gq_group_size (32 / 64 / 128) input features
         (nvl_set_gq_weight_dtype; bf16 precision, no TP, not with weight_dtype / mx_weight_dtype); the LM head, the embeddings
-        and the MoE experts stay bf16.  The model computes with W~ = bf16(s * (q - z)), which get_weight returns."""
+        and the MoE experts stay bf16.  The model computes with W~ = bf16(s * (q - z)), which get_weight returns.
+        gq_expert_dtype="uint4" (needs gq_weight_dtype="uint4", a MoE model whose hidden and expert widths are multiples of
+        gq_group_size): the experts' weights are INT4 too, one scale and zero point per gq_group_size input features of an
+        (expert, output row) (nvl_set_gq_expert_dtype)."""
         self.cfg = dict(cfg)
         self.lib = L.lib()
         self.h = C.c_void_p()
@@ -115,6 +118,10 @@ class HipTransformerModel:
             raise ValueError(f"gq_group_size must be one of {L.GQ_GROUP_SIZES}")
         if gq_weight_dtype != "none" and (weight_dtype != "auto" or mx_weight_dtype != "none"):
             raise ValueError('gq_weight_dtype="uint4" cannot be combined with weight_dtype="fp8_e4m3" or mx_weight_dtype="fp4_e2m1"')
+        if gq_expert_dtype not in L.GQ_EXPERT_DTYPE:
+            raise ValueError(f"gq_expert_dtype must be one of {sorted(L.GQ_EXPERT_DTYPE)}")
+        if gq_expert_dtype != "none" and gq_weight_dtype != "uint4":
+            raise ValueError('gq_expert_dtype="uint4" needs gq_weight_dtype="uint4"')
         L.check(self.lib.nvl_create(C.byref(self._c), C.byref(opts), C.byref(self.h)))
         self.weight_dtype = weight_dtype
         self.gq_weight_dtype = gq_weight_dtype
@@ -127,10 +134,12 @@ class HipTransformerModel:
                 raise L.NvlError(rc, msg.decode() if msg else "")
         self.mx_weight_dtype = mx_weight_dtype
         self.mx_expert_dtype = mx_expert_dtype
+        self.gq_expert_dtype = gq_expert_dtype
         self.mx_head_dtype = mx_head_dtype
         self.act_dtype = act_dtype
         self.expert_dtype = expert_dtype
-        for setter, table, value in ((self.lib.nvl_set_mx_weight_dtype, L.MX_WEIGHT_DTYPE, mx_weight_dtype),
+        for setter, table, value in ((self.lib.nvl_set_gq_expert_dtype, L.GQ_EXPERT_DTYPE, gq_expert_dtype),
+                                     (self.lib.nvl_set_mx_weight_dtype, L.MX_WEIGHT_DTYPE, mx_weight_dtype),
                                      (self.lib.nvl_set_mx_expert_dtype, L.MX_EXPERT_DTYPE, mx_expert_dtype),
                                      (self.lib.nvl_set_mx_head_dtype, L.MX_HEAD_DTYPE, mx_head_dtype),
                                      (self.lib.nvl_set_weight_dtype, L.WEIGHT_DTYPE, weight_dtype),
@@ -247,7 +256,8 @@ class HipTransformerModel:
 
     def upload_int4(self, slot: str, layer: int, codes, scales, zeros):
         """nvl_upload_tensor_int4: pre-quantized codes [out][in/2] (even k in the low nibble), fp16 scales [out][in/g] (float16
-        values or their uint16 bit patterns) and zero points [out][in/g] (0..15)"""
+        values or their uint16 bit patterns) and zero points [out][in/g] (0..15); with gq_expert_dtype="uint4" also moe_in /
+        moe_out, as [E * out][in/2] codes and [E * out][in/g] scales and zero points"""
         codes = np.ascontiguousarray(codes, np.uint8)
         scales = np.ascontiguousarray(scales)
         scales = scales.view(np.uint16) if scales.dtype == np.float16 else np.ascontiguousarray(scales, np.uint16)

@@ -64,6 +64,9 @@ check(r"gemm_skinny_wide_moe_mxfp4w_kernelILi[124]E", "wide MoE projection, MXFP
 # the INT4 group-quantized forms (w4g.h): the MXFP4 forms' budget
 check(r"gemm_skinny_int4w_kernelILi[124]E", "narrow projection, INT4 weights", lambda r: r["spill"] <= 12 and r["vgpr"] <= 512)
 check(r"gemm_skinny_wide_int4w_kernelILi[124]E", "wide projection, INT4 weights", lambda r: r["spill"] <= 12 and r["vgpr"] <= 512)
+# ... and their MoE instantiations (nvl_set_gq_expert_dtype)
+check(r"gemm_skinny_moe_int4w_kernelILi[124]E", "narrow MoE projection, INT4 experts", lambda r: r["spill"] <= 12 and r["vgpr"] <= 512)
+check(r"gemm_skinny_wide_moe_int4w_kernelILi[124]E", "wide MoE projection, INT4 experts", lambda r: r["spill"] <= 12 and r["vgpr"] <= 512)
 sys.exit(1 if bad else 0)
 PY
 exit $rc
