@@ -844,6 +844,67 @@ enum {
 int nvl_op_moe_stages(int device, int precision, const float* x, const float* router, const float* w_in,
                       const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter,
                       float* y, float* router_logits, float* gate, int32_t* form);
+/* The dense layer tail of generic_model.go:320-326,383-418 as a layer of the model runs it, stage by stage, bf16 mode only:
+ * O projection, FFN norm, FFN-up, FFN-down, the norm after the layer and the projection that reads it.  The op executes the
+ * model's own decisions (which projection carries the next norm — the deferred RMSNorm —, which is split over K and left
+ * pending for the next norm, the parallel block's order) through the code the forward pass runs, on workspaces sized as
+ * nvl_create sizes them for max_batch_tokens = rows, every scratch buffer and output 0xFF bytes (NaN) beforehand.
+ * In: x [rows][hidden] the residual stream before the O projection; attn_out [rows][q_width]; wo [hidden][q_width], bo;
+ * norm_w / norm_b [hidden], the FFN norm (parallel block: the block's one norm, run first); w1 [2 ffn][hidden] (SwiGLU: gate
+ * rows, then up rows) or [ffn][hidden] (GELU), b1 [ffn]; w2 [hidden][ffn], b2; next_norm_w / next_norm_b, the norm after the
+ * layer; wn [n_next][hidden], the projection behind it (n_next need not be a multiple of anything).  Biases may be NULL
+ * (LayerNorm needs its two).  residual_multiplier 0 = 1 (as in a model config); a parallel block applies its two multipliers
+ * only when both are non-zero.  max_len = 1: a decode pass.  has_next = 1: a layer follows (its attention norm, wn its
+ * QKV); 0: the last layer — the final norm on last_rows [n_last_rows] (a decode pass lists every row) and wn as the LM head.
+ * Out: x1 / x2 [rows][hidden], x after the O projection / after FFN-down (a pending add completed as the debug tap
+ * completes it); op1 / op2, the bf16 operand rows of FFN-up / of wn as fp32 ([rows][hidden]; op2 of a last layer that did
+ * not defer: [n_last_rows][hidden]); rs1 / rs2 [rows][hidden / 8], the x^2 partials beside a deferred operand, the first
+ * ran[NVL_DENSE_RAN_RS1_TILES] / [..RS2_TILES] of a row valid (0 tiles: the operand is already normalised); h [rows][ffn];
+ * yn [rows or n_last_rows][n_next]; x_end [rows][hidden], x after the last launch; ran [NVL_DENSE_RAN_INTS], what ran.
+ * Refuses what nvl_create refuses (hidden, ffn, q_width % 64; a negative attention_multiplier) with NVL_ERR_INVALID. */
+enum {      /* ran[]: per residual projection p (0 = O projection, 1 = FFN-down) four ints at 4p */
+    NVL_DENSE_RAN_PRODUCER = 0,     /* 1: the launch carried the next norm (xn_raw + x^2 partials) */
+    NVL_DENSE_RAN_HALF = 1,         /* 1: on 8-row half tiles (partials per 8 columns) */
+    NVL_DENSE_RAN_FORM = 2,         /* NVL_RESID_FORM_* */
+    NVL_DENSE_RAN_SLICES = 3,       /* K slices left pending for the next norm (0: the add happened in the launch) */
+    NVL_DENSE_RAN_NORMS = 8,        /* norm launches */
+    NVL_DENSE_RAN_CONSUMER = 9,     /* [9 + p]: the norm kernel that completed projection p's pending add (NVL_NORM_RAN_*, 0 = none) */
+    NVL_DENSE_RAN_RS1_TILES = 12, NVL_DENSE_RAN_RS2_TILES = 13,
+    NVL_DENSE_RAN_INTS = 14
+};
+enum {
+    NVL_RESID_FORM_TILE = 0,        /* the prefill tile kernels */
+    NVL_RESID_FORM_MSPLIT = 1,      /* decode kernel, one workgroup per (weight tile, 16-row activation tile), all of K */
+    NVL_RESID_FORM_GROUPS = 2,      /* decode kernel over 64-row groups, one launch */
+    NVL_RESID_FORM_GROUPS_SERIAL = 3,   /* ... one launch per group */
+    NVL_RESID_FORM_DECODE = 4       /* decode kernel, one workgroup per weight tile (and K slice) */
+};
+enum { NVL_NORM_RAN_ROW = 1, NVL_NORM_RAN_ROW_IDX = 2, NVL_NORM_RAN_TILE16 = 3 };
+typedef struct nvl_dense_stages {
+    int32_t struct_bytes;           /* sizeof(nvl_dense_stages) */
+    int32_t rows, hidden, q_width, ffn, n_next;
+    int32_t norm_type, activation_type, block_style;       /* NVL_NORM_*, NVL_ACT_*, NVL_BLOCK_* */
+    int32_t max_len, has_next, n_last_rows;
+    float residual_multiplier, attention_multiplier, norm_eps;
+    int32_t reserved;
+    const float *x, *attn_out, *wo, *bo, *norm_w, *norm_b, *w1, *b1, *w2, *b2, *next_norm_w, *next_norm_b, *wn;
+    const int32_t* last_rows;
+    float *x1, *op1, *rs1, *h, *x2, *op2, *rs2, *yn, *x_end;
+    int32_t* ran;
+} nvl_dense_stages;
+int nvl_op_dense_stages(int device, int precision, const nvl_dense_stages* io);
+/* The same tail with the MoE block of moe.go:43-128 between the projections, decode only (rows <= 64; RMSNorm, sequential
+ * block): the O projection carries the FFN norm, the router and the expert up projection read the deferred operand
+ * (moe() with deferred_norm), the expert down projection leaves its K slices pending.  router [hidden][n_experts], w_in
+ * [n_experts][2 inter][hidden], w_out [n_experts][hidden][inter] as nvl_op_moe_stages takes them.  Out: x1, op1, rs1 and
+ * ran as nvl_op_dense_stages gives them (ran's FFN-down record holds only the slices moe() left pending); router_logits
+ * and gate [rows][n_experts]; y [rows][hidden], x after the block (the pending slices added as the debug tap adds them);
+ * *form, NVL_MOE_FORM_*. */
+int nvl_op_dense_moe_stages(int device, int precision, const float* x, const float* attn_out, const float* wo, const float* bo,
+                            const float* norm_w, const float* router, const float* w_in, const float* w_out,
+                            const float* next_norm_w, int rows, int hidden, int q_width, int n_experts, int top_k, int inter,
+                            float residual_multiplier, float norm_eps, float* x1, float* op1, float* rs1,
+                            float* router_logits, float* gate, float* y, int32_t* form, int32_t* ran);
 /* argmax cmd/ask/main.go:389-402 (first strict maximum) */
 int nvl_op_argmax(int device, const float* x, int rows, int cols, int32_t* out);
 

@@ -105,6 +105,15 @@ def sampling_params(temperature=1.0, top_p=1.0, top_k=0, repetition_penalty=1.2)
     return SamplingParamsC(float(temperature), float(top_p), int(top_k), float(repetition_penalty))
 
 
+class DenseStagesC(C.Structure):      # nvl_dense_stages
+    _fields_ = ([(n, C.c_int32) for n in ("struct_bytes", "rows", "hidden", "q_width", "ffn", "n_next", "norm_type", "activation_type",
+                                          "block_style", "max_len", "has_next", "n_last_rows")] +
+                [(n, C.c_float) for n in ("residual_multiplier", "attention_multiplier", "norm_eps")] + [("reserved", C.c_int32)] +
+                [(n, C.c_void_p) for n in ("x", "attn_out", "wo", "bo", "norm_w", "norm_b", "w1", "b1", "w2", "b2", "next_norm_w",
+                                           "next_norm_b", "wn", "last_rows", "x1", "op1", "rs1", "h", "x2", "op2", "rs2", "yn", "x_end",
+                                           "ran")])
+
+
 def declared_symbols() -> list[str]:
     """Every function include/nvllm.h declares (the drop-in surface)."""
     text = HEADER.read_text()
@@ -218,6 +227,8 @@ def lib():
     L.nvl_lookup_draft.argtypes = [vp, C.c_int, C.c_int, C.c_int, vp]
     L.nvl_decode_greedy_lookup.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.nvl_op_attention_mq.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]
+    L.nvl_op_dense_stages.argtypes = [C.c_int, C.c_int, C.POINTER(DenseStagesC)]
+    L.nvl_op_dense_moe_stages.argtypes = [C.c_int, C.c_int] + [vp] * 9 + [C.c_int] * 6 + [f32, f32] + [vp] * 8
     L.nvl_op_moe_stages.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp] + [C.c_int] * 5 + [vp] * 4
     L.nvl_op_attention_batch.argtypes = ([C.c_int] * 6 + [f32, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_double,
                                           C.c_int, f32, f32, vp, vp, vp])

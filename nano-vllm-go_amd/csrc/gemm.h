@@ -1655,6 +1655,9 @@ static int g_force_tile = 0;                      // 0 automatic, 1: 128x128x2st
 
 template <int EPI, typename OutT, int WF = 0>
 static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a, const float* ws = nullptr, int gsh = 0);
+// how the last decode-form projection was launched (host side, for the record resid_gemm keeps: nvl_model::dense_ran):
+// NVL_RESID_FORM_* of nvllm.h (0, NVL_RESID_FORM_TILE: none of the decode launchers ran)
+static thread_local int t_skinny_form = 0, t_skinny_half = 0;
 constexpr int DEFER_MAX_M = 128;    // deferred RMSNorm (decode): rows of the x^2 partial buffer.  Above 64 rows the producer
                                     // runs as 64-row groups like every narrow projection (one workgroup per 16-row tile
                                     // was measured at M = 128: -13 %); above 128 rows FFN-up belongs on the tile kernels
@@ -1675,6 +1678,7 @@ static inline bool launch_skinny_passes_serial(hipStream_t st, const GemmArgs& a
         }
         if (!launch_gemm_skinny_bf16<EPI, OutT, WF>(st, c, ws, gsh)) return false;
     }
+    t_skinny_form = NVL_RESID_FORM_GROUPS_SERIAL;
     return true;
 }
 
@@ -1764,10 +1768,12 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
             }
             if (a.rs_half) {      // <= 16 rows: 8 weight rows per workgroup, twice the workgroups (HALF above)
                 if (a.M > 16) return false;
+                t_skinny_form = NVL_RESID_FORM_MSPLIT; t_skinny_half = 1;
                 launch_skinny_wf<WF, 1, NTW, 4, EPI, OutT, false, false, true>(dim3(2 * nblocks, 1), dim3(NTW * ks * 64), (size_t)NTW * ks * 64 * 16, st, a, ws, gsh);
                 return true;
             }
         }
+        t_skinny_form = NVL_RESID_FORM_MSPLIT; t_skinny_half = 0;
         launch_skinny_wf<WF, 1, NTW, 4, EPI, OutT>(dim3(nblocks, cdiv(a.M, 16)), dim3(NTW * ks * 64), (size_t)NTW * ks * 64 * 16, st, a, ws, gsh);
         return true;
     }
@@ -1802,6 +1808,7 @@ static inline bool launch_gemm_skinny_ntw(hipStream_t st, const GemmArgs& a, con
             return false;     // (quantized experts: no other epilogue; bf16 falls through to the plain kernel, as it always has)
         }
     }
+    t_skinny_form = a.m_passes > 1 ? NVL_RESID_FORM_GROUPS : NVL_RESID_FORM_DECODE; t_skinny_half = 0;
     if (a.m_passes > 1) NVL_SK(4, 2, true); else if (MT == 1) NVL_SK(1, 4, false); else if (MT == 2) NVL_SK(2, 4, false); else NVL_SK(4, 2, false);
 #undef NVL_SK
     return true;

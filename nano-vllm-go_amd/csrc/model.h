@@ -180,6 +180,8 @@ struct nvl_model {
     int ctx_hint = 0;    // longest context (keys) of the batch being enqueued; 0 = unknown (decode attention sizing)
     float* sk_part = nullptr; int sk_max_slices = 4; int pending_slices = 0, pending_rows = 0; float pending_alpha = 1.f; const float* pending_part = nullptr;
     int sk_rows = 64;             // rows the sk_part slices are allocated for
+    int pending_from = 0;         // which residual projection left the pending slices (0 = O projection, 1 = FFN-down)
+    int dense_ran[NVL_DENSE_RAN_INTS] = {0};   // what the residual projections and norms of the last layer tail ran (nvllm.h NVL_DENSE_RAN_*; resid_gemm / launch_norm write it, nvl_op_dense_stages reports it)
     const int32_t* pending_slot_of = nullptr; const float* pending_gate_w = nullptr;   // MoE combine folded into the next norm
     // per-call metadata (one pinned host block mirrored on the device)
     int32_t* meta_host = nullptr; int32_t* meta_dev = nullptr; int64_t meta_ints = 0;

@@ -1581,6 +1581,8 @@ void launch_norm(nvl_model* m, float* x, const int32_t* rows_idx, const float* w
                  void* y, int rows) {
     KScope ks(m, KC_OTHER, 0, KS_NORM, (double)rows * m->H * (4.0 + (double)m->wsize));
     PendingResid pr{nullptr, 0, 0, 0.f, nullptr, nullptr};
+    m->dense_ran[NVL_DENSE_RAN_NORMS]++;    // (what ran, for nvl_op_dense_stages; below: the kernel that completes a projection's pending add)
+    int* consumed = m->pending_slices > 0 && !m->pending_slot_of ? &m->dense_ran[NVL_DENSE_RAN_CONSUMER + m->pending_from] : nullptr;
     if (m->pending_slices > 0) {            // complete the residual add the previous decode GEMM left as split-K slices
         pr.part = m->pending_part; pr.slices = m->pending_slices; pr.rows_total = m->pending_rows; pr.alpha = m->pending_alpha;
         pr.slot_of = m->pending_slot_of; pr.gate_w = m->pending_gate_w;
@@ -1589,10 +1591,11 @@ void launch_norm(nvl_model* m, float* x, const int32_t* rows_idx, const float* w
         const bool tile_kernel = sizeof(ActT) == 2 && m->H % 32 == 0 && m->H <= 2048 && g_norm_t16 && !pr.slot_of;   // (the 16-chunk instance would spill)
         if (!row_kernel && !tile_kernel) throw std::runtime_error("norm: no kernel for this pending residual");
     }
-    if (rows <= 512 && m->H <= 1024 * NORM_ROW_MAXCH)
+    if (rows <= 512 && m->H <= 1024 * NORM_ROW_MAXCH) {
+        if (consumed) *consumed = rows_idx ? NVL_NORM_RAN_ROW_IDX : NVL_NORM_RAN_ROW;
         hipLaunchKernelGGL((norm_row_kernel<ActT>), dim3(rows), dim3(256), 0, m->stream, x, rows_idx, w, b,
                            m->cfg.norm_eps, (ActT*)y, m->H, pr);
-    else if (sizeof(ActT) == 2 && m->H % 32 == 0 && m->H <= 4096 && g_norm_t16) {   // (wider rows would spill: norm_kernel)
+    } else if (sizeof(ActT) == 2 && m->H % 32 == 0 && m->H <= 4096 && g_norm_t16) {   // (wider rows would spill: norm_kernel)
         // 16 rows x H bf16 of LDS (up to 160 KiB); the row sits in registers: instance by chunks per lane
 #define NVL_NT16(CH, PEND)                                                                                             \
         do {                                                                                                           \
@@ -1600,6 +1603,7 @@ void launch_norm(nvl_model* m, float* x, const int32_t* rows_idx, const float* w
             hipLaunchKernelGGL((norm_tile16_kernel<CH, PEND>), dim3(cdiv(rows, 16)), dim3(1024), (size_t)16 * m->H * 2, m->stream, x, \
                                rows_idx, w, b, m->cfg.norm_eps, (bf16_t*)y, rows, m->H, pr);                            \
         } while (0)
+        if (consumed) *consumed = NVL_NORM_RAN_TILE16;
         if (pr.part) NVL_NT16(8, true);        // (H <= 2048: checked above)
         else { if (m->H <= 2048) NVL_NT16(8, false); else NVL_NT16(16, false); }
 #undef NVL_NT16
@@ -1843,7 +1847,10 @@ static int g_half_tiles = 1;   // nvl_set_tuning key 27: deferred-norm residual 
 // (producer and consumer agree through M alone: every projection of a pass has the same row count)
 // (only while the 16-row tiles leave CUs idle: at H = 4096 — 256 tiles — the halves doubled the x^2 partials every consumer
 // sums and the workgroups that each fetch the activations: Llama-3-8B B = 16 FFN-down 23.7 -> 34.2 us, O 9.3 -> 12.4 us)
-bool defer_half(const nvl_model* m, int M) { return g_half_tiles && M <= 16 && m->H % 128 == 0 && m->H / 16 < 256; }
+static int g_defer_norm = 1;   // nvl_set_tuning key 3: deferred RMSNorm between O-proj and FFN-up in decode (0 = off)
+// (keys 3 = 2 / 3: the producer runs without m_split, and only the m_split form has half tiles — it writes H / 16 partials
+//  per row, so the consumers must not look for H / 8: they summed the next rows' partials into rows 1..15)
+bool defer_half(const nvl_model* m, int M) { return g_half_tiles && g_defer_norm < 2 && M <= 16 && m->H % 128 == 0 && m->H / 16 < 256; }
 // after a forward's stream sync: did a P2P wait give up?  (a peer died or never called: the residual stream is garbage)
 void p2p_check(nvl_model* m) {
     if (!m->p2p_ready) return;
@@ -1896,7 +1903,6 @@ static int g_moe_small = 1;    // nvl_set_tuning key 8: fused MoE planning launc
 static int g_mamba_ssd = 1;    // nvl_set_tuning key 30: chunked (SSD) Mamba2 scan on MFMA for prefill-sized bf16 calls (0 = the sequential scan,
                                // 2 = chunk after chunk only, never the chunk-parallel three-launch form)
 static int g_decode_seam = 1;  // nvl_set_tuning key 7: decode_seam_kernel in nvl_decode_greedy (0 = separate kernels)
-static int g_defer_norm = 1;   // nvl_set_tuning key 3: deferred RMSNorm between O-proj and FFN-up in decode (0 = off)
 static int g_sk_slices = 0;    // tuning override (nvl_set_tuning key 1): 0 automatic, 1 = never split
 // consumer side of the deferred RMSNorm: the projection reads xn_raw and scales its accumulators (gemm.h)
 void set_deferred_in(nvl_model* m, GemmArgs& a) {
@@ -1922,10 +1928,18 @@ void resid_gemm(nvl_model* m, const void* A, int lda, const void* W, const float
         return;
     }
     GemmArgs a = mk(A, lda, W, m->x, N, bias, alpha, M, N, K);
+    // what this projection ran, for nvl_op_dense_stages (nvl_model::dense_ran): the O projection's record, or FFN-down's
+    const int which = m->site == KS_FFN_DOWN ? 1 : 0;
+    int* ran = m->dense_ran + 4 * which;
+    t_skinny_form = 0; t_skinny_half = 0;
+    auto record = [&](int producer, int slices) {
+        ran[NVL_DENSE_RAN_PRODUCER] = producer; ran[NVL_DENSE_RAN_HALF] = t_skinny_half; ran[NVL_DENSE_RAN_FORM] = t_skinny_form; ran[NVL_DENSE_RAN_SLICES] = slices;
+    };
     if (defer_norm_w) {     // deferred RMSNorm: x complete in this launch (no K split over workgroups) + xn_raw + x^2 partials
         a.nrm_w = defer_norm_w; a.nrm_xn = (bf16_t*)m->xn; a.rs_out = m->rs_part; a.m_split = g_defer_norm >= 2 ? 0 : 1;
         a.rs_half = a.m_split && N == m->H && defer_half(m, M) ? 1 : 0;
         gemm(m, EPI_RESID, true, a);
+        record(1, 0);
         return;
     }
     int slices = 1;
@@ -1951,8 +1965,11 @@ void resid_gemm(nvl_model* m, const void* A, int lda, const void* W, const float
         a.sk_part = m->sk_part; a.sk_slices = slices;
         gemm(m, EPI_RESID, true, a);
         m->pending_part = m->sk_part; m->pending_slices = slices; m->pending_rows = M; m->pending_alpha = alpha;
+        m->pending_from = which;
+        record(0, slices);
     } else {
         gemm(m, EPI_RESID, true, a);
+        record(0, 0);
     }
 }
 
@@ -2226,6 +2243,111 @@ void tap_layer(nvl_model* m, int li, int M) {
     NVL_HIP(hipGetLastError());
 }
 
+// What a pass decides once, for all of its layers, about the dense layer tail (enqueue_forward; nvl_op_dense_stages).
+// decode, RMSNorm + SwiGLU, sequential block: every residual projection carries the norm that follows it (deferred
+// RMSNorm, gemm.h), so a step keeps ONE norm launch (layer 0's, after the embedding) instead of 2L + 1
+struct TailPlan { bool big_decode, defer_ok, defer_moe_ok, all_rows; int n_seqs; };
+TailPlan tail_plan(const nvl_model* m, int M, int n_seqs, int max_len, uint32_t flags) {
+    const nvl_model_config& c = m->cfg;
+    const int H = m->H;
+    const bool big_decode = max_len == 1 && M <= g_chunk_max_m && g_force_tile == 0;
+    // (tensor parallel: the all-reduce launch carries the norm — one-shot payloads only, i.e. M <= 64 — when the P2P group is attached)
+    const bool tp_on = m->tp > 1 || m->tp_force;
+    const bool tp_defer = tp_on && m->p2p_ready && M <= g_p2p_oneshot_rows && M <= 64;
+    TailPlan t{};
+    t.big_decode = big_decode;      // (a decode batch that keeps the decode form above 64 rows: the QKV dispatch asks too)
+    t.defer_ok = g_defer_norm && !m->f32 && (M <= 64 || (M <= DEFER_MAX_M && big_decode && g_defer_norm == 1 && !tp_on)) && !c.use_moe && (!tp_on || tp_defer) && !m->keep_hidden &&
+                 c.block_style == NVL_BLOCK_SEQUENTIAL && c.norm_type == NVL_NORM_RMS &&
+                 c.activation_type == NVL_ACT_SWIGLU && H % 256 == 0 && m->rs_part && m->n_mamba == 0;
+    // MoE layers (decode form): only the O projection carries a norm (the FFN norm); the expert-down projection leaves
+    // K-slice partials that the next attention norm sums
+    t.defer_moe_ok = g_defer_norm && c.use_moe && M <= 64 && m->tp == 1 && !m->tp_force && c.block_style == NVL_BLOCK_SEQUENTIAL &&
+                     c.norm_type == NVL_NORM_RMS && H % 256 == 0 && m->rs_part && m->n_mamba == 0;
+    t.all_rows = (flags & NVL_FWD_ALL_LOGITS) != 0;
+    t.n_seqs = n_seqs;
+    return t;
+}
+
+// nvl_op_dense_stages looks at the buffers between the launches of layer_tail (a model passes none)
+enum { TAIL_X1 = 0, TAIL_OPERAND, TAIL_H, TAIL_X2 };     // after the O projection | FFN-up's operand in place | after FFN-up | after FFN-down
+struct StageHook { void (*fn)(void* ctx, int stage); void* ctx; };
+
+// One attention layer from its O projection to the end: both residual projections, the FFN (or MoE) between them, the
+// norms they do not carry.  Returns whether m->xn / m->rs_part hold the deferred operand of the norm (nxt_w, nxt_b) that
+// follows the layer (has_next: a layer's attention norm; else the final norm).
+bool layer_tail(nvl_model* m, const LayerW& l, int li, int M, const TailPlan& tp, const DevTensor* nxt_w, const DevTensor* nxt_b,
+                bool has_next, const StageHook* hook = nullptr) {
+    const nvl_model_config& c = m->cfg;
+    const int H = m->H, qw = m->nH * m->hd;
+    const bool defer_ok = tp.defer_ok, defer_moe_ok = tp.defer_moe_ok, all_rows = tp.all_rows;
+    const int n_seqs = tp.n_seqs;
+    bool xn_deferred = false;
+    auto at = [&](int stage) { if (hook) hook->fn(hook->ctx, stage); };
+    const float* bo = (const float*)l.t[NVL_T_BO].p;
+    if (c.block_style == NVL_BLOCK_PARALLEL) {
+        // generic_model.go:395-418: r + [am*]attn + [rm*]ffn, both branches read the same normed x
+        const bool mults = c.attention_multiplier != 0.f && c.residual_multiplier != 0.f;
+        ffn_up(m, l, M);
+        at(TAIL_H);
+        m->site = KS_OPROJ;
+        resid_gemm(m, m->attn_out, qw, l.t[NVL_T_WO].p, bo, mults ? c.attention_multiplier : 1.f, M, H, qw);
+        at(TAIL_X1);
+        m->site = KS_FFN_DOWN;
+        resid_gemm(m, m->hbuf, m->F, l.t[NVL_T_W2].p, (const float*)l.t[NVL_T_B2].p, mults ? c.residual_multiplier : 1.f,
+                   M, H, m->F);   // (only one of the two may be pending: the second one adds into x directly)
+        at(TAIL_X2);
+    } else {
+        // decode, RMSNorm + SwiGLU: the O-projection carries the FFN norm (deferred RMSNorm, gemm.h) — one launch less
+        const bool defer = (defer_ok || (defer_moe_ok && moe_dense_ok(m, l, M))) && m->pending_slices == 0 && !l.t[NVL_T_FFN_NORM_B].present();
+        m->site = KS_OPROJ;
+        if (defer) {
+            resid_gemm(m, m->attn_out, qw, l.t[NVL_T_WO].p, bo, m->resid_alpha, M, H, qw, (const float*)l.t[NVL_T_FFN_NORM_W].p);
+            at(TAIL_X1);
+        } else {
+            resid_gemm(m, m->attn_out, qw, l.t[NVL_T_WO].p, bo, m->resid_alpha, M, H, qw);
+            at(TAIL_X1);
+            norm(m, m->x, nullptr, l.t[NVL_T_FFN_NORM_W], l.t[NVL_T_FFN_NORM_B], m->xn, M);
+        }
+        at(TAIL_OPERAND);
+        // the FFN-down projection carries the NEXT layer's attention norm, or the final norm when every row is
+        // a last row (decode)
+        if (c.use_moe) {
+            const bool defer2 = defer && defer_moe_ok && g_defer_norm != 3 && !nxt_b->present() &&
+                                (has_next || (!all_rows && M == n_seqs && M <= 64));
+            xn_deferred = moe(m, l, M, defer, defer2 ? (const float*)nxt_w->p : nullptr);
+        } else {
+            ffn_up(m, l, M, defer);
+            at(TAIL_H);
+            const bool defer2 = defer_ok && g_defer_norm != 3 && m->pending_slices == 0 && !nxt_b->present() &&
+                                (has_next || (!all_rows && M == n_seqs && M <= 64));   // (the LM head of a larger batch runs on the tile kernels)
+            m->site = KS_FFN_DOWN;
+            resid_gemm(m, m->hbuf, m->F, l.t[NVL_T_W2].p, (const float*)l.t[NVL_T_B2].p, m->resid_alpha, M, H, m->F,
+                       defer2 ? (const float*)nxt_w->p : nullptr);
+            xn_deferred = defer2;
+        }
+        at(TAIL_X2);
+    }
+    tap_layer(m, li, M);
+    return xn_deferred;
+}
+
+// The norm after the last layer and the projection that reads it: the LM head of a model (W = lm_head, out = logits).
+// xn_deferred: the last FFN-down projection already produced the final norm's operand for every row.
+void head_proj(nvl_model* m, bool xn_deferred, const int32_t* rows_idx, int rows, const void* W, float* out, int ld, int N) {
+    const int H = m->H;
+    if (xn_deferred) {
+        GemmArgs al = mk(m->xn, H, W, out, ld, nullptr, 1.f, rows, N, H);
+        set_deferred_in(m, al);
+        m->site = KS_LM_HEAD;
+        gemm(m, EPI_STORE, true, al);
+    } else {
+        norm(m, m->x, rows_idx, m->g[NVL_T_FINAL_NORM_W], m->g[NVL_T_FINAL_NORM_B], m->xn_last, rows);
+        if (m->pending_slices != 0) throw std::runtime_error("forward: a split-K residual was left unconsumed");
+        m->site = KS_LM_HEAD;
+        gemm(m, EPI_STORE, true, mk(m->xn_last, H, W, out, ld, nullptr, 1.f, rows, N, H));
+    }
+}
+
 // Mamba2Layer.Forward between its two projections (mamba2.go:107-170) for the batch `a` describes: conv + softplus (and
 // the tail of a chained prefill), the scan in the form the batch calls for, gate + RMS norm into `out` (the out_proj
 // operand, ActT).  `a` arrives without the chunk-parallel scratch, which is the model's and grows here.  y_pre != NULL
@@ -2320,6 +2442,7 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
     m->kv_written = true;                  // (nvl_set_kv_scales is refused from here on)
     m->draft_valid = false;                // (the kept proposals of nvl_draft_sampled describe the pass before this one)
     m->pending_slices = 0;
+    std::fill(m->dense_ran, m->dense_ran + NVL_DENSE_RAN_INTS, 0);
     m->phase = max_len > 1 ? 0 : 1;         // per-site profile: prefill / decode
     if ((m->keep_hidden || m->tap) && m->hidden_tokens < M) {
         dfree(m->hidden);
@@ -2350,23 +2473,8 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
         NVL_HIP(hipGetLastError());
     }
 
-    const int qw = m->nH * m->hd;
-    const bool parallel = c.block_style == NVL_BLOCK_PARALLEL;
-
-    // decode, RMSNorm + SwiGLU, sequential block: every residual projection carries the norm that follows it (deferred
-    // RMSNorm, gemm.h), so a step keeps ONE norm launch (layer 0's, after the embedding) instead of 2L + 1
-    const bool big_decode = max_len == 1 && M <= g_chunk_max_m && g_force_tile == 0;
-    // (tensor parallel: the all-reduce launch carries the norm — one-shot payloads only, i.e. M <= 64 — when the P2P group is attached)
-    const bool tp_on = m->tp > 1 || m->tp_force;
-    const bool tp_defer = tp_on && m->p2p_ready && M <= g_p2p_oneshot_rows && M <= 64;
-    const bool defer_ok = g_defer_norm && !m->f32 && (M <= 64 || (M <= DEFER_MAX_M && big_decode && g_defer_norm == 1 && !tp_on)) && !c.use_moe && (!tp_on || tp_defer) && !m->keep_hidden &&
-                          c.block_style == NVL_BLOCK_SEQUENTIAL && c.norm_type == NVL_NORM_RMS &&
-                          c.activation_type == NVL_ACT_SWIGLU && H % 256 == 0 && m->rs_part && m->n_mamba == 0;
-    // MoE layers (decode form): only the O projection carries a norm (the FFN norm); the expert-down projection leaves
-    // K-slice partials that the next attention norm sums
-    const bool defer_moe_ok = g_defer_norm && c.use_moe && M <= 64 && m->tp == 1 && !m->tp_force && c.block_style == NVL_BLOCK_SEQUENTIAL &&
-                              c.norm_type == NVL_NORM_RMS && H % 256 == 0 && m->rs_part && m->n_mamba == 0;
-    const bool all_rows = (flags & NVL_FWD_ALL_LOGITS) != 0;
+    const TailPlan tp_ = tail_plan(m, M, n_seqs, max_len, flags);
+    const bool big_decode = tp_.big_decode;
     bool xn_deferred = false;       // m->xn holds xn_raw of the upcoming norm, m->rs_part its x^2 partials
     for (int li = 0; li < m->L; li++) {
         const LayerW& l = m->layers[li];
@@ -2431,45 +2539,9 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
                           (char*)m->vcache + (size_t)li * m->layer_stride, m->k_scale[li], m->v_scale[li]);
         else
             attention(m, li, md, n_seqs, max_len, attn_flops, fused_dec, (seam & 8) != 0);
-        const float* bo = (const float*)l.t[NVL_T_BO].p;
-        if (parallel) {
-            // generic_model.go:395-418: r + [am*]attn + [rm*]ffn, both branches read the same normed x
-            const bool mults = c.attention_multiplier != 0.f && c.residual_multiplier != 0.f;
-            ffn_up(m, l, M);
-            m->site = KS_OPROJ;
-            resid_gemm(m, m->attn_out, qw, l.t[NVL_T_WO].p, bo, mults ? c.attention_multiplier : 1.f, M, H, qw);
-            m->site = KS_FFN_DOWN;
-            resid_gemm(m, m->hbuf, m->F, l.t[NVL_T_W2].p, (const float*)l.t[NVL_T_B2].p, mults ? c.residual_multiplier : 1.f,
-                       M, H, m->F);   // (only one of the two may be pending: the second one adds into x directly)
-        } else {
-            // decode, RMSNorm + SwiGLU: the O-projection carries the FFN norm (deferred RMSNorm, gemm.h) — one launch less
-            const bool defer = (defer_ok || (defer_moe_ok && moe_dense_ok(m, l, M))) && m->pending_slices == 0 && !l.t[NVL_T_FFN_NORM_B].present();
-            m->site = KS_OPROJ;
-            if (defer) {
-                resid_gemm(m, m->attn_out, qw, l.t[NVL_T_WO].p, bo, m->resid_alpha, M, H, qw, (const float*)l.t[NVL_T_FFN_NORM_W].p);
-            } else {
-                resid_gemm(m, m->attn_out, qw, l.t[NVL_T_WO].p, bo, m->resid_alpha, M, H, qw);
-                norm(m, m->x, nullptr, l.t[NVL_T_FFN_NORM_W], l.t[NVL_T_FFN_NORM_B], m->xn, M);
-            }
-            // the FFN-down projection carries the NEXT layer's attention norm, or the final norm when every row is
-            // a last row (decode)
-            const DevTensor* nxt_w = li + 1 < m->L ? &m->layers[li + 1].t[NVL_T_ATTN_NORM_W] : &m->g[NVL_T_FINAL_NORM_W];
-            const DevTensor* nxt_b = li + 1 < m->L ? &m->layers[li + 1].t[NVL_T_ATTN_NORM_B] : &m->g[NVL_T_FINAL_NORM_B];
-            if (c.use_moe) {
-                const bool defer2 = defer && defer_moe_ok && g_defer_norm != 3 && !nxt_b->present() &&
-                                    (li + 1 < m->L || (!all_rows && M == n_seqs && M <= 64));
-                xn_deferred = moe(m, l, M, defer, defer2 ? (const float*)nxt_w->p : nullptr);
-            } else {
-                ffn_up(m, l, M, defer);
-                const bool defer2 = defer_ok && g_defer_norm != 3 && m->pending_slices == 0 && !nxt_b->present() &&
-                                    (li + 1 < m->L || (!all_rows && M == n_seqs && M <= 64));   // (the LM head of a larger batch runs on the tile kernels)
-                m->site = KS_FFN_DOWN;
-                resid_gemm(m, m->hbuf, m->F, l.t[NVL_T_W2].p, (const float*)l.t[NVL_T_B2].p, m->resid_alpha, M, H, m->F,
-                           defer2 ? (const float*)nxt_w->p : nullptr);
-                xn_deferred = defer2;
-            }
-        }
-        tap_layer(m, li, M);
+        const DevTensor* nxt_w = li + 1 < m->L ? &m->layers[li + 1].t[NVL_T_ATTN_NORM_W] : &m->g[NVL_T_FINAL_NORM_W];
+        const DevTensor* nxt_b = li + 1 < m->L ? &m->layers[li + 1].t[NVL_T_ATTN_NORM_B] : &m->g[NVL_T_FINAL_NORM_B];
+        xn_deferred = layer_tail(m, l, li, M, tp_, nxt_w, nxt_b, li + 1 < m->L);
     }
 
     // ---- final norm + LM head on the rows the caller keeps (generic_model.go:464-477, :595-604) ----
@@ -2510,17 +2582,7 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
         m->ctx_hint = 0;
         return M;
     }
-    if (xn_deferred) {       // the last FFN-down projection already produced the final norm's operand for every row
-        GemmArgs al = mk(m->xn, H, m->lm_head, m->logits, m->Vpad, nullptr, 1.f, rows, m->V, H);
-        set_deferred_in(m, al);
-        m->site = KS_LM_HEAD;
-        gemm(m, EPI_STORE, true, al);
-    } else {
-        norm(m, m->x, all ? nullptr : md.last_rows, m->g[NVL_T_FINAL_NORM_W], m->g[NVL_T_FINAL_NORM_B], m->xn_last, rows);
-        if (m->pending_slices != 0) throw std::runtime_error("forward: a split-K residual was left unconsumed");
-        m->site = KS_LM_HEAD;
-        gemm(m, EPI_STORE, true, mk(m->xn_last, H, m->lm_head, m->logits, m->Vpad, nullptr, 1.f, rows, m->V, H));
-    }
+    head_proj(m, xn_deferred, all ? nullptr : md.last_rows, rows, m->lm_head, m->logits, m->Vpad, m->V);
     if (seam & 4) {      // sampling reads the logits: apply LogitsScaling here (argmax_partial_kernel does it otherwise)
         if (c.logits_scaling != 0.f) {
             KScope ks(m, KC_OTHER);

@@ -803,29 +803,19 @@ extern "C" int nvl_op_moe(int device, int precision, const float* x, const float
     OP_CATCH
 }
 
-// moe() as a layer of the model runs it, stage by stage: finalize's weight forms (the interleaved gate|up rows with their
-// zero pad rows, the down matrices side by side along K under finalize's own predicate), the decode scratch of the
-// workspace allocation, keep_hidden off — so moe_dense_ok() answers as it does in a model —, then whatever moe() left for
-// the next norm completed by tap_hidden_kernel, as tap_layer does.  Every scratch buffer a form owns starts as 0xFF bytes
-// (NaN in bf16 and in fp32): the columns of an expert nobody picked, an unwritten K slice or a stale row show in y.
-extern "C" int nvl_op_moe_stages(int device, int precision, const float* x, const float* router, const float* w_in,
-                                 const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter, float* y,
-                                 float* router_logits, float* gate, int32_t* form) {
-    if (!x || !router || !w_in || !w_out || !y || !router_logits || !gate || !form || precision != NVL_PRECISION_BF16 || rows <= 0 ||
-        rows > (1 << 16) || hidden <= 0 || hidden % 64 || inter <= 0 || inter % 32 || n_experts < 1 || n_experts > 64 || top_k < 1 ||
-        top_k > n_experts)
-        return op_fail("nvl_op_moe_stages: bad arguments (bf16 only; hidden % 64, inter % 32, top_k <= n_experts <= 64)");
-    OP_TRY
-    OpCtx cx(device, precision);
+namespace {
+// The experts of one MoE layer as a model holds them, for the op entry points that run moe(): finalize's weight forms (the
+// interleaved gate|up rows with their zero pad rows, the down matrices side by side along K under finalize's own predicate),
+// the decode scratch and the sorted forms' workspaces of nvl_create, every buffer a form owns 0xFF bytes.  Sets m.H, m.F and
+// the expert counts; keep_hidden off, so moe_dense_ok() answers as in a model.  router [H][E], w_in [E][2 inter][H],
+// w_out [E][H][inter].
+void moe_op_setup(OpCtx& cx, LayerW& l, const float* router, const float* w_in, const float* w_out, int rows, int H, int E, int k, int inter) {
     nvl_model& m = cx.m;
-    const int E = n_experts, H = hidden, k = top_k;
     const int64_t pairs = (int64_t)rows * k, hp = round_up(H, W_ROW_PAD);
     auto nan_fill = [&](int64_t bytes) { void* p = cx.alloc(bytes); NVL_HIP(hipMemsetAsync(p, 0xFF, (size_t)bytes, m.stream)); return p; };
     m.H = H; m.F = inter;
     m.cfg.num_experts = E; m.cfg.num_experts_per_tok = k; m.cfg.use_moe = 1;
-    m.cfg.residual_multiplier = 0.f; m.resid_alpha = 1.f;      // multiplier 1 both ways (nvl_create's reading of 0)
     m.keep_hidden = false;
-    LayerW l;
     // the decode form's scratch (nvl_create) and weight (finalize, under its dense_form predicate)
     m.moe_gate = (float*)nan_fill(64 * (int64_t)E * 4);
     m.moe_hall = nan_fill(64 * (int64_t)E * inter * 2);
@@ -849,7 +839,6 @@ extern "C" int nvl_op_moe_stages(int device, int precision, const float* x, cons
                     memcpy(&pin[(size_t)((e * 2 * I + (int64_t)half * I) * H)], w_in + (e * 2 * inter + (int64_t)half * inter) * H, (size_t)inter * H * 4);
         }
     }
-    m.xn = cx.up_mat(x, rows, H, false);
     l.t[NVL_T_ROUTER].p = cx.up_mat(router, E, H, true, W_ROW_PAD);
     void* inc = cx.up_mat(I != inter ? pin.data() : w_in, (int64_t)E * 2 * I, H, false, W_ROW_PAD);
     std::vector<int32_t> idx;
@@ -877,6 +866,60 @@ extern "C" int nvl_op_moe_stages(int device, int precision, const float* x, cons
     m.moe_eo = (float*)nan_fill(pairs * H * 4);
     m.moe_xg = cx.alloc(round_up(pairs, 64) * H * 2);
     m.hbuf = nan_fill(round_up(pairs, 64) * I * 2);
+}
+// the fp32 router logits the routing consumed [rows][E] and the dense gate matrix [rows][E] (the sorted forms' expert ids /
+// weights scattered on the host); false: the routing chose an expert out of range
+bool moe_op_results(OpCtx& cx, int rows, int E, int k, float* router_logits, float* gate) {
+    nvl_model& m = cx.m;
+    const int64_t pairs = (int64_t)rows * k;
+    std::vector<float> lg((size_t)rows * 128);
+    cx.down(lg.data(), m.router_logits, (int64_t)rows * 128);
+    for (int r = 0; r < rows; r++) memcpy(router_logits + (size_t)r * E, &lg[(size_t)r * 128], (size_t)E * 4);
+    if (m.moe_form == NVL_MOE_FORM_DENSE_FUSED || m.moe_form == NVL_MOE_FORM_DENSE) {
+        cx.down(gate, m.moe_gate, (int64_t)rows * E);
+        return true;
+    }
+    std::vector<int32_t> ids((size_t)pairs);       // (token, rank) -> dense
+    std::vector<float> gw((size_t)pairs);
+    NVL_HIP(hipMemcpyAsync(ids.data(), m.expert_ids, (size_t)pairs * 4, hipMemcpyDeviceToHost, m.stream));
+    cx.down(gw.data(), m.expert_w, pairs);
+    std::fill(gate, gate + (size_t)rows * E, 0.f);
+    for (int64_t i = 0; i < pairs; i++) {
+        if (ids[(size_t)i] < 0 || ids[(size_t)i] >= E) return false;
+        gate[(size_t)((i / k) * E + ids[(size_t)i])] = gw[(size_t)i];
+    }
+    return true;
+}
+void moe_op_release(OpCtx& cx, LayerW& l) {      // (the buffers are the OpCtx's)
+    nvl_model& m = cx.m;
+    l.moe_in = nullptr; l.moe_out_cat = nullptr; l.t[NVL_T_ROUTER].p = nullptr; l.t[NVL_T_MOE_OUT].p = nullptr;
+    m.hbuf = nullptr; m.router_logits = nullptr; m.expert_ids = nullptr;
+    m.expert_w = nullptr; m.seg_start = m.perm_token = m.slot_of = nullptr; m.moe_eo = nullptr; m.moe_xg = nullptr;
+    m.moe_counts = m.moe_cursor = m.moe_tile_map = m.moe_n_mtiles = nullptr;
+    m.moe_gate = nullptr; m.moe_hall = nullptr; m.moe_part = nullptr;
+}
+}  // namespace
+
+// moe() as a layer of the model runs it, stage by stage: finalize's weight forms (the interleaved gate|up rows with their
+// zero pad rows, the down matrices side by side along K under finalize's own predicate), the decode scratch of the
+// workspace allocation, keep_hidden off — so moe_dense_ok() answers as it does in a model —, then whatever moe() left for
+// the next norm completed by tap_hidden_kernel, as tap_layer does.  Every scratch buffer a form owns starts as 0xFF bytes
+// (NaN in bf16 and in fp32): the columns of an expert nobody picked, an unwritten K slice or a stale row show in y.
+extern "C" int nvl_op_moe_stages(int device, int precision, const float* x, const float* router, const float* w_in,
+                                 const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter, float* y,
+                                 float* router_logits, float* gate, int32_t* form) {
+    if (!x || !router || !w_in || !w_out || !y || !router_logits || !gate || !form || precision != NVL_PRECISION_BF16 || rows <= 0 ||
+        rows > (1 << 16) || hidden <= 0 || hidden % 64 || inter <= 0 || inter % 32 || n_experts < 1 || n_experts > 64 || top_k < 1 ||
+        top_k > n_experts)
+        return op_fail("nvl_op_moe_stages: bad arguments (bf16 only; hidden % 64, inter % 32, top_k <= n_experts <= 64)");
+    OP_TRY
+    OpCtx cx(device, precision);
+    nvl_model& m = cx.m;
+    const int E = n_experts, H = hidden, k = top_k;
+    m.cfg.residual_multiplier = 0.f; m.resid_alpha = 1.f;      // multiplier 1 both ways (nvl_create's reading of 0)
+    LayerW l;
+    moe_op_setup(cx, l, router, w_in, w_out, rows, H, E, k, inter);
+    m.xn = cx.up_mat(x, rows, H, false);
     m.x = (float*)cx.alloc((int64_t)rows * H * 4);
     NVL_HIP(hipMemsetAsync(m.x, 0, (size_t)rows * H * 4, m.stream));
     moe(&m, l, rows);
@@ -890,27 +933,258 @@ extern "C" int nvl_op_moe_stages(int device, int precision, const float* x, cons
         NVL_HIP(hipGetLastError());
     }
     cx.down(y, yd, (int64_t)rows * H);
-    std::vector<float> lg((size_t)rows * 128);
-    cx.down(lg.data(), m.router_logits, (int64_t)rows * 128);
-    for (int r = 0; r < rows; r++) memcpy(router_logits + (size_t)r * E, &lg[(size_t)r * 128], (size_t)E * 4);
-    if (m.moe_form == NVL_MOE_FORM_DENSE_FUSED || m.moe_form == NVL_MOE_FORM_DENSE) {
-        cx.down(gate, m.moe_gate, (int64_t)rows * E);
-    } else {       // (token, rank) -> dense
-        std::vector<int32_t> ids((size_t)pairs);
-        std::vector<float> gw((size_t)pairs);
-        NVL_HIP(hipMemcpyAsync(ids.data(), m.expert_ids, (size_t)pairs * 4, hipMemcpyDeviceToHost, m.stream));
-        cx.down(gw.data(), m.expert_w, pairs);
-        std::fill(gate, gate + (size_t)rows * E, 0.f);
-        for (int64_t i = 0; i < pairs; i++) {
-            if (ids[(size_t)i] < 0 || ids[(size_t)i] >= E) return op_fail("nvl_op_moe_stages: the routing chose an expert out of range", NVL_ERR_STATE);
-            gate[(size_t)((i / k) * E + ids[(size_t)i])] = gw[(size_t)i];
+    if (!moe_op_results(cx, rows, E, k, router_logits, gate)) return op_fail("nvl_op_moe_stages: the routing chose an expert out of range", NVL_ERR_STATE);
+    moe_op_release(cx, l);
+    m.xn = nullptr; m.x = nullptr;
+    m.pending_part = nullptr; m.pending_slices = 0; m.pending_slot_of = nullptr; m.pending_gate_w = nullptr;
+    return NVL_OK;
+    OP_CATCH
+}
+
+// The dense layer tail as a layer of the model runs it — layer_tail() itself, under tail_plan()'s decisions — on host inputs,
+// bf16 mode: O projection, FFN norm, FFN-up, FFN-down, the norm after the layer and the projection that reads it (a next
+// layer's QKV-shaped projection, or head_proj() on last_rows).  Scratch as nvl_create sizes it (sk_part, rs_part, xn, hbuf,
+// xn_last), every scratch buffer and every output 0xFF bytes (NaN as bf16 and as fp32) beforehand.  Between the launches a
+// StageHook copies what the next launch will read; a residual add still pending is completed by tap_hidden_kernel into the
+// copy, as tap_layer does, and stays pending for the norm that consumes it in the model.
+namespace {
+struct DenseTap {
+    nvl_model* m; int M;
+    float *x1, *x2, *rs1; void *op1, *h; int rs1_tiles = 0; int64_t op_bytes, h_bytes, rs_bytes;
+    void take_x(float* dst) {
+        if (m->pending_slices == 0) { NVL_HIP(hipMemcpyAsync(dst, m->x, (size_t)M * m->H * 4, hipMemcpyDeviceToDevice, m->stream)); return; }
+        PendingResid pr{m->pending_part, m->pending_slices, m->pending_rows, m->pending_alpha, m->pending_slot_of, m->pending_gate_w};
+        hipLaunchKernelGGL(tap_hidden_kernel, dim3(M), dim3(256), 0, m->stream, m->x, dst, m->H, pr);
+        NVL_HIP(hipGetLastError());
+    }
+    void stage(int which) {
+        if (which == TAIL_X1) take_x(x1);
+        else if (which == TAIL_X2) take_x(x2);
+        else if (which == TAIL_H) NVL_HIP(hipMemcpyAsync(h, m->hbuf, (size_t)h_bytes, hipMemcpyDeviceToDevice, m->stream));
+        else {
+            NVL_HIP(hipMemcpyAsync(op1, m->xn, (size_t)op_bytes, hipMemcpyDeviceToDevice, m->stream));
+            NVL_HIP(hipMemcpyAsync(rs1, m->rs_part, (size_t)rs_bytes, hipMemcpyDeviceToDevice, m->stream));
+            rs1_tiles = m->dense_ran[NVL_DENSE_RAN_PRODUCER] ? (defer_half(m, M) ? m->H / 8 : m->H / 16) : 0;
         }
     }
-    l.moe_in = nullptr; l.moe_out_cat = nullptr; l.t[NVL_T_ROUTER].p = nullptr; l.t[NVL_T_MOE_OUT].p = nullptr;
-    m.xn = m.hbuf = nullptr; m.x = nullptr; m.router_logits = nullptr; m.expert_ids = nullptr;
-    m.expert_w = nullptr; m.seg_start = m.perm_token = m.slot_of = nullptr; m.moe_eo = nullptr; m.moe_xg = nullptr;
-    m.moe_counts = m.moe_cursor = m.moe_tile_map = m.moe_n_mtiles = nullptr;
-    m.moe_gate = nullptr; m.moe_hall = nullptr; m.moe_part = nullptr;
+    static void call(void* ctx, int which) { ((DenseTap*)ctx)->stage(which); }
+};
+}  // namespace
+
+extern "C" int nvl_op_dense_stages(int device, int precision, const nvl_dense_stages* d) {
+    if (!d || precision != NVL_PRECISION_BF16 || d->struct_bytes != (int32_t)sizeof(nvl_dense_stages))
+        return op_fail("nvl_op_dense_stages: bad arguments (bf16 only; struct_bytes = sizeof(nvl_dense_stages))");
+    const int M = d->rows, H = d->hidden, qw = d->q_width, F = d->ffn, Nn = d->n_next, nl = d->n_last_rows;
+    const bool swiglu = d->activation_type == NVL_ACT_SWIGLU, last = !d->has_next;
+    if (!d->x || !d->attn_out || !d->wo || !d->norm_w || !d->w1 || !d->w2 || !d->next_norm_w || !d->wn || !d->x1 || !d->op1 || !d->rs1 ||
+        !d->h || !d->x2 || !d->op2 || !d->rs2 || !d->yn || !d->x_end || !d->ran)
+        return op_fail("nvl_op_dense_stages: null argument");
+    // what nvl_create refuses
+    if (M <= 0 || M > SK_TILE_MAX_M || H <= 0 || F <= 0 || qw <= 0 || Nn <= 0 || d->max_len <= 0)
+        return op_fail("nvl_op_dense_stages: non-positive dimension (rows <= 2048)");
+    if (H % 64 != 0 || F % 64 != 0 || qw % 64 != 0) return op_fail("nvl_op_dense_stages: hidden, ffn and q_width must be multiples of 64");
+    if (d->attention_multiplier < 0.f) return op_fail("nvl_op_dense_stages: attention_multiplier must not be negative");
+    if ((d->norm_type != NVL_NORM_RMS && d->norm_type != NVL_NORM_LAYER) || (d->activation_type != NVL_ACT_SWIGLU && d->activation_type != NVL_ACT_GELU) ||
+        (d->block_style != NVL_BLOCK_SEQUENTIAL && d->block_style != NVL_BLOCK_PARALLEL))
+        return op_fail("nvl_op_dense_stages: bad norm_type / activation_type / block_style");
+    if (d->norm_type == NVL_NORM_LAYER && (!d->norm_b || !d->next_norm_b)) return op_fail("nvl_op_dense_stages: LayerNorm needs its biases");
+    if (last && (!d->last_rows || nl <= 0 || nl > M)) return op_fail("nvl_op_dense_stages: the last layer needs last_rows (1..rows of them)");
+    if (!last && (d->last_rows || nl != 0)) return op_fail("nvl_op_dense_stages: last_rows belong to the last layer");
+    for (int i = 0; last && i < nl; i++)
+        if (d->last_rows[i] < 0 || d->last_rows[i] >= M) return op_fail("nvl_op_dense_stages: last_rows out of range", NVL_ERR_POSITION);
+    if (d->max_len == 1 && last && nl != M) return op_fail("nvl_op_dense_stages: a decode pass keeps every row (n_last_rows = rows)");
+    OP_TRY
+    OpCtx cx(device, precision);
+    nvl_model& m = cx.m;
+    auto nan_fill = [&](int64_t bytes) { void* p = cx.alloc(bytes); NVL_HIP(hipMemsetAsync(p, 0xFF, (size_t)bytes, m.stream)); return p; };
+    m.H = H; m.F = F; m.hd = 64; m.nH = qw / 64; m.L = last ? 1 : 2;
+    m.cfg.norm_type = d->norm_type; m.cfg.activation_type = d->activation_type; m.cfg.block_style = d->block_style;
+    m.cfg.norm_eps = d->norm_eps; m.cfg.attention_multiplier = d->attention_multiplier; m.cfg.residual_multiplier = d->residual_multiplier;
+    m.cfg.use_moe = 0;
+    m.resid_alpha = d->residual_multiplier != 0.f ? d->residual_multiplier : 1.0f;      // (nvl_create)
+    m.keep_hidden = false;
+    const int64_t Mp = round_up(M, 64), rows_out = last ? nl : M;
+    // workspaces (nvl_create, max_batch_tokens = rows)
+    m.x = cx.up_f32(d->x, (int64_t)M * H);
+    m.attn_out = cx.up_mat(d->attn_out, M, qw, false);
+    m.xn = nan_fill(Mp * H * 2);
+    m.hbuf = nan_fill(Mp * F * 2);
+    m.xn_last = nan_fill(round_up(rows_out, 64) * H * 2);
+    m.sk_rows = (int)std::min<int64_t>(std::max<int64_t>(M, 64), SK_TILE_MAX_M);
+    const int64_t sk_floats = (int64_t)std::max(m.sk_max_slices, SK_TILE_MAX_SLICES) * m.sk_rows * H;
+    m.sk_part = (float*)nan_fill(sk_floats * 4);
+    const int64_t rs_floats = (int64_t)cdiv(H, 8) * DEFER_MAX_M;
+    m.rs_part = (float*)nan_fill(rs_floats * 4);
+    // weights (finalize's forms)
+    LayerW l;
+    l.t[NVL_T_WO].p = cx.up_mat(d->wo, H, qw, false, W_ROW_PAD);
+    if (d->bo) l.t[NVL_T_BO].p = cx.up_f32(d->bo, H);
+    l.t[NVL_T_FFN_NORM_W].p = cx.up_f32(d->norm_w, H);
+    if (d->norm_b) l.t[NVL_T_FFN_NORM_B].p = cx.up_f32(d->norm_b, H);
+    const int n1 = swiglu ? 2 * F : F;
+    void* w1c = cx.up_mat(d->w1, n1, H, false, W_ROW_PAD);       // canonical [n1][H] (gate rows | up rows)
+    if (swiglu) {
+        auto idx = swiglu_interleave(F, 0);
+        idx.resize((size_t)round_up(n1, W_ROW_PAD), -1);
+        l.w1 = cx.alloc((int64_t)idx.size() * H * 2);
+        gather_rows(&m, w1c, idx, l.w1, H);
+    } else {
+        l.w1 = w1c;
+    }
+    if (d->b1) l.t[NVL_T_B1].p = cx.up_f32(d->b1, F);
+    l.t[NVL_T_W2].p = cx.up_mat(d->w2, H, F, false, W_ROW_PAD);
+    if (d->b2) l.t[NVL_T_B2].p = cx.up_f32(d->b2, H);
+    m.g[NVL_T_FINAL_NORM_W].p = cx.up_f32(d->next_norm_w, H);     // (the norm after the layer, whichever it is)
+    if (d->next_norm_b) m.g[NVL_T_FINAL_NORM_B].p = cx.up_f32(d->next_norm_b, H);
+    void* wn = cx.up_mat(d->wn, Nn, H, false, W_ROW_PAD);
+    const int ldn = (int)round_up(Nn, 128);
+    float* yn = (float*)nan_fill(round_up(rows_out, 64) * (int64_t)ldn * 4);
+    int32_t* rows_idx = nullptr;
+    if (last) {
+        rows_idx = (int32_t*)cx.alloc((int64_t)nl * 4);
+        NVL_HIP(hipMemcpyAsync(rows_idx, d->last_rows, (size_t)nl * 4, hipMemcpyHostToDevice, m.stream));
+    }
+    DenseTap tap{&m, M};
+    tap.op_bytes = Mp * H * 2; tap.h_bytes = Mp * F * 2; tap.rs_bytes = rs_floats * 4;
+    tap.x1 = (float*)nan_fill((int64_t)M * H * 4); tap.x2 = (float*)nan_fill((int64_t)M * H * 4);
+    tap.op1 = nan_fill(tap.op_bytes); tap.h = nan_fill(tap.h_bytes); tap.rs1 = (float*)nan_fill(tap.rs_bytes);
+    const StageHook hook{&DenseTap::call, &tap};
+    std::fill(m.dense_ran, m.dense_ran + NVL_DENSE_RAN_INTS, 0);
+    m.pending_slices = 0;
+    m.phase = d->max_len > 1 ? 0 : 1;
+    const TailPlan plan = tail_plan(&m, M, last ? nl : (d->max_len == 1 ? M : 1), d->max_len, 0);
+    if (d->block_style == NVL_BLOCK_PARALLEL) {      // both branches read the block's one norm, which precedes the attention
+        norm(&m, m.x, nullptr, l.t[NVL_T_FFN_NORM_W], l.t[NVL_T_FFN_NORM_B], m.xn, M);
+        tap.stage(TAIL_OPERAND);
+    }
+    const bool xn_deferred = layer_tail(&m, l, 0, M, plan, &m.g[NVL_T_FINAL_NORM_W], &m.g[NVL_T_FINAL_NORM_B], !last, &hook);
+    const void* op2_src = m.xn;
+    if (!last) {      // the next layer's front: its attention norm unless the operand is deferred, then its projection
+        if (!xn_deferred) norm(&m, m.x, nullptr, m.g[NVL_T_FINAL_NORM_W], m.g[NVL_T_FINAL_NORM_B], m.xn, M);
+        GemmArgs aq = mk(m.xn, H, wn, yn, ldn, nullptr, 1.f, M, Nn, H);
+        if (xn_deferred) set_deferred_in(&m, aq);
+        m.site = KS_QKV;
+        gemm(&m, EPI_STORE, true, aq);
+    } else {
+        head_proj(&m, xn_deferred, rows_idx, (int)rows_out, wn, yn, ldn, Nn);
+        if (!xn_deferred) op2_src = m.xn_last;
+    }
+    if (m.pending_slices != 0) throw std::runtime_error("nvl_op_dense_stages: a split-K residual was left unconsumed");
+    const int rs2_tiles = xn_deferred ? (defer_half(&m, M) ? H / 8 : H / 16) : 0;
+    // ---- read back
+    NVL_HIP(hipStreamSynchronize(m.stream));
+    cx.down(d->x1, tap.x1, (int64_t)M * H);
+    cx.down(d->x2, tap.x2, (int64_t)M * H);
+    cx.down(d->x_end, m.x, (int64_t)M * H);
+    auto unfrag = [&](float* dst, const void* src, int64_t rows, int64_t K) {
+        std::vector<uint16_t> ob((size_t)(round_up(rows, 16) * K));
+        NVL_HIP(hipMemcpyAsync(ob.data(), src, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
+        NVL_HIP(hipStreamSynchronize(m.stream));
+        for (int64_t r = 0; r < rows; r++)
+            for (int64_t c = 0; c < K; c++) {
+                const uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, K)]) << 16;
+                memcpy(&dst[(size_t)(r * K + c)], &u, 4);
+            }
+    };
+    auto partials = [&](float* dst, const float* src, int tiles, int64_t rows) {      // [rows][tiles] of [rows][hidden / 8]
+        std::vector<float> rs((size_t)rs_floats);
+        cx.down(rs.data(), src, rs_floats);
+        for (int64_t r = 0; r < rows; r++)
+            for (int t = 0; t < H / 8; t++) dst[(size_t)(r * (H / 8) + t)] = t < tiles ? rs[(size_t)(r * tiles + t)] : 0.f;
+    };
+    unfrag(d->op1, tap.op1, M, H);
+    partials(d->rs1, tap.rs1, tap.rs1_tiles, M);
+    unfrag(d->h, tap.h, M, F);
+    unfrag(d->op2, op2_src, xn_deferred ? M : rows_out, H);
+    partials(d->rs2, m.rs_part, rs2_tiles, M);
+    {
+        std::vector<float> y((size_t)(rows_out * ldn));
+        cx.down(y.data(), yn, rows_out * ldn);
+        for (int64_t r = 0; r < rows_out; r++) memcpy(d->yn + (size_t)(r * Nn), &y[(size_t)(r * ldn)], (size_t)Nn * 4);
+    }
+    for (int i = 0; i < NVL_DENSE_RAN_INTS; i++) d->ran[i] = m.dense_ran[i];
+    d->ran[NVL_DENSE_RAN_RS1_TILES] = tap.rs1_tiles; d->ran[NVL_DENSE_RAN_RS2_TILES] = rs2_tiles;
+    for (auto& t : l.t) t.p = nullptr;
+    l.w1 = nullptr;
+    m.g[NVL_T_FINAL_NORM_W].p = nullptr; m.g[NVL_T_FINAL_NORM_B].p = nullptr;
+    m.x = nullptr; m.attn_out = m.xn = m.hbuf = m.xn_last = nullptr; m.sk_part = m.rs_part = nullptr;
+    m.pending_part = nullptr; m.pending_slices = 0;
+    return NVL_OK;
+    OP_CATCH
+}
+
+// The same tail with a MoE block between the projections, decode only (rows <= 64): the O projection as the deferred-RMSNorm
+// producer of the FFN norm, then moe(m, l, M, deferred_norm = true) — the router (in either routing form) and the expert up
+// projection scale their accumulators by rstd from the x^2 partials —, whose down projection leaves K slices in moe_part
+// pending for the next norm.  layer_tail() again, under tail_plan(); experts and scratch from moe_op_setup().
+extern "C" int nvl_op_dense_moe_stages(int device, int precision, const float* x, const float* attn_out, const float* wo,
+                                       const float* bo, const float* norm_w, const float* router, const float* w_in,
+                                       const float* w_out, const float* next_norm_w, int rows, int hidden, int q_width,
+                                       int n_experts, int top_k, int inter, float residual_multiplier, float norm_eps,
+                                       float* x1, float* op1, float* rs1, float* router_logits, float* gate, float* y,
+                                       int32_t* form, int32_t* ran) {
+    if (!x || !attn_out || !wo || !norm_w || !router || !w_in || !w_out || !next_norm_w || !x1 || !op1 || !rs1 || !router_logits ||
+        !gate || !y || !form || !ran || precision != NVL_PRECISION_BF16 || rows <= 0 || rows > 64 || hidden <= 0 || hidden % 64 ||
+        q_width <= 0 || q_width % 64 || inter <= 0 || inter % 64 || n_experts < 1 || n_experts > 64 || top_k < 1 || top_k > n_experts)
+        return op_fail("nvl_op_dense_moe_stages: bad arguments (bf16 only; rows <= 64; hidden, q_width, inter % 64; top_k <= n_experts <= 64)");
+    OP_TRY
+    OpCtx cx(device, precision);
+    nvl_model& m = cx.m;
+    const int M = rows, H = hidden, E = n_experts;
+    auto nan_fill = [&](int64_t bytes) { void* p = cx.alloc(bytes); NVL_HIP(hipMemsetAsync(p, 0xFF, (size_t)bytes, m.stream)); return p; };
+    m.hd = 64; m.nH = q_width / 64; m.L = 2;
+    m.cfg.norm_type = NVL_NORM_RMS; m.cfg.activation_type = NVL_ACT_SWIGLU; m.cfg.block_style = NVL_BLOCK_SEQUENTIAL;
+    m.cfg.norm_eps = norm_eps; m.cfg.residual_multiplier = residual_multiplier;
+    m.resid_alpha = residual_multiplier != 0.f ? residual_multiplier : 1.0f;      // (nvl_create)
+    LayerW l;
+    moe_op_setup(cx, l, router, w_in, w_out, M, H, E, top_k, inter);
+    const int64_t Mp = round_up(M, 64);
+    m.x = cx.up_f32(x, (int64_t)M * H);
+    m.attn_out = cx.up_mat(attn_out, M, q_width, false);
+    m.xn = nan_fill(Mp * H * 2);
+    m.sk_rows = 64;
+    m.sk_part = (float*)nan_fill((int64_t)std::max(m.sk_max_slices, SK_TILE_MAX_SLICES) * m.sk_rows * H * 4);
+    const int64_t rs_floats = (int64_t)cdiv(H, 8) * DEFER_MAX_M;
+    m.rs_part = (float*)nan_fill(rs_floats * 4);
+    l.t[NVL_T_WO].p = cx.up_mat(wo, H, q_width, false, W_ROW_PAD);
+    if (bo) l.t[NVL_T_BO].p = cx.up_f32(bo, H);
+    l.t[NVL_T_FFN_NORM_W].p = cx.up_f32(norm_w, H);
+    m.g[NVL_T_FINAL_NORM_W].p = cx.up_f32(next_norm_w, H);
+    DenseTap tap{&m, M};
+    tap.op_bytes = Mp * H * 2; tap.h_bytes = 0; tap.rs_bytes = rs_floats * 4;
+    tap.x1 = (float*)nan_fill((int64_t)M * H * 4); tap.x2 = (float*)nan_fill((int64_t)M * H * 4);
+    tap.op1 = nan_fill(tap.op_bytes); tap.h = nullptr; tap.rs1 = (float*)nan_fill(tap.rs_bytes);
+    const StageHook hook{&DenseTap::call, &tap};
+    std::fill(m.dense_ran, m.dense_ran + NVL_DENSE_RAN_INTS, 0);
+    m.pending_slices = 0;
+    m.phase = 1;
+    const TailPlan plan = tail_plan(&m, M, M, 1, 0);
+    const bool xn_deferred = layer_tail(&m, l, 0, M, plan, &m.g[NVL_T_FINAL_NORM_W], &m.g[NVL_T_FINAL_NORM_B], true, &hook);
+    *form = m.moe_form;
+    NVL_HIP(hipStreamSynchronize(m.stream));
+    cx.down(x1, tap.x1, (int64_t)M * H);
+    cx.down(y, tap.x2, (int64_t)M * H);
+    {
+        std::vector<uint16_t> ob((size_t)(round_up(M, 16) * H));
+        NVL_HIP(hipMemcpyAsync(ob.data(), tap.op1, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
+        std::vector<float> rs((size_t)rs_floats);
+        cx.down(rs.data(), tap.rs1, rs_floats);
+        for (int64_t r = 0; r < M; r++) {
+            for (int64_t c = 0; c < H; c++) {
+                const uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, H)]) << 16;
+                memcpy(&op1[(size_t)(r * H + c)], &u, 4);
+            }
+            for (int t = 0; t < H / 8; t++) rs1[(size_t)(r * (H / 8) + t)] = t < tap.rs1_tiles ? rs[(size_t)(r * tap.rs1_tiles + t)] : 0.f;
+        }
+    }
+    if (!moe_op_results(cx, M, E, top_k, router_logits, gate)) return op_fail("nvl_op_dense_moe_stages: the routing chose an expert out of range", NVL_ERR_STATE);
+    for (int i = 0; i < NVL_DENSE_RAN_INTS; i++) ran[i] = m.dense_ran[i];
+    ran[NVL_DENSE_RAN_SLICES + 4] = m.pending_slices;      // (what moe() left for the next norm: its down projection is no resid_gemm)
+    ran[NVL_DENSE_RAN_RS1_TILES] = tap.rs1_tiles; ran[NVL_DENSE_RAN_RS2_TILES] = xn_deferred ? 1 : 0;
+    moe_op_release(cx, l);
+    for (auto& t : l.t) t.p = nullptr;
+    m.g[NVL_T_FINAL_NORM_W].p = nullptr;
+    m.x = nullptr; m.attn_out = m.xn = nullptr; m.sk_part = m.rs_part = nullptr;
     m.pending_part = nullptr; m.pending_slices = 0; m.pending_slot_of = nullptr; m.pending_gate_w = nullptr;
     return NVL_OK;
     OP_CATCH

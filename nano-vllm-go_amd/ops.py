@@ -241,6 +241,87 @@ def moe_stages(x, router, w_in, w_out, top_k, precision="bf16", device=0):   # M
     return out
 
 
+RESID_FORMS = {0: "tile", 1: "msplit", 2: "groups", 3: "groups_serial", 4: "decode"}      # NVL_RESID_FORM_*
+NORM_RAN = {0: None, 1: "row", 2: "row_idx", 3: "tile16"}                                   # NVL_NORM_RAN_*
+
+
+def dense_stages(x, attn_out, wo, norm_w, w1, w2, next_norm_w, wn, bo=None, norm_b=None, b1=None, b2=None, next_norm_b=None,
+                 norm="rms", act="swiglu", block="sequential", residual_multiplier=0.0, attention_multiplier=0.0, norm_eps=1e-5,
+                 max_len=1, last_rows=None, has_next=True, precision="bf16", device=0):   # generic_model.go:320-418
+    """The dense layer tail as a layer of the model runs it, stage by stage (nvl_op_dense_stages; bf16 only).  x [M][H],
+    attn_out [M][qw], wo [H][qw], w1 [2F][H] (gate rows | up rows; GELU: [F][H]), w2 [H][F], wn [Nn][H]; has_next=False is
+    the last layer: last_rows (default: every row, a decode pass) feed the final norm and wn as the LM head.
+    -> dict(x1, op1, rs1 (None = op1 is already normalised, else the x^2 partials [M][tiles]), h, x2, op2, rs2, yn, x_end,
+    ran = dict(o=..., down=..., norms, rs1_tiles, rs2_tiles) with o / down = dict(producer, half, form (a RESID_FORMS
+    name), slices, consumer (a NORM_RAN name)))."""
+    x, attn_out, wo, norm_w, w1, w2, next_norm_w, wn = (_f(a) for a in (x, attn_out, wo, norm_w, w1, w2, next_norm_w, wn))
+    opt = [None if a is None else _f(a) for a in (bo, norm_b, b1, b2, next_norm_b)]
+    M, H = x.shape
+    qw, Nn, swiglu = attn_out.shape[1], wn.shape[0], act == "swiglu"
+    F = w2.shape[1]
+    if attn_out.shape != (M, qw) or wo.shape != (H, qw) or w1.shape != ((2 * F if swiglu else F), H) or w2.shape != (H, F) or \
+            wn.shape != (Nn, H) or norm_w.shape != (H,) or next_norm_w.shape != (H,):
+        raise ValueError("dense_stages: shapes do not match")
+    lr = None
+    if not has_next:
+        lr = np.ascontiguousarray(np.arange(M) if last_rows is None else last_rows, dtype=np.int32)
+    elif last_rows is not None:
+        raise ValueError("dense_stages: last_rows belong to the last layer")
+    n_out = M if lr is None else len(lr)
+    nan = lambda *s: np.full(s, np.nan, np.float32)
+    out = dict(x1=nan(M, H), op1=nan(M, H), rs1=nan(M, H // 8), h=nan(M, F), x2=nan(M, H), op2=nan(M, H), rs2=nan(M, H // 8),
+               yn=nan(n_out, Nn), x_end=nan(M, H))
+    ran = np.zeros(14, np.int32)
+    d = L.DenseStagesC(struct_bytes=C.sizeof(L.DenseStagesC), rows=M, hidden=H, q_width=qw, ffn=F, n_next=Nn,
+                       norm_type=1 if norm == "rms" else 0, activation_type=1 if swiglu else 0,
+                       block_style=1 if block == "parallel" else 0, max_len=int(max_len), has_next=1 if has_next else 0,
+                       n_last_rows=0 if lr is None else len(lr), residual_multiplier=residual_multiplier,
+                       attention_multiplier=attention_multiplier, norm_eps=norm_eps)
+    keep = dict(x=x, attn_out=attn_out, wo=wo, bo=opt[0], norm_w=norm_w, norm_b=opt[1], w1=w1, b1=opt[2], w2=w2, b2=opt[3],
+                next_norm_w=next_norm_w, next_norm_b=opt[4], wn=wn, last_rows=lr, ran=ran, **out)
+    for k, v in keep.items():
+        setattr(d, k, None if v is None else v.ctypes.data)
+    L.check(L.lib().nvl_op_dense_stages(device, L.PRECISION[precision], C.byref(d)))
+    t1, t2 = int(ran[12]), int(ran[13])
+    out["rs1"] = out["rs1"][:, :t1].copy() if t1 else None
+    out["rs2"] = out["rs2"][:, :t2].copy() if t2 else None
+    if not t2:
+        out["op2"] = out["op2"][:n_out]
+    proj = lambda p: dict(producer=int(ran[4 * p]), half=int(ran[4 * p + 1]), form=RESID_FORMS[int(ran[4 * p + 2])],
+                          slices=int(ran[4 * p + 3]), consumer=NORM_RAN[int(ran[9 + p])])
+    out["ran"] = dict(o=proj(0), down=proj(1), norms=int(ran[8]), rs1_tiles=t1, rs2_tiles=t2)
+    return out
+
+
+def dense_moe_stages(x, attn_out, wo, norm_w, router, w_in, w_out, next_norm_w, top_k, bo=None, residual_multiplier=0.0,
+                     norm_eps=1e-5, precision="bf16", device=0):   # generic_model.go:320-389 around moe.go:43
+    """The layer tail with a MoE block, decode (nvl_op_dense_moe_stages): the O projection carries the FFN norm, moe() reads
+    the deferred operand, its down projection stays pending.  router [H][E], w_in [E][2I][H], w_out [E][H][I] ->
+    dict(x1, op1, rs1 (x^2 partials, None = op1 is normalised), router_logits, gate, y (x after the block), form (a
+    MOE_FORMS name), ran as dense_stages gives it; ran["down"]["slices"] = what moe() left pending)."""
+    x, attn_out, wo, norm_w, router, w_in, w_out, next_norm_w = (_f(a) for a in (x, attn_out, wo, norm_w, router, w_in, w_out, next_norm_w))
+    bo = None if bo is None else _f(bo)
+    M, H = x.shape
+    qw, E, I = attn_out.shape[1], router.shape[1], w_out.shape[2]
+    if attn_out.shape != (M, qw) or wo.shape != (H, qw) or router.shape != (H, E) or w_in.shape != (E, 2 * I, H) or \
+            w_out.shape != (E, H, I) or norm_w.shape != (H,) or next_norm_w.shape != (H,):
+        raise ValueError("dense_moe_stages: shapes do not match")
+    nan = lambda *s: np.full(s, np.nan, np.float32)
+    out = dict(x1=nan(M, H), op1=nan(M, H), rs1=nan(M, H // 8), router_logits=nan(M, E), gate=nan(M, E), y=nan(M, H))
+    ran, form = np.zeros(14, np.int32), np.zeros(1, np.int32)
+    L.check(L.lib().nvl_op_dense_moe_stages(device, L.PRECISION[precision], _p(x), _p(attn_out), _p(wo), _p(bo), _p(norm_w), _p(router),
+                                            _p(w_in), _p(w_out), _p(next_norm_w), M, H, qw, E, int(top_k), I, residual_multiplier,
+                                            norm_eps, _p(out["x1"]), _p(out["op1"]), _p(out["rs1"]), _p(out["router_logits"]),
+                                            _p(out["gate"]), _p(out["y"]), _p(form), _p(ran)))
+    t1 = int(ran[12])
+    out["rs1"] = out["rs1"][:, :t1].copy() if t1 else None
+    proj = lambda p: dict(producer=int(ran[4 * p]), half=int(ran[4 * p + 1]), form=RESID_FORMS[int(ran[4 * p + 2])],
+                          slices=int(ran[4 * p + 3]), consumer=NORM_RAN[int(ran[9 + p])])
+    out["ran"] = dict(o=proj(0), down=proj(1), norms=int(ran[8]), rs1_tiles=t1, rs2_tiles=0)
+    out["form"] = MOE_FORMS[int(form[0])]
+    return out
+
+
 ATTN_OP_FORMS = {"plain": 0, "fused": 1, "mq": 2, "kv8": 3}                                  # NVL_ATTN_OP_*
 ATTN_RAN = {1: "f32", 2: "prefill", 3: "prefill_kv8", 4: "decode", 5: "decode_fused", 6: "decode_kv8", 7: "decode_mq",
             8: "decode_stamped"}                                                                 # NVL_ATTN_RAN_*

@@ -10,10 +10,10 @@ def test_library_exports_every_declared_symbol(pkg):
     L = pkg.lib()
     names = pkg.declared_symbols()
     assert len(names) >= 30 and "nvl_forward" in names and "nvl_runner_run" in names and "nvl_op_moe_stages" in names
-    assert "nvl_op_attention_batch" in names
+    assert "nvl_op_attention_batch" in names and "nvl_op_dense_stages" in names and "nvl_op_dense_moe_stages" in names
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing
-    assert L.nvl_abi_version() == 3                                 # (nvl_op_moe_stages / nvl_op_attention_batch are additions: the version stays)
+    assert L.nvl_abi_version() == 3                                 # (nvl_op_moe_stages / nvl_op_attention_batch / nvl_op_dense_stages are additions: the version stays)
 
 
 def test_header_cites_the_reference_for_every_entry_point(pkg):
@@ -65,6 +65,42 @@ def test_moe_stages_refuses_bad_arguments_before_touching_a_device(pkg):
     text = pkg._lib.HEADER.read_text()
     for code, name in enumerate(("DENSE_FUSED", "DENSE", "PLAN", "GROUPED"), 1):
         assert re.search(rf"NVL_MOE_FORM_{name} = {code}\b", text), name
+
+
+def test_dense_stages_refuses_bad_arguments_before_touching_a_device(pkg):
+    """nvl_op_dense_stages is bf16 only and refuses what nvl_create refuses, before the device probe (NVL_ERR_INVALID /
+    NVL_ERR_POSITION, not NVL_ERR_NO_DEVICE, on a machine without a GPU); its struct and codes match the header."""
+    import numpy as np
+    z = lambda *s: np.zeros(s, np.float32)
+
+    def call(M=2, H=256, qw=256, F=512, Nn=384, **kw):
+        return pkg.ops.dense_stages(z(M, H), z(M, qw), z(H, qw), z(H), z(2 * F, H), z(H, F), z(H), z(Nn, H), **kw)
+    for kw, code in ((dict(precision="f32"), -1), (dict(H=96), -1), (dict(F=96), -1), (dict(qw=32), -1), (dict(M=4096), -1),
+                     (dict(attention_multiplier=-1.0), -1), (dict(norm="layer"), -1), (dict(max_len=0), -1),
+                     (dict(has_next=False, last_rows=[0, 2]), -2), (dict(has_next=False, last_rows=[0], max_len=1), -1)):
+        with pytest.raises(pkg.NvlError) as e:
+            call(**kw)
+        assert e.value.code == code, (kw, e.value)
+    with pytest.raises(ValueError):
+        call(last_rows=[0])                                         # last_rows belong to the last layer
+    text = pkg._lib.HEADER.read_text()
+    assert C.sizeof(pkg._lib.DenseStagesC) == 64 + 24 * C.sizeof(C.c_void_p)
+    fields = re.search(r"typedef struct nvl_dense_stages \{(.*?)\} nvl_dense_stages;", text, re.S).group(1)
+    fields = re.sub(r"/\*.*?\*/", "", fields, flags=re.S)
+    names = [n for n in re.findall(r"[*\s,]([a-z_0-9]+)\s*[,;]", fields)]
+    assert names == [n for n, _ in pkg._lib.DenseStagesC._fields_], names
+    for table, prefix in ((pkg.ops.RESID_FORMS, "NVL_RESID_FORM_"), (pkg.ops.NORM_RAN, "NVL_NORM_RAN_")):
+        for code, name in table.items():
+            if name is not None:
+                assert re.search(rf"{prefix}{name.upper()} = {code}\b", text), name
+    assert re.search(r"NVL_DENSE_RAN_INTS = 14\b", text)
+    for kw in (dict(M=65), dict(H=96), dict(I=96), dict(k=9), dict(qw=32)):            # the MoE chain: decode rows, nvl_create's widths
+        a = dict(M=2, H=256, qw=256, E=8, k=2, I=64)
+        a.update(kw)
+        with pytest.raises(pkg.NvlError) as e:
+            pkg.ops.dense_moe_stages(z(a["M"], a["H"]), z(a["M"], a["qw"]), z(a["H"], a["qw"]), z(a["H"]), z(a["H"], a["E"]),
+                                     z(a["E"], 2 * a["I"], a["H"]), z(a["E"], a["H"], a["I"]), z(a["H"]), a["k"])
+        assert e.value.code == -1, (kw, e.value)
 
 
 def test_attention_batch_refuses_bad_arguments_before_touching_a_device(pkg):
