@@ -905,6 +905,31 @@ int nvl_op_dense_moe_stages(int device, int precision, const float* x, const flo
                             const float* next_norm_w, int rows, int hidden, int q_width, int n_experts, int top_k, int inter,
                             float residual_multiplier, float norm_eps, float* x1, float* op1, float* rs1,
                             float* router_logits, float* gate, float* y, int32_t* form, int32_t* ran);
+/* nvl_op_moe_stages / nvl_op_dense_moe_stages with the EXPERTS' storage format as a parameter (the router and the O projection
+ * stay bf16).  NVL_OP_EXPERTS_BF16 is the call above, result for result.  A quantized format builds the experts the way a
+ * model gets them: w_in as [n_experts * 2 inter][hidden] and w_out as [n_experts * hidden][inter] through the upload
+ * quantizer of the format, then nvl_finalize's own code (the gate|up interleave of codes and scales with its pad rows, the
+ * down codes and scales side by side over K = n_experts * inter, the fp8 row scales one row per expert), registered for the
+ * decode dispatch as finalize registers them, the grouped forms' W~ scratch zeroed as finalize zeroes it.  group_size: INT4
+ * only (32, 64 or 128, dividing hidden and inter; anything else is NVL_ERR_INVALID before a device is touched, as is
+ * NVL_PRECISION_F32).
+ * Two further outputs, each optional (NULL):
+ *   wt_in [n_experts][2 inter][hidden], wt_out [n_experts][hidden][inter] (quantized formats only): W~ of the experts as the
+ *     device holds them after finalize, read back through the dequantize kernels of the grouped forms and de-interleaved;
+ *   h [rows][n_experts * inter]: the dense-masked forms' intermediate bf16(silu(g) u gate) after the up projection, copied
+ *     between the two launches; NaN where no launch wrote (the columns of an expert no row picked; every column when a
+ *     sorted form ran). */
+enum { NVL_OP_EXPERTS_BF16 = 0, NVL_OP_EXPERTS_FP8 = 1, NVL_OP_EXPERTS_MXFP4 = 2, NVL_OP_EXPERTS_INT4 = 3 };
+int nvl_op_moe_stages_q(int device, int precision, const float* x, const float* router, const float* w_in,
+                        const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter,
+                        int expert_format, int group_size, float* y, float* router_logits, float* gate, int32_t* form,
+                        float* wt_in, float* wt_out, float* h);
+int nvl_op_dense_moe_stages_q(int device, int precision, const float* x, const float* attn_out, const float* wo, const float* bo,
+                              const float* norm_w, const float* router, const float* w_in, const float* w_out,
+                              const float* next_norm_w, int rows, int hidden, int q_width, int n_experts, int top_k, int inter,
+                              float residual_multiplier, float norm_eps, int expert_format, int group_size, float* x1,
+                              float* op1, float* rs1, float* router_logits, float* gate, float* y, int32_t* form, int32_t* ran,
+                              float* wt_in, float* wt_out, float* h);
 /* argmax cmd/ask/main.go:389-402 (first strict maximum) */
 int nvl_op_argmax(int device, const float* x, int rows, int cols, int32_t* out);
 

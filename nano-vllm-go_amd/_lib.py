@@ -230,6 +230,8 @@ def lib():
     L.nvl_op_dense_stages.argtypes = [C.c_int, C.c_int, C.POINTER(DenseStagesC)]
     L.nvl_op_dense_moe_stages.argtypes = [C.c_int, C.c_int] + [vp] * 9 + [C.c_int] * 6 + [f32, f32] + [vp] * 8
     L.nvl_op_moe_stages.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp] + [C.c_int] * 5 + [vp] * 4
+    L.nvl_op_dense_moe_stages_q.argtypes = [C.c_int, C.c_int] + [vp] * 9 + [C.c_int] * 6 + [f32, f32] + [C.c_int] * 2 + [vp] * 11
+    L.nvl_op_moe_stages_q.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp] + [C.c_int] * 7 + [vp] * 7
     L.nvl_op_attention_batch.argtypes = ([C.c_int] * 6 + [f32, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_double,
                                           C.c_int, f32, f32, vp, vp, vp])
     L.nvl_op_mamba_mixer.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp] + [C.c_int] * 6 + [vp] * 8 + [C.c_int] + [vp] * 4

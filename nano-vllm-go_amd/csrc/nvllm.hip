@@ -935,6 +935,65 @@ void fuse_w1(nvl_model* m, LayerW& l, bool swiglu) {
     }
 }
 
+// does finalize build the decode (dense-masked) form of a MoE layer's down matrices?  (nvl_finalize; ops_impl.h moe_op_setup)
+inline bool moe_dense_form(int64_t H, int64_t E, int64_t I) {
+    return I % 32 == 0 && H % 16 == 0 && E <= 64 && E / moe_down_slices((int)E) <= 16;
+}
+
+// The quantized experts of one MoE layer from their uploaded tensors (l.t[NVL_T_MOE_IN] [E*2I][H], l.t[NVL_T_MOE_OUT]
+// [E*H][I]: codes + scales of the upload quantizer), as nvl_finalize leaves them — and as ops_impl.h moe_op_setup builds
+// them, through this one function.  idx: the SwiGLU interleave of all experts' gate|up rows.  Frees the uploaded tensors.
+void finalize_q_experts(nvl_model* m, LayerW& l, std::vector<int32_t>& idx, int64_t E, int64_t I, bool dense_form) {
+    const int64_t H = m->H;
+    const int wf = l.t[NVL_T_MOE_IN].wf;
+    const int64_t np = round_up(E * 2 * I, W_ROW_PAD), hp = round_up(H, W_ROW_PAD);
+    idx.resize((size_t)np, -1);
+    l.moe_in = dmalloc_bytes(wf_code_bytes(wf, np * H));
+    l.qs_moe_in = dmalloc_bytes(wf_scale_bytes(wf, np, H));
+    gather_rows_q(m, l.t[NVL_T_MOE_IN], idx, l.moe_in, l.qs_moe_in, H);
+    // down: codes over K = E*I, [H_pad][E*I] (the decode form's layout; the tile path dequantizes from it)
+    const DevTensor& d = l.t[NVL_T_MOE_OUT];
+    l.moe_out_q = dmalloc_bytes(wf_code_bytes(wf, hp * E * I));
+    NVL_HIP(hipMemsetAsync(l.moe_out_q, 0, (size_t)wf_code_bytes(wf, hp * E * I), m->stream));
+    if (wf == WF_MXFP4) {     // block scales over the same K, moved with the code tiles
+        l.qs_moe_out = q_alloc_scales(m, wf, hp, E * I);
+        hipLaunchKernelGGL(moe_cat_down_w4_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream, (const uint8_t*)d.p,
+                           (const uint8_t*)d.qs, (uint8_t*)l.moe_out_q, (uint8_t*)l.qs_moe_out, (int)H, (int)I, (int)E);
+    } else if (wf_base(wf) == WF_INT4) {     // group words over the same K (pad rows: {s = 1, z = 0}), moved with the code tiles
+        l.qs_moe_out = q_alloc_scales(m, wf, hp, E * I);
+        hipLaunchKernelGGL(moe_cat_down_w4g_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream, (const uint8_t*)d.p,
+                           (const uint32_t*)d.qs, (uint8_t*)l.moe_out_q, (uint32_t*)l.qs_moe_out, (int)H, (int)I, (int)E, wf_gshift(wf));
+    } else {                // row scales [E][H_pad]: one row per expert, through the host
+        l.qs_moe_out = q_alloc_scales(m, wf, E * hp, I);
+        hipLaunchKernelGGL(moe_cat_down_w8_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream,
+                           (const uint8_t*)d.p, (uint8_t*)l.moe_out_q, (int)H, (int)I, (int)E);
+        std::vector<float> sd((size_t)d.rows_pad);
+        NVL_HIP(hipMemcpy(sd.data(), d.qs, sd.size() * 4, hipMemcpyDeviceToHost));
+        for (int64_t e = 0; e < E; e++)
+            NVL_HIP(hipMemcpy((float*)l.qs_moe_out + e * hp, &sd[(size_t)(e * H)], (size_t)H * 4, hipMemcpyHostToDevice));
+    }
+    NVL_HIP(hipGetLastError());
+    NVL_HIP(hipStreamSynchronize(m->stream));
+    if (dense_form) l.moe_out_cat = l.moe_out_q;
+    for (int k : {NVL_T_MOE_IN, NVL_T_MOE_OUT}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].qs); l.t[k].qs = nullptr; }
+}
+
+// quantized experts after finalize_q_experts: the codes by pointer (decode dispatch), and the scratch of one layer's W~ (up,
+// then down) for the grouped GEMMs, zeroed
+void register_q_experts(nvl_model* m, const LayerW* layers, size_t n_layers, int64_t E, int64_t I) {
+    const int64_t H = m->H, hp = round_up(H, W_ROW_PAD);
+    for (size_t i = 0; i < n_layers; i++) {
+        const LayerW& l = layers[i];
+        if (!l.qs_moe_in) continue;
+        m->qmap[l.moe_in] = nvl_model::QRef{m->ef, l.qs_moe_in, round_up(E * 2 * I, W_ROW_PAD)};
+        if (l.moe_out_cat) m->qmap[l.moe_out_cat] = nvl_model::QRef{m->ef, l.qs_moe_out, hp};
+    }
+    // (down: the grouped GEMMs read whole 256-row tiles of the last expert past its H rows)
+    m->eq_scratch_elems = std::max(round_up(E * 2 * I, W_ROW_PAD) * H, (E * H + 2 * W_ROW_PAD) * I);
+    m->eq_scratch = dmalloc<bf16_t>(m->eq_scratch_elems);
+    NVL_HIP(hipMemsetAsync(m->eq_scratch, 0, (size_t)m->eq_scratch_elems * 2, m->stream));
+}
+
 }  // namespace
 
 extern "C" int nvl_set_kv_scales(nvl_model* m, const float* k_scale, const float* v_scale) {
@@ -1160,39 +1219,9 @@ extern "C" int nvl_finalize(nvl_model* m) {
                     auto one = swiglu_interleave(I, e * 2 * I);
                     idx.insert(idx.end(), one.begin(), one.end());
                 }
-                const bool dense_form = I % 32 == 0 && H % 16 == 0 && E <= 64 && E / moe_down_slices((int)E) <= 16;
+                const bool dense_form = moe_dense_form(H, E, I);
                 if (l.t[NVL_T_MOE_IN].qs) {     // quantized experts: codes + scales follow the interleave
-                    const int wf = l.t[NVL_T_MOE_IN].wf;
-                    const int64_t np = round_up(E * 2 * I, W_ROW_PAD), hp = round_up(H, W_ROW_PAD);
-                    idx.resize((size_t)np, -1);
-                    l.moe_in = dmalloc_bytes(wf_code_bytes(wf, np * H));
-                    l.qs_moe_in = dmalloc_bytes(wf_scale_bytes(wf, np, H));
-                    gather_rows_q(m, l.t[NVL_T_MOE_IN], idx, l.moe_in, l.qs_moe_in, H);
-                    // down: codes over K = E*I, [H_pad][E*I] (the decode form's layout; the tile path dequantizes from it)
-                    const DevTensor& d = l.t[NVL_T_MOE_OUT];
-                    l.moe_out_q = dmalloc_bytes(wf_code_bytes(wf, hp * E * I));
-                    NVL_HIP(hipMemsetAsync(l.moe_out_q, 0, (size_t)wf_code_bytes(wf, hp * E * I), m->stream));
-                    if (wf == WF_MXFP4) {     // block scales over the same K, moved with the code tiles
-                        l.qs_moe_out = q_alloc_scales(m, wf, hp, E * I);
-                        hipLaunchKernelGGL(moe_cat_down_w4_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream, (const uint8_t*)d.p,
-                                           (const uint8_t*)d.qs, (uint8_t*)l.moe_out_q, (uint8_t*)l.qs_moe_out, (int)H, (int)I, (int)E);
-                    } else if (wf_base(wf) == WF_INT4) {     // group words over the same K (pad rows: {s = 1, z = 0}), moved with the code tiles
-                        l.qs_moe_out = q_alloc_scales(m, wf, hp, E * I);
-                        hipLaunchKernelGGL(moe_cat_down_w4g_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream, (const uint8_t*)d.p,
-                                           (const uint32_t*)d.qs, (uint8_t*)l.moe_out_q, (uint32_t*)l.qs_moe_out, (int)H, (int)I, (int)E, wf_gshift(wf));
-                    } else {                // row scales [E][H_pad]: one row per expert, through the host
-                        l.qs_moe_out = q_alloc_scales(m, wf, E * hp, I);
-                        hipLaunchKernelGGL(moe_cat_down_w8_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream,
-                                           (const uint8_t*)d.p, (uint8_t*)l.moe_out_q, (int)H, (int)I, (int)E);
-                        std::vector<float> sd((size_t)d.rows_pad);
-                        NVL_HIP(hipMemcpy(sd.data(), d.qs, sd.size() * 4, hipMemcpyDeviceToHost));
-                        for (int64_t e = 0; e < E; e++)
-                            NVL_HIP(hipMemcpy((float*)l.qs_moe_out + e * hp, &sd[(size_t)(e * H)], (size_t)H * 4, hipMemcpyHostToDevice));
-                    }
-                    NVL_HIP(hipGetLastError());
-                    NVL_HIP(hipStreamSynchronize(m->stream));
-                    if (dense_form) l.moe_out_cat = l.moe_out_q;
-                    for (int k : {NVL_T_MOE_IN, NVL_T_MOE_OUT}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].qs); l.t[k].qs = nullptr; }
+                    finalize_q_experts(m, l, idx, E, I, dense_form);
                     continue;
                 }
                 l.moe_in = dmalloc_bytes(round_up(E * 2 * I, W_ROW_PAD) * H * (int64_t)m->wsize);   // (+ zero pad rows: the decode kernels read whole tiles)
@@ -1239,18 +1268,8 @@ extern "C" int nvl_finalize(nvl_model* m) {
         }
         m->wq_scratch_elems = big;
         if (big) m->wq_scratch = dmalloc<bf16_t>(big);
-        if (m->ef != WF_BF16) {   // quantized experts: the codes by pointer (decode dispatch), and the scratch of one layer's W~ (up, then down)
-            const int64_t E = c.num_experts, I = m->F, hp = round_up(H, W_ROW_PAD);
-            for (auto& l : m->layers) {
-                if (!l.qs_moe_in) continue;
-                m->qmap[l.moe_in] = nvl_model::QRef{m->ef, l.qs_moe_in, round_up(E * 2 * I, W_ROW_PAD)};
-                if (l.moe_out_cat) m->qmap[l.moe_out_cat] = nvl_model::QRef{m->ef, l.qs_moe_out, hp};
-            }
-            // (down: the grouped GEMMs read whole 256-row tiles of the last expert past its H rows)
-            m->eq_scratch_elems = std::max(round_up(E * 2 * I, W_ROW_PAD) * H, (E * H + 2 * W_ROW_PAD) * I);
-            m->eq_scratch = dmalloc<bf16_t>(m->eq_scratch_elems);
-            NVL_HIP(hipMemsetAsync(m->eq_scratch, 0, (size_t)m->eq_scratch_elems * 2, m->stream));
-        }
+        // quantized experts: the codes by pointer (decode dispatch), and the scratch of one layer's W~ (up, then down)
+        if (m->ef != WF_BF16) register_q_experts(m, m->layers.data(), m->layers.size(), c.num_experts, m->F);
         if (m->a8) {   // the activation codes + row scales of the W8A8 tile step: every row of a batch, the widest K
             int64_t kmax = H;
             for (auto& l : m->layers) {
@@ -2003,6 +2022,10 @@ void ffn_up(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false) {
 // the (token, rank) pairs by expert -> ONE grouped gate/up GEMM and ONE grouped down GEMM over all experts
 // (m-tiles mapped to (expert, row segment) by a device table; token rows gathered by per-lane source address)
 // -> combine in rank order into x (with the residual multiplier).  The fp32 parity mode launches per expert.
+// the op entry points look at the buffers between the launches of layer_tail and of moe (a model passes no hook)
+enum { TAIL_X1 = 0, TAIL_OPERAND, TAIL_H, TAIL_X2 };     // after the O projection | FFN-up's operand in place | after FFN-up | after FFN-down
+struct StageHook { void (*fn)(void* ctx, int stage); void* ctx; };
+
 // can this call take the decode ("dense-masked") MoE form?  (also decides whether the O projection may carry the FFN norm)
 // (the down form's per-wave live-block mask is 32 bits wide: an expert of more than 32 blocks of U k-steps — U = 4 up to 32
 // rows, 2 above — would lose the blocks past 32, so such widths take the grouped form: I > 4096, or I > 2048 above 32 rows)
@@ -2013,12 +2036,28 @@ bool moe_dense_ok(const nvl_model* m, const LayerW& l, int M) {
     return !m->f32 && M <= 64 && g_moe_dense && l.moe_out_cat && m->moe_part && !m->keep_hidden && m->H % 4 == 0 &&
            m->H <= 1024 * NORM_ROW_MAXCH && g_force_tile == 0 && (m->F >> 5) / u_down <= 32;
 }
+// quantized experts, the grouped forms: W~ of the layer's down matrices from the stored [H_pad][E*I] codes into dst, [E][H][I]
+// fragment-major per expert (ops_impl.h reads the experts back through it too)
+void dequant_down_experts(nvl_model* m, const LayerW& l, int H, int I, int E, bf16_t* dst) {
+    const int64_t n8 = (int64_t)E * H * I / 8;
+    if (m->ef == WF_MXFP4)
+        hipLaunchKernelGGL(e4_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
+                           (const uint8_t*)l.qs_moe_out, H, I, E, n8, dst);
+    else if (wf_base(m->ef) == WF_INT4)
+        hipLaunchKernelGGL(e4g_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
+                           (const uint32_t*)l.qs_moe_out, H, I, E, wf_gshift(m->ef), n8, dst);
+    else
+        hipLaunchKernelGGL(e8_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
+                           (const float*)l.qs_moe_out, H, I, E, round_up(H, W_ROW_PAD), n8, dst);
+    NVL_HIP(hipGetLastError());
+}
 // deferred_norm: m->xn holds xn_raw = bf16(x * w_norm) and m->rs_part the x^2 partials (the O projection carried the FFN
 // norm): the router and the expert-up projection scale their accumulators by rstd[m] instead of reading a normed operand
 // next_norm_w (decode, dense-masked form only): the down projection carries the NEXT norm (the following layer's attention
 // norm / the final norm) as the deferred-RMSNorm producer — all of K in one workgroup per (weight half-tile, row tile), no
 // slices left for a norm launch to sum; returns true when it did (m->xn / m->rs_part then hold that norm's operand).
-bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const float* next_norm_w = nullptr) {
+// hook (the op entry points only): called with TAIL_H between the dense-masked form's two projections, moe_hall written
+bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const float* next_norm_w = nullptr, const StageHook* hook = nullptr) {
     const nvl_model_config& c = m->cfg;
     const int E = c.num_experts, k = c.num_experts_per_tok, I = m->F, H = m->H;
     const int pairs = M * k;
@@ -2059,6 +2098,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
         if (deferred_norm) set_deferred_in(m, a);
         m->site = KS_MOE_UP; m->site_bytes = e_touch * 2 * I * H * eb + ((double)M * H + e_touch * M * I) * (double)m->wsize;
         gemm(m, EPI_SWIGLU, false, a, 2.0 * pairs * 2 * I * H);
+        if (hook) hook->fn(hook->ctx, TAIL_H);
         const int nks = (E * I) >> 5, spe = I >> 5;
         // (8-bit experts: no producer form — a wave's live blocks cross experts, the scale would change with the block;
         //  MXFP4 and INT4 experts: no instance of it either — key 33 is off by default and was measured slower)
@@ -2160,17 +2200,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
         gemm(m, EPI_SWIGLU, false, a, 2.0 * pairs * 2 * I * H);
         if (m->ef != WF_BF16) {
             KScope ks(m, KC_OTHER, 0, KS_MOE_DOWN, (double)E * H * I * dq_bytes);
-            const int64_t n8 = (int64_t)E * H * I / 8;
-            if (m->ef == WF_MXFP4)
-                hipLaunchKernelGGL(e4_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
-                                   (const uint8_t*)l.qs_moe_out, H, I, E, n8, m->eq_scratch);
-            else if (wf_base(m->ef) == WF_INT4)
-                hipLaunchKernelGGL(e4g_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
-                                   (const uint32_t*)l.qs_moe_out, H, I, E, wf_gshift(m->ef), n8, m->eq_scratch);
-            else
-                hipLaunchKernelGGL(e8_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
-                                   (const float*)l.qs_moe_out, H, I, E, round_up(H, W_ROW_PAD), n8, m->eq_scratch);
-            NVL_HIP(hipGetLastError());
+            dequant_down_experts(m, l, H, I, E, m->eq_scratch);
             w_down = m->eq_scratch;
         }
         GemmArgs d = mk(m->hbuf, I, w_down, m->moe_eo, H, nullptr, 1.f, max_mtiles, H, I);
@@ -2268,10 +2298,6 @@ TailPlan tail_plan(const nvl_model* m, int M, int n_seqs, int max_len, uint32_t 
     return t;
 }
 
-// nvl_op_dense_stages looks at the buffers between the launches of layer_tail (a model passes none)
-enum { TAIL_X1 = 0, TAIL_OPERAND, TAIL_H, TAIL_X2 };     // after the O projection | FFN-up's operand in place | after FFN-up | after FFN-down
-struct StageHook { void (*fn)(void* ctx, int stage); void* ctx; };
-
 // One attention layer from its O projection to the end: both residual projections, the FFN (or MoE) between them, the
 // norms they do not carry.  Returns whether m->xn / m->rs_part hold the deferred operand of the norm (nxt_w, nxt_b) that
 // follows the layer (has_next: a layer's attention norm; else the final norm).
@@ -2314,7 +2340,7 @@ bool layer_tail(nvl_model* m, const LayerW& l, int li, int M, const TailPlan& tp
         if (c.use_moe) {
             const bool defer2 = defer && defer_moe_ok && g_defer_norm != 3 && !nxt_b->present() &&
                                 (has_next || (!all_rows && M == n_seqs && M <= 64));
-            xn_deferred = moe(m, l, M, defer, defer2 ? (const float*)nxt_w->p : nullptr);
+            xn_deferred = moe(m, l, M, defer, defer2 ? (const float*)nxt_w->p : nullptr, hook);
         } else {
             ffn_up(m, l, M, defer);
             at(TAIL_H);

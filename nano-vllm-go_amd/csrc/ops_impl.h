@@ -809,19 +809,25 @@ namespace {
 // the decode scratch and the sorted forms' workspaces of nvl_create, every buffer a form owns 0xFF bytes.  Sets m.H, m.F and
 // the expert counts; keep_hidden off, so moe_dense_ok() answers as in a model.  router [H][E], w_in [E][2 inter][H],
 // w_out [E][H][inter].
-void moe_op_setup(OpCtx& cx, LayerW& l, const float* router, const float* w_in, const float* w_out, int rows, int H, int E, int k, int inter) {
+// wf: the experts' format (a host format id of wq.h; the router stays bf16).  A quantized format goes the way of a model:
+// both tensors through the upload quantizer, then finalize_q_experts() and register_q_experts() — nvl_finalize's own code —,
+// so the codes and scales lie where finalize lays them, moe_out_cat = moe_out_q under finalize's predicate, and eq_scratch
+// (the grouped forms' W~) starts zeroed as finalize zeroes it.
+void moe_op_setup(OpCtx& cx, LayerW& l, const float* router, const float* w_in, const float* w_out, int rows, int H, int E, int k, int inter,
+                  int wf = WF_BF16) {
     nvl_model& m = cx.m;
     const int64_t pairs = (int64_t)rows * k, hp = round_up(H, W_ROW_PAD);
     auto nan_fill = [&](int64_t bytes) { void* p = cx.alloc(bytes); NVL_HIP(hipMemsetAsync(p, 0xFF, (size_t)bytes, m.stream)); return p; };
     m.H = H; m.F = inter;
     m.cfg.num_experts = E; m.cfg.num_experts_per_tok = k; m.cfg.use_moe = 1;
     m.keep_hidden = false;
+    m.ef = wf;
     // the decode form's scratch (nvl_create) and weight (finalize, under its dense_form predicate)
     m.moe_gate = (float*)nan_fill(64 * (int64_t)E * 4);
     m.moe_hall = nan_fill(64 * (int64_t)E * inter * 2);
     m.moe_part = (float*)nan_fill((int64_t)MOE_DOWN_SLICES * 64 * H * 4);
-    const bool dense_form = inter % 32 == 0 && H % 16 == 0 && E <= 64 && E / moe_down_slices(E) <= 16;
-    if (dense_form) l.moe_out_cat = cx.alloc(hp * E * inter * 2);
+    const bool dense_form = moe_dense_form(H, E, inter);
+    if (dense_form) l.moe_out_cat = wf == WF_BF16 ? cx.alloc(hp * E * inter * 2) : (void*)m.moe_part;   // (quantized: a stand-in for the question below)
     // The grouped GEMMs of the sorted forms stream K in 64-wide tiles (nvl_create refuses ffn_dim % 64 != 0), the decode
     // kernels in 32-wide k-steps: a call that will not take the dense form on inter % 64 == 32 runs on experts padded
     // with 32 zero columns — h = silu(0) * 0 = 0 there, times a zero weight: every sum gains exact zeros.
@@ -840,21 +846,39 @@ void moe_op_setup(OpCtx& cx, LayerW& l, const float* router, const float* w_in, 
         }
     }
     l.t[NVL_T_ROUTER].p = cx.up_mat(router, E, H, true, W_ROW_PAD);
-    void* inc = cx.up_mat(I != inter ? pin.data() : w_in, (int64_t)E * 2 * I, H, false, W_ROW_PAD);
     std::vector<int32_t> idx;
     for (int e = 0; e < E; e++) {
         auto one = swiglu_interleave(I, (int64_t)e * 2 * I);
         idx.insert(idx.end(), one.begin(), one.end());
     }
-    idx.resize((size_t)round_up((int64_t)E * 2 * I, W_ROW_PAD), -1);      // (+ zero pad rows: the decode kernels read whole tiles)
-    l.moe_in = cx.alloc((int64_t)idx.size() * H * 2);
-    gather_rows(&m, inc, idx, l.moe_in, H);
-    l.t[NVL_T_MOE_OUT].p = cx.up_mat(pout.data(), (int64_t)E * H + 128, I, false, W_ROW_PAD);
-    if (l.moe_out_cat) {
-        NVL_HIP(hipMemsetAsync(l.moe_out_cat, 0, (size_t)(hp * E * I) * 2, m.stream));
-        hipLaunchKernelGGL(moe_cat_down_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m.stream,
-                           (const bf16_t*)l.t[NVL_T_MOE_OUT].p, (bf16_t*)l.moe_out_cat, H, I, E);
-        NVL_HIP(hipGetLastError());
+    if (wf != WF_BF16) {
+        l.moe_out_cat = nullptr;
+        DevTensor &tin = l.t[NVL_T_MOE_IN], &tout = l.t[NVL_T_MOE_OUT];
+        try {     // (rows = (expert, output row), as nvl_upload_tensor passes MOE_IN / MOE_OUT)
+            upload_2d_q(&m, &tin, wf, I != inter ? pin.data() : w_in, NVL_DTYPE_F32, (int64_t)E * 2 * I, H, false);
+            upload_2d_q(&m, &tout, wf, pout.data(), NVL_DTYPE_F32, (int64_t)E * H, I, false);
+            finalize_q_experts(&m, l, idx, E, I, dense_form && I == inter);
+        } catch (...) {
+            for (DevTensor* t : {&tin, &tout}) { dfree(t->p); dfree(t->qs); t->p = t->qs = nullptr; }
+            for (void* p : {l.moe_in, l.qs_moe_in, l.moe_out_q, l.qs_moe_out}) dfree(p);
+            l.moe_in = l.qs_moe_in = l.moe_out_q = l.qs_moe_out = l.moe_out_cat = nullptr;
+            throw;
+        }
+        for (void* p : {l.moe_in, l.qs_moe_in, l.moe_out_q, l.qs_moe_out}) cx.bufs.push_back(p);
+        register_q_experts(&m, &l, 1, E, I);
+        cx.bufs.push_back(m.eq_scratch);
+    } else {
+        void* inc = cx.up_mat(I != inter ? pin.data() : w_in, (int64_t)E * 2 * I, H, false, W_ROW_PAD);
+        idx.resize((size_t)round_up((int64_t)E * 2 * I, W_ROW_PAD), -1);      // (+ zero pad rows: the decode kernels read whole tiles)
+        l.moe_in = cx.alloc((int64_t)idx.size() * H * 2);
+        gather_rows(&m, inc, idx, l.moe_in, H);
+        l.t[NVL_T_MOE_OUT].p = cx.up_mat(pout.data(), (int64_t)E * H + 128, I, false, W_ROW_PAD);
+        if (l.moe_out_cat) {
+            NVL_HIP(hipMemsetAsync(l.moe_out_cat, 0, (size_t)(hp * E * I) * 2, m.stream));
+            hipLaunchKernelGGL(moe_cat_down_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m.stream,
+                               (const bf16_t*)l.t[NVL_T_MOE_OUT].p, (bf16_t*)l.moe_out_cat, H, I, E);
+            NVL_HIP(hipGetLastError());
+        }
     }
     // the sorted forms' workspaces (nvl_create)
     m.router_logits = (float*)nan_fill((int64_t)rows * 128 * 4);
@@ -890,8 +914,78 @@ bool moe_op_results(OpCtx& cx, int rows, int E, int k, float* router_logits, flo
     }
     return true;
 }
+// the experts' format of the *_q entry points -> the host format id (wq.h); -1: what the format's setter would refuse
+int moe_op_wf(int expert_format, int group_size, int H, int inter) {
+    switch (expert_format) {
+        case NVL_OP_EXPERTS_BF16: return WF_BF16;
+        case NVL_OP_EXPERTS_FP8: return WF_FP8;
+        case NVL_OP_EXPERTS_MXFP4: return WF_MXFP4;
+        case NVL_OP_EXPERTS_INT4:
+            if ((group_size != 32 && group_size != 64 && group_size != 128) || H % group_size || inter % group_size) return -1;
+            return wf_int4(group_size);
+        default: return -1;
+    }
+}
+// moe()'s hook: moe_hall between the two projections of the dense-masked form (the sorted forms never call it)
+struct MoeHTap {
+    nvl_model* m; void* h; int64_t bytes;
+    static void call(void* ctx, int which) {
+        MoeHTap* t = (MoeHTap*)ctx;
+        if (which == TAIL_H && t->h) NVL_HIP(hipMemcpyAsync(t->h, t->m->moe_hall, (size_t)t->bytes, hipMemcpyDeviceToDevice, t->m->stream));
+    }
+};
+inline float bf16_bits_f32(uint16_t b) { const uint32_t u = ((uint32_t)b) << 16; float f; memcpy(&f, &u, 4); return f; }
+// the copy of moe_hall (fragment-major [64][E * inter]) -> h [rows][E * inter]; what no launch wrote is NaN
+void moe_op_h(OpCtx& cx, const void* hcopy, int rows, int E, int inter, float* h) {
+    const int64_t K = (int64_t)E * inter;
+    if (cx.m.moe_form != NVL_MOE_FORM_DENSE_FUSED && cx.m.moe_form != NVL_MOE_FORM_DENSE) {      // a sorted form: moe_hall was not touched (and rows may exceed its 64)
+        std::fill(h, h + (size_t)rows * K, std::numeric_limits<float>::quiet_NaN());
+        return;
+    }
+    std::vector<uint16_t> hb((size_t)(64 * K));
+    NVL_HIP(hipMemcpyAsync(hb.data(), hcopy, hb.size() * 2, hipMemcpyDeviceToHost, cx.m.stream));
+    NVL_HIP(hipStreamSynchronize(cx.m.stream));
+    for (int64_t r = 0; r < rows; r++)
+        for (int64_t c = 0; c < K; c++) h[(size_t)(r * K + c)] = bf16_bits_f32(hb[(size_t)fm_index(r, c, K)]);
+}
+// W~ of the quantized experts as the device holds them after finalize, read through the grouped forms' own dequantize
+// launches (wf_dequant_rows on moe_in / qs_moe_in, dequant_down_experts on moe_out_q / qs_moe_out) into buffers of their
+// own and de-interleaved on the host: wt_in [E][2 inter][H] (gate rows, then up rows), wt_out [E][H][inter]
+void moe_op_wt(OpCtx& cx, const LayerW& l, int H, int E, int inter, float* wt_in, float* wt_out) {
+    nvl_model& m = cx.m;
+    const int64_t I = m.F, np = round_up((int64_t)E * 2 * I, W_ROW_PAD);      // (I: inter, or inter + 32 zero columns)
+    if (wt_in) {
+        bf16_t* d = (bf16_t*)cx.alloc(np * H * 2);
+        wf_dequant_rows(m.stream, m.ef, l.moe_in, l.qs_moe_in, H, 0, np, d);
+        NVL_HIP(hipGetLastError());
+        std::vector<uint16_t> hb((size_t)(np * H));
+        NVL_HIP(hipMemcpyAsync(hb.data(), d, hb.size() * 2, hipMemcpyDeviceToHost, m.stream));
+        NVL_HIP(hipStreamSynchronize(m.stream));
+        for (int64_t e = 0; e < E; e++) {
+            const auto idx = swiglu_interleave(I, 0);      // device row e * 2I + j holds the expert's canonical row idx[j]
+            for (int64_t j = 0; j < 2 * I; j++) {
+                const int64_t half = idx[(size_t)j] / I, rr = idx[(size_t)j] % I;
+                if (rr >= inter) continue;
+                float* dst = wt_in + (size_t)((e * 2 * inter + half * inter + rr) * H);
+                for (int64_t c = 0; c < H; c++) dst[c] = bf16_bits_f32(hb[(size_t)fm_index(e * 2 * I + j, c, H)]);
+            }
+        }
+    }
+    if (wt_out) {
+        bf16_t* d = (bf16_t*)cx.alloc((int64_t)E * H * I * 2);
+        dequant_down_experts(&m, l, H, (int)I, E, d);
+        std::vector<uint16_t> hb((size_t)((int64_t)E * H * I));
+        NVL_HIP(hipMemcpyAsync(hb.data(), d, hb.size() * 2, hipMemcpyDeviceToHost, m.stream));
+        NVL_HIP(hipStreamSynchronize(m.stream));
+        for (int64_t e = 0; e < E; e++)
+            for (int64_t r = 0; r < H; r++)
+                for (int64_t c = 0; c < inter; c++)
+                    wt_out[(size_t)((e * H + r) * inter + c)] = bf16_bits_f32(hb[(size_t)(e * H * I + fm_index(r, c, I))]);
+    }
+}
 void moe_op_release(OpCtx& cx, LayerW& l) {      // (the buffers are the OpCtx's)
     nvl_model& m = cx.m;
+    l.qs_moe_in = nullptr; l.moe_out_q = nullptr; l.qs_moe_out = nullptr; m.eq_scratch = nullptr; m.eq_scratch_elems = 0; m.qmap.clear();
     l.moe_in = nullptr; l.moe_out_cat = nullptr; l.t[NVL_T_ROUTER].p = nullptr; l.t[NVL_T_MOE_OUT].p = nullptr;
     m.hbuf = nullptr; m.router_logits = nullptr; m.expert_ids = nullptr;
     m.expert_w = nullptr; m.seg_start = m.perm_token = m.slot_of = nullptr; m.moe_eo = nullptr; m.moe_xg = nullptr;
@@ -905,24 +999,34 @@ void moe_op_release(OpCtx& cx, LayerW& l) {      // (the buffers are the OpCtx's
 // workspace allocation, keep_hidden off — so moe_dense_ok() answers as it does in a model —, then whatever moe() left for
 // the next norm completed by tap_hidden_kernel, as tap_layer does.  Every scratch buffer a form owns starts as 0xFF bytes
 // (NaN in bf16 and in fp32): the columns of an expert nobody picked, an unwritten K slice or a stale row show in y.
-extern "C" int nvl_op_moe_stages(int device, int precision, const float* x, const float* router, const float* w_in,
-                                 const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter, float* y,
-                                 float* router_logits, float* gate, int32_t* form) {
+//
+// nvl_op_moe_stages_q: the same with the experts in a quantized format — built as nvl_finalize builds them (moe_op_setup) —,
+// W~ read back (moe_op_wt) and moe_hall copied between the dense-masked form's two projections (MoeHTap).
+extern "C" int nvl_op_moe_stages_q(int device, int precision, const float* x, const float* router, const float* w_in,
+                                   const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter,
+                                   int expert_format, int group_size, float* y, float* router_logits, float* gate, int32_t* form,
+                                   float* wt_in, float* wt_out, float* h) {
     if (!x || !router || !w_in || !w_out || !y || !router_logits || !gate || !form || precision != NVL_PRECISION_BF16 || rows <= 0 ||
         rows > (1 << 16) || hidden <= 0 || hidden % 64 || inter <= 0 || inter % 32 || n_experts < 1 || n_experts > 64 || top_k < 1 ||
         top_k > n_experts)
         return op_fail("nvl_op_moe_stages: bad arguments (bf16 only; hidden % 64, inter % 32, top_k <= n_experts <= 64)");
+    const int wf = moe_op_wf(expert_format, group_size, hidden, inter);
+    if (wf < 0) return op_fail("nvl_op_moe_stages_q: unknown expert format, or INT4 experts whose group size is not 32, 64 or 128 or does not divide hidden and inter");
+    if (wf == WF_BF16 && (wt_in || wt_out)) return op_fail("nvl_op_moe_stages_q: wt_in / wt_out are the read-back of quantized experts");
     OP_TRY
     OpCtx cx(device, precision);
     nvl_model& m = cx.m;
     const int E = n_experts, H = hidden, k = top_k;
     m.cfg.residual_multiplier = 0.f; m.resid_alpha = 1.f;      // multiplier 1 both ways (nvl_create's reading of 0)
     LayerW l;
-    moe_op_setup(cx, l, router, w_in, w_out, rows, H, E, k, inter);
+    moe_op_setup(cx, l, router, w_in, w_out, rows, H, E, k, inter, wf);
     m.xn = cx.up_mat(x, rows, H, false);
     m.x = (float*)cx.alloc((int64_t)rows * H * 4);
     NVL_HIP(hipMemsetAsync(m.x, 0, (size_t)rows * H * 4, m.stream));
-    moe(&m, l, rows);
+    MoeHTap tap{&m, nullptr, 64 * (int64_t)E * inter * 2};
+    if (h) { tap.h = cx.alloc(tap.bytes); NVL_HIP(hipMemsetAsync(tap.h, 0xFF, (size_t)tap.bytes, m.stream)); }
+    const StageHook hook{&MoeHTap::call, &tap};
+    moe(&m, l, rows, false, nullptr, h ? &hook : nullptr);
     *form = m.moe_form;
     float* yd = (float*)cx.alloc((int64_t)rows * H * 4);
     if (m.pending_slices == 0) {
@@ -934,11 +1038,19 @@ extern "C" int nvl_op_moe_stages(int device, int precision, const float* x, cons
     }
     cx.down(y, yd, (int64_t)rows * H);
     if (!moe_op_results(cx, rows, E, k, router_logits, gate)) return op_fail("nvl_op_moe_stages: the routing chose an expert out of range", NVL_ERR_STATE);
+    if (h) moe_op_h(cx, tap.h, rows, E, inter, h);
+    if (wf != WF_BF16) moe_op_wt(cx, l, H, E, inter, wt_in, wt_out);
     moe_op_release(cx, l);
     m.xn = nullptr; m.x = nullptr;
     m.pending_part = nullptr; m.pending_slices = 0; m.pending_slot_of = nullptr; m.pending_gate_w = nullptr;
     return NVL_OK;
     OP_CATCH
+}
+extern "C" int nvl_op_moe_stages(int device, int precision, const float* x, const float* router, const float* w_in,
+                                 const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter, float* y,
+                                 float* router_logits, float* gate, int32_t* form) {
+    return nvl_op_moe_stages_q(device, precision, x, router, w_in, w_out, rows, hidden, n_experts, top_k, inter, NVL_OP_EXPERTS_BF16, 0,
+                               y, router_logits, gate, form, nullptr, nullptr, nullptr);
 }
 
 // The dense layer tail as a layer of the model runs it — layer_tail() itself, under tail_plan()'s decisions — on host inputs,
@@ -951,6 +1063,7 @@ namespace {
 struct DenseTap {
     nvl_model* m; int M;
     float *x1, *x2, *rs1; void *op1, *h; int rs1_tiles = 0; int64_t op_bytes, h_bytes, rs_bytes;
+    const void* h_src = nullptr;      // (the MoE chain: moe_hall, where moe() raises TAIL_H; else hbuf)
     void take_x(float* dst) {
         if (m->pending_slices == 0) { NVL_HIP(hipMemcpyAsync(dst, m->x, (size_t)M * m->H * 4, hipMemcpyDeviceToDevice, m->stream)); return; }
         PendingResid pr{m->pending_part, m->pending_slices, m->pending_rows, m->pending_alpha, m->pending_slot_of, m->pending_gate_w};
@@ -960,7 +1073,7 @@ struct DenseTap {
     void stage(int which) {
         if (which == TAIL_X1) take_x(x1);
         else if (which == TAIL_X2) take_x(x2);
-        else if (which == TAIL_H) NVL_HIP(hipMemcpyAsync(h, m->hbuf, (size_t)h_bytes, hipMemcpyDeviceToDevice, m->stream));
+        else if (which == TAIL_H) { if (h) NVL_HIP(hipMemcpyAsync(h, h_src ? h_src : m->hbuf, (size_t)h_bytes, hipMemcpyDeviceToDevice, m->stream)); }
         else {
             NVL_HIP(hipMemcpyAsync(op1, m->xn, (size_t)op_bytes, hipMemcpyDeviceToDevice, m->stream));
             NVL_HIP(hipMemcpyAsync(rs1, m->rs_part, (size_t)rs_bytes, hipMemcpyDeviceToDevice, m->stream));
@@ -1117,16 +1230,21 @@ extern "C" int nvl_op_dense_stages(int device, int precision, const nvl_dense_st
 // producer of the FFN norm, then moe(m, l, M, deferred_norm = true) — the router (in either routing form) and the expert up
 // projection scale their accumulators by rstd from the x^2 partials —, whose down projection leaves K slices in moe_part
 // pending for the next norm.  layer_tail() again, under tail_plan(); experts and scratch from moe_op_setup().
-extern "C" int nvl_op_dense_moe_stages(int device, int precision, const float* x, const float* attn_out, const float* wo,
-                                       const float* bo, const float* norm_w, const float* router, const float* w_in,
-                                       const float* w_out, const float* next_norm_w, int rows, int hidden, int q_width,
-                                       int n_experts, int top_k, int inter, float residual_multiplier, float norm_eps,
-                                       float* x1, float* op1, float* rs1, float* router_logits, float* gate, float* y,
-                                       int32_t* form, int32_t* ran) {
+// nvl_op_dense_moe_stages_q: the experts in a quantized format (moe_op_setup), the O projection and the router bf16; W~ read
+// back and moe_hall copied between the two expert projections, as nvl_op_moe_stages_q does.
+extern "C" int nvl_op_dense_moe_stages_q(int device, int precision, const float* x, const float* attn_out, const float* wo,
+                                         const float* bo, const float* norm_w, const float* router, const float* w_in,
+                                         const float* w_out, const float* next_norm_w, int rows, int hidden, int q_width,
+                                         int n_experts, int top_k, int inter, float residual_multiplier, float norm_eps,
+                                         int expert_format, int group_size, float* x1, float* op1, float* rs1, float* router_logits,
+                                         float* gate, float* y, int32_t* form, int32_t* ran, float* wt_in, float* wt_out, float* h) {
     if (!x || !attn_out || !wo || !norm_w || !router || !w_in || !w_out || !next_norm_w || !x1 || !op1 || !rs1 || !router_logits ||
         !gate || !y || !form || !ran || precision != NVL_PRECISION_BF16 || rows <= 0 || rows > 64 || hidden <= 0 || hidden % 64 ||
         q_width <= 0 || q_width % 64 || inter <= 0 || inter % 64 || n_experts < 1 || n_experts > 64 || top_k < 1 || top_k > n_experts)
         return op_fail("nvl_op_dense_moe_stages: bad arguments (bf16 only; rows <= 64; hidden, q_width, inter % 64; top_k <= n_experts <= 64)");
+    const int wf = moe_op_wf(expert_format, group_size, hidden, inter);
+    if (wf < 0) return op_fail("nvl_op_dense_moe_stages_q: unknown expert format, or INT4 experts whose group size is not 32, 64 or 128 or does not divide hidden and inter");
+    if (wf == WF_BF16 && (wt_in || wt_out)) return op_fail("nvl_op_dense_moe_stages_q: wt_in / wt_out are the read-back of quantized experts");
     OP_TRY
     OpCtx cx(device, precision);
     nvl_model& m = cx.m;
@@ -1137,7 +1255,7 @@ extern "C" int nvl_op_dense_moe_stages(int device, int precision, const float* x
     m.cfg.norm_eps = norm_eps; m.cfg.residual_multiplier = residual_multiplier;
     m.resid_alpha = residual_multiplier != 0.f ? residual_multiplier : 1.0f;      // (nvl_create)
     LayerW l;
-    moe_op_setup(cx, l, router, w_in, w_out, M, H, E, top_k, inter);
+    moe_op_setup(cx, l, router, w_in, w_out, M, H, E, top_k, inter, wf);
     const int64_t Mp = round_up(M, 64);
     m.x = cx.up_f32(x, (int64_t)M * H);
     m.attn_out = cx.up_mat(attn_out, M, q_width, false);
@@ -1154,6 +1272,7 @@ extern "C" int nvl_op_dense_moe_stages(int device, int precision, const float* x
     tap.op_bytes = Mp * H * 2; tap.h_bytes = 0; tap.rs_bytes = rs_floats * 4;
     tap.x1 = (float*)nan_fill((int64_t)M * H * 4); tap.x2 = (float*)nan_fill((int64_t)M * H * 4);
     tap.op1 = nan_fill(tap.op_bytes); tap.h = nullptr; tap.rs1 = (float*)nan_fill(tap.rs_bytes);
+    if (h) { tap.h_bytes = 64 * (int64_t)E * inter * 2; tap.h = nan_fill(tap.h_bytes); tap.h_src = m.moe_hall; }      // (TAIL_H comes from moe() here)
     const StageHook hook{&DenseTap::call, &tap};
     std::fill(m.dense_ran, m.dense_ran + NVL_DENSE_RAN_INTS, 0);
     m.pending_slices = 0;
@@ -1181,6 +1300,8 @@ extern "C" int nvl_op_dense_moe_stages(int device, int precision, const float* x
     for (int i = 0; i < NVL_DENSE_RAN_INTS; i++) ran[i] = m.dense_ran[i];
     ran[NVL_DENSE_RAN_SLICES + 4] = m.pending_slices;      // (what moe() left for the next norm: its down projection is no resid_gemm)
     ran[NVL_DENSE_RAN_RS1_TILES] = tap.rs1_tiles; ran[NVL_DENSE_RAN_RS2_TILES] = xn_deferred ? 1 : 0;
+    if (h) moe_op_h(cx, tap.h, M, E, inter, h);
+    if (wf != WF_BF16) moe_op_wt(cx, l, H, E, inter, wt_in, wt_out);
     moe_op_release(cx, l);
     for (auto& t : l.t) t.p = nullptr;
     m.g[NVL_T_FINAL_NORM_W].p = nullptr;
@@ -1188,6 +1309,16 @@ extern "C" int nvl_op_dense_moe_stages(int device, int precision, const float* x
     m.pending_part = nullptr; m.pending_slices = 0; m.pending_slot_of = nullptr; m.pending_gate_w = nullptr;
     return NVL_OK;
     OP_CATCH
+}
+extern "C" int nvl_op_dense_moe_stages(int device, int precision, const float* x, const float* attn_out, const float* wo,
+                                       const float* bo, const float* norm_w, const float* router, const float* w_in,
+                                       const float* w_out, const float* next_norm_w, int rows, int hidden, int q_width,
+                                       int n_experts, int top_k, int inter, float residual_multiplier, float norm_eps,
+                                       float* x1, float* op1, float* rs1, float* router_logits, float* gate, float* y,
+                                       int32_t* form, int32_t* ran) {
+    return nvl_op_dense_moe_stages_q(device, precision, x, attn_out, wo, bo, norm_w, router, w_in, w_out, next_norm_w, rows, hidden, q_width,
+                                     n_experts, top_k, inter, residual_multiplier, norm_eps, NVL_OP_EXPERTS_BF16, 0, x1, op1, rs1,
+                                     router_logits, gate, y, form, ran, nullptr, nullptr, nullptr);
 }
 
 extern "C" int nvl_op_argmax(int device, const float* x, int rows, int cols, int32_t* out) {

@@ -222,10 +222,25 @@ def moe_forward(x, router, w_in, w_out, top_k, precision="bf16", device=0):   # 
 MOE_FORMS = {1: "dense_fused", 2: "dense", 3: "plan", 4: "grouped"}      # NVL_MOE_FORM_*
 
 
-def moe_stages(x, router, w_in, w_out, top_k, precision="bf16", device=0):   # MoELayer.Forward moe.go:43
-    """The MoE block as a layer of the model runs it (nvl_op_moe_stages: the decode form wherever a model would take it,
+EXPERT_FORMATS = {"bf16": 0, "fp8": 1, "mxfp4": 2, "int4": 3}             # NVL_OP_EXPERTS_*
+
+
+def _expert_outputs(out, expert_format, M, E, I, hidden):
+    """the optional outputs of the *_q entry points: W~ of quantized experts, and h of the dense-masked forms"""
+    if expert_format not in EXPERT_FORMATS:
+        raise ValueError(f"expert_format must be one of {sorted(EXPERT_FORMATS)}")
+    out["h"] = np.full((M, E * I), np.nan, np.float32)
+    if expert_format != "bf16":
+        out["wt_in"], out["wt_out"] = np.full((E, 2 * I, hidden), np.nan, np.float32), np.full((E, hidden, I), np.nan, np.float32)
+    return [_p(out.get("wt_in")), _p(out.get("wt_out")), _p(out["h"])]
+
+
+def moe_stages(x, router, w_in, w_out, top_k, precision="bf16", device=0, expert_format="bf16", group_size=0):   # MoELayer.Forward moe.go:43
+    """The MoE block as a layer of the model runs it (nvl_op_moe_stages_q: the decode form wherever a model would take it,
     every scratch buffer pre-filled with NaN).  x [rows][H], router [H][E], w_in [E][2I][H], w_out [E][H][I] ->
-    dict(y [rows][H], router_logits [rows][E], gate [rows][E] (0 = not picked), form (a MOE_FORMS name))."""
+    dict(y [rows][H], router_logits [rows][E], gate [rows][E] (0 = not picked), form (a MOE_FORMS name), h [rows][E I] (the
+    dense forms' intermediate after the up projection; NaN where no launch wrote)).  expert_format "fp8" | "mxfp4" | "int4"
+    (group_size 32 / 64 / 128): the experts quantized and finalized as a model's, and wt_in / wt_out, W~ as the device holds it."""
     x, router, w_in, w_out = _f(x), _f(router), _f(w_in), _f(w_out)
     rows, hidden = x.shape
     E, I = router.shape[1], w_out.shape[2]
@@ -233,10 +248,11 @@ def moe_stages(x, router, w_in, w_out, top_k, precision="bf16", device=0):   # M
         raise ValueError("moe_stages: shapes do not match")
     out = dict(y=np.empty((rows, hidden), np.float32), router_logits=np.empty((rows, E), np.float32),
                gate=np.empty((rows, E), np.float32))
+    extra = _expert_outputs(out, expert_format, rows, E, I, hidden)
     form = C.c_int32(0)
-    L.check(L.lib().nvl_op_moe_stages(device, L.PRECISION[precision], _p(x), _p(router), _p(w_in), _p(w_out), rows, hidden, E,
-                                      int(top_k), I, _p(out["y"]), _p(out["router_logits"]), _p(out["gate"]),
-                                      C.cast(C.byref(form), C.c_void_p)))
+    L.check(L.lib().nvl_op_moe_stages_q(device, L.PRECISION[precision], _p(x), _p(router), _p(w_in), _p(w_out), rows, hidden, E,
+                                        int(top_k), I, EXPERT_FORMATS[expert_format], int(group_size), _p(out["y"]),
+                                        _p(out["router_logits"]), _p(out["gate"]), C.cast(C.byref(form), C.c_void_p), *extra))
     out["form"] = MOE_FORMS[form.value]
     return out
 
@@ -294,11 +310,12 @@ def dense_stages(x, attn_out, wo, norm_w, w1, w2, next_norm_w, wn, bo=None, norm
 
 
 def dense_moe_stages(x, attn_out, wo, norm_w, router, w_in, w_out, next_norm_w, top_k, bo=None, residual_multiplier=0.0,
-                     norm_eps=1e-5, precision="bf16", device=0):   # generic_model.go:320-389 around moe.go:43
-    """The layer tail with a MoE block, decode (nvl_op_dense_moe_stages): the O projection carries the FFN norm, moe() reads
+                     norm_eps=1e-5, precision="bf16", device=0, expert_format="bf16", group_size=0):   # generic_model.go:320-389 around moe.go:43
+    """The layer tail with a MoE block, decode (nvl_op_dense_moe_stages_q): the O projection carries the FFN norm, moe() reads
     the deferred operand, its down projection stays pending.  router [H][E], w_in [E][2I][H], w_out [E][H][I] ->
     dict(x1, op1, rs1 (x^2 partials, None = op1 is normalised), router_logits, gate, y (x after the block), form (a
-    MOE_FORMS name), ran as dense_stages gives it; ran["down"]["slices"] = what moe() left pending)."""
+    MOE_FORMS name), ran as dense_stages gives it; ran["down"]["slices"] = what moe() left pending; h, and for a quantized
+    expert_format wt_in / wt_out, as moe_stages gives them)."""
     x, attn_out, wo, norm_w, router, w_in, w_out, next_norm_w = (_f(a) for a in (x, attn_out, wo, norm_w, router, w_in, w_out, next_norm_w))
     bo = None if bo is None else _f(bo)
     M, H = x.shape
@@ -309,10 +326,12 @@ def dense_moe_stages(x, attn_out, wo, norm_w, router, w_in, w_out, next_norm_w, 
     nan = lambda *s: np.full(s, np.nan, np.float32)
     out = dict(x1=nan(M, H), op1=nan(M, H), rs1=nan(M, H // 8), router_logits=nan(M, E), gate=nan(M, E), y=nan(M, H))
     ran, form = np.zeros(14, np.int32), np.zeros(1, np.int32)
-    L.check(L.lib().nvl_op_dense_moe_stages(device, L.PRECISION[precision], _p(x), _p(attn_out), _p(wo), _p(bo), _p(norm_w), _p(router),
-                                            _p(w_in), _p(w_out), _p(next_norm_w), M, H, qw, E, int(top_k), I, residual_multiplier,
-                                            norm_eps, _p(out["x1"]), _p(out["op1"]), _p(out["rs1"]), _p(out["router_logits"]),
-                                            _p(out["gate"]), _p(out["y"]), _p(form), _p(ran)))
+    extra = _expert_outputs(out, expert_format, M, E, I, H)
+    L.check(L.lib().nvl_op_dense_moe_stages_q(device, L.PRECISION[precision], _p(x), _p(attn_out), _p(wo), _p(bo), _p(norm_w), _p(router),
+                                              _p(w_in), _p(w_out), _p(next_norm_w), M, H, qw, E, int(top_k), I, residual_multiplier,
+                                              norm_eps, EXPERT_FORMATS[expert_format], int(group_size), _p(out["x1"]), _p(out["op1"]),
+                                              _p(out["rs1"]), _p(out["router_logits"]), _p(out["gate"]), _p(out["y"]), _p(form), _p(ran),
+                                              *extra))
     t1 = int(ran[12])
     out["rs1"] = out["rs1"][:, :t1].copy() if t1 else None
     proj = lambda p: dict(producer=int(ran[4 * p]), half=int(ran[4 * p + 1]), form=RESID_FORMS[int(ran[4 * p + 2])],

@@ -437,8 +437,22 @@ MOE_CASES = [(M, keys, form, _ran(P(1, 1 if M <= 16 else 0, "msplit"), P(0, 0, "
              for M in (1, 16, 40) for keys, form in (({}, "dense_fused"), ({31: 0}, "dense"))]
 
 
-def moe_inputs(M, seed=0):
-    s = MOE_SHAPE
+# quantized experts (tests/test_moe_q_ops_gpu.py): the same chain per format (INT4 g = 64) with W~ in inp, and one
+# Granite-shaped case — 64 rows, E = 32, k = 8, I = 512, INT4 g = 128: MT = 4 and the wide up form under the deferred scale
+# (fmt, group, M, keys, form, ran, shape)
+GRANITE_SHAPE = dict(H=256, qw=256, E=32, k=8, I=512)
+MOE_Q_CASES = ([(fmt, 64, M, keys, form, ran, MOE_SHAPE) for fmt in MR.FORMATS for M, keys, form, ran in MOE_CASES]
+               + [("int4", 128, 64, {}, "dense_fused", _ran(P(1, 0, "msplit"), P(0, 0, "tile", 4), 0, 16, 0), GRANITE_SHAPE)])
+
+
+def moe_inputs_q(M, fmt, g, shape=None):
+    """moe_inputs with W~ of the format in w_in / w_out (the reference's experts) and the unquantized ones, which the op
+    is given, in raw_in / raw_out"""
+    return MR.quantized(moe_inputs(M, shape=shape), fmt, g)
+
+
+def moe_inputs(M, seed=0, shape=None):
+    s = shape or MOE_SHAPE
     r = np.random.default_rng(977 * M + seed)
     n = lambda *sh: r.standard_normal(sh, dtype=np.float32)
     inp = dict(x=n(M, s["H"]), attn_out=n(M, s["qw"]), wo=n(s["H"], s["qw"]) * 0.05, norm_w=1.0 + 0.3 * n(s["H"]),

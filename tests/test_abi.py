@@ -11,9 +11,10 @@ def test_library_exports_every_declared_symbol(pkg):
     names = pkg.declared_symbols()
     assert len(names) >= 30 and "nvl_forward" in names and "nvl_runner_run" in names and "nvl_op_moe_stages" in names
     assert "nvl_op_attention_batch" in names and "nvl_op_dense_stages" in names and "nvl_op_dense_moe_stages" in names
+    assert "nvl_op_moe_stages_q" in names and "nvl_op_dense_moe_stages_q" in names
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing
-    assert L.nvl_abi_version() == 3                                 # (nvl_op_moe_stages / nvl_op_attention_batch / nvl_op_dense_stages are additions: the version stays)
+    assert L.nvl_abi_version() == 3                                 # (nvl_op_moe_stages / nvl_op_attention_batch / nvl_op_dense_stages and the *_q entry points are additions: the version stays)
 
 
 def test_header_cites_the_reference_for_every_entry_point(pkg):
@@ -61,6 +62,26 @@ def test_moe_stages_refuses_bad_arguments_before_touching_a_device(pkg):
             pkg.ops.moe_stages(z((M, H), np.float32), z((H, E), np.float32), z((E, 2 * I, H), np.float32), z((E, H, I), np.float32),
                                kw.get("top_k", 2), precision=kw.get("precision", "bf16"))
         assert e.value.code == -1, (kw, shape)                      # NVL_ERR_INVALID
+    # the expert format: what the format's setter would refuse — an unknown format, an INT4 group that is not 32 / 64 / 128 or
+    # does not divide hidden and inter, f32 — is refused the same way, in both entry points
+    M, H, E, I = 2, 256, 4, 96
+    args = (z((M, H), np.float32), z((H, E), np.float32), z((E, 2 * I, H), np.float32), z((E, H, I), np.float32), 2)
+    for kw in (dict(expert_format="int4", group_size=64), dict(expert_format="int4", group_size=16), dict(expert_format="int4"),
+               dict(expert_format="fp8", precision="f32"), dict(expert_format="mxfp4", precision="f32")):
+        with pytest.raises(pkg.NvlError) as e:
+            pkg.ops.moe_stages(*args, **kw)
+        assert e.value.code == -1, kw
+    with pytest.raises(ValueError):
+        pkg.ops.moe_stages(*args, expert_format="fp4")
+    I = 192
+    chain = (z((M, H), np.float32), z((M, H), np.float32), z((H, H), np.float32), z(H, np.float32), z((H, E), np.float32),
+             z((E, 2 * I, H), np.float32), z((E, H, I), np.float32), z(H, np.float32), 2)
+    for kw in (dict(expert_format="int4", group_size=128), dict(expert_format="int4", group_size=48), dict(expert_format="fp8", precision="f32")):
+        with pytest.raises(pkg.NvlError) as e:
+            pkg.ops.dense_moe_stages(*chain, **kw)
+        assert e.value.code == -1, kw
+    assert pkg.ops.EXPERT_FORMATS == {"bf16": 0, "fp8": 1, "mxfp4": 2, "int4": 3}
+    assert re.search(r"NVL_OP_EXPERTS_BF16 = 0, NVL_OP_EXPERTS_FP8 = 1, NVL_OP_EXPERTS_MXFP4 = 2, NVL_OP_EXPERTS_INT4 = 3", pkg._lib.HEADER.read_text())
     assert pkg.ops.MOE_FORMS == {1: "dense_fused", 2: "dense", 3: "plan", 4: "grouped"}
     text = pkg._lib.HEADER.read_text()
     for code, name in enumerate(("DENSE_FUSED", "DENSE", "PLAN", "GROUPED"), 1):

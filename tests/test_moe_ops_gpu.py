@@ -32,9 +32,9 @@ What test_experts case 2 found: E = 5 gives one K slice, for which the down kern
 partial, while moe() still announced one pending slice — the next norm added the unwritten moe_part rows (NaN here, a
 stale layer's partials in a model).  moe() now leaves nothing pending for one slice.
 
-Out of scope: quantized experts (model-level mirrors exist: test_fp8_experts_gpu.py, test_mxfp4_experts_gpu.py), the
-key-33 deferred-norm producer form of the down projection (off by default), and the deferred_norm input path (it needs
-the preceding O projection).  The sorted forms' cases with I % 64 == 32 (I = 96, 32, 160 — widths nvl_create refuses,
+Quantized experts (fp8, MXFP4, INT4) have this file's cases and checks, plus W~ and h, in tests/test_moe_q_ops_gpu.py; the
+deferred_norm input path (it needs the preceding O projection) is test_dense_ops_gpu.py::test_moe_chain.  Out of scope: the
+key-33 deferred-norm producer form of the down projection (off by default).  The sorted forms' cases with I % 64 == 32 (I = 96, 32, 160 — widths nvl_create refuses,
 their grouped GEMMs stream K in 64-wide tiles) run on experts zero-padded by 32 columns inside the op."""
 import numpy as np
 import pytest

@@ -130,3 +130,207 @@ def test_mutation_f_gate_row_off_by_one():
     assert not np.array_equal(out["gate"][-1], out["gate"][-2])
     with pytest.raises(AssertionError):
         R.check_experts(inp, mutated(inp, gate=g), MOE_RATIO_BOUND)
+
+
+# ---- quantized experts: tests/test_moe_q_ops_gpu.py proved without a GPU ------------------------------------------------
+# The stand-in (moe_reference.emulated_device_q) reports W~ of the mirror and computes with it: unmutated it passes every
+# check of every case and format, its h at a ratio of exactly 1.  Each mutation below makes it COMPUTE with what a wrong
+# kernel would read — while it still reports the right W~, as a device whose decode kernel is wrong and whose dequantize
+# kernel is right would — and must fail the check aimed at it.
+import dense_reference as D
+from test_int4_weights_gpu import bf16_rne
+from test_kv_fp8_gpu import VALUES
+from test_moe_q_ops_gpu import ALL_Q_CASES, MOE_Q_RATIO_BOUND, chain_gu, inputs
+
+QB = MOE_Q_RATIO_BOUND
+CHECK_H = lambda q, o: R.check_h(q, o, QB)
+CHECK_DOWN = lambda q, o: R.check_down(q, o)
+CHECK_Y = lambda q, o: R.check_experts(q, o, QB)
+
+
+@pytest.mark.parametrize("name,fmt,shape,g,crafted,forms", ALL_Q_CASES, ids=[c[0] for c in ALL_Q_CASES])
+def test_unmutated_q_passes(name, fmt, shape, g, crafted, forms):
+    q = inputs(shape, fmt, g, crafted)
+    assert np.array_equal(bf16_rne(q["w_in"]).view(np.uint32), q["w_in"].view(np.uint32))          # W~ is exact in bf16
+    assert np.array_equal(bf16_rne(q["w_out"]).view(np.uint32), q["w_out"].view(np.uint32))
+    for form in sorted({"dense" if f in R.DENSE_FORMS else "plan" for f, _ in forms}):
+        out = R.emulated_device_q(q, form)
+        ratio = R.check_all_q(q, out, QB, name)
+        assert np.abs(ratio - 1.0).max() <= 1e-3        # (y of the stand-in is the emulation rounded to fp32)
+        if form == "dense":
+            assert set(R.h_ratio(q, out).values()) == {1.0}       # (its h IS the emulation)
+
+
+def chain_standin(q, ran, form, mut=None):
+    """dense_reference.emulated_moe_device with the outputs the quantized op adds: W~ as reported, h from the same scales"""
+    out = D.emulated_moe_device(q, ran, form, mut)
+    out.update(wt_in=q["w_in"].copy(), wt_out=q["w_out"].copy())
+    rs_u = np.roll(out["rs1"], -1, 0) if mut == "neighbour_rstd" else out["rs1"]
+    out["h"] = R.emulated_h(q, out["gate"], gu=chain_gu(q, dict(out, rs1=rs_u)))
+    return out
+
+
+def check_chain(q, out):
+    R.check_wt(out, q)
+    D.check_moe_chain(q, out, QB)
+    R.check_h(q, out, QB, "", chain_gu(q, out))
+    R.check_down(q, out, "", base=out["x1"], alpha=float(np.float32(D.alphas(q)[0])))
+
+
+CHAIN_Q = [c for c in D.MOE_Q_CASES if c[3] == {}]       # (the stand-in does not depend on the routing form)
+
+
+@pytest.mark.parametrize("fmt,g,M,keys,form,ran,shape", CHAIN_Q, ids=[f"{c[0]}-M{c[2]}-E{c[6]['E']}" for c in CHAIN_Q])
+def test_unmutated_chain_q_passes(fmt, g, M, keys, form, ran, shape):
+    q = D.moe_inputs_q(M, fmt, g, shape)
+    out = chain_standin(q, ran, form)
+    check_chain(q, out)
+    assert set(R.h_ratio(q, out, chain_gu(q, out)).values()) == {1.0}
+
+
+def q_case(fmt, number):
+    shape, g = R.Q_CASES[number - 1]
+    return inputs(shape, fmt, g, number in R.Q_CRAFTED)
+
+
+def fails(q, compute_with, checks, form="dense_fused", **kw):
+    """the stand-in computing with the mutated experts passes check_wt (it reports the right W~) and fails each check"""
+    for key, w in compute_with.items():
+        assert not np.array_equal(w, q[key]), "the mutation changed nothing"
+    out = R.emulated_device_q(q, form, compute_with, **kw)
+    R.check_wt(out, q)
+    for check in checks:
+        with pytest.raises(AssertionError):
+            check(q, out)
+
+
+def rows2d(q, key):
+    E, N, K = q[key].shape
+    return R.mirror(q["fmt"])(q["raw_" + key[2:]].reshape(E * N, K), q["g"]), (E, N, K)
+
+
+def nibbles(packed):
+    c = np.empty((packed.shape[0], 2 * packed.shape[1]), np.float32)
+    c[:, 0::2], c[:, 1::2] = packed & 15, packed >> 4
+    return c
+
+
+def first_live_expert(q):
+    return int(np.flatnonzero(R.emulated_device(q, "dense")["gate"].any(0))[0])
+
+
+def test_q_mutation_a_fp8_down_scale_rows_of_the_next_expert():
+    q = q_case("fp8", 4)
+    m, (E, H, I) = rows2d(q, "w_out")
+    s = np.roll(m["s"].reshape(E, H), -1, 0)
+    w = bf16_rne(VALUES[m["codes"]].astype(np.float32).reshape(E, H, I) * s[:, :, None])
+    fails(q, dict(w_out=w), [CHECK_DOWN, CHECK_Y])
+
+
+def test_q_mutation_b_fp8_up_scales_not_following_the_interleave():
+    q = q_case("fp8", 2)
+    m, (E, N, K) = rows2d(q, "w_in")
+    I = N // 2
+    idx = np.concatenate([np.r_[16 * b:16 * b + 16, I + 16 * b:I + 16 * b + 16] for b in range(I // 16)])     # device row p holds row idx[p]
+    s = m["s"].reshape(E, N).copy()
+    s[:, idx] = m["s"].reshape(E, N)          # ... and is scaled by the scale of row p
+    w = bf16_rne(VALUES[m["codes"]].astype(np.float32).reshape(E, N, K) * s[:, :, None])
+    fails(q, dict(w_in=w), [CHECK_H])
+
+
+def test_q_mutation_c_mxfp4_last_block_scale_from_the_next_expert():
+    q = q_case("mxfp4", 2)
+    m, (E, H, I) = rows2d(q, "w_out")
+    s = m["s"].reshape(E, H, I // 32).astype(np.int32)
+    w = q["w_out"].copy()
+    w[:-1, :, -32:] = np.ldexp(w[:-1, :, -32:], (s[1:, :, 0] - s[:-1, :, -1])[:, :, None])
+    fails(q, dict(w_out=w), [CHECK_DOWN, CHECK_Y])
+
+
+def test_q_mutation_d_int4_group_words_shifted_across_the_expert_boundary():
+    q = q_case("int4", 2)                              # I = 96, g = 32: the last of three groups takes the next expert's first word
+    m, (E, H, I) = rows2d(q, "w_out")
+    g = q["g"]
+    s, z = m["s"].astype(np.float32).reshape(E, H, I // g), m["z"].astype(np.float32).reshape(E, H, I // g)
+    code = nibbles(m["codes"]).reshape(E, H, I)
+    w = q["w_out"].copy()
+    w[:-1, :, -g:] = bf16_rne(s[1:, :, :1] * (code[:-1, :, -g:] - z[1:, :, :1]))
+    fails(q, dict(w_out=w), [CHECK_DOWN, CHECK_Y])
+
+
+def test_q_mutation_e_int4_zero_point_of_one_group_read_as_0():
+    q = q_case("int4", 1)
+    m, (E, N, K) = rows2d(q, "w_in")
+    e, r = first_live_expert(q), 7                     # one group of one gate row of a live expert
+    g = q["g"]
+    assert m["z"].reshape(E, N, K // g)[e, r, 0] != 0
+    w = q["w_in"].copy()
+    w[e, r, :g] = bf16_rne(m["s"].astype(np.float32).reshape(E, N, K // g)[e, r, 0] * nibbles(m["codes"]).reshape(E, N, K)[e, r, :g])
+    fails(q, dict(w_in=w), [CHECK_H])
+
+
+@pytest.mark.parametrize("fmt", ["mxfp4", "int4"])
+def test_q_mutation_f_nibble_order_swapped_in_one_k_step(fmt):
+    q = q_case(fmt, 3)                                 # I = 32: the down matrix of an expert is one k-step
+    e = first_live_expert(q)
+    w = q["w_out"].copy()
+    w[e, :, 0:32:2], w[e, :, 1:32:2] = q["w_out"][e, :, 1:32:2], q["w_out"][e, :, 0:32:2]
+    fails(q, dict(w_out=w), [CHECK_DOWN, CHECK_Y])
+    w = q["w_in"].copy()                               # ... and the first k-step of its up matrix
+    w[e, :, 0:32:2], w[e, :, 1:32:2] = q["w_in"][e, :, 1:32:2], q["w_in"][e, :, 0:32:2]
+    fails(q, dict(w_in=w), [CHECK_H])
+
+
+def test_q_mutation_g_last_k_step_dropped_at_one_k_step_per_register_set():
+    shape, g, form = R.Q_MASK_EDGES["int4"][0]          # 33 rows, I = 1024: 32 blocks of one k-step
+    q = inputs(shape, "int4", g)
+    w = q["w_out"].copy()
+    w[first_live_expert(q), :, -32:] = 0.0
+    fails(q, dict(w_out=w), [CHECK_DOWN, CHECK_Y], form="dense")
+
+
+@pytest.mark.parametrize("fmt", R.FORMATS)
+def test_q_mutation_h_neighbour_rstd_in_the_deferred_chain(fmt):
+    assert "neighbour_rstd" in D.MOE_MUTATIONS
+    _, g, M, _, form, ran, shape = next(c for c in D.MOE_Q_CASES if c[0] == fmt and c[2] == 16)
+    q = D.moe_inputs_q(M, fmt, g, shape)
+    out = chain_standin(q, ran, form, "neighbour_rstd")
+    R.check_wt(out, q)
+    with pytest.raises(AssertionError):
+        D.check_moe_chain(q, out, QB)
+    with pytest.raises(AssertionError):
+        R.check_h(q, out, QB, "", chain_gu(q, out))
+
+
+def test_q_mutation_i_untouched_expert_read_as_0_instead_of_skipped():
+    q = q_case("mxfp4", 1)                              # one row, two of eight experts live
+    out = R.emulated_device_q(q, "dense_fused", untouched=0.0)
+    R.check_experts(q, out, QB)                         # (y cannot tell)
+    with pytest.raises(AssertionError, match="picked by no row"):
+        R.check_h(q, out, QB)
+
+
+def test_q_mutation_j_int4_pad_word_applied_to_a_real_row():
+    q = q_case("int4", 4)
+    m, (E, H, I) = rows2d(q, "w_out")
+    e = first_live_expert(q)
+    w = q["w_out"].copy()
+    w[e, 3] = bf16_rne(nibbles(m["codes"]).reshape(E, H, I)[e, 3])          # {s = 1, z = 0}: W~ = q
+    fails(q, dict(w_out=w), [CHECK_DOWN, CHECK_Y])
+
+
+@pytest.mark.parametrize("fmt", R.FORMATS)
+def test_unmutated_q_skews_and_routing_pass(fmt):
+    for skew in R.SKEWS:
+        q = inputs(None, fmt, 64, False, skew)
+        out = R.emulated_device_q(q, "dense")
+        assert [tuple(np.flatnonzero(g)) for g in out["gate"]] == [tuple(sorted(p)) for p in q["picks"]]
+        R.check_all_q(q, out, QB, skew)
+    for M, E, k in R.ROUTING_CASES:
+        q = inputs((M, E, k), fmt, 64, False, "routing")
+        for form in ("dense_fused", "plan"):
+            out = R.emulated_device_q(q, form)
+            R.check_routing_exact(q, out)
+            R.check_wt(out, q)
+            base = R.emulated_device(dict(q, w_in=q["raw_in"], w_out=q["raw_out"]), form)       # the bf16-expert call
+            assert np.array_equal(out["router_logits"], base["router_logits"]) and np.array_equal(out["gate"], base["gate"])
