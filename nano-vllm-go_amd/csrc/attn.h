@@ -449,8 +449,16 @@ __device__ __forceinline__ void rope_load8(const float* row, const float* cs, co
 __device__ __forceinline__ void rope_math8(const RopeRaw& r, bool rot, bf16x8& lo, bf16x8& hi) {
     f32x4 yl0 = r.a0, yl1 = r.a1, yh0 = r.b0, yh1 = r.b1;
     if (rot) {
-        yl0 = r.a0 * r.c0 + (-r.b0) * r.s0; yl1 = r.a1 * r.c1 + (-r.b1) * r.s1;
-        yh0 = r.b0 * r.c0 + r.a0 * r.s0;    yh1 = r.b1 * r.c1 + r.a1 * r.s1;
+        // which product of x*cos + rotate_half(x)*sin is rounded on its own and which rides the fused multiply-add is
+        // written out: left to the compiler's contraction it changed with the code around it (the high half came out as
+        // fma(b, c, a*s) in one build and fma(a, s, b*c) in the next: last-bit differences in q and the appended k)
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            yl0[e] = __builtin_fmaf(r.a0[e], r.c0[e], -(r.b0[e] * r.s0[e]));
+            yl1[e] = __builtin_fmaf(r.a1[e], r.c1[e], -(r.b1[e] * r.s1[e]));
+            yh0[e] = __builtin_fmaf(r.b0[e], r.c0[e], r.a0[e] * r.s0[e]);
+            yh1[e] = __builtin_fmaf(r.b1[e], r.c1[e], r.a1[e] * r.s1[e]);
+        }
     }
 #pragma unroll
     for (int e = 0; e < 4; e++) {
@@ -536,9 +544,12 @@ __device__ __forceinline__ void attn_decode_finish(const AttnArgs& p, char* smem
     __syncthreads();
     stamps.mark(4);                     // every wave's tiles done
     if (gridDim.z == 1 && NW >= DT) {
-        // whole (sequence, kv head) in this workgroup: wave d combines output block d (same sums, same order as below;
+        // whole (sequence, kv head) in this workgroup: one wave per output block (same sums, same order as below;
         // one wave doing all DT blocks: B = 32 33.55 K -> 33.80 K decode tok/s, B = 8 +0.9 %, same-box A/B)
-        if (wave >= DT || !row_ok) return;
+        // The LAST DT waves do it: tiles are dealt from wave 0 up, so the first waves are the ones that may carry a second
+        // tile and arrive last; which wave sums does not change the sum.
+        const int blk = wave - (NW - DT);
+        if (blk < 0 || !row_ok) return;
         float ms = red_m[0][fq];
 #pragma unroll
         for (int w = 1; w < NW; w++) ms = fmaxf(ms, red_m[w][fq]);
@@ -548,9 +559,9 @@ __device__ __forceinline__ void attn_decode_finish(const AttnArgs& p, char* smem
         for (int w = 0; w < NW; w++) {
             const float sc = __builtin_amdgcn_exp2f(red_m[w][fq] - ms);
             Ls += red_l[w][fq] * sc;
-            Od += ((const f32x4*)(smem + w * TILE_BYTES))[wave * 64 + lane] * sc;
+            Od += ((const f32x4*)(smem + w * TILE_BYTES))[blk * 64 + lane] * sc;
         }
-        act_store4<bf16_t>((bf16_t*)p.out, tok, head * HD + wave * 16 + fg * 4, p.out_stride, Od * (osc / Ls));
+        act_store4<bf16_t>((bf16_t*)p.out, tok, head * HD + blk * 16 + fg * 4, p.out_stride, Od * (osc / Ls));
         return;
     }
     if (wave != 0 || !row_ok) return;
@@ -603,7 +614,7 @@ __device__ __forceinline__ void attn_decode_finish(const AttnArgs& p, char* smem
 // fetched the argument block in two dependent pieces first (in-kernel stamps: 2.4 us from entry to the first vector load
 // at B = 1, against 0.4 us in the projection kernels).
 template <int HD, int NW, bool FUSED, bool STAMP = false>
-__global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
+__global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                    int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p) {
     constexpr int KS = HD / 32, DT = HD / 16, HALF = HD / 2, CPR = HD / 8, KPI = 64 / CPR, NVL = 64 / KPI;
     constexpr int NT2 = HD <= 64 ? 2 : 1;                    // key tiles whose loads are in flight together, per wave
@@ -667,17 +678,27 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t
     // one workgroup serves the whole group (GQA / MHA), and lines that stay out of L2 leave it to the projections'
     // activations: decode +5 % at B = 32 (32.0 K -> 33.7 K tok/s), GPT-2 B = 128 +3.2 %; it loses 2 % at 32-64 workgroups
     // (profiles/r03_kv_nontemporal.txt).  Falcon's MQA (5 workgroups share one K/V stream through L2) keeps the default policy.
-    auto issue_round_t = [&](int kt0, auto nt_tag) {
+    // Every piece of a round is instantiated for the number of tiles the wave really holds in it (NTL = 1 .. NT2, a
+    // wave-uniform choice made once per round, at the call): a "does tile h exist" branch around some of the loads makes the
+    // compiler count its waits for the path with the fewest loads in flight, and a two-tile wave then waits for most of its
+    // round before the first score MFMA.
+    // Order inside a round: the K fragments of ALL its tiles, then the V rows of all its tiles (vector loads return in issue
+    // order): the scores of every tile, the joint maximum and the softmax run while the round's V is still in flight, and
+    // only V -> LDS, the transposed reads and P.V stay behind the last byte.
+    auto issue_round_t = [&](int kt0, auto nt_tag, auto ntl_tag) __attribute__((always_inline)) {
         constexpr bool NT = decltype(nt_tag)::value;
+        constexpr int NTL = decltype(ntl_tag)::value;
+        int64_t blk_off[NTL];
 #pragma unroll
-        for (int h = 0; h < NT2; h++) {
+        for (int h = 0; h < NTL; h++) {
             const int kt = kt0 + h * nvw;
-            if (kt >= n_kt) continue;
             const int bi = kv_block_index(p, kt * 64), krow0 = kt * 64 - bi * p.Tmax;     // the KV block holding this tile
             const int blk = kt0 == vw ? first_blk[h] : tbl[bi];
-            const int64_t blk_off = (int64_t)blk * p.slot_stride + ((int64_t)kvh * p.Tmax + krow0) * HD;
-            const bf16_t* kbase = (const bf16_t*)p.kcache + blk_off;
-            const bf16_t* vbase = (const bf16_t*)p.vcache + blk_off;
+            blk_off[h] = (int64_t)blk * p.slot_stride + ((int64_t)kvh * p.Tmax + krow0) * HD;
+        }
+#pragma unroll
+        for (int h = 0; h < NTL; h++) {
+            const bf16_t* kbase = (const bf16_t*)p.kcache + blk_off[h];
 #pragma unroll
             for (int t = 0; t < 4; t++)
 #pragma unroll
@@ -686,15 +707,19 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t
                     const bf16x8* src = (const bf16x8*)(kbase + (int64_t)(t * 16 + fq) * HD + ks * 32 + fg * 8);
                     if constexpr (NT) kf[h][t][ks] = __builtin_nontemporal_load(src); else kf[h][t][ks] = *src;
                 }
+        }
+#pragma unroll
+        for (int h = 0; h < NTL; h++) {
+            const bf16_t* vbase = (const bf16_t*)p.vcache + blk_off[h];
 #pragma unroll
             for (int i = 0; i < NVL; i++) {                                                                 // 1 KiB, contiguous
                 const bf16x8* src = (const bf16x8*)(vbase + (int64_t)lane * 8 + i * 512);
                 if constexpr (NT) vch[h][i] = __builtin_nontemporal_load(src); else vch[h][i] = *src;
             }
         }
-    };
-    auto issue_round = [&](int kt0) {
-        if (p.kv_nt) issue_round_t(kt0, std::true_type{}); else issue_round_t(kt0, std::false_type{});
+        // the whole round leaves before anything that waits: with no branch left between the loads and the RoPE arithmetic
+        // the scheduler pulled part of it, and its wait for the row, in front of the last V loads
+        __builtin_amdgcn_sched_barrier(0);
     };
     // Load order (vector loads return in issue order): the new token's fp32 q/k/v row + cos/sin FIRST (a dozen small loads),
     // the round's K/V stream right behind them with no wait in between, THEN the RoPE arithmetic — it waits for the row only
@@ -740,38 +765,36 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t
 #pragma unroll
         for (int ks = 0; ks < KS; ks++) qf[ks] = *(const bf16x8*)(qp + ks * 32 + fg * 8);
     }
-    if (vw < n_kt) issue_round(vw);
-    stamps.mark(1);                     // first round's K/V loads issued
-    if (ROW_FIRST) {
+    // the RoPE arithmetic of the row-first form, behind the first round's issue
+    auto rotate_row = [&]() __attribute__((always_inline)) {
+        stamps.mark(1);                     // first round's K/V loads issued
+        if (ROW_FIRST) {
 #pragma unroll
-        for (int ks = 0; ks < KS / 2; ks++) {
-            rk[ks].c0 = rq[ks].c0; rk[ks].c1 = rq[ks].c1; rk[ks].s0 = rq[ks].s0; rk[ks].s1 = rq[ks].s1;
-            rope_math8(rq[ks], cs != nullptr, qf[ks], qf[ks + KS / 2]);
-            rope_math8(rk[ks], cs != nullptr, knew[ks], knew[ks + KS / 2]);
+            for (int ks = 0; ks < KS / 2; ks++) {
+                rk[ks].c0 = rq[ks].c0; rk[ks].c1 = rq[ks].c1; rk[ks].s0 = rq[ks].s0; rk[ks].s1 = rq[ks].s1;
+                rope_math8(rq[ks], cs != nullptr, qf[ks], qf[ks + KS / 2]);
+                rope_math8(rk[ks], cs != nullptr, knew[ks], knew[ks + KS / 2]);
+            }
+#pragma unroll
+            for (int e = 0; e < 4; e++) { vnew8[e] = (bf16_t)v0[e]; vnew8[4 + e] = (bf16_t)v1[e]; }
         }
-#pragma unroll
-        for (int e = 0; e < 4; e++) { vnew8[e] = (bf16_t)v0[e]; vnew8[4 + e] = (bf16_t)v1[e]; }
-    }
-    stamps.mark(2);                     // q/k/v of the new token rotated
-    // one round: scores, online softmax, O^T += V^T P^T of the tiles whose K/V fragments issue_round left in kf / vch.
-    // (The first round is peeled — its loads went out above, ahead of the RoPE arithmetic — instead of making the issue
+        stamps.mark(2);                     // q/k/v of the new token rotated
+    };
+    // one round: scores, online softmax, O^T += V^T P^T of the NTL tiles whose K/V fragments issue_round left in kf / vch.
+    // (The first round is peeled — its loads go out ahead of the RoPE arithmetic — instead of making the issue
     // conditional inside ONE loop: there every fragment register became a loop-carried value with a select per iteration,
     // 213 -> 252 registers on the 2- and 4-wave hd-64 kernels (MHA models: one wave per SIMD instead of two) and 25
     // spilled on the 8-wave hd-128 kernel.)
-    auto do_round = [&](int kt0) __attribute__((always_inline)) {
-        // ---- scores of the round's tiles ----
-        f32x4 s[NT2][4];
+    auto do_round = [&](int kt0, auto ntl_tag) __attribute__((always_inline)) {
+        constexpr int NTL = decltype(ntl_tag)::value;
+        // ---- scores of the round's tiles: they wait for K only ----
+        f32x4 s[NTL][4];
         float tmax = -INFINITY;
 #pragma unroll
-        for (int h = 0; h < NT2; h++) {
+        for (int h = 0; h < NTL; h++) {
             const int kt = kt0 + h * nvw;
-            if (kt >= n_kt) {
-#pragma unroll
-                for (int t = 0; t < 4; t++) s[h][t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
-                continue;
-            }
             if (FUSED && kt == n_kt - 1) {
-                // the tile that holds key pos0: its slab row is not written yet (or not visible): patch the operands
+                // the tile that holds key pos0: its slab row is not written yet (or not visible): patch the operand
                 const int kl = pos0 & 63;
 #pragma unroll
                 for (int t = 0; t < 4; t++)
@@ -779,9 +802,6 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t
 #pragma unroll
                         for (int ks = 0; ks < KS; ks++) kf[h][t][ks] = knew[ks];
                     }
-#pragma unroll
-                for (int i = 0; i < NVL; i++)
-                    if (i == kl / KPI && ksub == kl % KPI) vch[h][i] = vnew8;
             }
 #pragma unroll
             for (int t = 0; t < 4; t++) {
@@ -799,33 +819,61 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_bf16_kernel(const int32_t
                 s[h][t] = acc;
             }
         }
-        attn_decode_softmax<HD, NT2>(s, tmax, m_run, l_run, o);
+        attn_decode_softmax<HD, NTL>(s, tmax, m_run, l_run, o);
         // ---- O^T += V^T · P^T: the tile's V rows go through this wave's LDS image and come back as the transposed
         // MFMA operand (ds_read_b64_tr_b16); a wave's LDS accesses execute in order, so no barrier ----
 #pragma unroll
-        for (int h = 0; h < NT2; h++) {
-            if (kt0 + h * nvw >= n_kt) continue;
+        for (int h = 0; h < NTL; h++) {
+            if (FUSED && kt0 + h * nvw == n_kt - 1) {
+                // the new token's V row, patched HERE and not beside the K patch: a select on vch ahead of the scores made the
+                // wave that holds the newest tile — at 9-10 tiles over 8 waves a two-tile wave, the tile its LAST load — wait
+                // for its whole round before the first score MFMA
+                const int kl = pos0 & 63;
+#pragma unroll
+                for (int i = 0; i < NVL; i++)
+                    if (i == kl / KPI && ksub == kl % KPI) vch[h][i] = vnew8;
+            }
 #pragma unroll
             for (int i = 0; i < NVL; i++) *(bf16x8*)(vimg + w_base[i & 1] + i * (16 * KPI * CPR)) = vch[h][i];
             attn_pv_tile<HD, 1, false>(vimg, v_off, &s[h], &o, nullptr);
         }
     };
-    if (vw < n_kt) do_round(vw);
-    for (int kt0 = vw + NT2 * nvw; kt0 < n_kt; kt0 += NT2 * nvw) {
-        issue_round(kt0);
-        do_round(kt0);
-    }
-    if (FUSED && blockIdx.z == 0 && qt == 0) {
-        // append the new key/value to the slabs for the following steps — after every load of this step (which used
-        // the register copies), so the loads above are not ordered behind these stores
+    // A whole round — issue, (first round: the RoPE arithmetic,) scores, softmax, P.V — per (load policy, tiles held): the
+    // choice is made ONCE, around the round, so that no path without the loads joins between a load and its wait (the
+    // compiler counts a wait for the emptiest path that reaches it; a policy branch around the issue alone did that).
+    using One = std::integral_constant<int, 1>;
+    using All = std::integral_constant<int, NT2>;
+#define NVL_ATTN_ROUND(KT0, FIRST, NT, NTL)                                             \
+    do {                                                                                \
+        issue_round_t(KT0, std::integral_constant<bool, NT>{}, NTL{});                  \
+        if (FIRST) rotate_row();                                                        \
+        do_round(KT0, NTL{});                                                           \
+    } while (0)
+#define NVL_ATTN_ROUND_OF(KT0, FIRST)                                                   \
+    do {                                                                                \
+        const bool all = NT2 > 1 && (KT0) + nvw < n_kt;                                 \
+        if (p.kv_nt) { if (all) NVL_ATTN_ROUND(KT0, FIRST, true, All); else NVL_ATTN_ROUND(KT0, FIRST, true, One); }      \
+        else { if (all) NVL_ATTN_ROUND(KT0, FIRST, false, All); else NVL_ATTN_ROUND(KT0, FIRST, false, One); }            \
+    } while (0)
+    if (vw < n_kt) NVL_ATTN_ROUND_OF(vw, true);
+    else rotate_row();                  // (a wave without a tile may still be the one that appends the new row)
+    for (int kt0 = vw + NT2 * nvw; kt0 < n_kt; kt0 += NT2 * nvw) NVL_ATTN_ROUND_OF(kt0, false);
+#undef NVL_ATTN_ROUND_OF
+#undef NVL_ATTN_ROUND
+    // append the new key/value to the slabs for the following steps — after every load of this step (which used the
+    // register copies), so the loads above are not ordered behind these stores.  The LAST two waves do it (whole waves
+    // branch around it, the block-table lookup included): tiles are dealt from wave 0 up, so the waves that carry a
+    // second tile are the first ones, and the last ones are done early.
+    constexpr int K_WAVE = NW - 1, V_WAVE = NW > 1 ? NW - 2 : 0;
+    if (FUSED && blockIdx.z == 0 && qt == 0 && (wave == K_WAVE || wave == V_WAVE)) {
         int nblk, nrow;
         kv_locate(tbl, 0, pos0, p.Tmax, nblk, nrow);
         const int64_t noff = (int64_t)nblk * p.slot_stride + ((int64_t)kvh * p.Tmax + nrow) * HD;
-        if (wave == 0 && fq == 0) {      // lanes fg = 0..3 of column 0 hold all of K_new between them
+        if (wave == K_WAVE && fq == 0) {      // lanes fg = 0..3 of column 0 hold all of K_new between them
 #pragma unroll
             for (int ks = 0; ks < KS; ks++) *(bf16x8*)((bf16_t*)p.kcache + noff + ks * 32 + fg * 8) = knew[ks];
         }
-        if (wave == 1 % NW && ksub == 0)  // lanes dch = 0..CPR-1 hold the V row: one contiguous row
+        if (wave == V_WAVE && ksub == 0)      // lanes dch = 0..CPR-1 hold the V row: one contiguous row
             *(bf16x8*)((bf16_t*)p.vcache + noff + dch * 8) = vnew8;
     }
     // ---- flash-decoding combine through LDS (the partial O^T overwrites this wave's own V image), fixed wave order ----
