@@ -185,6 +185,26 @@ enum {
 /* After nvl_set_weight_dtype(m, NVL_W_FP8_E4M3), before nvl_finalize (else NVL_ERR_STATE).  NVL_ERR_INVALID for an unknown
  * value and for NVL_ACT_FP8_E4M3 without 8-bit weights (so also with f32 precision or tensor parallelism). */
 int nvl_set_act_dtype(nvl_model* m, int dtype);
+/* Convolution window of the Mamba2 layers across calls.  The reference's Mamba2Layer.causalConv1d pads
+ * EVERY Forward call with zeros and never uses its ConvCache field (mamba2.go:27,181-254,356): a decode call convolves its
+ * one token with K-1 zeros, and so does the first token after every seam of a prompt fed in several calls.  That is the
+ * default here too (PER_CALL), so prefill(P) + decode(t) is the reference's function of its calls, not the model's
+ * function of the P + t tokens.  CARRIED makes it the latter: recommended for real hybrid checkpoints. */
+enum { NVL_MAMBA_CONV_PER_CALL = 0,   /* every call zero-pads (mamba2.go:181-254): today's behaviour */
+       NVL_MAMBA_CONV_CARRIED  = 1 }; /* the window reaches into the sequence's previous calls        */
+/* After nvl_create, before nvl_finalize (else NVL_ERR_STATE).  NVL_ERR_INVALID for a NULL model, an unknown mode and a model
+ * without Mamba2 layers.  A convolution width K of 1 is accepted and changes nothing.
+ * Contract of CARRIED: for sequence i of a call, its token at absolute position p and window element q = p - back
+ * (back = 0 .. K-1): q >= seq_pos[i] is this call's raw xBC row; 0 <= q < seq_pos[i] is the kept row of position q; q < 0
+ * is zero.  A sequence whose call starts at position 0 never reads what its slot kept (an evicted or reset slot does not
+ * leak).  After every call each of its sequences keeps the last K-1 rows of concat(old rows, or zeros at seq_pos == 0,
+ * this call's raw rows): positions before 0 are zeros in the kept rows, and a call shorter than K-1 keeps the newest old
+ * rows.  The rows are the fp32 in-projection output in both precisions.  This holds per sequence for any batch (ragged,
+ * permuted slots, prefill rows mixed with decode rows) through nvl_forward, nvl_score, nvl_runner_run*, nvl_decode_greedy
+ * and nvl_decode_sampled, graph replay included.  The SSM reset at position 0 stays; speculative calls, nvl_seq_truncate,
+ * paged and tensor-parallel hybrids stay refused.  No memory is added: the rows live in the buffer the runner's chunked
+ * prefill already used.  A decode pass pays no extra launch for it (nvl_set_tuning key 39). */
+int nvl_set_mamba_conv_state(nvl_model* m, int mode);
 /* Pre-quantized 8-bit weight, taken as it is (the dtype of nvl_load_safetensors' F8_E4M3 tensors): codes [rows][cols] OCP
  * e4m3fn in the checkpoint's [out, in] order (layout must be NVL_LAYOUT_OUT_IN), scales [rows] fp32, W~ = bf16(s * e4m3(q)).
  * Counterpart of nvl_upload_tensor (generic_loader.go:353-604) for a kind this model stores 8-bit; NVL_ERR_INVALID for any
@@ -485,6 +505,9 @@ int nvl_get_kv(nvl_model* m, int64_t seq_id, int layer, float* k_out, float* v_o
 /* Mamba2Layer.SSMState of a sequence's slot for a Mamba2 layer, [heads, head_dim, state] fp32 (mamba2.go:29-30; per
  * SEQUENCE here, per layer in the reference).  Returns the number of floats, or < 0. */
 int nvl_get_mamba_state(nvl_model* m, int64_t seq_id, int layer, float* out);
+/* The kept convolution rows of a sequence's slot for a Mamba2 layer (nvl_set_mamba_conv_state; also what the runner's chunked
+ * prefill left): [K-1][conv_dim] fp32 raw xBC rows, oldest row first.  Returns the number of floats (0 when K == 1), or < 0. */
+int nvl_get_mamba_conv_state(nvl_model* m, int64_t seq_id, int layer, float* out);
 /* Debug/parity: read a 2-D weight back from the device as the reference holds it after loading ([in, out] fp32,
  * generic_loader.go:398-403) — whatever layout the kernels keep it in.  kind = NVL_T_*; out is [in_features][out_features].
  * Available between the upload and nvl_finalize for the projections finalize fuses (Q, K, V, KV, W1, MoE-in), at any
@@ -740,7 +763,9 @@ int nvl_op_attention_mq(int device, const float* q, const float* k, const float*
  * n_seqs sequences back to back, sequence i with seq_len[i] tokens from position seq_pos[i] in state slot seq_slot[i]
  * (distinct, < n_slots).  conv_w [conv_dim][K]; conv_b, a_log, D, dt_bias, norm_w may be NULL.  state
  * [n_slots][nh][hd][ss] and tail [n_slots][K-1][conv_dim] (may be NULL) are read and written in place; chain 0 / 1 / 2 is
- * the conv tail of a chained prefill (mamba.h MambaArgs::chain), non-zero only with n_seqs == 1.  Out: xbc [M][conv_dim],
+ * the conv tail of a chained prefill (mamba.h MambaArgs::chain), non-zero only with n_seqs == 1; chain 3 is the carried window
+ * of NVL_MAMBA_CONV_CARRIED for any n_seqs (a tail is required when K > 1; with every seq_len == 1 and nvl_set_tuning key 39
+ * at 1 the pass runs mamba_conv_step_kernel).  Out: xbc [M][conv_dim],
  * delta [M][nh], y [M][EH] before gating, normed [M][EH] (bf16: the rounded out_proj operand).  A geometry the kernels do
  * not cover is NVL_ERR_INVALID, before anything is launched. */
 int nvl_op_mamba_mixer(int device, int precision, const float* proj, int n_seqs, const int32_t* seq_len,
@@ -1004,6 +1029,9 @@ int nvl_bench_gemm(int device, int M, int N, int K, int epi, int force_bnt, int 
  * multiple of 16, at least 16): the logits workspace of a scoring pass is that many rows.
  * key 38: verify passes (nvl_verify_greedy*, nvl_decode_greedy_lookup, nvl_verify_sampled*, nvl_decode_sampled_lookup) in bf16 over a bf16 cache run the multi-position
  * decode attention (1, default); 0 = rope_kv + the prefill attention kernel, the route of an nvl_forward of 1 + k rows.
+ * key 39: decode passes (one row per sequence) of a model set to NVL_MAMBA_CONV_CARRIED run the convolution, the shift of the
+ * kept rows and softplus(dt) as one launch per Mamba2 layer (1, default); 0 = the convolution kernel plus the tail kernel.  No
+ * effect in NVL_MAMBA_CONV_PER_CALL mode.
  * The settings are PROCESS-GLOBAL and unsynchronised (every model in the process sees them): set them from one thread
  * while no forward call is running.  Every call starts a new tuning epoch: captured decode graphs bake the tuning in and are re-captured.
  * Returns the previous value. */

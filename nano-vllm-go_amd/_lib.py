@@ -42,6 +42,7 @@ GQ_GROUP_SIZES = (32, 64, 128)
 GQ_EXPERT_DTYPE = {"none": 0, "uint4": 1}                # NVL_GQE_* (nvl_set_gq_expert_dtype)
 ACT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                   # NVL_ACT_AUTO / NVL_ACT_FP8_E4M3 (nvl_set_act_dtype)
 EXPERT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                # NVL_EXPERT_AUTO / NVL_EXPERT_FP8_E4M3 (nvl_set_expert_dtype)
+MAMBA_CONV_STATE = {"per_call": 0, "carried": 1}         # NVL_MAMBA_CONV_PER_CALL / NVL_MAMBA_CONV_CARRIED (nvl_set_mamba_conv_state)
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 LAYOUT_IN_OUT, LAYOUT_OUT_IN = 0, 1
 FWD_ALL_LOGITS = 1
@@ -164,6 +165,8 @@ def lib():
     L.nvl_get_hidden.argtypes = [vp, C.c_int, vp, i64]
     L.nvl_get_kv.argtypes = [vp, i64, C.c_int, vp, vp]
     L.nvl_get_mamba_state.argtypes = [vp, i64, C.c_int, vp]
+    L.nvl_set_mamba_conv_state.argtypes = [vp, C.c_int]
+    L.nvl_get_mamba_conv_state.argtypes = [vp, i64, C.c_int, vp]
     L.nvl_get_weight.argtypes = [vp, C.c_int, C.c_int, vp, i64, i64]
     L.nvl_get_stamps.argtypes = [vp, vp, C.c_int, vp, i64]
     L.nvl_runner_run.argtypes = [vp, C.c_int, vp, vp, vp, C.c_int, vp, vp]

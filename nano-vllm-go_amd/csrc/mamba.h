@@ -4,6 +4,8 @@
 //
 //   in_proj GEMM -> proj [tokens][gate EH | xBC conv_dim | dt nh]   (fp32)
 //   mamba_conv_kernel      causal conv1d + bias + SiLU on xBC, softplus(dt + bias)        mamba2.go:107-131, 183-254, 360-376
+//   mamba_tail_kernel      keeps a sequence's last K-1 raw xBC rows (chained prefill; carried window, MambaArgs::chain)
+//   mamba_conv_step_kernel the two above for a decode pass of a carried model, in one launch
 //   mamba_scan_kernel      per (sequence, head): state = abar*state + dt*B*u; y = C·state + D*u   mamba2.go:256-351
 //   mamba_gate_norm_kernel y *= SiLU(gate); RMS norm over EH (eps 1e-5); * norm weight -> out_proj operand   :135-170
 //   out_proj GEMM (+ residual)
@@ -11,8 +13,11 @@
 // State: the reference keeps SSMState ON THE LAYER (mamba2.go:29-30), i.e. one state for whatever sequence ran last —
 // wrong for more than one live sequence.  Here every KV slot (sequence) owns its state,
 // [slot][mamba layer][head][head_dim][state] fp32 in HBM, zeroed when the sequence (re)starts at position 0.
-// The reference carries NO convolution state across calls (ConvCache is never used): a decode call convolves its one
-// token with zeros.  That is mirrored — the conv window never reaches before the call's first token of a sequence.
+// The reference carries NO convolution state across calls (ConvCache, mamba2.go:27, is cleared in ResetState :356 and
+// never used; causalConv1d :181-254 zero-pads every call): a decode call convolves its one token with zeros.  That is
+// mirrored by default — the conv window never reaches before the call's first token of a sequence.  A model set to
+// NVL_MAMBA_CONV_CARRIED (nvl_set_mamba_conv_state) keeps every sequence's last K-1 raw xBC rows in its slot instead
+// (MambaArgs::chain 3): the window then reaches into the sequence's previous calls, whatever their lengths.
 #pragma once
 #include "common.h"
 
@@ -42,7 +47,10 @@ struct MambaArgs {
     // runs it as ONE Forward whose convolution window spans the whole history.  For those chunks only, the raw xBC rows of
     // the last K-1 tokens of the previous chunk are kept per (slot, Mamba2 layer) and stand in for the zero padding:
     // chain 0 = off (every other call: the reference's zero padding), 1 = first chunk (save the tail), 2 = later chunk
-    // (use the saved tail, then save the new one).
+    // (use the saved tail, then save the new one).  1 and 2 describe ONE sequence (2 reads the tail whatever seq_pos says).
+    // chain 3 = carried (NVL_MAMBA_CONV_CARRIED), any batch: per sequence, window elements before the call come from the
+    // slot's tail iff seq_pos > 0 — a sequence that starts at position 0 never reads what its slot kept — and every
+    // sequence of the call keeps the last K-1 rows of (old rows, or zeros at seq_pos == 0) ++ (this call's raw rows).
     float* tail;                   // this layer's tails: slot s at tail + s * tail_slot_stride, [K-1][conv_dim]
     int64_t tail_slot_stride;
     int chain;
@@ -67,16 +75,19 @@ __device__ __forceinline__ float softplus_ref(float x) { return x > 20.f ? x : l
 
 // grid (tokens), 256 threads over channels (+ the nh dt values)
 __global__ __launch_bounds__(256) void mamba_conv_kernel(MambaArgs p) {
-    const int t = blockIdx.x;
-    const int j = p.tok_pos[t] - p.seq_pos[p.tok_seq[t]];      // tokens of this sequence before t IN THIS CALL
+    const int t = blockIdx.x, seq = p.tok_seq[t];
+    const int j = p.tok_pos[t] - p.seq_pos[seq];                // tokens of this sequence before t IN THIS CALL
     const float* row = p.proj + (int64_t)t * p.P + p.EH;        // xBC of token t
+    // continued chunk (2) / carried window (3: only a sequence past position 0): the window reaches into the sequence's last
+    // K-1 rows before this call
+    const bool reach = p.chain == 2 || (p.chain == 3 && p.seq_pos[seq] > 0);
     for (int c = threadIdx.x; c < p.conv_dim; c += blockDim.x) {
         float sum = 0.f;
         for (int k = 0; k < p.K; k++) {                         // out[t] = sum_k x[t - (K-1) + k] * w[c][k], zero before the call
             const int back = p.K - 1 - k;
             if (back <= j) sum = fmaf(row[c - (int64_t)back * p.P], p.conv_w[(int64_t)c * p.K + k], sum);
-            else if (p.chain == 2)     // continued chunk: the window reaches into the previous chunk's last K-1 tokens
-                sum = fmaf(p.tail[(int64_t)p.seq_slot[p.tok_seq[t]] * p.tail_slot_stride + (int64_t)(p.K - 1 - (back - j)) * p.conv_dim + c],
+            else if (reach)
+                sum = fmaf(p.tail[(int64_t)p.seq_slot[seq] * p.tail_slot_stride + (int64_t)(p.K - 1 - (back - j)) * p.conv_dim + c],
                            p.conv_w[(int64_t)c * p.K + k], sum);
         }
         if (p.conv_b) sum += p.conv_b[c];
@@ -89,13 +100,14 @@ __global__ __launch_bounds__(256) void mamba_conv_kernel(MambaArgs p) {
     }
 }
 
-// grid (sequences), 256 threads over channels: after the convolution of a chunk of a chained prefill (chain >= 1), keep the
-// raw xBC rows of the sequence's last K-1 tokens for the next chunk (a chunk shorter than K-1 keeps the newest old rows).
+// grid (sequences), 256 threads over channels: after the convolution of a chunk of a chained prefill (chain 1 / 2) or of
+// any call of a carried model (chain 3), keep the raw xBC rows of the sequence's last K-1 tokens for the next call (a call
+// shorter than K-1 keeps the newest old rows).
 __global__ __launch_bounds__(256) void mamba_tail_kernel(MambaArgs p) {
     const int seq = blockIdx.x;
     const int t0 = p.seq_tok_start[seq], n = p.seq_len[seq];
     float* tl = p.tail + (int64_t)p.seq_slot[seq] * p.tail_slot_stride;
-    const bool have_old = p.chain == 2 && p.seq_pos[seq] > 0;
+    const bool have_old = p.chain >= 2 && p.seq_pos[seq] > 0;
     for (int c = threadIdx.x; c < p.conv_dim; c += blockDim.x) {
         float old[8], nw[8];
         for (int i = 0; i < p.K - 1; i++) old[i] = have_old ? tl[(int64_t)i * p.conv_dim + c] : 0.f;
@@ -105,6 +117,60 @@ __global__ __launch_bounds__(256) void mamba_tail_kernel(MambaArgs p) {
         }
         for (int i = 0; i < p.K - 1; i++) tl[(int64_t)i * p.conv_dim + c] = nw[i];
     }
+}
+
+// The decode step of a carried model (chain 3, every sequence of the pass has ONE row): convolution, tail shift and the
+// softplus(dt + bias) rows in one launch, so that the option costs a decode step no launch per Mamba2 layer.
+// grid (cdiv(conv_dim / 4 + nh, 64), sequences), 64 threads.  A thread owns four neighbouring channels of one sequence end
+// to end — the K-1 tail rows in registers, as mamba_tail_kernel has them — or one dt value; no two threads touch the same
+// tail element, and two rows of a pass never share a slot.  The channels are spread over the grid (conv_kernel spends one
+// workgroup on a whole row: at B = 1 that is 3-7 K channels through one workgroup).  conv_dim % 4 == 0 follows from
+// mamba_geometry_ok (EH = nh x hd is a multiple of 64, state = SG x PER with PER >= 4), so the tail, xbc, bias and the
+// four channels' K weights are 16-byte accesses; the raw row is one too where the row stride P keeps it aligned (nh % 4
+// == 0), four scalar loads otherwise.  Same arithmetic as mamba_conv_kernel: fmaf over k ascending, bias, silu_ref.
+// Slots, positions and tails are read from device memory: nothing of the pass is in the arguments (graph replay).
+template <int K>
+__global__ __launch_bounds__(64) void mamba_conv_step_kernel(MambaArgs p) {
+    const int seq = blockIdx.y;
+    const int t = p.seq_tok_start[seq];                         // the sequence's one row
+    const int i = blockIdx.x * 64 + threadIdx.x, quads = p.conv_dim >> 2;
+    if (i >= quads) {
+        const int h = i - quads;
+        if (h < p.nh) {
+            float v = p.proj[(int64_t)t * p.P + p.EH + p.conv_dim + h];
+            if (p.dt_bias) v += p.dt_bias[h];
+            p.delta[(int64_t)t * p.nh + h] = softplus_ref(v);
+        }
+        return;
+    }
+    const int c = i * 4;
+    const float* row = p.proj + (int64_t)t * p.P + p.EH + c;
+    f32x4 x;
+    if ((p.P & 3) == 0) x = *(const f32x4*)row;                 // (EH % 4 == 0: the row start decides)
+    else x = f32x4{row[0], row[1], row[2], row[3]};
+    float* tl = p.tail + (int64_t)p.seq_slot[seq] * p.tail_slot_stride + c;
+    const bool have_old = p.seq_pos[seq] > 0;                   // a sequence that (re)starts never reads what its slot kept
+    f32x4 win[K];                                               // window rows, oldest first; win[K-1] = this token
+#pragma unroll
+    for (int k = 0; k < K - 1; k++) win[k] = have_old ? *(const f32x4*)(tl + (int64_t)k * p.conv_dim) : f32x4{0.f, 0.f, 0.f, 0.f};
+    win[K - 1] = x;
+    float w[4 * K];                                             // conv_w[c + r][k] = w[r * K + k]
+#pragma unroll
+    for (int q = 0; q < K; q++) {
+        const f32x4 v = *(const f32x4*)(p.conv_w + (int64_t)c * K + 4 * q);
+        w[4 * q] = v[0]; w[4 * q + 1] = v[1]; w[4 * q + 2] = v[2]; w[4 * q + 3] = v[3];
+    }
+    f32x4 sum = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+    for (int k = 0; k < K; k++)
+#pragma unroll
+        for (int r = 0; r < 4; r++) sum[r] = fmaf(win[k][r], w[r * K + k], sum[r]);
+    if (p.conv_b) sum += *(const f32x4*)(p.conv_b + c);
+#pragma unroll
+    for (int r = 0; r < 4; r++) sum[r] = silu_ref(sum[r]);
+    *(f32x4*)(p.xbc + (int64_t)t * p.conv_dim + c) = sum;
+#pragma unroll
+    for (int k = 0; k < K - 1; k++) *(f32x4*)(tl + (int64_t)k * p.conv_dim) = win[k + 1];      // the shifted tail
 }
 
 // grid (nh, sequences), 256 threads = head_dim x SG state groups; PER = ss / SG states per thread in registers.

@@ -189,8 +189,9 @@ struct nvl_model {
     int n_mamba = 0, mEH = 0, mConv = 0, mP = 0, m_nh = 0, m_hd = 0, m_ss = 0, m_ng = 0, m_K = 0;
     float* ssm_state = nullptr; int64_t ssm_layer_stride = 0, ssm_slot_stride = 0;
     float *mproj = nullptr, *mxbc = nullptr, *mdelta = nullptr, *my = nullptr; void* myn = nullptr;
-    float* conv_tail = nullptr; int64_t conv_tail_layer_stride = 0, conv_tail_slot_stride = 0;   // chunked prefill only (mamba.h MambaArgs::chain)
+    float* conv_tail = nullptr; int64_t conv_tail_layer_stride = 0, conv_tail_slot_stride = 0;   // chunked prefill, or every call of a carried model (mamba.h MambaArgs::chain)
     int conv_chain = 0;          // set by runner_impl around the chunks of one long history
+    bool conv_carried = false;   // nvl_set_mamba_conv_state(NVL_MAMBA_CONV_CARRIED): every pass runs chain 3
     float *ssd_z = nullptr, *ssd_decay = nullptr; int64_t ssd_z_floats = 0, ssd_decay_floats = 0;   // chunk-parallel SSD scan scratch (mamba.h)
     SampleBufs samp;             // nvl_sample scratch
     LogprobBufs lpb;             // nvl_logprobs / nvl_score scratch

@@ -1144,6 +1144,16 @@ extern "C" int nvl_set_act_dtype(nvl_model* m, int dtype) {
     return NVL_OK;
 }
 
+extern "C" int nvl_set_mamba_conv_state(nvl_model* m, int mode) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mamba_conv_state: no model");
+    if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_set_mamba_conv_state: call it before nvl_finalize");
+    if (mode != NVL_MAMBA_CONV_PER_CALL && mode != NVL_MAMBA_CONV_CARRIED)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_mamba_conv_state: unknown mode");
+    if (!m->n_mamba) return fail(m, NVL_ERR_INVALID, "nvl_set_mamba_conv_state: the model has no Mamba2 layers");
+    m->conv_carried = mode == NVL_MAMBA_CONV_CARRIED;      // (K == 1: no tail, nothing to carry — accepted, changes nothing)
+    return NVL_OK;
+}
+
 extern "C" int nvl_finalize(nvl_model* m) {
     if (!m) return NVL_ERR_INVALID;
     if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_finalize: already finalized");
@@ -1921,6 +1931,8 @@ static int g_moe_fused_route = 1;   // nvl_set_tuning key 31: MoE decode routing
 static int g_moe_small = 1;    // nvl_set_tuning key 8: fused MoE planning launch + combine folded into the next norm (0 = off)
 static int g_mamba_ssd = 1;    // nvl_set_tuning key 30: chunked (SSD) Mamba2 scan on MFMA for prefill-sized bf16 calls (0 = the sequential scan,
                                // 2 = chunk after chunk only, never the chunk-parallel three-launch form)
+static int g_mamba_conv_step = 1;   // nvl_set_tuning key 39: decode passes of a carried model (NVL_MAMBA_CONV_CARRIED) run mamba_conv_step_kernel
+                                    // (0 = mamba_conv_kernel + mamba_tail_kernel)
 static int g_decode_seam = 1;  // nvl_set_tuning key 7: decode_seam_kernel in nvl_decode_greedy (0 = separate kernels)
 static int g_sk_slices = 0;    // tuning override (nvl_set_tuning key 1): 0 automatic, 1 = never split
 // consumer side of the deferred RMSNorm: the projection reads xn_raw and scales its accumulators (gemm.h)
@@ -2380,11 +2392,33 @@ void head_proj(nvl_model* m, bool xn_deferred, const int32_t* rows_idx, int rows
 // (nvl_op_mamba_mixer) receives the scan's y before the gate kernel overwrites it in place.
 void mamba_mixer(nvl_model* m, MambaArgs a, int M, int n_seqs, int max_len, void* out, float* y_pre = nullptr) {
     const int64_t state_floats = (int64_t)a.nh * a.hd * a.ss;
-    {
-        KScope ks(m, KC_OTHER, 0, KS_MAMBA_CONV, (double)M * (a.P + a.conv_dim + a.nh) * 4.0);
-        hipLaunchKernelGGL(mamba_conv_kernel, dim3(M), dim3(256), 0, m->stream, a);
-        if (a.chain) hipLaunchKernelGGL(mamba_tail_kernel, dim3(n_seqs), dim3(256), 0, m->stream, a);
+    const double tail_bytes = a.chain ? 2.0 * n_seqs * (double)(a.K - 1) * a.conv_dim * 4.0 : 0.0;
+    if (a.chain == 3 && max_len == 1 && g_mamba_conv_step) {
+        // a decode pass of a carried model: conv, tail shift and softplus in one launch (mamba.h mamba_conv_step_kernel)
+        KScope ks(m, KC_OTHER, 0, KS_MAMBA_CONV, (double)M * (a.P + a.conv_dim + a.nh) * 4.0 + tail_bytes);
+        const dim3 grid(cdiv(a.conv_dim / 4 + a.nh, 64), n_seqs);
+        switch (a.K) {     // (K == 1 has no tail and so no chain)
+            case 2: hipLaunchKernelGGL(mamba_conv_step_kernel<2>, grid, dim3(64), 0, m->stream, a); break;
+            case 3: hipLaunchKernelGGL(mamba_conv_step_kernel<3>, grid, dim3(64), 0, m->stream, a); break;
+            case 4: hipLaunchKernelGGL(mamba_conv_step_kernel<4>, grid, dim3(64), 0, m->stream, a); break;
+            case 5: hipLaunchKernelGGL(mamba_conv_step_kernel<5>, grid, dim3(64), 0, m->stream, a); break;
+            case 6: hipLaunchKernelGGL(mamba_conv_step_kernel<6>, grid, dim3(64), 0, m->stream, a); break;
+            case 7: hipLaunchKernelGGL(mamba_conv_step_kernel<7>, grid, dim3(64), 0, m->stream, a); break;
+            case 8: hipLaunchKernelGGL(mamba_conv_step_kernel<8>, grid, dim3(64), 0, m->stream, a); break;
+            default: throw std::runtime_error("mamba_mixer: a carried conv window needs 2 <= K <= 8");
+        }
         NVL_HIP(hipGetLastError());
+    } else {
+        {
+            KScope ks(m, KC_OTHER, 0, KS_MAMBA_CONV, (double)M * (a.P + a.conv_dim + a.nh) * 4.0);
+            hipLaunchKernelGGL(mamba_conv_kernel, dim3(M), dim3(256), 0, m->stream, a);
+            NVL_HIP(hipGetLastError());
+        }
+        if (a.chain) {     // (a launch of its own in the per-site profile)
+            KScope ks(m, KC_OTHER, 0, KS_MAMBA_CONV, tail_bytes);
+            hipLaunchKernelGGL(mamba_tail_kernel, dim3(n_seqs), dim3(256), 0, m->stream, a);
+            NVL_HIP(hipGetLastError());
+        }
     }
     {
         KScope ks(m, KC_OTHER, 2.0 * 3.0 * (double)M * a.EH * a.ss, KS_MAMBA_SCAN,
@@ -2519,7 +2553,8 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
             a.state = m->ssm_state + (int64_t)l.mamba_idx * m->ssm_layer_stride; a.state_slot_stride = m->ssm_slot_stride;
             a.tok_pos = md.tok_pos; a.tok_seq = md.tok_tbl; a.seq_tok_start = md.seq_tok_start; a.seq_len = md.seq_len;
             a.seq_pos = md.seq_pos; a.seq_slot = md.blk_table;     // slab mode: token -> sequence index i, blk_table[i] = slot
-            a.chain = m->conv_tail ? m->conv_chain : 0;
+            // a carried model runs every pass as chain 3; the runner's chunk loop (conv_chain 1 / 2) is then a special case of it
+            a.chain = m->conv_tail ? (m->conv_carried ? 3 : m->conv_chain) : 0;
             a.tail = m->conv_tail ? m->conv_tail + (int64_t)l.mamba_idx * m->conv_tail_layer_stride : nullptr;
             a.tail_slot_stride = m->conv_tail_slot_stride;
             mamba_mixer(m, a, M, n_seqs, max_len, m->myn);
@@ -3868,6 +3903,21 @@ extern "C" int nvl_get_mamba_state(nvl_model* m, int64_t seq_id, int layer, floa
     const float* src = m->ssm_state + (int64_t)it->second * m->ssm_slot_stride + (int64_t)m->layers[(size_t)layer].mamba_idx * m->ssm_layer_stride;
     NVL_HIP(hipMemcpy(out, src, (size_t)m->ssm_layer_stride * 4, hipMemcpyDeviceToHost));
     return (int)m->ssm_layer_stride;
+    NVL_CATCH(m)
+}
+
+extern "C" int nvl_get_mamba_conv_state(nvl_model* m, int64_t seq_id, int layer, float* out) {
+    if (!m || !out) return NVL_ERR_INVALID;
+    auto it = m->seq_slot.find(seq_id);
+    if (it == m->seq_slot.end()) return fail(m, NVL_ERR_UNKNOWN_SEQ, "nvl_get_mamba_conv_state: unknown sequence");
+    if (layer < 0 || layer >= m->L || !m->layers[(size_t)layer].mamba) return fail(m, NVL_ERR_INVALID, "nvl_get_mamba_conv_state: not a Mamba2 layer");
+    if (!m->conv_tail) return 0;       // K == 1: the window is the token itself
+    NVL_TRY(m)
+    NVL_HIP(hipSetDevice(m->device));
+    NVL_HIP(hipStreamSynchronize(m->stream));
+    const float* src = m->conv_tail + (int64_t)it->second * m->conv_tail_slot_stride + (int64_t)m->layers[(size_t)layer].mamba_idx * m->conv_tail_layer_stride;
+    NVL_HIP(hipMemcpy(out, src, (size_t)m->conv_tail_layer_stride * 4, hipMemcpyDeviceToHost));
+    return (int)m->conv_tail_layer_stride;
     NVL_CATCH(m)
 }
 

@@ -287,8 +287,8 @@ extern "C" int nvl_op_mamba_mixer(int device, int precision, const float* proj, 
     if (!proj || !seq_len || !seq_pos || !seq_slot || !conv_w || !state || !xbc || !delta || !y || !normed || n_seqs <= 0 || n_slots <= 0)
         return op_fail("nvl_op_mamba_mixer: bad arguments");
     if (!mamba_geometry_ok(nh, hd, ss, ng, K)) return op_fail("nvl_op_mamba_mixer: head_dim / state_size / groups / conv kernel not supported by the kernels");
-    if (chain < 0 || chain > 2 || (chain && (n_seqs != 1 || (K > 1 && !tail))))
-        return op_fail("nvl_op_mamba_mixer: a chained prefill is one sequence with a tail");
+    if (chain < 0 || chain > 3 || (chain && ((chain != 3 && n_seqs != 1) || (K > 1 && !tail))))
+        return op_fail("nvl_op_mamba_mixer: a chained prefill (chain 1 / 2) is one sequence with a tail; a carried window (chain 3) needs a tail");
     int64_t M64 = 0;
     int max_len = 0;
     std::vector<char> used((size_t)n_slots, 0);
@@ -1559,6 +1559,7 @@ extern "C" int nvl_set_tuning(int key, int value) {
     if (key == 35) { const int old = g_attn_kv_nt; g_attn_kv_nt = value; return old; }
     if (key == 36) { const int old = g_wide_ntb; g_wide_ntb = value; return old; }
     if (key == 38) { const int old = g_verify_mq; g_verify_mq = value; return old; }
+    if (key == 39) { const int old = g_mamba_conv_step; g_mamba_conv_step = value; return old; }
     if (key == 37) { const int old = g_score_rows; g_score_rows = value < 16 ? 16 : (value + 15) / 16 * 16; return old; }
     return -1;
 }

@@ -49,7 +49,7 @@ class HipTransformerModel:
                  kv_cache_dtype: str = "auto", kv_scales=None, weight_dtype: str = "auto",
                  act_dtype: str = "auto", expert_dtype: str = "auto", mx_weight_dtype: str = "none",
                  mx_expert_dtype: str = "none", mx_head_dtype: str = "none", gq_weight_dtype: str = "none",
-                 gq_group_size: int = 128, gq_expert_dtype: str = "none"):
+                 gq_group_size: int = 128, gq_expert_dtype: str = "none", mamba_conv_state: str = "per_call"):
         """tensors=None defers finalize(): upload() each tensor, then call finalize().
         tp_size > 1 makes this the tp_rank-th tensor-parallel shard: pass the FULL tensors, the library keeps
         its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests).
@@ -74,7 +74,10 @@ class HipTransformerModel:
         and the MoE experts stay bf16.  The model computes with W~ = bf16(s * (q - z)), which get_weight returns.
         gq_expert_dtype="uint4" (needs gq_weight_dtype="uint4", a MoE model whose hidden and expert widths are multiples of
         gq_group_size): the experts' weights are INT4 too, one scale and zero point per gq_group_size input features of an
-        (expert, output row) (nvl_set_gq_expert_dtype)."""
+        (expert, output row) (nvl_set_gq_expert_dtype).
+        mamba_conv_state="carried" (a hybrid model): the Mamba2 convolution window reaches into the sequence's previous
+        calls, so feeding a sequence in one call or token by token gives the same logits (nvl_set_mamba_conv_state);
+        "per_call" (default) zero-pads every call as the reference does (mamba2.go:181-254)."""
         self.cfg = dict(cfg)
         self.lib = L.lib()
         self.h = C.c_void_p()
@@ -122,6 +125,8 @@ class HipTransformerModel:
             raise ValueError(f"gq_expert_dtype must be one of {sorted(L.GQ_EXPERT_DTYPE)}")
         if gq_expert_dtype != "none" and gq_weight_dtype != "uint4":
             raise ValueError('gq_expert_dtype="uint4" needs gq_weight_dtype="uint4"')
+        if mamba_conv_state not in L.MAMBA_CONV_STATE:
+            raise ValueError(f"mamba_conv_state must be one of {sorted(L.MAMBA_CONV_STATE)}")
         L.check(self.lib.nvl_create(C.byref(self._c), C.byref(opts), C.byref(self.h)))
         self.weight_dtype = weight_dtype
         self.gq_weight_dtype = gq_weight_dtype
@@ -148,6 +153,13 @@ class HipTransformerModel:
             if value in ("auto", "none"):
                 continue
             rc = setter(self.h, table[value])
+            if rc < 0:
+                msg = self.lib.nvl_last_error(self.h)
+                self.close()
+                raise L.NvlError(rc, msg.decode() if msg else "")
+        self.mamba_conv_state = mamba_conv_state
+        if mamba_conv_state != "per_call":
+            rc = self.lib.nvl_set_mamba_conv_state(self.h, L.MAMBA_CONV_STATE[mamba_conv_state])
             if rc < 0:
                 msg = self.lib.nvl_last_error(self.h)
                 self.close()
@@ -668,6 +680,14 @@ class HipTransformerModel:
         hd = c.get("mamba_head_dim") or c["mamba_expand"] * c["hidden"] // c["mamba_num_heads"]
         out = np.empty((c["mamba_num_heads"], hd, c["mamba_state_size"]), np.float32)
         L.check(self.lib.nvl_get_mamba_state(self.h, seq_id, layer, _ptr(out)), self.h)
+        return out
+
+    def get_mamba_conv_state(self, seq_id: int, layer: int):
+        """The raw xBC rows of the sequence's last K-1 positions kept for a Mamba2 layer, [K-1, conv_dim], oldest first."""
+        c = self.cfg
+        conv_dim = c["mamba_expand"] * c["hidden"] + 2 * c["mamba_n_groups"] * c["mamba_state_size"]
+        out = np.empty((c["mamba_conv_kernel"] - 1, conv_dim), np.float32)
+        L.check(self.lib.nvl_get_mamba_conv_state(self.h, seq_id, layer, _ptr(out)), self.h)
         return out
 
     def get_kv(self, seq_id: int, layer: int):

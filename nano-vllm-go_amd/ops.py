@@ -86,7 +86,8 @@ def mamba_mixer(proj, seq_len, seq_pos, seq_slot, state, nh, hd, ss, ng, K, conv
                 dt_bias=None, norm_w=None, tail=None, chain=0, precision="bf16", device=0):   # mamba2.go:107-170
     """The Mamba2 mixer between its projections through the model's dispatch (csrc/mamba.h): proj [M][EH + conv_dim + nh],
     sequence i = seq_len[i] rows from position seq_pos[i] in slot seq_slot[i] of state [n_slots][nh][hd][ss] (and of tail
-    [n_slots][K-1][conv_dim]).  -> dict(xbc, delta, y (before gating), normed, state, tail); state / tail are new arrays."""
+    [n_slots][K-1][conv_dim]).  chain: 0 zero padding, 1 / 2 a chained prefill of one sequence, 3 the carried window of
+    NVL_MAMBA_CONV_CARRIED for any batch (csrc/mamba.h MambaArgs::chain).  -> dict(xbc, delta, y (before gating), normed, state, tail); state / tail are new arrays."""
     proj, conv_w = _f(proj), _f(conv_w)
     opt = [None if v is None else _f(v) for v in (conv_b, a_log, D, dt_bias, norm_w)]
     sl, sp, so = (np.ascontiguousarray(v, dtype=np.int32) for v in (seq_len, seq_pos, seq_slot))
