@@ -29,6 +29,7 @@
 #include <stdexcept>
 #include <type_traits>
 #include "common.h"
+#include "wfmt.h"
 
 namespace nvl {
 
@@ -640,8 +641,7 @@ __device__ __forceinline__ bf16x8 w8_frag(u32x2 c, float s) {
     }
     return o;
 }
-// weight formats of the decode bodies below (gemm_skinny_body / gemm_skinny_wide_body)
-enum { WF_BF16 = 0, WF_FP8 = 1, WF_MXFP4 = 2, WF_INT4 = 3 };
+// weight formats of the decode bodies below (gemm_skinny_body / gemm_skinny_wide_body): wfmt.h WF_*
 // MXFP4 (w4.h): eight e2m1 codes of one weight row (4 bytes, even k in the low nibble) and the e8m0 byte E of
 // their 32-k block -> the bf16 MFMA fragment of W~ = +-grid[q] * 2^(E - 127).  2^(E - 127) is the fp32 with exponent field E
 // (E in [7, 252]: a normal number), and the product is exact in bf16: v_cvt_scalef32_pk_bf16_fp4 rounds nothing.

@@ -26,8 +26,8 @@ namespace nvl {
 
 struct DevTensor {
     void* p = nullptr;      // canonical device copy: 2-D [rows_pad][cols] in weight dtype, 1-D fp32
-    void* qs = nullptr;     // quantized weights (wf != WF_BF16): p holds the codes, qs their scales in the format's layout (wq.h)
-    int wf = WF_BF16;       // stored format (gemm.h WF_*; INT4: with its group size, wq.h wf_int4)
+    void* qs = nullptr;     // quantized weights (wf != WF_BF16): p holds the codes, qs their scales in the format's layout (wfmt.h)
+    int wf = WF_BF16;       // stored format (wfmt.h WF_*; INT4: with its group size, wf_int4)
     int64_t rows = 0, cols = 0, rows_pad = 0;
     bool present() const { return p != nullptr; }
 };
@@ -40,10 +40,11 @@ struct LayerW {
     void* qs_qkv = nullptr; void* qs1 = nullptr;   // quantized weights: the scales of w_qkv / w1 (they follow the fused rows / 16-row tiles)
     void* moe_in = nullptr;              // [E][2I (interleaved in bf16 mode)][H]
     void* moe_out_cat = nullptr;         // bf16: W_down of all experts along K, [H_pad][E*I] (decode "dense-masked" form)
-    // quantized experts (nvl_set_expert_dtype / nvl_set_mx_expert_dtype): moe_in holds codes in the same interleaved order,
-    // qs_moe_in its scales; moe_out_q the down codes over K = E*I, [H_pad][E*I] (the layout of moe_out_cat: moe_out_cat =
-    // moe_out_q when the decode form applies), qs_moe_out its scales — fp8: [E][H_pad], one row per expert; MXFP4:
-    // [H_pad/16][E*I/32][16], beside the code tiles
+    // quantized experts (nvl_set_expert_dtype / nvl_set_mx_expert_dtype / nvl_set_gq_expert_dtype): moe_in holds codes in the
+    // same interleaved order, qs_moe_in its scales; moe_out_q the down codes over K = E*I, [H_pad][E*I] (the layout of
+    // moe_out_cat: moe_out_cat = moe_out_q when the decode form applies), qs_moe_out its scales (wq.h wf_down_scale_dims) —
+    // fp8: [E][H_pad], one row per expert; MXFP4: [H_pad/16][E*I/32][16] bytes, beside the code tiles; INT4:
+    // [H_pad/16][E*I/g][16] group words, beside the code tiles too
     void* qs_moe_in = nullptr;
     void* moe_out_q = nullptr; void* qs_moe_out = nullptr;
     bool mamba = false;                  // a Mamba2 block (attention tensors absent); index among the Mamba2 layers
@@ -102,9 +103,10 @@ struct nvl_model {
     int kv_esize = 2;                      // bytes per cached K/V element (wsize, or 1 in 8-bit mode)
     std::vector<float> k_scale, v_scale;   // [num_layers], default 1 (Mamba2 layers' entries unused)
     bool kv_written = false;               // a forward has been enqueued: the scales are fixed from then on
-    // quantized weights (wq.h): the stored format of the projections (nvl_set_weight_dtype: WF_FP8, nvl_set_mx_weight_dtype:
-    // WF_MXFP4, nvl_set_gq_weight_dtype: wq.h wf_int4(g), WF_INT4 with its group size), of the MoE experts (nvl_set_expert_dtype / nvl_set_mx_expert_dtype / nvl_set_gq_expert_dtype; WF_BF16 or the projections' format, INT4 with the same group size) and
-    // of the MXFP4 LM head / tied embedding (nvl_set_mx_head_dtype; WF_BF16 or WF_MXFP4 — the fp8 head follows wf itself)
+    // quantized weights: the stored format of the projections (wf), of the MoE experts (ef: WF_BF16 or wf itself, INT4 with the
+    // same group size) and of the MXFP4 LM head / tied embedding (hf: WF_BF16 or WF_MXFP4 — the fp8 head follows wf itself).
+    // Only the nvl_set_*_dtype entry points write them, and only as wfmt.h's wf_decide() answers: the rules of every setter are
+    // there, once.  What differs by format after that is a wf_* function of wfmt.h (host facts) or wq.h (launches)
     int wf = nvl::WF_BF16, ef = nvl::WF_BF16, hf = nvl::WF_BF16;
     bool w2d_uploaded = false;             // a 2-D tensor has been uploaded: the weight dtype is fixed from then on
     bool expert_uploaded = false;          // an expert tensor has been uploaded: the expert dtype is fixed from then on

@@ -441,19 +441,10 @@ namespace {
 // the quantized format this 2-D kind is stored in (wq.h wf_covers), or WF_BF16
 int q_kind(const nvl_model* m, int kind) { return wf_covers(m->wf, m->ef, m->hf, kind, m->cfg.tied_embedding != 0) ? m->wf : WF_BF16; }
 
-// the scales of `rows` rows of K inputs, every one the pad value of the format: fp32 1.0, the e8m0 byte 127 (2^0), or the
-// INT4 group word {s = 1, z = 0}
+// the scales of `rows` rows of K inputs, every one the pad value of the format (wq.h wf_fill_pad_scales)
 void* q_alloc_scales(nvl_model* m, int wf, int64_t rows, int64_t K) {
     void* qs = dmalloc_bytes(wf_scale_bytes(wf, rows, K));
-    if (wf == WF_MXFP4) {
-        NVL_HIP(hipMemsetAsync(qs, 127, (size_t)wf_scale_bytes(wf, rows, K), m->stream));
-    } else if (wf_base(wf) == WF_INT4) {
-        const std::vector<uint32_t> pad((size_t)(wf_scale_bytes(wf, rows, K) / 4), W4G_PAD_WORD);
-        NVL_HIP(hipMemcpy(qs, pad.data(), pad.size() * 4, hipMemcpyHostToDevice));
-    } else {
-        const std::vector<float> ones((size_t)rows, 1.0f);
-        NVL_HIP(hipMemcpy(qs, ones.data(), (size_t)rows * 4, hipMemcpyHostToDevice));   // (synchronous: `ones` is pageable and local)
-    }
+    wf_fill_pad_scales(m->stream, wf, qs, rows, K);
     return qs;
 }
 
@@ -472,7 +463,7 @@ double q_bytes(const DevTensor& t) { return (double)wf_code_bytes(t.wf, t.rows_p
 // device, then the format's quantizer -> codes + scales in its device layout (w8.h / w4.h)
 void upload_2d_q(nvl_model* m, DevTensor* t, int wf, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out) {
     if (K % 32 != 0) throw std::runtime_error(std::string(wf_name(wf)) + " weights: the input width must be a multiple of 32");
-    if (wf_base(wf) == WF_INT4 && K % wf_group(wf) != 0) throw std::runtime_error("INT4 weights: the input width must be a multiple of the group size");
+    if (K % wf_in_multiple(wf) != 0) throw std::runtime_error(std::string(wf_name(wf)) + " weights: the input width must be a multiple of the group size");
     const size_t esz = dtype == NVL_DTYPE_F32 ? 4 : 2;
     void* raw = dmalloc_bytes(N * K * (int64_t)esz);
     NVL_HIP(hipMemcpyAsync(raw, data, (size_t)(N * K) * esz, hipMemcpyDefault, m->stream));
@@ -483,12 +474,7 @@ void upload_2d_q(nvl_model* m, DevTensor* t, int wf, const void* data, int dtype
     q_alloc(m, t, wf, N, K);
     int* bad = dmalloc<int>(1);
     NVL_HIP(hipMemsetAsync(bad, 0, 4, m->stream));
-    if (wf_base(wf) == WF_INT4)
-        hipLaunchKernelGGL(w4g_quant_rows_kernel, dim3((unsigned)N), dim3(64), 0, m->stream, (const float*)f, K, wf_gshift(wf), (uint8_t*)t->p, (uint32_t*)t->qs, bad);
-    else if (wf == WF_MXFP4)
-        hipLaunchKernelGGL(w4_quant_rows_kernel, dim3((unsigned)N), dim3(64), 0, m->stream, (const float*)f, K, (uint8_t*)t->p, (uint8_t*)t->qs, bad);
-    else
-        hipLaunchKernelGGL(w8_quant_rows_kernel, dim3((unsigned)N), dim3(256), 0, m->stream, (const float*)f, K, (uint8_t*)t->p, (float*)t->qs, bad);
+    wf_quant_rows(m->stream, wf, f, N, K, t->p, t->qs, bad);
     NVL_HIP(hipGetLastError());
     int h_bad = 0;
     NVL_HIP(hipMemcpyAsync(&h_bad, bad, 4, hipMemcpyDeviceToHost, m->stream));
@@ -496,8 +482,7 @@ void upload_2d_q(nvl_model* m, DevTensor* t, int wf, const void* data, int dtype
     dfree(bad); dfree(f); dfree(raw);
     if (h_bad) {
         dfree(t->p); dfree(t->qs); t->p = t->qs = nullptr;
-        throw std::runtime_error(std::string("nvl_upload_tensor: a weight is not finite (") + wf_name(wf) + " weights refuse NaN / Inf" +
-                                 (wf_base(wf) == WF_INT4 ? ", and a group whose scale exceeds the fp16 range)" : ")"));
+        throw std::runtime_error(std::string("nvl_upload_tensor: a weight is not finite (") + wf_name(wf) + " weights refuse " + wf_quant_refuses(wf) + ")");
     }
     m->stats.weight_bytes += q_bytes(*t);
 }
@@ -566,6 +551,23 @@ int64_t full_in(const nvl_model* m, int kind) {
         default: return m->H;
     }
 }
+// the shape [out][in] an upload of a 2-D kind must have, whole (unsharded): the token embedding [V][H]; the experts of a layer
+// [E * out][in], gate | up rows [2F][H] or down rows [H][F] per expert (per_expert: one expert's out); a weight its
+// full_out x full_in (out < 0: not a 2-D weight kind)
+void expected_2d_shape(const nvl_model* m, int kind, int64_t* out, int64_t* in, int64_t* per_expert = nullptr) {
+    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {
+        const int64_t one = kind == NVL_T_MOE_IN ? 2 * (int64_t)m->F : m->H;
+        if (per_expert) *per_expert = one;
+        *out = m->cfg.num_experts * one;
+        *in = kind == NVL_T_MOE_IN ? m->H : m->F;
+    } else if (kind == NVL_T_TOK_EMB) { *out = m->V; *in = m->H; }
+    else { *out = full_out(m, kind); *in = full_in(m, kind); }
+}
+// one whole 2-D tensor in the format its kind is stored in (the setters refuse tensor parallelism for the quantized ones)
+void upload_2d_whole(nvl_model* m, DevTensor* t, int kind, const void* data, int dtype, int64_t N, int64_t K, bool src_is_in_out) {
+    if (q_kind(m, kind)) upload_2d_q(m, t, q_kind(m, kind), data, dtype, N, K, src_is_in_out);
+    else upload_2d(m, t, data, dtype, N, K, src_is_in_out, Slice2D{N, K, 0, 0, 0}, N, true);
+}
 
 }  // namespace
 
@@ -617,23 +619,20 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
             return fail(m, NVL_ERR_INVALID, buf);
         }
         m->w2d_uploaded = true;
-        if (q_kind(m, kind)) upload_2d_q(m, t, q_kind(m, kind), data, dtype, rows, cols, false);
-        else upload_2d(m, t, data, dtype, rows, cols, false, Slice2D{rows, cols, 0, 0, 0}, rows, true);
+        upload_2d_whole(m, t, kind, data, dtype, rows, cols, false);
         return NVL_OK;
     }
     if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {
-        const int64_t E = m->cfg.num_experts;
-        const int64_t out = kind == NVL_T_MOE_IN ? 2 * (int64_t)m->F : m->H;
-        const int64_t in = kind == NVL_T_MOE_IN ? m->H : m->F;
-        if (rows != E * out || cols != in) {
+        int64_t out, in, one;
+        expected_2d_shape(m, kind, &out, &in, &one);
+        if (rows != out || cols != in) {
             snprintf(buf, sizeof buf, "MoE tensor shape [%lld,%lld] does not match [E*%lld,%lld]", (long long)rows,
-                     (long long)cols, (long long)out, (long long)in);
+                     (long long)cols, (long long)one, (long long)in);
             return fail(m, NVL_ERR_INVALID, buf);
         }
         m->w2d_uploaded = true;
         m->expert_uploaded = true;
-        if (q_kind(m, kind)) upload_2d_q(m, t, q_kind(m, kind), data, dtype, rows, cols, false);     // scales per (expert, output row)
-        else upload_2d(m, t, data, dtype, rows, cols, false, Slice2D{rows, cols, 0, 0, 0}, rows, true);
+        upload_2d_whole(m, t, kind, data, dtype, rows, cols, false);     // (quantized: scales per (expert, output row))
         return NVL_OK;
     }
     if (kind >= NVL_T_MAMBA_IN_PROJ && !m->n_mamba) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor: the model has no Mamba2 layers");
@@ -648,12 +647,8 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
     }
     const bool io = layout == NVL_LAYOUT_IN_OUT;
     m->w2d_uploaded = true;
-    if (q_kind(m, kind)) {     // (tp == 1: the weight dtype setters refuse tensor parallelism)
-        upload_2d_q(m, t, q_kind(m, kind), data, dtype, SN, SK, io);
-        return NVL_OK;
-    }
-    if (m->tp == 1) {
-        upload_2d(m, t, data, dtype, SN, SK, io, Slice2D{SN, SK, 0, 0, 0}, SN, true);
+    if (q_kind(m, kind) || m->tp == 1) {     // (a quantized kind: tp == 1, the weight dtype setters refuse tensor parallelism)
+        upload_2d_whole(m, t, kind, data, dtype, SN, SK, io);
         return NVL_OK;
     }
     // ---- tensor-parallel shard of the uploaded FULL tensor ----
@@ -682,121 +677,61 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
     NVL_CATCH(m)
 }
 
-// The pre-quantized uploads: codes [rows][cols] in the ABI packing of format wf ([out, in], as in the checkpoint) and their
-// scales, taken as they are.  fn / setter: the entry point's name and its mode's setter, for the messages.
-static int upload_prequant(nvl_model* m, int wf, const char* fn, const char* setter, int kind, int layer, const uint8_t* codes,
-                           const void* scales, int64_t rows, int64_t cols, int layout) {
+// The pre-quantized uploads: codes [rows][cols] in the ABI packing of the format family `base` ([out, in], as in the checkpoint),
+// their scales and (INT4) zero points, taken as they are.  The format itself is the model's (INT4: with its group size).
+// fn / setter: the entry point's name and its mode's setter, for the messages.
+static int upload_prequant(nvl_model* m, int base, const char* fn, const char* setter, int kind, int layer, const uint8_t* codes,
+                           const void* scales, const uint8_t* zeros, int64_t rows, int64_t cols, int layout) {
     char buf[200];
     auto bad = [&](int code, const char* fmt, auto... args) { snprintf(buf, sizeof buf, fmt, fn, args...); return fail(m, code, buf); };
-    if (!m || !codes || !scales) return bad(NVL_ERR_INVALID, "%s: null argument");
+    if (!m || !codes || !scales || (base == WF_INT4 && !zeros)) return bad(NVL_ERR_INVALID, "%s: null argument");
     if (m->finalized) return bad(NVL_ERR_STATE, "%s: model already finalized");
-    if (q_kind(m, kind) != wf) return bad(NVL_ERR_INVALID, "%s: not an %s weight kind of this model (%s)", wf_name(wf), setter);
+    const int wf = q_kind(m, kind);
+    if (wf_base(wf) != base) return bad(NVL_ERR_INVALID, "%s: not an %s weight kind of this model (%s)", wf_name(base), setter);
     if (layout != NVL_LAYOUT_OUT_IN) return bad(NVL_ERR_INVALID, "%s: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
     DevTensor* t = tensor_slot(m, kind, layer);
     if (!t) return bad(NVL_ERR_INVALID, "%s: bad kind or layer");
-    int64_t SN = kind == NVL_T_TOK_EMB ? m->V : full_out(m, kind), SK = kind == NVL_T_TOK_EMB ? m->H : full_in(m, kind);
-    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {     // [E * out][in], scales per (expert, output row)
-        SN = (int64_t)m->cfg.num_experts * (kind == NVL_T_MOE_IN ? 2 * (int64_t)m->F : m->H);
-        SK = kind == NVL_T_MOE_IN ? m->H : m->F;
-    }
-    if (rows != SN || cols != SK || SK % 32 != 0)
+    int64_t SN, SK;
+    expected_2d_shape(m, kind, &SN, &SK);
+    if (rows != SN || cols != SK || SK % wf_in_multiple(wf) != 0)
         return bad(NVL_ERR_INVALID, "%s: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld]%s", kind, (long long)rows,
-                   (long long)cols, (long long)SN, (long long)SK, wf == WF_MXFP4 ? ", in % 32 == 0" : "");
-    if (wf == WF_MXFP4) {
-        for (int64_t i = 0; i < rows * (cols / 32); i++)
-            if (((const uint8_t*)scales)[i] < W4_E_MIN + 127 || ((const uint8_t*)scales)[i] > W4_E_MAX + 127)
-                return bad(NVL_ERR_INVALID, "%s: a scale byte is outside [7, 252] (0xff is the e8m0 NaN)");
-    } else {
-        for (int64_t i = 0; i < rows * cols; i++)
-            if ((codes[i] & 0x7F) == 0x7F) return bad(NVL_ERR_INVALID, "%s: NaN code (0x7f / 0xff)");
-        for (int64_t r = 0; r < rows; r++)
-            if (!(((const float*)scales)[r] > 0.f) || !std::isfinite(((const float*)scales)[r])) return bad(NVL_ERR_INVALID, "%s: scales must be finite and positive");
-    }
+                   (long long)cols, (long long)SN, (long long)SK, wf_in_multiple_hint(wf));
+    if (const char* why = wf_check_prequant(wf, codes, scales, zeros, rows, cols)) return bad(NVL_ERR_INVALID, why);
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));
     m->w2d_uploaded = true;
     if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) m->expert_uploaded = true;
     q_alloc(m, t, wf, rows, cols);
-    const int64_t cb = wf_code_bytes(wf, rows * cols), sb = wf_scale_bytes(wf, rows, cols);
-    uint8_t* raw = (uint8_t*)dmalloc_bytes(cb);
-    NVL_HIP(hipMemcpy(raw, codes, (size_t)cb, hipMemcpyHostToDevice));
-    if (wf == WF_MXFP4) {     // the scales are placed with the codes (row-major -> beside the 16-row tiles)
-        uint8_t* raw_s = (uint8_t*)dmalloc_bytes(sb);
-        NVL_HIP(hipMemcpy(raw_s, scales, (size_t)sb, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(w4_place_kernel, dim3((unsigned)cdiv(rows * cols / 8, 256)), dim3(256), 0, m->stream, (const uint8_t*)raw,
-                           (const uint8_t*)raw_s, rows, cols, (uint8_t*)t->p, (uint8_t*)t->qs);
-        NVL_HIP(hipStreamSynchronize(m->stream));
-        dfree(raw_s);
-    } else {                  // one scale per row: the device layout is the caller's
-        NVL_HIP(hipMemcpy(t->qs, scales, (size_t)sb, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(w8_place_kernel, dim3((unsigned)cdiv(rows * cols / 4, 256)), dim3(256), 0, m->stream, (const uint8_t*)raw, rows,
-                           cols, (uint8_t*)t->p);
+    const int64_t bytes[3] = {wf_code_bytes(wf, rows * cols), wf_abi_scale_bytes(wf, rows, cols), wf_abi_zero_bytes(wf, rows, cols)};
+    const void* host[3] = {codes, scales, zeros};
+    void* raw[3] = {nullptr, nullptr, nullptr};
+    for (int i = 0; i < 3; i++) {
+        if (!bytes[i]) continue;
+        raw[i] = dmalloc_bytes(bytes[i]);
+        NVL_HIP(hipMemcpy(raw[i], host[i], (size_t)bytes[i], hipMemcpyHostToDevice));
     }
+    wf_place(m->stream, wf, (const uint8_t*)raw[0], raw[1], (const uint8_t*)raw[2], rows, cols, t->p, t->qs);
     NVL_HIP(hipGetLastError());
     NVL_HIP(hipStreamSynchronize(m->stream));
-    dfree(raw);
+    for (void* r : raw) dfree(r);
     m->stats.weight_bytes += q_bytes(*t);
     return NVL_OK;
     NVL_CATCH(m)
 }
 extern "C" int nvl_upload_tensor_fp8(nvl_model* m, int kind, int layer, const uint8_t* codes, const float* scales,
                                      int64_t rows, int64_t cols, int layout) {
-    return upload_prequant(m, WF_FP8, "nvl_upload_tensor_fp8", "nvl_set_weight_dtype", kind, layer, codes, scales, rows, cols, layout);
+    return upload_prequant(m, WF_FP8, "nvl_upload_tensor_fp8", "nvl_set_weight_dtype", kind, layer, codes, scales, nullptr, rows, cols, layout);
 }
 // MXFP4: codes [rows][cols/2] (even k in the low nibble), e8m0 scales [rows][cols/32]
 extern "C" int nvl_upload_tensor_mxfp4(nvl_model* m, int kind, int layer, const uint8_t* codes, const uint8_t* scales,
                                        int64_t rows, int64_t cols, int layout) {
-    return upload_prequant(m, WF_MXFP4, "nvl_upload_tensor_mxfp4", "nvl_set_mx_weight_dtype", kind, layer, codes, scales, rows, cols, layout);
+    return upload_prequant(m, WF_MXFP4, "nvl_upload_tensor_mxfp4", "nvl_set_mx_weight_dtype", kind, layer, codes, scales, nullptr, rows, cols, layout);
 }
-
-// INT4 (w4g.h): codes [rows][cols/2] (even k in the low nibble), fp16 scales and zero points [rows][cols/g]; taken as they are.
+// INT4 (w4g.h): codes [rows][cols/2] (even k in the low nibble), fp16 scales and zero points [rows][cols/g].
 // With nvl_set_gq_expert_dtype also MOE_IN / MOE_OUT, as [E * out][in] (q_kind covers them only then)
 extern "C" int nvl_upload_tensor_int4(nvl_model* m, int kind, int layer, const uint8_t* codes, const uint16_t* scales, const uint8_t* zeros,
                                       int64_t rows, int64_t cols, int layout) {
-    const char* fn = "nvl_upload_tensor_int4";
-    char buf[200];
-    auto bad = [&](int code, const char* fmt, auto... args) { snprintf(buf, sizeof buf, fmt, fn, args...); return fail(m, code, buf); };
-    if (!m || !codes || !scales || !zeros) return bad(NVL_ERR_INVALID, "%s: null argument");
-    if (m->finalized) return bad(NVL_ERR_STATE, "%s: model already finalized");
-    const int wf = m->wf;
-    if (wf_base(wf) != WF_INT4 || q_kind(m, kind) != wf) return bad(NVL_ERR_INVALID, "%s: not an INT4 weight kind of this model (nvl_set_gq_weight_dtype)");
-    if (layout != NVL_LAYOUT_OUT_IN) return bad(NVL_ERR_INVALID, "%s: codes must be [out, in] (NVL_LAYOUT_OUT_IN)");
-    DevTensor* t = tensor_slot(m, kind, layer);
-    if (!t) return bad(NVL_ERR_INVALID, "%s: bad kind or layer");
-    int64_t SN = full_out(m, kind), SK = full_in(m, kind);
-    const int64_t g = wf_group(wf);
-    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) {     // INT4 experts: [E * out][in], words per (expert, output row)
-        SN = (int64_t)m->cfg.num_experts * (kind == NVL_T_MOE_IN ? 2 * (int64_t)m->F : m->H);
-        SK = kind == NVL_T_MOE_IN ? m->H : m->F;
-    }
-    if (rows != SN || cols != SK || SK % g != 0 || SK % 32 != 0)
-        return bad(NVL_ERR_INVALID, "%s: kind %d: got [out=%lld,in=%lld], model needs [out=%lld,in=%lld], in %% group size == 0", kind,
-                   (long long)rows, (long long)cols, (long long)SN, (long long)SK);
-    const int64_t ng = rows * (cols / g);
-    for (int64_t i = 0; i < ng; i++) {
-        if (zeros[i] > 15) return bad(NVL_ERR_INVALID, "%s: a zero point is above 15");
-        const uint16_t h = scales[i];     // fp16 bits: positive (sign 0, not zero) and finite (exponent field below 31)
-        if ((h & 0x8000) || h == 0 || (h & 0x7c00) == 0x7c00) return bad(NVL_ERR_INVALID, "%s: scales must be finite and positive");
-    }
-    NVL_TRY(m)
-    NVL_HIP(hipSetDevice(m->device));
-    m->w2d_uploaded = true;
-    if (kind == NVL_T_MOE_IN || kind == NVL_T_MOE_OUT) m->expert_uploaded = true;
-    q_alloc(m, t, wf, rows, cols);
-    uint8_t* raw = (uint8_t*)dmalloc_bytes(rows * cols / 2);
-    uint16_t* raw_s = (uint16_t*)dmalloc_bytes(ng * 2);
-    uint8_t* raw_z = (uint8_t*)dmalloc_bytes(ng);
-    NVL_HIP(hipMemcpy(raw, codes, (size_t)(rows * cols / 2), hipMemcpyHostToDevice));
-    NVL_HIP(hipMemcpy(raw_s, scales, (size_t)ng * 2, hipMemcpyHostToDevice));
-    NVL_HIP(hipMemcpy(raw_z, zeros, (size_t)ng, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(w4g_place_kernel, dim3((unsigned)cdiv(rows * cols / 8, 256)), dim3(256), 0, m->stream, (const uint8_t*)raw,
-                       (const uint16_t*)raw_s, (const uint8_t*)raw_z, rows, cols, wf_gshift(wf), (uint8_t*)t->p, (uint32_t*)t->qs);
-    NVL_HIP(hipGetLastError());
-    NVL_HIP(hipStreamSynchronize(m->stream));
-    dfree(raw); dfree(raw_s); dfree(raw_z);
-    m->stats.weight_bytes += q_bytes(*t);
-    return NVL_OK;
-    NVL_CATCH(m)
+    return upload_prequant(m, WF_INT4, "nvl_upload_tensor_int4", "nvl_set_gq_weight_dtype", kind, layer, codes, scales, zeros, rows, cols, layout);
 }
 
 // splitGPT2QKV (generic_loader.go:674-702): c_attn [H, 3H] is [in,out]; columns split Q|K|V.
@@ -888,23 +823,13 @@ std::vector<int32_t> swiglu_interleave(int64_t F, int64_t src_base) {
     return idx;
 }
 
-// gather_rows for a quantized weight: the codes move as 16-row tiles and the scales with them.  Pad rows (idx < 0) get
-// codes 0 and, fp8: scale 1 (the per-row scales are permuted on the host); MXFP4: zero scale bytes, a tile's K/2 scale
-// bytes being contiguous like its codes; INT4: zero group words, moved the same way (W~ = 0 every way; pad outputs are never stored)
+// gather_rows for a quantized weight: the codes move as 16-row tiles and the scales with them (wq.h wf_gather_scales; pad
+// rows, idx < 0, get codes 0)
 void gather_rows_q(nvl_model* m, const DevTensor& src, const std::vector<int32_t>& idx, void* dst, void* dst_qs, int64_t K) {
     const std::vector<int32_t> use = gather_tiles(idx);
     int32_t* didx = dmalloc<int32_t>((int64_t)use.size());
     NVL_HIP(hipMemcpyAsync(didx, use.data(), use.size() * 4, hipMemcpyHostToDevice, m->stream));
-    std::vector<float> sc, ssrc;     // (fp8; alive until the synchronize below)
-    if (src.wf == WF_MXFP4 || wf_base(src.wf) == WF_INT4) {
-        hipLaunchKernelGGL((gather_rows_kernel<uint8_t>), dim3((unsigned)use.size()), dim3(256), 0, m->stream,
-                           (const uint8_t*)src.qs, didx, (uint8_t*)dst_qs, wf_scale_bytes(src.wf, 16, K));
-    } else {
-        ssrc.resize((size_t)src.rows_pad);
-        NVL_HIP(hipMemcpy(ssrc.data(), src.qs, ssrc.size() * 4, hipMemcpyDeviceToHost));
-        for (int32_t i : idx) sc.push_back(i < 0 ? 1.0f : ssrc[(size_t)i]);
-        NVL_HIP(hipMemcpyAsync(dst_qs, sc.data(), sc.size() * 4, hipMemcpyHostToDevice, m->stream));
-    }
+    wf_gather_scales(m->stream, src.wf, src.qs, src.rows_pad, idx, didx, dst_qs, K);
     hipLaunchKernelGGL((gather_rows_kernel<uint8_t>), dim3((unsigned)use.size()), dim3(256), 0, m->stream,
                        (const uint8_t*)src.p, didx, (uint8_t*)dst, wf_code_bytes(src.wf, 16 * K));
     NVL_HIP(hipGetLastError());
@@ -955,23 +880,10 @@ void finalize_q_experts(nvl_model* m, LayerW& l, std::vector<int32_t>& idx, int6
     const DevTensor& d = l.t[NVL_T_MOE_OUT];
     l.moe_out_q = dmalloc_bytes(wf_code_bytes(wf, hp * E * I));
     NVL_HIP(hipMemsetAsync(l.moe_out_q, 0, (size_t)wf_code_bytes(wf, hp * E * I), m->stream));
-    if (wf == WF_MXFP4) {     // block scales over the same K, moved with the code tiles
-        l.qs_moe_out = q_alloc_scales(m, wf, hp, E * I);
-        hipLaunchKernelGGL(moe_cat_down_w4_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream, (const uint8_t*)d.p,
-                           (const uint8_t*)d.qs, (uint8_t*)l.moe_out_q, (uint8_t*)l.qs_moe_out, (int)H, (int)I, (int)E);
-    } else if (wf_base(wf) == WF_INT4) {     // group words over the same K (pad rows: {s = 1, z = 0}), moved with the code tiles
-        l.qs_moe_out = q_alloc_scales(m, wf, hp, E * I);
-        hipLaunchKernelGGL(moe_cat_down_w4g_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream, (const uint8_t*)d.p,
-                           (const uint32_t*)d.qs, (uint8_t*)l.moe_out_q, (uint32_t*)l.qs_moe_out, (int)H, (int)I, (int)E, wf_gshift(wf));
-    } else {                // row scales [E][H_pad]: one row per expert, through the host
-        l.qs_moe_out = q_alloc_scales(m, wf, E * hp, I);
-        hipLaunchKernelGGL(moe_cat_down_w8_kernel, dim3((unsigned)(H / 16), (unsigned)E), dim3(256), 0, m->stream,
-                           (const uint8_t*)d.p, (uint8_t*)l.moe_out_q, (int)H, (int)I, (int)E);
-        std::vector<float> sd((size_t)d.rows_pad);
-        NVL_HIP(hipMemcpy(sd.data(), d.qs, sd.size() * 4, hipMemcpyDeviceToHost));
-        for (int64_t e = 0; e < E; e++)
-            NVL_HIP(hipMemcpy((float*)l.qs_moe_out + e * hp, &sd[(size_t)(e * H)], (size_t)H * 4, hipMemcpyHostToDevice));
-    }
+    int64_t s_rows, s_K;     // where the down scales live (wq.h)
+    wf_down_scale_dims(wf, hp, E, I, &s_rows, &s_K);
+    l.qs_moe_out = q_alloc_scales(m, wf, s_rows, s_K);
+    wf_cat_down(m->stream, wf, d.p, d.qs, d.rows_pad, l.moe_out_q, l.qs_moe_out, H, I, E);
     NVL_HIP(hipGetLastError());
     NVL_HIP(hipStreamSynchronize(m->stream));
     if (dense_form) l.moe_out_cat = l.moe_out_q;
@@ -1014,135 +926,26 @@ extern "C" int nvl_set_kv_scales(nvl_model* m, const float* k_scale, const float
     return NVL_OK;
 }
 
-extern "C" int nvl_set_weight_dtype(nvl_model* m, int dtype) {
-    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_weight_dtype: no model");
-    if (m->finalized || m->w2d_uploaded)
-        return fail(m, NVL_ERR_STATE, "nvl_set_weight_dtype: call it after nvl_create and before the first 2-D weight upload");
-    if (dtype != NVL_W_AUTO && dtype != NVL_W_FP8_E4M3) return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: unknown weight dtype");
-    if (dtype == NVL_W_FP8_E4M3 && m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights need bf16 precision");
-    if (dtype == NVL_W_FP8_E4M3 && (m->tp > 1 || m->tp_force))
-        return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: 8-bit weights are not available with tensor parallelism");
-    if (dtype == NVL_W_FP8_E4M3 && m->wf == WF_MXFP4)
-        return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: the model stores MXFP4 weights (nvl_set_mx_weight_dtype)");
-    if (dtype == NVL_W_FP8_E4M3 && wf_base(m->wf) == WF_INT4)
-        return fail(m, NVL_ERR_INVALID, "nvl_set_weight_dtype: the model stores INT4 weights (nvl_set_gq_weight_dtype)");
-    if (dtype == NVL_W_FP8_E4M3) m->wf = WF_FP8;
-    else if (m->wf == WF_FP8) { m->wf = m->ef = WF_BF16; m->a8 = false; }     // (8-bit activations and experts need 8-bit weights)
+// The weight-format setters: every rule is wfmt.h's wf_decide(); an entry point names what it sets and through which family.
+static int set_dtype(nvl_model* m, int target, int family, int value, int group, const char* fn) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, std::string(fn) + ": no model");
+    const WfFacts facts{m->f32, m->tp > 1 || m->tp_force, m->cfg.use_moe && m->cfg.num_experts > 0, m->H, m->F,
+                        m->finalized, m->w2d_uploaded, m->expert_uploaded};
+    const WfDecision d = wf_decide(WfState{m->wf, m->ef, m->hf, m->a8}, facts, WfRequest{target, family, value, group, fn});
+    if (d.code != NVL_OK) return fail(m, d.code, d.msg);
+    m->wf = d.state.wf; m->ef = d.state.ef; m->hf = d.state.hf; m->a8 = d.state.a8;
     return NVL_OK;
 }
-
-extern "C" int nvl_set_mx_weight_dtype(nvl_model* m, int dtype) {
-    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: no model");
-    if (m->finalized || m->w2d_uploaded)
-        return fail(m, NVL_ERR_STATE, "nvl_set_mx_weight_dtype: call it after nvl_create and before the first 2-D weight upload");
-    if (dtype != NVL_MX_NONE && dtype != NVL_MX_FP4_E2M1) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: unknown MX weight dtype");
-    if (dtype == NVL_MX_FP4_E2M1 && m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: MXFP4 weights need bf16 precision");
-    if (dtype == NVL_MX_FP4_E2M1 && (m->tp > 1 || m->tp_force))
-        return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: MXFP4 weights are not available with tensor parallelism");
-    if (dtype == NVL_MX_FP4_E2M1 && m->wf == WF_FP8)
-        return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores 8-bit weights (nvl_set_weight_dtype)");
-    if (dtype == NVL_MX_FP4_E2M1 && wf_base(m->wf) == WF_INT4)
-        return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores INT4 weights (nvl_set_gq_weight_dtype)");
-    if (dtype == NVL_MX_NONE && m->ef == WF_MXFP4)
-        return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores MXFP4 experts (nvl_set_mx_expert_dtype), which need MXFP4 weights");
-    if (dtype == NVL_MX_NONE && m->hf == WF_MXFP4)
-        return fail(m, NVL_ERR_INVALID, "nvl_set_mx_weight_dtype: the model stores an MXFP4 LM head (nvl_set_mx_head_dtype), which needs MXFP4 weights");
-    if (dtype == NVL_MX_FP4_E2M1) m->wf = WF_MXFP4;
-    else if (m->wf == WF_MXFP4) m->wf = WF_BF16;
-    return NVL_OK;
-}
-
+extern "C" int nvl_set_weight_dtype(nvl_model* m, int dtype) { return set_dtype(m, WT_PROJ, WFAM_FP8, dtype, 0, "nvl_set_weight_dtype"); }
+extern "C" int nvl_set_mx_weight_dtype(nvl_model* m, int dtype) { return set_dtype(m, WT_PROJ, WFAM_MX, dtype, 0, "nvl_set_mx_weight_dtype"); }
 extern "C" int nvl_set_gq_weight_dtype(nvl_model* m, int dtype, int group_size) {
-    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: no model");
-    if (m->finalized || m->w2d_uploaded)
-        return fail(m, NVL_ERR_STATE, "nvl_set_gq_weight_dtype: call it after nvl_create and before the first 2-D weight upload");
-    if (dtype != NVL_GQ_NONE && dtype != NVL_GQ_UINT4) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: unknown group-quantized weight dtype");
-    if (group_size != 32 && group_size != 64 && group_size != 128)
-        return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: the group size must be 32, 64 or 128");
-    if (dtype == NVL_GQ_UINT4 && m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: INT4 weights need bf16 precision");
-    if (dtype == NVL_GQ_UINT4 && (m->tp > 1 || m->tp_force))
-        return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: INT4 weights are not available with tensor parallelism");
-    if (dtype == NVL_GQ_UINT4 && m->wf == WF_FP8)
-        return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: the model stores 8-bit weights (nvl_set_weight_dtype)");
-    if (dtype == NVL_GQ_UINT4 && m->wf == WF_MXFP4)
-        return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: the model stores MXFP4 weights (nvl_set_mx_weight_dtype)");
-    if (wf_base(m->ef) == WF_INT4 && (dtype == NVL_GQ_NONE || wf_int4(group_size) != m->ef))
-        return fail(m, NVL_ERR_INVALID, "nvl_set_gq_weight_dtype: the model stores INT4 experts (nvl_set_gq_expert_dtype), which need INT4 weights of their group size");
-    if (dtype == NVL_GQ_UINT4) m->wf = wf_int4(group_size);
-    else if (wf_base(m->wf) == WF_INT4) m->wf = WF_BF16;
-    return NVL_OK;
+    return set_dtype(m, WT_PROJ, WFAM_GQ, dtype, group_size, "nvl_set_gq_weight_dtype");
 }
-
-extern "C" int nvl_set_gq_expert_dtype(nvl_model* m, int dtype) {
-    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: no model");
-    if (m->finalized || m->expert_uploaded)
-        return fail(m, NVL_ERR_STATE, "nvl_set_gq_expert_dtype: call it after nvl_set_gq_weight_dtype and before the first expert upload");
-    if (dtype != NVL_GQE_NONE && dtype != NVL_GQE_UINT4) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: unknown group-quantized expert dtype");
-    if (dtype == NVL_GQE_UINT4) {
-        if (!m->cfg.use_moe || m->cfg.num_experts <= 0) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: the model has no MoE layers");
-        if (m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: INT4 experts need bf16 precision");
-        if (wf_base(m->wf) != WF_INT4) return fail(m, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: INT4 experts need INT4 projection weights (nvl_set_gq_weight_dtype first)");
-        // (a group of the concatenated down matrix, K = E*I, must lie inside one expert)
-        if (m->H % wf_group(m->wf) != 0 || m->F % wf_group(m->wf) != 0)
-            return fail(m, NVL_ERR_INVALID, "nvl_set_gq_expert_dtype: the hidden width and the expert width must be multiples of the group size");
-    }
-    if (dtype == NVL_GQE_UINT4) m->ef = m->wf;
-    else if (wf_base(m->ef) == WF_INT4) m->ef = WF_BF16;
-    return NVL_OK;
-}
-
-extern "C" int nvl_set_mx_head_dtype(nvl_model* m, int dtype) {
-    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mx_head_dtype: no model");
-    if (m->finalized || m->w2d_uploaded)
-        return fail(m, NVL_ERR_STATE, "nvl_set_mx_head_dtype: call it after nvl_set_mx_weight_dtype and before the first 2-D weight upload");
-    if (dtype != NVL_MXH_NONE && dtype != NVL_MXH_FP4_E2M1) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_head_dtype: unknown MX head dtype");
-    if (dtype == NVL_MXH_FP4_E2M1) {
-        if (m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_head_dtype: an MXFP4 LM head needs bf16 precision");
-        if (m->wf != WF_MXFP4) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_head_dtype: an MXFP4 LM head needs MXFP4 projection weights (nvl_set_mx_weight_dtype first)");
-    }
-    m->hf = dtype == NVL_MXH_FP4_E2M1 ? WF_MXFP4 : WF_BF16;
-    return NVL_OK;
-}
-
-extern "C" int nvl_set_mx_expert_dtype(nvl_model* m, int dtype) {
-    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: no model");
-    if (m->finalized || m->expert_uploaded)
-        return fail(m, NVL_ERR_STATE, "nvl_set_mx_expert_dtype: call it after nvl_set_mx_weight_dtype and before the first expert upload");
-    if (dtype != NVL_MXE_NONE && dtype != NVL_MXE_FP4_E2M1) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: unknown MX expert dtype");
-    if (dtype == NVL_MXE_FP4_E2M1) {
-        if (!m->cfg.use_moe || m->cfg.num_experts <= 0) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: the model has no MoE layers");
-        if (m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: MXFP4 experts need bf16 precision");
-        if (m->wf != WF_MXFP4) return fail(m, NVL_ERR_INVALID, "nvl_set_mx_expert_dtype: MXFP4 experts need MXFP4 projection weights (nvl_set_mx_weight_dtype first)");
-    }
-    if (dtype == NVL_MXE_FP4_E2M1) m->ef = WF_MXFP4;
-    else if (m->ef == WF_MXFP4) m->ef = WF_BF16;
-    return NVL_OK;
-}
-
-extern "C" int nvl_set_expert_dtype(nvl_model* m, int dtype) {
-    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_expert_dtype: no model");
-    if (m->finalized || m->expert_uploaded)
-        return fail(m, NVL_ERR_STATE, "nvl_set_expert_dtype: call it after nvl_set_weight_dtype and before the first expert upload");
-    if (dtype != NVL_EXPERT_AUTO && dtype != NVL_EXPERT_FP8_E4M3) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: unknown expert dtype");
-    if (dtype == NVL_EXPERT_FP8_E4M3) {
-        if (!m->cfg.use_moe || m->cfg.num_experts <= 0) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: the model has no MoE layers");
-        if (m->f32) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: 8-bit experts need bf16 precision");
-        if (m->wf != WF_FP8) return fail(m, NVL_ERR_INVALID, "nvl_set_expert_dtype: 8-bit experts need 8-bit projection weights (nvl_set_weight_dtype first)");
-    }
-    if (dtype == NVL_EXPERT_FP8_E4M3) m->ef = WF_FP8;
-    else if (m->ef == WF_FP8) m->ef = WF_BF16;
-    return NVL_OK;
-}
-
-extern "C" int nvl_set_act_dtype(nvl_model* m, int dtype) {
-    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_act_dtype: no model");
-    if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_set_act_dtype: call it before nvl_finalize");
-    if (dtype != NVL_ACT_AUTO && dtype != NVL_ACT_FP8_E4M3) return fail(m, NVL_ERR_INVALID, "nvl_set_act_dtype: unknown activation dtype");
-    if (dtype == NVL_ACT_FP8_E4M3 && m->wf != WF_FP8)
-        return fail(m, NVL_ERR_INVALID, "nvl_set_act_dtype: 8-bit activations need 8-bit weights (nvl_set_weight_dtype first)");
-    m->a8 = dtype == NVL_ACT_FP8_E4M3;
-    return NVL_OK;
-}
+extern "C" int nvl_set_expert_dtype(nvl_model* m, int dtype) { return set_dtype(m, WT_EXPERT, WFAM_FP8, dtype, 0, "nvl_set_expert_dtype"); }
+extern "C" int nvl_set_mx_expert_dtype(nvl_model* m, int dtype) { return set_dtype(m, WT_EXPERT, WFAM_MX, dtype, 0, "nvl_set_mx_expert_dtype"); }
+extern "C" int nvl_set_gq_expert_dtype(nvl_model* m, int dtype) { return set_dtype(m, WT_EXPERT, WFAM_GQ, dtype, 0, "nvl_set_gq_expert_dtype"); }
+extern "C" int nvl_set_mx_head_dtype(nvl_model* m, int dtype) { return set_dtype(m, WT_HEAD, WFAM_MX, dtype, 0, "nvl_set_mx_head_dtype"); }
+extern "C" int nvl_set_act_dtype(nvl_model* m, int dtype) { return set_dtype(m, WT_ACT, WFAM_FP8, dtype, 0, "nvl_set_act_dtype"); }
 
 extern "C" int nvl_set_mamba_conv_state(nvl_model* m, int mode) {
     if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mamba_conv_state: no model");
@@ -2051,16 +1854,7 @@ bool moe_dense_ok(const nvl_model* m, const LayerW& l, int M) {
 // quantized experts, the grouped forms: W~ of the layer's down matrices from the stored [H_pad][E*I] codes into dst, [E][H][I]
 // fragment-major per expert (ops_impl.h reads the experts back through it too)
 void dequant_down_experts(nvl_model* m, const LayerW& l, int H, int I, int E, bf16_t* dst) {
-    const int64_t n8 = (int64_t)E * H * I / 8;
-    if (m->ef == WF_MXFP4)
-        hipLaunchKernelGGL(e4_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
-                           (const uint8_t*)l.qs_moe_out, H, I, E, n8, dst);
-    else if (wf_base(m->ef) == WF_INT4)
-        hipLaunchKernelGGL(e4g_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
-                           (const uint32_t*)l.qs_moe_out, H, I, E, wf_gshift(m->ef), n8, dst);
-    else
-        hipLaunchKernelGGL(e8_dequant_down_kernel, dim3((unsigned)cdiv(n8, 256)), dim3(256), 0, m->stream, (const uint8_t*)l.moe_out_q,
-                           (const float*)l.qs_moe_out, H, I, E, round_up(H, W_ROW_PAD), n8, dst);
+    wf_dequant_down(m->stream, m->ef, l.moe_out_q, l.qs_moe_out, H, I, E, dst);
     NVL_HIP(hipGetLastError());
 }
 // deferred_norm: m->xn holds xn_raw = bf16(x * w_norm) and m->rs_part the x^2 partials (the O projection carried the FFN
@@ -2075,9 +1869,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
     const int pairs = M * k;
     // algorithmic weight bytes of the expert GEMMs: the experts a batch of `pairs` (token, rank) pairs can touch, once
     const double e_touch = (double)std::min(E, pairs);
-    // bytes per expert weight (quantized experts: codes; the row and block scales are not counted, INT4's group words — 4 / g
-    // bytes per weight, a quarter of the codes at g = 32 — are)
-    const double eb = m->ef != WF_BF16 ? wf_code_bytes(m->ef, 2) / 2.0 + (wf_base(m->ef) == WF_INT4 ? 4.0 / wf_group(m->ef) : 0.0) : (double)m->wsize;
+    const double eb = m->ef != WF_BF16 ? wf_stored_bytes(m->ef) : (double)m->wsize;     // bytes per expert weight
     m->site = KS_MOE_ROUTER;
     const bool dense = moe_dense_ok(m, l, M) && m->pending_slices == 0;
     // decode: router logits, softmax, top-k and the dense gate matrix in one launch (gemm.h moe_router_gate_kernel)
@@ -2197,11 +1989,9 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
         }
         a.w_expert_stride = (int64_t)2 * I * H; a.grp_bm = pp ? 512 : BM; a.grp_deep = small && g_moe_deep;
         // quantized experts: the grouped GEMMs run on this layer's W~, dequantized into one scratch buffer — up first, then down
-        // over it, in stream order (the down dequantize starts after the up GEMM has read the scratch).  Algorithmic bytes
-        // of a dequantize, per element: the code + its share of the scales in, 2 bytes out (3.0 for fp8, 2.53 for MXFP4,
-        // 2.5 + 4 / g for INT4)
+        // over it, in stream order (the down dequantize starts after the up GEMM has read the scratch).
         const void* w_down = l.t[NVL_T_MOE_OUT].p;
-        const double dq_bytes = m->ef == WF_MXFP4 ? 2.53 : (wf_base(m->ef) == WF_INT4 ? 2.5 + 4.0 / wf_group(m->ef) : 3.0);
+        const double dq_bytes = wf_dequant_bytes(m->ef);     // algorithmic bytes of a dequantize, per element
         if (m->ef != WF_BF16) {
             KScope ks(m, KC_OTHER, 0, KS_MOE_UP, (double)round_up(E * 2 * I, W_ROW_PAD) * H * dq_bytes);
             wf_dequant_rows(m->stream, m->ef, l.moe_in, l.qs_moe_in, H, 0, round_up(E * 2 * I, W_ROW_PAD), m->eq_scratch);
@@ -3931,25 +3721,12 @@ extern "C" int nvl_get_weight(nvl_model* m, int kind, int layer, float* out, int
     NVL_HIP(hipSetDevice(m->device));
     NVL_HIP(hipStreamSynchronize(m->stream));
     const int64_t N = t->rows, K = t->cols, n_el = t->rows_pad * K;
-    if (t->qs && wf_base(t->wf) == WF_INT4) {     // INT4: W~ = bf16_rne(s * (q - z)) (w4g.h)
-        std::vector<uint8_t> codes((size_t)wf_code_bytes(t->wf, n_el));
-        std::vector<uint32_t> words((size_t)wf_scale_bytes(t->wf, t->rows_pad, K) / 4);
-        NVL_HIP(hipMemcpy(codes.data(), t->p, codes.size(), hipMemcpyDeviceToHost));
-        NVL_HIP(hipMemcpy(words.data(), t->qs, words.size() * 4, hipMemcpyDeviceToHost));
-        const int64_t g = wf_group(t->wf);
-        for (int64_t n = 0; n < N; n++)
-            for (int64_t k = 0; k < K; k++)
-                out[k * N + n] = w4g_value(w4_code_at(codes.data(), n, k, K), words[(size_t)w4g_word_index(n, k / g, K / g)]);
-        return NVL_OK;
-    }
-    if (t->qs) {     // quantized weight: W~, the values every GEMM path computes with — fp8: bf16_rne(s * e4m3(q)); MXFP4: +-grid[q] * 2^e
+    if (t->qs) {     // quantized weight: W~, the values every GEMM path computes with (wq.h wf_value_at)
         std::vector<uint8_t> codes((size_t)wf_code_bytes(t->wf, n_el)), sc((size_t)wf_scale_bytes(t->wf, t->rows_pad, K));
         NVL_HIP(hipMemcpy(codes.data(), t->p, codes.size(), hipMemcpyDeviceToHost));
         NVL_HIP(hipMemcpy(sc.data(), t->qs, sc.size(), hipMemcpyDeviceToHost));
         for (int64_t n = 0; n < N; n++)
-            for (int64_t k = 0; k < K; k++)
-                out[k * N + n] = t->wf == WF_MXFP4 ? w4_value(w4_code_at(codes.data(), n, k, K), sc[(size_t)w4_scale_index(n, k >> 5, K >> 5)])
-                                                   : w8_value(codes[(size_t)fm_index(n, k, K)], ((const float*)sc.data())[n]);
+            for (int64_t k = 0; k < K; k++) out[k * N + n] = wf_value_at(t->wf, codes.data(), sc.data(), n, k, K);
         return NVL_OK;
     }
     std::vector<char> raw((size_t)n_el * m->wsize);

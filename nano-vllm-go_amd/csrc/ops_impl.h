@@ -359,9 +359,12 @@ extern "C" int nvl_op_mamba_mixer(int device, int precision, const float* proj, 
 }
 
 // The one-weight model of the quantized matmul ops: W [K][N] ([in, out], as nvl_op_matmul) quantized by the upload quantizer
-// of format wf into t and registered for gemm(), a tile-path scratch of at most scratch_rows weight rows, then
-// C = bf16(A) · W~^T through the model's dispatch into c [M][N].
-static void op_matmul_q(OpCtx& cx, int wf, const float* a, const float* w, int M, int N, int K, float* c, DevTensor& t, int64_t scratch_rows) {
+// of format wf into a tensor registered for gemm(), a tile-path scratch of at most scratch_rows weight rows, then
+// C = bf16(A) · W~^T through the model's dispatch into c [M][N]; then the quantizer's codes, scales and (INT4) zero points in
+// the ABI packing of the prequantized upload, where asked for.
+static void op_matmul_q(OpCtx& cx, int wf, const float* a, const float* w, int M, int N, int K, float* c, int64_t scratch_rows,
+                        uint8_t* codes_out = nullptr, void* scales_out = nullptr, uint8_t* zeros_out = nullptr) {
+    DevTensor t;
     cx.m.wf = wf;
     void* A = cx.up_mat(a, M, K, false);
     upload_2d_q(&cx.m, &t, wf, w, NVL_DTYPE_F32, N, K, true);
@@ -375,6 +378,12 @@ static void op_matmul_q(OpCtx& cx, int wf, const float* a, const float* w, int M
     std::vector<float> tmp((size_t)M * ldc);
     cx.down(tmp.data(), C, (int64_t)M * ldc);
     for (int i = 0; i < M; i++) memcpy(c + (size_t)i * N, &tmp[(size_t)i * ldc], (size_t)N * 4);
+    if (codes_out || scales_out || zeros_out) {
+        std::vector<uint8_t> codes((size_t)wf_code_bytes(wf, t.rows_pad * K)), sc((size_t)wf_scale_bytes(wf, t.rows_pad, K));
+        NVL_HIP(hipMemcpy(codes.data(), t.p, codes.size(), hipMemcpyDeviceToHost));
+        NVL_HIP(hipMemcpy(sc.data(), t.qs, sc.size(), hipMemcpyDeviceToHost));
+        wf_to_abi(wf, codes.data(), sc.data(), N, K, codes_out, scales_out, zeros_out);
+    }
 }
 
 // 8-bit weights (w8.h): M <= 64 the fp8-weight decode kernels, larger M the 64-row groups or dequantize + tile; the scratch
@@ -385,18 +394,7 @@ extern "C" int nvl_op_matmul_fp8w(int device, const float* a, const float* w, in
     if (K % 64 != 0) return op_fail("nvl_op_matmul_fp8w: K must be a multiple of 64");
     OP_TRY
     OpCtx cx(device, NVL_PRECISION_BF16);
-    DevTensor t;
-    op_matmul_q(cx, WF_FP8, a, w, M, N, K, c, t, 2048);
-    if (codes_out || scales_out) {
-        std::vector<uint8_t> codes((size_t)(t.rows_pad * K));
-        std::vector<float> sc((size_t)t.rows_pad);
-        NVL_HIP(hipMemcpy(codes.data(), t.p, codes.size(), hipMemcpyDeviceToHost));
-        NVL_HIP(hipMemcpy(sc.data(), t.qs, sc.size() * 4, hipMemcpyDeviceToHost));
-        if (scales_out) memcpy(scales_out, sc.data(), (size_t)N * 4);
-        if (codes_out)
-            for (int64_t n = 0; n < N; n++)
-                for (int64_t k = 0; k < K; k++) codes_out[n * K + k] = codes[(size_t)fm_index(n, k, K)];
-    }
+    op_matmul_q(cx, WF_FP8, a, w, M, N, K, c, 2048, codes_out, scales_out);
     return NVL_OK;
     OP_CATCH
 }
@@ -408,17 +406,7 @@ extern "C" int nvl_op_matmul_mxfp4w(int device, const float* a, const float* w, 
     if (K % 64 != 0) return op_fail("nvl_op_matmul_mxfp4w: K must be a multiple of 64");
     OP_TRY
     OpCtx cx(device, NVL_PRECISION_BF16);
-    DevTensor t;
-    op_matmul_q(cx, WF_MXFP4, a, w, M, N, K, c, t, INT64_MAX);
-    if (codes_out || scales_out) {
-        std::vector<uint8_t> codes((size_t)(t.rows_pad * K / 2)), sc((size_t)(t.rows_pad * K / 32));
-        NVL_HIP(hipMemcpy(codes.data(), t.p, codes.size(), hipMemcpyDeviceToHost));
-        NVL_HIP(hipMemcpy(sc.data(), t.qs, sc.size(), hipMemcpyDeviceToHost));
-        std::vector<uint8_t> co((size_t)N * K / 2), so((size_t)N * K / 32);
-        w4_to_abi(codes.data(), sc.data(), N, K, co.data(), so.data());
-        if (codes_out) memcpy(codes_out, co.data(), co.size());
-        if (scales_out) memcpy(scales_out, so.data(), so.size());
-    }
+    op_matmul_q(cx, WF_MXFP4, a, w, M, N, K, c, INT64_MAX, codes_out, scales_out);
     return NVL_OK;
     OP_CATCH
 }
@@ -431,15 +419,7 @@ extern "C" int nvl_op_matmul_int4w(int device, const float* a, const float* w, i
     if (K % 64 != 0 || K % group_size != 0) return op_fail("nvl_op_matmul_int4w: K must be a multiple of 64 and of the group size");
     OP_TRY
     OpCtx cx(device, NVL_PRECISION_BF16);
-    DevTensor t;
-    op_matmul_q(cx, wf_int4(group_size), a, w, M, N, K, c, t, INT64_MAX);
-    if (codes_out || scales_out || zeros_out) {
-        std::vector<uint8_t> codes((size_t)(t.rows_pad * K / 2));
-        std::vector<uint32_t> words((size_t)(t.rows_pad * (K / group_size)));
-        NVL_HIP(hipMemcpy(codes.data(), t.p, codes.size(), hipMemcpyDeviceToHost));
-        NVL_HIP(hipMemcpy(words.data(), t.qs, words.size() * 4, hipMemcpyDeviceToHost));
-        w4g_to_abi(codes.data(), words.data(), N, K, group_size, codes_out, scales_out, zeros_out);
-    }
+    op_matmul_q(cx, wf_int4(group_size), a, w, M, N, K, c, INT64_MAX, codes_out, scales_out, zeros_out);
     return NVL_OK;
     OP_CATCH
 }
@@ -474,8 +454,7 @@ extern "C" int nvl_op_matmul_w8a8(int device, const float* a, const float* w, in
     const std::vector<float> ones((size_t)cx.m.a8_rows, 1.0f);
     NVL_HIP(hipMemcpyAsync(cx.m.a8_scale, ones.data(), ones.size() * 4, hipMemcpyHostToDevice, cx.m.stream));
     NVL_HIP(hipStreamSynchronize(cx.m.stream));     // (pageable source)
-    DevTensor t;
-    op_matmul_q(cx, WF_FP8, a, w, M, N, K, c, t, 2048);
+    op_matmul_q(cx, WF_FP8, a, w, M, N, K, c, 2048);
     if (a_codes_out || a_scales_out) a8_read_back(cx, cx.m.a8_codes, cx.m.a8_scale, M, K, a_codes_out, a_scales_out);
     cx.m.a8_codes = nullptr; cx.m.a8_scale = nullptr;       // owned by cx.bufs
     return NVL_OK;
@@ -914,7 +893,7 @@ bool moe_op_results(OpCtx& cx, int rows, int E, int k, float* router_logits, flo
     }
     return true;
 }
-// the experts' format of the *_q entry points -> the host format id (wq.h); -1: what the format's setter would refuse
+// the experts' format of the *_q entry points -> the host format id (wfmt.h); -1: what the format's setter would refuse
 int moe_op_wf(int expert_format, int group_size, int H, int inter) {
     switch (expert_format) {
         case NVL_OP_EXPERTS_BF16: return WF_BF16;

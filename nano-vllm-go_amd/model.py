@@ -38,6 +38,25 @@ def _ptr(a):
     return None if a is None else a.ctypes.data_as(C.c_void_p)
 
 
+# The weight-format keywords of HipTransformerModel, in the order they are checked: keyword, value table, the keyword that must
+# be switched on with it, the keywords it cannot be combined with, setter.  The library decides every combination
+# (csrc/wfmt.h wf_decide); what is checked here is what can be said before a model exists.
+_DTYPE_KEYWORDS = (
+    ("weight_dtype", L.WEIGHT_DTYPE, None, (), "nvl_set_weight_dtype"),
+    ("act_dtype", L.ACT_DTYPE, "weight_dtype", (), "nvl_set_act_dtype"),
+    ("expert_dtype", L.EXPERT_DTYPE, "weight_dtype", (), "nvl_set_expert_dtype"),
+    ("mx_weight_dtype", L.MX_WEIGHT_DTYPE, None, ("weight_dtype",), "nvl_set_mx_weight_dtype"),
+    ("mx_expert_dtype", L.MX_EXPERT_DTYPE, "mx_weight_dtype", (), "nvl_set_mx_expert_dtype"),
+    ("mx_head_dtype", L.MX_HEAD_DTYPE, "mx_weight_dtype", (), "nvl_set_mx_head_dtype"),
+    ("gq_weight_dtype", L.GQ_WEIGHT_DTYPE, None, ("weight_dtype", "mx_weight_dtype"), "nvl_set_gq_weight_dtype"),
+    ("gq_expert_dtype", L.GQ_EXPERT_DTYPE, "gq_weight_dtype", (), "nvl_set_gq_expert_dtype"),
+)
+_ON = {kw: next(name for name, v in table.items() if v == 1) for kw, table, *_ in _DTYPE_KEYWORDS}      # e.g. "fp8_e4m3"
+# the order the setters are called in: a family's projections before what needs them
+_SETTER_ORDER = ("gq_weight_dtype", "gq_expert_dtype", "mx_weight_dtype", "mx_expert_dtype", "mx_head_dtype", "weight_dtype",
+                 "expert_dtype", "act_dtype")
+
+
 class HipTransformerModel:
     """tensor.TransformerModel on one MI355X.  `tensors` is {(slot, layer): array} in the reference's
     post-load layout (2-D weights [in, out]); arrays may be numpy fp32 or torch tensors (fp32/bf16,
@@ -93,66 +112,29 @@ class HipTransformerModel:
         opts.kv_cache_dtype = L.KV_CACHE_DTYPE[kv_cache_dtype]
         self.kv_cache_dtype = kv_cache_dtype
         self._c = _cfg_struct(cfg)
-        if weight_dtype not in L.WEIGHT_DTYPE:
-            raise ValueError(f"weight_dtype must be one of {sorted(L.WEIGHT_DTYPE)}")
-        if act_dtype not in L.ACT_DTYPE:
-            raise ValueError(f"act_dtype must be one of {sorted(L.ACT_DTYPE)}")
-        if act_dtype != "auto" and weight_dtype != "fp8_e4m3":
-            raise ValueError('act_dtype="fp8_e4m3" needs weight_dtype="fp8_e4m3"')
-        if expert_dtype not in L.EXPERT_DTYPE:
-            raise ValueError(f"expert_dtype must be one of {sorted(L.EXPERT_DTYPE)}")
-        if expert_dtype != "auto" and weight_dtype != "fp8_e4m3":
-            raise ValueError('expert_dtype="fp8_e4m3" needs weight_dtype="fp8_e4m3"')
-        if mx_weight_dtype not in L.MX_WEIGHT_DTYPE:
-            raise ValueError(f"mx_weight_dtype must be one of {sorted(L.MX_WEIGHT_DTYPE)}")
-        if mx_weight_dtype != "none" and weight_dtype != "auto":
-            raise ValueError('mx_weight_dtype="fp4_e2m1" cannot be combined with weight_dtype="fp8_e4m3"')
-        if mx_expert_dtype not in L.MX_EXPERT_DTYPE:
-            raise ValueError(f"mx_expert_dtype must be one of {sorted(L.MX_EXPERT_DTYPE)}")
-        if mx_expert_dtype != "none" and mx_weight_dtype != "fp4_e2m1":
-            raise ValueError('mx_expert_dtype="fp4_e2m1" needs mx_weight_dtype="fp4_e2m1"')
-        if mx_head_dtype not in L.MX_HEAD_DTYPE:
-            raise ValueError(f"mx_head_dtype must be one of {sorted(L.MX_HEAD_DTYPE)}")
-        if mx_head_dtype != "none" and mx_weight_dtype != "fp4_e2m1":
-            raise ValueError('mx_head_dtype="fp4_e2m1" needs mx_weight_dtype="fp4_e2m1"')
-        if gq_weight_dtype not in L.GQ_WEIGHT_DTYPE:
-            raise ValueError(f"gq_weight_dtype must be one of {sorted(L.GQ_WEIGHT_DTYPE)}")
-        if gq_group_size not in L.GQ_GROUP_SIZES:
-            raise ValueError(f"gq_group_size must be one of {L.GQ_GROUP_SIZES}")
-        if gq_weight_dtype != "none" and (weight_dtype != "auto" or mx_weight_dtype != "none"):
-            raise ValueError('gq_weight_dtype="uint4" cannot be combined with weight_dtype="fp8_e4m3" or mx_weight_dtype="fp4_e2m1"')
-        if gq_expert_dtype not in L.GQ_EXPERT_DTYPE:
-            raise ValueError(f"gq_expert_dtype must be one of {sorted(L.GQ_EXPERT_DTYPE)}")
-        if gq_expert_dtype != "none" and gq_weight_dtype != "uint4":
-            raise ValueError('gq_expert_dtype="uint4" needs gq_weight_dtype="uint4"')
+        given = dict(weight_dtype=weight_dtype, act_dtype=act_dtype, expert_dtype=expert_dtype, mx_weight_dtype=mx_weight_dtype,
+                     mx_expert_dtype=mx_expert_dtype, mx_head_dtype=mx_head_dtype, gq_weight_dtype=gq_weight_dtype,
+                     gq_expert_dtype=gq_expert_dtype)
+        for kw, table, needs, excludes, _ in _DTYPE_KEYWORDS:
+            if given[kw] not in table:
+                raise ValueError(f"{kw} must be one of {sorted(table)}")
+            if kw == "gq_weight_dtype" and gq_group_size not in L.GQ_GROUP_SIZES:
+                raise ValueError(f"gq_group_size must be one of {L.GQ_GROUP_SIZES}")
+            if table[given[kw]] and needs and given[needs] != _ON[needs]:
+                raise ValueError(f'{kw}="{_ON[kw]}" needs {needs}="{_ON[needs]}"')
+            if table[given[kw]] and any(given[o] == _ON[o] for o in excludes):      # (checked above: a value is off or on)
+                raise ValueError(f'{kw}="{_ON[kw]}" cannot be combined with ' + " or ".join(f'{o}="{_ON[o]}"' for o in excludes))
         if mamba_conv_state not in L.MAMBA_CONV_STATE:
             raise ValueError(f"mamba_conv_state must be one of {sorted(L.MAMBA_CONV_STATE)}")
         L.check(self.lib.nvl_create(C.byref(self._c), C.byref(opts), C.byref(self.h)))
-        self.weight_dtype = weight_dtype
-        self.gq_weight_dtype = gq_weight_dtype
+        for kw, value in given.items():
+            setattr(self, kw, value)
         self.gq_group_size = gq_group_size
-        if gq_weight_dtype != "none":
-            rc = self.lib.nvl_set_gq_weight_dtype(self.h, L.GQ_WEIGHT_DTYPE[gq_weight_dtype], int(gq_group_size))
-            if rc < 0:
-                msg = self.lib.nvl_last_error(self.h)
-                self.close()
-                raise L.NvlError(rc, msg.decode() if msg else "")
-        self.mx_weight_dtype = mx_weight_dtype
-        self.mx_expert_dtype = mx_expert_dtype
-        self.gq_expert_dtype = gq_expert_dtype
-        self.mx_head_dtype = mx_head_dtype
-        self.act_dtype = act_dtype
-        self.expert_dtype = expert_dtype
-        for setter, table, value in ((self.lib.nvl_set_gq_expert_dtype, L.GQ_EXPERT_DTYPE, gq_expert_dtype),
-                                     (self.lib.nvl_set_mx_weight_dtype, L.MX_WEIGHT_DTYPE, mx_weight_dtype),
-                                     (self.lib.nvl_set_mx_expert_dtype, L.MX_EXPERT_DTYPE, mx_expert_dtype),
-                                     (self.lib.nvl_set_mx_head_dtype, L.MX_HEAD_DTYPE, mx_head_dtype),
-                                     (self.lib.nvl_set_weight_dtype, L.WEIGHT_DTYPE, weight_dtype),
-                                     (self.lib.nvl_set_expert_dtype, L.EXPERT_DTYPE, expert_dtype),
-                                     (self.lib.nvl_set_act_dtype, L.ACT_DTYPE, act_dtype)):
-            if value in ("auto", "none"):
+        for kw, table, _, _, setter in sorted(_DTYPE_KEYWORDS, key=lambda row: _SETTER_ORDER.index(row[0])):
+            if not table[given[kw]]:
                 continue
-            rc = setter(self.h, table[value])
+            fn = getattr(self.lib, setter)
+            rc = fn(self.h, table[given[kw]], int(gq_group_size)) if kw == "gq_weight_dtype" else fn(self.h, table[given[kw]])
             if rc < 0:
                 msg = self.lib.nvl_last_error(self.h)
                 self.close()
