@@ -815,6 +815,68 @@ int nvl_op_attention_batch(int device, int precision, int form, int nH, int nKV,
                            const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
                            int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
                            int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt);
+/* The FRONT of an attention layer as a layer of the model runs it, stage by stage (generic_model.go:295-302 embedWithOffset,
+ * :304-318 attention norm, the QKV projection with its bias, rope.go:153-205 on Q and K, Q into the attention operand
+ * buffer, K / V into the paged cache): the forward pass's own embed() and qkv_front() on a batch laid out as the paged
+ * front end lays it out (see nvl_op_attention_batch: seq_len / seq_pos / block_table [n_seqs][tbl_stride] / n_blocks /
+ * block_size / max_seq mean the same), set up as nvl_create sets a paged model up (Tmax = block_size, blocks_per_seq =
+ * tbl_stride, one layer).  qkv_front() takes the model's decisions — the fused-epilogue tile kernels (EPI_QKV), the
+ * decode-form projection + rope_kv_kernel for up to 64 rows and for the short-prefill row groups (nvl_set_tuning key 18),
+ * rope_kv8_kernel for an 8-bit cache, the fp32 kernels, and a bf16 decode step, where the projection only stores fp32 rows
+ * because the attention kernel does RoPE and the append — and nvl_set_tuning keys 0 / 11 / 18 act as in a model.
+ * The op runs the NON-DEFERRED operand path only: the deferred-RMSNorm operand into the QKV projection is held by
+ * nvl_op_dense_stages (yn with has_next = 1), the fused decode append by nvl_op_attention_batch (NVL_ATTN_OP_FUSED).
+ * In: x [tokens][hidden], the residual stream; norm_w (/ norm_b for NVL_NORM_LAYER) [hidden] — norm_w == NULL: x is the
+ * normed operand already (as behind the decode seam), rounded to the operand type on upload, no norm runs; w_qkv
+ * [(nH + 2 nKV) hd][hidden], b_qkv or NULL; rope_base (0: no RoPE, the tables stay NULL); k_pool / v_pool
+ * [n_blocks][nKV][block_size][hd], the layer's cache before the pass (kv8: quantized with k_scale / v_scale by the cache's
+ * own quantizer first; bf16 only).  The embedding stage, when tokens != NULL: tokens / tok_pos [tokens], emb [vocab][hidden],
+ * pos_emb [pos_rows][hidden] or NULL, embedding_multiplier (0 = none); x is then an OUTPUT.
+ * Every output and scratch buffer is 0xFF bytes (NaN) beforehand.  Out: op [tokens][hidden], the projection's operand rows as
+ * fp32; qkv [tokens][n_qkv], the fp32 projection (the store forms; NaN in the epilogue form); q [round_up(tokens, 256)][nH
+ * hd], the WHOLE operand buffer (rows from tokens on stay NaN); k_pool / v_pool after the pass as fp32 (kv8: scale *
+ * e4m3(code), and the raw codes in k_codes / v_codes [n_blocks][nKV][block_size][hd], either may be NULL); ran
+ * [NVL_QKV_RAN_INTS].  Refused before anything is launched, with NVL_ERR_INVALID / NVL_ERR_POSITION as nvl_op_attention_batch
+ * refuses: a bad shape, a negative position, seq_pos + seq_len > max_seq, a table too short, ANY table entry outside
+ * [0, n_blocks), a token id outside [0, vocab). */
+enum { NVL_QKV_RAN_FORM = 0, NVL_QKV_RAN_GEMM = 1, NVL_QKV_RAN_NORM = 2, NVL_QKV_RAN_EMBED = 3, NVL_QKV_RAN_INTS = 4 };
+enum {      /* ran[NVL_QKV_RAN_FORM] */
+    NVL_QKV_FORM_F32_STORE_ROPE = 1,        /* gemm_f32_kernel + rope_kv_kernel<float> */
+    NVL_QKV_FORM_DECODE_STORE_ROPE = 2,     /* decode-form projection (<= 64 rows) + rope_kv_kernel<bf16> */
+    NVL_QKV_FORM_GROUPS_STORE_ROPE = 3,     /* ... over 64-row groups (short prefill) + rope_kv_kernel<bf16> */
+    NVL_QKV_FORM_EPILOGUE = 4,              /* a tile kernel with the EPI_QKV epilogue */
+    NVL_QKV_FORM_STORE_ROPE_KV8 = 5,        /* projection + rope_kv8_kernel */
+    NVL_QKV_FORM_STORE_ONLY = 6             /* a bf16 decode step: the projection alone (the pools stay as they were) */
+};
+enum {      /* ran[NVL_QKV_RAN_GEMM]: the instance launch_gemm_bf16 launched (0: none of them, e.g. the fp32 kernel) */
+    NVL_GEMM_RAN_NONE = 0,
+    NVL_GEMM_RAN_TILE1 = 1,                 /* 128x128, two stages */
+    NVL_GEMM_RAN_TILE2 = 2,                 /* 256x128, three stages */
+    NVL_GEMM_RAN_TILE3 = 3,                 /* 256x256 as 2x4 waves */
+    NVL_GEMM_RAN_PINGPONG = 5,              /* the ping-pong 256x256 kernel */
+    NVL_GEMM_RAN_HD128_4X2 = 6,             /* EPI_QKV, head_dim 128: 256x256 as 4x2 waves */
+    NVL_GEMM_RAN_HD128_PINGPONG = 7,        /* EPI_QKV, head_dim 128: the ping-pong kernel, wave tile 64x128 */
+    NVL_GEMM_RAN_DECODE = 8,                /* the decode kernels, up to 64 rows */
+    NVL_GEMM_RAN_GROUPS = 9                 /* the decode kernels over 64-row groups */
+};
+enum {      /* ran[NVL_QKV_RAN_NORM]: 0 = no norm ran, else NVL_NORM_RAN_* (NVL_NORM_RAN_WAVE: norm_kernel);
+             * ran[NVL_QKV_RAN_EMBED]: 0 = no embedding stage */
+    NVL_EMBED_RAN_F32 = 1, NVL_EMBED_RAN_BF16 = 2, NVL_EMBED_RAN_W8 = 3, NVL_EMBED_RAN_W4 = 4
+};
+typedef struct nvl_qkv_stages {
+    int32_t struct_bytes;           /* sizeof(nvl_qkv_stages) */
+    int32_t kv8, nH, nKV, hd, hidden;
+    int32_t n_seqs, tbl_stride, n_blocks, block_size, max_seq;
+    int32_t norm_type, vocab, pos_rows;
+    float norm_eps, k_scale, v_scale, embedding_multiplier;
+    double rope_base;
+    const int32_t *seq_len, *seq_pos, *block_table, *tokens, *tok_pos;
+    const float *norm_w, *norm_b, *w_qkv, *b_qkv, *emb, *pos_emb;
+    float *x, *op, *qkv, *q, *k_pool, *v_pool;
+    uint8_t *k_codes, *v_codes;
+    int32_t* ran;
+} nvl_qkv_stages;
+int nvl_op_qkv_stages(int device, int precision, const nvl_qkv_stages* io);
 /* 8-bit weights: tensor.MatMul (tensor.go:62-88) with b = w [K][N] quantized by the model's upload quantizer
  * (NVL_W_FP8_E4M3), c [M][N] = bf16(a) · W~ through the model's own GEMM dispatch (M selects the decode or the tile form).
  * codes_out [N][K] / scales_out [N] (either may be NULL) receive the quantized weight.  K % 64 == 0. */
@@ -904,7 +966,7 @@ enum {
     NVL_RESID_FORM_GROUPS_SERIAL = 3,   /* ... one launch per group */
     NVL_RESID_FORM_DECODE = 4       /* decode kernel, one workgroup per weight tile (and K slice) */
 };
-enum { NVL_NORM_RAN_ROW = 1, NVL_NORM_RAN_ROW_IDX = 2, NVL_NORM_RAN_TILE16 = 3 };
+enum { NVL_NORM_RAN_ROW = 1, NVL_NORM_RAN_ROW_IDX = 2, NVL_NORM_RAN_TILE16 = 3, NVL_NORM_RAN_WAVE = 4 /* norm_kernel: one wave per row */ };
 typedef struct nvl_dense_stages {
     int32_t struct_bytes;           /* sizeof(nvl_dense_stages) */
     int32_t rows, hidden, q_width, ffn, n_next;

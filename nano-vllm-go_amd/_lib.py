@@ -115,6 +115,15 @@ class DenseStagesC(C.Structure):      # nvl_dense_stages
                                            "ran")])
 
 
+class QkvStagesC(C.Structure):        # nvl_qkv_stages
+    _fields_ = ([(n, C.c_int32) for n in ("struct_bytes", "kv8", "nH", "nKV", "hd", "hidden", "n_seqs", "tbl_stride", "n_blocks",
+                                          "block_size", "max_seq", "norm_type", "vocab", "pos_rows")] +
+                [(n, C.c_float) for n in ("norm_eps", "k_scale", "v_scale", "embedding_multiplier")] + [("rope_base", C.c_double)] +
+                [(n, C.c_void_p) for n in ("seq_len", "seq_pos", "block_table", "tokens", "tok_pos", "norm_w", "norm_b", "w_qkv",
+                                           "b_qkv", "emb", "pos_emb", "x", "op", "qkv", "q", "k_pool", "v_pool", "k_codes",
+                                           "v_codes", "ran")])
+
+
 def declared_symbols() -> list[str]:
     """Every function include/nvllm.h declares (the drop-in surface)."""
     text = HEADER.read_text()
@@ -231,6 +240,7 @@ def lib():
     L.nvl_decode_greedy_lookup.argtypes = [vp, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]
     L.nvl_op_attention_mq.argtypes = [C.c_int, vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, f32, vp]
     L.nvl_op_dense_stages.argtypes = [C.c_int, C.c_int, C.POINTER(DenseStagesC)]
+    L.nvl_op_qkv_stages.argtypes = [C.c_int, C.c_int, C.POINTER(QkvStagesC)]
     L.nvl_op_dense_moe_stages.argtypes = [C.c_int, C.c_int] + [vp] * 9 + [C.c_int] * 6 + [f32, f32] + [vp] * 8
     L.nvl_op_moe_stages.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp] + [C.c_int] * 5 + [vp] * 4
     L.nvl_op_dense_moe_stages_q.argtypes = [C.c_int, C.c_int] + [vp] * 9 + [C.c_int] * 6 + [f32, f32] + [C.c_int] * 2 + [vp] * 11

@@ -1658,6 +1658,8 @@ static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a, co
 // how the last decode-form projection was launched (host side, for the record resid_gemm keeps: nvl_model::dense_ran):
 // NVL_RESID_FORM_* of nvllm.h (0, NVL_RESID_FORM_TILE: none of the decode launchers ran)
 static thread_local int t_skinny_form = 0, t_skinny_half = 0;
+// which instance launch_gemm_bf16 launched last (host side: NVL_GEMM_RAN_* of nvllm.h; gemm() copies it to nvl_model::gemm_ran)
+static thread_local int t_gemm_ran = 0;
 constexpr int DEFER_MAX_M = 128;    // deferred RMSNorm (decode): rows of the x^2 partial buffer.  Above 64 rows the producer
                                     // runs as 64-row groups like every narrow projection (one workgroup per 16-row tile
                                     // was measured at M = 128: -13 %); above 128 rows FFN-up belongs on the tile kernels
@@ -1920,8 +1922,9 @@ static inline bool skinny_groups_ok(const GemmArgs& a) {
 
 template <int EPI, typename OutT>
 static inline void launch_gemm_bf16(hipStream_t st, const GemmArgs& a) {
+    t_gemm_ran = NVL_GEMM_RAN_NONE;
     if (a.tile_map) { launch_gemm_grouped<EPI, OutT>(st, a, a.M); return; }   // a.M carries the m-tile bound
-    if (launch_gemm_skinny_bf16<EPI, OutT>(st, a)) return;
+    if (launch_gemm_skinny_bf16<EPI, OutT>(st, a)) { t_gemm_ran = NVL_GEMM_RAN_DECODE; return; }
     if constexpr (EPI != EPI_QKV) {
         // 64 < M <= g_chunk_max_m (large decode batches): the tile kernels would launch only N/128 * M/128 workgroups, far
         // too few to stream the weights at HBM rate.  Run the decode form over ceil(M/64) groups of 64 activation rows
@@ -1933,7 +1936,7 @@ static inline void launch_gemm_bf16(hipStream_t st, const GemmArgs& a) {
             c.m_passes = cdiv(a.M, 64);
             const bool ok = g_pass_interleave ? launch_gemm_skinny_bf16<EPI, OutT>(st, c)
                                               : launch_skinny_passes_serial<EPI, OutT>(st, c);
-            if (ok) return;
+            if (ok) { t_gemm_ran = NVL_GEMM_RAN_GROUPS; return; }
         }
     }
     if (a.rs_in || a.rs_out) throw std::runtime_error("gemm: a deferred-RMSNorm projection did not fit the decode kernels");
@@ -1943,9 +1946,11 @@ static inline void launch_gemm_bf16(hipStream_t st, const GemmArgs& a) {
             if (g_force_tile == 0 && t3 >= 192 && cu_fill(t3, 1) >= 0.74 && a.K >= 160 && !a.seg && !a.a_rows) {
                 NVL_LDS_ATTR((gemm_bf16_pp_kernel<EPI, OutT, 4, 0, 2>), 4 * 32 * 1024);     // the ping-pong form, wave tile 64x128
                 hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI, OutT, 4, 0, 2>), dim3(t3), dim3(512), 4 * 32 * 1024, st, a);
+                t_gemm_ran = NVL_GEMM_RAN_HD128_PINGPONG;
                 return;
             }
             launch_gemm_tile<256, 256, 4, 2, 2, EPI, OutT>(st, a);
+            t_gemm_ran = NVL_GEMM_RAN_HD128_4X2;
             return;
         }
     }
@@ -1965,6 +1970,7 @@ static inline void launch_gemm_bf16(hipStream_t st, const GemmArgs& a) {
         NVL_LDS_ATTR((gemm_bf16_pp_kernel<EPI, OutT, ST, PR>), ST * 32 * 1024);                                        \
         hipLaunchKernelGGL((gemm_bf16_pp_kernel<EPI, OutT, ST, PR>), dim3(cdiv(a.M, 256) * cdiv(a.N, 256)), dim3(512), \
                            ST * 32 * 1024, st, a);                                                                     \
+        t_gemm_ran = NVL_GEMM_RAN_PINGPONG;                                                                            \
         return;                                                                                                        \
     }
     NVL_PP(5, 4, 0)      // the default large-M form: 4-slot ring (5 slots: -3 %, 3 slots: -3 %, r01 sweep)
@@ -1972,6 +1978,7 @@ static inline void launch_gemm_bf16(hipStream_t st, const GemmArgs& a) {
     if (tile == 3) launch_gemm_tile<256, 256, 2, 4, 2, EPI, OutT>(st, a);
     else if (tile == 2) launch_gemm_tile<256, 128, 4, 2, 3, EPI, OutT>(st, a);
     else launch_gemm_tile<128, 128, 2, 2, 2, EPI, OutT>(st, a);
+    t_gemm_ran = tile == 3 ? NVL_GEMM_RAN_TILE3 : (tile == 2 ? NVL_GEMM_RAN_TILE2 : NVL_GEMM_RAN_TILE1);
 }
 
 template <int EPI, typename OutT>

@@ -184,6 +184,8 @@ struct nvl_model {
     int sk_rows = 64;             // rows the sk_part slices are allocated for
     int pending_from = 0;         // which residual projection left the pending slices (0 = O projection, 1 = FFN-down)
     int dense_ran[NVL_DENSE_RAN_INTS] = {0};   // what the residual projections and norms of the last layer tail ran (nvllm.h NVL_DENSE_RAN_*; resid_gemm / launch_norm write it, nvl_op_dense_stages reports it)
+    int gemm_ran = 0, norm_ran = 0;   // the last bf16 projection's instance (NVL_GEMM_RAN_*, gemm()) and the last norm launch's kernel (NVL_NORM_RAN_*, launch_norm)
+    int front_ran[NVL_QKV_RAN_INTS] = {0};     // what the last layer front ran (nvllm.h NVL_QKV_RAN_*; embed / qkv_front write it, nvl_op_qkv_stages reports it)
     const int32_t* pending_slot_of = nullptr; const float* pending_gate_w = nullptr;   // MoE combine folded into the next norm
     // per-call metadata (one pinned host block mirrored on the device)
     int32_t* meta_host = nullptr; int32_t* meta_dev = nullptr; int64_t meta_ints = 0;

@@ -192,6 +192,7 @@ void gemm(nvl_model* m, int epi, bool out_f32, GemmArgs a, double flops = -1.0) 
         : wbytes + (double)a.M * a.K * (double)m->wsize + (double)a.M * a.N * (out_f32 || epi == EPI_RESID ? 4.0 : (double)m->wsize);
     KScope ks(m, KC_GEMM, flops >= 0 ? flops : 2.0 * (double)a.M * (double)a.N * (double)a.K, -1, gbytes);
     hipStream_t st = m->stream;
+    m->gemm_ran = NVL_GEMM_RAN_NONE;      // (the instance of a bf16 projection, for nvl_op_qkv_stages: launch_gemm_bf16 names it)
     if (q) {     // the same dispatch on the kernels of the weight's format / dequantize + tile (wq.h)
         if (q->wf == WF_FP8) gemm_q<WF_FP8>(m, epi, out_f32, a, *q);
         else if (wf_base(q->wf) == WF_INT4) gemm_q<WF_INT4>(m, epi, out_f32, a, *q);
@@ -218,6 +219,7 @@ void gemm(nvl_model* m, int epi, bool out_f32, GemmArgs a, double flops = -1.0) 
             case EPI_QKV:    launch_gemm_bf16<EPI_QKV, bf16_t>(st, a); break;
             default: throw std::runtime_error("gemm: bad epilogue");
         }
+        m->gemm_ran = t_gemm_ran;
     }
     NVL_HIP(hipGetLastError());
 }
@@ -1424,6 +1426,7 @@ void launch_norm(nvl_model* m, float* x, const int32_t* rows_idx, const float* w
         if (!row_kernel && !tile_kernel) throw std::runtime_error("norm: no kernel for this pending residual");
     }
     if (rows <= 512 && m->H <= 1024 * NORM_ROW_MAXCH) {
+        m->norm_ran = rows_idx ? NVL_NORM_RAN_ROW_IDX : NVL_NORM_RAN_ROW;
         if (consumed) *consumed = rows_idx ? NVL_NORM_RAN_ROW_IDX : NVL_NORM_RAN_ROW;
         hipLaunchKernelGGL((norm_row_kernel<ActT>), dim3(rows), dim3(256), 0, m->stream, x, rows_idx, w, b,
                            m->cfg.norm_eps, (ActT*)y, m->H, pr);
@@ -1435,13 +1438,16 @@ void launch_norm(nvl_model* m, float* x, const int32_t* rows_idx, const float* w
             hipLaunchKernelGGL((norm_tile16_kernel<CH, PEND>), dim3(cdiv(rows, 16)), dim3(1024), (size_t)16 * m->H * 2, m->stream, x, \
                                rows_idx, w, b, m->cfg.norm_eps, (bf16_t*)y, rows, m->H, pr);                            \
         } while (0)
+        m->norm_ran = NVL_NORM_RAN_TILE16;
         if (consumed) *consumed = NVL_NORM_RAN_TILE16;
         if (pr.part) NVL_NT16(8, true);        // (H <= 2048: checked above)
         else { if (m->H <= 2048) NVL_NT16(8, false); else NVL_NT16(16, false); }
 #undef NVL_NT16
-    } else
+    } else {
+        m->norm_ran = NVL_NORM_RAN_WAVE;
         hipLaunchKernelGGL((norm_kernel<ActT>), dim3(cdiv(rows, 4)), dim3(256), 0, m->stream, x, rows_idx, w, b,
                            m->cfg.norm_eps, (ActT*)y, rows, m->H);
+    }
 }
 void norm(nvl_model* m, float* x, const int32_t* rows_idx, const DevTensor& w, const DevTensor& b, void* y, int rows) {
     if (m->f32) launch_norm<float>(m, x, rows_idx, (const float*)w.p, (const float*)b.p, y, rows);
@@ -2075,6 +2081,80 @@ void tap_layer(nvl_model* m, int li, int M) {
     NVL_HIP(hipGetLastError());
 }
 
+// ---- embed (generic_model.go:295-302): tokens -> the residual stream m->x, by the kernel of the table's format ----
+void embed(nvl_model* m, const Meta& md, int M) {
+    const nvl_model_config& c = m->cfg;
+    const int H = m->H;
+    KScope ks(m, KC_OTHER, 0, KS_EMBED, (double)M * H * (4.0 + (double)m->wsize));
+    const void* pe = (c.position_type == NVL_POS_LEARNED) ? m->g[NVL_T_POS_EMB].p : nullptr;
+    const int pe_rows = pe ? (int)std::min<int64_t>(m->g[NVL_T_POS_EMB].rows, c.max_seq_len) : 0;
+    if (m->f32) {
+        m->front_ran[NVL_QKV_RAN_EMBED] = NVL_EMBED_RAN_F32;
+        hipLaunchKernelGGL((embed_kernel<float, false>), dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
+                           (const float*)m->g[NVL_T_TOK_EMB].p, (const float*)pe, pe_rows, c.embedding_multiplier, m->x, H);
+    } else if (m->g[NVL_T_TOK_EMB].wf == WF_MXFP4) {     // MXFP4 tied table (w4.h)
+        m->front_ran[NVL_QKV_RAN_EMBED] = NVL_EMBED_RAN_W4;
+        hipLaunchKernelGGL(embed_w4_kernel, dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
+                           (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const uint8_t*)m->g[NVL_T_TOK_EMB].qs, (const bf16_t*)pe, pe_rows,
+                           c.embedding_multiplier, m->x, H);
+    } else if (m->g[NVL_T_TOK_EMB].qs) {     // 8-bit tied table (w8.h)
+        m->front_ran[NVL_QKV_RAN_EMBED] = NVL_EMBED_RAN_W8;
+        hipLaunchKernelGGL(embed_w8_kernel, dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
+                           (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const float*)m->g[NVL_T_TOK_EMB].qs, (const bf16_t*)pe, pe_rows,
+                           c.embedding_multiplier, m->x, H);
+    } else {
+        m->front_ran[NVL_QKV_RAN_EMBED] = NVL_EMBED_RAN_BF16;
+        hipLaunchKernelGGL((embed_kernel<bf16_t, true>), dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
+                           (const bf16_t*)m->g[NVL_T_TOK_EMB].p, (const bf16_t*)pe, pe_rows, c.embedding_multiplier, m->x, H);
+    }
+    NVL_HIP(hipGetLastError());
+}
+
+// ---- the front of an attention layer: attention norm -> QKV projection (+ bias) -> RoPE -> Q into m->q, K / V into the
+// cache (enqueue_forward; nvl_op_qkv_stages).  m->xn holds the projection's operand already, and no norm runs, when the
+// layer before deferred it (qkv_deferred: xn_raw + the x^2 partials) or the decode seam left it (seam_operand).  Returns fused_dec: the
+// projection only stored its fp32 rows, RoPE and the K / V append are left to the decode attention kernel.
+// What ran goes to m->front_ran (NVL_QKV_RAN_*).
+bool qkv_front(nvl_model* m, const LayerW& l, int li, const Meta& md, int M, int max_len, bool big_decode, bool qkv_deferred,
+               bool seam_operand) {
+    const int H = m->H;
+    m->front_ran[NVL_QKV_RAN_NORM] = 0;
+    if (!qkv_deferred && !seam_operand) {
+        norm(m, m->x, nullptr, l.t[NVL_T_ATTN_NORM_W], l.t[NVL_T_ATTN_NORM_B], m->xn, M);
+        m->front_ran[NVL_QKV_RAN_NORM] = m->norm_ran;
+    }
+    bool fused_dec = false;
+    // a decode batch of 64 < M <= g_chunk_max_m rows keeps the decode form (64-row passes, gemm.h) and the fused
+    // decode attention
+    // short prefill batches (65..g_qkv_store_max_m tokens): the fused-epilogue tile kernel would run on M/128 * 24
+    // workgroups; the decode form + rope_kv_kernel is faster there
+    const bool short_prefill = max_len > 1 && M <= g_qkv_store_max_m && M <= g_chunk_max_m && g_force_tile == 0;
+    if (!m->f32 && !m->kv8 && M > 64 && !big_decode && !short_prefill) {
+        // prefill: RoPE + Q/K/V placement fused into the projection's epilogue (no fp32 qkv round trip)
+        GemmArgs a = mk(m->xn, H, l.w_qkv, nullptr, 0, l.b_qkv, 1.f, M, m->n_qkv, H);
+        a.qkv.tok_pos = md.tok_pos; a.qkv.tok_tbl = md.tok_tbl; a.qkv.blk_table = md.blk_table; a.qkv.cos_t = m->rope_cos; a.qkv.sin_t = m->rope_sin;
+        a.qkv.q_out = (bf16_t*)m->q;
+        a.qkv.kcache = (bf16_t*)m->kcache + (int64_t)li * m->layer_stride;
+        a.qkv.vcache = (bf16_t*)m->vcache + (int64_t)li * m->layer_stride;
+        a.qkv.slot_stride = m->slot_stride; a.qkv.Tmax = m->Tmax; a.qkv.nH = m->nH; a.qkv.nKV = m->nKV; a.qkv.hd = m->hd;
+        m->site = KS_QKV;
+        gemm(m, EPI_QKV, false, a);
+        m->front_ran[NVL_QKV_RAN_FORM] = NVL_QKV_FORM_EPILOGUE;
+    } else {
+        GemmArgs aq = mk(m->xn, H, l.w_qkv, m->qkv, m->n_qkv, l.b_qkv, 1.f, M, m->n_qkv, H);
+        if (qkv_deferred) set_deferred_in(m, aq);
+        m->site = KS_QKV;
+        gemm(m, EPI_STORE, true, aq);
+        fused_dec = !m->f32 && !m->kv8 && max_len == 1;     // decode: RoPE + KV append live in the attention kernel
+        if (!fused_dec) rope_kv(m, li, md, M);     // (8-bit mode: always here — rope_kv8_kernel is its only K/V writer)
+        m->front_ran[NVL_QKV_RAN_FORM] = fused_dec ? NVL_QKV_FORM_STORE_ONLY : m->kv8 ? NVL_QKV_FORM_STORE_ROPE_KV8
+            : m->f32 ? NVL_QKV_FORM_F32_STORE_ROPE
+            : m->gemm_ran == NVL_GEMM_RAN_GROUPS ? NVL_QKV_FORM_GROUPS_STORE_ROPE : NVL_QKV_FORM_DECODE_STORE_ROPE;
+    }
+    m->front_ran[NVL_QKV_RAN_GEMM] = m->gemm_ran;
+    return fused_dec;
+}
+
 // What a pass decides once, for all of its layers, about the dense layer tail (enqueue_forward; nvl_op_dense_stages).
 // decode, RMSNorm + SwiGLU, sequential block: every residual projection carries the norm that follows it (deferred
 // RMSNorm, gemm.h), so a step keeps ONE norm launch (layer 0's, after the embedding) instead of 2L + 1
@@ -2301,27 +2381,7 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
     }
     m->hidden_last_M = M;
 
-    // ---- embed (generic_model.go:295-302) -------------------------------------------------
-    if (!(seam & 1)) {
-        KScope ks(m, KC_OTHER, 0, KS_EMBED, (double)M * H * (4.0 + (double)m->wsize));
-        const void* pe = (c.position_type == NVL_POS_LEARNED) ? m->g[NVL_T_POS_EMB].p : nullptr;
-        const int pe_rows = pe ? (int)std::min<int64_t>(m->g[NVL_T_POS_EMB].rows, c.max_seq_len) : 0;
-        if (m->f32)
-            hipLaunchKernelGGL((embed_kernel<float, false>), dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
-                               (const float*)m->g[NVL_T_TOK_EMB].p, (const float*)pe, pe_rows, c.embedding_multiplier, m->x, H);
-        else if (m->g[NVL_T_TOK_EMB].wf == WF_MXFP4)     // MXFP4 tied table (w4.h)
-            hipLaunchKernelGGL(embed_w4_kernel, dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
-                               (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const uint8_t*)m->g[NVL_T_TOK_EMB].qs, (const bf16_t*)pe, pe_rows,
-                               c.embedding_multiplier, m->x, H);
-        else if (m->g[NVL_T_TOK_EMB].qs)     // 8-bit tied table (w8.h)
-            hipLaunchKernelGGL(embed_w8_kernel, dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
-                               (const uint8_t*)m->g[NVL_T_TOK_EMB].p, (const float*)m->g[NVL_T_TOK_EMB].qs, (const bf16_t*)pe, pe_rows,
-                               c.embedding_multiplier, m->x, H);
-        else
-            hipLaunchKernelGGL((embed_kernel<bf16_t, true>), dim3(M), dim3(256), 0, m->stream, md.tokens, md.tok_pos,
-                               (const bf16_t*)m->g[NVL_T_TOK_EMB].p, (const bf16_t*)pe, pe_rows, c.embedding_multiplier, m->x, H);
-        NVL_HIP(hipGetLastError());
-    }
+    if (!(seam & 1)) embed(m, md, M);
 
     const TailPlan tp_ = tail_plan(m, M, n_seqs, max_len, flags);
     const bool big_decode = tp_.big_decode;
@@ -2357,34 +2417,8 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
             tap_layer(m, li, M);
             continue;
         }
-        const bool qkv_deferred = xn_deferred;
-        if (!xn_deferred && !(li == 0 && (seam & 1)))
-            norm(m, m->x, nullptr, l.t[NVL_T_ATTN_NORM_W], l.t[NVL_T_ATTN_NORM_B], m->xn, M);
+        const bool fused_dec = qkv_front(m, l, li, md, M, max_len, big_decode, xn_deferred, li == 0 && (seam & 1));
         xn_deferred = false;
-        bool fused_dec = false;
-        // a decode batch of 64 < M <= g_chunk_max_m rows keeps the decode form (64-row passes, gemm.h) and the fused
-        // decode attention
-        // short prefill batches (65..g_qkv_store_max_m tokens): the fused-epilogue tile kernel would run on M/128 * 24
-        // workgroups; the decode form + rope_kv_kernel is faster there
-        const bool short_prefill = max_len > 1 && M <= g_qkv_store_max_m && M <= g_chunk_max_m && g_force_tile == 0;
-        if (!m->f32 && !m->kv8 && M > 64 && !big_decode && !short_prefill) {
-            // prefill: RoPE + Q/K/V placement fused into the projection's epilogue (no fp32 qkv round trip)
-            GemmArgs a = mk(m->xn, H, l.w_qkv, nullptr, 0, l.b_qkv, 1.f, M, m->n_qkv, H);
-            a.qkv.tok_pos = md.tok_pos; a.qkv.tok_tbl = md.tok_tbl; a.qkv.blk_table = md.blk_table; a.qkv.cos_t = m->rope_cos; a.qkv.sin_t = m->rope_sin;
-            a.qkv.q_out = (bf16_t*)m->q;
-            a.qkv.kcache = (bf16_t*)m->kcache + (int64_t)li * m->layer_stride;
-            a.qkv.vcache = (bf16_t*)m->vcache + (int64_t)li * m->layer_stride;
-            a.qkv.slot_stride = m->slot_stride; a.qkv.Tmax = m->Tmax; a.qkv.nH = m->nH; a.qkv.nKV = m->nKV; a.qkv.hd = m->hd;
-            m->site = KS_QKV;
-            gemm(m, EPI_QKV, false, a);
-        } else {
-            GemmArgs aq = mk(m->xn, H, l.w_qkv, m->qkv, m->n_qkv, l.b_qkv, 1.f, M, m->n_qkv, H);
-            if (qkv_deferred) set_deferred_in(m, aq);
-            m->site = KS_QKV;
-            gemm(m, EPI_STORE, true, aq);
-            fused_dec = !m->f32 && !m->kv8 && max_len == 1;     // decode: RoPE + KV append live in the attention kernel
-            if (!fused_dec) rope_kv(m, li, md, M);     // (8-bit mode: always here — rope_kv8_kernel is its only K/V writer)
-        }
         if (m->kv8)
             attention_kv8(m, md, n_seqs, max_len, (char*)m->kcache + (size_t)li * m->layer_stride,
                           (char*)m->vcache + (size_t)li * m->layer_stride, m->k_scale[li], m->v_scale[li]);

@@ -698,6 +698,179 @@ extern "C" int nvl_op_attention_batch(int device, int precision, int form, int n
     OP_CATCH
 }
 
+// The front of an attention layer on a paged batch, stage by stage: the forward pass's own embed() and qkv_front() — attention
+// norm, QKV projection (+ bias), RoPE, Q into the attention operand buffer, K / V into the cache — under the decisions
+// qkv_front() takes (the EPI_QKV tile kernels; the decode-form projection + rope_kv_kernel; rope_kv8_kernel; the fp32
+// kernels; a bf16 decode step's bare projection), on a model set up as nvl_create sets a paged one up (Tmax = the block size,
+// blocks_per_seq = the table's stride, one layer) and metadata as plan_paged / plan_rows leave it.  Every output and scratch
+// buffer starts as 0xFF bytes, the q buffer whole 256-row tiles of them: a padded row m >= M that a tile kernel stored shows.
+// THE NON-DEFERRED OPERAND PATH ONLY: the deferred-RMSNorm operand into the QKV projection is held by nvl_op_dense_stages
+// (yn with has_next = 1), the fused decode append (what NVL_QKV_FORM_STORE_ONLY leaves to the attention kernel) by
+// nvl_op_attention_batch (NVL_ATTN_OP_FUSED).  Nothing that could index outside the pools or the tables reaches a kernel:
+// every table entry, used or not, and every token id is checked first.
+extern "C" int nvl_op_qkv_stages(int device, int precision, const nvl_qkv_stages* d) {
+    const char* who = "nvl_op_qkv_stages: ";
+    if (!d || d->struct_bytes != (int32_t)sizeof(nvl_qkv_stages) || (precision != NVL_PRECISION_BF16 && precision != NVL_PRECISION_F32))
+        return op_fail(std::string(who) + "bad arguments (struct_bytes = sizeof(nvl_qkv_stages))");
+    const int nH = d->nH, nKV = d->nKV, hd = d->hd, H = d->hidden, n_seqs = d->n_seqs, bs = d->block_size, stride = d->tbl_stride;
+    const bool kv8 = d->kv8 != 0, embed_stage = d->tokens != nullptr;
+    if (!d->seq_len || !d->seq_pos || !d->block_table || !d->w_qkv || !d->k_pool || !d->v_pool || !d->x || !d->op || !d->qkv || !d->q || !d->ran)
+        return op_fail(std::string(who) + "null argument");
+    if (nH <= 0 || nKV <= 0 || nH % nKV || (hd != 64 && hd != 128) || H <= 0 || H % 64 || n_seqs <= 0 || n_seqs > 4096 || d->n_blocks <= 0 ||
+        bs <= 0 || bs % 64 || stride <= 0 || d->max_seq <= 0 || (d->kv8 != 0 && d->kv8 != 1))
+        return op_fail(std::string(who) + "bad shape (hd 64 / 128, hidden % 64, block_size % 64)");
+    if (kv8 && precision != NVL_PRECISION_BF16) return op_fail(std::string(who) + "the 8-bit cache is bf16 only");
+    if (kv8 && (!(d->k_scale > 0.f) || !(d->v_scale > 0.f) || !std::isfinite(d->k_scale) || !std::isfinite(d->v_scale)))
+        return op_fail(std::string(who) + "k_scale / v_scale must be finite and positive");
+    if (!(d->rope_base >= 0.0) || !std::isfinite(d->rope_base)) return op_fail(std::string(who) + "rope_base must be finite and >= 0");
+    if ((d->norm_type != NVL_NORM_RMS && d->norm_type != NVL_NORM_LAYER) || !(d->norm_eps >= 0.f) || !std::isfinite(d->norm_eps))
+        return op_fail(std::string(who) + "bad norm_type / norm_eps");
+    if (d->norm_w && d->norm_type == NVL_NORM_LAYER && !d->norm_b) return op_fail(std::string(who) + "LayerNorm needs its bias");
+    if (d->norm_b && (!d->norm_w || d->norm_type != NVL_NORM_LAYER)) return op_fail(std::string(who) + "norm_b belongs to a LayerNorm");
+    if (embed_stage && (!d->tok_pos || !d->emb || d->vocab <= 0 || !d->norm_w || (d->pos_emb && d->pos_rows <= 0) || !std::isfinite(d->embedding_multiplier)))
+        return op_fail(std::string(who) + "the embedding stage needs tokens, tok_pos, emb [vocab][hidden] and a norm behind it");
+    // plan_paged's refusals, in its order, then the rest of the table and the token rows
+    int64_t tokens = 0;
+    int max_len = 0;
+    for (int i = 0; i < n_seqs; i++) {
+        if (d->seq_len[i] <= 0 || d->seq_len[i] > (1 << 16)) return op_fail(std::string(who) + "sequence without rows (or more than 65536)");
+        if (d->seq_pos[i] < 0) return op_fail(std::string(who) + "negative position");
+        if (d->seq_pos[i] > d->max_seq - d->seq_len[i]) return op_fail(std::string(who) + "position exceeds max_seq", NVL_ERR_POSITION);
+        if (stride < cdiv((int64_t)d->seq_pos[i] + d->seq_len[i], bs)) return op_fail(std::string(who) + "block table shorter than the positions it must cover");
+        tokens += d->seq_len[i];
+        max_len = std::max(max_len, d->seq_len[i]);
+    }
+    if (tokens > (1 << 16)) return op_fail(std::string(who) + "more than 65536 rows");
+    for (int64_t i = 0; i < (int64_t)n_seqs * stride; i++)
+        if (d->block_table[i] < 0 || d->block_table[i] >= d->n_blocks) return op_fail(std::string(who) + "block id out of range");
+    for (int64_t t = 0; embed_stage && t < tokens; t++) {
+        if (d->tokens[t] < 0 || d->tokens[t] >= d->vocab) return op_fail(std::string(who) + "token id out of range");
+        if (d->tok_pos[t] < 0) return op_fail(std::string(who) + "negative position");
+    }
+    OP_TRY
+    OpCtx cx(device, precision);
+    nvl_model& m = cx.m;
+    auto nan_fill = [&](int64_t bytes) { void* p = cx.alloc(bytes); NVL_HIP(hipMemsetAsync(p, 0xFF, (size_t)bytes, m.stream)); return p; };
+    const int M = (int)tokens;
+    const int64_t qw = (int64_t)nH * hd, n_el = (int64_t)d->n_blocks * nKV * bs * hd, Mp = round_up(M, 64), Mq = round_up(M, 256);
+    m.H = H; m.nH = nH; m.nKV = nKV; m.group = nH / nKV; m.hd = hd; m.L = 1; m.n_qkv = (nH + 2 * nKV) * hd;
+    m.paged = 1; m.Tmax = bs; m.num_blocks = d->n_blocks; m.blocks_per_seq = stride;
+    m.layer_stride = (int64_t)nKV * bs * hd; m.slot_stride = m.layer_stride;
+    m.kv8 = kv8; m.kv_esize = kv8 ? 1 : (int)m.wsize;
+    m.k_scale.assign(1, d->k_scale); m.v_scale.assign(1, d->v_scale);
+    m.cfg.norm_type = d->norm_type; m.cfg.norm_eps = d->norm_eps; m.cfg.max_seq_len = d->max_seq;
+    m.cfg.position_type = d->pos_emb ? NVL_POS_LEARNED : (d->rope_base > 0.0 ? NVL_POS_ROPE : NVL_POS_NONE);
+    m.cfg.embedding_multiplier = d->embedding_multiplier;
+    m.keep_hidden = false;
+    // workspaces (nvl_create, max_batch_tokens = tokens; q in whole 256-row tiles)
+    m.x = embed_stage ? (float*)nan_fill((int64_t)M * H * 4) : cx.up_f32(d->x, (int64_t)M * H);
+    m.xn = d->norm_w ? nan_fill(Mp * H * (int64_t)m.wsize) : cx.up_mat(d->x, M, H, false);
+    m.qkv = (float*)nan_fill((int64_t)M * m.n_qkv * 4);
+    m.q = nan_fill(Mq * qw * (int64_t)m.wsize);
+    if (kv8) {      // the 8-bit blocks, written by the shared quantizer from the fp32 values
+        const float* dk = cx.up_f32(d->k_pool, n_el);
+        const float* dv = cx.up_f32(d->v_pool, n_el);
+        m.kcache = cx.alloc(n_el); m.vcache = cx.alloc(n_el);
+        const unsigned qblocks = (unsigned)cdiv(cdiv(n_el, 4), 256);
+        hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dk, n_el, d->k_scale, (uint8_t*)m.kcache);
+        hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dv, n_el, d->v_scale, (uint8_t*)m.vcache);
+        NVL_HIP(hipGetLastError());
+    } else {
+        m.kcache = cx.up_mat(d->k_pool, 1, n_el, false, 1, true);
+        m.vcache = cx.up_mat(d->v_pool, 1, n_el, false, 1, true);
+    }
+    if (d->rope_base > 0.0) {
+        std::vector<float> ct, st;
+        rope_tables(d->rope_base, d->max_seq, hd, ct, st);
+        m.rope_cos = cx.up_f32(ct.data(), (int64_t)ct.size());
+        m.rope_sin = cx.up_f32(st.data(), (int64_t)st.size());
+    }
+    // weights (finalize's forms)
+    LayerW l;
+    l.w_qkv = cx.up_mat(d->w_qkv, m.n_qkv, H, false, W_ROW_PAD);
+    l.n_qkv = m.n_qkv;
+    if (d->b_qkv) l.b_qkv = cx.up_f32(d->b_qkv, m.n_qkv);
+    if (d->norm_w) l.t[NVL_T_ATTN_NORM_W].p = cx.up_f32(d->norm_w, H);
+    if (d->norm_b) l.t[NVL_T_ATTN_NORM_B].p = cx.up_f32(d->norm_b, H);
+    if (embed_stage) {
+        m.g[NVL_T_TOK_EMB].p = cx.up_mat(d->emb, d->vocab, H, false, W_ROW_PAD);
+        if (d->pos_emb) { m.g[NVL_T_POS_EMB].p = cx.up_mat(d->pos_emb, d->pos_rows, H, false, W_ROW_PAD); m.g[NVL_T_POS_EMB].rows = d->pos_rows; }
+    }
+    // the pass's metadata as plan_paged / plan_rows leave it:
+    // [tok_start | len | pos | tbl | the table, verbatim | tokens | tok_pos | tok_tbl | the embedding stage's own tok_pos]
+    const size_t S = (size_t)n_seqs, T = (size_t)n_seqs * stride;
+    std::vector<int32_t> meta(4 * S + T + 4 * (size_t)M, 0);
+    int32_t *h_tok = &meta[4 * S + T], *h_pos = h_tok + M, *h_tbl = h_pos + M, *h_epos = h_tbl + M;
+    for (int i = 0, t = 0; i < n_seqs; i++) {
+        meta[(size_t)i] = t; meta[S + i] = d->seq_len[i]; meta[2 * S + i] = d->seq_pos[i]; meta[3 * S + i] = i * stride;
+        for (int j = 0; j < d->seq_len[i]; j++, t++) {
+            h_tok[t] = embed_stage ? d->tokens[t] : 0; h_pos[t] = d->seq_pos[i] + j; h_tbl[t] = i * stride;
+            h_epos[t] = embed_stage ? d->tok_pos[t] : h_pos[t];
+        }
+    }
+    memcpy(&meta[4 * S], d->block_table, T * 4);
+    int32_t* dmeta = (int32_t*)cx.alloc((int64_t)meta.size() * 4);
+    NVL_HIP(hipMemcpyAsync(dmeta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, m.stream));
+    Meta md{};
+    md.seq_tok_start = dmeta; md.seq_len = dmeta + S; md.seq_pos = dmeta + 2 * S; md.seq_tbl = dmeta + 3 * S; md.blk_table = dmeta + 4 * S;
+    md.tokens = md.blk_table + T; md.tok_pos = md.tokens + M; md.tok_tbl = md.tok_pos + M;
+    Meta md_embed = md;
+    md_embed.tok_pos = md.tok_tbl + M;
+    auto release = [&]() {                             // everything is owned by cx.bufs
+        m.x = nullptr; m.xn = m.q = m.kcache = m.vcache = nullptr; m.qkv = nullptr; m.rope_cos = m.rope_sin = nullptr;
+        for (auto& t : l.t) t.p = nullptr;
+        l.w_qkv = nullptr; l.b_qkv = nullptr;
+        m.g[NVL_T_TOK_EMB].p = nullptr; m.g[NVL_T_POS_EMB].p = nullptr;
+    };
+    try {
+        std::fill(m.front_ran, m.front_ran + NVL_QKV_RAN_INTS, 0);
+        m.phase = max_len > 1 ? 0 : 1;
+        if (embed_stage) embed(&m, md_embed, M);
+        const bool big_decode = tail_plan(&m, M, n_seqs, max_len, 0).big_decode;
+        qkv_front(&m, l, 0, md, M, max_len, big_decode, false, d->norm_w == nullptr);
+        // ---- read back
+        NVL_HIP(hipStreamSynchronize(m.stream));
+        for (int i = 0; i < NVL_QKV_RAN_INTS; i++) d->ran[i] = m.front_ran[i];
+        if (embed_stage) cx.down(d->x, m.x, (int64_t)M * H);
+        auto widen = [&](float* dst, const void* src, int64_t n) {      // n row-major elements of the activation type -> fp32
+            if (m.f32) { cx.down(dst, src, n); return; }
+            std::vector<uint16_t> b((size_t)n);
+            NVL_HIP(hipMemcpyAsync(b.data(), src, (size_t)n * 2, hipMemcpyDeviceToHost, m.stream));
+            NVL_HIP(hipStreamSynchronize(m.stream));
+            for (int64_t i = 0; i < n; i++) { const uint32_t u = ((uint32_t)b[(size_t)i]) << 16; memcpy(&dst[i], &u, 4); }
+        };
+        if (m.f32) {
+            cx.down(d->op, m.xn, (int64_t)M * H);
+        } else {        // the fragment-major operand
+            std::vector<uint16_t> ob((size_t)(round_up(M, 16) * H));
+            NVL_HIP(hipMemcpyAsync(ob.data(), m.xn, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
+            NVL_HIP(hipStreamSynchronize(m.stream));
+            for (int64_t r = 0; r < M; r++)
+                for (int64_t c = 0; c < H; c++) {
+                    const uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, H)]) << 16;
+                    memcpy(&d->op[(size_t)(r * H + c)], &u, 4);
+                }
+        }
+        cx.down(d->qkv, m.qkv, (int64_t)M * m.n_qkv);
+        widen(d->q, m.q, Mq * qw);
+        for (int which = 0; which < 2; which++) {
+            float* dst = which ? d->v_pool : d->k_pool;
+            const void* src = which ? m.vcache : m.kcache;
+            if (!kv8) { widen(dst, src, n_el); continue; }
+            std::vector<uint8_t> codes((size_t)n_el);
+            NVL_HIP(hipMemcpyAsync(codes.data(), src, (size_t)n_el, hipMemcpyDeviceToHost, m.stream));
+            NVL_HIP(hipStreamSynchronize(m.stream));
+            const float sc = which ? d->v_scale : d->k_scale;
+            for (int64_t i = 0; i < n_el; i++) dst[i] = e4m3fn_value(codes[(size_t)i]) * sc;
+            uint8_t* raw = which ? d->v_codes : d->k_codes;
+            if (raw) memcpy(raw, codes.data(), (size_t)n_el);
+        }
+    } catch (...) { release(); throw; }
+    release();
+    return NVL_OK;
+    OP_CATCH
+}
+
 extern "C" int nvl_op_ffn(int device, int precision, const float* x, const float* w1, const float* b1, const float* w2,
                           const float* b2, int rows, int hidden, int ffn, int swiglu, float* y) {
     if (!x || !w1 || !w2 || !y || rows <= 0 || hidden % 64 || ffn % 64) return op_fail("nvl_op_ffn: bad arguments");

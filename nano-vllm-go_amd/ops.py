@@ -259,7 +259,7 @@ def moe_stages(x, router, w_in, w_out, top_k, precision="bf16", device=0, expert
 
 
 RESID_FORMS = {0: "tile", 1: "msplit", 2: "groups", 3: "groups_serial", 4: "decode"}      # NVL_RESID_FORM_*
-NORM_RAN = {0: None, 1: "row", 2: "row_idx", 3: "tile16"}                                   # NVL_NORM_RAN_*
+NORM_RAN = {0: None, 1: "row", 2: "row_idx", 3: "tile16", 4: "wave"}                        # NVL_NORM_RAN_*
 
 
 def dense_stages(x, attn_out, wo, norm_w, w1, w2, next_norm_w, wn, bo=None, norm_b=None, b1=None, b2=None, next_norm_b=None,
@@ -374,6 +374,61 @@ def attention_batch(q, k_pool, v_pool, block_table, seq_len, seq_pos, nH, form="
     if form == "fused":
         res.update(k_pool=k_pool, v_pool=v_pool)
     return res
+
+
+QKV_FORMS = {1: "f32_store_rope", 2: "decode_store_rope", 3: "groups_store_rope", 4: "epilogue", 5: "store_rope_kv8",
+             6: "store_only"}                                                                    # NVL_QKV_FORM_*
+GEMM_RAN = {0: None, 1: "tile1", 2: "tile2", 3: "tile3", 5: "pingpong", 6: "hd128_4x2", 7: "hd128_pingpong", 8: "decode",
+            9: "groups"}                                                                         # NVL_GEMM_RAN_*
+EMBED_RAN = {0: None, 1: "f32", 2: "bf16", 3: "w8", 4: "w4"}                                    # NVL_EMBED_RAN_*
+
+
+def qkv_stages(x, w_qkv, k_pool, v_pool, block_table, seq_len, seq_pos, nH, b_qkv=None, norm_w=None, norm_b=None, norm="rms",
+               norm_eps=1e-5, rope_base=0.0, max_seq=0, kv8=False, k_scale=1.0, v_scale=1.0, tokens=None, tok_pos=None, emb=None,
+               pos_emb=None, embedding_multiplier=0.0, precision="bf16", device=0):   # generic_model.go:295-318 + rope.go:153
+    """The front of an attention layer on a paged batch, stage by stage (nvl_op_qkv_stages): x [tokens][hidden] (None with the
+    embedding stage: tokens / tok_pos [tokens], emb [V][hidden], pos_emb [P][hidden] or None), the attention norm (norm_w
+    None: x is the operand already), w_qkv [(nH + 2 nKV) hd][hidden] (+ b_qkv), RoPE with rope_base (0: none), Q into the
+    operand buffer, K / V into k_pool / v_pool [n_blocks][nKV][block][hd] through block_table [n_seqs][stride]; sequence i =
+    seq_len[i] rows behind seq_pos[i] cached keys.  max_seq 0 = what the table covers.
+    -> dict(x (the embedding stage's), op [tokens][hidden], qkv [tokens][n_qkv] (NaN in the epilogue form), q [round_up(tokens,
+    256)][nH hd], k_pool, v_pool after the pass (kv8: dequantized, plus k_codes / v_codes), ran = dict(form (a QKV_FORMS
+    name), gemm (GEMM_RAN), norm (NORM_RAN), embed (EMBED_RAN)))."""
+    k_pool, v_pool, w_qkv = _f(k_pool).copy(), _f(v_pool).copy(), _f(w_qkv)
+    tbl = np.ascontiguousarray(block_table, dtype=np.int32)
+    sl, sp = np.ascontiguousarray(seq_len, dtype=np.int32), np.ascontiguousarray(seq_pos, dtype=np.int32)
+    n_blocks, nKV, bs, hd = k_pool.shape
+    if tbl.ndim != 2 or sl.ndim != 1 or sp.ndim != 1:
+        raise ValueError("qkv_stages: shapes do not match")
+    n_seqs, stride = tbl.shape
+    M, (N, H) = int(sl.sum()), w_qkv.shape
+    opt = {k: None if a is None else _f(a) for k, a in dict(b_qkv=b_qkv, norm_w=norm_w, norm_b=norm_b, emb=emb, pos_emb=pos_emb).items()}
+    ints = {k: None if a is None else np.ascontiguousarray(a, dtype=np.int32) for k, a in dict(tokens=tokens, tok_pos=tok_pos).items()}
+    x = np.full((M, H), np.nan, np.float32) if tokens is not None else _f(x).copy()
+    if v_pool.shape != k_pool.shape or sl.shape != (n_seqs,) or sp.shape != (n_seqs,) or N != (nH + 2 * nKV) * hd or x.shape != (M, H) or \
+            any(a is not None and a.shape != s for a, s in ((opt["b_qkv"], (N,)), (opt["norm_w"], (H,)), (opt["norm_b"], (H,)),
+                                                            (ints["tokens"], (M,)), (ints["tok_pos"], (M,)))) or \
+            any(a is not None and (a.ndim != 2 or a.shape[1] != H) for a in (opt["emb"], opt["pos_emb"])):
+        raise ValueError("qkv_stages: shapes do not match")
+    nan = lambda *s: np.full(s, np.nan, np.float32)
+    Mq = -(-M // 256) * 256
+    out = dict(op=nan(M, H), qkv=nan(M, N), q=nan(Mq, nH * hd))
+    codes = dict(k_codes=np.zeros(k_pool.shape, np.uint8), v_codes=np.zeros(k_pool.shape, np.uint8)) if kv8 else {}
+    ran = np.zeros(4, np.int32)
+    d = L.QkvStagesC(struct_bytes=C.sizeof(L.QkvStagesC), kv8=1 if kv8 else 0, nH=nH, nKV=nKV, hd=hd, hidden=H, n_seqs=n_seqs,
+                     tbl_stride=stride, n_blocks=n_blocks, block_size=bs, max_seq=int(max_seq) if max_seq else stride * bs,
+                     norm_type=1 if norm == "rms" else 0, vocab=0 if opt["emb"] is None else opt["emb"].shape[0],
+                     pos_rows=0 if opt["pos_emb"] is None else opt["pos_emb"].shape[0], norm_eps=norm_eps, k_scale=k_scale,
+                     v_scale=v_scale, embedding_multiplier=embedding_multiplier, rope_base=float(rope_base))
+    keep = dict(seq_len=sl, seq_pos=sp, block_table=tbl, w_qkv=w_qkv, x=x, k_pool=k_pool, v_pool=v_pool, ran=ran, **opt, **ints, **out, **codes)
+    for k, v in keep.items():
+        setattr(d, k, None if v is None else v.ctypes.data)
+    L.check(L.lib().nvl_op_qkv_stages(device, L.PRECISION[precision], C.byref(d)))
+    out.update(k_pool=k_pool, v_pool=v_pool, **codes)
+    if tokens is not None:
+        out["x"] = x
+    out["ran"] = dict(form=QKV_FORMS[int(ran[0])], gemm=GEMM_RAN[int(ran[1])], norm=NORM_RAN[int(ran[2])], embed=EMBED_RAN[int(ran[3])])
+    return out
 
 
 def argmax(x, device=0):                                       # argmax cmd/ask/main.go:389

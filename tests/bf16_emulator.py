@@ -29,8 +29,9 @@ def _rms(v, g, eps):
     return v / np.sqrt((v * v).mean(-1, keepdims=True) + eps) * g
 
 
-def layer(x, w, li, cfg, sw):
-    """one decoder layer on the [S, H] stream x; sw = the set of rounding points that are on.  Computes in x.dtype:
+def layer(x, w, li, cfg, sw, tap=None):
+    """one decoder layer on the [S, H] stream x; sw = the set of rounding points that are on; tap (a dict) receives the
+    layer's xn, q, k, v as the attention reads them (tests/test_qkv_reference_host.py).  Computes in x.dtype:
     float64 (the default of forward(): "exact" beside the roundings) or float32 (the 7-8 B-parameter configs: numpy sgemm,
     relative error ~1e-6, three orders below one bf16 rounding — and no float64 copy of every weight matrix)"""
     nH, nKV, hd, F = cfg["num_heads"], cfg["num_kv_heads"], cfg["head_dim"], cfg["ffn_dim"]
@@ -60,6 +61,8 @@ def layer(x, w, li, cfg, sw):
     q = r(rope(q, nH), "q")
     k = r(rope(k, nKV), "k")
     v = r(v.reshape(S, nKV, hd), "v")
+    if tap is not None:
+        tap.update(xn=xn, q=q, k=k, v=v)
     g = nH // nKV
     ao = np.zeros((S, nH, hd), dt)
     mask = np.tril(np.ones((S, S), bool))

@@ -11,7 +11,7 @@ def test_library_exports_every_declared_symbol(pkg):
     names = pkg.declared_symbols()
     assert len(names) >= 30 and "nvl_forward" in names and "nvl_runner_run" in names and "nvl_op_moe_stages" in names
     assert "nvl_op_attention_batch" in names and "nvl_op_dense_stages" in names and "nvl_op_dense_moe_stages" in names
-    assert "nvl_op_moe_stages_q" in names and "nvl_op_dense_moe_stages_q" in names
+    assert "nvl_op_moe_stages_q" in names and "nvl_op_dense_moe_stages_q" in names and "nvl_op_qkv_stages" in names
     missing = [n for n in names if not hasattr(L, n)]
     assert not missing, missing
     assert L.nvl_abi_version() == 3                                 # (nvl_op_moe_stages / nvl_op_attention_batch / nvl_op_dense_stages and the *_q entry points are additions: the version stays)
@@ -145,6 +145,28 @@ def test_attention_batch_refuses_bad_arguments_before_touching_a_device(pkg):
         assert re.search(rf"NVL_ATTN_RAN_{name.upper()} = {code}\b", text), name
     for name, code in pkg.ops.ATTN_OP_FORMS.items():
         assert re.search(rf"NVL_ATTN_OP_{name.upper()} = {code}\b", text), name
+
+
+def test_qkv_stages_struct_and_codes_match_the_header(pkg):
+    """nvl_op_qkv_stages is an addition (the ABI version stays 3): its struct mirror and the names ops.qkv_stages reports
+    match include/nvllm.h.  (Its refusals before the device probe: tests/test_qkv_reference_host.py.)"""
+    text = pkg._lib.HEADER.read_text()
+    assert pkg.lib().nvl_abi_version() == 3
+    assert C.sizeof(pkg._lib.QkvStagesC) == 80 + 20 * C.sizeof(C.c_void_p)
+    fields = re.search(r"typedef struct nvl_qkv_stages \{(.*?)\} nvl_qkv_stages;", text, re.S).group(1)
+    fields = re.sub(r"/\*.*?\*/", "", fields, flags=re.S)
+    names = [n for n in re.findall(r"[*\s,]([A-Za-z_0-9]+)\s*[,;]", fields)]
+    assert names == [n for n, _ in pkg._lib.QkvStagesC._fields_], names
+    for table, prefix in ((pkg.ops.QKV_FORMS, "NVL_QKV_FORM_"), (pkg.ops.GEMM_RAN, "NVL_GEMM_RAN_"), (pkg.ops.EMBED_RAN, "NVL_EMBED_RAN_"),
+                          (pkg.ops.NORM_RAN, "NVL_NORM_RAN_")):
+        for code, name in table.items():
+            if name is not None:
+                assert re.search(rf"{prefix}{name.upper()} = {code}\b", text), name
+    assert re.search(r"NVL_QKV_RAN_FORM = 0, NVL_QKV_RAN_GEMM = 1, NVL_QKV_RAN_NORM = 2, NVL_QKV_RAN_EMBED = 3, NVL_QKV_RAN_INTS = 4\b", text)
+    with pytest.raises(pkg.NvlError) as e:          # a struct of another size is refused
+        d = pkg._lib.QkvStagesC(struct_bytes=8)
+        pkg._lib.check(pkg.lib().nvl_op_qkv_stages(0, 0, C.byref(d)))
+    assert e.value.code == -1
 
 
 def test_product_package_never_imports_the_oracle(pkg):
