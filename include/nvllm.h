@@ -205,6 +205,24 @@ enum { NVL_MAMBA_CONV_PER_CALL = 0,   /* every call zero-pads (mamba2.go:181-254
  * paged and tensor-parallel hybrids stay refused.  No memory is added: the rows live in the buffer the runner's chunked
  * prefill already used.  A decode pass pays no extra launch for it (nvl_set_tuning key 39). */
 int nvl_set_mamba_conv_state(nvl_model* m, int mode);
+/* Speculative decoding on a hybrid model.  A Mamba2 state that a pass of 1 + k rows has advanced cannot
+ * go back to 1 + n_accepted rows, so by default (NONE) every verify entry point refuses a model with Mamba2 layers.  VERIFY
+ * makes the pass not advance it: each Mamba2 layer of a verify pass reads the slot's state and kept convolution rows and
+ * writes neither, and one launch after the accept decision advances both, in every Mamba2 layer, by the rows that stay. */
+enum { NVL_MAMBA_ROLLBACK_NONE   = 0,   /* verify calls refuse a hybrid model: today's behaviour */
+       NVL_MAMBA_ROLLBACK_VERIFY = 1 }; /* verify, then commit the accepted rows                  */
+/* After nvl_create, before nvl_finalize (else NVL_ERR_STATE).  NVL_ERR_INVALID for a NULL model, an unknown mode and a model
+ * without Mamba2 layers.  With VERIFY, nvl_verify_greedy, nvl_decode_greedy_lookup, nvl_verify_sampled,
+ * nvl_decode_sampled_lookup, nvl_verify_speculative and nvl_decode_speculative accept a hybrid TARGET.  Contract of a pass of
+ * 1 + k rows per sequence: row j gets the logits a one-token decode step would give it after rows 0 .. j-1 — under
+ * NVL_MAMBA_CONV_CARRIED its window is the kept rows followed by rows 0 .. j of the pass, under PER_CALL K-1 zeros and the
+ * row itself, as a decode call has it; afterwards state and kept rows of every Mamba2 layer are those of the sequence
+ * advanced by the rows that stay in the cache (1 + n_accepted, or fewer where a loop's last steps cut the run), never by
+ * the 1 + k; a sequence at position 0 starts from a zero state and zero window.  Graph replay included.  Still refused
+ * whatever the mode: nvl_seq_truncate on a hybrid model (a host cannot name a past state), a hybrid DRAFT model
+ * (nvl_draft_sampled, nvl_decode_speculative), paged and tensor-parallel hybrids.  Memory: per Mamba2 layer,
+ * min(max_batch_tokens, 8 x max_seqs) rows of conv_dim + heads floats (twice conv_dim under CARRIED). */
+int nvl_set_mamba_rollback(nvl_model* m, int mode);
 /* Pre-quantized 8-bit weight, taken as it is (the dtype of nvl_load_safetensors' F8_E4M3 tensors): codes [rows][cols] OCP
  * e4m3fn in the checkpoint's [out, in] order (layout must be NVL_LAYOUT_OUT_IN), scales [rows] fp32, W~ = bf16(s * e4m3(q)).
  * Counterpart of nvl_upload_tensor (generic_loader.go:353-604) for a kind this model stores 8-bit; NVL_ERR_INVALID for any
@@ -773,6 +791,17 @@ int nvl_op_mamba_mixer(int device, int precision, const float* proj, int n_seqs,
                        const float* conv_w, const float* conv_b, const float* a_log, const float* D, const float* dt_bias,
                        const float* norm_w, float* state, float* tail, int chain, float* xbc, float* delta, float* y,
                        float* normed);
+/* A Mamba2 layer of a verify pass and the pass's commit (nvl_set_mamba_rollback; csrc/mamba.h mamba_verify_kernel,
+ * mamba_commit_kernel) on nvl_op_mamba_mixer's arguments: every sequence has the same seq_len of 1 .. 8 rows, chain is 0 (per
+ * call) or 3 (carried; a tail is required when K > 1), n_acc[i] = accepted drafts of sequence i (0 .. seq_len - 1).  The verify
+ * launch runs, xbc / delta / y (before gating) and state / tail come back — the latter two as the pass left them, which
+ * must be as they came; then the commit runs and state_commit [n_slots][nh][hd][ss] / tail_commit [n_slots][K-1][conv_dim]
+ * (NULL with tail) hold the buffers advanced by 1 + n_acc[i] rows. */
+int nvl_op_mamba_verify(int device, int precision, const float* proj, int n_seqs, const int32_t* seq_len,
+                        const int32_t* seq_pos, const int32_t* seq_slot, const int32_t* n_acc, int n_slots, int nh, int hd, int ss,
+                        int ng, int K, const float* conv_w, const float* conv_b, const float* a_log, const float* D,
+                        const float* dt_bias, const float* norm_w, float* state, float* tail, int chain, float* xbc, float* delta,
+                        float* y, float* state_commit, float* tail_commit);
 /* 8-bit KV cache.  The device quantizer and read path on an array: codes[i] = e4m3fn(x[i] / scale)
  * (round-to-nearest-even, saturating to +-448, NaN -> NaN code), back[i] = scale * bf16(codes[i]) in fp32. */
 int nvl_op_fp8_kv_roundtrip(int device, const float* x, int64_t n, float scale, uint8_t* codes, float* back);

@@ -43,6 +43,7 @@ GQ_EXPERT_DTYPE = {"none": 0, "uint4": 1}                # NVL_GQE_* (nvl_set_gq
 ACT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                   # NVL_ACT_AUTO / NVL_ACT_FP8_E4M3 (nvl_set_act_dtype)
 EXPERT_DTYPE = {"auto": 0, "fp8_e4m3": 1}                # NVL_EXPERT_AUTO / NVL_EXPERT_FP8_E4M3 (nvl_set_expert_dtype)
 MAMBA_CONV_STATE = {"per_call": 0, "carried": 1}         # NVL_MAMBA_CONV_PER_CALL / NVL_MAMBA_CONV_CARRIED (nvl_set_mamba_conv_state)
+MAMBA_ROLLBACK = {"none": 0, "verify": 1}                # NVL_MAMBA_ROLLBACK_NONE / NVL_MAMBA_ROLLBACK_VERIFY (nvl_set_mamba_rollback)
 DTYPE_F32, DTYPE_BF16, DTYPE_F16 = 0, 1, 2
 LAYOUT_IN_OUT, LAYOUT_OUT_IN = 0, 1
 FWD_ALL_LOGITS = 1
@@ -175,6 +176,7 @@ def lib():
     L.nvl_get_kv.argtypes = [vp, i64, C.c_int, vp, vp]
     L.nvl_get_mamba_state.argtypes = [vp, i64, C.c_int, vp]
     L.nvl_set_mamba_conv_state.argtypes = [vp, C.c_int]
+    L.nvl_set_mamba_rollback.argtypes = [vp, C.c_int]
     L.nvl_get_mamba_conv_state.argtypes = [vp, i64, C.c_int, vp]
     L.nvl_get_weight.argtypes = [vp, C.c_int, C.c_int, vp, i64, i64]
     L.nvl_get_stamps.argtypes = [vp, vp, C.c_int, vp, i64]
@@ -248,6 +250,7 @@ def lib():
     L.nvl_op_attention_batch.argtypes = ([C.c_int] * 6 + [f32, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_double,
                                           C.c_int, f32, f32, vp, vp, vp])
     L.nvl_op_mamba_mixer.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp] + [C.c_int] * 6 + [vp] * 8 + [C.c_int] + [vp] * 4
+    L.nvl_op_mamba_verify.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp] + [C.c_int] * 6 + [vp] * 8 + [C.c_int] + [vp] * 5
     sp = C.POINTER(SamplingParamsC)
     L.nvl_verify_sampled.argtypes = [vp, C.c_int, vp, vp, C.c_int, sp, vp, vp, vp, vp, vp]
     L.nvl_verify_sampled_paged.argtypes = [vp, C.c_int, vp, C.c_int, vp, vp, vp, sp, vp, vp, vp, vp, vp]

@@ -500,4 +500,168 @@ __global__ __launch_bounds__(256) void mamba_gate_norm_kernel(MambaArgs p, ActT*
     }
 }
 
+// ------------------------------------------------------------------------------------------
+// Verify, then commit (NVL_MAMBA_ROLLBACK_VERIFY): a verify pass of S = 1 + k rows per sequence must give row j the output
+// of a one-token decode step after rows 0 .. j-1, and leave state and kept rows advanced by the ACCEPTED rows only — which
+// nobody knows until the LM head and the accept kernel have run.  So the pass reads state and tail and writes neither
+// (mamba_verify_kernel, per Mamba2 layer, in place of conv + tail + scan), keeps what the recurrence consumed, and ONE
+// launch after the accept kernel replays 1 + n_accepted steps of every layer onto the state and shifts the window
+// (mamba_commit_kernel).  The recurrence runs twice over at most 8 rows; each state is read once by the pass, as a decode
+// step reads it, and read and written once by the commit.
+//
+// What the pass keeps, per (Mamba2 layer, token row): its xbc row (the post-conv u, B, C the scan consumed) and its dt —
+// p.xbc / p.delta of the verify launch ARE the layer's keep rows, the model's shared mxbc / mdelta being overwritten by
+// the next layer — and, for a carried model, the raw xBC row the window will hold.  Keeping post-conv values is what lets
+// the commit not convolve: a workgroup that recomputed the convolution would read tail rows another one is shifting.
+// ------------------------------------------------------------------------------------------
+
+// grid (nh, sequences), 256 threads = head_dim x SG lane groups, PER states per thread (mamba_scan_kernel's mapping and
+// geometries); every sequence has S = seq_len rows, 1 .. 8.  Dynamic LDS: S x (hd + 2 ss) operands + S dt values.
+//   phase 0  the state loads are issued (16-byte loads; zeros for a sequence at position 0) — they land under phase 1
+//   phase 1  SiLU(conv + bias) of the S rows for the channels THIS workgroup consumes only — its head's hd u channels, its
+//            group's ss B and ss C channels — from the raw proj rows and, carried (chain 3) and past position 0, the slot's
+//            tail; mamba_conv_kernel's arithmetic (fmaf over k ascending, bias, silu_ref).  chain 0 (per call): every row
+//            is a call of its own, its window K-1 zeros and the row itself.  Results go to LDS, B and C interleaved so
+//            that state n = sg * PER + q sits at q * SG + sg: in phase 2 the lanes of a wave read consecutive words or the
+//            same word.  u is stored by its head, B / C (computed by every head of the group) by the group's first head.
+//   phase 2  S steps of the recurrence from LDS, the scan kernel's expressions and order; y per row; the state is dropped.
+// Slots, positions and row starts come from device memory: nothing of the pass is in the arguments (graph replay).
+template <int PER>
+__global__ __launch_bounds__(256) void mamba_verify_kernel(MambaArgs p, float* __restrict__ raw_keep) {
+    extern __shared__ __attribute__((aligned(16))) char smem_v[];
+    const int h = blockIdx.x, seq = blockIdx.y, tid = threadIdx.x;
+    const int SG = 256 / p.hd, d = tid / SG, sg = tid % SG;
+    const int t0 = p.seq_tok_start[seq], S = p.seq_len[seq], pos = p.seq_pos[seq];
+    const int64_t slot = p.seq_slot[seq];
+    const int nc = p.hd + 2 * p.ss;
+    float* s_x = (float*)smem_v;                     // [S][nc]: u hd | B ss | C ss
+    float* s_dt = s_x + S * nc;                      // [S]
+    // ---- phase 0 ----
+    const float* st = p.state + slot * p.state_slot_stride + ((int64_t)h * p.hd + d) * p.ss + sg * PER;
+    f32x4 sv[PER / 4];
+#pragma unroll
+    for (int i = 0; i < PER / 4; i++) sv[i] = pos == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4*)(st + 4 * i);
+    const int g = min(h * p.ng / p.nh, p.ng - 1);
+    const bool lead = h == 0 || (h - 1) * p.ng / p.nh != g;      // the first head of the group stores B and C
+    // ---- phase 1 ----
+    const bool carried = p.chain == 3, reach = carried && pos > 0;
+    const float* tl = p.tail + slot * p.tail_slot_stride;         // (read only where reach: chain 3 has a tail)
+    for (int e = tid; e < S * nc; e += 256) {
+        const int j = e / nc, i = e - j * nc;
+        int c, li;
+        bool own = true;
+        if (i < p.hd) { c = h * p.hd + i; li = i; }
+        else {
+            const int isC = (i - p.hd) >= p.ss, n = i - p.hd - isC * p.ss;
+            c = p.EH + (isC * p.ng + g) * p.ss + n;
+            li = p.hd + isC * p.ss + (n % PER) * SG + n / PER;
+            own = lead;
+        }
+        const float* row = p.proj + (int64_t)(t0 + j) * p.P + p.EH + c;
+        const int jj = carried ? j : 0;                           // rows of the sequence inside row j's window
+        float sum = 0.f;
+        for (int k = 0; k < p.K; k++) {
+            const int back = p.K - 1 - k;
+            if (back <= jj) sum = fmaf(row[-(int64_t)back * p.P], p.conv_w[(int64_t)c * p.K + k], sum);
+            else if (reach) sum = fmaf(tl[(int64_t)(p.K - 1 - (back - j)) * p.conv_dim + c], p.conv_w[(int64_t)c * p.K + k], sum);
+        }
+        if (p.conv_b) sum += p.conv_b[c];
+        const float v = silu_ref(sum);
+        s_x[j * nc + li] = v;
+        if (own) {
+            p.xbc[(int64_t)(t0 + j) * p.conv_dim + c] = v;
+            if (raw_keep) raw_keep[(int64_t)(t0 + j) * p.conv_dim + c] = row[0];
+        }
+    }
+    if (tid < S) {
+        float v = p.proj[(int64_t)(t0 + tid) * p.P + p.EH + p.conv_dim + h];
+        if (p.dt_bias) v += p.dt_bias[h];
+        v = softplus_ref(v);
+        s_dt[tid] = v;
+        p.delta[(int64_t)(t0 + tid) * p.nh + h] = v;
+    }
+    __syncthreads();
+    // ---- phase 2 ----
+    float s[PER];
+#pragma unroll
+    for (int i = 0; i < PER; i++) s[i] = sv[i >> 2][i & 3];
+    const float A = p.a_log ? -__expf(p.a_log[h]) : 0.f;
+    const float Dh = p.Dskip ? p.Dskip[h] : 0.f;
+    for (int j = 0; j < S; j++) {
+        const float dt = s_dt[j];
+        const float abar = p.a_log ? __expf(A * dt) : 1.0f;
+        const float* xr = s_x + j * nc;
+        const float u = xr[d];
+        const float* Bt = xr + p.hd + sg;
+        const float* Ct = Bt + p.ss;
+        float acc = 0.f;
+#pragma unroll
+        for (int q = 0; q < PER; q++) {
+            const float v = fmaf(abar, s[q], (dt * Bt[q * SG]) * u);
+            s[q] = v;
+            acc = fmaf(Ct[q * SG], v, acc);
+        }
+        for (int msk = 1; msk < SG; msk <<= 1) acc += __shfl_xor(acc, msk, 64);
+        if (sg == 0) p.y[(int64_t)(t0 + j) * p.EH + h * p.hd + d] = acc + Dh * u;
+    }
+}
+
+// What mamba_commit_kernel needs beside MambaArgs (whose state / tail / xbc / delta point at Mamba2 layer 0): layer l's
+// buffers lie l strides further, its a_log comes from a device table built at finalize (an entry may be NULL).
+struct MambaCommitArgs {
+    const float* const* a_log;       // [layers]
+    const float* raw;                // the kept raw xBC rows, layer 0 (carried models; NULL otherwise)
+    int64_t state_layer_stride, tail_layer_stride, xbc_layer_stride, delta_layer_stride;
+    const int32_t* n_acc;            // per sequence: accepted drafts (the accept kernel's result)
+    const int32_t* keep;             // per sequence: at most this many rows stay (a loop's last steps)
+};
+
+// grid (nh, sequences, Mamba2 layers), 256 threads, once per verify pass after the accept kernel: the sequence advances by
+// rows = min(1 + n_accepted, keep) of its S rows.  The state is loaded (zeros at position 0), taken through `rows` steps
+// of the recurrence from the kept u / B / dt (the scan's expression; no C, no y) and stored.  Carried (chain 3): the
+// window becomes the last K-1 rows of (old rows, or zeros at position 0) ++ (raw rows 0 .. rows-1).  The layer's conv_dim
+// columns are dealt over its nh workgroups, a column's K-1 elements are read and written by ONE thread, oldest first: the
+// element read for tail row i is tail row i + rows, which is written later.
+template <int PER>
+__global__ __launch_bounds__(256) void mamba_commit_kernel(MambaArgs p, MambaCommitArgs ca) {
+    const int h = blockIdx.x, seq = blockIdx.y, l = blockIdx.z, tid = threadIdx.x;
+    const int SG = 256 / p.hd, d = tid / SG, sg = tid % SG;
+    const int t0 = p.seq_tok_start[seq], pos = p.seq_pos[seq];
+    const int64_t slot = p.seq_slot[seq];
+    const int rows = max(min(min(ca.n_acc[seq] + 1, ca.keep[seq]), p.seq_len[seq]), 0);
+    float* st = p.state + slot * p.state_slot_stride + l * ca.state_layer_stride + ((int64_t)h * p.hd + d) * p.ss + sg * PER;
+    f32x4 sv[PER / 4];
+#pragma unroll
+    for (int i = 0; i < PER / 4; i++) sv[i] = pos == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : *(const f32x4*)(st + 4 * i);
+    const float* al = ca.a_log[l];
+    const float A = al ? -__expf(al[h]) : 0.f;
+    const int g = min(h * p.ng / p.nh, p.ng - 1);
+    const float* xbc = p.xbc + l * ca.xbc_layer_stride + (int64_t)t0 * p.conv_dim;
+    const float* delta = p.delta + l * ca.delta_layer_stride + (int64_t)t0 * p.nh;
+    for (int i = 0; i < rows; i++) {
+        const float dt = delta[i * p.nh + h];
+        const float abar = al ? __expf(A * dt) : 1.0f;
+        const float* xr = xbc + (int64_t)i * p.conv_dim;
+        const float u = xr[h * p.hd + d];
+        const float* Bt = xr + p.EH + g * p.ss + sg * PER;
+#pragma unroll
+        for (int q = 0; q < PER / 4; q++) {
+            const f32x4 b = *(const f32x4*)(Bt + 4 * q);
+#pragma unroll
+            for (int r = 0; r < 4; r++) sv[q][r] = fmaf(abar, sv[q][r], (dt * b[r]) * u);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < PER / 4; i++) *(f32x4*)(st + 4 * i) = sv[i];
+    if (p.chain != 3) return;
+    float* tl = p.tail + slot * p.tail_slot_stride + l * ca.tail_layer_stride;
+    const float* raw = ca.raw + l * ca.xbc_layer_stride + (int64_t)t0 * p.conv_dim;
+    for (int c = h * 256 + tid; c < p.conv_dim; c += p.nh * 256)
+        for (int i = 0; i < p.K - 1; i++) {
+            const int rel = rows - (p.K - 1) + i;               // row of this pass that lands in tail row i
+            const float v = rel >= 0 ? raw[(int64_t)rel * p.conv_dim + c] : (pos > 0 ? tl[(int64_t)(i + rows) * p.conv_dim + c] : 0.f);
+            tl[(int64_t)i * p.conv_dim + c] = v;
+        }
+}
+
 }  // namespace nvl

@@ -55,7 +55,7 @@ enum KClass { KC_GEMM = 0, KC_ATTN = 1, KC_OTHER = 2 };
 // where in the layer a launch sits (per-kernel roofline entries of nvl_get_kernel_stats; names in nvllm.hip)
 enum KSite { KS_OTHER = 0, KS_QKV, KS_ATTN, KS_OPROJ, KS_FFN_UP, KS_FFN_DOWN, KS_LM_HEAD, KS_NORM, KS_MOE_ROUTER, KS_MOE_PLAN,
              KS_MOE_UP, KS_MOE_DOWN, KS_MOE_COMBINE, KS_EMBED, KS_ARGMAX, KS_ROPE, KS_MAMBA_IN, KS_MAMBA_CONV, KS_MAMBA_SCAN,
-             KS_MAMBA_GATE, KS_MAMBA_OUT, KS_ALLREDUCE, KS_LOGPROBS, KS_SPEC_REJECT, KS_COUNT };
+             KS_MAMBA_GATE, KS_MAMBA_OUT, KS_ALLREDUCE, KS_LOGPROBS, KS_SPEC_REJECT, KS_MAMBA_VERIFY, KS_MAMBA_COMMIT, KS_COUNT };
 
 struct ProfRec { hipEvent_t a, b; int cls; double flops; int site, phase; double bytes; };
 struct SiteStat { double ms = 0, flops = 0, bytes = 0; uint64_t launches = 0; };
@@ -196,6 +196,12 @@ struct nvl_model {
     float* conv_tail = nullptr; int64_t conv_tail_layer_stride = 0, conv_tail_slot_stride = 0;   // chunked prefill, or every call of a carried model (mamba.h MambaArgs::chain)
     int conv_chain = 0;          // set by runner_impl around the chunks of one long history
     bool conv_carried = false;   // nvl_set_mamba_conv_state(NVL_MAMBA_CONV_CARRIED): every pass runs chain 3
+    // nvl_set_mamba_rollback(NVL_MAMBA_ROLLBACK_VERIFY): verify passes run mamba_verify_kernel + one mamba_commit_kernel
+    // (mamba.h).  Per (Mamba2 layer, row of the pass): the xbc and dt rows the pass consumed and, carried, the raw xBC rows
+    bool mamba_rollback = false;
+    float *vk_xbc = nullptr, *vk_raw = nullptr, *vk_delta = nullptr; int64_t vk_rows = 0;
+    const float** vk_alog = nullptr;                              // device table: a_log of Mamba2 layer l (or NULL)
+    int32_t* vk_keep_host = nullptr; int32_t* vk_keep_dev = nullptr;   // per sequence of a pass: rows that may stay (pinned, device)
     float *ssd_z = nullptr, *ssd_decay = nullptr; int64_t ssd_z_floats = 0, ssd_decay_floats = 0;   // chunk-parallel SSD scan scratch (mamba.h)
     SampleBufs samp;             // nvl_sample scratch
     LogprobBufs lpb;             // nvl_logprobs / nvl_score scratch

@@ -414,6 +414,8 @@ extern "C" void nvl_destroy(nvl_model* m) {
     dfree(m->ring_pos0);
     dfree(m->conv_tail); dfree(m->stamp_buf); dfree(m->ssd_z); dfree(m->ssd_decay);
     dfree(m->ssm_state); dfree(m->mproj); dfree(m->mxbc); dfree(m->mdelta); dfree(m->my); dfree(m->myn);
+    dfree(m->vk_xbc); dfree(m->vk_raw); dfree(m->vk_delta); dfree((void*)m->vk_alog); dfree(m->vk_keep_dev);
+    if (m->vk_keep_host) (void)hipHostFree(m->vk_keep_host);
     free_sample_bufs(m->samp);
     free_logprob_bufs(m->lpb);
     dfree(m->samp_hist); dfree(m->samp_hist_len); dfree(m->samp_u_steps);
@@ -959,6 +961,16 @@ extern "C" int nvl_set_mamba_conv_state(nvl_model* m, int mode) {
     return NVL_OK;
 }
 
+extern "C" int nvl_set_mamba_rollback(nvl_model* m, int mode) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mamba_rollback: no model");
+    if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_set_mamba_rollback: call it before nvl_finalize");
+    if (mode != NVL_MAMBA_ROLLBACK_NONE && mode != NVL_MAMBA_ROLLBACK_VERIFY)
+        return fail(m, NVL_ERR_INVALID, "nvl_set_mamba_rollback: unknown mode");
+    if (!m->n_mamba) return fail(m, NVL_ERR_INVALID, "nvl_set_mamba_rollback: the model has no Mamba2 layers");
+    m->mamba_rollback = mode == NVL_MAMBA_ROLLBACK_VERIFY;
+    return NVL_OK;
+}
+
 extern "C" int nvl_finalize(nvl_model* m) {
     if (!m) return NVL_ERR_INVALID;
     if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_finalize: already finalized");
@@ -1189,6 +1201,18 @@ extern "C" int nvl_finalize(nvl_model* m) {
         m->my = dmalloc<float>(Mmax * m->mEH);
         m->myn = dmalloc_bytes(Mp * m->mEH * (int64_t)m->wsize);
         NVL_HIP(hipMemsetAsync(m->myn, 0, (size_t)(Mp * m->mEH) * m->wsize, m->stream));
+        if (m->mamba_rollback) {      // what a verify pass keeps for its commit, per (Mamba2 layer, row): mamba.h
+            m->vk_rows = std::min<int64_t>(Mmax, 8 * (int64_t)S);
+            m->vk_xbc = dmalloc<float>(m->n_mamba * m->vk_rows * m->mConv);
+            m->vk_delta = dmalloc<float>(m->n_mamba * m->vk_rows * m->m_nh);
+            if (m->conv_carried && m->m_K > 1) m->vk_raw = dmalloc<float>(m->n_mamba * m->vk_rows * m->mConv);
+            std::vector<const float*> alog((size_t)m->n_mamba);
+            for (const LayerW& l : m->layers) if (l.mamba) alog[(size_t)l.mamba_idx] = (const float*)l.t[NVL_T_MAMBA_A_LOG].p;
+            m->vk_alog = (const float**)dmalloc_bytes((int64_t)m->n_mamba * sizeof(float*));
+            NVL_HIP(hipMemcpy(m->vk_alog, alog.data(), alog.size() * sizeof(float*), hipMemcpyHostToDevice));
+            NVL_HIP(hipHostMalloc((void**)&m->vk_keep_host, (size_t)S * 4, hipHostMallocDefault));
+            m->vk_keep_dev = dmalloc<int32_t>(S);
+        }
     }
     // split-K partial slices of the residual projections: decode (<= 64 rows) and mid-size batches (<= SK_TILE_MAX_M rows)
     m->sk_rows = (int)std::min<int64_t>(std::max<int64_t>(Mmax, 64), SK_TILE_MAX_M);
@@ -2353,12 +2377,55 @@ void mamba_mixer(nvl_model* m, MambaArgs a, int M, int n_seqs, int max_len, void
     }
 }
 
+// mamba_mixer for a Mamba2 layer of a verify pass of a rollback model (n_seqs sequences of S = 1 .. 8 rows each): ONE launch
+// in place of conv + tail + scan that writes neither state nor tail (mamba.h mamba_verify_kernel), then the gate-norm.
+// a.xbc / a.delta are the layer's keep rows, raw_keep its kept raw rows (carried) or NULL.
+void mamba_verify(nvl_model* m, const MambaArgs& a, float* raw_keep, int M, int n_seqs, int S, void* out, float* y_pre = nullptr) {
+    if (S < 1 || S > 8 || M != n_seqs * S) throw std::runtime_error("mamba_verify: a verify pass has 1 .. 8 rows per sequence");
+    {
+        const double tail_bytes = a.chain == 3 ? (double)n_seqs * (a.K - 1) * a.conv_dim * 4.0 : 0.0;
+        KScope ks(m, KC_OTHER, 2.0 * 3.0 * (double)M * a.EH * a.ss, KS_MAMBA_VERIFY,
+                  (double)M * (a.P + (a.chain == 3 ? 2 : 1) * a.conv_dim + 2 * a.nh) * 4.0 + tail_bytes + (double)n_seqs * a.nh * a.hd * a.ss * 4.0);
+        const int per = a.ss / (256 / a.hd);
+        const int lds = (S * (a.hd + 2 * a.ss) + S) * 4;
+        const dim3 grid(a.nh, n_seqs);
+#define NVL_MV(PERv)                                                                                    \
+        do {                                                                                            \
+            if (lds > 64 * 1024) NVL_LDS_ATTR(mamba_verify_kernel<PERv>, 160 * 1024);                   \
+            hipLaunchKernelGGL(mamba_verify_kernel<PERv>, grid, dim3(256), lds, m->stream, a, raw_keep); \
+        } while (0)
+        if (per <= 4) NVL_MV(4); else if (per <= 8) NVL_MV(8); else if (per <= 16) NVL_MV(16); else NVL_MV(32);
+#undef NVL_MV
+        NVL_HIP(hipGetLastError());
+    }
+    if (y_pre) NVL_HIP(hipMemcpyAsync(y_pre, a.y, (size_t)M * a.EH * 4, hipMemcpyDeviceToDevice, m->stream));
+    KScope ks(m, KC_OTHER, 0, KS_MAMBA_GATE, (double)M * a.EH * (8.0 + (double)m->wsize));
+    if (m->f32) hipLaunchKernelGGL((mamba_gate_norm_kernel<float>), dim3(M), dim3(256), 0, m->stream, a, (float*)out);
+    else hipLaunchKernelGGL((mamba_gate_norm_kernel<bf16_t>), dim3(M), dim3(256), 0, m->stream, a, (bf16_t*)out);
+    NVL_HIP(hipGetLastError());
+}
+
+// The commit of a verify pass: every Mamba2 layer's state and window advance by the accepted rows, in ONE launch (mamba.h
+// mamba_commit_kernel).  `a` describes layer 0 and the pass, `ca` the strides to layer l and the accept counts.
+void mamba_commit(nvl_model* m, const MambaArgs& a, const MambaCommitArgs& ca, int n_seqs, int layers) {
+    KScope ks(m, KC_OTHER, 0, KS_MAMBA_COMMIT, 2.0 * layers * n_seqs * ((double)a.nh * a.hd * a.ss + (a.chain == 3 ? (a.K - 1) * a.conv_dim : 0)) * 4.0);
+    const int per = a.ss / (256 / a.hd);
+    const dim3 grid(a.nh, n_seqs, layers);
+    if (per <= 4) hipLaunchKernelGGL(mamba_commit_kernel<4>, grid, dim3(256), 0, m->stream, a, ca);
+    else if (per <= 8) hipLaunchKernelGGL(mamba_commit_kernel<8>, grid, dim3(256), 0, m->stream, a, ca);
+    else if (per <= 16) hipLaunchKernelGGL(mamba_commit_kernel<16>, grid, dim3(256), 0, m->stream, a, ca);
+    else hipLaunchKernelGGL(mamba_commit_kernel<32>, grid, dim3(256), 0, m->stream, a, ca);
+    NVL_HIP(hipGetLastError());
+}
+
 // Enqueue ONE forward pass (embedding ... argmax) on the model's stream for the batch described by the device
 // metadata `md` — no host synchronisation.  Returns the number of logits rows produced.
 // seam: 0 = whole pass; bit 0 = x and layer 0's normed operand are already in place (skip embed + first norm);
 // bit 1 = stop after the argmax partials (the caller's decode_seam_kernel finishes the step); bit 2 = no argmax at
 // all (the caller samples from the logits); bit 3 = a verify pass (nvl_verify_greedy*): its 2..8 positions per sequence
-// take the multi-position decode attention instead of the prefill kernel (attention_mq_ok)
+// take the multi-position decode attention instead of the prefill kernel (attention_mq_ok); bit 4 = a verify pass of a
+// model set to NVL_MAMBA_ROLLBACK_VERIFY, whatever its attention route: every Mamba2 layer runs mamba_verify (the caller
+// enqueues mamba_commit after its accept kernel)
 // Either tail leaves LogitsScaling APPLIED IN PLACE in m->logits (argmax_partial_kernel writes the divided value back,
 // scale_rows_kernel is the division itself): nvl_sample and nvl_logprobs read final logits and never divide again.
 // `sc` != NULL (nvl_score; flags carry NVL_FWD_ALL_LOGITS): the tail is final norm over every row, then LM head +
@@ -2407,6 +2474,11 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
             a.chain = m->conv_tail ? (m->conv_carried ? 3 : m->conv_chain) : 0;
             a.tail = m->conv_tail ? m->conv_tail + (int64_t)l.mamba_idx * m->conv_tail_layer_stride : nullptr;
             a.tail_slot_stride = m->conv_tail_slot_stride;
+            if (seam & 16) {      // a verify pass: state and window are read, not written; the layer's keep rows feed the commit
+                a.xbc = m->vk_xbc + (int64_t)l.mamba_idx * m->vk_rows * m->mConv;
+                a.delta = m->vk_delta + (int64_t)l.mamba_idx * m->vk_rows * m->m_nh;
+                mamba_verify(m, a, m->vk_raw ? m->vk_raw + (int64_t)l.mamba_idx * m->vk_rows * m->mConv : nullptr, M, n_seqs, max_len, m->myn);
+            } else
             mamba_mixer(m, a, M, n_seqs, max_len, m->myn);
             m->site = KS_MAMBA_OUT;
             resid_gemm(m, m->myn, m->mEH, l.t[NVL_T_MAMBA_OUT_PROJ].p, nullptr, m->resid_alpha, M, H, m->mEH);
@@ -3091,8 +3163,10 @@ void reserve_sample_hist(nvl_model* m) {
 // launches, accept kernel and result download — captured and replayed like a decode pass when every projection is in
 // decode form (<= 64 rows) — then the host copies.  Leaves the n_seqs x (1+k) logits rows as the last forward group.
 // A sampled kind finds vs_host filled and the histories on the device.
-void verify_pass(nvl_model* m, int n_seqs, int k, int32_t* n_acc_out, int32_t* out_tokens, const VerifyKind& vk) {
+void verify_pass(nvl_model* m, int n_seqs, int k, int32_t* n_acc_out, int32_t* out_tokens, const int* keep, const VerifyKind& vk) {
     const int S = 1 + k, M = n_seqs * S;
+    const int roll = m->mamba_rollback ? 16 : 0;      // hybrid: Mamba2 layers verify now, one commit follows the accept kernel
+    if (roll) for (int i = 0; i < n_seqs; i++) m->vk_keep_host[i] = keep ? keep[i] : S;
     const Meta md = bind_meta(m, m->meta_dev, M);
     NVL_HIP(hipEventRecord(m->ev0, m->stream));
     const double attn_flops = attn_cost(m, bind_meta(m, m->meta_host, M), n_seqs);
@@ -3102,9 +3176,10 @@ void verify_pass(nvl_model* m, int n_seqs, int k, int32_t* n_acc_out, int32_t* o
     if (vk.samples()) reserve_sample_rows(m, M);
     auto pass = [&] {
         NVL_HIP(hipMemcpyAsync(m->meta_dev, m->meta_host, meta_bytes(m, M), hipMemcpyHostToDevice, m->stream));
+        if (roll) NVL_HIP(hipMemcpyAsync(m->vk_keep_dev, m->vk_keep_host, (size_t)n_seqs * 4, hipMemcpyHostToDevice, m->stream));
         if (vk.samples()) {
             NVL_HIP(hipMemcpyAsync(m->vs_dev, m->vs_host, (size_t)(4 + 2 * n_seqs + M) * 4, hipMemcpyHostToDevice, m->stream));
-            enqueue_forward(m, md, n_seqs, M, S, attn_flops, NVL_FWD_ALL_LOGITS, (mq ? 8 : 0) | 4);
+            enqueue_forward(m, md, n_seqs, M, S, attn_flops, NVL_FWD_ALL_LOGITS, (mq ? 8 : 0) | 4 | roll);
             const VsBlock vs = bind_vs(m->vs_dev, n_seqs);
             SampleArgs a = sample_args(m, vs.u);
             a.ext = md.tokens; a.ext_S = S; a.hist_row = vs.hist_row; a.params = vs.params;
@@ -3122,10 +3197,22 @@ void verify_pass(nvl_model* m, int n_seqs, int k, int32_t* n_acc_out, int32_t* o
                                (const int32_t*)md.tokens, k, n_seqs, m->verify_dev, vk.tag == VerifyKind::IN_LOOP ? m->samp_hist : (int32_t*)nullptr,
                                (int64_t)m->cfg.max_seq_len, m->samp_hist_len, (const int32_t*)vs.hist_row, (const int32_t*)vs.keep);
         } else {
-            enqueue_forward(m, md, n_seqs, M, S, attn_flops, NVL_FWD_ALL_LOGITS, mq ? 8 : 0);
+            enqueue_forward(m, md, n_seqs, M, S, attn_flops, NVL_FWD_ALL_LOGITS, (mq ? 8 : 0) | roll);
             hipLaunchKernelGGL(verify_accept_kernel, dim3(cdiv(n_seqs, 64)), dim3(64), 0, m->stream, m->argmax_dev, md.tokens, k, n_seqs, m->verify_dev);
         }
         NVL_HIP(hipGetLastError());
+        if (roll) {     // the accept counts are on the device: advance every Mamba2 layer by min(1 + accepted, keep) rows
+            MambaArgs a{};
+            a.EH = m->mEH; a.conv_dim = m->mConv; a.nh = m->m_nh; a.hd = m->m_hd; a.ss = m->m_ss; a.ng = m->m_ng; a.K = m->m_K;
+            a.xbc = m->vk_xbc; a.delta = m->vk_delta;
+            a.state = m->ssm_state; a.state_slot_stride = m->ssm_slot_stride;
+            a.seq_tok_start = md.seq_tok_start; a.seq_len = md.seq_len; a.seq_pos = md.seq_pos; a.seq_slot = md.blk_table;
+            a.chain = m->conv_tail && m->conv_carried ? 3 : 0;
+            a.tail = m->conv_tail; a.tail_slot_stride = m->conv_tail_slot_stride;
+            const MambaCommitArgs ca{m->vk_alog, m->vk_raw, m->ssm_layer_stride, m->conv_tail_layer_stride, m->vk_rows * m->mConv,
+                                     m->vk_rows * m->m_nh, m->verify_dev, m->vk_keep_dev};
+            mamba_commit(m, a, ca, n_seqs, m->n_mamba);
+        }
         NVL_HIP(hipMemcpyAsync(m->verify_host, m->verify_dev, (size_t)nres * 4, hipMemcpyDeviceToHost, m->stream));
         if (spec && vk.spec.accept_prob_out)      // (a speculative pass is never captured: the host address is not baked in)
             NVL_HIP(hipMemcpyAsync(vk.spec.accept_prob_out, m->spec_ap, (size_t)n_seqs * k * 2 * 4, hipMemcpyDeviceToHost, m->stream));
@@ -3156,7 +3243,7 @@ int verify_refusals(nvl_model* m, const char* who, int n_seqs, int k, int k_min)
     if (k < k_min || k > 7) return fail(m, NVL_ERR_INVALID, std::string(who) + ": k outside 1..7");
     if (n_seqs <= 0 || n_seqs > m->opts.max_seqs) return fail(m, NVL_ERR_INVALID, std::string(who) + ": n_seqs outside 1..max_seqs");
     if ((int64_t)n_seqs * (1 + k) > m->opts.max_batch_tokens) return fail(m, NVL_ERR_INVALID, std::string(who) + ": n_seqs x (1 + k) exceeds max_batch_tokens");
-    if (m->n_mamba) return fail(m, NVL_ERR_STATE, std::string(who) + ": a Mamba2 state cannot be rolled back");
+    if (m->n_mamba && !m->mamba_rollback) return fail(m, NVL_ERR_STATE, std::string(who) + ": a Mamba2 state cannot be rolled back");
     if (m->tp > 1 || m->tp_force) return fail(m, NVL_ERR_STATE, std::string(who) + ": tensor-parallel models are not supported");
     return NVL_OK;
 }
@@ -3228,7 +3315,7 @@ int verify_batch(nvl_model* m, const char* who, int n_seqs, const KvRef& kv, con
         if (vk.tag == VerifyKind::SPECULATIVE && !m->spec_ap) m->spec_ap = dmalloc<float>((int64_t)m->opts.max_seqs * 7 * 2);
         sampled_stage_pass(m, n_seqs, k, vk.rq);
     }
-    verify_pass(m, n_seqs, k, n_acc_out, out_tokens, vk);
+    verify_pass(m, n_seqs, k, n_acc_out, out_tokens, keep, vk);
     // slab rollback: the accepted prefix and the row that produced the first unaccepted id stay; the rows behind are dead
     advance_slots(m, h_slot, [&](int i) { const int adv = m->verify_host[i] + 1; return keep ? std::min(adv, keep[i]) : adv; });
     return NVL_OK;
@@ -3812,7 +3899,7 @@ extern "C" int nvl_reset_stats(nvl_model* m) {
 static const char* const k_site_names[KS_COUNT] = {
     "other", "qkv_proj", "attention", "o_proj", "ffn_up", "ffn_down", "lm_head", "norm", "moe_router", "moe_plan", "moe_up",
     "moe_down", "moe_combine", "embed", "argmax", "rope_kv", "mamba_in_proj", "mamba_conv", "mamba_scan", "mamba_gate_norm",
-    "mamba_out_proj", "tp_allreduce", "logprobs", "spec_reject"};
+    "mamba_out_proj", "tp_allreduce", "logprobs", "spec_reject", "mamba_verify", "mamba_commit"};
 extern "C" const char* nvl_kernel_site_name(int site) { return site >= 0 && site < KS_COUNT ? k_site_names[site] : ""; }
 extern "C" int nvl_get_kernel_stats(nvl_model* m, nvl_kernel_stat* out, int cap) {
     if (!m || (cap > 0 && !out)) return NVL_ERR_INVALID;

@@ -358,6 +358,72 @@ extern "C" int nvl_op_mamba_mixer(int device, int precision, const float* proj, 
     OP_CATCH
 }
 
+// One Mamba2 layer of a verify pass, then the commit (nvllm.hip mamba_verify / mamba_commit): the verify launch on buffers
+// that come back as it left them, then the commit launch on the same device buffers.  The keep rows are the op's xbc /
+// delta buffers and a raw-row buffer, as the model has them per layer; keep = seq_len (a single verify call's).
+extern "C" int nvl_op_mamba_verify(int device, int precision, const float* proj, int n_seqs, const int32_t* seq_len,
+                                   const int32_t* seq_pos, const int32_t* seq_slot, const int32_t* n_acc, int n_slots, int nh, int hd,
+                                   int ss, int ng, int K, const float* conv_w, const float* conv_b, const float* a_log, const float* D,
+                                   const float* dt_bias, const float* norm_w, float* state, float* tail, int chain, float* xbc,
+                                   float* delta, float* y, float* state_commit, float* tail_commit) {
+    if (!proj || !seq_len || !seq_pos || !seq_slot || !n_acc || !conv_w || !state || !xbc || !delta || !y || !state_commit || n_seqs <= 0 || n_slots <= 0)
+        return op_fail("nvl_op_mamba_verify: bad arguments");
+    if (!mamba_geometry_ok(nh, hd, ss, ng, K)) return op_fail("nvl_op_mamba_verify: head_dim / state_size / groups / conv kernel not supported by the kernels");
+    const bool have_tail = tail && K > 1;
+    if ((chain != 0 && chain != 3) || (chain == 3 && K > 1 && !tail) || (have_tail && !tail_commit))
+        return op_fail("nvl_op_mamba_verify: chain is 0 or 3; a carried window (chain 3) needs a tail");
+    const int S = seq_len[0], M = n_seqs * S;
+    std::vector<char> used((size_t)n_slots, 0);
+    for (int i = 0; i < n_seqs; i++) {
+        if (S < 1 || S > 8 || seq_len[i] != S || seq_pos[i] < 0 || seq_slot[i] < 0 || seq_slot[i] >= n_slots || used[(size_t)seq_slot[i]] || n_acc[i] < 0 || n_acc[i] >= S)
+            return op_fail("nvl_op_mamba_verify: every sequence has the same 1 .. 8 rows, a slot of its own and 0 <= n_acc < rows");
+        used[(size_t)seq_slot[i]] = 1;
+    }
+    OP_TRY
+    OpCtx cx(device, precision);
+    nvl_model& m = cx.m;
+    const int EH = nh * hd, conv_dim = EH + 2 * ng * ss, P = EH + conv_dim + nh;
+    std::vector<int32_t> meta((size_t)(6 * n_seqs));       // starts | lens | positions | slots | accepted | keep
+    for (int i = 0; i < n_seqs; i++) {
+        meta[(size_t)i] = i * S; meta[(size_t)(n_seqs + i)] = S; meta[(size_t)(2 * n_seqs + i)] = seq_pos[i];
+        meta[(size_t)(3 * n_seqs + i)] = seq_slot[i]; meta[(size_t)(4 * n_seqs + i)] = n_acc[i]; meta[(size_t)(5 * n_seqs + i)] = S;
+    }
+    int32_t* dmeta = (int32_t*)cx.alloc((int64_t)meta.size() * 4);
+    NVL_HIP(hipMemcpyAsync(dmeta, meta.data(), meta.size() * 4, hipMemcpyHostToDevice, m.stream));
+    MambaArgs a{};
+    a.proj = cx.up_f32(proj, (int64_t)M * P); a.P = P; a.EH = EH; a.conv_dim = conv_dim; a.nh = nh; a.hd = hd; a.ss = ss; a.ng = ng; a.K = K;
+    a.conv_w = cx.up_f32(conv_w, (int64_t)conv_dim * K);
+    a.conv_b = conv_b ? cx.up_f32(conv_b, conv_dim) : nullptr;
+    a.a_log = a_log ? cx.up_f32(a_log, nh) : nullptr;
+    a.Dskip = D ? cx.up_f32(D, nh) : nullptr;
+    a.dt_bias = dt_bias ? cx.up_f32(dt_bias, nh) : nullptr;
+    a.norm_w = norm_w ? cx.up_f32(norm_w, EH) : nullptr;
+    a.xbc = (float*)cx.alloc((int64_t)M * conv_dim * 4); a.delta = (float*)cx.alloc((int64_t)M * nh * 4); a.y = (float*)cx.alloc((int64_t)M * EH * 4);
+    const int64_t state_floats = (int64_t)nh * hd * ss, tail_floats = (int64_t)(K - 1) * conv_dim;
+    a.state = cx.up_f32(state, state_floats * n_slots); a.state_slot_stride = state_floats;
+    a.seq_tok_start = dmeta; a.seq_len = dmeta + n_seqs; a.seq_pos = dmeta + 2 * n_seqs; a.seq_slot = dmeta + 3 * n_seqs;
+    a.tail = have_tail ? cx.up_f32(tail, tail_floats * n_slots) : nullptr; a.tail_slot_stride = tail_floats;
+    a.chain = have_tail ? chain : 0;
+    float* raw = a.chain == 3 ? (float*)cx.alloc((int64_t)M * conv_dim * 4) : nullptr;
+    const float** alog_tbl = (const float**)cx.alloc(sizeof(float*));
+    NVL_HIP(hipMemcpyAsync(alog_tbl, &a.a_log, sizeof(float*), hipMemcpyHostToDevice, m.stream));
+    float* y_pre = (float*)cx.alloc((int64_t)M * EH * 4);
+    const int64_t Mp = round_up(M, 64);
+    void* out = cx.alloc(Mp * EH * (int64_t)m.wsize);
+    NVL_HIP(hipMemsetAsync(out, 0, (size_t)(Mp * EH) * m.wsize, m.stream));
+    mamba_verify(&m, a, raw, M, n_seqs, S, out, y_pre);
+    cx.down(xbc, a.xbc, (int64_t)M * conv_dim);
+    cx.down(delta, a.delta, (int64_t)M * nh);
+    cx.down(y, y_pre, (int64_t)M * EH);
+    cx.down(state, a.state, state_floats * n_slots);
+    if (have_tail) cx.down(tail, a.tail, tail_floats * n_slots);
+    mamba_commit(&m, a, MambaCommitArgs{alog_tbl, raw, 0, 0, 0, 0, dmeta + 4 * n_seqs, dmeta + 5 * n_seqs}, n_seqs, 1);
+    cx.down(state_commit, a.state, state_floats * n_slots);
+    if (have_tail) cx.down(tail_commit, a.tail, tail_floats * n_slots);
+    return NVL_OK;
+    OP_CATCH
+}
+
 // The one-weight model of the quantized matmul ops: W [K][N] ([in, out], as nvl_op_matmul) quantized by the upload quantizer
 // of format wf into a tensor registered for gemm(), a tile-path scratch of at most scratch_rows weight rows, then
 // C = bf16(A) · W~^T through the model's dispatch into c [M][N]; then the quantizer's codes, scales and (INT4) zero points in

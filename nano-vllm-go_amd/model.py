@@ -68,7 +68,8 @@ class HipTransformerModel:
                  kv_cache_dtype: str = "auto", kv_scales=None, weight_dtype: str = "auto",
                  act_dtype: str = "auto", expert_dtype: str = "auto", mx_weight_dtype: str = "none",
                  mx_expert_dtype: str = "none", mx_head_dtype: str = "none", gq_weight_dtype: str = "none",
-                 gq_group_size: int = 128, gq_expert_dtype: str = "none", mamba_conv_state: str = "per_call"):
+                 gq_group_size: int = 128, gq_expert_dtype: str = "none", mamba_conv_state: str = "per_call",
+                 mamba_rollback: str = "none"):
         """tensors=None defers finalize(): upload() each tensor, then call finalize().
         tp_size > 1 makes this the tp_rank-th tensor-parallel shard: pass the FULL tensors, the library keeps
         its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests).
@@ -96,7 +97,10 @@ class HipTransformerModel:
         (expert, output row) (nvl_set_gq_expert_dtype).
         mamba_conv_state="carried" (a hybrid model): the Mamba2 convolution window reaches into the sequence's previous
         calls, so feeding a sequence in one call or token by token gives the same logits (nvl_set_mamba_conv_state);
-        "per_call" (default) zero-pads every call as the reference does (mamba2.go:181-254)."""
+        "per_call" (default) zero-pads every call as the reference does (mamba2.go:181-254).
+        mamba_rollback="verify" (a hybrid model): the verify calls and the lookup / speculative loops accept the model — a
+        pass reads the Mamba2 states and kept rows without writing them, one launch after the accept decision advances
+        them by the accepted rows (nvl_set_mamba_rollback); "none" (default) keeps refusing those calls."""
         self.cfg = dict(cfg)
         self.lib = L.lib()
         self.h = C.c_void_p()
@@ -126,6 +130,8 @@ class HipTransformerModel:
                 raise ValueError(f'{kw}="{_ON[kw]}" cannot be combined with ' + " or ".join(f'{o}="{_ON[o]}"' for o in excludes))
         if mamba_conv_state not in L.MAMBA_CONV_STATE:
             raise ValueError(f"mamba_conv_state must be one of {sorted(L.MAMBA_CONV_STATE)}")
+        if mamba_rollback not in L.MAMBA_ROLLBACK:
+            raise ValueError(f"mamba_rollback must be one of {sorted(L.MAMBA_ROLLBACK)}")
         L.check(self.lib.nvl_create(C.byref(self._c), C.byref(opts), C.byref(self.h)))
         for kw, value in given.items():
             setattr(self, kw, value)
@@ -139,9 +145,10 @@ class HipTransformerModel:
                 msg = self.lib.nvl_last_error(self.h)
                 self.close()
                 raise L.NvlError(rc, msg.decode() if msg else "")
-        self.mamba_conv_state = mamba_conv_state
-        if mamba_conv_state != "per_call":
-            rc = self.lib.nvl_set_mamba_conv_state(self.h, L.MAMBA_CONV_STATE[mamba_conv_state])
+        self.mamba_conv_state, self.mamba_rollback = mamba_conv_state, mamba_rollback
+        for on, setter, mode in ((mamba_conv_state != "per_call", self.lib.nvl_set_mamba_conv_state, L.MAMBA_CONV_STATE[mamba_conv_state]),
+                                 (mamba_rollback != "none", self.lib.nvl_set_mamba_rollback, L.MAMBA_ROLLBACK[mamba_rollback])):
+            rc = setter(self.h, mode) if on else 0
             if rc < 0:
                 msg = self.lib.nvl_last_error(self.h)
                 self.close()

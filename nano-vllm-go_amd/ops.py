@@ -107,6 +107,30 @@ def mamba_mixer(proj, seq_len, seq_pos, seq_slot, state, nh, hd, ss, ng, K, conv
     return out
 
 
+def mamba_verify(proj, seq_len, seq_pos, seq_slot, n_acc, state, nh, hd, ss, ng, K, conv_w, conv_b=None, a_log=None, D=None,
+                 dt_bias=None, norm_w=None, tail=None, chain=0, precision="f32", device=0):
+    """A Mamba2 layer of a verify pass, then the pass's commit (csrc/mamba.h mamba_verify_kernel, mamba_commit_kernel) on
+    mamba_mixer's arguments: every sequence has the same 1 .. 8 rows, chain 0 or 3, n_acc[i] accepted drafts.
+    -> dict(xbc, delta, y, state, tail after the verify launch; state_commit, tail_commit after the commit)."""
+    proj, conv_w = _f(proj), _f(conv_w)
+    opt = [None if v is None else _f(v) for v in (conv_b, a_log, D, dt_bias, norm_w)]
+    sl, sp, so, na = (np.ascontiguousarray(v, dtype=np.int32) for v in (seq_len, seq_pos, seq_slot, n_acc))
+    state = _f(state).copy()
+    tail = None if tail is None else _f(tail).copy()
+    M, EH, conv_dim = proj.shape[0], nh * hd, nh * hd + 2 * ng * ss
+    if proj.shape != (M, EH + conv_dim + nh) or conv_w.shape != (conv_dim, K) or M != int(sl.sum()) or not sl.size == sp.size == so.size == na.size:
+        raise ValueError("mamba_verify: shapes do not match the geometry")
+    if state.ndim != 4 or state.shape[1:] != (nh, hd, ss) or (tail is not None and tail.shape != (state.shape[0], K - 1, conv_dim)):
+        raise ValueError("mamba_verify: state / tail shape")
+    out = dict(xbc=np.empty((M, conv_dim), np.float32), delta=np.empty((M, nh), np.float32), y=np.empty((M, EH), np.float32),
+               state_commit=np.empty_like(state), tail_commit=None if tail is None else np.empty_like(tail))
+    L.check(L.lib().nvl_op_mamba_verify(device, L.PRECISION[precision], _p(proj), sl.size, _p(sl), _p(sp), _p(so), _p(na), state.shape[0],
+                                        nh, hd, ss, ng, K, _p(conv_w), *[_p(v) for v in opt], _p(state), _p(tail), chain,
+                                        _p(out["xbc"]), _p(out["delta"]), _p(out["y"]), _p(out["state_commit"]), _p(out["tail_commit"])))
+    out["state"], out["tail"] = state, tail
+    return out
+
+
 def lookup_draft(history, k, ngram=3):
     """nvl_lookup_draft (host only): -> (draft [k], number of real draft tokens)."""
     h = np.ascontiguousarray(history, dtype=np.int32)
