@@ -467,8 +467,8 @@ int nvl_decode_greedy(nvl_model* m, int n_seqs, const int64_t* seq_ids, const in
  * n_accepted_out[i] = a_i; out_tokens [n_seqs][1+k]: out_tokens[i][0..a_i] = g[i][0..a_i], the rest -1.  Afterwards the
  * cached length is P_i + a_i + 1 (rows behind it are dead and get overwritten).  Only n_seqs x (2 + k) int32 come back; the
  * n_seqs x (1+k) logits rows stay as the last forward group, in token order, for nvl_logprobs / nvl_sample.
- * In bf16 with a bf16 cache the pass runs the multi-position decode attention (nvl_set_tuning key 38); in f32 and over an
- * 8-bit cache it runs the existing kernels.  A pass of at most 64 rows whose shape was seen before is replayed as a graph.
+ * In bf16 the pass runs the multi-position decode attention (nvl_set_tuning key 38): attn_decode_mq_bf16_kernel over a bf16
+ * cache, attn_decode_mq_kv8_kernel over an 8-bit cache; in f32 it runs the existing kernels.  A pass of at most 64 rows whose shape was seen before is replayed as a graph.
  * k outside 1..7 or n_seqs x (1+k) > max_batch_tokens: NVL_ERR_INVALID; P_i + 1 + k > max_seq_len: NVL_ERR_POSITION; no
  * slot: NVL_ERR_UNKNOWN_SEQ; a model with Mamba2 layers (its state cannot be rolled back), a tensor-parallel model or a
  * paged model: NVL_ERR_STATE.  A refused call changes no length. */
@@ -520,6 +520,10 @@ int nvl_get_stamps(nvl_model* m, int32_t* recs, int rec_cap, uint64_t* stamps, i
 /* Debug/parity: copy a sequence's cache for one layer as the reference lays it out,
  * K and V each [nKV, T, hd] fp32 (kv_cache.go:5-6).  Returns T. */
 int nvl_get_kv(nvl_model* m, int64_t seq_id, int layer, float* k_out, float* v_out);
+/* The model's last attention launch (the last attention layer of its last pass): ran[3] = {NVL_ATTN_RAN_* of the kernel
+ * that ran, waves per workgroup, workgroups per (sequence, kv head) of a key split}, as nvl_op_attention_batch reports them;
+ * all zero before the first pass. */
+int nvl_attention_ran(const nvl_model* m, int32_t ran[3]);
 /* Mamba2Layer.SSMState of a sequence's slot for a Mamba2 layer, [heads, head_dim, state] fp32 (mamba2.go:29-30; per
  * SEQUENCE here, per layer in the reference).  Returns the number of floats, or < 0. */
 int nvl_get_mamba_state(nvl_model* m, int64_t seq_id, int layer, float* out);
@@ -824,12 +828,14 @@ int nvl_op_attention_kv8(int device, const float* q, const float* k, const float
  *                      its tile and appends K / V to the pools, which are written back to k_pool / v_pool as fp32
  *   NVL_ATTN_OP_MQ     bf16: PLAIN with the verify pass's flag (2..8 rows per sequence run the multi-position kernel)
  *   NVL_ATTN_OP_KV8    bf16: the pools are quantized with k_scale / v_scale by the cache's own quantizer first
+ *   NVL_ATTN_OP_MQ_KV8 bf16: KV8's quantized pools with the verify pass's flag (2..8 rows per sequence run the 8-bit
+ *                      multi-position kernel); k_scale / v_scale finite and positive, as for KV8
  * Out: out [tokens][nH][hd]; ran[3] = {NVL_ATTN_RAN_* of the kernel that ran, waves per workgroup, workgroups per
  * (sequence, kv head) of a key split}; part_cnt [32], the split's tickets after the launch (all zero again).
  * Refused before anything is launched: what the paged front end refuses — a negative position (NVL_ERR_INVALID),
  * seq_pos + seq_len > max_seq (NVL_ERR_POSITION), a table too short for seq_pos + seq_len — and ANY table entry outside
  * [0, n_blocks).  More than 128 table entries per sequence are refused by the bf16 prefill kernel's launch. */
-enum { NVL_ATTN_OP_PLAIN = 0, NVL_ATTN_OP_FUSED = 1, NVL_ATTN_OP_MQ = 2, NVL_ATTN_OP_KV8 = 3 };
+enum { NVL_ATTN_OP_PLAIN = 0, NVL_ATTN_OP_FUSED = 1, NVL_ATTN_OP_MQ = 2, NVL_ATTN_OP_KV8 = 3, NVL_ATTN_OP_MQ_KV8 = 4 };
 enum {
     NVL_ATTN_RAN_F32 = 1,             /* attn_f32_kernel */
     NVL_ATTN_RAN_PREFILL = 2,         /* attn_prefill_bf16_kernel */
@@ -838,7 +844,8 @@ enum {
     NVL_ATTN_RAN_DECODE_FUSED = 5,    /* attn_decode_bf16_kernel with RoPE + append */
     NVL_ATTN_RAN_DECODE_KV8 = 6,      /* attn_decode_kv8_kernel */
     NVL_ATTN_RAN_DECODE_MQ = 7,       /* attn_decode_mq_bf16_kernel */
-    NVL_ATTN_RAN_DECODE_STAMPED = 8   /* the diagnostic instantiation of the fused form (nvl_set_debug mode 4) */
+    NVL_ATTN_RAN_DECODE_STAMPED = 8,  /* the diagnostic instantiation of the fused form (nvl_set_debug mode 4) */
+    NVL_ATTN_RAN_DECODE_MQ_KV8 = 9    /* attn_decode_mq_kv8_kernel */
 };
 int nvl_op_attention_batch(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
                            const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
@@ -1118,11 +1125,14 @@ int nvl_bench_gemm(int device, int M, int N, int K, int epi, int force_bnt, int 
  * 0 (default): measured slower (rejected list (27)).
  * key 37: rows per chunk of nvl_score's final norm + LM head + log-probability reduction (default 1024; rounded up to a
  * multiple of 16, at least 16): the logits workspace of a scoring pass is that many rows.
- * key 38: verify passes (nvl_verify_greedy*, nvl_decode_greedy_lookup, nvl_verify_sampled*, nvl_decode_sampled_lookup) in bf16 over a bf16 cache run the multi-position
- * decode attention (1, default); 0 = rope_kv + the prefill attention kernel, the route of an nvl_forward of 1 + k rows.
+ * key 38: verify passes (nvl_verify_greedy*, nvl_decode_greedy_lookup, nvl_verify_sampled*, nvl_decode_sampled_lookup, nvl_verify_speculative) in bf16 run the multi-position
+ * decode attention, over a bf16 cache and over an 8-bit one (1, default); 0 = rope_kv + the prefill attention kernel of the cache type, the route of an nvl_forward of 1 + k rows.
  * key 39: decode passes (one row per sequence) of a model set to NVL_MAMBA_CONV_CARRIED run the convolution, the shift of the
  * kept rows and softplus(dt) as one launch per Mamba2 layer (1, default); 0 = the convolution kernel plus the tail kernel.  No
  * effect in NVL_MAMBA_CONV_PER_CALL mode.
+ * key 40: query tiles per workgroup of the 8-bit multi-position decode attention when a pass has two or more 16-row tiles per
+ * (sequence, kv head) and the head size is 64: 0 (default) two — their K/V loaded and converted once — when one tile per workgroup
+ * would make 320 workgroups or more, else one; 1 = always one; 2 = always two.
  * The settings are PROCESS-GLOBAL and unsynchronised (every model in the process sees them): set them from one thread
  * while no forward call is running.  Every call starts a new tuning epoch: captured decode graphs bake the tuning in and are re-captured.
  * Returns the previous value. */

@@ -174,6 +174,7 @@ def lib():
     L.nvl_set_debug.argtypes = [vp, C.c_int]
     L.nvl_get_hidden.argtypes = [vp, C.c_int, vp, i64]
     L.nvl_get_kv.argtypes = [vp, i64, C.c_int, vp, vp]
+    L.nvl_attention_ran.argtypes = [vp, vp]
     L.nvl_get_mamba_state.argtypes = [vp, i64, C.c_int, vp]
     L.nvl_set_mamba_conv_state.argtypes = [vp, C.c_int]
     L.nvl_set_mamba_rollback.argtypes = [vp, C.c_int]

@@ -14,6 +14,8 @@
 //           permuted identically: MFMA step ks = 2 ks2 + j covers columns ks2*64 + fg*16 + j*8 .. +8); V as whole rows,
 //           16 codes per lane, converted into the bf16 LDS image of attn.h and read back transposed (ds_read_b64_tr_b16).
 //           The same number of tiles per round as the bf16 kernel: half the bytes (and half the registers) in flight.
+//           attn_decode_mq_kv8_kernel is the same stream for the 2..8 positions per sequence of a verify pass: up to two
+//           16-row query tiles per workgroup, so that every K fragment and V tile is loaded and converted once.
 //   prefill: the 8-bit K/V tiles come through registers (16 bytes per lane per tile half), are converted and written
 //           into the bf16 LDS images of attn.h; the next tile's loads are in flight during the current tile's MFMAs.
 #pragma once
@@ -45,6 +47,11 @@ __device__ __forceinline__ bf16x8 kv8_to_bf16x8(uint32_t w0, uint32_t w1) {
     return bf16x8{a[0], a[1], a[2], a[3], b[0], b[1], b[2], b[3]};
 }
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
+#if defined(__HIP_DEVICE_COMPILE__)
+#define NVL_NO_PK_F32 __attribute__((target("no-packed-fp32-ops")))      /* (a device-side target feature: the host pass ignores it loudly) */
+#else
+#define NVL_NO_PK_F32
+#endif
 
 // x [n] fp32 -> codes [n] (4 per thread)
 __global__ __launch_bounds__(256) void kv8_quant_kernel(const float* __restrict__ x, int64_t n, float s, uint8_t* __restrict__ codes) {
@@ -238,6 +245,207 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
     }
     NvlStampsT<false> stamps(nullptr, 0);
     attn_decode_finish<HD, NW>(p, smem, vimg, red_m, red_l, o, m_run, l_run, seq, tok, head, row_ok, wave, lane, fq, fg, vsc, stamps);
+}
+
+// ------------------------------------------------------------------------------------------
+// 8-bit multi-position decode kernel (a verify pass of speculative decoding over an 8-bit cache: S = 2..8 new positions
+// per sequence, their K/V already in the cache as codes, Q pre-rotated bf16).  Rows, masks and grid rules are
+// attn_decode_mq_bf16_kernel's: query row r = j * group + g (position-major), r < min(seq_len, S) * group, each lane its
+// own causal limit qlim = pos0 + j (padding rows: -1, never stored), the workgroup walks the key tiles of its last real
+// row, softmax with GUARD, gridDim.z == 1.  Stream and numerics are attn_decode_kv8_kernel's: 16-byte K code loads
+// straight into VGPRs with Q in the same permuted k order, V as whole rows of 16 codes per lane converted into the wave's
+// bf16 LDS image, k_scale inside sl2, v_scale at the final normalisation, non-temporal loads under p.kv_nt, the same
+// waves and tiles in flight.
+// What is this kernel's own: ONE stream serves up to TQ = 2 consecutive 16-row query tiles of a (sequence, kv head),
+// grid.x = nKV * cdiv(QT, TQ).  Over an 8-bit cache a K fragment costs conversion instructions (4 cvt per MFMA operand)
+// as well as bytes, and the V tile a conversion pass into LDS; with group 4 and S = 5..8 the bf16 kernel's one workgroup
+// per query tile would load and convert the same K/V twice.  Here every K fragment is converted once and meets both
+// tiles' Q fragments (qf[TQ][KS]); the V image is written once and its transposed reads feed both tiles' MFMAs
+// (attn_pv_tile<HD, 2>); m_run / l_run / o[DT] are kept per tile.  A second tile without a real row (an odd tile count,
+// or a sequence shorter than the batch's longest) is skipped by whole workgroups: the rounds are instantiated for one
+// and for two tiles and the choice is made around the round.  The combine runs attn_decode_finish once per tile; a
+// partial O^T is half a V image, so tile qi uses half qi of each wave's image and its own reduction arrays, and no
+// barrier separates the two.  Tile 0's sums do not depend on TQ: the output is bit-equal for TQ = 1 and 2.
+// Registers (gfx950, 8 waves = 256 per lane): hd 64 with TQ = 2 takes 254 and no scratch; hd 128 with TQ = 2 does not fit
+// (two tiles' O^T are 64 registers, Q 32, the round's codes 64, the scores 32: 132 spilled, 312 bytes of scratch), so
+// hd 128 is launched with TQ = 1 only (149 registers) and its second query tile gets a workgroup of its own
+// (scripts/check_isa.sh holds every launched instantiation to "no spill, no scratch").
+// The kernel is compiled without packed fp32 arithmetic (v_pk_mul / add / fma_f32): the per-function form of hipcc's
+// -Xclang -target-feature -Xclang -packed-fp32-ops.
+// ------------------------------------------------------------------------------------------
+template <int HD, int NW, int TQ>
+__global__ __launch_bounds__(NW * 64) NVL_NO_PK_F32 void attn_decode_mq_kv8_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
+                                                                     int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p, int S,
+                                                                     float ksc, float vsc) {
+    constexpr int KS = HD / 32, DT = HD / 16;
+    constexpr int CPR8 = HD / 16, KPI8 = 64 / CPR8, NVL8 = 64 / KPI8;     // 16-code chunks per row, rows per load, loads per tile
+    constexpr int NT2 = HD <= 64 ? 2 : 1;
+    constexpr int TILE_BYTES = 64 * HD * 2, O_BYTES = TILE_BYTES / 2;     // the bf16 LDS image; one tile's partial O^T
+    extern __shared__ __attribute__((aligned(16))) char smem[];           // [NW] wave-private V images (later: TQ partial O^T each)
+    __shared__ float red_m[TQ][NW][16];
+    __shared__ float red_l[TQ][NW][16];
+    const int QT = (S * a_group + 15) >> 4, QW = (QT + TQ - 1) / TQ;
+    const int seq = blockIdx.y, kvh = blockIdx.x / QW, qt0 = (blockIdx.x - kvh * QW) * TQ;
+    const int32_t* tbl = a_blk_table + (int64_t)seq * a_tbl_stride;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int pos0 = a_seq_pos[seq], tok0 = p.seq_tok_start[seq];
+    const int R = min(p.seq_len[seq], S) * a_group;          // real query rows of this (sequence, kv head)
+    if (qt0 * 16 >= R) return;                               // (the whole workgroup: a sequence shorter than the batch's longest)
+    const bool two = TQ == 2 && (qt0 + 1) * 16 < R;          // (workgroup-uniform) the second tile holds a real row
+    const int fq = lane & 15, fg = lane >> 4;                // MFMA role: query row (qt0 + qi)*16 + fq, k group fg
+    const int dch8 = lane % CPR8, ksub8 = lane / CPR8;       // row role: 16-code chunk dch8 of key row ksub8 (+ i*KPI8)
+    bool row_ok[TQ];
+    int tok[TQ], head[TQ], qlim[TQ];
+#pragma unroll
+    for (int qi = 0; qi < TQ; qi++) {
+        const int r = (qt0 + qi) * 16 + fq;
+        row_ok[qi] = r < R;
+        const int rc = row_ok[qi] ? r : qt0 * 16;            // padding rows load a real row's Q; nothing of theirs is stored
+        const int j = rc / a_group;
+        tok[qi] = tok0 + j;
+        head[qi] = kvh * a_group + (rc - j * a_group);
+        qlim[qi] = row_ok[qi] ? pos0 + j : -1;               // last key this lane's row may see
+    }
+    const int n_kt = (pos0 + min(qt0 * 16 + 16 * TQ - 1, R - 1) / a_group) / 64 + 1;     // key tiles of the workgroup's last real row
+    char* vimg = smem + wave * TILE_BYTES;
+    const int vw = wave, nvw = NW;
+    f32x4 o[TQ][DT];
+    float m_run[TQ], l_run[TQ];                              // exp2 domain
+#pragma unroll
+    for (int qi = 0; qi < TQ; qi++) {
+        m_run[qi] = -INFINITY; l_run[qi] = 0.f;
+#pragma unroll
+        for (int d = 0; d < DT; d++) o[qi][d] = f32x4{0.f, 0.f, 0.f, 0.f};
+    }
+    const float sl2 = p.scale * ksc * 1.4426950408889634f;
+    int v_off[DT];
+#pragma unroll
+    for (int d = 0; d < DT; d++) v_off[d] = attn_v_off<HD>(fq, fg, d);
+    // Q of every tile in the permuted k order of the 16-byte K loads
+    bf16x8 qf[TQ][KS];
+#pragma unroll
+    for (int qi = 0; qi < TQ; qi++) {
+        const bf16_t* qp = (const bf16_t*)p.q + (int64_t)tok[qi] * p.q_stride + head[qi] * HD;
+#pragma unroll
+        for (int ks = 0; ks < KS; ks++) qf[qi][ks] = *(const bf16x8*)(qp + (ks >> 1) * 64 + fg * 16 + (ks & 1) * 8);
+    }
+    u32x4 kraw[NT2][4][KS / 2];
+    u32x4 vraw[NT2][NVL8];
+    // (every lambda is always_inline: the kernel's target attribute is not theirs, and the inliner's heuristics refuse a
+    // callee whose target features differ — the round would become calls, with its arrays in scratch)
+    auto issue_round_t = [&](int kt0, auto nt_tag) __attribute__((always_inline)) {
+        constexpr bool NT = decltype(nt_tag)::value;
+#pragma unroll
+        for (int h = 0; h < NT2; h++) {
+            const int kt = kt0 + h * nvw;
+            if (kt >= n_kt) continue;
+            const int bi = kv_block_index(p, kt * 64), krow0 = kt * 64 - bi * p.Tmax;     // the KV block holding this tile
+            const int blk = tbl[min(bi, a_tbl_stride - 1)];
+            const int64_t blk_off = (int64_t)blk * p.slot_stride + ((int64_t)kvh * p.Tmax + krow0) * HD;   // (bytes = elements)
+            const uint8_t* kbase = (const uint8_t*)p.kcache + blk_off;
+            const uint8_t* vbase = (const uint8_t*)p.vcache + blk_off;
+#pragma unroll
+            for (int t = 0; t < 4; t++)
+#pragma unroll
+                for (int k2 = 0; k2 < KS / 2; k2++) {
+                    const u32x4* src = (const u32x4*)(kbase + (int64_t)(t * 16 + fq) * HD + k2 * 64 + fg * 16);
+                    if constexpr (NT) kraw[h][t][k2] = __builtin_nontemporal_load(src); else kraw[h][t][k2] = *src;
+                }
+#pragma unroll
+            for (int i = 0; i < NVL8; i++) {                                                   // 1 KiB, contiguous
+                const u32x4* src = (const u32x4*)(vbase + (int64_t)lane * 16 + i * 1024);
+                if constexpr (NT) vraw[h][i] = __builtin_nontemporal_load(src); else vraw[h][i] = *src;
+            }
+        }
+    };
+    auto issue_round = [&](int kt0) __attribute__((always_inline)) {
+        if (p.kv_nt) issue_round_t(kt0, std::true_type{}); else issue_round_t(kt0, std::false_type{});
+    };
+    // one round for NQ = 1 or 2 query tiles: every K fragment converted once for NQ MFMAs, per-tile softmax, the V image
+    // written once for NQ tiles' P.V
+    auto do_round = [&](int kt0, auto nq_tag) __attribute__((always_inline)) {
+        constexpr int NQ = decltype(nq_tag)::value;
+        f32x4 s[NQ][NT2][4];
+        float tmax[NQ];
+#pragma unroll
+        for (int qi = 0; qi < NQ; qi++) tmax[qi] = -INFINITY;
+#pragma unroll
+        for (int h = 0; h < NT2; h++) {
+            const int kt = kt0 + h * nvw;
+            if (kt >= n_kt) {
+#pragma unroll
+                for (int qi = 0; qi < NQ; qi++)
+#pragma unroll
+                    for (int t = 0; t < 4; t++) s[qi][h][t] = f32x4{-INFINITY, -INFINITY, -INFINITY, -INFINITY};
+                continue;
+            }
+#pragma unroll
+            for (int t = 0; t < 4; t++) {
+                f32x4 acc[NQ];
+#pragma unroll
+                for (int qi = 0; qi < NQ; qi++) acc[qi] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int k2 = 0; k2 < KS / 2; k2++) {
+                    const u32x4 w = kraw[h][t][k2];
+                    const bf16x8 ka = kv8_to_bf16x8(w[0], w[1]), kb = kv8_to_bf16x8(w[2], w[3]);
+#pragma unroll
+                    for (int qi = 0; qi < NQ; qi++) {
+                        acc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ka, qf[qi][2 * k2], acc[qi], 0, 0, 0);
+                        acc[qi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kb, qf[qi][2 * k2 + 1], acc[qi], 0, 0, 0);
+                    }
+                }
+#pragma unroll
+                for (int qi = 0; qi < NQ; qi++) {
+                    const int lim = qlim[qi] - kt * 64 - fg * 4;      // this row's last visible key, relative to the lane's first
+#pragma unroll
+                    for (int r4 = 0; r4 < 4; r4++) {
+                        float v = acc[qi][r4] * sl2;
+                        v = (t * 16 + r4 <= lim) ? v : -INFINITY;
+                        acc[qi][r4] = v;
+                        tmax[qi] = fmaxf(tmax[qi], v);
+                    }
+                    s[qi][h][t] = acc[qi];
+                }
+            }
+        }
+#pragma unroll
+        for (int qi = 0; qi < NQ; qi++) attn_decode_softmax<HD, NT2, true>(s[qi], tmax[qi], m_run[qi], l_run[qi], o[qi]);
+#pragma unroll
+        for (int h = 0; h < NT2; h++) {
+            if (kt0 + h * nvw >= n_kt) continue;
+#pragma unroll
+            for (int i = 0; i < NVL8; i++) {          // 16 codes of row i*KPI8 + ksub8 -> bf16 chunks 2 dch8, 2 dch8 + 1
+                const int row = i * KPI8 + ksub8;
+                const u32x4 w = vraw[h][i];
+                *(bf16x8*)(vimg + 16 * kv_img_chunk<HD>(row, 2 * dch8)) = kv8_to_bf16x8(w[0], w[1]);
+                *(bf16x8*)(vimg + 16 * kv_img_chunk<HD>(row, 2 * dch8 + 1)) = kv8_to_bf16x8(w[2], w[3]);
+            }
+            f32x4 pt[NQ][4];                          // this key tile's P^T of every query tile
+#pragma unroll
+            for (int qi = 0; qi < NQ; qi++)
+#pragma unroll
+                for (int t = 0; t < 4; t++) pt[qi][t] = s[qi][h][t];
+            attn_pv_tile<HD, NQ, false>(vimg, v_off, pt, o, nullptr);
+        }
+    };
+    for (int kt0 = vw; kt0 < n_kt; kt0 += NT2 * nvw) {
+        issue_round(kt0);
+        if constexpr (TQ == 2) {
+            if (two) do_round(kt0, std::integral_constant<int, 2>{}); else do_round(kt0, std::integral_constant<int, 1>{});
+        } else {
+            do_round(kt0, std::integral_constant<int, 1>{});
+        }
+    }
+    // the one-position kernel's combine, once per tile (every real row saw key 0, so its maximum over the waves is finite;
+    // a wave that saw none of a row's keys enters with weight exp2(-inf) = 0)
+    NvlStampsT<false> stamps(nullptr, 0);
+#pragma unroll
+    for (int qi = 0; qi < TQ; qi++) {
+        if (qi == 1 && !two) break;
+        attn_decode_finish<HD, NW>(p, smem + qi * O_BYTES, vimg + qi * O_BYTES, red_m[qi], red_l[qi], o[qi], m_run[qi], l_run[qi],
+                                   seq, tok[qi], head[qi], row_ok[qi], wave, lane, fq, fg, vsc, stamps);
+    }
 }
 
 // ------------------------------------------------------------------------------------------

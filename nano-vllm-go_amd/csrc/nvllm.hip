@@ -1486,6 +1486,7 @@ static int g_attn_nw = 0;      // nvl_set_tuning key 15: waves per decode-attent
 static int g_attn_tq2 = 1;     // nvl_set_tuning key 10: unused since round 2 (the prefill kernel always keeps two sub-tiles per wave)
 static int g_attn_kv_nt = 1;   // nvl_set_tuning key 35: non-temporal K/V loads in the decode attention (0 never, 1 automatic, 2 always)
 static int g_attn_split = 1;   // nvl_set_tuning key 25: split a decode attention's keys over up to 8 workgroups per (sequence, kv head) (0 = never)
+static int g_mq_kv8_tq = 0;    // nvl_set_tuning key 40: query tiles per workgroup of the 8-bit multi-position decode attention (0 = by grid size, 1 = one, 2 = two where the pass has them)
 static int g_verify_mq = 1;    // nvl_set_tuning key 38: verify passes (nvl_verify_greedy*) run the multi-position decode attention (0 = rope_kv + the prefill kernel)
 // Launch shape of the decode attention for the batch being enqueued (also part of a captured graph's key): waves per
 // workgroup | workgroups per (sequence, kv head) << 8.
@@ -1496,11 +1497,22 @@ static int g_verify_mq = 1;    // nvl_set_tuning key 38: verify passes (nvl_veri
 // Llama-3.2-1B, 2048 / 1024 keys): B=1 0.891 -> 0.811 / 0.808 -> 0.780, B=2 0.893 -> 0.834 / 0.869 -> 0.792, B=4 (4
 // workgroups per pair) 0.924 -> 0.883 / 0.812 -> 0.817 (hence from 2048 keys on above 16 pairs); B=8 loses either way
 // (2 workgroups per pair 0.96 -> 0.99, 8 per pair -> 1.13).
-// mq_S > 0: the multi-position kernel with mq_S positions per sequence — its grid, and never a key split.
+// mq_S > 0: the multi-position kernel with mq_S positions per sequence — its grid, and never a key split.  Over an 8-bit
+// cache a workgroup takes mq_kv8_tq query tiles (kv8.h attn_decode_mq_kv8_kernel).  Two need two tiles and head size 64 (hd 128
+// with two tiles does not fit the register file: kv8.h), and pay only once the one-tile grid would fill the chip — from
+// 320 workgroups on, where the wave ladder below starts to shrink.  Below that a second workgroup per kv head is free
+// parallelism and re-reads its K/V from L2 (profiles/r20_spec_kv_fp8.txt, Llama-3.2-1B, k = 7, ms per pass two / one tile at
+// 512 and at 4096 keys: B = 1 0.872 / 0.834 and 1.105 / 0.990, B = 16 (256 workgroups) 1.802 / 1.781 and 2.064 / 2.046; B = 20
+// (320) 2.019 / 2.023 and 2.273 / 2.377, B = 32 (512) 2.221 / 2.272 and 2.515 / 2.908).
+static int mq_kv8_tq(const nvl_model* m, int qt, int n_seqs) {
+    if (qt < 2 || m->hd != 64 || g_mq_kv8_tq == 1) return 1;
+    return g_mq_kv8_tq == 2 || m->nKV * qt * n_seqs >= 320 ? 2 : 1;
+}
 int decode_attn_cfg(const nvl_model* m, int n_seqs, int mq_S = 0) {
     const int n_kt = m->ctx_hint > 0 ? (m->ctx_hint - 1) / 64 + 1 : 1 << 20;
     const int per_wave = m->hd == 64 ? 2 : 1;
-    const int wgs = m->nKV * cdiv(m->group * std::max(mq_S, 1), 16) * n_seqs;
+    const int qt = cdiv(m->group * std::max(mq_S, 1), 16);
+    const int wgs = m->nKV * (mq_S && m->kv8 ? cdiv(qt, mq_kv8_tq(m, qt, n_seqs)) : qt) * n_seqs;
     if (!mq_S && g_attn_split && !g_attn_nw && m->attn_part && m->ctx_hint > 0 && wgs <= ATTN_SPLIT_MAX_PAIRS && n_kt >= 16) {
         const int want = cdiv(n_kt, 2 * per_wave);                       // workgroups of 2 waves that get a full round each
         const int ns = (wgs > 16 && n_kt < 32) ? 1 : std::min(std::min(want, ATTN_SPLIT_MAX), 128 / wgs);
@@ -1528,8 +1540,9 @@ static void launch_decode_attn(nvl_model* m, dim3 grid, int nw, int tile_bytes, 
 // are then the layer's code slabs (same element layout, one byte per element; kv8.h) — else NULL.  The 8-bit kernels have
 // no fused (RoPE + append) and no stamped form, and their prefill kernel reads the block table from global memory (no
 // 128-block limit); grids, wave choices and the K/V load policy are the same.
-// mq: the caller is a verify pass (or nvl_op_attention_mq): 2..8 positions per sequence on attn_decode_mq_bf16_kernel.
-static bool attention_mq_ok(const nvl_model* m, int max_len) { return !m->f32 && !m->kv8 && max_len >= 2 && max_len <= 8; }
+// mq: the caller is a verify pass (or nvl_op_attention_mq): 2..8 positions per sequence on attn_decode_mq_bf16_kernel, over
+// an 8-bit cache on attn_decode_mq_kv8_kernel.
+static bool attention_mq_ok(const nvl_model* m, int max_len) { return !m->f32 && max_len >= 2 && max_len <= 8; }
 static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_len, const void* kc, const void* vc,
                              double flops, double abytes, bool fused_qkv, const float* kv8, bool mq = false) {
     AttnArgs a{};
@@ -1547,6 +1560,18 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         if (lds > 64 * 1024) NVL_LDS_ATTR(attn_f32_kernel, 160 * 1024 - 64);
         hipLaunchKernelGGL(attn_f32_kernel, dim3(max_len, m->nH, n_seqs), dim3(256), lds, m->stream, a, m->hd);
         m->attn_ran[0] = NVL_ATTN_RAN_F32; m->attn_ran[1] = 4; m->attn_ran[2] = 1;
+    } else if (mq && kv8 && attention_mq_ok(m, max_len)) {
+        const int nw = decode_attn_cfg(m, n_seqs, max_len) & 255;
+        const int qt = cdiv(m->group * max_len, 16), tq = mq_kv8_tq(m, qt, n_seqs), qw = cdiv(qt, tq);
+        dim3 grid(m->nKV * qw, n_seqs, 1);     // (kv head x group of tq 16-row query tiles, sequence); no key split
+        // K/V read once per step by its only workgroup: the one-position launch's policy, with this grid
+        a.kv_nt = g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && qw == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
+#define NVL_DEC_MQ8(HDv, TQv) launch_decode_attn<attn_decode_mq_kv8_kernel<HDv, 2, TQv>, attn_decode_mq_kv8_kernel<HDv, 4, TQv>, \
+                                                 attn_decode_mq_kv8_kernel<HDv, 8, TQv>>(m, grid, nw, 64 * HDv * 2, a, max_len, kv8[0], kv8[1])
+        if (m->hd == 64) { if (tq == 2) NVL_DEC_MQ8(64, 2); else NVL_DEC_MQ8(64, 1); }
+        else NVL_DEC_MQ8(128, 1);
+#undef NVL_DEC_MQ8
+        m->attn_ran[0] = NVL_ATTN_RAN_DECODE_MQ_KV8; m->attn_ran[1] = nw; m->attn_ran[2] = 1;
     } else if (mq && !kv8 && attention_mq_ok(m, max_len)) {
         const int nw = decode_attn_cfg(m, n_seqs, max_len) & 255;
         dim3 grid(m->nKV * cdiv(m->group * max_len, 16), n_seqs, 1);     // (kv head x 16-row query tile, sequence); no key split
@@ -1620,10 +1645,10 @@ void attention(nvl_model* m, int li, const Meta& md, int n_seqs, int max_len, do
                      (char*)m->vcache + (size_t)li * m->layer_stride * m->wsize, flops, m->kv_tok * 2.0 * m->nKV * m->hd * (double)m->wsize, fused_qkv, nullptr, mq);
 }
 // attention over an 8-bit cache: kc / vc the layer's code slabs, k_scale / v_scale the layer's scales.  bf16 only.
-void attention_kv8(nvl_model* m, const Meta& md, int n_seqs, int max_len, const void* kc, const void* vc, float ksc, float vsc) {
+void attention_kv8(nvl_model* m, const Meta& md, int n_seqs, int max_len, const void* kc, const void* vc, float ksc, float vsc, bool mq = false) {
     if (m->f32) throw std::runtime_error("attention_kv8: the 8-bit KV cache is bf16-only");
     const float scales[2] = {ksc, vsc};
-    attention_launch(m, md, n_seqs, max_len, kc, vc, 0.0, m->kv_tok * 2.0 * m->nKV * m->hd, false, scales);
+    attention_launch(m, md, n_seqs, max_len, kc, vc, 0.0, m->kv_tok * 2.0 * m->nKV * m->hd, false, scales, mq);
 }
 
 void rope_kv(nvl_model* m, int li, const Meta& md, int M) {
@@ -2493,7 +2518,7 @@ int enqueue_forward(nvl_model* m, const Meta& md, int n_seqs, int M, int max_len
         xn_deferred = false;
         if (m->kv8)
             attention_kv8(m, md, n_seqs, max_len, (char*)m->kcache + (size_t)li * m->layer_stride,
-                          (char*)m->vcache + (size_t)li * m->layer_stride, m->k_scale[li], m->v_scale[li]);
+                          (char*)m->vcache + (size_t)li * m->layer_stride, m->k_scale[li], m->v_scale[li], (seam & 8) != 0);
         else
             attention(m, li, md, n_seqs, max_len, attn_flops, fused_dec, (seam & 8) != 0);
         const DevTensor* nxt_w = li + 1 < m->L ? &m->layers[li + 1].t[NVL_T_ATTN_NORM_W] : &m->g[NVL_T_FINAL_NORM_W];
@@ -3801,6 +3826,12 @@ extern "C" int nvl_get_kv(nvl_model* m, int64_t seq_id, int layer, float* k_out,
     read_kv(m, &slot, 1, T, layer, k_out, v_out);
     return T;
     NVL_CATCH(m)
+}
+
+extern "C" int nvl_attention_ran(const nvl_model* m, int32_t ran[3]) {
+    if (!m || !ran) return NVL_ERR_INVALID;
+    for (int i = 0; i < 3; i++) ran[i] = m->attn_ran[i];
+    return NVL_OK;
 }
 
 extern "C" int nvl_get_mamba_state(nvl_model* m, int64_t seq_id, int layer, float* out) {

@@ -627,7 +627,7 @@ extern "C" int nvl_op_attention_kv8(int device, const float* q, const float* k, 
     OP_CATCH
 }
 
-// attention() / attention_kv8() on a batch as plan_paged lays it out, set up as nvl_create sets a model up: Tmax = the block
+// attention() / attention_kv8() (with the verify flag: NVL_ATTN_OP_MQ / NVL_ATTN_OP_MQ_KV8) on a batch as plan_paged lays it out, set up as nvl_create sets a model up: Tmax = the block
 // size, slot_stride = one block of one layer, blocks_per_seq = the table's stride, ctx_hint as attn_cost computes it, the
 // split scratch and its zeroed tickets.  attn_out and attn_part start as 0xFF bytes (NaN in bf16 and fp32): a row nobody
 // wrote, or a partial record read before its workgroup wrote it, shows in `out`.  Nothing that could index outside the
@@ -639,10 +639,11 @@ extern "C" int nvl_op_attention_batch(int device, int precision, int form, int n
     const char* who = "nvl_op_attention_batch: ";
     if (!seq_len || !seq_pos || !k_pool || !v_pool || !block_table || !q || !out || !ran || !part_cnt || nH <= 0 || nKV <= 0 ||
         nH % nKV || (hd != 64 && hd != 128) || n_seqs <= 0 || n_seqs > 4096 || n_blocks <= 0 || block_size <= 0 || block_size % 64 ||
-        tbl_stride <= 0 || max_seq <= 0 || form < NVL_ATTN_OP_PLAIN || form > NVL_ATTN_OP_KV8 ||
+        tbl_stride <= 0 || max_seq <= 0 || form < NVL_ATTN_OP_PLAIN || form > NVL_ATTN_OP_MQ_KV8 ||
         (precision != NVL_PRECISION_BF16 && precision != NVL_PRECISION_F32) || !(scale >= 0.f) || !std::isfinite(scale))
         return op_fail(std::string(who) + "bad arguments");
-    const bool fused = form == NVL_ATTN_OP_FUSED, kv8 = form == NVL_ATTN_OP_KV8, mq = form == NVL_ATTN_OP_MQ;
+    const bool fused = form == NVL_ATTN_OP_FUSED, kv8 = form == NVL_ATTN_OP_KV8 || form == NVL_ATTN_OP_MQ_KV8;
+    const bool mq = form == NVL_ATTN_OP_MQ || form == NVL_ATTN_OP_MQ_KV8;
     if (form != NVL_ATTN_OP_PLAIN && precision != NVL_PRECISION_BF16) return op_fail(std::string(who) + "the fused, mq and kv8 forms are bf16 only");
     if (kv8 && (!(k_scale > 0.f) || !(v_scale > 0.f) || !std::isfinite(k_scale) || !std::isfinite(v_scale)))
         return op_fail(std::string(who) + "k_scale / v_scale must be finite and positive");
@@ -725,7 +726,7 @@ extern "C" int nvl_op_attention_batch(int device, int precision, int form, int n
         m.attn_part = nullptr; m.attn_part_cnt = nullptr;
     };
     try {
-        if (kv8) attention_kv8(&m, md, n_seqs, max_len, k8, v8, k_scale, v_scale);
+        if (kv8) attention_kv8(&m, md, n_seqs, max_len, k8, v8, k_scale, v_scale, mq);
         else attention(&m, 0, md, n_seqs, max_len, 0.0, fused, mq);
     } catch (...) { release(); throw; }
     for (int i = 0; i < 3; i++) ran[i] = m.attn_ran[i];
@@ -1777,6 +1778,7 @@ extern "C" int nvl_set_tuning(int key, int value) {
     if (key == 35) { const int old = g_attn_kv_nt; g_attn_kv_nt = value; return old; }
     if (key == 36) { const int old = g_wide_ntb; g_wide_ntb = value; return old; }
     if (key == 38) { const int old = g_verify_mq; g_verify_mq = value; return old; }
+    if (key == 40) { const int old = g_mq_kv8_tq; g_mq_kv8_tq = value; return old; }
     if (key == 39) { const int old = g_mamba_conv_step; g_mamba_conv_step = value; return old; }
     if (key == 37) { const int old = g_score_rows; g_score_rows = value < 16 ? 16 : (value + 15) / 16 * 16; return old; }
     return -1;

@@ -688,6 +688,14 @@ class HipTransformerModel:
         L.check(self.lib.nvl_get_kv(self.h, seq_id, layer, _ptr(k), _ptr(v)), self.h)
         return k, v
 
+    def attention_ran(self):
+        """The model's last attention launch: (an ops.ATTN_RAN name or None, waves per workgroup, workgroups per
+        (sequence, kv head) of a key split)."""
+        from .ops import ATTN_RAN
+        ran = np.zeros(3, np.int32)
+        L.check(self.lib.nvl_attention_ran(self.h, _ptr(ran)), self.h)
+        return ATTN_RAN.get(int(ran[0])), int(ran[1]), int(ran[2])
+
     # -- measurement -------------------------------------------------------------------------------
     def set_profile(self, on: bool):
         L.check(self.lib.nvl_set_profile(self.h, int(on)), self.h)

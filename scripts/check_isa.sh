@@ -34,7 +34,7 @@ for blk in re.split(r"\n  - \.agpr_count:", meta)[1:]:
     g = lambda k: int(re.search(r"\." + k + r": *(\d+)", blk).group(1))
     name = re.search(r"\.name: *(\S+)", blk).group(1)
     agpr = int(re.match(r" *(\d+)", blk).group(1))
-    kern[name] = dict(vgpr=g("vgpr_count"), agpr=agpr, spill=g("vgpr_spill_count"))
+    kern[name] = dict(vgpr=g("vgpr_count"), agpr=agpr, spill=g("vgpr_spill_count"), scratch=g("private_segment_fixed_size"))
 bad = 0
 def check(pattern, what, ok):
     global bad
@@ -51,6 +51,9 @@ check(r"attn_decode_bf16_kernelILi64ELi[248]ELb[01]ELb0E", "decode attention hd 
 check(r"attn_decode_bf16_kernelILi128ELi8ELb[01]ELb0E", "decode attention hd 128, 8 waves", lambda r: r["vgpr"] <= 256 and r["spill"] <= 8)
 # the multi-position decode attention of a verify pass: the same budget at every wave count and both head sizes
 check(r"attn_decode_mq_bf16_kernelILi(64|128)ELi[248]E", "multi-position decode attention", lambda r: r["vgpr"] <= 256 and r["spill"] == 0)
+# ... and its form over an 8-bit cache (kv8.h; hd 128 is launched with one query tile per workgroup only).  Scratch too: a lambda
+# of the kernel that is not inlined passes the round's arrays through it without a single spill being counted
+check(r"attn_decode_mq_kv8_kernelILi(64|128)ELi[248]ELi[12]E", "multi-position decode attention, 8-bit cache", lambda r: r["vgpr"] <= 512 and r["spill"] == 0 and r["scratch"] == 0)
 # decode projections: the 64-row-group instantiations (PASSES) and the wide form
 check(r"gemm_skinny_bf16_kernelILi4ELi[124]ELi2ELi[0-4]E\w+Lb1ELb0ELb0E", "narrow projection, 64-row groups", lambda r: r["spill"] <= 12)
 check(r"gemm_skinny_bf16_kernelILi[12]ELi[124]ELi4ELi[0-4]E\w+Lb0ELb0ELb[01]E", "narrow projection, <= 32 rows", lambda r: r["spill"] <= 12)

@@ -29,7 +29,16 @@ launched eagerly), the rejection kernel's own time from the library's per-kernel
 "spec_reject"; taken in a separate run of the same passes), one step of nvl_decode_sampled on the target, and the
 accepted drafts per pass from which a pass pair pays:  (draft + verify) / plain step - 1.
 
-    python scripts/spec_decode.py --draft --ks 3"""
+    python scripts/spec_decode.py --draft --ks 3
+
+--kv-fp8: verify passes over the 8-bit KV cache (kv_cache_dtype="fp8_e4m3") on the Llama-3.2-1B and
+Llama-3-8B shapes, at every (context, batch, k) of --ctxs x --batches x --ks: nvl_verify_greedy under nvl_set_tuning key 38 =
+1 (kv8.h attn_decode_mq_kv8_kernel) and key 38 = 0 (rope_kv + the 8-bit prefill kernel), and where the pass has two query
+tiles per kv head (k = 7, hd 64) also key 40 = 1 / 2 (one / two tiles per workgroup), timed alternately in one process: wall clock per
+pass, best and median of --reps windows of --passes passes, then — in a run of its own with the library's per-kernel events
+on (nvl_set_profile) — the "attention" site's time per launch.
+
+    python scripts/spec_decode.py --kv-fp8 --batches 1,8,32 --ks 3,7 --ctxs 512,4096"""
 import argparse
 import importlib
 import importlib.util
@@ -62,11 +71,16 @@ def main():
     ap.add_argument("--sampled", action="store_true")
     ap.add_argument("--draft", action="store_true")
     ap.add_argument("--draft-layers", type=int, default=4)
+    ap.add_argument("--kv-fp8", action="store_true")
+    ap.add_argument("--ctxs", default="512,4096")
+    ap.add_argument("--models", default="llama-3.2-1b,llama-3-8b")
     args = ap.parse_args()
     import torch
     pkg = importlib.import_module("nano-vllm-go_amd")
     assert pkg.lib().nvl_device_count() >= 1, "no GPU: nothing here can be measured without one"
     bench = load_bench()
+    if args.kv_fp8:
+        return kv_fp8_mode(args, pkg, bench, torch)
     cfg = dict(pkg.synth.FULL_CONFIGS["llama-3.2-1b"])
     V, S, G = cfg["vocab_size"], args.ctx, args.gen
     batches = [int(b) for b in args.batches.split(",")]
@@ -191,6 +205,72 @@ def main():
                       f"{res[0][1]} passes, always wrong {res[1][0]:9.1f} tok/s in {res[1][1]} passes "
                       f"(plain greedy: {B / statistics.median(plain) * 1e3:9.1f} tok/s)", flush=True)
     model.close()
+
+
+def kv_fp8_mode(args, pkg, bench, torch):
+    tune = pkg.lib().nvl_set_tuning
+    ctxs, batches, ks = ([int(x) for x in a.split(",")] for a in (args.ctxs, args.batches, args.ks))
+    Bmax = max(batches)
+    r = np.random.default_rng(0)
+    for name in args.models.split(","):
+        cfg = dict(pkg.synth.FULL_CONFIGS[name], max_seq_len=max(ctxs) + 64)
+        V = cfg["vocab_size"]
+        model = pkg.HipTransformerModel(cfg, None, device=0, precision="bf16", kv_cache_dtype="fp8_e4m3", max_seqs=Bmax,
+                                        max_batch_tokens=max(max(ctxs), Bmax * 8))
+        bench.gen_weights_on_device(pkg, cfg, model, torch, torch.device("cuda", 0), keep_host=False)
+        model.finalize()
+        for S in ctxs:
+            for i in range(Bmax):                       # one sequence per prefill pass: the batch only has to hold one context
+                model.seq_reset(i)
+                model.forward_batch([i], [r.integers(0, V, S).astype(np.int32)], [0], want_logits=False)
+            for B in batches:
+                ids = list(range(B))
+                for k in ks:
+                    rows = r.integers(0, V, (B, 1 + k)).astype(np.int32)
+                    routes = {"key38=1": {38: 1}, "key38=0": {38: 0}}
+                    if (1 + k) * cfg["num_heads"] // cfg["num_kv_heads"] > 16 and cfg["head_dim"] == 64:
+                        routes.update({"key38=1 key40=1": {38: 1, 40: 1}, "key38=1 key40=2": {38: 1, 40: 2}})
+
+                    def many():
+                        for _ in range(args.passes):
+                            model.verify_greedy(ids, rows, k)
+                            for i in ids:
+                                model.seq_truncate(i, S)
+                        torch.cuda.synchronize()
+
+                    def under(keys, fn):
+                        old = {key: tune(key, value) for key, value in keys.items()}
+                        out = fn()
+                        for key, value in old.items():
+                            tune(key, value)
+                        return out
+
+                    def timed():
+                        t0 = time.perf_counter()
+                        many()
+                        return (time.perf_counter() - t0) / args.passes * 1e3
+
+                    def site():                          # the attention launches alone: per-kernel events, in a run of their own
+                        model.set_profile(True)
+                        model.reset_stats()
+                        many()
+                        st = [x for x in model.kernel_stats() if x["site"] == "attention"]
+                        model.set_profile(False)
+                        model.reset_stats()
+                        return sum(x["ms"] for x in st) / max(1, sum(x["launches"] for x in st)) * 1e3, model.attention_ran()
+
+                    wall = {n: [] for n in routes}
+                    for rep_i in range(args.reps + 1):    # rep 0: warm-up of every route (first sight, graph capture)
+                        for n, keys in routes.items():
+                            t = under(keys, timed)
+                            if rep_i:
+                                wall[n].append(t)
+                    for n, keys in routes.items():
+                        us, ran = under(keys, site)
+                        print(f"{name} ctx={S} B={B} k={k} ({n}): {min(wall[n]):.4f} ms per pass best, {statistics.median(wall[n]):.4f} "
+                              f"median, {max(wall[n]):.4f} worst of {args.reps} x {args.passes}; attention site {us:.2f} us per launch "
+                              f"({ran[0]}, {ran[1]} waves)", flush=True)
+        model.close()
 
 
 def sampled_mode(args, pkg, model, prompts, batches, ks, clock):
