@@ -205,6 +205,16 @@ enum { NVL_MAMBA_CONV_PER_CALL = 0,   /* every call zero-pads (mamba2.go:181-254
  * paged and tensor-parallel hybrids stay refused.  No memory is added: the rows live in the buffer the runner's chunked
  * prefill already used.  A decode pass pays no extra launch for it (nvl_set_tuning key 39). */
 int nvl_set_mamba_conv_state(nvl_model* m, int mode);
+/* Sliding-window attention (Mistral).  window = W >= 1: in every attention layer the query at absolute
+ * position i sees keys j with i - W < j <= i — W keys, itself included (HF Mistral's kv_idx > q_idx - sliding_window); 0
+ * (default) is causal attention over every key.  After nvl_create, before nvl_finalize (else NVL_ERR_STATE); a negative window
+ * and a NULL model are NVL_ERR_INVALID.  Every pass honours it: nvl_forward, paged, nvl_score, the greedy and sampled loops and
+ * their graph replay, the verify / lookup / speculative calls, tensor parallel, both precisions and both cache dtypes.  The
+ * kernels start at the tile of the lowest visible key, so a decode step reads W + <64 keys per (sequence, kv head) whatever
+ * the context.  The cache is not circular: keys below the window stay where they are (nvl_seq_truncate and the verify
+ * rollback work as before) and no block is freed.  A hybrid model's Mamba2 layers are untouched. */
+int nvl_set_sliding_window(nvl_model* m, int window);
+int nvl_get_sliding_window(const nvl_model* m);   /* 0 for a NULL model */
 /* Speculative decoding on a hybrid model.  A Mamba2 state that a pass of 1 + k rows has advanced cannot
  * go back to 1 + n_accepted rows, so by default (NONE) every verify entry point refuses a model with Mamba2 layers.  VERIFY
  * makes the pass not advance it: each Mamba2 layer of a verify pass reads the slot's state and kept convolution rows and
@@ -363,6 +373,10 @@ int nvl_load_safetensors(nvl_model* m, const char* path);
  * the reference's model_info.json) -> nvl_model_config.  Reference quirks kept: max_position_embeddings and
  * rope_scaling are not read.  Errors are reported through nvl_last_error(NULL). */
 int nvl_load_config_json(const char* path, nvl_model_config* cfg);
+/* nvl_load_config_json's sibling for what nvl_model_config cannot carry: *window = the config's "sliding_window" (a JSON
+ * null, 0 or an absent key: 0).  model_type "mistral" / "MistralForCausalLM" selects the Llama template above.
+ * nvl_load_safetensors on a checkpoint DIRECTORY applies its config.json's window when the model has none set. */
+int nvl_load_config_window(const char* path, int* window);
 
 /* Helpers for checkpoints that keep fused projections (generic_loader.go:674-765):
  * GPT-2 c_attn [H, 3H] split by columns; Falcon query_key_value given in the reference's
@@ -851,6 +865,12 @@ int nvl_op_attention_batch(int device, int precision, int form, int nH, int nKV,
                            const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
                            int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
                            int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt);
+/* The same under nvl_set_sliding_window(window) (window >= 0; 0 = nvl_op_attention_batch): the windowed instantiations of
+ * the same kernel families, so ran[] keeps the NVL_ATTN_RAN_* codes. */
+int nvl_op_attention_batch_window(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                                  const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                                  int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                                  int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window);
 /* The FRONT of an attention layer as a layer of the model runs it, stage by stage (generic_model.go:295-302 embedWithOffset,
  * :304-318 attention norm, the QKV projection with its bias, rope.go:153-205 on Q and K, Q into the attention operand
  * buffer, K / V into the paged cache): the forward pass's own embed() and qkv_front() on a batch laid out as the paged

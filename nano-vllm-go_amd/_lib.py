@@ -159,6 +159,7 @@ def lib():
     L.nvl_upload_falcon_qkv.argtypes = [vp, C.c_int, vp]
     L.nvl_load_safetensors.argtypes = [vp, C.c_char_p]
     L.nvl_load_config_json.argtypes = [C.c_char_p, C.POINTER(ModelConfigC)]
+    L.nvl_load_config_window.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
     L.nvl_finalize.argtypes = [vp]
     L.nvl_destroy.argtypes = [vp]
     L.nvl_destroy.restype = None
@@ -178,6 +179,8 @@ def lib():
     L.nvl_get_mamba_state.argtypes = [vp, i64, C.c_int, vp]
     L.nvl_set_mamba_conv_state.argtypes = [vp, C.c_int]
     L.nvl_set_mamba_rollback.argtypes = [vp, C.c_int]
+    L.nvl_set_sliding_window.argtypes = [vp, C.c_int]
+    L.nvl_get_sliding_window.argtypes = [vp]
     L.nvl_get_mamba_conv_state.argtypes = [vp, i64, C.c_int, vp]
     L.nvl_get_weight.argtypes = [vp, C.c_int, C.c_int, vp, i64, i64]
     L.nvl_get_stamps.argtypes = [vp, vp, C.c_int, vp, i64]
@@ -250,6 +253,7 @@ def lib():
     L.nvl_op_moe_stages_q.argtypes = [C.c_int, C.c_int, vp, vp, vp, vp] + [C.c_int] * 7 + [vp] * 7
     L.nvl_op_attention_batch.argtypes = ([C.c_int] * 6 + [f32, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_double,
                                           C.c_int, f32, f32, vp, vp, vp])
+    L.nvl_op_attention_batch_window.argtypes = L.nvl_op_attention_batch.argtypes + [C.c_int]
     L.nvl_op_mamba_mixer.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp] + [C.c_int] * 6 + [vp] * 8 + [C.c_int] + [vp] * 4
     L.nvl_op_mamba_verify.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp] + [C.c_int] * 6 + [vp] * 8 + [C.c_int] + [vp] * 5
     sp = C.POINTER(SamplingParamsC)

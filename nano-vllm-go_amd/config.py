@@ -45,6 +45,7 @@ class ModelConfig:
     mamba_head_dim: int = 0
     mamba_n_groups: int = 0
     mamba_conv_kernel: int = 0
+    sliding_window: int = 0           # HF Mistral "sliding_window": row i sees keys i - W < j <= i; 0 / null = none
 
     @property
     def mamba_layer_mask(self):
@@ -106,7 +107,7 @@ def _infer_config_from_json(raw: dict) -> ModelConfig:    # generic_loader.go:97
         return new_gpt2_config()
     if mt in ("falcon", "RefinedWeb", "RefinedWebModel"):
         return new_falcon_config("7b")
-    if mt in ("llama", "LlamaForCausalLM"):
+    if mt in ("llama", "LlamaForCausalLM", "mistral", "MistralForCausalLM"):     # ArchMistral: Llama + sliding_window
         return new_llama_config("7b")
     if mt == "granitemoe":
         return new_granite_moe_config("350m")
@@ -207,4 +208,7 @@ def load_model_config(raw: dict | str) -> ModelConfig:
     v = num("num_experts_per_tok")
     if v is not None:
         c.num_experts_per_tok = int(v)
+    v = num("sliding_window")                               # (null or absent: none)
+    if v is not None:
+        c.sliding_window = int(v)
     return c

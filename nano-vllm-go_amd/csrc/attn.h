@@ -54,7 +54,16 @@ struct AttnArgs {
     int32_t* part_cnt;    // zero between launches
     unsigned long long* stamps;   // diagnostic runs: per-workgroup time stamps (common.h nvl_stamp), else NULL
     int kv_nt;                    // decode: non-temporal K/V loads (set by the host: attention() in nvllm.hip)
+    // sliding window (the WINDOW instantiations only; W >= 1): the row at position i sees keys i - W < j <= i.  Keys
+    // below a row's window stay in the cache and are not read: every kernel starts at the tile of its first row's lowest key.
+    int window;
 };
+// The two-sided mask of a windowed kernel as ONE unsigned compare: with lo = limit - (W - 1) the lowest visible key,
+// lo <= key <= limit  <=>  (unsigned)(key - lo) <= W - 1 (keys, limit and lo relative to the same origin; the host keeps
+// W <= 2^30, so nothing wraps).  A padding row's limit -1 puts every key >= 0 at distance >= W: masked.
+__device__ __forceinline__ bool attn_in_window(int key, int lo, int wm1) { return (unsigned)(key - lo) <= (unsigned)wm1; }
+// first key tile of a row at position qpos under window W
+__device__ __forceinline__ int attn_window_kt_lo(int qpos, int window) { return max(0, qpos - window + 1) >> 6; }
 template <int HD> constexpr int attn_part_floats() { return (HD / 16) * 64 * 4 + 32; }
 
 // index of the KV block that holds key `key`
@@ -219,12 +228,24 @@ __device__ __forceinline__ void attn_prefill_setup(const AttnArgs& p, const Attn
     wave_n_kt = w_row0 < w.R ? (w.pos0 + w_last / p.group) / 64 + 1 : 0;
     wave_first_limit = w.pos0 + w_row0 / p.group;
 }
+// The lower ends under a sliding window (WINDOW instantiations): the causal triangle becomes a band, and a workgroup walks
+// key tiles kt_lo .. n_kt-1 only — kt_lo holds the lowest key of its first row (always a valid one), so about
+// (256 / group + W) / 64 tiles instead of every tile below the diagonal.  Each wave skips the tiles wholly below its own
+// first row's window (wave_kt_lo, the mirror of wave_n_kt), and a tile needs the lower mask only while it reaches below the
+// window of the wave's LAST valid row (wave_last_lo: that row's lowest key; tiles from it on lie inside every row's window).
+struct AttnPrefillWindow { int wm1, kt_lo, wave_kt_lo, wave_last_lo; };
+__device__ __forceinline__ AttnPrefillWindow attn_prefill_window_setup(const AttnArgs& p, const AttnPrefillRows& w) {
+    const int w_row0 = min(w.qt * PF_QROWS + w.wave * 32, w.R - 1), w_last = min(w.qt * PF_QROWS + w.wave * 32 + 31, w.R - 1);
+    return AttnPrefillWindow{p.window - 1, attn_window_kt_lo(w.pos0 + w.qt * PF_QROWS / p.group, p.window),
+                             attn_window_kt_lo(w.pos0 + w_row0 / p.group, p.window), w.pos0 + w_last / p.group - p.window + 1};
+}
 // one 64-key tile from its LDS images: scores, causal mask (qpos: the last key each of the lane's rows may see), online
 // softmax, O^T += V^T · P^T
-template <int HD>
+template <int HD, bool WINDOW = false>
 __device__ __forceinline__ void attn_prefill_tile(int fg, const int (&qpos)[PF_TQ], int kt, int wave_first_limit, float sl2,
                                                   const char* kimg, const char* vimg, const int (&k_off)[HD / 32], const int (&v_off)[HD / 16],
-                                                  const bf16x8 (&qf)[PF_TQ][HD / 32], f32x4 (&o)[PF_TQ][HD / 16], f32x4 (&lacc)[PF_TQ], float (&m_run)[PF_TQ]) {
+                                                  const bf16x8 (&qf)[PF_TQ][HD / 32], f32x4 (&o)[PF_TQ][HD / 16], f32x4 (&lacc)[PF_TQ], float (&m_run)[PF_TQ],
+                                                  const AttnPrefillWindow& win = AttnPrefillWindow{}) {
     constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, TQ = PF_TQ;
     // ---- S^T = K · Q^T : 4 sub-tiles of 16 keys, each K fragment used for both query sub-tiles ----
     f32x4 s[TQ][4];
@@ -243,7 +264,20 @@ __device__ __forceinline__ void attn_prefill_tile(int fg, const int (&qpos)[PF_T
         }
     // lane holds S^T[key = kt*64 + 16t + 4fg + r][q = fq] per sub-tile
     const bool whole = kt * 64 + 63 <= wave_first_limit;      // every row of the wave sees the whole tile
-    if (!whole) {                                             // a tile on the causal diagonal
+    if constexpr (WINDOW) {
+        // ... and the tile reaches below no row's window: else both edges in one compare (attn_in_window)
+        if (!whole || kt * 64 < win.wave_last_lo) {
+#pragma unroll
+            for (int qi = 0; qi < TQ; qi++) {
+                const int lo = qpos[qi] - win.wm1 - kt * 64 - fg * 4;     // lowest key (tile-relative) this row may see
+#pragma unroll
+                for (int t = 0; t < 4; t++)
+#pragma unroll
+                    for (int r = 0; r < 4; r++)
+                        s[qi][t][r] = attn_in_window(t * 16 + r, lo, win.wm1) ? s[qi][t][r] : -INFINITY;
+            }
+        }
+    } else if (!whole) {                                      // a tile on the causal diagonal
 #pragma unroll
         for (int qi = 0; qi < TQ; qi++) {
             const int lim = qpos[qi] - kt * 64 - fg * 4;      // last key (tile-relative) this row may see
@@ -256,18 +290,25 @@ __device__ __forceinline__ void attn_prefill_tile(int fg, const int (&qpos)[PF_T
     }
     // scores stay RAW; the softmax scale (sl2 > 0: checked by the host) is folded into the exponent's fma:
     // p = exp2(s * sl2 - m), m = running max of s * sl2 (finite from the first tile on: key 0 <= limit)
-    float m_new[TQ];
+    // WINDOW: that no longer holds.  The first tile a wave processes belongs to its FIRST row's window; a later row of the
+    // same wave (its window starts up to 31 / group keys higher, possibly in the next tile) can find it entirely masked.  Its
+    // maximum is then still -inf, and exp2(m_run - m_new) and exp2(s * sl2 - m_new) would be exp2(nan).  As in
+    // attn_decode_softmax<.., GUARD> the exponentials take 0 as their reference while the maximum is -inf: alpha =
+    // exp2(-inf) = 0 on a state that is all zeros, every P = exp2(-inf) = 0 — which is also what ones . P^T adds to lacc —
+    // and the row's state stays m = -inf, l = 0, O = 0 until its first visible key (m_run keeps the unguarded maximum).
+    float m_new[TQ], m_ref[TQ];
     bool moved = false;
 #pragma unroll
     for (int qi = 0; qi < TQ; qi++) {
         const float tmax = rows_max(vmax16(s[qi][0], s[qi][1], s[qi][2], s[qi][3]));
         m_new[qi] = vmax2(m_run[qi], tmax * sl2);
         moved |= m_new[qi] != m_run[qi];
+        m_ref[qi] = WINDOW && m_new[qi] == -INFINITY ? 0.f : m_new[qi];
     }
     if (__any(moved)) {                                       // the running maximum moved for some row: rescale
 #pragma unroll
         for (int qi = 0; qi < TQ; qi++) {
-            const float alpha = __builtin_amdgcn_exp2f(m_run[qi] - m_new[qi]);
+            const float alpha = __builtin_amdgcn_exp2f(m_run[qi] - m_ref[qi]);
             lacc[qi] *= alpha;
 #pragma unroll
             for (int d = 0; d < DT; d++) o[qi][d] *= alpha;
@@ -279,7 +320,7 @@ __device__ __forceinline__ void attn_prefill_tile(int fg, const int (&qpos)[PF_T
 #pragma unroll
         for (int t = 0; t < 4; t++)
 #pragma unroll
-            for (int r = 0; r < 4; r++) s[qi][t][r] = __builtin_amdgcn_exp2f(fmaf(s[qi][t][r], sl2, -m_new[qi]));
+            for (int r = 0; r < 4; r++) s[qi][t][r] = __builtin_amdgcn_exp2f(fmaf(s[qi][t][r], sl2, -m_ref[qi]));
     attn_pv_tile<HD, TQ, true>(vimg, v_off, s, o, lacc);
 }
 // normalise (osc / l: osc = 1, or the v_scale of an 8-bit cache) and store
@@ -307,8 +348,12 @@ __device__ __forceinline__ void attn_prefill_store(const AttnArgs& p, const Attn
 // issuing wave's vmcnt + that barrier).  hd 64: four waves per SIMD (two workgroups per CU), so one wave's softmax VALU
 // runs beside another's MFMAs; hd 128: two.
 // ------------------------------------------------------------------------------------------
-template <int HD>
-__global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_kernel(AttnArgs p) {
+// WINDOW (attn_prefill_bf16_win_kernel): the ring starts at the workgroup's kt_lo instead of tile 0 — the same two issues
+// ahead, the same counted waits and slot rotation, over tiles kt_lo .. n_kt-1 — and a wave also skips the tiles below its own
+// rows' windows, after the barrier like the skip at the top (attn_prefill_window_setup).  The body is shared; the
+// unwindowed kernel keeps its name and its code.
+template <int HD, bool WINDOW>
+__device__ __forceinline__ void attn_prefill_bf16_body(const AttnArgs& p) {
     constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, TQ = PF_TQ, QROWS = PF_QROWS;
     constexpr int TILE_BYTES = 64 * HD * 2, PIECES = TILE_BYTES / 1024, PW = 2 * PIECES / 8, NBUF = 3;
     extern __shared__ __attribute__((aligned(16))) char smem[];     // NBUF x [K image | V image]
@@ -381,10 +426,14 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_kerne
     float m_run[TQ] = {-INFINITY, -INFINITY};
     const float sl2 = p.scale * 1.4426950408889634f;     // exp2 domain
 
-    issue(0, 0);
-    if (n_kt > 1) issue(1, 1);
+    AttnPrefillWindow win{};
+    if constexpr (WINDOW) win = attn_prefill_window_setup(p, w);
+    const int kt_lo = WINDOW ? win.kt_lo : 0;            // (< n_kt: the tile of the first row's lowest key)
+
+    issue(kt_lo, 0);
+    if (n_kt > kt_lo + 1) issue(kt_lo + 1, 1);
     int buf = 0;
-    for (int kt = 0; kt < n_kt; kt++) {
+    for (int kt = kt_lo; kt < n_kt; kt++) {
         // my pieces of tile kt have landed (tile kt+1's may stay in flight)
         if (kt + 1 < n_kt) {
             if (PW == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
@@ -398,11 +447,16 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_kerne
         const char* vimg = kimg + TILE_BYTES;
         buf = buf + 1 == NBUF ? 0 : buf + 1;
         if (kt >= wave_n_kt) continue;                   // (wave-uniform) every row of this wave is masked out here
+        if (WINDOW && kt < win.wave_kt_lo) continue;     // (wave-uniform) ... or the tile lies below all of their windows
 
-        attn_prefill_tile<HD>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run);
+        attn_prefill_tile<HD, WINDOW>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run, win);
     }
     attn_prefill_store<HD>(p, w, o, lacc, 1.0f);
 }
+template <int HD>
+__global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_kernel(AttnArgs p) { attn_prefill_bf16_body<HD, false>(p); }
+template <int HD>
+__global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_win_kernel(AttnArgs p) { attn_prefill_bf16_body<HD, true>(p); }
 template <int HD> constexpr int attn_prefill_lds_bytes() { return 3 * 2 * 64 * HD * 2; }
 
 // ------------------------------------------------------------------------------------------
@@ -613,7 +667,7 @@ __device__ __forceinline__ void attn_decode_finish(const AttnArgs& p, char* smem
 // sequence's position, the block id of its first tile) leave at once — with everything inside the struct the compiler
 // fetched the argument block in two dependent pieces first (in-kernel stamps: 2.4 us from entry to the first vector load
 // at B = 1, against 0.4 us in the projection kernels).
-template <int HD, int NW, bool FUSED, bool STAMP = false>
+template <int HD, int NW, bool FUSED, bool STAMP = false, bool WINDOW = false>
 __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                    int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p) {
     constexpr int KS = HD / 32, DT = HD / 16, HALF = HD / 2, CPR = HD / 8, KPI = 64 / CPR, NVL = 64 / KPI;
@@ -638,12 +692,17 @@ __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_ke
     constexpr int NT2_ = HD <= 64 ? 2 : 1;
     const int vw_ = blockIdx.z * NW + wave, nvw_ = NW * gridDim.z;
     const int tok = seq, pos0 = a_seq_pos[seq];              // (decode launches carry one token per sequence, in sequence order)
+    // WINDOW: the wave's first tiles are kt_lo + vw, .., and kt_lo comes from the position, so their block ids cannot leave
+    // with it: the windowed instantiations take the second dependent scalar round trip (position, then block id: about
+    // 0.35 us per launch by the figure above) and read every block id where the round is issued.
     int first_blk[NT2_];
+    if constexpr (!WINDOW) {
 #pragma unroll
-    for (int h = 0; h < NT2_; h++) {
-        const int key = (vw_ + h * nvw_) * 64;
-        const int bi = a_bs_shift >= 0 ? (key >> a_bs_shift) : key / a_Tmax;
-        first_blk[h] = tbl[min(bi, a_tbl_stride - 1)];
+        for (int h = 0; h < NT2_; h++) {
+            const int key = (vw_ + h * nvw_) * 64;
+            const int bi = a_bs_shift >= 0 ? (key >> a_bs_shift) : key / a_Tmax;
+            first_blk[h] = tbl[min(bi, a_tbl_stride - 1)];
+        }
     }
     const int fq = lane & 15, fg = lane >> 4;                // MFMA role: query head qt*16 + fq of the group, k group fg
     const int dch = lane % CPR, ksub = lane / CPR;           // row role: 16-byte chunk dch of key row ksub (+ i*KPI)
@@ -655,7 +714,12 @@ __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_ke
     // key tiles are dealt round-robin over "virtual waves": the NW waves of each of the gridDim.z workgroups of this
     // (sequence, kv head).  gridDim.z > 1 (long contexts in small batches: one workgroup would pull the whole K/V of its
     // head through one CU, ~50 GB/s) leaves partial results for attn_decode_merge_kernel.
-    const int vw = blockIdx.z * NW + wave, nvw = NW * gridDim.z;
+    // WINDOW: the deal starts at kt_lo, the tile of the lowest visible key pos0 - W + 1 — tiles kt_lo + vw, kt_lo + vw + nvw, ..
+    // so it stays dense over the NW x gridDim.z virtual waves and nothing below the window is read.  Only tile kt_lo can
+    // reach below the window; the mask of every tile is the one two-sided compare (attn_in_window).  Every tile dealt
+    // holds a visible key, so the maximum of a round is finite as before.
+    const int kt_lo = WINDOW ? attn_window_kt_lo(pos0, p.window) : 0, wm1 = WINDOW ? p.window - 1 : 0;
+    const int vw = kt_lo + blockIdx.z * NW + wave, nvw = NW * gridDim.z;
     // (FUSED: the new token's q / k / v are fetched and rotated AFTER the first round's K/V loads are issued: below)
     bf16x8 knew[KS];
     bf16x8 vnew8;
@@ -693,7 +757,7 @@ __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_ke
         for (int h = 0; h < NTL; h++) {
             const int kt = kt0 + h * nvw;
             const int bi = kv_block_index(p, kt * 64), krow0 = kt * 64 - bi * p.Tmax;     // the KV block holding this tile
-            const int blk = kt0 == vw ? first_blk[h] : tbl[bi];
+            const int blk = !WINDOW && kt0 == vw ? first_blk[h] : tbl[bi];
             blk_off[h] = (int64_t)blk * p.slot_stride + ((int64_t)kvh * p.Tmax + krow0) * HD;
         }
 #pragma unroll
@@ -812,7 +876,7 @@ __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_ke
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     float v = acc[r] * sl2;
-                    v = (t * 16 + r <= lim) ? v : -INFINITY;
+                    v = (WINDOW ? attn_in_window(t * 16 + r, lim - wm1, wm1) : (t * 16 + r <= lim)) ? v : -INFINITY;
                     acc[r] = v;
                     tmax = fmaxf(tmax, v);
                 }
@@ -892,7 +956,9 @@ __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_ke
 // entirely (limit -1), never stored.  Stream, split-T over the waves, kv_nt policy and the combine are the one-position
 // kernel's; keys are never split over workgroups (gridDim.z == 1: the partial-result buffers hold one tile per pair).
 // ------------------------------------------------------------------------------------------
-template <int HD, int NW>
+// WINDOW: each lane's lower limit is qlim - W + 1 (one two-sided compare: attn_in_window), and the workgroup walks from the
+// kt_lo of its FIRST real row to the n_kt of its last; GUARD already covers a row that finds a round fully masked.
+template <int HD, int NW, bool WINDOW = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_mq_bf16_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                       int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p, int S) {
     constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, KPI = 64 / CPR, NVL = 64 / KPI;
@@ -920,7 +986,8 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_mq_bf16_kernel(const int3
     const int qlim = row_ok ? pos0 + j : -1;                 // last key this lane's row may see
     const int n_kt = (pos0 + (min(qt * 16 + 15, R - 1)) / a_group) / 64 + 1;     // key tiles of the tile's last real row
     char* vimg = smem + wave * TILE_BYTES;
-    const int vw = wave, nvw = NW;
+    const int kt_lo = WINDOW ? attn_window_kt_lo(pos0 + qt * 16 / a_group, p.window) : 0, wm1 = WINDOW ? p.window - 1 : 0;
+    const int vw = kt_lo + wave, nvw = NW;
     bf16x8 qf[KS];
     f32x4 o[DT];
 #pragma unroll
@@ -988,7 +1055,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_mq_bf16_kernel(const int3
 #pragma unroll
                 for (int r4 = 0; r4 < 4; r4++) {
                     float v = acc[r4] * sl2;
-                    v = (t * 16 + r4 <= lim) ? v : -INFINITY;
+                    v = (WINDOW ? attn_in_window(t * 16 + r4, lim - wm1, wm1) : (t * 16 + r4 <= lim)) ? v : -INFINITY;
                     acc[r4] = v;
                     tmax = fmaxf(tmax, v);
                 }
@@ -1016,7 +1083,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_mq_bf16_kernel(const int3
 
 // ------------------------------------------------------------------------------------------
 // fp32 parity kernel: block = (query position, head), 256 threads, T <= 8192
+// WINDOW: keys max(0, T - W) .. T - 1; the score buffer stays indexed by absolute key.
 // ------------------------------------------------------------------------------------------
+template <bool WINDOW = false>
 __global__ __launch_bounds__(256) void attn_f32_kernel(AttnArgs p, int HD) {
     extern __shared__ float sc[];                 // [T_max_needed] scores then probs
     __shared__ float red[8];
@@ -1026,6 +1095,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(AttnArgs p, int HD) {
     const int kvh = head / p.group;
     const int tok = p.seq_tok_start[seq] + s_idx;
     const int T = p.seq_pos[seq] + s_idx + 1;     // keys 0..limit
+    const int j_lo = WINDOW ? max(0, T - p.window) : 0;
     const int32_t* tbl = p.blk_table + (int64_t)seq * p.tbl_stride;
     const float* q = (const float*)p.q + (int64_t)tok * p.q_stride + head * HD;
     auto kv_row = [&](const void* cache, int j) {       // row of key j: [block][kvh][Tmax][HD]
@@ -1034,7 +1104,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(AttnArgs p, int HD) {
     };
 
     float lmax = -INFINITY;
-    for (int j = tid; j < T; j += 256) {
+    for (int j = j_lo + tid; j < T; j += 256) {
         const float* kr = kv_row(p.kcache, j);
         float sum = 0.f;
         for (int d = 0; d < HD; d++) sum = fmaf(q[d], kr[d], sum);
@@ -1047,7 +1117,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(AttnArgs p, int HD) {
     __syncthreads();
     const float mx = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
     float lsum = 0.f;
-    for (int j = tid; j < T; j += 256) {
+    for (int j = j_lo + tid; j < T; j += 256) {
         const float e = expf(sc[j] - mx);
         sc[j] = e;
         lsum += e;
@@ -1057,12 +1127,12 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(AttnArgs p, int HD) {
     if ((tid & 63) == 0) red[4 + (tid >> 6)] = lsum;
     __syncthreads();
     const float tot = red[4] + red[5] + red[6] + red[7];
-    for (int j = tid; j < T; j += 256) sc[j] = sc[j] / tot;      // attention.go:463-466
+    for (int j = j_lo + tid; j < T; j += 256) sc[j] = sc[j] / tot;      // attention.go:463-466
     __syncthreads();
     float* op = (float*)p.out + (int64_t)tok * p.out_stride + head * HD;
     for (int d = tid; d < HD; d += 256) {
         float acc = 0.f;
-        for (int j = 0; j < T; j++) acc = fmaf(sc[j], kv_row(p.vcache, j)[d], acc);
+        for (int j = j_lo; j < T; j++) acc = fmaf(sc[j], kv_row(p.vcache, j)[d], acc);
         op[d] = acc;
     }
 }

@@ -125,7 +125,8 @@ __global__ void rope_kv8_kernel(const float* __restrict__ qkv, int qkv_stride, c
 // ------------------------------------------------------------------------------------------
 // 8-bit decode kernel: attn_decode_bf16_kernel's non-fused form over an 8-bit cache (see the header comment).
 // ------------------------------------------------------------------------------------------
-template <int HD, int NW>
+// WINDOW: attn_decode_bf16_kernel's rule — the deal starts at kt_lo, the tile of key pos0 - W + 1; one two-sided compare.
+template <int HD, int NW, bool WINDOW = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                   int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p,
                                                                   float ksc, float vsc) {
@@ -148,7 +149,8 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
     const int head = kvh * p.group + (row_ok ? qt * 16 + fq : 0);
     char* vimg = smem + wave * TILE_BYTES;
     const int n_kt = pos0 / 64 + 1;
-    const int vw = blockIdx.z * NW + wave, nvw = NW * gridDim.z;
+    const int kt_lo = WINDOW ? attn_window_kt_lo(pos0, p.window) : 0, wm1 = WINDOW ? p.window - 1 : 0;
+    const int vw = kt_lo + blockIdx.z * NW + wave, nvw = NW * gridDim.z;
     f32x4 o[DT];
 #pragma unroll
     for (int d = 0; d < DT; d++) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -218,7 +220,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     float v = acc[r] * sl2;
-                    v = (t * 16 + r <= lim) ? v : -INFINITY;
+                    v = (WINDOW ? attn_in_window(t * 16 + r, lim - wm1, wm1) : (t * 16 + r <= lim)) ? v : -INFINITY;
                     acc[r] = v;
                     tmax = fmaxf(tmax, v);
                 }
@@ -273,7 +275,9 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
 // The kernel is compiled without packed fp32 arithmetic (v_pk_mul / add / fma_f32): the per-function form of hipcc's
 // -Xclang -target-feature -Xclang -packed-fp32-ops.
 // ------------------------------------------------------------------------------------------
-template <int HD, int NW, int TQ>
+// WINDOW: attn_decode_mq_bf16_kernel's rule — per-lane lower limit qlim - W + 1, tiles from the kt_lo of the workgroup's
+// first real row (row qt0 * 16) to the n_kt of its last.
+template <int HD, int NW, int TQ, bool WINDOW = false>
 __global__ __launch_bounds__(NW * 64) NVL_NO_PK_F32 void attn_decode_mq_kv8_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                      int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p, int S,
                                                                      float ksc, float vsc) {
@@ -309,7 +313,8 @@ __global__ __launch_bounds__(NW * 64) NVL_NO_PK_F32 void attn_decode_mq_kv8_kern
     }
     const int n_kt = (pos0 + min(qt0 * 16 + 16 * TQ - 1, R - 1) / a_group) / 64 + 1;     // key tiles of the workgroup's last real row
     char* vimg = smem + wave * TILE_BYTES;
-    const int vw = wave, nvw = NW;
+    const int kt_lo = WINDOW ? attn_window_kt_lo(pos0 + qt0 * 16 / a_group, p.window) : 0, wm1 = WINDOW ? p.window - 1 : 0;
+    const int vw = kt_lo + wave, nvw = NW;
     f32x4 o[TQ][DT];
     float m_run[TQ], l_run[TQ];                              // exp2 domain
 #pragma unroll
@@ -401,7 +406,7 @@ __global__ __launch_bounds__(NW * 64) NVL_NO_PK_F32 void attn_decode_mq_kv8_kern
 #pragma unroll
                     for (int r4 = 0; r4 < 4; r4++) {
                         float v = acc[qi][r4] * sl2;
-                        v = (t * 16 + r4 <= lim) ? v : -INFINITY;
+                        v = (WINDOW ? attn_in_window(t * 16 + r4, lim - wm1, wm1) : (t * 16 + r4 <= lim)) ? v : -INFINITY;
                         acc[qi][r4] = v;
                         tmax[qi] = fmaxf(tmax[qi], v);
                     }
@@ -453,7 +458,9 @@ __global__ __launch_bounds__(NW * 64) NVL_NO_PK_F32 void attn_decode_mq_kv8_kern
 // an 8-bit cache.  A K+V tile pair is 2 * 64 * HD codes = HD / 64 16-byte pieces per thread; they are loaded into
 // registers one tile ahead, converted, and written into ONE bf16 [K image | V image] (two barriers per tile).
 // ------------------------------------------------------------------------------------------
-template <int HD>
+// WINDOW: the register-staged loop starts at the workgroup's kt_lo and each wave skips the tiles below its own rows'
+// windows, as in attn_prefill_bf16_body.
+template <int HD, bool WINDOW = false>
 __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_kv8_kernel(AttnArgs p, float ksc, float vsc) {
     constexpr int KS = HD / 32, DT = HD / 16, CPR8 = HD / 16, TQ = PF_TQ, QROWS = PF_QROWS;
     constexpr int TILE_BYTES = 64 * HD * 2, CH = 64 * CPR8, NCH = 2 * CH / 512;
@@ -512,8 +519,11 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_kv8_kernel
     const char* kimg = smem;
     const char* vimg = smem + TILE_BYTES;
 
-    load_tile(0);
-    for (int kt = 0; kt < n_kt; kt++) {
+    AttnPrefillWindow win{};
+    if constexpr (WINDOW) win = attn_prefill_window_setup(p, w);
+    const int kt_lo = WINDOW ? win.kt_lo : 0;
+    load_tile(kt_lo);
+    for (int kt = kt_lo; kt < n_kt; kt++) {
         __syncthreads();                                 // every wave is done reading the previous tile's images
         // (the row offset of chunk 2 c8 + 1 in the image: kv_img_chunk flips only bit 0 between the pair)
 #pragma unroll
@@ -523,8 +533,8 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_kv8_kernel
         }
         if (kt + 1 < n_kt) load_tile(kt + 1);            // in flight during this tile's MFMAs
         __syncthreads();
-        if (kt >= wave_n_kt) continue;
-        attn_prefill_tile<HD>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run);
+        if (kt >= wave_n_kt || (WINDOW && kt < win.wave_kt_lo)) continue;
+        attn_prefill_tile<HD, WINDOW>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run, win);
     }
     attn_prefill_store<HD>(p, w, o, lacc, vsc);
 }

@@ -426,6 +426,27 @@ inline void load_kv_scales(nvl_model* m, const StSet& st, const std::string& p, 
     m->k_scale[(size_t)l] = ks; m->v_scale[(size_t)l] = vs;
 }
 
+// "sliding_window" of a config.json (HF Mistral): a positive number is the window, null / absent / 0 is none
+static int config_sliding_window(const std::string& path) {
+    const std::string txt = nvl_loader::read_text(path);
+    const JVal raw = nvl_loader::JParser(txt.c_str(), txt.size()).parse();
+    if (raw.kind != JVal::OBJ) throw std::runtime_error("config is not a JSON object");
+    const JVal* v = raw.get("sliding_window");
+    if (!v || v->kind != JVal::NUM) return 0;
+    if (!(v->num >= 0) || v->num > 2147483647.0) throw std::runtime_error("sliding_window out of range");
+    return (int)v->num;
+}
+extern "C" int nvl_load_config_window(const char* path, int* window) {
+    if (!path || !window) return NVL_ERR_INVALID;
+    try {
+        *window = config_sliding_window(path);
+        return NVL_OK;
+    } catch (const std::exception& e) {
+        g_create_err = std::string("nvl_load_config_window: ") + e.what();
+        return NVL_ERR_INVALID;
+    }
+}
+
 extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
     if (!m || !path) return NVL_ERR_INVALID;
     if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_load_safetensors: model already finalized");
@@ -433,6 +454,11 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
     StSet st;
     st.open_path(path);
     st.link_scales();
+    // a checkpoint directory's config.json carries the sliding window (nvl_model_config has no field for it): applied
+    // unless the host set one
+    bool is_dir = false;
+    const std::string cfg_json = std::string(path) + "/config.json";
+    if (!m->window && nvl_loader::exists(path, &is_dir) && is_dir && nvl_loader::exists(cfg_json)) m->window = config_sliding_window(cfg_json);
     const nvl_model_config& c = m->cfg;
     // which WeightMapping (:60-181) — told from the checkpoint's own names
     const bool gpt2 = st.find("wte.weight") != nullptr;
@@ -590,6 +616,7 @@ extern "C" int nvl_load_config_json(const char* path, nvl_model_config* out) {
             if (mt == "gpt2") arch = "gpt2";
             else if (mt == "falcon" || mt == "RefinedWeb" || mt == "RefinedWebModel") arch = "falcon";
             else if (mt == "llama" || mt == "LlamaForCausalLM") arch = "llama";
+            else if (mt == "mistral" || mt == "MistralForCausalLM") arch = "llama";      // ArchMistral (config.go:10): Llama + nvl_load_config_window
             else if (mt == "granitemoe") arch = "granitemoe";
             else if (mt == "granitemoehybrid") arch = "granitehybrid";
             else arch = "gpt2";

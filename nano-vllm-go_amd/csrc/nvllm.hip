@@ -961,6 +961,15 @@ extern "C" int nvl_set_mamba_conv_state(nvl_model* m, int mode) {
     return NVL_OK;
 }
 
+extern "C" int nvl_set_sliding_window(nvl_model* m, int window) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_sliding_window: no model");
+    if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_set_sliding_window: call it before nvl_finalize");
+    if (window < 0) return fail(m, NVL_ERR_INVALID, "nvl_set_sliding_window: negative window");
+    m->window = window;
+    return NVL_OK;
+}
+extern "C" int nvl_get_sliding_window(const nvl_model* m) { return m ? m->window : 0; }
+
 extern "C" int nvl_set_mamba_rollback(nvl_model* m, int mode) {
     if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mamba_rollback: no model");
     if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_set_mamba_rollback: call it before nvl_finalize");
@@ -1508,8 +1517,12 @@ static int mq_kv8_tq(const nvl_model* m, int qt, int n_seqs) {
     if (qt < 2 || m->hd != 64 || g_mq_kv8_tq == 1) return 1;
     return g_mq_kv8_tq == 2 || m->nKV * qt * n_seqs >= 320 ? 2 : 1;
 }
+// Sliding window: waves and the key split follow the keys a workgroup READS, min(context, W + 63) (W keys that may start
+// anywhere in their first tile), not the context: 32 K keys of context under W = 128 are three tiles, not an 8-way split.
+// The window is fixed per model, so the graph keys built from this value stay a function of (batch, context) as before.
 int decode_attn_cfg(const nvl_model* m, int n_seqs, int mq_S = 0) {
-    const int n_kt = m->ctx_hint > 0 ? (m->ctx_hint - 1) / 64 + 1 : 1 << 20;
+    const int ctx = m->window > 0 ? std::min(m->ctx_hint > 0 ? m->ctx_hint : 1 << 26, m->window > (1 << 26) ? 1 << 26 : m->window + 63) : m->ctx_hint;
+    const int n_kt = ctx > 0 ? (ctx - 1) / 64 + 1 : 1 << 20;
     const int per_wave = m->hd == 64 ? 2 : 1;
     const int qt = cdiv(m->group * std::max(mq_S, 1), 16);
     const int wgs = m->nKV * (mq_S && m->kv8 ? cdiv(qt, mq_kv8_tq(m, qt, n_seqs)) : qt) * n_seqs;
@@ -1553,12 +1566,16 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
     a.seq_tok_start = md.seq_tok_start; a.seq_len = md.seq_len; a.seq_pos = md.seq_pos; a.blk_table = md.blk_table; a.tbl_stride = m->blocks_per_seq;
     a.bs_shift = (m->Tmax & (m->Tmax - 1)) == 0 ? __builtin_ctz((unsigned)m->Tmax) : -1;
     a.nH = m->nH; a.nKV = m->nKV; a.group = m->group; a.scale = m->attn_scale;
+    // sliding window: the WINDOW instantiation of the same kernel family, chosen here for every route (no caller knows)
+    const bool win = m->window > 0;
+    a.window = std::min(m->window, 1 << 30);
     KScope ks(m, KC_ATTN, flops, KS_ATTN, abytes);
     if (m->f32) {
         // one score per key a row can see: up to blocks_per_seq blocks of Tmax keys (slab mode: the one block)
         const size_t lds = (size_t)m->Tmax * m->blocks_per_seq * 4;
-        if (lds > 64 * 1024) NVL_LDS_ATTR(attn_f32_kernel, 160 * 1024 - 64);
-        hipLaunchKernelGGL(attn_f32_kernel, dim3(max_len, m->nH, n_seqs), dim3(256), lds, m->stream, a, m->hd);
+        if (lds > 64 * 1024) { if (win) NVL_LDS_ATTR(attn_f32_kernel<true>, 160 * 1024 - 64); else NVL_LDS_ATTR(attn_f32_kernel<false>, 160 * 1024 - 64); }
+        if (win) hipLaunchKernelGGL(attn_f32_kernel<true>, dim3(max_len, m->nH, n_seqs), dim3(256), lds, m->stream, a, m->hd);
+        else hipLaunchKernelGGL(attn_f32_kernel<false>, dim3(max_len, m->nH, n_seqs), dim3(256), lds, m->stream, a, m->hd);
         m->attn_ran[0] = NVL_ATTN_RAN_F32; m->attn_ran[1] = 4; m->attn_ran[2] = 1;
     } else if (mq && kv8 && attention_mq_ok(m, max_len)) {
         const int nw = decode_attn_cfg(m, n_seqs, max_len) & 255;
@@ -1566,20 +1583,23 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         dim3 grid(m->nKV * qw, n_seqs, 1);     // (kv head x group of tq 16-row query tiles, sequence); no key split
         // K/V read once per step by its only workgroup: the one-position launch's policy, with this grid
         a.kv_nt = g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && qw == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
-#define NVL_DEC_MQ8(HDv, TQv) launch_decode_attn<attn_decode_mq_kv8_kernel<HDv, 2, TQv>, attn_decode_mq_kv8_kernel<HDv, 4, TQv>, \
-                                                 attn_decode_mq_kv8_kernel<HDv, 8, TQv>>(m, grid, nw, 64 * HDv * 2, a, max_len, kv8[0], kv8[1])
+#define NVL_DEC_MQ8W(HDv, TQv, Wv) launch_decode_attn<attn_decode_mq_kv8_kernel<HDv, 2, TQv, Wv>, attn_decode_mq_kv8_kernel<HDv, 4, TQv, Wv>, \
+                                                      attn_decode_mq_kv8_kernel<HDv, 8, TQv, Wv>>(m, grid, nw, 64 * HDv * 2, a, max_len, kv8[0], kv8[1])
+#define NVL_DEC_MQ8(HDv, TQv) do { if (win) NVL_DEC_MQ8W(HDv, TQv, true); else NVL_DEC_MQ8W(HDv, TQv, false); } while (0)
         if (m->hd == 64) { if (tq == 2) NVL_DEC_MQ8(64, 2); else NVL_DEC_MQ8(64, 1); }
         else NVL_DEC_MQ8(128, 1);
 #undef NVL_DEC_MQ8
+#undef NVL_DEC_MQ8W
         m->attn_ran[0] = NVL_ATTN_RAN_DECODE_MQ_KV8; m->attn_ran[1] = nw; m->attn_ran[2] = 1;
     } else if (mq && !kv8 && attention_mq_ok(m, max_len)) {
         const int nw = decode_attn_cfg(m, n_seqs, max_len) & 255;
         dim3 grid(m->nKV * cdiv(m->group * max_len, 16), n_seqs, 1);     // (kv head x 16-row query tile, sequence); no key split
         // K/V read once per step by its only workgroup: the one-position launch's policy, with this grid
         a.kv_nt = g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && cdiv(m->group * max_len, 16) == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
-#define NVL_DEC_MQ(HDv, NWv) attn_decode_mq_bf16_kernel<HDv, NWv>
-        if (m->hd == 64) launch_decode_attn<NVL_DEC_MQ(64, 2), NVL_DEC_MQ(64, 4), NVL_DEC_MQ(64, 8)>(m, grid, nw, 64 * 64 * 2, a, max_len);
-        else launch_decode_attn<NVL_DEC_MQ(128, 2), NVL_DEC_MQ(128, 4), NVL_DEC_MQ(128, 8)>(m, grid, nw, 64 * 128 * 2, a, max_len);
+#define NVL_DEC_MQ(HDv, Wv) launch_decode_attn<attn_decode_mq_bf16_kernel<HDv, 2, Wv>, attn_decode_mq_bf16_kernel<HDv, 4, Wv>, \
+                                               attn_decode_mq_bf16_kernel<HDv, 8, Wv>>(m, grid, nw, 64 * HDv * 2, a, max_len)
+        if (m->hd == 64) { if (win) NVL_DEC_MQ(64, true); else NVL_DEC_MQ(64, false); }
+        else { if (win) NVL_DEC_MQ(128, true); else NVL_DEC_MQ(128, false); }
 #undef NVL_DEC_MQ
         m->attn_ran[0] = NVL_ATTN_RAN_DECODE_MQ; m->attn_ran[1] = nw; m->attn_ran[2] = 1;
     } else if (max_len == 1) {
@@ -1595,7 +1615,7 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         // the launch fills the chip — by batch size on Llama-3.2-1B (8 kv heads, 520 keys; profiles/r03_kv_nontemporal.txt):
         // B = 1 +1.7 %, 2 +-0, 4 -2.3 %, 8 -2.4 %, 16 +-0, 24 +2.7 %, 32 +5 %, 48 +1 %; GPT-2 B = 128 (1536 workgroups) +3.2 %
         a.kv_nt = g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && cdiv(m->group, 16) == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
-        a.stamps = (fused_qkv && m->hd == 64) ? next_stamps(m, KS_ATTN, (int)(grid.x * grid.y * grid.z)) : nullptr;
+        a.stamps = (fused_qkv && m->hd == 64 && !win) ? next_stamps(m, KS_ATTN, (int)(grid.x * grid.y * grid.z)) : nullptr;   // (the stamped form has no window)
         if (fused_qkv) {   // RoPE + KV append + attention in one launch, straight from the QKV projection's fp32 output
             a.qkv = m->qkv; a.qkv_stride = m->n_qkv; a.cos_t = m->rope_cos; a.sin_t = m->rope_sin;
         }
@@ -1604,8 +1624,17 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
 #define NVL_DEC_PLAIN(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, false>
 #define NVL_DEC_FUSED(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true>
 #define NVL_DEC_STAMP(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true, true>     /* diagnostic: the in-kernel stamps compiled in */
-        if (kv8) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_KV8, kv8[0], kv8[1]); else NVL_DEC(128, NVL_DEC_KV8, kv8[0], kv8[1]); }
+#define NVL_DEC_KV8_W(HDv, NWv) attn_decode_kv8_kernel<HDv, NWv, true>
+#define NVL_DEC_PLAIN_W(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, false, false, true>
+#define NVL_DEC_FUSED_W(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true, false, true>
+        if (win && kv8) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_KV8_W, kv8[0], kv8[1]); else NVL_DEC(128, NVL_DEC_KV8_W, kv8[0], kv8[1]); }
+        else if (win && fused_qkv) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_FUSED_W); else NVL_DEC(128, NVL_DEC_FUSED_W); }
+        else if (win) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_PLAIN_W); else NVL_DEC(128, NVL_DEC_PLAIN_W); }
+        else if (kv8) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_KV8, kv8[0], kv8[1]); else NVL_DEC(128, NVL_DEC_KV8, kv8[0], kv8[1]); }
         else if (a.stamps) NVL_DEC(64, NVL_DEC_STAMP);
+#undef NVL_DEC_FUSED_W
+#undef NVL_DEC_PLAIN_W
+#undef NVL_DEC_KV8_W
         else if (fused_qkv) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_FUSED); else NVL_DEC(128, NVL_DEC_FUSED); }
         else { if (m->hd == 64) NVL_DEC(64, NVL_DEC_PLAIN); else NVL_DEC(128, NVL_DEC_PLAIN); }
         m->attn_ran[0] = kv8 ? NVL_ATTN_RAN_DECODE_KV8 : (a.stamps ? NVL_ATTN_RAN_DECODE_STAMPED : (fused_qkv ? NVL_ATTN_RAN_DECODE_FUSED : NVL_ATTN_RAN_DECODE));
@@ -1622,7 +1651,11 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         m->attn_ran[0] = kv8 ? NVL_ATTN_RAN_PREFILL_KV8 : NVL_ATTN_RAN_PREFILL; m->attn_ran[1] = 8; m->attn_ran[2] = 1;
         if (kv8) {     // K/V tiles through registers into one bf16 image pair
             if (m->hd == 64) {
-                hipLaunchKernelGGL((attn_prefill_kv8_kernel<64>), grid, dim3(512), attn_prefill_kv8_lds_bytes<64>(), m->stream, a, kv8[0], kv8[1]);
+                if (win) hipLaunchKernelGGL((attn_prefill_kv8_kernel<64, true>), grid, dim3(512), attn_prefill_kv8_lds_bytes<64>(), m->stream, a, kv8[0], kv8[1]);
+                else hipLaunchKernelGGL((attn_prefill_kv8_kernel<64>), grid, dim3(512), attn_prefill_kv8_lds_bytes<64>(), m->stream, a, kv8[0], kv8[1]);
+            } else if (win) {
+                NVL_LDS_ATTR((attn_prefill_kv8_kernel<128, true>), attn_prefill_kv8_lds_bytes<128>());
+                hipLaunchKernelGGL((attn_prefill_kv8_kernel<128, true>), grid, dim3(512), attn_prefill_kv8_lds_bytes<128>(), m->stream, a, kv8[0], kv8[1]);
             } else {
                 NVL_LDS_ATTR(attn_prefill_kv8_kernel<128>, attn_prefill_kv8_lds_bytes<128>());
                 hipLaunchKernelGGL((attn_prefill_kv8_kernel<128>), grid, dim3(512), attn_prefill_kv8_lds_bytes<128>(), m->stream, a, kv8[0], kv8[1]);
@@ -1630,7 +1663,11 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         } else {       // K/V tiles by LDS-DMA; the kernel keeps the sequence's block table in LDS
             if (m->blocks_per_seq > 128) throw std::runtime_error("attention: more than 128 KV blocks per sequence");
             if (m->hd == 64) {
-                hipLaunchKernelGGL((attn_prefill_bf16_kernel<64>), grid, dim3(512), attn_prefill_lds_bytes<64>(), m->stream, a);
+                if (win) hipLaunchKernelGGL((attn_prefill_bf16_win_kernel<64>), grid, dim3(512), attn_prefill_lds_bytes<64>(), m->stream, a);
+                else hipLaunchKernelGGL((attn_prefill_bf16_kernel<64>), grid, dim3(512), attn_prefill_lds_bytes<64>(), m->stream, a);
+            } else if (win) {
+                NVL_LDS_ATTR(attn_prefill_bf16_win_kernel<128>, attn_prefill_lds_bytes<128>());
+                hipLaunchKernelGGL((attn_prefill_bf16_win_kernel<128>), grid, dim3(512), attn_prefill_lds_bytes<128>(), m->stream, a);
             } else {
                 NVL_LDS_ATTR(attn_prefill_bf16_kernel<128>, attn_prefill_lds_bytes<128>());
                 hipLaunchKernelGGL((attn_prefill_bf16_kernel<128>), grid, dim3(512), attn_prefill_lds_bytes<128>(), m->stream, a);
@@ -2701,9 +2738,12 @@ double attn_cost(nvl_model* m, const Meta& hm, int n_seqs, int step = 0) {
     double attn_flops = 0, kv_tok = 0;
     for (int i = 0; i < n_seqs; i++) {
         const double s = hm.seq_len[i], p0 = hm.seq_pos[i] + step;
-        attn_flops += 4.0 * m->hd * m->nH * (s * p0 + s * (s + 1) / 2);
+        // sliding window W: row j sees min(p0 + j + 1, W) keys — the first n1 = clamp(W - p0, 0, s) rows all of theirs — and
+        // the pass reads keys max(0, p0 - W + 1) .. p0 + s - 1
+        const double W = m->window, n1 = std::min(std::max(W - p0, 0.0), s);
+        attn_flops += 4.0 * m->hd * m->nH * (m->window > 0 ? n1 * p0 + n1 * (n1 + 1) / 2 + (s - n1) * W : s * p0 + s * (s + 1) / 2);
         m->ctx_hint = std::max(m->ctx_hint, hm.seq_pos[i] + step + hm.seq_len[i]);
-        kv_tok += p0 + s;
+        kv_tok += m->window > 0 ? std::min(p0 + s, W + s - 1) : p0 + s;
     }
     m->kv_tok = kv_tok;
     return attn_flops;

@@ -632,12 +632,13 @@ extern "C" int nvl_op_attention_kv8(int device, const float* q, const float* k, 
 // split scratch and its zeroed tickets.  attn_out and attn_part start as 0xFF bytes (NaN in bf16 and fp32): a row nobody
 // wrote, or a partial record read before its workgroup wrote it, shows in `out`.  Nothing that could index outside the
 // pools reaches a kernel: every table entry is checked, used or not.
-extern "C" int nvl_op_attention_batch(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
-                                      const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
-                                      int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
-                                      int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt) {
+// window: nvl_set_sliding_window's value for the stand-in model (0 = causal): the WINDOW instantiations of the same families.
+extern "C" int nvl_op_attention_batch_window(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                                             const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                                             int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                                             int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window) {
     const char* who = "nvl_op_attention_batch: ";
-    if (!seq_len || !seq_pos || !k_pool || !v_pool || !block_table || !q || !out || !ran || !part_cnt || nH <= 0 || nKV <= 0 ||
+    if (window < 0 || !seq_len || !seq_pos || !k_pool || !v_pool || !block_table || !q || !out || !ran || !part_cnt || nH <= 0 || nKV <= 0 ||
         nH % nKV || (hd != 64 && hd != 128) || n_seqs <= 0 || n_seqs > 4096 || n_blocks <= 0 || block_size <= 0 || block_size % 64 ||
         tbl_stride <= 0 || max_seq <= 0 || form < NVL_ATTN_OP_PLAIN || form > NVL_ATTN_OP_MQ_KV8 ||
         (precision != NVL_PRECISION_BF16 && precision != NVL_PRECISION_F32) || !(scale >= 0.f) || !std::isfinite(scale))
@@ -677,6 +678,7 @@ extern "C" int nvl_op_attention_batch(int device, int precision, int form, int n
     m.layer_stride = (int64_t)nKV * block_size * hd; m.slot_stride = m.layer_stride;
     m.n_qkv = (nH + 2 * nKV) * hd;
     m.attn_scale = scale != 0.f ? scale : 1.0f / std::sqrt((float)hd);
+    m.window = window;
     m.kv8 = kv8; m.kv_esize = kv8 ? 1 : (int)m.wsize;
     uint8_t *k8 = nullptr, *v8 = nullptr;
     if (kv8) {      // the 8-bit blocks, written by the shared quantizer from the fp32 values
@@ -763,6 +765,14 @@ extern "C" int nvl_op_attention_batch(int device, int precision, int form, int n
     release();
     return NVL_OK;
     OP_CATCH
+}
+
+extern "C" int nvl_op_attention_batch(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                                      const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                                      int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                                      int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt) {
+    return nvl_op_attention_batch_window(device, precision, form, nH, nKV, hd, scale, n_seqs, seq_len, seq_pos, k_pool, v_pool, n_blocks,
+                                         block_size, block_table, tbl_stride, q, rope_base, max_seq, k_scale, v_scale, out, ran, part_cnt, 0);
 }
 
 // The front of an attention layer on a paged batch, stage by stage: the forward pass's own embed() and qkv_front() — attention

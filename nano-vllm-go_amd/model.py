@@ -69,7 +69,7 @@ class HipTransformerModel:
                  act_dtype: str = "auto", expert_dtype: str = "auto", mx_weight_dtype: str = "none",
                  mx_expert_dtype: str = "none", mx_head_dtype: str = "none", gq_weight_dtype: str = "none",
                  gq_group_size: int = 128, gq_expert_dtype: str = "none", mamba_conv_state: str = "per_call",
-                 mamba_rollback: str = "none"):
+                 mamba_rollback: str = "none", sliding_window: int | None = None):
         """tensors=None defers finalize(): upload() each tensor, then call finalize().
         tp_size > 1 makes this the tp_rank-th tensor-parallel shard: pass the FULL tensors, the library keeps
         its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests).
@@ -100,7 +100,9 @@ class HipTransformerModel:
         "per_call" (default) zero-pads every call as the reference does (mamba2.go:181-254).
         mamba_rollback="verify" (a hybrid model): the verify calls and the lookup / speculative loops accept the model — a
         pass reads the Mamba2 states and kept rows without writing them, one launch after the accept decision advances
-        them by the accepted rows (nvl_set_mamba_rollback); "none" (default) keeps refusing those calls."""
+        them by the accepted rows (nvl_set_mamba_rollback); "none" (default) keeps refusing those calls.
+        sliding_window=W (Mistral): every attention layer's query at position i sees keys i - W < j <= i
+        (nvl_set_sliding_window); 0 is causal attention over every key; None (default) takes cfg["sliding_window"], else 0."""
         self.cfg = dict(cfg)
         self.lib = L.lib()
         self.h = C.c_void_p()
@@ -153,6 +155,13 @@ class HipTransformerModel:
                 msg = self.lib.nvl_last_error(self.h)
                 self.close()
                 raise L.NvlError(rc, msg.decode() if msg else "")
+        self.sliding_window = int(cfg.get("sliding_window") or 0) if sliding_window is None else int(sliding_window)
+        if self.sliding_window:
+            rc = self.lib.nvl_set_sliding_window(self.h, self.sliding_window)
+            if rc < 0:
+                msg = self.lib.nvl_last_error(self.h)
+                self.close()
+                raise L.NvlError(rc, msg.decode() if msg else "")
         if kv_scales is not None:
             self.set_kv_scales(*kv_scales)
         self.V = cfg["vocab_size"]
@@ -175,10 +184,12 @@ class HipTransformerModel:
         model_info.json) through nvl_load_config_json, weights through nvl_load_safetensors (mmap -> device)."""
         import os
         c = L.ModelConfigC()
+        window = C.c_int(0)
         for name in ("config.json", "model_info.json"):
             cp = os.path.join(path, name)
             if os.path.exists(cp):
                 L.check(L.lib().nvl_load_config_json(cp.encode(), C.byref(c)))
+                L.check(L.lib().nvl_load_config_window(cp.encode(), C.byref(window)))
                 break
         else:
             raise FileNotFoundError(f"no config.json / model_info.json in {path}")
@@ -193,6 +204,7 @@ class HipTransformerModel:
                     cfg["hybrid_layers"] = ["mamba" if (v[i >> 6] >> (i & 63)) & 1 else "attention" for i in range(c.num_layers)]
                 continue
             cfg[name] = inv[name][v] if name in inv else (bool(v) if name in ("tied_embedding", "use_moe") else v)
+        cfg["sliding_window"] = window.value
         m = cls(cfg, None, **kw)
         L.check(m.lib.nvl_load_safetensors(m.h, path.encode()), m.h)
         m.finalize()

@@ -373,13 +373,14 @@ ATTN_OP_FORMS_KV8 = {"mq_kv8": 4}            # NVL_ATTN_OP_MQ_KV8: "kv8" with th
 
 
 def attention_batch(q, k_pool, v_pool, block_table, seq_len, seq_pos, nH, form="plain", scale=0.0, rope_base=0.0, max_seq=0,
-                    k_scale=1.0, v_scale=1.0, precision="bf16", device=0):   # generic_model.go:276 over block tables
+                    k_scale=1.0, v_scale=1.0, precision="bf16", device=0, window=0):   # generic_model.go:276 over block tables
     """One layer's attention on a batch laid out as the paged front end lays it out, through the model's own dispatch
     (nvl_op_attention_batch): k_pool / v_pool [n_blocks][nKV][block_size][hd], block_table [n_seqs][tbl_stride] (passed
     verbatim), sequence i = seq_len[i] new rows behind seq_pos[i] cached keys.  q [tokens][nH][hd]; form "fused": the fp32
     QKV rows [n_seqs][(nH + 2 nKV) hd] of a decode step (RoPE with rope_base, 0 = none; K / V appended by the kernel);
     "mq" / "mq_kv8": a verify pass over a bf16 / an 8-bit cache (2..8 rows per sequence run the multi-position kernels).
-    max_seq 0 = what the table covers.  -> dict(out [tokens][nH][hd], ran (an ATTN_RAN name), nw, nsplit, part_cnt [32],
+    max_seq 0 = what the table covers.  window = W > 0: sliding-window attention, row at position i sees keys i - W < j <= i
+    (nvl_op_attention_batch_window; 0 = causal).  -> dict(out [tokens][nH][hd], ran (an ATTN_RAN name), nw, nsplit, part_cnt [32],
     and for "fused" k_pool / v_pool after the launch)."""
     k_pool, v_pool = _f(k_pool).copy(), _f(v_pool).copy()
     q = _f(q)
@@ -393,9 +394,10 @@ def attention_batch(q, k_pool, v_pool, block_table, seq_len, seq_pos, nH, form="
         raise ValueError("attention_batch: shapes do not match")
     out = np.empty((tokens, nH, hd), np.float32)
     ran, cnt = np.zeros(3, np.int32), np.zeros(32, np.int32)
-    L.check(L.lib().nvl_op_attention_batch(device, L.PRECISION[precision], {**ATTN_OP_FORMS, **ATTN_OP_FORMS_KV8}[form], nH, nKV, hd, scale, n_seqs, _p(sl),
-                                           _p(sp), _p(k_pool), _p(v_pool), n_blocks, bs, _p(tbl), stride, _p(q), float(rope_base),
-                                           int(max_seq) if max_seq else stride * bs, k_scale, v_scale, _p(out), _p(ran), _p(cnt)))
+    L.check(L.lib().nvl_op_attention_batch_window(device, L.PRECISION[precision], {**ATTN_OP_FORMS, **ATTN_OP_FORMS_KV8}[form], nH, nKV, hd, scale,
+                                                  n_seqs, _p(sl), _p(sp), _p(k_pool), _p(v_pool), n_blocks, bs, _p(tbl), stride, _p(q),
+                                                  float(rope_base), int(max_seq) if max_seq else stride * bs, k_scale, v_scale, _p(out),
+                                                  _p(ran), _p(cnt), int(window)))
     res = dict(out=out, ran=ATTN_RAN[int(ran[0])], nw=int(ran[1]), nsplit=int(ran[2]), part_cnt=cnt)
     if form == "fused":
         res.update(k_pool=k_pool, v_pool=v_pool)

@@ -46,6 +46,7 @@ type Options struct {
 	MXExpertDType  int  // C.NVL_MXE_NONE (0) or C.NVL_MXE_FP4_E2M1 (1): MXFP4 MoE expert weights (needs MXWeightDType 1)
 	MXHeadDType    int  // C.NVL_MXH_NONE (0) or C.NVL_MXH_FP4_E2M1 (1): MXFP4 LM head / tied embedding (needs MXWeightDType 1)
 	ExpertDType    int  // C.NVL_EXPERT_AUTO (0) or C.NVL_EXPERT_FP8_E4M3 (1): 8-bit MoE expert weights (needs WeightDType 1)
+	SlidingWindow  int  // Mistral (ArchMistral): the query at position i sees keys i-W < j <= i; 0 = every key.  NewHipModelRunnerFromDir takes the checkpoint's own when this is 0
 }
 
 // HipModelRunner implements nanovllm.ModelRunner on one MI355X.
@@ -361,6 +362,13 @@ func create(cfg *C.nvl_model_config, o Options) (*HipModelRunner, error) {
 	if o.ExpertDType != 0 { // right after the weight dtype, before the experts are uploaded (nvl_set_expert_dtype)
 		if rc := C.nvl_set_expert_dtype(r.h, C.int(o.ExpertDType)); rc != 0 {
 			err := fmt.Errorf("nvl_set_expert_dtype: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
+			C.nvl_destroy(r.h)
+			return nil, err
+		}
+	}
+	if o.SlidingWindow != 0 { // before nvl_finalize (nvl_set_sliding_window)
+		if rc := C.nvl_set_sliding_window(r.h, C.int(o.SlidingWindow)); rc != 0 {
+			err := fmt.Errorf("nvl_set_sliding_window: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
 			C.nvl_destroy(r.h)
 			return nil, err
 		}
