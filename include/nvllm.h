@@ -28,7 +28,9 @@ extern "C" {
 #endif
 
 #define NVL_ABI_VERSION 3      /* 2: Mamba2 / hybrid layers (config fields, tensor kinds), nvl_stats.evictions, kernel stats;
-                                  3: nvl_get_weight, nvl_get_stamps, nvl_tp_p2p_rearm, debug modes 2 / 4 (additions only) */
+                                  3: nvl_get_weight, nvl_get_stamps, nvl_tp_p2p_rearm, debug modes 2 / 4 (additions only);
+                                     still 3: the tensor kinds NVL_T_Q_NORM_W / NVL_T_K_NORM_W (per-head QK RMSNorm), appended
+                                     behind the older kinds, nvl_qkv_stages_qknorm, nvl_op_attention_batch_qknorm (additions only) */
 
 typedef enum nvl_status {
     NVL_OK = 0,
@@ -136,6 +138,18 @@ typedef enum nvl_tensor_kind {
     NVL_T_MAMBA_DT_BIAS,   /* [heads]                                                                */
     NVL_T_MAMBA_NORM,      /* [EH]                                                                   */
     NVL_T_MAMBA_OUT_PROJ,  /* OUT_IN: [H, EH]  OutProj, MatMul(y, Transpose(OutProj))           mamba2.go:175 */
+    /* Per-head QK RMSNorm (HF Qwen3Attention q_norm / k_norm; OLMoE, Qwen3-MoE): [head_dim] each, per layer, F32 / BF16 / F16,
+     * kept fp32; one vector for all Q heads of the layer and one for all K heads (replicated under tensor parallelism).
+     * A layer that has BOTH normalises every Q head and every K head over the head dimension after the projection (+ bias)
+     * and before RoPE: y[d] = x[d] / sqrt(mean(x^2) + norm_eps) * w[d], in fp32; the cache holds the normed, rotated K; V and
+     * the softmax scale are untouched.  nvl_finalize refuses a layer with exactly one of them (NVL_ERR_STATE); any length but
+     * head_dim is NVL_ERR_INVALID at upload.  Mamba2 layers ignore them.  Every route honours it.  The bf16 decode step
+     * fuses it into the attention kernel at head_dim 128 (NVL_ATTN_RAN_DECODE_FUSED); at head_dim 64 it deliberately does not
+     * (no released QK-norm model has it, and that kernel has no registers to spare): such a layer runs the projection, one
+     * norm + RoPE + append launch and the plain decode kernel (NVL_ATTN_RAN_DECODE).  nvl_get_weight returns them with
+     * in_features = head_dim, out_features = 1. */
+    NVL_T_Q_NORM_W,
+    NVL_T_K_NORM_W,
     NVL_T_COUNT
 } nvl_tensor_kind;
 
@@ -871,6 +885,14 @@ int nvl_op_attention_batch_window(int device, int precision, int form, int nH, i
                                   const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
                                   int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
                                   int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window);
+/* nvl_op_attention_batch_window for a QK-norm layer (NVL_ATTN_OP_FUSED only; other forms consume Q and K that are normed
+ * already): q_norm_w / k_norm_w [hd] and eps as NVL_T_Q_NORM_W / NVL_T_K_NORM_W and norm_eps of a model; both NULL =
+ * nvl_op_attention_batch_window.  hd must be 128 (the model does not fuse at 64). */
+int nvl_op_attention_batch_qknorm(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                                  const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                                  int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                                  int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window,
+                                  const float* q_norm_w, const float* k_norm_w, float eps);
 /* The FRONT of an attention layer as a layer of the model runs it, stage by stage (generic_model.go:295-302 embedWithOffset,
  * :304-318 attention norm, the QKV projection with its bias, rope.go:153-205 on Q and K, Q into the attention operand
  * buffer, K / V into the paged cache): the forward pass's own embed() and qkv_front() on a batch laid out as the paged
@@ -932,6 +954,14 @@ typedef struct nvl_qkv_stages {
     uint8_t *k_codes, *v_codes;
     int32_t* ran;
 } nvl_qkv_stages;
+/* nvl_qkv_stages with the per-head QK RMSNorm weights [hd] behind `ran` (NVL_T_Q_NORM_W / NVL_T_K_NORM_W; eps = norm_eps):
+ * nvl_op_qkv_stages takes either struct and tells them apart by struct_bytes.  Both NULL, or the shorter struct: no QK-norm,
+ * bit for bit; exactly one: NVL_ERR_INVALID.  ran[] keeps its codes: a QK-norm layer's store forms run qk_norm_rope_kv_kernel
+ * in place of rope_kv_kernel / rope_kv8_kernel, its epilogue form the EPI_QKV_NORM instances of the same tile kernels. */
+typedef struct nvl_qkv_stages_qknorm {
+    nvl_qkv_stages s;               /* s.struct_bytes = sizeof(nvl_qkv_stages_qknorm) */
+    const float *q_norm_w, *k_norm_w;
+} nvl_qkv_stages_qknorm;
 int nvl_op_qkv_stages(int device, int precision, const nvl_qkv_stages* io);
 /* 8-bit weights: tensor.MatMul (tensor.go:62-88) with b = w [K][N] quantized by the model's upload quantizer
  * (NVL_W_FP8_E4M3), c [M][N] = bf16(a) · W~ through the model's own GEMM dispatch (M selects the decode or the tile form).

@@ -21,7 +21,11 @@ SLOTS = [
     "mamba_in_proj", "mamba_conv_w", "mamba_conv_b", "mamba_a_log", "mamba_d", "mamba_dt_bias", "mamba_norm", "mamba_out_proj",
 ]
 SLOT_ID = {n: i for i, n in enumerate(SLOTS)}
-ONE_D = {"final_norm_w", "final_norm_b", "attn_norm_w", "attn_norm_b", "ffn_norm_w", "ffn_norm_b",
+# per-head QK RMSNorm (NVL_T_Q_NORM_W / NVL_T_K_NORM_W): [head_dim] each, appended behind the older kinds, directly before NVL_T_COUNT
+QK_NORM_SLOTS = ["q_norm_w", "k_norm_w"]
+SLOT_ID.update({n: len(SLOTS) + i for i, n in enumerate(QK_NORM_SLOTS)})
+T_COUNT = len(SLOTS) + len(QK_NORM_SLOTS)
+ONE_D = {"q_norm_w", "k_norm_w", "final_norm_w", "final_norm_b", "attn_norm_w", "attn_norm_b", "ffn_norm_w", "ffn_norm_b",
          "bq", "bk", "bv", "bo", "b1", "b2",
          "mamba_conv_w", "mamba_conv_b", "mamba_a_log", "mamba_d", "mamba_dt_bias", "mamba_norm"}
 OUT_IN_SLOTS = {"mamba_in_proj", "mamba_out_proj"}      # kept in the checkpoint's [out, in] layout by the reference's loader
@@ -123,6 +127,10 @@ class QkvStagesC(C.Structure):        # nvl_qkv_stages
                 [(n, C.c_void_p) for n in ("seq_len", "seq_pos", "block_table", "tokens", "tok_pos", "norm_w", "norm_b", "w_qkv",
                                            "b_qkv", "emb", "pos_emb", "x", "op", "qkv", "q", "k_pool", "v_pool", "k_codes",
                                            "v_codes", "ran")])
+
+
+class QkvStagesQkNormC(C.Structure):  # nvl_qkv_stages_qknorm
+    _fields_ = [("s", QkvStagesC), ("q_norm_w", C.c_void_p), ("k_norm_w", C.c_void_p)]
 
 
 def declared_symbols() -> list[str]:
@@ -254,6 +262,7 @@ def lib():
     L.nvl_op_attention_batch.argtypes = ([C.c_int] * 6 + [f32, C.c_int, vp, vp, vp, vp, C.c_int, C.c_int, vp, C.c_int, vp, C.c_double,
                                           C.c_int, f32, f32, vp, vp, vp])
     L.nvl_op_attention_batch_window.argtypes = L.nvl_op_attention_batch.argtypes + [C.c_int]
+    L.nvl_op_attention_batch_qknorm.argtypes = L.nvl_op_attention_batch_window.argtypes + [vp, vp, f32]
     L.nvl_op_mamba_mixer.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp] + [C.c_int] * 6 + [vp] * 8 + [C.c_int] + [vp] * 4
     L.nvl_op_mamba_verify.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp] + [C.c_int] * 6 + [vp] * 8 + [C.c_int] + [vp] * 5
     sp = C.POINTER(SamplingParamsC)

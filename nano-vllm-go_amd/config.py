@@ -46,6 +46,8 @@ class ModelConfig:
     mamba_n_groups: int = 0
     mamba_conv_kernel: int = 0
     sliding_window: int = 0           # HF Mistral "sliding_window": row i sees keys i - W < j <= i; 0 / null = none
+    qk_norm: bool = False             # synthetic models only (synth.make_weights): per-head QK RMSNorm weights, as Qwen3 has them
+                                      # (a checkpoint turns it on by carrying q_norm / k_norm tensors, not through a flag)
 
     @property
     def mamba_layer_mask(self):
@@ -107,7 +109,8 @@ def _infer_config_from_json(raw: dict) -> ModelConfig:    # generic_loader.go:97
         return new_gpt2_config()
     if mt in ("falcon", "RefinedWeb", "RefinedWebModel"):
         return new_falcon_config("7b")
-    if mt in ("llama", "LlamaForCausalLM", "mistral", "MistralForCausalLM"):     # ArchMistral: Llama + sliding_window
+    if mt in ("llama", "LlamaForCausalLM", "mistral", "MistralForCausalLM",     # ArchMistral: Llama + sliding_window
+              "qwen3", "Qwen3ForCausalLM"):                                      # Qwen3: Llama + per-head QK RMSNorm tensors
         return new_llama_config("7b")
     if mt == "granitemoe":
         return new_granite_moe_config("350m")

@@ -57,6 +57,11 @@ struct AttnArgs {
     // sliding window (the WINDOW instantiations only; W >= 1): the row at position i sees keys i - W < j <= i.  Keys
     // below a row's window stay in the cache and are not read: every kernel starts at the tile of its first row's lowest key.
     int window;
+    // fused decode with the per-head QK RMSNorm (the QKNORM instantiations only; qknorm.h): the layer's q_norm / k_norm
+    // weights [HD] and eps.  Behind everything else: no older field moves.
+    const float* q_norm_w;
+    const float* k_norm_w;
+    float qk_norm_eps;
 };
 // The two-sided mask of a windowed kernel as ONE unsigned compare: with lo = limit - (W - 1) the lowest visible key,
 // lo <= key <= limit  <=>  (unsigned)(key - lo) <= W - 1 (keys, limit and lo relative to the same origin; the host keeps
@@ -521,6 +526,31 @@ __device__ __forceinline__ void rope_math8(const RopeRaw& r, bool rot, bf16x8& l
     }
 }
 
+// QK RMSNorm of the fused decode prologue at head_dim 128 (qknorm.h): the lanes fg = 0..3 of a column fq hold one head row
+// between them, 32 values each (two RopeRaw: d = ks*32 + fg*8 .. +7 and the same + 64), so the head's sum of squares is
+// the local sum and two cross-lane steps over fg (lane ^ 16, lane ^ 32); every lane is active here.  Scales r[] in
+// place by (1 / rms) * w; rope_math8 rotates it afterwards.
+template <int HD>
+__device__ __forceinline__ void qk_norm_raw(RopeRaw (&r)[HD / 64], const float* w, float eps, int fg) {
+    float ss = 0.f;
+#pragma unroll
+    for (int ks = 0; ks < HD / 64; ks++)
+#pragma unroll
+        for (int e = 0; e < 4; e++) {
+            ss = __builtin_fmaf(r[ks].a0[e], r[ks].a0[e], ss); ss = __builtin_fmaf(r[ks].a1[e], r[ks].a1[e], ss);
+            ss = __builtin_fmaf(r[ks].b0[e], r[ks].b0[e], ss); ss = __builtin_fmaf(r[ks].b1[e], r[ks].b1[e], ss);
+        }
+    ss += __shfl_xor(ss, 16);
+    ss += __shfl_xor(ss, 32);
+    const float rs = qk_norm_scale<HD>(ss, eps);
+#pragma unroll
+    for (int ks = 0; ks < HD / 64; ks++) {
+        const float* wd = w + ks * 32 + fg * 8;
+        r[ks].a0 = (r[ks].a0 * rs) * *(const f32x4*)wd;              r[ks].a1 = (r[ks].a1 * rs) * *(const f32x4*)(wd + 4);
+        r[ks].b0 = (r[ks].b0 * rs) * *(const f32x4*)(wd + HD / 2);   r[ks].b1 = (r[ks].b1 * rs) * *(const f32x4*)(wd + HD / 2 + 4);
+    }
+}
+
 // The softmax step of a decode round, from the round's masked, scaled scores s (exp2 domain) and their lane maximum tmax:
 // the new running maximum and denominator, s -> P^T, and the rescale of O^T.
 // GUARD (the multi-position kernel): a row may have seen no key at all so far — its mask limit lies below the tiles this
@@ -667,7 +697,10 @@ __device__ __forceinline__ void attn_decode_finish(const AttnArgs& p, char* smem
 // sequence's position, the block id of its first tile) leave at once — with everything inside the struct the compiler
 // fetched the argument block in two dependent pieces first (in-kernel stamps: 2.4 us from entry to the first vector load
 // at B = 1, against 0.4 us in the projection kernels).
-template <int HD, int NW, bool FUSED, bool STAMP = false, bool WINDOW = false>
+// QKNORM (FUSED, head_dim 128 only): the new token's Q rows and K row pass through the per-head QK RMSNorm (qk_norm_raw)
+// before the rotation, so the K used for the step's own score and the K appended to the cache are the normed one.  hd 64 is
+// deliberately not instantiated: that kernel sits at 239 of the 256 registers two waves per SIMD leave it.
+template <int HD, int NW, bool FUSED, bool STAMP = false, bool WINDOW = false, bool QKNORM = false>
 __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                    int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p) {
     constexpr int KS = HD / 32, DT = HD / 16, HALF = HD / 2, CPR = HD / 8, KPI = 64 / CPR, NVL = 64 / KPI;
@@ -815,10 +848,28 @@ __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_ke
         const float* row = p.qkv + (int64_t)tok * p.qkv_stride;
         const float* cs2 = p.cos_t ? p.cos_t + (int64_t)pos0 * HD : nullptr;
         const float* sn = p.sin_t ? p.sin_t + (int64_t)pos0 * HD : nullptr;
+        if constexpr (QKNORM) {
+            static_assert(HD == 128 && !STAMP, "QK-norm is fused into the head_dim 128 decode kernel only");
+            RopeRaw nq[KS / 2], nk[KS / 2];
 #pragma unroll
-        for (int ks = 0; ks < KS / 2; ks++) {
-            rope_pair8(row + head * HD, cs2, sn, ks * 32 + fg * 8, HALF, qf[ks], qf[ks + KS / 2]);
-            rope_pair8(row + (p.nH + kvh) * HD, cs2, sn, ks * 32 + fg * 8, HALF, knew[ks], knew[ks + KS / 2]);
+            for (int ks = 0; ks < KS / 2; ks++) {
+                rope_load8(row + head * HD, cs2, sn, ks * 32 + fg * 8, HALF, nq[ks]);
+                rope_load8(row + (p.nH + kvh) * HD, nullptr, nullptr, ks * 32 + fg * 8, HALF, nk[ks]);     // (cos / sin: the query's copy)
+            }
+            qk_norm_raw<HD>(nq, p.q_norm_w, p.qk_norm_eps, fg);
+            qk_norm_raw<HD>(nk, p.k_norm_w, p.qk_norm_eps, fg);
+#pragma unroll
+            for (int ks = 0; ks < KS / 2; ks++) {
+                nk[ks].c0 = nq[ks].c0; nk[ks].c1 = nq[ks].c1; nk[ks].s0 = nq[ks].s0; nk[ks].s1 = nq[ks].s1;
+                rope_math8(nq[ks], cs2 != nullptr, qf[ks], qf[ks + KS / 2]);
+                rope_math8(nk[ks], cs2 != nullptr, knew[ks], knew[ks + KS / 2]);
+            }
+        } else {
+#pragma unroll
+            for (int ks = 0; ks < KS / 2; ks++) {
+                rope_pair8(row + head * HD, cs2, sn, ks * 32 + fg * 8, HALF, qf[ks], qf[ks + KS / 2]);
+                rope_pair8(row + (p.nH + kvh) * HD, cs2, sn, ks * 32 + fg * 8, HALF, knew[ks], knew[ks + KS / 2]);
+            }
         }
         const float* vrow = row + (p.nH + p.nKV + kvh) * HD + dch * 8;
         const f32x4 w0 = *(const f32x4*)vrow, w1 = *(const f32x4*)(vrow + 4);

@@ -69,6 +69,11 @@ __device__ __forceinline__ void kv_locate(const int32_t* __restrict__ blk_table,
     row = pos - bi * bs;
 }
 
+// per-head QK RMSNorm (qknorm.h): 1 / rms of a head from its sum of squares — the one expression its three appliers share
+// (division and square root are correctly rounded in this build: no fast-math)
+template <int HD>
+__device__ __forceinline__ float qk_norm_scale(float sumsq, float eps) { return 1.0f / sqrtf(sumsq * (1.0f / HD) + eps); }
+
 __device__ __forceinline__ float gelu_tanh_f(float x) {
     // tensor.go:181-190: 0.5 x (1 + tanh(sqrt(2/pi) (x + 0.044715 x^3))), the tanh in float64 there.
     // tanh(u) = 1 - 2 / (exp(2u) + 1) on the hardware exp2 / rcp (both ~1 ulp): ABSOLUTE error ~1e-7, and only the absolute

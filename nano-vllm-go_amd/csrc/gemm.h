@@ -41,7 +41,10 @@ enum GemmEpi {
     EPI_QKV = 4,     // fused QKV projection epilogue (head_dim 64 / 128): bias, RoPE on Q and K (rope.go:153-205),
                      // Q -> q buffer, K and V -> their KV slabs [pos][hd]  (replaces the fp32 qkv
                      // round trip + rope_kv_kernel in prefill; Concatenate tensor.go:283-321)
+    EPI_QKV_NORM = 5 // EPI_QKV with the per-head QK RMSNorm (qknorm.h) between the bias and RoPE: a variant of its own, so
+                     // that the EPI_QKV instances stay what they were (bf16 weights, and W~ of a quantized one: wq.h)
 };
+constexpr bool epi_is_qkv(int epi) { return epi == EPI_QKV || epi == EPI_QKV_NORM; }
 
 struct QkvEpi {             // EPI_QKV only
     const int32_t* tok_pos;
@@ -113,6 +116,10 @@ struct GemmArgs {
     // projection's K reduction the weighted combine itself (moe.go:105-120) — no sort, no plan, no combine launch.
     const float* moe_gate;
     int moe_E, moe_I;
+    // EPI_QKV_NORM: the layer's q_norm / k_norm weights [hd] and eps (behind everything else: no older field moves)
+    const float* q_norm_w;
+    const float* k_norm_w;
+    float qk_norm_eps;
 };
 // does any row of the batch (M <= 64: one per lane) route to expert e?  Call with all 64 lanes active.
 __device__ __forceinline__ bool moe_expert_live(const GemmArgs& p, int e) {
@@ -204,14 +211,34 @@ __device__ __forceinline__ void epilogue_swiglu4(const GemmArgs& p, int m, int f
 
 // EPI_QKV: one wave sub-tile of TH*16 columns = one head (TH = 4: hd 64, TH = 8: hd 128).  The lane holds, for
 // token m, d = 16j + 4fg + r (j = 0..TH-1): the RoPE partner d + hd/2 is tile j + TH/2 of the SAME lane.
-template <int TH>
+// QKN (EPI_QKV_NORM): the QK RMSNorm of qknorm.h between the bias and the rotation.  The lane holds a quarter of token m's
+// head; the other three quarters sit in the lanes fg ^ 1, fg ^ 2 (lane ^ 16, lane ^ 32) of the same column fr, so the sum of
+// squares is the local sum and two cross-lane steps.  Rows m >= p.M stay in the exchange — their partners are lanes of the
+// same row m, so nothing of theirs reaches a stored row — and leave behind it.
+template <int TH, bool QKN = false>
 __device__ __forceinline__ void epilogue_qkv_head(const GemmArgs& p, int m, int head, int fg, f32x4 (&t)[TH]) {
     constexpr int HD = TH * 16;
-    if (m >= p.M) return;
+    if constexpr (!QKN) { if (m >= p.M) return; }
     const QkvEpi& q = p.qkv;
     if (p.bias) {
 #pragma unroll
         for (int j = 0; j < TH; j++) t[j] += *(const f32x4*)(p.bias + head * HD + 16 * j + 4 * fg);
+    }
+    if constexpr (QKN) {
+        if (head < q.nH + q.nKV) {                      // (wave-uniform: a wave's columns are one head)
+            float ss = 0.f;
+#pragma unroll
+            for (int j = 0; j < TH; j++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) ss = __builtin_fmaf(t[j][r], t[j][r], ss);
+            ss += __shfl_xor(ss, 16);
+            ss += __shfl_xor(ss, 32);
+            const float rs = qk_norm_scale<HD>(ss, p.qk_norm_eps);
+            const float* wn = (head < q.nH ? p.q_norm_w : p.k_norm_w) + 4 * fg;
+#pragma unroll
+            for (int j = 0; j < TH; j++) t[j] = (t[j] * rs) * *(const f32x4*)(wn + 16 * j);
+        }
+        if (m >= p.M) return;
     }
     const int pos = q.tok_pos[m];
     if (head < q.nH + q.nKV && q.cos_t) {
@@ -410,10 +437,10 @@ void gemm_bf16_kernel(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < TM; i++) {
         const int m = m0 + wm * (TM * 16) + i * 16 + fr;
-        if (EPI == EPI_QKV) {
+        if (epi_is_qkv(EPI)) {
             // the wave's column tile is exactly one head: TN = 4 <-> head_dim 64, TN = 8 <-> head_dim 128
             const int head = (n0 + wn * (TN * 16)) / (TN * 16);
-            if (head * (TN * 16) < p.N) epilogue_qkv_head<TN>(p, m, head, fg, acc[i]);
+            if (head * (TN * 16) < p.N) epilogue_qkv_head<TN, EPI == EPI_QKV_NORM>(p, m, head, fg, acc[i]);
         } else if (EPI == EPI_SWIGLU) {
 #pragma unroll
             for (int j = 0; j < TN; j += 2) {
@@ -574,9 +601,9 @@ __global__ __launch_bounds__(512, 1) void gemm_bf16_pp_kernel(GemmArgs p) {
 #pragma unroll
     for (int i = 0; i < TM; i++) {
         const int m = m0 + wm * (TM * 16) + i * 16 + fr;
-        if (EPI == EPI_QKV) {
+        if (epi_is_qkv(EPI)) {
             const int head = (n0 + wn * (TN * 16)) / (TN * 16);      // the wave's column block is exactly one head
-            if (head * (TN * 16) < p.N) epilogue_qkv_head<TN>(p, m, head, fg, acc[i]);
+            if (head * (TN * 16) < p.N) epilogue_qkv_head<TN, EPI == EPI_QKV_NORM>(p, m, head, fg, acc[i]);
         } else if (EPI == EPI_SWIGLU) {
 #pragma unroll
             for (int j = 0; j < TN; j += 2) {
@@ -1856,7 +1883,7 @@ static inline bool launch_gemm_skinny_wide(hipStream_t st, const GemmArgs& a, co
 }
 template <int EPI, typename OutT, int WF>
 static inline bool launch_gemm_skinny_bf16(hipStream_t st, const GemmArgs& a0, const float* ws, int gsh) {
-    if (EPI == EPI_QKV) return false;               // prefill-only epilogue (a decode workgroup owns 16 columns, not a head)
+    if (epi_is_qkv(EPI)) return false;              // prefill-only epilogue (a decode workgroup owns 16 columns, not a head)
     if (skinny_rows(a0) > 64 || a0.a_rows || a0.seg || a0.tile_map) return false;
     GemmArgs a = a0;
     a.x_mask = (g_x_mask && a0.M % 16 != 0) ? 1 : 0;     // padded rows of the last 16-row activation tile are not fetched
@@ -1925,7 +1952,7 @@ static inline void launch_gemm_bf16(hipStream_t st, const GemmArgs& a) {
     t_gemm_ran = NVL_GEMM_RAN_NONE;
     if (a.tile_map) { launch_gemm_grouped<EPI, OutT>(st, a, a.M); return; }   // a.M carries the m-tile bound
     if (launch_gemm_skinny_bf16<EPI, OutT>(st, a)) { t_gemm_ran = NVL_GEMM_RAN_DECODE; return; }
-    if constexpr (EPI != EPI_QKV) {
+    if constexpr (!epi_is_qkv(EPI)) {
         // 64 < M <= g_chunk_max_m (large decode batches): the tile kernels would launch only N/128 * M/128 workgroups, far
         // too few to stream the weights at HBM rate.  Run the decode form over ceil(M/64) groups of 64 activation rows
         // in one launch instead (GemmArgs::m_passes): the groups of a weight block run side by side on one XCD, so the
@@ -1940,7 +1967,7 @@ static inline void launch_gemm_bf16(hipStream_t st, const GemmArgs& a) {
         }
     }
     if (a.rs_in || a.rs_out) throw std::runtime_error("gemm: a deferred-RMSNorm projection did not fit the decode kernels");
-    if constexpr (EPI == EPI_QKV) {
+    if constexpr (epi_is_qkv(EPI)) {
         if (a.qkv.hd == 128) {     // a wave must own a whole 128-column head: 256x256 tile as 4x2 waves of 64x128
             const int t3 = cdiv(a.M, 256) * cdiv(a.N, 256);
             if (g_force_tile == 0 && t3 >= 192 && cu_fill(t3, 1) >= 0.74 && a.K >= 160 && !a.seg && !a.a_rows) {

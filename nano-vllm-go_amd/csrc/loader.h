@@ -540,6 +540,9 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
             up2d_proj(m, NVL_T_WK, l, st, p + ".self_attn.k_proj");
             up2d_proj(m, NVL_T_WV, l, st, p + ".self_attn.v_proj");
             up2d_proj(m, NVL_T_WO, l, st, p + ".self_attn.o_proj");
+            // per-head QK RMSNorm (Qwen3, OLMoE): both or neither — nvl_finalize refuses a lone one
+            if (const StTensor* t = st.find(p + ".self_attn.q_norm.weight")) up1d(m, NVL_T_Q_NORM_W, l, *t);
+            if (const StTensor* t = st.find(p + ".self_attn.k_norm.weight")) up1d(m, NVL_T_K_NORM_W, l, *t);
             load_kv_scales(m, st, p, l);
             if (c.use_moe) {                                                   // loadMoE (:566-592)
                 up2d(m, NVL_T_ROUTER, l, st.need(p + ".block_sparse_moe.router.layer.weight"), OI);   // [E, H]: "always transpose"
@@ -617,6 +620,7 @@ extern "C" int nvl_load_config_json(const char* path, nvl_model_config* out) {
             else if (mt == "falcon" || mt == "RefinedWeb" || mt == "RefinedWebModel") arch = "falcon";
             else if (mt == "llama" || mt == "LlamaForCausalLM") arch = "llama";
             else if (mt == "mistral" || mt == "MistralForCausalLM") arch = "llama";      // ArchMistral (config.go:10): Llama + nvl_load_config_window
+            else if (mt == "qwen3" || mt == "Qwen3ForCausalLM") arch = "llama";          // Qwen3: Llama + the q_norm / k_norm tensors of its checkpoint
             else if (mt == "granitemoe") arch = "granitemoe";
             else if (mt == "granitemoehybrid") arch = "granitehybrid";
             else arch = "gpt2";

@@ -12,6 +12,7 @@
 #include "../../include/nvllm.h"
 #include "attn.h"
 #include "kv8.h"
+#include "qknorm.h"
 #include "common.h"
 #include "elem.h"
 #include "sample.h"
@@ -49,6 +50,8 @@ struct LayerW {
     void* moe_out_q = nullptr; void* qs_moe_out = nullptr;
     bool mamba = false;                  // a Mamba2 block (attention tensors absent); index among the Mamba2 layers
     int mamba_idx = -1;
+    // per-head QK RMSNorm (qknorm.h): on when the layer has both weights (nvl_finalize refuses exactly one)
+    bool qk_norm() const { return t[NVL_T_Q_NORM_W].present() && t[NVL_T_K_NORM_W].present(); }
 };
 
 enum KClass { KC_GEMM = 0, KC_ATTN = 1, KC_OTHER = 2 };
@@ -186,6 +189,8 @@ struct nvl_model {
     int pending_from = 0;         // which residual projection left the pending slices (0 = O projection, 1 = FFN-down)
     int dense_ran[NVL_DENSE_RAN_INTS] = {0};   // what the residual projections and norms of the last layer tail ran (nvllm.h NVL_DENSE_RAN_*; resid_gemm / launch_norm write it, nvl_op_dense_stages reports it)
     int gemm_ran = 0, norm_ran = 0;   // the last bf16 projection's instance (NVL_GEMM_RAN_*, gemm()) and the last norm launch's kernel (NVL_NORM_RAN_*, launch_norm)
+    const float* qkn_q = nullptr;              // the QK-norm weights of the layer whose front ran last, or NULL (qkv_front sets them,
+    const float* qkn_k = nullptr;              // the fused decode attention launch behind it reads them)
     int front_ran[NVL_QKV_RAN_INTS] = {0};     // what the last layer front ran (nvllm.h NVL_QKV_RAN_*; embed / qkv_front write it, nvl_op_qkv_stages reports it)
     const int32_t* pending_slot_of = nullptr; const float* pending_gate_w = nullptr;   // MoE combine folded into the next norm
     // per-call metadata (one pinned host block mirrored on the device)

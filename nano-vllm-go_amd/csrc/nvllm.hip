@@ -113,7 +113,7 @@ bool is_1d(int kind) {
         case NVL_T_FFN_NORM_W: case NVL_T_FFN_NORM_B: case NVL_T_BQ: case NVL_T_BK: case NVL_T_BV:
         case NVL_T_BO: case NVL_T_B1: case NVL_T_B2:
         case NVL_T_MAMBA_CONV_W: case NVL_T_MAMBA_CONV_B: case NVL_T_MAMBA_A_LOG: case NVL_T_MAMBA_D: case NVL_T_MAMBA_DT_BIAS:
-        case NVL_T_MAMBA_NORM: return true;
+        case NVL_T_MAMBA_NORM: case NVL_T_Q_NORM_W: case NVL_T_K_NORM_W: return true;
         default: return false;
     }
 }
@@ -178,6 +178,7 @@ void gemm_q(nvl_model* m, int epi, bool out_f32, const GemmArgs& a, const nvl_mo
         case EPI_SWIGLU: NVL_GQ(EPI_SWIGLU, bf16_t); break;
         case EPI_GELU:   NVL_GQ(EPI_GELU, bf16_t); break;
         case EPI_QKV:    NVL_GQ(EPI_QKV, bf16_t); break;
+        case EPI_QKV_NORM: NVL_GQ(EPI_QKV_NORM, bf16_t); break;
         default: throw std::runtime_error("gemm: bad epilogue");
     }
 #undef NVL_GQ
@@ -217,6 +218,7 @@ void gemm(nvl_model* m, int epi, bool out_f32, GemmArgs a, double flops = -1.0) 
             case EPI_SWIGLU: launch_gemm_bf16<EPI_SWIGLU, bf16_t>(st, a); break;
             case EPI_GELU:   launch_gemm_bf16<EPI_GELU, bf16_t>(st, a); break;
             case EPI_QKV:    launch_gemm_bf16<EPI_QKV, bf16_t>(st, a); break;
+            case EPI_QKV_NORM: launch_gemm_bf16<EPI_QKV_NORM, bf16_t>(st, a); break;
             default: throw std::runtime_error("gemm: bad epilogue");
         }
         m->gemm_ran = t_gemm_ran;
@@ -598,7 +600,8 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
             else if (kind == NVL_T_MAMBA_CONV_B) want = m->mConv;
             else if (kind == NVL_T_MAMBA_A_LOG || kind == NVL_T_MAMBA_D || kind == NVL_T_MAMBA_DT_BIAS) want = m->m_nh;
             else if (kind == NVL_T_MAMBA_NORM) want = m->mEH;
-            if (kind >= NVL_T_MAMBA_IN_PROJ && !m->n_mamba) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor: the model has no Mamba2 layers");
+            else if (kind == NVL_T_Q_NORM_W || kind == NVL_T_K_NORM_W) want = m->hd;     // per head dimension: replicated under tensor parallelism
+            if (kind >= NVL_T_MAMBA_IN_PROJ && kind <= NVL_T_MAMBA_OUT_PROJ && !m->n_mamba) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor: the model has no Mamba2 layers");
             if (rows <= 0 || n != want) {
                 snprintf(buf, sizeof buf, "1-D tensor kind %d has %lld elements, the model needs %lld", kind, (long long)n,
                          (long long)want);
@@ -639,7 +642,7 @@ extern "C" int nvl_upload_tensor(nvl_model* m, int kind, int layer, const void* 
         upload_2d_whole(m, t, kind, data, dtype, rows, cols, false);     // (quantized: scales per (expert, output row))
         return NVL_OK;
     }
-    if (kind >= NVL_T_MAMBA_IN_PROJ && !m->n_mamba) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor: the model has no Mamba2 layers");
+    if (kind >= NVL_T_MAMBA_IN_PROJ && kind <= NVL_T_MAMBA_OUT_PROJ && !m->n_mamba) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor: the model has no Mamba2 layers");
     const int64_t SN = full_out(m, kind), SK = full_in(m, kind);
     if (SN < 0) return fail(m, NVL_ERR_INVALID, "nvl_upload_tensor: kind is not a 2-D weight");
     const int64_t got_in = layout == NVL_LAYOUT_IN_OUT ? rows : cols;
@@ -1005,6 +1008,8 @@ extern "C" int nvl_finalize(nvl_model* m) {
             continue;
         }
         need(l.t[NVL_T_WQ].present() && l.t[NVL_T_WO].present(), "attention Q/O projection");
+        if (l.t[NVL_T_Q_NORM_W].present() != l.t[NVL_T_K_NORM_W].present())
+            return fail(m, NVL_ERR_STATE, "nvl_finalize: a layer has only one of NVL_T_Q_NORM_W / NVL_T_K_NORM_W (QK-norm needs both)");
         const bool mqa = c.attention_type == NVL_ATTN_MQA;
         if (mqa) need(l.t[NVL_T_WKV].present(), "MQA fused KV projection");
         else need(l.t[NVL_T_WK].present() && l.t[NVL_T_WV].present(), "K/V projection");
@@ -1618,7 +1623,10 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         a.stamps = (fused_qkv && m->hd == 64 && !win) ? next_stamps(m, KS_ATTN, (int)(grid.x * grid.y * grid.z)) : nullptr;   // (the stamped form has no window)
         if (fused_qkv) {   // RoPE + KV append + attention in one launch, straight from the QKV projection's fp32 output
             a.qkv = m->qkv; a.qkv_stride = m->n_qkv; a.cos_t = m->rope_cos; a.sin_t = m->rope_sin;
+            a.q_norm_w = m->qkn_q; a.k_norm_w = m->qkn_k; a.qk_norm_eps = m->cfg.norm_eps;
         }
+        const bool qkn = fused_qkv && m->qkn_q;      // (qkv_front fuses a QK-norm layer at head_dim 128 only)
+        if (qkn && m->hd != 128) throw std::runtime_error("attention: the fused decode form with QK-norm needs head_dim 128");
 #define NVL_DEC(HDv, KERN, ...) launch_decode_attn<KERN(HDv, 2), KERN(HDv, 4), KERN(HDv, 8)>(m, grid, nw, 64 * HDv * 2, a, ##__VA_ARGS__)
 #define NVL_DEC_KV8(HDv, NWv) attn_decode_kv8_kernel<HDv, NWv>
 #define NVL_DEC_PLAIN(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, false>
@@ -1627,11 +1635,16 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
 #define NVL_DEC_KV8_W(HDv, NWv) attn_decode_kv8_kernel<HDv, NWv, true>
 #define NVL_DEC_PLAIN_W(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, false, false, true>
 #define NVL_DEC_FUSED_W(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true, false, true>
-        if (win && kv8) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_KV8_W, kv8[0], kv8[1]); else NVL_DEC(128, NVL_DEC_KV8_W, kv8[0], kv8[1]); }
+#define NVL_DEC_FUSED_N(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true, false, false, true>
+#define NVL_DEC_FUSED_WN(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true, false, true, true>
+        if (qkn) { if (win) NVL_DEC(128, NVL_DEC_FUSED_WN); else NVL_DEC(128, NVL_DEC_FUSED_N); }
+        else if (win && kv8) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_KV8_W, kv8[0], kv8[1]); else NVL_DEC(128, NVL_DEC_KV8_W, kv8[0], kv8[1]); }
         else if (win && fused_qkv) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_FUSED_W); else NVL_DEC(128, NVL_DEC_FUSED_W); }
         else if (win) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_PLAIN_W); else NVL_DEC(128, NVL_DEC_PLAIN_W); }
         else if (kv8) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_KV8, kv8[0], kv8[1]); else NVL_DEC(128, NVL_DEC_KV8, kv8[0], kv8[1]); }
         else if (a.stamps) NVL_DEC(64, NVL_DEC_STAMP);
+#undef NVL_DEC_FUSED_WN
+#undef NVL_DEC_FUSED_N
 #undef NVL_DEC_FUSED_W
 #undef NVL_DEC_PLAIN_W
 #undef NVL_DEC_KV8_W
@@ -1688,13 +1701,28 @@ void attention_kv8(nvl_model* m, const Meta& md, int n_seqs, int max_len, const 
     attention_launch(m, md, n_seqs, max_len, kc, vc, 0.0, m->kv_tok * 2.0 * m->nKV * m->hd, false, scales, mq);
 }
 
+// a QK-norm layer's form of rope_kv (below): qk_norm_rope_kv_kernel (qknorm.h), one launch, whole waves per token
+template <typename ActT, int HD, bool KV8>
+static void launch_qk_norm_rope_kv(nvl_model* m, int li, const Meta& md, int M, void* kc, void* vc) {
+    const int wpt = cdiv(m->nH + 2 * m->nKV, 64 / (HD / 8));
+    hipLaunchKernelGGL((qk_norm_rope_kv_kernel<ActT, HD, KV8>), dim3(cdiv(M * wpt, 4)), dim3(256), 0, m->stream, m->qkv, m->n_qkv, M,
+                       md.tok_pos, md.tok_tbl, md.blk_table, m->rope_cos, m->rope_sin, m->qkn_q, m->qkn_k, m->cfg.norm_eps,
+                       (ActT*)m->q, m->nH * m->hd, kc, vc, m->slot_stride, m->Tmax, m->nH, m->nKV,
+                       KV8 ? m->k_scale[li] : 1.f, KV8 ? m->v_scale[li] : 1.f);
+}
 void rope_kv(nvl_model* m, int li, const Meta& md, int M) {
     KScope ks(m, KC_OTHER, 0, KS_ROPE, (double)M * m->n_qkv * (4.0 + (double)m->wsize));
     dim3 grid(M, m->nH + 2 * m->nKV);
     const int thr = m->hd / 2;
     void* kc = (char*)m->kcache + (size_t)li * m->layer_stride * m->kv_esize;
     void* vc = (char*)m->vcache + (size_t)li * m->layer_stride * m->kv_esize;
-    if (m->kv8)
+    if (m->qkn_q) {
+        if (m->hd != 64 && m->hd != 128) throw std::runtime_error("QK-norm needs head_dim 64 or 128");
+#define NVL_QKN(ActTv, KV8v) do { if (m->hd == 64) launch_qk_norm_rope_kv<ActTv, 64, KV8v>(m, li, md, M, kc, vc); \
+                                  else launch_qk_norm_rope_kv<ActTv, 128, KV8v>(m, li, md, M, kc, vc); } while (0)
+        if (m->kv8) NVL_QKN(bf16_t, true); else if (m->f32) NVL_QKN(float, false); else NVL_QKN(bf16_t, false);
+#undef NVL_QKN
+    } else if (m->kv8)
         hipLaunchKernelGGL(rope_kv8_kernel, grid, dim3(thr), 0, m->stream, m->qkv, m->n_qkv,
                            md.tok_pos, md.tok_tbl, md.blk_table, m->rope_cos, m->rope_sin, (bf16_t*)m->q, m->nH * m->hd,
                            (uint8_t*)kc, (uint8_t*)vc, m->slot_stride, m->Tmax, m->nH, m->nKV, m->hd, m->k_scale[li], m->v_scale[li]);
@@ -2210,12 +2238,19 @@ bool qkv_front(nvl_model* m, const LayerW& l, int li, const Meta& md, int M, int
         m->front_ran[NVL_QKV_RAN_NORM] = m->norm_ran;
     }
     bool fused_dec = false;
+    // per-head QK RMSNorm (qknorm.h): between the projection and the rotation in each of the three forms below.  The epilogue
+    // variant serves bf16 weights and, on W~, every quantized format (wq.h); the W8A8 tile kernel (a8.h) has none, so a
+    // QK-norm layer under 8-bit activations takes the store form.
+    const bool qkn = l.qk_norm();
+    m->qkn_q = qkn ? (const float*)l.t[NVL_T_Q_NORM_W].p : nullptr;
+    m->qkn_k = qkn ? (const float*)l.t[NVL_T_K_NORM_W].p : nullptr;
+    const bool qkn_store = qkn && m->a8 && m->qmap.count(l.w_qkv) != 0;
     // a decode batch of 64 < M <= g_chunk_max_m rows keeps the decode form (64-row passes, gemm.h) and the fused
     // decode attention
     // short prefill batches (65..g_qkv_store_max_m tokens): the fused-epilogue tile kernel would run on M/128 * 24
     // workgroups; the decode form + rope_kv_kernel is faster there
     const bool short_prefill = max_len > 1 && M <= g_qkv_store_max_m && M <= g_chunk_max_m && g_force_tile == 0;
-    if (!m->f32 && !m->kv8 && M > 64 && !big_decode && !short_prefill) {
+    if (!m->f32 && !m->kv8 && M > 64 && !big_decode && !short_prefill && !qkn_store) {
         // prefill: RoPE + Q/K/V placement fused into the projection's epilogue (no fp32 qkv round trip)
         GemmArgs a = mk(m->xn, H, l.w_qkv, nullptr, 0, l.b_qkv, 1.f, M, m->n_qkv, H);
         a.qkv.tok_pos = md.tok_pos; a.qkv.tok_tbl = md.tok_tbl; a.qkv.blk_table = md.blk_table; a.qkv.cos_t = m->rope_cos; a.qkv.sin_t = m->rope_sin;
@@ -2223,15 +2258,18 @@ bool qkv_front(nvl_model* m, const LayerW& l, int li, const Meta& md, int M, int
         a.qkv.kcache = (bf16_t*)m->kcache + (int64_t)li * m->layer_stride;
         a.qkv.vcache = (bf16_t*)m->vcache + (int64_t)li * m->layer_stride;
         a.qkv.slot_stride = m->slot_stride; a.qkv.Tmax = m->Tmax; a.qkv.nH = m->nH; a.qkv.nKV = m->nKV; a.qkv.hd = m->hd;
+        a.q_norm_w = m->qkn_q; a.k_norm_w = m->qkn_k; a.qk_norm_eps = m->cfg.norm_eps;
         m->site = KS_QKV;
-        gemm(m, EPI_QKV, false, a);
+        gemm(m, qkn ? EPI_QKV_NORM : EPI_QKV, false, a);
         m->front_ran[NVL_QKV_RAN_FORM] = NVL_QKV_FORM_EPILOGUE;
     } else {
         GemmArgs aq = mk(m->xn, H, l.w_qkv, m->qkv, m->n_qkv, l.b_qkv, 1.f, M, m->n_qkv, H);
         if (qkv_deferred) set_deferred_in(m, aq);
         m->site = KS_QKV;
         gemm(m, EPI_STORE, true, aq);
-        fused_dec = !m->f32 && !m->kv8 && max_len == 1;     // decode: RoPE + KV append live in the attention kernel
+        // decode: RoPE + KV append live in the attention kernel — and the QK-norm at head_dim 128; a QK-norm layer with
+        // head_dim 64 keeps the norm + RoPE launch and the plain decode kernel (the fused hd-64 kernel has no registers for it)
+        fused_dec = !m->f32 && !m->kv8 && max_len == 1 && !(qkn && m->hd != 128);
         if (!fused_dec) rope_kv(m, li, md, M);     // (8-bit mode: always here — rope_kv8_kernel is its only K/V writer)
         m->front_ran[NVL_QKV_RAN_FORM] = fused_dec ? NVL_QKV_FORM_STORE_ONLY : m->kv8 ? NVL_QKV_FORM_STORE_ROPE_KV8
             : m->f32 ? NVL_QKV_FORM_F32_STORE_ROPE
@@ -3906,8 +3944,18 @@ extern "C" int nvl_get_mamba_conv_state(nvl_model* m, int64_t seq_id, int layer,
 extern "C" int nvl_get_weight(nvl_model* m, int kind, int layer, float* out, int64_t in_features, int64_t out_features) {
     if (!m || !out) return NVL_ERR_INVALID;
     DevTensor* t = tensor_slot(m, kind, layer);
-    if (!t || is_1d(kind)) return fail(m, NVL_ERR_INVALID, "nvl_get_weight: not a 2-D weight kind");
+    const bool qkn = kind == NVL_T_Q_NORM_W || kind == NVL_T_K_NORM_W;      // the two 1-D kinds it returns: [head_dim] x 1, fp32
+    if (!t || (is_1d(kind) && !qkn)) return fail(m, NVL_ERR_INVALID, "nvl_get_weight: not a 2-D weight kind");
     if (!t->present()) return fail(m, NVL_ERR_STATE, "nvl_get_weight: the tensor is not on the device (never uploaded, or fused away by nvl_finalize)");
+    if (qkn) {
+        if (in_features != t->rows || out_features != 1) return fail(m, NVL_ERR_INVALID, "nvl_get_weight: shape mismatch");
+        NVL_TRY(m)
+        NVL_HIP(hipSetDevice(m->device));
+        NVL_HIP(hipStreamSynchronize(m->stream));
+        NVL_HIP(hipMemcpy(out, t->p, (size_t)t->rows * 4, hipMemcpyDeviceToHost));
+        return NVL_OK;
+        NVL_CATCH(m)
+    }
     if (t->rows != out_features || t->cols != in_features) return fail(m, NVL_ERR_INVALID, "nvl_get_weight: shape mismatch");
     NVL_TRY(m)
     NVL_HIP(hipSetDevice(m->device));

@@ -633,11 +633,15 @@ extern "C" int nvl_op_attention_kv8(int device, const float* q, const float* k, 
 // wrote, or a partial record read before its workgroup wrote it, shows in `out`.  Nothing that could index outside the
 // pools reaches a kernel: every table entry is checked, used or not.
 // window: nvl_set_sliding_window's value for the stand-in model (0 = causal): the WINDOW instantiations of the same families.
-extern "C" int nvl_op_attention_batch_window(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+// q_norm_w / k_norm_w [hd], eps: the fused form of a QK-norm layer (the QKNORM instantiations, head_dim 128); both NULL: none.
+extern "C" int nvl_op_attention_batch_qknorm(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
                                              const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
                                              int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
-                                             int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window) {
+                                             int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window,
+                                             const float* q_norm_w, const float* k_norm_w, float eps) {
     const char* who = "nvl_op_attention_batch: ";
+    if ((q_norm_w != nullptr) != (k_norm_w != nullptr) || (q_norm_w && (form != NVL_ATTN_OP_FUSED || hd != 128 || !(eps >= 0.f) || !std::isfinite(eps))))
+        return op_fail(std::string(who) + "QK-norm: both weights, the fused form, head_dim 128, a finite eps >= 0");
     if (window < 0 || !seq_len || !seq_pos || !k_pool || !v_pool || !block_table || !q || !out || !ran || !part_cnt || nH <= 0 || nKV <= 0 ||
         nH % nKV || (hd != 64 && hd != 128) || n_seqs <= 0 || n_seqs > 4096 || n_blocks <= 0 || block_size <= 0 || block_size % 64 ||
         tbl_stride <= 0 || max_seq <= 0 || form < NVL_ATTN_OP_PLAIN || form > NVL_ATTN_OP_MQ_KV8 ||
@@ -701,6 +705,7 @@ extern "C" int nvl_op_attention_batch_window(int device, int precision, int form
             m.rope_cos = cx.up_f32(ct.data(), (int64_t)ct.size());
             m.rope_sin = cx.up_f32(st.data(), (int64_t)st.size());
         }
+        if (q_norm_w) { m.qkn_q = cx.up_f32(q_norm_w, hd); m.qkn_k = cx.up_f32(k_norm_w, hd); m.cfg.norm_eps = eps; }
     } else {
         m.q = cx.up_mat(q, tokens, W, false, 1, true);
     }
@@ -725,7 +730,7 @@ extern "C" int nvl_op_attention_batch_window(int device, int precision, int form
     m.ctx_hint = ctx;                                  // attn_cost: the longest context of the batch
     auto release = [&]() {                             // everything is owned by cx.bufs
         m.q = m.kcache = m.vcache = m.attn_out = nullptr; m.qkv = nullptr; m.rope_cos = m.rope_sin = nullptr;
-        m.attn_part = nullptr; m.attn_part_cnt = nullptr;
+        m.attn_part = nullptr; m.attn_part_cnt = nullptr; m.qkn_q = m.qkn_k = nullptr;
     };
     try {
         if (kv8) attention_kv8(&m, md, n_seqs, max_len, k8, v8, k_scale, v_scale, mq);
@@ -767,6 +772,15 @@ extern "C" int nvl_op_attention_batch_window(int device, int precision, int form
     OP_CATCH
 }
 
+extern "C" int nvl_op_attention_batch_window(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                                             const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                                             int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                                             int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window) {
+    return nvl_op_attention_batch_qknorm(device, precision, form, nH, nKV, hd, scale, n_seqs, seq_len, seq_pos, k_pool, v_pool, n_blocks,
+                                         block_size, block_table, tbl_stride, q, rope_base, max_seq, k_scale, v_scale, out, ran, part_cnt, window,
+                                         nullptr, nullptr, 0.f);
+}
+
 extern "C" int nvl_op_attention_batch(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
                                       const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
                                       int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
@@ -787,8 +801,14 @@ extern "C" int nvl_op_attention_batch(int device, int precision, int form, int n
 // every table entry, used or not, and every token id is checked first.
 extern "C" int nvl_op_qkv_stages(int device, int precision, const nvl_qkv_stages* d) {
     const char* who = "nvl_op_qkv_stages: ";
-    if (!d || d->struct_bytes != (int32_t)sizeof(nvl_qkv_stages) || (precision != NVL_PRECISION_BF16 && precision != NVL_PRECISION_F32))
-        return op_fail(std::string(who) + "bad arguments (struct_bytes = sizeof(nvl_qkv_stages))");
+    if (!d || (d->struct_bytes != (int32_t)sizeof(nvl_qkv_stages) && d->struct_bytes != (int32_t)sizeof(nvl_qkv_stages_qknorm)) ||
+        (precision != NVL_PRECISION_BF16 && precision != NVL_PRECISION_F32))
+        return op_fail(std::string(who) + "bad arguments (struct_bytes = sizeof(nvl_qkv_stages) or sizeof(nvl_qkv_stages_qknorm))");
+    // the longer layout carries the QK-norm weights behind `ran`; the shorter one, or two NULLs, is a layer without QK-norm
+    const bool has_qkn = d->struct_bytes == (int32_t)sizeof(nvl_qkv_stages_qknorm);
+    const float* q_norm_w = has_qkn ? ((const nvl_qkv_stages_qknorm*)d)->q_norm_w : nullptr;
+    const float* k_norm_w = has_qkn ? ((const nvl_qkv_stages_qknorm*)d)->k_norm_w : nullptr;
+    if ((q_norm_w != nullptr) != (k_norm_w != nullptr)) return op_fail(std::string(who) + "QK-norm needs both q_norm_w and k_norm_w");
     const int nH = d->nH, nKV = d->nKV, hd = d->hd, H = d->hidden, n_seqs = d->n_seqs, bs = d->block_size, stride = d->tbl_stride;
     const bool kv8 = d->kv8 != 0, embed_stage = d->tokens != nullptr;
     if (!d->seq_len || !d->seq_pos || !d->block_table || !d->w_qkv || !d->k_pool || !d->v_pool || !d->x || !d->op || !d->qkv || !d->q || !d->ran)
@@ -869,6 +889,7 @@ extern "C" int nvl_op_qkv_stages(int device, int precision, const nvl_qkv_stages
     if (d->b_qkv) l.b_qkv = cx.up_f32(d->b_qkv, m.n_qkv);
     if (d->norm_w) l.t[NVL_T_ATTN_NORM_W].p = cx.up_f32(d->norm_w, H);
     if (d->norm_b) l.t[NVL_T_ATTN_NORM_B].p = cx.up_f32(d->norm_b, H);
+    if (q_norm_w) { l.t[NVL_T_Q_NORM_W].p = cx.up_f32(q_norm_w, hd); l.t[NVL_T_K_NORM_W].p = cx.up_f32(k_norm_w, hd); }
     if (embed_stage) {
         m.g[NVL_T_TOK_EMB].p = cx.up_mat(d->emb, d->vocab, H, false, W_ROW_PAD);
         if (d->pos_emb) { m.g[NVL_T_POS_EMB].p = cx.up_mat(d->pos_emb, d->pos_rows, H, false, W_ROW_PAD); m.g[NVL_T_POS_EMB].rows = d->pos_rows; }

@@ -216,7 +216,7 @@ static inline void launch_gemm_q(hipStream_t st, const GemmArgs& a, const void* 
         throw err(" MoE projection did not fit the decode kernels");
     }
     if (launch_gemm_skinny_bf16<EPI, OutT, WF>(st, a, ws, gsh)) return;
-    if constexpr (EPI != EPI_QKV) {
+    if constexpr (!epi_is_qkv(EPI)) {
         if (skinny_groups_ok(a)) {     // (the 64-row-group condition of launch_gemm_bf16)
             GemmArgs c = a;
             c.m_passes = cdiv(a.M, 64);
@@ -226,7 +226,7 @@ static inline void launch_gemm_q(hipStream_t st, const GemmArgs& a, const void* 
         }
     }
     if (a.rs_in || a.rs_out) throw std::runtime_error("gemm: a deferred-RMSNorm projection did not fit the decode kernels");
-    if constexpr (WF == WF_FP8) {
+    if constexpr (WF == WF_FP8 && EPI != EPI_QKV_NORM) {     // (qkv_front sends a W8A8 QK-norm layer to the store form)
         if (a8) {
             launch_gemm_w8a8<EPI, OutT>(st, a, ws, *a8);
             return;

@@ -373,14 +373,15 @@ ATTN_OP_FORMS_KV8 = {"mq_kv8": 4}            # NVL_ATTN_OP_MQ_KV8: "kv8" with th
 
 
 def attention_batch(q, k_pool, v_pool, block_table, seq_len, seq_pos, nH, form="plain", scale=0.0, rope_base=0.0, max_seq=0,
-                    k_scale=1.0, v_scale=1.0, precision="bf16", device=0, window=0):   # generic_model.go:276 over block tables
+                    k_scale=1.0, v_scale=1.0, precision="bf16", device=0, window=0, q_norm_w=None, k_norm_w=None, norm_eps=1e-6):   # generic_model.go:276 over block tables
     """One layer's attention on a batch laid out as the paged front end lays it out, through the model's own dispatch
     (nvl_op_attention_batch): k_pool / v_pool [n_blocks][nKV][block_size][hd], block_table [n_seqs][tbl_stride] (passed
     verbatim), sequence i = seq_len[i] new rows behind seq_pos[i] cached keys.  q [tokens][nH][hd]; form "fused": the fp32
     QKV rows [n_seqs][(nH + 2 nKV) hd] of a decode step (RoPE with rope_base, 0 = none; K / V appended by the kernel);
     "mq" / "mq_kv8": a verify pass over a bf16 / an 8-bit cache (2..8 rows per sequence run the multi-position kernels).
     max_seq 0 = what the table covers.  window = W > 0: sliding-window attention, row at position i sees keys i - W < j <= i
-    (nvl_op_attention_batch_window; 0 = causal).  -> dict(out [tokens][nH][hd], ran (an ATTN_RAN name), nw, nsplit, part_cnt [32],
+    (nvl_op_attention_batch_window; 0 = causal).  q_norm_w / k_norm_w [hd] with norm_eps ("fused", hd 128): the per-head QK
+    RMSNorm of a Qwen3 layer ahead of the rotation (nvl_op_attention_batch_qknorm).  -> dict(out [tokens][nH][hd], ran (an ATTN_RAN name), nw, nsplit, part_cnt [32],
     and for "fused" k_pool / v_pool after the launch)."""
     k_pool, v_pool = _f(k_pool).copy(), _f(v_pool).copy()
     q = _f(q)
@@ -394,10 +395,14 @@ def attention_batch(q, k_pool, v_pool, block_table, seq_len, seq_pos, nH, form="
         raise ValueError("attention_batch: shapes do not match")
     out = np.empty((tokens, nH, hd), np.float32)
     ran, cnt = np.zeros(3, np.int32), np.zeros(32, np.int32)
-    L.check(L.lib().nvl_op_attention_batch_window(device, L.PRECISION[precision], {**ATTN_OP_FORMS, **ATTN_OP_FORMS_KV8}[form], nH, nKV, hd, scale,
+    qn, kn = (None if a is None else _f(a) for a in (q_norm_w, k_norm_w))
+    if any(a is not None and a.shape != (hd,) for a in (qn, kn)):
+        raise ValueError("attention_batch: q_norm_w / k_norm_w are [hd]")
+    L.check(L.lib().nvl_op_attention_batch_qknorm(device, L.PRECISION[precision], {**ATTN_OP_FORMS, **ATTN_OP_FORMS_KV8}[form], nH, nKV, hd, scale,
                                                   n_seqs, _p(sl), _p(sp), _p(k_pool), _p(v_pool), n_blocks, bs, _p(tbl), stride, _p(q),
                                                   float(rope_base), int(max_seq) if max_seq else stride * bs, k_scale, v_scale, _p(out),
-                                                  _p(ran), _p(cnt), int(window)))
+                                                  _p(ran), _p(cnt), int(window), None if qn is None else _p(qn),
+                                                  None if kn is None else _p(kn), float(norm_eps)))
     res = dict(out=out, ran=ATTN_RAN[int(ran[0])], nw=int(ran[1]), nsplit=int(ran[2]), part_cnt=cnt)
     if form == "fused":
         res.update(k_pool=k_pool, v_pool=v_pool)
@@ -413,12 +418,15 @@ EMBED_RAN = {0: None, 1: "f32", 2: "bf16", 3: "w8", 4: "w4"}                    
 
 def qkv_stages(x, w_qkv, k_pool, v_pool, block_table, seq_len, seq_pos, nH, b_qkv=None, norm_w=None, norm_b=None, norm="rms",
                norm_eps=1e-5, rope_base=0.0, max_seq=0, kv8=False, k_scale=1.0, v_scale=1.0, tokens=None, tok_pos=None, emb=None,
-               pos_emb=None, embedding_multiplier=0.0, precision="bf16", device=0):   # generic_model.go:295-318 + rope.go:153
+               pos_emb=None, embedding_multiplier=0.0, precision="bf16", device=0, q_norm_w=None, k_norm_w=None,
+               qk_norm_struct=None):   # generic_model.go:295-318 + rope.go:153
     """The front of an attention layer on a paged batch, stage by stage (nvl_op_qkv_stages): x [tokens][hidden] (None with the
     embedding stage: tokens / tok_pos [tokens], emb [V][hidden], pos_emb [P][hidden] or None), the attention norm (norm_w
     None: x is the operand already), w_qkv [(nH + 2 nKV) hd][hidden] (+ b_qkv), RoPE with rope_base (0: none), Q into the
     operand buffer, K / V into k_pool / v_pool [n_blocks][nKV][block][hd] through block_table [n_seqs][stride]; sequence i =
-    seq_len[i] rows behind seq_pos[i] cached keys.  max_seq 0 = what the table covers.
+    seq_len[i] rows behind seq_pos[i] cached keys.  max_seq 0 = what the table covers.  q_norm_w / k_norm_w [hd]: the per-head
+    QK RMSNorm of a Qwen3 layer (eps = norm_eps) between the projection and RoPE; they travel in nvl_qkv_stages_qknorm, which
+    qk_norm_struct=True also sends with two NULLs (default: only when a weight is given).
     -> dict(x (the embedding stage's), op [tokens][hidden], qkv [tokens][n_qkv] (NaN in the epilogue form), q [round_up(tokens,
     256)][nH hd], k_pool, v_pool after the pass (kv8: dequantized, plus k_codes / v_codes), ran = dict(form (a QKV_FORMS
     name), gemm (GEMM_RAN), norm (NORM_RAN), embed (EMBED_RAN)))."""
@@ -443,7 +451,12 @@ def qkv_stages(x, w_qkv, k_pool, v_pool, block_table, seq_len, seq_pos, nH, b_qk
     out = dict(op=nan(M, H), qkv=nan(M, N), q=nan(Mq, nH * hd))
     codes = dict(k_codes=np.zeros(k_pool.shape, np.uint8), v_codes=np.zeros(k_pool.shape, np.uint8)) if kv8 else {}
     ran = np.zeros(4, np.int32)
-    d = L.QkvStagesC(struct_bytes=C.sizeof(L.QkvStagesC), kv8=1 if kv8 else 0, nH=nH, nKV=nKV, hd=hd, hidden=H, n_seqs=n_seqs,
+    qkn = dict(q_norm_w=None if q_norm_w is None else _f(q_norm_w), k_norm_w=None if k_norm_w is None else _f(k_norm_w))
+    if any(a is not None and a.shape != (hd,) for a in qkn.values()):
+        raise ValueError("qkv_stages: q_norm_w / k_norm_w are [hd]")
+    long_form = qk_norm_struct if qk_norm_struct is not None else any(a is not None for a in qkn.values())
+    whole = L.QkvStagesQkNormC() if long_form else None
+    d = L.QkvStagesC(struct_bytes=C.sizeof(L.QkvStagesQkNormC if long_form else L.QkvStagesC), kv8=1 if kv8 else 0, nH=nH, nKV=nKV, hd=hd, hidden=H, n_seqs=n_seqs,
                      tbl_stride=stride, n_blocks=n_blocks, block_size=bs, max_seq=int(max_seq) if max_seq else stride * bs,
                      norm_type=1 if norm == "rms" else 0, vocab=0 if opt["emb"] is None else opt["emb"].shape[0],
                      pos_rows=0 if opt["pos_emb"] is None else opt["pos_emb"].shape[0], norm_eps=norm_eps, k_scale=k_scale,
@@ -451,7 +464,11 @@ def qkv_stages(x, w_qkv, k_pool, v_pool, block_table, seq_len, seq_pos, nH, b_qk
     keep = dict(seq_len=sl, seq_pos=sp, block_table=tbl, w_qkv=w_qkv, x=x, k_pool=k_pool, v_pool=v_pool, ran=ran, **opt, **ints, **out, **codes)
     for k, v in keep.items():
         setattr(d, k, None if v is None else v.ctypes.data)
-    L.check(L.lib().nvl_op_qkv_stages(device, L.PRECISION[precision], C.byref(d)))
+    if long_form:
+        whole.s = d
+        for k, v in qkn.items():
+            setattr(whole, k, None if v is None else v.ctypes.data)
+    L.check(L.lib().nvl_op_qkv_stages(device, L.PRECISION[precision], C.cast(C.byref(whole), C.POINTER(L.QkvStagesC)) if long_form else C.byref(d)))
     out.update(k_pool=k_pool, v_pool=v_pool, **codes)
     if tokens is not None:
         out["x"] = x

@@ -81,6 +81,12 @@ def make_weights(cfg: dict, seed: int = 42, scale: float = 0.02, peaked_head: fl
             t[("wk", li)] = w(r, H, nKV * hd)
             t[("wv", li)] = w(r, H, nKV * hd)
         t[("wo", li)] = w(r, nH * hd, H)
+        if cfg.get("qk_norm", False):
+            # per-head QK RMSNorm (Qwen3): one [hd] vector for Q and another for K, around 1 with a visible spread; a
+            # generator of their own, so every other tensor is what the same config without qk_norm gets
+            rn = np.random.default_rng(seed + 7919 * (li + 1))
+            for name in ("q_norm_w", "k_norm_w"):
+                t[(name, li)] = round_bf16(1.0 + 0.25 * rn.standard_normal(hd, dtype=np.float32))
         if at == "mha":   # GPT-2: attention biases ARE loaded (generic_loader.go:418-441)
             for b, n in (("bq", nH * hd), ("bk", nKV * hd), ("bv", nKV * hd), ("bo", H)):
                 t[(b, li)] = nb(r, n)

@@ -532,3 +532,11 @@ func (r *HipModelRunner) Close() error {
 	}
 	return nil
 }
+
+// Per-head QK RMSNorm (Qwen3 q_norm / k_norm, [head_dim] per layer): the tensor kinds behind NVL_T_MAMBA_OUT_PROJ.  A layer
+// that has both uploaded norms every Q head and K head before RoPE; the reference's attention layers carry no such tensors,
+// so the shim uploads none by itself.
+const (
+	TensorQNormW = int(C.NVL_T_Q_NORM_W)
+	TensorKNormW = int(C.NVL_T_K_NORM_W)
+)
