@@ -1554,6 +1554,39 @@ static void launch_decode_attn(nvl_model* m, dim3 grid, int nw, int tile_bytes, 
     }
 #undef NVL_DEC_LEAD
 }
+// Which attention kernel a launch takes: family and template arguments, filled once by attention_launch.  attn_variant_exists is
+// the whole rule of which combinations the library holds: asked at run time (refusal) and in `if constexpr` (never instantiated).
+enum AttnFamily { ATTN_F32, ATTN_PREFILL, ATTN_DECODE, ATTN_DECODE_MQ };
+struct AttnVariant {
+    AttnFamily family;
+    int hd;                                          // (the f32 kernel takes it as a run-time argument)
+    bool kv8, window, fused, qknorm, stamped;        // fused: RoPE + KV append inside the decode kernel; stamped: its diagnostic in-kernel stamps
+    int tq;                                          // query tiles per workgroup (mq_kv8_tq)
+};
+constexpr bool attn_variant_exists(const AttnVariant& v) {
+    if (v.fused && (v.family != ATTN_DECODE || v.kv8)) return false;         // only the one-position bf16 decode kernel appends
+    if (v.qknorm && !(v.fused && v.hd == 128)) return false;                 // (qkv_front fuses a QK-norm layer at head_dim 128 only: attn.h)
+    if (v.stamped && !(v.fused && v.hd == 64 && !v.window)) return false;    // (the stamped form has no window)
+    if (v.tq == 2) return v.family == ATTN_DECODE_MQ && v.kv8 && v.hd == 64; // (hd 128 with two tiles does not fit the register file: kv8.h)
+    return v.tq == 1;
+}
+// a run-time flag as a template argument: f gets std::true_type / std::false_type, or the head size as an integral_constant
+template <typename F> static void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
+template <typename F> static void with_hd(int hd, F&& f) { if (hd == 64) f(std::integral_constant<int, 64>{}); else f(std::integral_constant<int, 128>{}); }
+// The prefill and f32 launch.  lds_limit > 0: raise the kernel's dynamic-LDS limit to it first — the head_dim 128 prefill forms
+// (the 8-bit one among them, whose 32 KB would fit the default limit) and an f32 score buffer above 64 KB.
+template <auto Kernel, typename... Args>
+static void launch_prefill(nvl_model* m, dim3 grid, int threads, size_t lds_bytes, int lds_limit, const Args&... args) {
+    if (lds_limit > 0) NVL_LDS_ATTR(Kernel, lds_limit);
+    hipLaunchKernelGGL(Kernel, grid, dim3(threads), lds_bytes, m->stream, args...);
+}
+// non-temporal K/V loads when one workgroup serves a (sequence, kv head)'s whole group (the K/V are then read once) and
+// the launch fills the chip — by batch size on Llama-3.2-1B (8 kv heads, 520 keys; profiles/r03_kv_nontemporal.txt):
+// B = 1 +1.7 %, 2 +-0, 4 -2.3 %, 8 -2.4 %, 16 +-0, 24 +2.7 %, 32 +5 %, 48 +1 %; GPT-2 B = 128 (1536 workgroups) +3.2 %.
+// The multi-position launches take the same policy with their own grid: workgroups per kv head, of 1 or 2 query tiles each.
+static bool kv_nt_policy(const nvl_model* m, int n_seqs, int query_tiles_per_kv_head) {
+    return g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && query_tiles_per_kv_head == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
+}
 // Every attention launch.  kc / vc: the layer's K / V slabs; kv8: {k_scale, v_scale} of an 8-bit (e4m3fn) cache — the slabs
 // are then the layer's code slabs (same element layout, one byte per element; kv8.h) — else NULL.  The 8-bit kernels have
 // no fused (RoPE + append) and no stamped form, and their prefill kernel reads the block table from global memory (no
@@ -1575,39 +1608,43 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
     const bool win = m->window > 0;
     a.window = std::min(m->window, 1 << 30);
     KScope ks(m, KC_ATTN, flops, KS_ATTN, abytes);
-    if (m->f32) {
+    AttnVariant v{};
+    v.family = m->f32 ? ATTN_F32 : (mq && attention_mq_ok(m, max_len)) ? ATTN_DECODE_MQ : (max_len == 1 ? ATTN_DECODE : ATTN_PREFILL);
+    v.hd = m->hd; v.kv8 = kv8 != nullptr; v.window = win;
+    v.fused = v.family == ATTN_DECODE && fused_qkv;
+    v.qknorm = v.fused && m->qkn_q;      // (qkv_front fuses a QK-norm layer at head_dim 128 only)
+    const int qt = cdiv(m->group * (v.family == ATTN_DECODE_MQ ? max_len : 1), 16);      // 16-row query tiles per kv head
+    v.tq = v.family == ATTN_DECODE_MQ && v.kv8 ? mq_kv8_tq(m, qt, n_seqs) : 1;
+    if (v.qknorm && v.hd != 128) throw std::runtime_error("attention: the fused decode form with QK-norm needs head_dim 128");
+    if (!attn_variant_exists(v)) throw std::runtime_error("attention: no kernel for this combination of forms");     // (unreachable today: `if constexpr` below would launch nothing)
+    if (v.family == ATTN_PREFILL && !v.kv8 && m->blocks_per_seq > 128) throw std::runtime_error("attention: more than 128 KV blocks per sequence");
+    if (v.family == ATTN_F32) {
         // one score per key a row can see: up to blocks_per_seq blocks of Tmax keys (slab mode: the one block)
         const size_t lds = (size_t)m->Tmax * m->blocks_per_seq * 4;
-        if (lds > 64 * 1024) { if (win) NVL_LDS_ATTR(attn_f32_kernel<true>, 160 * 1024 - 64); else NVL_LDS_ATTR(attn_f32_kernel<false>, 160 * 1024 - 64); }
-        if (win) hipLaunchKernelGGL(attn_f32_kernel<true>, dim3(max_len, m->nH, n_seqs), dim3(256), lds, m->stream, a, m->hd);
-        else hipLaunchKernelGGL(attn_f32_kernel<false>, dim3(max_len, m->nH, n_seqs), dim3(256), lds, m->stream, a, m->hd);
+        with_bool(win, [&](auto Wt) {
+            launch_prefill<attn_f32_kernel<decltype(Wt)::value>>(m, dim3(max_len, m->nH, n_seqs), 256, lds, lds > 64 * 1024 ? 160 * 1024 - 64 : 0, a, m->hd);
+        });
         m->attn_ran[0] = NVL_ATTN_RAN_F32; m->attn_ran[1] = 4; m->attn_ran[2] = 1;
-    } else if (mq && kv8 && attention_mq_ok(m, max_len)) {
+    } else if (v.family == ATTN_DECODE_MQ) {
         const int nw = decode_attn_cfg(m, n_seqs, max_len) & 255;
-        const int qt = cdiv(m->group * max_len, 16), tq = mq_kv8_tq(m, qt, n_seqs), qw = cdiv(qt, tq);
-        dim3 grid(m->nKV * qw, n_seqs, 1);     // (kv head x group of tq 16-row query tiles, sequence); no key split
-        // K/V read once per step by its only workgroup: the one-position launch's policy, with this grid
-        a.kv_nt = g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && qw == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
-#define NVL_DEC_MQ8W(HDv, TQv, Wv) launch_decode_attn<attn_decode_mq_kv8_kernel<HDv, 2, TQv, Wv>, attn_decode_mq_kv8_kernel<HDv, 4, TQv, Wv>, \
-                                                      attn_decode_mq_kv8_kernel<HDv, 8, TQv, Wv>>(m, grid, nw, 64 * HDv * 2, a, max_len, kv8[0], kv8[1])
-#define NVL_DEC_MQ8(HDv, TQv) do { if (win) NVL_DEC_MQ8W(HDv, TQv, true); else NVL_DEC_MQ8W(HDv, TQv, false); } while (0)
-        if (m->hd == 64) { if (tq == 2) NVL_DEC_MQ8(64, 2); else NVL_DEC_MQ8(64, 1); }
-        else NVL_DEC_MQ8(128, 1);
-#undef NVL_DEC_MQ8
-#undef NVL_DEC_MQ8W
-        m->attn_ran[0] = NVL_ATTN_RAN_DECODE_MQ_KV8; m->attn_ran[1] = nw; m->attn_ran[2] = 1;
-    } else if (mq && !kv8 && attention_mq_ok(m, max_len)) {
-        const int nw = decode_attn_cfg(m, n_seqs, max_len) & 255;
-        dim3 grid(m->nKV * cdiv(m->group * max_len, 16), n_seqs, 1);     // (kv head x 16-row query tile, sequence); no key split
-        // K/V read once per step by its only workgroup: the one-position launch's policy, with this grid
-        a.kv_nt = g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && cdiv(m->group * max_len, 16) == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
-#define NVL_DEC_MQ(HDv, Wv) launch_decode_attn<attn_decode_mq_bf16_kernel<HDv, 2, Wv>, attn_decode_mq_bf16_kernel<HDv, 4, Wv>, \
-                                               attn_decode_mq_bf16_kernel<HDv, 8, Wv>>(m, grid, nw, 64 * HDv * 2, a, max_len)
-        if (m->hd == 64) { if (win) NVL_DEC_MQ(64, true); else NVL_DEC_MQ(64, false); }
-        else { if (win) NVL_DEC_MQ(128, true); else NVL_DEC_MQ(128, false); }
-#undef NVL_DEC_MQ
-        m->attn_ran[0] = NVL_ATTN_RAN_DECODE_MQ; m->attn_ran[1] = nw; m->attn_ran[2] = 1;
-    } else if (max_len == 1) {
+        const int qw = cdiv(qt, v.tq);
+        dim3 grid(m->nKV * qw, n_seqs, 1);     // (kv head x group of tq 16-row query tiles — one over a bf16 cache —, sequence); no key split
+        a.kv_nt = kv_nt_policy(m, n_seqs, qw);
+        with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) {
+            constexpr int HD = decltype(HDt)::value;
+            constexpr bool W = decltype(Wt)::value;
+            if (!kv8)
+                launch_decode_attn<attn_decode_mq_bf16_kernel<HD, 2, W>, attn_decode_mq_bf16_kernel<HD, 4, W>,
+                                   attn_decode_mq_bf16_kernel<HD, 8, W>>(m, grid, nw, 64 * HD * 2, a, max_len);
+            else with_bool(v.tq == 2, [&](auto T2t) {
+                constexpr int TQ = decltype(T2t)::value ? 2 : 1;
+                if constexpr (attn_variant_exists(AttnVariant{ATTN_DECODE_MQ, HD, true, W, false, false, false, TQ}))
+                    launch_decode_attn<attn_decode_mq_kv8_kernel<HD, 2, TQ, W>, attn_decode_mq_kv8_kernel<HD, 4, TQ, W>,
+                                       attn_decode_mq_kv8_kernel<HD, 8, TQ, W>>(m, grid, nw, 64 * HD * 2, a, max_len, kv8[0], kv8[1]);
+            });
+        }); });
+        m->attn_ran[0] = kv8 ? NVL_ATTN_RAN_DECODE_MQ_KV8 : NVL_ATTN_RAN_DECODE_MQ; m->attn_ran[1] = nw; m->attn_ran[2] = 1;
+    } else if (v.family == ATTN_DECODE) {
         const int cfg = decode_attn_cfg(m, n_seqs), nsplit = cfg >> 8;
         dim3 grid(m->nKV * cdiv(m->group, 16), n_seqs, nsplit);      // (kv head x 16-head query tile, sequence, key split)
         a.part = m->attn_part; a.part_cnt = m->attn_part_cnt;
@@ -1616,76 +1653,46 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         // fills the chip (>= 2 workgroups per CU) fewer, longer-running waves stream better than many short ones
         // (profiles/r01g_decode_attention_waves.txt).  ctx_hint = the batch's longest context when the caller knows it.
         const int nw = cfg & 255;
-        // non-temporal K/V loads when one workgroup serves a (sequence, kv head)'s whole group (the K/V are then read once) and
-        // the launch fills the chip — by batch size on Llama-3.2-1B (8 kv heads, 520 keys; profiles/r03_kv_nontemporal.txt):
-        // B = 1 +1.7 %, 2 +-0, 4 -2.3 %, 8 -2.4 %, 16 +-0, 24 +2.7 %, 32 +5 %, 48 +1 %; GPT-2 B = 128 (1536 workgroups) +3.2 %
-        a.kv_nt = g_attn_kv_nt == 2 || (g_attn_kv_nt == 1 && cdiv(m->group, 16) == 1 && (m->nKV * n_seqs >= 160 || n_seqs == 1));
-        a.stamps = (fused_qkv && m->hd == 64 && !win) ? next_stamps(m, KS_ATTN, (int)(grid.x * grid.y * grid.z)) : nullptr;   // (the stamped form has no window)
-        if (fused_qkv) {   // RoPE + KV append + attention in one launch, straight from the QKV projection's fp32 output
+        a.kv_nt = kv_nt_policy(m, n_seqs, qt);
+        AttnVariant vs = v;
+        vs.stamped = true;     // diagnostic: the in-kernel stamps compiled in, where that form exists and a stamp buffer is to be had
+        a.stamps = attn_variant_exists(vs) ? next_stamps(m, KS_ATTN, (int)(grid.x * grid.y * grid.z)) : nullptr;
+        v.stamped = a.stamps != nullptr;
+        if (v.fused) {   // RoPE + KV append + attention in one launch, straight from the QKV projection's fp32 output
             a.qkv = m->qkv; a.qkv_stride = m->n_qkv; a.cos_t = m->rope_cos; a.sin_t = m->rope_sin;
             a.q_norm_w = m->qkn_q; a.k_norm_w = m->qkn_k; a.qk_norm_eps = m->cfg.norm_eps;
         }
-        const bool qkn = fused_qkv && m->qkn_q;      // (qkv_front fuses a QK-norm layer at head_dim 128 only)
-        if (qkn && m->hd != 128) throw std::runtime_error("attention: the fused decode form with QK-norm needs head_dim 128");
-#define NVL_DEC(HDv, KERN, ...) launch_decode_attn<KERN(HDv, 2), KERN(HDv, 4), KERN(HDv, 8)>(m, grid, nw, 64 * HDv * 2, a, ##__VA_ARGS__)
-#define NVL_DEC_KV8(HDv, NWv) attn_decode_kv8_kernel<HDv, NWv>
-#define NVL_DEC_PLAIN(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, false>
-#define NVL_DEC_FUSED(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true>
-#define NVL_DEC_STAMP(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true, true>     /* diagnostic: the in-kernel stamps compiled in */
-#define NVL_DEC_KV8_W(HDv, NWv) attn_decode_kv8_kernel<HDv, NWv, true>
-#define NVL_DEC_PLAIN_W(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, false, false, true>
-#define NVL_DEC_FUSED_W(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true, false, true>
-#define NVL_DEC_FUSED_N(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true, false, false, true>
-#define NVL_DEC_FUSED_WN(HDv, NWv) attn_decode_bf16_kernel<HDv, NWv, true, false, true, true>
-        if (qkn) { if (win) NVL_DEC(128, NVL_DEC_FUSED_WN); else NVL_DEC(128, NVL_DEC_FUSED_N); }
-        else if (win && kv8) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_KV8_W, kv8[0], kv8[1]); else NVL_DEC(128, NVL_DEC_KV8_W, kv8[0], kv8[1]); }
-        else if (win && fused_qkv) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_FUSED_W); else NVL_DEC(128, NVL_DEC_FUSED_W); }
-        else if (win) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_PLAIN_W); else NVL_DEC(128, NVL_DEC_PLAIN_W); }
-        else if (kv8) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_KV8, kv8[0], kv8[1]); else NVL_DEC(128, NVL_DEC_KV8, kv8[0], kv8[1]); }
-        else if (a.stamps) NVL_DEC(64, NVL_DEC_STAMP);
-#undef NVL_DEC_FUSED_WN
-#undef NVL_DEC_FUSED_N
-#undef NVL_DEC_FUSED_W
-#undef NVL_DEC_PLAIN_W
-#undef NVL_DEC_KV8_W
-        else if (fused_qkv) { if (m->hd == 64) NVL_DEC(64, NVL_DEC_FUSED); else NVL_DEC(128, NVL_DEC_FUSED); }
-        else { if (m->hd == 64) NVL_DEC(64, NVL_DEC_PLAIN); else NVL_DEC(128, NVL_DEC_PLAIN); }
+        with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) {
+            constexpr int HD = decltype(HDt)::value;
+            constexpr bool W = decltype(Wt)::value;
+            if (kv8)
+                launch_decode_attn<attn_decode_kv8_kernel<HD, 2, W>, attn_decode_kv8_kernel<HD, 4, W>,
+                                   attn_decode_kv8_kernel<HD, 8, W>>(m, grid, nw, 64 * HD * 2, a, kv8[0], kv8[1]);
+            else with_bool(v.fused, [&](auto Ft) { with_bool(v.qknorm, [&](auto Nt) { with_bool(v.stamped, [&](auto St) {
+                constexpr bool F = decltype(Ft)::value, N = decltype(Nt)::value, S = decltype(St)::value;
+                if constexpr (attn_variant_exists(AttnVariant{ATTN_DECODE, HD, false, W, F, N, S, 1}))
+                    launch_decode_attn<attn_decode_bf16_kernel<HD, 2, F, S, W, N>, attn_decode_bf16_kernel<HD, 4, F, S, W, N>,
+                                       attn_decode_bf16_kernel<HD, 8, F, S, W, N>>(m, grid, nw, 64 * HD * 2, a);
+            }); }); });
+        }); });
         m->attn_ran[0] = kv8 ? NVL_ATTN_RAN_DECODE_KV8 : (a.stamps ? NVL_ATTN_RAN_DECODE_STAMPED : (fused_qkv ? NVL_ATTN_RAN_DECODE_FUSED : NVL_ATTN_RAN_DECODE));
         m->attn_ran[1] = nw; m->attn_ran[2] = nsplit;
-#undef NVL_DEC_STAMP
-#undef NVL_DEC_FUSED
-#undef NVL_DEC_PLAIN
-#undef NVL_DEC_KV8
-#undef NVL_DEC
     } else {
         // 256 query rows (position x head-in-group, position-major) per workgroup of 8 waves
         const int64_t qrows = (int64_t)max_len * m->group;
         dim3 grid(m->nKV, n_seqs, cdiv(qrows, 256));      // (kv head fastest, query tile slowest: attn.h)
         m->attn_ran[0] = kv8 ? NVL_ATTN_RAN_PREFILL_KV8 : NVL_ATTN_RAN_PREFILL; m->attn_ran[1] = 8; m->attn_ran[2] = 1;
-        if (kv8) {     // K/V tiles through registers into one bf16 image pair
-            if (m->hd == 64) {
-                if (win) hipLaunchKernelGGL((attn_prefill_kv8_kernel<64, true>), grid, dim3(512), attn_prefill_kv8_lds_bytes<64>(), m->stream, a, kv8[0], kv8[1]);
-                else hipLaunchKernelGGL((attn_prefill_kv8_kernel<64>), grid, dim3(512), attn_prefill_kv8_lds_bytes<64>(), m->stream, a, kv8[0], kv8[1]);
-            } else if (win) {
-                NVL_LDS_ATTR((attn_prefill_kv8_kernel<128, true>), attn_prefill_kv8_lds_bytes<128>());
-                hipLaunchKernelGGL((attn_prefill_kv8_kernel<128, true>), grid, dim3(512), attn_prefill_kv8_lds_bytes<128>(), m->stream, a, kv8[0], kv8[1]);
-            } else {
-                NVL_LDS_ATTR(attn_prefill_kv8_kernel<128>, attn_prefill_kv8_lds_bytes<128>());
-                hipLaunchKernelGGL((attn_prefill_kv8_kernel<128>), grid, dim3(512), attn_prefill_kv8_lds_bytes<128>(), m->stream, a, kv8[0], kv8[1]);
-            }
-        } else {       // K/V tiles by LDS-DMA; the kernel keeps the sequence's block table in LDS
-            if (m->blocks_per_seq > 128) throw std::runtime_error("attention: more than 128 KV blocks per sequence");
-            if (m->hd == 64) {
-                if (win) hipLaunchKernelGGL((attn_prefill_bf16_win_kernel<64>), grid, dim3(512), attn_prefill_lds_bytes<64>(), m->stream, a);
-                else hipLaunchKernelGGL((attn_prefill_bf16_kernel<64>), grid, dim3(512), attn_prefill_lds_bytes<64>(), m->stream, a);
-            } else if (win) {
-                NVL_LDS_ATTR(attn_prefill_bf16_win_kernel<128>, attn_prefill_lds_bytes<128>());
-                hipLaunchKernelGGL((attn_prefill_bf16_win_kernel<128>), grid, dim3(512), attn_prefill_lds_bytes<128>(), m->stream, a);
-            } else {
-                NVL_LDS_ATTR(attn_prefill_bf16_kernel<128>, attn_prefill_lds_bytes<128>());
-                hipLaunchKernelGGL((attn_prefill_bf16_kernel<128>), grid, dim3(512), attn_prefill_lds_bytes<128>(), m->stream, a);
-            }
-        }
+        with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) {
+            constexpr int HD = decltype(HDt)::value;
+            constexpr bool W = decltype(Wt)::value;
+            const int lds = kv8 ? attn_prefill_kv8_lds_bytes<HD>() : attn_prefill_lds_bytes<HD>(), limit = HD == 128 ? lds : 0;
+            if (kv8)       // K/V tiles through registers into one bf16 image pair
+                launch_prefill<attn_prefill_kv8_kernel<HD, W>>(m, grid, 512, lds, limit, a, kv8[0], kv8[1]);
+            else if constexpr (W)      // K/V tiles by LDS-DMA; the kernel keeps the sequence's block table in LDS
+                launch_prefill<attn_prefill_bf16_win_kernel<HD>>(m, grid, 512, lds, limit, a);
+            else
+                launch_prefill<attn_prefill_bf16_kernel<HD>>(m, grid, 512, lds, limit, a);
+        }); });
     }
     NVL_HIP(hipGetLastError());
 }
@@ -1718,10 +1725,12 @@ void rope_kv(nvl_model* m, int li, const Meta& md, int M) {
     void* vc = (char*)m->vcache + (size_t)li * m->layer_stride * m->kv_esize;
     if (m->qkn_q) {
         if (m->hd != 64 && m->hd != 128) throw std::runtime_error("QK-norm needs head_dim 64 or 128");
-#define NVL_QKN(ActTv, KV8v) do { if (m->hd == 64) launch_qk_norm_rope_kv<ActTv, 64, KV8v>(m, li, md, M, kc, vc); \
-                                  else launch_qk_norm_rope_kv<ActTv, 128, KV8v>(m, li, md, M, kc, vc); } while (0)
-        if (m->kv8) NVL_QKN(bf16_t, true); else if (m->f32) NVL_QKN(float, false); else NVL_QKN(bf16_t, false);
-#undef NVL_QKN
+        with_hd(m->hd, [&](auto HDt) {
+            constexpr int HD = decltype(HDt)::value;
+            if (m->kv8) launch_qk_norm_rope_kv<bf16_t, HD, true>(m, li, md, M, kc, vc);
+            else if (m->f32) launch_qk_norm_rope_kv<float, HD, false>(m, li, md, M, kc, vc);
+            else launch_qk_norm_rope_kv<bf16_t, HD, false>(m, li, md, M, kc, vc);
+        });
     } else if (m->kv8)
         hipLaunchKernelGGL(rope_kv8_kernel, grid, dim3(thr), 0, m->stream, m->qkv, m->n_qkv,
                            md.tok_pos, md.tok_tbl, md.blk_table, m->rope_cos, m->rope_sin, (bf16_t*)m->q, m->nH * m->hd,

@@ -47,6 +47,25 @@ struct OpCtx {   // a model-less nvl_model carrying just a stream and the fields
         NVL_HIP(hipMemcpyAsync(h, d, (size_t)n * 4, hipMemcpyDeviceToHost, m.stream));
         NVL_HIP(hipStreamSynchronize(m.stream));
     }
+    // device bf16 [round_up(rows, 64)][W], fragment-major (a kernel wrote a GEMM's operand) -> host fp32 [rows][W], row-major
+    void down_fm(float* out, const void* dev_bf16, int64_t rows, int64_t W) {
+        std::vector<uint16_t> ob((size_t)(round_up(rows, 64) * W));
+        NVL_HIP(hipMemcpyAsync(ob.data(), dev_bf16, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
+        NVL_HIP(hipStreamSynchronize(m.stream));
+        for (int64_t r = 0; r < rows; r++)
+            for (int64_t c = 0; c < W; c++) {
+                const uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, W)]) << 16;
+                memcpy(&out[(size_t)(r * W + c)], &u, 4);
+            }
+    }
+    // host fp32 K or V values -> the 8-bit codes of a cache, written on the device by the shared quantizer (kv8.h)
+    uint8_t* quantize_pool(const float* host_f32, int64_t n_el, float scale) {
+        const float* d = up_f32(host_f32, n_el);
+        uint8_t* codes = (uint8_t*)alloc(n_el);
+        hipLaunchKernelGGL(kv8_quant_kernel, dim3((unsigned)cdiv(cdiv(n_el, 4), 256)), dim3(256), 0, m.stream, d, n_el, scale, codes);
+        NVL_HIP(hipGetLastError());
+        return codes;
+    }
 };
 
 int op_fail(const std::string& s, int code = NVL_ERR_INVALID) { g_create_err = s; return code; }
@@ -167,59 +186,80 @@ extern "C" int nvl_op_rope(int device, float* t, int heads, int seq, int hd, int
     OP_CATCH
 }
 
-extern "C" int nvl_op_attention(int device, int precision, const float* q, const float* k, const float* v, int nH, int nKV,
-                                int S, int T, int hd, float scale, float* out) {
-    if (!q || !k || !v || !out || nH <= 0 || nKV <= 0 || nH % nKV || S <= 0 || T < S || (hd != 64 && hd != 128))
-        return op_fail("nvl_op_attention: bad arguments");
-    OP_TRY
-    OpCtx cx(device, precision);
+namespace {
+
+// One sequence of S new rows over T keys, through attention() / attention_kv8() on a slab-mode stand-in model: q [nH][S][hd]
+// and k / v [nKV][T][hd] in, out [nH][S][hd].  What the entry points below set differently decides the launch shape their
+// tests see, so each asks for it here and nothing is unified.
+struct AttnOpOne {
+    int precision = NVL_PRECISION_BF16;
+    bool mq = false;                // the verify flag: the multi-position decode kernel
+    const float* kv8 = nullptr;     // {k_scale, v_scale}: K / V go through the shared quantizer into 8-bit slabs
+    bool ctx_hint = false;          // ctx_hint = T (the wave ladder follows the context, as in the model path)
+    bool split_scratch = false;     // the key-split decode form's partial-result scratch and its zeroed tickets
+};
+void attention_op_one(int device, const AttnOpOne& rq, const float* q, const float* k, const float* v, int nH, int nKV, int S, int T,
+                      int hd, float scale, float* out) {
+    OpCtx cx(device, rq.precision);
     nvl_model& m = cx.m;
     const int Tmax = (int)round_up(T, 64);
-    if (m.f32 && Tmax > 12000) return op_fail("nvl_op_attention: T too long for the f32 kernel");
+    if (m.f32 && Tmax > 12000) throw std::runtime_error("nvl_op_attention: T too long for the f32 kernel");
     // token-major Q, slab-layout K and V
-    std::vector<float> qt((size_t)S * nH * hd), kc((size_t)nKV * Tmax * hd, 0.f), vc((size_t)nKV * Tmax * hd, 0.f);
+    const int64_t W = (int64_t)nH * hd;
+    std::vector<float> qt((size_t)(S * W)), kc((size_t)nKV * Tmax * hd, 0.f), vc((size_t)nKV * Tmax * hd, 0.f);
     for (int h = 0; h < nH; h++)
         for (int s = 0; s < S; s++)
             memcpy(&qt[((size_t)s * nH + h) * hd], q + ((size_t)h * S + s) * hd, (size_t)hd * 4);
     for (int h = 0; h < nKV; h++)
-        for (int t = 0; t < T; t++)
-            for (int d = 0; d < hd; d++) {
-                kc[((size_t)h * Tmax + t) * hd + d] = k[((size_t)h * T + t) * hd + d];
-                vc[((size_t)h * Tmax + t) * hd + d] = v[((size_t)h * T + t) * hd + d];
-            }
-    m.q = cx.up_mat(qt.data(), S, (int64_t)nH * hd, false, 1, true);
-    m.kcache = cx.up_mat(kc.data(), 1, (int64_t)kc.size(), false, 1, true);
-    m.vcache = cx.up_mat(vc.data(), 1, (int64_t)vc.size(), false, 1, true);
-    m.attn_out = cx.alloc(round_up(S, 64) * nH * hd * (int64_t)m.wsize);
+        for (int t = 0; t < T; t++) {
+            memcpy(&kc[((size_t)h * Tmax + t) * hd], k + ((size_t)h * T + t) * hd, (size_t)hd * 4);
+            memcpy(&vc[((size_t)h * Tmax + t) * hd], v + ((size_t)h * T + t) * hd, (size_t)hd * 4);
+        }
+    m.q = cx.up_mat(qt.data(), S, W, false, 1, true);
+    m.attn_out = cx.alloc(round_up(S, 64) * W * (int64_t)m.wsize);
     m.nH = nH; m.nKV = nKV; m.group = nH / nKV; m.hd = hd; m.Tmax = Tmax; m.L = 1;
     m.layer_stride = (int64_t)nKV * Tmax * hd; m.slot_stride = m.layer_stride;
     m.attn_scale = scale != 0.f ? scale : 1.0f / std::sqrt((float)hd);
+    if (rq.split_scratch) {
+        m.attn_part = (float*)cx.alloc((int64_t)ATTN_SPLIT_MAX_PAIRS * ATTN_SPLIT_MAX * (hd == 64 ? attn_part_floats<64>() : attn_part_floats<128>()) * 4);
+        m.attn_part_cnt = (int32_t*)cx.alloc(ATTN_SPLIT_MAX_PAIRS * 4);
+        NVL_HIP(hipMemsetAsync(m.attn_part_cnt, 0, ATTN_SPLIT_MAX_PAIRS * 4, m.stream));
+    }
+    if (rq.ctx_hint) m.ctx_hint = T;
     const int32_t meta[5] = {0, S, T - S, 0, 0};      // one sequence whose block table is the single block 0
     int32_t* dmeta = (int32_t*)cx.alloc(20);
     NVL_HIP(hipMemcpyAsync(dmeta, meta, 20, hipMemcpyHostToDevice, m.stream));
     Meta md{};
     md.seq_tok_start = dmeta; md.seq_len = dmeta + 1; md.seq_pos = dmeta + 2; md.seq_tbl = dmeta + 3; md.blk_table = dmeta + 4;
     m.blocks_per_seq = 1;
-    attention(&m, 0, md, 1, S, 0.0);
-    // back to fp32 [nH, S, hd]
-    std::vector<float> ot((size_t)S * nH * hd);
-    if (m.f32) {
-        cx.down(ot.data(), m.attn_out, (int64_t)ot.size());
+    if (rq.kv8) {      // (padding rows: code 0)
+        const uint8_t* k8 = cx.quantize_pool(kc.data(), (int64_t)kc.size(), rq.kv8[0]);
+        const uint8_t* v8 = cx.quantize_pool(vc.data(), (int64_t)vc.size(), rq.kv8[1]);
+        attention_kv8(&m, md, 1, S, k8, v8, rq.kv8[0], rq.kv8[1], rq.mq);
     } else {
-        std::vector<uint16_t> ob((size_t)(round_up(S, 64) * nH * hd));
-        NVL_HIP(hipMemcpyAsync(ob.data(), m.attn_out, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
-        NVL_HIP(hipStreamSynchronize(m.stream));
-        const int64_t W = (int64_t)nH * hd;     // the kernel wrote the next GEMM's fragment-major operand
-        for (int64_t r = 0; r < S; r++)
-            for (int64_t c = 0; c < W; c++) {
-                uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, W)]) << 16;
-                memcpy(&ot[(size_t)(r * W + c)], &u, 4);
-            }
+        m.kcache = cx.up_mat(kc.data(), 1, (int64_t)kc.size(), false, 1, true);
+        m.vcache = cx.up_mat(vc.data(), 1, (int64_t)vc.size(), false, 1, true);
+        attention(&m, 0, md, 1, S, 0.0, false, rq.mq);
     }
+    // back to fp32 [nH, S, hd]
+    std::vector<float> ot((size_t)(S * W));
+    if (m.f32) cx.down(ot.data(), m.attn_out, (int64_t)ot.size());
+    else cx.down_fm(ot.data(), m.attn_out, S, W);
     for (int h = 0; h < nH; h++)
         for (int s = 0; s < S; s++)
             memcpy(out + ((size_t)h * S + s) * hd, &ot[((size_t)s * nH + h) * hd], (size_t)hd * 4);
-    m.q = m.kcache = m.vcache = m.attn_out = nullptr;   // owned by cx.bufs
+}
+
+}  // namespace
+
+extern "C" int nvl_op_attention(int device, int precision, const float* q, const float* k, const float* v, int nH, int nKV,
+                                int S, int T, int hd, float scale, float* out) {
+    if (!q || !k || !v || !out || nH <= 0 || nKV <= 0 || nH % nKV || S <= 0 || T < S || (hd != 64 && hd != 128))
+        return op_fail("nvl_op_attention: bad arguments");
+    OP_TRY
+    AttnOpOne rq;
+    rq.precision = precision;
+    attention_op_one(device, rq, q, k, v, nH, nKV, S, T, hd, scale, out);
     return NVL_OK;
     OP_CATCH
 }
@@ -230,47 +270,9 @@ extern "C" int nvl_op_attention_mq(int device, const float* q, const float* k, c
     if (!q || !k || !v || !out || nH <= 0 || nKV <= 0 || nH % nKV || S < 2 || S > 8 || T < S || (hd != 64 && hd != 128))
         return op_fail("nvl_op_attention_mq: bad arguments");
     OP_TRY
-    OpCtx cx(device, NVL_PRECISION_BF16);
-    nvl_model& m = cx.m;
-    const int Tmax = (int)round_up(T, 64);
-    std::vector<float> qt((size_t)S * nH * hd), kc((size_t)nKV * Tmax * hd, 0.f), vc((size_t)nKV * Tmax * hd, 0.f);
-    for (int h = 0; h < nH; h++)
-        for (int s = 0; s < S; s++)
-            memcpy(&qt[((size_t)s * nH + h) * hd], q + ((size_t)h * S + s) * hd, (size_t)hd * 4);
-    for (int h = 0; h < nKV; h++)
-        for (int t = 0; t < T; t++) {
-            memcpy(&kc[((size_t)h * Tmax + t) * hd], k + ((size_t)h * T + t) * hd, (size_t)hd * 4);
-            memcpy(&vc[((size_t)h * Tmax + t) * hd], v + ((size_t)h * T + t) * hd, (size_t)hd * 4);
-        }
-    m.q = cx.up_mat(qt.data(), S, (int64_t)nH * hd, false, 1, true);
-    m.kcache = cx.up_mat(kc.data(), 1, (int64_t)kc.size(), false, 1, true);
-    m.vcache = cx.up_mat(vc.data(), 1, (int64_t)vc.size(), false, 1, true);
-    m.attn_out = cx.alloc(round_up(S, 64) * nH * hd * 2);
-    m.nH = nH; m.nKV = nKV; m.group = nH / nKV; m.hd = hd; m.Tmax = Tmax; m.L = 1;
-    m.layer_stride = (int64_t)nKV * Tmax * hd; m.slot_stride = m.layer_stride;
-    m.attn_scale = scale != 0.f ? scale : 1.0f / std::sqrt((float)hd);
-    m.ctx_hint = T;                                   // (the wave ladder follows the context, as in the model path)
-    const int32_t meta[5] = {0, S, T - S, 0, 0};      // one sequence whose block table is the single block 0
-    int32_t* dmeta = (int32_t*)cx.alloc(20);
-    NVL_HIP(hipMemcpyAsync(dmeta, meta, 20, hipMemcpyHostToDevice, m.stream));
-    Meta md{};
-    md.seq_tok_start = dmeta; md.seq_len = dmeta + 1; md.seq_pos = dmeta + 2; md.seq_tbl = dmeta + 3; md.blk_table = dmeta + 4;
-    m.blocks_per_seq = 1;
-    attention(&m, 0, md, 1, S, 0.0, false, true);
-    std::vector<float> ot((size_t)S * nH * hd);
-    std::vector<uint16_t> ob((size_t)(round_up(S, 64) * nH * hd));
-    NVL_HIP(hipMemcpyAsync(ob.data(), m.attn_out, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
-    NVL_HIP(hipStreamSynchronize(m.stream));
-    const int64_t W = (int64_t)nH * hd;     // the kernel wrote the next GEMM's fragment-major operand
-    for (int64_t r = 0; r < S; r++)
-        for (int64_t c = 0; c < W; c++) {
-            uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, W)]) << 16;
-            memcpy(&ot[(size_t)(r * W + c)], &u, 4);
-        }
-    for (int h = 0; h < nH; h++)
-        for (int s = 0; s < S; s++)
-            memcpy(out + ((size_t)h * S + s) * hd, &ot[((size_t)s * nH + h) * hd], (size_t)hd * 4);
-    m.q = m.kcache = m.vcache = m.attn_out = nullptr;   // owned by cx.bufs
+    AttnOpOne rq;
+    rq.mq = true; rq.ctx_hint = true;
+    attention_op_one(device, rq, q, k, v, nH, nKV, S, T, hd, scale, out);
     return NVL_OK;
     OP_CATCH
 }
@@ -342,18 +344,8 @@ extern "C" int nvl_op_mamba_mixer(int device, int precision, const float* proj, 
     cx.down(y, y_pre, (int64_t)M * EH);
     cx.down(state, a.state, state_floats * n_slots);
     if (have_tail) cx.down(tail, a.tail, tail_floats * n_slots);
-    if (m.f32) {
-        cx.down(normed, out, (int64_t)M * EH);
-    } else {
-        std::vector<uint16_t> ob((size_t)(Mp * EH));
-        NVL_HIP(hipMemcpyAsync(ob.data(), out, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
-        NVL_HIP(hipStreamSynchronize(m.stream));
-        for (int64_t r = 0; r < M; r++)       // the kernel wrote the out_proj GEMM's fragment-major operand
-            for (int64_t c = 0; c < EH; c++) {
-                uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, EH)]) << 16;
-                memcpy(&normed[(size_t)(r * EH + c)], &u, 4);
-            }
-    }
+    if (m.f32) cx.down(normed, out, (int64_t)M * EH);
+    else cx.down_fm(normed, out, M, EH);       // the kernel wrote the out_proj GEMM's fragment-major operand
     return NVL_OK;
     OP_CATCH
 }
@@ -570,59 +562,10 @@ extern "C" int nvl_op_attention_kv8(int device, const float* q, const float* k, 
     if (!(k_scale > 0.f) || !(v_scale > 0.f) || !std::isfinite(k_scale) || !std::isfinite(v_scale))
         return op_fail("nvl_op_attention_kv8: k_scale / v_scale must be finite and positive");
     OP_TRY
-    OpCtx cx(device, NVL_PRECISION_BF16);
-    nvl_model& m = cx.m;
-    const int Tmax = (int)round_up(T, 64);
-    std::vector<float> qt((size_t)S * nH * hd), kc((size_t)nKV * Tmax * hd, 0.f), vc((size_t)nKV * Tmax * hd, 0.f);
-    for (int h = 0; h < nH; h++)
-        for (int s = 0; s < S; s++)
-            memcpy(&qt[((size_t)s * nH + h) * hd], q + ((size_t)h * S + s) * hd, (size_t)hd * 4);
-    for (int h = 0; h < nKV; h++)
-        for (int t = 0; t < T; t++) {
-            memcpy(&kc[((size_t)h * Tmax + t) * hd], k + ((size_t)h * T + t) * hd, (size_t)hd * 4);
-            memcpy(&vc[((size_t)h * Tmax + t) * hd], v + ((size_t)h * T + t) * hd, (size_t)hd * 4);
-        }
-    m.q = cx.up_mat(qt.data(), S, (int64_t)nH * hd, false, 1, true);
-    // the 8-bit slabs, written by the shared quantizer from the fp32 values (padding rows: code 0)
-    const int64_t n_el = (int64_t)kc.size();
-    const float* dk = cx.up_f32(kc.data(), n_el);
-    const float* dv = cx.up_f32(vc.data(), n_el);
-    uint8_t* k8 = (uint8_t*)cx.alloc(n_el);
-    uint8_t* v8 = (uint8_t*)cx.alloc(n_el);
-    const unsigned qblocks = (unsigned)cdiv(cdiv(n_el, 4), 256);
-    hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dk, n_el, k_scale, k8);
-    hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dv, n_el, v_scale, v8);
-    NVL_HIP(hipGetLastError());
-    m.attn_out = cx.alloc(round_up(S, 64) * nH * hd * 2);
-    m.nH = nH; m.nKV = nKV; m.group = nH / nKV; m.hd = hd; m.Tmax = Tmax; m.L = 1;
-    m.layer_stride = (int64_t)nKV * Tmax * hd; m.slot_stride = m.layer_stride;
-    m.attn_scale = scale != 0.f ? scale : 1.0f / std::sqrt((float)hd);
-    // the key-split decode form needs its partial-result scratch and the context length (as the model path)
-    m.attn_part = (float*)cx.alloc((int64_t)ATTN_SPLIT_MAX_PAIRS * ATTN_SPLIT_MAX * (hd == 64 ? attn_part_floats<64>() : attn_part_floats<128>()) * 4);
-    m.attn_part_cnt = (int32_t*)cx.alloc(ATTN_SPLIT_MAX_PAIRS * 4);
-    NVL_HIP(hipMemsetAsync(m.attn_part_cnt, 0, ATTN_SPLIT_MAX_PAIRS * 4, m.stream));
-    m.ctx_hint = T;
-    const int32_t meta[5] = {0, S, T - S, 0, 0};
-    int32_t* dmeta = (int32_t*)cx.alloc(20);
-    NVL_HIP(hipMemcpyAsync(dmeta, meta, 20, hipMemcpyHostToDevice, m.stream));
-    Meta md{};
-    md.seq_tok_start = dmeta; md.seq_len = dmeta + 1; md.seq_pos = dmeta + 2; md.seq_tbl = dmeta + 3; md.blk_table = dmeta + 4;
-    m.blocks_per_seq = 1;
-    attention_kv8(&m, md, 1, S, k8, v8, k_scale, v_scale);
-    std::vector<float> ot((size_t)S * nH * hd);
-    std::vector<uint16_t> ob((size_t)(round_up(S, 64) * nH * hd));
-    NVL_HIP(hipMemcpyAsync(ob.data(), m.attn_out, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
-    NVL_HIP(hipStreamSynchronize(m.stream));
-    const int64_t W = (int64_t)nH * hd;
-    for (int64_t r = 0; r < S; r++)
-        for (int64_t c = 0; c < W; c++) {
-            uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, W)]) << 16;
-            memcpy(&ot[(size_t)(r * W + c)], &u, 4);
-        }
-    for (int h = 0; h < nH; h++)
-        for (int s = 0; s < S; s++)
-            memcpy(out + ((size_t)h * S + s) * hd, &ot[((size_t)s * nH + h) * hd], (size_t)hd * 4);
-    m.q = m.attn_out = nullptr; m.attn_part = nullptr; m.attn_part_cnt = nullptr;   // owned by cx.bufs
+    const float scales[2] = {k_scale, v_scale};
+    AttnOpOne rq;
+    rq.kv8 = scales; rq.ctx_hint = true; rq.split_scratch = true;
+    attention_op_one(device, rq, q, k, v, nH, nKV, S, T, hd, scale, out);
     return NVL_OK;
     OP_CATCH
 }
@@ -686,13 +629,8 @@ extern "C" int nvl_op_attention_batch_qknorm(int device, int precision, int form
     m.kv8 = kv8; m.kv_esize = kv8 ? 1 : (int)m.wsize;
     uint8_t *k8 = nullptr, *v8 = nullptr;
     if (kv8) {      // the 8-bit blocks, written by the shared quantizer from the fp32 values
-        const float* dk = cx.up_f32(k_pool, n_el);
-        const float* dv = cx.up_f32(v_pool, n_el);
-        k8 = (uint8_t*)cx.alloc(n_el); v8 = (uint8_t*)cx.alloc(n_el);
-        const unsigned qblocks = (unsigned)cdiv(cdiv(n_el, 4), 256);
-        hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dk, n_el, k_scale, k8);
-        hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dv, n_el, v_scale, v8);
-        NVL_HIP(hipGetLastError());
+        k8 = cx.quantize_pool(k_pool, n_el, k_scale);
+        v8 = cx.quantize_pool(v_pool, n_el, v_scale);
     } else {
         m.kcache = cx.up_mat(k_pool, 1, n_el, false, 1, true);
         m.vcache = cx.up_mat(v_pool, 1, n_el, false, 1, true);
@@ -738,18 +676,8 @@ extern "C" int nvl_op_attention_batch_qknorm(int device, int precision, int form
     } catch (...) { release(); throw; }
     for (int i = 0; i < 3; i++) ran[i] = m.attn_ran[i];
     // out: token-major [tokens][nH][hd]
-    if (m.f32) {
-        cx.down(out, m.attn_out, tokens * W);
-    } else {
-        std::vector<uint16_t> ob((size_t)(round_up(tokens, 64) * W));
-        NVL_HIP(hipMemcpyAsync(ob.data(), m.attn_out, ob.size() * 2, hipMemcpyDeviceToHost, m.stream));
-        NVL_HIP(hipStreamSynchronize(m.stream));
-        for (int64_t r = 0; r < tokens; r++)        // the kernel wrote the next GEMM's fragment-major operand
-            for (int64_t c = 0; c < W; c++) {
-                const uint32_t u = ((uint32_t)ob[(size_t)fm_index(r, c, W)]) << 16;
-                memcpy(&out[(size_t)(r * W + c)], &u, 4);
-            }
-    }
+    if (m.f32) cx.down(out, m.attn_out, tokens * W);
+    else cx.down_fm(out, m.attn_out, tokens, W);        // the kernel wrote the next GEMM's fragment-major operand
     std::fill(part_cnt, part_cnt + ATTN_SPLIT_MAX_PAIRS, 0);
     if (m.attn_part_cnt) {
         NVL_HIP(hipMemcpyAsync(part_cnt, m.attn_part_cnt, ATTN_SPLIT_MAX_PAIRS * 4, hipMemcpyDeviceToHost, m.stream));
@@ -865,13 +793,8 @@ extern "C" int nvl_op_qkv_stages(int device, int precision, const nvl_qkv_stages
     m.qkv = (float*)nan_fill((int64_t)M * m.n_qkv * 4);
     m.q = nan_fill(Mq * qw * (int64_t)m.wsize);
     if (kv8) {      // the 8-bit blocks, written by the shared quantizer from the fp32 values
-        const float* dk = cx.up_f32(d->k_pool, n_el);
-        const float* dv = cx.up_f32(d->v_pool, n_el);
-        m.kcache = cx.alloc(n_el); m.vcache = cx.alloc(n_el);
-        const unsigned qblocks = (unsigned)cdiv(cdiv(n_el, 4), 256);
-        hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dk, n_el, d->k_scale, (uint8_t*)m.kcache);
-        hipLaunchKernelGGL(kv8_quant_kernel, dim3(qblocks), dim3(256), 0, m.stream, dv, n_el, d->v_scale, (uint8_t*)m.vcache);
-        NVL_HIP(hipGetLastError());
+        m.kcache = cx.quantize_pool(d->k_pool, n_el, d->k_scale);
+        m.vcache = cx.quantize_pool(d->v_pool, n_el, d->v_scale);
     } else {
         m.kcache = cx.up_mat(d->k_pool, 1, n_el, false, 1, true);
         m.vcache = cx.up_mat(d->v_pool, 1, n_el, false, 1, true);
@@ -1192,11 +1115,7 @@ void moe_op_h(OpCtx& cx, const void* hcopy, int rows, int E, int inter, float* h
         std::fill(h, h + (size_t)rows * K, std::numeric_limits<float>::quiet_NaN());
         return;
     }
-    std::vector<uint16_t> hb((size_t)(64 * K));
-    NVL_HIP(hipMemcpyAsync(hb.data(), hcopy, hb.size() * 2, hipMemcpyDeviceToHost, cx.m.stream));
-    NVL_HIP(hipStreamSynchronize(cx.m.stream));
-    for (int64_t r = 0; r < rows; r++)
-        for (int64_t c = 0; c < K; c++) h[(size_t)(r * K + c)] = bf16_bits_f32(hb[(size_t)fm_index(r, c, K)]);
+    cx.down_fm(h, hcopy, rows, K);      // (the dense forms are decode: 1 .. 64 rows, the buffer's one 64-row group)
 }
 // W~ of the quantized experts as the device holds them after finalize, read through the grouped forms' own dequantize
 // launches (wf_dequant_rows on moe_in / qs_moe_in, dequant_down_experts on moe_out_q / qs_moe_out) into buffers of their

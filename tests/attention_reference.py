@@ -25,6 +25,8 @@ ROUNDED P in the prefill forms (ones . P^T rides the MFMA pipe) and of the unrou
 the running maximum of its own tile order (and per split partial), so the two are different correct roundings of the
 same thing — which is why the ratio of (b) is measured (profiles/attention_op_tests.txt) and not 1.
 f32 precision: 5e-5 of the row's maximum, per row."""
+import contextlib
+
 import numpy as np
 
 GARBAGE_K, GARBAGE_V = 64.0, 1024.0
@@ -181,8 +183,29 @@ MQ_CASES = {
     "M1": _c(pos=(62, 0, 1030), lens=(4, 4, 4), expect=(8, 1)),
     "M2": _c(pos=(62, 0, 1030), lens=(4, 2, 4), expect=(8, 1)),
 }
+# further verify passes, for the test files of the 8-bit and the windowed forms (which add them to ALL_CASES themselves);
+# expect: as decode_attn_cfg chooses for the 8-bit form
+VERIFY_CASES = {
+    "Q1": _c(pos=(62, 0, 1030), lens=(8, 5, 8), expect=(8, 1)),        # group 4: two query tiles in one workgroup, the second ragged
+    "Q2": _c(nH=4, nKV=1, hd=128, block=192, pos=(200,), lens=(3,), expect=(4, 1)),   # hd 128, block no power of two, partial tile
+    "Q3": _c(nH=10, nKV=2, pos=(63, 130), lens=(7, 3), expect=(2, 1)),  # group 5: 35 rows = a two-tile workgroup and a single
+    "Q4": _c(nH=4, nKV=1, hd=128, block=192, pos=(300,), lens=(3,), expect=(8, 1)),   # Q2 behind five key tiles
+}
 ALL_CASES = {**DECODE_CASES, **PREFILL_CASES, **MQ_CASES}
 CENSUS_CASES = ["D1", "D3", "D7", "P1"]
+
+
+@contextlib.contextmanager
+def tuning(gpu, keys):
+    """nvl_set_tuning keys for a block, restored afterwards"""
+    old = {key: gpu.lib().nvl_set_tuning(key, value) for key, value in keys.items()}
+    try:
+        yield
+    finally:
+        for key, value in old.items():
+            gpu.lib().nvl_set_tuning(key, value)
+
+
 KV8_SCALES = (2.0 ** -4, 2.0 ** -5)          # k_scale, v_scale of the random batches (+-28 / +-14 before saturation)
 CENSUS_KV8_SCALES = (1.0, 4.0)               # marks (1 -> code 0.25) and the garbage (1024 -> code 256) stay exact
 ROPE_BASE = 10000.0

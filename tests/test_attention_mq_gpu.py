@@ -25,7 +25,7 @@ SHAPES = [(8, 2, 4, 66, 64),      # P = 62: the new keys straddle the first tile
           (8, 2, 4, 68, 128),     # hd 128
           (8, 2, 4, 2104, 64),    # several rounds per wave
           (4, 1, 3, 700, 128)]    # long context, hd 128
-CASES = [(s, 0) for s in SHAPES] + [(s, nw) for s in SHAPES if s[3] in (66, 2104) for nw in (2, 4, 8)]
+CASES = [(s, 0) for s in SHAPES] + [(s, nw) for s in SHAPES if s[3] in (66, 68, 2104) for nw in (2, 4, 8)]      # (68: hd 128)
 
 _REF = {}
 

@@ -3,8 +3,6 @@ ops.attention_batch(form="mq_kv8") against the float64 statement of tests/attent
 and through a tiny model's verify_greedy.  Bounds (a) / (b) and the census are that file's; RATIO follows
 test_attention_ops_gpu.py's rule: 1.25 x the largest device / emulation rms ratio measured on the MI355X over the cases of
 this file where that exceeds ATTN_RATIO_BOUND = 1.550, never above 2 (profiles/attention_mq_kv8_tests.txt)."""
-import contextlib
-
 import numpy as np
 import pytest
 
@@ -15,31 +13,16 @@ pytestmark = pytest.mark.gpu
 RATIO = 1.550                    # the largest measured ratio, 1.25 x it and the choice: profiles/attention_mq_kv8_tests.txt
 FP8_KV_TOL = 1e-1                # tests/test_spec_decode_gpu.py: the 8-bit cache's stated logits tolerance
 
-# expect = (waves per workgroup, workgroups per (sequence, kv head)) as decode_attn_cfg chooses them for the 8-bit form
-R.ALL_CASES.update({
-    "Q1": R._c(pos=(62, 0, 1030), lens=(8, 5, 8), expect=(8, 1)),        # group 4: two query tiles in one workgroup, the second ragged
-    "Q2": R._c(nH=4, nKV=1, hd=128, block=192, pos=(200,), lens=(3,), expect=(4, 1)),   # hd 128, block no power of two, partial tile
-    "Q3": R._c(nH=10, nKV=2, pos=(63, 130), lens=(7, 3), expect=(2, 1)),  # group 5: 35 rows = a two-tile workgroup and a single
-})
+R.ALL_CASES.update(R.VERIFY_CASES)       # Q1 - Q3
 CASES = ["M1", "M2", "Q1", "Q2", "Q3"]
 TWO = {40: 2}                    # nvl_set_tuning key 40: two query tiles per workgroup whatever the grid size (Q1, Q3: these small
                                  # grids take one by default)
 
 
-@contextlib.contextmanager
-def tuning(gpu, keys):
-    old = {key: gpu.lib().nvl_set_tuning(key, value) for key, value in keys.items()}
-    try:
-        yield
-    finally:
-        for key, value in old.items():
-            gpu.lib().nvl_set_tuning(key, value)
-
-
 def run(gpu, b, keys=None, **over):
     a = dict(form="mq_kv8", k_scale=b["k_scale"], v_scale=b["v_scale"])
     a.update(over)
-    with tuning(gpu, keys or {}):
+    with R.tuning(gpu, keys or {}):
         return gpu.ops.attention_batch(b["q"], b["k_pool"], b["v_pool"], b["table"], b["seq_len"], b["seq_pos"], b["nH"], **a)
 
 
@@ -59,6 +42,11 @@ def test_verify_pass_kv8(gpu, name):
         ran_as(two, b["expect"], (name, TWO))
         R.check_bf16(b, two, RATIO, "key 40 = 2")
         assert np.array_equal(two["out"], res["out"]), (name, "key 40")
+    if name in ("M1", "Q2"):     # one tile per workgroup at the wave counts its context does not take: 4 at hd 64; 2 and 8 at hd 128
+        for nw in {"M1": (4,), "Q2": (2, 8)}[name]:
+            forced = run(gpu, b, keys={15: nw})
+            ran_as(forced, (nw, 1), (name, "key 15", nw))
+            R.check_bf16(b, forced, RATIO, f"key 15 = {nw}")
 
 
 def test_wave_counts_and_load_policy(gpu):
@@ -107,7 +95,7 @@ def test_model_verify_takes_the_kernel(gpu):
         rows, targets = r.integers(0, V, (2, 1 + k)).astype(np.int32), r.integers(0, V, 2 * (1 + k)).astype(np.int32)
         lps = {}
         for key38, ran in ((1, "decode_mq_kv8"), (0, "prefill_kv8")):
-            with tuning(gpu, {38: key38}):
+            with R.tuning(gpu, {38: key38}):
                 for i, p in enumerate(prompts):
                     hm.seq_reset(i)
                     hm.forward_batch([i], [p], [0], want_logits=False)

@@ -83,10 +83,11 @@ def test_decode(gpu, name, form):
         assert not res["part_cnt"].any()
 
 
-@pytest.mark.parametrize("name", ["D1", "D2"])
+@pytest.mark.parametrize("name", ["D1", "D2", "D4"])
 def test_decode_wave_counts_and_load_policy(gpu, name):
     """nvl_set_tuning key 15 (2 / 4 / 8 waves per workgroup, which also turns the key split off) under both bounds; key 35
-    (non-temporal K/V loads never / always) changes no bit"""
+    (non-temporal K/V loads never / always) changes no bit.  D4: the head_dim 128 instantiations, which take 4 and 8 waves
+    in no other case of this file"""
     for form in DECODE_FORMS:
         b = R.batch(name, form)
         for nw in (2, 4, 8):

@@ -13,15 +13,28 @@ pytestmark = pytest.mark.gpu
 WINDOW_RATIO_BOUND = 1.550       # the largest measured ratio is below 1.24: test_attention_ops_gpu.py's ATTN_RATIO_BOUND
 CASES = ([(n, f) for n in ("D1", "D2", "D3", "D4", "D5", "D7") for f in ("plain", "fused", "kv8")] +
          [(n, f) for n in ("P1", "P2", "P3") for f in ("plain", "kv8")] + [(n, f) for n in ("M1", "M2") for f in ("mq", "mq_kv8")])
-RAN = {"plain": "decode", "fused": "decode_fused", "kv8": "decode_kv8", "mq": "decode_mq", "mq_kv8": "decode_mq_kv8"}
+RAN = {"plain": "decode", "fused": "decode_fused", "kv8": "decode_kv8", "mq": "decode_mq", "mq_kv8": "decode_mq_kv8",
+       "mq_kv8_two": "decode_mq_kv8"}
+WINDOWS = [1, 64, 65, 100, 192]
+# The launch shape follows the keys a workgroup reads, min(context, W + 63): the windows above are at most four tiles, which is
+# two waves at head_dim 64 and two or four at 128.  The WINDOW instantiations they leave unreached, with the shape
+# (waves, workgroups per (sequence, kv head)) decode_attn_cfg gives them: the one-position forms at 8 and 6 - 9 tiles; the
+# verify forms at 6 tiles, at head_dim 128 (Q4) and with two query tiles per workgroup (Q1, form "mq_kv8_two": the 8-bit
+# verify form under nvl_set_tuning key 40 = 2).
+R.ALL_CASES.update(R.VERIFY_CASES)
+SHAPES = {("D2", 500): (8, 1), ("D4", 500): (8, 1), ("D7", 500): (4, 1), ("M1", 300): (4, 1),
+          ("Q4", 1): (2, 1), ("Q4", 100): (4, 1), ("Q4", 500): (8, 1), ("Q1", 100): (2, 1), ("Q1", 300): (4, 1), ("Q1", 500): (8, 1)}
+MORE = ([(n, f, 500) for n in ("D2", "D4", "D7") for f in ("plain", "fused", "kv8")] + [("M1", f, 300) for f in ("mq", "mq_kv8")] +
+        [("Q4", f, w) for f in ("mq", "mq_kv8") for w in (1, 100, 500)] + [("Q1", "mq_kv8_two", w) for w in (100, 300, 500)])
 _REFS = {}
 
 
 def run(gpu, name, form, window, precision="bf16"):      # (the verify forms: the plain / kv8 batch under the verify flag)
-    b = R.batch(name, {"mq": "plain", "mq_kv8": "kv8"}.get(form, form))
-    return b, gpu.ops.attention_batch(b["q"], b["k_pool"], b["v_pool"], b["table"], b["seq_len"], b["seq_pos"], b["nH"], form=form,
-                                      rope_base=b["rope_base"], max_seq=b["max_seq"], k_scale=b.get("k_scale", 1.0),
-                                      v_scale=b.get("v_scale", 1.0), precision=precision, window=window)
+    b = R.batch(name, {"mq": "plain", "mq_kv8": "kv8", "mq_kv8_two": "kv8"}.get(form, form))
+    with R.tuning(gpu, {40: 2} if form == "mq_kv8_two" else {}):
+        return b, gpu.ops.attention_batch(b["q"], b["k_pool"], b["v_pool"], b["table"], b["seq_len"], b["seq_pos"], b["nH"],
+                                          form=form.replace("_two", ""), rope_base=b["rope_base"], max_seq=b["max_seq"],
+                                          k_scale=b.get("k_scale", 1.0), v_scale=b.get("v_scale", 1.0), precision=precision, window=window)
 
 
 def references(b, window):
@@ -54,11 +67,12 @@ def check(b, res, window, tag):
     assert top <= WINDOW_RATIO_BOUND, (tag, "rms ratio", top)
 
 
-@pytest.mark.parametrize("window", [1, 64, 65, 100, 192])
-@pytest.mark.parametrize("name,form", CASES)
+@pytest.mark.parametrize("name,form,window", [(n, f, w) for w in WINDOWS for n, f in CASES] + MORE)
 def test_window(gpu, name, form, window):
     b, res = run(gpu, name, form, window)
     assert res["ran"] == (RAN[form] if name[0] != "P" else {"plain": "prefill", "kv8": "prefill_kv8"}[form]), (name, form, res["ran"])
+    if (name, form, window) in MORE:
+        assert (res["nw"], res["nsplit"]) == SHAPES[name, window], (name, form, window, res["nw"], res["nsplit"])
     check(b, res, window, f"{name} {form} W={window}")
     if form == "fused":
         R.check_append(b, res)
