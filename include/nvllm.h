@@ -1065,6 +1065,27 @@ typedef struct nvl_dense_stages {
     float *x1, *op1, *rs1, *h, *x2, *op2, *rs2, *yn, *x_end;
     int32_t* ran;
 } nvl_dense_stages;
+/* nvl_dense_stages with the WEIGHTS' storage format behind it: nvl_op_dense_stages takes either struct and tells them apart by
+ * struct_bytes (the shorter one: bf16 weights, bit for bit).  A quantized format builds the layer the way a model gets it: wo,
+ * w1, w2 (and wn, see quantize_next) through the upload quantizer of the format, then nvl_finalize's own code — the SwiGLU
+ * interleave of W1's codes and scales with its pad rows, the registration for the decode dispatch, the tile path's dequantize
+ * scratch —, and layer_tail() then takes the model's decisions on the kernels of that format.  ran[] keeps its codes.
+ * weight_format: NVL_OP_EXPERTS_* (the codes of the *_q entry points below); group_size: INT4 only (32, 64 or 128, dividing
+ * hidden, q_width and ffn), else 0.  quantize_next: is wn quantized too?  -1 = what a model does — with has_next wn is the next
+ * layer's QKV projection, which is quantized; the last layer's LM head is quantized under fp8, bf16 under MXFP4 (the head is
+ * opt-in there, nvl_set_mx_head_dtype) and always bf16 under INT4 —, 0 / 1 = no / yes (1 on an INT4 head or with bf16 weights:
+ * NVL_ERR_INVALID).  wt_o [hidden][q_width], wt_1 [2 ffn or ffn][hidden] (canonical order: gate rows, then up rows), wt_2
+ * [hidden][ffn], wt_n [n_next][hidden], each optional (NULL): W~ of the weight as the device holds it after finalize, read back
+ * through the tile path's dequantize kernel and de-interleaved.  A wt_* with a weight that stays bf16, an unknown format,
+ * NVL_PRECISION_F32, a bad group size or any other struct_bytes are NVL_ERR_INVALID before a device is touched. */
+typedef struct nvl_dense_stages_q {
+    nvl_dense_stages s;             /* s.struct_bytes = sizeof(nvl_dense_stages_q) */
+    int32_t weight_format;
+    int32_t group_size;
+    int32_t quantize_next;
+    int32_t pad;
+    float *wt_o, *wt_1, *wt_2, *wt_n;
+} nvl_dense_stages_q;
 int nvl_op_dense_stages(int device, int precision, const nvl_dense_stages* io);
 /* The same tail with the MoE block of moe.go:43-128 between the projections, decode only (rows <= 64; RMSNorm, sequential
  * block): the O projection carries the FFN norm, the router and the expert up projection read the deferred operand

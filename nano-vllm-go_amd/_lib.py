@@ -120,6 +120,11 @@ class DenseStagesC(C.Structure):      # nvl_dense_stages
                                            "ran")])
 
 
+class DenseStagesQC(C.Structure):     # nvl_dense_stages_q
+    _fields_ = ([("s", DenseStagesC)] + [(n, C.c_int32) for n in ("weight_format", "group_size", "quantize_next", "pad")] +
+                [(n, C.c_void_p) for n in ("wt_o", "wt_1", "wt_2", "wt_n")])
+
+
 class QkvStagesC(C.Structure):        # nvl_qkv_stages
     _fields_ = ([(n, C.c_int32) for n in ("struct_bytes", "kv8", "nH", "nKV", "hd", "hidden", "n_seqs", "tbl_stride", "n_blocks",
                                           "block_size", "max_seq", "norm_type", "vocab", "pos_rows")] +

@@ -897,6 +897,15 @@ void finalize_q_experts(nvl_model* m, LayerW& l, std::vector<int32_t>& idx, int6
     for (int k : {NVL_T_MOE_IN, NVL_T_MOE_OUT}) { dfree(l.t[k].p); l.t[k].p = nullptr; dfree(l.t[k].qs); l.t[k].qs = nullptr; }
 }
 
+// a finalized quantized projection weight (codes p, scales qs, format m->wf) by code pointer, for gemm()'s dispatch -> the
+// elements its W~ needs of the tile path's dequantize scratch: all of its padded rows, or, in_chunks (the LM head, which the
+// tile path runs in row chunks), one row tile.  nvl_finalize and ops_impl.h nvl_op_dense_stages both register through it.
+int64_t register_q_weight(nvl_model* m, const void* p, const void* qs, int64_t rows, int64_t K, bool in_chunks = false) {
+    if (!p || !qs) return 0;
+    m->qmap[p] = nvl_model::QRef{m->wf, qs, round_up(rows, W_ROW_PAD)};
+    return (in_chunks ? W_ROW_PAD : round_up(rows, W_ROW_PAD)) * K;
+}
+
 // quantized experts after finalize_q_experts: the codes by pointer (decode dispatch), and the scratch of one layer's W~ (up,
 // then down) for the grouped GEMMs, zeroed
 void register_q_experts(nvl_model* m, const LayerW* layers, size_t n_layers, int64_t E, int64_t I) {
@@ -1094,19 +1103,14 @@ extern "C" int nvl_finalize(nvl_model* m) {
     m->lm_head = head.p;
     if (m->wf != WF_BF16) {   // the quantized weights by code pointer (gemm() dispatch) and the dequantize scratch of the tile path
         int64_t big = 0;
-        auto reg = [&](const void* p, const void* qs, int64_t rows, int64_t K) {
-            if (!p || !qs) return;
-            m->qmap[p] = nvl_model::QRef{m->wf, qs, round_up(rows, W_ROW_PAD)};
-            big = std::max(big, round_up(rows, W_ROW_PAD) * K);
+        auto reg = [&](const void* p, const void* qs, int64_t rows, int64_t K, bool in_chunks = false) {
+            big = std::max(big, register_q_weight(m, p, qs, rows, K, in_chunks));
         };
         for (auto& l : m->layers) {
             reg(l.w_qkv, l.qs_qkv, l.n_qkv, H); reg(l.w1, l.qs1, l.n1, H);
             reg(l.t[NVL_T_WO].p, l.t[NVL_T_WO].qs, H, l.t[NVL_T_WO].cols); reg(l.t[NVL_T_W2].p, l.t[NVL_T_W2].qs, H, l.t[NVL_T_W2].cols);
         }
-        if (head.qs) {   // (fp8, or MXFP4 with nvl_set_mx_head_dtype; at least one row tile of the LM head: it runs in chunks)
-            m->qmap[head.p] = nvl_model::QRef{m->wf, head.qs, round_up(m->V, W_ROW_PAD)};
-            big = std::max(big, W_ROW_PAD * H);
-        }
+        reg(head.p, head.qs, m->V, H, true);   // (fp8, or MXFP4 with nvl_set_mx_head_dtype)
         m->wq_scratch_elems = big;
         if (big) m->wq_scratch = dmalloc<bf16_t>(big);
         // quantized experts: the codes by pointer (decode dispatch), and the scratch of one layer's W~ (up, then down)

@@ -1228,6 +1228,9 @@ extern "C" int nvl_op_moe_stages(int device, int precision, const float* x, cons
 // xn_last), every scratch buffer and every output 0xFF bytes (NaN as bf16 and as fp32) beforehand.  Between the launches a
 // StageHook copies what the next launch will read; a residual add still pending is completed by tap_hidden_kernel into the
 // copy, as tap_layer does, and stays pending for the norm that consumes it in the model.
+// nvl_dense_stages_q (told apart by struct_bytes): the weights in a quantized format — uploaded, fused and registered as
+// nvl_finalize does it (upload_2d_q, fuse_w1, register_q_weight; m.wf as a model's) —, so gemm() sends every projection of
+// the same layer_tail() to the kernels of that format; W~ read back through wf_dequant_rows.
 namespace {
 struct DenseTap {
     nvl_model* m; int M;
@@ -1254,8 +1257,10 @@ struct DenseTap {
 }  // namespace
 
 extern "C" int nvl_op_dense_stages(int device, int precision, const nvl_dense_stages* d) {
-    if (!d || precision != NVL_PRECISION_BF16 || d->struct_bytes != (int32_t)sizeof(nvl_dense_stages))
-        return op_fail("nvl_op_dense_stages: bad arguments (bf16 only; struct_bytes = sizeof(nvl_dense_stages))");
+    if (!d || precision != NVL_PRECISION_BF16 ||
+        (d->struct_bytes != (int32_t)sizeof(nvl_dense_stages) && d->struct_bytes != (int32_t)sizeof(nvl_dense_stages_q)))
+        return op_fail("nvl_op_dense_stages: bad arguments (bf16 precision only; struct_bytes = sizeof(nvl_dense_stages) or sizeof(nvl_dense_stages_q))");
+    const nvl_dense_stages_q* dq = d->struct_bytes == (int32_t)sizeof(nvl_dense_stages_q) ? (const nvl_dense_stages_q*)d : nullptr;
     const int M = d->rows, H = d->hidden, qw = d->q_width, F = d->ffn, Nn = d->n_next, nl = d->n_last_rows;
     const bool swiglu = d->activation_type == NVL_ACT_SWIGLU, last = !d->has_next;
     if (!d->x || !d->attn_out || !d->wo || !d->norm_w || !d->w1 || !d->w2 || !d->next_norm_w || !d->wn || !d->x1 || !d->op1 || !d->rs1 ||
@@ -1275,6 +1280,20 @@ extern "C" int nvl_op_dense_stages(int device, int precision, const nvl_dense_st
     for (int i = 0; last && i < nl; i++)
         if (d->last_rows[i] < 0 || d->last_rows[i] >= M) return op_fail("nvl_op_dense_stages: last_rows out of range", NVL_ERR_POSITION);
     if (d->max_len == 1 && last && nl != M) return op_fail("nvl_op_dense_stages: a decode pass keeps every row (n_last_rows = rows)");
+    // the weights' format (nvl_dense_stages_q) and whether wn follows it (quantize_next = -1: as wfmt.h wf_covers answers for a model)
+    int wf = WF_BF16;
+    bool q_next = false;
+    if (dq) {
+        wf = moe_op_wf(dq->weight_format, dq->group_size, H, F);
+        if (wf < 0 || (wf_base(wf) == WF_INT4 && qw % dq->group_size))
+            return op_fail("nvl_op_dense_stages: unknown weight format, or INT4 weights whose group size is not 32, 64 or 128 or does not divide hidden, q_width and ffn");
+        if (dq->quantize_next < -1 || dq->quantize_next > 1) return op_fail("nvl_op_dense_stages: quantize_next is -1, 0 or 1");
+        q_next = dq->quantize_next < 0 ? wf != WF_BF16 && (!last || wf == WF_FP8) : dq->quantize_next == 1;
+        if (q_next && (wf == WF_BF16 || (last && wf_base(wf) == WF_INT4)))
+            return op_fail("nvl_op_dense_stages: quantize_next = 1 needs a quantized format, and an INT4 model keeps its LM head bf16");
+        if ((wf == WF_BF16 && (dq->wt_o || dq->wt_1 || dq->wt_2)) || (!q_next && dq->wt_n))
+            return op_fail("nvl_op_dense_stages: wt_o / wt_1 / wt_2 / wt_n are the read-back of quantized weights");
+    }
     OP_TRY
     OpCtx cx(device, precision);
     nvl_model& m = cx.m;
@@ -1299,26 +1318,57 @@ extern "C" int nvl_op_dense_stages(int device, int precision, const nvl_dense_st
     m.rs_part = (float*)nan_fill(rs_floats * 4);
     // weights (finalize's forms)
     LayerW l;
-    l.t[NVL_T_WO].p = cx.up_mat(d->wo, H, qw, false, W_ROW_PAD);
     if (d->bo) l.t[NVL_T_BO].p = cx.up_f32(d->bo, H);
     l.t[NVL_T_FFN_NORM_W].p = cx.up_f32(d->norm_w, H);
     if (d->norm_b) l.t[NVL_T_FFN_NORM_B].p = cx.up_f32(d->norm_b, H);
     const int n1 = swiglu ? 2 * F : F;
-    void* w1c = cx.up_mat(d->w1, n1, H, false, W_ROW_PAD);       // canonical [n1][H] (gate rows | up rows)
-    if (swiglu) {
-        auto idx = swiglu_interleave(F, 0);
-        idx.resize((size_t)round_up(n1, W_ROW_PAD), -1);
-        l.w1 = cx.alloc((int64_t)idx.size() * H * 2);
-        gather_rows(&m, w1c, idx, l.w1, H);
+    DevTensor tn;      // wn, when it is quantized
+    if (wf != WF_BF16) {
+        // a quantized layer as a model gets it: the upload quantizer per tensor, then finalize's own fuse_w1() (the SwiGLU
+        // interleave of codes and scales) and register_q_weight() (gemm()'s dispatch, the tile path's scratch)
+        m.wf = wf;
+        auto up_q = [&](DevTensor& t, const float* w, int64_t N, int64_t K) {
+            upload_2d_q(&m, &t, wf, w, NVL_DTYPE_F32, N, K, false);
+            cx.bufs.push_back(t.p); cx.bufs.push_back(t.qs);
+        };
+        up_q(l.t[NVL_T_WO], d->wo, H, qw);
+        up_q(l.t[NVL_T_W2], d->w2, H, F);
+        if (q_next) up_q(tn, d->wn, Nn, H);
+        DevTensor& t1 = l.t[NVL_T_W1];
+        l.n1 = n1;
+        try {
+            upload_2d_q(&m, &t1, wf, d->w1, NVL_DTYPE_F32, n1, H, false);
+            fuse_w1(&m, l, swiglu);
+        } catch (...) {
+            for (void* p : {t1.p, t1.qs, l.w1, l.qs1}) dfree(p);
+            t1.p = t1.qs = l.w1 = l.qs1 = nullptr;
+            throw;
+        }
+        cx.bufs.push_back(l.w1); cx.bufs.push_back(l.qs1);
+        int64_t big = register_q_weight(&m, l.t[NVL_T_WO].p, l.t[NVL_T_WO].qs, H, qw);
+        big = std::max(big, register_q_weight(&m, l.w1, l.qs1, n1, H));
+        big = std::max(big, register_q_weight(&m, l.t[NVL_T_W2].p, l.t[NVL_T_W2].qs, H, F));
+        big = std::max(big, register_q_weight(&m, tn.p, tn.qs, Nn, H, last));      // (has_next: a QKV projection; else the LM head)
+        m.wq_scratch_elems = big;
+        m.wq_scratch = (bf16_t*)cx.alloc(big * 2);
     } else {
-        l.w1 = w1c;
+        l.t[NVL_T_WO].p = cx.up_mat(d->wo, H, qw, false, W_ROW_PAD);
+        void* w1c = cx.up_mat(d->w1, n1, H, false, W_ROW_PAD);       // canonical [n1][H] (gate rows | up rows)
+        if (swiglu) {
+            auto idx = swiglu_interleave(F, 0);
+            idx.resize((size_t)round_up(n1, W_ROW_PAD), -1);
+            l.w1 = cx.alloc((int64_t)idx.size() * H * 2);
+            gather_rows(&m, w1c, idx, l.w1, H);
+        } else {
+            l.w1 = w1c;
+        }
+        l.t[NVL_T_W2].p = cx.up_mat(d->w2, H, F, false, W_ROW_PAD);
     }
     if (d->b1) l.t[NVL_T_B1].p = cx.up_f32(d->b1, F);
-    l.t[NVL_T_W2].p = cx.up_mat(d->w2, H, F, false, W_ROW_PAD);
     if (d->b2) l.t[NVL_T_B2].p = cx.up_f32(d->b2, H);
     m.g[NVL_T_FINAL_NORM_W].p = cx.up_f32(d->next_norm_w, H);     // (the norm after the layer, whichever it is)
     if (d->next_norm_b) m.g[NVL_T_FINAL_NORM_B].p = cx.up_f32(d->next_norm_b, H);
-    void* wn = cx.up_mat(d->wn, Nn, H, false, W_ROW_PAD);
+    void* wn = q_next ? tn.p : cx.up_mat(d->wn, Nn, H, false, W_ROW_PAD);
     const int ldn = (int)round_up(Nn, 128);
     float* yn = (float*)nan_fill(round_up(rows_out, 64) * (int64_t)ldn * 4);
     int32_t* rows_idx = nullptr;
@@ -1386,8 +1436,32 @@ extern "C" int nvl_op_dense_stages(int device, int precision, const nvl_dense_st
     }
     for (int i = 0; i < NVL_DENSE_RAN_INTS; i++) d->ran[i] = m.dense_ran[i];
     d->ran[NVL_DENSE_RAN_RS1_TILES] = tap.rs1_tiles; d->ran[NVL_DENSE_RAN_RS2_TILES] = rs2_tiles;
-    for (auto& t : l.t) t.p = nullptr;
-    l.w1 = nullptr;
+    // W~ of a quantized weight as the device holds it after finalize, through the tile path's dequantize launch into a buffer
+    // of its own; idx: device row j holds canonical row idx[j] (W1 under the SwiGLU interleave)
+    auto read_wt = [&](float* dst, const void* codes, const void* qs, int64_t rows, int64_t K, const std::vector<int32_t>* idx) {
+        if (!dst) return;
+        const int64_t np = round_up(rows, W_ROW_PAD);
+        bf16_t* dv = (bf16_t*)cx.alloc(np * K * 2);
+        wf_dequant_rows(m.stream, wf, codes, qs, K, 0, np, dv);
+        NVL_HIP(hipGetLastError());
+        std::vector<uint16_t> hb((size_t)(np * K));
+        NVL_HIP(hipMemcpyAsync(hb.data(), dv, hb.size() * 2, hipMemcpyDeviceToHost, m.stream));
+        NVL_HIP(hipStreamSynchronize(m.stream));
+        for (int64_t j = 0; j < rows; j++) {
+            float* row = dst + (size_t)((idx ? (*idx)[(size_t)j] : j) * K);
+            for (int64_t c = 0; c < K; c++) row[c] = bf16_bits_f32(hb[(size_t)fm_index(j, c, K)]);
+        }
+    };
+    if (dq && wf != WF_BF16) {
+        const std::vector<int32_t> idx = swiglu_interleave(F, 0);
+        read_wt(dq->wt_o, l.t[NVL_T_WO].p, l.t[NVL_T_WO].qs, H, qw, nullptr);
+        read_wt(dq->wt_1, l.w1, l.qs1, n1, H, swiglu ? &idx : nullptr);
+        read_wt(dq->wt_2, l.t[NVL_T_W2].p, l.t[NVL_T_W2].qs, H, F, nullptr);
+        if (q_next) read_wt(dq->wt_n, tn.p, tn.qs, Nn, H, nullptr);
+    }
+    m.qmap.clear(); m.wq_scratch = nullptr; m.wq_scratch_elems = 0;
+    for (auto& t : l.t) { t.p = nullptr; t.qs = nullptr; }
+    l.w1 = nullptr; l.qs1 = nullptr;
     m.g[NVL_T_FINAL_NORM_W].p = nullptr; m.g[NVL_T_FINAL_NORM_B].p = nullptr;
     m.x = nullptr; m.attn_out = m.xn = m.hbuf = m.xn_last = nullptr; m.sk_part = m.rs_part = nullptr;
     m.pending_part = nullptr; m.pending_slices = 0;

@@ -288,13 +288,21 @@ NORM_RAN = {0: None, 1: "row", 2: "row_idx", 3: "tile16", 4: "wave"}            
 
 def dense_stages(x, attn_out, wo, norm_w, w1, w2, next_norm_w, wn, bo=None, norm_b=None, b1=None, b2=None, next_norm_b=None,
                  norm="rms", act="swiglu", block="sequential", residual_multiplier=0.0, attention_multiplier=0.0, norm_eps=1e-5,
-                 max_len=1, last_rows=None, has_next=True, precision="bf16", device=0):   # generic_model.go:320-418
-    """The dense layer tail as a layer of the model runs it, stage by stage (nvl_op_dense_stages; bf16 only).  x [M][H],
+                 max_len=1, last_rows=None, has_next=True, precision="bf16", device=0, weight_format="bf16", group_size=0,
+                 quantize_next=None):   # generic_model.go:320-418
+    """The dense layer tail as a layer of the model runs it, stage by stage (nvl_op_dense_stages; bf16 precision).  x [M][H],
     attn_out [M][qw], wo [H][qw], w1 [2F][H] (gate rows | up rows; GELU: [F][H]), w2 [H][F], wn [Nn][H]; has_next=False is
     the last layer: last_rows (default: every row, a decode pass) feed the final norm and wn as the LM head.
     -> dict(x1, op1, rs1 (None = op1 is already normalised, else the x^2 partials [M][tiles]), h, x2, op2, rs2, yn, x_end,
     ran = dict(o=..., down=..., norms, rs1_tiles, rs2_tiles) with o / down = dict(producer, half, form (a RESID_FORMS
-    name), slices, consumer (a NORM_RAN name)))."""
+    name), slices, consumer (a NORM_RAN name))).
+    weight_format "fp8" | "mxfp4" | "int4" (an EXPERT_FORMATS name; group_size 32 / 64 / 128 for INT4): wo, w1, w2 quantized
+    and finalized as a model's (nvl_dense_stages_q), and wn too when quantize_next says so (None: what a model does — the next
+    layer's QKV yes, the LM head under fp8 only); the dict then also holds wt_o, wt_1, wt_2, wt_n: W~ as the device holds it
+    ([out][in], W1 in canonical gate-then-up order; wt_n None where wn stayed bf16).  With "bf16" and quantize_next None the
+    shorter struct is sent and nothing else changes."""
+    if weight_format not in EXPERT_FORMATS:
+        raise ValueError(f"weight_format must be one of {sorted(EXPERT_FORMATS)}")
     x, attn_out, wo, norm_w, w1, w2, next_norm_w, wn = (_f(a) for a in (x, attn_out, wo, norm_w, w1, w2, next_norm_w, wn))
     opt = [None if a is None else _f(a) for a in (bo, norm_b, b1, b2, next_norm_b)]
     M, H = x.shape
@@ -322,7 +330,21 @@ def dense_stages(x, attn_out, wo, norm_w, w1, w2, next_norm_w, wn, bo=None, norm
                 next_norm_w=next_norm_w, next_norm_b=opt[4], wn=wn, last_rows=lr, ran=ran, **out)
     for k, v in keep.items():
         setattr(d, k, None if v is None else v.ctypes.data)
-    L.check(L.lib().nvl_op_dense_stages(device, L.PRECISION[precision], C.byref(d)))
+    if weight_format == "bf16" and not group_size and quantize_next is None:
+        L.check(L.lib().nvl_op_dense_stages(device, L.PRECISION[precision], C.byref(d)))
+    else:
+        quantized = weight_format != "bf16"
+        q_next = (quantized and (has_next or weight_format == "fp8")) if quantize_next is None else bool(quantize_next)
+        wt = dict(wt_o=nan(*wo.shape), wt_1=nan(*w1.shape), wt_2=nan(*w2.shape)) if quantized else {}
+        if q_next and quantized:
+            wt["wt_n"] = nan(*wn.shape)
+        d.struct_bytes = C.sizeof(L.DenseStagesQC)
+        whole = L.DenseStagesQC(s=d, weight_format=EXPERT_FORMATS[weight_format], group_size=int(group_size),
+                                quantize_next=-1 if quantize_next is None else int(bool(quantize_next)),
+                                **{k: v.ctypes.data for k, v in wt.items()})
+        L.check(L.lib().nvl_op_dense_stages(device, L.PRECISION[precision], C.cast(C.byref(whole), C.POINTER(L.DenseStagesC))))
+        out.update(wt_o=None, wt_1=None, wt_2=None, wt_n=None)
+        out.update(wt)
     t1, t2 = int(ran[12]), int(ran[13])
     out["rs1"] = out["rs1"][:, :t1].copy() if t1 else None
     out["rs2"] = out["rs2"][:, :t2].copy() if t2 else None

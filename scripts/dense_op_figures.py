@@ -3,7 +3,11 @@ family) whether what ran matches the case's literals, whether every check of den
 stage (x1, the FFN-up operand, h, x2, the next operand, yn) the largest per-row ratio rms(dev - f64) / rms(emulated - f64)
 of the random family, each reference fed the device's output of the stage before.  Stops at the first error that is not
 a failed assertion (a device error: nothing more is launched after one).
-Usage: python scripts/dense_op_figures.py [output file, default profiles/dense_op_tests.txt]"""
+With `q` as the first argument: the same table for tests/test_dense_q_ops_gpu.py — the quantized weight formats, per (case,
+family, format, INT4 group), plus whether W~ read back equals the mirror —, kept in profiles/dense_q_op_tests.txt, written
+line by line so that a run cut short leaves what it measured.
+Usage: python scripts/dense_op_figures.py [output file, default profiles/dense_op_tests.txt]
+       python scripts/dense_op_figures.py q [output file, default profiles/dense_q_op_tests.txt]"""
 import importlib
 import sys
 from pathlib import Path
@@ -16,6 +20,51 @@ gpu = importlib.import_module("nano-vllm-go_amd")
 assert gpu.lib().nvl_device_count() >= 1, "needs the GPU"
 
 STAGES = ("x1", "op1", "h", "x2", "op2", "yn")
+
+
+def quantized(out_path):
+    """tests/test_dense_q_ops_gpu.py's cases: ran, W~, every derived check, and the ratios DENSE_Q_RATIO_BOUND comes from"""
+    TQ = importlib.import_module("test_dense_q_ops_gpu")
+    out_path.parent.mkdir(parents=True, exist_ok=True)
+    worst, where = 0.0, ""
+    with open(out_path, "w") as f:
+        def emit(line):
+            print(line, flush=True)
+            f.write(line + "\n")
+            f.flush()
+        emit("# tests/test_dense_q_ops_gpu.py on the MI355X (scripts/dense_op_figures.py q)")
+        emit("# per row m and stage: rms(dev[m] - f64[m]) / rms(emulated[m] - f64[m]), both computing with W~ of the numpy mirror,")
+        emit("# each reference fed the device's previous stage ('-': a derived bound instead — exact family, a deferred operand")
+        emit("# bit for bit, x2 and a quantized wn's yn, whose operands are exact in bf16)")
+        emit(f"# {'case':30s} {'family':6s} {'format':8s} {'ran':4s} {'W~':4s} {'checks':6s} " + " ".join(f"{s:>7s}" for s in STAGES))
+        for name, fam, fmt, g in R.Q_PARAMS:
+            inp, out = TQ.run(gpu, name, fam, fmt, g)
+            ran_ok = out["ran"] == R.CASES_Q[name]["ran"]
+            fig, held, wt = {}, "ok", "ok"
+            try:
+                R.check_wt(out, inp)
+            except AssertionError as e:
+                wt = "DIFF"
+                print(f"{name} {fam} {fmt} g{g}: {str(e)[:300]}", flush=True)
+            try:
+                fig = R.check_stages(inp, out, 2.0, f"{name} {fam} {fmt} g{g}")
+            except AssertionError as e:
+                held = "FAILED"
+                print(f"{name} {fam} {fmt} g{g}: {str(e)[:300]}", flush=True)
+            if not ran_ok:
+                print(f"{name} {fam} {fmt} g{g}: ran {out['ran']}\n{'':12s}expected {R.CASES_Q[name]['ran']}", flush=True)
+            emit(f"{name:32s} {fam:6s} {fmt + (f'/{g}' if g else ''):8s} {'ok' if ran_ok else 'DIFF':4s} {wt:4s} {held:6s} " +
+                 " ".join(f"{fig[s].max():7.4f}" if s in fig else f"{'-':>7s}" for s in STAGES))
+            for s, r in fig.items():
+                if r.max() > worst:
+                    worst, where = float(r.max()), f"{name} {fam} {fmt}{f'/{g}' if g else ''} {s} row {int(r.argmax())}"
+        emit(f"# largest ratio {worst:.4f} ({where})  ->  DENSE_Q_RATIO_BOUND = min(2, 1.25 x {worst:.4f}) = {min(2.0, 1.25 * worst):.3f}")
+
+
+if sys.argv[1:2] == ["q"]:
+    quantized(Path(sys.argv[2]) if len(sys.argv) > 2 else ROOT / "profiles" / "dense_q_op_tests.txt")
+    sys.exit(0)
+
 lines = ["# tests/test_dense_ops_gpu.py on the MI355X (scripts/dense_op_figures.py)",
          "# per row m and stage: rms(dev[m] - f64[m]) / rms(emulated[m] - f64[m]), each reference fed the device's previous stage",
          "# (moe-chain rows: x1, and under x2 the block's output y; routing and logits have derived bounds)",

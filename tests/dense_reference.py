@@ -1,6 +1,7 @@
 """The dense layer tail (generic_model.go:320-326,383-418: O projection, FFN norm, FFN-up, FFN-down, the next norm, the
 next projection) in float64, stage by stage — numpy only, test infrastructure like tests/moe_reference.py — plus the
-inputs, the case table and the assertions tests/test_dense_ops_gpu.py and tests/test_dense_reference_host.py share.
+inputs, the case table and the assertions tests/test_dense_ops_gpu.py, tests/test_dense_q_ops_gpu.py (the same tail on
+quantized weights: "quantized weights" below) and tests/test_dense_reference_host.py share.
 
 Every stage's reference is FED THE DEVICE'S OWN OUTPUT of the stage before (out: what ops.dense_stages returns): x1 from
 the inputs, the FFN-up operand from the device's x1, h from the device's operand and partials, x2 from the device's x1
@@ -338,7 +339,7 @@ def check_stages(inp, out, bound, name=""):
         fig["h"] = _ratio(out["h"], h64, ffn_h(out["op1"], out["rs1"], inp, True))
     # x2 from the device's x1 and h
     f64 = resid(out["x1"], out["h"], inp["w2"], inp.get("b2"), a_d, False)
-    if fam == "exact":
+    if fam == "exact" or inp.get("fmt"):      # (quantized: h and W~ are both exact in bf16 — the emulation IS float64, no ratio)
         err = np.abs(_f64(out["x2"]) - f64)
         assert (err <= _resid_exact_bound(out["x1"], out["h"], inp["w2"], inp.get("b2"), a_d)).all(), f"{name}: x2 beyond the fp32 dot product bound"
     else:
@@ -358,7 +359,7 @@ def check_stages(inp, out, bound, name=""):
     e = np.abs(_f64(out["yn"]) - y64r).max() / np.abs(y64r).max()
     print(f"{name}: yn against the float64 product of its bf16 operands: {e:.2e} of max")
     assert e <= F32_TOL, f"{name}: yn"
-    if fam != "exact":
+    if fam != "exact" and not inp.get("wn_quantized"):      # (a quantized wn is exact in bf16, like its operand: F32_TOL above holds yn)
         fig["yn"] = _ratio(out["yn"], next_y(op2, rs2, inp, False), y64r)
     for stage, r in fig.items():
         print(f"{name} {stage}: max row ratio {r.max():.4f} (row {int(r.argmax())})")
@@ -367,15 +368,195 @@ def check_stages(inp, out, bound, name=""):
     return fig
 
 
+# ---- quantized weights (tests/test_dense_q_ops_gpu.py; ops.dense_stages(..., weight_format=...)) ----------------------
+# The op quantizes wo, w1, w2 (and wn where a model would) itself — the upload quantizer, then finalize's fuse_w1 and
+# registration —; the reference computes with W~ of the bit-exact numpy mirrors (moe_reference.mirror), so quantization
+# error is in no figure.  W~ is exact in bf16: every rounding point above is unchanged, the projections' weight operand just
+# has nothing left to round.  Where BOTH operands of a product are exact in bf16 — x2 = x1 + alpha h . W~2^T from the
+# device's own h, and yn behind a quantized wn — the emulation equals float64 and a ratio is undefined: x2 is held to the
+# exact family's fp32 dot product bound instead (in both families), yn to F32_TOL alone.
+import moe_reference as MR
+
+Q_FORMATS = (("fp8", 0), ("mxfp4", 0), ("int4", 32), ("int4", 64), ("int4", 128))      # (format, INT4 group)
+Q_WEIGHTS = ("wo", "w1", "w2", "wn")
+
+
+def next_is_quantized(fmt, has_next):
+    """what quantize_next = -1 decides, as a model: the next layer's QKV follows the format; the LM head only under fp8"""
+    return fmt != "bf16" and (has_next or fmt == "fp8")
+
+
+def exact_int4(rng, n, k, g):
+    """test_int4_weights_gpu.exact_weights with e = 0: integers (q - z), q = 0 and q = 15 present in every group of g ->
+    range 15, s = 1, W~ == w bit for bit.  (-1, 0, 1 do NOT survive INT4: their range 2 gives s = 2 / 15.)"""
+    from test_int4_weights_gpu import exact_weights
+    w, e = exact_weights(rng, n, k, g)                       # (q - z) 2^e per group
+    return (w.reshape(n, k // g, g) * np.exp2(-e)).astype(np.float32).reshape(n, k)
+
+
+def exact_inputs_q(M, H, qw, F, Nn, fmt, g, **kw):
+    """exact_inputs whose weights survive the format unchanged.  fp8 / MXFP4: the family's {-1, 0, 1} as they are.  INT4:
+    exact_int4 weights up to +-15 — with attn_out thinned to 16 non-zeros per row (|x1| stays below 256: xn_raw's integers fit
+    bf16, every partial sum stays below 2^24) and the norm weights 2^-9..2^-7 instead of 2^-5..2^-3 (the pre-activations g, u
+    keep the size they have with {-1, 0, 1} weights, for which H_F32_REL was worked out).  exact_inputs' own assertions run on
+    the result."""
+    if fmt != "int4":
+        return exact_inputs(M, H, qw, F, Nn, **kw)
+    r = np.random.default_rng(11 * M + H + qw + F + Nn + g)
+    attn = np.zeros((M, qw), np.float32)
+    for m in range(M):
+        attn[m, r.permutation(qw)[:16]] = r.integers(-1, 2, 16)
+    p2 = lambda: (2.0 ** r.integers(-9, -6, H)).astype(np.float32)
+    return exact_inputs(M, H, qw, F, Nn, attn_out=attn, wo=exact_int4(r, H, qw, g), w1=exact_int4(r, 2 * F, H, g),
+                        w2=exact_int4(r, H, F, g), wn=exact_int4(r, Nn, H, g), norm_w=p2(), next_norm_w=p2(), **kw)
+
+
+def crafted_rows(w, fmt, g, seed):
+    """the crafted groups of the format's weight test in the first rows of w (moe_reference.crafted_experts on one matrix)"""
+    return MR.crafted_experts(np.asarray(w, np.float32)[None], fmt, g, seed)[0]
+
+
+def quantize(inp, fmt, g, crafted=True):
+    """inp with wo, w1, w2 (and wn, where a model quantizes it) replaced by W~ of the mirror; raw_*: what the op is given"""
+    mir = MR.mirror(fmt)
+    out = dict(inp, fmt=fmt, g=g, wn_quantized=next_is_quantized(fmt, inp.get("has_next", True)))
+    for i, k in enumerate(Q_WEIGHTS):
+        raw = crafted_rows(inp[k], fmt, g, 21 + i) if crafted else np.asarray(inp[k], np.float32)
+        out["raw_" + k] = raw
+        out[k] = mir(raw, g)["wt"] if (k != "wn" or out["wn_quantized"]) else raw
+    return out
+
+
+def q_formats(case):
+    """the (format, group) pairs a case runs in: INT4 groups that divide hidden, q_width and ffn"""
+    _, H, qw, F, _ = CASES_Q[case]["shape"]
+    return [(f, g) for f, g in Q_FORMATS if f != "int4" or (H % g == 0 and qw % g == 0 and F % g == 0)]
+
+
+def quantized_inputs(case, family, fmt, g):
+    c = CASES_Q[case]
+    kw = dict(c["kw"])
+    if family == "exact":
+        kw.setdefault("residual_multiplier", 0.0)
+        inp = quantize(exact_inputs_q(*c["shape"], fmt, g, **kw), fmt, g, crafted=False)
+        for k in Q_WEIGHTS:
+            assert np.array_equal(inp[k].view(np.uint32), inp["raw_" + k].view(np.uint32)), f"{case}: {k} does not survive {fmt}"
+        return inp
+    return quantize(random_inputs(*c["shape"], **kw), fmt, g)
+
+
+def op_args_q(inp):
+    """the arguments of ops.dense_stages for quantized inputs: the raw weights, the format"""
+    pos = [inp[k] for k in ("x", "attn_out", "raw_wo", "norm_w", "raw_w1", "raw_w2", "next_norm_w", "raw_wn")]
+    kw = {k: inp[k] for k in OP_KEYS if k in inp}
+    return pos, dict(kw, weight_format=inp["fmt"], group_size=inp["g"])
+
+
+def check_wt(out, inp):
+    """W~ as the device holds it after finalize (fuse_w1's interleave undone) equals the mirror bit for bit"""
+    for k in Q_WEIGHTS:
+        got = out["wt_" + k[1:]]
+        if k == "wn" and not inp["wn_quantized"]:
+            assert got is None, "wt_n of a projection that stays bf16"
+            continue
+        want = inp[k]
+        assert got is not None and got.shape == want.shape, (k, None if got is None else got.shape, want.shape)
+        bad = np.argwhere(got.view(np.uint32) != want.view(np.uint32))
+        assert bad.size == 0, f"W~ of {k} differs from the {inp['fmt']} mirror at {len(bad)} places, first (matrix, row, k) = {(k, *map(int, bad[0]))}"
+
+
+# The case table of the quantized file: the bf16 cases it keeps, by name, with their literals — gemm.h: "every weight format
+# takes the same decisions" —, and the shapes the bf16 file does not have.  New literals by hand from resid_gemm / the launchers:
+#  ragged-*   K = 768 = 24 k-steps in both residual projections.  Deferred: g_msplit_ks = 8 -> 24 / 8 = 3 < 4 -> ks = 4, six
+#             k-steps a wave: waves 1 and 3 start at k = 192 and 576, inside a 128-group.  The form is the ladder's (half tiles
+#             at 5 rows, m_split at 40).  Key 3 = 0, key 1 = 2: two slices of 12 k-steps each, cut at k = 384.
+#  wide-*     F = 8192: FFN-up has 2 F / 64 = 256 groups -> the wide kernel (rows > 16) reading rs_in, PASSES at 100 rows
+#             (256 / NTB % 8 == 0); FFN-down runs K = 8192 (256 k-steps, ks = 8) as the ladder's producer: m_split up to 64
+#             rows, 64-row groups at 100 (16 weight blocks, a multiple of 8: one launch).
+CASES_Q = {}
+for _n in (["llama-M%d" % M for M in (1, 5, 16, 17, 32, 33, 64, 65, 100, 128, 129)] + ["llama-M100-serial", "llama-M5-nohalf"] +
+           ["llama-M%d-key3=0%s" % (M, t) for M in (1, 17, 64) for t in ("", "-key1=2", "-key1=4")] +
+           ["llama-M%d-key3=%d" % (M, k) for M in (5, 40) for k in (2, 3)] + ["h2048-M8", "wide-H4096-M8"] +
+           ["llama-last-M5", "llama-last-M40", "llama-last-rows"] + ["gpt2-M%d" % M for M in (1, 17, 64)] +
+           ["falcon-H%d-M%d" % (H, M) for H in (192, 256) for M in (3, 40)] + ["tile-M130", "tile-M520", "groups-M130-key26=0"]):
+    CASES_Q[_n] = CASES[_n]
+for _n in ("h2048-M8", "wide-H4096-M8"):
+    CASES_Q[_n] = dict(CASES[_n], families=("random",))
+for M in (5, 40):
+    CASES_Q[f"ragged-M{M}"] = dict(shape=(M, 256, 768, 768, 384), ran=HALF if M <= 16 else MSPLIT, keys={}, families=("random", "exact"), kw={})
+    CASES_Q[f"ragged-M{M}-key3=0-key1=2"] = dict(shape=(M, 256, 768, 768, 384), ran=sk(2, 2), keys={3: 0, 1: 2}, families=("random", "exact"), kw={})
+for M in (17, 33, 64, 100):
+    CASES_Q[f"wide-F8192-M{M}"] = dict(shape=(M, 256, 256, 8192, 384), ran=MSPLIT if M <= 64 else GROUPS, keys={}, families=("random",), kw={})
+Q_PARAMS = [(n, fam, f, g) for n, c in CASES_Q.items() for fam in c["families"] for f, g in q_formats(n)]
+
+
+def _scaled_from(m, fmt, rows_from=None, groups_from=None, zero_points=True):
+    """W~ of a mirror result m with every row's scales (and zero points) taken from row rows_from[r], every group's from
+    group groups_from[j] of the same row: what a kernel computes that fetches the wrong scale"""
+    wt = _f64(m["wt"])
+    N, K = wt.shape
+    rf = np.arange(N) if rows_from is None else np.asarray(rows_from)
+    if fmt == "fp8":
+        s = _f64(m["s"])
+        return round_bf16((wt / s[:, None] * s[rf][:, None]).astype(np.float32))
+    G = m["s"].shape[1]
+    gf = np.arange(G) if groups_from is None else np.asarray(groups_from)
+    if fmt == "mxfp4":
+        e = m["s"].astype(np.int64)
+        return np.ldexp(wt.reshape(N, G, -1), (e[rf][:, gf] - e)[:, :, None]).reshape(N, K).astype(np.float32)
+    c = m["codes"]
+    q = np.stack([c & 15, c >> 4], -1).reshape(N, G, -1).astype(np.float64)
+    s, z = _f64(m["s"])[rf][:, gf], _f64(m["z"])[rf][:, gf] * (1.0 if zero_points else 0.0)
+    return round_bf16((s[:, :, None] * (q - z[:, :, None])).astype(np.float32)).reshape(N, K)
+
+
+Q_MUTATIONS = ("w1_scales_before_interleave", "group_off_by_one_at_wave_start", "zero_point_dropped", "slice_last_kstep_skipped",
+               "rstd_on_the_scale", "second_group_first_scales", "wt1_interleaved")
+
+
+def _mutated_weights(inp, ran, mut):
+    """the weights a kernel with the mutation computes with (the stand-in still REPORTS the mirror's W~)"""
+    fmt, g = inp.get("fmt"), inp.get("g", 0)
+    if fmt is None or mut not in ("w1_scales_before_interleave", "group_off_by_one_at_wave_start", "zero_point_dropped"):
+        return {}
+    mir = MR.mirror(fmt)
+    if mut == "w1_scales_before_interleave":      # device row p holds canonical row idx[p] but keeps the scales of canonical row p
+        F = inp["w1"].shape[0] // 2
+        idx = np.arange(2 * F).reshape(2, F // 16, 16).transpose(1, 0, 2).reshape(-1)      # fuse_w1's interleave
+        src = np.empty(2 * F, np.int64)
+        src[idx] = np.arange(2 * F)
+        return dict(w1=_scaled_from(mir(inp["raw_w1"], g), fmt, rows_from=src))
+    if mut == "zero_point_dropped":
+        assert fmt == "int4"
+        return dict(wo=_scaled_from(mir(inp["raw_wo"], g), fmt, zero_points=False))
+    # the O projection's producer form: ks waves of K / 32 / ks k-steps each; a wave's first k-step takes the group before its own
+    assert fmt in ("mxfp4", "int4") and ran["o"]["producer"]
+    K = inp["wo"].shape[1]
+    ks = 8
+    while ks > 1 and (K // 32) // ks < 4:
+        ks //= 2
+    m = mir(inp["raw_wo"], g)
+    per = g if fmt == "int4" else 32
+    bad = _scaled_from(m, fmt, groups_from=np.maximum(np.arange(K // per) - 1, 0))
+    wo = np.array(inp["wo"], np.float32)
+    for w in range(1, ks):
+        k0 = w * (K // 32 // ks) * 32
+        wo[:, k0:k0 + 32] = bad[:, k0:k0 + 32]
+    return dict(wo=wo)
+
+
 # ---- a stand-in for ops.dense_stages made of the reference alone (tests/test_dense_reference_host.py) ----------------
 MUTATIONS = ("slice_dropped", "bias_every_slice", "alpha_on_x", "tile_missing", "eps_left_out", "normalised_before_rounding",
-             "rows_15_16_swapped", "second_group_first_rstd", "gate_up_swapped", "multiplier_skipped")
+             "rows_15_16_swapped", "second_group_first_rstd", "gate_up_swapped", "multiplier_skipped") + Q_MUTATIONS
 
 
 def emulated_device(inp, ran, mut=None):
     """float64 with the kernels' bf16 roundings, stored as fp32, in the shape of ops.dense_stages' result; mut: one of
-    MUTATIONS, applied where the kernel would go wrong"""
+    MUTATIONS, applied where the kernel would go wrong.  Quantized inputs (quantized_inputs): computes with W~ and reports it
+    as wt_o / wt_1 / wt_2 / wt_n."""
     f32 = lambda a: np.asarray(a, np.float64).astype(np.float32)
+    given = inp
+    inp = dict(inp, **_mutated_weights(inp, ran, mut))
     a_o, a_d = alphas(inp)
     eps, kind = inp["norm_eps"], inp.get("norm", "rms")
     M, H = inp["x"].shape
@@ -386,7 +567,8 @@ def emulated_device(inp, ran, mut=None):
         s = max(slices, 1)
         K = a.shape[1]
         cuts = [K * i // s for i in range(s + 1)]
-        parts = [_r64(a)[:, cuts[i]:cuts[i + 1]] @ _r64(w)[:, cuts[i]:cuts[i + 1]].T for i in range(s)]
+        ends = [c - 32 if (mut == "slice_last_kstep_skipped" and s > 1) else c for c in cuts]
+        parts = [_r64(a)[:, cuts[i]:ends[i + 1]] @ _r64(w)[:, cuts[i]:ends[i + 1]].T for i in range(s)]
         b = 0.0 if bias is None else _f64(bias)
         if mut == "slice_dropped" and s > 1:
             parts = parts[:-1]
@@ -408,6 +590,13 @@ def emulated_device(inp, ran, mut=None):
         return round_bf16(f32(norm64(xs, w, b, 0.0 if mut == "eps_left_out" else eps, kind))), None
 
     x1 = residual(inp["x"], inp["attn_out"], inp["wo"], inp.get("bo"), a_o, ran["o"]["slices"])
+    if mut == "second_group_first_scales" and M > 64:
+        # the 64-row groups of one launch: weight block b of group 1 fetching the scales of block b // 2 (an index that
+        # forgot the groups are interleaved with the weight blocks)
+        m = MR.mirror(inp["fmt"])(inp["raw_wo"], inp["g"])
+        n = inp["wo"].shape[0]
+        wo_bad = _scaled_from(m, inp["fmt"], rows_from=(np.arange(n) // 16 // 2) * 16 + np.arange(n) % 16)
+        x1[64:] = residual(inp["x"], inp["attn_out"], wo_bad, inp.get("bo"), a_o, ran["o"]["slices"])[64:]
     if mut == "rows_15_16_swapped" and M > 16:
         x1[[15, 16]] = x1[[16, 15]]
     src = inp["x"] if inp.get("block") == "parallel" else x1
@@ -418,17 +607,29 @@ def emulated_device(inp, ran, mut=None):
     if rs1 is not None and mut == "second_group_first_rstd" and M > 64:
         rs_h = rs1.copy()
         rs_h[64:] = rs1[:M - 64]
-    h = f32(ffn_h(op1, rs_h, inp, True, swap=(mut == "gate_up_swapped")))
+    if rs1 is not None and mut == "rstd_on_the_scale":
+        # rstd folded into the dequantized weight, W~' = bf16(rstd W~), instead of scaling the fp32 accumulator: one more rounding
+        rstd = rstd_of(rs1, H, eps)
+        h = np.concatenate([ffn_h(op1[m:m + 1], None, dict(inp, w1=round_bf16(f32(rstd[m] * _f64(inp["w1"])))), True) for m in range(M)])
+        h = f32(h)
+    else:
+        h = f32(ffn_h(op1, rs_h, inp, True, swap=(mut == "gate_up_swapped")))
     x2 = residual(f32(x1), h, inp["w2"], inp.get("b2"), a_d, ran["down"]["slices"])
     sel = rows if (last and not ran["rs2_tiles"]) else None
     op2, rs2 = operand(x2, inp["next_norm_w"], inp.get("next_norm_b"), ran["rs2_tiles"], sel)
     o2, r2 = (op2, rs2) if not (last and rs2 is not None) else (op2[rows], rs2[rows])
     yn = f32(next_y(o2, r2, inp, True))
-    return dict(x1=f32(x1), op1=op1, rs1=rs1, h=h, x2=f32(x2), op2=op2, rs2=rs2, yn=yn, x_end=f32(x2), ran=ran)
+    out = dict(x1=f32(x1), op1=op1, rs1=rs1, h=h, x2=f32(x2), op2=op2, rs2=rs2, yn=yn, x_end=f32(x2), ran=ran)
+    if given.get("fmt"):
+        out.update({"wt_" + k[1:]: (given[k].copy() if (k != "wn" or given["wn_quantized"]) else None) for k in Q_WEIGHTS})
+        if mut == "wt1_interleaved":
+            F = given["w1"].shape[0] // 2
+            out["wt_1"] = given["w1"][np.arange(2 * F).reshape(2, F // 16, 16).transpose(1, 0, 2).reshape(-1)]
+    return out
 
 
 # ---- the MoE chain: O projection (producer) -> moe(deferred_norm) -> pending moe_part (ops.dense_moe_stages) ----------
-import moe_reference as MR        # (its softmax / route / tolerances: the routing is held exactly as test_moe_ops_gpu.py holds it)
+# (moe_reference's softmax / route / tolerances: the routing is held exactly as test_moe_ops_gpu.py holds it)
 
 MOE_SHAPE = dict(H=256, qw=256, E=8, k=2, I=64)
 # (M, tuning keys, MoE form, ran): E = 8 -> moe_down_slices = 4 slices left in moe_part; the O projection is the producer

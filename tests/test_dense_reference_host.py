@@ -11,7 +11,9 @@ test_dense_ops_gpu.py's docstring, one mutation each:
   rows_15_16_swapped          two rows across a 16-row tile edge                -> x1 exact          (gap 4)
   second_group_first_rstd     rows 64.. scaled with rows 0..'s rstd             -> h ratio           (gap 2)
   gate_up_swapped             silu(u) g                                         -> h ratio
-  multiplier_skipped          a pending add summed without the multiplier       -> x2 ratio          (gap 5)"""
+  multiplier_skipped          a pending add summed without the multiplier       -> x2 ratio          (gap 5)
+The quantized families of tests/test_dense_q_ops_gpu.py follow: the stand-in passes every case in every format, the exact
+families round-trip each mirror, and seven further mutations (AIMED_Q below) each fail their check."""
 import numpy as np
 import pytest
 
@@ -48,8 +50,90 @@ def test_each_mutation_fails_its_check(mut, name, fam):
         R.check_stages(inp, R.emulated_device(inp, c["ran"], mut), BOUND, f"{name} {mut}")
 
 
+def check_q(inp, out, name):
+    """what tests/test_dense_q_ops_gpu.py asserts of one call (the ran literal apart)"""
+    R.check_wt(out, inp)
+    return R.check_stages(inp, out, BOUND, name)
+
+
+SMALL_Q = [n for n, c in R.CASES_Q.items() if c["shape"][1] <= 768 and c["shape"][3] <= 3072 and c["shape"][0] <= 130]
+
+
+@pytest.mark.parametrize("name", SMALL_Q)
+def test_emulated_device_passes_every_quantized_case(name):
+    """the quantized families (tests/test_dense_q_ops_gpu.py): the stand-in computing with W~ of the mirrors passes every
+    check under the case's literal, in every format the case runs in"""
+    c = R.CASES_Q[name]
+    for fam in c["families"]:
+        for fmt, g in R.q_formats(name):
+            inp = R.quantized_inputs(name, fam, fmt, g)
+            fig = check_q(inp, R.emulated_device(inp, c["ran"]), f"{name} {fam} {fmt} g{g}")
+            assert all(abs(r.max() - 1.0) < 0.05 for r in fig.values())
+
+
+# the quantized kernels' own ways of going wrong (dense_reference.Q_MUTATIONS), one case each:
+#   w1_scales_before_interleave     W1's scale rows not moved with fuse_w1's interleave         -> h ratio
+#   group_off_by_one_at_wave_start  a wave starting inside a 128-group takes the group before   -> x1 ratio (K = 768, ks = 4)
+#   zero_point_dropped              INT4 s q instead of s (q - z)                               -> x1 ratio
+#   slice_last_kstep_skipped        a K slice one k-step short                                  -> x1 ratio
+#   rstd_on_the_scale               bf16(rstd W~) instead of rstd x the fp32 accumulator        -> h, exact family
+#   second_group_first_scales       rows 64.. with the scales of another weight block           -> x1 ratio
+#   wt1_interleaved                 wt_1 left in fuse_w1's order                                -> W~ bit for bit
+AIMED_Q = [("w1_scales_before_interleave", "llama-M5", "random", "fp8", 0),
+           ("group_off_by_one_at_wave_start", "ragged-M40", "random", "int4", 128),
+           ("zero_point_dropped", "llama-M5", "random", "int4", 64),
+           ("slice_last_kstep_skipped", "llama-M17-key3=0-key1=2", "random", "fp8", 0),
+           ("rstd_on_the_scale", "llama-M5", "exact", "fp8", 0),
+           ("second_group_first_scales", "llama-M100", "random", "mxfp4", 0),
+           ("wt1_interleaved", "llama-M5", "random", "int4", 32)]
+
+
+@pytest.mark.parametrize("mut,name,fam,fmt,g", AIMED_Q, ids=[a[0] for a in AIMED_Q])
+def test_each_quantized_mutation_fails_its_check(mut, name, fam, fmt, g):
+    assert mut in R.Q_MUTATIONS
+    c = R.CASES_Q[name]
+    inp = R.quantized_inputs(name, fam, fmt, g)
+    check_q(inp, R.emulated_device(inp, c["ran"]), name)                                # sound without the mutation
+    with pytest.raises(AssertionError):
+        check_q(inp, R.emulated_device(inp, c["ran"], mut), f"{name} {mut}")
+
+
 def test_every_mutation_is_aimed_at():
-    assert sorted(a[0] for a in AIMED) == sorted(R.MUTATIONS)
+    assert sorted(a[0] for a in AIMED + AIMED_Q) == sorted(R.MUTATIONS)
+
+
+@pytest.mark.parametrize("fmt,g", R.Q_FORMATS)
+def test_exact_families_round_trip_the_mirror(fmt, g):
+    """W~ == w bit for bit in the exact family of every format; {-1, 0, 1} survive fp8 and MXFP4 and do NOT survive INT4"""
+    for name in ("llama-M5", "ragged-M40", "llama-last-M5"):
+        inp = R.quantized_inputs(name, "exact", fmt, g)
+        for k in R.Q_WEIGHTS:
+            assert np.array_equal(inp[k].view(np.uint32), inp["raw_" + k].view(np.uint32)), (name, k)
+    w = R.exact_inputs(5, 256, 256, 512, 384)["wo"]
+    wt = R.MR.mirror(fmt)(w, g)["wt"]
+    assert np.array_equal(wt, w) == (fmt != "int4")
+    if fmt == "int4":
+        assert 0.06 < np.abs(wt - w).max() < 0.07            # step 2 / 15: off by up to 1 / 15
+
+
+def test_h_f32_term_of_the_int4_exact_family():
+    """test_h_f32_term on the INT4 exact family (weights up to +-15, norm weights 2^-9..2^-7): H_F32_REL covers it too"""
+    worst = 0.0
+    for name, g in (("llama-M5", 32), ("llama-M40-key3=2", 64), ("llama-M100", 128), ("ragged-M40", 128)):
+        c = R.CASES_Q[name]
+        inp = R.quantized_inputs(name, "exact", "int4", g)
+        dev = R.emulated_device(inp, c["ran"])
+        H, F = inp["x"].shape[1], inp["w2"].shape[1]
+        acc = (dev["op1"].astype(np.float64) @ inp["w1"].astype(np.float64).T).astype(np.float32)
+        s = dev["rs1"].astype(np.float32).sum(1, dtype=np.float32)
+        rstd = (np.float32(1.0) / np.sqrt(s * np.float32(1.0 / H) + np.float32(inp["norm_eps"]))).astype(np.float32)
+        g_, u = acc[:, :F] * rstd[:, None], acc[:, F:] * rstd[:, None]
+        h32 = (g_ / (np.float32(1.0) + np.exp(-g_))) * u
+        h64 = R.ffn_h(dev["op1"], dev["rs1"], inp, False)
+        nz = h64 != 0
+        worst = max(worst, float((np.abs(h32.astype(np.float64) - h64)[nz] / np.abs(h64[nz])).max()))
+    print(f"float32 evaluation of h, INT4 exact family: largest relative error {worst:.3e} (H_F32_REL {R.H_F32_REL:.1e})")
+    assert worst <= R.H_F32_REL
 
 
 def test_h_f32_term():
