@@ -58,6 +58,8 @@ typedef struct nvl_model_config {
     double  rope_base;       /* config.go:89; ignored for MQA, which hard-wires 10000 (mqa.go:35) */
     float   norm_eps;
     int32_t tied_embedding;
+    /* use_moe: num_experts 1..64, or 80..256 in multiples of 16 with num_experts_per_tok 1..8 (Qwen3-MoE: 128, top-8);
+     * anything else is NVL_ERR_INVALID from nvl_create */
     int32_t use_moe, num_experts, num_experts_per_tok;
     float   embedding_multiplier, attention_multiplier, residual_multiplier, logits_scaling;
     /* Mamba2 / hybrid layers (config.go:100-115; Granite-4: attention + Mamba2 blocks): layer li is a Mamba2 block when
@@ -993,7 +995,8 @@ int nvl_op_act_quant_fp8(int device, const float* a, int M, int K, int lda, uint
 int nvl_op_ffn(int device, int precision, const float* x, const float* w1, const float* b1,
                const float* w2, const float* b2, int rows, int hidden, int ffn, int swiglu,
                float* y);
-/* MoELayer.Forward moe.go:43-128 with separate experts (:167-226) */
+/* MoELayer.Forward moe.go:43-128 with separate experts (:167-226).  n_experts of this and of every MoE op below follows
+ * nvl_model_config's rule: 1..64, or 80..256 in multiples of 16 with top_k <= 8; else NVL_ERR_INVALID before the device probe */
 int nvl_op_moe(int device, int precision, const float* x, const float* router, const float* w_in,
                const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter,
                float* y);
@@ -1003,8 +1006,9 @@ int nvl_op_moe(int device, int precision, const float* x, const float* router, c
  * residual stream with multiplier 1, and completes what that leaves pending for the next norm the way debug mode 2 reads
  * it.  So rows <= 64 take the decode ("dense-masked") form wherever a model would, and nvl_set_tuning keys 31 / 22 / 8 /
  * 2 / 16 / 17 select the other forms.  Every scratch buffer the forms own is filled with 0xFF bytes (NaN as bf16 and as
- * fp32) before the call: a read of something no launch wrote shows in y.  hidden % 64 == 0, inter % 32 == 0, n_experts <=
- * 64.  (A sorted form on inter % 64 == 32 — a width nvl_create refuses — runs on experts zero-padded to inter + 32.)
+ * fp32) before the call: a read of something no launch wrote shows in y.  hidden % 64 == 0, inter % 32 == 0.  n_experts >
+ * 64 runs and reports the sorted forms only (PLAN up to 64 rows, with key 31 = 2 the router and the plan in one launch;
+ * GROUPED above).  (A sorted form on inter % 64 == 32 — a width nvl_create refuses — runs on experts zero-padded to inter + 32.)
  * Out: y [rows][hidden]; router_logits [rows][n_experts], the fp32 logits the routing consumed; gate [rows][n_experts],
  * the renormalised routing weight of (token, expert), 0 where the token did not pick the expert (moe.go:63-103; the
  * sorted forms' expert ids / weights scattered on the host); *form, what ran. */

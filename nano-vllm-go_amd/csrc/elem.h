@@ -803,6 +803,209 @@ __global__ __launch_bounds__(256) void moe_scatter_kernel(const int32_t* __restr
 }
 
 // ---------------------------------------------------------------------------------------
+// More than 64 experts (64 < E <= MOE_WIDE_MAX_E, E % 16 == 0: Qwen3-MoE has 128).  The kernels above give every expert
+// a lane of one wave; these keep the wave and give a lane several experts.  Selected by E > 64 alone.
+// ---------------------------------------------------------------------------------------
+constexpr int MOE_WIDE_MAX_E = 256;
+// moe_route_row's contract with EPL = 2 or 4 experts per lane, in registers: slot j of a lane is expert lane + 64 j.  The
+// rank is counted as there — every probability broadcast once by readlane, EPL x 64 broadcasts against EPL registers —
+// so there is still no LDS and no dependent argmax chain; a tie goes to the lower expert index, which for two slots of
+// different lanes is a comparison of lane + 64 j, not of lanes.
+template <int EPL>
+__device__ __forceinline__ void moe_route_row_wide(const float* __restrict__ logits_row, int E, int top_k, int lane,
+                                                   int32_t* __restrict__ ids_row, float* __restrict__ w_row) {
+    float v[EPL], prob[EPL];
+    int pbits[EPL], rank[EPL];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int j = 0; j < EPL; j++) {
+        v[j] = (lane + 64 * j < E) ? logits_row[lane + 64 * j] : -INFINITY;
+        mx = fmaxf(mx, v[j]);
+    }
+    mx = wave_max(mx);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < EPL; j++) {
+        v[j] = (lane + 64 * j < E) ? expf(v[j] - mx) : 0.f;
+        s += v[j];
+    }
+    s = wave_sum(s);
+#pragma unroll
+    for (int j = 0; j < EPL; j++) {
+        prob[j] = (lane + 64 * j < E) ? v[j] / s : -1.f;      // (slots past E hold -1: they never outrank an expert)
+        pbits[j] = __builtin_bit_cast(int, prob[j]);
+        rank[j] = 0;
+    }
+#pragma unroll
+    for (int js = 0; js < EPL; js++) {
+        if (64 * js >= E) break;
+#pragma unroll 8
+        for (int ls = 0; ls < 64; ls++) {
+            const float ps = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pbits[js], ls));
+            const int es = ls + 64 * js;
+#pragma unroll
+            for (int j = 0; j < EPL; j++) rank[j] += (ps > prob[j] || (ps == prob[j] && es < lane + 64 * j)) ? 1 : 0;
+        }
+    }
+    float wsum = 0.f;
+    for (int k = 0; k < top_k; k++) {     // moe.go:89-92: fp32 sum in rank order; exactly one slot of one lane has rank k
+        float pk = 0.f;
+#pragma unroll
+        for (int j = 0; j < EPL; j++) {
+            const unsigned long long b = __ballot(rank[j] == k);
+            if (b) pk = __builtin_bit_cast(float, __builtin_amdgcn_readlane(pbits[j], __ffsll(b) - 1));
+        }
+        wsum += pk;
+    }
+#pragma unroll
+    for (int j = 0; j < EPL; j++)
+        if (rank[j] < top_k && lane + 64 * j < E) {
+            ids_row[rank[j]] = lane + 64 * j;
+            w_row[rank[j]] = prob[j] / wsum;        // moe.go:103
+        }
+}
+template <int EPL>
+__global__ __launch_bounds__(256) void moe_route_wide_kernel(const float* __restrict__ router_logits, int ld, int rows, int E, int top_k,
+                                                             int32_t* __restrict__ expert_ids, float* __restrict__ expert_w) {
+    const int lane = threadIdx.x & 63;
+    const int r = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= rows) return;
+    moe_route_row_wide<EPL>(router_logits + (int64_t)r * ld, E, top_k, lane, expert_ids + (int64_t)r * top_k, expert_w + (int64_t)r * top_k);
+}
+// moe_hist_kernel with a thread per expert: 256 LDS counters
+__global__ __launch_bounds__(256) void moe_hist_wide_kernel(const int32_t* __restrict__ expert_ids, int n_pairs, int E, int32_t* __restrict__ counts) {
+    __shared__ int lc[MOE_WIDE_MAX_E];
+    lc[threadIdx.x] = 0;
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < MOE_PAIRS_PER_WG / 256; j++) {
+        const int i = blockIdx.x * MOE_PAIRS_PER_WG + j * 256 + threadIdx.x;
+        if (i < n_pairs) atomicAdd(&lc[expert_ids[i]], 1);
+    }
+    __syncthreads();
+    if (threadIdx.x < E && lc[threadIdx.x]) atomicAdd(&counts[threadIdx.x], lc[threadIdx.x]);
+}
+// moe_scan_kernel's exclusive scans by one wave over up to 256 experts: a lane takes the four consecutive experts
+// 4 lane .. 4 lane + 3 (a scan wants neighbours together, unlike the routing), sums them, and the wave scans the lane sums
+__device__ __forceinline__ void moe_scan_wide(int lane, const int* __restrict__ counts, int E, int BM, int32_t* __restrict__ seg_start,
+                                              int* __restrict__ cursor, int32_t* __restrict__ tile_map, int32_t* __restrict__ n_mtiles) {
+    int c[4], nt[4], row = 0, tile = 0;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        c[j] = 4 * lane + j < E ? counts[4 * lane + j] : 0;
+        nt[j] = (c[j] + BM - 1) / BM;
+        row += c[j]; tile += nt[j];
+    }
+    int row0 = -row, tile0 = -tile;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int yr = __shfl_up(row, o, 64), yt = __shfl_up(tile, o, 64);
+        if (lane >= o) { row += yr; tile += yt; }
+    }
+    row0 += row; tile0 += tile;
+#pragma unroll
+    for (int j = 0; j < 4; j++) {
+        const int e = 4 * lane + j;
+        if (e < E) {
+            seg_start[e] = row0;
+            cursor[e] = row0;
+            for (int t = 0; t < nt[j]; t++) {
+                const int r = t * BM;
+                tile_map[4 * (tile0 + t)] = e; tile_map[4 * (tile0 + t) + 1] = row0 + r;
+                tile_map[4 * (tile0 + t) + 2] = (c[j] - r < BM) ? (c[j] - r) : BM; tile_map[4 * (tile0 + t) + 3] = 0;
+            }
+        }
+        row0 += c[j]; tile0 += nt[j];
+    }
+    if (lane == 63) { seg_start[E] = row; *n_mtiles = tile; }
+}
+__global__ __launch_bounds__(64) void moe_scan_wide_kernel(const int32_t* __restrict__ counts, int E, int BM,
+                                                           int32_t* __restrict__ seg_start, int32_t* __restrict__ cursor,
+                                                           int32_t* __restrict__ tile_map, int32_t* __restrict__ n_mtiles) {
+    moe_scan_wide(threadIdx.x, counts, E, BM, seg_start, cursor, tile_map, n_mtiles);
+}
+// moe_scatter_kernel with a thread per expert: 256 LDS counters and bases
+__global__ __launch_bounds__(256) void moe_scatter_wide_kernel(const int32_t* __restrict__ expert_ids, int n_pairs, int top_k, int E,
+                                                               int32_t* __restrict__ cursor, int32_t* __restrict__ perm_token,
+                                                               int32_t* __restrict__ slot_of) {
+    __shared__ int lc[MOE_WIDE_MAX_E], base[MOE_WIDE_MAX_E];
+    lc[threadIdx.x] = 0;
+    __syncthreads();
+    int e[MOE_PAIRS_PER_WG / 256], r[MOE_PAIRS_PER_WG / 256];
+#pragma unroll
+    for (int j = 0; j < MOE_PAIRS_PER_WG / 256; j++) {
+        const int i = blockIdx.x * MOE_PAIRS_PER_WG + j * 256 + threadIdx.x;
+        e[j] = 0; r[j] = 0;
+        if (i < n_pairs) { e[j] = expert_ids[i]; r[j] = atomicAdd(&lc[e[j]], 1); }
+    }
+    __syncthreads();
+    if (threadIdx.x < E && lc[threadIdx.x]) base[threadIdx.x] = atomicAdd(&cursor[threadIdx.x], lc[threadIdx.x]);
+    __syncthreads();
+#pragma unroll
+    for (int j = 0; j < MOE_PAIRS_PER_WG / 256; j++) {
+        const int i = blockIdx.x * MOE_PAIRS_PER_WG + j * 256 + threadIdx.x;
+        if (i < n_pairs) {
+            const int pos = base[e[j]] + r[j];
+            perm_token[pos] = i / top_k;
+            slot_of[i] = pos;
+        }
+    }
+}
+// moe_plan_kernel's phases behind the routing — histogram, scans with the m-tile map, scatter in (token, rank) order — for
+// up to 256 experts, by a whole workgroup.  ids / gw [rows * top_k] hold the routing in LDS, counts / cursor [256] are LDS
+// with counts zeroed, and a barrier lies between those writes and this call.  Shared by the two decode routes of E > 64
+// (moe_plan_wide_kernel here, gemm.h moe_router_plan_kernel): what they leave is the same bit for bit.
+__device__ __forceinline__ void moe_plan_sort_wide(const int32_t* __restrict__ ids, const float* __restrict__ gw, int* __restrict__ counts,
+                                                   int* __restrict__ cursor, int rows, int E, int top_k, int BM,
+                                                   int32_t* __restrict__ expert_ids, float* __restrict__ expert_w,
+                                                   int32_t* __restrict__ seg_start, int32_t* __restrict__ tile_map,
+                                                   int32_t* __restrict__ n_mtiles, int32_t* __restrict__ perm_token,
+                                                   int32_t* __restrict__ slot_of) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int pairs = rows * top_k, nw = blockDim.x >> 6;
+    for (int i = threadIdx.x; i < pairs; i += blockDim.x) {
+        const int e = ids[i];
+        expert_ids[i] = e;
+        expert_w[i] = gw[i];
+        atomicAdd(&counts[e], 1);
+    }
+    __syncthreads();
+    if (wave == 0) moe_scan_wide(lane, counts, E, BM, seg_start, cursor, tile_map, n_mtiles);
+    __syncthreads();
+    for (int e = wave; e < E; e += nw) {      // per-expert scan, not atomics: the row order inside a segment is the same on every run
+        int base = cursor[e];
+        for (int i0 = 0; i0 < pairs; i0 += 64) {
+            const int i = i0 + lane;
+            const bool mine = i < pairs && ids[i] == e;
+            const unsigned long long b = __ballot(mine);
+            if (mine) {
+                const int pos = base + __popcll(b & ((1ull << lane) - 1ull));
+                perm_token[pos] = i / top_k;
+                slot_of[i] = pos;
+            }
+            base += __popcll(b);
+        }
+    }
+}
+// moe_plan_kernel for E > 64 (reads the router logits a GEMM launch wrote: the two-launch decode route, tuning key 31 = 0)
+template <int EPL>
+__global__ __launch_bounds__(1024) void moe_plan_wide_kernel(const float* __restrict__ router_logits, int ld, int rows, int E,
+                                                             int top_k, int BM, int32_t* __restrict__ expert_ids,
+                                                             float* __restrict__ expert_w, int32_t* __restrict__ seg_start,
+                                                             int32_t* __restrict__ tile_map, int32_t* __restrict__ n_mtiles,
+                                                             int32_t* __restrict__ perm_token, int32_t* __restrict__ slot_of) {
+    __shared__ int32_t ids[MOE_PLAN_MAX_PAIRS];
+    __shared__ float gw[MOE_PLAN_MAX_PAIRS];
+    __shared__ int counts[MOE_WIDE_MAX_E], cursor[MOE_WIDE_MAX_E];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nw = blockDim.x >> 6;
+    if (threadIdx.x < MOE_WIDE_MAX_E) counts[threadIdx.x] = 0;
+    for (int r = wave; r < rows; r += nw)
+        moe_route_row_wide<EPL>(router_logits + (int64_t)r * ld, E, top_k, lane, ids + r * top_k, gw + r * top_k);
+    __syncthreads();
+    moe_plan_sort_wide(ids, gw, counts, cursor, rows, E, top_k, BM, expert_ids, expert_w, seg_start, tile_map, n_mtiles, perm_token, slot_of);
+}
+
+// ---------------------------------------------------------------------------------------
 // load-time converters (generic_loader.go:642-663 dtype expansion, tensor.go:112-125 Transpose)
 // ---------------------------------------------------------------------------------------
 __device__ __forceinline__ float ld_as_f32(const void* p, int dtype, int64_t i) {

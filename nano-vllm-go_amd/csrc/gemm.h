@@ -1320,6 +1320,70 @@ __global__ __launch_bounds__(1024) void moe_router_gate_kernel(GemmArgs p, int t
 }
 
 // ------------------------------------------------------------------------------------------
+// MoE decode with more than 64 experts (64 < E <= 256, E % 16 == 0; elem.h MOE_WIDE_MAX_E): from the activations to the
+// expert plan of the grouped GEMMs in ONE launch of ONE workgroup — router logits, routing, histogram, scans, scatter.
+// Before: the router as a skinny GEMM launch + moe_plan_wide_kernel, two launch floors.
+//  (a) logits on the MFMA: the tasks (16-row tile of the batch, 16-expert tile) are dealt round-robin to the 16 waves; a
+//      task runs over ALL of K with fragments straight from the fragment-major operand and router (as
+//      moe_router_gate_kernel reads them), so there is no K split and no cross-wave sum.  A task's 16x16 logits go to the
+//      LDS tile lg [16 MT][E] fp32 (64 KB at 64 rows x 256 experts) and to logits_out.
+//  (b) wave w routes rows w, w + 16, .. from lg with a lane holding EPL experts (elem.h moe_route_row_wide)
+//  (c) the plan, as moe_plan_wide_kernel makes it (elem.h moe_plan_sort_wide)
+// Dynamic LDS: lg | ids, gw [MOE_PLAN_MAX_PAIRS] | counts, cursor [MOE_WIDE_MAX_E] = moe_router_plan_lds(M, E) bytes.
+// p: A (fragment-major operand, normed: no deferred-norm form at E > 64), W (router, fragment-major), M <= 64, N = E, K.
+// ------------------------------------------------------------------------------------------
+static inline int moe_router_plan_lds(int M, int E) {
+    return ((M + 15) / 16 * 16) * E * 4 + MOE_PLAN_MAX_PAIRS * 8 + MOE_WIDE_MAX_E * 8;
+}
+template <int EPL>
+__global__ __launch_bounds__(1024) void moe_router_plan_kernel(GemmArgs p, int top_k, int BM, float* __restrict__ logits_out, int ld_logits,
+                                                               int32_t* __restrict__ expert_ids, float* __restrict__ expert_w,
+                                                               int32_t* __restrict__ seg_start, int32_t* __restrict__ tile_map,
+                                                               int32_t* __restrict__ n_mtiles, int32_t* __restrict__ perm_token,
+                                                               int32_t* __restrict__ slot_of) {
+    extern __shared__ __attribute__((aligned(16))) char smem_rp[];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int fr = lane & 15, fg = lane >> 4;
+    const int E = p.N, ET = E >> 4, MT = (p.M + 15) >> 4, nks = p.K >> 5;
+    float* lg = (float*)smem_rp;
+    int32_t* ids = (int32_t*)(lg + MT * 16 * E);
+    float* gw = (float*)(ids + MOE_PLAN_MAX_PAIRS);
+    int* counts = (int*)(gw + MOE_PLAN_MAX_PAIRS);
+    int* cursor = counts + MOE_WIDE_MAX_E;
+    if (tid < MOE_WIDE_MAX_E) counts[tid] = 0;
+    const bf16x8 zero = {};
+    for (int task = wave; task < MT * ET; task += 16) {
+        const int mt = task / ET, et = task - mt * ET;
+        const bf16_t* wp = (const bf16_t*)p.W + ((int64_t)et * nks * 64 + lane) * 8;
+        const bf16_t* xp = (const bf16_t*)p.A + ((int64_t)mt * nks * 64 + lane) * 8;
+        const bool x_live = mt * 16 + fr < p.M;
+        f32x4 acc = f32x4{0.f, 0.f, 0.f, 0.f};
+        int s = 0;
+        for (; s + 8 <= nks; s += 8) {        // eight k-steps of both operands in flight: the wave is alone on its tile's stream
+            bf16x8 w[8], x[8];
+#pragma unroll
+            for (int u = 0; u < 8; u++) {
+                w[u] = *(const bf16x8*)(wp + (int64_t)(s + u) * 512);
+                x[u] = x_live ? *(const bf16x8*)(xp + (int64_t)(s + u) * 512) : zero;
+            }
+#pragma unroll
+            for (int u = 0; u < 8; u++) acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(w[u], x[u], acc, 0, 0, 0);
+        }
+        for (; s < nks; s++)
+            acc = __builtin_amdgcn_mfma_f32_16x16x32_bf16(*(const bf16x8*)(wp + (int64_t)s * 512), x_live ? *(const bf16x8*)(xp + (int64_t)s * 512) : zero, acc, 0, 0, 0);
+        // acc of lane (fr, fg): row fr of the tile, experts 16 et + 4 fg .. + 3
+        const int row = mt * 16 + fr, col = 16 * et + 4 * fg;
+        *(f32x4*)(lg + row * E + col) = acc;
+        if (x_live) *(f32x4*)(logits_out + (int64_t)row * ld_logits + col) = acc;
+    }
+    __syncthreads();
+    for (int r = wave; r < p.M; r += 16)
+        moe_route_row_wide<EPL>(lg + r * E, E, top_k, lane, ids + r * top_k, gw + r * top_k);
+    __syncthreads();
+    moe_plan_sort_wide(ids, gw, counts, cursor, p.M, E, top_k, BM, expert_ids, expert_w, seg_start, tile_map, n_mtiles, perm_token, slot_of);
+}
+
+// ------------------------------------------------------------------------------------------
 // fp32 kernel (parity mode): 64x64 tile, BK=16, 256 threads, 4x4 outputs per thread, k ascending.
 // EPI_SWIGLU is not instantiated: the f32 path keeps W1 un-interleaved and applies the
 // activation with swiglu_kernel.

@@ -544,7 +544,27 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
             if (const StTensor* t = st.find(p + ".self_attn.q_norm.weight")) up1d(m, NVL_T_Q_NORM_W, l, *t);
             if (const StTensor* t = st.find(p + ".self_attn.k_norm.weight")) up1d(m, NVL_T_K_NORM_W, l, *t);
             load_kv_scales(m, st, p, l);
-            if (c.use_moe) {                                                   // loadMoE (:566-592)
+            if (c.use_moe && st.find(p + ".mlp.gate.weight")) {
+                // Qwen3-MoE: the router is mlp.gate [E, H]; expert e's gate_proj | up_proj [I, H] each stack into MOE_IN
+                // [E, 2I, H], its down_proj [H, I] into MOE_OUT [E, H, I]
+                up2d(m, NVL_T_ROUTER, l, st.need(p + ".mlp.gate.weight"), OI);
+                const int64_t E = c.num_experts, H = c.hidden, I = c.ffn_dim;
+                std::vector<float> win((size_t)(E * 2 * I * H)), wout((size_t)(E * H * I));
+                for (int64_t e = 0; e < E; e++) {
+                    const std::string pe = p + ".mlp.experts." + std::to_string(e);
+                    const char* names[3] = {".gate_proj.weight", ".up_proj.weight", ".down_proj.weight"};
+                    for (int j = 0; j < 3; j++) {
+                        const StTensor& t = st.need(pe + names[j]);
+                        const std::vector<int64_t> want = j < 2 ? std::vector<int64_t>{I, H} : std::vector<int64_t>{H, I};
+                        if (t.shape != want) throw std::runtime_error("loader: " + pe + names[j] + ": shape does not match the model's");
+                        const std::vector<float> f = to_f32(t);
+                        memcpy(j < 2 ? &win[(size_t)((e * 2 + j) * I * H)] : &wout[(size_t)(e * H * I)], f.data(), f.size() * 4);
+                    }
+                }
+                if (nvl_upload_tensor(m, NVL_T_MOE_IN, l, win.data(), NVL_DTYPE_F32, E * 2 * I, H, OI) ||
+                    nvl_upload_tensor(m, NVL_T_MOE_OUT, l, wout.data(), NVL_DTYPE_F32, E * H, I, OI))
+                    throw std::runtime_error(nvl_last_error(m));
+            } else if (c.use_moe) {                                            // loadMoE (:566-592)
                 up2d(m, NVL_T_ROUTER, l, st.need(p + ".block_sparse_moe.router.layer.weight"), OI);   // [E, H]: "always transpose"
                 for (int which = 0; which < 2; which++) {
                     const std::string name = p + (which ? ".block_sparse_moe.output_linear.weight" : ".block_sparse_moe.input_linear.weight");
@@ -615,6 +635,8 @@ extern "C" int nvl_load_config_json(const char* path, nvl_model_config* out) {
         // ---- templates (config.go:125-376); `architecture` first, then model_type (:822-836, :975-1007), default GPT-2
         std::string arch = str("architecture");
         const std::string mt = str("model_type");
+        const bool qwen3_moe = mt == "qwen3_moe" || mt == "Qwen3MoeForCausalLM";     // Qwen3 with MoE blocks: the Llama path + use_moe (below)
+        if (qwen3_moe) arch = "llama";
         if (arch != "gpt2" && arch != "falcon" && arch != "llama") {
             if (mt == "gpt2") arch = "gpt2";
             else if (mt == "falcon" || mt == "RefinedWeb" || mt == "RefinedWebModel") arch = "falcon";
@@ -701,6 +723,15 @@ extern "C" int nvl_load_config_json(const char* path, nvl_model_config* out) {
         // run the dense shared MLP: 0 experts is treated as "no MoE" here)
         if (num("num_local_experts", v)) { c.num_experts = (int)v; c.use_moe = v > 0 ? 1 : 0; }
         if (num("num_experts_per_tok", v)) c.num_experts_per_tok = (int)v;
+        if (qwen3_moe) {      // every layer a MoE block of num_experts experts, moe_intermediate_size wide, top-k weights renormalised
+            if (num("num_experts", v)) { c.num_experts = (int)v; c.use_moe = v > 0 ? 1 : 0; }
+            if (num("moe_intermediate_size", v)) c.ffn_dim = (int)v;
+            if (const JVal* t = raw.get("norm_topk_prob")) if (t->kind == JVal::BOOL && !t->b)
+                throw std::runtime_error("qwen3_moe: norm_topk_prob = false is not supported (the routing kernels renormalise the top-k weights, as moe.go:103 does)");
+            if (num("decoder_sparse_step", v) && (int)v != 1) throw std::runtime_error("qwen3_moe: decoder_sparse_step must be 1 (every layer a MoE block)");
+            if (const JVal* t = raw.get("mlp_only_layers")) if (t->kind == JVal::ARR && !t->arr.empty())
+                throw std::runtime_error("qwen3_moe: mlp_only_layers must be empty (every layer a MoE block)");
+        }
         *out = c;
         return NVL_OK;
     } catch (const std::exception& e) {

@@ -22,6 +22,12 @@ constexpr int ATTN_SPLIT_MAX_PAIRS = 32, ATTN_SPLIT_MAX = 8;     // split decode
 constexpr int SK_TILE_MAX_M = 2048, SK_TILE_MAX_SLICES = 8;      // split-K of the tile kernel for mid-size residual projections (resid_gemm)
 static int g_sk_tile = 1;            // nvl_set_tuning key 26: that split (0 = off)
 constexpr int MOE_DOWN_SLICES = 4;    // at most this many K slices (workgroups per column tile) in the dense-masked MoE down projection
+static inline int moe_logits_ld(int E) { return E > 128 ? 256 : 128; }      // row stride of router_logits
+// the expert counts the routing kernels cover: a lane per expert up to 64; above, whole 16-expert tiles up to
+// MOE_WIDE_MAX_E with at most 8 experts per token (elem.h moe_route_row_wide, gemm.h moe_router_plan_kernel)
+static inline bool moe_experts_ok(int E, int top_k) {
+    return (E >= 1 && E <= 64) || (E > 64 && E <= MOE_WIDE_MAX_E && E % 16 == 0 && top_k >= 1 && top_k <= 8);
+}
 static inline int moe_down_slices(int E) { int s = MOE_DOWN_SLICES; while (s > 1 && E % s) s--; return s; }   // a whole number of experts per slice
 
 namespace {
@@ -301,6 +307,8 @@ extern "C" int nvl_create(const nvl_model_config* cfg, const nvl_runtime_opts* o
         if (c.num_heads % tp || nkv_full % tp || c.ffn_dim % (tp * 64))
             return fail(nullptr, NVL_ERR_INVALID, "nvl_create: heads, kv heads and ffn_dim/64 must divide by tp_size");
     }
+    if (c.use_moe && !moe_experts_ok(c.num_experts, c.num_experts_per_tok))
+        return fail(nullptr, NVL_ERR_INVALID, "nvl_create: num_experts must be 1..64, or 80..256 in multiples of 16 with num_experts_per_tok 1..8");
     if (opts->device < 0 || nvl_device_count() <= opts->device)
         return fail(nullptr, NVL_ERR_NO_DEVICE,
                     "nvl_create: no HIP device (this library has no CPU fallback)");
@@ -1183,7 +1191,7 @@ extern "C" int nvl_finalize(nvl_model* m) {
     m->argmax_pval = dmalloc<float>(std::max<int64_t>(S, Mmax) * cdiv(m->V, ARGMAX_CHUNK));
     m->argmax_pidx = dmalloc<int32_t>(std::max<int64_t>(S, Mmax) * cdiv(m->V, ARGMAX_CHUNK));
     if (c.use_moe) {
-        m->router_logits = dmalloc<float>(Mmax * 128);
+        m->router_logits = dmalloc<float>(Mmax * moe_logits_ld(c.num_experts));
         m->expert_ids = dmalloc<int32_t>(Mmax * k);
         m->expert_w = dmalloc<float>(Mmax * k);
         m->seg_start = dmalloc<int32_t>(c.num_experts + 1);
@@ -1195,7 +1203,7 @@ extern "C" int nvl_finalize(nvl_model* m) {
         m->slot_of = dmalloc<int32_t>(Mmax * k);
         m->moe_eo = dmalloc<float>(Mmax * k * H);
         if (!m->f32) m->moe_xg = dmalloc_bytes(round_up(Mmax * k, 64) * H * 2);
-        if (!m->f32) {
+        if (!m->f32 && moe_dense_form(H, c.num_experts, m->F)) {     // the dense-masked decode form's scratch (E <= 64)
             m->moe_gate = dmalloc<float>(64 * (int64_t)c.num_experts);
             m->moe_hall = dmalloc_bytes(64 * (int64_t)c.num_experts * m->F * 2);
             NVL_HIP(hipMemsetAsync(m->moe_hall, 0, (size_t)(64 * (int64_t)c.num_experts * m->F) * 2, m->stream));
@@ -1864,6 +1872,9 @@ static int g_moe_defer_down = 0;    // nvl_set_tuning key 33: MoE decode: the do
                                     // 16 waves each wave walks 8 blocks (two experts) instead of 4 — Granite-1B B=8 down projection 8.9 -> 14.5 us, more
                                     // than the norm launch it saves: 6.48 K -> 6.26 K decode tok/s (profiles/r03_moe_decode_experiments.txt)
 static int g_moe_fused_route = 1;   // nvl_set_tuning key 31: MoE decode routing (router GEMM + softmax / top-k / gate matrix) as one launch (0 = two)
+                                    // 2 = also at E > 64 (router + routing + plan: gemm.h moe_router_plan_kernel), where two launches are
+                                    // the measured default: 0.165 / 0.307 / 0.626 ms per step in one launch against 0.167 / 0.302 / 0.614 in
+                                    // two at 1 / 8 / 32 rows (profiles/moe_wide_decode.txt)
 static int g_moe_small = 1;    // nvl_set_tuning key 8: fused MoE planning launch + combine folded into the next norm (0 = off)
 static int g_mamba_ssd = 1;    // nvl_set_tuning key 30: chunked (SSD) Mamba2 scan on MFMA for prefill-sized bf16 calls (0 = the sequential scan,
                                // 2 = chunk after chunk only, never the chunk-parallel three-launch form)
@@ -2005,15 +2016,33 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
     const double eb = m->ef != WF_BF16 ? wf_stored_bytes(m->ef) : (double)m->wsize;     // bytes per expert weight
     m->site = KS_MOE_ROUTER;
     const bool dense = moe_dense_ok(m, l, M) && m->pending_slices == 0;
+    // E > 64 (elem.h MOE_WIDE_MAX_E; never dense: moe_dense_form): a lane of the routing wave holds EPL = 2 or 4 experts
+    const bool wide = E > 64;
+    const int ld = moe_logits_ld(E);
+    // decode-sized batches: one planning launch, and the weighted combine rides on the norm that follows
+    const bool small = !m->f32 && M <= 64 && pairs <= MOE_PLAN_MAX_PAIRS && (wide || E <= MOE_PLAN_MAX_E) && g_moe_small;
+    // E > 64, decode: router logits, routing and the plan in one launch (gemm.h moe_router_plan_kernel) — on request only (key 31 = 2)
+    const bool fused_plan = wide && small && !dense && g_moe_fused_route == 2 && H % 32 == 0;
     // decode: router logits, softmax, top-k and the dense gate matrix in one launch (gemm.h moe_router_gate_kernel)
     const bool fused_route = dense && g_moe_fused_route && E <= 64 && H % 32 == 0;
     m->moe_form = dense ? (fused_route ? NVL_MOE_FORM_DENSE_FUSED : NVL_MOE_FORM_DENSE) : 0;      // (the sorted forms: below)
     {
-        GemmArgs ar = mk(m->xn, H, l.t[NVL_T_ROUTER].p, m->router_logits, 128, nullptr, 1.f, M, E, H);
+        GemmArgs ar = mk(m->xn, H, l.t[NVL_T_ROUTER].p, m->router_logits, ld, nullptr, 1.f, M, E, H);
         if (deferred_norm) set_deferred_in(m, ar);
-        if (fused_route) {
+        if (fused_plan) {
+            if (deferred_norm) throw std::runtime_error("moe: a deferred FFN norm needs the dense-masked decode form");
+            KScope ks(m, KC_GEMM, 2.0 * (double)M * E * H, -1, ((double)E * H + (double)M * H) * (double)m->wsize + (double)M * E * 4.0);
+            const int lds = moe_router_plan_lds(M, E);
+            auto launch = [&](auto kernel) {
+                NVL_LDS_ATTR(kernel, moe_router_plan_lds(64, MOE_WIDE_MAX_E));
+                hipLaunchKernelGGL(kernel, dim3(1), dim3(1024), lds, m->stream, ar, k, 128, m->router_logits, ld, m->expert_ids, m->expert_w,
+                                   m->seg_start, m->moe_tile_map, m->moe_n_mtiles, m->perm_token, m->slot_of);
+            };
+            if (E <= 128) launch(moe_router_plan_kernel<2>); else launch(moe_router_plan_kernel<4>);
+            NVL_HIP(hipGetLastError());
+        } else if (fused_route) {
             KScope ks(m, KC_GEMM, 2.0 * (double)M * E * H, -1, ((double)E * H + (double)M * H) * (double)m->wsize + (double)M * E * 8.0);
-            hipLaunchKernelGGL(moe_router_gate_kernel, dim3(cdiv(M, 16)), dim3(1024), 0, m->stream, ar, k, m->moe_gate, m->router_logits, 128);
+            hipLaunchKernelGGL(moe_router_gate_kernel, dim3(cdiv(M, 16)), dim3(1024), 0, m->stream, ar, k, m->moe_gate, m->router_logits, ld);
             NVL_HIP(hipGetLastError());
         } else {
             gemm(m, EPI_STORE, true, ar);
@@ -2027,7 +2056,7 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
     if (dense) {
         if (!fused_route) {
             KScope ks(m, KC_OTHER, 0, KS_MOE_PLAN, (double)M * (128 + E) * 4.0);
-            hipLaunchKernelGGL(moe_gate_kernel, dim3(cdiv(M, 4)), dim3(256), 0, m->stream, m->router_logits, 128, M, E, k, m->moe_gate);
+            hipLaunchKernelGGL(moe_gate_kernel, dim3(cdiv(M, 4)), dim3(256), 0, m->stream, m->router_logits, ld, M, E, k, m->moe_gate);
             NVL_HIP(hipGetLastError());
         }
         GemmArgs a = mk(m->xn, H, l.moe_in, m->moe_hall, E * I, nullptr, 1.f, M, E * 2 * I, H);
@@ -2061,23 +2090,39 @@ bool moe(nvl_model* m, const LayerW& l, int M, bool deferred_norm = false, const
         if (nsl > 1) { m->pending_part = m->moe_part; m->pending_slices = nsl; m->pending_rows = M; m->pending_alpha = m->resid_alpha; }
         return false;
     }
-    // decode-sized batches: one planning launch, and the weighted combine rides on the norm that follows
-    const bool small = !m->f32 && M <= 64 && pairs <= MOE_PLAN_MAX_PAIRS && E <= MOE_PLAN_MAX_E && g_moe_small;
     // m-tile height of the grouped GEMMs: 128 rows; the 256x128 three-stage instance stays a tuning option (Granite-1B,
     // 4096 rows per expert: 441 K vs 450 K prefill tok/s)
     // prefill default: 256-row m-tiles on the ping-pong kernel (needs the rows copied into expert order and K >= 160)
     const bool pp = !m->f32 && !small && g_moe_bm == 0 && m->moe_xg && g_moe_gather && H >= 160 && I >= 160 && (2 * I) % 256 == 0 && H % 256 == 0;
     const int BM = pp ? 256 : ((!m->f32 && !small && g_moe_bm == 256) ? 256 : 128);
     m->moe_form = small ? NVL_MOE_FORM_PLAN : NVL_MOE_FORM_GROUPED;
-    if (small) {
+    if (fused_plan) {      // (planned by the router's launch above)
+    } else if (small) {
         KScope ks(m, KC_OTHER, 0, KS_MOE_PLAN);
-        hipLaunchKernelGGL(moe_plan_kernel, dim3(1), dim3(M <= 4 ? 256 : (M <= 8 ? 512 : 1024)), 0, m->stream, m->router_logits, 128, M, E, k, 128, m->expert_ids,
-                           m->expert_w, m->seg_start, m->moe_tile_map, m->moe_n_mtiles, m->perm_token, m->slot_of);
+        const dim3 block(M <= 4 ? 256 : (M <= 8 ? 512 : 1024));
+        auto launch = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(1), block, 0, m->stream, m->router_logits, ld, M, E, k, 128, m->expert_ids,
+                               m->expert_w, m->seg_start, m->moe_tile_map, m->moe_n_mtiles, m->perm_token, m->slot_of);
+        };
+        if (!wide) launch(moe_plan_kernel); else if (E <= 128) launch(moe_plan_wide_kernel<2>); else launch(moe_plan_wide_kernel<4>);
+        NVL_HIP(hipGetLastError());
+    } else if (wide) {
+        KScope ks(m, KC_OTHER, 0, KS_MOE_PLAN);
+        NVL_HIP(hipMemsetAsync(m->moe_counts, 0, (size_t)E * 4, m->stream));
+        auto route = [&](auto kernel) {
+            hipLaunchKernelGGL(kernel, dim3(cdiv(M, 4)), dim3(256), 0, m->stream, m->router_logits, ld, M, E, k, m->expert_ids, m->expert_w);
+        };
+        if (E <= 128) route(moe_route_wide_kernel<2>); else route(moe_route_wide_kernel<4>);
+        hipLaunchKernelGGL(moe_hist_wide_kernel, dim3(cdiv(pairs, MOE_PAIRS_PER_WG)), dim3(256), 0, m->stream, m->expert_ids, pairs, E, m->moe_counts);
+        hipLaunchKernelGGL(moe_scan_wide_kernel, dim3(1), dim3(64), 0, m->stream, m->moe_counts, E, BM, m->seg_start, m->moe_cursor,
+                           m->moe_tile_map, m->moe_n_mtiles);
+        hipLaunchKernelGGL(moe_scatter_wide_kernel, dim3(cdiv(pairs, MOE_PAIRS_PER_WG)), dim3(256), 0, m->stream, m->expert_ids, pairs, k, E,
+                           m->moe_cursor, m->perm_token, m->slot_of);
         NVL_HIP(hipGetLastError());
     } else {
         KScope ks(m, KC_OTHER, 0, KS_MOE_PLAN);
         NVL_HIP(hipMemsetAsync(m->moe_counts, 0, (size_t)E * 4, m->stream));
-        hipLaunchKernelGGL(moe_route_kernel, dim3(cdiv(M, 4)), dim3(256), 0, m->stream, m->router_logits, 128, M, E, k,
+        hipLaunchKernelGGL(moe_route_kernel, dim3(cdiv(M, 4)), dim3(256), 0, m->stream, m->router_logits, ld, M, E, k,
                            m->expert_ids, m->expert_w);
         hipLaunchKernelGGL(moe_hist_kernel, dim3(cdiv(pairs, MOE_PAIRS_PER_WG)), dim3(256), 0, m->stream, m->expert_ids, pairs, m->moe_counts);
         hipLaunchKernelGGL(moe_scan_kernel, dim3(1), dim3(64), 0, m->stream, m->moe_counts, E, BM, m->seg_start, m->moe_cursor,

@@ -929,7 +929,7 @@ extern "C" int nvl_op_ffn(int device, int precision, const float* x, const float
 
 extern "C" int nvl_op_moe(int device, int precision, const float* x, const float* router, const float* w_in,
                           const float* w_out, int rows, int hidden, int n_experts, int top_k, int inter, float* y) {
-    if (!x || !router || !w_in || !w_out || !y || rows <= 0 || hidden % 64 || inter % 64 || n_experts > 64 || top_k > n_experts)
+    if (!x || !router || !w_in || !w_out || !y || rows <= 0 || hidden % 64 || inter % 64 || !moe_experts_ok(n_experts, top_k) || top_k > n_experts)
         return op_fail("nvl_op_moe: bad arguments");
     OP_TRY
     OpCtx cx(device, precision);
@@ -953,7 +953,7 @@ extern "C" int nvl_op_moe(int device, int precision, const float* x, const float
     }
     l.t[NVL_T_MOE_OUT].p = cx.up_mat(w_out, (int64_t)n_experts * hidden, inter, false, W_ROW_PAD);
     const int64_t pairs = (int64_t)rows * top_k;
-    m.router_logits = (float*)cx.alloc((int64_t)rows * 128 * 4);
+    m.router_logits = (float*)cx.alloc((int64_t)rows * moe_logits_ld(n_experts) * 4);
     m.expert_ids = (int32_t*)cx.alloc(pairs * 4); m.expert_w = (float*)cx.alloc(pairs * 4);
     m.seg_start = (int32_t*)cx.alloc((n_experts + 1) * 4);
     m.moe_counts = (int32_t*)cx.alloc(n_experts * 4); m.moe_cursor = (int32_t*)cx.alloc(n_experts * 4);
@@ -1054,7 +1054,7 @@ void moe_op_setup(OpCtx& cx, LayerW& l, const float* router, const float* w_in, 
         }
     }
     // the sorted forms' workspaces (nvl_create)
-    m.router_logits = (float*)nan_fill((int64_t)rows * 128 * 4);
+    m.router_logits = (float*)nan_fill((int64_t)rows * moe_logits_ld(E) * 4);
     m.expert_ids = (int32_t*)cx.alloc(pairs * 4); m.expert_w = (float*)cx.alloc(pairs * 4);
     m.seg_start = (int32_t*)cx.alloc((E + 1) * 4);
     m.moe_counts = (int32_t*)cx.alloc(E * 4); m.moe_cursor = (int32_t*)cx.alloc(E * 4);
@@ -1069,9 +1069,10 @@ void moe_op_setup(OpCtx& cx, LayerW& l, const float* router, const float* w_in, 
 bool moe_op_results(OpCtx& cx, int rows, int E, int k, float* router_logits, float* gate) {
     nvl_model& m = cx.m;
     const int64_t pairs = (int64_t)rows * k;
-    std::vector<float> lg((size_t)rows * 128);
-    cx.down(lg.data(), m.router_logits, (int64_t)rows * 128);
-    for (int r = 0; r < rows; r++) memcpy(router_logits + (size_t)r * E, &lg[(size_t)r * 128], (size_t)E * 4);
+    const int ld = moe_logits_ld(E);
+    std::vector<float> lg((size_t)rows * ld);
+    cx.down(lg.data(), m.router_logits, (int64_t)rows * ld);
+    for (int r = 0; r < rows; r++) memcpy(router_logits + (size_t)r * E, &lg[(size_t)r * ld], (size_t)E * 4);
     if (m.moe_form == NVL_MOE_FORM_DENSE_FUSED || m.moe_form == NVL_MOE_FORM_DENSE) {
         cx.down(gate, m.moe_gate, (int64_t)rows * E);
         return true;
@@ -1176,9 +1177,9 @@ extern "C" int nvl_op_moe_stages_q(int device, int precision, const float* x, co
                                    int expert_format, int group_size, float* y, float* router_logits, float* gate, int32_t* form,
                                    float* wt_in, float* wt_out, float* h) {
     if (!x || !router || !w_in || !w_out || !y || !router_logits || !gate || !form || precision != NVL_PRECISION_BF16 || rows <= 0 ||
-        rows > (1 << 16) || hidden <= 0 || hidden % 64 || inter <= 0 || inter % 32 || n_experts < 1 || n_experts > 64 || top_k < 1 ||
+        rows > (1 << 16) || hidden <= 0 || hidden % 64 || inter <= 0 || inter % 32 || !moe_experts_ok(n_experts, top_k) || top_k < 1 ||
         top_k > n_experts)
-        return op_fail("nvl_op_moe_stages: bad arguments (bf16 only; hidden % 64, inter % 32, top_k <= n_experts <= 64)");
+        return op_fail("nvl_op_moe_stages: bad arguments (bf16 only; hidden % 64, inter % 32, top_k <= n_experts; n_experts 1..64, or 80..256 in multiples of 16 with top_k <= 8)");
     const int wf = moe_op_wf(expert_format, group_size, hidden, inter);
     if (wf < 0) return op_fail("nvl_op_moe_stages_q: unknown expert format, or INT4 experts whose group size is not 32, 64 or 128 or does not divide hidden and inter");
     if (wf == WF_BF16 && (wt_in || wt_out)) return op_fail("nvl_op_moe_stages_q: wt_in / wt_out are the read-back of quantized experts");
@@ -1483,8 +1484,8 @@ extern "C" int nvl_op_dense_moe_stages_q(int device, int precision, const float*
                                          float* gate, float* y, int32_t* form, int32_t* ran, float* wt_in, float* wt_out, float* h) {
     if (!x || !attn_out || !wo || !norm_w || !router || !w_in || !w_out || !next_norm_w || !x1 || !op1 || !rs1 || !router_logits ||
         !gate || !y || !form || !ran || precision != NVL_PRECISION_BF16 || rows <= 0 || rows > 64 || hidden <= 0 || hidden % 64 ||
-        q_width <= 0 || q_width % 64 || inter <= 0 || inter % 64 || n_experts < 1 || n_experts > 64 || top_k < 1 || top_k > n_experts)
-        return op_fail("nvl_op_dense_moe_stages: bad arguments (bf16 only; rows <= 64; hidden, q_width, inter % 64; top_k <= n_experts <= 64)");
+        q_width <= 0 || q_width % 64 || inter <= 0 || inter % 64 || !moe_experts_ok(n_experts, top_k) || top_k < 1 || top_k > n_experts)
+        return op_fail("nvl_op_dense_moe_stages: bad arguments (bf16 only; rows <= 64; hidden, q_width, inter % 64; top_k <= n_experts; n_experts 1..64, or 80..256 in multiples of 16 with top_k <= 8)");
     const int wf = moe_op_wf(expert_format, group_size, hidden, inter);
     if (wf < 0) return op_fail("nvl_op_dense_moe_stages_q: unknown expert format, or INT4 experts whose group size is not 32, 64 or 128 or does not divide hidden and inter");
     if (wf == WF_BF16 && (wt_in || wt_out)) return op_fail("nvl_op_dense_moe_stages_q: wt_in / wt_out are the read-back of quantized experts");
