@@ -368,7 +368,11 @@ int nvl_set_gq_expert_dtype(nvl_model* m, int dtype);
 /* ---- lifecycle ---- */
 
 /* Replaces tensor.NewTransformerModel (generic_model.go:41-61) + the runner's model ownership
- * (tensor_model_runner.go:21-33).  Fails with NVL_ERR_NO_DEVICE when no GPU is present. */
+ * (tensor_model_runner.go:21-33).  Fails with NVL_ERR_NO_DEVICE when no GPU is present.
+ * head_dim is 64, 128 or 256 (anything else: NVL_ERR_INVALID).  256 (Gemma 2 / 3, Qwen3-Next) runs its own attention kernels
+ * (NVL_ATTN_RAN_PREFILL_HD256 / NVL_ATTN_RAN_DECODE_HD256; f32 as ever): the QKV projection stores its rows and one launch
+ * rotates and appends (QK-norm included) on every route, verify passes of 2..8 rows run on the prefill kernel, and there is
+ * no kernel over the fp8 KV cache: head_dim 256 with NVL_KV_FP8_E4M3 is NVL_ERR_INVALID.  Tensor parallelism at 256 is untested. */
 int nvl_create(const nvl_model_config* cfg, const nvl_runtime_opts* opts, nvl_model** out);
 
 /* Replaces loadTensorFromData + the per-kind placement in loadAttention/loadFFN/loadMoE/loadNorm
@@ -875,7 +879,9 @@ enum {
     NVL_ATTN_RAN_DECODE_KV8 = 6,      /* attn_decode_kv8_kernel */
     NVL_ATTN_RAN_DECODE_MQ = 7,       /* attn_decode_mq_bf16_kernel */
     NVL_ATTN_RAN_DECODE_STAMPED = 8,  /* the diagnostic instantiation of the fused form (nvl_set_debug mode 4) */
-    NVL_ATTN_RAN_DECODE_MQ_KV8 = 9    /* attn_decode_mq_kv8_kernel */
+    NVL_ATTN_RAN_DECODE_MQ_KV8 = 9,   /* attn_decode_mq_kv8_kernel */
+    NVL_ATTN_RAN_PREFILL_HD256 = 10,  /* attn256_prefill_kernel: head_dim 256, prefill and verify passes */
+    NVL_ATTN_RAN_DECODE_HD256 = 11    /* attn256_decode_kernel: head_dim 256, Q / K / V prepared by earlier launches */
 };
 int nvl_op_attention_batch(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
                            const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,

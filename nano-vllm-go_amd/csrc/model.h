@@ -11,6 +11,7 @@
 
 #include "../../include/nvllm.h"
 #include "attn.h"
+#include "attn256.h"
 #include "kv8.h"
 #include "qknorm.h"
 #include "common.h"

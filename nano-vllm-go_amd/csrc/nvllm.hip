@@ -279,8 +279,8 @@ extern "C" int nvl_create(const nvl_model_config* cfg, const nvl_runtime_opts* o
     if (c.hidden <= 0 || c.num_layers <= 0 || c.num_heads <= 0 || c.head_dim <= 0 || c.vocab_size <= 0 ||
         c.max_seq_len <= 0)
         return fail(nullptr, NVL_ERR_INVALID, "nvl_create: non-positive model dimension");
-    if (c.head_dim != 64 && c.head_dim != 128)
-        return fail(nullptr, NVL_ERR_INVALID, "nvl_create: head_dim must be 64 or 128");
+    if (c.head_dim != 64 && c.head_dim != 128 && c.head_dim != 256)
+        return fail(nullptr, NVL_ERR_INVALID, "nvl_create: head_dim must be 64, 128 or 256");
     if (c.attention_multiplier < 0.f)      // the kernels take the row maximum before scaling
         return fail(nullptr, NVL_ERR_INVALID, "nvl_create: attention_multiplier must not be negative");
     if (c.hidden % 64 != 0 || (c.ffn_dim % 64) != 0)
@@ -297,6 +297,8 @@ extern "C" int nvl_create(const nvl_model_config* cfg, const nvl_runtime_opts* o
         return fail(nullptr, NVL_ERR_INVALID, "nvl_create: the fp8 KV cache needs NVL_PRECISION_BF16");
     if (opts->kv_cache_dtype == NVL_KV_FP8_E4M3 && ((opts->tp_size > 1) || opts->tp_force_single == 1))
         return fail(nullptr, NVL_ERR_INVALID, "nvl_create: the fp8 KV cache does not cover tensor parallelism");
+    if (opts->kv_cache_dtype == NVL_KV_FP8_E4M3 && c.head_dim == 256)      // (attn256.h reads the bf16 cache only)
+        return fail(nullptr, NVL_ERR_INVALID, "nvl_create: head_dim 256 has no kernels over the fp8 KV cache (it needs head_dim 64 or 128)");
     const int tp = opts->tp_size > 1 ? opts->tp_size : 1;
     if (tp > 1) {
         const int nkv_full = c.attention_type == NVL_ATTN_MHA ? c.num_heads : c.num_kv_heads;
@@ -1172,8 +1174,8 @@ extern "C" int nvl_finalize(nvl_model* m) {
     m->qkv = dmalloc<float>(Mmax * m->n_qkv);
     m->q = dmalloc_bytes(Mmax * qw * (int64_t)m->wsize);
     m->attn_out = dmalloc_bytes(Mp * qw * (int64_t)m->wsize);
-    if (!m->f32 && (m->hd == 64 || m->hd == 128)) {     // partial results of a split decode attention (attn.h)
-        m->attn_part = dmalloc<float>((int64_t)ATTN_SPLIT_MAX_PAIRS * ATTN_SPLIT_MAX * (m->hd == 64 ? attn_part_floats<64>() : attn_part_floats<128>()));
+    if (!m->f32) {     // partial results of a split decode attention (attn.h, attn256.h)
+        m->attn_part = dmalloc<float>((int64_t)ATTN_SPLIT_MAX_PAIRS * ATTN_SPLIT_MAX * attn_part_floats_rt(m->hd));
         m->attn_part_cnt = dmalloc<int32_t>(ATTN_SPLIT_MAX_PAIRS);
         NVL_HIP(hipMemset(m->attn_part_cnt, 0, ATTN_SPLIT_MAX_PAIRS * sizeof(int32_t)));
     }
@@ -1548,9 +1550,10 @@ int decode_attn_cfg(const nvl_model* m, int n_seqs, int mq_S = 0) {
         const int ns = (wgs > 16 && n_kt < 32) ? 1 : std::min(std::min(want, ATTN_SPLIT_MAX), 128 / wgs);
         if (ns >= 2) return 2 | (ns << 8);
     }
-    const int cap = wgs >= 512 ? 2 : (wgs >= 320 ? 4 : 8);
+    // hd 256: one tile per wave and round, and four waves at most — a wave per SIMD, 32 KB of LDS each (attn256.h)
+    const int cap = wgs >= 512 ? 2 : (wgs >= 320 || m->hd == 256 ? 4 : 8);
     const int nw = n_kt <= 2 * per_wave ? 2 : (n_kt <= 4 * per_wave ? 4 : 8);
-    return (g_attn_nw ? g_attn_nw : std::min(nw, cap)) | (1 << 8);
+    return (g_attn_nw ? (m->hd == 256 ? std::min(g_attn_nw, 4) : g_attn_nw) : std::min(nw, cap)) | (1 << 8);
 }
 int decode_attn_waves(const nvl_model* m, int n_seqs) { return decode_attn_cfg(m, n_seqs); }   // (graph keys: the whole shape)
 // The decode launch ladder: 2 / 4 / 8 waves per workgroup, K2 / K4 / K8 the kernel's instantiations for them; `rest` are
@@ -1576,6 +1579,8 @@ struct AttnVariant {
     int tq;                                          // query tiles per workgroup (mq_kv8_tq)
 };
 constexpr bool attn_variant_exists(const AttnVariant& v) {
+    // hd 256 (attn256.h): the prefill kernel, the unfused decode kernel, f32 — each causal or windowed, nothing else
+    if (v.hd == 256) return v.family != ATTN_DECODE_MQ && !v.kv8 && !v.fused && !v.qknorm && !v.stamped && v.tq == 1;
     if (v.fused && (v.family != ATTN_DECODE || v.kv8)) return false;         // only the one-position bf16 decode kernel appends
     if (v.qknorm && !(v.fused && v.hd == 128)) return false;                 // (qkv_front fuses a QK-norm layer at head_dim 128 only: attn.h)
     if (v.stamped && !(v.fused && v.hd == 64 && !v.window)) return false;    // (the stamped form has no window)
@@ -1584,7 +1589,9 @@ constexpr bool attn_variant_exists(const AttnVariant& v) {
 }
 // a run-time flag as a template argument: f gets std::true_type / std::false_type, or the head size as an integral_constant
 template <typename F> static void with_bool(bool b, F&& f) { if (b) f(std::true_type{}); else f(std::false_type{}); }
-template <typename F> static void with_hd(int hd, F&& f) { if (hd == 64) f(std::integral_constant<int, 64>{}); else f(std::integral_constant<int, 128>{}); }
+template <typename F> static void with_hd(int hd, F&& f) {
+    if (hd == 64) f(std::integral_constant<int, 64>{}); else if (hd == 128) f(std::integral_constant<int, 128>{}); else f(std::integral_constant<int, 256>{});
+}
 // The prefill and f32 launch.  lds_limit > 0: raise the kernel's dynamic-LDS limit to it first — the head_dim 128 prefill forms
 // (the 8-bit one among them, whose 32 KB would fit the default limit) and an f32 score buffer above 64 KB.
 template <auto Kernel, typename... Args>
@@ -1605,7 +1612,8 @@ static bool kv_nt_policy(const nvl_model* m, int n_seqs, int query_tiles_per_kv_
 // 128-block limit); grids, wave choices and the K/V load policy are the same.
 // mq: the caller is a verify pass (or nvl_op_attention_mq): 2..8 positions per sequence on attn_decode_mq_bf16_kernel, over
 // an 8-bit cache on attn_decode_mq_kv8_kernel.
-static bool attention_mq_ok(const nvl_model* m, int max_len) { return !m->f32 && max_len >= 2 && max_len <= 8; }
+// hd 256 has no multi-position kernel: its verify passes run on attn256_prefill_kernel (after rope_kv, like any prefill).
+static bool attention_mq_ok(const nvl_model* m, int max_len) { return !m->f32 && m->hd != 256 && max_len >= 2 && max_len <= 8; }
 static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_len, const void* kc, const void* vc,
                              double flops, double abytes, bool fused_qkv, const float* kv8, bool mq = false) {
     AttnArgs a{};
@@ -1645,7 +1653,8 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) {
             constexpr int HD = decltype(HDt)::value;
             constexpr bool W = decltype(Wt)::value;
-            if (!kv8)
+            if constexpr (HD == 256) return;      // (attn_variant_exists: never reached)
+            else if (!kv8)
                 launch_decode_attn<attn_decode_mq_bf16_kernel<HD, 2, W>, attn_decode_mq_bf16_kernel<HD, 4, W>,
                                    attn_decode_mq_bf16_kernel<HD, 8, W>>(m, grid, nw, 64 * HD * 2, a, max_len);
             else with_bool(v.tq == 2, [&](auto T2t) {
@@ -1677,7 +1686,17 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) {
             constexpr int HD = decltype(HDt)::value;
             constexpr bool W = decltype(Wt)::value;
-            if (kv8)
+            if constexpr (HD == 256) {      // two or four waves, a 32-KB image each (decode_attn_cfg caps the ladder)
+                if (nw == 2) {
+                    NVL_LDS_ATTR((attn256_decode_kernel<2, W>), attn256_decode_lds_bytes(2));
+                    hipLaunchKernelGGL((attn256_decode_kernel<2, W>), grid, dim3(128), attn256_decode_lds_bytes(2), m->stream,
+                                       a.seq_pos, a.blk_table, a.tbl_stride, a.bs_shift, a.Tmax, a.group, a);
+                } else if (nw == 4) {
+                    NVL_LDS_ATTR((attn256_decode_kernel<4, W>), attn256_decode_lds_bytes(4));
+                    hipLaunchKernelGGL((attn256_decode_kernel<4, W>), grid, dim3(256), attn256_decode_lds_bytes(4), m->stream,
+                                       a.seq_pos, a.blk_table, a.tbl_stride, a.bs_shift, a.Tmax, a.group, a);
+                } else throw std::runtime_error("attention: head_dim 256 decodes on 2 or 4 waves per workgroup");
+            } else if (kv8)
                 launch_decode_attn<attn_decode_kv8_kernel<HD, 2, W>, attn_decode_kv8_kernel<HD, 4, W>,
                                    attn_decode_kv8_kernel<HD, 8, W>>(m, grid, nw, 64 * HD * 2, a, kv8[0], kv8[1]);
             else with_bool(v.fused, [&](auto Ft) { with_bool(v.qknorm, [&](auto Nt) { with_bool(v.stamped, [&](auto St) {
@@ -1687,23 +1706,31 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
                                        attn_decode_bf16_kernel<HD, 8, F, S, W, N>>(m, grid, nw, 64 * HD * 2, a);
             }); }); });
         }); });
-        m->attn_ran[0] = kv8 ? NVL_ATTN_RAN_DECODE_KV8 : (a.stamps ? NVL_ATTN_RAN_DECODE_STAMPED : (fused_qkv ? NVL_ATTN_RAN_DECODE_FUSED : NVL_ATTN_RAN_DECODE));
+        m->attn_ran[0] = v.hd == 256 ? NVL_ATTN_RAN_DECODE_HD256
+            : kv8 ? NVL_ATTN_RAN_DECODE_KV8 : (a.stamps ? NVL_ATTN_RAN_DECODE_STAMPED : (fused_qkv ? NVL_ATTN_RAN_DECODE_FUSED : NVL_ATTN_RAN_DECODE));
         m->attn_ran[1] = nw; m->attn_ran[2] = nsplit;
     } else {
         // 256 query rows (position x head-in-group, position-major) per workgroup of 8 waves
+        // (hd 256: 128 rows per workgroup of 4 waves: attn256.h)
         const int64_t qrows = (int64_t)max_len * m->group;
-        dim3 grid(m->nKV, n_seqs, cdiv(qrows, 256));      // (kv head fastest, query tile slowest: attn.h)
-        m->attn_ran[0] = kv8 ? NVL_ATTN_RAN_PREFILL_KV8 : NVL_ATTN_RAN_PREFILL; m->attn_ran[1] = 8; m->attn_ran[2] = 1;
+        const int wg_rows = v.hd == 256 ? PF256_QROWS : 256;
+        dim3 grid(m->nKV, n_seqs, cdiv(qrows, wg_rows));      // (kv head fastest, query tile slowest: attn.h)
+        m->attn_ran[0] = v.hd == 256 ? NVL_ATTN_RAN_PREFILL_HD256 : kv8 ? NVL_ATTN_RAN_PREFILL_KV8 : NVL_ATTN_RAN_PREFILL;
+        m->attn_ran[1] = v.hd == 256 ? PF256_WAVES : 8; m->attn_ran[2] = 1;
         with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) {
             constexpr int HD = decltype(HDt)::value;
             constexpr bool W = decltype(Wt)::value;
-            const int lds = kv8 ? attn_prefill_kv8_lds_bytes<HD>() : attn_prefill_lds_bytes<HD>(), limit = HD == 128 ? lds : 0;
-            if (kv8)       // K/V tiles through registers into one bf16 image pair
-                launch_prefill<attn_prefill_kv8_kernel<HD, W>>(m, grid, 512, lds, limit, a, kv8[0], kv8[1]);
-            else if constexpr (W)      // K/V tiles by LDS-DMA; the kernel keeps the sequence's block table in LDS
-                launch_prefill<attn_prefill_bf16_win_kernel<HD>>(m, grid, 512, lds, limit, a);
-            else
-                launch_prefill<attn_prefill_bf16_kernel<HD>>(m, grid, 512, lds, limit, a);
+            if constexpr (HD == 256) {
+                launch_prefill<attn256_prefill_kernel<W>>(m, grid, PF256_WAVES * 64, attn256_prefill_lds_bytes(), attn256_prefill_lds_bytes(), a);
+            } else {
+                const int lds = kv8 ? attn_prefill_kv8_lds_bytes<HD>() : attn_prefill_lds_bytes<HD>(), limit = HD == 128 ? lds : 0;
+                if (kv8)       // K/V tiles through registers into one bf16 image pair
+                    launch_prefill<attn_prefill_kv8_kernel<HD, W>>(m, grid, 512, lds, limit, a, kv8[0], kv8[1]);
+                else if constexpr (W)      // K/V tiles by LDS-DMA; the kernel keeps the sequence's block table in LDS
+                    launch_prefill<attn_prefill_bf16_win_kernel<HD>>(m, grid, 512, lds, limit, a);
+                else
+                    launch_prefill<attn_prefill_bf16_kernel<HD>>(m, grid, 512, lds, limit, a);
+            }
         }); });
     }
     NVL_HIP(hipGetLastError());
@@ -1736,10 +1763,13 @@ void rope_kv(nvl_model* m, int li, const Meta& md, int M) {
     void* kc = (char*)m->kcache + (size_t)li * m->layer_stride * m->kv_esize;
     void* vc = (char*)m->vcache + (size_t)li * m->layer_stride * m->kv_esize;
     if (m->qkn_q) {
-        if (m->hd != 64 && m->hd != 128) throw std::runtime_error("QK-norm needs head_dim 64 or 128");
+        if (m->hd != 64 && m->hd != 128 && m->hd != 256) throw std::runtime_error("QK-norm needs head_dim 64, 128 or 256");
         with_hd(m->hd, [&](auto HDt) {
             constexpr int HD = decltype(HDt)::value;
-            if (m->kv8) launch_qk_norm_rope_kv<bf16_t, HD, true>(m, li, md, M, kc, vc);
+            if constexpr (HD != 256) {      // (no 8-bit cache at 256: nvl_create)
+                if (m->kv8) { launch_qk_norm_rope_kv<bf16_t, HD, true>(m, li, md, M, kc, vc); return; }
+            }
+            if (m->kv8) throw std::runtime_error("QK-norm: no 8-bit cache at head_dim 256");
             else if (m->f32) launch_qk_norm_rope_kv<float, HD, false>(m, li, md, M, kc, vc);
             else launch_qk_norm_rope_kv<bf16_t, HD, false>(m, li, md, M, kc, vc);
         });
@@ -2308,7 +2338,9 @@ bool qkv_front(nvl_model* m, const LayerW& l, int li, const Meta& md, int M, int
     // short prefill batches (65..g_qkv_store_max_m tokens): the fused-epilogue tile kernel would run on M/128 * 24
     // workgroups; the decode form + rope_kv_kernel is faster there
     const bool short_prefill = max_len > 1 && M <= g_qkv_store_max_m && M <= g_chunk_max_m && g_force_tile == 0;
-    if (!m->f32 && !m->kv8 && M > 64 && !big_decode && !short_prefill && !qkn_store) {
+    // head_dim 256 takes the store form everywhere: the EPI_QKV epilogues give a wave one whole head of 64 or 128 columns, and
+    // the hd-256 decode kernel does not fuse RoPE and the append (attn256.h)
+    if (!m->f32 && !m->kv8 && M > 64 && !big_decode && !short_prefill && !qkn_store && m->hd != 256) {
         // prefill: RoPE + Q/K/V placement fused into the projection's epilogue (no fp32 qkv round trip)
         GemmArgs a = mk(m->xn, H, l.w_qkv, nullptr, 0, l.b_qkv, 1.f, M, m->n_qkv, H);
         a.qkv.tok_pos = md.tok_pos; a.qkv.tok_tbl = md.tok_tbl; a.qkv.blk_table = md.blk_table; a.qkv.cos_t = m->rope_cos; a.qkv.sin_t = m->rope_sin;
@@ -2327,7 +2359,7 @@ bool qkv_front(nvl_model* m, const LayerW& l, int li, const Meta& md, int M, int
         gemm(m, EPI_STORE, true, aq);
         // decode: RoPE + KV append live in the attention kernel — and the QK-norm at head_dim 128; a QK-norm layer with
         // head_dim 64 keeps the norm + RoPE launch and the plain decode kernel (the fused hd-64 kernel has no registers for it)
-        fused_dec = !m->f32 && !m->kv8 && max_len == 1 && !(qkn && m->hd != 128);
+        fused_dec = !m->f32 && !m->kv8 && max_len == 1 && !(qkn && m->hd != 128) && m->hd != 256;
         if (!fused_dec) rope_kv(m, li, md, M);     // (8-bit mode: always here — rope_kv8_kernel is its only K/V writer)
         m->front_ran[NVL_QKV_RAN_FORM] = fused_dec ? NVL_QKV_FORM_STORE_ONLY : m->kv8 ? NVL_QKV_FORM_STORE_ROPE_KV8
             : m->f32 ? NVL_QKV_FORM_F32_STORE_ROPE

@@ -221,7 +221,7 @@ void attention_op_one(int device, const AttnOpOne& rq, const float* q, const flo
     m.layer_stride = (int64_t)nKV * Tmax * hd; m.slot_stride = m.layer_stride;
     m.attn_scale = scale != 0.f ? scale : 1.0f / std::sqrt((float)hd);
     if (rq.split_scratch) {
-        m.attn_part = (float*)cx.alloc((int64_t)ATTN_SPLIT_MAX_PAIRS * ATTN_SPLIT_MAX * (hd == 64 ? attn_part_floats<64>() : attn_part_floats<128>()) * 4);
+        m.attn_part = (float*)cx.alloc((int64_t)ATTN_SPLIT_MAX_PAIRS * ATTN_SPLIT_MAX * attn_part_floats_rt(hd) * 4);
         m.attn_part_cnt = (int32_t*)cx.alloc(ATTN_SPLIT_MAX_PAIRS * 4);
         NVL_HIP(hipMemsetAsync(m.attn_part_cnt, 0, ATTN_SPLIT_MAX_PAIRS * 4, m.stream));
     }
@@ -254,7 +254,7 @@ void attention_op_one(int device, const AttnOpOne& rq, const float* q, const flo
 
 extern "C" int nvl_op_attention(int device, int precision, const float* q, const float* k, const float* v, int nH, int nKV,
                                 int S, int T, int hd, float scale, float* out) {
-    if (!q || !k || !v || !out || nH <= 0 || nKV <= 0 || nH % nKV || S <= 0 || T < S || (hd != 64 && hd != 128))
+    if (!q || !k || !v || !out || nH <= 0 || nKV <= 0 || nH % nKV || S <= 0 || T < S || (hd != 64 && hd != 128 && hd != 256))
         return op_fail("nvl_op_attention: bad arguments");
     OP_TRY
     AttnOpOne rq;
@@ -586,10 +586,12 @@ extern "C" int nvl_op_attention_batch_qknorm(int device, int precision, int form
     if ((q_norm_w != nullptr) != (k_norm_w != nullptr) || (q_norm_w && (form != NVL_ATTN_OP_FUSED || hd != 128 || !(eps >= 0.f) || !std::isfinite(eps))))
         return op_fail(std::string(who) + "QK-norm: both weights, the fused form, head_dim 128, a finite eps >= 0");
     if (window < 0 || !seq_len || !seq_pos || !k_pool || !v_pool || !block_table || !q || !out || !ran || !part_cnt || nH <= 0 || nKV <= 0 ||
-        nH % nKV || (hd != 64 && hd != 128) || n_seqs <= 0 || n_seqs > 4096 || n_blocks <= 0 || block_size <= 0 || block_size % 64 ||
+        nH % nKV || (hd != 64 && hd != 128 && hd != 256) || n_seqs <= 0 || n_seqs > 4096 || n_blocks <= 0 || block_size <= 0 || block_size % 64 ||
         tbl_stride <= 0 || max_seq <= 0 || form < NVL_ATTN_OP_PLAIN || form > NVL_ATTN_OP_MQ_KV8 ||
         (precision != NVL_PRECISION_BF16 && precision != NVL_PRECISION_F32) || !(scale >= 0.f) || !std::isfinite(scale))
         return op_fail(std::string(who) + "bad arguments");
+    if (hd == 256 && form != NVL_ATTN_OP_PLAIN && form != NVL_ATTN_OP_MQ)       // (attn256.h; "mq" runs on its prefill kernel)
+        return op_fail(std::string(who) + "head_dim 256 has the plain and mq forms only (no fused, kv8 or mq_kv8 kernel)");
     const bool fused = form == NVL_ATTN_OP_FUSED, kv8 = form == NVL_ATTN_OP_KV8 || form == NVL_ATTN_OP_MQ_KV8;
     const bool mq = form == NVL_ATTN_OP_MQ || form == NVL_ATTN_OP_MQ_KV8;
     if (form != NVL_ATTN_OP_PLAIN && precision != NVL_PRECISION_BF16) return op_fail(std::string(who) + "the fused, mq and kv8 forms are bf16 only");
@@ -649,7 +651,7 @@ extern "C" int nvl_op_attention_batch_qknorm(int device, int precision, int form
     }
     m.attn_out = nan_fill(round_up(tokens, 64) * W * (int64_t)m.wsize);
     if (!m.f32) {       // (nvl_create: the split scratch of every bf16 model with a head size the kernels have)
-        m.attn_part = (float*)nan_fill((int64_t)ATTN_SPLIT_MAX_PAIRS * ATTN_SPLIT_MAX * (hd == 64 ? attn_part_floats<64>() : attn_part_floats<128>()) * 4);
+        m.attn_part = (float*)nan_fill((int64_t)ATTN_SPLIT_MAX_PAIRS * ATTN_SPLIT_MAX * attn_part_floats_rt(hd) * 4);
         m.attn_part_cnt = (int32_t*)cx.alloc(ATTN_SPLIT_MAX_PAIRS * 4);
         NVL_HIP(hipMemsetAsync(m.attn_part_cnt, 0, ATTN_SPLIT_MAX_PAIRS * 4, m.stream));
     }

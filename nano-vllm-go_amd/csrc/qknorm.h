@@ -19,13 +19,20 @@ __device__ __forceinline__ float qk_dpp_add(float v) {
 // sum over the LPH = 8 or 16 adjacent lanes of one head (aligned groups inside a 16-lane DPP row): quad_perm [1,0,3,2],
 // quad_perm [2,3,0,1], row_half_mirror, (16: row_mirror).  After each step the lanes that were combined hold equal sums,
 // so a mirror reaches the other half's total.  All lanes end with the same value, summed in the same order.
+// LPH = 32 (hd 256: two heads per wave, a head = two adjacent DPP rows): one step more across the row pair, both rows'
+// totals exchanged by v_permlane16_swap (rows 0 <-> 1 and 2 <-> 3 trade places) and added: commutative, so still one value
+// and one order for all 32 lanes.
 template <int LPH>
 __device__ __forceinline__ float qk_head_sum(float v) {
-    static_assert(LPH == 8 || LPH == 16, "a head spans 8 or 16 lanes");
+    static_assert(LPH == 8 || LPH == 16 || LPH == 32, "a head spans 8, 16 or 32 lanes");
     v = qk_dpp_add<0xB1>(v);
     v = qk_dpp_add<0x4E>(v);
     v = qk_dpp_add<0x141>(v);
-    if constexpr (LPH == 16) v = qk_dpp_add<0x140>(v);
+    if constexpr (LPH >= 16) v = qk_dpp_add<0x140>(v);
+    if constexpr (LPH == 32) {
+        const auto sw = __builtin_amdgcn_permlane16_swap(__float_as_uint(v), __float_as_uint(v), false, false);
+        v = __uint_as_float(sw[0]) + __uint_as_float(sw[1]);
+    }
     return v;
 }
 

@@ -390,7 +390,7 @@ def dense_moe_stages(x, attn_out, wo, norm_w, router, w_in, w_out, next_norm_w, 
 
 ATTN_OP_FORMS = {"plain": 0, "fused": 1, "mq": 2, "kv8": 3}                                  # NVL_ATTN_OP_*
 ATTN_RAN = {1: "f32", 2: "prefill", 3: "prefill_kv8", 4: "decode", 5: "decode_fused", 6: "decode_kv8", 7: "decode_mq",
-            8: "decode_stamped", 9: "decode_mq_kv8"}                                             # NVL_ATTN_RAN_*
+            8: "decode_stamped", 9: "decode_mq_kv8", 10: "prefill_hd256", 11: "decode_hd256"}                                           # NVL_ATTN_RAN_*
 ATTN_OP_FORMS_KV8 = {"mq_kv8": 4}            # NVL_ATTN_OP_MQ_KV8: "kv8" with the verify pass's flag (k_scale / v_scale as there)
 
 
