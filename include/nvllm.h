@@ -231,6 +231,16 @@ int nvl_set_mamba_conv_state(nvl_model* m, int mode);
  * rollback work as before) and no block is freed.  A hybrid model's Mamba2 layers are untouched. */
 int nvl_set_sliding_window(nvl_model* m, int window);
 int nvl_get_sliding_window(const nvl_model* m);   /* 0 for a NULL model */
+/* Attention logit soft-capping (Gemma 2: 50, Grok-1: 30).  cap > 0: every attention layer bends the scores
+ * of the reference's attention (generic_model.go:276-480) to cap * tanh(score / cap), score = scale * q.k as today, BEFORE the
+ * causal or sliding-window mask — a masked key is still -inf — and the softmax; 0 (default) switches it off: the kernels
+ * launched are then the ones launched before this option existed.  After nvl_create, before nvl_finalize (else NVL_ERR_STATE);
+ * a negative, NaN or infinite cap and a NULL model are NVL_ERR_INVALID.  Every pass honours it, as for the window: both
+ * precisions, both cache dtypes, every head size (64, 128, 256), paged, graphs, verify passes, tensor parallel.  A QK-norm
+ * layer under a cap decodes on the unfused form (norm + RoPE launch, plain decode kernel).  NOT part of it: a cap on the
+ * final logits (final_logit_softcapping), Gemma 2's alternating local / global layers, its extra norms and GeGLU. */
+int nvl_set_attn_softcap(nvl_model* m, float cap);
+float nvl_get_attn_softcap(const nvl_model* m);   /* 0 for a NULL model */
 /* Speculative decoding on a hybrid model.  A Mamba2 state that a pass of 1 + k rows has advanced cannot
  * go back to 1 + n_accepted rows, so by default (NONE) every verify entry point refuses a model with Mamba2 layers.  VERIFY
  * makes the pass not advance it: each Mamba2 layer of a verify pass reads the slot's state and kept convolution rows and
@@ -397,6 +407,10 @@ int nvl_load_config_json(const char* path, nvl_model_config* cfg);
  * null, 0 or an absent key: 0).  model_type "mistral" / "MistralForCausalLM" selects the Llama template above.
  * nvl_load_safetensors on a checkpoint DIRECTORY applies its config.json's window when the model has none set. */
 int nvl_load_config_window(const char* path, int* window);
+/* ... and *cap = the config's "attn_logit_softcapping" (HF Gemma 2): a number > 0 is the cap, a JSON null or an absent key 0,
+ * anything else NVL_ERR_INVALID.  nvl_load_safetensors on a checkpoint DIRECTORY applies it when the model has no cap set, and
+ * refuses a config.json that carries a non-null "final_logit_softcapping" (not supported: nothing is loaded half-right). */
+int nvl_load_config_softcap(const char* path, float* cap);
 
 /* Helpers for checkpoints that keep fused projections (generic_loader.go:674-765):
  * GPT-2 c_attn [H, 3H] split by columns; Falcon query_key_value given in the reference's
@@ -901,6 +915,15 @@ int nvl_op_attention_batch_qknorm(int device, int precision, int form, int nH, i
                                   int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
                                   int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window,
                                   const float* q_norm_w, const float* k_norm_w, float eps);
+/* nvl_op_attention_batch_qknorm under nvl_set_attn_softcap(softcap): the scores of generic_model.go:276-480 bent to
+ * softcap * tanh(score / softcap) before the mask, on the SOFTCAP instantiations of the same kernel families, so ran[] keeps
+ * the NVL_ATTN_RAN_* codes.  softcap == 0 is nvl_op_attention_batch_qknorm; a negative, NaN or infinite softcap, and a
+ * softcap > 0 together with QK-norm weights, are NVL_ERR_INVALID (answered before the device is touched). */
+int nvl_op_attention_batch_softcap(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                                   const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                                   int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                                   int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window,
+                                   const float* q_norm_w, const float* k_norm_w, float eps, float softcap);
 /* The FRONT of an attention layer as a layer of the model runs it, stage by stage (generic_model.go:295-302 embedWithOffset,
  * :304-318 attention norm, the QKV projection with its bias, rope.go:153-205 on Q and K, Q into the attention operand
  * buffer, K / V into the paged cache): the forward pass's own embed() and qkv_front() on a batch laid out as the paged

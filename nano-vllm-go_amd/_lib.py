@@ -173,6 +173,7 @@ def lib():
     L.nvl_load_safetensors.argtypes = [vp, C.c_char_p]
     L.nvl_load_config_json.argtypes = [C.c_char_p, C.POINTER(ModelConfigC)]
     L.nvl_load_config_window.argtypes = [C.c_char_p, C.POINTER(C.c_int)]
+    L.nvl_load_config_softcap.argtypes = [C.c_char_p, C.POINTER(f32)]
     L.nvl_finalize.argtypes = [vp]
     L.nvl_destroy.argtypes = [vp]
     L.nvl_destroy.restype = None
@@ -194,6 +195,9 @@ def lib():
     L.nvl_set_mamba_rollback.argtypes = [vp, C.c_int]
     L.nvl_set_sliding_window.argtypes = [vp, C.c_int]
     L.nvl_get_sliding_window.argtypes = [vp]
+    L.nvl_set_attn_softcap.argtypes = [vp, f32]
+    L.nvl_get_attn_softcap.argtypes = [vp]
+    L.nvl_get_attn_softcap.restype = f32
     L.nvl_get_mamba_conv_state.argtypes = [vp, i64, C.c_int, vp]
     L.nvl_get_weight.argtypes = [vp, C.c_int, C.c_int, vp, i64, i64]
     L.nvl_get_stamps.argtypes = [vp, vp, C.c_int, vp, i64]
@@ -268,6 +272,7 @@ def lib():
                                           C.c_int, f32, f32, vp, vp, vp])
     L.nvl_op_attention_batch_window.argtypes = L.nvl_op_attention_batch.argtypes + [C.c_int]
     L.nvl_op_attention_batch_qknorm.argtypes = L.nvl_op_attention_batch_window.argtypes + [vp, vp, f32]
+    L.nvl_op_attention_batch_softcap.argtypes = L.nvl_op_attention_batch_qknorm.argtypes + [f32]
     L.nvl_op_mamba_mixer.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp] + [C.c_int] * 6 + [vp] * 8 + [C.c_int] + [vp] * 4
     L.nvl_op_mamba_verify.argtypes = [C.c_int, C.c_int, vp, C.c_int, vp, vp, vp, vp] + [C.c_int] * 6 + [vp] * 8 + [C.c_int] + [vp] * 5
     sp = C.POINTER(SamplingParamsC)

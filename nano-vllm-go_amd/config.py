@@ -45,6 +45,7 @@ class ModelConfig:
     mamba_head_dim: int = 0
     mamba_n_groups: int = 0
     mamba_conv_kernel: int = 0
+    attn_logit_softcap: float = 0.0   # HF Gemma 2 "attn_logit_softcapping": scores cap * tanh(score / cap); 0 / null = none
     sliding_window: int = 0           # HF Mistral "sliding_window": row i sees keys i - W < j <= i; 0 / null = none
     qk_norm: bool = False             # synthetic models only (synth.make_weights): per-head QK RMSNorm weights, as Qwen3 has them
                                       # (a checkpoint turns it on by carrying q_norm / k_norm tensors, not through a flag)
@@ -214,4 +215,9 @@ def load_model_config(raw: dict | str) -> ModelConfig:
     v = num("sliding_window")                               # (null or absent: none)
     if v is not None:
         c.sliding_window = int(v)
+    if raw.get("attn_logit_softcapping") is not None:       # (null or absent: none; nvl_load_config_softcap's rule)
+        v = num("attn_logit_softcapping")
+        if v is None or not 0 < v < float("inf"):
+            raise ValueError("attn_logit_softcapping must be a number > 0 or null")
+        c.attn_logit_softcap = float(v)
     return c

@@ -62,7 +62,32 @@ struct AttnArgs {
     const float* q_norm_w;
     const float* k_norm_w;
     float qk_norm_eps;
+    // logit soft-capping (the SOFTCAP instantiations only; cap > 0): s' = cap * tanh(s / cap), s = scale * q.k, BEFORE the
+    // mask.  Behind everything else again — and ONE float, in what was the struct's tail padding: its size, and with it the
+    // offset of every kernel argument behind it, stay what they were.  The two constants the bf16 / 8-bit kernels work with
+    // (attn_cap_c2, attn_cap_a) are three instructions per wave from it.
+    float softcap;
 };
+// the cap in exp2 units, C2 = cap * log2(e), and the factor of the cap's argument, a = 2 * log2(e) * scale / cap (ksc: the
+// k_scale of an 8-bit cache, which multiplies the raw scores as it does inside sl2)
+__device__ __forceinline__ float attn_cap_c2(const AttnArgs& p) { return p.softcap * 1.4426950408889634f; }
+__device__ __forceinline__ float attn_cap_a(const AttnArgs& p, float ksc = 1.0f) {
+    return 2.0f * 1.4426950408889634f * p.scale * ksc * __builtin_amdgcn_rcpf(p.softcap);
+}
+// Soft-capping in the exp2 domain.  With e = exp2(a * raw) = exp(2 s / cap):  tanh(s / cap) = 1 - 2 / (1 + e), so the capped
+// score in exp2 units is  C2 + 2 C2 * u,  u = -1 / (1 + e) = rcp(-1 - e)  in [-1, -0]: one multiply, v_exp_f32, one subtract,
+// v_rcp_f32, and the fma that the caller folds its reference into.  It saturates without a NaN: e = inf -> u = -0 -> +C2,
+// e = 0 -> u = -1 -> -C2 ((e - 1) / (e + 1) would be inf / inf).  u is monotone in the score, so maxima may be taken over u,
+// and a masked key is u = -inf: C2 + 2 C2 * (-inf) = -inf, as a masked score was.
+__device__ __forceinline__ float attn_cap_u(float raw, float cap_a) {
+    return __builtin_amdgcn_rcpf(-1.0f - __builtin_amdgcn_exp2f(raw * cap_a));
+}
+// a score in exp2 units as the decode rounds take it off the MFMA accumulator: raw * sl2, or capped
+template <bool SOFTCAP>
+__device__ __forceinline__ float attn_score2(float raw, float sl2, float cap_a, float cap_c2) {
+    if constexpr (SOFTCAP) return __builtin_fmaf(2.0f * cap_c2, attn_cap_u(raw, cap_a), cap_c2);
+    else return raw * sl2;
+}
 // The two-sided mask of a windowed kernel as ONE unsigned compare: with lo = limit - (W - 1) the lowest visible key,
 // lo <= key <= limit  <=>  (unsigned)(key - lo) <= W - 1 (keys, limit and lo relative to the same origin; the host keeps
 // W <= 2^30, so nothing wraps).  A padding row's limit -1 puts every key >= 0 at distance >= W: masked.
@@ -246,11 +271,15 @@ __device__ __forceinline__ AttnPrefillWindow attn_prefill_window_setup(const Att
 }
 // one 64-key tile from its LDS images: scores, causal mask (qpos: the last key each of the lane's rows may see), online
 // softmax, O^T += V^T · P^T
-template <int HD, bool WINDOW = false>
+// SOFTCAP: each f32x4 of scores is replaced by its u (attn_cap_u) where it leaves the MFMA, before the mask selects — so the
+// mask's -inf, the maxima (vmax16 / rows_max over u: monotone) and the -inf guards are the code below unchanged, and the cap's
+// last fma IS the exponent's: p = exp2(u * 2 C2 + (C2 - m)), m = the running maximum of the CAPPED scores.  (The maximum stays:
+// with +C2 as a fixed reference p could be as small as exp2(-2 C2) = e^-100 at cap 50, below the fp32 normal range.)
+template <int HD, bool WINDOW = false, bool SOFTCAP = false>
 __device__ __forceinline__ void attn_prefill_tile(int fg, const int (&qpos)[PF_TQ], int kt, int wave_first_limit, float sl2,
                                                   const char* kimg, const char* vimg, const int (&k_off)[HD / 32], const int (&v_off)[HD / 16],
                                                   const bf16x8 (&qf)[PF_TQ][HD / 32], f32x4 (&o)[PF_TQ][HD / 16], f32x4 (&lacc)[PF_TQ], float (&m_run)[PF_TQ],
-                                                  const AttnPrefillWindow& win = AttnPrefillWindow{}) {
+                                                  const AttnPrefillWindow& win = AttnPrefillWindow{}, float cap_a = 0.f, float cap_c2 = 0.f) {
     constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, TQ = PF_TQ;
     // ---- S^T = K · Q^T : 4 sub-tiles of 16 keys, each K fragment used for both query sub-tiles ----
     f32x4 s[TQ][4];
@@ -259,7 +288,7 @@ __device__ __forceinline__ void attn_prefill_tile(int fg, const int (&qpos)[PF_T
 #pragma unroll
         for (int t = 0; t < 4; t++) s[qi][t] = f32x4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-    for (int t = 0; t < 4; t++)
+    for (int t = 0; t < 4; t++) {
 #pragma unroll
         for (int ks = 0; ks < KS; ks++) {
             const bf16x8 kf = *(const bf16x8*)(kimg + k_off[ks] + t * (16 * CPR * 16));
@@ -267,6 +296,13 @@ __device__ __forceinline__ void attn_prefill_tile(int fg, const int (&qpos)[PF_T
             for (int qi = 0; qi < TQ; qi++)
                 s[qi][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf, qf[qi][ks], s[qi][t], 0, 0, 0);
         }
+        if constexpr (SOFTCAP) {
+#pragma unroll
+            for (int qi = 0; qi < TQ; qi++)
+#pragma unroll
+                for (int r = 0; r < 4; r++) s[qi][t][r] = attn_cap_u(s[qi][t][r], cap_a);
+        }
+    }
     // lane holds S^T[key = kt*64 + 16t + 4fg + r][q = fq] per sub-tile
     const bool whole = kt * 64 + 63 <= wave_first_limit;      // every row of the wave sees the whole tile
     if constexpr (WINDOW) {
@@ -306,7 +342,8 @@ __device__ __forceinline__ void attn_prefill_tile(int fg, const int (&qpos)[PF_T
 #pragma unroll
     for (int qi = 0; qi < TQ; qi++) {
         const float tmax = rows_max(vmax16(s[qi][0], s[qi][1], s[qi][2], s[qi][3]));
-        m_new[qi] = vmax2(m_run[qi], tmax * sl2);
+        if constexpr (SOFTCAP) m_new[qi] = vmax2(m_run[qi], __builtin_fmaf(2.0f * cap_c2, tmax, cap_c2));
+        else m_new[qi] = vmax2(m_run[qi], tmax * sl2);
         moved |= m_new[qi] != m_run[qi];
         m_ref[qi] = WINDOW && m_new[qi] == -INFINITY ? 0.f : m_new[qi];
     }
@@ -325,7 +362,10 @@ __device__ __forceinline__ void attn_prefill_tile(int fg, const int (&qpos)[PF_T
 #pragma unroll
         for (int t = 0; t < 4; t++)
 #pragma unroll
-            for (int r = 0; r < 4; r++) s[qi][t][r] = __builtin_amdgcn_exp2f(fmaf(s[qi][t][r], sl2, -m_ref[qi]));
+            for (int r = 0; r < 4; r++) {
+                if constexpr (SOFTCAP) s[qi][t][r] = __builtin_amdgcn_exp2f(fmaf(s[qi][t][r], 2.0f * cap_c2, cap_c2 - m_ref[qi]));
+                else s[qi][t][r] = __builtin_amdgcn_exp2f(fmaf(s[qi][t][r], sl2, -m_ref[qi]));
+            }
     attn_pv_tile<HD, TQ, true>(vimg, v_off, s, o, lacc);
 }
 // normalise (osc / l: osc = 1, or the v_scale of an 8-bit cache) and store
@@ -357,7 +397,7 @@ __device__ __forceinline__ void attn_prefill_store(const AttnArgs& p, const Attn
 // ahead, the same counted waits and slot rotation, over tiles kt_lo .. n_kt-1 — and a wave also skips the tiles below its own
 // rows' windows, after the barrier like the skip at the top (attn_prefill_window_setup).  The body is shared; the
 // unwindowed kernel keeps its name and its code.
-template <int HD, bool WINDOW>
+template <int HD, bool WINDOW, bool SOFTCAP = false>
 __device__ __forceinline__ void attn_prefill_bf16_body(const AttnArgs& p) {
     constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, TQ = PF_TQ, QROWS = PF_QROWS;
     constexpr int TILE_BYTES = 64 * HD * 2, PIECES = TILE_BYTES / 1024, PW = 2 * PIECES / 8, NBUF = 3;
@@ -430,6 +470,7 @@ __device__ __forceinline__ void attn_prefill_bf16_body(const AttnArgs& p) {
     f32x4 lacc[TQ] = {};              // softmax denominators out of the MFMA pipe: ones · P^T, every row the complete sum
     float m_run[TQ] = {-INFINITY, -INFINITY};
     const float sl2 = p.scale * 1.4426950408889634f;     // exp2 domain
+    const float cap_a = SOFTCAP ? attn_cap_a(p) : 0.f, cap_c2 = SOFTCAP ? attn_cap_c2(p) : 0.f;
 
     AttnPrefillWindow win{};
     if constexpr (WINDOW) win = attn_prefill_window_setup(p, w);
@@ -454,7 +495,7 @@ __device__ __forceinline__ void attn_prefill_bf16_body(const AttnArgs& p) {
         if (kt >= wave_n_kt) continue;                   // (wave-uniform) every row of this wave is masked out here
         if (WINDOW && kt < win.wave_kt_lo) continue;     // (wave-uniform) ... or the tile lies below all of their windows
 
-        attn_prefill_tile<HD, WINDOW>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run, win);
+        attn_prefill_tile<HD, WINDOW, SOFTCAP>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run, win, cap_a, cap_c2);
     }
     attn_prefill_store<HD>(p, w, o, lacc, 1.0f);
 }
@@ -462,6 +503,9 @@ template <int HD>
 __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_kernel(AttnArgs p) { attn_prefill_bf16_body<HD, false>(p); }
 template <int HD>
 __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_win_kernel(AttnArgs p) { attn_prefill_bf16_body<HD, true>(p); }
+// SOFTCAP (causal or windowed): a kernel of its own name, as the windowed one is — the two above keep theirs and their code
+template <int HD, bool WINDOW>
+__global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_bf16_cap_kernel(AttnArgs p) { attn_prefill_bf16_body<HD, WINDOW, true>(p); }
 template <int HD> constexpr int attn_prefill_lds_bytes() { return 3 * 2 * 64 * HD * 2; }
 
 // ------------------------------------------------------------------------------------------
@@ -585,6 +629,7 @@ __device__ __forceinline__ void attn_decode_softmax(f32x4 (&s)[NT2][4], float tm
 // combine of a split decode launch: the nsplit partial results of one (sequence, kv head, query tile), in workgroup order
 // whichever workgroup runs it.  One wave, the lanes of real heads; lane (fq, fg) as in the kernel's own combine.
 // osc: the output scale (1, or the v_scale of an 8-bit cache: kv8.h).
+// Soft-capping changes nothing here: the partials' m and l are those of the CAPPED scores, in the same exp2 units.
 template <int HD>
 __device__ __forceinline__ void attn_decode_merge(const AttnArgs& p, int pair, int tok, int head, int nsplit, int lane, float osc) {
     constexpr int DT = HD / 16;
@@ -700,7 +745,9 @@ __device__ __forceinline__ void attn_decode_finish(const AttnArgs& p, char* smem
 // QKNORM (FUSED, head_dim 128 only): the new token's Q rows and K row pass through the per-head QK RMSNorm (qk_norm_raw)
 // before the rotation, so the K used for the step's own score and the K appended to the cache are the normed one.  hd 64 is
 // deliberately not instantiated: that kernel sits at 239 of the 256 registers two waves per SIMD leave it.
-template <int HD, int NW, bool FUSED, bool STAMP = false, bool WINDOW = false, bool QKNORM = false>
+// SOFTCAP: attn_score2 in place of acc * sl2, sub-tile by sub-tile and before the mask (no second copy of the scores lives).
+// Not with QKNORM or STAMP (no model has both; the diagnostic form is one kernel): attn_variant_exists in nvllm.hip.
+template <int HD, int NW, bool FUSED, bool STAMP = false, bool WINDOW = false, bool QKNORM = false, bool SOFTCAP = false>
 __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                    int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p) {
     constexpr int KS = HD / 32, DT = HD / 16, HALF = HD / 2, CPR = HD / 8, KPI = 64 / CPR, NVL = 64 / KPI;
@@ -761,6 +808,7 @@ __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_ke
     for (int d = 0; d < DT; d++) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;     // exp2 domain
     const float sl2 = p.scale * 1.4426950408889634f;
+    const float cap_a = SOFTCAP ? attn_cap_a(p) : 0.f, cap_c2 = SOFTCAP ? attn_cap_c2(p) : 0.f;
     // LDS offsets: where this lane's V chunks go (row i*KPI + ksub, chunk dch) and where its transposed reads come from
     // (row i*KPI + ksub: the swizzle pattern only depends on i & 1, so two bases + compile-time row offsets)
     const int w_base[2] = {16 * kv_img_chunk<HD>(ksub, dch), 16 * kv_img_chunk<HD>(KPI + ksub, dch) - 16 * KPI * CPR};
@@ -926,7 +974,7 @@ __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_ke
                 const int lim = pos0 - kt * 64 - fg * 4;      // last visible key, relative to this lane's first
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-                    float v = acc[r] * sl2;
+                    float v = attn_score2<SOFTCAP>(acc[r], sl2, cap_a, cap_c2);
                     v = (WINDOW ? attn_in_window(t * 16 + r, lim - wm1, wm1) : (t * 16 + r <= lim)) ? v : -INFINITY;
                     acc[r] = v;
                     tmax = fmaxf(tmax, v);
@@ -1009,7 +1057,7 @@ __global__ __launch_bounds__(NW * 64, HD <= 64 ? 2 : 1) void attn_decode_bf16_ke
 // ------------------------------------------------------------------------------------------
 // WINDOW: each lane's lower limit is qlim - W + 1 (one two-sided compare: attn_in_window), and the workgroup walks from the
 // kt_lo of its FIRST real row to the n_kt of its last; GUARD already covers a row that finds a round fully masked.
-template <int HD, int NW, bool WINDOW = false>
+template <int HD, int NW, bool WINDOW = false, bool SOFTCAP = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_mq_bf16_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                       int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p, int S) {
     constexpr int KS = HD / 32, DT = HD / 16, CPR = HD / 8, KPI = 64 / CPR, NVL = 64 / KPI;
@@ -1045,6 +1093,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_mq_bf16_kernel(const int3
     for (int d = 0; d < DT; d++) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;     // exp2 domain
     const float sl2 = p.scale * 1.4426950408889634f;
+    const float cap_a = SOFTCAP ? attn_cap_a(p) : 0.f, cap_c2 = SOFTCAP ? attn_cap_c2(p) : 0.f;
     const int w_base[2] = {16 * kv_img_chunk<HD>(ksub, dch), 16 * kv_img_chunk<HD>(KPI + ksub, dch) - 16 * KPI * CPR};
     int v_off[DT];
 #pragma unroll
@@ -1105,7 +1154,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_mq_bf16_kernel(const int3
                 const int lim = qlim - kt * 64 - fg * 4;      // this row's last visible key, relative to the lane's first
 #pragma unroll
                 for (int r4 = 0; r4 < 4; r4++) {
-                    float v = acc[r4] * sl2;
+                    float v = attn_score2<SOFTCAP>(acc[r4], sl2, cap_a, cap_c2);
                     v = (WINDOW ? attn_in_window(t * 16 + r4, lim - wm1, wm1) : (t * 16 + r4 <= lim)) ? v : -INFINITY;
                     acc[r4] = v;
                     tmax = fmaxf(tmax, v);
@@ -1136,7 +1185,8 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_mq_bf16_kernel(const int3
 // fp32 parity kernel: block = (query position, head), 256 threads, T <= 8192
 // WINDOW: keys max(0, T - W) .. T - 1; the score buffer stays indexed by absolute key.
 // ------------------------------------------------------------------------------------------
-template <bool WINDOW = false>
+// SOFTCAP: cap * tanhf(s / cap) on the scaled score, before the mask (only visible keys are scored here at all)
+template <bool WINDOW = false, bool SOFTCAP = false>
 __global__ __launch_bounds__(256) void attn_f32_kernel(AttnArgs p, int HD) {
     extern __shared__ float sc[];                 // [T_max_needed] scores then probs
     __shared__ float red[8];
@@ -1160,6 +1210,7 @@ __global__ __launch_bounds__(256) void attn_f32_kernel(AttnArgs p, int HD) {
         float sum = 0.f;
         for (int d = 0; d < HD; d++) sum = fmaf(q[d], kr[d], sum);
         sum *= p.scale;
+        if constexpr (SOFTCAP) sum = p.softcap * tanhf(sum / p.softcap);
         sc[j] = sum;
         lmax = fmaxf(lmax, sum);
     }

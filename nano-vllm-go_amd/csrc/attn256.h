@@ -63,7 +63,7 @@ inline int attn_part_floats_rt(int hd) { return hd == 64 ? attn_part_floats<64>(
 // permutation goes into the SOURCE address (lane l of a piece lands at byte 16 l of it).
 // Inside the loop the only vector-memory operations are the LDS-DMA pieces (block ids come from LDS: attn.h).
 // ------------------------------------------------------------------------------------------
-template <bool WINDOW>
+template <bool WINDOW, bool SOFTCAP = false>
 __global__ __launch_bounds__(PF256_WAVES * 64, 1) void attn256_prefill_kernel(AttnArgs p) {
     constexpr int HD = A256_HD, KS = HD / 32, DT = HD / 16, CPR = HD / 8, TQ = PF_TQ, QROWS = PF256_QROWS;
     constexpr int TILE_BYTES = A256_TILE_BYTES, PW = 2 * (TILE_BYTES / 1024) / PF256_WAVES;      // 16 pieces per wave and tile
@@ -142,6 +142,7 @@ __global__ __launch_bounds__(PF256_WAVES * 64, 1) void attn256_prefill_kernel(At
     f32x4 lacc[TQ] = {};
     float m_run[TQ] = {-INFINITY, -INFINITY};
     const float sl2 = p.scale * 1.4426950408889634f;     // exp2 domain
+    const float cap_a = SOFTCAP ? attn_cap_a(p) : 0.f, cap_c2 = SOFTCAP ? attn_cap_c2(p) : 0.f;
 
     issue(kt_lo, 0);
     int buf = 0;
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(PF256_WAVES * 64, 1) void attn256_prefill_kernel(At
         buf ^= 1;
         if (kt >= wave_n_kt) continue;                   // (wave-uniform) every row of this wave is masked out here
         if (WINDOW && kt < win.wave_kt_lo) continue;     // (wave-uniform) ... or the tile lies below all of their windows
-        attn_prefill_tile<HD, WINDOW>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run, win);
+        attn_prefill_tile<HD, WINDOW, SOFTCAP>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run, win, cap_a, cap_c2);
     }
 #pragma unroll
     for (int qi = 0; qi < TQ; qi++) {
@@ -180,7 +181,8 @@ __global__ __launch_bounds__(PF256_WAVES * 64, 1) void attn256_prefill_kernel(At
 // compiler's counted waits are exact: the scores wait for K with the 32 V loads behind them still in flight.
 // The leading arguments repeat AttnArgs fields for the kernarg preload (attn.h).
 // ------------------------------------------------------------------------------------------
-template <int NW, bool WINDOW>
+// SOFTCAP: attn_score2 per 16-key sub-tile, where its f32x4 leaves the MFMA (this kernel sits at 492 of 512 registers).
+template <int NW, bool WINDOW, bool SOFTCAP = false>
 __global__ __launch_bounds__(NW * 64, 1) void attn256_decode_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                     int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p) {
     static_assert(NW == 2 || NW == 4, "a wave per SIMD at most: 512 registers each, 32 KB of LDS each");
@@ -204,6 +206,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn256_decode_kernel(const int32_
     const int kt_lo = WINDOW ? attn_window_kt_lo(pos0, p.window) : 0, wm1 = WINDOW ? p.window - 1 : 0;
     const int vw = kt_lo + blockIdx.z * NW + wave, nvw = NW * gridDim.z;
     const float sl2 = p.scale * 1.4426950408889634f;
+    const float cap_a = SOFTCAP ? attn_cap_a(p) : 0.f, cap_c2 = SOFTCAP ? attn_cap_c2(p) : 0.f;
 
     bf16x8 qf[KS];
     {
@@ -262,7 +265,7 @@ __global__ __launch_bounds__(NW * 64, 1) void attn256_decode_kernel(const int32_
                 const int lim = pos0 - kt * 64 - fg * 4;      // last visible key, relative to this lane's first
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-                    float v = acc[r] * sl2;
+                    float v = attn_score2<SOFTCAP>(acc[r], sl2, cap_a, cap_c2);
                     v = (WINDOW ? attn_in_window(t * 16 + r, lim - wm1, wm1) : (t * 16 + r <= lim)) ? v : -INFINITY;
                     acc[r] = v;
                     tmax = fmaxf(tmax, v);

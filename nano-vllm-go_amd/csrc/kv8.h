@@ -126,7 +126,8 @@ __global__ void rope_kv8_kernel(const float* __restrict__ qkv, int qkv_stride, c
 // 8-bit decode kernel: attn_decode_bf16_kernel's non-fused form over an 8-bit cache (see the header comment).
 // ------------------------------------------------------------------------------------------
 // WINDOW: attn_decode_bf16_kernel's rule — the deal starts at kt_lo, the tile of key pos0 - W + 1; one two-sided compare.
-template <int HD, int NW, bool WINDOW = false>
+// SOFTCAP: attn_score2 (attn.h); k_scale enters the cap's argument factor as it enters sl2.
+template <int HD, int NW, bool WINDOW = false, bool SOFTCAP = false>
 __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                   int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p,
                                                                   float ksc, float vsc) {
@@ -156,6 +157,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
     for (int d = 0; d < DT; d++) o[d] = f32x4{0.f, 0.f, 0.f, 0.f};
     float m_run = -INFINITY, l_run = 0.f;
     const float sl2 = p.scale * ksc * 1.4426950408889634f;
+    const float cap_a = SOFTCAP ? attn_cap_a(p, ksc) : 0.f, cap_c2 = SOFTCAP ? attn_cap_c2(p) : 0.f;
     int v_off[DT];
 #pragma unroll
     for (int d = 0; d < DT; d++) v_off[d] = attn_v_off<HD>(fq, fg, d);
@@ -219,7 +221,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
                 const int lim = pos0 - kt * 64 - fg * 4;
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
-                    float v = acc[r] * sl2;
+                    float v = attn_score2<SOFTCAP>(acc[r], sl2, cap_a, cap_c2);
                     v = (WINDOW ? attn_in_window(t * 16 + r, lim - wm1, wm1) : (t * 16 + r <= lim)) ? v : -INFINITY;
                     acc[r] = v;
                     tmax = fmaxf(tmax, v);
@@ -277,7 +279,7 @@ __global__ __launch_bounds__(NW * 64) void attn_decode_kv8_kernel(const int32_t*
 // ------------------------------------------------------------------------------------------
 // WINDOW: attn_decode_mq_bf16_kernel's rule — per-lane lower limit qlim - W + 1, tiles from the kt_lo of the workgroup's
 // first real row (row qt0 * 16) to the n_kt of its last.
-template <int HD, int NW, int TQ, bool WINDOW = false>
+template <int HD, int NW, int TQ, bool WINDOW = false, bool SOFTCAP = false>
 __global__ __launch_bounds__(NW * 64) NVL_NO_PK_F32 void attn_decode_mq_kv8_kernel(const int32_t* __restrict__ a_seq_pos, const int32_t* __restrict__ a_blk_table,
                                                                      int a_tbl_stride, int a_bs_shift, int a_Tmax, int a_group, AttnArgs p, int S,
                                                                      float ksc, float vsc) {
@@ -324,6 +326,7 @@ __global__ __launch_bounds__(NW * 64) NVL_NO_PK_F32 void attn_decode_mq_kv8_kern
         for (int d = 0; d < DT; d++) o[qi][d] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const float sl2 = p.scale * ksc * 1.4426950408889634f;
+    const float cap_a = SOFTCAP ? attn_cap_a(p, ksc) : 0.f, cap_c2 = SOFTCAP ? attn_cap_c2(p) : 0.f;
     int v_off[DT];
 #pragma unroll
     for (int d = 0; d < DT; d++) v_off[d] = attn_v_off<HD>(fq, fg, d);
@@ -405,7 +408,7 @@ __global__ __launch_bounds__(NW * 64) NVL_NO_PK_F32 void attn_decode_mq_kv8_kern
                     const int lim = qlim[qi] - kt * 64 - fg * 4;      // this row's last visible key, relative to the lane's first
 #pragma unroll
                     for (int r4 = 0; r4 < 4; r4++) {
-                        float v = acc[qi][r4] * sl2;
+                        float v = attn_score2<SOFTCAP>(acc[qi][r4], sl2, cap_a, cap_c2);
                         v = (WINDOW ? attn_in_window(t * 16 + r4, lim - wm1, wm1) : (t * 16 + r4 <= lim)) ? v : -INFINITY;
                         acc[qi][r4] = v;
                         tmax[qi] = fmaxf(tmax[qi], v);
@@ -460,7 +463,7 @@ __global__ __launch_bounds__(NW * 64) NVL_NO_PK_F32 void attn_decode_mq_kv8_kern
 // ------------------------------------------------------------------------------------------
 // WINDOW: the register-staged loop starts at the workgroup's kt_lo and each wave skips the tiles below its own rows'
 // windows, as in attn_prefill_bf16_body.
-template <int HD, bool WINDOW = false>
+template <int HD, bool WINDOW = false, bool SOFTCAP = false>
 __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_kv8_kernel(AttnArgs p, float ksc, float vsc) {
     constexpr int KS = HD / 32, DT = HD / 16, CPR8 = HD / 16, TQ = PF_TQ, QROWS = PF_QROWS;
     constexpr int TILE_BYTES = 64 * HD * 2, CH = 64 * CPR8, NCH = 2 * CH / 512;
@@ -516,6 +519,7 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_kv8_kernel
         for (int d = 0; d < DT; d++) o[qi][d] = f32x4{0.f, 0.f, 0.f, 0.f};
     }
     const float sl2 = p.scale * ksc * 1.4426950408889634f;
+    const float cap_a = SOFTCAP ? attn_cap_a(p, ksc) : 0.f, cap_c2 = SOFTCAP ? attn_cap_c2(p) : 0.f;
     const char* kimg = smem;
     const char* vimg = smem + TILE_BYTES;
 
@@ -534,7 +538,7 @@ __global__ __launch_bounds__(512, HD == 64 ? 4 : 2) void attn_prefill_kv8_kernel
         if (kt + 1 < n_kt) load_tile(kt + 1);            // in flight during this tile's MFMAs
         __syncthreads();
         if (kt >= wave_n_kt || (WINDOW && kt < win.wave_kt_lo)) continue;
-        attn_prefill_tile<HD, WINDOW>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run, win);
+        attn_prefill_tile<HD, WINDOW, SOFTCAP>(fg, qpos, kt, wave_first_limit, sl2, kimg, vimg, k_off, v_off, qf, o, lacc, m_run, win, cap_a, cap_c2);
     }
     attn_prefill_store<HD>(p, w, o, lacc, vsc);
 }

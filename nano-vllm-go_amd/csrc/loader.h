@@ -447,6 +447,34 @@ extern "C" int nvl_load_config_window(const char* path, int* window) {
     }
 }
 
+// "attn_logit_softcapping" of a config.json (HF Gemma 2): a number > 0 is the cap, null / absent is none, anything else refused
+static float config_attn_softcap(const std::string& path) {
+    const std::string txt = nvl_loader::read_text(path);
+    const JVal raw = nvl_loader::JParser(txt.c_str(), txt.size()).parse();
+    if (raw.kind != JVal::OBJ) throw std::runtime_error("config is not a JSON object");
+    const JVal* v = raw.get("attn_logit_softcapping");
+    if (!v || v->kind == JVal::NUL) return 0.f;
+    if (v->kind != JVal::NUM || !(v->num > 0) || !std::isfinite((float)v->num)) throw std::runtime_error("attn_logit_softcapping must be a number > 0 or null");
+    return (float)v->num;
+}
+// ... and whether it carries a final-logit cap (Gemma 2's "final_logit_softcapping"), which this library does not apply
+static bool config_has_final_softcap(const std::string& path) {
+    const std::string txt = nvl_loader::read_text(path);
+    const JVal raw = nvl_loader::JParser(txt.c_str(), txt.size()).parse();
+    const JVal* v = raw.kind == JVal::OBJ ? raw.get("final_logit_softcapping") : nullptr;
+    return v && v->kind != JVal::NUL;
+}
+extern "C" int nvl_load_config_softcap(const char* path, float* cap) {
+    if (!path || !cap) return NVL_ERR_INVALID;
+    try {
+        *cap = config_attn_softcap(path);
+        return NVL_OK;
+    } catch (const std::exception& e) {
+        g_create_err = std::string("nvl_load_config_softcap: ") + e.what();
+        return NVL_ERR_INVALID;
+    }
+}
+
 extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
     if (!m || !path) return NVL_ERR_INVALID;
     if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_load_safetensors: model already finalized");
@@ -458,7 +486,12 @@ extern "C" int nvl_load_safetensors(nvl_model* m, const char* path) {
     // unless the host set one
     bool is_dir = false;
     const std::string cfg_json = std::string(path) + "/config.json";
-    if (!m->window && nvl_loader::exists(path, &is_dir) && is_dir && nvl_loader::exists(cfg_json)) m->window = config_sliding_window(cfg_json);
+    const bool has_cfg = nvl_loader::exists(path, &is_dir) && is_dir && nvl_loader::exists(cfg_json);
+    if (!m->window && has_cfg) m->window = config_sliding_window(cfg_json);
+    // ... and the attention soft cap, the same way; a final-logit cap is not applied anywhere: such a checkpoint is refused whole
+    if (has_cfg && config_has_final_softcap(cfg_json))
+        throw std::runtime_error("nvl_load_safetensors: config.json has final_logit_softcapping, which is not supported (only attn_logit_softcapping is)");
+    if (!(m->softcap > 0.f) && has_cfg) m->softcap = config_attn_softcap(cfg_json);
     const nvl_model_config& c = m->cfg;
     // which WeightMapping (:60-181) — told from the checkpoint's own names
     const bool gpt2 = st.find("wte.weight") != nullptr;

@@ -992,6 +992,15 @@ extern "C" int nvl_set_sliding_window(nvl_model* m, int window) {
 }
 extern "C" int nvl_get_sliding_window(const nvl_model* m) { return m ? m->window : 0; }
 
+extern "C" int nvl_set_attn_softcap(nvl_model* m, float cap) {
+    if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_attn_softcap: no model");
+    if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_set_attn_softcap: call it before nvl_finalize");
+    if (!(cap >= 0.f) || !std::isfinite(cap)) return fail(m, NVL_ERR_INVALID, "nvl_set_attn_softcap: the cap must be finite and >= 0");
+    m->softcap = cap;
+    return NVL_OK;
+}
+extern "C" float nvl_get_attn_softcap(const nvl_model* m) { return m ? m->softcap : 0.f; }
+
 extern "C" int nvl_set_mamba_rollback(nvl_model* m, int mode) {
     if (!m) return fail(nullptr, NVL_ERR_INVALID, "nvl_set_mamba_rollback: no model");
     if (m->finalized) return fail(m, NVL_ERR_STATE, "nvl_set_mamba_rollback: call it before nvl_finalize");
@@ -1577,8 +1586,12 @@ struct AttnVariant {
     int hd;                                          // (the f32 kernel takes it as a run-time argument)
     bool kv8, window, fused, qknorm, stamped;        // fused: RoPE + KV append inside the decode kernel; stamped: its diagnostic in-kernel stamps
     int tq;                                          // query tiles per workgroup (mq_kv8_tq)
+    bool softcap;                                    // logit soft-capping (nvl_set_attn_softcap): the SOFTCAP instantiations
 };
 constexpr bool attn_variant_exists(const AttnVariant& v) {
+    // soft-capping: every family, head size, cache and window — but not with the fused QK-norm (no model has both: such a
+    // layer takes the store form and the plain capped decode kernel, qkv_front) and not with the diagnostic stamps
+    if (v.softcap && (v.qknorm || v.stamped)) return false;
     // hd 256 (attn256.h): the prefill kernel, the unfused decode kernel, f32 — each causal or windowed, nothing else
     if (v.hd == 256) return v.family != ATTN_DECODE_MQ && !v.kv8 && !v.fused && !v.qknorm && !v.stamped && v.tq == 1;
     if (v.fused && (v.family != ATTN_DECODE || v.kv8)) return false;         // only the one-position bf16 decode kernel appends
@@ -1627,10 +1640,13 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
     // sliding window: the WINDOW instantiation of the same kernel family, chosen here for every route (no caller knows)
     const bool win = m->window > 0;
     a.window = std::min(m->window, 1 << 30);
+    // logit soft-capping: the SOFTCAP instantiations, chosen here for every route too
+    const bool cap = m->softcap > 0.f;
+    a.softcap = m->softcap;
     KScope ks(m, KC_ATTN, flops, KS_ATTN, abytes);
     AttnVariant v{};
     v.family = m->f32 ? ATTN_F32 : (mq && attention_mq_ok(m, max_len)) ? ATTN_DECODE_MQ : (max_len == 1 ? ATTN_DECODE : ATTN_PREFILL);
-    v.hd = m->hd; v.kv8 = kv8 != nullptr; v.window = win;
+    v.hd = m->hd; v.kv8 = kv8 != nullptr; v.window = win; v.softcap = cap;
     v.fused = v.family == ATTN_DECODE && fused_qkv;
     v.qknorm = v.fused && m->qkn_q;      // (qkv_front fuses a QK-norm layer at head_dim 128 only)
     const int qt = cdiv(m->group * (v.family == ATTN_DECODE_MQ ? max_len : 1), 16);      // 16-row query tiles per kv head
@@ -1641,29 +1657,29 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
     if (v.family == ATTN_F32) {
         // one score per key a row can see: up to blocks_per_seq blocks of Tmax keys (slab mode: the one block)
         const size_t lds = (size_t)m->Tmax * m->blocks_per_seq * 4;
-        with_bool(win, [&](auto Wt) {
-            launch_prefill<attn_f32_kernel<decltype(Wt)::value>>(m, dim3(max_len, m->nH, n_seqs), 256, lds, lds > 64 * 1024 ? 160 * 1024 - 64 : 0, a, m->hd);
-        });
+        with_bool(win, [&](auto Wt) { with_bool(cap, [&](auto Ct) {
+            launch_prefill<attn_f32_kernel<decltype(Wt)::value, decltype(Ct)::value>>(m, dim3(max_len, m->nH, n_seqs), 256, lds, lds > 64 * 1024 ? 160 * 1024 - 64 : 0, a, m->hd);
+        }); });
         m->attn_ran[0] = NVL_ATTN_RAN_F32; m->attn_ran[1] = 4; m->attn_ran[2] = 1;
     } else if (v.family == ATTN_DECODE_MQ) {
         const int nw = decode_attn_cfg(m, n_seqs, max_len) & 255;
         const int qw = cdiv(qt, v.tq);
         dim3 grid(m->nKV * qw, n_seqs, 1);     // (kv head x group of tq 16-row query tiles — one over a bf16 cache —, sequence); no key split
         a.kv_nt = kv_nt_policy(m, n_seqs, qw);
-        with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) {
+        with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) { with_bool(cap, [&](auto Ct) {
             constexpr int HD = decltype(HDt)::value;
-            constexpr bool W = decltype(Wt)::value;
+            constexpr bool W = decltype(Wt)::value, C = decltype(Ct)::value;
             if constexpr (HD == 256) return;      // (attn_variant_exists: never reached)
             else if (!kv8)
-                launch_decode_attn<attn_decode_mq_bf16_kernel<HD, 2, W>, attn_decode_mq_bf16_kernel<HD, 4, W>,
-                                   attn_decode_mq_bf16_kernel<HD, 8, W>>(m, grid, nw, 64 * HD * 2, a, max_len);
+                launch_decode_attn<attn_decode_mq_bf16_kernel<HD, 2, W, C>, attn_decode_mq_bf16_kernel<HD, 4, W, C>,
+                                   attn_decode_mq_bf16_kernel<HD, 8, W, C>>(m, grid, nw, 64 * HD * 2, a, max_len);
             else with_bool(v.tq == 2, [&](auto T2t) {
                 constexpr int TQ = decltype(T2t)::value ? 2 : 1;
-                if constexpr (attn_variant_exists(AttnVariant{ATTN_DECODE_MQ, HD, true, W, false, false, false, TQ}))
-                    launch_decode_attn<attn_decode_mq_kv8_kernel<HD, 2, TQ, W>, attn_decode_mq_kv8_kernel<HD, 4, TQ, W>,
-                                       attn_decode_mq_kv8_kernel<HD, 8, TQ, W>>(m, grid, nw, 64 * HD * 2, a, max_len, kv8[0], kv8[1]);
+                if constexpr (attn_variant_exists(AttnVariant{ATTN_DECODE_MQ, HD, true, W, false, false, false, TQ, C}))
+                    launch_decode_attn<attn_decode_mq_kv8_kernel<HD, 2, TQ, W, C>, attn_decode_mq_kv8_kernel<HD, 4, TQ, W, C>,
+                                       attn_decode_mq_kv8_kernel<HD, 8, TQ, W, C>>(m, grid, nw, 64 * HD * 2, a, max_len, kv8[0], kv8[1]);
             });
-        }); });
+        }); }); });
         m->attn_ran[0] = kv8 ? NVL_ATTN_RAN_DECODE_MQ_KV8 : NVL_ATTN_RAN_DECODE_MQ; m->attn_ran[1] = nw; m->attn_ran[2] = 1;
     } else if (v.family == ATTN_DECODE) {
         const int cfg = decode_attn_cfg(m, n_seqs), nsplit = cfg >> 8;
@@ -1683,29 +1699,29 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
             a.qkv = m->qkv; a.qkv_stride = m->n_qkv; a.cos_t = m->rope_cos; a.sin_t = m->rope_sin;
             a.q_norm_w = m->qkn_q; a.k_norm_w = m->qkn_k; a.qk_norm_eps = m->cfg.norm_eps;
         }
-        with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) {
+        with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) { with_bool(cap, [&](auto Ct) {
             constexpr int HD = decltype(HDt)::value;
-            constexpr bool W = decltype(Wt)::value;
+            constexpr bool W = decltype(Wt)::value, C = decltype(Ct)::value;
             if constexpr (HD == 256) {      // two or four waves, a 32-KB image each (decode_attn_cfg caps the ladder)
                 if (nw == 2) {
-                    NVL_LDS_ATTR((attn256_decode_kernel<2, W>), attn256_decode_lds_bytes(2));
-                    hipLaunchKernelGGL((attn256_decode_kernel<2, W>), grid, dim3(128), attn256_decode_lds_bytes(2), m->stream,
+                    NVL_LDS_ATTR((attn256_decode_kernel<2, W, C>), attn256_decode_lds_bytes(2));
+                    hipLaunchKernelGGL((attn256_decode_kernel<2, W, C>), grid, dim3(128), attn256_decode_lds_bytes(2), m->stream,
                                        a.seq_pos, a.blk_table, a.tbl_stride, a.bs_shift, a.Tmax, a.group, a);
                 } else if (nw == 4) {
-                    NVL_LDS_ATTR((attn256_decode_kernel<4, W>), attn256_decode_lds_bytes(4));
-                    hipLaunchKernelGGL((attn256_decode_kernel<4, W>), grid, dim3(256), attn256_decode_lds_bytes(4), m->stream,
+                    NVL_LDS_ATTR((attn256_decode_kernel<4, W, C>), attn256_decode_lds_bytes(4));
+                    hipLaunchKernelGGL((attn256_decode_kernel<4, W, C>), grid, dim3(256), attn256_decode_lds_bytes(4), m->stream,
                                        a.seq_pos, a.blk_table, a.tbl_stride, a.bs_shift, a.Tmax, a.group, a);
                 } else throw std::runtime_error("attention: head_dim 256 decodes on 2 or 4 waves per workgroup");
             } else if (kv8)
-                launch_decode_attn<attn_decode_kv8_kernel<HD, 2, W>, attn_decode_kv8_kernel<HD, 4, W>,
-                                   attn_decode_kv8_kernel<HD, 8, W>>(m, grid, nw, 64 * HD * 2, a, kv8[0], kv8[1]);
+                launch_decode_attn<attn_decode_kv8_kernel<HD, 2, W, C>, attn_decode_kv8_kernel<HD, 4, W, C>,
+                                   attn_decode_kv8_kernel<HD, 8, W, C>>(m, grid, nw, 64 * HD * 2, a, kv8[0], kv8[1]);
             else with_bool(v.fused, [&](auto Ft) { with_bool(v.qknorm, [&](auto Nt) { with_bool(v.stamped, [&](auto St) {
                 constexpr bool F = decltype(Ft)::value, N = decltype(Nt)::value, S = decltype(St)::value;
-                if constexpr (attn_variant_exists(AttnVariant{ATTN_DECODE, HD, false, W, F, N, S, 1}))
-                    launch_decode_attn<attn_decode_bf16_kernel<HD, 2, F, S, W, N>, attn_decode_bf16_kernel<HD, 4, F, S, W, N>,
-                                       attn_decode_bf16_kernel<HD, 8, F, S, W, N>>(m, grid, nw, 64 * HD * 2, a);
+                if constexpr (attn_variant_exists(AttnVariant{ATTN_DECODE, HD, false, W, F, N, S, 1, C}))
+                    launch_decode_attn<attn_decode_bf16_kernel<HD, 2, F, S, W, N, C>, attn_decode_bf16_kernel<HD, 4, F, S, W, N, C>,
+                                       attn_decode_bf16_kernel<HD, 8, F, S, W, N, C>>(m, grid, nw, 64 * HD * 2, a);
             }); }); });
-        }); });
+        }); }); });
         m->attn_ran[0] = v.hd == 256 ? NVL_ATTN_RAN_DECODE_HD256
             : kv8 ? NVL_ATTN_RAN_DECODE_KV8 : (a.stamps ? NVL_ATTN_RAN_DECODE_STAMPED : (fused_qkv ? NVL_ATTN_RAN_DECODE_FUSED : NVL_ATTN_RAN_DECODE));
         m->attn_ran[1] = nw; m->attn_ran[2] = nsplit;
@@ -1717,21 +1733,23 @@ static void attention_launch(nvl_model* m, const Meta& md, int n_seqs, int max_l
         dim3 grid(m->nKV, n_seqs, cdiv(qrows, wg_rows));      // (kv head fastest, query tile slowest: attn.h)
         m->attn_ran[0] = v.hd == 256 ? NVL_ATTN_RAN_PREFILL_HD256 : kv8 ? NVL_ATTN_RAN_PREFILL_KV8 : NVL_ATTN_RAN_PREFILL;
         m->attn_ran[1] = v.hd == 256 ? PF256_WAVES : 8; m->attn_ran[2] = 1;
-        with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) {
+        with_hd(v.hd, [&](auto HDt) { with_bool(win, [&](auto Wt) { with_bool(cap, [&](auto Ct) {
             constexpr int HD = decltype(HDt)::value;
-            constexpr bool W = decltype(Wt)::value;
+            constexpr bool W = decltype(Wt)::value, C = decltype(Ct)::value;
             if constexpr (HD == 256) {
-                launch_prefill<attn256_prefill_kernel<W>>(m, grid, PF256_WAVES * 64, attn256_prefill_lds_bytes(), attn256_prefill_lds_bytes(), a);
+                launch_prefill<attn256_prefill_kernel<W, C>>(m, grid, PF256_WAVES * 64, attn256_prefill_lds_bytes(), attn256_prefill_lds_bytes(), a);
             } else {
                 const int lds = kv8 ? attn_prefill_kv8_lds_bytes<HD>() : attn_prefill_lds_bytes<HD>(), limit = HD == 128 ? lds : 0;
                 if (kv8)       // K/V tiles through registers into one bf16 image pair
-                    launch_prefill<attn_prefill_kv8_kernel<HD, W>>(m, grid, 512, lds, limit, a, kv8[0], kv8[1]);
+                    launch_prefill<attn_prefill_kv8_kernel<HD, W, C>>(m, grid, 512, lds, limit, a, kv8[0], kv8[1]);
+                else if constexpr (C)      // (a kernel of its own name, causal or windowed: attn.h)
+                    launch_prefill<attn_prefill_bf16_cap_kernel<HD, W>>(m, grid, 512, lds, limit, a);
                 else if constexpr (W)      // K/V tiles by LDS-DMA; the kernel keeps the sequence's block table in LDS
                     launch_prefill<attn_prefill_bf16_win_kernel<HD>>(m, grid, 512, lds, limit, a);
                 else
                     launch_prefill<attn_prefill_bf16_kernel<HD>>(m, grid, 512, lds, limit, a);
             }
-        }); });
+        }); }); });
     }
     NVL_HIP(hipGetLastError());
 }
@@ -2359,7 +2377,8 @@ bool qkv_front(nvl_model* m, const LayerW& l, int li, const Meta& md, int M, int
         gemm(m, EPI_STORE, true, aq);
         // decode: RoPE + KV append live in the attention kernel — and the QK-norm at head_dim 128; a QK-norm layer with
         // head_dim 64 keeps the norm + RoPE launch and the plain decode kernel (the fused hd-64 kernel has no registers for it)
-        fused_dec = !m->f32 && !m->kv8 && max_len == 1 && !(qkn && m->hd != 128) && m->hd != 256;
+        // (nor under a soft cap: there is no SOFTCAP x QKNORM decode kernel — attn_variant_exists — so that layer does the same)
+        fused_dec = !m->f32 && !m->kv8 && max_len == 1 && !(qkn && (m->hd != 128 || m->softcap > 0.f)) && m->hd != 256;
         if (!fused_dec) rope_kv(m, li, md, M);     // (8-bit mode: always here — rope_kv8_kernel is its only K/V writer)
         m->front_ran[NVL_QKV_RAN_FORM] = fused_dec ? NVL_QKV_FORM_STORE_ONLY : m->kv8 ? NVL_QKV_FORM_STORE_ROPE_KV8
             : m->f32 ? NVL_QKV_FORM_F32_STORE_ROPE

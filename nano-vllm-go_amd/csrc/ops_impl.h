@@ -577,12 +577,15 @@ extern "C" int nvl_op_attention_kv8(int device, const float* q, const float* k, 
 // pools reaches a kernel: every table entry is checked, used or not.
 // window: nvl_set_sliding_window's value for the stand-in model (0 = causal): the WINDOW instantiations of the same families.
 // q_norm_w / k_norm_w [hd], eps: the fused form of a QK-norm layer (the QKNORM instantiations, head_dim 128); both NULL: none.
-extern "C" int nvl_op_attention_batch_qknorm(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
-                                             const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
-                                             int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
-                                             int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window,
-                                             const float* q_norm_w, const float* k_norm_w, float eps) {
+// softcap: nvl_set_attn_softcap's value for the stand-in model (0 = none): the SOFTCAP instantiations; not with the QK-norm weights.
+static int attention_batch_op(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                              const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                              int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                              int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window,
+                              const float* q_norm_w, const float* k_norm_w, float eps, float softcap) {
     const char* who = "nvl_op_attention_batch: ";
+    if (!(softcap >= 0.f) || !std::isfinite(softcap)) return op_fail(std::string(who) + "the soft cap must be finite and >= 0");
+    if (softcap > 0.f && (q_norm_w || k_norm_w)) return op_fail(std::string(who) + "no fused QK-norm under a soft cap (such a layer decodes unfused)");
     if ((q_norm_w != nullptr) != (k_norm_w != nullptr) || (q_norm_w && (form != NVL_ATTN_OP_FUSED || hd != 128 || !(eps >= 0.f) || !std::isfinite(eps))))
         return op_fail(std::string(who) + "QK-norm: both weights, the fused form, head_dim 128, a finite eps >= 0");
     if (window < 0 || !seq_len || !seq_pos || !k_pool || !v_pool || !block_table || !q || !out || !ran || !part_cnt || nH <= 0 || nKV <= 0 ||
@@ -628,6 +631,7 @@ extern "C" int nvl_op_attention_batch_qknorm(int device, int precision, int form
     m.n_qkv = (nH + 2 * nKV) * hd;
     m.attn_scale = scale != 0.f ? scale : 1.0f / std::sqrt((float)hd);
     m.window = window;
+    m.softcap = softcap;
     m.kv8 = kv8; m.kv_esize = kv8 ? 1 : (int)m.wsize;
     uint8_t *k8 = nullptr, *v8 = nullptr;
     if (kv8) {      // the 8-bit blocks, written by the shared quantizer from the fp32 values
@@ -700,6 +704,27 @@ extern "C" int nvl_op_attention_batch_qknorm(int device, int precision, int form
     release();
     return NVL_OK;
     OP_CATCH
+}
+
+extern "C" int nvl_op_attention_batch_qknorm(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                                             const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                                             int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                                             int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window,
+                                             const float* q_norm_w, const float* k_norm_w, float eps) {
+    return attention_batch_op(device, precision, form, nH, nKV, hd, scale, n_seqs, seq_len, seq_pos, k_pool, v_pool, n_blocks, block_size,
+                              block_table, tbl_stride, q, rope_base, max_seq, k_scale, v_scale, out, ran, part_cnt, window, q_norm_w, k_norm_w, eps, 0.f);
+}
+
+extern "C" int nvl_op_attention_batch_softcap(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,
+                                              const int32_t* seq_len, const int32_t* seq_pos, float* k_pool, float* v_pool, int n_blocks,
+                                              int block_size, const int32_t* block_table, int tbl_stride, const float* q, double rope_base,
+                                              int max_seq, float k_scale, float v_scale, float* out, int32_t* ran, int32_t* part_cnt, int window,
+                                              const float* q_norm_w, const float* k_norm_w, float eps, float softcap) {
+    if (softcap == 0.f)
+        return nvl_op_attention_batch_qknorm(device, precision, form, nH, nKV, hd, scale, n_seqs, seq_len, seq_pos, k_pool, v_pool, n_blocks, block_size,
+                                             block_table, tbl_stride, q, rope_base, max_seq, k_scale, v_scale, out, ran, part_cnt, window, q_norm_w, k_norm_w, eps);
+    return attention_batch_op(device, precision, form, nH, nKV, hd, scale, n_seqs, seq_len, seq_pos, k_pool, v_pool, n_blocks, block_size,
+                              block_table, tbl_stride, q, rope_base, max_seq, k_scale, v_scale, out, ran, part_cnt, window, q_norm_w, k_norm_w, eps, softcap);
 }
 
 extern "C" int nvl_op_attention_batch_window(int device, int precision, int form, int nH, int nKV, int hd, float scale, int n_seqs,

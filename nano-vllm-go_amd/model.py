@@ -69,7 +69,7 @@ class HipTransformerModel:
                  act_dtype: str = "auto", expert_dtype: str = "auto", mx_weight_dtype: str = "none",
                  mx_expert_dtype: str = "none", mx_head_dtype: str = "none", gq_weight_dtype: str = "none",
                  gq_group_size: int = 128, gq_expert_dtype: str = "none", mamba_conv_state: str = "per_call",
-                 mamba_rollback: str = "none", sliding_window: int | None = None):
+                 mamba_rollback: str = "none", sliding_window: int | None = None, attn_logit_softcap: float | None = None):
         """tensors=None defers finalize(): upload() each tensor, then call finalize().
         tp_size > 1 makes this the tp_rank-th tensor-parallel shard: pass the FULL tensors, the library keeps
         its slice; join the shards with tp_init (RCCL, one process per GPU) or attach_local_group (tests).
@@ -102,7 +102,9 @@ class HipTransformerModel:
         pass reads the Mamba2 states and kept rows without writing them, one launch after the accept decision advances
         them by the accepted rows (nvl_set_mamba_rollback); "none" (default) keeps refusing those calls.
         sliding_window=W (Mistral): every attention layer's query at position i sees keys i - W < j <= i
-        (nvl_set_sliding_window); 0 is causal attention over every key; None (default) takes cfg["sliding_window"], else 0."""
+        (nvl_set_sliding_window); 0 is causal attention over every key; None (default) takes cfg["sliding_window"], else 0.
+        attn_logit_softcap=cap (Gemma 2: 50, Grok-1: 30): every attention layer's scores become cap * tanh(score / cap) before
+        the mask (nvl_set_attn_softcap); 0 is none; None (default) takes cfg["attn_logit_softcap"], else 0."""
         self.cfg = dict(cfg)
         self.lib = L.lib()
         self.h = C.c_void_p()
@@ -162,6 +164,13 @@ class HipTransformerModel:
                 msg = self.lib.nvl_last_error(self.h)
                 self.close()
                 raise L.NvlError(rc, msg.decode() if msg else "")
+        self.attn_logit_softcap = float(cfg.get("attn_logit_softcap") or 0.0) if attn_logit_softcap is None else float(attn_logit_softcap)
+        if self.attn_logit_softcap:
+            rc = self.lib.nvl_set_attn_softcap(self.h, self.attn_logit_softcap)
+            if rc < 0:
+                msg = self.lib.nvl_last_error(self.h)
+                self.close()
+                raise L.NvlError(rc, msg.decode() if msg else "")
         if kv_scales is not None:
             self.set_kv_scales(*kv_scales)
         self.V = cfg["vocab_size"]
@@ -184,12 +193,13 @@ class HipTransformerModel:
         model_info.json) through nvl_load_config_json, weights through nvl_load_safetensors (mmap -> device)."""
         import os
         c = L.ModelConfigC()
-        window = C.c_int(0)
+        window, cap = C.c_int(0), C.c_float(0.0)
         for name in ("config.json", "model_info.json"):
             cp = os.path.join(path, name)
             if os.path.exists(cp):
                 L.check(L.lib().nvl_load_config_json(cp.encode(), C.byref(c)))
                 L.check(L.lib().nvl_load_config_window(cp.encode(), C.byref(window)))
+                L.check(L.lib().nvl_load_config_softcap(cp.encode(), C.byref(cap)))
                 break
         else:
             raise FileNotFoundError(f"no config.json / model_info.json in {path}")
@@ -205,6 +215,7 @@ class HipTransformerModel:
                 continue
             cfg[name] = inv[name][v] if name in inv else (bool(v) if name in ("tied_embedding", "use_moe") else v)
         cfg["sliding_window"] = window.value
+        cfg["attn_logit_softcap"] = cap.value
         m = cls(cfg, None, **kw)
         L.check(m.lib.nvl_load_safetensors(m.h, path.encode()), m.h)
         m.finalize()

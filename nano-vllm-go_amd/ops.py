@@ -395,7 +395,7 @@ ATTN_OP_FORMS_KV8 = {"mq_kv8": 4}            # NVL_ATTN_OP_MQ_KV8: "kv8" with th
 
 
 def attention_batch(q, k_pool, v_pool, block_table, seq_len, seq_pos, nH, form="plain", scale=0.0, rope_base=0.0, max_seq=0,
-                    k_scale=1.0, v_scale=1.0, precision="bf16", device=0, window=0, q_norm_w=None, k_norm_w=None, norm_eps=1e-6):   # generic_model.go:276 over block tables
+                    k_scale=1.0, v_scale=1.0, precision="bf16", device=0, window=0, q_norm_w=None, k_norm_w=None, norm_eps=1e-6, softcap=0.0):   # generic_model.go:276 over block tables
     """One layer's attention on a batch laid out as the paged front end lays it out, through the model's own dispatch
     (nvl_op_attention_batch): k_pool / v_pool [n_blocks][nKV][block_size][hd], block_table [n_seqs][tbl_stride] (passed
     verbatim), sequence i = seq_len[i] new rows behind seq_pos[i] cached keys.  q [tokens][nH][hd]; form "fused": the fp32
@@ -403,7 +403,9 @@ def attention_batch(q, k_pool, v_pool, block_table, seq_len, seq_pos, nH, form="
     "mq" / "mq_kv8": a verify pass over a bf16 / an 8-bit cache (2..8 rows per sequence run the multi-position kernels).
     max_seq 0 = what the table covers.  window = W > 0: sliding-window attention, row at position i sees keys i - W < j <= i
     (nvl_op_attention_batch_window; 0 = causal).  q_norm_w / k_norm_w [hd] with norm_eps ("fused", hd 128): the per-head QK
-    RMSNorm of a Qwen3 layer ahead of the rotation (nvl_op_attention_batch_qknorm).  -> dict(out [tokens][nH][hd], ran (an ATTN_RAN name), nw, nsplit, part_cnt [32],
+    RMSNorm of a Qwen3 layer ahead of the rotation (nvl_op_attention_batch_qknorm).  softcap = cap > 0: the scores become
+    cap * tanh(score / cap) before the mask (nvl_op_attention_batch_softcap, the entry point every call takes; 0 = none).
+    -> dict(out [tokens][nH][hd], ran (an ATTN_RAN name), nw, nsplit, part_cnt [32],
     and for "fused" k_pool / v_pool after the launch)."""
     k_pool, v_pool = _f(k_pool).copy(), _f(v_pool).copy()
     q = _f(q)
@@ -420,11 +422,11 @@ def attention_batch(q, k_pool, v_pool, block_table, seq_len, seq_pos, nH, form="
     qn, kn = (None if a is None else _f(a) for a in (q_norm_w, k_norm_w))
     if any(a is not None and a.shape != (hd,) for a in (qn, kn)):
         raise ValueError("attention_batch: q_norm_w / k_norm_w are [hd]")
-    L.check(L.lib().nvl_op_attention_batch_qknorm(device, L.PRECISION[precision], {**ATTN_OP_FORMS, **ATTN_OP_FORMS_KV8}[form], nH, nKV, hd, scale,
+    L.check(L.lib().nvl_op_attention_batch_softcap(device, L.PRECISION[precision], {**ATTN_OP_FORMS, **ATTN_OP_FORMS_KV8}[form], nH, nKV, hd, scale,
                                                   n_seqs, _p(sl), _p(sp), _p(k_pool), _p(v_pool), n_blocks, bs, _p(tbl), stride, _p(q),
                                                   float(rope_base), int(max_seq) if max_seq else stride * bs, k_scale, v_scale, _p(out),
                                                   _p(ran), _p(cnt), int(window), None if qn is None else _p(qn),
-                                                  None if kn is None else _p(kn), float(norm_eps)))
+                                                  None if kn is None else _p(kn), float(norm_eps), float(softcap)))
     res = dict(out=out, ran=ATTN_RAN[int(ran[0])], nw=int(ran[1]), nsplit=int(ran[2]), part_cnt=cnt)
     if form == "fused":
         res.update(k_pool=k_pool, v_pool=v_pool)

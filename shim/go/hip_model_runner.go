@@ -47,6 +47,7 @@ type Options struct {
 	MXHeadDType    int  // C.NVL_MXH_NONE (0) or C.NVL_MXH_FP4_E2M1 (1): MXFP4 LM head / tied embedding (needs MXWeightDType 1)
 	ExpertDType    int  // C.NVL_EXPERT_AUTO (0) or C.NVL_EXPERT_FP8_E4M3 (1): 8-bit MoE expert weights (needs WeightDType 1)
 	SlidingWindow  int  // Mistral (ArchMistral): the query at position i sees keys i-W < j <= i; 0 = every key.  NewHipModelRunnerFromDir takes the checkpoint's own when this is 0
+	AttnSoftcap    float32 // Gemma 2 (50) / Grok-1 (30): attention scores become cap * tanh(score / cap) before the mask; 0 = none.  NewHipModelRunnerFromDir takes the checkpoint's own ("attn_logit_softcapping") when this is 0
 }
 
 // HipModelRunner implements nanovllm.ModelRunner on one MI355X.
@@ -362,6 +363,13 @@ func create(cfg *C.nvl_model_config, o Options) (*HipModelRunner, error) {
 	if o.ExpertDType != 0 { // right after the weight dtype, before the experts are uploaded (nvl_set_expert_dtype)
 		if rc := C.nvl_set_expert_dtype(r.h, C.int(o.ExpertDType)); rc != 0 {
 			err := fmt.Errorf("nvl_set_expert_dtype: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
+			C.nvl_destroy(r.h)
+			return nil, err
+		}
+	}
+	if o.AttnSoftcap != 0 { // before nvl_finalize (nvl_set_attn_softcap)
+		if rc := C.nvl_set_attn_softcap(r.h, C.float(o.AttnSoftcap)); rc != 0 {
+			err := fmt.Errorf("nvl_set_attn_softcap: %d: %s", int(rc), C.GoString(C.nvl_last_error(r.h)))
 			C.nvl_destroy(r.h)
 			return nil, err
 		}
